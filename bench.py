@@ -2,7 +2,7 @@
 """bench.py -- forward-model + logL evaluations per second on N MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|c2|c3|c4|c5|c5_full|c2g|c3g] [--batch B]
-                    [--search reference|fast|fast_rayleigh] [--full] [--out bench_full.json]
+                    [--search reference|fast|fast_rayleigh] [--full] [--out bench_full.json] [--dump-outputs DIR]
 
 Rank 0 prints ONE COMPACT JSON line (a few KB; tests/test_host_logic.py holds it under 8 KB): the c2 headline -- the
 configuration the metric is quoted on -- with `roofline`, `cpu_baseline`, a five-key `parity_check` and a `summary` of
@@ -67,6 +67,8 @@ CLOCK_WARMUP_MS = float(os.environ.get("BH_BENCH_CLOCK_WARMUP_MS", "150"))   # u
 RF_CUT_WA = 12.5132         # csrc/rf_kernel.hip: w/a beyond which the Gauss low-pass is below 1e-17
 PRIOR_LAYERS = 21           # c2p: array capacity of models drawn from the chains' prior (layers = (1, 20) above the half-space)
 RF_FLOP_PER_LAYER_STEP = 600.0   # flop-equivalents of one layer of the reflectivity recursion for one frequency
+DUMP_BLOCK_BYTES = 8 << 20  # --dump-outputs: per workload block; a run dumps at most 8 blocks (--workload all), 64 MB in all
+CHAIN_STATE = ("n", "vs", "z", "vpvs", "noise", "like", "misfits", "propdist", "naccepted", "beta")   # what DeviceChains leaves a caller
 
 
 def build_workload(name, B, L, seed):
@@ -102,6 +104,21 @@ def build_workload(name, B, L, seed):
         else:
             noise[:, 2 * t + 1] = rs.uniform(0.005, 0.05, B)
     return spec, batches, noise, true_model(10 if name == "c2p" else L), np.random.RandomState(SEED + 2)
+
+
+def dump_outputs(outdir, prefix, arrays):
+    """--dump-outputs: `arrays` (name -> array, models or chains on axis 0) as <outdir>/<prefix>_<name>.npy in float64.  Beyond
+    DUMP_BLOCK_BYTES a fixed seeded sample of the rows is written, and the sampled row numbers as <prefix>_rows.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(1, n)
+    if n * row_bytes > DUMP_BLOCK_BYTES:
+        rows = np.sort(np.random.RandomState(0).choice(n, DUMP_BLOCK_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, "%s_%s.npy" % (prefix, name)), a)
 
 
 def observed_data(eng, spec, truth, nrs):
@@ -271,7 +288,7 @@ def cpu_baseline(spec, batch, noise, workload):
                       % (n, workload, best, sorted(probe_rates), ncpu, 1.0 / per_model)}
 
 
-def run_chains(args, eng, rank, world, dist, dev, workload, steps, warmup):
+def run_chains(args, eng, rank, world, dist, dev, workload, steps, warmup, dump=True):
     """c4 / c5: device-resident chains (bayhunter_amd.device_chains) on the c3 targets.  Returns the result block on
     rank 0 (None elsewhere).  `steps` / `warmup` are ITERATIONS of every chain (main phase timed, burn-in untimed); one
     evaluation launch advances every chain by `spec_depth` iterations (speculative windows, chain_kernel.hip)."""
@@ -337,6 +354,8 @@ def run_chains(args, eng, rank, world, dist, dev, workload, steps, warmup):
     if rank != 0:
         return None
     st = dc.state_host()
+    if dump and args.dump_outputs:   # the chains' state after the last timed iteration, chain-major
+        dump_outputs(args.dump_outputs, workload, {k: (v.T if v.ndim == 2 else v) for k, v in st.items() if k in CHAIN_STATE and v is not None})
     launches = dc.launches - launches0
     return {"metric": "chain-iterations/s (device-resident transdimensional chains)",
             "value": world * C * timed_iters / elapsed, "unit": "chain-iterations/s", "n_gpus": world, "steps": steps,
@@ -524,7 +543,7 @@ def rf_roofline(eng, spec, d_batch, B, L, dev, reps=20):
             "rf_per_s": B / (ms * 1e-3)}
 
 
-def run_eval(args, eng, rank, world, dist, dev, workload, dryrun, with_cpu=True, rf_roof=True):
+def run_eval(args, eng, rank, world, dist, dev, workload, dryrun, with_cpu=True, rf_roof=True, dump=True):
     """One evaluate workload (c2 / c3 / c2g / c3g): untimed clock warm-up, `--warmup` steps, then EXACTLY `--steps`
     steps between barrier + synchronize on both sides, max over ranks.  Returns the result block on rank 0."""
     import torch
@@ -604,6 +623,8 @@ def run_eval(args, eng, rank, world, dist, dev, workload, dryrun, with_cpu=True,
         elapsed = float(tall.max().item())
     if rank != 0:
         return None
+    if dump and args.dump_outputs:   # what the last timed step returned (the parity check below evaluates that batch again)
+        dump_outputs(args.dump_outputs, workload, {"logL": d_logL.cpu().numpy(), "misfits": d_misf.cpu().numpy(), "err": d_err.cpu().numpy()})
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
     # dominant kernel: the dispersion kernel (all dispersion targets of a step in one launch);
@@ -850,7 +871,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rf-roofline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the last step (after the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of every workload block returned as DIR/<workload>_<name>.npy (float64; "
+                         "seeded inputs, identical from run to run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     chain_search = args.search or "fast"   # (DeviceChains' own default)
     args.search = args.search or "fast"
 
@@ -948,13 +974,13 @@ def main():
                 eng.set_swd_search(alt_name)
                 for w in ("c2", "c3"):
                     g0 = np.array(eng.guard_totals())
-                    alt[w] = run_eval(args, eng, rank, world, dist, dev, w, dryrun, with_cpu=False, rf_roof=False)
+                    alt[w] = run_eval(args, eng, rank, world, dist, dev, w, dryrun, with_cpu=False, rf_roof=False, dump=False)
                     if alt[w] is not None and alt_name != "reference":
                         alt[w]["models_rerun_by_the_guard"] = int((np.array(eng.guard_totals()) - g0).sum())
                 eng.set_swd_search(alt_name)
                 for w in chain_workloads:
                     try:
-                        alt[w] = run_chains(args, eng, rank, world, dist, dev, w, csteps, max(100, csteps // 2))
+                        alt[w] = run_chains(args, eng, rank, world, dist, dev, w, csteps, max(100, csteps // 2), dump=False)
                     except Exception as ex:
                         alt[w] = {"error": repr(ex)}
             except Exception as ex:

@@ -11,6 +11,8 @@ rfmini_modrf) unmodified from /root/reference/src, with
 Nothing of the reference is copied: the outputs are data (inputs + expected outputs).
 
     python tests/golden/gen_golden.py          # rewrites tests/golden/*.npz and st3/*.dat
+    python tests/golden/gen_golden.py merge    # rewrites tests/golden/merge_golden.npz only
+    python tests/golden/gen_golden.py compiled # rewrites tests/golden/compiled_golden.npz only
 """
 import os
 import shutil
@@ -398,8 +400,44 @@ def merge_fixture():
     print("merge_golden.npz: outliers", out["outliers"], "merged rows", out["c_likes"].size)
 
 
+def compiled_fixture():
+    """tests/golden/compiled_golden.npz: the compiled reference (oracle/_ref: surfdisp96.f, rfmini) on the random inputs
+    of the oracle's bit-equality tests, which the tests generate themselves (compiled_reference_cases of
+    tests/test_oracle_swd.py and tests/test_oracle_rf.py, group_velocity_sets of tests/test_oracle_swd.py):
+    swd_err / swd_vel [model, target (rdispph, rdispgr, ldispph, ldispgr), period], dltar [case, (dltar1, dltar4)],
+    rf [case, sample], group_err / group_vel [every 5th prior-like model, period] (Rayleigh group velocities)."""
+    from oracle import refshim
+    assert refshim.available(), "run `make -C oracle ref` first"
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_swd as S
+    import test_oracle_rf as R
+    models, secular = S.compiled_reference_cases()
+    out = {"swd_err": np.zeros((len(models), len(S.REFS)), np.int32),
+           "swd_vel": np.zeros((len(models), len(S.REFS), S.COMPILED_PERIODS.size))}
+    for i, (h, vp, vs, rho) in enumerate(models):
+        for j, (iwave, igr) in enumerate(S.REFS.values()):
+            out["swd_err"][i, j] = refshim.surfdisp96(h, vp, vs, rho, h.size, 0, iwave, 1, igr, S.COMPILED_PERIODS.size,
+                                                      S.COMPILED_PERIODS, out["swd_vel"][i, j])
+    out["dltar"] = np.array([[refshim.dltar(om / c, om, ifunc, h, vp, vs, rho) for ifunc in (1, 2)]
+                             for om, c, h, vp, vs, rho in secular])
+    out["rf"] = np.array([refshim.synrf(*args)[2] for args in R.compiled_reference_cases()])
+    nlay, h, vp, vs, rho, per = S.group_velocity_sets()[1]
+    rows = np.arange(0, nlay.size, 5)
+    out["group_err"] = np.zeros(rows.size, np.int32)
+    out["group_vel"] = np.zeros((rows.size, per.size))
+    for k, b in enumerate(rows):
+        n = int(nlay[b])
+        out["group_err"][k] = refshim.surfdisp96(h[b, :n], vp[b, :n], vs[b, :n], rho[b, :n], n, 0, 2, 1, 1, per.size, per,
+                                                 out["group_vel"][k])
+    np.savez_compressed(os.path.join(HERE, "compiled_golden.npz"), **out)
+    print("compiled_golden.npz:", {k: v.shape for k, v in out.items()})
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "merge":
         merge_fixture()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "compiled":
+        compiled_fixture()
         sys.exit(0)
     main()

@@ -154,6 +154,44 @@ def test_the_bench_path_against_the_oracle(workload, search):
     eng.close()
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last of its `--steps` timed steps returned: a fresh engine in this process,
+    given the same seeded workload, computes the same bits for that step's batch (batch (W + K - 1) mod NPOOL)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    import bench
+    K, W, Bn, L = 3, 2, 512, 10
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", str(K),
+                        "--warmup", str(W), "--batch", str(Bn), "--no-cpu-baseline", "--no-parity", "--out", str(tmp_path / "full.json"),
+                        "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600, cwd=repo)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == K
+    assert sorted(os.listdir(tmp_path / "dump")) == ["c2_err.npy", "c2_logL.npy", "c2_misfits.npy"]
+    eng = E.Engine(0)
+    eng.set_swd_search("fast")                 # bench.py's default search
+    spec, batches, noise, truth, nrs = bench.build_workload("c2", Bn, L, seed=20260927)
+    bench.observed_data(eng, spec, truth, nrs)
+    eng.set_targets(spec)
+    dev = torch.device("cuda", 0)
+    d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in batches[(W + K - 1) % bench.NPOOL]]
+    d_noise = torch.from_numpy(noise).to(dev)
+    d_logL = torch.zeros(Bn, dtype=torch.float64, device=dev)
+    d_misf = torch.zeros((Bn, len(spec) + 1), dtype=torch.float64, device=dev)
+    d_err = torch.zeros(Bn, dtype=torch.int32, device=dev)
+    eng.evaluate_batch_dev(Bn, L, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
+                           Bn, 1, d_noise.data_ptr(), d_logL.data_ptr(), d_misf.data_ptr(), d_err.data_ptr(),
+                           stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    for name, a in (("logL", d_logL), ("misfits", d_misf), ("err", d_err)):
+        dumped = np.load(tmp_path / "dump" / ("c2_%s.npy" % name))
+        assert dumped.dtype == np.float64 and np.array_equal(dumped, a.cpu().numpy().astype(np.float64)), name
+    eng.close()
+
+
 def test_large_call_of_the_lane_kernel_two_wavefronts_per_workgroup(engine, oracle):
     """More than 2048 wavefronts in one call: the lane-per-evaluation kernel runs with two wavefronts per workgroup
     (shared libm tables) and time-sliced priorities, the Neville orders from five on in its global work array.

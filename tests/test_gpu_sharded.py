@@ -113,7 +113,7 @@ def test_rccl_code_path_world_size_1():
         dist.destroy_process_group()
 
 
-def test_bench_line_of_a_two_rank_tempered_job_parses():
+def test_bench_line_of_a_two_rank_tempered_job_parses(tmp_path):
     """`bench.py --gpus 2 --workload c5` as the driver launches it (torch.distributed.run, two ranks), in its
     dry-run form (BH_BENCH_DRYRUN=1: both ranks on GPU 0 over gloo -- the boxes of the build have one GPU): rank 0 prints ONE
     parseable line under the size limit, the ladder laid across the ranks exchanges temperatures."""
@@ -122,8 +122,7 @@ def test_bench_line_of_a_two_rank_tempered_job_parses():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BH_BENCH_DRYRUN="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(repo, "bench.py"), "--gpus", "2", "--workload", "c5", "--steps", "300",
-           "--warmup", "100", "--out", os.path.join(repo, "gpurun_out", "bench_full_dryrun.json")]
-    os.makedirs(os.path.join(repo, "gpurun_out"), exist_ok=True)
+           "--warmup", "100", "--out", str(tmp_path / "bench_full_dryrun.json")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=repo)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

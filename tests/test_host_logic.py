@@ -208,3 +208,30 @@ def test_bench_line_stays_compact_and_parseable():
     line8 = json.loads(bench.compact_line(full, None))
     assert line8["collective_check"]["rccl_ranks"] == 8 and "all" not in line8["rank_ms_per_step"]
     assert len(bench.compact_line(full, None)) < 4096
+
+
+def test_bench_dump_outputs_writes_float64_and_samples_rows_beyond_its_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <prefix>_<name>.npy in float64; a block larger than DUMP_BLOCK_BYTES is cut to a
+    fixed seeded sample of rows (the same in every run) whose row numbers are written beside it."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    logL, misf, err = np.linspace(-5, 5, 1000), np.arange(3000.0).reshape(1000, 3), (np.arange(1000) % 7 == 0).astype(np.int32)
+    bench.dump_outputs(str(tmp_path / "small"), "c2", {"logL": logL, "misfits": misf, "err": err})
+    assert sorted(os.listdir(tmp_path / "small")) == ["c2_err.npy", "c2_logL.npy", "c2_misfits.npy"]
+    for name, a in (("logL", logL), ("misfits", misf), ("err", err)):
+        d = np.load(tmp_path / "small" / ("c2_%s.npy" % name))
+        assert d.dtype == np.float64 and np.array_equal(d, a), name
+    monkeypatch.setattr(bench, "DUMP_BLOCK_BYTES", 8192)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), "c2", {"logL": logL, "misfits": misf, "err": err})
+    assert sorted(os.listdir(tmp_path / "a")) == ["c2_err.npy", "c2_logL.npy", "c2_misfits.npy", "c2_rows.npy"]
+    rows = np.load(tmp_path / "a" / "c2_rows.npy")
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and 0 < rows.size < 1000
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "c2_logL.npy"), logL[r]) and np.array_equal(np.load(tmp_path / "a" / "c2_misfits.npy"), misf[r])
+    assert np.array_equal(np.load(tmp_path / "a" / "c2_err.npy"), err[r])
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in os.listdir(tmp_path / "a")) <= 8192
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f

@@ -42,15 +42,27 @@ def test_oracle_matches_tutorial_files(oracle, ref, wtype):
     assert np.max(np.abs(rf - y)) <= 1e-4
 
 
-def test_oracle_matches_compiled_reference_random(oracle):
-    from oracle import refshim
-    if not refshim.available():
-        pytest.skip("oracle/_ref not built (needs the build container)")
+def compiled_reference_cases():
+    """The random synrf arguments of the bit-equality test against the compiled reference (its outputs on them are stored
+    in tests/golden/compiled_golden.npz by `tests/golden/gen_golden.py compiled`)."""
     rs = np.random.RandomState(6)
+    cases = []
     for it in range(12):
         L = rs.randint(2, 22)
         vs = np.sort(rs.uniform(2.0, 4.8, L)); h = rs.uniform(0.5, 8, L); h[-1] = 0
         vp = vs * rs.uniform(1.5, 2.0); rho = 0.32 * vp + 0.77
         z = np.concatenate(([0], np.cumsum(h)[:-1]))
-        args = (z, vp, vs, rho, np.ones(L) * 500., np.ones(L) * 225., rs.uniform(4, 8), rs.uniform(1, 3), 512, 5.0, 5.0, vs[0], 0.25, "P" if it % 2 else "SV")
-        assert np.array_equal(oracle.synrf(*args)[2], refshim.synrf(*args)[2])
+        cases.append((z, vp, vs, rho, np.ones(L) * 500., np.ones(L) * 225., rs.uniform(4, 8), rs.uniform(1, 3), 512, 5.0, 5.0, vs[0], 0.25, "P" if it % 2 else "SV"))
+    return cases
+
+
+def test_oracle_matches_compiled_reference_random(oracle):
+    """Bit-equality with the compiled reference: against its stored outputs, and where oracle/_ref is built, against the
+    reference itself as well."""
+    from oracle import refshim
+    g = golden("compiled_golden.npz")
+    for i, args in enumerate(compiled_reference_cases()):
+        rf = oracle.synrf(*args)[2]
+        assert np.array_equal(rf, g["rf"][i]), i
+        if refshim.available():
+            assert np.array_equal(rf, refshim.synrf(*args)[2])

@@ -74,13 +74,15 @@ def test_oracle_matches_tutorial_files(oracle, ref):
     assert np.max(np.abs(cg - y)) <= 5.1e-5
 
 
-def test_oracle_matches_compiled_reference_random(oracle):
-    """Where oracle/_ref exists (it travels with the repo): bit-equality on fresh random models."""
-    from oracle import refshim
-    if not refshim.available():
-        pytest.skip("oracle/_ref not built (needs the build container)")
+COMPILED_PERIODS = np.linspace(2, 60, 30)
+
+
+def compiled_reference_cases():
+    """The random inputs of the bit-equality test against the compiled reference (its outputs on them are stored in
+    tests/golden/compiled_golden.npz by `tests/golden/gen_golden.py compiled`): 60 models, then 200 arguments of the
+    secular functions (om, c, h, vp, vs, rho)."""
     rs = np.random.RandomState(5)
-    per = np.linspace(2, 60, 30)
+    models, secular = [], []
     for it in range(60):
         L = rs.randint(2, 22)
         vs = np.sort(rs.uniform(2.0, 4.8, L))
@@ -88,17 +90,38 @@ def test_oracle_matches_compiled_reference_random(oracle):
             vs[rs.randint(1, L - 1)] *= 0.85
         h = rs.uniform(0.5, 8, L); h[-1] = 0
         vp = vs * rs.uniform(1.5, 2.0); rho = 0.32 * vp + 0.77
-        for iwave, igr in REFS.values():
-            a = np.zeros(30); b = np.zeros(30)
-            ea = oracle.surfdisp96(h, vp, vs, rho, L, 0, iwave, 1, igr, 30, per, a)
-            eb = refshim.surfdisp96(h, vp, vs, rho, L, 0, iwave, 1, igr, 30, per, b)
-            assert ea == eb and np.array_equal(a, b)
+        models.append((h, vp, vs, rho))
     for _ in range(200):
         L = rs.randint(2, 12)
         vs = np.sort(rs.uniform(2.0, 4.8, L)); h = rs.uniform(0.5, 8, L); vp = vs * 1.75; rho = 0.32 * vp + 0.77
         om = 2 * np.pi / rs.uniform(1, 60); c = rs.uniform(1.7, 5.0)
-        for ifunc in (1, 2):
-            assert oracle.dltar(om / c, om, ifunc, h, vp, vs, rho) == refshim.dltar(om / c, om, ifunc, h, vp, vs, rho)
+        secular.append((om, c, h, vp, vs, rho))
+    return models, secular
+
+
+def test_oracle_matches_compiled_reference_random(oracle):
+    """Bit-equality with the compiled reference on random models: against its stored outputs, and where oracle/_ref is
+    built, against the reference itself as well."""
+    from oracle import refshim
+    g = golden("compiled_golden.npz")
+    live = refshim.available()
+    models, secular = compiled_reference_cases()
+    per = COMPILED_PERIODS
+    for i, (h, vp, vs, rho) in enumerate(models):
+        for j, (iwave, igr) in enumerate(REFS.values()):
+            a = np.zeros(30)
+            ea = oracle.surfdisp96(h, vp, vs, rho, h.size, 0, iwave, 1, igr, 30, per, a)
+            assert ea == g["swd_err"][i, j] and np.array_equal(a, g["swd_vel"][i, j]), (i, j)
+            if live:
+                b = np.zeros(30)
+                eb = refshim.surfdisp96(h, vp, vs, rho, h.size, 0, iwave, 1, igr, 30, per, b)
+                assert ea == eb and np.array_equal(a, b)
+    for i, (om, c, h, vp, vs, rho) in enumerate(secular):
+        for j, ifunc in enumerate((1, 2)):
+            d = oracle.dltar(om / c, om, ifunc, h, vp, vs, rho)
+            assert d == g["dltar"][i, j], (i, j)
+            if live:
+                assert d == refshim.dltar(om / c, om, ifunc, h, vp, vs, rho)
 
 
 def test_short_refinement_restatement_stays_within_tolerance_of_the_reference(oracle):
@@ -232,21 +255,28 @@ def test_guarded_short_refinement_returns_the_reference_failure_flags(oracle):
     assert nraw > 10   # the unguarded sequence does differ on these sets
 
 
-def test_group_velocity_roots_in_the_device_order_are_the_reference_bits(oracle):
-    """The device runs a fundamental-mode group velocity as the chain of its first roots (t/(1+h)) and then the second roots (t/(1-h))
-    as independent searches (bh_engine.hip launch_swd_jobs, DESIGN.md 3.5): the second root of a period starts from the first root of
-    the same period and from nothing else (surfdisp96.f:282-287).  The oracle in that order (last period first) against the
-    reference's order: the same bits and flags -- golden models (with the models surf96 fails on), sorted velocities with a
-    low-velocity zone, models drawn from a sampler's prior, flat and flattened, with and without the counted Love scan; and
-    against the compiled reference where it is built."""
+def group_velocity_sets():
+    """(nlay, h, vp, vs, rho [model-major], periods) of the test below: golden models, sorted velocities with a low-velocity
+    zone, models drawn from a sampler's prior."""
     from bayhunter_amd.synth import synth_models, prior_models
-    from oracle import refshim
     g = golden("swd_golden.npz")
     sets = [(g["nlay"], g["h"], g["vp"], g["vs"], g["rho"], g["x_p30"])]
     rs = np.random.RandomState(314)
     for gen in (lambda: synth_models(rs, 150, 12, lvz_frac=0.4, ragged=True), lambda: prior_models(rs, 150, 21)):
         nlay, h, vp, vs, rho = gen()
         sets.append((nlay, h.T, vp.T, vs.T, rho.T, np.sort(rs.uniform(1.0, 70.0, 24))))
+    return sets
+
+
+def test_group_velocity_roots_in_the_device_order_are_the_reference_bits(oracle):
+    """The device runs a fundamental-mode group velocity as the chain of its first roots (t/(1+h)) and then the second roots (t/(1-h))
+    as independent searches (bh_engine.hip launch_swd_jobs, DESIGN.md 3.5): the second root of a period starts from the first root of
+    the same period and from nothing else (surfdisp96.f:282-287).  The oracle in that order (last period first) against the
+    reference's order: the same bits and flags -- golden models (with the models surf96 fails on), sorted velocities with a
+    low-velocity zone, models drawn from a sampler's prior, flat and flattened, with and without the counted Love scan; and
+    against the compiled reference: its stored outputs, and the reference itself where it is built."""
+    from oracle import refshim
+    sets = group_velocity_sets()
     nfail = 0
     for nlay, h, vp, vs, rho, per in sets:
         for iwave in (1, 2):
@@ -259,11 +289,14 @@ def test_group_velocity_roots_in_the_device_order_are_the_reference_bits(oracle)
                     assert np.array_equal(se, oe) and np.array_equal(sv, ov), (iwave, flsph, counted)
                 nfail += int(oe.sum())
     assert nfail > 0   # (models whose chain of first roots ends early are among them)
+    nlay, h, vp, vs, rho, per = sets[1]
+    with oracle.swd_group_split():
+        sv, se, _ = oracle.swd_batch(nlay, h, vp, vs, rho, per, 2, 1)
+    rows = np.arange(0, nlay.size, 5)
+    c = golden("compiled_golden.npz")
+    assert np.array_equal(se[rows], c["group_err"]) and np.array_equal(sv[rows], c["group_vel"])
     if refshim.available():
-        nlay, h, vp, vs, rho, per = sets[1]
-        with oracle.swd_group_split():
-            sv, se, _ = oracle.swd_batch(nlay, h, vp, vs, rho, per, 2, 1)
-        for b in range(0, nlay.size, 5):
+        for b in rows:
             n = int(nlay[b]); r = np.zeros(per.size)
             er = refshim.surfdisp96(h[b, :n], vp[b, :n], vs[b, :n], rho[b, :n], n, 0, 2, 1, 1, per.size, per, r)
             assert er == se[b] and np.array_equal(r, sv[b])
