@@ -228,6 +228,8 @@ constexpr size_t BH_RF_MAX_LDS = 160 * 1024;
 constexpr int BH_RF_MAX_NSAMP = 1 << 18;
 size_t bh_rf_lds_bytes(int nsamp);
 int bh_launch_rf(const RfKernelArgs &a, hipStream_t stream); // 0, or -1 when the trace does not fit a workgroup's LDS
+// bh_probe_math ops 11-16: the synthesis kernel's own elementary functions (include/bh_engine_debug.h); -1 for another op
+int bh_launch_rf_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 
 struct LikeTargetDev {
     int law, n, off; // off: column offset of this target's samples inside a ymod row

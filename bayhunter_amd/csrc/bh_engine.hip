@@ -1554,7 +1554,7 @@ int bh_loglike_batch(bh_engine *e, int memspace, void *stream, int B, const doub
 
 int bh_probe_math(bh_engine *e, int op, int n, const double *in, double *out)
 {
-    if (!e || n < 0 || !in || !out) return BH_EINVAL;
+    if (!e || n < 0 || !in || !out || op < 0 || op > 16 || (op == 16 && (n & 1))) return BH_EINVAL;
     if (n == 0) return BH_OK;
     int rc;
     HIPCHK(e, hipSetDevice(e->device));
@@ -1562,7 +1562,8 @@ int bh_probe_math(bh_engine *e, int op, int n, const double *in, double *out)
     if ((rc = ensure(e, e->probe_in, nin * sizeof(double)))) return rc;
     if ((rc = ensure(e, e->probe_out, (size_t)n * sizeof(double)))) return rc;
     HIPCHK(e, hipMemcpyAsync(e->probe_in.p, in, nin * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    bh_launch_probe(op, n, (const double *)e->probe_in.p, (double *)e->probe_out.p, e->stream);
+    if (op >= 11) bh_launch_rf_probe(op, n, (const double *)e->probe_in.p, (double *)e->probe_out.p, e->stream);
+    else bh_launch_probe(op, n, (const double *)e->probe_in.p, (double *)e->probe_out.p, e->stream);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(out, e->probe_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));

@@ -817,7 +817,38 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     rf_synth_body<true>(A, logm, jcut);
 }
 
+// Probe of the elementary functions above (bh_probe_math ops 11-16): the same inlined text, built with this file's flags,
+// so that the tests measure the very functions the synthesis kernel calls.  csqrt_f reads and writes pairs (re, im).
+__global__ __launch_bounds__(256) void rf_probe_kernel(int op, int n, const double *__restrict__ in, double *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (op == 16) {
+        if (2 * i + 1 >= n) return;
+        const cd r = csqrt_f(cd{in[2 * i], in[2 * i + 1]});
+        out[2 * i] = r.re;
+        out[2 * i + 1] = r.im;
+        return;
+    }
+    if (i >= n) return;
+    const double x = in[i];
+    double s = 0.0, c = 0.0;
+    switch (op) {
+    case 11: out[i] = rcp_nr(x); break;
+    case 12: out[i] = rsq_nr(x); break;
+    case 13: sincos_cw(x, &s, &c); out[i] = s; break;
+    case 14: sincos_cw(x, &s, &c); out[i] = c; break;
+    default: out[i] = exp_cw(x); break;
+    }
+}
+
 } // namespace
+
+int bh_launch_rf_probe(int op, int n, const double *in, double *out, hipStream_t stream)
+{
+    if (op < 11 || op > 16 || (op == 16 && (n & 1))) return -1;
+    hipLaunchKernelGGL(rf_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, op, n, in, out);
+    return 0;
+}
 
 size_t bh_rf_coef_doubles(int Lmax) { return rec_doubles(Lmax); }
 

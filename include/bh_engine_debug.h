@@ -68,7 +68,11 @@ int bh_engine_get_tuning(bh_engine *e, const char *name, int *value);
  * op 0 sqrt, 1 sin, 2 cos, 3 exp, 4 log, 5 1/x; op 6 / 7: in holds n pairs (a, b), out[i] = a/b
  * through the shared-reciprocal sequence of the kernels (6) or the plain operator (7); op 8 / 9 / 10:
  * sin / cos / exp through the kernels' glibc-exact restatement (csrc/bh_libm.h).  Used by the tests to document how far the
- * device math library is from the host's libm (SURVEY.md 7 "FMA contraction & device libm"). */
+ * device math library is from the host's libm (SURVEY.md 7 "FMA contraction & device libm").
+ * Ops 11-16 run the receiver-function synthesis kernel's own fast functions (csrc/rf_kernel.hip, the same inlined text and
+ * compile flags): 11 rcp_nr (1/x: hardware seed + one Newton step), 12 rsq_nr (1/sqrt(x), x > 0), 13 / 14 sin / cos of
+ * sincos_cw (Cody-Waite reduction, meant for |x| < 2^20), 15 exp_cw (clamped to [-800, 800]; NaN passes through),
+ * 16 csqrt_f (principal complex square root): in and out hold n / 2 pairs (re, im), n even.  BH_EINVAL for any other op. */
 int bh_probe_math(bh_engine *e, int op, int n, const double *in, double *out);
 
 /* Instrumentation (off by default; bench.py and the tests turn it on).
