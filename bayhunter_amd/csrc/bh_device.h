@@ -242,6 +242,15 @@ struct LikeTargetDev {
 int bh_gauss_nsplit(int B, int n);
 void bh_launch_gauss_quad(int B, int n, int ldy, const double *ymod, const double *yobs,
                           const double *rinv, int nsplit, double *partial, hipStream_t stream);
+// Site tables of bh_evaluate_sites (include/bh_engine_sites.h): model b compares with the observed data of site site[b].
+// Gauss contraction: the residual row of model b is ymod row b - yobs + site[b] * ldo (yobs already at the target's column
+// offset); a site out of range reads site 0's row (its model is reported failed by the likelihood kernel).
+struct GaussSiteArgs {
+    const int32_t *site; // device [B]
+    int nsites, ldo;
+};
+void bh_launch_gauss_quad_sites(int B, int n, int ldy, const double *ymod, const double *yobs, const GaussSiteArgs &sites,
+                                const double *rinv, int nsplit, double *partial, hipStream_t stream);
 struct LikeKernelArgs {
     int B, nt, ldy;
     const double *ymod; // [B][ldy]
@@ -253,6 +262,16 @@ struct LikeKernelArgs {
     int32_t *err;    // [B]
 };
 void bh_launch_like(const LikeKernelArgs &a, hipStream_t stream);
+// Likelihood kernel: LikeTargetDev::yobs / yerr_scaled / logdet_extra of target t become, for a model of site s,
+// yobs + s * ldy + off, yerr_scaled + s * ldy + off (law 1) and logdet_extra[s * nt + t] (law 1).
+struct LikeSiteArgs {
+    const int32_t *site;         // device [B]: site of every model
+    int nsites;
+    const double *yobs;          // device [nsites][ldy]: observed data, targets in ymod's column order
+    const double *yerr_scaled;   // device [nsites][ldy]: yerr / min(yerr) in the columns of law-1 targets (else unread)
+    const double *logdet_extra;  // device [nsites][nt]: ln prod(yerr / min(yerr)) of law-1 targets (else unread)
+};
+void bh_launch_like_sites(const LikeKernelArgs &a, const LikeSiteArgs &sites, hipStream_t stream);
 
 void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 

@@ -5,6 +5,7 @@
 // swd_kernel.hip / rf_kernel.hip / like_kernel.hip.  There is no CPU code path in here: if no
 // HIP device is usable, bh_engine_create fails.
 #include "../../include/bh_engine_debug.h"
+#include "../../include/bh_engine_sites.h"
 #include "bh_device.h"
 
 #include <cmath>
@@ -134,6 +135,10 @@ struct bh_engine {
     int nt = 0;
     int ldy = 0;
     std::vector<TargetHost> targets;
+    // site table (bh_sites_set, include/bh_engine_sites.h): observed data of nsites stations for the registered targets
+    int nsites = 0;
+    DevBuf site_yobs, site_yerr, site_logdet; // [nsites][ldy], [nsites][ldy] (law-1 columns), [nsites][nt]
+    DevBuf site_idx;                          // host calls: the site index of every model, staged
     // instrumentation
     bool timing = false, counting = false;
     bool no_mfma = false; // BH_NO_MFMA env: Gauss law through the in-kernel mat-vec (A/B testing)
@@ -212,6 +217,26 @@ void release(DevBuf &b)
 void release_target(TargetHost &t)
 {
     for (DevBuf *b : {&t.x, &t.yobs, &t.yerr_scaled, &t.rinv, &t.quad, &t.sums, &t.x60, &t.vel60}) release(*b);
+}
+
+// the site table's buffers (they belong to the registered targets: bh_targets_set and bh_engine_destroy release them)
+void release_sites(bh_engine *e)
+{
+    for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx}) release(*b);
+    e->nsites = 0;
+}
+
+// Targets.py:124-128, the nocorr_scalederr law: out = yerr / min(yerr), returns ln prod(out) (bh_targets_set, bh_sites_set)
+double scaled_errors(const double *yerr, int n, double *out)
+{
+    double mn = yerr[0];
+    for (int i = 0; i < n; ++i) mn = yerr[i] < mn ? yerr[i] : mn;
+    double prod = 1.0;
+    for (int i = 0; i < n; ++i) {
+        out[i] = yerr[i] / mn;
+        prod *= out[i];
+    }
+    return std::log(prod);
 }
 
 size_t span_elems(int B, int Lmax, ptrdiff_t sl, ptrdiff_t sb)
@@ -844,8 +869,10 @@ int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, pt
 }
 
 // Fill the likelihood descriptor of target t; for the Gauss law run the MFMA contraction first.
+// site: null, or the site index of every model (device; bh_evaluate_sites): the Gauss contraction reads the observed data
+// of each model's site from the site table
 int prepare_like_target(bh_engine *e, hipStream_t st, int B, int ldy, const double *ymod_d, TargetHost &T,
-                        LikeTargetDev &L)
+                        LikeTargetDev &L, const int32_t *site = nullptr)
 {
     L.law = T.d.law; L.n = T.d.n; L.off = T.off;
     L.yobs = (const double *)T.yobs.p;
@@ -860,7 +887,13 @@ int prepare_like_target(bh_engine *e, hipStream_t st, int B, int ldy, const doub
         int rc = ensure(e, T.quad, (size_t)B * nsplit * sizeof(double));
         if (rc) return rc;
         ev_begin(e, 2, st);
-        bh_launch_gauss_quad(B, T.d.n, ldy, ymod_d + T.off, L.yobs, L.rinv, nsplit, (double *)T.quad.p, st);
+        if (site) {
+            const GaussSiteArgs gs{site, e->nsites, ldy};
+            bh_launch_gauss_quad_sites(B, T.d.n, ldy, ymod_d + T.off, (const double *)e->site_yobs.p + T.off, gs, L.rinv, nsplit,
+                                       (double *)T.quad.p, st);
+        } else {
+            bh_launch_gauss_quad(B, T.d.n, ldy, ymod_d + T.off, L.yobs, L.rinv, nsplit, (double *)T.quad.p, st);
+        }
         L.quad = (const double *)T.quad.p;
         L.nsplit = nsplit;
     }
@@ -1061,6 +1094,7 @@ void bh_engine_destroy(bh_engine *e)
     for (auto &t : e->targets) {
         release_target(t);
     }
+    release_sites(e);
     for (auto &s : e->evsets)
         for (auto &ev : s.ev)
             if (ev) (void)hipEventDestroy(ev);
@@ -1256,6 +1290,7 @@ int bh_targets_set(bh_engine *e, int nt, const bh_target_desc *td)
     for (auto &t : e->targets) {
         release_target(t);
     }
+    release_sites(e);
     e->targets.clear();
     e->nt = 0;
     e->ldy = 0;
@@ -1306,15 +1341,8 @@ int bh_targets_set(bh_engine *e, int nt, const bh_target_desc *td)
             }
         }
         if (!rc && d.law == BH_LAW_NOCORR_SCALED) { // Targets.py:124-128
-            std::vector<double> se(d.yerr, d.yerr + d.n);
-            double mn = se[0];
-            for (double v : se) mn = v < mn ? v : mn;
-            double prod = 1.0;
-            for (double &v : se) {
-                v = v / mn;
-                prod *= v;
-            }
-            t.logdet_extra = std::log(prod);
+            std::vector<double> se((size_t)d.n);
+            t.logdet_extra = scaled_errors(d.yerr, d.n, se.data());
             rc = ensure(e, t.yerr_scaled, nb);
             if (!rc && hipMemcpy(t.yerr_scaled.p, se.data(), nb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(e, BH_EHIP, "copy yerr");
         }
@@ -1338,10 +1366,14 @@ int bh_targets_set(bh_engine *e, int nt, const bh_target_desc *td)
     return BH_OK;
 }
 
-int bh_evaluate_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax,
-                      const int32_t *nlay, const double *h, const double *vp, const double *vs,
-                      const double *rho, ptrdiff_t sl, ptrdiff_t sb, const double *noise,
-                      double *logL, double *misfits, int32_t *err, double *ymod)
+} // extern "C"
+
+namespace {
+
+// bh_evaluate_batch (site == nullptr: exactly its launches) and bh_evaluate_sites (site = the caller's site index per model)
+int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const int32_t *nlay, const double *h, const double *vp,
+             const double *vs, const double *rho, ptrdiff_t sl, ptrdiff_t sb, const int32_t *site, const double *noise,
+             double *logL, double *misfits, int32_t *err, double *ymod)
 {
     int rc;
     if ((rc = check_models(e, B, Lmax, sl, sb))) return rc;
@@ -1349,6 +1381,9 @@ int bh_evaluate_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax,
     for (const auto &T : e->targets)
         if (T.d.kind == BH_TARGET_USER) return fail(e, BH_EINVAL, "a BH_TARGET_USER target has no forward model: use bh_loglike_batch");
     if (!nlay || !h || !vp || !vs || !noise || !logL || !misfits || !err) return fail(e, BH_EINVAL, "null argument");
+    if (site && memspace != BH_DEVICE)
+        for (int b = 0; b < B; ++b)
+            if (site[b] < 0 || site[b] >= e->nsites) return fail(e, BH_EINVAL, "site index out of range (bh_sites_set)");
     if (B == 0) return BH_OK;
     HIPCHK(e, hipSetDevice(e->device));
     const int nt = e->nt, ldy = e->ldy;
@@ -1366,6 +1401,11 @@ int bh_evaluate_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax,
         if ((rc = ensure(e, e->errb, (size_t)B * sizeof(int32_t)))) return rc;
         HIPCHK(e, hipMemcpyAsync(e->noise.p, noise, (size_t)B * 2 * nt * sizeof(double), hipMemcpyHostToDevice, st));
         noise_d = (const double *)e->noise.p;
+        if (site) {
+            if ((rc = ensure(e, e->site_idx, (size_t)B * sizeof(int32_t)))) return rc;
+            HIPCHK(e, hipMemcpyAsync(e->site_idx.p, site, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            site = (const int32_t *)e->site_idx.p;
+        }
         logL_d = (double *)e->logL.p;
         misf_d = (double *)e->misfits.p;
         err_d = (int32_t *)e->errb.p;
@@ -1469,7 +1509,8 @@ int bh_evaluate_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax,
         // Fused likelihood ("write nothing if the likelihood is fused"): the caller did not ask for the
         // synthetics and the target's law needs only sums over the trace -- the synthesis kernel forms them from the samples
         // in LDS (like_kernel's order: the same bits) and writes four numbers per model instead of the trace.
-        T.fused = !ymod && bh_tuning().rf_no_fuse == 0 && (d.law == BH_LAW_NOCORR || d.law == BH_LAW_EXP) && bh_tuning().rf_threads != 128;
+        // (sites: the trace goes to the ymod workspace and the site-indexed likelihood kernel forms the sums)
+        T.fused = !ymod && !site && bh_tuning().rf_no_fuse == 0 && (d.law == BH_LAW_NOCORR || d.law == BH_LAW_EXP) && bh_tuning().rf_threads != 128;
         if (T.fused && (rc = ensure(e, T.sums, (size_t)B * 4 * sizeof(double)))) return rc;
         rc = launch_rf(e, rst, B, Lmax, m, sl, sb, d.p_s_per_deg, d.gauss, d.nsamp, d.fsamp, d.tshift,
                        d.nsv, d.waveno, d.n, ymod_d + T.off, ldy, fork, T.fused ? (const double *)T.yobs.p : nullptr,
@@ -1481,9 +1522,15 @@ int bh_evaluate_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax,
         HIPCHK(e, hipStreamWaitEvent(st, e->ev_join, 0));
     }
     for (int t = 0; t < nt; ++t)
-        if ((rc = prepare_like_target(e, st, B, ldy, ymod_d, e->targets[(size_t)t], la.t[t]))) return rc;
+        if ((rc = prepare_like_target(e, st, B, ldy, ymod_d, e->targets[(size_t)t], la.t[t], site))) return rc;
     ev_begin(e, 2, st);
-    bh_launch_like(la, st);
+    if (site) {
+        const LikeSiteArgs ls{site, e->nsites, (const double *)e->site_yobs.p, (const double *)e->site_yerr.p,
+                              (const double *)e->site_logdet.p};
+        bh_launch_like_sites(la, ls, st);
+    } else {
+        bh_launch_like(la, st);
+    }
     ev_end(e, 2, st);
     call_end(e, st);
     HIPCHK(e, hipGetLastError());
@@ -1495,6 +1542,66 @@ int bh_evaluate_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax,
         HIPCHK(e, hipStreamSynchronize(st));
     }
     return BH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int bh_evaluate_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax,
+                      const int32_t *nlay, const double *h, const double *vp, const double *vs,
+                      const double *rho, ptrdiff_t sl, ptrdiff_t sb, const double *noise,
+                      double *logL, double *misfits, int32_t *err, double *ymod)
+{
+    return evaluate(e, memspace, stream, B, Lmax, nlay, h, vp, vs, rho, sl, sb, nullptr, noise, logL, misfits, err, ymod);
+}
+
+int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yerr)
+{
+    if (!e) return BH_EINVAL;
+    if (e->nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
+    if (nsites < 1 || !yobs) return fail(e, BH_EINVAL, "bh_sites_set needs nsites >= 1 and yobs");
+    const int nt = e->nt, ldy = e->ldy;
+    bool scaled = false;
+    for (const auto &T : e->targets) scaled = scaled || T.d.law == BH_LAW_NOCORR_SCALED;
+    if (scaled && !yerr) return fail(e, BH_EINVAL, "a BH_LAW_NOCORR_SCALED target needs yerr of every site");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    release_sites(e);
+    const size_t S = (size_t)nsites;
+    std::vector<double> se(S * ldy, 1.0), ld(S * nt, 0.0);
+    for (size_t s = 0; s < S; ++s)
+        for (int t = 0; t < nt; ++t) {
+            const TargetHost &T = e->targets[(size_t)t];
+            ld[s * nt + t] = T.logdet_extra;
+            if (T.d.law == BH_LAW_NOCORR_SCALED)
+                ld[s * nt + t] = scaled_errors(yerr + s * ldy + T.off, T.d.n, se.data() + s * ldy + T.off);
+        }
+    int rc;
+    if ((rc = ensure(e, e->site_yobs, S * ldy * sizeof(double))) || (rc = ensure(e, e->site_yerr, S * ldy * sizeof(double))) ||
+        (rc = ensure(e, e->site_logdet, S * nt * sizeof(double)))) {
+        release_sites(e);
+        return rc;
+    }
+    if (hipMemcpy(e->site_yobs.p, yobs, S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(e->site_yerr.p, se.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(e->site_logdet.p, ld.data(), S * nt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        release_sites(e);
+        return fail(e, BH_EHIP, "copy site table");
+    }
+    e->nsites = nsites;
+    return BH_OK;
+}
+
+int bh_evaluate_sites(bh_engine *e, int memspace, void *stream, int B, int Lmax, const int32_t *nlay,
+                      const double *h, const double *vp, const double *vs, const double *rho,
+                      ptrdiff_t stride_l, ptrdiff_t stride_b, const int32_t *site, const double *noise,
+                      double *logL, double *misfits, int32_t *err, double *ymod)
+{
+    if (!e) return BH_EINVAL;
+    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (!site) return fail(e, BH_EINVAL, "null argument");
+    return evaluate(e, memspace, stream, B, Lmax, nlay, h, vp, vs, rho, stride_l, stride_b, site, noise, logL, misfits, err, ymod);
 }
 
 int bh_loglike_batch(bh_engine *e, int memspace, void *stream, int B, const double *ymod,

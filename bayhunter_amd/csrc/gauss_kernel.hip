@@ -24,84 +24,31 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 constexpr int KT = 32;  // K tile
 constexpr int LDT = 80; // LDS row stride in doubles: 64 + 16 puts consecutive k rows 128 B apart mod 256 B
 
+// SITES: the observed data of model b is the row of its site (GaussSiteArgs, bh_device.h), gathered per model row from a
+// table that stays in L2; a site out of range reads site 0's row (the likelihood kernel reports that model failed)
+__device__ __forceinline__ const double *site_row(const double *yobs, const GaussSiteArgs &S, int b)
+{
+    const int s = S.site[b];
+    return yobs + (size_t)((s >= 0 && s < S.nsites) ? s : 0) * S.ldo;
+}
+
 __global__ __launch_bounds__(256, 2) void gauss_quad_kernel(int B, int n, int ldy, const double *ymod,
                                                             const double *yobs, const double *rinv,
                                                             int nsplit, int cols_per_split, double *partial)
 {
-    __shared__ double Dt[KT][LDT]; // residuals, [k][model]
-    __shared__ double Rt[KT][LDT]; // R^-1 tile, [k][col]
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    const int m0 = blockIdx.x * 64;
-    const int c_begin = blockIdx.y * cols_per_split;
-    const int c_end = min(n, c_begin + cols_per_split);
-    const int fi = l & 15, fk = l >> 4; // fragment coordinates
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-
-    // staging coordinates: D tile: thread -> model tid/4, 8 consecutive k; R^-1 tile: thread -> row tid/8, 8 consecutive columns
-    const int d_mdl = tid >> 2, d_kq = (tid & 3) * 8, d_gb = m0 + d_mdl;
-    const int r_kr = tid >> 3, r_cq = (tid & 7) * 8;
-    for (int jt = c_begin; jt < c_end; jt += 64) {
-        double4_t c[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) c[b] = double4_t{0.0, 0.0, 0.0, 0.0};
-        // software pipeline: the global loads of K tile t+1 are in flight while the MFMAs of tile t run
-        double dreg[8], rreg[8];
-        auto fetch = [&](int k0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int k = k0 + d_kq + i;
-                dreg[i] = (d_gb < B && k < n) ? ymod[(size_t)d_gb * ldy + k] - yobs[k] : 0.0;
-            }
-            const int k = k0 + r_kr;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int col = jt + r_cq + i;
-                rreg[i] = (k < n && col < c_end) ? rinv[(size_t)k * n + col] : 0.0;
-            }
-        };
-        fetch(0);
-        for (int k0 = 0; k0 < n; k0 += KT) {
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                Dt[d_kq + i][d_mdl] = dreg[i];
-                Rt[r_kr][r_cq + i] = rreg[i];
-            }
-            __syncthreads();
-            if (k0 + KT < n) fetch(k0 + KT);
-#pragma unroll
-            for (int kk = 0; kk < KT; kk += 4) {
-                const double a = Dt[kk + fk][w * 16 + fi];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const double bv = Rt[kk + fk][b * 16 + fi];
-                    c[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, c[b], 0, 0, 0);
-                }
-            }
-        }
-        // epilogue: c[b][r] = V[model 16w + fk + 4r][col jt + 16b + fi]; fold in D of the same entry
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int gb = m0 + w * 16 + fk + 4 * r;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int col = jt + b * 16 + fi;
-                if (gb < B && col < c_end) acc[r] += c[b][r] * (ymod[(size_t)gb * ldy + col] - yobs[col]);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        double v = acc[r];
-        v += __shfl_xor(v, 1);
-        v += __shfl_xor(v, 2);
-        v += __shfl_xor(v, 4);
-        v += __shfl_xor(v, 8);
-        const int gb = m0 + w * 16 + fk + 4 * r;
-        if (fi == 0 && gb < B) partial[(size_t)gb * nsplit + blockIdx.y] = v;
-    }
+    constexpr bool SITES = false;
+    constexpr GaussSiteArgs S{};
+#include "gauss_body.inc"
 }
 
+// the same with a site table (bh_evaluate_sites)
+__global__ __launch_bounds__(256, 2) void gauss_quad_sites_kernel(int B, int n, int ldy, const double *ymod,
+                                                            const double *yobs, const double *rinv,
+                                                            int nsplit, int cols_per_split, double *partial, GaussSiteArgs S)
+{
+    constexpr bool SITES = true;
+#include "gauss_body.inc"
+}
 
 // ---- the large-problem form (round 3): 128 models x 128 columns per workgroup ---------------------------------
 // The 64 x 64 tiles above read 1 MB from L2 for every 8.4 MFLOP (every workgroup streams its 64 residual rows and
@@ -126,89 +73,18 @@ __global__ __launch_bounds__(512) void gauss_quad_kernel_128(int B, int n, int l
                                                              const double *__restrict__ yobs, const double *__restrict__ rinv,
                                                              int nsplit, int kper, double *__restrict__ partial)
 {
-    __shared__ __align__(16) double Dm[2][BM * PA];
-    __shared__ __align__(16) double Rt[2][KT2 * PB];
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    const int wm = w >> 1, wn = w & 1;
-    const int fi = l & 15, fk = l >> 4;
-    const int m0 = blockIdx.x * BM, c0 = blockIdx.y * BN;
-    // staging coordinates
-    const int d_mdl = tid >> 2, d_kq = (tid & 3) * NPT;                           // residuals: model, NPT consecutive k
-    const int r_row = tid / (BN / NPT), r_cq = (tid % (BN / NPT)) * NPT;          // R^-1: k row, NPT consecutive columns
-    const int d_gb = m0 + d_mdl;
-    const bool d_ok = d_gb < B;
-    const double *yrow = ymod + (size_t)(d_ok ? d_gb : 0) * ldy;
-    // this workgroup's share of K (blockIdx.z): the quadratic form is a sum over k as well, so a K range is one more slab
-    const int kbeg = blockIdx.z * kper, kend = min(n, kbeg + kper);
-    double dreg[NPT], rreg[NPT];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < NPT; ++i) {
-            const int k = k0 + d_kq + i;
-            dreg[i] = (d_ok && k < kend) ? yrow[k] - yobs[k] : 0.0;
-        }
-        const int k = k0 + r_row;
-#pragma unroll
-        for (int i = 0; i < NPT; ++i) {
-            const int col = c0 + r_cq + i;
-            rreg[i] = (k < kend && col < n) ? rinv[(size_t)k * n + col] : 0.0;
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NPT; ++i) Dm[buf][d_mdl * PA + d_kq + i] = dreg[i];
-        double2 *dst = reinterpret_cast<double2 *>(&Rt[buf][r_row * PB + r_cq]);
-#pragma unroll
-        for (int i = 0; i < NPT / 2; ++i) dst[i] = make_double2(rreg[2 * i], rreg[2 * i + 1]);
-    };
-    double4_t c[2][4];
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) c[rb][cb] = double4_t{0.0, 0.0, 0.0, 0.0};
-    const int ntile = (kend - kbeg + KT2 - 1) / KT2;
-    fetch(kbeg);
-    stage(0);
-    __syncthreads();
-    for (int t = 0; t < ntile; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < ntile) fetch(kbeg + (t + 1) * KT2);
-        const double *da = &Dm[buf][(wm * 32 + fi) * PA + fk];
-        const double *rb_ = &Rt[buf][fk * PB + wn * 64 + fi];
-#pragma unroll
-        for (int kk = 0; kk < KT2; kk += 4) {
-            const double a0 = da[kk], a1 = da[16 * PA + kk];
-            double bv[4];
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) bv[cb] = rb_[kk * PB + cb * 16];
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                c[0][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bv[cb], c[0][cb], 0, 0, 0);
-                c[1][cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, bv[cb], c[1][cb], 0, 0, 0);
-            }
-        }
-        if (t + 1 < ntile) stage(buf ^ 1);
-        __syncthreads();
-    }
-    // epilogue: c[rb][cb][r] = V[model m0 + 32 wm + 16 rb + fk + 4 r][column c0 + 64 wn + 16 cb + fi]; fold in D of the same
-    // entry, sum over this wavefront's 64 columns; one slab per (column block, column half)
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int gb = m0 + wm * 32 + rb * 16 + fk + 4 * r;
-            double v = 0.0;
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb) {
-                const int col = c0 + wn * 64 + cb * 16 + fi;
-                if (gb < B && col < n) v += c[rb][cb][r] * (ymod[(size_t)gb * ldy + col] - yobs[col]);
-            }
-            v += __shfl_xor(v, 1);
-            v += __shfl_xor(v, 2);
-            v += __shfl_xor(v, 4);
-            v += __shfl_xor(v, 8);
-            if (fi == 0 && gb < B) partial[(size_t)gb * nsplit + (blockIdx.y * 2 + wn) * gridDim.z + blockIdx.z] = v;
-        }
+    constexpr bool SITES = false;
+    constexpr GaussSiteArgs S{};
+#include "gauss_body_128.inc"
+}
+
+// the same with a site table (bh_evaluate_sites)
+__global__ __launch_bounds__(512) void gauss_quad_sites_kernel_128(int B, int n, int ldy, const double *__restrict__ ymod,
+                                                             const double *__restrict__ yobs, const double *__restrict__ rinv,
+                                                             int nsplit, int kper, double *__restrict__ partial, GaussSiteArgs S)
+{
+    constexpr bool SITES = true;
+#include "gauss_body_128.inc"
 }
 
 } // namespace
@@ -243,18 +119,38 @@ int bh_gauss_nsplit(int B, int n)
     return nsplit;
 }
 
-void bh_launch_gauss_quad(int B, int n, int ldy, const double *ymod, const double *yobs,
-                          const double *rinv, int nsplit, double *partial, hipStream_t stream)
+static void launch_gauss_quad(int B, int n, int ldy, const double *ymod, const double *yobs, const GaussSiteArgs *sites,
+                              const double *rinv, int nsplit, double *partial, hipStream_t stream)
 {
     if (use_big_tiles(B, n)) {
         const int ks = big_ksplit(B, n);
         const int kper = (((n + ks - 1) / ks + KT2 - 1) / KT2) * KT2;
-        hipLaunchKernelGGL(gauss_quad_kernel_128, dim3((B + BM - 1) / BM, (n + BN - 1) / BN, ks), dim3(512), 0, stream, B, n, ldy,
-                           ymod, yobs, rinv, nsplit, kper, partial);
+        const dim3 grid((B + BM - 1) / BM, (n + BN - 1) / BN, ks);
+        if (sites)
+            hipLaunchKernelGGL(gauss_quad_sites_kernel_128, grid, dim3(512), 0, stream, B, n, ldy, ymod, yobs, rinv, nsplit, kper,
+                               partial, *sites);
+        else
+            hipLaunchKernelGGL(gauss_quad_kernel_128, grid, dim3(512), 0, stream, B, n, ldy, ymod, yobs, rinv, nsplit, kper, partial);
         return;
     }
     const int tiles = (n + 63) / 64;
     const int cols_per_split = ((tiles + nsplit - 1) / nsplit) * 64;
-    hipLaunchKernelGGL(gauss_quad_kernel, dim3((B + 63) / 64, nsplit), dim3(256), 0, stream, B, n, ldy, ymod,
-                       yobs, rinv, nsplit, cols_per_split, partial);
+    const dim3 grid((B + 63) / 64, nsplit);
+    if (sites)
+        hipLaunchKernelGGL(gauss_quad_sites_kernel, grid, dim3(256), 0, stream, B, n, ldy, ymod, yobs, rinv, nsplit, cols_per_split,
+                           partial, *sites);
+    else
+        hipLaunchKernelGGL(gauss_quad_kernel, grid, dim3(256), 0, stream, B, n, ldy, ymod, yobs, rinv, nsplit, cols_per_split, partial);
+}
+
+void bh_launch_gauss_quad(int B, int n, int ldy, const double *ymod, const double *yobs,
+                          const double *rinv, int nsplit, double *partial, hipStream_t stream)
+{
+    launch_gauss_quad(B, n, ldy, ymod, yobs, nullptr, rinv, nsplit, partial, stream);
+}
+
+void bh_launch_gauss_quad_sites(int B, int n, int ldy, const double *ymod, const double *yobs, const GaussSiteArgs &sites,
+                                const double *rinv, int nsplit, double *partial, hipStream_t stream)
+{
+    launch_gauss_quad(B, n, ldy, ymod, yobs, &sites, rinv, nsplit, partial, stream);
 }

@@ -1,0 +1,82 @@
+// bayhunter_amd/csrc/like_small_body.inc -- the body of like_small_kernel and like_small_sites_kernel (like_kernel.hip), included inside each kernel.
+// In scope: LikeKernelArgs A, LikeSiteArgs S and the compile-time `constexpr bool SITES` (true: model b compares with
+// the observed data of its site S.site[b]; a site out of range fails the model in band and reads no observed data).
+// The body is included rather than called: a device function inlined into the kernel is optimised in another order, and
+// the kernels without sites keep the machine code they had before the site variants existed.
+    const int lane = threadIdx.x & 63;
+    const int ib = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ib >= A.B) return;
+    const double *y = A.ymod + (size_t)ib * A.ldy;
+    double logL = 0.0, joint = 0.0;
+    bool failed = false;
+    for (int t = 0; t < A.nt; ++t) failed = failed || (A.err_t[(size_t)t * A.B + ib] != 0);
+    int site = 0;
+    if (SITES) { // the wavefront's model: a scalar load
+        site = S.site[__builtin_amdgcn_readfirstlane(ib)];
+        failed = failed || site < 0 || site >= S.nsites;
+    }
+    for (int t = 0; t < A.nt && !failed; ++t) {
+        const LikeTargetDev T = SITES ? site_target(A.t[t], S, site, A.ldy, A.nt, t) : A.t[t];
+        const int n = T.n;
+        const double *ym = y + T.off;
+        const double corr = A.noise[(size_t)ib * 2 * A.nt + 2 * t];
+        const double sigma = A.noise[(size_t)ib * 2 * A.nt + 2 * t + 1];
+        double s0 = 0.0, s1 = 0.0, sw = 0.0, d0 = 0.0, dn = 0.0;
+        if (T.pre != nullptr) { // the forward kernel formed the sums (fused likelihood, RfKernelArgs::sums)
+            const double *pre = T.pre + (size_t)ib * 4;
+            s0 = pre[0];
+            s1 = pre[1];
+            d0 = pre[2];
+            dn = pre[3];
+        } else {
+        if (lane < n) {
+            const double d = ym[lane] - T.yobs[lane];
+            s0 += d * d;
+            if (T.law == 2 && lane + 1 < n) s1 += d * (ym[lane + 1] - T.yobs[lane + 1]);
+            if (T.law == 1) sw += d * d / T.yerr_scaled[lane];
+        }
+        if (T.law == 3 && lane == 0)
+            for (int sidx = 0; sidx < T.nsplit; ++sidx) sw += T.quad[(size_t)ib * T.nsplit + sidx];
+        for (int off = 32; off > 0; off >>= 1) s0 += __shfl_xor(s0, off);
+        if (T.law == 2)
+            for (int off = 32; off > 0; off >>= 1) s1 += __shfl_xor(s1, off);
+        if (T.law == 1 || T.law == 3)
+            for (int off = 32; off > 0; off >>= 1) sw += __shfl_xor(sw, off);
+        if (T.law == 2) {
+            d0 = ym[0] - T.yobs[0];
+            dn = ym[n - 1] - T.yobs[n - 1];
+        }
+        }
+        const double s2 = sigma * sigma;
+        double phi, logdet = (2.0 * n) * log(sigma);
+        if (T.law == 0) {
+            phi = s0 / s2;
+        } else if (T.law == 1) {
+            phi = sw / s2;
+            logdet += T.logdet_extra;
+        } else if (T.law == 2) {
+            const double edge = (n > 1) ? (d0 * d0 + dn * dn) : (d0 * d0);
+            const double r2 = corr * corr;
+            phi = ((1.0 + r2) * s0 - r2 * edge - 2.0 * corr * s1) / (s2 * (1.0 - r2));
+            logdet += (n - 1) * log(1.0 - r2);
+        } else {
+            phi = sw / s2;
+            logdet += T.logdet_extra;
+        }
+        const double part = -0.5 * ((double)n * log(2.0 * M_PI) + logdet);
+        logL += part - phi / 2.0;
+        const double rms = sqrt(s0 / (double)n);
+        joint += rms;
+        if (lane == 0) A.misfits[(size_t)ib * (A.nt + 1) + t] = rms;
+    }
+    if (lane == 0) {
+        if (failed) { // Targets.py:325-328
+            A.logL[ib] = -1e15;
+            for (int t = 0; t <= A.nt; ++t) A.misfits[(size_t)ib * (A.nt + 1) + t] = 1e15;
+            A.err[ib] = 1;
+        } else {
+            A.logL[ib] = logL;
+            A.misfits[(size_t)ib * (A.nt + 1) + A.nt] = joint;
+            A.err[ib] = 0;
+        }
+    }

@@ -42,6 +42,7 @@ import numpy as np
 from .chains import ChainBatch, DEFAULT_INITPARAMS, DEFAULT_PRIORS, _is_fixed
 from .engine import BH_CHAIN_MAXDEPTH, BH_CHAIN_MAXLAYERS, ChainConfig, ChainState, EngineError
 from .Targets import JointTarget
+from .sites import SiteTargets, window_site_map
 
 
 def auto_spec_depth(nchains, budget=None):
@@ -94,10 +95,18 @@ class DeviceChains(object):
         same trajectory; its guarded models (2 % of a sampler's Love proposals) are re-run by a second launch.  "exact": the
         reference's rounding points -- the windows then take the layer-parallel kernel, which restarts a guarded model in
         place.  Measured on MI355X (chain-iterations/s, "fast" / "exact"): 8 chains 7.4e4 / 5.2e4, a 64-chain tempered rung
-        2.18e5 / 1.83e5, 512 chains 4.6e5 / 3.9e5.  None: whatever the engine is set to."""
+        2.18e5 / 1.83e5, 512 chains 4.6e5 / 3.9e5.  None: whatever the engine is set to.
+        Many stations: `targets` = a SiteTargets of S sites runs `nchains` chains PER SITE in one lock-step launch: chain c of
+        site s is chain s*nchains + c (plus chain_offset) and walks exactly the trajectory of a one-site
+        DeviceChains(site s, nchains, chain_offset=s*nchains) with the same seed; every model of a window is compared with
+        its own site's data (Engine.evaluate_sites_dev).  Tempering ladders must lie within one site; `dist` is refused
+        (spread sites over GPUs by giving each process its own sites)."""
         import torch
         self.torch = torch
-        self.targets = targets if isinstance(targets, JointTarget) else JointTarget(targets)
+        self.sites = targets if isinstance(targets, SiteTargets) else None
+        if self.sites is not None and dist is not None:
+            raise EngineError("DeviceChains with SiteTargets does not shard: give each process its own sites instead of dist")
+        self.targets = targets if isinstance(targets, (JointTarget, SiteTargets)) else JointTarget(targets)
         if self.targets._engine is None and device is not None:
             from .engine import default_engine
             self.targets._engine = default_engine(int(device))   # kernels and tensors on the same GPU
@@ -117,7 +126,9 @@ class DeviceChains(object):
         self.initparams = dict(DEFAULT_INITPARAMS)
         self.initparams.update(initparams or {})
         ip, pr = self.initparams, self.priors
-        self.C = int(nchains)
+        self.C_site = int(nchains)                        # chains per site (sites: S blocks of them, site after site)
+        self.nsites = 1 if self.sites is None else self.sites.nsites
+        self.C = self.C_site * self.nsites
         self.nt = self.targets.ntargets
         self.ML = int(pr["layers"][1]) + 1
         if self.ML > BH_CHAIN_MAXLAYERS:
@@ -144,12 +155,18 @@ class DeviceChains(object):
         self.rank = dist.get_rank() if dist is not None and dist.is_initialized() else 0
 
         # ---- initial state through the reference-order host code --------------------------------
-        host = ChainBatch(self.targets, chain_seeds(seed, off, self.C), ip, pr,
-                          search=self.search if self.search is not None else self.targets.engine.swd_search(),
-                          arith=self.arith if self.arith is not None else self.targets.engine.swd_arith(),
-                          trials=self.TRIALS)   # (the windows' count: the initial likelihoods are the windows' bits)
-        self.noisepriors = host.noisepriors
-        self.targets._register()  # constant target data + laws live on the device from here on
+        # (sites: one ChainBatch per site, on that site's targets, with the seeds of its global chain numbers)
+        hosts = [ChainBatch(self.targets if self.sites is None else self.sites.site(s),
+                            chain_seeds(seed, off + s * self.C_site, self.C_site), ip, pr,
+                            search=self.search if self.search is not None else self.targets.engine.swd_search(),
+                            arith=self.arith if self.arith is not None else self.targets.engine.swd_arith(),
+                            trials=self.TRIALS)   # (the windows' count: the initial likelihoods are the windows' bits)
+                 for s in range(self.nsites)]
+        self.noisepriors = hosts[0].noisepriors
+        if any(h.noisepriors != self.noisepriors for h in hosts):
+            raise EngineError("the sites' noise priors differ")
+        host_chains = [ch for h in hosts for ch in h.chains]
+        self.targets._register()  # constant target data + laws (+ the site table) live on the device from here on
 
         cfg = ChainConfig()
         cfg.nt, cfg.maxlayers = self.nt, self.ML
@@ -186,7 +203,7 @@ class DeviceChains(object):
         vs0 = np.zeros((ML, Cn)); z0 = np.zeros((ML, Cn)); n0 = np.zeros(Cn, dtype=np.int32)
         noise0 = np.zeros((2 * nt, Cn)); mis0 = np.zeros((nt + 1, Cn))
         like0 = np.zeros(Cn); vpvs0 = np.zeros(Cn); pd0 = np.zeros((5, Cn))
-        for c, ch in enumerate(host.chains):
+        for c, ch in enumerate(host_chains):
             m = np.asarray(ch.currentmodel, dtype=float)
             n = m.size // 2
             n0[c] = n
@@ -204,6 +221,14 @@ class DeviceChains(object):
         t["naccepted"] = torch.zeros(Cn, dtype=torch.int64, device=dev)
         t["beta"] = None if betas is None else torch.as_tensor(np.asarray(betas, dtype=np.float64)).to(dev)
         self.ladder = None if betas is None else np.asarray(ladder if ladder is not None else np.zeros(Cn), dtype=np.int64)
+        self.site_map = None
+        if self.sites is not None:
+            if self.ladder is not None:
+                of = np.arange(Cn) // self.C_site
+                for lid in np.unique(self.ladder):
+                    if np.unique(of[self.ladder == lid]).size > 1:
+                        raise EngineError("tempering ladder %d spans sites: every ladder must lie within one site" % lid)
+            self.site_map = torch.from_numpy(window_site_map(self.C_site, self.nsites, self.ld)).to(dev)
         ld = self.ld                                      # node j of chain c in column j*C + c
         for k in ("pn", "move", "valid", "lay_n"):
             t[k] = torch.zeros(ld, **i32)
@@ -273,9 +298,16 @@ class DeviceChains(object):
             e.set_swd_arith(self.arith)
         e.set_swd_trials(self.TRIALS)
         try:
-            e.evaluate_batch_dev(B, self.ML, t["lay_n"].data_ptr(), t["lay_h"].data_ptr(), t["lay_vp"].data_ptr(),
-                                 t["lay_vs"].data_ptr(), t["lay_rho"].data_ptr(), self.ld, 1, t["pnoise"].data_ptr(), self.logL.data_ptr(),
-                                 self.mis.data_ptr(), self.err.data_ptr())
+            if self.sites is not None:
+                if e._owner is not self.sites:          # (another caller registered its targets since)
+                    self.sites._register()
+                e.evaluate_sites_dev(B, self.ML, t["lay_n"].data_ptr(), t["lay_h"].data_ptr(), t["lay_vp"].data_ptr(),
+                                     t["lay_vs"].data_ptr(), t["lay_rho"].data_ptr(), self.ld, 1, self.site_map.data_ptr(),
+                                     t["pnoise"].data_ptr(), self.logL.data_ptr(), self.mis.data_ptr(), self.err.data_ptr())
+            else:
+                e.evaluate_batch_dev(B, self.ML, t["lay_n"].data_ptr(), t["lay_h"].data_ptr(), t["lay_vp"].data_ptr(),
+                                     t["lay_vs"].data_ptr(), t["lay_rho"].data_ptr(), self.ld, 1, t["pnoise"].data_ptr(),
+                                     self.logL.data_ptr(), self.mis.data_ptr(), self.err.data_ptr())
         finally:
             e.set_typical_layers(0)
             if prev is not None and prev != self.search:
@@ -344,9 +376,10 @@ class DeviceChains(object):
         self.engine.synchronize()
         return {k: (None if v is None else v.cpu().numpy()) for k, v in self.t.items()}
 
-    def samples(self, phase="p2", cold_only=False, gather=False):
+    def samples(self, phase="p2", cold_only=False, gather=False, site=None):
         """Thinned samples: dict of arrays with leading axes [nsnap, C]; `models` in the reference's row layout
         [vs_1..vs_n NaN.., z_1..z_n NaN..] (2*maxlayers wide).
+        site (SiteTargets): the columns of that site only (its nchains chains; cold_only: its ladders), else all.
         gather: all chains of a sharded job (global chain order) instead of this rank's, on every rank.
         cold_only (tempered runs): one column per LADDER -- at every snapshot the state of the chain holding
         beta = 1; implies gather (the cold chain of a ladder moves between chains, hence between ranks);
@@ -369,6 +402,12 @@ class DeviceChains(object):
         out["noise"] = np.array([r["noise"].T for r in S], dtype=np.float32).reshape(ns, Cn, 2 * self.nt)
         if ns and S[0]["beta"] is not None:
             out["beta"] = np.array([r["beta"] for r in S]).reshape(ns, Cn)   # cold samples: out["beta"] == 1
+        if site is not None:
+            if self.sites is None:
+                raise EngineError("samples(site=...) needs DeviceChains over SiteTargets")
+            if not 0 <= int(site) < self.nsites:
+                raise IndexError("site %d of %d" % (site, self.nsites))
+            return self._site_block(out, int(site), phase, cold_only, gather)
         if not (gather or cold_only):
             return out
         from .parallel import gather_chain_axis, cold_samples
@@ -385,12 +424,28 @@ class DeviceChains(object):
             out["ladder"] = ids
         return out
 
+    def _site_block(self, allcols, s, phase, cold_only, gather):
+        """samples() of site s: its block of columns (chains s*nchains ..), with gather / cold_only as for all chains"""
+        blk = slice(s * self.C_site, (s + 1) * self.C_site)
+        out = {k: v[:, blk] for k, v in allcols.items()}
+        if not (gather or cold_only):
+            return out
+        out["chain_id"] = self.chain_offset + np.arange(self.C, dtype=np.int64)[blk]
+        if cold_only and "beta" in out:
+            from .parallel import cold_samples
+            out.pop("chain_id")
+            ids, out = cold_samples(out, self.ladder[blk])
+            out["ladder"] = ids
+        return out
+
     def save(self, savepath=None):
         """c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy, the reference's per-chain result files
         (src/SingleChain.py:646-690), written by rank 0 for ALL chains of the job with their global numbers
         (end-of-run all-gather of the thinned snapshots).  Tempered runs: one file set per ladder, holding the
         beta = 1 samples only (hot chains are not posterior samples)."""
         from .parallel import write_chain_files
+        if self.sites is not None:
+            return self._save_sites(savepath)
         savepath = op.join(savepath or self.initparams["savepath"], "data")
         tempered = self.t["beta"] is not None
         for tag in ("p1", "p2"):
@@ -409,3 +464,24 @@ class DeviceChains(object):
         if self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1:
             self.dist.barrier()
         return savepath
+
+    def _save_sites(self, savepath=None):
+        """SiteTargets: one reference-format folder per site, <savepath>/<name>/data/ with the chain files of that site's
+        chains (global numbers, as a one-site run with chain_offset = s*nchains writes them) and <name>_config.pkl built
+        from that site's targets.  Returns the list of data folders."""
+        from .parallel import write_chain_files
+        from .results import save_config
+        root = savepath or self.initparams["savepath"]
+        tempered = self.t["beta"] is not None
+        out = []
+        for s, name in enumerate(self.sites.names):
+            datapath = op.join(root, name, "data")
+            for tag in ("p1", "p2"):
+                if not self.snap[tag]:
+                    continue
+                smp = self.samples(tag, cold_only=tempered, gather=True, site=s)
+                write_chain_files(datapath, tag, smp, smp["ladder"] if tempered else smp["chain_id"])
+            ip = dict(self.initparams, station=name, savepath=op.join(root, name))
+            save_config(self.sites.site(s), op.join(datapath, "%s_config.pkl" % name), priors=self.priors, initparams=ip)
+            out.append(datapath)
+        return out

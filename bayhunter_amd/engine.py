@@ -138,6 +138,9 @@ def load_library():
                                     C.c_ssize_t, C.c_ssize_t, vp, vp, vp, vp, vp]
     L.bh_loglike_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bh_probe_math.argtypes = [vp, C.c_int, C.c_int, _d, _d]
+    L.bh_sites_set.argtypes = [vp, C.c_int, vp, vp]
+    L.bh_evaluate_sites.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                    C.c_ssize_t, C.c_ssize_t, vp, vp, vp, vp, vp, vp]
     L.bh_chain_propose.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int]
     L.bh_chain_accept.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, vp, vp]
     L.bh_chain_propose_window.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, C.c_int, C.c_ssize_t]
@@ -145,7 +148,7 @@ def load_library():
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
-                 "bh_chain_propose_window", "bh_chain_accept_window"):
+                 "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites"):
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -165,6 +168,8 @@ DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_e
                  "bh_engine_get_swd_scan", "bh_engine_set_tuning",
                  "bh_engine_get_tuning", "bh_probe_math", "bh_engine_set_instrumentation", "bh_timing_reset",
                  "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace")
+# include/bh_engine_sites.h: many stations at once (site-indexed observed data)
+SITE_SYMBOLS = ("bh_sites_set", "bh_evaluate_sites")
 
 
 def _f64(a):
@@ -203,6 +208,7 @@ class Engine(object):
         self._owner = None  # the JointTarget whose targets are currently registered
         self.ntargets = 0
         self.ldy = 0
+        self.nsites = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -473,6 +479,7 @@ class Engine(object):
         self._check(self._L.bh_targets_set(self._h, len(descs), arr))
         self.ntargets = len(descs)
         self.ldy = ldy
+        self.nsites = 0
 
     def evaluate_batch(self, nlay, h, vp, vs, noise, rho=None, layout="layer_major", want_ymod=False):
         """Batched JointTarget.evaluate.  noise[B, 2*nt].  Returns (logL[B], misfits[B, nt+1],
@@ -489,6 +496,38 @@ class Engine(object):
         self._check(self._L.bh_evaluate_batch(self._h, HOST, None, B, Lmax, _ptr(nlay), _ptr(h),
                                               _ptr(vp), _ptr(vs), _ptr(rho), sl, sb, _ptr(noise),
                                               _ptr(logL), _ptr(misf), _ptr(err), _ptr(ymod)))
+        return (logL, misf, err, ymod) if want_ymod else (logL, misf, err)
+
+    def set_sites(self, yobs, yerr=None):
+        """Observed data of S sites for the registered targets (bh_sites_set): yobs[S, ldy], target after target as in ymod;
+        yerr[S, ldy] is read in the columns of nocorr_scalederr targets only (None if there is none).  set_targets drops it."""
+        yobs = _f64(yobs)
+        if yobs.ndim != 2 or yobs.shape[1] != self.ldy or yobs.shape[0] < 1:
+            raise ValueError("yobs must have shape (nsites, %d)" % self.ldy)
+        if yerr is not None:
+            yerr = _f64(yerr)
+            if yerr.shape != yobs.shape:
+                raise ValueError("yerr must have the shape of yobs")
+        self._check(self._L.bh_sites_set(self._h, yobs.shape[0], _ptr(yobs), _ptr(yerr)))
+        self.nsites = yobs.shape[0]
+
+    def evaluate_sites(self, nlay, h, vp, vs, noise, site, rho=None, layout="layer_major", want_ymod=False):
+        """evaluate_batch with model b compared with the observed data of site site[b] (bh_evaluate_sites).  Returns (logL[B],
+        misfits[B, nt+1], err[B][, ymod[B, ldy]])."""
+        B, Lmax, sl, sb, nlay, (h, vp, vs, rho) = self._model_args(nlay, h, vp, vs, rho, layout)
+        nt = self.ntargets
+        noise = _f64(noise)
+        if noise.shape != (B, 2 * nt):
+            raise ValueError("noise must have shape (B, 2*ntargets)")
+        site = np.ascontiguousarray(site, dtype=np.int32)
+        if site.shape != (B,):
+            raise ValueError("site must have shape (B,)")
+        logL = np.zeros(B)
+        misf = np.zeros((B, nt + 1))
+        err = np.zeros(B, dtype=np.int32)
+        ymod = np.zeros((B, self.ldy)) if want_ymod else None
+        self._check(self._L.bh_evaluate_sites(self._h, HOST, None, B, Lmax, _ptr(nlay), _ptr(h), _ptr(vp), _ptr(vs), _ptr(rho),
+                                              sl, sb, _ptr(site), _ptr(noise), _ptr(logL), _ptr(misf), _ptr(err), _ptr(ymod)))
         return (logL, misf, err, ymod) if want_ymod else (logL, misf, err)
 
     def loglike_batch(self, ymod, noise, fail=None):
@@ -542,6 +581,12 @@ class Engine(object):
                            ymod=None, stream=None):
         self._check(self._L.bh_evaluate_batch(self._h, DEVICE, stream, B, Lmax, nlay, h, vp, vs, rho,
                                               sl, sb, noise, logL, misfits, err, ymod))
+
+    def evaluate_sites_dev(self, B, Lmax, nlay, h, vp, vs, rho, sl, sb, site, noise, logL, misfits, err,
+                           ymod=None, stream=None):
+        """Device pointers; site = int32 [B] (a site out of range: that model fails in band)."""
+        self._check(self._L.bh_evaluate_sites(self._h, DEVICE, stream, B, Lmax, nlay, h, vp, vs, rho,
+                                              sl, sb, site, noise, logL, misfits, err, ymod))
 
 
     def chain_propose(self, cfg, state, C_, iiter):

@@ -1,0 +1,152 @@
+"""Many stations at once: a SITE is one station's observed data for a fixed target structure.
+
+Stations of one array (or nodes of a tomography grid) usually share the periods of their dispersion curves, their
+receiver-function parameters and their noise laws; they differ only in the observed values y (and sometimes in yerr).
+The forward models depend on the model and x only, so one evaluation batch may mix models of many sites, each compared
+with the observed data of its own site (include/bh_engine_sites.h).  `SiteTargets` holds one `JointTarget` per site and
+registers site 0's target descriptors plus the table of every site's observed data on the engine.
+"""
+import numpy as np
+
+from .Targets import JointTarget, LAWS
+from .rfmini_modrf import RFminiModRF
+from .surf96_modsw import SurfDisp
+
+
+def window_site_map(nchains, nsites, ld):
+    """Site of every column of a speculative window (include/bh_engine.h: node j of chain c in column j*C + c, with
+    C = nsites * nchains chains, site s holding chains s*nchains .. (s+1)*nchains - 1): int32 [ld]."""
+    C = int(nsites) * int(nchains)
+    return ((np.arange(int(ld), dtype=np.int64) % C) // int(nchains)).astype(np.int32)
+
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).tobytes()
+
+
+class SiteTargets(object):
+    """One `JointTarget` per site, evaluated together.  Every site must have the same number and classes of targets, the
+    same x (bit for bit), the same plugin parameters (SWD mode / flsph, every receiver-function call argument), the same
+    installed noise law and -- Gauss law -- identical corr_inv and logcorr_det; only engine-backed plugins.  y and yerr
+    may differ.  The checks run when the sites are registered (the noise laws are installed by the sampler)."""
+
+    def __init__(self, jointtargets, names=None, engine=None):
+        self._sites = [jt if isinstance(jt, JointTarget) else JointTarget(jt) for jt in jointtargets]
+        if not self._sites:
+            raise ValueError("SiteTargets needs at least one site")
+        self._names = ["site%03d" % s for s in range(len(self._sites))] if names is None else [str(n) for n in names]
+        if len(self._names) != len(self._sites) or len(set(self._names)) != len(self._names):
+            raise ValueError("names must be %d distinct names, one per site" % len(self._sites))
+        self._engine = engine
+        for jt in self._sites:          # every site on one engine
+            if jt._engine is None:
+                jt._engine = engine
+        self._registered = None
+
+    # ---- the JointTarget surface the chain drivers use -----------------------------------------------
+    @property
+    def engine(self):
+        if self._engine is None:
+            self._engine = self._sites[0].engine
+        for jt in self._sites:          # every site on the same engine
+            if jt._engine is None:
+                jt._engine = self._engine
+        return self._engine
+
+    @property
+    def targets(self):
+        """site 0's targets (the target structure every site shares)"""
+        return self._sites[0].targets
+
+    @property
+    def ntargets(self):
+        return self._sites[0].ntargets
+
+    @property
+    def nsites(self):
+        return len(self._sites)
+
+    @property
+    def names(self):
+        return list(self._names)
+
+    def site(self, s):
+        """the JointTarget of site s"""
+        return self._sites[int(s)]
+
+    # ---- checks and registration -------------------------------------------------------------------
+    def check(self):
+        """Raise ValueError unless every site shares site 0's target structure (class docstring)."""
+        ref = self._sites[0]
+        for s, jt in enumerate(self._sites):
+            who = "site %d (%s)" % (s, self._names[s])
+            if jt.ntargets != ref.ntargets:
+                raise ValueError("%s has %d targets, site 0 has %d" % (who, jt.ntargets, ref.ntargets))
+            for i, (t, t0) in enumerate(zip(jt.targets, ref.targets)):
+                what = "%s, target %d (%s)" % (who, i, t.ref)
+                if not t.engine_backed():
+                    raise ValueError("%s: a user plugin; a site set takes engine-backed targets only" % what)
+                if type(t) is not type(t0):
+                    raise ValueError("%s is a %s, site 0's is a %s" % (what, type(t).__name__, type(t0).__name__))
+                x, x0 = np.asarray(t.obsdata.x, dtype=float), np.asarray(t0.obsdata.x, dtype=float)
+                if x.shape != x0.shape or _bits(x) != _bits(x0):
+                    raise ValueError("%s: x differs from site 0's (sites share x bit for bit)" % what)
+                if np.size(t.obsdata.y) != x.size:
+                    raise ValueError("%s: y has %d values for %d samples" % (what, np.size(t.obsdata.y), x.size))
+                p, p0 = t.moddata.plugin, t0.moddata.plugin
+                if type(p) is not type(p0):
+                    raise ValueError("%s: plugin %s, site 0's is %s" % (what, type(p).__name__, type(p0).__name__))
+                if isinstance(p, SurfDisp):
+                    a = (p.wavetype, p.veltype, p.modelparams["mode"], p.modelparams["flsph"])
+                    a0 = (p0.wavetype, p0.veltype, p0.modelparams["mode"], p0.modelparams["flsph"])
+                    if a != a0:
+                        raise ValueError("%s: dispersion parameters (wave, velocity, mode, flsph) %r, site 0's %r" % (what, a, a0))
+                elif isinstance(p, RFminiModRF):
+                    a, a0 = p._call_args(), p0._call_args()
+                    if a != a0:
+                        raise ValueError("%s: receiver-function parameters %r, site 0's %r" % (what, a, a0))
+                law, law0 = t.law(), t0.law()
+                if law != law0:
+                    raise ValueError("%s: noise law %r, site 0's %r" % (what, law, law0))
+                if law == "gauss":
+                    v, v0 = t.valuation, t0.valuation
+                    if (np.shape(v.corr_inv) != np.shape(v0.corr_inv) or _bits(v.corr_inv) != _bits(v0.corr_inv)
+                            or _bits(v.logcorr_det) != _bits(v0.logcorr_det)):
+                        raise ValueError("%s: Gauss law with another R^-1 / ln|R| than site 0's (sites share corr)" % what)
+
+    def site_arrays(self):
+        """(yobs[S, ldy], yerr[S, ldy] or None): every site's observed data, target after target as in ymod"""
+        yobs = np.vstack([np.concatenate([np.asarray(t.obsdata.y, dtype=float).ravel() for t in jt.targets])
+                          for jt in self._sites])
+        if not any(LAWS[t.law()] == LAWS["nocorr_scalederr"] for t in self.targets):
+            return yobs, None
+        yerr = np.vstack([np.concatenate([np.asarray(t.obsdata.yerr, dtype=float).ravel() for t in jt.targets])
+                          for jt in self._sites])
+        return yobs, yerr
+
+    def _signature(self):
+        """What the registration depends on, by identity as JointTarget._signature: every site's targets, plugins and laws,
+        and the arrays of its x, y and yerr (O(sites x targets) per call; replacing an array re-registers)."""
+        return tuple((jt._signature(), tuple((id(t.obsdata.x), id(t.obsdata.y), id(t.obsdata.yerr)) for t in jt.targets))
+                     for jt in self._sites)
+
+    def _register(self):
+        """Site 0's descriptors + the site table on the engine, checked (`check`) and registered again only when the signature
+        changed or another caller registered its own targets since (Engine._owner)."""
+        sig = self._signature()
+        e = self.engine
+        if self._registered != sig:
+            self.check()
+        if self._registered != sig or e._owner is not self:
+            e.set_targets([t.engine_desc() for t in self.targets])
+            yobs, yerr = self.site_arrays()
+            e.set_sites(yobs, yerr)
+            e._owner = self
+            self._registered = sig
+            # the arrays the signature names stay alive while it is in force: their ids cannot be handed to replacements
+            self._held = [(t.obsdata.x, t.obsdata.y, t.obsdata.yerr) for jt in self._sites for t in jt.targets]
+
+    def evaluate_batch(self, nlay, h, vp, vs, noise, site, rho=None, layout="layer_major", want_ymod=False):
+        """B models, model b compared with site site[b]: returns (logL[B], misfits[B, nt+1], err[B][, ymod])."""
+        self._register()
+        return self.engine.evaluate_sites(nlay, h, vp, vs, noise, site, rho=rho, layout=layout, want_ymod=want_ymod)
