@@ -54,7 +54,7 @@ class Model(object):
 
 class ModelMatrix(object):
     """The one helper of the reference's `ModelMatrix` the result store needs (src/Models.py:227-274; the
-    depth-interpolation / histogram helpers of that class serve plotting only and stay with the reference)."""
+    depth-interpolation / histogram summaries of that class run on the GPU in bayhunter_amd/posterior.py)."""
 
     @staticmethod
     def get_weightedvalues(weights, models=None, likes=None, misfits=None, noiseparams=None, vpvs=None):

@@ -276,3 +276,8 @@ void bh_launch_like_sites(const LikeKernelArgs &a, const LikeSiteArgs &sites, hi
 void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 
 // out = [val n][bound n][certified n]
+
+// the engine as other translation units reach it (bh_engine.hip; posterior_kernel.hip, include/bh_engine_posterior.h)
+struct bh_engine;
+__attribute__((visibility("hidden"))) int bh_engine_fail_internal(bh_engine *e, int code, const char *what); // sets last_error
+__attribute__((visibility("hidden"))) int bh_engine_device_internal(const bh_engine *e);

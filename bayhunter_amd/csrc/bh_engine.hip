@@ -1114,6 +1114,13 @@ void bh_engine_destroy(bh_engine *e)
 }
 
 const char *bh_engine_last_error(const bh_engine *e) { return e ? e->err.c_str() : "null engine"; }
+
+} // extern "C"
+
+int bh_engine_fail_internal(bh_engine *e, int code, const char *what) { return fail(e, code, what); }
+int bh_engine_device_internal(const bh_engine *e) { return e->device; }
+
+extern "C" {
 void *bh_engine_stream(bh_engine *e) { return e ? (void *)e->stream : nullptr; }
 
 int bh_engine_synchronize(bh_engine *e)

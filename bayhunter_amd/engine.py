@@ -145,6 +145,15 @@ def load_library():
     L.bh_chain_accept.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, vp, vp]
     L.bh_chain_propose_window.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, C.c_int, C.c_ssize_t]
     L.bh_chain_accept_window.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp, vp]
+    L.bh_posterior_create.argtypes = [vp, C.POINTER(vp)]
+    L.bh_posterior_destroy.argtypes = [vp]
+    L.bh_posterior_destroy.restype = None
+    L.bh_posterior_load.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int64, vp, vp, C.c_int, vp, vp, vp]
+    L.bh_posterior_columns.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.bh_posterior_hist.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.bh_posterior_interfaces.argtypes = [vp, C.c_int, vp, vp]
+    for name in ("bh_posterior_create", "bh_posterior_load", "bh_posterior_columns", "bh_posterior_hist", "bh_posterior_interfaces"):
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
@@ -170,6 +179,9 @@ DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_e
                  "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace")
 # include/bh_engine_sites.h: many stations at once (site-indexed observed data)
 SITE_SYMBOLS = ("bh_sites_set", "bh_evaluate_sites")
+# include/bh_engine_posterior.h: posterior velocity-depth summaries of many sites (bayhunter_amd/posterior.py)
+POSTERIOR_SYMBOLS = ("bh_posterior_create", "bh_posterior_destroy", "bh_posterior_load", "bh_posterior_columns",
+                     "bh_posterior_hist", "bh_posterior_interfaces")
 
 
 def _f64(a):

@@ -1,0 +1,329 @@
+"""Posterior velocity-depth summaries of many sites on the GPU (include/bh_engine_posterior.h).
+
+`posterior_models` returns per site what BayHunter's ModelMatrix.get_singlemodels returns (mean, median, minmax,
+stdminmax, mode, minmisfit) plus `count`, `mode_valid` and `invalid_rows`; `posterior_hist2d` returns the numbers of the
+2-D posterior plot (the vs-depth histogram and the histogram of interface depths).  Rows are the reference's
+[vs_1..vs_n, z_1..z_n, NaN...], float32 or float64, numpy arrays or device torch tensors, with a site index each.
+
+Exactness ("Posterior summaries"): min, max, median, counts, histograms and mode are the reference's bits.
+The mean and std come from exact integer sums formed on the device (every interpolated vs is an integer multiple of the
+column's lowest set bit); they are rounded here from Python integers, within one rounding of the exact values.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import engine as E
+
+VS_INTERVAL = 0.025  # km/s: the mode's vs bin width (get_singlemodels) and the 2-D plot's
+MAX_COUNTS = 1 << 27  # BH_POSTERIOR_MAXCOUNTS: histogram cells of one call
+
+
+def default_dep_int():
+    return np.linspace(0, 100, 201)
+
+
+def _ptr(a):
+    return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def _keys_to_values(k, keys32):
+    """The inverse of the ordered-key map of include/bh_engine_posterior.h."""
+    k = np.asarray(k, dtype=np.uint64)
+    if keys32:
+        u = k.astype(np.uint32)
+        neg = (u >> np.uint32(31)) == 0
+        u = np.where(neg, ~u, u & np.uint32(0x7fffffff)).astype(np.uint32)
+        return u.view(np.float32).astype(np.float64)
+    neg = (k >> np.uint64(63)) == 0
+    u = np.where(neg, ~k, k & np.uint64(0x7fffffffffffffff)).astype(np.uint64)
+    return u.view(np.float64)
+
+
+def depth_bins(samples, edges):
+    """numpy.histogram2d's depth bin of every sample (searchsorted 'right', the last edge into the last bin); -1 outside."""
+    samples, edges = np.asarray(samples, np.float64), np.asarray(edges, np.float64)
+    idx = np.searchsorted(edges, samples, side="right")
+    idx[samples == edges[-1]] -= 1
+    return np.where((idx >= 1) & (idx <= edges.size - 1), idx - 1, -1).astype(np.int32)
+
+
+def vs_round(v):
+    """Down to the 0.025 km/s grid, as the reference's Plotting.vs_round rounds."""
+    fl = np.floor(v)
+    return fl + np.round(40 * (v - fl)) / 40
+
+
+def hist2d_edges(vmin, vmax, dep_int=None):
+    """The 2-D plot's default binning (_plot_bestmodels_hist): (depth sampling, depth edges) from dep_int, and for a
+    site's vs range [vmin, vmax] (over the vs sampled at that depth sampling) the vs edges -- 0.025 km/s steps from two
+    steps below vs_round(vmin) to below vs_round(vmax) + 3 steps."""
+    if dep_int is None:
+        samples, depbins = np.linspace(0, 100, 201), np.linspace(0, 100, 101)
+    else:
+        dep_int = np.asarray(dep_int, np.float64)
+        step = dep_int[1] - dep_int[0]
+        samples = np.arange(dep_int[0], dep_int[-1] + step / 2., step / 2.)
+        depbins = np.arange(0, int(np.ceil(dep_int.max())) + 2 * step, step)
+    if vmin is None:
+        return samples, depbins, None
+    lo = vs_round(vmin) - 2 * VS_INTERVAL
+    hi = vs_round(vmax) + 3 * VS_INTERVAL
+    return samples, depbins, np.arange(lo, hi, VS_INTERVAL)
+
+
+def stepmodel(row):
+    """The step model of one row (Model.get_stepmodel: vs_step, dep_step), in the row's dtype where the reference keeps it."""
+    row = np.asarray(row)
+    vals = row[~np.isnan(row)]
+    n = vals.size // 2
+    vs, z = vals[:n], vals[n:]
+    zd = (z[:-1] + z[1:]) / row.dtype.type(2)
+    h = np.zeros(n)
+    h[:n - 1] = np.diff(np.concatenate((np.zeros(1), zd.astype(np.float64))))
+    dep = np.cumsum(h)
+    dep_step = np.concatenate((np.zeros(1), np.repeat(dep, 2)[:-1]))
+    dep_step[-1] = max(150.0, dep_step[-1] * 2.5)
+    return np.repeat(vs, 2), dep_step
+
+
+class _Loaded(object):
+    """Rows loaded into a bh_posterior handle (one per call of the public functions)."""
+
+    def __init__(self, models, site, engine, nsites=None):
+        self.eng = engine if engine is not None else E.default_engine(0)
+        L = self.eng._L
+        self._L = L
+        h = C.c_void_p()
+        self.eng._check(L.bh_posterior_create(self.eng._h, C.byref(h)))
+        self._p = h
+        self._keep = []
+        try:
+            import torch
+            is_t = isinstance(models, torch.Tensor)
+        except ImportError:
+            is_t = False
+        if is_t:
+            if models.dim() != 2 or models.dtype not in (torch.float32, torch.float64) or not models.is_cuda:
+                raise ValueError("models must be a 2-D float32/float64 device tensor")
+            if models.stride(1) != 1:
+                models = models.contiguous()
+            N, W = models.shape
+            ld = models.stride(0)
+            elem = models.element_size()
+            if site is not None:
+                site = torch.as_tensor(site, device=models.device).to(torch.int32).contiguous()
+                if nsites is None:
+                    nsites = int(site.max().item()) + 1 if site.numel() else 1
+            self._keep += [models, site]
+            mptr = C.c_void_p(models.data_ptr())
+            sptr = C.c_void_p(site.data_ptr()) if site is not None else None
+            mem, stream = E.DEVICE, C.c_void_p(torch.cuda.current_stream(models.device).cuda_stream)
+            self.dtype = np.float32 if elem == 4 else np.float64
+        else:
+            models = np.asarray(models)
+            if models.ndim != 2 or models.dtype not in (np.float32, np.float64):
+                raise ValueError("models must be a 2-D float32 or float64 array")
+            models = np.ascontiguousarray(models)
+            N, W = models.shape
+            ld, elem = W, models.itemsize
+            if site is not None:
+                site = np.ascontiguousarray(site, dtype=np.int32)
+                if site.shape != (N,):
+                    raise ValueError("site must have one index per row")
+                if nsites is None:
+                    nsites = int(site.max()) + 1 if N else 1
+            self._keep += [models, site]
+            mptr, sptr = _ptr(models), _ptr(site)
+            mem, stream = E.HOST, None
+            self.dtype = models.dtype.type
+        if W % 2:
+            raise ValueError("rows are 2*ML values wide")
+        self.S = int(nsites) if nsites is not None else 1
+        self.ML = W // 2
+        self.rows = np.zeros(self.S, np.int64)
+        self.invalid = np.zeros(self.S, np.int64)
+        dropped = np.zeros(1, np.int64)
+        self.eng._check(L.bh_posterior_load(h, mem, stream, elem, N, self.ML, ld, mptr, sptr, self.S,
+                                            _ptr(self.rows), _ptr(self.invalid), _ptr(dropped)))
+        self.dropped = int(dropped[0])
+        self.N = N
+        self._keep = None
+
+    def close(self):
+        if self._p:
+            self._L.bh_posterior_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def columns(self, dep, median=True):
+        dep = np.ascontiguousarray(dep, np.float64)
+        D, S = dep.size, self.S
+        out = dict(kmin=np.zeros((S, D), np.uint64), kmax=np.zeros((S, D), np.uint64), scale=np.zeros((S, D), np.int32),
+                   x0=np.zeros((S, D), np.int64), exact=np.zeros((S, D), np.int32), sums=np.zeros((S, D, 6), np.uint64),
+                   median=np.zeros((S, D, 2), np.uint64) if median else None)
+        k32 = np.zeros(1, np.int32)
+        self.eng._check(self._L.bh_posterior_columns(self._p, D, _ptr(dep), _ptr(out["kmin"]), _ptr(out["kmax"]),
+                                                     _ptr(out["scale"]), _ptr(out["x0"]), _ptr(out["exact"]),
+                                                     _ptr(out["sums"]), _ptr(out["median"]), _ptr(k32)))
+        out["min"] = _keys_to_values(out["kmin"], False).reshape(S, D)
+        out["max"] = _keys_to_values(out["kmax"], False).reshape(S, D)
+        out["keys32"] = bool(k32[0])
+        return out
+
+    def hist(self, dep, dbin, nd, edges_per_site, argmax=False):
+        dep = np.ascontiguousarray(dep, np.float64)
+        dbin = np.ascontiguousarray(dbin, np.int32)
+        nb = np.array([e.size - 1 for e in edges_per_site], np.int64)
+        edge_off = np.concatenate(([0], np.cumsum(nb + 1))).astype(np.int64)
+        edges = np.ascontiguousarray(np.concatenate(edges_per_site), np.float64)
+        counts = np.zeros(int(np.sum(nb * nd)), np.uint32)
+        am = np.zeros((self.S, nd), np.int32) if argmax else None
+        self.eng._check(self._L.bh_posterior_hist(self._p, dep.size, _ptr(dep), _ptr(dbin), int(nd), _ptr(edge_off),
+                                                  _ptr(edges), _ptr(counts), _ptr(am)))
+        off = np.concatenate(([0], np.cumsum(nb * nd)))
+        return [counts[off[s]:off[s + 1]].reshape(nb[s], nd) for s in range(self.S)], am
+
+    def interfaces(self, edges):
+        edges = np.ascontiguousarray(edges, np.float64)
+        counts = np.zeros((self.S, edges.size - 1), np.uint32)
+        self.eng._check(self._L.bh_posterior_interfaces(self._p, edges.size, _ptr(edges), _ptr(counts)))
+        return counts
+
+
+def _mean_std(n, sums, scale, x0):
+    """mean and population std of one column from its exact integer sums (include/bh_engine_posterior.h)."""
+    s = [int(v) for v in sums]
+    S1 = s[0] + (s[1] << 32)
+    S2 = s[2] + (s[3] << 32) + (s[4] << 64) + (s[5] << 96)
+    L, X0 = int(scale), int(x0)
+    num = S1 + n * X0                                   # sum(v) * 2^-L
+    mean = (num << L) / n if L >= 0 else num / (n << -L)  # int / int: correctly rounded
+    V = n * S2 - S1 * S1                                # n^2 var * 2^-2L, >= 0
+    if V == 0:
+        return mean, 0.0
+    k = max(0, (120 - V.bit_length()) // 2 + 1)
+    q = math.isqrt(V << (2 * k))                        # floor(sqrt(V) * 2^k), >= 2^60
+    e = L - k
+    std = (q << e) / n if e >= 0 else q / (n << -e)
+    return mean, std
+
+
+def _site_groups(misfits, site, N):
+    if misfits is None:
+        return None
+    try:
+        import torch
+        if isinstance(misfits, torch.Tensor):
+            misfits = misfits.detach().cpu().numpy()
+        if isinstance(site, torch.Tensor):
+            site = site.detach().cpu().numpy()
+    except ImportError:
+        pass
+    misfits = np.asarray(misfits, np.float64).reshape(-1)
+    if misfits.size != N:
+        raise ValueError("one misfit per row")
+    return misfits, (np.zeros(N, np.int64) if site is None else np.asarray(site).astype(np.int64))
+
+
+def _row(models, i):
+    r = models[i]
+    if hasattr(r, "detach"):
+        r = r.detach().cpu().numpy()
+    return np.asarray(r)
+
+
+def posterior_models(models, site=None, dep_int=None, misfits=None, engine=None, nsites=None):
+    """get_singlemodels of every site: a list of dicts (one dict when site is None).  Keys: mean, median, minmax,
+    stdminmax (each (values, dep_int)), mode ((vs_mode, dep_center); NaN and mode_valid False where the reference raises,
+    i.e. the site's vs range is below one 0.025 km/s bin), minmisfit (with misfits), count, mode_valid, invalid_rows."""
+    dep = default_dep_int() if dep_int is None else np.ascontiguousarray(dep_int, np.float64)
+    ld = _Loaded(models, site, engine, nsites)
+    try:
+        col = ld.columns(dep, median=True)
+        S, D = ld.S, dep.size
+        vmin_s = np.array([col["min"][s].min() if ld.rows[s] else np.nan for s in range(S)])
+        vmax_s = np.array([col["max"][s].max() if ld.rows[s] else np.nan for s in range(S)])
+        nbins = np.zeros(S, np.int64)
+        edges = []
+        for s in range(S):
+            if ld.rows[s]:
+                nbins[s] = int((vmax_s[s] - vmin_s[s]) / VS_INTERVAL)
+        if int(np.sum(nbins)) * (D - 1) > MAX_COUNTS:   # (before numpy builds the edges of a wild range)
+            raise E.EngineError("engine call failed (%d): the mode histogram would hold %d cells, above "
+                                "BH_POSTERIOR_MAXCOUNTS (%d): is the vs range sane?" % (E.BH_EINVAL, int(np.sum(nbins)) * (D - 1), MAX_COUNTS))
+        for s in range(S):
+            edges.append(np.linspace(vmin_s[s], vmax_s[s], nbins[s] + 1) if nbins[s] > 0 else np.array([0.0, 1.0]))
+        dbin = depth_bins(dep, dep)
+        _, am = ld.hist(dep, dbin, D - 1, edges, argmax=True)
+        med = _keys_to_values(col["median"].reshape(-1), col["keys32"]).reshape(S, D, 2)
+    finally:
+        ld.close()
+    groups = _site_groups(misfits, site, ld.N)
+    dep_center = (dep[:-1] + dep[1:]) / 2.
+    out = []
+    for s in range(S):
+        n = int(ld.rows[s])
+        r = dict(count=n, invalid_rows=int(ld.invalid[s]), mode_valid=bool(nbins[s] > 0))
+        if n:
+            ms = [_mean_std(n, col["sums"][s, j], col["scale"][s, j], col["x0"][s, j]) for j in range(D)]
+            mean = np.array([m for m, _ in ms])
+            std = np.array([v for _, v in ms])
+            lo, hi = med[s, :, 0], med[s, :, 1]
+            median = (lo + hi) / 2. if n % 2 == 0 else lo.copy()
+            vmin, vmax = col["min"][s], col["max"][s]
+        else:
+            mean = std = median = vmin = vmax = np.full(D, np.nan)
+        r["mean"] = (mean, dep)
+        r["median"] = (median, dep)
+        r["minmax"] = (np.array((vmin, vmax)), dep)
+        r["stdminmax"] = (np.array((mean - std, mean + std)), dep)
+        if r["mode_valid"]:
+            e = edges[s]
+            vs_center = (e[:-1] + e[1:]) / 2.
+            r["mode"] = (vs_center[am[s]], dep_center)
+        else:
+            r["mode"] = (np.full(D - 1, np.nan), dep_center)
+        if groups is not None:
+            mis, sidx = groups
+            idx = np.flatnonzero(sidx == s)
+            if idx.size:
+                r["minmisfit"] = stepmodel(_row(models, idx[np.argmin(mis[idx])]))
+        out.append(r)
+    return out[0] if site is None else out
+
+
+def posterior_hist2d(models, site=None, dep_int=None, vs_edges=None, dep_edges=None, engine=None, nsites=None):
+    """The 2-D posterior plot's numbers (_plot_bestmodels_hist) of every site: a list of dicts (one dict when site is
+    None) with counts [nvs, ndep] of the vs sampled at `samples` over vs_edges x dep_edges (numpy.histogram2d), and
+    interfaces [ndep] = numpy.histogram of the interface depths over dep_edges.  The defaults are the plot's
+    (hist2d_edges): dep_int None -> 0.5 km sampling of 0..100 km and 1 km depth bins; vs edges from each site's range."""
+    samples, depbins, _ = hist2d_edges(None, None, dep_int)
+    if dep_edges is not None:
+        depbins = np.asarray(dep_edges, np.float64)
+    ld = _Loaded(models, site, engine, nsites)
+    try:
+        S = ld.S
+        if vs_edges is None:
+            col = ld.columns(samples, median=False)
+            vs_e = []
+            for s in range(S):
+                if not ld.rows[s]:
+                    vs_e.append(np.array([0.0, 1.0]))
+                    continue
+                vs_e.append(hist2d_edges(col["min"][s].min(), col["max"][s].max(), dep_int)[2])
+        else:
+            vs_e = [np.asarray(vs_edges, np.float64)] * S
+        counts, _ = ld.hist(samples, depth_bins(samples, depbins), depbins.size - 1, vs_e)
+        inter = ld.interfaces(depbins)
+    finally:
+        ld.close()
+    out = [dict(counts=counts[s], vs_edges=vs_e[s], dep_edges=depbins, samples=samples, interfaces=inter[s],
+                count=int(ld.rows[s]), invalid_rows=int(ld.invalid[s])) for s in range(S)]
+    return out[0] if site is None else out

@@ -164,3 +164,25 @@ def save_final_distribution(datapath, maxmodels=200000, dev=0.05, rstate=None):
     for k in ("models", "likes", "misfits", "noise", "vpvs"):
         np.save(op.join(datapath, "c_%s" % k), out[k][keep])
     return outliers
+
+
+def posterior_from_storage(datapaths, dep_int=None, engine=None):
+    """Posterior velocity-depth summaries of many sites in one GPU call (bayhunter_amd.posterior.posterior_models):
+    datapaths[s] is site s's data directory after save_final_distribution (c_models.npy; c_misfits.npy, its last column
+    the joint misfit, for `minmisfit`).  Rows of different widths are padded with NaN.  Returns one dict per site."""
+    from .posterior import posterior_models
+    models = [np.load(op.join(p, "c_models.npy")) for p in datapaths]
+    misfits = []
+    for p, m in zip(datapaths, models):
+        f = op.join(p, "c_misfits.npy")
+        misfits.append(np.load(f).reshape(len(m), -1)[:, -1] if op.exists(f) else None)
+    W = max(m.shape[1] for m in models)
+    rows = np.full((sum(len(m) for m in models), W), np.nan)
+    site = np.zeros(len(rows), np.int32)
+    start = 0
+    for s, m in enumerate(models):
+        rows[start:start + len(m), :m.shape[1]] = m
+        site[start:start + len(m)] = s
+        start += len(m)
+    mis = None if any(x is None for x in misfits) else np.concatenate(misfits)
+    return posterior_models(rows, site=site, dep_int=dep_int, misfits=mis, engine=engine, nsites=len(datapaths))
