@@ -110,7 +110,6 @@ struct bh_engine {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipStream_t aux2 = nullptr;            // second dispersion target of a lane-per-model call runs here, beside the first
     hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;
-    int look_r = 0, look_l = 0;            // BH_SWD_LOOK_R / BH_SWD_LOOK_L env (experiment switches): trials per round by wave type
     bool overlap_rf = true;                // BH_NO_OVERLAP env turns it off (A/B testing)
     int rf_lds_beside_swd = 40 * 1024;     // BH_RF_LDS_BESIDE env (bytes; experiment switch), see launch_rf
     // co-resident receiver function (see bh_evaluate_batch): the dispersion kernel counts its started workgroups here
@@ -118,7 +117,6 @@ struct bh_engine {
     unsigned started_expected = 0;         // value after every launch enqueued so far has started
     int swd_prio_low = 1;                  // BH_SWD_PRIO_LOW env: dispersion wavefronts' low priority while RF wavefronts run beside them
     SwdPairWork pairwork{};                // SIMD-pairing order of the group kernel (bh_device.h)
-    bool no_pair = false;                  // BH_SWD_NO_PAIR env: order by depth only (A/B testing)
     int swd_trials = 0;                    // bh_engine_set_swd_trials: trials per round of the trial-per-lane kernel (0 = by the call's shape)
     int last_swd_kernel = -1;              // bh_engine_last_swd_kernel
     SwdLaunchInfo last_swd{};              // of the most recent group-kernel launch (workgroups == 0: none)
@@ -142,7 +140,6 @@ struct bh_engine {
     // instrumentation
     bool timing = false, counting = false;
     bool no_mfma = false; // BH_NO_MFMA env: Gauss law through the in-kernel mat-vec (A/B testing)
-    bool no_order = false; // BH_NO_ORDER env: wavefronts take the models in batch order (A/B testing)
     bool as_given = false; // bh_engine_set_model_order(e, 0): the caller's batches need no sorting by depth
     int force_group = 0; // BH_SWD_GROUP env / bh_engine_set_swd_group: 0 = choose automatically
     int force_look = 0;  // BH_SWD_LOOKAHEAD env / bh_engine_set_swd_lookahead: 0 = choose automatically
@@ -155,7 +152,6 @@ struct bh_engine {
     uint64_t guard_total[BH_MAX_TARGETS] = {0}; // guarded models of retired buffers (the live buffer carries its own running sum)
     bool guard_fresh = true;     // the guard buffer is new: zero its cumulative words as well
     bool guard_last = false;     // the most recent dispersion call had targets with the short refinement (its counts are in the buffer)
-    int love_inlook = 0; // BH_SWD_LOVE_INLOOK env (experiment switch): Love trials inside a lane group, 0 = automatic
     // one EventSet per timed *_batch call since the last bh_timing_reset()
     struct EventSet {
         hipEvent_t ev[8];
@@ -344,23 +340,25 @@ void call_end(bh_engine *e, hipStream_t st)
     if (s) (void)hipEventRecord(s->ev[7], st);
 }
 
-int swd_supported(bh_engine *e, int K, int iwave, int mode, int flsph)
+// igr: 0 is a phase velocity; any value > 0 a group velocity (surfdisp96.f:77, :232, :282), normalised here to BH_VEL_GROUP
+int swd_supported(bh_engine *e, int K, int iwave, int &igr, int mode, int flsph)
 {
     if (K < 0 || K > BH_MAX_PERIODS) return fail(e, BH_EINVAL, "K must be 0..60 (surfdisp96.f:61-62)");
     if (iwave != BH_WAVE_LOVE && iwave != BH_WAVE_RAYLEIGH) return fail(e, BH_EINVAL, "iwave must be 1 (Love) or 2 (Rayleigh)");
+    if (igr < 0) return fail(e, BH_EINVAL, "igr must be 0 (phase velocity) or > 0 (group velocity)");
     if (mode < 1 || mode > 16) return fail(e, BH_EINVAL, "mode must be 1..16");
     if (flsph != 0 && flsph != 1) return fail(e, BH_EINVAL, "flsph must be 0 or 1");
+    igr = igr > 0 ? BH_VEL_GROUP : BH_VEL_PHASE;
     return BH_OK;
 }
 
 struct SwdJob {
-    int K, iwave, igr, ldv;
+    int K, iwave, igr, ldv; // igr: BH_VEL_PHASE or BH_VEL_GROUP (swd_supported)
     const double *periods_dev;
     double *vel;
     int32_t *err;
     int mode = 1;
     int flsph = 0;
-    double *first = nullptr; // igr = 2 (launch_swd_jobs: the chain of a group velocity's first roots): SwdKernelArgs::first
 };
 
 int swd_counter(bh_engine *e, hipStream_t st, unsigned long long **out)
@@ -403,6 +401,249 @@ int guard_space(bh_engine *e, hipStream_t st, int B, int32_t **counts, int32_t *
     return BH_OK;
 }
 
+// which jobs take the short refinement: fundamental-mode phase velocities; with BH_SEARCH_FAST_RAYLEIGH only the Rayleigh ones
+bool takes_fast(int search, const SwdJob &J)
+{
+    return J.igr == BH_VEL_PHASE && J.mode <= 1 && (search == BH_SEARCH_FAST || (search == BH_SEARCH_FAST_RAYLEIGH && J.iwave == BH_WAVE_RAYLEIGH));
+}
+
+// processing order of the models: the caller's; deepest first (models of more than Lcut layers a class of their own:
+// SwdMultiArgs::split); by predicted search length (trial-per-lane kernel, PairOrderTarget); paired over the SIMDs (SwdPairWork)
+enum SwdOrder { ORDER_NONE, ORDER_DEPTH, ORDER_LENGTH, ORDER_PAIR };
+
+// What the launches of one dispersion call do.  The call's targets are its jobs with K > 0, in job order.
+struct SwdPlan {
+    bool first_roots[BH_MAX_TARGETS]; // per job: the chain of first roots of a group velocity split in two launches
+    int nsplit;                        // jobs that are
+    int ntargets, kmax, maxmode;
+    bool any_sphere;
+    int typ_layers;                    // typical depth the lanes per model were chosen for (0: unknown, or ignored)
+    int kernel;                        // BH_KERNEL_LEAN / GROUP / LANE
+    int G, lean_trials;                // lanes per model; trials per round of the trial-per-lane kernel (>= 4: it runs)
+    int order, Lcut;                   // SwdOrder; Lcut < Lmax: two depth classes
+    int len_mpw, len_xcd;              // ORDER_LENGTH: models per wavefront and wavefronts per workgroup of the XCD blocks (0: none)
+    bool any_fast, farith, adapt_ok;   // some target takes the short refinement; its fast arithmetic; kernel may size lanes per model
+    // per target: its job, trials per round, Love trials inside a lane group, and the trials of the group kernel's plan
+    // (BH_DEBUG_PLAN prints these; the trial-per-lane kernel's differ)
+    int job[BH_MAX_TARGETS], look[BH_MAX_TARGETS], inlook[BH_MAX_TARGETS], look_group[BH_MAX_TARGETS];
+    // per target: takes the short refinement; a phase velocity that keeps the reference's sequence in a launch with it
+    bool fast[BH_MAX_TARGETS], refseq[BH_MAX_TARGETS];
+};
+
+// The plan of one dispersion call, from the engine's settings, the experiment switches (bh_tuning.h) and the call's shape:
+// no HIP call, no allocation.  typ_given: the batch's typical layer count (0 = unknown).
+SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, const SwdJob *jobs)
+{
+    const BhTuning &tun = bh_tuning();
+    SwdPlan p{};
+    p.maxmode = 1;
+    int iw[BH_MAX_TARGETS], nfast = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const SwdJob &J = jobs[j];
+        if (J.K == 0) continue;
+        // Group velocities of the fundamental mode: two launches.  The root at t/(1+h) of period k + 1 starts from the root at
+        // t/(1+h) of period k (surfdisp96.f:262-266); the root at t/(1-h) starts from the root at t/(1+h) of ITS OWN period
+        // (:282-287) and nothing starts from it.  One search after the other is a chain of 2 K dependent roots; here the target
+        // first runs as the chain of its K first roots (beside the call's other targets, in whatever kernel the call takes,
+        // every root stored unrounded in the output row), then a launch of B x K independent searches (one lane each, or up to
+        // 16 trial lanes while that still fits the chip at once: launch_second_roots) finds the second roots and puts the group
+        // velocities in their place.  The same searches on the same values: the same bits (tests/test_gpu_swd.py's golden rows
+        // and oracle comparisons run through here).  Measured, one launch -> two (ms per call): one model 2.26 -> 1.43; two
+        // targets x 256 / 1024 / 4096 / 8192 / 16 384 / 65 536 models: 2.64 -> 1.90, 2.91 -> 2.10, 5.51 -> 4.64, 11.2 -> 8.09,
+        // 17.2 -> 12.5, 31.5 -> 29.9 (the second roots are a third of the evaluations but run as full wavefronts of independent
+        // searches, one lane each; in one launch they sit in the chain's wavefronts, whose lanes wait for each other's searches).
+        // bh_tuning.h swd_gsplit: the largest call in (model, period) pairs that is split (0: none).
+        p.first_roots[j] = J.igr == BH_VEL_GROUP && J.mode <= 1 && tun.swd_gsplit > 0 && (long)B * J.K <= (long)tun.swd_gsplit;
+        p.nsplit += p.first_roots[j] ? 1 : 0;
+        const int t = p.ntargets++;
+        p.job[t] = j;
+        iw[t] = J.iwave;
+        p.fast[t] = takes_fast(e->swd_search, J);
+        nfast += p.fast[t] ? 1 : 0;
+        p.kmax = J.K > p.kmax ? J.K : p.kmax;
+        p.maxmode = J.mode > p.maxmode ? J.mode : p.maxmode;
+        p.any_sphere = p.any_sphere || J.flsph == 1;
+    }
+    const int nlive = p.ntargets;
+    if (nlive == 0) return p;
+    // Typical depth of the batch (0 = unknown: the array capacity is planned for).  Ignored where every (model, target) gets a
+    // wavefront of its own anyway (at most 2048 of them: the chip's two per SIMD) -- the regime of the chains' speculative
+    // windows.  There a depth class of its own for the shallow bulk buys nothing (the models per wavefront cannot grow), the
+    // narrower lane groups cost a second pass over the layers and seven instead of four trials per round more transitions:
+    // measured on windows of 1016 models of 3-9 layers in arrays of 21 (c4): 1.50 ms without the hint, 1.70-1.83 ms with it.
+    p.typ_layers = ((long)nlive * B <= 2048 && tun.swd_hint_always == 0) ? 0 : typ_given;
+    int look[BH_MAX_TARGETS];
+    {
+        // lanes per model follow the TYPICAL depth of the batch (deeper models take further passes over
+        // their layers): known for host batches, a caller's hint for device-resident ones, else Lmax
+        int Lplan = p.typ_layers > 0 ? p.typ_layers : Lmax;
+        if (Lplan > Lmax) Lplan = Lmax;
+        bh_swd_plan(B, Lplan, nlive, iw, e->force_group, &p.G, look);
+        if (e->force_look > 0)
+            for (int t = 0; t < nlive; ++t) look[t] = e->force_look; // (one lane per model: rounded down to a power of two)
+    }
+    const size_t lds_cap = 64 * 1024;
+    if (p.G <= 1 && bh_swd_lds_bytes(Lmax, p.kmax, p.maxmode) > lds_cap) p.G = 2; // deep models / many periods
+    // The trial-per-lane kernel (swd_lean.hip): every target of the call takes the short refinement with the fast arithmetic, in
+    // calls of up to 2^20 (model, target) pairs (with four trials per round it stays ahead of one lane per evaluation -- swd_kernel's
+    // FA builds -- as far as measured: c2 at B = 65 536 7.99 against 8.44 ms).
+    {
+        bool all = e->swd_arith == BH_ARITH_FAST && e->swd_search == BH_SEARCH_FAST && e->force_group == 0 && e->force_look == 0 &&
+                   tun.swd_look_r == 0 && tun.swd_look_l == 0 && tun.swd_no_lean == 0 && p.maxmode <= 1 && p.kmax <= BH_MAX_PERIODS &&
+                   Lmax <= 32 && (long)B * nlive <= (tun.swd_lean_pairs > 0 ? (long)tun.swd_lean_pairs : (1L << 20));
+        for (int t = 0; t < nlive; ++t) all = all && jobs[p.job[t]].igr == BH_VEL_PHASE;
+        if (all) p.lean_trials = e->swd_trials > 0 ? e->swd_trials : bh_swd_lean_trials(B, nlive);
+        if (p.lean_trials >= 4 && bh_swd_lean_lds_bytes(p.lean_trials, Lmax, p.kmax) > lds_cap) p.lean_trials = 0; // (a workgroup's LDS)
+    }
+    const bool lean = p.lean_trials >= 4;
+    if (lean && p.G <= 1) p.G = bh_swd_pick_group(B, nlive, Lmax); // (the launch is set up where the group kernel's is)
+    p.kernel = p.G <= 1 ? BH_KERNEL_LANE : (lean ? BH_KERNEL_LEAN : BH_KERNEL_GROUP);
+    // processing order: deepest models first, wavefronts of (nearly) one depth
+    const bool ordered = B > 1 && tun.no_order == 0 && !e->as_given;
+    const bool shallow_bulk = p.typ_layers > 0 && p.typ_layers + 2 < Lmax;
+    // One depth class, lanes per model > 1: the launcher orders the models itself, by predicted search length and paired
+    // over the SIMDs (SwdPairWork); mixed depths are ordered by depth there as well.
+    // Measured (bench.py c2, B = 2048 ... 4096, same session with / without): -3 % at 4096 and -4 % at 3800, where the
+    // launch nearly fills two wavefronts per SIMD and the Rayleigh wavefronts (look-ahead 2) outnumber the Love ones
+    // (trials inside the lane groups) 7 : 3; neutral at 3500; +2.5 % at 2048 / 3072, where the planner gives both targets
+    // the same look-ahead and every SIMD holds one Rayleigh and one Love wavefront (why the one-to-one mix loses is not
+    // understood).  Hence: two targets, >= 7/8 of two wavefronts per SIMD, unequal wavefront counts.
+    if (ordered && !lean && tun.swd_no_pair == 0 && p.G > 1 && nlive == 2 && bh_pair_order_fits(B) && !shallow_bulk) {
+        long plan_waves = 0, wmin = 0, wmax = 0;
+        for (int t = 0; t < nlive; ++t) {
+            int J = look[t] > 1 ? look[t] : 1;
+            while (J > 1 && p.G * J > 64) --J;
+            const int mpw = 64 / (p.G * J);
+            const long w = (B + mpw - 1) / mpw;
+            plan_waves += w;
+            wmin = (t == 0 || w < wmin) ? w : wmin;
+            wmax = w > wmax ? w : wmax;
+        }
+        const int pair_min = tun.swd_pair_minwaves;
+        if (plan_waves >= (pair_min >= 0 ? pair_min : 7 * (long)e->pairwork.ncu) && (pair_min >= 0 || 2 * wmax >= 3 * wmin))
+            p.order = ORDER_PAIR;
+    }
+    p.Lcut = Lmax;
+    if (ordered && p.order != ORDER_PAIR) {
+        if (lean && bh_pair_order_fits(B) && tun.swd_lean_no_sort == 0) {
+            // The trial-per-lane kernel: the models in the order of their PREDICTED search length, longest first (mixed depths:
+            // deepest first) -- wavefronts of like models idle fewer rounds on finished ones, and the long wavefronts are
+            // dispatched first with the short ones filling the launch's tail (c2: 0.79 -> 0.72 ms).  Scheduling only.
+            // Sorted inside eight blocks of the batch, block x for the wavefronts of XCD x, where the shapes divide: each XCD's L2
+            // then fetches an eighth of the model arrays instead of all of them (HBM reads of the launch 10.7 -> 1.9 MB at c2).
+            p.order = ORDER_LENGTH;
+            p.len_mpw = 1;
+            const int mpw = BH_WAVE / p.lean_trials, per_wg = (nlive == 2) ? 2 : 4;
+            if (tun.swd_lean_xcd != 0 && tun.swd_lean_r < 4 && tun.swd_lean_l < 4 && B % mpw == 0 && B % 8 == 0 && (B / mpw) % (8 * per_wg) == 0) {
+                p.len_mpw = mpw;
+                p.len_xcd = per_wg;
+            }
+        } else {
+            // LDS rows for the bulk of the batch: its typical depth plus a margin; deeper models get their own launch
+            p.order = ORDER_DEPTH;
+            if (shallow_bulk) p.Lcut = p.typ_layers + 2;
+        }
+    }
+    // trials per round and sequence of every target
+    p.any_fast = nfast > 0;
+    p.farith = e->swd_arith == BH_ARITH_FAST;
+    p.adapt_ok = e->force_group == 0 && e->force_look == 0 && tun.swd_look_r == 0 && tun.swd_look_l == 0;
+    for (int t = 0; t < nlive; ++t) {
+        // Where some phase-velocity targets take the short refinement and others keep the reference's sequence
+        // (BH_SEARCH_FAST_RAYLEIGH with Love targets in the call) the ONE launch of the group kernel takes the build with both
+        // sequences and the targets say which is theirs (two launches side by side were measured: the Rayleigh / Love pairs on
+        // the SIMDs are lost, c4 1.37 -> 1.58 ms per window).
+        p.refseq[t] = nfast > 0 && jobs[p.job[t]].igr == BH_VEL_PHASE && !p.fast[t];
+        if (p.kernel == BH_KERNEL_LANE) { // (a launch per target: one lane per trial)
+            p.look[t] = look[t] > 1 ? look[t] : 1;
+            continue;
+        }
+        // Love: two trials inside each lane group pay while the group count is small (measured: wavefront
+        // 7 % shorter at look = 1, neutral at 2, slower beyond)
+        p.inlook[t] = (iw[t] != BH_WAVE_LOVE) ? 1 : (tun.swd_love_inlook > 0 ? tun.swd_love_inlook : (look[t] <= 2 ? 2 : 1));
+        int L = look[t];
+        if (tun.swd_look_r > 0 && iw[t] == BH_WAVE_RAYLEIGH) L = tun.swd_look_r;
+        if (tun.swd_look_l > 0 && iw[t] == BH_WAVE_LOVE) L = tun.swd_look_l;
+        p.look_group[t] = L;
+        if (lean) {
+            L = p.lean_trials;
+            if (iw[t] == BH_WAVE_RAYLEIGH && tun.swd_lean_r >= 4) L = tun.swd_lean_r;
+            if (iw[t] == BH_WAVE_LOVE && tun.swd_lean_l >= 4) L = tun.swd_lean_l;
+        }
+        p.look[t] = L;
+    }
+    return p;
+}
+
+// One dispersion call as it is launched: its plan, the model arrays and work space the launches read.
+struct SwdCall {
+    bh_engine *e; hipStream_t st;
+    int B, Lmax; const Staged &m; ptrdiff_t sl, sb;
+    const SwdJob *jobs; const SwdPlan &p;
+    const double *sph = nullptr;         // flsph = 1: earth-flattened h, vp, vs, Love rho, Rayleigh rho, [Lmax][B] each
+    double *first[BH_MAX_TARGETS] = {};  // per job of the chain of first roots: where the kernel keeps them (SwdKernelArgs::first)
+    const int32_t *perm = nullptr, *split = nullptr;
+    unsigned long long *counter = nullptr;
+    int32_t *gcounts = nullptr, *glists = nullptr; // the guard of the short refinement (guard_space)
+};
+
+// The kernel arguments of job j as a target: its model arrays (the batch's, or the flattened copies with the density of its wave
+// type), periods and outputs.  igr = 2 tells the kernels that a job is the chain of first roots (SwdKernelArgs::first).
+SwdTarget swd_target(const SwdCall &c, int j)
+{
+    const SwdJob &J = c.jobs[j];
+    SwdTarget t{};
+    t.iwave = J.iwave; t.igr = c.p.first_roots[j] ? 2 : J.igr; t.K = J.K; t.ldv = J.ldv; t.mode = J.mode;
+    t.h = c.m.h; t.vp = c.m.vp; t.vs = c.m.vs; t.rho = c.m.rho; t.sl = c.sl; t.sb = c.sb;
+    if (J.flsph == 1) {
+        const size_t ne = (size_t)c.Lmax * c.B;
+        t.h = c.sph; t.vp = c.sph + ne; t.vs = c.sph + 2 * ne; t.rho = c.sph + (J.iwave == BH_WAVE_LOVE ? 3 : 4) * ne;
+        t.sl = c.B; t.sb = 1;
+    }
+    t.periods = J.periods_dev; t.vel = J.vel; t.err = J.err;
+    t.first = c.first[j];
+    return t;
+}
+
+// the one-lane-per-model kernel's arguments of a target
+SwdKernelArgs lane_args(const SwdCall &c, const SwdTarget &t)
+{
+    SwdKernelArgs a{};
+    a.B = c.B; a.Lmax = c.Lmax; a.K = t.K; a.igr = t.igr; a.mode = t.mode; a.perm = c.perm;
+    a.nlay = c.m.nlay; a.h = t.h; a.vp = t.vp; a.vs = t.vs; a.rho = t.rho; a.sl = t.sl; a.sb = t.sb;
+    a.periods = t.periods; a.vel = t.vel; a.ldv = t.ldv; a.err = t.err; a.first = t.first;
+    a.neval = c.counter; a.counted = c.e->swd_scan;
+    return a;
+}
+
+// progress board of the group kernel (scheduling aid; zeroed once, entries carry a launch stamp)
+int swd_board(bh_engine *e, hipStream_t st, unsigned **board)
+{
+    if (!e->board.p) {
+        int rc = ensure(e, e->board, (size_t)BH_BOARD_WORDS * sizeof(unsigned));
+        if (rc) return rc;
+        HIPCHK(e, hipMemsetAsync(e->board.p, 0, (size_t)BH_BOARD_WORDS * sizeof(unsigned), st));
+    }
+    *board = (unsigned *)e->board.p;
+    return BH_OK;
+}
+
+// the next launch stamp of the group kernel (16 bits, never 0)
+unsigned swd_stamp(bh_engine *e)
+{
+    const unsigned s = (++e->swd_stamp) & 0xffffu;
+    return s != 0 ? s : (++e->swd_stamp) & 0xffffu;
+}
+
+// stream `to` waits for what `from` has enqueued so far: the fork to and the join from the engine's second stream, on which
+// every second launch of a call runs side by side with the others
+int wait_for(bh_engine *e, hipEvent_t ev, hipStream_t from, hipStream_t to)
+{
+    HIPCHK(e, hipEventRecord(ev, from));
+    HIPCHK(e, hipStreamWaitEvent(to, ev, 0));
+    return BH_OK;
+}
+
 // Second launch of a call in BH_SEARCH_FAST: the models the guard fired on (per target: counts[t], lists + t * (B + 4)),
 // again, with the reference's sequence -- one model per wavefront, as many trials per round as its lanes admit.  The launch
 // is sized for the worst case and reads the counts on the device: workgroups beyond them leave at once (no host round trip;
@@ -417,8 +658,7 @@ int launch_swd_rerun(bh_engine *e, hipStream_t st, const SwdMultiArgs &main, int
     a.split = nullptr;
     a.Lcut = a.Lmax;
     a.started = nullptr;
-    a.stamp = (++e->swd_stamp) & 0xffffu;
-    if (a.stamp == 0) a.stamp = (++e->swd_stamp) & 0xffffu;
+    a.stamp = swd_stamp(e);
     a.adapt_ok = 1;
     const int G = bh_swd_pick_group(a.B, a.ntargets, a.Lmax);
     for (int t = 0; t < a.ntargets; ++t) {
@@ -437,395 +677,208 @@ int launch_swd_rerun(bh_engine *e, hipStream_t st, const SwdMultiArgs &main, int
     return BH_OK;
 }
 
-// All dispersion targets of one call.  Small batches go to the group kernel (G lanes per model,
-// one launch for all targets); batches that fill the chip by themselves use one lane per model.
-int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl,
-                    ptrdiff_t sb, int njobs, const SwdJob *jobs_given)
+// The order the plan asks for, computed on the device: c.perm (and c.split for two depth classes).
+int order_models(SwdCall &c)
 {
-    if (B == 0 || njobs == 0) return BH_OK;
+    const SwdPlan &p = c.p;
+    if (p.order == ORDER_NONE || p.order == ORDER_PAIR) return BH_OK; // (the pairing order is the group kernel launcher's)
+    bh_engine *e = c.e;
     int rc;
-    // Group velocities of the fundamental mode: two launches.  The root at t/(1+h) of period k + 1 starts from the root at
-    // t/(1+h) of period k (surfdisp96.f:262-266); the root at t/(1-h) starts from the root at t/(1+h) of ITS OWN period
-    // (:282-287) and nothing starts from it.  One search after the other is a chain of 2 K dependent roots; here the target
-    // first runs as the chain of its K first roots (igr = 2: beside the call's other targets, in whatever kernel the call
-    // takes, every root stored unrounded in the output row), then a launch of B x K independent searches (one lane each, or
-    // up to 16 trial lanes while that still fits the chip at once: swd_kernel, SwdKernelArgs::second) finds the second roots
-    // and puts the group velocities in their place.  The same searches on the same values: the same bits (tests/test_gpu_swd.py's
-    // golden rows and oracle comparisons run through here).  Measured, one launch -> two (ms per call): one model 2.26 -> 1.43;
-    // two targets x 256 / 1024 / 4096 / 8192 / 16 384 / 65 536 models: 2.64 -> 1.90, 2.91 -> 2.10, 5.51 -> 4.64, 11.2 -> 8.09,
-    // 17.2 -> 12.5, 31.5 -> 29.9 (the second roots are a third of the evaluations but run as full wavefronts of independent
-    // searches, one lane each; in one launch they sit in the chain's wavefronts, whose lanes wait for each other's searches).
-    // bh_tuning.h swd_gsplit: the largest call in (model, period) pairs that is split (0: none).
-    SwdJob jobs_split[BH_MAX_TARGETS];
-    const SwdJob *jobs = jobs_given;
-    int nsplit = 0;
-    {
-        const long cap = bh_tuning().swd_gsplit;
-        bool take[BH_MAX_TARGETS] = {false};
-        for (int j = 0; j < njobs && njobs <= BH_MAX_TARGETS; ++j) {
-            take[j] = jobs_given[j].K != 0 && jobs_given[j].igr == 1 && jobs_given[j].mode <= 1 && cap > 0 && (long)B * jobs_given[j].K <= cap;
-            nsplit += take[j] ? 1 : 0;
-        }
-        if (nsplit > 0) {
-            if ((rc = ensure(e, e->gfirst, (size_t)nsplit * B * sizeof(double)))) return rc;
-            int n = 0;
-            for (int j = 0; j < njobs; ++j) {
-                jobs_split[j] = jobs_given[j];
-                if (take[j]) {
-                    jobs_split[j].igr = 2;
-                    jobs_split[j].first = (double *)e->gfirst.p + (size_t)(n++) * B;
-                }
-            }
-            jobs = jobs_split;
-        }
+    if ((rc = ensure(e, e->perm, ((size_t)c.B + 4) * sizeof(int32_t)))) return rc;
+    int32_t *perm = (int32_t *)e->perm.p;
+    if (p.order == ORDER_LENGTH) {
+        const PairOrderTarget tg{p.len_mpw, c.B / p.len_mpw, nullptr, perm + 4, p.len_xcd};
+        bh_launch_pair_order(c.B, c.Lmax, c.m.nlay, c.m.vs, c.sl, c.sb, 1, &tg, c.st);
+    } else {
+        bh_launch_order(c.B, c.m.nlay, perm + 4, p.Lcut, perm, c.st);
+        c.split = (p.Lcut < c.Lmax) ? perm : nullptr;
     }
-    int kmax = 0, maxmode = 1, nlive = 0;
-    bool any_sphere = false;
-    for (int j = 0; j < njobs; ++j) {
-        if (jobs[j].K == 0) continue;
-        ++nlive;
-        kmax = jobs[j].K > kmax ? jobs[j].K : kmax;
-        maxmode = jobs[j].mode > maxmode ? jobs[j].mode : maxmode;
-        any_sphere = any_sphere || jobs[j].flsph == 1;
+    c.perm = perm + 4;
+    return BH_OK;
+}
+
+// One lane per model: a launch per target.  A wavefront of these kernels keeps its SIMD's vector issue ~60 % busy
+// (profiles/), so the targets of a call run SIDE BY SIDE: every second one on a second stream.  ra: the targets for the
+// re-run of guarded models (which goes through the group kernel).
+int launch_swd_lanes(SwdCall &c, SwdMultiArgs &ra)
+{
+    bh_engine *e = c.e;
+    const SwdPlan &p = c.p;
+    const int B = c.B, n = p.ntargets;
+    const bool fork = n > 1 && e->aux2 != nullptr;
+    int rc;
+    // work array of the launches (the Neville orders the kernel does not keep in LDS): one region per target,
+    // the targets run concurrently
+    size_t nev_off[BH_MAX_TARGETS + 1] = {0};
+    for (int t = 0; t < n; ++t) nev_off[t + 1] = nev_off[t] + bh_swd_nev_high_doubles(B, p.look[t]);
+    if ((rc = ensure(e, e->nevhi, nev_off[n] * sizeof(double)))) return rc;
+    long lane_waves = 0; // wavefronts of the call
+    for (int t = 0; t < n; ++t) lane_waves += (long)((B + 63) / 64) * p.look[t];
+    e->guard_last = p.any_fast;
+    ra.B = B; ra.Lmax = c.Lmax; ra.nlay = c.m.nlay; ra.neval = c.counter; ra.counted = e->swd_scan;
+    if (p.any_fast && ((rc = guard_space(e, c.st, B, &c.gcounts, &c.glists)) || (rc = swd_board(e, c.st, &ra.board)))) return rc;
+    e->last_swd_kernel = BH_KERNEL_LANE;
+    ev_begin(e, 0, c.st);
+    if (fork && (rc = wait_for(e, e->ev_fork2, c.st, e->aux2))) return rc;
+    for (int t = 0; t < n; ++t) {
+        const SwdTarget tg = swd_target(c, p.job[t]);
+        SwdKernelArgs a = lane_args(c, tg);
+        a.look = p.look[t];
+        // priority time slice (log2 cycles) of wavefronts that share a SIMD, see swd_kernel; wavefronts with a SIMD of
+        // their own are left alone (a low-priority phase costs them 8 %: the CU's front end is shared)
+        a.fair = lane_waves <= 1024 ? -1 : (lane_waves <= 2048 ? 18 : 12);
+        a.nev_high = (double *)e->nevhi.p + nev_off[t];
+        a.fast = p.fast[t] ? 1 : 0;
+        a.farith = (p.fast[t] && p.farith) ? 1 : 0;
+        if (a.fast) {
+            a.gcount = c.gcounts + t;
+            a.glist = c.glists + (size_t)t * (size_t)(B + 4);
+        }
+        bh_launch_swd(a, tg.iwave, (fork && (t & 1)) ? e->aux2 : c.st);
+        ra.t[ra.ntargets++] = tg;
     }
-    if (nlive == 0) return BH_OK;
-    // earth-flattened copies of the batch (layer-major), made once per call
-    const double *sh = nullptr, *svp = nullptr, *svs = nullptr, *srl = nullptr, *srr = nullptr;
-    if (any_sphere) {
-        const size_t nb = (size_t)Lmax * B * sizeof(double);
-        if ((rc = ensure(e, e->sph, 5 * nb))) return rc;
-        double *base = (double *)e->sph.p;
-        const size_t ne = (size_t)Lmax * B;
-        bh_launch_sphere(B, Lmax, m.nlay, m.h, m.vp, m.vs, m.rho, sl, sb, base, base + ne, base + 2 * ne,
-                         base + 3 * ne, base + 4 * ne, st);
-        sh = base; svp = base + ne; svs = base + 2 * ne; srl = base + 3 * ne; srr = base + 4 * ne;
+    if (fork && (rc = wait_for(e, e->ev_join2, e->aux2, c.st))) return rc;
+    HIPCHK(e, hipGetLastError());
+    return BH_OK;
+}
+
+// All targets in ONE launch of the group kernel (G lanes per model) or of the trial-per-lane kernel.  a: the launch's arguments
+// (what the re-run of guarded models starts from).
+int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
+{
+    bh_engine *e = c.e;
+    const SwdPlan &p = c.p;
+    const int B = c.B;
+    int rc;
+    if ((rc = swd_board(e, c.st, &a.board))) return rc;
+    a.stamp = swd_stamp(e);
+    a.B = B; a.Lmax = c.Lmax; a.nlay = c.m.nlay; a.neval = c.counter; a.perm = c.perm;
+    a.split = c.split; a.Lcut = p.Lcut;
+    a.ntargets = p.ntargets;
+    for (int t = 0; t < p.ntargets; ++t) {
+        a.t[t] = swd_target(c, p.job[t]);
+        a.t[t].look = p.look[t];
+        a.t[t].inlook = p.inlook[t];
+        a.t[t].refseq = p.refseq[t] ? 1 : 0;
     }
-    // Typical depth of the batch (0 = unknown: the array capacity is planned for).  Ignored where every (model, target) gets a
-    // wavefront of its own anyway (at most 2048 of them: the chip's two per SIMD) -- the regime of the chains' speculative
-    // windows.  There a depth class of its own for the shallow bulk buys nothing (the models per wavefront cannot grow), the
-    // narrower lane groups cost a second pass over the layers and seven instead of four trials per round more transitions:
-    // measured on windows of 1016 models of 3-9 layers in arrays of 21 (c4): 1.50 ms without the hint, 1.70-1.83 ms with it.
-    const int typ_given = m.typ_layers > 0 ? m.typ_layers : e->hint_layers;
-    const bool hint_always = bh_tuning().swd_hint_always != 0;
-    const int typ_layers = ((long)nlive * B <= 2048 && !hint_always) ? 0 : typ_given;
-    int iw[BH_MAX_TARGETS], look[BH_MAX_TARGETS], G = 1;
-    {
-        int n = 0;
-        for (int j = 0; j < njobs; ++j)
-            if (jobs[j].K != 0) iw[n++] = jobs[j].iwave;
-        // lanes per model follow the TYPICAL depth of the batch (deeper models take further passes over
-        // their layers): known for host batches, a caller's hint for device-resident ones, else Lmax
-        int Lplan = typ_layers > 0 ? typ_layers : Lmax;
-        if (Lplan > Lmax) Lplan = Lmax;
-        bh_swd_plan(B, Lplan, n, iw, e->force_group, &G, look);
-        if (e->force_look > 0)
-            for (int t = 0; t < n; ++t) look[t] = e->force_look; // (one lane per model: rounded down to a power of two)
-    }
-    const size_t lds_cap = 64 * 1024;
-    if (G <= 1 && bh_swd_lds_bytes(Lmax, kmax, maxmode) > lds_cap) G = 2; // deep models / many periods
-    // The trial-per-lane kernel (swd_lean.hip): every target of the call takes the short refinement with the fast arithmetic, in
-    // calls of up to 2^20 (model, target) pairs (with four trials per round it stays ahead of one lane per evaluation -- swd_kernel's
-    // FA builds -- as far as measured: c2 at B = 65 536 7.99 against 8.44 ms).
-    int lean_trials = 0;
-    {
-        bool all = e->swd_arith == BH_ARITH_FAST && e->swd_search == BH_SEARCH_FAST && e->force_group == 0 && e->force_look == 0 &&
-                   e->look_r == 0 && e->look_l == 0 && bh_tuning().swd_no_lean == 0 && maxmode <= 1 && kmax <= BH_MAX_PERIODS && Lmax <= 32 &&
-                   (long)B * nlive <= (bh_tuning().swd_lean_pairs > 0 ? (long)bh_tuning().swd_lean_pairs : (1L << 20));
-        for (int j = 0; j < njobs; ++j) all = all && (jobs[j].K == 0 || jobs[j].igr == 0);
-        if (all) lean_trials = e->swd_trials > 0 ? e->swd_trials : bh_swd_lean_trials(B, nlive);
-        if (lean_trials >= 4 && bh_swd_lean_lds_bytes(lean_trials, Lmax, kmax) > lds_cap) lean_trials = 0; // (a workgroup's LDS)
-    }
-    const bool lean = lean_trials >= 4;
-    if (lean && G <= 1) G = bh_swd_pick_group(B, nlive, Lmax); // (the launch is set up where the group kernel's is)
-    unsigned long long *counter = nullptr;
-    if ((rc = swd_counter(e, st, &counter))) return rc;
-    // the launches of the second roots of the group-velocity targets run as two chains (above), after the call's other launches
-    auto second_roots = [&]() -> int {
-        int J2 = 16; // trial lanes per search while all searches of the call still fit the chip at once (2048 wavefronts)
-        {
-            long searches = 0;
-            for (int j = 0; j < njobs; ++j) searches += jobs[j].igr == 2 ? (long)B * jobs[j].K : 0;
-            while (J2 > 1 && searches * J2 > 2048L * 64) J2 >>= 1;
-        }
-        size_t off[BH_MAX_TARGETS + 1] = {0};
-        int n = 0;
-        for (int j = 0; j < njobs; ++j)
-            if (jobs[j].igr == 2) {
-                off[n + 1] = off[n] + bh_swd_nev_high_doubles(B * jobs[j].K, J2);
-                ++n;
-            }
-        int rc2 = ensure(e, e->nevhi2, off[n] * sizeof(double));
-        if (rc2) return rc2;
-        // (as with the one-lane-per-model launches below: every second target on a second stream, side by side)
-        const bool fork = n > 1 && e->aux2 != nullptr;
-        if (fork) {
-            HIPCHK(e, hipEventRecord(e->ev_fork2, st));
-            HIPCHK(e, hipStreamWaitEvent(e->aux2, e->ev_fork2, 0));
-        }
-        n = 0;
-        for (int j = 0; j < njobs; ++j) {
-            const SwdJob &J = jobs[j];
-            if (J.igr != 2) continue;
-            SwdKernelArgs a{};
-            a.B = B * J.K; a.Bm = B; a.second = 1; a.first = J.first;
-            a.Lmax = Lmax; a.K = J.K; a.igr = 1; a.mode = 1; a.perm = nullptr;
-            a.nlay = m.nlay; a.h = m.h; a.vp = m.vp; a.vs = m.vs; a.rho = m.rho; a.sl = sl; a.sb = sb;
-            if (J.flsph == 1) {
-                a.h = sh; a.vp = svp; a.vs = svs; a.rho = (J.iwave == BH_WAVE_LOVE) ? srl : srr;
-                a.sl = B; a.sb = 1;
-            }
-            a.periods = J.periods_dev; a.vel = J.vel; a.ldv = J.ldv; a.err = J.err; a.neval = counter;
-            a.look = J2;
-            const long waves = ((long)a.B * J2 + 63) / 64;
-            a.fair = waves <= 1024 ? -1 : (waves <= 2048 ? 18 : 12);
-            a.nev_high = (double *)e->nevhi2.p + off[n];
-            a.fast = 0; a.farith = 0; a.counted = e->swd_scan;
-            bh_launch_swd(a, J.iwave, (fork && (n & 1)) ? e->aux2 : st);
-            ++n;
-        }
-        if (fork) {
-            HIPCHK(e, hipEventRecord(e->ev_join2, e->aux2));
-            HIPCHK(e, hipStreamWaitEvent(st, e->ev_join2, 0));
-        }
-        HIPCHK(e, hipGetLastError());
-        return BH_OK;
-    };
-    // processing order: deepest models first, wavefronts of (nearly) one depth
-    const int32_t *perm = nullptr, *split = nullptr;
-    int Lcut = Lmax;
-    // One depth class, lanes per model > 1: the launcher orders the models itself, by predicted search length and paired
-    // over the SIMDs (SwdPairWork); mixed depths are ordered by depth there as well.
-    // Measured (bench.py c2, B = 2048 ... 4096, same session with / without): -3 % at 4096 and -4 % at 3800, where the
-    // launch nearly fills two wavefronts per SIMD and the Rayleigh wavefronts (look-ahead 2) outnumber the Love ones
-    // (trials inside the lane groups) 7 : 3; neutral at 3500; +2.5 % at 2048 / 3072, where the planner gives both targets
-    // the same look-ahead and every SIMD holds one Rayleigh and one Love wavefront (why the one-to-one mix loses is not
-    // understood).  Hence: two targets, >= 7/8 of two wavefronts per SIMD, unequal wavefront counts.
-    long plan_waves = 0, wmin = 0, wmax = 0;
-    if (G > 1)
-        for (int t = 0; t < nlive; ++t) {
-            int J = look[t] > 1 ? look[t] : 1;
-            while (J > 1 && G * J > 64) --J;
-            const int mpw = 64 / (G * J);
-            const long w = (B + mpw - 1) / mpw;
-            plan_waves += w;
-            wmin = (t == 0 || w < wmin) ? w : wmin;
-            wmax = w > wmax ? w : wmax;
-        }
-    const int pair_min = bh_tuning().swd_pair_minwaves;
-    const bool use_pair = !lean && B > 1 && !e->no_order && !e->as_given && !e->no_pair && G > 1 && nlive == 2 && bh_pair_order_fits(B) &&
-                          plan_waves >= (pair_min >= 0 ? pair_min : 7 * (long)e->pairwork.ncu) && (pair_min >= 0 || 2 * wmax >= 3 * wmin) &&
-                          !(typ_layers > 0 && typ_layers + 2 < Lmax);
-    if (B > 1 && !e->no_order && !e->as_given && !use_pair) {
-        if ((rc = ensure(e, e->perm, ((size_t)B + 4) * sizeof(int32_t)))) return rc;
-        int32_t *p = (int32_t *)e->perm.p;
-        // LDS rows for the bulk of the batch: its typical depth plus a margin; deeper models get their own launch
-        const int typ = typ_layers;
-        if (lean && bh_pair_order_fits(B) && bh_tuning().swd_lean_no_sort == 0) {
-            // The trial-per-lane kernel: the models in the order of their PREDICTED search length, longest first (mixed depths:
-            // deepest first) -- wavefronts of like models idle fewer rounds on finished ones, and the long wavefronts are
-            // dispatched first with the short ones filling the launch's tail (c2: 0.79 -> 0.72 ms).  Scheduling only.
-            // Sorted inside eight blocks of the batch, block x for the wavefronts of XCD x, where the shapes divide: each XCD's L2
-            // then fetches an eighth of the model arrays instead of all of them (HBM reads of the launch 10.7 -> 1.9 MB at c2).
-            PairOrderTarget tg{1, B, nullptr, p + 4, 0};
-            const int mpw = BH_WAVE / lean_trials, per_wg = (nlive == 2) ? 2 : 4;
-            if (bh_tuning().swd_lean_xcd != 0 && bh_tuning().swd_lean_r < 4 && bh_tuning().swd_lean_l < 4 && B % mpw == 0 && B % 8 == 0 &&
-                (B / mpw) % (8 * per_wg) == 0)
-                tg = PairOrderTarget{mpw, B / mpw, nullptr, p + 4, per_wg};
-            bh_launch_pair_order(B, Lmax, m.nlay, m.vs, sl, sb, 1, &tg, st);
-            perm = p + 4;
-        } else {
-            if (typ > 0 && typ + 2 < Lmax) Lcut = typ + 2;
-            bh_launch_order(B, m.nlay, p + 4, Lcut, p, st);
-            perm = p + 4;
-            split = (Lcut < Lmax) ? p : nullptr;
-        }
-    }
-    if (G <= 1) {
-        // One lane per model: a launch per target.  A wavefront of these kernels keeps its SIMD's vector issue ~60 %
-        // busy (profiles/), so the targets of a call run SIDE BY SIDE: every second one on a second stream.
-        int nlive2 = 0;
-        for (int j = 0; j < njobs; ++j) nlive2 += (jobs[j].K != 0);
-        const bool fork2 = nlive2 > 1 && e->aux2 != nullptr;
-        // work array of the launches (the Neville orders the kernel does not keep in LDS): one region per target,
-        // the targets run concurrently
-        size_t nev_off[BH_MAX_TARGETS + 1] = {0};
-        for (int t = 0; t < nlive2; ++t) nev_off[t + 1] = nev_off[t] + bh_swd_nev_high_doubles(B, look[t] > 1 ? look[t] : 1);
-        if ((rc = ensure(e, e->nevhi, nev_off[nlive2] * sizeof(double)))) return rc;
-        long lane_waves = 0; // wavefronts of the call
-        for (int t = 0; t < nlive2; ++t) lane_waves += (long)((B + 63) / 64) * (look[t] > 1 ? look[t] : 1);
-        int32_t *gcounts = nullptr, *glists = nullptr;
-        bool any_fast = false;
-        for (int j = 0; j < njobs; ++j)
-            any_fast = any_fast || (jobs[j].K != 0 && jobs[j].igr == 0 && jobs[j].mode <= 1 &&
-                                    (e->swd_search == BH_SEARCH_FAST || (e->swd_search == BH_SEARCH_FAST_RAYLEIGH && jobs[j].iwave == BH_WAVE_RAYLEIGH)));
-        e->guard_last = any_fast;
-        if (any_fast && (rc = guard_space(e, st, B, &gcounts, &glists))) return rc;
-        SwdMultiArgs ra{}; // (the re-run of guarded models goes through the group kernel)
-        ra.B = B; ra.Lmax = Lmax; ra.nlay = m.nlay; ra.neval = counter; ra.counted = e->swd_scan;
-        if (any_fast) {
-            if (!e->board.p) {
-                if ((rc = ensure(e, e->board, (size_t)BH_BOARD_WORDS * sizeof(unsigned)))) return rc;
-                HIPCHK(e, hipMemsetAsync(e->board.p, 0, (size_t)BH_BOARD_WORDS * sizeof(unsigned), st));
-            }
-            ra.board = (unsigned *)e->board.p;
-        }
-        e->last_swd_kernel = BH_KERNEL_LANE;
-        ev_begin(e, 0, st);
-        if (fork2) {
-            HIPCHK(e, hipEventRecord(e->ev_fork2, st));
-            HIPCHK(e, hipStreamWaitEvent(e->aux2, e->ev_fork2, 0));
-        }
-        int nth = 0;
-        for (int j = 0; j < njobs; ++j) {
-            const SwdJob &J = jobs[j];
-            if (J.K == 0) continue;
-            SwdKernelArgs a{};
-            a.B = B; a.Lmax = Lmax; a.K = J.K; a.igr = J.igr; a.mode = J.mode; a.perm = perm;
-            a.nlay = m.nlay; a.h = m.h; a.vp = m.vp; a.vs = m.vs; a.rho = m.rho; a.sl = sl; a.sb = sb;
-            if (J.flsph == 1) {
-                a.h = sh; a.vp = svp; a.vs = svs; a.rho = (J.iwave == BH_WAVE_LOVE) ? srl : srr;
-                a.sl = B; a.sb = 1;
-            }
-            a.periods = J.periods_dev; a.vel = J.vel; a.ldv = J.ldv; a.err = J.err; a.neval = counter;
-            a.first = J.first;
-            a.look = look[nth] > 1 ? look[nth] : 1;
-            // priority time slice (log2 cycles) of wavefronts that share a SIMD, see swd_kernel; wavefronts with a SIMD of
-            // their own are left alone (a low-priority phase costs them 8 %: the CU's front end is shared)
-            a.fair = lane_waves <= 1024 ? -1 : (lane_waves <= 2048 ? 18 : 12);
-            a.nev_high = (double *)e->nevhi.p + nev_off[nth];
-            a.fast = (J.igr == 0 && J.mode <= 1 && (e->swd_search == BH_SEARCH_FAST || (e->swd_search == BH_SEARCH_FAST_RAYLEIGH && J.iwave == BH_WAVE_RAYLEIGH))) ? 1 : 0;
-            a.counted = e->swd_scan;
-            a.farith = (a.fast && e->swd_arith == BH_ARITH_FAST) ? 1 : 0;
-            if (a.fast) {
-                a.gcount = gcounts + nth;
-                a.glist = glists + (size_t)nth * (size_t)(B + 4);
-            }
-            bh_launch_swd(a, J.iwave, (fork2 && (nth & 1)) ? e->aux2 : st);
-            SwdTarget &t = ra.t[ra.ntargets++];
-            t.iwave = J.iwave; t.igr = J.igr; t.K = J.K; t.ldv = J.ldv; t.mode = J.mode;
-            t.h = a.h; t.vp = a.vp; t.vs = a.vs; t.rho = a.rho; t.sl = a.sl; t.sb = a.sb;
-            t.periods = J.periods_dev; t.vel = J.vel; t.err = J.err;
-            ++nth;
-        }
-        if (fork2) {
-            HIPCHK(e, hipEventRecord(e->ev_join2, e->aux2));
-            HIPCHK(e, hipStreamWaitEvent(st, e->ev_join2, 0));
-        }
-        HIPCHK(e, hipGetLastError());
-        if (any_fast && (rc = launch_swd_rerun(e, st, ra, gcounts, glists))) return rc;
-        if (nsplit > 0 && (rc = second_roots())) return rc;
-        ev_end(e, 0, st);
-        return BH_OK;
-    }
-    SwdMultiArgs a{};
-    if (!e->board.p) { // progress board of the group kernel (scheduling aid; zeroed once, entries carry a launch stamp)
-        if ((rc = ensure(e, e->board, (size_t)BH_BOARD_WORDS * sizeof(unsigned)))) return rc;
-        HIPCHK(e, hipMemsetAsync(e->board.p, 0, (size_t)BH_BOARD_WORDS * sizeof(unsigned), st));
-    }
-    a.board = (unsigned *)e->board.p;
-    a.stamp = (++e->swd_stamp) & 0xffffu;
-    if (a.stamp == 0) a.stamp = (++e->swd_stamp) & 0xffffu;
-    a.B = B; a.Lmax = Lmax; a.ntargets = 0; a.nlay = m.nlay; a.neval = counter; a.perm = perm;
-    a.split = split; a.Lcut = Lcut;
-    for (int j = 0; j < njobs; ++j) {
-        const SwdJob &J = jobs[j];
-        if (J.K == 0) continue;
-        SwdTarget &t = a.t[a.ntargets++];
-        t.iwave = J.iwave; t.igr = J.igr; t.K = J.K; t.ldv = J.ldv; t.mode = J.mode;
-        t.look = look[a.ntargets - 1];
-        // Love: two trials inside each lane group pay while the group count is small (measured: wavefront
-        // 7 % shorter at look = 1, neutral at 2, slower beyond)
-        t.inlook = (J.iwave != BH_WAVE_LOVE) ? 1 : (e->love_inlook > 0 ? e->love_inlook : (t.look <= 2 ? 2 : 1));
-        t.h = m.h; t.vp = m.vp; t.vs = m.vs; t.rho = m.rho; t.sl = sl; t.sb = sb;
-        if (J.flsph == 1) {
-            t.h = sh; t.vp = svp; t.vs = svs; t.rho = (J.iwave == BH_WAVE_LOVE) ? srl : srr;
-            t.sl = B; t.sb = 1;
-        }
-        t.periods = J.periods_dev; t.vel = J.vel; t.err = J.err;
-        t.first = J.first;
-    }
-    // which targets take the short refinement: phase velocities; with BH_SEARCH_FAST_RAYLEIGH only the Rayleigh ones
-    auto takes_fast = [&](const SwdTarget &t) {
-        return t.igr == 0 && t.mode <= 1 && (e->swd_search == BH_SEARCH_FAST || (e->swd_search == BH_SEARCH_FAST_RAYLEIGH && t.iwave == BH_WAVE_RAYLEIGH));
-    };
     a.counted = e->swd_scan;
-    a.farith = e->swd_arith == BH_ARITH_FAST ? 1 : 0;
-    for (int t = 0; t < a.ntargets; ++t) {
-        if (e->look_r > 0 && a.t[t].iwave == BH_WAVE_RAYLEIGH) a.t[t].look = e->look_r;
-        if (e->look_l > 0 && a.t[t].iwave == BH_WAVE_LOVE) a.t[t].look = e->look_l;
-    }
+    a.farith = p.farith ? 1 : 0;
     a.started = e->started;
     a.prio_low = e->swd_prio_low_now;
-    a.adapt_ok = (e->force_group == 0 && e->force_look == 0 && e->look_r == 0 && e->look_l == 0) ? 1 : 0;
-    {
-        const bool dbg = bh_tuning().debug_plan != 0;
-        if (dbg) {
-            std::fprintf(stderr, "[bh] dispersion plan B=%d Lmax=%d: lanes per model %d, typical layers %d (hint %d), Lcut %d%s, pairing %d; trials per round:",
-                         B, Lmax, G, m.typ_layers, e->hint_layers, Lcut, split ? " (two depth classes)" : "", (int)use_pair);
-            for (int t = 0; t < a.ntargets; ++t) std::fprintf(stderr, " %s %d/%d", a.t[t].iwave == BH_WAVE_LOVE ? "L" : "R", a.t[t].look, a.t[t].inlook);
-            std::fprintf(stderr, "\n");
-        }
+    a.adapt_ok = p.adapt_ok ? 1 : 0;
+    a.fast = p.any_fast ? 1 : 0;
+    a.restart = 1; // (takes effect in launches of one model per wavefront: see bh_launch_swd_group)
+    if (bh_tuning().debug_plan != 0) {
+        std::fprintf(stderr, "[bh] dispersion plan B=%d Lmax=%d: lanes per model %d, typical layers %d (hint %d), Lcut %d%s, pairing %d; trials per round:",
+                     B, c.Lmax, p.G, c.m.typ_layers, e->hint_layers, p.Lcut, p.Lcut < c.Lmax ? " (two depth classes)" : "", (int)(p.order == ORDER_PAIR));
+        for (int t = 0; t < p.ntargets; ++t) std::fprintf(stderr, " %s %d/%d", a.t[t].iwave == BH_WAVE_LOVE ? "L" : "R", p.look_group[t], p.inlook[t]);
+        std::fprintf(stderr, "\n");
     }
-    // ONE launch for all targets.  Where some phase-velocity targets take the short refinement and others keep the reference's
-    // sequence (BH_SEARCH_FAST_RAYLEIGH with Love targets in the call) the launch takes the build with both sequences and the
-    // targets say which is theirs (two launches side by side were measured: the Rayleigh / Love pairs on the SIMDs are lost,
-    // c4 1.37 -> 1.58 ms per window).
-    {
-        int nfast = 0;
-        for (int t = 0; t < a.ntargets; ++t) nfast += takes_fast(a.t[t]) ? 1 : 0;
-        for (int t = 0; t < a.ntargets; ++t) a.t[t].refseq = (nfast > 0 && a.t[t].igr == 0 && !takes_fast(a.t[t])) ? 1 : 0;
-        a.fast = nfast > 0 ? 1 : 0;
-        a.restart = 1; // (takes effect in launches of one model per wavefront: see bh_launch_swd_group)
-    }
-    int32_t *gcounts = nullptr, *glists = nullptr;
-    e->guard_last = a.fast != 0;
-    if (a.fast) {
-        if ((rc = guard_space(e, st, B, &gcounts, &glists))) return rc;
+    e->guard_last = p.any_fast;
+    if (p.any_fast) {
+        if ((rc = guard_space(e, c.st, B, &c.gcounts, &c.glists))) return rc;
         for (int t = 0; t < a.ntargets; ++t)
-            if (a.t[t].igr == 0) {
-                a.t[t].gcount = gcounts + t;
-                a.t[t].glist = glists + (size_t)t * (size_t)(B + 4);
+            if (a.t[t].igr == BH_VEL_PHASE) {
+                a.t[t].gcount = c.gcounts + t;
+                a.t[t].glist = c.glists + (size_t)t * (size_t)(B + 4);
             }
     }
-    ev_begin(e, 0, st);
-    int lrc;
-    if (lean) {
-        const BhTuning &tun = bh_tuning();
-        for (int t = 0; t < a.ntargets; ++t) {
-            int Jt = lean_trials;
-            if (a.t[t].iwave == BH_WAVE_RAYLEIGH && tun.swd_lean_r >= 4) Jt = tun.swd_lean_r;
-            if (a.t[t].iwave == BH_WAVE_LOVE && tun.swd_lean_l >= 4) Jt = tun.swd_lean_l;
-            a.t[t].look = Jt;
-        }
-        lrc = bh_launch_swd_lean(a, st, &e->last_swd);
-        e->last_swd_kernel = BH_KERNEL_LEAN;
-    } else {
-        e->last_swd_kernel = BH_KERNEL_GROUP;
-        lrc = bh_launch_swd_group(a, G, st, &e->last_swd, 2, use_pair ? &e->pairwork : nullptr);
-    }
+    ev_begin(e, 0, c.st);
+    const bool lean = p.kernel == BH_KERNEL_LEAN;
+    e->last_swd_kernel = p.kernel;
+    const int lrc = lean ? bh_launch_swd_lean(a, c.st, &e->last_swd)
+                         : bh_launch_swd_group(a, p.G, c.st, &e->last_swd, 2, p.order == ORDER_PAIR ? &e->pairwork : nullptr);
     e->last_swd_wpb = lean ? 4 : 2; // (wavefronts per workgroup of the kernel that was launched)
-    if (lrc != 0) {
-        ev_end(e, 0, st);
-        return fail(e, BH_EINVAL, "model too deep for LDS");
-    }
+    if (lrc != 0) return fail(e, BH_EINVAL, "model too deep for LDS");
     // (the counter a second stream waits on moves only once the launch is known to have been accepted: a failed launch
     // never increments the device word, and every later wait for the advanced value would hang -- ADVICE r03)
     const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) {
-        ev_end(e, 0, st);
-        return fail(e, BH_EHIP, "dispersion kernel launch", le);
-    }
+    if (le != hipSuccess) return fail(e, BH_EHIP, "dispersion kernel launch", le);
     if (e->started) e->started_expected += e->last_swd.workgroups;
-    if (a.fast && !e->last_swd.restarts_in_place && (rc = launch_swd_rerun(e, st, a, gcounts, glists))) {
-        ev_end(e, 0, st);
-        return rc;
-    }
-    if (nsplit > 0 && (rc = second_roots())) {
-        ev_end(e, 0, st);
-        return rc;
-    }
-    ev_end(e, 0, st);
     return BH_OK;
+}
+
+// The second roots of the group-velocity targets split in two launches (plan_swd): B x K independent searches per target,
+// after the call's other launches.  Each search reads the first root its chain kept and puts the group velocity in its place.
+int launch_second_roots(const SwdCall &c)
+{
+    bh_engine *e = c.e;
+    const int B = c.B;
+    int J2 = 16; // trial lanes per search while all searches of the call still fit the chip at once (2048 wavefronts)
+    {
+        long searches = 0;
+        for (int t = 0; t < c.p.ntargets; ++t) searches += c.p.first_roots[c.p.job[t]] ? (long)B * c.jobs[c.p.job[t]].K : 0;
+        while (J2 > 1 && searches * J2 > 2048L * 64) J2 >>= 1;
+    }
+    size_t off[BH_MAX_TARGETS + 1] = {0};
+    int n = 0;
+    for (int t = 0; t < c.p.ntargets; ++t)
+        if (c.p.first_roots[c.p.job[t]]) {
+            off[n + 1] = off[n] + bh_swd_nev_high_doubles(B * c.jobs[c.p.job[t]].K, J2);
+            ++n;
+        }
+    int rc = ensure(e, e->nevhi2, off[n] * sizeof(double));
+    if (rc) return rc;
+    // (as with the one-lane-per-model launches: every second target on a second stream, side by side)
+    const bool fork = n > 1 && e->aux2 != nullptr;
+    if (fork && (rc = wait_for(e, e->ev_fork2, c.st, e->aux2))) return rc;
+    n = 0;
+    for (int t = 0; t < c.p.ntargets; ++t) {
+        if (!c.p.first_roots[c.p.job[t]]) continue;
+        const SwdTarget tg = swd_target(c, c.p.job[t]);
+        SwdKernelArgs a = lane_args(c, tg);
+        a.B = B * tg.K; a.Bm = B; a.second = 1;
+        a.igr = BH_VEL_GROUP; a.mode = 1; a.perm = nullptr;
+        a.look = J2;
+        const long waves = ((long)a.B * J2 + 63) / 64;
+        a.fair = waves <= 1024 ? -1 : (waves <= 2048 ? 18 : 12);
+        a.nev_high = (double *)e->nevhi2.p + off[n];
+        bh_launch_swd(a, tg.iwave, (fork && (n & 1)) ? e->aux2 : c.st);
+        ++n;
+    }
+    if (fork && (rc = wait_for(e, e->ev_join2, e->aux2, c.st))) return rc;
+    HIPCHK(e, hipGetLastError());
+    return BH_OK;
+}
+
+// All dispersion targets of one call: the plan, the flattened copies and the order it needs, then its launches -- the group or
+// trial-per-lane kernel (one launch for all targets) or one lane per model (a launch per target) -- the re-run of the models
+// the guard of the short refinement fired on, and the second roots of split group velocities.
+int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl,
+                    ptrdiff_t sb, int njobs, const SwdJob *jobs)
+{
+    if (B == 0 || njobs == 0) return BH_OK;
+    const SwdPlan p = plan_swd(e, B, Lmax, m.typ_layers > 0 ? m.typ_layers : e->hint_layers, njobs, jobs);
+    SwdCall c{e, st, B, Lmax, m, sl, sb, jobs, p};
+    int rc;
+    if (p.nsplit > 0) {
+        if ((rc = ensure(e, e->gfirst, (size_t)p.nsplit * B * sizeof(double)))) return rc;
+        int n = 0;
+        for (int j = 0; j < njobs; ++j)
+            if (p.first_roots[j]) c.first[j] = (double *)e->gfirst.p + (size_t)(n++) * B;
+    }
+    if (p.ntargets == 0) return BH_OK;
+    if (p.any_sphere) { // earth-flattened copies of the batch (layer-major), made once per call
+        const size_t ne = (size_t)Lmax * B;
+        if ((rc = ensure(e, e->sph, 5 * ne * sizeof(double)))) return rc;
+        double *base = (double *)e->sph.p;
+        bh_launch_sphere(B, Lmax, m.nlay, m.h, m.vp, m.vs, m.rho, sl, sb, base, base + ne, base + 2 * ne, base + 3 * ne, base + 4 * ne, st);
+        c.sph = base;
+    }
+    if ((rc = swd_counter(e, st, &c.counter)) || (rc = order_models(c))) return rc;
+    SwdMultiArgs a{};
+    bool rerun;
+    if (p.kernel == BH_KERNEL_LANE) {
+        rc = launch_swd_lanes(c, a);
+        rerun = p.any_fast;
+    } else {
+        rc = launch_swd_multi(c, a);
+        rerun = p.any_fast && !e->last_swd.restarts_in_place;
+    }
+    if (!rc && rerun) rc = launch_swd_rerun(e, st, a, c.gcounts, c.glists);
+    if (!rc && p.nsplit > 0) rc = launch_second_roots(c);
+    ev_end(e, 0, st);
+    return rc;
 }
 
 int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl,
@@ -943,7 +996,6 @@ int bh_engine_create(int device, bh_engine **out)
     const BhTuning &tun = bh_tuning(); // (the experiment switches: parsed once per process, bh_tuning.h)
     if (tun.no_overlap) e->overlap_rf = false;
     if (tun.rf_lds_beside >= 0) e->rf_lds_beside_swd = tun.rf_lds_beside;
-    if (tun.swd_no_pair) e->no_pair = true;
     {
         hipDeviceProp_t prop;
         e->pairwork.ncu = (hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 0;
@@ -971,11 +1023,7 @@ int bh_engine_create(int device, bh_engine **out)
     if (tun.swd_search >= 0) e->swd_search = tun.swd_search;
     if (tun.swd_arith >= 0) e->swd_arith = tun.swd_arith != 0 ? BH_ARITH_FAST : BH_ARITH_EXACT;
     if (tun.swd_scan >= 0) e->swd_scan = tun.swd_scan;
-    e->love_inlook = tun.swd_love_inlook;
-    e->look_r = tun.swd_look_r;
-    e->look_l = tun.swd_look_l;
     if (tun.no_mfma) e->no_mfma = true;
-    if (tun.no_order) e->no_order = true;
     *out = e;
     return BH_OK;
 }
@@ -1223,7 +1271,7 @@ int bh_swd_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax, cons
 {
     int rc;
     if ((rc = check_models(e, B, Lmax, sl, sb))) return rc;
-    if ((rc = swd_supported(e, K, iwave, mode, flsph))) return rc;
+    if ((rc = swd_supported(e, K, iwave, igr, mode, flsph))) return rc;
     if (!nlay || !h || !vp || !vs || !rho || !periods || !vel || !err) return fail(e, BH_EINVAL, "null argument");
     if (B == 0) return BH_OK;
     HIPCHK(e, hipSetDevice(e->device));
@@ -1314,7 +1362,7 @@ int bh_targets_set(bh_engine *e, int nt, const bh_target_desc *td)
             rc = fail(e, BH_EINVAL, "unknown covariance law");
         if (!rc && d.kind == BH_TARGET_SWD) {
             if (!d.x) rc = fail(e, BH_EINVAL, "SWD target needs periods x");
-            if (!rc) rc = swd_supported(e, d.n > BH_MAX_PERIODS ? BH_MAX_PERIODS : d.n, d.iwave, d.mode, d.flsph);
+            if (!rc) rc = swd_supported(e, d.n > BH_MAX_PERIODS ? BH_MAX_PERIODS : d.n, d.iwave, t.d.igr, d.mode, d.flsph);
         } else if (!rc && d.kind == BH_TARGET_RF) {
             rc = rf_args_ok(e, d.nsamp, d.n, d.gauss, d.fsamp, d.waveno);
         } else if (!rc && d.kind == BH_TARGET_USER) {

@@ -157,7 +157,9 @@ int bh_engine_synchronize(bh_engine *e);
 
 /* ---- surface-wave dispersion: replaces surfdisp96 (surfdisp96.f:55-360) -----------------
  * For each of B models: velocities at K <= 60 periods [s] for wave type `iwave`, velocity
- * type `igr`, modes 1..`mode` computed in turn with the values of the last one returned
+ * type `igr` (0 phase velocity, any value > 0 group velocity as in surfdisp96.f:77, :232, :282;
+ * a negative value is refused with BH_EINVAL -- bh_targets_set reads bh_target_desc::igr the same
+ * way), modes 1..`mode` computed in turn with the values of the last one returned
  * (surfdisp96.f:219-357; a higher mode that finds no root leaves zeros and does not set err,
  * :313), flat (`flsph` = 0) or earth-flattened (`flsph` = 1, surfdisp96.f:486-553) model.
  * Results are bit-identical to the reference, with or without the flattening transform.

@@ -124,12 +124,18 @@ def test_parity_statistics_lvz_rich(engine, oracle):
 
 
 def test_bad_arguments_fail_loudly(engine):
+    from bayhunter_amd import engine as E
     from bayhunter_amd.engine import EngineError
     nlay, h, vp, vs, rho = synth_models(np.random.RandomState(1), 2, 3)
     with pytest.raises(EngineError):
         engine.swd_batch(nlay, h, vp, vs, rho, np.linspace(1, 100, 61), 2, 0)  # > 60 periods (NP = 60)
     with pytest.raises(EngineError):
         engine.swd_batch(nlay, h, vp, vs, rho, np.linspace(1, 30, 5), 3, 0)    # iwave must be 1 or 2
+    with pytest.raises(EngineError):
+        engine.swd_batch(nlay, h, vp, vs, rho, np.linspace(1, 30, 5), 2, -1)   # igr must be 0 or > 0
+    per = np.linspace(1, 30, 5)
+    with pytest.raises(EngineError):
+        engine.set_targets([{"kind": E.TARGET_SWD, "law": E.LAW_NOCORR, "n": 5, "x": per, "yobs": 3.4 + 0 * per, "iwave": 2, "igr": -1}])
 
 
 @pytest.mark.parametrize("mode", [2, 3])
@@ -351,3 +357,33 @@ def test_group_velocity_chains_as_two_launches_return_the_same_bits(engine, orac
                 assert np.array_equal(v, ov), (B, cap)
     finally:
         engine.set_tuning("swd_gsplit", 1 << 24)
+
+
+def test_any_positive_igr_is_a_group_velocity(engine, oracle):
+    """igr > 0 means group velocity, as in the reference (surfdisp96.f:77, :232, :282): bh_swd_batch and bh_targets_set read
+    igr = 2 or 7 as igr = 1, split in two launches or not (swd_gsplit), and a call of two group-velocity targets registered
+    as igr = 1 and igr = 2 returns what it returns with both set to 1."""
+    from bayhunter_amd import engine as E
+    rs = np.random.RandomState(91)
+    nlay, h, vp, vs, rho = synth_models(rs, 300, 12, lvz_frac=0.3, ragged=True)
+    per = np.sort(rs.uniform(1.5, 70.0, 21))
+    assert engine.tuning("swd_gsplit") == 1 << 24
+    try:
+        for iwave in (1, 2):
+            ov, oe, _ = oracle.swd_batch(nlay, h.T, vp.T, vs.T, rho.T, per, iwave, 1)
+            for cap in (0, 1 << 24):
+                engine.set_tuning("swd_gsplit", cap)
+                for igr in (1, 2, 7):
+                    v, e = engine.swd_batch(nlay, h, vp, vs, rho, per, iwave, igr)
+                    assert np.array_equal(e, oe), (iwave, cap, igr)
+                    assert np.array_equal(v, ov), (iwave, cap, igr)
+    finally:
+        engine.set_tuning("swd_gsplit", 1 << 24)
+    noise = np.tile(np.array([0.0, 0.05, 0.0, 0.05]), (nlay.size, 1))
+    out = []
+    for igr2 in (1, 2):
+        engine.set_targets([{"kind": E.TARGET_SWD, "law": E.LAW_NOCORR, "n": per.size, "x": per, "yobs": 3.4 + 0.01 * per, "iwave": 2, "igr": 1},
+                            {"kind": E.TARGET_SWD, "law": E.LAW_NOCORR, "n": per.size, "x": per, "yobs": 3.2 + 0.01 * per, "iwave": 1, "igr": igr2}])
+        out.append(engine.evaluate_batch(nlay, h, vp, vs, noise, want_ymod=True))
+    for a, b in zip(*out):  # logL, misfits, err, ymod: the same bits
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
