@@ -221,6 +221,15 @@ struct RfKernelArgs {
     int coef_small; // 1: the 96-register build of the coefficient kernel (fused call: resident beside the dispersion wavefronts)
     int no_rot;    // experiment switch: 1 = no rotation of the bins over a workgroup's wavefronts
 };
+// Receiver-function parameters per site (bh_sites_set_rf, include/bh_engine_sites_rf.h): the coefficient kernels give a model of
+// site s the ray parameter p[s * ld] and near-surface velocity nsv[s * ld] instead of RfKernelArgs::p_s_per_deg / nsv (the
+// synthesis kernel reads p from the record).  A site out of range reads nothing of the table and marks the record bad.
+struct RfSiteArgs {
+    const int32_t *site;    // device [B]: site of every model
+    int nsites;
+    int ld;                 // row stride of the tables (the number of targets)
+    const double *p, *nsv;  // device [nsites][ld], already offset to the target's column
+};
 size_t bh_rf_coef_doubles(int Lmax);
 // LDS of one workgroup of the synthesis kernel for traces of nsamp samples; a CU has 160 KB, one workgroup may use all
 constexpr size_t BH_RF_MAX_LDS = 160 * 1024;
@@ -228,7 +237,8 @@ constexpr size_t BH_RF_MAX_LDS = 160 * 1024;
 // butterflies there; the largest transform served (the second twiddle table, nsamp / 128 entries, stays in LDS)
 constexpr int BH_RF_MAX_NSAMP = 1 << 18;
 size_t bh_rf_lds_bytes(int nsamp);
-int bh_launch_rf(const RfKernelArgs &a, hipStream_t stream); // 0, or -1 when the trace does not fit a workgroup's LDS
+// 0, or -1 when the trace does not fit a workgroup's LDS; sites: null, or the site-indexed coefficient kernels
+int bh_launch_rf(const RfKernelArgs &a, hipStream_t stream, const RfSiteArgs *sites = nullptr);
 // bh_probe_math ops 11-16: the synthesis kernel's own elementary functions (include/bh_engine_debug.h); -1 for another op
 int bh_launch_rf_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 

@@ -6,6 +6,7 @@
 // HIP device is usable, bh_engine_create fails.
 #include "../../include/bh_engine_debug.h"
 #include "../../include/bh_engine_sites.h"
+#include "../../include/bh_engine_sites_rf.h"
 #include "bh_device.h"
 
 #include <cmath>
@@ -137,6 +138,9 @@ struct bh_engine {
     int nsites = 0;
     DevBuf site_yobs, site_yerr, site_logdet; // [nsites][ldy], [nsites][ldy] (law-1 columns), [nsites][nt]
     DevBuf site_idx;                          // host calls: the site index of every model, staged
+    // receiver-function parameters per site (bh_sites_set_rf, include/bh_engine_sites_rf.h): part of the site table
+    bool site_rf = false;
+    DevBuf site_p, site_nsv;                  // [nsites][nt]: p (s/deg) and nsv of every site, read in the RF columns only
     // instrumentation
     bool timing = false, counting = false;
     bool no_mfma = false; // BH_NO_MFMA env: Gauss law through the in-kernel mat-vec (A/B testing)
@@ -218,8 +222,9 @@ void release_target(TargetHost &t)
 // the site table's buffers (they belong to the registered targets: bh_targets_set and bh_engine_destroy release them)
 void release_sites(bh_engine *e)
 {
-    for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx}) release(*b);
+    for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx, &e->site_p, &e->site_nsv}) release(*b);
     e->nsites = 0;
+    e->site_rf = false;
 }
 
 // Targets.py:124-128, the nocorr_scalederr law: out = yerr / min(yerr), returns ln prod(out) (bh_targets_set, bh_sites_set)
@@ -884,7 +889,7 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
 int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl,
               ptrdiff_t sb, double p, double gauss, int nsamp, double fsamp, double tshift,
               double nsv, int waveno, int nkeep, double *rf, int ldr, bool beside_swd = false, const double *yobs = nullptr,
-              double *sums = nullptr)
+              double *sums = nullptr, const RfSiteArgs *sites = nullptr)
 {
     if (B == 0) return BH_OK;
     int rc;
@@ -914,7 +919,7 @@ int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, pt
     }
     a.coef_small = (beside_swd && e->rf_gated_now && bh_tuning().rf_coef_big == 0) ? 1 : 0;
     ev_begin(e, 1, st);
-    const int lrc = bh_launch_rf(a, st);
+    const int lrc = bh_launch_rf(a, st, sites);
     ev_end(e, 1, st);
     if (lrc != 0) return fail(e, BH_EUNSUPPORTED, "receiver function: nsamp above 262144 is not supported");
     HIPCHK(e, hipGetLastError());
@@ -1567,9 +1572,13 @@ int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const in
         // (sites: the trace goes to the ymod workspace and the site-indexed likelihood kernel forms the sums)
         T.fused = !ymod && !site && bh_tuning().rf_no_fuse == 0 && (d.law == BH_LAW_NOCORR || d.law == BH_LAW_EXP) && bh_tuning().rf_threads != 128;
         if (T.fused && (rc = ensure(e, T.sums, (size_t)B * 4 * sizeof(double)))) return rc;
+        // (sites with their own p / nsv, bh_sites_set_rf: the coefficient kernels read them from the table, column t)
+        const bool rf_table = site && e->site_rf;
+        RfSiteArgs rs{};
+        if (rf_table) rs = RfSiteArgs{site, e->nsites, nt, (const double *)e->site_p.p + t, (const double *)e->site_nsv.p + t};
         rc = launch_rf(e, rst, B, Lmax, m, sl, sb, d.p_s_per_deg, d.gauss, d.nsamp, d.fsamp, d.tshift,
                        d.nsv, d.waveno, d.n, ymod_d + T.off, ldy, fork, T.fused ? (const double *)T.yobs.p : nullptr,
-                       T.fused ? (double *)T.sums.p : nullptr);
+                       T.fused ? (double *)T.sums.p : nullptr, rf_table ? &rs : nullptr);
         if (rc) return rc;
     }
     if (fork) {
@@ -1645,6 +1654,31 @@ int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yer
         return fail(e, BH_EHIP, "copy site table");
     }
     e->nsites = nsites;
+    return BH_OK;
+}
+
+int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const double *nsv)
+{
+    if (!e) return BH_EINVAL;
+    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (nsites != e->nsites) return fail(e, BH_EINVAL, "bh_sites_set_rf: nsites differs from the site table's");
+    if (!p_s_per_deg || !nsv) return fail(e, BH_EINVAL, "null argument");
+    const int nt = e->nt;
+    const size_t n = (size_t)nsites * (size_t)nt;
+    for (int t = 0; t < nt; ++t) {
+        if (e->targets[(size_t)t].d.kind != BH_TARGET_RF) continue;
+        for (int s = 0; s < nsites; ++s)
+            if (!std::isfinite(p_s_per_deg[(size_t)s * nt + t]) || !std::isfinite(nsv[(size_t)s * nt + t]))
+                return fail(e, BH_EINVAL, "bh_sites_set_rf: a receiver-function column holds a non-finite value");
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->site_rf = false;
+    int rc;
+    if ((rc = ensure(e, e->site_p, n * sizeof(double))) || (rc = ensure(e, e->site_nsv, n * sizeof(double)))) return rc;
+    HIPCHK(e, hipMemcpy(e->site_p.p, p_s_per_deg, n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->site_nsv.p, nsv, n * sizeof(double), hipMemcpyHostToDevice));
+    e->site_rf = true;
     return BH_OK;
 }
 

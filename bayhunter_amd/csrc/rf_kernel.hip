@@ -374,125 +374,17 @@ __device__ __forceinline__ cd rf_one_frequency(const double *__restrict__ rec, i
     return v * cq;
 }
 
+// The coefficient record, one lane per model (body: rf_coef_body.inc; SITES: the site-indexed p and nsv of bh_sites_set_rf)
 __global__ __launch_bounds__(256) void rf_coef_kernel(RfKernelArgs A)
 {
-    const int ib = blockIdx.x * blockDim.x + threadIdx.x;
-    if (ib >= A.B) return;
-    const int Lmax = A.Lmax;
-    double *rec = A.coef + (size_t)ib * rec_doubles(Lmax);
-    const int nlay = A.nlay[ib];
-    const ptrdiff_t base = (ptrdiff_t)ib * A.sb;
-    const double R = 6371.0;
-    const double p = A.p_s_per_deg * 0.00899; // wrap.cpp:55
-    const double p2 = p * p;
-    double bad = 0.0;
-    double nf = 0.0; // stays 0 while every coefficient of the record is finite
-    double im = 0.0; // stays 0 while every interface matrix is real
-
-    // top-layer quantities before flattening (q = 1 for the top layer anyway)
-    const double vp0 = A.vp[base], vs0 = A.vs[base];
-    // rfmini_modrf.py:125-130 and wrap.cpp:13,73-74
-    const double kap = vp0 / vs0;
-    const double poisson = (2 - kap * kap) / (2 - 2 * (kap * kap));
-    const double nsv = (A.nsv > 0.0) ? A.nsv : vs0;
-    const double vptop = nsv * sqrt((1. - poisson) / (.5 - poisson));
-    const double vstop = nsv;
-
-    // flatten layer by layer (model.cpp:221-252); z = depth of the layer top = running sum of h
-    double ztop = 0.0, t0 = 0.0;
-    double pvp = 0, pvs = 0, prh = 0; // previous (upper) layer, flattened
-    for (int l = 0; l < nlay; ++l) {
-        const ptrdiff_t o = base + (ptrdiff_t)l * A.sl;
-        // thickness the way synrf.cpp:28-32 forms it from the depths z = cumsum(h)
-        // (rfmini_modrf.py:119-123): z[l+1] - z[l]; the half-space gets -1
-        const double znext = ztop + A.h[o];
-        const bool half = (l == nlay - 1);
-        double hh = half ? -1.0 : (znext - ztop);
-        double vp = A.vp[o], vs = A.vs[o], rh = A.rho[o];
-        const double qp = A.qp ? A.qp[o] : 500.0, qs = A.qs ? A.qs[o] : 225.0;
-        const double zb = ztop + hh;
-        double r = R - ztop;
-        double q = R / r;
-        const double zf = R * log(q);
-        vp *= q;
-        vs *= q;
-        rh /= q;
-        const bool lower_halfspace = !(hh > 0.0) && !(vp < 1.0 && rh < 0.1);
-        if (!lower_halfspace) {
-            r = R - zb;
-            q = R / r;
-            hh = R * log(q) - zf;
-        }
-        double *lay = rec + REC_HEAD + 8 * l;
-        lay[0] = 1.0 / (vp * vp); lay[1] = 1.0 / (vs * vs); lay[2] = hh;
-        lay[3] = 1.0 / (M_PI * qp); lay[4] = 1.0 / (2.0 * qp); lay[5] = 1.0 / (M_PI * qs); lay[6] = 1.0 / (2.0 * qs);
-        for (int k = 0; k < 7; ++k) nf += nf1(lay[k]);
-        // direct-wave delay (greens.cpp:510-526); only its NaN-ness can reach the RF
-        const double vv = (A.waveno == 0) ? vp : vs;
-        t0 += hh * sqrt(1. / (vv * vv) - p2);
-        if (l == 0) {
-            // free surface, greens.cpp:87-112 (plain sqrt) and displacement matrix :307-322
-            const cd a = csqrt_d(C(1. / (vp * vp) - p2));
-            const cd b = csqrt_d(C(1. / (vs * vs) - p2));
-            const double t1 = 2. * vs * vs;
-            const double t2 = t1 * p2 - 1.;
-            const cd d1 = C(t2 * t2);
-            const cd d2 = (t1 * t1 * p2) * a * b;
-            const cd d = d1 + d2;
-            const cd t3 = C(2. * t1 * p * t2) / d;
-            cm2 ru;
-            ru.c11 = (d2 - d1) / d;
-            ru.c12 = -(b * t3);
-            ru.c21 = a * t3;
-            ru.c22 = ru.c11;
-            store_cm2(rec + 16, ru);
-            const double vp2 = vp * vp, vs2 = vs * vs, x = 1. - 2. * vs2 * p2;
-            const cd a1 = conj(a), b1 = conj(b);
-            const cd qq = crecip(C(x * x) + (4. * vs2 * vs2 * p2) * a1 * b1);
-            cm2 hm;
-            hm.c11 = qq * a1 * b1 * (2. * vs2 * p);
-            hm.c12 = qq * b1 * (1. - 2. * vs2 * p2);
-            hm.c21 = qq * a1 * (1. - 2. * vs2 * p2);
-            hm.c22 = -(qq * a1 * b1 * (2. * vs2 * p));
-            hm.c11 = 2.0 * hm.c11; hm.c12 = 2.0 * hm.c12; hm.c21 = 2.0 * hm.c21; hm.c22 = 2.0 * hm.c22;
-            store_cm2(rec + 8, hm);
-            nf += nonfinite(ru) + nonfinite(hm);
-            im += imag_mass(ru);
-            (void)vp2;
-        } else {
-            cm2 rd, td, ru, tu;
-            interface_coeffs(p, pvp, pvs, prh, vp, vs, rh, rd, td, ru, tu);
-            double *ic = rec + REC_HEAD + 8 * Lmax + 32 * (l - 1);
-            store_cm2(ic, rd);
-            store_cm2(ic + 8, td);
-            store_cm2(ic + 16, ru);
-            store_cm2(ic + 24, tu);
-            nf += nonfinite(rd) + nonfinite(td) + nonfinite(ru) + nonfinite(tu);
-            im += imag_mass(rd) + imag_mass(td) + imag_mass(ru) + imag_mass(tu);
-        }
-        pvp = vp; pvs = vs; prh = rh;
-        ztop = znext;
-    }
-    if (t0 != t0) bad = 1.0;
-    if (nlay < 2) bad = 1.0; // the reference reads an uninitialised matrix here
-    // rotation Z/R -> P/SV with REAL vertical slownesses (greens.cpp:324-341)
-    double do_decomp = 0.0, m11 = 0, m12 = 0, m21 = 0, m22 = 0;
-    if (vstop > 0.01 && fabs(p) > 0.0001) {
-        do_decomp = 1.0;
-        const double aa = sqrt(1. / (vptop * vptop) - p * p), bb = sqrt(1. / (vstop * vstop) - p * p);
-        m11 = -(2 * vstop * vstop * p * p - 1.) / (vptop * aa);
-        m12 = 2. * p * vstop * vstop / vptop;
-        m21 = -2. * p * vstop;
-        m22 = (1. - 2. * vstop * vstop * p * p) / (vstop * bb);
-        nf += nf1(m11) + nf1(m12) + nf1(m21) + nf1(m22);
-    }
-    // A non-finite coefficient makes every bin of the reference's spectrum non-finite, hence the whole trace (the
-    // inverse FFT sums all bins); with the spectral cut-off the bins above it are not formed here, so the record
-    // carries the flag instead of relying on the propagation
-    if (nf != 0.0) bad = 1.0;
-    rec[0] = (double)nlay; rec[1] = p; rec[2] = do_decomp; rec[3] = bad;
-    rec[4] = m11; rec[5] = m12; rec[6] = m21; rec[7] = m22;
-    rec[REC_HEAD + 40 * (size_t)Lmax] = (im == 0.0) ? 1.0 : 0.0;
+    constexpr bool SITES = false;
+    const RfSiteArgs S{};
+#include "rf_coef_body.inc"
+}
+__global__ __launch_bounds__(256) void rf_coef_sites_kernel(RfKernelArgs A, RfSiteArgs S)
+{
+    constexpr bool SITES = true;
+#include "rf_coef_body.inc"
 }
 
 // The same record with LP lanes per model, lane l = layer l (LP = 16 or 32 >= Lmax): the serial kernel above is a
@@ -500,8 +392,9 @@ __global__ __launch_bounds__(256) void rf_coef_kernel(RfKernelArgs A)
 // the receiver function's time); here every layer's flattening and the interface above it are one lane's work.
 // Same operations per layer: the depth of a layer's top is the reference's running sum, formed in its order; the
 // direct-wave delay is summed by the model's first lane in layer order.  (The Nyquist bin is the synthesis kernel's.)
-template <int LP>
-__device__ __forceinline__ void rf_coef_layers_body(const RfKernelArgs &A)
+// SITES: as in rf_coef_body.inc -- p becomes a value per model (with LP = 16 a wavefront holds four models); the first lane reads nsv.
+template <int LP, bool SITES>
+__device__ __forceinline__ void rf_coef_layers_body(const RfKernelArgs &A, const RfSiteArgs &S)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int ibr = t / LP, l = t % LP, lane = threadIdx.x & 63, lbase = lane - l;
@@ -512,7 +405,12 @@ __device__ __forceinline__ void rf_coef_layers_body(const RfKernelArgs &A)
     const int nlay = A.nlay[ib];
     const ptrdiff_t base = (ptrdiff_t)ib * A.sb;
     const double R = 6371.0;
-    const double p = A.p_s_per_deg * 0.00899; // wrap.cpp:55
+    double p_sd = A.p_s_per_deg;
+    if (SITES) {
+        const int s = S.site[ib];
+        if (s >= 0 && s < S.nsites) p_sd = S.p[(size_t)s * S.ld];
+    }
+    const double p = p_sd * 0.00899; // wrap.cpp:55
     const double p2 = p * p;
     const bool on = vm && l < nlay;
     const int lc = (l < nlay) ? l : (nlay > 0 ? nlay - 1 : 0);
@@ -604,7 +502,12 @@ __device__ __forceinline__ void rf_coef_layers_body(const RfKernelArgs &A)
         const double vp0 = A.vp[base], vs0 = A.vs[base];
         const double kap = vp0 / vs0;
         const double poisson = (2 - kap * kap) / (2 - 2 * (kap * kap));
-        const double nsv = (A.nsv > 0.0) ? A.nsv : vs0;
+        // (the site index is read again here rather than kept live through the interface computation: the _small build's
+        // 96 registers)
+        const int site = SITES ? S.site[ib] : 0;
+        const bool off_table = SITES && (site < 0 || site >= S.nsites);
+        const double nsv_in = (SITES && !off_table) ? S.nsv[(size_t)site * S.ld] : A.nsv;
+        const double nsv = (nsv_in > 0.0) ? nsv_in : vs0;
         const double vptop = nsv * sqrt((1. - poisson) / (.5 - poisson));
         const double vstop = nsv;
         double bad = 0.0;
@@ -624,6 +527,7 @@ __device__ __forceinline__ void rf_coef_layers_body(const RfKernelArgs &A)
         // non-finite coefficients anywhere in the record: the whole trace is non-finite in the reference (see rf_coef_kernel)
         nfall += nonfinite(ru) + nonfinite(hm);
         if (nfall != 0.0) bad = 1.0;
+        if (SITES && off_table) bad = 1.0;
         rec[0] = (double)nlay; rec[1] = p; rec[2] = do_decomp; rec[3] = bad;
         rec[4] = m11; rec[5] = m12; rec[6] = m21; rec[7] = m22;
         rec[REC_HEAD + 40 * (size_t)Lmax] = (imall + imag_mass(ru) == 0.0 && nfall == 0.0) ? 1.0 : 0.0;
@@ -633,7 +537,12 @@ __device__ __forceinline__ void rf_coef_layers_body(const RfKernelArgs &A)
 template <int LP>
 __global__ __launch_bounds__(256) void rf_coef_layers_kernel(RfKernelArgs A)
 {
-    rf_coef_layers_body<LP>(A);
+    rf_coef_layers_body<LP, false>(A, RfSiteArgs{});
+}
+template <int LP>
+__global__ __launch_bounds__(256) void rf_coef_layers_sites_kernel(RfKernelArgs A, RfSiteArgs S)
+{
+    rf_coef_layers_body<LP, true>(A, S);
 }
 // The same with at most 96 registers (a few spilled): in the fused call the coefficient kernel is dispatched behind
 // the start gate, when two dispersion wavefronts of 208 registers sit on every SIMD -- the 124-register build could
@@ -642,7 +551,12 @@ __global__ __launch_bounds__(256) void rf_coef_layers_kernel(RfKernelArgs A)
 template <int LP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void rf_coef_layers_kernel_small(RfKernelArgs A)
 {
-    rf_coef_layers_body<LP>(A);
+    rf_coef_layers_body<LP, false>(A, RfSiteArgs{});
+}
+template <int LP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void rf_coef_layers_sites_kernel_small(RfKernelArgs A, RfSiteArgs S)
+{
+    rf_coef_layers_body<LP, true>(A, S);
 }
 
 // Spectrum of one model into LDS, then the inverse real FFT there:
@@ -857,7 +771,7 @@ size_t bh_rf_lds_bytes(int nsamp)
     return (size_t)(nsamp / 2) * 16 + 16 + 64 * 16 + (size_t)(nsamp >= 128 ? nsamp / 128 : 1) * 16;
 }
 
-int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream)
+int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs *sites)
 {
     RfKernelArgs a = a_in;
     const BhTuning &tun = bh_tuning(); // (experiment switches, bh_tuning.h)
@@ -880,7 +794,19 @@ int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream)
         const void *k[2] = {reinterpret_cast<const void *>(rf_synth_kernel), reinterpret_cast<const void *>(rf_synth_kernel_w3)};
         if (!bh_allow_big_lds(&allowed, k, 2, (int)BH_RF_MAX_LDS)) return -1;
     }
-    if (a.Lmax <= 16 && a.coef_small)
+    if (sites) { // (the same choice of build, each with its site variant)
+        const RfSiteArgs s = *sites;
+        if (a.Lmax <= 16 && a.coef_small)
+            hipLaunchKernelGGL((rf_coef_layers_sites_kernel_small<16>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a, s);
+        else if (a.Lmax <= 32 && a.coef_small)
+            hipLaunchKernelGGL((rf_coef_layers_sites_kernel_small<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a, s);
+        else if (a.Lmax <= 16)
+            hipLaunchKernelGGL((rf_coef_layers_sites_kernel<16>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a, s);
+        else if (a.Lmax <= 32)
+            hipLaunchKernelGGL((rf_coef_layers_sites_kernel<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a, s);
+        else
+            hipLaunchKernelGGL(rf_coef_sites_kernel, dim3((a.B + 255) / 256), dim3(256), 0, stream, a, s);
+    } else if (a.Lmax <= 16 && a.coef_small)
         hipLaunchKernelGGL((rf_coef_layers_kernel_small<16>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a);
     else if (a.Lmax <= 32 && a.coef_small)
         hipLaunchKernelGGL((rf_coef_layers_kernel_small<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a);

@@ -139,6 +139,7 @@ def load_library():
     L.bh_loglike_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bh_probe_math.argtypes = [vp, C.c_int, C.c_int, _d, _d]
     L.bh_sites_set.argtypes = [vp, C.c_int, vp, vp]
+    L.bh_sites_set_rf.argtypes = [vp, C.c_int, vp, vp]
     L.bh_evaluate_sites.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                     C.c_ssize_t, C.c_ssize_t, vp, vp, vp, vp, vp, vp]
     L.bh_chain_propose.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int]
@@ -157,7 +158,7 @@ def load_library():
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
-                 "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites"):
+                 "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf"):
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -179,6 +180,8 @@ DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_e
                  "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace")
 # include/bh_engine_sites.h: many stations at once (site-indexed observed data)
 SITE_SYMBOLS = ("bh_sites_set", "bh_evaluate_sites")
+# include/bh_engine_sites_rf.h: receiver-function ray parameter and near-surface velocity per site
+SITE_RF_SYMBOLS = ("bh_sites_set_rf",)
 # include/bh_engine_posterior.h: posterior velocity-depth summaries of many sites (bayhunter_amd/posterior.py)
 POSTERIOR_SYMBOLS = ("bh_posterior_create", "bh_posterior_destroy", "bh_posterior_load", "bh_posterior_columns",
                      "bh_posterior_hist", "bh_posterior_interfaces")
@@ -522,6 +525,15 @@ class Engine(object):
                 raise ValueError("yerr must have the shape of yobs")
         self._check(self._L.bh_sites_set(self._h, yobs.shape[0], _ptr(yobs), _ptr(yerr)))
         self.nsites = yobs.shape[0]
+
+    def set_sites_rf(self, p, nsv):
+        """Receiver-function ray parameter p (s/deg) and near-surface velocity nsv (<= 0: the model's top-layer vs) of every
+        site (bh_sites_set_rf): float64 arrays [nsites, ntargets], read in the columns of receiver-function targets only.
+        evaluate_sites then gives a model its site's values; set_sites and set_targets drop them."""
+        p, nsv = _f64(p), _f64(nsv)
+        if p.ndim != 2 or p.shape[1] != self.ntargets or nsv.shape != p.shape:
+            raise ValueError("p and nsv must have shape (nsites, %d)" % self.ntargets)
+        self._check(self._L.bh_sites_set_rf(self._h, p.shape[0], _ptr(p), _ptr(nsv)))
 
     def evaluate_sites(self, nlay, h, vp, vs, noise, site, rho=None, layout="layer_major", want_ymod=False):
         """evaluate_batch with model b compared with the observed data of site site[b] (bh_evaluate_sites).  Returns (logL[B],

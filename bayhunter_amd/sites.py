@@ -4,7 +4,9 @@ Stations of one array (or nodes of a tomography grid) usually share the periods 
 receiver-function parameters and their noise laws; they differ only in the observed values y (and sometimes in yerr).
 The forward models depend on the model and x only, so one evaluation batch may mix models of many sites, each compared
 with the observed data of its own site (include/bh_engine_sites.h).  `SiteTargets` holds one `JointTarget` per site and
-registers site 0's target descriptors plus the table of every site's observed data on the engine.
+registers site 0's target descriptors plus the table of every site's observed data on the engine.  The ray parameter p and
+near-surface velocity nsv of the receiver functions may differ between sites as well (per_site_rf=True,
+include/bh_engine_sites_rf.h): they enter only the coefficient stage of the forward model.
 """
 import numpy as np
 
@@ -24,13 +26,22 @@ def _bits(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).tobytes()
 
 
+# the receiver-function call arguments that may differ between sites with per_site_rf=True (RFminiModRF._call_args)
+SITE_RF_ARGS = ("p", "nsv")
+
+
 class SiteTargets(object):
     """One `JointTarget` per site, evaluated together.  Every site must have the same number and classes of targets, the
     same x (bit for bit), the same plugin parameters (SWD mode / flsph, every receiver-function call argument), the same
     installed noise law and -- Gauss law -- identical corr_inv and logcorr_det; only engine-backed plugins.  y and yerr
-    may differ.  The checks run when the sites are registered (the noise laws are installed by the sampler)."""
+    may differ.  The checks run when the sites are registered (the noise laws are installed by the sampler).
 
-    def __init__(self, jointtargets, names=None, engine=None):
+    per_site_rf=True: the receiver-function plugins of the sites may also differ in their ray parameter `p` and near-surface
+    velocity `nsv` (a station's slowness depends on the events it recorded); every other receiver-function argument (gauss,
+    nsamp, fsamp, tshift, wave type, nkeep) must still match.  Each model is then computed with its own site's p and nsv.
+    The default (False) rejects a differing p or nsv like any other mismatch."""
+
+    def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False):
         self._sites = [jt if isinstance(jt, JointTarget) else JointTarget(jt) for jt in jointtargets]
         if not self._sites:
             raise ValueError("SiteTargets needs at least one site")
@@ -38,6 +49,7 @@ class SiteTargets(object):
         if len(self._names) != len(self._sites) or len(set(self._names)) != len(self._names):
             raise ValueError("names must be %d distinct names, one per site" % len(self._sites))
         self._engine = engine
+        self.per_site_rf = bool(per_site_rf)
         for jt in self._sites:          # every site on one engine
             if jt._engine is None:
                 jt._engine = engine
@@ -103,6 +115,8 @@ class SiteTargets(object):
                         raise ValueError("%s: dispersion parameters (wave, velocity, mode, flsph) %r, site 0's %r" % (what, a, a0))
                 elif isinstance(p, RFminiModRF):
                     a, a0 = p._call_args(), p0._call_args()
+                    if self.per_site_rf:
+                        a, a0 = [{k: v for k, v in d.items() if k not in SITE_RF_ARGS} for d in (a, a0)]
                     if a != a0:
                         raise ValueError("%s: receiver-function parameters %r, site 0's %r" % (what, a, a0))
                 law, law0 = t.law(), t0.law()
@@ -124,6 +138,18 @@ class SiteTargets(object):
                           for jt in self._sites])
         return yobs, yerr
 
+    def site_rf_arrays(self):
+        """(p[S, nt], nsv[S, nt]): every site's receiver-function ray parameter (s/deg) and near-surface velocity (0: the
+        model's top-layer vs) in the columns of its receiver-function targets, 0 elsewhere (Engine.set_sites_rf)"""
+        S, nt = self.nsites, self.ntargets
+        p, nsv = np.zeros((S, nt)), np.zeros((S, nt))
+        for s, jt in enumerate(self._sites):
+            for i, t in enumerate(jt.targets):
+                if isinstance(t.moddata.plugin, RFminiModRF):
+                    a = t.moddata.plugin._call_args()
+                    p[s, i], nsv[s, i] = float(a["p"]), float(a["nsv"])
+        return p, nsv
+
     def _signature(self):
         """What the registration depends on, by identity as JointTarget._signature: every site's targets, plugins and laws,
         and the arrays of its x, y and yerr (O(sites x targets) per call; replacing an array re-registers)."""
@@ -141,6 +167,8 @@ class SiteTargets(object):
             e.set_targets([t.engine_desc() for t in self.targets])
             yobs, yerr = self.site_arrays()
             e.set_sites(yobs, yerr)
+            if self.per_site_rf:
+                e.set_sites_rf(*self.site_rf_arrays())
             e._owner = self
             self._registered = sig
             # the arrays the signature names stay alive while it is in force: their ids cannot be handed to replacements
