@@ -122,24 +122,24 @@ struct SwdMultiArgs {
     // batch whose array capacity (Lmax) is far above its typical depth still packs many models per
     // wavefront.  Both classes run in ONE launch (blockIdx.z = class) with the same LDS budget per
     // wavefront: the deep class simply takes fewer models per wavefront (more lanes per model).
-    // split == nullptr: one class (index 1), rows = Lmax.  rows[] / lanes[] are set by the launcher.
+    // split == nullptr: one class (index 1), rows = Lmax.  rows[] / lanes[]: the group plan's (bh_plan_swd_group).
     const int32_t *split;
     int Lcut;
     int rows[2], lanes[2]; // per class (0 = deep, 1 = the rest): LDS rows per model, lanes per model (G)
-    int wg_n0, wg_n1;      // set by the launcher: > 0 = one-dimensional grid of two targets, interleaved (wavefront counts)
+    int wg_n0, wg_n1;      // the launch plan's: > 0 = one-dimensional grid of two targets, interleaved (wavefront counts)
     unsigned long long *neval;
     unsigned *board;  // optional: progress board of the group kernel, 2 words per physical SIMD (BH_BOARD_WORDS), see the kernel
     unsigned stamp;   // launch stamp (16 bits) that marks this launch's entries of the board
     unsigned *started; // optional: every workgroup adds 1 when it starts (cumulative over launches): a second stream waits
                        // for "all workgroups of this launch are resident" before it dispatches work beside them
     int prio_low;      // s_setprio level of a wavefront's unfavoured phase (0; 1 when receiver-function wavefronts at 0 run beside it)
-    int fast;          // 1: the build with the short refinement (SearchT<.., FAST>; phase-velocity targets take it)
+    int fast;          // the build's sequences (SwdGroupBuild::fastm): 0 = reference, 1 = both, 2 = the short refinement only
     int adapt_ok;      // 1: a launch of one model per wavefront may let every wavefront size its lane groups and trials for its
                        // own model (swd_group_kernel<.., ADAPT>); 0: the caller fixed lanes or trials (experiments)
     int counted;       // 1: Love scans skip the steps a mode count proves empty (SearchT: the counted scan; same bits)
     int rerun;         // 1: the launch re-runs listed models (SwdTarget::count): plain two-dimensional grid, no SIMD pairing
     int farith;        // 1: launches in which every target takes the short refinement evaluate the secular functions with the fast
-                       //    arithmetic (swd_fa.h, swd_group_kernel<.., FA>); set to what took effect by the launcher
+                       //    arithmetic (swd_fa.h, swd_group_kernel<.., FA>); the group plan's decision
     int restart;       // 1: in a launch of one model per wavefront a model the guard fires on starts again with the reference's
                        //    sequence in its own wavefront (the build with both sequences) instead of being listed for a re-run launch
     SwdTarget t[8];
@@ -147,7 +147,7 @@ struct SwdMultiArgs {
 int bh_swd_pick_group(int B, int ntargets, int Lmax);
 double bh_swd_plan(int B, int Lmax, int ntargets, const int *iwave, int Gforce, int *G, int *look);
 size_t bh_swd_group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode);
-// Work space of the SIMD-pairing order (swd_kernel.hip: pair_order_kernel; swd_group_kernel.hip: the launcher).  The
+// Work space of the SIMD-pairing order (swd_kernel.hip: pair_order_kernel; bh_engine.hip: order_models).  The
 // dispersion kernel's time is that of its slowest SIMD, a SIMD's time follows the SUM of the root-search lengths of the
 // two wavefronts it holds, and which wavefronts of a launch share a SIMD is a fixed function of their grid index; so the
 // models are dealt to the wavefronts by PREDICTED search length such that every SIMD gets a long and a short wavefront
@@ -157,7 +157,7 @@ struct SwdPairWork {
     int32_t *perm[2] = {nullptr, nullptr};      // device, [B] each: processing order of target 0 / 1
     int32_t *slot_rank[2] = {nullptr, nullptr}; // device, [wavefronts of the target]: rank of the wavefront's load (0 = longest models)
     int cap_perm = 0, cap_rank[2] = {0, 0};
-    int key_n0 = -1, key_n1 = -1, key_wpb = -1; // geometry the slot_rank tables were built for
+    int key_n0 = -1, key_n1 = -1;     // wavefront counts the slot_rank tables were built for
 };
 struct PairOrderTarget {
     int mpw, nwaves;          // models per wavefront, wavefronts of the target
@@ -174,19 +174,59 @@ struct SwdLaunchInfo {
     unsigned workgroups; // of the launch (what SwdMultiArgs::started is advanced by)
     long waves;          // wavefronts that do work
     size_t lds;          // bytes per workgroup
-    int fast_arith;      // the launch evaluates with the fast arithmetic (SwdMultiArgs::farith took effect)
-    int restarts_in_place; // the launch handles guarded models itself (SwdMultiArgs::restart took effect): no re-run launch needed
+    int wpb;             // wavefronts per workgroup
 };
-// the launches of the builds with the fast arithmetic (swd_group_fa.hip); called by bh_launch_swd_group
-void bh_launch_swd_group_fa(const SwdMultiArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t stream, int redundant, int wave_lds,
-                            bool adapt, bool counted, bool cntb);
-// the launches of the one-model-per-wavefront builds (swd_group_adapt.hip); called by bh_launch_swd_group
-void bh_launch_swd_group_adapt(const SwdMultiArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t stream, int redundant, int wave_lds,
-                               int fm, bool pr, bool cn);
-// the launch of the build that needs one wavefront per SIMD as its register budget (swd_group_big.hip); called by bh_launch_swd_group
-void bh_launch_swd_group_big(const SwdMultiArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t stream, int redundant, int wave_lds);
-int bh_launch_swd_group(const SwdMultiArgs &a, int G, hipStream_t stream, SwdLaunchInfo *info = nullptr, int wavefronts_per_workgroup = 2,
-                        SwdPairWork *pair = nullptr);
+// Trials per round that fit a wavefront of G-lane groups: `look` (at least 1), fewer while G x trials exceeds a wavefront.
+inline int bh_trials_fit(int G, int look)
+{
+    int J = look > 1 ? look : 1;
+    while (J > 1 && G * J > BH_WAVE) --J;
+    return J;
+}
+// What one launch of the group kernel is asked for: its shape and the caller's requests (bh_plan_swd_group).
+struct SwdGroupAsk {
+    int B, Lmax, Lcut, ntargets; // Lcut < Lmax: two depth classes (SwdMultiArgs::split)
+    int G0;                      // lanes per model of the engine's plan
+    struct Target {
+        int K, look, iwave, mode;
+        bool group, refseq;      // a group velocity (igr != 0); SwdTarget::refseq
+    } t[8];                      // (as SwdMultiArgs::t)
+    bool fast, farith, restart;  // the short refinement, its fast arithmetic, restarts in place: asked for
+    bool adapt_ok, rerun;        // SwdMultiArgs::adapt_ok and ::rerun
+    bool counters;               // the build with counters and clocks (SwdMultiArgs::neval set)
+    int scan;                    // the counted scan asked for: 0, 1 = wherever a Love target is, 2 = where it pays
+};
+// Which instantiation of swd_group_kernel a launch takes (its template arguments but WPB).
+struct SwdGroupBuild {
+    int fastm;                          // FASTM: 0 = reference sequence, 1 = both sequences, 2 = short refinement only
+    bool simple, prof, adapt, cntb, fa; // SIMPLE, PROF (counters and clocks), ADAPT, CNTB (counted Love scan), FA
+};
+// Everything a launch of the group kernel does, decided by bh_plan_swd_group with no HIP call.
+struct SwdGroupPlan {
+    bool fits;               // false: a class's layers do not fit a workgroup's LDS (the call fails)
+    int rows[2], lanes[2];   // per class (0 = deep, 1 = the rest; one class: both the same): LDS rows, lanes per model
+    int wg_n0, wg_n1;        // > 0: the two targets' wavefronts interleaved in a one-dimensional grid (their counts)
+    size_t wave_lds, lds;    // LDS of a wavefront's region, of a workgroup
+    dim3 grid, block;
+    int Gflags;              // the kernel's experiment flags (bh_tuning.h swd_redundant, swd_no_board, swd_no_fair)
+    bool restart;            // guarded models restart in place (SwdMultiArgs::restart): no re-run launch follows
+    SwdGroupBuild build;
+    // SIMD-pairing geometry (SwdPairWork): pair = the launch admits the order (one class, a one-dimensional grid, at most two
+    // targets, a batch pair_order_kernel takes); per target its models per wavefront and wavefronts
+    bool pair;
+    int pair_mpw[2], pair_waves[2];
+    SwdLaunchInfo info;
+};
+struct BhTuning;
+SwdGroupPlan bh_plan_swd_group(const SwdGroupAsk &q, const BhTuning &tun);
+// The launch of plan g with arguments a (whose rows, lanes, wg_n*, fast, counted, farith and restart are g's).  Every build a plan
+// can name is compiled (tests/test_swd_group_plan.py).
+void bh_launch_swd_group(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stream);
+// The builds each translation unit of swd_group_kernel compiles (swd_group_fa.hip, swd_group_adapt.hip, swd_group_big.hip), one
+// signature: launches g's build if it is one of them.
+bool bh_swd_group_builds_fa(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stream);
+bool bh_swd_group_builds_adapt(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stream);
+bool bh_swd_group_builds_big(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stream);
 // swd_lean.hip: fundamental-mode phase velocities with the fast arithmetic, one lane per trial velocity (the kernel of the
 // engine's default settings for batches up to a few ten thousand models); a.t[t].look = trials per model and round
 int bh_swd_lean_trials(int B, int ntargets);

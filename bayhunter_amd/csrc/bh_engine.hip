@@ -9,6 +9,7 @@
 #include "../../include/bh_engine_sites_rf.h"
 #include "bh_device.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -121,7 +122,6 @@ struct bh_engine {
     int swd_trials = 0;                    // bh_engine_set_swd_trials: trials per round of the trial-per-lane kernel (0 = by the call's shape)
     int last_swd_kernel = -1;              // bh_engine_last_swd_kernel
     SwdLaunchInfo last_swd{};              // of the most recent group-kernel launch (workgroups == 0: none)
-    int last_swd_wpb = 2;                  // its wavefronts per workgroup
     int err_t_nt = -1, err_t_B = -1;       // layout for which err_t's untouched rows are known to be zero
     int swd_prio_low_now = 0;              // per call: what the next dispersion launch gets
     bool rf_gated_now = false;             // per call: the RF stream waits for the dispersion kernel's workgroups to be resident
@@ -506,8 +506,8 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
     // processing order: deepest models first, wavefronts of (nearly) one depth
     const bool ordered = B > 1 && tun.no_order == 0 && !e->as_given;
     const bool shallow_bulk = p.typ_layers > 0 && p.typ_layers + 2 < Lmax;
-    // One depth class, lanes per model > 1: the launcher orders the models itself, by predicted search length and paired
-    // over the SIMDs (SwdPairWork); mixed depths are ordered by depth there as well.
+    // One depth class, lanes per model > 1: the models by predicted search length, paired over the SIMDs (SwdPairWork; at
+    // the lanes the group kernel's plan launches, order_models); mixed depths are ordered by depth.
     // Measured (bench.py c2, B = 2048 ... 4096, same session with / without): -3 % at 4096 and -4 % at 3800, where the
     // launch nearly fills two wavefronts per SIMD and the Rayleigh wavefronts (look-ahead 2) outnumber the Love ones
     // (trials inside the lane groups) 7 : 3; neutral at 3500; +2.5 % at 2048 / 3072, where the planner gives both targets
@@ -516,9 +516,7 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
     if (ordered && !lean && tun.swd_no_pair == 0 && p.G > 1 && nlive == 2 && bh_pair_order_fits(B) && !shallow_bulk) {
         long plan_waves = 0, wmin = 0, wmax = 0;
         for (int t = 0; t < nlive; ++t) {
-            int J = look[t] > 1 ? look[t] : 1;
-            while (J > 1 && p.G * J > 64) --J;
-            const int mpw = 64 / (p.G * J);
+            const int mpw = BH_WAVE / (p.G * bh_trials_fit(p.G, look[t]));
             const long w = (B + mpw - 1) / mpw;
             plan_waves += w;
             wmin = (t == 0 || w < wmin) ? w : wmin;
@@ -580,6 +578,21 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
     return p;
 }
 
+// The group kernel's launch of a call planned by plan_swd (BH_KERNEL_GROUP)
+SwdGroupPlan plan_group(const bh_engine *e, const SwdPlan &p, int B, int Lmax, const SwdJob *jobs)
+{
+    SwdGroupAsk q{};
+    q.B = B; q.Lmax = Lmax; q.Lcut = p.Lcut; q.ntargets = p.ntargets; q.G0 = p.G;
+    for (int t = 0; t < p.ntargets; ++t) {
+        const SwdJob &J = jobs[p.job[t]];
+        q.t[t] = SwdGroupAsk::Target{J.K, p.look[t], J.iwave, J.mode, J.igr != BH_VEL_PHASE, p.refseq[t]};
+    }
+    q.fast = p.any_fast; q.farith = p.farith;
+    q.restart = true; // (takes effect in launches of one model per wavefront)
+    q.adapt_ok = p.adapt_ok; q.counters = e->counting; q.scan = e->swd_scan;
+    return bh_plan_swd_group(q, bh_tuning());
+}
+
 // One dispersion call as it is launched: its plan, the model arrays and work space the launches read.
 struct SwdCall {
     bh_engine *e; hipStream_t st;
@@ -587,7 +600,9 @@ struct SwdCall {
     const SwdJob *jobs; const SwdPlan &p;
     const double *sph = nullptr;         // flsph = 1: earth-flattened h, vp, vs, Love rho, Rayleigh rho, [Lmax][B] each
     double *first[BH_MAX_TARGETS] = {};  // per job of the chain of first roots: where the kernel keeps them (SwdKernelArgs::first)
+    SwdGroupPlan g{};                    // the group kernel's launch (BH_KERNEL_GROUP)
     const int32_t *perm = nullptr, *split = nullptr;
+    const int32_t *pair_perm[2] = {};    // ORDER_PAIR: the order of target 0 / 1 (SwdTarget::perm)
     unsigned long long *counter = nullptr;
     int32_t *gcounts = nullptr, *glists = nullptr; // the guard of the short refinement (guard_space)
 };
@@ -649,6 +664,82 @@ int wait_for(bh_engine *e, hipEvent_t ev, hipStream_t from, hipStream_t to)
     return BH_OK;
 }
 
+// The group kernel's decisions (bh_plan_swd_group) in its arguments a
+void set_group_args(SwdMultiArgs &a, const SwdGroupPlan &g)
+{
+    for (int k = 0; k < 2; ++k) {
+        a.rows[k] = g.rows[k];
+        a.lanes[k] = g.lanes[k];
+    }
+    a.wg_n0 = g.wg_n0;
+    a.wg_n1 = g.wg_n1;
+    a.fast = g.build.fastm;
+    a.counted = g.build.cntb ? 1 : 0;
+    a.farith = g.build.fa ? 1 : 0;
+    a.restart = g.restart ? 1 : 0;
+}
+
+// Load ranks of the wavefronts of a launch for the SIMD-pairing order (SwdPairWork).  Placement rule of the workgroup
+// dispatcher, read off the wavefront trace (tools/gpu_trace.py, MAP=...; identical from run to run): workgroup g of a
+// one-dimensional grid runs on CU g mod ncu in pass g / ncu, and its two wavefronts sit on SIMD (pass + j) mod 4 -- so SIMD
+// s of a CU holds wavefront 0 of its pass-s workgroup and wavefront 1 of its pass-(s-1) workgroup, and the SIMDs whose
+// partner workgroup does not exist (the last pass is not full) hold one wavefront only.
+// Every wavefront gets a wanted load quantile q (0 = longest models): 0 for a wavefront alone on its SIMD, u and 1 - u for
+// the two of a pair (u spread over (0, 1/2) across the pairs); per target the wavefronts are ranked by q.
+bool build_slot_ranks(int n0, int n1, int ncu, std::vector<int32_t> rank[2])
+{
+    const int NW = n0 + n1, nwg = (NW + 1) / 2;
+    if (ncu <= 0 || nwg > 4 * ncu) return false; // more than one round of workgroups: placement not fixed by the index
+    auto target_of = [&](int W, int &ty, int &wid) {
+        if (n1 > 0) {
+            const long long N = NW;
+            const int l0 = (int)(((long long)W * n1) / N), l1 = (int)((((long long)W + 1) * n1) / N);
+            ty = (l1 > l0) ? 1 : 0;
+            wid = (l1 > l0) ? l0 : W - l0;
+        } else {
+            ty = 0;
+            wid = W;
+        }
+    };
+    std::vector<int> on_simd[2]; // per (cu, simd): wavefront 0 / wavefront 1 member (grid wavefront index or -1)
+    on_simd[0].assign((size_t)ncu * 4, -1);
+    on_simd[1].assign((size_t)ncu * 4, -1);
+    for (int W = 0; W < NW; ++W) {
+        const int g = W / 2, j = W % 2, cu = g % ncu, pass = g / ncu, simd = (pass + j) % 4;
+        on_simd[j][(size_t)cu * 4 + simd] = W;
+    }
+    std::vector<double> q((size_t)NW, 0.0);
+    int npairs = 0;
+    for (size_t k = 0; k < on_simd[0].size(); ++k) npairs += (on_simd[0][k] >= 0 && on_simd[1][k] >= 0);
+    int ip = 0;
+    for (size_t k = 0; k < on_simd[0].size(); ++k) {
+        const int a = on_simd[0][k], b = on_simd[1][k];
+        if (a >= 0 && b >= 0) {
+            const double u = (ip + 0.5) / (2.0 * npairs);
+            q[(size_t)((ip & 1) ? a : b)] = u;        // (alternating which member takes the long share spreads the long
+            q[(size_t)((ip & 1) ? b : a)] = 1.0 - u;  //  models evenly over the two targets)
+            ++ip;
+        } else if (a >= 0) {
+            q[(size_t)a] = 0.0;
+        } else if (b >= 0) {
+            q[(size_t)b] = 0.0;
+        }
+    }
+    const int nw[2] = {n0, n1};
+    for (int t = 0; t < 2; ++t) {
+        std::vector<std::pair<double, int>> v;
+        for (int W = 0; W < NW; ++W) {
+            int ty, wid;
+            target_of(W, ty, wid);
+            if (ty == t && wid < nw[t] - 1) v.emplace_back(q[(size_t)W], wid); // (the last wavefront keeps the tail)
+        }
+        std::sort(v.begin(), v.end());
+        rank[t].assign((size_t)(nw[t] > 0 ? nw[t] : 1), 0);
+        for (size_t r = 0; r < v.size(); ++r) rank[t][(size_t)v[r].second] = (int32_t)r;
+    }
+    return true;
+}
+
 // Second launch of a call in BH_SEARCH_FAST: the models the guard fired on (per target: counts[t], lists + t * (B + 4)),
 // again, with the reference's sequence -- one model per wavefront, as many trials per round as its lanes admit.  The launch
 // is sized for the worst case and reads the counts on the device: workgroups beyond them leave at once (no host round trip;
@@ -656,37 +747,90 @@ int wait_for(bh_engine *e, hipEvent_t ev, hipStream_t from, hipStream_t to)
 int launch_swd_rerun(bh_engine *e, hipStream_t st, const SwdMultiArgs &main, int32_t *counts, int32_t *lists)
 {
     SwdMultiArgs a = main;
-    a.fast = 0;
     a.rerun = 1;
-    a.restart = 0;
     a.perm = nullptr;
     a.split = nullptr;
     a.Lcut = a.Lmax;
     a.started = nullptr;
     a.stamp = swd_stamp(e);
     a.adapt_ok = 1;
-    const int G = bh_swd_pick_group(a.B, a.ntargets, a.Lmax);
+    SwdGroupAsk q{};
+    q.B = a.B; q.Lmax = q.Lcut = a.Lmax; q.ntargets = a.ntargets;
+    q.G0 = bh_swd_pick_group(a.B, a.ntargets, a.Lmax);
     for (int t = 0; t < a.ntargets; ++t) {
-        a.t[t].perm = lists + (size_t)t * (size_t)(a.B + 4);
-        a.t[t].count = counts + t;
-        a.t[t].gcount = nullptr;
-        a.t[t].glist = nullptr;
-        a.t[t].look = 64 / G > 1 ? 64 / G : 1; // one model per wavefront
-        a.t[t].inlook = 1;
+        SwdTarget &T = a.t[t];
+        T.perm = lists + (size_t)t * (size_t)(a.B + 4);
+        T.count = counts + t;
+        T.gcount = nullptr;
+        T.glist = nullptr;
+        T.look = 64 / q.G0 > 1 ? 64 / q.G0 : 1; // one model per wavefront
+        T.inlook = 1;
+        q.t[t] = SwdGroupAsk::Target{T.K, T.look, T.iwave, T.mode, T.igr != 0, T.refseq != 0};
     }
-    SwdLaunchInfo info{};
-    const int lrc = bh_launch_swd_group(a, G, st, &info, 2, nullptr);
-    if (lrc != 0) return fail(e, BH_EINVAL, "model too deep for LDS");
+    q.adapt_ok = q.rerun = true; q.counters = a.neval != nullptr; q.scan = e->swd_scan;
+    const SwdGroupPlan g = bh_plan_swd_group(q, bh_tuning());
+    if (!g.fits) return fail(e, BH_EINVAL, "model too deep for LDS");
+    set_group_args(a, g);
+    bh_launch_swd_group(a, g, st);
     HIPCHK(e, hipGetLastError());
     ++e->rerun_launches;
     return BH_OK;
 }
 
-// The order the plan asks for, computed on the device: c.perm (and c.split for two depth classes).
+// The SIMD-pairing order (SwdPairWork) of the group kernel's launch c.g: c.pair_perm.  Placement tables are rebuilt when the
+// launch's wavefront counts change; where they cannot be made the order is the plain sorted one, where work space cannot be
+// allocated the models keep the caller's order.
+int pair_models(SwdCall &c)
+{
+    SwdPairWork &pw = c.e->pairwork;
+    const SwdGroupPlan &g = c.g;
+    const int nt = c.p.ntargets, B = c.B;
+    const int *n = g.pair_waves;
+    bool ok = true, geom = true;
+    if (pw.key_n0 != n[0] || pw.key_n1 != n[1]) { // (rare: the batch shape changed)
+        std::vector<int32_t> rank[2];
+        geom = build_slot_ranks(n[0], n[1], pw.ncu, rank); // false: placement unknown -> plain sorted order
+        for (int t = 0; ok && geom && t < nt; ++t) {
+            if (pw.cap_rank[t] < n[t]) {
+                if (pw.slot_rank[t]) (void)hipFree(pw.slot_rank[t]);
+                pw.slot_rank[t] = nullptr;
+                ok = hipMalloc((void **)&pw.slot_rank[t], (size_t)(n[t] + 64) * sizeof(int32_t)) == hipSuccess;
+                pw.cap_rank[t] = ok ? n[t] + 64 : 0;
+            }
+            if (ok) {
+                ok = hipStreamSynchronize(c.st) == hipSuccess && // (an earlier launch may still read the old table)
+                     hipMemcpy(pw.slot_rank[t], rank[t].data(), (size_t)n[t] * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+            }
+        }
+        pw.key_n0 = (ok && geom) ? n[0] : -1;
+        pw.key_n1 = (ok && geom) ? n[1] : -1;
+    }
+    if (ok && pw.cap_perm < B) {
+        for (int t = 0; t < 2; ++t) {
+            if (pw.perm[t]) (void)hipFree(pw.perm[t]);
+            pw.perm[t] = nullptr;
+            ok = ok && hipStreamSynchronize(c.st) == hipSuccess &&
+                 hipMalloc((void **)&pw.perm[t], (size_t)(B + B / 4 + 64) * sizeof(int32_t)) == hipSuccess;
+        }
+        pw.cap_perm = ok ? B + B / 4 + 64 : 0;
+    }
+    if (ok) {
+        PairOrderTarget tg[2];
+        for (int t = 0; t < nt; ++t) tg[t] = PairOrderTarget{g.pair_mpw[t], n[t], geom ? pw.slot_rank[t] : nullptr, pw.perm[t]};
+        const SwdTarget t0 = swd_target(c, c.p.job[0]); // (its S velocities predict the search lengths: flattened for flsph = 1)
+        bh_launch_pair_order(B, c.Lmax, c.m.nlay, t0.vs, t0.sl, t0.sb, nt, tg, c.st);
+        for (int t = 0; t < nt; ++t) c.pair_perm[t] = pw.perm[t];
+    }
+    (void)hipGetLastError();
+    return BH_OK;
+}
+
+// The order the plan asks for, computed on the device: c.perm (and c.split for two depth classes), or c.pair_perm.
 int order_models(SwdCall &c)
 {
     const SwdPlan &p = c.p;
-    if (p.order == ORDER_NONE || p.order == ORDER_PAIR) return BH_OK; // (the pairing order is the group kernel launcher's)
+    if (p.order == ORDER_NONE) return BH_OK;
+    if (p.order == ORDER_PAIR) return c.g.pair ? pair_models(c) : BH_OK; // (not in a two-dimensional grid: the caller's order)
     bh_engine *e = c.e;
     int rc;
     if ((rc = ensure(e, e->perm, ((size_t)c.B + 4) * sizeof(int32_t)))) return rc;
@@ -766,17 +910,23 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
         a.t[t].inlook = p.inlook[t];
         a.t[t].refseq = p.refseq[t] ? 1 : 0;
     }
-    a.counted = e->swd_scan;
-    a.farith = p.farith ? 1 : 0;
     a.started = e->started;
     a.prio_low = e->swd_prio_low_now;
     a.adapt_ok = p.adapt_ok ? 1 : 0;
-    a.fast = p.any_fast ? 1 : 0;
-    a.restart = 1; // (takes effect in launches of one model per wavefront: see bh_launch_swd_group)
+    const bool lean = p.kernel == BH_KERNEL_LEAN;
+    if (lean) {
+        a.counted = e->swd_scan;
+        a.farith = p.farith ? 1 : 0;
+        a.fast = p.any_fast ? 1 : 0;
+    } else {
+        for (int t = 0; t < 2; ++t) a.t[t].perm = c.pair_perm[t];
+        set_group_args(a, c.g);
+    }
     if (bh_tuning().debug_plan != 0) {
         std::fprintf(stderr, "[bh] dispersion plan B=%d Lmax=%d: lanes per model %d, typical layers %d (hint %d), Lcut %d%s, pairing %d; trials per round:",
                      B, c.Lmax, p.G, c.m.typ_layers, e->hint_layers, p.Lcut, p.Lcut < c.Lmax ? " (two depth classes)" : "", (int)(p.order == ORDER_PAIR));
         for (int t = 0; t < p.ntargets; ++t) std::fprintf(stderr, " %s %d/%d", a.t[t].iwave == BH_WAVE_LOVE ? "L" : "R", p.look_group[t], p.inlook[t]);
+        if (!lean) std::fprintf(stderr, "; launched lanes per model %d/%d", c.g.lanes[0], c.g.lanes[1]);
         std::fprintf(stderr, "\n");
     }
     e->guard_last = p.any_fast;
@@ -789,12 +939,13 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
             }
     }
     ev_begin(e, 0, c.st);
-    const bool lean = p.kernel == BH_KERNEL_LEAN;
     e->last_swd_kernel = p.kernel;
-    const int lrc = lean ? bh_launch_swd_lean(a, c.st, &e->last_swd)
-                         : bh_launch_swd_group(a, p.G, c.st, &e->last_swd, 2, p.order == ORDER_PAIR ? &e->pairwork : nullptr);
-    e->last_swd_wpb = lean ? 4 : 2; // (wavefronts per workgroup of the kernel that was launched)
-    if (lrc != 0) return fail(e, BH_EINVAL, "model too deep for LDS");
+    if (lean) {
+        if (bh_launch_swd_lean(a, c.st, &e->last_swd) != 0) return fail(e, BH_EINVAL, "model too deep for LDS");
+    } else {
+        bh_launch_swd_group(a, c.g, c.st);
+        e->last_swd = c.g.info;
+    }
     // (the counter a second stream waits on moves only once the launch is known to have been accepted: a failed launch
     // never increments the device word, and every later wait for the advanced value would hang -- ADVICE r03)
     const hipError_t le = hipGetLastError();
@@ -855,6 +1006,10 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
     if (B == 0 || njobs == 0) return BH_OK;
     const SwdPlan p = plan_swd(e, B, Lmax, m.typ_layers > 0 ? m.typ_layers : e->hint_layers, njobs, jobs);
     SwdCall c{e, st, B, Lmax, m, sl, sb, jobs, p};
+    if (p.kernel == BH_KERNEL_GROUP) {
+        c.g = plan_group(e, p, B, Lmax, jobs);
+        if (!c.g.fits) return fail(e, BH_EINVAL, "model too deep for LDS");
+    }
     int rc;
     if (p.nsplit > 0) {
         if ((rc = ensure(e, e->gfirst, (size_t)p.nsplit * B * sizeof(double)))) return rc;
@@ -872,15 +1027,9 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
     }
     if ((rc = swd_counter(e, st, &c.counter)) || (rc = order_models(c))) return rc;
     SwdMultiArgs a{};
-    bool rerun;
-    if (p.kernel == BH_KERNEL_LANE) {
-        rc = launch_swd_lanes(c, a);
-        rerun = p.any_fast;
-    } else {
-        rc = launch_swd_multi(c, a);
-        rerun = p.any_fast && !e->last_swd.restarts_in_place;
-    }
-    if (!rc && rerun) rc = launch_swd_rerun(e, st, a, c.gcounts, c.glists);
+    rc = p.kernel == BH_KERNEL_LANE ? launch_swd_lanes(c, a) : launch_swd_multi(c, a);
+    // (guarded models of the short refinement: re-run, unless the group kernel restarts them in place)
+    if (!rc && p.any_fast && !(p.kernel == BH_KERNEL_GROUP && c.g.restart)) rc = launch_swd_rerun(e, st, a, c.gcounts, c.glists);
     if (!rc && p.nsplit > 0) rc = launch_second_roots(c);
     ev_end(e, 0, st);
     return rc;
@@ -1553,7 +1702,7 @@ int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const in
         e->rf_gated_now = bh_tuning().rf_keep_floor == 0;
         // all workgroups of the launch, or -- a launch of more workgroups than the chip holds at once (2048 wavefronts) --
         // as many as can be resident together (the rest start as others end: waiting for them would be waiting for the kernel)
-        const unsigned resident = 2048u / (unsigned)(e->last_swd.lds > 0 && e->last_swd.workgroups > 0 ? (e->last_swd_wpb > 0 ? e->last_swd_wpb : 2) : 2);
+        const unsigned resident = 2048u / (unsigned)(e->last_swd.lds > 0 && e->last_swd.wpb > 0 ? e->last_swd.wpb : 2);
         const unsigned need = e->last_swd.workgroups < resident ? e->last_swd.workgroups : resident;
         HIPCHK(e, hipStreamWaitValue32(e->aux, e->started, e->started_expected - e->last_swd.workgroups + need, hipStreamWaitValueGte,
                                        0xffffffffu));

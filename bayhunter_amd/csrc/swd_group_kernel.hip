@@ -6,10 +6,8 @@
 #include "bh_device.h"
 #include "bh_tuning.h"
 #include <algorithm>
-#include <cstdlib>
+#include <cassert>
 #include <type_traits>
-#include <utility>
-#include <vector>
 #define BH_HD __device__ __forceinline__
 #define BH_TAB static __device__ const
 #include "bh_libm.h"
@@ -222,7 +220,7 @@ __global__ __launch_bounds__(BH_WAVE * WPB) __attribute__((amdgpu_waves_per_eu(B
     // Rayleigh round, 61 per Love round).  A workgroup's wavefronts only share the libm tables.
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / BH_WAVE));
     // PASSES (the re-run of the models a guard listed, one model per wavefront, reference sequence): the launch is a SMALL grid
-    // (bh_launch_swd_group: bh_tuning.h swd_rerun_wgs = 256 per target) whose workgroups stride over the list, whose length lives on
+    // (bh_plan_swd_group: bh_tuning.h swd_rerun_wgs = 256 per target) whose workgroups stride over the list, whose length lives on
     // the device -- nearly always it is empty or a handful of models, and a launch sized for the worst case (one wavefront per
     // model of the batch: 2048 workgroups at B = 4096) had to be dispatched workgroup by workgroup only to leave at once (4.5 us
     // alone, 0.2 ms when receiver-function workgroups of the other stream were waiting for the same wave slots).
@@ -827,7 +825,50 @@ restart_with_the_reference_sequence:
     }
 }
 
-#if !defined(BH_GROUP_FA_TU) && !defined(BH_GROUP_BIG_TU) && !defined(BH_GROUP_ADAPT_TU)
+// Launches build <FM, SI, PR, AD, CN, FA> of the kernel if it is plan g's.  Every translation unit lists the builds it compiles
+// (their flags and register budgets are what its machine code depends on: Makefile, swd_group_fa.hip, _adapt, _big).
+template <int FM, bool SI, bool PR, bool AD, bool CN, bool FA = false>
+bool launch_build(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stream)
+{
+    const SwdGroupBuild &b = g.build;
+    if (b.fastm != FM || b.simple != SI || b.prof != PR || b.adapt != AD || b.cntb != CN || b.fa != FA) return false;
+    hipLaunchKernelGGL((swd_group_kernel<GROUP_WPB, FM, SI, PR, AD, CN, FA>), g.grid, g.block, g.lds, stream, a, g.Gflags, (int)g.wave_lds);
+    return true;
+}
+} // namespace
+
+#if defined(BH_GROUP_BIG_TU)
+// The build that needs more than 256 registers (this translation unit: swd_group_big.hip, ONE wavefront per SIMD as its register
+// budget): one model per wavefront, both sequences, the counted Love scan AND the counters and clocks -- an instrumented launch of a
+// sampler's window under BH_SEARCH_FAST_RAYLEIGH; counters and clocks are what it is for, not speed.
+bool bh_swd_group_builds_big(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t s)
+{
+    return launch_build<1, true, true, true, true>(a, g, s);
+}
+#elif defined(BH_GROUP_ADAPT_TU)
+// The one-model-per-wavefront builds (ADAPT: a sampler's windows, single models, the re-run of guarded models) in a translation unit
+// of their own (swd_group_adapt.hip: the same source, the same flags) -- a third of this file's instantiations: it halves the
+// build's longest compile.  (Both sequences with the counted scan and the counters: swd_group_big.hip.)
+bool bh_swd_group_builds_adapt(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t s)
+{
+    return launch_build<2, true, true, true, false>(a, g, s) || launch_build<2, true, true, true, true>(a, g, s) ||
+           launch_build<2, true, false, true, false>(a, g, s) || launch_build<2, true, false, true, true>(a, g, s) ||
+           launch_build<1, true, true, true, false>(a, g, s) ||
+           launch_build<1, true, false, true, false>(a, g, s) || launch_build<1, true, false, true, true>(a, g, s) ||
+           launch_build<0, true, true, true, false>(a, g, s) || launch_build<0, true, true, true, true>(a, g, s) ||
+           launch_build<0, true, false, true, false>(a, g, s) || launch_build<0, true, false, true, true>(a, g, s);
+}
+#elif defined(BH_GROUP_FA_TU)
+// The builds with the fast arithmetic (this translation unit: swd_group_fa.hip).
+bool bh_swd_group_builds_fa(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t s)
+{
+    return launch_build<2, true, true, true, true, true>(a, g, s) || launch_build<2, true, true, true, false, true>(a, g, s) ||
+           launch_build<2, true, false, true, true, true>(a, g, s) || launch_build<2, true, false, true, false, true>(a, g, s) ||
+           launch_build<2, true, true, false, true, true>(a, g, s) || launch_build<2, true, true, false, false, true>(a, g, s) ||
+           launch_build<2, true, false, false, true, true>(a, g, s) || launch_build<2, true, false, false, false, true>(a, g, s);
+}
+#else
+namespace {
 size_t group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode)
 {
     const int MPW = BH_WAVE / (G * J);
@@ -836,58 +877,19 @@ size_t group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode)
            (((size_t)4 * Lmax * MPW * sizeof(float) + 15) & ~(size_t)15) +
            (maxmode > 1 ? (size_t)2 * Kmax * MPW * sizeof(double) : 0);
 }
-#endif
 
+// The builds of several models per wavefront in the reference's arithmetic (this translation unit).
+bool launch_builds(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t s)
+{
+    return launch_build<2, true, true, false, false>(a, g, s) || launch_build<2, true, true, false, true>(a, g, s) ||
+           launch_build<2, true, false, false, false>(a, g, s) || launch_build<2, true, false, false, true>(a, g, s) ||
+           launch_build<2, false, true, false, false>(a, g, s) || launch_build<2, false, true, false, true>(a, g, s) ||
+           launch_build<1, false, true, false, false>(a, g, s) ||
+           launch_build<0, true, true, false, false>(a, g, s) || launch_build<0, true, true, false, true>(a, g, s) ||
+           launch_build<0, true, false, false, false>(a, g, s) || launch_build<0, true, false, false, true>(a, g, s) ||
+           launch_build<0, false, true, false, false>(a, g, s) || launch_build<0, false, true, false, true>(a, g, s);
+}
 } // namespace
-
-#ifdef BH_GROUP_BIG_TU
-// The build that needs more than 256 registers (this translation unit: swd_group_big.hip, ONE wavefront per SIMD as its register
-// budget): one model per wavefront, both sequences, the counted Love scan AND the counters and clocks -- an instrumented launch of a
-// sampler's window under BH_SEARCH_FAST_RAYLEIGH; counters and clocks are what it is for, not speed.
-void bh_launch_swd_group_big(const SwdMultiArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t stream, int redundant, int wave_lds)
-{
-    hipLaunchKernelGGL((swd_group_kernel<GROUP_WPB, 1, true, true, true, true>), grid, block, lds, stream, a, redundant, wave_lds);
-}
-#elif defined(BH_GROUP_ADAPT_TU)
-// The one-model-per-wavefront builds (ADAPT: a sampler's windows, single models, the re-run of guarded models) in a translation unit
-// of their own (swd_group_adapt.hip: the same source, the same flags) -- a third of this file's instantiations: it halves the
-// build's longest compile.  fm = the sequences compiled in (FASTM), pr = with counters and clocks, cn = with the counted Love scan.
-void bh_launch_swd_group_adapt(const SwdMultiArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t stream, int redundant, int wave_lds,
-                               int fm, bool pr, bool cn)
-{
-#define BH_AD_(FM, PR, CN) hipLaunchKernelGGL((swd_group_kernel<GROUP_WPB, FM, true, PR, true, CN>), grid, block, lds, stream, a, redundant, wave_lds)
-#define BH_AD(FM, PR) do { if (cn) BH_AD_(FM, PR, true); else BH_AD_(FM, PR, false); } while (0)
-    if (fm == 2) {
-        if (pr) BH_AD(2, true);
-        else BH_AD(2, false);
-    } else if (fm == 1) {
-        if (pr) BH_AD_(1, true, false); // (with the counted scan as well: swd_group_big.hip)
-        else BH_AD(1, false);
-    } else {
-        if (pr) BH_AD(0, true);
-        else BH_AD(0, false);
-    }
-#undef BH_AD
-#undef BH_AD_
-}
-#elif defined(BH_GROUP_FA_TU)
-// The launches of the builds with the fast arithmetic (this translation unit: swd_group_fa.hip).
-void bh_launch_swd_group_fa(const SwdMultiArgs &a, dim3 grid, dim3 block, size_t lds, hipStream_t stream, int redundant, int wave_lds,
-                            bool adapt, bool counted, bool cntb)
-{
-#define BH_FA_(PR, AD, CN) hipLaunchKernelGGL((swd_group_kernel<GROUP_WPB, 2, true, PR, AD, CN, true>), grid, block, lds, stream, a, redundant, wave_lds)
-#define BH_FA(PR, AD) do { if (cntb) BH_FA_(PR, AD, true); else BH_FA_(PR, AD, false); } while (0)
-    if (adapt) {
-        if (counted) BH_FA(true, true);
-        else BH_FA(false, true);
-    } else {
-        if (counted) BH_FA(true, false);
-        else BH_FA(false, false);
-    }
-#undef BH_FA
-#undef BH_FA_
-}
-#else
 
 // LDS of one workgroup = shared libm tables + GROUP_WPB wavefront regions
 size_t bh_swd_group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode)
@@ -899,266 +901,116 @@ size_t bh_swd_group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode)
 constexpr size_t WAVE_LDS_TARGET = (160 * 1024 / 4 - LIBM_TAB_PAD) / GROUP_WPB;
 constexpr size_t WG_LDS_CAP = 64 * 1024;
 
-namespace {
-// Load ranks of the wavefronts of a launch for the SIMD-pairing order (SwdPairWork).  Placement rule of the workgroup
-// dispatcher, read off the wavefront trace (tools/gpu_trace.py, MAP=...; identical from run to run): workgroup g of a
-// one-dimensional grid runs on CU g mod ncu in pass g / ncu, and its two wavefronts sit on SIMD (pass + j) mod 4 -- so SIMD
-// s of a CU holds wavefront 0 of its pass-s workgroup and wavefront 1 of its pass-(s-1) workgroup, and the SIMDs whose
-// partner workgroup does not exist (the last pass is not full) hold one wavefront only.
-// Every wavefront gets a wanted load quantile q (0 = longest models): 0 for a wavefront alone on its SIMD, u and 1 - u for
-// the two of a pair (u spread over (0, 1/2) across the pairs); per target the wavefronts are ranked by q.
-bool build_slot_ranks(int n0, int n1, int ncu, std::vector<int32_t> rank[2])
+SwdGroupPlan bh_plan_swd_group(const SwdGroupAsk &q, const BhTuning &tun)
 {
-    const int NW = n0 + n1, nwg = (NW + 1) / 2;
-    if (ncu <= 0 || nwg > 4 * ncu) return false; // more than one round of workgroups: placement not fixed by the index
-    auto target_of = [&](int W, int &ty, int &wid) {
-        if (n1 > 0) {
-            const long long N = NW;
-            const int l0 = (int)(((long long)W * n1) / N), l1 = (int)((((long long)W + 1) * n1) / N);
-            ty = (l1 > l0) ? 1 : 0;
-            wid = (l1 > l0) ? l0 : W - l0;
-        } else {
-            ty = 0;
-            wid = W;
-        }
-    };
-    std::vector<int> on_simd[2]; // per (cu, simd): wavefront 0 / wavefront 1 member (grid wavefront index or -1)
-    on_simd[0].assign((size_t)ncu * 4, -1);
-    on_simd[1].assign((size_t)ncu * 4, -1);
-    for (int W = 0; W < NW; ++W) {
-        const int g = W / 2, j = W % 2, cu = g % ncu, pass = g / ncu, simd = (pass + j) % 4;
-        on_simd[j][(size_t)cu * 4 + simd] = W;
-    }
-    std::vector<double> q((size_t)NW, 0.0);
-    int npairs = 0;
-    for (size_t k = 0; k < on_simd[0].size(); ++k) npairs += (on_simd[0][k] >= 0 && on_simd[1][k] >= 0);
-    int ip = 0;
-    for (size_t k = 0; k < on_simd[0].size(); ++k) {
-        const int a = on_simd[0][k], b = on_simd[1][k];
-        if (a >= 0 && b >= 0) {
-            const double u = (ip + 0.5) / (2.0 * npairs);
-            q[(size_t)((ip & 1) ? a : b)] = u;        // (alternating which member takes the long share spreads the long
-            q[(size_t)((ip & 1) ? b : a)] = 1.0 - u;  //  models evenly over the two targets)
-            ++ip;
-        } else if (a >= 0) {
-            q[(size_t)a] = 0.0;
-        } else if (b >= 0) {
-            q[(size_t)b] = 0.0;
-        }
-    }
-    const int nw[2] = {n0, n1};
-    for (int t = 0; t < 2; ++t) {
-        std::vector<std::pair<double, int>> v;
-        for (int W = 0; W < NW; ++W) {
-            int ty, wid;
-            target_of(W, ty, wid);
-            if (ty == t && wid < nw[t] - 1) v.emplace_back(q[(size_t)W], wid); // (the last wavefront keeps the tail)
-        }
-        std::sort(v.begin(), v.end());
-        rank[t].assign((size_t)(nw[t] > 0 ? nw[t] : 1), 0);
-        for (size_t r = 0; r < v.size(); ++r) rank[t][(size_t)v[r].second] = (int32_t)r;
-    }
-    return true;
-}
-} // namespace
-
-int bh_launch_swd_group(const SwdMultiArgs &a0, int G0, hipStream_t stream, SwdLaunchInfo *info, int wpb, SwdPairWork *pair)
-{
-    wpb = GROUP_WPB; // (four wavefronts per workgroup were the co-resident receiver-function experiment of rounds 3-5: gone)
+    SwdGroupPlan g{};
+    const int nt = q.ntargets;
     int kmax = 0, maxmode = 1;
-    for (int t = 0; t < a0.ntargets; ++t) {
-        kmax = a0.t[t].K > kmax ? a0.t[t].K : kmax;
-        maxmode = a0.t[t].mode > maxmode ? a0.t[t].mode : maxmode;
+    for (int t = 0; t < nt; ++t) {
+        kmax = q.t[t].K > kmax ? q.t[t].K : kmax;
+        maxmode = q.t[t].mode > maxmode ? q.t[t].mode : maxmode;
     }
-    const BhTuning &tun = bh_tuning(); // (experiment switches, bh_tuning.h)
-    const int redundant = (tun.swd_redundant ? 0x100 : 0) | (tun.swd_no_board ? 0x400 : 0) | (tun.swd_no_fair ? 0x800 : 0);
-    SwdMultiArgs a = a0;
-    const bool two = a0.split != nullptr && a0.Lcut < a0.Lmax;
-    if (!two) a.split = nullptr;
-    size_t wave_lds = 0;
-    int nwaves = 1;
+    g.Gflags = (tun.swd_redundant ? 0x100 : 0) | (tun.swd_no_board ? 0x400 : 0) | (tun.swd_no_fair ? 0x800 : 0);
+    const bool two = q.Lcut < q.Lmax;
+    // target t with G lanes per model: models per wavefront, wavefronts
+    auto mpw_at = [&](int G, int t) { return BH_WAVE / (G * bh_trials_fit(G, q.t[t].look)); };
+    auto waves_at = [&](int G, int t) { return (q.B + mpw_at(G, t) - 1) / mpw_at(G, t); };
+    long nwaves = 1;
     for (int cls = two ? 0 : 1; cls <= 1; ++cls) {
-        const int rows = (two && cls == 1) ? a0.Lcut : a0.Lmax;
+        const int rows = (two && cls == 1) ? q.Lcut : q.Lmax;
+        auto wave_bytes = [&](int G) {
+            size_t w = 0;
+            for (int t = 0; t < nt; ++t)
+                w = std::max(w, (group_lds_bytes(G, bh_trials_fit(G, q.t[t].look), rows, kmax, maxmode) + 15) & ~(size_t)15);
+            return w;
+        };
         // fewer models per wavefront (more lanes per model) until the parked layers fit: first the
         // residency target, at the latest the 64 KB a workgroup may ask for
-        int G = G0;
-        auto trials = [&](int g, int t) {
-            int J = a.t[t].look > 1 ? a.t[t].look : 1;
-            while (J > 1 && g * J > BH_WAVE) --J;
-            return J;
-        };
-        auto wave_bytes = [&](int g) {
-            size_t w = 0;
-            for (int t = 0; t < a.ntargets; ++t) {
-                const size_t l = (group_lds_bytes(g, trials(g, t), rows, kmax, maxmode) + 15) & ~(size_t)15;
-                w = l > w ? l : w;
-            }
-            return w;
-        };
-        auto waves = [&](int g) {
-            long w = 0;
-            for (int t = 0; t < a.ntargets; ++t) {
-                const int mpw = BH_WAVE / (g * trials(g, t));
-                w += (a.B + mpw - 1) / mpw;
-            }
-            return w;
-        };
-        auto most_models = [&](int g) {
-            int m = 1;
-            for (int t = 0; t < a.ntargets; ++t) {
-                const int mpw = BH_WAVE / (g * trials(g, t));
-                m = mpw > m ? mpw : m;
-            }
-            return m;
-        };
+        int G = q.G0;
         // a batch that leaves half the chip idle anyway: one lane per layer of the deepest model of the
         // class (a single pass over the layers) instead of lanes for the typical depth
         // (only where that costs neither look-ahead nor residency)
         for (int Gwide = rows - 1 > 16 ? 16 : rows - 1; Gwide > G; --Gwide) {
-            bool same = waves(Gwide) <= 256;
-            for (int t = 0; t < a.ntargets; ++t) same = same && trials(Gwide, t) == trials(G, t);
-            if (same) {
+            long w = 0;
+            bool same = true;
+            for (int t = 0; t < nt; ++t) {
+                w += waves_at(Gwide, t);
+                same = same && bh_trials_fit(Gwide, q.t[t].look) == bh_trials_fit(G, q.t[t].look);
+            }
+            if (w <= 256 && same) {
                 G = Gwide;
                 break;
             }
         }
-        while (most_models(G) > 1 && wave_bytes(G) > WAVE_LDS_TARGET) G += 1;
-        // (the cap is what a workgroup of GROUP_WPB wavefronts may ask for by default; the same models per wavefront with 4)
+        auto several = [&](int lanes) { // several models per wavefront for some target
+            bool any = false;
+            for (int t = 0; t < nt; ++t) any = any || mpw_at(lanes, t) > 1;
+            return any;
+        };
+        while (several(G) && wave_bytes(G) > WAVE_LDS_TARGET) G += 1;
+        // (the cap is what a workgroup of GROUP_WPB wavefronts may ask for by default)
         while (G < BH_WAVE && LIBM_TAB_PAD + GROUP_WPB * wave_bytes(G) > WG_LDS_CAP) G += 1;
-        if (LIBM_TAB_PAD + GROUP_WPB * wave_bytes(G) > WG_LDS_CAP) return -1;
-        a.rows[cls] = rows;
-        a.lanes[cls] = G;
-        const size_t wb = wave_bytes(G);
-        wave_lds = wb > wave_lds ? wb : wave_lds;
-        for (int t = 0; t < a.ntargets; ++t) {
-            const int mpw = BH_WAVE / (G * trials(G, t));
-            const int nx = (a.B + mpw - 1) / mpw; // worst case: the whole batch is in this class
-            nwaves = nx > nwaves ? nx : nwaves;
-        }
+        if (LIBM_TAB_PAD + GROUP_WPB * wave_bytes(G) > WG_LDS_CAP) return g; // (fits = false)
+        g.rows[cls] = rows;
+        g.lanes[cls] = G;
+        g.wave_lds = std::max(g.wave_lds, wave_bytes(G));
+        for (int t = 0; t < nt; ++t) nwaves = std::max(nwaves, (long)waves_at(G, t)); // worst case: the whole batch is in this class
     }
+    g.fits = true;
     if (!two) {
-        a.rows[0] = a.rows[1];
-        a.lanes[0] = a.lanes[1];
+        g.rows[0] = g.rows[1];
+        g.lanes[0] = g.lanes[1];
     }
-    dim3 grid((nwaves + wpb - 1) / wpb, a.ntargets, two ? 2 : 1);
-    a.wg_n0 = a.wg_n1 = 0;
-    const bool no_mix = tun.swd_no_mix != 0;
-    if (a.ntargets == 2 && !two && !no_mix && !a.rerun) { // two targets, one depth class: interleave their wavefronts (see the kernel)
-        int n[2];
-        for (int t = 0; t < 2; ++t) {
-            int J = a.t[t].look > 1 ? a.t[t].look : 1;
-            while (J > 1 && a.lanes[1] * J > BH_WAVE) --J;
-            const int mpw = BH_WAVE / (a.lanes[1] * J);
-            n[t] = (a.B + mpw - 1) / mpw; // wavefronts of this target
-        }
-        a.wg_n0 = n[0];
-        a.wg_n1 = n[1];
-        grid = dim3((n[0] + n[1] + wpb - 1) / wpb, 1, 1);
+    // per target at the launched lanes of one class: models per wavefront, wavefronts
+    int mpw[8], nw[8];
+    for (int t = 0; t < nt; ++t) {
+        mpw[t] = mpw_at(g.lanes[1], t);
+        nw[t] = waves_at(g.lanes[1], t);
+    }
+    g.grid = dim3((unsigned)((nwaves + GROUP_WPB - 1) / GROUP_WPB), nt, two ? 2 : 1);
+    if (nt == 2 && !two && tun.swd_no_mix == 0 && !q.rerun) { // two targets, one depth class: interleave their wavefronts (see the kernel)
+        g.wg_n0 = nw[0];
+        g.wg_n1 = nw[1];
+        g.grid = dim3((nw[0] + nw[1] + GROUP_WPB - 1) / GROUP_WPB, 1, 1);
     }
     // SIMD-pairing order of the models (SwdPairWork): a one-dimensional grid of one class, workgroups of two wavefronts
-    if (pair != nullptr && !two && wpb == 2 && grid.y == 1 && grid.z == 1 && a.ntargets <= 2 && bh_pair_order_fits(a.B)) {
-        int n[2] = {0, 0}, mpw[2] = {1, 1};
-        for (int t = 0; t < a.ntargets; ++t) {
-            int J = a.t[t].look > 1 ? a.t[t].look : 1;
-            while (J > 1 && a.lanes[1] * J > BH_WAVE) --J;
-            mpw[t] = BH_WAVE / (a.lanes[1] * J);
-            n[t] = (a.B + mpw[t] - 1) / mpw[t];
-        }
-        bool ok = true, geom = true;
-        const bool by_depth_only = false; // (whether the pairing applies is the engine's decision: launch_swd_jobs)
-        if (!by_depth_only && (pair->key_n0 != n[0] || pair->key_n1 != n[1] || pair->key_wpb != wpb)) { // (rare: the batch shape changed)
-            std::vector<int32_t> rank[2];
-            geom = build_slot_ranks(n[0], n[1], pair->ncu, rank); // false: placement unknown -> plain sorted order
-            for (int t = 0; ok && geom && t < a.ntargets; ++t) {
-                if (pair->cap_rank[t] < n[t]) {
-                    if (pair->slot_rank[t]) (void)hipFree(pair->slot_rank[t]);
-                    pair->slot_rank[t] = nullptr;
-                    ok = hipMalloc((void **)&pair->slot_rank[t], (size_t)(n[t] + 64) * sizeof(int32_t)) == hipSuccess;
-                    pair->cap_rank[t] = ok ? n[t] + 64 : 0;
-                }
-                if (ok) {
-                    ok = hipStreamSynchronize(stream) == hipSuccess && // (an earlier launch may still read the old table)
-                         hipMemcpy(pair->slot_rank[t], rank[t].data(), (size_t)n[t] * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
-                }
-            }
-            pair->key_n0 = (ok && geom) ? n[0] : -1;
-            pair->key_n1 = (ok && geom) ? n[1] : -1;
-            pair->key_wpb = (ok && geom) ? wpb : -1;
-        }
-        if (ok && pair->cap_perm < a.B) {
-            for (int t = 0; t < 2; ++t) {
-                if (pair->perm[t]) (void)hipFree(pair->perm[t]);
-                pair->perm[t] = nullptr;
-                ok = ok && hipStreamSynchronize(stream) == hipSuccess &&
-                     hipMalloc((void **)&pair->perm[t], (size_t)(a.B + a.B / 4 + 64) * sizeof(int32_t)) == hipSuccess;
-            }
-            pair->cap_perm = ok ? a.B + a.B / 4 + 64 : 0;
-        }
-        if (ok && by_depth_only) {
-            bh_launch_order(a.B, a.nlay, pair->perm[0], a.Lmax, nullptr, stream);
-            a.perm = pair->perm[0];
-        } else if (ok) {
-            PairOrderTarget tg[2];
-            for (int t = 0; t < a.ntargets; ++t) tg[t] = PairOrderTarget{mpw[t], n[t], geom ? pair->slot_rank[t] : nullptr, pair->perm[t]};
-            bh_launch_pair_order(a.B, a.Lmax, a.nlay, a.t[0].vs, a.t[0].sl, a.t[0].sb, a.ntargets, tg, stream);
-            for (int t = 0; t < a.ntargets; ++t) a.t[t].perm = pair->perm[t];
-        }
-        (void)hipGetLastError();
+    g.pair = !two && g.grid.y == 1 && g.grid.z == 1 && nt <= 2 && bh_pair_order_fits(q.B);
+    for (int t = 0; t < 2; ++t) {
+        g.pair_mpw[t] = t < nt ? mpw[t] : 1;
+        g.pair_waves[t] = t < nt ? nw[t] : 0;
     }
     // One model per wavefront for every target (a chain window, a single model), one class, the usual targets: every wavefront
     // sizes its lane groups and trials for its own model (ADAPT, see the kernel) within the region all wavefronts can be
     // resident with.
-    const bool no_adapt = tun.swd_no_adapt != 0;
-    // (capacity up to 32 rows: at least two trials fit the region; deeper arrays keep the launcher's own choice of fewer, wider
+    // (capacity up to 32 rows: at least two trials fit the region; deeper arrays keep the plan's own choice of fewer, wider
     // lane groups in a larger region)
-    bool adapt = a.adapt_ok && !no_adapt && !two && wpb == GROUP_WPB && a.Lmax <= 32 && a.Lmax >= 2;
-    {
-        bool plain = true;
-        for (int t = 0; t < a.ntargets; ++t) {
-            int J = a.t[t].look > 1 ? a.t[t].look : 1;
-            while (J > 1 && a.lanes[1] * J > BH_WAVE) --J;
-            adapt = adapt && BH_WAVE / (a.lanes[1] * J) == 1;
-            plain = plain && a.t[t].igr == 0 && a.t[t].mode <= 1 && a.t[t].K <= 64;
-        }
-        adapt = adapt && plain;
-        if (adapt) wave_lds = WAVE_LDS_TARGET & ~(size_t)15;
+    bool adapt = q.adapt_ok && tun.swd_no_adapt == 0 && !two && q.Lmax <= 32 && q.Lmax >= 2;
+    bool any_phase = false, any_group = false, any_modes = false, any_refseq = false, any_love = false, all_love = true;
+    for (int t = 0; t < nt; ++t) {
+        const SwdGroupAsk::Target &T = q.t[t];
+        adapt = adapt && mpw[t] == 1 && !T.group && T.mode <= 1 && T.K <= 64;
+        any_phase = any_phase || (!T.group && !T.refseq);
+        any_group = any_group || T.group;
+        any_refseq = any_refseq || (!T.group && T.refseq);
+        any_modes = any_modes || T.mode > 1;
+        any_love = any_love || T.iwave == 1;
+        all_love = all_love && T.iwave == 1;
     }
-    const size_t lds = LIBM_TAB_PAD + wpb * wave_lds;
-    if (info != nullptr) {
-        info->workgroups = grid.x * grid.y * grid.z;
-        info->waves = (a.wg_n1 > 0) ? (long)a.wg_n0 + a.wg_n1 : (long)nwaves * a.ntargets;
-        info->lds = lds;
-    }
-    // build: 0 = reference sequence; with the short refinement asked for: 2 = no group-velocity target in the launch (nevill
+    if (adapt) g.wave_lds = WAVE_LDS_TARGET & ~(size_t)15;
+    g.lds = LIBM_TAB_PAD + GROUP_WPB * g.wave_lds;
+    g.block = dim3(BH_WAVE * GROUP_WPB);
+    g.info = SwdLaunchInfo{g.grid.x * g.grid.y * g.grid.z, g.wg_n1 > 0 ? (long)g.wg_n0 + g.wg_n1 : nwaves * nt, g.lds, GROUP_WPB};
+    // (one model per wavefront and SwdMultiArgs::restart: the build with both sequences, guarded models restart in place;
+    //  not with the fast arithmetic: the reference's sequence runs in the reference's arithmetic -- the re-run launch)
+    g.restart = adapt && q.restart && q.fast && any_phase && tun.swd_no_restart == 0 && !(q.farith && !any_group && !any_refseq && !any_modes);
+    // fastm: 0 = reference sequence; with the short refinement asked for: 2 = no group-velocity target in the launch (nevill
     // not compiled in), 1 = mixed (group-velocity targets keep the reference sequence), 0 = group-velocity targets only.
+    const int fastm = (q.fast && any_phase) ? ((any_group || any_refseq || g.restart) ? 1 : 2) : 0;
     // simple: fundamental-mode phase velocities only (builds 0 and 2; no second root, no mode loop in the kernel).
-    bool any_phase = false, any_group = false, any_modes = false, any_refseq = false;
-    for (int t = 0; t < a.ntargets; ++t) {
-        any_phase = any_phase || (a.t[t].igr == 0 && !a.t[t].refseq);
-        any_group = any_group || a.t[t].igr != 0;
-        any_refseq = any_refseq || (a.t[t].igr == 0 && a.t[t].refseq);
-        any_modes = any_modes || a.t[t].mode > 1;
-    }
-    // (one model per wavefront and SwdMultiArgs::restart: the build with both sequences, guarded models restart in place)
-    const bool no_restart = tun.swd_no_restart != 0;
-    // (not with the fast arithmetic: the reference's sequence runs in the reference's arithmetic -- the re-run launch)
-    const bool restart = adapt && a.restart != 0 && a.fast && any_phase && !no_restart && !(a.farith != 0 && !any_group && !any_refseq && !any_modes);
-    a.restart = restart ? 1 : 0;
-    if (info != nullptr) info->restarts_in_place = restart ? 1 : 0;
-    const int build = (a.fast && any_phase) ? ((any_group || any_refseq || restart) ? 1 : 2) : 0;
-    const bool no_simple = tun.swd_no_simple != 0;
-    const bool simple = !any_group && !any_modes && !no_simple;
-    a.fast = build;
-    const dim3 block(BH_WAVE * wpb);
-    const bool counted = a.neval != nullptr;
+    const bool simple = !any_group && !any_modes && tun.swd_no_simple == 0;
     // The builds with the counted scan (CNTB, see the kernel): asked for, a Love target in the launch, and the launch is of the
-    // kind it pays in -- one model per wavefront, or Love targets only.  BH_SWD_SCAN_ALWAYS=1: wherever asked for (measurements).
-    bool any_love = false, all_love = true;
-    for (int t = 0; t < a.ntargets; ++t) {
-        any_love = any_love || a.t[t].iwave == 1;
-        all_love = all_love && a.t[t].iwave == 1;
-    }
-    // a.counted: 1 = wherever a Love target is (BH_SCAN_COUNTED), 2 = where it pays (BH_SCAN_AUTO): with several models per
+    // kind it pays in -- one model per wavefront, or Love targets only.
+    // q.scan: 1 = wherever a Love target is (BH_SCAN_COUNTED), 2 = where it pays (BH_SCAN_AUTO): with several models per
     // wavefront, launches of Love targets only (B = 4096: 2.06 -> 1.71 ms) and Rayleigh + Love launches of the short refinement
     // (there the LOVE wavefronts set the time: 379 rounds against the Rayleigh wavefronts' 302; counted 149 rounds of twice the
     // length: c2 2.51 -> 2.30 ms, c3 2.60 -> 2.49).  One model per wavefront (the trial lanes already walk the scan seven
@@ -1166,48 +1018,24 @@ int bh_launch_swd_group(const SwdMultiArgs &a0, int G0, hipStream_t stream, SwdL
     // Rayleigh wavefronts set the time: c2 3.37 -> 3.47 ms) do not gain.
     // (not in a launch of several models per wavefront that mixes both refinements: that build would spill; one model per
     //  wavefront -- the chains' windows -- has it)
-    const bool cntb = any_love && wpb == GROUP_WPB && !(build == 1 && !adapt) && (a.counted == 1 || (a.counted == 2 && !adapt && (all_love ? build != 1 : build == 2)));
-    a.counted = cntb ? 1 : 0;
-#define BH_GROUP_LAUNCH_(WP, FM, SI, PR, AD, CN) hipLaunchKernelGGL((swd_group_kernel<WP, FM, SI, PR, AD, CN>), grid, block, lds, stream, a, redundant, (int)wave_lds)
-#define BH_GROUP_LAUNCH(WP, FM, SI, PR) do { if (cntb) BH_GROUP_LAUNCH_(WP, FM, SI, PR, false, true); else BH_GROUP_LAUNCH_(WP, FM, SI, PR, false, false); } while (0)
-#define BH_GROUP_LAUNCH_ADAPT(FM, PR) bh_launch_swd_group_adapt(a, grid, block, lds, stream, redundant, (int)wave_lds, FM, PR, cntb) /* swd_group_adapt.hip */
-    // The builds without the counters exist for the SIMPLE launches only: there they are worth 2 % (c2 3.44 -> 3.37 ms; 4 instead
-    // of 33 spilled SGPRs); a launch with group-velocity targets is 2 % SLOWER without them (c2g 5.55 -> 5.67 ms).
+    const bool cntb = any_love && !(fastm == 1 && !adapt) && (q.scan == 1 || (q.scan == 2 && !adapt && (all_love ? fastm != 1 : fastm == 2)));
     // the fast arithmetic (FA, see the kernel): every target of the launch takes the short refinement, the usual targets
-    const bool farith = a.farith != 0 && build == 2 && simple && wpb == GROUP_WPB;
-    a.farith = farith ? 1 : 0;
-    if (info != nullptr) info->fast_arith = a.farith;
-    if (farith) {
-        bh_launch_swd_group_fa(a, grid, block, lds, stream, redundant, (int)wave_lds, adapt, counted, cntb);
-    } else if (adapt && build == 2) {
-        if (counted) BH_GROUP_LAUNCH_ADAPT(2, true);
-        else BH_GROUP_LAUNCH_ADAPT(2, false);
-    } else if (adapt && build == 1) { // (both sequences in one launch: Rayleigh targets short, Love targets the reference's)
-        // (the instrumented build with both sequences AND the counted scan needs more than 256 registers: it is compiled with
-        //  the one-wavefront-per-SIMD budget of swd_group_big.hip -- counters and clocks are what it is for, not speed)
-        if (counted && cntb) bh_launch_swd_group_big(a, grid, block, lds, stream, redundant, (int)wave_lds);
-        else if (counted) bh_launch_swd_group_adapt(a, grid, block, lds, stream, redundant, (int)wave_lds, 1, true, false);
-        else BH_GROUP_LAUNCH_ADAPT(1, false);
-    } else if (adapt) {
-        if (a.rerun && tun.swd_rerun_wgs > 0 && grid.x > (unsigned)tun.swd_rerun_wgs) grid.x = (unsigned)tun.swd_rerun_wgs; // (the kernel's PASSES: its workgroups stride over the list)
-        if (counted) BH_GROUP_LAUNCH_ADAPT(0, true);
-        else BH_GROUP_LAUNCH_ADAPT(0, false);
-    } else if (build == 2 && simple) {
-        if (counted) BH_GROUP_LAUNCH(GROUP_WPB, 2, true, true);
-        else BH_GROUP_LAUNCH(GROUP_WPB, 2, true, false);
-    } else if (build == 2) {
-        BH_GROUP_LAUNCH(GROUP_WPB, 2, false, true);
-    } else if (build == 1) {
-        BH_GROUP_LAUNCH_(GROUP_WPB, 1, false, true, false, false);
-    } else if (simple) {
-        if (counted) BH_GROUP_LAUNCH(GROUP_WPB, 0, true, true);
-        else BH_GROUP_LAUNCH(GROUP_WPB, 0, true, false);
-    } else {
-        BH_GROUP_LAUNCH(GROUP_WPB, 0, false, true);
-    }
-#undef BH_GROUP_LAUNCH_ADAPT
-#undef BH_GROUP_LAUNCH
-#undef BH_GROUP_LAUNCH_
-    return 0;
+    const bool fa = q.farith && fastm == 2 && simple;
+    // The builds without the counters exist for the SIMPLE launches only: there they are worth 2 % (c2 3.44 -> 3.37 ms; 4 instead
+    // of 33 spilled SGPRs); a launch with group-velocity targets is 2 % SLOWER without them (c2g 5.55 -> 5.67 ms).  The ADAPT
+    // builds (plain targets only) are all SIMPLE; the build with both sequences of several models per wavefront is not.
+    const bool simple_build = adapt || (simple && fastm != 1);
+    g.build = SwdGroupBuild{fastm, simple_build, q.counters || !simple_build, adapt, cntb, fa};
+    // (the re-run: the kernel's PASSES, its workgroups stride over the list)
+    if (adapt && fastm == 0 && q.rerun && tun.swd_rerun_wgs > 0 && g.grid.x > (unsigned)tun.swd_rerun_wgs) g.grid.x = (unsigned)tun.swd_rerun_wgs;
+    return g;
 }
-#endif // BH_GROUP_FA_TU
+
+void bh_launch_swd_group(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stream)
+{
+    const bool launched = launch_builds(a, g, stream) || bh_swd_group_builds_adapt(a, g, stream) ||
+                          bh_swd_group_builds_fa(a, g, stream) || bh_swd_group_builds_big(a, g, stream);
+    assert(launched && "the plan's build is compiled");
+    (void)launched;
+}
+#endif

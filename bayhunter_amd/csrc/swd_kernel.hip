@@ -258,7 +258,7 @@ __global__ __launch_bounds__(1024) void order_kernel(int B, const int32_t *nlay,
 // one period to that of the next in steps of dc: the longer the walk, the more secular evaluations; correlation with the
 // evaluations counted by the oracle on bench.py's models: 0.94 Rayleigh, 0.81 Love).  Models sorted by it (bucket sort,
 // 1024 buckets, longest first); wavefront `wid` of a target takes the group of rank slot_rank[wid] -- the ranks come
-// from the launcher, which knows which wavefronts share a SIMD.  A batch of mixed depths is ordered by depth instead
+// from order_models (bh_engine.hip), which knows which wavefronts share a SIMD.  A batch of mixed depths is ordered by depth instead
 // (deepest first, as order_kernel does): wavefronts of one depth matter more there.
 constexpr int PAIR_BUCKETS = 1024;
 constexpr int PAIR_MAX_B = 12288; // models the sorted list holds in LDS

@@ -923,8 +923,7 @@ int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo
         info->workgroups = grid.x * grid.y;
         info->waves = wsum;
         info->lds = lds;
-        info->fast_arith = 1;
-        info->restarts_in_place = 0;
+        info->wpb = LEAN_WPB;
     }
     int flip = bh_tuning().swd_lean_flip;
     if (a.ntargets == 2 && nw[0] == nw[1] && nw[1] % 16 == 0) flip |= 2048; // (the opposite order can stay inside the XCDs)
