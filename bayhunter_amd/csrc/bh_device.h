@@ -89,7 +89,14 @@ struct SwdKernelArgs {
     double *first;
 };
 
-void bh_launch_swd(const SwdKernelArgs &a, int iwave, hipStream_t stream);
+// Which instantiation a launch of the lane kernel (swd_kernel) or of the trial-per-lane kernel (swd_lean_kernel) took: its
+// template arguments (lane: IFUNC, LOOK, WPB, FAST, SIMPLE, FA; lean: J, CNT), workgroups and time slice (bh_engine_debug.h).
+struct SwdLaneBuild {
+    int key[6];
+    unsigned grid_x;
+    int fair;
+};
+void bh_launch_swd(const SwdKernelArgs &a, int iwave, hipStream_t stream, SwdLaneBuild *build = nullptr);
 // perm[0..B) = model indices sorted by layer count, deepest first: wavefronts then hold models of (nearly)
 // one depth -- no masked layers, and the long-running deep models start first.  Results do not depend on it.
 void bh_launch_order(int B, const int32_t *nlay, int32_t *perm, int Lcut, int32_t *split, hipStream_t stream);
@@ -231,7 +238,7 @@ bool bh_swd_group_builds_big(const SwdMultiArgs &a, const SwdGroupPlan &g, hipSt
 // engine's default settings for batches up to a few ten thousand models); a.t[t].look = trials per model and round
 int bh_swd_lean_trials(int B, int ntargets);
 size_t bh_swd_lean_lds_bytes(int J, int Lmax, int Kmax);
-int bh_launch_swd_lean(const SwdMultiArgs &a, hipStream_t stream, SwdLaunchInfo *info);
+int bh_launch_swd_lean(const SwdMultiArgs &a, hipStream_t stream, SwdLaunchInfo *info, SwdLaneBuild *build = nullptr);
 // earth-flattening of a batch (surfdisp96.f:486-553): writes layer-major [Lmax][B] float64 copies
 // (binary32-valued) of thickness, vp, vs and the Love / Rayleigh density mappings
 void bh_launch_sphere(int B, int Lmax, const int32_t *nlay, const double *h, const double *vp,

@@ -121,6 +121,8 @@ struct bh_engine {
     SwdPairWork pairwork{};                // SIMD-pairing order of the group kernel (bh_device.h)
     int swd_trials = 0;                    // bh_engine_set_swd_trials: trials per round of the trial-per-lane kernel (0 = by the call's shape)
     int last_swd_kernel = -1;              // bh_engine_last_swd_kernel
+    bh_swd_launch swd_launches[3 * BH_MAX_TARGETS]{}; // bh_engine_last_swd_launches: of the most recent call with dispersion targets
+    int n_swd_launches = 0;
     SwdLaunchInfo last_swd{};              // of the most recent group-kernel launch (workgroups == 0: none)
     int err_t_nt = -1, err_t_B = -1;       // layout for which err_t's untouched rows are known to be zero
     int swd_prio_low_now = 0;              // per call: what the next dispersion launch gets
@@ -664,6 +666,23 @@ int wait_for(bh_engine *e, hipEvent_t ev, hipStream_t from, hipStream_t to)
     return BH_OK;
 }
 
+// One launch of the current call for bh_engine_last_swd_launches (host side: the plans' and launchers' own choices)
+void note_launch(bh_engine *e, int family, int role, const int key[6], bool two, bool inter, bool pair, bool restart, unsigned grid_x, int fair)
+{
+    if (e->n_swd_launches >= (int)(sizeof(e->swd_launches) / sizeof(e->swd_launches[0]))) return;
+    bh_swd_launch &r = e->swd_launches[e->n_swd_launches++];
+    r.family = family; r.role = role;
+    for (int k = 0; k < 6; ++k) r.key[k] = key[k];
+    r.two_classes = two; r.interleaved = inter; r.pair_order = pair; r.restart = restart; r.grid_x = (int)grid_x; r.fair = fair;
+}
+void note_lane(bh_engine *e, int role, const SwdLaneBuild &b) { note_launch(e, BH_KERNEL_LANE, role, b.key, false, false, false, false, b.grid_x, b.fair); }
+void note_group(bh_engine *e, int role, const SwdGroupPlan &g, bool pair)
+{
+    const SwdGroupBuild &b = g.build;
+    const int key[6] = {b.fastm, b.simple, b.prof, b.adapt, b.cntb, b.fa};
+    note_launch(e, BH_KERNEL_GROUP, role, key, g.grid.z == 2, g.wg_n1 > 0, pair, g.restart, g.grid.x, 0);
+}
+
 // The group kernel's decisions (bh_plan_swd_group) in its arguments a
 void set_group_args(SwdMultiArgs &a, const SwdGroupPlan &g)
 {
@@ -772,6 +791,7 @@ int launch_swd_rerun(bh_engine *e, hipStream_t st, const SwdMultiArgs &main, int
     if (!g.fits) return fail(e, BH_EINVAL, "model too deep for LDS");
     set_group_args(a, g);
     bh_launch_swd_group(a, g, st);
+    note_group(e, BH_SWD_RERUN, g, false);
     HIPCHK(e, hipGetLastError());
     ++e->rerun_launches;
     return BH_OK;
@@ -883,7 +903,9 @@ int launch_swd_lanes(SwdCall &c, SwdMultiArgs &ra)
             a.gcount = c.gcounts + t;
             a.glist = c.glists + (size_t)t * (size_t)(B + 4);
         }
-        bh_launch_swd(a, tg.iwave, (fork && (t & 1)) ? e->aux2 : c.st);
+        SwdLaneBuild lb{};
+        bh_launch_swd(a, tg.iwave, (fork && (t & 1)) ? e->aux2 : c.st, &lb);
+        note_lane(e, BH_SWD_MAIN, lb);
         ra.t[ra.ntargets++] = tg;
     }
     if (fork && (rc = wait_for(e, e->ev_join2, e->aux2, c.st))) return rc;
@@ -941,9 +963,12 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
     ev_begin(e, 0, c.st);
     e->last_swd_kernel = p.kernel;
     if (lean) {
-        if (bh_launch_swd_lean(a, c.st, &e->last_swd) != 0) return fail(e, BH_EINVAL, "model too deep for LDS");
+        SwdLaneBuild lb{};
+        if (bh_launch_swd_lean(a, c.st, &e->last_swd, &lb) != 0) return fail(e, BH_EINVAL, "model too deep for LDS");
+        note_launch(e, BH_KERNEL_LEAN, BH_SWD_MAIN, lb.key, false, p.ntargets == 2, false, false, lb.grid_x, 0);
     } else {
         bh_launch_swd_group(a, c.g, c.st);
+        note_group(e, BH_SWD_MAIN, c.g, c.pair_perm[0] != nullptr);
         e->last_swd = c.g.info;
     }
     // (the counter a second stream waits on moves only once the launch is known to have been accepted: a failed launch
@@ -989,7 +1014,9 @@ int launch_second_roots(const SwdCall &c)
         const long waves = ((long)a.B * J2 + 63) / 64;
         a.fair = waves <= 1024 ? -1 : (waves <= 2048 ? 18 : 12);
         a.nev_high = (double *)e->nevhi2.p + off[n];
-        bh_launch_swd(a, tg.iwave, (fork && (n & 1)) ? e->aux2 : c.st);
+        SwdLaneBuild lb{};
+        bh_launch_swd(a, tg.iwave, (fork && (n & 1)) ? e->aux2 : c.st, &lb);
+        note_lane(e, BH_SWD_SECOND, lb);
         ++n;
     }
     if (fork && (rc = wait_for(e, e->ev_join2, e->aux2, c.st))) return rc;
@@ -1018,6 +1045,7 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
             if (p.first_roots[j]) c.first[j] = (double *)e->gfirst.p + (size_t)(n++) * B;
     }
     if (p.ntargets == 0) return BH_OK;
+    e->n_swd_launches = 0; // (bh_engine_last_swd_launches: this call's)
     if (p.any_sphere) { // earth-flattened copies of the batch (layer-major), made once per call
         const size_t ne = (size_t)Lmax * B;
         if ((rc = ensure(e, e->sph, 5 * ne * sizeof(double)))) return rc;
@@ -1239,6 +1267,14 @@ int bh_engine_set_swd_arith(bh_engine *e, int arith)
 }
 int bh_engine_get_swd_arith(const bh_engine *e) { return e ? e->swd_arith : 0; }
 int bh_engine_last_swd_kernel(const bh_engine *e) { return e ? e->last_swd_kernel : -1; }
+int bh_engine_last_swd_launches(const bh_engine *e, bh_swd_launch *out, int max, int *n)
+{
+    if (!e || !n || max < 0 || (max > 0 && !out)) return BH_EINVAL;
+    const int m = e->n_swd_launches < max ? e->n_swd_launches : max;
+    for (int i = 0; i < m; ++i) out[i] = e->swd_launches[i];
+    *n = m;
+    return BH_OK;
+}
 int bh_engine_set_swd_trials(bh_engine *e, int trials)
 {
     if (!e) return BH_EINVAL;

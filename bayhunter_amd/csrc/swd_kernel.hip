@@ -506,7 +506,7 @@ size_t bh_swd_nev_high_doubles(int B, int look)
     return (size_t)2 * (NEV_MAX - NEV_LO) * waves * BH_WAVE;
 }
 
-void bh_launch_swd(const SwdKernelArgs &a, int iwave, hipStream_t stream)
+void bh_launch_swd(const SwdKernelArgs &a, int iwave, hipStream_t stream, SwdLaneBuild *build)
 {
     SwdKernelArgs b = a;
     int J = 1;
@@ -529,6 +529,10 @@ void bh_launch_swd(const SwdKernelArgs &a, int iwave, hipStream_t stream)
     // 65 536 and +6 % at 131 072 (one lane per model: the Love build drops to 165 registers there, a third wavefront per SIMD
     // upsets the Rayleigh / Love pairs the time-sliced priorities are tuned for); short refinement -3 % at 65 536.
     const bool simple = a.igr == 0 && a.mode <= 1 && !no_simple && (J > 1 || a.fast);
+    if (build != nullptr) { // (the instantiation the macros below pick)
+        const int fs = (a.fast && a.igr == 0) ? 2 : 0;
+        *build = SwdLaneBuild{{iwave == 1 ? 1 : 2, J > 1, two ? 2 : 1, fs, simple, fs == 2 && simple && a.farith != 0}, grid.x, b.fair};
+    }
 #define BH_LANE_LAUNCH(IF, LK, WP, FS, SI) hipLaunchKernelGGL((swd_kernel<IF, LK, WP, FS, SI>), grid, block, lds, stream, b)
 #define BH_LANE_PICK_FS(IF, LK, WP)                                                  \
     do {                                                                             \

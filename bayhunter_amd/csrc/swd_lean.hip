@@ -893,7 +893,7 @@ int bh_swd_lean_trials(int B, int nt)
 }
 
 // All targets of `a` (fundamental-mode phase velocities, a.t[t].look = trials per round, gcount / glist set) in one launch.
-int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo *info)
+int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo *info, SwdLaneBuild *build)
 {
     SwdMultiArgs a = a0;
     int kmax = 0, jmin = BH_WAVE;
@@ -931,6 +931,7 @@ int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo
     for (int t = 1; t < a.ntargets; ++t)
         if (a.t[t].look != J) return -1;
     const bool cnt = a.neval != nullptr; // (the build with the counters: bh_engine_set_instrumentation)
+    if (build != nullptr) *build = SwdLaneBuild{{(J == 4 || J == 8 || J == 16 || J == 32) ? J : 64, cnt, 0, 0, 0, 0}, grid.x * grid.y, 0};
 #define LEAN_LAUNCH(JJ)                                                                                                             \
     do {                                                                                                                            \
         if (cnt) hipLaunchKernelGGL((swd_lean_kernel<JJ, true>), grid, block, lds, stream, a, (int)wave_lds, flip);                 \

@@ -39,6 +39,12 @@ class EngineError(RuntimeError):
     pass
 
 
+class SwdLaunch(C.Structure):
+    """Mirror of `bh_swd_launch` (include/bh_engine_debug.h)."""
+    _fields_ = [("family", C.c_int), ("role", C.c_int), ("key", C.c_int * 6), ("two_classes", C.c_int), ("interleaved", C.c_int),
+                ("pair_order", C.c_int), ("restart", C.c_int), ("grid_x", C.c_int), ("fair", C.c_int)]
+
+
 class TargetDesc(C.Structure):
     """Mirror of `bh_target_desc` (include/bh_engine.h)."""
     _fields_ = [("kind", C.c_int32), ("law", C.c_int32), ("n", C.c_int32),
@@ -112,6 +118,7 @@ def load_library():
     L.bh_engine_get_swd_search.argtypes = [vp]
     L.bh_engine_set_swd_arith.argtypes = [vp, C.c_int]
     L.bh_engine_last_swd_kernel.argtypes = [vp]
+    L.bh_engine_last_swd_launches.argtypes = [vp, C.POINTER(SwdLaunch), C.c_int, C.POINTER(C.c_int)]
     L.bh_engine_set_swd_trials.argtypes = [vp, C.c_int]
     L.bh_engine_get_swd_trials.argtypes = [vp]
     L.bh_engine_get_swd_arith.argtypes = [vp]
@@ -174,7 +181,8 @@ EXPORTED_SYMBOLS = ("bh_abi_version", "bh_engine_create", "bh_engine_destroy", "
                     "bh_swd_batch", "bh_rf_batch", "bh_targets_set", "bh_evaluate_batch", "bh_loglike_batch",
                     "bh_chain_propose", "bh_chain_accept", "bh_chain_propose_window", "bh_chain_accept_window")
 # include/bh_engine_debug.h: measurement, diagnostics, experiment switches (bench.py, tools/, tests)
-DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_last_swd_kernel", "bh_engine_set_swd_scan",
+DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_last_swd_kernel", "bh_engine_last_swd_launches",
+                 "bh_engine_set_swd_scan",
                  "bh_engine_get_swd_scan", "bh_engine_set_tuning",
                  "bh_engine_get_tuning", "bh_probe_math", "bh_engine_set_instrumentation", "bh_timing_reset",
                  "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace")
@@ -329,6 +337,18 @@ class Engine(object):
     def last_swd_kernel(self):
         """Which dispersion kernel the most recent call launched: "group", "lane", "lean" (bh_engine_last_swd_kernel) or None."""
         return {0: "group", 1: "lane", 2: "lean"}.get(self._L.bh_engine_last_swd_kernel(self._h))
+
+    def last_swd_launches(self):
+        """Every dispersion kernel launch of the most recent call with dispersion targets (bh_engine_last_swd_launches), in launch
+        order: dicts of family ("group" / "lane" / "lean"), role ("main" / "rerun" / "second"), key (the instantiation's template
+        arguments, a tuple of 6 ints) and the launch's features."""
+        out = (SwdLaunch * 32)()
+        n = C.c_int(0)
+        self._check(self._L.bh_engine_last_swd_launches(self._h, out, 32, C.byref(n)))
+        return [dict(family={0: "group", 1: "lane", 2: "lean"}[r.family], role={0: "main", 1: "rerun", 2: "second"}[r.role],
+                     key=tuple(r.key), two_classes=bool(r.two_classes), interleaved=bool(r.interleaved),
+                     pair_order=bool(r.pair_order), restart=bool(r.restart), grid_x=int(r.grid_x), fair=int(r.fair))
+                for r in out[:n.value]]
 
     def swd_arith(self):
         return "fast" if self._L.bh_engine_get_swd_arith(self._h) == ARITH_FAST else "exact"

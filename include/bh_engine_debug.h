@@ -40,6 +40,25 @@ int bh_engine_set_swd_lookahead(bh_engine *e, int trials_per_round);
 #define BH_KERNEL_LEAN 2
 int bh_engine_last_swd_kernel(const bh_engine *e);
 
+/* Every dispersion kernel launch of the most recent call with dispersion targets (diagnostic; filled on the host from the launch
+ * plans, in launch order).  family: BH_KERNEL_*; role: BH_SWD_MAIN (the call's targets), BH_SWD_RERUN (the models the guard of
+ * the short refinement listed, again with the reference's sequence), BH_SWD_SECOND (the second roots of split group velocities).
+ * key: the template arguments of the instantiation launched --
+ *   BH_KERNEL_GROUP  FASTM, SIMPLE, PROF, ADAPT, CNTB, FA   (swd_group_kernel)
+ *   BH_KERNEL_LANE   IFUNC, LOOK, WPB, FAST, SIMPLE, FA     (swd_kernel)
+ *   BH_KERNEL_LEAN   J, CNT, 0, 0, 0, 0                     (swd_lean_kernel)
+ * and the launch's features: two depth classes, two targets interleaved in one grid, the SIMD-pairing order of the models,
+ * restart in place of guarded models, workgroups in x, the lane kernel's priority time slice (log2 cycles; 0 = none).
+ * Writes at most `max` records and returns their number in *n. */
+typedef struct {
+    int family, role, key[6];
+    int two_classes, interleaved, pair_order, restart, grid_x, fair;
+} bh_swd_launch;
+#define BH_SWD_MAIN 0
+#define BH_SWD_RERUN 1
+#define BH_SWD_SECOND 2
+int bh_engine_last_swd_launches(const bh_engine *e, bh_swd_launch *out, int max, int *n);
+
 /* The bracket scan of Love targets (any root refinement).  Results never depend on this setting.
  * getsol's scan (surfdisp96.f:437-460) evaluates every step of its grid until the secular function changes sign.  For Love
  * waves the number of sign changes below a trial velocity is read off the recursion that evaluates the function (a Sturm
