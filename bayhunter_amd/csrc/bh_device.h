@@ -151,9 +151,36 @@ struct SwdMultiArgs {
                        //    sequence in its own wavefront (the build with both sequences) instead of being listed for a re-run launch
     SwdTarget t[8];
 };
+// Dispersion periods per site (bh_sites_set_x, include/bh_engine_sites_x.h): an argument of its own of the SITE-PERIOD builds of
+// the dispersion kernels (swd_lean_x.hip, swd_group_x.hip: the same sources compiled with BH_SWD_SITEX), so that SwdMultiArgs
+// and the builds without it keep their layout and machine code.  A model of site s searches target `ty` of the launch at the
+// n[s * nt + col[ty]] periods x[s * ldx + off[ty] ...]; SwdTarget::K is the CAPACITY of the target's ymod columns (the largest
+// count of any site), SwdTarget::periods is not read.  A site out of range reads nothing of the tables and fails in band.
+struct SwdSiteXArgs {
+    const int32_t *site; // device [B]: site of every model (null: the call has no per-site periods)
+    int nsites, nt, ldx; // row strides of n (the registered targets) and x (ymod's row)
+    const int32_t *n;    // device [nsites][nt]
+    const double *x;     // device [nsites][ldx], targets in ymod's column layout
+    int col[8], off[8];  // per target of the launch (SwdMultiArgs::t): its registered target and column offset
+};
+// the count of periods (0 ... cap; -1: site out of range) of model ib for target ty of the launch
+__device__ __forceinline__ int bh_site_count(const SwdSiteXArgs &X, int ty, int ib, int cap)
+{
+    const int s = X.site[ib];
+    if (s < 0 || s >= X.nsites) return -1;
+    const int n = X.n[(size_t)s * X.nt + X.col[ty]];
+    return n < 0 ? 0 : (n > cap ? cap : n);
+}
+// ... and the periods themselves (per; the table's start for a site out of range: nothing of it is read)
+__device__ __forceinline__ int bh_site_periods(const SwdSiteXArgs &X, int ty, int ib, int cap, const double *&per)
+{
+    const int n = bh_site_count(X, ty, ib, cap);
+    per = n < 0 ? X.x : X.x + (size_t)X.site[ib] * X.ldx + X.off[ty];
+    return n;
+}
 int bh_swd_pick_group(int B, int ntargets, int Lmax);
 double bh_swd_plan(int B, int Lmax, int ntargets, const int *iwave, int Gforce, int *G, int *look);
-size_t bh_swd_group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode);
+size_t bh_swd_group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode, bool sitex = false);
 // Work space of the SIMD-pairing order (swd_kernel.hip: pair_order_kernel; bh_engine.hip: order_models).  The
 // dispersion kernel's time is that of its slowest SIMD, a SIMD's time follows the SUM of the root-search lengths of the
 // two wavefronts it holds, and which wavefronts of a launch share a SIMD is a fixed function of their grid index; so the
@@ -201,6 +228,7 @@ struct SwdGroupAsk {
     bool fast, farith, restart;  // the short refinement, its fast arithmetic, restarts in place: asked for
     bool adapt_ok, rerun;        // SwdMultiArgs::adapt_ok and ::rerun
     bool counters;               // the build with counters and clocks (SwdMultiArgs::neval set)
+    bool sitex;                  // periods per MODEL (SwdSiteXArgs): a wavefront's LDS holds a row of K periods for each of its models
     int scan;                    // the counted scan asked for: 0, 1 = wherever a Love target is, 2 = where it pays
 };
 // Which instantiation of swd_group_kernel a launch takes (its template arguments but WPB).
@@ -229,6 +257,15 @@ SwdGroupPlan bh_plan_swd_group(const SwdGroupAsk &q, const BhTuning &tun);
 // The launch of plan g with arguments a (whose rows, lanes, wg_n*, fast, counted, farith and restart are g's).  Every build a plan
 // can name is compiled (tests/test_swd_group_plan.py).
 void bh_launch_swd_group(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stream);
+// ... of the site-period build of the same name (swd_group_x.hip; q.sitex was set): false if the plan's build is not compiled
+bool bh_launch_swd_group_x(const SwdMultiArgs &a, const SwdGroupPlan &g, const SwdSiteXArgs &x, hipStream_t stream);
+struct SwdGroupXStream { // what a site-period build is launched with
+    hipStream_t st;
+    const SwdSiteXArgs *x;
+};
+bool bh_swd_group_builds_fa_x(const SwdMultiArgs &a, const SwdGroupPlan &g, SwdGroupXStream s);
+bool bh_swd_group_builds_adapt_x(const SwdMultiArgs &a, const SwdGroupPlan &g, SwdGroupXStream s);
+bool bh_swd_group_builds_big_x(const SwdMultiArgs &a, const SwdGroupPlan &g, SwdGroupXStream s);
 // The builds each translation unit of swd_group_kernel compiles (swd_group_fa.hip, swd_group_adapt.hip, swd_group_big.hip), one
 // signature: launches g's build if it is one of them.
 bool bh_swd_group_builds_fa(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stream);
@@ -237,8 +274,9 @@ bool bh_swd_group_builds_big(const SwdMultiArgs &a, const SwdGroupPlan &g, hipSt
 // swd_lean.hip: fundamental-mode phase velocities with the fast arithmetic, one lane per trial velocity (the kernel of the
 // engine's default settings for batches up to a few ten thousand models); a.t[t].look = trials per model and round
 int bh_swd_lean_trials(int B, int ntargets);
-size_t bh_swd_lean_lds_bytes(int J, int Lmax, int Kmax);
+size_t bh_swd_lean_lds_bytes(int J, int Lmax, int Kmax, bool sitex = false); // sitex: a row of Kmax periods per model
 int bh_launch_swd_lean(const SwdMultiArgs &a, hipStream_t stream, SwdLaunchInfo *info, SwdLaneBuild *build = nullptr);
+int bh_launch_swd_lean_x(const SwdMultiArgs &a, const SwdSiteXArgs &x, hipStream_t stream, SwdLaunchInfo *info, SwdLaneBuild *build = nullptr);
 // earth-flattening of a batch (surfdisp96.f:486-553): writes layer-major [Lmax][B] float64 copies
 // (binary32-valued) of thickness, vp, vs and the Love / Rayleigh density mappings
 void bh_launch_sphere(int B, int Lmax, const int32_t *nlay, const double *h, const double *vp,
@@ -330,6 +368,13 @@ struct LikeSiteArgs {
     const double *logdet_extra;  // device [nsites][nt]: ln prod(yerr / min(yerr)) of law-1 targets (else unread)
 };
 void bh_launch_like_sites(const LikeKernelArgs &a, const LikeSiteArgs &sites, hipStream_t stream);
+// ... with the sample count of every (site, target) from a table (bh_sites_set_x): LikeTargetDev::n is then the capacity of the
+// target's columns.  n is uniform per workgroup / wavefront (one model each), the sums run over the site's first n samples in the
+// order the kernels without the table use for that n.
+struct LikeSiteXArgs : LikeSiteArgs {
+    const int32_t *n; // device [nsites][nt]
+};
+void bh_launch_like_sites_x(const LikeKernelArgs &a, const LikeSiteXArgs &sites, hipStream_t stream);
 
 void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 

@@ -7,6 +7,7 @@
 #include "../../include/bh_engine_debug.h"
 #include "../../include/bh_engine_sites.h"
 #include "../../include/bh_engine_sites_rf.h"
+#include "../../include/bh_engine_sites_x.h"
 #include "bh_device.h"
 
 #include <algorithm>
@@ -143,6 +144,9 @@ struct bh_engine {
     // receiver-function parameters per site (bh_sites_set_rf, include/bh_engine_sites_rf.h): part of the site table
     bool site_rf = false;
     DevBuf site_p, site_nsv;                  // [nsites][nt]: p (s/deg) and nsv of every site, read in the RF columns only
+    // dispersion periods per site (bh_sites_set_x, include/bh_engine_sites_x.h): registered together with the site table
+    bool site_x = false;
+    DevBuf site_xn, site_xper;                // [nsites][nt] sample counts (int32), [nsites][ldy] periods in ymod's column layout
     // instrumentation
     bool timing = false, counting = false;
     bool no_mfma = false; // BH_NO_MFMA env: Gauss law through the in-kernel mat-vec (A/B testing)
@@ -224,9 +228,10 @@ void release_target(TargetHost &t)
 // the site table's buffers (they belong to the registered targets: bh_targets_set and bh_engine_destroy release them)
 void release_sites(bh_engine *e)
 {
-    for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx, &e->site_p, &e->site_nsv}) release(*b);
+    for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx, &e->site_p, &e->site_nsv, &e->site_xn, &e->site_xper}) release(*b);
     e->nsites = 0;
     e->site_rf = false;
+    e->site_x = false;
 }
 
 // Targets.py:124-128, the nocorr_scalederr law: out = yerr / min(yerr), returns ln prod(out) (bh_targets_set, bh_sites_set)
@@ -359,6 +364,13 @@ int swd_supported(bh_engine *e, int K, int iwave, int &igr, int mode, int flsph)
     return BH_OK;
 }
 
+// The optional site arguments of a dispersion job: the periods and their count come from the model's site (SwdSiteXArgs), the
+// job's K is the capacity of its output columns and periods_dev is not read.  tab: null = the job's own periods.
+struct SwdSiteJob {
+    const SwdSiteXArgs *tab; // the call's table (site, nsites, strides, n, x); col / off filled per launch
+    int col, off;            // the job's registered target and its column offset in a row of x
+};
+
 struct SwdJob {
     int K, iwave, igr, ldv; // igr: BH_VEL_PHASE or BH_VEL_GROUP (swd_supported)
     const double *periods_dev;
@@ -366,6 +378,7 @@ struct SwdJob {
     int32_t *err;
     int mode = 1;
     int flsph = 0;
+    SwdSiteJob sx{}; // periods per site (bh_evaluate_sites with a table of bh_sites_set_x)
 };
 
 int swd_counter(bh_engine *e, hipStream_t st, unsigned long long **out)
@@ -429,6 +442,7 @@ struct SwdPlan {
     int G, lean_trials;                // lanes per model; trials per round of the trial-per-lane kernel (>= 4: it runs)
     int order, Lcut;                   // SwdOrder; Lcut < Lmax: two depth classes
     int len_mpw, len_xcd;              // ORDER_LENGTH: models per wavefront and wavefronts per workgroup of the XCD blocks (0: none)
+    bool sitex;                        // periods per model (SwdSiteJob): LDS rows of periods per model, no one-lane-per-evaluation kernel
     bool any_fast, farith, adapt_ok;   // some target takes the short refinement; its fast arithmetic; kernel may size lanes per model
     // per target: its job, trials per round, Love trials inside a lane group, and the trials of the group kernel's plan
     // (BH_DEBUG_PLAN prints these; the trial-per-lane kernel's differ)
@@ -439,11 +453,18 @@ struct SwdPlan {
 
 // The plan of one dispersion call, from the engine's settings, the experiment switches (bh_tuning.h) and the call's shape:
 // no HIP call, no allocation.  typ_given: the batch's typical layer count (0 = unknown).
+//   Periods per site (a job with SwdSiteJob::tab; then every job of the call has it): the site-period builds of the trial-per-lane
+// and group kernels keep a row of kmax periods for EACH model of a wavefront, so LDS is sized for "periods per model" (p.sitex).
+// Where the trial-per-lane kernel then asks for more than a workgroup's LDS -- few trials per round are many models per
+// wavefront: 4 trials = 16 models x 60 periods x 8 B beside 16 models of 16 layers are 86 KB -- the call falls back to the group
+// kernel, as it does for deep arrays.  The one-lane-per-evaluation kernel (swd_kernel) has no site-period build: such calls take at least two
+// lanes per model (the group kernel), as deep arrays already do.
 SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, const SwdJob *jobs)
 {
     const BhTuning &tun = bh_tuning();
     SwdPlan p{};
     p.maxmode = 1;
+    for (int j = 0; j < njobs; ++j) p.sitex = p.sitex || jobs[j].sx.tab != nullptr;
     int iw[BH_MAX_TARGETS], nfast = 0;
     for (int j = 0; j < njobs; ++j) {
         const SwdJob &J = jobs[j];
@@ -490,7 +511,7 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
             for (int t = 0; t < nlive; ++t) look[t] = e->force_look; // (one lane per model: rounded down to a power of two)
     }
     const size_t lds_cap = 64 * 1024;
-    if (p.G <= 1 && bh_swd_lds_bytes(Lmax, p.kmax, p.maxmode) > lds_cap) p.G = 2; // deep models / many periods
+    if (p.G <= 1 && (p.sitex || bh_swd_lds_bytes(Lmax, p.kmax, p.maxmode) > lds_cap)) p.G = 2; // deep models / many periods / periods per site
     // The trial-per-lane kernel (swd_lean.hip): every target of the call takes the short refinement with the fast arithmetic, in
     // calls of up to 2^20 (model, target) pairs (with four trials per round it stays ahead of one lane per evaluation -- swd_kernel's
     // FA builds -- as far as measured: c2 at B = 65 536 7.99 against 8.44 ms).
@@ -500,7 +521,7 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
                    Lmax <= 32 && (long)B * nlive <= (tun.swd_lean_pairs > 0 ? (long)tun.swd_lean_pairs : (1L << 20));
         for (int t = 0; t < nlive; ++t) all = all && jobs[p.job[t]].igr == BH_VEL_PHASE;
         if (all) p.lean_trials = e->swd_trials > 0 ? e->swd_trials : bh_swd_lean_trials(B, nlive);
-        if (p.lean_trials >= 4 && bh_swd_lean_lds_bytes(p.lean_trials, Lmax, p.kmax) > lds_cap) p.lean_trials = 0; // (a workgroup's LDS)
+        if (p.lean_trials >= 4 && bh_swd_lean_lds_bytes(p.lean_trials, Lmax, p.kmax, p.sitex) > lds_cap) p.lean_trials = 0; // (a workgroup's LDS)
     }
     const bool lean = p.lean_trials >= 4;
     if (lean && p.G <= 1) p.G = bh_swd_pick_group(B, nlive, Lmax); // (the launch is set up where the group kernel's is)
@@ -591,7 +612,7 @@ SwdGroupPlan plan_group(const bh_engine *e, const SwdPlan &p, int B, int Lmax, c
     }
     q.fast = p.any_fast; q.farith = p.farith;
     q.restart = true; // (takes effect in launches of one model per wavefront)
-    q.adapt_ok = p.adapt_ok; q.counters = e->counting; q.scan = e->swd_scan;
+    q.adapt_ok = p.adapt_ok; q.counters = e->counting; q.scan = e->swd_scan; q.sitex = p.sitex;
     return bh_plan_swd_group(q, bh_tuning());
 }
 
@@ -607,6 +628,7 @@ struct SwdCall {
     const int32_t *pair_perm[2] = {};    // ORDER_PAIR: the order of target 0 / 1 (SwdTarget::perm)
     unsigned long long *counter = nullptr;
     int32_t *gcounts = nullptr, *glists = nullptr; // the guard of the short refinement (guard_space)
+    SwdSiteXArgs sx{};                   // p.sitex: the period table with the launch's targets (launch_swd_multi)
 };
 
 // The kernel arguments of job j as a target: its model arrays (the batch's, or the flattened copies with the density of its wave
@@ -763,7 +785,8 @@ bool build_slot_ranks(int n0, int n1, int ncu, std::vector<int32_t> rank[2])
 // again, with the reference's sequence -- one model per wavefront, as many trials per round as its lanes admit.  The launch
 // is sized for the worst case and reads the counts on the device: workgroups beyond them leave at once (no host round trip;
 // nearly always all of them).  Rows and failure flags of the listed models are overwritten with the reference's.
-int launch_swd_rerun(bh_engine *e, hipStream_t st, const SwdMultiArgs &main, int32_t *counts, int32_t *lists)
+// sx: null, or the period table of the main launch (its targets are this launch's): the site-period build of the same name.
+int launch_swd_rerun(bh_engine *e, hipStream_t st, const SwdMultiArgs &main, int32_t *counts, int32_t *lists, const SwdSiteXArgs *sx = nullptr)
 {
     SwdMultiArgs a = main;
     a.rerun = 1;
@@ -786,11 +809,12 @@ int launch_swd_rerun(bh_engine *e, hipStream_t st, const SwdMultiArgs &main, int
         T.inlook = 1;
         q.t[t] = SwdGroupAsk::Target{T.K, T.look, T.iwave, T.mode, T.igr != 0, T.refseq != 0};
     }
-    q.adapt_ok = q.rerun = true; q.counters = a.neval != nullptr; q.scan = e->swd_scan;
+    q.adapt_ok = q.rerun = true; q.counters = a.neval != nullptr; q.scan = e->swd_scan; q.sitex = sx != nullptr;
     const SwdGroupPlan g = bh_plan_swd_group(q, bh_tuning());
     if (!g.fits) return fail(e, BH_EINVAL, "model too deep for LDS");
     set_group_args(a, g);
-    bh_launch_swd_group(a, g, st);
+    if (sx == nullptr) bh_launch_swd_group(a, g, st);
+    else if (!bh_launch_swd_group_x(a, g, *sx, st)) return fail(e, BH_EUNSUPPORTED, "no site-period build of this dispersion launch");
     note_group(e, BH_SWD_RERUN, g, false);
     HIPCHK(e, hipGetLastError());
     ++e->rerun_launches;
@@ -935,6 +959,13 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
     a.started = e->started;
     a.prio_low = e->swd_prio_low_now;
     a.adapt_ok = p.adapt_ok ? 1 : 0;
+    if (p.sitex) { // the period table with this launch's targets
+        c.sx = *c.jobs[p.job[0]].sx.tab;
+        for (int t = 0; t < p.ntargets; ++t) {
+            c.sx.col[t] = c.jobs[p.job[t]].sx.col;
+            c.sx.off[t] = c.jobs[p.job[t]].sx.off;
+        }
+    }
     const bool lean = p.kernel == BH_KERNEL_LEAN;
     if (lean) {
         a.counted = e->swd_scan;
@@ -964,10 +995,12 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
     e->last_swd_kernel = p.kernel;
     if (lean) {
         SwdLaneBuild lb{};
-        if (bh_launch_swd_lean(a, c.st, &e->last_swd, &lb) != 0) return fail(e, BH_EINVAL, "model too deep for LDS");
+        if ((p.sitex ? bh_launch_swd_lean_x(a, c.sx, c.st, &e->last_swd, &lb) : bh_launch_swd_lean(a, c.st, &e->last_swd, &lb)) != 0)
+            return fail(e, BH_EINVAL, "model too deep for LDS");
         note_launch(e, BH_KERNEL_LEAN, BH_SWD_MAIN, lb.key, false, p.ntargets == 2, false, false, lb.grid_x, 0);
     } else {
-        bh_launch_swd_group(a, c.g, c.st);
+        if (!p.sitex) bh_launch_swd_group(a, c.g, c.st);
+        else if (!bh_launch_swd_group_x(a, c.g, c.sx, c.st)) return fail(e, BH_EUNSUPPORTED, "no site-period build of this dispersion launch");
         note_group(e, BH_SWD_MAIN, c.g, c.pair_perm[0] != nullptr);
         e->last_swd = c.g.info;
     }
@@ -1057,7 +1090,7 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
     SwdMultiArgs a{};
     rc = p.kernel == BH_KERNEL_LANE ? launch_swd_lanes(c, a) : launch_swd_multi(c, a);
     // (guarded models of the short refinement: re-run, unless the group kernel restarts them in place)
-    if (!rc && p.any_fast && !(p.kernel == BH_KERNEL_GROUP && c.g.restart)) rc = launch_swd_rerun(e, st, a, c.gcounts, c.glists);
+    if (!rc && p.any_fast && !(p.kernel == BH_KERNEL_GROUP && c.g.restart)) rc = launch_swd_rerun(e, st, a, c.gcounts, c.glists, p.sitex ? &c.sx : nullptr);
     if (!rc && p.nsplit > 0) rc = launch_second_roots(c);
     ev_end(e, 0, st);
     return rc;
@@ -1685,6 +1718,9 @@ int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const in
     la.noise = noise_d; la.logL = logL_d; la.misfits = misf_d; la.err = err_d;
     SwdJob jobs[BH_MAX_TARGETS];
     int njobs = 0;
+    // (periods per site, bh_sites_set_x: every dispersion job reads its models' periods and counts from the table)
+    const bool x_table = site && e->site_x;
+    const SwdSiteXArgs xtab{site, e->nsites, nt, ldy, (const int32_t *)e->site_xn.p, (const double *)e->site_xper.p, {}, {}};
     for (int t = 0; t < nt; ++t) {
         TargetHost &T = e->targets[(size_t)t];
         const bh_target_desc &d = T.d;
@@ -1692,6 +1728,7 @@ int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const in
             int32_t *errp = (int32_t *)e->err_t.p + (size_t)t * B;
             if (T.kfwd == d.n) {
                 jobs[njobs++] = SwdJob{d.n, d.iwave, d.igr, ldy, (const double *)T.x.p, ymod_d + T.off, errp, d.mode, d.flsph};
+                if (x_table) jobs[njobs - 1].sx = SwdSiteJob{&xtab, t, T.off};
             } else { // > 60 periods: run on the 60-point grid, interpolate afterwards
                 if ((rc = ensure(e, T.vel60, (size_t)B * T.kfwd * sizeof(double)))) return rc;
                 jobs[njobs++] = SwdJob{T.kfwd, d.iwave, d.igr, T.kfwd, (const double *)T.x60.p, (double *)T.vel60.p, errp, d.mode, d.flsph};
@@ -1773,7 +1810,12 @@ int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const in
     for (int t = 0; t < nt; ++t)
         if ((rc = prepare_like_target(e, st, B, ldy, ymod_d, e->targets[(size_t)t], la.t[t], site))) return rc;
     ev_begin(e, 2, st);
-    if (site) {
+    if (x_table) { // (a site's own sample counts)
+        LikeSiteXArgs lx{};
+        lx.site = site; lx.nsites = e->nsites; lx.yobs = (const double *)e->site_yobs.p; lx.yerr_scaled = (const double *)e->site_yerr.p;
+        lx.logdet_extra = (const double *)e->site_logdet.p; lx.n = (const int32_t *)e->site_xn.p;
+        bh_launch_like_sites_x(la, lx, st);
+    } else if (site) {
         const LikeSiteArgs ls{site, e->nsites, (const double *)e->site_yobs.p, (const double *)e->site_yerr.p,
                               (const double *)e->site_logdet.p};
         bh_launch_like_sites(la, ls, st);
@@ -1805,26 +1847,25 @@ int bh_evaluate_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax,
     return evaluate(e, memspace, stream, B, Lmax, nlay, h, vp, vs, rho, sl, sb, nullptr, noise, logL, misfits, err, ymod);
 }
 
-int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yerr)
+// bh_sites_set (n == null: every site has the descriptors' counts) and bh_sites_set_x (n[s * nt + t] samples of site s for
+// target t: yobs, yerr and the scaled-error tables are formed over a site's own samples; the columns beyond them hold 0 / 1)
+static int sites_register(bh_engine *e, int nsites, const int32_t *n, const double *yobs, const double *yerr)
 {
-    if (!e) return BH_EINVAL;
-    if (e->nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
-    if (nsites < 1 || !yobs) return fail(e, BH_EINVAL, "bh_sites_set needs nsites >= 1 and yobs");
     const int nt = e->nt, ldy = e->ldy;
-    bool scaled = false;
-    for (const auto &T : e->targets) scaled = scaled || T.d.law == BH_LAW_NOCORR_SCALED;
-    if (scaled && !yerr) return fail(e, BH_EINVAL, "a BH_LAW_NOCORR_SCALED target needs yerr of every site");
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     release_sites(e);
     const size_t S = (size_t)nsites;
-    std::vector<double> se(S * ldy, 1.0), ld(S * nt, 0.0);
+    std::vector<double> se(S * ldy, 1.0), ld(S * nt, 0.0), yo;
+    if (n) yo.assign(S * ldy, 0.0);
     for (size_t s = 0; s < S; ++s)
         for (int t = 0; t < nt; ++t) {
             const TargetHost &T = e->targets[(size_t)t];
+            const int ns = n ? n[s * nt + t] : T.d.n;
             ld[s * nt + t] = T.logdet_extra;
             if (T.d.law == BH_LAW_NOCORR_SCALED)
-                ld[s * nt + t] = scaled_errors(yerr + s * ldy + T.off, T.d.n, se.data() + s * ldy + T.off);
+                ld[s * nt + t] = scaled_errors(yerr + s * ldy + T.off, ns, se.data() + s * ldy + T.off);
+            if (n) std::copy(yobs + s * ldy + T.off, yobs + s * ldy + T.off + ns, yo.data() + s * ldy + T.off);
         }
     int rc;
     if ((rc = ensure(e, e->site_yobs, S * ldy * sizeof(double))) || (rc = ensure(e, e->site_yerr, S * ldy * sizeof(double))) ||
@@ -1832,13 +1873,82 @@ int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yer
         release_sites(e);
         return rc;
     }
-    if (hipMemcpy(e->site_yobs.p, yobs, S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+    if (hipMemcpy(e->site_yobs.p, n ? yo.data() : yobs, S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(e->site_yerr.p, se.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(e->site_logdet.p, ld.data(), S * nt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
         release_sites(e);
         return fail(e, BH_EHIP, "copy site table");
     }
     e->nsites = nsites;
+    return BH_OK;
+}
+
+int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yerr)
+{
+    if (!e) return BH_EINVAL;
+    if (e->nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
+    if (nsites < 1 || !yobs) return fail(e, BH_EINVAL, "bh_sites_set needs nsites >= 1 and yobs");
+    bool scaled = false;
+    for (const auto &T : e->targets) scaled = scaled || T.d.law == BH_LAW_NOCORR_SCALED;
+    if (scaled && !yerr) return fail(e, BH_EINVAL, "a BH_LAW_NOCORR_SCALED target needs yerr of every site");
+    return sites_register(e, nsites, nullptr, yobs, yerr);
+}
+
+int bh_sites_set_x(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+{
+    if (!e) return BH_EINVAL;
+    if (e->nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
+    if (nsites < 1 || !n || !x || !yobs) return fail(e, BH_EINVAL, "bh_sites_set_x needs nsites >= 1, n, x and yobs");
+    const int nt = e->nt, ldy = e->ldy;
+    bool scaled = false;
+    for (const auto &T : e->targets) scaled = scaled || T.d.law == BH_LAW_NOCORR_SCALED;
+    if (scaled && !yerr) return fail(e, BH_EINVAL, "a BH_LAW_NOCORR_SCALED target needs yerr of every site");
+    const size_t S = (size_t)nsites;
+    for (int t = 0; t < nt; ++t) {
+        const TargetHost &T = e->targets[(size_t)t];
+        const bh_target_desc &d = T.d;
+        if (d.kind != BH_TARGET_SWD) { // (a receiver function's x is its descriptor's time axis: shared)
+            for (size_t s = 0; s < S; ++s)
+                if (n[s * nt + t] != d.n) return fail(e, BH_EINVAL, "bh_sites_set_x: the sample count of a target that is no dispersion curve differs from its descriptor's");
+            continue;
+        }
+        if (d.law == BH_LAW_GAUSS) return fail(e, BH_EINVAL, "bh_sites_set_x: a dispersion target with the Gauss law (its R^-1 depends on the sample count)");
+        if (T.kfwd != d.n) return fail(e, BH_EUNSUPPORTED, "bh_sites_set_x: a dispersion target of more than 60 periods (the interpolation path)");
+        for (size_t s = 0; s < S; ++s) {
+            const int ns = n[s * nt + t];
+            if (ns < 1 || ns > d.n) return fail(e, BH_EINVAL, "bh_sites_set_x: a site's period count is below 1 or above the descriptor's n (the capacity)");
+            for (int i = 0; i < ns; ++i) {
+                const double v = x[s * ldy + T.off + i];
+                if (!std::isfinite(v) || !(v > 0.0)) return fail(e, BH_EINVAL, "bh_sites_set_x: a period that is not finite and positive");
+            }
+        }
+        if (d.igr != BH_VEL_PHASE || d.mode > 1) { // group velocities, higher modes: only with the descriptor's periods at every site
+            std::vector<double> x0((size_t)d.n);
+            HIPCHK(e, hipSetDevice(e->device));
+            HIPCHK(e, hipMemcpy(x0.data(), T.x.p, (size_t)d.n * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t s = 0; s < S; ++s)
+                if (n[s * nt + t] != d.n || std::memcmp(x0.data(), x + s * ldy + T.off, (size_t)d.n * sizeof(double)) != 0)
+                    return fail(e, BH_EUNSUPPORTED, "bh_sites_set_x: per-site periods on a group-velocity or higher-mode target");
+        }
+    }
+    int rc = sites_register(e, nsites, n, yobs, yerr);
+    if (rc) return rc;
+    std::vector<double> xs(S * ldy, 0.0);
+    for (size_t s = 0; s < S; ++s)
+        for (int t = 0; t < nt; ++t) {
+            const TargetHost &T = e->targets[(size_t)t];
+            if (T.d.kind == BH_TARGET_SWD) std::copy(x + s * ldy + T.off, x + s * ldy + T.off + n[s * nt + t], xs.data() + s * ldy + T.off);
+        }
+    if ((rc = ensure(e, e->site_xn, S * nt * sizeof(int32_t))) || (rc = ensure(e, e->site_xper, S * ldy * sizeof(double)))) {
+        release_sites(e);
+        return rc;
+    }
+    if (hipMemcpy(e->site_xn.p, n, S * nt * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(e->site_xper.p, xs.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        release_sites(e);
+        return fail(e, BH_EHIP, "copy site table");
+    }
+    e->site_x = true;
     return BH_OK;
 }
 

@@ -40,6 +40,15 @@ __device__ __forceinline__ LikeTargetDev site_target(LikeTargetDev T, const Like
     return T;
 }
 
+// ... of a site with its own sample counts (bh_sites_set_x): n from the table -- uniform over the workgroup / wavefront, whose
+// model is one -- so the sums below run over the site's first n samples in the order they have for a target of n samples
+__device__ __forceinline__ LikeTargetDev site_target(LikeTargetDev T, const LikeSiteXArgs &S, int site, int ldy, int nt, int t)
+{
+    T = site_target(T, static_cast<const LikeSiteArgs &>(S), site, ldy, nt, t);
+    T.n = S.n[(size_t)site * nt + t];
+    return T;
+}
+
 __global__ __launch_bounds__(256) void like_kernel(LikeKernelArgs A)
 {
     constexpr bool SITES = false;
@@ -67,6 +76,18 @@ __global__ __launch_bounds__(256) void like_small_kernel(LikeKernelArgs A)
 
 // the same with a site table (bh_evaluate_sites)
 __global__ __launch_bounds__(256) void like_small_sites_kernel(LikeKernelArgs A, LikeSiteArgs S)
+{
+    constexpr bool SITES = true;
+#include "like_small_body.inc"
+}
+
+// the site kernels with the sample count of every (site, target) from a table (bh_sites_set_x)
+__global__ __launch_bounds__(256) void like_sites_x_kernel(LikeKernelArgs A, LikeSiteXArgs S)
+{
+    constexpr bool SITES = true;
+#include "like_body.inc"
+}
+__global__ __launch_bounds__(256) void like_small_sites_x_kernel(LikeKernelArgs A, LikeSiteXArgs S)
 {
     constexpr bool SITES = true;
 #include "like_small_body.inc"
@@ -107,7 +128,7 @@ __global__ void probe_kernel(int op, int n, const double *in, double *out)
 
 } // namespace
 
-static void launch_like(const LikeKernelArgs &a, const LikeSiteArgs *sites, hipStream_t stream)
+static void launch_like(const LikeKernelArgs &a, const LikeSiteArgs *sites, hipStream_t stream, const LikeSiteXArgs *sx = nullptr)
 {
     size_t lds = 0;
     for (int t = 0; t < a.nt; ++t)
@@ -118,6 +139,11 @@ static void launch_like(const LikeKernelArgs &a, const LikeSiteArgs *sites, hipS
     bool small = true;
     for (int t = 0; t < a.nt; ++t)
         small = small && (a.t[t].n <= 64 || (a.t[t].pre != nullptr && a.t[t].law != 3)) && !(a.t[t].law == 3 && a.t[t].quad == nullptr);
+    if (sx != nullptr) { // (n = the capacity of the target's columns: a site's own count is at most that)
+        if (small) hipLaunchKernelGGL(like_small_sites_x_kernel, dim3((a.B + 3) / 4), dim3(256), 0, stream, a, *sx);
+        else hipLaunchKernelGGL(like_sites_x_kernel, dim3(a.B), dim3(256), lds, stream, a, *sx);
+        return;
+    }
     if (sites != nullptr) {
         if (small) hipLaunchKernelGGL(like_small_sites_kernel, dim3((a.B + 3) / 4), dim3(256), 0, stream, a, *sites);
         else hipLaunchKernelGGL(like_sites_kernel, dim3(a.B), dim3(256), lds, stream, a, *sites);
@@ -129,6 +155,7 @@ static void launch_like(const LikeKernelArgs &a, const LikeSiteArgs *sites, hipS
 
 void bh_launch_like(const LikeKernelArgs &a, hipStream_t stream) { launch_like(a, nullptr, stream); }
 void bh_launch_like_sites(const LikeKernelArgs &a, const LikeSiteArgs &sites, hipStream_t stream) { launch_like(a, &sites, stream); }
+void bh_launch_like_sites_x(const LikeKernelArgs &a, const LikeSiteXArgs &sites, hipStream_t stream) { launch_like(a, nullptr, stream, &sites); }
 
 void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t stream)
 {

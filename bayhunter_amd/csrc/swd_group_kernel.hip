@@ -207,8 +207,19 @@ constexpr int ADAPT_MAX_TRIALS = 8;
 #ifndef BH_GROUP_WAVES
 #define BH_GROUP_WAVES 2
 #endif
+// 1: the SITE-PERIOD builds (swd_group_x.hip includes this file once per translation unit's list of builds): a model's period
+// list and count are its site's (SwdSiteXArgs, bh_device.h).  The wavefront stages a row of T.K (the capacity) periods for each
+// of its models and SearchT -- which always held K and the period pointer per lane -- gets its model's; nothing else differs, so a
+// model gets the bits of a launch whose target has its site's periods.  0: the builds this file always had, the same machine code.
+#ifndef BH_SWD_SITEX
+#define BH_SWD_SITEX 0
+#endif
 template <int WPB, int FASTM, bool SIMPLE, bool PROF, bool ADAPT, bool CNTB, bool FA = false>
+#if BH_SWD_SITEX
+__global__ __launch_bounds__(BH_WAVE * WPB) __attribute__((amdgpu_waves_per_eu(BH_GROUP_WAVES, BH_GROUP_WAVES))) void swd_group_kernel(SwdMultiArgs A, int Gflags, int wave_lds, SwdSiteXArgs X)
+#else
 __global__ __launch_bounds__(BH_WAVE * WPB) __attribute__((amdgpu_waves_per_eu(BH_GROUP_WAVES, BH_GROUP_WAVES))) void swd_group_kernel(SwdMultiArgs A, int Gflags, int wave_lds)
+#endif
 {
     // "this workgroup is resident": what a second stream waits for before it dispatches wavefronts beside these
     if (A.started != nullptr && threadIdx.x == 0) atomicAdd(A.started, 1u);
@@ -293,7 +304,14 @@ next_pass:
     const int32_t *perm = T.perm != nullptr ? T.perm : A.perm; // processing order: the target's own (SIMD pairing) or the batch's
     const int ib = valid ? (perm ? perm[sidx] : sidx) : 0;
     const int Lmax = ADAPT ? rows_own : A.rows[cls]; // LDS rows per model of this class (>= every layer count it meets)
+#if BH_SWD_SITEX
+    // K: this lane's model's own count (0 for a site out of range: the model fails in band); Kcap: the columns of its output row
+    const int Kcap = T.K, KE = (Kcap + 1) & ~1;
+    const int Kown = valid ? bh_site_count(X, ty, ib, Kcap) : 0;
+    const int K = Kown > 0 ? Kown : 0;
+#else
     const int K = T.K;
+#endif
     const int ifunc = T.iwave; // 1 Love, 2 Rayleigh: uniform per wavefront
 
     // LDS carve-up of the wavefront's region (all offsets multiples of 16 B)
@@ -301,12 +319,31 @@ next_pass:
     double *ca = reinterpret_cast<double *>(smem);                 // [MPW*J][prow][CA_STRIDE]
     double *xs = ca + (size_t)MPW * J * prow * CA_STRIDE;          // [11][MPW]
     double *ys = xs + NEV_MAX * MPW;
+#if BH_SWD_SITEX
+    double *per_all = ys + NEV_MAX * MPW;                          // [MPW][KE]: a row per model
+    float *mdl = reinterpret_cast<float *>(per_all + MPW * KE);    // [4][Lmax][MPW]
+    const double *per = per_all + g * KE;
+#else
     double *per = ys + NEV_MAX * MPW;                              // [K]
     float *mdl = reinterpret_cast<float *>(per + ((K + 1) & ~1));  // [4][Lmax][MPW]
+#endif
     unsigned char *after = reinterpret_cast<unsigned char *>(mdl) + (((size_t)4 * Lmax * MPW * sizeof(float) + 15) & ~(size_t)15);
     double *cpl = reinterpret_cast<double *>(after); // [2][Kmax][MPW], only if a target has mode > 1
 
+#if BH_SWD_SITEX
+    for (int idx = lane; idx < MPW * Kcap; idx += BH_WAVE) {
+        const int mg = idx / Kcap, kk = idx - mg * Kcap;
+        const int sbx = lo + wid * MPW + mg;
+        if (sbx < hi) {
+            const double *pr = X.x;
+            const int32_t *permx = T.perm != nullptr ? T.perm : A.perm;
+            const int kb = bh_site_periods(X, ty, permx ? permx[sbx] : sbx, Kcap, pr);
+            if (kk < kb) per_all[mg * KE + kk] = pr[kk];
+        }
+    }
+#else
     for (int k = lane; k < K; k += BH_WAVE) per[k] = T.periods[k];
+#endif
     // stage the models of this wave: consecutive lanes -> consecutive models (coalesced for
     // layer-major input), binary32 rounding like the f2py boundary
     for (int idx = lane; idx < Lmax * MPW; idx += BH_WAVE) {
@@ -357,7 +394,13 @@ next_pass:
     unsigned evals_before = 0u; // (evaluations of the abandoned first search: they count, as the re-run launch's would)
 restart_with_the_reference_sequence:
     S.init(md, mmax, valid, T.igr, K, per, xs + g, ys + g, T.vel + (size_t)ib * T.ldv, li == 0 && rr == 0 && !spare,
+#if BH_SWD_SITEX
+           T.mode, cpl + g, cpl + (size_t)Kcap * MPW + g, ifunc, CNTB && A.counted != 0, refseq_now, FA);
+    if (valid && li == 0 && rr == 0 && !spare && !restarted)
+        for (int i = K; i < Kcap; ++i) (T.vel + (size_t)ib * T.ldv)[i] = 0.0; // the columns beyond the site's own periods
+#else
            T.mode, cpl + g, cpl + (size_t)K * MPW + g, ifunc, CNTB && A.counted != 0, refseq_now, FA);
+#endif
     S.evals += evals_before;
 
     // per-period constants of this lane's first layer (m = li) and of the half-space: they depend
@@ -778,7 +821,11 @@ restart_with_the_reference_sequence:
     }
     if (board != nullptr) *reinterpret_cast<volatile unsigned *>(board + hw_slot) = (A.stamp << 16) | 0xffffu;
     if (valid && li == 0 && rr == 0 && !spare) {
+#if BH_SWD_SITEX
+        T.err[ib] = Kown < 0 ? 1 : S.errflag; // (site out of range)
+#else
         T.err[ib] = S.errflag;
+#endif
         if (!SIMPLE && T.igr == 2 && T.first != nullptr) T.first[ib] = S.del1st; // (the chain of a group velocity's first roots: SwdKernelArgs)
         if (FAST && S.has(S.F_GUARD) && T.gcount != nullptr) { // to be run again with the reference's sequence
             T.glist[atomicAdd(T.gcount, 1)] = ib;
@@ -827,12 +874,24 @@ restart_with_the_reference_sequence:
 
 // Launches build <FM, SI, PR, AD, CN, FA> of the kernel if it is plan g's.  Every translation unit lists the builds it compiles
 // (their flags and register budgets are what its machine code depends on: Makefile, swd_group_fa.hip, _adapt, _big).
+// (site-period builds: the "stream" is the stream and the period table, SwdGroupXStream, and the functions below end in _x)
+#if BH_SWD_SITEX
+typedef SwdGroupXStream GroupStream;
+#define BH_GROUP_FN(name) name##_x
+#else
+typedef hipStream_t GroupStream;
+#define BH_GROUP_FN(name) name
+#endif
 template <int FM, bool SI, bool PR, bool AD, bool CN, bool FA = false>
-bool launch_build(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stream)
+bool launch_build(const SwdMultiArgs &a, const SwdGroupPlan &g, GroupStream stream)
 {
     const SwdGroupBuild &b = g.build;
     if (b.fastm != FM || b.simple != SI || b.prof != PR || b.adapt != AD || b.cntb != CN || b.fa != FA) return false;
+#if BH_SWD_SITEX
+    hipLaunchKernelGGL((swd_group_kernel<GROUP_WPB, FM, SI, PR, AD, CN, FA>), g.grid, g.block, g.lds, stream.st, a, g.Gflags, (int)g.wave_lds, *stream.x);
+#else
     hipLaunchKernelGGL((swd_group_kernel<GROUP_WPB, FM, SI, PR, AD, CN, FA>), g.grid, g.block, g.lds, stream, a, g.Gflags, (int)g.wave_lds);
+#endif
     return true;
 }
 } // namespace
@@ -841,7 +900,7 @@ bool launch_build(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t stre
 // The build that needs more than 256 registers (this translation unit: swd_group_big.hip, ONE wavefront per SIMD as its register
 // budget): one model per wavefront, both sequences, the counted Love scan AND the counters and clocks -- an instrumented launch of a
 // sampler's window under BH_SEARCH_FAST_RAYLEIGH; counters and clocks are what it is for, not speed.
-bool bh_swd_group_builds_big(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t s)
+bool BH_GROUP_FN(bh_swd_group_builds_big)(const SwdMultiArgs &a, const SwdGroupPlan &g, GroupStream s)
 {
     return launch_build<1, true, true, true, true>(a, g, s);
 }
@@ -849,7 +908,7 @@ bool bh_swd_group_builds_big(const SwdMultiArgs &a, const SwdGroupPlan &g, hipSt
 // The one-model-per-wavefront builds (ADAPT: a sampler's windows, single models, the re-run of guarded models) in a translation unit
 // of their own (swd_group_adapt.hip: the same source, the same flags) -- a third of this file's instantiations: it halves the
 // build's longest compile.  (Both sequences with the counted scan and the counters: swd_group_big.hip.)
-bool bh_swd_group_builds_adapt(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t s)
+bool BH_GROUP_FN(bh_swd_group_builds_adapt)(const SwdMultiArgs &a, const SwdGroupPlan &g, GroupStream s)
 {
     return launch_build<2, true, true, true, false>(a, g, s) || launch_build<2, true, true, true, true>(a, g, s) ||
            launch_build<2, true, false, true, false>(a, g, s) || launch_build<2, true, false, true, true>(a, g, s) ||
@@ -860,7 +919,7 @@ bool bh_swd_group_builds_adapt(const SwdMultiArgs &a, const SwdGroupPlan &g, hip
 }
 #elif defined(BH_GROUP_FA_TU)
 // The builds with the fast arithmetic (this translation unit: swd_group_fa.hip).
-bool bh_swd_group_builds_fa(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t s)
+bool BH_GROUP_FN(bh_swd_group_builds_fa)(const SwdMultiArgs &a, const SwdGroupPlan &g, GroupStream s)
 {
     return launch_build<2, true, true, true, true, true>(a, g, s) || launch_build<2, true, true, true, false, true>(a, g, s) ||
            launch_build<2, true, false, true, true, true>(a, g, s) || launch_build<2, true, false, true, false, true>(a, g, s) ||
@@ -869,17 +928,8 @@ bool bh_swd_group_builds_fa(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStr
 }
 #else
 namespace {
-size_t group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode)
-{
-    const int MPW = BH_WAVE / (G * J);
-    return ((size_t)MPW * J * (Lmax > 1 ? Lmax - 1 : 1) * CA_STRIDE + (size_t)2 * NEV_MAX * MPW +
-            (size_t)((Kmax + 1) & ~1)) * sizeof(double) +
-           (((size_t)4 * Lmax * MPW * sizeof(float) + 15) & ~(size_t)15) +
-           (maxmode > 1 ? (size_t)2 * Kmax * MPW * sizeof(double) : 0);
-}
-
 // The builds of several models per wavefront in the reference's arithmetic (this translation unit).
-bool launch_builds(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t s)
+bool launch_builds(const SwdMultiArgs &a, const SwdGroupPlan &g, GroupStream s)
 {
     return launch_build<2, true, true, false, false>(a, g, s) || launch_build<2, true, true, false, true>(a, g, s) ||
            launch_build<2, true, false, false, false>(a, g, s) || launch_build<2, true, false, false, true>(a, g, s) ||
@@ -889,12 +939,30 @@ bool launch_builds(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream_t s)
            launch_build<0, true, false, false, false>(a, g, s) || launch_build<0, true, false, false, true>(a, g, s) ||
            launch_build<0, false, true, false, false>(a, g, s) || launch_build<0, false, true, false, true>(a, g, s);
 }
+#if !BH_SWD_SITEX
+// (sitex: the site-period builds keep a row of Kmax periods for each of the wavefront's models)
+size_t group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode, bool sitex)
+{
+    const int MPW = BH_WAVE / (G * J);
+    return ((size_t)MPW * J * (Lmax > 1 ? Lmax - 1 : 1) * CA_STRIDE + (size_t)2 * NEV_MAX * MPW +
+            (size_t)((Kmax + 1) & ~1) * (sitex ? MPW : 1)) * sizeof(double) +
+           (((size_t)4 * Lmax * MPW * sizeof(float) + 15) & ~(size_t)15) +
+           (maxmode > 1 ? (size_t)2 * Kmax * MPW * sizeof(double) : 0);
+}
+#endif
 } // namespace
 
-// LDS of one workgroup = shared libm tables + GROUP_WPB wavefront regions
-size_t bh_swd_group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode)
+#if BH_SWD_SITEX
+bool bh_launch_swd_group_x(const SwdMultiArgs &a, const SwdGroupPlan &g, const SwdSiteXArgs &x, hipStream_t stream)
 {
-    return LIBM_TAB_PAD + GROUP_WPB * ((group_lds_bytes(G, J, Lmax, Kmax, maxmode) + 15) & ~(size_t)15);
+    const SwdGroupXStream s{stream, &x};
+    return launch_builds(a, g, s) || bh_swd_group_builds_adapt_x(a, g, s) || bh_swd_group_builds_fa_x(a, g, s) || bh_swd_group_builds_big_x(a, g, s);
+}
+#else
+// LDS of one workgroup = shared libm tables + GROUP_WPB wavefront regions
+size_t bh_swd_group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode, bool sitex)
+{
+    return LIBM_TAB_PAD + GROUP_WPB * ((group_lds_bytes(G, J, Lmax, Kmax, maxmode, sitex) + 15) & ~(size_t)15);
 }
 
 // A wavefront's LDS region small enough for 8 wavefronts (4 workgroups) per CU of 160 KB
@@ -921,7 +989,7 @@ SwdGroupPlan bh_plan_swd_group(const SwdGroupAsk &q, const BhTuning &tun)
         auto wave_bytes = [&](int G) {
             size_t w = 0;
             for (int t = 0; t < nt; ++t)
-                w = std::max(w, (group_lds_bytes(G, bh_trials_fit(G, q.t[t].look), rows, kmax, maxmode) + 15) & ~(size_t)15);
+                w = std::max(w, (group_lds_bytes(G, bh_trials_fit(G, q.t[t].look), rows, kmax, maxmode, q.sitex) + 15) & ~(size_t)15);
             return w;
         };
         // fewer models per wavefront (more lanes per model) until the parked layers fit: first the
@@ -1038,4 +1106,5 @@ void bh_launch_swd_group(const SwdMultiArgs &a, const SwdGroupPlan &g, hipStream
     assert(launched && "the plan's build is compiled");
     (void)launched;
 }
+#endif
 #endif

@@ -34,6 +34,13 @@
 #define BH_HD __device__ __forceinline__
 #define BH_TAB static __device__ const
 #include "bh_libm.h"
+// 1: the SITE-PERIOD builds (swd_lean_x.hip includes this file): a model's period list and count are its site's (SwdSiteXArgs,
+// bh_device.h).  A wavefront stages a row of T.K (the capacity) angular frequencies for each of its models and every lane reads
+// its model's row; everything else -- the search, its arithmetic, the order of its operations -- is the code below, so a model
+// gets the bits of a launch whose target has its site's periods.  0: the builds this file always had, the same machine code.
+#ifndef BH_SWD_SITEX
+#define BH_SWD_SITEX 0
+#endif
 
 namespace {
 #include "swd_common.h"
@@ -148,7 +155,11 @@ constexpr int LEAN_WPB = 4; // wavefronts per workgroup: independent (no barrier
 // `counting`).  The counters cost 12 registers; without them the <16> build needs 197 (200 allocated), so that an 88-register
 // receiver-function wavefront fits beside the two dispersion wavefronts of a SIMD (2 x 200 + 88 <= 512).
 template <int J, bool CNT>
+#if BH_SWD_SITEX
+__global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiArgs A, int wave_lds, int flip, SwdSiteXArgs X)
+#else
 __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiArgs A, int wave_lds, int flip)
+#endif
 {
     // "this workgroup is resident": what a second stream waits for before it dispatches wavefronts beside these
     if (A.started != nullptr && threadIdx.x == 0) atomicAdd(A.started, 1u);
@@ -184,13 +195,33 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
     const bool valid = sidx < A.B;
     const int32_t *perm = T.perm != nullptr ? T.perm : A.perm;
     const int ib = valid ? (perm ? perm[sidx] : sidx) : 0;
-    const int Lmax = A.Lmax, K = T.K, ifunc = T.iwave;
     extern __shared__ __align__(16) unsigned char smem_lean[];
+    constexpr double dc = (double)0.005f, onea = (double)1.5f, twopi = 2.0 * 3.141592653589793, guard_rel = 3.0e-6;
+#if BH_SWD_SITEX
+    // K: this lane's model's own count (0 for a site out of range: the model fails in band); Kcap: the columns of its output row
+    const int Lmax = A.Lmax, Kcap = T.K, ifunc = T.iwave, KE = (Kcap + 1) & ~1;
+    const int Kown = valid ? bh_site_count(X, ty, ib, Kcap) : 0;
+    const int K = Kown > 0 ? Kown : 0;
+    double *omg_all = reinterpret_cast<double *>(smem_lean + (size_t)wave * wave_lds); // [MPW][KE]: 2 pi / period, a row per model
+    double *mdl = omg_all + MPW * KE;                                                  // [7][Lmax][MPW]
+    const double *omg = omg_all + g * KE;
+    const int LS = Lmax * MPW;
+    for (int idx = lane; idx < MPW * Kcap; idx += BH_WAVE) {
+        const int mg = idx / Kcap, kk = idx - mg * Kcap;
+        const int sbx = wid * MPW + mg;
+        if (sbx < A.B) {
+            const double *pr = X.x;
+            const int kb = bh_site_periods(X, ty, perm ? perm[sbx] : sbx, Kcap, pr);
+            if (kk < kb) omg_all[mg * KE + kk] = twopi / pr[kk];
+        }
+    }
+#else
+    const int Lmax = A.Lmax, K = T.K, ifunc = T.iwave;
     double *omg = reinterpret_cast<double *>(smem_lean + (size_t)wave * wave_lds); // [K]: 2 pi / period
     double *mdl = omg + ((K + 1) & ~1);                                            // [7][Lmax][MPW]
     const int LS = Lmax * MPW;
-    constexpr double dc = (double)0.005f, onea = (double)1.5f, twopi = 2.0 * 3.141592653589793, guard_rel = 3.0e-6;
     for (int k = lane; k < K; k += BH_WAVE) omg[k] = twopi / T.periods[k];
+#endif
     for (int idx = lane; idx < LS; idx += BH_WAVE) {
         const int l = idx / MPW, mg = idx - l * MPW;
         const int sb = wid * MPW + mg;
@@ -269,6 +300,11 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
         if (writer)
             for (int i = 0; i < K; ++i) vel[i] = 0.0;
     }
+#if BH_SWD_SITEX
+    if (valid && Kown < 0) errflag = 1; // (site out of range)
+    if (writer)
+        for (int i = K; i < Kcap; ++i) vel[i] = 0.0; // the columns beyond the site's own periods
+#endif
     if (active && md.Bv(0) <= 0.0) { // water layer on top: the reference's sequence
         LEAN_GUARD(1);
         active = false;
@@ -872,11 +908,15 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
 } // namespace
 
 // LDS of one workgroup (LEAN_WPB wavefronts, a private region each)
-static size_t lean_wave_lds(int J, int Lmax, int Kmax)
+// (sitex: the site-period builds keep a row of Kmax frequencies per model -- with 4 trials per round, 16 models per wavefront,
+// 60 periods and arrays of 16 layers that is 86 KB per workgroup instead of 58: more than a workgroup may ask for, the call
+// takes the group kernel, as it does without a period table from 18 layers on)
+static size_t lean_wave_lds(int J, int Lmax, int Kmax, bool sitex)
 {
-    return ((((size_t)((Kmax + 1) & ~1) + (size_t)7 * Lmax * (BH_WAVE / J)) * sizeof(double)) + 15) & ~(size_t)15;
+    return ((((size_t)((Kmax + 1) & ~1) * (sitex ? BH_WAVE / J : 1) + (size_t)7 * Lmax * (BH_WAVE / J)) * sizeof(double)) + 15) & ~(size_t)15;
 }
-size_t bh_swd_lean_lds_bytes(int J, int Lmax, int Kmax) { return LEAN_WPB * lean_wave_lds(J, Lmax, Kmax); }
+#if !BH_SWD_SITEX
+size_t bh_swd_lean_lds_bytes(int J, int Lmax, int Kmax, bool sitex) { return LEAN_WPB * lean_wave_lds(J, Lmax, Kmax, sitex); }
 
 // Trials per model and round for a call of `nt` targets over B models.  A round of J trials costs a wavefront what one trial
 // costs, so few models get many trials (the latency regime: fewer rounds) and many models few (the throughput regime: fewer
@@ -891,9 +931,14 @@ int bh_swd_lean_trials(int B, int nt)
     const long pairs = (long)B * nt;
     return pairs <= 1024 ? 64 : (pairs <= 5120 ? 32 : (pairs <= 10240 ? 16 : (pairs <= 28672 ? 8 : 4)));
 }
+#endif
 
 // All targets of `a` (fundamental-mode phase velocities, a.t[t].look = trials per round, gcount / glist set) in one launch.
+#if BH_SWD_SITEX
+int bh_launch_swd_lean_x(const SwdMultiArgs &a0, const SwdSiteXArgs &x, hipStream_t stream, SwdLaunchInfo *info, SwdLaneBuild *build)
+#else
 int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo *info, SwdLaneBuild *build)
+#endif
 {
     SwdMultiArgs a = a0;
     int kmax = 0, jmin = BH_WAVE;
@@ -908,7 +953,7 @@ int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo
         wmax = nw[t] > wmax ? nw[t] : wmax;
         wsum += nw[t];
     }
-    const size_t wave_lds = lean_wave_lds(jmin, a.Lmax, kmax);
+    const size_t wave_lds = lean_wave_lds(jmin, a.Lmax, kmax, BH_SWD_SITEX != 0);
     const size_t lds = LEAN_WPB * wave_lds;
     if (lds > 64 * 1024) return -1;
     dim3 grid((unsigned)((wmax + LEAN_WPB - 1) / LEAN_WPB), (unsigned)a.ntargets);
@@ -932,11 +977,19 @@ int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo
         if (a.t[t].look != J) return -1;
     const bool cnt = a.neval != nullptr; // (the build with the counters: bh_engine_set_instrumentation)
     if (build != nullptr) *build = SwdLaneBuild{{(J == 4 || J == 8 || J == 16 || J == 32) ? J : 64, cnt, 0, 0, 0, 0}, grid.x * grid.y, 0};
+#if BH_SWD_SITEX
+#define LEAN_LAUNCH(JJ)                                                                                                             \
+    do {                                                                                                                            \
+        if (cnt) hipLaunchKernelGGL((swd_lean_kernel<JJ, true>), grid, block, lds, stream, a, (int)wave_lds, flip, x);              \
+        else hipLaunchKernelGGL((swd_lean_kernel<JJ, false>), grid, block, lds, stream, a, (int)wave_lds, flip, x);                 \
+    } while (0)
+#else
 #define LEAN_LAUNCH(JJ)                                                                                                             \
     do {                                                                                                                            \
         if (cnt) hipLaunchKernelGGL((swd_lean_kernel<JJ, true>), grid, block, lds, stream, a, (int)wave_lds, flip);                 \
         else hipLaunchKernelGGL((swd_lean_kernel<JJ, false>), grid, block, lds, stream, a, (int)wave_lds, flip);                    \
     } while (0)
+#endif
     switch (J) {
     case 4: LEAN_LAUNCH(4); break;
     case 8: LEAN_LAUNCH(8); break;

@@ -147,6 +147,7 @@ def load_library():
     L.bh_probe_math.argtypes = [vp, C.c_int, C.c_int, _d, _d]
     L.bh_sites_set.argtypes = [vp, C.c_int, vp, vp]
     L.bh_sites_set_rf.argtypes = [vp, C.c_int, vp, vp]
+    L.bh_sites_set_x.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_evaluate_sites.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                     C.c_ssize_t, C.c_ssize_t, vp, vp, vp, vp, vp, vp]
     L.bh_chain_propose.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int]
@@ -165,7 +166,7 @@ def load_library():
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
-                 "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf"):
+                 "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x"):
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -190,6 +191,8 @@ DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_e
 SITE_SYMBOLS = ("bh_sites_set", "bh_evaluate_sites")
 # include/bh_engine_sites_rf.h: receiver-function ray parameter and near-surface velocity per site
 SITE_RF_SYMBOLS = ("bh_sites_set_rf",)
+# include/bh_engine_sites_x.h: dispersion periods per site
+SITE_X_SYMBOLS = ("bh_sites_set_x",)
 # include/bh_engine_posterior.h: posterior velocity-depth summaries of many sites (bayhunter_amd/posterior.py)
 POSTERIOR_SYMBOLS = ("bh_posterior_create", "bh_posterior_destroy", "bh_posterior_load", "bh_posterior_columns",
                      "bh_posterior_hist", "bh_posterior_interfaces")
@@ -544,6 +547,26 @@ class Engine(object):
             if yerr.shape != yobs.shape:
                 raise ValueError("yerr must have the shape of yobs")
         self._check(self._L.bh_sites_set(self._h, yobs.shape[0], _ptr(yobs), _ptr(yerr)))
+        self.nsites = yobs.shape[0]
+
+    def set_sites_x(self, n, x, yobs, yerr=None):
+        """The site table together with every site's own dispersion periods (bh_sites_set_x, instead of set_sites): n[S, nt]
+        int32 samples of every (site, target); x, yobs and yerr[S, ldy] in ymod's column layout, the columns beyond a site's
+        count unread.  The registered descriptors give every dispersion target's capacity (their n) and a placeholder x.
+        evaluate_sites then computes a model's dispersion curves at its site's periods; set_targets and set_sites drop the table."""
+        n = np.ascontiguousarray(n, dtype=np.int32)
+        x, yobs = _f64(x), _f64(yobs)
+        if yobs.ndim != 2 or yobs.shape[1] != self.ldy or yobs.shape[0] < 1:
+            raise ValueError("yobs must have shape (nsites, %d)" % self.ldy)
+        if x.shape != yobs.shape:
+            raise ValueError("x must have the shape of yobs")
+        if n.shape != (yobs.shape[0], self.ntargets):
+            raise ValueError("n must have shape (nsites, %d)" % self.ntargets)
+        if yerr is not None:
+            yerr = _f64(yerr)
+            if yerr.shape != yobs.shape:
+                raise ValueError("yerr must have the shape of yobs")
+        self._check(self._L.bh_sites_set_x(self._h, yobs.shape[0], _ptr(n), _ptr(x), _ptr(yobs), _ptr(yerr)))
         self.nsites = yobs.shape[0]
 
     def set_sites_rf(self, p, nsv):

@@ -6,13 +6,19 @@ The forward models depend on the model and x only, so one evaluation batch may m
 with the observed data of its own site (include/bh_engine_sites.h).  `SiteTargets` holds one `JointTarget` per site and
 registers site 0's target descriptors plus the table of every site's observed data on the engine.  The ray parameter p and
 near-surface velocity nsv of the receiver functions may differ between sites as well (per_site_rf=True,
-include/bh_engine_sites_rf.h): they enter only the coefficient stage of the forward model.
+include/bh_engine_sites_rf.h): they enter only the coefficient stage of the forward model.  So may the periods of the
+dispersion curves and their number (per_site_x=True, include/bh_engine_sites_x.h): every model is then searched at the
+periods of its own site, as a one-site run searches it.
 """
 import numpy as np
 
+from . import engine as _engine
 from .Targets import JointTarget, LAWS
 from .rfmini_modrf import RFminiModRF
 from .surf96_modsw import SurfDisp
+
+# the most periods a site may have with per_site_x=True (beyond them a one-site run interpolates: surf96_modsw.py)
+SITE_X_MAX_PERIODS = 60
 
 
 def window_site_map(nchains, nsites, ld):
@@ -39,9 +45,15 @@ class SiteTargets(object):
     per_site_rf=True: the receiver-function plugins of the sites may also differ in their ray parameter `p` and near-surface
     velocity `nsv` (a station's slowness depends on the events it recorded); every other receiver-function argument (gauss,
     nsamp, fsamp, tshift, wave type, nkeep) must still match.  Each model is then computed with its own site's p and nsv.
-    The default (False) rejects a differing p or nsv like any other mismatch."""
+    The default (False) rejects a differing p or nsv like any other mismatch.
 
-    def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False):
+    per_site_x=True: the dispersion targets of fundamental-mode phase velocity may also differ in their periods x and in the
+    number of them (1 to 60 per site; not with the Gauss law, whose R^-1 depends on the number).  Each model's curve is then
+    computed at its own site's periods and compared over its own site's samples; in the synthetics a site's velocities are
+    followed by zeros up to the largest count of any site.  Group-velocity and higher-mode targets and receiver functions
+    still share x bit for bit.  The default (False) keeps the check above."""
+
+    def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False):
         self._sites = [jt if isinstance(jt, JointTarget) else JointTarget(jt) for jt in jointtargets]
         if not self._sites:
             raise ValueError("SiteTargets needs at least one site")
@@ -50,6 +62,7 @@ class SiteTargets(object):
             raise ValueError("names must be %d distinct names, one per site" % len(self._sites))
         self._engine = engine
         self.per_site_rf = bool(per_site_rf)
+        self.per_site_x = bool(per_site_x)
         for jt in self._sites:          # every site on one engine
             if jt._engine is None:
                 jt._engine = engine
@@ -101,8 +114,12 @@ class SiteTargets(object):
                 if type(t) is not type(t0):
                     raise ValueError("%s is a %s, site 0's is a %s" % (what, type(t).__name__, type(t0).__name__))
                 x, x0 = np.asarray(t.obsdata.x, dtype=float), np.asarray(t0.obsdata.x, dtype=float)
-                if x.shape != x0.shape or _bits(x) != _bits(x0):
+                same_x = x.shape == x0.shape and _bits(x) == _bits(x0)
+                site_x = self.per_site_x and isinstance(t.moddata.plugin, SurfDisp) and isinstance(t0.moddata.plugin, SurfDisp)
+                if not same_x and not site_x:
                     raise ValueError("%s: x differs from site 0's (sites share x bit for bit)" % what)
+                if site_x:
+                    self._check_site_x(what, t, x, same_x)
                 if np.size(t.obsdata.y) != x.size:
                     raise ValueError("%s: y has %d values for %d samples" % (what, np.size(t.obsdata.y), x.size))
                 p, p0 = t.moddata.plugin, t0.moddata.plugin
@@ -127,6 +144,58 @@ class SiteTargets(object):
                     if (np.shape(v.corr_inv) != np.shape(v0.corr_inv) or _bits(v.corr_inv) != _bits(v0.corr_inv)
                             or _bits(v.logcorr_det) != _bits(v0.logcorr_det)):
                         raise ValueError("%s: Gauss law with another R^-1 / ln|R| than site 0's (sites share corr)" % what)
+
+    def _check_site_x(self, what, t, x, same_x):
+        """what the engine refuses of a dispersion target registered with periods per site (include/bh_engine_sites_x.h);
+        same_x: the site's x is site 0's"""
+        p = t.moddata.plugin
+        if not same_x and (p.veltype != 0 or p.modelparams["mode"] > 1):
+            raise ValueError("%s: x differs from site 0's on a group-velocity or higher-mode target (per_site_x serves "
+                             "fundamental-mode phase velocities)" % what)
+        if x.ndim != 1 or x.size < 1 or x.size > SITE_X_MAX_PERIODS:
+            raise ValueError("%s: %d periods; a site has 1 to %d with per_site_x" % (what, x.size, SITE_X_MAX_PERIODS))
+        if not np.all(np.isfinite(x) & (x > 0)):
+            raise ValueError("%s: a period that is not finite and positive" % what)
+        if t.law() == "gauss":
+            raise ValueError("%s: Gauss law on a dispersion target with periods per site (R^-1 depends on their number)" % what)
+
+    def site_x_arrays(self):
+        """(n[S, nt] int32, x[S, ldy], yobs[S, ldy], yerr[S, ldy] or None) for Engine.set_sites_x: the samples of every (site,
+        target) and every site's x, observed data and errors in ymod's column layout, where a target's columns are as many as
+        its largest count over the sites; beyond a site's own count x and yobs hold 0 and yerr 1 (unread)."""
+        S, nt = self.nsites, self.ntargets
+        n = np.array([[np.size(t.obsdata.x) for t in jt.targets] for jt in self._sites], dtype=np.int32).reshape(S, nt)
+        cap = n.max(axis=0)
+        off = np.concatenate([[0], np.cumsum(cap)]).astype(int)
+        scaled = any(LAWS[t.law()] == LAWS["nocorr_scalederr"] for t in self.targets)
+        x, yobs = np.zeros((S, off[-1])), np.zeros((S, off[-1]))
+        yerr = np.ones((S, off[-1])) if scaled else None
+        for s, jt in enumerate(self._sites):
+            for i, t in enumerate(jt.targets):
+                c = slice(off[i], off[i] + n[s, i])
+                x[s, c] = np.asarray(t.obsdata.x, dtype=float).ravel()
+                yobs[s, c] = np.asarray(t.obsdata.y, dtype=float).ravel()
+                if scaled and LAWS[t.law()] == LAWS["nocorr_scalederr"]:
+                    yerr[s, c] = np.asarray(t.obsdata.yerr, dtype=float).ravel()
+        return n, x, yobs, yerr
+
+    def _capacity_descs(self):
+        """site 0's descriptors; a fundamental-mode phase-velocity target's n is the largest count of any site and its x, yobs
+        (and yerr) placeholders of that length -- the site path reads the tables, never these.  Group-velocity and higher-mode
+        targets keep site 0's x, which every site shares: the engine checks the table against it, and a group velocity's
+        second roots are searched at the descriptor's periods."""
+        n = np.array([[np.size(t.obsdata.x) for t in jt.targets] for jt in self._sites])
+        descs = []
+        for i, t in enumerate(self.targets):
+            d = t.engine_desc()
+            if d["kind"] == _engine.TARGET_SWD and d["igr"] == 0 and d["mode"] <= 1:
+                cap = int(n[:, i].max())
+                d["n"] = cap
+                d["x"], d["yobs"] = np.ones(cap), np.zeros(cap)
+                if "yerr" in d:
+                    d["yerr"] = np.ones(cap)
+            descs.append(d)
+        return descs
 
     def site_arrays(self):
         """(yobs[S, ldy], yerr[S, ldy] or None): every site's observed data, target after target as in ymod"""
@@ -164,9 +233,13 @@ class SiteTargets(object):
         if self._registered != sig:
             self.check()
         if self._registered != sig or e._owner is not self:
-            e.set_targets([t.engine_desc() for t in self.targets])
-            yobs, yerr = self.site_arrays()
-            e.set_sites(yobs, yerr)
+            if self.per_site_x:
+                e.set_targets(self._capacity_descs())
+                e.set_sites_x(*self.site_x_arrays())
+            else:
+                e.set_targets([t.engine_desc() for t in self.targets])
+                yobs, yerr = self.site_arrays()
+                e.set_sites(yobs, yerr)
             if self.per_site_rf:
                 e.set_sites_rf(*self.site_rf_arrays())
             e._owner = self
