@@ -97,8 +97,7 @@ struct TargetHost {
     bh_target_desc d{};
     int off = 0; // column offset in a ymod row
     DevBuf x, yobs, yerr_scaled, rinv, quad;
-    DevBuf sums;       // receiver function, fused likelihood: [B][4] sums of the last call (RfKernelArgs::sums)
-    bool fused = false; // this call's likelihood of the target comes from `sums` (set per call by bh_evaluate_batch)
+    DevBuf sums;       // receiver function, fused likelihood (EvalPlan::rf_fused): [B][4] sums of the call (RfKernelArgs::sums)
     DevBuf x60, vel60; // > 60 periods: the 60-point grid the forward model runs on + its output
     int kfwd = 0;      // periods the forward model computes (n, or 60 when n > 60)
     double logdet_extra = 0.0;
@@ -114,8 +113,8 @@ struct bh_engine {
     hipStream_t aux2 = nullptr;            // second dispersion target of a lane-per-model call runs here, beside the first
     hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;
     bool overlap_rf = true;                // BH_NO_OVERLAP env turns it off (A/B testing)
-    int rf_lds_beside_swd = 40 * 1024;     // BH_RF_LDS_BESIDE env (bytes; experiment switch), see launch_rf
-    // co-resident receiver function (see bh_evaluate_batch): the dispersion kernel counts its started workgroups here
+    int rf_lds_beside_swd = 40 * 1024;     // BH_RF_LDS_BESIDE env (bytes; experiment switch), see rf_place
+    // co-resident receiver function (the start gate: plan_eval, gate_need): the dispersion kernel counts its started workgroups here
     unsigned *started = nullptr;           // device word (signal memory where available), cumulative over launches
     unsigned started_expected = 0;         // value after every launch enqueued so far has started
     int swd_prio_low = 1;                  // BH_SWD_PRIO_LOW env: dispersion wavefronts' low priority while RF wavefronts run beside them
@@ -124,10 +123,7 @@ struct bh_engine {
     int last_swd_kernel = -1;              // bh_engine_last_swd_kernel
     bh_swd_launch swd_launches[3 * BH_MAX_TARGETS]{}; // bh_engine_last_swd_launches: of the most recent call with dispersion targets
     int n_swd_launches = 0;
-    SwdLaunchInfo last_swd{};              // of the most recent group-kernel launch (workgroups == 0: none)
     int err_t_nt = -1, err_t_B = -1;       // layout for which err_t's untouched rows are known to be zero
-    int swd_prio_low_now = 0;              // per call: what the next dispersion launch gets
-    bool rf_gated_now = false;             // per call: the RF stream waits for the dispersion kernel's workgroups to be resident
     std::string err;
     // staging / workspace
     DevBuf nlay, h, vp, vs, rho, qp, qs, periods, vel, errb, rf, coef, ymod, noise, logL,
@@ -272,43 +268,27 @@ struct Staged {
     int typ_layers = 0; // typical layer count of the batch when the host can see it (0 = unknown)
 };
 
-// Copy the model arrays of a BH_HOST call into the engine's device buffers.
-int stage_models(bh_engine *e, int B, int Lmax, ptrdiff_t sl, ptrdiff_t sb, const int32_t *nlay,
-                 const double *h, const double *vp, const double *vs, const double *rho,
-                 const double *qp, const double *qs, Staged &s)
+// Copy the model arrays of a BH_HOST call into the engine's device buffers: m's host pointers become device pointers
+// (rho, qp and qs may be null and stay so).
+int stage_models(bh_engine *e, int B, int Lmax, ptrdiff_t sl, ptrdiff_t sb, Staged &m)
 {
-    const size_t nel = span_elems(B, Lmax, sl, sb), bytes = nel * sizeof(double);
-    int rc;
-    if ((rc = ensure(e, e->nlay, (size_t)B * sizeof(int32_t)))) return rc;
-    if ((rc = ensure(e, e->h, bytes))) return rc;
-    if ((rc = ensure(e, e->vp, bytes))) return rc;
-    if ((rc = ensure(e, e->vs, bytes))) return rc;
-    if ((rc = ensure(e, e->rho, bytes))) return rc;
-    HIPCHK(e, hipMemcpyAsync(e->nlay.p, nlay, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->h.p, h, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->vp.p, vp, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->vs.p, vs, bytes, hipMemcpyHostToDevice, e->stream));
-    if (rho) HIPCHK(e, hipMemcpyAsync(e->rho.p, rho, bytes, hipMemcpyHostToDevice, e->stream));
+    const size_t bytes = span_elems(B, Lmax, sl, sb) * sizeof(double);
     {   // mean layer count, rounded up: what the lanes-per-model choice should be sized for
         long sum = 0;
-        for (int b = 0; b < B; ++b) sum += nlay[b];
-        s.typ_layers = B > 0 ? (int)((sum + B - 1) / B) : 0;
+        for (int b = 0; b < B; ++b) sum += m.nlay[b];
+        m.typ_layers = B > 0 ? (int)((sum + B - 1) / B) : 0;
     }
-    s.nlay = (const int32_t *)e->nlay.p;
-    s.h = (const double *)e->h.p;
-    s.vp = (const double *)e->vp.p;
-    s.vs = (const double *)e->vs.p;
-    s.rho = rho ? (const double *)e->rho.p : nullptr;
-    s.qp = s.qs = nullptr;
-    if (qp) {
-        if ((rc = ensure(e, e->qp, bytes))) return rc;
-        HIPCHK(e, hipMemcpyAsync(e->qp.p, qp, bytes, hipMemcpyHostToDevice, e->stream));
-        s.qp = (const double *)e->qp.p;
-    }
-    if (qs) {
-        if ((rc = ensure(e, e->qs, bytes))) return rc;
-        HIPCHK(e, hipMemcpyAsync(e->qs.p, qs, bytes, hipMemcpyHostToDevice, e->stream));
-        s.qs = (const double *)e->qs.p;
+    int rc;
+    if ((rc = ensure(e, e->nlay, (size_t)B * sizeof(int32_t)))) return rc;
+    HIPCHK(e, hipMemcpyAsync(e->nlay.p, m.nlay, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    m.nlay = (const int32_t *)e->nlay.p;
+    const double **arr[6] = {&m.h, &m.vp, &m.vs, &m.rho, &m.qp, &m.qs};
+    DevBuf *buf[6] = {&e->h, &e->vp, &e->vs, &e->rho, &e->qp, &e->qs};
+    for (int k = 0; k < 6; ++k) {
+        if (!*arr[k]) continue;
+        if ((rc = ensure(e, *buf[k], bytes))) return rc;
+        HIPCHK(e, hipMemcpyAsync(buf[k]->p, *arr[k], bytes, hipMemcpyHostToDevice, e->stream));
+        *arr[k] = (const double *)buf[k]->p;
     }
     return BH_OK;
 }
@@ -601,6 +581,114 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
     return p;
 }
 
+// What a target does in a fused call: nothing (a BH_TARGET_USER target has no forward model), dispersion at its own periods,
+// dispersion on the 60-period grid followed by interpolation, or a receiver function.
+enum EvalRole { ROLE_NONE, ROLE_SWD, ROLE_SWD60, ROLE_RF };
+// The likelihood launcher of a fused call: bh_launch_like, bh_launch_like_sites, bh_launch_like_sites_x (a site's own sample counts)
+enum EvalLike { LIKE_PLAIN, LIKE_SITES, LIKE_SITES_X };
+
+// What one fused call (bh_evaluate_batch, bh_evaluate_sites) does: everything its steps would otherwise decide.
+struct EvalPlan {
+    int B, nt, ldy;
+    EvalRole role[BH_MAX_TARGETS];
+    bool rf_fused[BH_MAX_TARGETS]; // receiver function: the synthesis kernel writes the likelihood's sums, not the trace
+    int nswd;                   // dispersion jobs of the call
+    bool no_forward;            // a target has no forward model to run: the call is refused
+    bool fork;                  // the receiver functions run on the second stream, beside the dispersion launch
+    bool want_gate;             // ... which waits for that launch's started workgroups (where the launch has any: gate_need)
+    int prio_low;               // SwdMultiArgs::prio_low of the dispersion launch
+    bool x_table, rf_table;     // the site table's periods (bh_sites_set_x) / receiver-function parameters (bh_sites_set_rf) are in force
+    EvalLike like;
+    bool err_zero_always;       // bh_tuning.h err_memset: the failure flags are zeroed on every call
+};
+
+// The plan of one fused call, from the registered targets, the engine's settings, the experiment switches (bh_tuning.h) and the
+// site table's flags: no HIP call, no allocation, no write to the engine.  sites: bh_evaluate_sites; want_ymod: the caller asked
+// for the synthetics.
+EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
+{
+    const BhTuning &tun = bh_tuning();
+    EvalPlan p{};
+    p.B = B; p.nt = e->nt; p.ldy = e->ldy;
+    bool have_rf = false;
+    for (int t = 0; t < p.nt; ++t) {
+        const TargetHost &T = e->targets[(size_t)t];
+        const bh_target_desc &d = T.d;
+        if (d.kind == BH_TARGET_SWD) {
+            p.role[t] = T.kfwd == d.n ? ROLE_SWD : ROLE_SWD60; // > 60 periods: run on the 60-point grid, interpolate afterwards
+            ++p.nswd;
+        } else if (d.kind == BH_TARGET_RF) {
+            p.role[t] = ROLE_RF;
+            have_rf = true;
+            // Fused likelihood ("write nothing if the likelihood is fused"): the caller did not ask for the
+            // synthetics and the target's law needs only sums over the trace -- the synthesis kernel forms them from the samples
+            // in LDS (like_kernel's order: the same bits) and writes four numbers per model instead of the trace.
+            // (sites: the trace goes to the ymod workspace and the site-indexed likelihood kernel forms the sums)
+            p.rf_fused[t] = !want_ymod && !sites && tun.rf_no_fuse == 0 && (d.law == BH_LAW_NOCORR || d.law == BH_LAW_EXP) && tun.rf_threads != 128;
+        } else {
+            p.no_forward = true;
+        }
+    }
+    // The receiver-function kernels are independent of the dispersion kernel and write other columns
+    // of ymod: they run on a second stream so that their (throughput-bound) wavefronts fill the issue
+    // slots the (latency-bound) dispersion wavefronts leave idle.  fork -> [swd | rf] -> join -> like.
+    p.fork = have_rf && p.nswd > 0 && e->overlap_rf;
+    // Start gate.  The dispersion group kernel counts on ALL its wavefronts being co-resident (one round of wavefronts,
+    // two per SIMD); an RF workgroup that takes a wave slot first displaces a dispersion wavefront for a whole lifetime
+    // (3.6 -> 7 ms when the 17.7 KB workgroups of round 3 slipped into the LDS the dispersion wavefronts leave free), and
+    // even the small coefficient kernel, dispatched while the dispersion kernel's workgroups are being placed, stretched
+    // that kernel's span by 0.3 ms in round 2.  The kernel's workgroups therefore count themselves in `started` as they
+    // begin, and the RF stream waits for the count (hipStreamWaitValue32) before anything of the RF is dispatched:
+    // c3 4.15 -> 4.04 ms, the dispersion kernel's time inside c3 = its time in c2 (3.62 ms).
+    // (Round 6: the dispersion kernel of the default settings allocates 200-208 registers and the synthesis kernel 88, so an RF
+    // wavefront becomes resident beside the two dispersion wavefronts of a SIMD and takes the issue slots they leave idle; the
+    // 96-register "beside" build of rounds 3-5 -- docs/HISTORY.md -- is gone.)
+    p.want_gate = p.fork && e->started != nullptr;
+    // (RF wavefronts move in beside the last dispersion wavefronts of a SIMD as its short ones end: the dispersion
+    // wavefronts' unfavoured phase runs at priority 1 then, above the RF's 0)
+    p.prio_low = p.want_gate ? e->swd_prio_low : 0;
+    // (periods per site, bh_sites_set_x: every dispersion job reads its models' periods and counts from the table)
+    p.x_table = sites && e->site_x;
+    // (sites with their own p / nsv, bh_sites_set_rf: the coefficient kernels read them from the table, column t)
+    p.rf_table = sites && e->site_rf;
+    p.like = p.x_table ? LIKE_SITES_X : (sites ? LIKE_SITES : LIKE_PLAIN);
+    p.err_zero_always = tun.err_memset != 0;
+    return p;
+}
+
+// The started workgroups of dispersion launch s the gated RF stream waits for: all workgroups of the launch, or -- a launch of
+// more workgroups than the chip holds at once (2048 wavefronts) -- as many as can be resident together (the rest start as others
+// end: waiting for them would be waiting for the kernel)
+unsigned gate_need(const SwdLaunchInfo &s)
+{
+    const unsigned resident = 2048u / (unsigned)(s.lds > 0 && s.wpb > 0 ? s.wpb : 2);
+    return s.workgroups < resident ? s.workgroups : resident;
+}
+
+// Where the workgroups of a receiver-function launch go: RfKernelArgs::lds_min and coef_small.
+struct RfPlace {
+    int lds_min = 0, coef_small = 0;
+};
+
+// The placement of a receiver-function launch.  beside_swd: it runs on the second stream of a forked call; gated: behind the
+// start gate (the gate was wanted, the dispersion launch had workgroups and bh_tuning.h rf_keep_floor is 0).
+//   Beside a dispersion launch (fused call, second stream): the synthesis workgroups must not take wave slots before
+// the dispersion kernel's wavefronts are resident -- that kernel counts on all of them being co-resident (one round
+// of wavefronts; displaced ones wait for a whole lifetime: 3.6 -> 7 ms measured when the 17.7 KB workgroups of
+// round 3 slipped into the 18 KB of LDS the dispersion wavefronts leave free on a CU).  Asking for more LDS than
+// that remainder keeps them out of CUs whose dispersion wavefronts are still running, as in round 2 (40 KB).
+// (with the start gate of plan_eval in force the LDS floor is not needed: RF workgroups are dispatched
+// after every dispersion wavefront is resident and only take what finished wavefronts have freed)
+RfPlace rf_place(bool beside_swd, bool gated, const BhTuning &tun, int rf_lds_beside_swd)
+{
+    RfPlace w;
+    if (!beside_swd) return w;
+    // (bh_tuning.h rf_lds_gated: LDS floor of the synthesis workgroups of a GATED fused call -- fewer of them per CU at a time)
+    w.lds_min = !gated ? rf_lds_beside_swd : (tun.rf_lds_gated > 0 ? tun.rf_lds_gated : 0);
+    w.coef_small = (gated && tun.rf_coef_big == 0) ? 1 : 0;
+    return w;
+}
+
 // The group kernel's launch of a call planned by plan_swd (BH_KERNEL_GROUP)
 SwdGroupPlan plan_group(const bh_engine *e, const SwdPlan &p, int B, int Lmax, const SwdJob *jobs)
 {
@@ -629,6 +717,8 @@ struct SwdCall {
     unsigned long long *counter = nullptr;
     int32_t *gcounts = nullptr, *glists = nullptr; // the guard of the short refinement (guard_space)
     SwdSiteXArgs sx{};                   // p.sitex: the period table with the launch's targets (launch_swd_multi)
+    int prio_low = 0;                    // the main launch's SwdMultiArgs::prio_low (EvalPlan::prio_low)
+    SwdLaunchInfo info{};                // of the group or trial-per-lane kernel's main launch (workgroups == 0: none)
 };
 
 // The kernel arguments of job j as a target: its model arrays (the batch's, or the flattened copies with the density of its wave
@@ -957,7 +1047,7 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
         a.t[t].refseq = p.refseq[t] ? 1 : 0;
     }
     a.started = e->started;
-    a.prio_low = e->swd_prio_low_now;
+    a.prio_low = c.prio_low;
     a.adapt_ok = p.adapt_ok ? 1 : 0;
     if (p.sitex) { // the period table with this launch's targets
         c.sx = *c.jobs[p.job[0]].sx.tab;
@@ -995,20 +1085,20 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
     e->last_swd_kernel = p.kernel;
     if (lean) {
         SwdLaneBuild lb{};
-        if ((p.sitex ? bh_launch_swd_lean_x(a, c.sx, c.st, &e->last_swd, &lb) : bh_launch_swd_lean(a, c.st, &e->last_swd, &lb)) != 0)
+        if ((p.sitex ? bh_launch_swd_lean_x(a, c.sx, c.st, &c.info, &lb) : bh_launch_swd_lean(a, c.st, &c.info, &lb)) != 0)
             return fail(e, BH_EINVAL, "model too deep for LDS");
         note_launch(e, BH_KERNEL_LEAN, BH_SWD_MAIN, lb.key, false, p.ntargets == 2, false, false, lb.grid_x, 0);
     } else {
         if (!p.sitex) bh_launch_swd_group(a, c.g, c.st);
         else if (!bh_launch_swd_group_x(a, c.g, c.sx, c.st)) return fail(e, BH_EUNSUPPORTED, "no site-period build of this dispersion launch");
         note_group(e, BH_SWD_MAIN, c.g, c.pair_perm[0] != nullptr);
-        e->last_swd = c.g.info;
+        c.info = c.g.info;
     }
     // (the counter a second stream waits on moves only once the launch is known to have been accepted: a failed launch
     // never increments the device word, and every later wait for the advanced value would hang -- ADVICE r03)
     const hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail(e, BH_EHIP, "dispersion kernel launch", le);
-    if (e->started) e->started_expected += e->last_swd.workgroups;
+    if (e->started) e->started_expected += c.info.workgroups;
     return BH_OK;
 }
 
@@ -1060,12 +1150,15 @@ int launch_second_roots(const SwdCall &c)
 // All dispersion targets of one call: the plan, the flattened copies and the order it needs, then its launches -- the group or
 // trial-per-lane kernel (one launch for all targets) or one lane per model (a launch per target) -- the re-run of the models
 // the guard of the short refinement fired on, and the second roots of split group velocities.
+// prio_low: SwdMultiArgs::prio_low of the main launch.  main: null, or where the SwdLaunchInfo of the call's main launch goes
+// once the call has dispersion targets (workgroups == 0: not a launch of the group or trial-per-lane kernel).
 int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl,
-                    ptrdiff_t sb, int njobs, const SwdJob *jobs)
+                    ptrdiff_t sb, int njobs, const SwdJob *jobs, int prio_low, SwdLaunchInfo *main)
 {
     if (B == 0 || njobs == 0) return BH_OK;
     const SwdPlan p = plan_swd(e, B, Lmax, m.typ_layers > 0 ? m.typ_layers : e->hint_layers, njobs, jobs);
     SwdCall c{e, st, B, Lmax, m, sl, sb, jobs, p};
+    c.prio_low = prio_low;
     if (p.kernel == BH_KERNEL_GROUP) {
         c.g = plan_group(e, p, B, Lmax, jobs);
         if (!c.g.fits) return fail(e, BH_EINVAL, "model too deep for LDS");
@@ -1089,6 +1182,7 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
     if ((rc = swd_counter(e, st, &c.counter)) || (rc = order_models(c))) return rc;
     SwdMultiArgs a{};
     rc = p.kernel == BH_KERNEL_LANE ? launch_swd_lanes(c, a) : launch_swd_multi(c, a);
+    if (main) *main = c.info;
     // (guarded models of the short refinement: re-run, unless the group kernel restarts them in place)
     if (!rc && p.any_fast && !(p.kernel == BH_KERNEL_GROUP && c.g.restart)) rc = launch_swd_rerun(e, st, a, c.gcounts, c.glists, p.sitex ? &c.sx : nullptr);
     if (!rc && p.nsplit > 0) rc = launch_second_roots(c);
@@ -1096,40 +1190,38 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
     return rc;
 }
 
-int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl,
-              ptrdiff_t sb, double p, double gauss, int nsamp, double fsamp, double tshift,
-              double nsv, int waveno, int nkeep, double *rf, int ldr, bool beside_swd = false, const double *yobs = nullptr,
-              double *sums = nullptr, const RfSiteArgs *sites = nullptr)
+// What one receiver-function launch synthesises: the descriptor's numbers, the output rows, the inputs of the fused
+// likelihood (yobs and sums, or null: the trace is written) and the site table (null: p and nsv as given).
+struct RfJob {
+    double p, gauss;
+    int nsamp;
+    double fsamp, tshift, nsv;
+    int waveno, nkeep;
+    double *rf; int ldr;
+    const double *yobs; double *sums;
+    const RfSiteArgs *sites;
+};
+
+int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl, ptrdiff_t sb, const RfJob &j, const RfPlace &where)
 {
     if (B == 0) return BH_OK;
     int rc;
     if ((rc = ensure(e, e->coef, (size_t)B * bh_rf_coef_doubles(Lmax) * sizeof(double)))) return rc;
     RfKernelArgs a{};
-    a.B = B; a.Lmax = Lmax; a.nsamp = nsamp; a.nkeep = nkeep; a.waveno = waveno;
+    a.B = B; a.Lmax = Lmax; a.nsamp = j.nsamp; a.nkeep = j.nkeep; a.waveno = j.waveno;
     a.nlay = m.nlay; a.h = m.h; a.vp = m.vp; a.vs = m.vs; a.rho = m.rho; a.qp = m.qp; a.qs = m.qs;
     a.sl = sl; a.sb = sb;
-    a.p_s_per_deg = p; a.gauss = gauss; a.fsamp = fsamp; a.tshift = tshift; a.nsv = nsv;
-    a.coef = (double *)e->coef.p; a.rf = rf; a.ldr = ldr;
-    a.yobs = yobs; a.sums = sums; // (fused likelihood: the sums instead of the trace)
-    if (bh_rf_lds_bytes(nsamp) > BH_RF_MAX_LDS) { // a trace longer than a workgroup's LDS holds: the spectra go through a workspace
-        if ((rc = ensure(e, e->rfz, (size_t)B * (size_t)(nsamp / 2) * 2 * sizeof(double)))) return rc;
+    a.p_s_per_deg = j.p; a.gauss = j.gauss; a.fsamp = j.fsamp; a.tshift = j.tshift; a.nsv = j.nsv;
+    a.coef = (double *)e->coef.p; a.rf = j.rf; a.ldr = j.ldr;
+    a.yobs = j.yobs; a.sums = j.sums; // (fused likelihood: the sums instead of the trace)
+    if (bh_rf_lds_bytes(j.nsamp) > BH_RF_MAX_LDS) { // a trace longer than a workgroup's LDS holds: the spectra go through a workspace
+        if ((rc = ensure(e, e->rfz, (size_t)B * (size_t)(j.nsamp / 2) * 2 * sizeof(double)))) return rc;
         a.zwork = (double *)e->rfz.p;
     }
-    // Beside a dispersion launch (fused call, second stream): the synthesis workgroups must not take wave slots before
-    // the dispersion kernel's wavefronts are resident -- that kernel counts on all of them being co-resident (one round
-    // of wavefronts; displaced ones wait for a whole lifetime: 3.6 -> 7 ms measured when the 17.7 KB workgroups of
-    // round 3 slipped into the 18 KB of LDS the dispersion wavefronts leave free on a CU).  Asking for more LDS than
-    // that remainder keeps them out of CUs whose dispersion wavefronts are still running, as in round 2 (40 KB).
-    // (with the start gate of bh_evaluate_batch in force the LDS floor is not needed: RF workgroups are dispatched
-    // after every dispersion wavefront is resident and only take what finished wavefronts have freed)
-    a.lds_min = (beside_swd && !e->rf_gated_now) ? e->rf_lds_beside_swd : 0;
-    {   // (bh_tuning.h: LDS floor of the synthesis workgroups of a GATED fused call -- fewer of them per CU at a time)
-        const int gated_floor = bh_tuning().rf_lds_gated;
-        if (beside_swd && e->rf_gated_now && gated_floor > 0) a.lds_min = gated_floor;
-    }
-    a.coef_small = (beside_swd && e->rf_gated_now && bh_tuning().rf_coef_big == 0) ? 1 : 0;
+    a.lds_min = where.lds_min;
+    a.coef_small = where.coef_small;
     ev_begin(e, 1, st);
-    const int lrc = bh_launch_rf(a, st, sites);
+    const int lrc = bh_launch_rf(a, st, j.sites);
     ev_end(e, 1, st);
     if (lrc != 0) return fail(e, BH_EUNSUPPORTED, "receiver function: nsamp above 262144 is not supported");
     HIPCHK(e, hipGetLastError());
@@ -1138,9 +1230,10 @@ int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, pt
 
 // Fill the likelihood descriptor of target t; for the Gauss law run the MFMA contraction first.
 // site: null, or the site index of every model (device; bh_evaluate_sites): the Gauss contraction reads the observed data
-// of each model's site from the site table
+// of each model's site from the site table.  fused: the target's likelihood comes from the sums of this call's synthesis launch
+// (EvalPlan::rf_fused), not from ymod
 int prepare_like_target(bh_engine *e, hipStream_t st, int B, int ldy, const double *ymod_d, TargetHost &T,
-                        LikeTargetDev &L, const int32_t *site = nullptr)
+                        LikeTargetDev &L, bool fused, const int32_t *site)
 {
     L.law = T.d.law; L.n = T.d.n; L.off = T.off;
     L.yobs = (const double *)T.yobs.p;
@@ -1149,7 +1242,7 @@ int prepare_like_target(bh_engine *e, hipStream_t st, int B, int ldy, const doub
     L.logdet_extra = T.logdet_extra;
     L.quad = nullptr;
     L.nsplit = 0;
-    L.pre = T.fused ? (const double *)T.sums.p : nullptr;
+    L.pre = fused ? (const double *)T.sums.p : nullptr;
     if (T.d.law == BH_LAW_GAUSS && !e->no_mfma) {
         const int nsplit = bh_gauss_nsplit(B, T.d.n);
         int rc = ensure(e, T.quad, (size_t)B * nsplit * sizeof(double));
@@ -1498,27 +1591,22 @@ int bh_swd_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax, cons
     if (!nlay || !h || !vp || !vs || !rho || !periods || !vel || !err) return fail(e, BH_EINVAL, "null argument");
     if (B == 0) return BH_OK;
     HIPCHK(e, hipSetDevice(e->device));
-    if (memspace == BH_DEVICE) {
-        hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-        Staged m{nlay, h, vp, vs, rho, nullptr, nullptr};
-        call_begin(e, st);
-        SwdJob job{K, iwave, igr, K, periods, vel, err, mode, flsph};
-        rc = launch_swd_jobs(e, st, B, Lmax, m, sl, sb, 1, &job);
-        call_end(e, st);
-        return rc;
+    const bool host = (memspace != BH_DEVICE);
+    hipStream_t st = (!host && stream) ? (hipStream_t)stream : e->stream;
+    Staged m{nlay, h, vp, vs, rho, nullptr, nullptr};
+    SwdJob job{K, iwave, igr, K, periods, vel, err, mode, flsph};
+    if (host) {
+        if ((rc = stage_models(e, B, Lmax, sl, sb, m))) return rc;
+        if ((rc = ensure(e, e->periods, (size_t)BH_MAX_PERIODS * sizeof(double)))) return rc;
+        if ((rc = ensure(e, e->vel, (size_t)B * K * sizeof(double)))) return rc;
+        if ((rc = ensure(e, e->errb, (size_t)B * sizeof(int32_t)))) return rc;
+        HIPCHK(e, hipMemcpyAsync(e->periods.p, periods, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
+        job.periods_dev = (const double *)e->periods.p; job.vel = (double *)e->vel.p; job.err = (int32_t *)e->errb.p;
     }
-    hipStream_t st = e->stream;
-    Staged m{};
-    if ((rc = stage_models(e, B, Lmax, sl, sb, nlay, h, vp, vs, rho, nullptr, nullptr, m))) return rc;
-    if ((rc = ensure(e, e->periods, (size_t)BH_MAX_PERIODS * sizeof(double)))) return rc;
-    if ((rc = ensure(e, e->vel, (size_t)B * K * sizeof(double)))) return rc;
-    if ((rc = ensure(e, e->errb, (size_t)B * sizeof(int32_t)))) return rc;
-    HIPCHK(e, hipMemcpyAsync(e->periods.p, periods, (size_t)K * sizeof(double), hipMemcpyHostToDevice, st));
     call_begin(e, st);
-    SwdJob job{K, iwave, igr, K, (const double *)e->periods.p, (double *)e->vel.p, (int32_t *)e->errb.p, mode, flsph};
-    rc = launch_swd_jobs(e, st, B, Lmax, m, sl, sb, 1, &job);
+    rc = launch_swd_jobs(e, st, B, Lmax, m, sl, sb, 1, &job, 0, nullptr);
     call_end(e, st);
-    if (rc) return rc;
+    if (rc || !host) return rc;
     HIPCHK(e, hipMemcpyAsync(vel, e->vel.p, (size_t)B * K * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(err, e->errb.p, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
@@ -1537,23 +1625,19 @@ int bh_rf_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax, const
     if (!nlay || !h || !vp || !vs || !rho || !rf) return fail(e, BH_EINVAL, "null argument");
     if (B == 0 || nkeep == 0) return BH_OK;
     HIPCHK(e, hipSetDevice(e->device));
-    if (memspace == BH_DEVICE) {
-        hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-        Staged m{nlay, h, vp, vs, rho, qp, qs};
-        call_begin(e, st);
-        rc = launch_rf(e, st, B, Lmax, m, sl, sb, p, gauss, nsamp, fsamp, tshift, nsv, waveno, nkeep, rf, nkeep);
-        call_end(e, st);
-        return rc;
+    const bool host = (memspace != BH_DEVICE);
+    hipStream_t st = (!host && stream) ? (hipStream_t)stream : e->stream;
+    Staged m{nlay, h, vp, vs, rho, qp, qs};
+    RfJob job{p, gauss, nsamp, fsamp, tshift, nsv, waveno, nkeep, rf, nkeep, nullptr, nullptr, nullptr};
+    if (host) {
+        if ((rc = stage_models(e, B, Lmax, sl, sb, m))) return rc;
+        if ((rc = ensure(e, e->rf, (size_t)B * nkeep * sizeof(double)))) return rc;
+        job.rf = (double *)e->rf.p;
     }
-    hipStream_t st = e->stream;
-    Staged m{};
-    if ((rc = stage_models(e, B, Lmax, sl, sb, nlay, h, vp, vs, rho, qp, qs, m))) return rc;
-    if ((rc = ensure(e, e->rf, (size_t)B * nkeep * sizeof(double)))) return rc;
     call_begin(e, st);
-    rc = launch_rf(e, st, B, Lmax, m, sl, sb, p, gauss, nsamp, fsamp, tshift, nsv, waveno, nkeep,
-                   (double *)e->rf.p, nkeep);
+    rc = launch_rf(e, st, B, Lmax, m, sl, sb, job, RfPlace{}); // (not beside anything)
     call_end(e, st);
-    if (rc) return rc;
+    if (rc || !host) return rc;
     HIPCHK(e, hipMemcpyAsync(rf, e->rf.p, (size_t)B * nkeep * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
     return BH_OK;
@@ -1648,190 +1732,198 @@ int bh_targets_set(bh_engine *e, int nt, const bh_target_desc *td)
 
 namespace {
 
-// bh_evaluate_batch (site == nullptr: exactly its launches) and bh_evaluate_sites (site = the caller's site index per model)
-int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const int32_t *nlay, const double *h, const double *vp,
-             const double *vs, const double *rho, ptrdiff_t sl, ptrdiff_t sb, const int32_t *site, const double *noise,
-             double *logL, double *misfits, int32_t *err, double *ymod)
+// A BH_HOST call: la's noise, logL, misfits and err, the caller's host arrays, become the engine's staging buffers, with the
+// noise copied in
+int stage_like_io(bh_engine *e, hipStream_t st, LikeKernelArgs &la)
+{
+    const int B = la.B, nt = la.nt;
+    int rc;
+    if ((rc = ensure(e, e->noise, (size_t)B * 2 * nt * sizeof(double)))) return rc;
+    if ((rc = ensure(e, e->logL, (size_t)B * sizeof(double)))) return rc;
+    if ((rc = ensure(e, e->misfits, (size_t)B * (nt + 1) * sizeof(double)))) return rc;
+    if ((rc = ensure(e, e->errb, (size_t)B * sizeof(int32_t)))) return rc;
+    HIPCHK(e, hipMemcpyAsync(e->noise.p, la.noise, (size_t)B * 2 * nt * sizeof(double), hipMemcpyHostToDevice, st));
+    la.noise = (const double *)e->noise.p; la.logL = (double *)e->logL.p;
+    la.misfits = (double *)e->misfits.p; la.err = (int32_t *)e->errb.p;
+    return BH_OK;
+}
+
+// ... and its results go back to the caller's host arrays (enqueued: the caller synchronises)
+int return_like_io(bh_engine *e, hipStream_t st, const LikeKernelArgs &la, double *logL, double *misfits, int32_t *err)
+{
+    HIPCHK(e, hipMemcpyAsync(logL, la.logL, (size_t)la.B * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(misfits, la.misfits, (size_t)la.B * (la.nt + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(err, la.err, (size_t)la.B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    return BH_OK;
+}
+
+// One fused call as its steps see it: the stream, the model arrays and where the kernels read and write.  As the caller gave
+// them until stage_eval_inputs and size_eval_workspaces have run, device memory from then on.
+struct EvalCall {
+    hipStream_t st;
+    int Lmax;
+    Staged m;
+    ptrdiff_t sl, sb;
+    const int32_t *site; // of every model; null: bh_evaluate_batch
+    double *ymod;        // [B][ldy] synthetics; null: the caller asked for none (the engine's workspace takes them)
+    LikeKernelArgs la;   // the likelihood launch: B, nt, ldy, noise, logL, misfits, err; ymod and err_t once sized (t[]: run_like)
+};
+
+int eval_args_ok(bh_engine *e, const EvalPlan &p, bool host, const EvalCall &c)
+{
+    if (p.nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
+    if (p.no_forward) return fail(e, BH_EINVAL, "a BH_TARGET_USER target has no forward model: use bh_loglike_batch");
+    if (!c.m.nlay || !c.m.h || !c.m.vp || !c.m.vs || !c.la.noise || !c.la.logL || !c.la.misfits || !c.la.err) return fail(e, BH_EINVAL, "null argument");
+    if (c.site && host)
+        for (int b = 0; b < p.B; ++b)
+            if (c.site[b] < 0 || c.site[b] >= e->nsites) return fail(e, BH_EINVAL, "site index out of range (bh_sites_set)");
+    return BH_OK;
+}
+
+// A BH_HOST call's arrays go to the engine's staging buffers; the density where the caller gave none
+int stage_eval_inputs(bh_engine *e, bool host, int B, EvalCall &c)
 {
     int rc;
-    if ((rc = check_models(e, B, Lmax, sl, sb))) return rc;
-    if (e->nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
-    for (const auto &T : e->targets)
-        if (T.d.kind == BH_TARGET_USER) return fail(e, BH_EINVAL, "a BH_TARGET_USER target has no forward model: use bh_loglike_batch");
-    if (!nlay || !h || !vp || !vs || !noise || !logL || !misfits || !err) return fail(e, BH_EINVAL, "null argument");
-    if (site && memspace != BH_DEVICE)
-        for (int b = 0; b < B; ++b)
-            if (site[b] < 0 || site[b] >= e->nsites) return fail(e, BH_EINVAL, "site index out of range (bh_sites_set)");
-    if (B == 0) return BH_OK;
-    HIPCHK(e, hipSetDevice(e->device));
-    const int nt = e->nt, ldy = e->ldy;
-    const bool host = (memspace != BH_DEVICE);
-    hipStream_t st = (!host && stream) ? (hipStream_t)stream : e->stream;
-    Staged m{nlay, h, vp, vs, rho, nullptr, nullptr};
-    const double *noise_d = noise;
-    double *logL_d = logL, *misf_d = misfits, *ymod_d = ymod;
-    int32_t *err_d = err;
     if (host) {
-        if ((rc = stage_models(e, B, Lmax, sl, sb, nlay, h, vp, vs, rho, nullptr, nullptr, m))) return rc;
-        if ((rc = ensure(e, e->noise, (size_t)B * 2 * nt * sizeof(double)))) return rc;
-        if ((rc = ensure(e, e->logL, (size_t)B * sizeof(double)))) return rc;
-        if ((rc = ensure(e, e->misfits, (size_t)B * (nt + 1) * sizeof(double)))) return rc;
-        if ((rc = ensure(e, e->errb, (size_t)B * sizeof(int32_t)))) return rc;
-        HIPCHK(e, hipMemcpyAsync(e->noise.p, noise, (size_t)B * 2 * nt * sizeof(double), hipMemcpyHostToDevice, st));
-        noise_d = (const double *)e->noise.p;
-        if (site) {
+        if ((rc = stage_models(e, B, c.Lmax, c.sl, c.sb, c.m))) return rc;
+        if ((rc = stage_like_io(e, c.st, c.la))) return rc;
+        if (c.site) {
             if ((rc = ensure(e, e->site_idx, (size_t)B * sizeof(int32_t)))) return rc;
-            HIPCHK(e, hipMemcpyAsync(e->site_idx.p, site, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            site = (const int32_t *)e->site_idx.p;
+            HIPCHK(e, hipMemcpyAsync(e->site_idx.p, c.site, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
+            c.site = (const int32_t *)e->site_idx.p;
         }
-        logL_d = (double *)e->logL.p;
-        misf_d = (double *)e->misfits.p;
-        err_d = (int32_t *)e->errb.p;
-        ymod_d = nullptr;
+        c.ymod = nullptr;
     }
-    if (!ymod_d) {
-        if ((rc = ensure(e, e->ymod, (size_t)B * ldy * sizeof(double)))) return rc;
-        ymod_d = (double *)e->ymod.p;
-    }
-    {
-        const size_t cap0 = e->err_t.cap;
-        if ((rc = ensure(e, e->err_t, (size_t)nt * B * sizeof(int32_t)))) return rc;
-        if (e->err_t.cap != cap0) e->err_t_nt = e->err_t_B = -1; // a new buffer: not zeroed yet
-    }
-    if (!m.rho) { // rho = 0.32 vp + 0.77 (Targets.py:319)
-        const size_t nel = span_elems(B, Lmax, sl, sb);
+    if (!c.m.rho) { // rho = 0.32 vp + 0.77 (Targets.py:319)
+        const size_t nel = span_elems(B, c.Lmax, c.sl, c.sb);
         if ((rc = ensure(e, e->rho, nel * sizeof(double)))) return rc;
-        hipLaunchKernelGGL(rho_from_vp_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, st, nel, m.vp, (double *)e->rho.p);
-        m.rho = (const double *)e->rho.p;
+        hipLaunchKernelGGL(rho_from_vp_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, c.st, nel, c.m.vp, (double *)e->rho.p);
+        c.m.rho = (const double *)e->rho.p;
     }
-    call_begin(e, st);
+    return BH_OK;
+}
+
+// The workspaces whose size follows from the plan: the synthetics, the failure flags, the 60-period grids' velocities and the
+// fused likelihoods' sums
+int size_eval_workspaces(bh_engine *e, const EvalPlan &p, EvalCall &c)
+{
+    int rc;
+    if (!c.ymod) {
+        if ((rc = ensure(e, e->ymod, (size_t)p.B * p.ldy * sizeof(double)))) return rc;
+        c.ymod = (double *)e->ymod.p;
+    }
+    const size_t cap0 = e->err_t.cap;
+    if ((rc = ensure(e, e->err_t, (size_t)p.nt * p.B * sizeof(int32_t)))) return rc;
+    if (e->err_t.cap != cap0) e->err_t_nt = e->err_t_B = -1; // a new buffer: not zeroed yet
+    c.la.ymod = c.ymod; c.la.err_t = (const int32_t *)e->err_t.p;
+    for (int t = 0; t < p.nt; ++t) {
+        TargetHost &T = e->targets[(size_t)t];
+        if (p.role[t] == ROLE_SWD60 && (rc = ensure(e, T.vel60, (size_t)p.B * T.kfwd * sizeof(double)))) return rc;
+        if (p.rf_fused[t] && (rc = ensure(e, T.sums, (size_t)p.B * 4 * sizeof(double)))) return rc;
+    }
+    return BH_OK;
+}
+
+// The forward models of the plan: fork -> [dispersion | gate, receiver functions] -> join
+int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
+{
+    const int B = p.B, nt = p.nt, ldy = p.ldy;
+    hipStream_t st = c.st, rst = p.fork ? e->aux : st;
+    int rc;
     // per-target failure flags [nt][B]: the dispersion kernels write every entry of their target's row on every call,
     // nothing writes the rows of the other targets -- they are zeroed once per (nt, B) layout, not once per call
-    const bool always_zero = bh_tuning().err_memset != 0;
-    if (always_zero || e->err_t_nt != nt || e->err_t_B != B) {
+    if (p.err_zero_always || e->err_t_nt != nt || e->err_t_B != B) {
         HIPCHK(e, hipMemsetAsync(e->err_t.p, 0, (size_t)nt * B * sizeof(int32_t), st));
         e->err_t_nt = nt;
         e->err_t_B = B;
     }
-    LikeKernelArgs la{};
-    la.B = B; la.nt = nt; la.ldy = ldy; la.ymod = ymod_d; la.err_t = (const int32_t *)e->err_t.p;
-    la.noise = noise_d; la.logL = logL_d; la.misfits = misf_d; la.err = err_d;
     SwdJob jobs[BH_MAX_TARGETS];
     int njobs = 0;
-    // (periods per site, bh_sites_set_x: every dispersion job reads its models' periods and counts from the table)
-    const bool x_table = site && e->site_x;
-    const SwdSiteXArgs xtab{site, e->nsites, nt, ldy, (const int32_t *)e->site_xn.p, (const double *)e->site_xper.p, {}, {}};
+    const SwdSiteXArgs xtab{c.site, e->nsites, nt, ldy, (const int32_t *)e->site_xn.p, (const double *)e->site_xper.p, {}, {}};
     for (int t = 0; t < nt; ++t) {
-        TargetHost &T = e->targets[(size_t)t];
+        const TargetHost &T = e->targets[(size_t)t];
         const bh_target_desc &d = T.d;
-        if (d.kind == BH_TARGET_SWD) {
-            int32_t *errp = (int32_t *)e->err_t.p + (size_t)t * B;
-            if (T.kfwd == d.n) {
-                jobs[njobs++] = SwdJob{d.n, d.iwave, d.igr, ldy, (const double *)T.x.p, ymod_d + T.off, errp, d.mode, d.flsph};
-                if (x_table) jobs[njobs - 1].sx = SwdSiteJob{&xtab, t, T.off};
-            } else { // > 60 periods: run on the 60-point grid, interpolate afterwards
-                if ((rc = ensure(e, T.vel60, (size_t)B * T.kfwd * sizeof(double)))) return rc;
-                jobs[njobs++] = SwdJob{T.kfwd, d.iwave, d.igr, T.kfwd, (const double *)T.x60.p, (double *)T.vel60.p, errp, d.mode, d.flsph};
-            }
+        int32_t *errp = (int32_t *)e->err_t.p + (size_t)t * B;
+        if (p.role[t] == ROLE_SWD) {
+            jobs[njobs++] = SwdJob{d.n, d.iwave, d.igr, ldy, (const double *)T.x.p, c.ymod + T.off, errp, d.mode, d.flsph};
+            if (p.x_table) jobs[njobs - 1].sx = SwdSiteJob{&xtab, t, T.off};
+        } else if (p.role[t] == ROLE_SWD60) {
+            jobs[njobs++] = SwdJob{T.kfwd, d.iwave, d.igr, T.kfwd, (const double *)T.x60.p, (double *)T.vel60.p, errp, d.mode, d.flsph};
         }
     }
-    // The receiver-function kernels are independent of the dispersion kernel and write other columns
-    // of ymod: they run on a second stream so that their (throughput-bound) wavefronts fill the issue
-    // slots the (latency-bound) dispersion wavefronts leave idle.  fork -> [swd | rf] -> join -> like.
-    bool have_rf = false;
-    for (int t = 0; t < nt; ++t) have_rf = have_rf || e->targets[(size_t)t].d.kind == BH_TARGET_RF;
-    const bool fork = have_rf && njobs > 0 && e->overlap_rf;
-    hipStream_t rst = fork ? e->aux : st;
-    if (fork) {
-        HIPCHK(e, hipEventRecord(e->ev_fork, st));
-        HIPCHK(e, hipStreamWaitEvent(e->aux, e->ev_fork, 0));
-    }
-    // Start gate.  The dispersion group kernel counts on ALL its wavefronts being co-resident (one round of wavefronts,
-    // two per SIMD); an RF workgroup that takes a wave slot first displaces a dispersion wavefront for a whole lifetime
-    // (3.6 -> 7 ms when the 17.7 KB workgroups of round 3 slipped into the LDS the dispersion wavefronts leave free), and
-    // even the small coefficient kernel, dispatched while the dispersion kernel's workgroups are being placed, stretched
-    // that kernel's span by 0.3 ms in round 2.  The kernel's workgroups therefore count themselves in `started` as they
-    // begin, and the RF stream waits for the count (hipStreamWaitValue32) before anything of the RF is dispatched:
-    // c3 4.15 -> 4.04 ms, the dispersion kernel's time inside c3 = its time in c2 (3.62 ms).
-    // (Round 6: the dispersion kernel of the default settings allocates 200-208 registers and the synthesis kernel 88, so an RF
-    // wavefront becomes resident beside the two dispersion wavefronts of a SIMD and takes the issue slots they leave idle; the
-    // 96-register "beside" build of rounds 3-5 -- docs/HISTORY.md -- is gone.)
-    const bool want_gate = fork && e->started != nullptr;
+    if (p.fork && (rc = wait_for(e, e->ev_fork, st, e->aux))) return rc;
     if (e->started != nullptr && e->started_expected > 0x70000000u) { // (the counter is cumulative: rewind it long before it wraps)
         HIPCHK(e, hipStreamSynchronize(st));
         HIPCHK(e, hipStreamSynchronize(e->aux));
         HIPCHK(e, hipMemset(e->started, 0, sizeof(unsigned)));
         e->started_expected = 0;
     }
-    // (RF wavefronts move in beside the last dispersion wavefronts of a SIMD as its short ones end: the dispersion
-    // wavefronts' unfavoured phase runs at priority 1 then, above the RF's 0)
-    e->swd_prio_low_now = want_gate ? e->swd_prio_low : 0;
-    e->last_swd = SwdLaunchInfo{};
-    rc = launch_swd_jobs(e, st, B, Lmax, m, sl, sb, njobs, jobs);
-    e->swd_prio_low_now = 0;
-    if (rc) return rc;
-    e->rf_gated_now = false;
-    if (want_gate && e->last_swd.workgroups > 0) {
-        e->rf_gated_now = bh_tuning().rf_keep_floor == 0;
-        // all workgroups of the launch, or -- a launch of more workgroups than the chip holds at once (2048 wavefronts) --
-        // as many as can be resident together (the rest start as others end: waiting for them would be waiting for the kernel)
-        const unsigned resident = 2048u / (unsigned)(e->last_swd.lds > 0 && e->last_swd.wpb > 0 ? e->last_swd.wpb : 2);
-        const unsigned need = e->last_swd.workgroups < resident ? e->last_swd.workgroups : resident;
-        HIPCHK(e, hipStreamWaitValue32(e->aux, e->started, e->started_expected - e->last_swd.workgroups + need, hipStreamWaitValueGte,
-                                       0xffffffffu));
-    }
+    SwdLaunchInfo swd{};
+    if ((rc = launch_swd_jobs(e, st, B, c.Lmax, c.m, c.sl, c.sb, njobs, jobs, p.prio_low, &swd))) return rc;
+    const bool gate = p.want_gate && swd.workgroups > 0;
+    if (gate)
+        HIPCHK(e, hipStreamWaitValue32(e->aux, e->started, e->started_expected - swd.workgroups + gate_need(swd), hipStreamWaitValueGte, 0xffffffffu));
+    const RfPlace where = rf_place(p.fork, gate && bh_tuning().rf_keep_floor == 0, bh_tuning(), e->rf_lds_beside_swd);
     for (int t = 0; t < nt; ++t) {
         TargetHost &T = e->targets[(size_t)t];
         const bh_target_desc &d = T.d;
-        if (d.kind == BH_TARGET_SWD && T.kfwd != d.n)
+        if (p.role[t] == ROLE_SWD60)
             bh_launch_interp(B, T.kfwd, (const double *)T.x60.p, (const double *)T.vel60.p, T.kfwd, d.n,
-                             (const double *)T.x.p, ymod_d + T.off, ldy, st);
-        T.fused = false;
-        if (d.kind != BH_TARGET_RF) continue;
-        // Fused likelihood ("write nothing if the likelihood is fused"): the caller did not ask for the
-        // synthetics and the target's law needs only sums over the trace -- the synthesis kernel forms them from the samples
-        // in LDS (like_kernel's order: the same bits) and writes four numbers per model instead of the trace.
-        // (sites: the trace goes to the ymod workspace and the site-indexed likelihood kernel forms the sums)
-        T.fused = !ymod && !site && bh_tuning().rf_no_fuse == 0 && (d.law == BH_LAW_NOCORR || d.law == BH_LAW_EXP) && bh_tuning().rf_threads != 128;
-        if (T.fused && (rc = ensure(e, T.sums, (size_t)B * 4 * sizeof(double)))) return rc;
-        // (sites with their own p / nsv, bh_sites_set_rf: the coefficient kernels read them from the table, column t)
-        const bool rf_table = site && e->site_rf;
+                             (const double *)T.x.p, c.ymod + T.off, ldy, st);
+        if (p.role[t] != ROLE_RF) continue;
         RfSiteArgs rs{};
-        if (rf_table) rs = RfSiteArgs{site, e->nsites, nt, (const double *)e->site_p.p + t, (const double *)e->site_nsv.p + t};
-        rc = launch_rf(e, rst, B, Lmax, m, sl, sb, d.p_s_per_deg, d.gauss, d.nsamp, d.fsamp, d.tshift,
-                       d.nsv, d.waveno, d.n, ymod_d + T.off, ldy, fork, T.fused ? (const double *)T.yobs.p : nullptr,
-                       T.fused ? (double *)T.sums.p : nullptr, rf_table ? &rs : nullptr);
-        if (rc) return rc;
+        if (p.rf_table) rs = RfSiteArgs{c.site, e->nsites, nt, (const double *)e->site_p.p + t, (const double *)e->site_nsv.p + t};
+        const RfJob job{d.p_s_per_deg, d.gauss, d.nsamp, d.fsamp, d.tshift, d.nsv, d.waveno, d.n, c.ymod + T.off, ldy,
+                        p.rf_fused[t] ? (const double *)T.yobs.p : nullptr, p.rf_fused[t] ? (double *)T.sums.p : nullptr, p.rf_table ? &rs : nullptr};
+        if ((rc = launch_rf(e, rst, B, c.Lmax, c.m, c.sl, c.sb, job, where))) return rc;
     }
-    if (fork) {
-        HIPCHK(e, hipEventRecord(e->ev_join, e->aux));
-        HIPCHK(e, hipStreamWaitEvent(st, e->ev_join, 0));
-    }
-    for (int t = 0; t < nt; ++t)
-        if ((rc = prepare_like_target(e, st, B, ldy, ymod_d, e->targets[(size_t)t], la.t[t], site))) return rc;
+    return p.fork ? wait_for(e, e->ev_join, e->aux, st) : BH_OK;
+}
+
+// The likelihood of every model from the synthetics (or the sums of the targets in `fused`) and the failure flags, by launcher
+// `like`.  site: of every model, or null (LIKE_PLAIN)
+int run_like(bh_engine *e, hipStream_t st, LikeKernelArgs la, const bool *fused, EvalLike like, const int32_t *site)
+{
+    int rc;
+    for (int t = 0; t < la.nt; ++t)
+        if ((rc = prepare_like_target(e, st, la.B, la.ldy, la.ymod, e->targets[(size_t)t], la.t[t], fused[t], site))) return rc;
+    LikeSiteXArgs lx{};
+    lx.site = site; lx.nsites = e->nsites; lx.yobs = (const double *)e->site_yobs.p; lx.yerr_scaled = (const double *)e->site_yerr.p;
+    lx.logdet_extra = (const double *)e->site_logdet.p; lx.n = (const int32_t *)e->site_xn.p;
     ev_begin(e, 2, st);
-    if (x_table) { // (a site's own sample counts)
-        LikeSiteXArgs lx{};
-        lx.site = site; lx.nsites = e->nsites; lx.yobs = (const double *)e->site_yobs.p; lx.yerr_scaled = (const double *)e->site_yerr.p;
-        lx.logdet_extra = (const double *)e->site_logdet.p; lx.n = (const int32_t *)e->site_xn.p;
-        bh_launch_like_sites_x(la, lx, st);
-    } else if (site) {
-        const LikeSiteArgs ls{site, e->nsites, (const double *)e->site_yobs.p, (const double *)e->site_yerr.p,
-                              (const double *)e->site_logdet.p};
-        bh_launch_like_sites(la, ls, st);
-    } else {
-        bh_launch_like(la, st);
-    }
+    if (like == LIKE_SITES_X) bh_launch_like_sites_x(la, lx, st); // (a site's own sample counts)
+    else if (like == LIKE_SITES) bh_launch_like_sites(la, lx, st);
+    else bh_launch_like(la, st);
     ev_end(e, 2, st);
-    call_end(e, st);
+    return BH_OK;
+}
+
+// bh_evaluate_batch (site == nullptr: exactly its launches) and bh_evaluate_sites (site = the caller's site index per model):
+// validate, stage the inputs, size the workspaces, run the plan's forward models and likelihood, copy the results back.
+// (The plan is pure and comes first: the validation refuses a call whose plan has a target without forward model.)
+int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const int32_t *nlay, const double *h, const double *vp,
+             const double *vs, const double *rho, ptrdiff_t sl, ptrdiff_t sb, const int32_t *site, const double *noise,
+             double *logL, double *misfits, int32_t *err, double *ymod)
+{
+    int rc;
+    if ((rc = check_models(e, B, Lmax, sl, sb))) return rc;
+    const bool host = (memspace != BH_DEVICE);
+    const EvalPlan p = plan_eval(e, B, site != nullptr, ymod != nullptr);
+    LikeKernelArgs la{};
+    la.B = B; la.nt = p.nt; la.ldy = p.ldy; la.noise = noise; la.logL = logL; la.misfits = misfits; la.err = err;
+    EvalCall c{(!host && stream) ? (hipStream_t)stream : e->stream, Lmax, Staged{nlay, h, vp, vs, rho, nullptr, nullptr}, sl, sb, site, ymod, la};
+    if ((rc = eval_args_ok(e, p, host, c))) return rc;
+    if (B == 0) return BH_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    if ((rc = stage_eval_inputs(e, host, B, c)) || (rc = size_eval_workspaces(e, p, c))) return rc;
+    call_begin(e, c.st);
+    if ((rc = run_forward(e, p, c)) || (rc = run_like(e, c.st, c.la, p.rf_fused, p.like, c.site))) return rc;
+    call_end(e, c.st);
     HIPCHK(e, hipGetLastError());
-    if (host) {
-        HIPCHK(e, hipMemcpyAsync(logL, logL_d, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(misfits, misf_d, (size_t)B * (nt + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(err, err_d, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (ymod) HIPCHK(e, hipMemcpyAsync(ymod, ymod_d, (size_t)B * ldy * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipStreamSynchronize(st));
-    }
+    if (!host) return BH_OK;
+    if ((rc = return_like_io(e, c.st, c.la, logL, misfits, err))) return rc;
+    if (ymod) HIPCHK(e, hipMemcpyAsync(ymod, c.ymod, (size_t)B * p.ldy * sizeof(double), hipMemcpyDeviceToHost, c.st));
+    HIPCHK(e, hipStreamSynchronize(c.st));
     return BH_OK;
 }
 
@@ -2009,15 +2101,10 @@ int bh_loglike_batch(bh_engine *e, int memspace, void *stream, int B, const doub
     la.err_t = failflags;
     if (host) {
         if ((rc = ensure(e, e->ymod, (size_t)B * ldy * sizeof(double)))) return rc;
-        if ((rc = ensure(e, e->noise, (size_t)B * 2 * nt * sizeof(double)))) return rc;
-        if ((rc = ensure(e, e->logL, (size_t)B * sizeof(double)))) return rc;
-        if ((rc = ensure(e, e->misfits, (size_t)B * (nt + 1) * sizeof(double)))) return rc;
-        if ((rc = ensure(e, e->errb, (size_t)B * sizeof(int32_t)))) return rc;
         HIPCHK(e, hipMemcpyAsync(e->ymod.p, ymod, (size_t)B * ldy * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPCHK(e, hipMemcpyAsync(e->noise.p, noise, (size_t)B * 2 * nt * sizeof(double), hipMemcpyHostToDevice, st));
+        if ((rc = stage_like_io(e, st, la))) return rc;
         if (failflags) HIPCHK(e, hipMemcpyAsync(e->err_t.p, failflags, (size_t)nt * B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        la.ymod = (const double *)e->ymod.p; la.noise = (const double *)e->noise.p;
-        la.logL = (double *)e->logL.p; la.misfits = (double *)e->misfits.p; la.err = (int32_t *)e->errb.p;
+        la.ymod = (const double *)e->ymod.p;
         la.err_t = failflags ? (const int32_t *)e->err_t.p : nullptr;
     }
     if (!la.err_t) {
@@ -2025,21 +2112,13 @@ int bh_loglike_batch(bh_engine *e, int memspace, void *stream, int B, const doub
         la.err_t = (const int32_t *)e->err_t.p;
     }
     call_begin(e, st);
-    for (int t = 0; t < nt; ++t) {
-        e->targets[(size_t)t].fused = false; // (the caller's synthetics, not sums of an earlier fused call)
-        if ((rc = prepare_like_target(e, st, B, ldy, la.ymod, e->targets[(size_t)t], la.t[t]))) return rc;
-    }
-    ev_begin(e, 2, st);
-    bh_launch_like(la, st);
-    ev_end(e, 2, st);
+    const bool unfused[BH_MAX_TARGETS] = {}; // (the caller's synthetics)
+    if ((rc = run_like(e, st, la, unfused, LIKE_PLAIN, nullptr))) return rc;
     call_end(e, st);
     HIPCHK(e, hipGetLastError());
-    if (host) {
-        HIPCHK(e, hipMemcpyAsync(logL, la.logL, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(misfits, la.misfits, (size_t)B * (nt + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipMemcpyAsync(err, la.err, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(e, hipStreamSynchronize(st));
-    }
+    if (!host) return BH_OK;
+    if ((rc = return_like_io(e, st, la, logL, misfits, err))) return rc;
+    HIPCHK(e, hipStreamSynchronize(st));
     return BH_OK;
 }
 
