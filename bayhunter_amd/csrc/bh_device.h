@@ -178,6 +178,11 @@ __device__ __forceinline__ int bh_site_periods(const SwdSiteXArgs &X, int ty, in
     per = n < 0 ? X.x : X.x + (size_t)X.site[ib] * X.ldx + X.off[ty];
     return n;
 }
+// The second roots of a split group velocity (SwdKernelArgs::second) at every model's own periods (bh_sites_set_x_all,
+// include/bh_engine_sites_x_all.h): the site-period build of swd_kernel (swd_kernel_x.hip).  a as for bh_launch_swd, a.K the
+// CAPACITY of the target's columns (a.B = a.Bm x a.K entries), a.periods not read; ty: the target of x (col / off) the launch is
+// for.  An entry whose period index is at or beyond its site's count, or whose site is out of range, is idle and writes nothing.
+void bh_launch_swd_second_x(const SwdKernelArgs &a, int iwave, const SwdSiteXArgs &x, int ty, hipStream_t stream, SwdLaneBuild *build = nullptr);
 int bh_swd_pick_group(int B, int ntargets, int Lmax);
 double bh_swd_plan(int B, int Lmax, int ntargets, const int *iwave, int Gforce, int *G, int *look);
 size_t bh_swd_group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode, bool sitex = false);

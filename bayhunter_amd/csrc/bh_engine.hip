@@ -8,6 +8,7 @@
 #include "../../include/bh_engine_sites.h"
 #include "../../include/bh_engine_sites_rf.h"
 #include "../../include/bh_engine_sites_x.h"
+#include "../../include/bh_engine_sites_x_all.h"
 #include "bh_device.h"
 
 #include <algorithm>
@@ -142,6 +143,7 @@ struct bh_engine {
     DevBuf site_p, site_nsv;                  // [nsites][nt]: p (s/deg) and nsv of every site, read in the RF columns only
     // dispersion periods per site (bh_sites_set_x, include/bh_engine_sites_x.h): registered together with the site table
     bool site_x = false;
+    bool site_x_all = false;                  // ... registered by bh_sites_set_x_all: group velocities' second roots at a site's own periods
     DevBuf site_xn, site_xper;                // [nsites][nt] sample counts (int32), [nsites][ldy] periods in ymod's column layout
     // instrumentation
     bool timing = false, counting = false;
@@ -227,7 +229,7 @@ void release_sites(bh_engine *e)
     for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx, &e->site_p, &e->site_nsv, &e->site_xn, &e->site_xper}) release(*b);
     e->nsites = 0;
     e->site_rf = false;
-    e->site_x = false;
+    e->site_x = e->site_x_all = false;
 }
 
 // Targets.py:124-128, the nocorr_scalederr law: out = yerr / min(yerr), returns ln prod(out) (bh_targets_set, bh_sites_set)
@@ -437,8 +439,9 @@ struct SwdPlan {
 // and group kernels keep a row of kmax periods for EACH model of a wavefront, so LDS is sized for "periods per model" (p.sitex).
 // Where the trial-per-lane kernel then asks for more than a workgroup's LDS -- few trials per round are many models per
 // wavefront: 4 trials = 16 models x 60 periods x 8 B beside 16 models of 16 layers are 86 KB -- the call falls back to the group
-// kernel, as it does for deep arrays.  The one-lane-per-evaluation kernel (swd_kernel) has no site-period build: such calls take at least two
-// lanes per model (the group kernel), as deep arrays already do.
+// kernel, as it does for deep arrays.  The one-lane-per-evaluation kernel (swd_kernel) has no site-period build of a main launch: such
+// calls take at least two lanes per model (the group kernel), as deep arrays already do.  (Its launch of second roots has one:
+// launch_second_roots, for the tables of bh_sites_set_x_all.)
 SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, const SwdJob *jobs)
 {
     const BhTuning &tun = bh_tuning();
@@ -1104,10 +1107,14 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
 
 // The second roots of the group-velocity targets split in two launches (plan_swd): B x K independent searches per target,
 // after the call's other launches.  Each search reads the first root its chain kept and puts the group velocity in its place.
+// Periods per site on such a target (bh_sites_set_x_all): K is the capacity of the target's columns -- the host does not know the
+// sites of a device-resident call, so lanes and work space are sized for B x capacity entries -- and the launch is the
+// site-period build's (bh_launch_swd_second_x), with the main launch's period table: an entry beyond its site's count is idle.
 int launch_second_roots(const SwdCall &c)
 {
     bh_engine *e = c.e;
     const int B = c.B;
+    const bool sitex = c.p.sitex && e->site_x_all;
     int J2 = 16; // trial lanes per search while all searches of the call still fit the chip at once (2048 wavefronts)
     {
         long searches = 0;
@@ -1138,7 +1145,8 @@ int launch_second_roots(const SwdCall &c)
         a.fair = waves <= 1024 ? -1 : (waves <= 2048 ? 18 : 12);
         a.nev_high = (double *)e->nevhi2.p + off[n];
         SwdLaneBuild lb{};
-        bh_launch_swd(a, tg.iwave, (fork && (n & 1)) ? e->aux2 : c.st, &lb);
+        if (sitex) bh_launch_swd_second_x(a, tg.iwave, c.sx, t, (fork && (n & 1)) ? e->aux2 : c.st, &lb);
+        else bh_launch_swd(a, tg.iwave, (fork && (n & 1)) ? e->aux2 : c.st, &lb);
         note_lane(e, BH_SWD_SECOND, lb);
         ++n;
     }
@@ -1986,11 +1994,14 @@ int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yer
     return sites_register(e, nsites, nullptr, yobs, yerr);
 }
 
-int bh_sites_set_x(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+// bh_sites_set_x and bh_sites_set_x_all (who: the entry point's name, for the messages).  all: per-site periods and counts on
+// group-velocity and higher-mode targets are accepted -- the one check bh_sites_set_x_all skips.
+static int sites_register_x(bh_engine *e, const char *who, bool all, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
     if (!e) return BH_EINVAL;
+    const std::string w(who);
     if (e->nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
-    if (nsites < 1 || !n || !x || !yobs) return fail(e, BH_EINVAL, "bh_sites_set_x needs nsites >= 1, n, x and yobs");
+    if (nsites < 1 || !n || !x || !yobs) return fail(e, BH_EINVAL, (w + " needs nsites >= 1, n, x and yobs").c_str());
     const int nt = e->nt, ldy = e->ldy;
     bool scaled = false;
     for (const auto &T : e->targets) scaled = scaled || T.d.law == BH_LAW_NOCORR_SCALED;
@@ -2001,26 +2012,26 @@ int bh_sites_set_x(bh_engine *e, int nsites, const int32_t *n, const double *x, 
         const bh_target_desc &d = T.d;
         if (d.kind != BH_TARGET_SWD) { // (a receiver function's x is its descriptor's time axis: shared)
             for (size_t s = 0; s < S; ++s)
-                if (n[s * nt + t] != d.n) return fail(e, BH_EINVAL, "bh_sites_set_x: the sample count of a target that is no dispersion curve differs from its descriptor's");
+                if (n[s * nt + t] != d.n) return fail(e, BH_EINVAL, (w + ": the sample count of a target that is no dispersion curve differs from its descriptor's").c_str());
             continue;
         }
-        if (d.law == BH_LAW_GAUSS) return fail(e, BH_EINVAL, "bh_sites_set_x: a dispersion target with the Gauss law (its R^-1 depends on the sample count)");
-        if (T.kfwd != d.n) return fail(e, BH_EUNSUPPORTED, "bh_sites_set_x: a dispersion target of more than 60 periods (the interpolation path)");
+        if (d.law == BH_LAW_GAUSS) return fail(e, BH_EINVAL, (w + ": a dispersion target with the Gauss law (its R^-1 depends on the sample count)").c_str());
+        if (T.kfwd != d.n) return fail(e, BH_EUNSUPPORTED, (w + ": a dispersion target of more than 60 periods (the interpolation path)").c_str());
         for (size_t s = 0; s < S; ++s) {
             const int ns = n[s * nt + t];
-            if (ns < 1 || ns > d.n) return fail(e, BH_EINVAL, "bh_sites_set_x: a site's period count is below 1 or above the descriptor's n (the capacity)");
+            if (ns < 1 || ns > d.n) return fail(e, BH_EINVAL, (w + ": a site's period count is below 1 or above the descriptor's n (the capacity)").c_str());
             for (int i = 0; i < ns; ++i) {
                 const double v = x[s * ldy + T.off + i];
-                if (!std::isfinite(v) || !(v > 0.0)) return fail(e, BH_EINVAL, "bh_sites_set_x: a period that is not finite and positive");
+                if (!std::isfinite(v) || !(v > 0.0)) return fail(e, BH_EINVAL, (w + ": a period that is not finite and positive").c_str());
             }
         }
-        if (d.igr != BH_VEL_PHASE || d.mode > 1) { // group velocities, higher modes: only with the descriptor's periods at every site
+        if (!all && (d.igr != BH_VEL_PHASE || d.mode > 1)) { // group velocities, higher modes: only with the descriptor's periods at every site
             std::vector<double> x0((size_t)d.n);
             HIPCHK(e, hipSetDevice(e->device));
             HIPCHK(e, hipMemcpy(x0.data(), T.x.p, (size_t)d.n * sizeof(double), hipMemcpyDeviceToHost));
             for (size_t s = 0; s < S; ++s)
                 if (n[s * nt + t] != d.n || std::memcmp(x0.data(), x + s * ldy + T.off, (size_t)d.n * sizeof(double)) != 0)
-                    return fail(e, BH_EUNSUPPORTED, "bh_sites_set_x: per-site periods on a group-velocity or higher-mode target");
+                    return fail(e, BH_EUNSUPPORTED, (w + ": per-site periods on a group-velocity or higher-mode target").c_str());
         }
     }
     int rc = sites_register(e, nsites, n, yobs, yerr);
@@ -2041,7 +2052,18 @@ int bh_sites_set_x(bh_engine *e, int nsites, const int32_t *n, const double *x, 
         return fail(e, BH_EHIP, "copy site table");
     }
     e->site_x = true;
+    e->site_x_all = all;
     return BH_OK;
+}
+
+int bh_sites_set_x(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+{
+    return sites_register_x(e, "bh_sites_set_x", false, nsites, n, x, yobs, yerr);
+}
+
+int bh_sites_set_x_all(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+{
+    return sites_register_x(e, "bh_sites_set_x_all", true, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const double *nsv)

@@ -76,8 +76,20 @@ __host__ __device__ inline size_t lane_wave_bytes(int Lmax, int K, int mode)
 // FAST: 0 the reference sequence, 2 the short refinement (a launch is one target); SIMPLE: a fundamental-mode phase-velocity
 // launch (SearchT, swd_common.h: no second root, no mode loop)
 // FA: the fast arithmetic (swd_fa.h; launches of the short refinement only)
+// BH_SWD_SITEX 1: the SITE-PERIOD build (swd_kernel_x.hip includes this file) of the launches of second roots: entry v = period
+// v / Bm of model v % Bm takes its site's count and that one period from the table (SwdSiteXArgs X, target 0 of it) -- enter_second
+// needs no other period, no shared row is staged -- and is idle, writing nothing, where the period index is at or beyond the
+// count or the site out of range.  A.K is the capacity of the output row.  Nothing else differs: a model gets the bits of a
+// launch whose target has its site's periods.  0: the builds this file always had, the same machine code.
+#ifndef BH_SWD_SITEX
+#define BH_SWD_SITEX 0
+#endif
 template <int IFUNC, bool LOOK, int LANE_WPB, int FAST, bool SIMPLE, bool FA = false>
+#if BH_SWD_SITEX
+__global__ __launch_bounds__(BH_WAVE * LANE_WPB) void swd_kernel(SwdKernelArgs A, SwdSiteXArgs X)
+#else
 __global__ __launch_bounds__(BH_WAVE * LANE_WPB) void swd_kernel(SwdKernelArgs A)
+#endif
 {
     extern __shared__ __align__(16) unsigned char smem_all[];
     const int lane = threadIdx.x & (BH_WAVE - 1);
@@ -87,6 +99,20 @@ __global__ __launch_bounds__(BH_WAVE * LANE_WPB) void swd_kernel(SwdKernelArgs A
     const int r = lane & (J - 1);         // this lane's trial
     const int lbase = lane - r;           // first lane of the model
     const int sidx = (wid * BH_WAVE + lane) / J; // position in the processing order
+#if BH_SWD_SITEX
+    static_assert(!SIMPLE && FAST == 0 && !FA, "the site-period build is the launch of second roots");
+    const bool inrange = sidx < A.B;
+    const int iv = inrange ? (A.perm ? A.perm[sidx] : sidx) : 0;
+    const bool second = true;
+    const int ib = iv % A.Bm;
+    const int Lmax = A.Lmax;
+    // this entry's model's own periods and their count (-1: site out of range); an entry beyond them is as one beyond the launch
+    const double *per = X.x;
+    const int Kown = inrange ? bh_site_periods(X, 0, ib, A.K, per) : -1;
+    const bool valid = inrange && iv / A.Bm < Kown;
+    const int K = valid ? Kown : 0;
+    constexpr int KROW = 0; // (no period row in LDS)
+#else
     const bool valid = sidx < A.B;
     const int iv = valid ? (A.perm ? A.perm[sidx] : sidx) : 0;
     // (a launch of second roots, SwdKernelArgs::second: entry iv = period iv / Bm of model iv % Bm -- neighbouring lanes, neighbouring models)
@@ -94,16 +120,25 @@ __global__ __launch_bounds__(BH_WAVE * LANE_WPB) void swd_kernel(SwdKernelArgs A
     const int ib = second ? iv % A.Bm : iv;
     const int Lmax = A.Lmax;
     const int K = A.K;
+#endif
 
     const LibmTabs LT = stage_libm_tables(smem_all, threadIdx.x, BH_WAVE * LANE_WPB);
+#if BH_SWD_SITEX
+    unsigned char *smem = smem_all + LANE_TAB_PAD + (size_t)wave * lane_wave_bytes(Lmax, KROW, 1);
+#else
     unsigned char *smem = smem_all + LANE_TAB_PAD + (size_t)wave * lane_wave_bytes(Lmax, K, A.mode);
+#endif
     float *mdl = reinterpret_cast<float *>(smem);                       // [4][Lmax][64]
     double *xs = reinterpret_cast<double *>(smem + (size_t)4 * Lmax * BH_WAVE * sizeof(float));
     double *ys = xs + NEV_LO * BH_WAVE;                                  // [NEV_LO][64] each
+#if BH_SWD_SITEX
+    double *cpl = ys + NEV_LO * BH_WAVE;                                 // (mode 1: not read)
+#else
     double *per = ys + NEV_LO * BH_WAVE;                                 // [K]
     double *cpl = per + ((K + 1) & ~1);                                  // [2][K][64], only if mode > 1
 
     for (int k = lane; k < K; k += BH_WAVE) per[k] = A.periods[k];
+#endif
 
     // ---- stage the model through LDS, rounding to binary32 like the f2py boundary -----------
     const int mmax = valid ? A.nlay[ib] : 2;
@@ -135,8 +170,13 @@ __global__ __launch_bounds__(BH_WAVE * LANE_WPB) void swd_kernel(SwdKernelArgs A
     const int llw = (md.Bf(0) <= 0.0f) ? 2 : 1;
 
     SearchT<BH_WAVE, NEV_LO, FAST, SIMPLE> S;
+#if BH_SWD_SITEX
+    S.init(md, mmax, valid, BH_VEL_GROUP, K, per, xs + lane, ys + lane, A.vel + (size_t)ib * A.ldv, r == 0, 1,
+           cpl + lane, cpl + lane, IFUNC, A.counted != 0, false, FA);
+#else
     S.init(md, mmax, valid, A.igr, K, per, xs + lane, ys + lane, A.vel + (size_t)ib * A.ldv, r == 0, A.mode,
            cpl + lane, cpl + (size_t)K * BH_WAVE + lane, IFUNC, A.counted != 0, false, FA);
+#endif
     {
         const size_t nl = (size_t)gridDim.x * LANE_WPB * BH_WAVE; // lanes of the launch
         double *hx = A.nev_high + (size_t)wid * BH_WAVE + lane;
@@ -222,6 +262,7 @@ __global__ __launch_bounds__(BH_WAVE * LANE_WPB) void swd_kernel(SwdKernelArgs A
     }
 }
 
+#if !BH_SWD_SITEX
 // ---- processing order: models by layer count, deepest first (counting sort, one workgroup) -------------
 __global__ __launch_bounds__(1024) void order_kernel(int B, const int32_t *nlay, int32_t *perm, int Lcut, int32_t *split)
 {
@@ -463,9 +504,43 @@ __global__ void interp_kernel(int B, int K0, const double *x0, const double *y0,
     }
     y1[(size_t)b * ld1 + k] = r;
 }
+#endif // !BH_SWD_SITEX
 
 } // namespace
 
+#if BH_SWD_SITEX
+// The launch of second roots at every model's own periods: bh_launch_swd's geometry and choice of build for such a launch
+// (reference sequence, not SIMPLE; wave type, look-ahead and wavefronts per workgroup picked here), the table with target ty first.
+void bh_launch_swd_second_x(const SwdKernelArgs &a, int iwave, const SwdSiteXArgs &x, int ty, hipStream_t stream, SwdLaneBuild *build)
+{
+    SwdKernelArgs b = a;
+    SwdSiteXArgs xt = x;
+    xt.col[0] = x.col[ty];
+    xt.off[0] = x.off[ty];
+    int J = 1;
+    while (2 * J <= a.look && 2 * J <= 16) J *= 2; // largest power of two <= look
+    b.look = J;
+    b.second = 1; b.igr = BH_VEL_GROUP; b.mode = 1; b.fast = 0; b.farith = 0;
+    const int no_fair = bh_tuning().swd_no_fair ? 1 : 0; // (experiment switches, bh_tuning.h)
+    const int slice = bh_tuning().swd_slice;
+    b.fair = (no_fair || a.fair < 0) ? 0 : (slice > 0 ? slice : (a.fair > 0 ? a.fair : 16));
+    const int mpw = BH_WAVE / J;
+    const int waves = (a.B + mpw - 1) / mpw;
+    const size_t wb = lane_wave_bytes(a.Lmax, 0, 1); // (no period row)
+    const bool two = a.fair == 12 && LANE_TAB_PAD + 2 * wb <= 64 * 1024;
+    const size_t lds = LANE_TAB_PAD + (two ? 2 : 1) * wb;
+    const dim3 grid(two ? (waves + 1) / 2 : waves), block((two ? 2 : 1) * BH_WAVE);
+    if (build != nullptr) *build = SwdLaneBuild{{iwave == 1 ? 1 : 2, J > 1, two ? 2 : 1, 0, false, false}, grid.x, b.fair};
+#define BH_SECOND_LAUNCH(IF, LK, WP) hipLaunchKernelGGL((swd_kernel<IF, LK, WP, 0, false>), grid, block, lds, stream, b, xt)
+#define BH_SECOND_PICK_WP(IF, LK) do { if (two) BH_SECOND_LAUNCH(IF, LK, 2); else BH_SECOND_LAUNCH(IF, LK, 1); } while (0)
+#define BH_SECOND_PICK_LK(IF) do { if (J > 1) BH_SECOND_PICK_WP(IF, true); else BH_SECOND_PICK_WP(IF, false); } while (0)
+    if (iwave == 1) BH_SECOND_PICK_LK(1);
+    else BH_SECOND_PICK_LK(2);
+#undef BH_SECOND_PICK_LK
+#undef BH_SECOND_PICK_WP
+#undef BH_SECOND_LAUNCH
+}
+#else
 
 void bh_launch_order(int B, const int32_t *nlay, int32_t *perm, int Lcut, int32_t *split, hipStream_t stream)
 {
@@ -665,3 +740,4 @@ double bh_swd_plan(int B, int Lmax, int ntargets, const int *iwave, int Gforce, 
     for (int t = 0; t < ntargets; ++t) look[t] = plan_fit(Gg, best_lvl[t]);
     return best;
 }
+#endif // !BH_SWD_SITEX

@@ -148,6 +148,7 @@ def load_library():
     L.bh_sites_set.argtypes = [vp, C.c_int, vp, vp]
     L.bh_sites_set_rf.argtypes = [vp, C.c_int, vp, vp]
     L.bh_sites_set_x.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.bh_sites_set_x_all.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_evaluate_sites.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                     C.c_ssize_t, C.c_ssize_t, vp, vp, vp, vp, vp, vp]
     L.bh_chain_propose.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int]
@@ -166,7 +167,7 @@ def load_library():
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
-                 "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x"):
+                 "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all"):
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -193,6 +194,8 @@ SITE_SYMBOLS = ("bh_sites_set", "bh_evaluate_sites")
 SITE_RF_SYMBOLS = ("bh_sites_set_rf",)
 # include/bh_engine_sites_x.h: dispersion periods per site
 SITE_X_SYMBOLS = ("bh_sites_set_x",)
+# include/bh_engine_sites_x_all.h: ... on every dispersion target (group velocities, higher modes)
+SITE_X_ALL_SYMBOLS = ("bh_sites_set_x_all",)
 # include/bh_engine_posterior.h: posterior velocity-depth summaries of many sites (bayhunter_amd/posterior.py)
 POSTERIOR_SYMBOLS = ("bh_posterior_create", "bh_posterior_destroy", "bh_posterior_load", "bh_posterior_columns",
                      "bh_posterior_hist", "bh_posterior_interfaces")
@@ -554,6 +557,15 @@ class Engine(object):
         int32 samples of every (site, target); x, yobs and yerr[S, ldy] in ymod's column layout, the columns beyond a site's
         count unread.  The registered descriptors give every dispersion target's capacity (their n) and a placeholder x.
         evaluate_sites then computes a model's dispersion curves at its site's periods; set_targets and set_sites drop the table."""
+        self._set_sites_x(self._L.bh_sites_set_x, n, x, yobs, yerr)
+
+    def set_sites_x_all(self, n, x, yobs, yerr=None):
+        """set_sites_x for every dispersion target the engine serves (bh_sites_set_x_all): group-velocity and higher-mode
+        targets may differ from site to site in their periods and counts as well; same arrays, same lifetime."""
+        self._set_sites_x(self._L.bh_sites_set_x_all, n, x, yobs, yerr)
+
+    def _set_sites_x(self, entry, n, x, yobs, yerr):
+        """set_sites_x / set_sites_x_all: the arrays checked and handed to entry point `entry`"""
         n = np.ascontiguousarray(n, dtype=np.int32)
         x, yobs = _f64(x), _f64(yobs)
         if yobs.ndim != 2 or yobs.shape[1] != self.ldy or yobs.shape[0] < 1:
@@ -566,7 +578,7 @@ class Engine(object):
             yerr = _f64(yerr)
             if yerr.shape != yobs.shape:
                 raise ValueError("yerr must have the shape of yobs")
-        self._check(self._L.bh_sites_set_x(self._h, yobs.shape[0], _ptr(n), _ptr(x), _ptr(yobs), _ptr(yerr)))
+        self._check(entry(self._h, yobs.shape[0], _ptr(n), _ptr(x), _ptr(yobs), _ptr(yerr)))
         self.nsites = yobs.shape[0]
 
     def set_sites_rf(self, p, nsv):

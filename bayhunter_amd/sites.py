@@ -8,7 +8,8 @@ registers site 0's target descriptors plus the table of every site's observed da
 near-surface velocity nsv of the receiver functions may differ between sites as well (per_site_rf=True,
 include/bh_engine_sites_rf.h): they enter only the coefficient stage of the forward model.  So may the periods of the
 dispersion curves and their number (per_site_x=True, include/bh_engine_sites_x.h): every model is then searched at the
-periods of its own site, as a one-site run searches it.
+periods of its own site, as a one-site run searches it.  per_site_x="all" extends that from fundamental-mode phase
+velocities to every dispersion target -- group velocities and higher modes (include/bh_engine_sites_x_all.h).
 """
 import numpy as np
 
@@ -51,7 +52,12 @@ class SiteTargets(object):
     number of them (1 to 60 per site; not with the Gauss law, whose R^-1 depends on the number).  Each model's curve is then
     computed at its own site's periods and compared over its own site's samples; in the synthetics a site's velocities are
     followed by zeros up to the largest count of any site.  Group-velocity and higher-mode targets and receiver functions
-    still share x bit for bit.  The default (False) keeps the check above."""
+    still share x bit for bit.  The default (False) keeps the check above.
+
+    per_site_x="all": as True, for EVERY dispersion target -- phase or group velocity, modes 1 to 3, Rayleigh or Love, flat or
+    flattened: group-velocity and higher-mode targets may differ in their periods and their number as well (a station's group
+    curve has its own usable band just as its phase curve has).  A group velocity's two roots per period and the mode loop
+    are searched at the model's own site's periods -- the bits of a one-site run.  Receiver functions still share x."""
 
     def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False):
         self._sites = [jt if isinstance(jt, JointTarget) else JointTarget(jt) for jt in jointtargets]
@@ -62,7 +68,9 @@ class SiteTargets(object):
             raise ValueError("names must be %d distinct names, one per site" % len(self._sites))
         self._engine = engine
         self.per_site_rf = bool(per_site_rf)
-        self.per_site_x = bool(per_site_x)
+        if isinstance(per_site_x, str) and per_site_x != "all":
+            raise ValueError("per_site_x is False, True or \"all\", not %r" % (per_site_x,))
+        self.per_site_x = "all" if isinstance(per_site_x, str) else bool(per_site_x)
         for jt in self._sites:          # every site on one engine
             if jt._engine is None:
                 jt._engine = engine
@@ -146,10 +154,11 @@ class SiteTargets(object):
                         raise ValueError("%s: Gauss law with another R^-1 / ln|R| than site 0's (sites share corr)" % what)
 
     def _check_site_x(self, what, t, x, same_x):
-        """what the engine refuses of a dispersion target registered with periods per site (include/bh_engine_sites_x.h);
+        """what the engine refuses of a dispersion target registered with periods per site (include/bh_engine_sites_x.h; with
+        per_site_x="all" include/bh_engine_sites_x_all.h, which serves group velocities and higher modes too);
         same_x: the site's x is site 0's"""
         p = t.moddata.plugin
-        if not same_x and (p.veltype != 0 or p.modelparams["mode"] > 1):
+        if self.per_site_x != "all" and not same_x and (p.veltype != 0 or p.modelparams["mode"] > 1):
             raise ValueError("%s: x differs from site 0's on a group-velocity or higher-mode target (per_site_x serves "
                              "fundamental-mode phase velocities)" % what)
         if x.ndim != 1 or x.size < 1 or x.size > SITE_X_MAX_PERIODS:
@@ -183,12 +192,13 @@ class SiteTargets(object):
         """site 0's descriptors; a fundamental-mode phase-velocity target's n is the largest count of any site and its x, yobs
         (and yerr) placeholders of that length -- the site path reads the tables, never these.  Group-velocity and higher-mode
         targets keep site 0's x, which every site shares: the engine checks the table against it, and a group velocity's
-        second roots are searched at the descriptor's periods."""
+        second roots are searched at the descriptor's periods.  per_site_x="all": every dispersion target gets the capacity
+        and placeholders -- all of them are searched at the table's periods."""
         n = np.array([[np.size(t.obsdata.x) for t in jt.targets] for jt in self._sites])
         descs = []
         for i, t in enumerate(self.targets):
             d = t.engine_desc()
-            if d["kind"] == _engine.TARGET_SWD and d["igr"] == 0 and d["mode"] <= 1:
+            if d["kind"] == _engine.TARGET_SWD and (self.per_site_x == "all" or (d["igr"] == 0 and d["mode"] <= 1)):
                 cap = int(n[:, i].max())
                 d["n"] = cap
                 d["x"], d["yobs"] = np.ones(cap), np.zeros(cap)
@@ -235,7 +245,10 @@ class SiteTargets(object):
         if self._registered != sig or e._owner is not self:
             if self.per_site_x:
                 e.set_targets(self._capacity_descs())
-                e.set_sites_x(*self.site_x_arrays())
+                if self.per_site_x == "all":
+                    e.set_sites_x_all(*self.site_x_arrays())
+                else:
+                    e.set_sites_x(*self.site_x_arrays())
             else:
                 e.set_targets([t.engine_desc() for t in self.targets])
                 yobs, yerr = self.site_arrays()
