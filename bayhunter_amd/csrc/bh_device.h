@@ -329,6 +329,14 @@ constexpr int BH_RF_MAX_NSAMP = 1 << 18;
 size_t bh_rf_lds_bytes(int nsamp);
 // 0, or -1 when the trace does not fit a workgroup's LDS; sites: null, or the site-indexed coefficient kernels
 int bh_launch_rf(const RfKernelArgs &a, hipStream_t stream, const RfSiteArgs *sites = nullptr);
+// Sites that lack a receiver-function target (bh_sites_set_missing, include/bh_engine_sites_missing.h): the builds of
+// rf_kernel_m.hip (rf_kernel.hip compiled with BH_RF_MISSING).  n[s * ld] is the sample count of site s for the target (0 or the
+// descriptor's): the coefficient stage marks the record of a model whose site has none ABSENT (rec[3] = 2, distinct from bad = 1),
+// and a workgroup of the synthesis kernel that finds that mark writes nkeep zeros and leaves -- no recursion, no transform.
+struct RfSiteMArgs : RfSiteArgs {
+    const int32_t *n; // device [nsites][ld], already offset to the target's column
+};
+int bh_launch_rf_m(const RfKernelArgs &a, hipStream_t stream, const RfSiteMArgs &sites);
 // bh_probe_math ops 11-16: the synthesis kernel's own elementary functions (include/bh_engine_debug.h); -1 for another op
 int bh_launch_rf_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 
@@ -363,6 +371,21 @@ struct LikeKernelArgs {
     int32_t *err;    // [B]
 };
 void bh_launch_like(const LikeKernelArgs &a, hipStream_t stream);
+// Which form a likelihood launch takes (every launcher of like_kernel.hip and like_kernel_m.hip): true = one wavefront per model --
+// every target fits one wavefront, or comes with its sums already formed by the forward kernel (a receiver function's fused
+// likelihood: nothing of its trace is read), and a Gauss law has its slab sums from the MFMA contraction; false = one workgroup per
+// model, with *lds bytes of dynamic LDS for the in-kernel Gauss mat-vec.  (With a count table n is the capacity of the target's
+// columns: a site's own count is at most that.)
+inline bool bh_like_small_form(const LikeKernelArgs &a, size_t *lds)
+{
+    *lds = 0;
+    bool small = true;
+    for (int t = 0; t < a.nt; ++t) {
+        if (a.t[t].law == 3 && a.t[t].quad == nullptr && (size_t)a.t[t].n * sizeof(double) > *lds) *lds = (size_t)a.t[t].n * sizeof(double);
+        small = small && (a.t[t].n <= 64 || (a.t[t].pre != nullptr && a.t[t].law != 3)) && !(a.t[t].law == 3 && a.t[t].quad == nullptr);
+    }
+    return small;
+}
 // Likelihood kernel: LikeTargetDev::yobs / yerr_scaled / logdet_extra of target t become, for a model of site s,
 // yobs + s * ldy + off, yerr_scaled + s * ldy + off (law 1) and logdet_extra[s * nt + t] (law 1).
 struct LikeSiteArgs {
@@ -380,6 +403,10 @@ struct LikeSiteXArgs : LikeSiteArgs {
     const int32_t *n; // device [nsites][nt]
 };
 void bh_launch_like_sites_x(const LikeKernelArgs &a, const LikeSiteXArgs &sites, hipStream_t stream);
+// ... where a count may be 0: the site lacks the target (bh_sites_set_missing; like_kernel_m.hip, like_kernel.hip compiled with
+// BH_LIKE_MISSING).  Such a target is skipped -- nothing of noise, yobs, ymod or its failure flag is read, nothing is added to logL
+// or to the joint misfit, its own misfit is 0 -- so the sums are those of the present targets in their order.
+void bh_launch_like_sites_m(const LikeKernelArgs &a, const LikeSiteXArgs &sites, hipStream_t stream);
 
 void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 

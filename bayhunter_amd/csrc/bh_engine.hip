@@ -9,6 +9,7 @@
 #include "../../include/bh_engine_sites_rf.h"
 #include "../../include/bh_engine_sites_x.h"
 #include "../../include/bh_engine_sites_x_all.h"
+#include "../../include/bh_engine_sites_missing.h"
 #include "bh_device.h"
 
 #include <algorithm>
@@ -144,6 +145,7 @@ struct bh_engine {
     // dispersion periods per site (bh_sites_set_x, include/bh_engine_sites_x.h): registered together with the site table
     bool site_x = false;
     bool site_x_all = false;                  // ... registered by bh_sites_set_x_all: group velocities' second roots at a site's own periods
+    bool site_missing = false;                // ... registered by bh_sites_set_missing: a count may be 0 (the site lacks the target)
     DevBuf site_xn, site_xper;                // [nsites][nt] sample counts (int32), [nsites][ldy] periods in ymod's column layout
     // instrumentation
     bool timing = false, counting = false;
@@ -229,7 +231,7 @@ void release_sites(bh_engine *e)
     for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx, &e->site_p, &e->site_nsv, &e->site_xn, &e->site_xper}) release(*b);
     e->nsites = 0;
     e->site_rf = false;
-    e->site_x = e->site_x_all = false;
+    e->site_x = e->site_x_all = e->site_missing = false;
 }
 
 // Targets.py:124-128, the nocorr_scalederr law: out = yerr / min(yerr), returns ln prod(out) (bh_targets_set, bh_sites_set)
@@ -588,7 +590,8 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
 // dispersion on the 60-period grid followed by interpolation, or a receiver function.
 enum EvalRole { ROLE_NONE, ROLE_SWD, ROLE_SWD60, ROLE_RF };
 // The likelihood launcher of a fused call: bh_launch_like, bh_launch_like_sites, bh_launch_like_sites_x (a site's own sample counts)
-enum EvalLike { LIKE_PLAIN, LIKE_SITES, LIKE_SITES_X };
+// (LIKE_SITES_M: bh_launch_like_sites_m, counts that may be 0)
+enum EvalLike { LIKE_PLAIN, LIKE_SITES, LIKE_SITES_X, LIKE_SITES_M };
 
 // What one fused call (bh_evaluate_batch, bh_evaluate_sites) does: everything its steps would otherwise decide.
 struct EvalPlan {
@@ -601,6 +604,8 @@ struct EvalPlan {
     bool want_gate;             // ... which waits for that launch's started workgroups (where the launch has any: gate_need)
     int prio_low;               // SwdMultiArgs::prio_low of the dispersion launch
     bool x_table, rf_table;     // the site table's periods (bh_sites_set_x) / receiver-function parameters (bh_sites_set_rf) are in force
+    bool missing;               // the table's counts may be 0 (bh_sites_set_missing): the receiver-function and likelihood builds that skip
+    bool rf_needs_table;        // ... and a receiver-function target is registered without bh_sites_set_rf: the call is refused
     EvalLike like;
     bool err_zero_always;       // bh_tuning.h err_memset: the failure flags are zeroed on every call
 };
@@ -654,7 +659,10 @@ EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
     p.x_table = sites && e->site_x;
     // (sites with their own p / nsv, bh_sites_set_rf: the coefficient kernels read them from the table, column t)
     p.rf_table = sites && e->site_rf;
-    p.like = p.x_table ? LIKE_SITES_X : (sites ? LIKE_SITES : LIKE_PLAIN);
+    // (sites that lack targets, bh_sites_set_missing: the coefficient stage looks the model's site up in the count table)
+    p.missing = p.x_table && e->site_missing;
+    p.rf_needs_table = p.missing && have_rf && !p.rf_table;
+    p.like = p.missing ? LIKE_SITES_M : (p.x_table ? LIKE_SITES_X : (sites ? LIKE_SITES : LIKE_PLAIN));
     p.err_zero_always = tun.err_memset != 0;
     return p;
 }
@@ -1208,6 +1216,7 @@ struct RfJob {
     double *rf; int ldr;
     const double *yobs; double *sums;
     const RfSiteArgs *sites;
+    const RfSiteMArgs *msites; // sites that may lack the target (bh_sites_set_missing): the builds of bh_launch_rf_m, or null
 };
 
 int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl, ptrdiff_t sb, const RfJob &j, const RfPlace &where)
@@ -1229,7 +1238,7 @@ int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, pt
     a.lds_min = where.lds_min;
     a.coef_small = where.coef_small;
     ev_begin(e, 1, st);
-    const int lrc = bh_launch_rf(a, st, j.sites);
+    const int lrc = j.msites ? bh_launch_rf_m(a, st, *j.msites) : bh_launch_rf(a, st, j.sites);
     ev_end(e, 1, st);
     if (lrc != 0) return fail(e, BH_EUNSUPPORTED, "receiver function: nsamp above 262144 is not supported");
     HIPCHK(e, hipGetLastError());
@@ -1781,6 +1790,7 @@ int eval_args_ok(bh_engine *e, const EvalPlan &p, bool host, const EvalCall &c)
 {
     if (p.nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
     if (p.no_forward) return fail(e, BH_EINVAL, "a BH_TARGET_USER target has no forward model: use bh_loglike_batch");
+    if (p.rf_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_missing with a receiver-function target needs bh_sites_set_rf");
     if (!c.m.nlay || !c.m.h || !c.m.vp || !c.m.vs || !c.la.noise || !c.la.logL || !c.la.misfits || !c.la.err) return fail(e, BH_EINVAL, "null argument");
     if (c.site && host)
         for (int b = 0; b < p.B; ++b)
@@ -1881,8 +1891,14 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
         if (p.role[t] != ROLE_RF) continue;
         RfSiteArgs rs{};
         if (p.rf_table) rs = RfSiteArgs{c.site, e->nsites, nt, (const double *)e->site_p.p + t, (const double *)e->site_nsv.p + t};
+        RfSiteMArgs rm{};
+        if (p.missing) {
+            static_cast<RfSiteArgs &>(rm) = rs;
+            rm.n = (const int32_t *)e->site_xn.p + t;
+        }
         const RfJob job{d.p_s_per_deg, d.gauss, d.nsamp, d.fsamp, d.tshift, d.nsv, d.waveno, d.n, c.ymod + T.off, ldy,
-                        p.rf_fused[t] ? (const double *)T.yobs.p : nullptr, p.rf_fused[t] ? (double *)T.sums.p : nullptr, p.rf_table ? &rs : nullptr};
+                        p.rf_fused[t] ? (const double *)T.yobs.p : nullptr, p.rf_fused[t] ? (double *)T.sums.p : nullptr, p.rf_table ? &rs : nullptr,
+                        p.missing ? &rm : nullptr};
         if ((rc = launch_rf(e, rst, B, c.Lmax, c.m, c.sl, c.sb, job, where))) return rc;
     }
     return p.fork ? wait_for(e, e->ev_join, e->aux, st) : BH_OK;
@@ -1899,7 +1915,8 @@ int run_like(bh_engine *e, hipStream_t st, LikeKernelArgs la, const bool *fused,
     lx.site = site; lx.nsites = e->nsites; lx.yobs = (const double *)e->site_yobs.p; lx.yerr_scaled = (const double *)e->site_yerr.p;
     lx.logdet_extra = (const double *)e->site_logdet.p; lx.n = (const int32_t *)e->site_xn.p;
     ev_begin(e, 2, st);
-    if (like == LIKE_SITES_X) bh_launch_like_sites_x(la, lx, st); // (a site's own sample counts)
+    if (like == LIKE_SITES_M) bh_launch_like_sites_m(la, lx, st); // (... of which some may be 0)
+    else if (like == LIKE_SITES_X) bh_launch_like_sites_x(la, lx, st); // (a site's own sample counts)
     else if (like == LIKE_SITES) bh_launch_like_sites(la, lx, st);
     else bh_launch_like(la, st);
     ev_end(e, 2, st);
@@ -1994,9 +2011,10 @@ int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yer
     return sites_register(e, nsites, nullptr, yobs, yerr);
 }
 
-// bh_sites_set_x and bh_sites_set_x_all (who: the entry point's name, for the messages).  all: per-site periods and counts on
-// group-velocity and higher-mode targets are accepted -- the one check bh_sites_set_x_all skips.
-static int sites_register_x(bh_engine *e, const char *who, bool all, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+// bh_sites_set_x, bh_sites_set_x_all and bh_sites_set_missing (who: the entry point's name, for the messages).  all: per-site
+// periods and counts on group-velocity and higher-mode targets are accepted -- the one check bh_sites_set_x_all skips.  missing
+// (with all): a count of 0 is accepted on any target -- the site lacks it -- but every site has a target and every target a site.
+static int sites_register_x(bh_engine *e, const char *who, bool all, bool missing, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
     if (!e) return BH_EINVAL;
     const std::string w(who);
@@ -2007,18 +2025,36 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, int nsites,
     for (const auto &T : e->targets) scaled = scaled || T.d.law == BH_LAW_NOCORR_SCALED;
     if (scaled && !yerr) return fail(e, BH_EINVAL, "a BH_LAW_NOCORR_SCALED target needs yerr of every site");
     const size_t S = (size_t)nsites;
+    if (missing) {
+        for (size_t s = 0; s < S; ++s) {
+            bool any = false;
+            for (int t = 0; t < nt; ++t) any = any || n[s * nt + t] != 0;
+            if (!any) return fail(e, BH_EINVAL, (w + ": a site with no target (every count 0)").c_str());
+        }
+        for (int t = 0; t < nt; ++t) {
+            bool any = false, lacks = false;
+            for (size_t s = 0; s < S; ++s) {
+                any = any || n[s * nt + t] != 0;
+                lacks = lacks || n[s * nt + t] == 0;
+            }
+            if (!any) return fail(e, BH_EINVAL, (w + ": a target no site has (every count 0)").c_str());
+            if (lacks && e->targets[(size_t)t].d.law == BH_LAW_GAUSS)
+                return fail(e, BH_EUNSUPPORTED, (w + ": a Gauss-law target that a site lacks (the contraction gathers every site's rows)").c_str());
+        }
+    }
     for (int t = 0; t < nt; ++t) {
         const TargetHost &T = e->targets[(size_t)t];
         const bh_target_desc &d = T.d;
         if (d.kind != BH_TARGET_SWD) { // (a receiver function's x is its descriptor's time axis: shared)
             for (size_t s = 0; s < S; ++s)
-                if (n[s * nt + t] != d.n) return fail(e, BH_EINVAL, (w + ": the sample count of a target that is no dispersion curve differs from its descriptor's").c_str());
+                if (n[s * nt + t] != d.n && !(missing && n[s * nt + t] == 0)) return fail(e, BH_EINVAL, (w + ": the sample count of a target that is no dispersion curve differs from its descriptor's").c_str());
             continue;
         }
         if (d.law == BH_LAW_GAUSS) return fail(e, BH_EINVAL, (w + ": a dispersion target with the Gauss law (its R^-1 depends on the sample count)").c_str());
         if (T.kfwd != d.n) return fail(e, BH_EUNSUPPORTED, (w + ": a dispersion target of more than 60 periods (the interpolation path)").c_str());
         for (size_t s = 0; s < S; ++s) {
             const int ns = n[s * nt + t];
+            if (missing && ns == 0) continue; // (the site lacks this curve)
             if (ns < 1 || ns > d.n) return fail(e, BH_EINVAL, (w + ": a site's period count is below 1 or above the descriptor's n (the capacity)").c_str());
             for (int i = 0; i < ns; ++i) {
                 const double v = x[s * ldy + T.off + i];
@@ -2053,17 +2089,23 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, int nsites,
     }
     e->site_x = true;
     e->site_x_all = all;
+    e->site_missing = missing;
     return BH_OK;
 }
 
 int bh_sites_set_x(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_x", false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_x", false, false, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_x_all(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_x_all", true, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_x_all", true, false, nsites, n, x, yobs, yerr);
+}
+
+int bh_sites_set_missing(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+{
+    return sites_register_x(e, "bh_sites_set_missing", true, true, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const double *nsv)

@@ -29,6 +29,24 @@
 // draws can be injected from a buffer instead.
 #include "../../include/bh_engine.h"
 #include "bh_device.h"
+// BH_CHAIN_ABSENT (chain_kernel_m.hip): the builds of the two propose kernels for chains whose site lacks some of the targets
+// (include/bh_engine_sites_missing.h) and their entry points only.  They take absent[C], one bit per target: the two noise
+// parameters of an absent target are never proposed, never checked against their bounds and never counted among the free ones.
+#ifndef BH_CHAIN_ABSENT
+#define BH_CHAIN_ABSENT 0
+#endif
+#if BH_CHAIN_ABSENT
+#include "../../include/bh_engine_sites_missing.h"
+#define BH_NOISE_FREE(i) (cfg.noise_lo[i] != cfg.noise_hi[i] && ((absent >> ((i) >> 1)) & 1u) == 0u)
+#define BH_ABSENT_PARAM , unsigned absent
+#define BH_ABSENT_ARG(c) , (unsigned)absent_of[c]
+#define BH_ABSENT_KPARAM , const uint8_t *absent_of
+#else
+#define BH_NOISE_FREE(i) (cfg.noise_lo[i] != cfg.noise_hi[i])
+#define BH_ABSENT_PARAM
+#define BH_ABSENT_ARG(c)
+#define BH_ABSENT_KPARAM
+#endif
 
 namespace {
 
@@ -95,6 +113,7 @@ __device__ Draws get_draws(const bh_chain_config &cfg, const bh_chain_state &S, 
     return d;
 }
 
+#if !BH_CHAIN_ABSENT
 // the accept step's draw alone (the same bits as get_draws(...).u_accept, without the other five)
 __device__ double get_accept_draw(const bh_chain_config &cfg, const bh_chain_state &S, int c, int C, int iiter, int k)
 {
@@ -104,6 +123,7 @@ __device__ double get_accept_draw(const bh_chain_config &cfg, const bh_chain_sta
     ph.gen(cfg.seed, (uint32_t)(cfg.chain_offset + (int64_t)c), (uint32_t)iiter, 1u, q);
     return u01(q[2], q[3]);
 }
+#endif
 
 enum { MV_VS = 0, MV_Z = 1, MV_BIRTH = 2, MV_DEATH = 3, MV_NOISE = 4, MV_VPVS = 5 };
 __device__ __forceinline__ int par_index(int mv) { return mv <= 1 ? mv : (mv <= 3 ? 2 : mv - 1); } // PAR_MAP
@@ -199,12 +219,12 @@ __device__ __forceinline__ int nearest_nucleus(const double *__restrict__ z, int
 // iteration `iiter`, into column node*C + c of the proposal arrays (leading dimension ldp).
 // `P` brings the storage; `lds_from` as in load_base.
 __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const bh_chain_state &S, int C, size_t ldp, int c, int iiter,
-                                             int from_node, int node, Params &P, const double *lds_from, bool *valid_out, const Draws &d)
+                                             int from_node, int node, Params &P, const double *lds_from, bool *valid_out, const Draws &d BH_ABSENT_PARAM)
 {
     const int ML = cfg.maxlayers, nt = cfg.nt;
     // ---- which modification (SingleChain.py:512-517, :596-599) ---------------------------------
     int nnoise = 0;
-    for (int i = 0; i < 2 * nt; ++i) nnoise += (cfg.noise_lo[i] != cfg.noise_hi[i]);
+    for (int i = 0; i < 2 * nt; ++i) nnoise += BH_NOISE_FREE(i);
     const bool vpvs_free = cfg.vpvsmin != cfg.vpvsmax;
     const bool early = (double)iiter < (-(double)cfg.iter_burnin + (double)cfg.iterations * 0.01);
     int moves[6], nm = 0;
@@ -265,13 +285,13 @@ __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const b
         if (pick >= nnoise) pick = nnoise - 1;
         int idx = 0;
         for (int i = 0, seen = 0; i < 2 * nt; ++i)
-            if (cfg.noise_lo[i] != cfg.noise_hi[i]) {
+            if (BH_NOISE_FREE(i)) {
                 if (seen == pick) idx = i;
                 ++seen;
             }
         noise[idx] = noise[idx] + d.normal * S.propdist[3 * (size_t)C + c];
         for (int i = 0; i < 2 * nt; ++i)
-            if (cfg.noise_lo[i] != cfg.noise_hi[i] && (noise[i] < cfg.noise_lo[i] || noise[i] > cfg.noise_hi[i])) valid = false;
+            if (BH_NOISE_FREE(i) && (noise[i] < cfg.noise_lo[i] || noise[i] > cfg.noise_hi[i])) valid = false;
     } else {
         vpvs = vpvs + d.normal * S.propdist[4 * (size_t)C + c];
         if (vpvs < cfg.vpvsmin || vpvs > cfg.vpvsmax) valid = false;
@@ -361,7 +381,7 @@ __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const b
 }
 
 // lane = chain, one proposal per chain (depth 1; ldp = C)
-__global__ void chain_propose_kernel(bh_chain_config cfg, bh_chain_state S, int C, int iiter)
+__global__ void chain_propose_kernel(bh_chain_config cfg, bh_chain_state S, int C, int iiter BH_ABSENT_KPARAM)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
@@ -369,7 +389,7 @@ __global__ void chain_propose_kernel(bh_chain_config cfg, bh_chain_state S, int 
     Params P;
     P.vs = vs; P.z = z; P.h = h; P.noise = noise;
     bool valid;
-    propose_node(cfg, S, C, (size_t)C, c, iiter, -1, 0, P, nullptr, &valid, get_draws(cfg, S, c, C, iiter, 0));
+    propose_node(cfg, S, C, (size_t)C, c, iiter, -1, 0, P, nullptr, &valid, get_draws(cfg, S, c, C, iiter, 0) BH_ABSENT_ARG(c));
 }
 
 // Speculative window: T = 2^(depth-1) lanes per chain (64 / T chains per single-wavefront workgroup); level k of the
@@ -379,7 +399,7 @@ __global__ void chain_propose_kernel(bh_chain_config cfg, bh_chain_state S, int 
 // levels (round 3, first form: state through global memory and __syncthreads -- 128 us per launch at depth 7, 7 % of a
 // c4 launch).  A workgroup is one wavefront: its LDS operations execute in order, the barrier only pins the compiler.
 __global__ __launch_bounds__(64) void chain_propose_window_kernel(bh_chain_config cfg, bh_chain_state S, int C, size_t ldp,
-                                                                   int iiter, int depth)
+                                                                   int iiter, int depth BH_ABSENT_KPARAM)
 {
     extern __shared__ __align__(16) double tree[];
     const int T = 1 << (depth - 1);
@@ -420,7 +440,7 @@ __global__ __launch_bounds__(64) void chain_propose_window_kernel(bh_chain_confi
             P.z = P.vs + (ML + 1);
             P.h = P.z + (ML + 1);
             bool valid;
-            propose_node(cfg, S, C, ldp, c, iiter + k, from, node, P, from >= 0 ? mine + (size_t)from * RS : nullptr, &valid, d);
+            propose_node(cfg, S, C, ldp, c, iiter + k, from, node, P, from >= 0 ? mine + (size_t)from * RS : nullptr, &valid, d BH_ABSENT_ARG(c));
             rec[0] = (double)P.n;
             rec[1] = valid ? 1.0 : 0.0;
             rec[2] = P.vpvs;
@@ -431,6 +451,7 @@ __global__ __launch_bounds__(64) void chain_propose_window_kernel(bh_chain_confi
     }
 }
 
+#if !BH_CHAIN_ABSENT
 // lane = chain: walk the realised path through the window's tree (depth 1: the plain accept step)
 __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C, size_t ldp, int iiter, int depth,
                                     const double *logL, const double *misfits)
@@ -608,20 +629,33 @@ __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config
     }
 }
 
+#endif
+
 } // namespace
 
 extern "C" {
 
+#if BH_CHAIN_ABSENT
+int bh_chain_propose_window_sites(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
+                                  int depth, ptrdiff_t ld, const uint8_t *absent)
+#else
 int bh_chain_propose_window(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
                             int depth, ptrdiff_t ld)
+#endif
 {
+#if BH_CHAIN_ABSENT
+    if (!absent) return BH_EINVAL;
+#define BH_ABSENT_LAUNCH , absent
+#else
+#define BH_ABSENT_LAUNCH
+#endif
     if (!cfg || !state || C < 0 || cfg->maxlayers > BH_CHAIN_MAXLAYERS || cfg->nt > BH_MAX_TARGETS) return BH_EINVAL;
     if (depth < 1 || depth > BH_CHAIN_MAXDEPTH || ld < (ptrdiff_t)C * ((1 << depth) - 1)) return BH_EINVAL;
     for (int k = 0; k + 1 < depth; ++k)
         if ((iiter + k) % 1000 == 0) return BH_EINVAL; // an adaptation iteration must be the last of its window
     if (C == 0) return BH_OK;
     if (depth == 1 && ld == C) {
-        hipLaunchKernelGGL(chain_propose_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, iiter);
+        hipLaunchKernelGGL(chain_propose_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, iiter BH_ABSENT_LAUNCH);
     } else {
         const int per_wg = 64 >> (depth - 1);
         const size_t lds = (size_t)per_wg * ((1 << depth) - 1) * (node_rec_doubles(cfg->nt, cfg->maxlayers) | 1) * sizeof(double);
@@ -632,10 +666,18 @@ int bh_chain_propose_window(void *stream, const bh_chain_config *cfg, const bh_c
             if (!bh_allow_big_lds(&big, k, 1, 160 * 1024)) return BH_EHIP;
         }
         hipLaunchKernelGGL(chain_propose_window_kernel, dim3((C + per_wg - 1) / per_wg), dim3(64), lds, (hipStream_t)stream, *cfg,
-                           *state, C, (size_t)ld, iiter, depth);
+                           *state, C, (size_t)ld, iiter, depth BH_ABSENT_LAUNCH);
     }
     return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
 }
+#undef BH_ABSENT_LAUNCH
+
+#if BH_CHAIN_ABSENT
+int bh_chain_propose_sites(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter, const uint8_t *absent)
+{
+    return bh_chain_propose_window_sites(stream, cfg, state, C, iiter, 1, C, absent);
+}
+#else
 
 int bh_chain_accept_window(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter, int depth,
                            ptrdiff_t ld, const double *logL, const double *misfits)
@@ -664,5 +706,7 @@ int bh_chain_accept(void *stream, const bh_chain_config *cfg, const bh_chain_sta
 {
     return bh_chain_accept_window(stream, cfg, state, C, iiter, 1, C, logL, misfits);
 }
+
+#endif
 
 } // extern "C"

@@ -11,15 +11,30 @@
     const double *y = A.ymod + (size_t)ib * A.ldy;
     double logL = 0.0, joint = 0.0;
     bool failed = false;
+#if !BH_LIKE_MISSING
     for (int t = 0; t < A.nt; ++t) failed = failed || (A.err_t[(size_t)t * A.B + ib] != 0);
+#endif
     int site = 0;
     if (SITES) { // the workgroup's model: a scalar load
         site = S.site[ib];
         failed = failed || site < 0 || site >= S.nsites;
     }
+#if BH_LIKE_MISSING
+    // BH_LIKE_MISSING (like_kernel_m.hip): a target the model's site lacks (count 0) is no part of the model's likelihood -- its
+    // failure flag is not read (the forward kernels leave it alone; a model with absurd values would set it), it is skipped below
+    const bool on_table = !failed;
+    for (int t = 0; t < A.nt && on_table; ++t)
+        failed = failed || (S.n[(size_t)site * A.nt + t] != 0 && A.err_t[(size_t)t * A.B + ib] != 0);
+#endif
     for (int t = 0; t < A.nt && !failed; ++t) {
         const LikeTargetDev T = SITES ? site_target(A.t[t], S, site, A.ldy, A.nt, t) : A.t[t];
         const int n = T.n;
+#if BH_LIKE_MISSING
+        if (n == 0) { // the site lacks this target (uniform over the model's lanes): nothing read, nothing added, misfit 0
+            if (tid == 0) A.misfits[(size_t)ib * (A.nt + 1) + t] = 0.0;
+            continue;
+        }
+#endif
         const double *ym = y + T.off;
         const double corr = A.noise[(size_t)ib * 2 * A.nt + 2 * t];
         const double sigma = A.noise[(size_t)ib * 2 * A.nt + 2 * t + 1];
@@ -99,7 +114,12 @@
     if (tid == 0) {
         if (failed) { // Targets.py:325-328
             A.logL[ib] = -1e15;
+#if BH_LIKE_MISSING
+            for (int t = 0; t <= A.nt; ++t) // (a target the site lacks keeps its 0)
+                A.misfits[(size_t)ib * (A.nt + 1) + t] = (t < A.nt && on_table && S.n[(size_t)site * A.nt + t] == 0) ? 0.0 : 1e15;
+#else
             for (int t = 0; t <= A.nt; ++t) A.misfits[(size_t)ib * (A.nt + 1) + t] = 1e15;
+#endif
             A.err[ib] = 1;
         } else {
             A.logL[ib] = logL;

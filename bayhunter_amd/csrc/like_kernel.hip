@@ -16,6 +16,11 @@
 #define BH_HD __device__ __forceinline__
 #define BH_TAB static __device__ const
 #include "bh_libm.h"
+// BH_LIKE_MISSING (like_kernel_m.hip): the builds for sites that lack some of the targets (bh_sites_set_missing,
+// include/bh_engine_sites_missing.h) -- the two kernels of the site-count table with a count of 0 skipped -- and their launcher only.
+#ifndef BH_LIKE_MISSING
+#define BH_LIKE_MISSING 0
+#endif
 
 namespace {
 
@@ -49,6 +54,7 @@ __device__ __forceinline__ LikeTargetDev site_target(LikeTargetDev T, const Like
     return T;
 }
 
+#if !BH_LIKE_MISSING
 __global__ __launch_bounds__(256) void like_kernel(LikeKernelArgs A)
 {
     constexpr bool SITES = false;
@@ -126,19 +132,35 @@ __global__ void probe_kernel(int op, int n, const double *in, double *out)
     out[i] = r;
 }
 
+#else
+// the kernels of the site-count table where a count may be 0: that target is skipped (like_body.inc, like_small_body.inc)
+__global__ __launch_bounds__(256) void like_sites_m_kernel(LikeKernelArgs A, LikeSiteXArgs S)
+{
+    constexpr bool SITES = true;
+#include "like_body.inc"
+}
+__global__ __launch_bounds__(256) void like_small_sites_m_kernel(LikeKernelArgs A, LikeSiteXArgs S)
+{
+    constexpr bool SITES = true;
+#include "like_small_body.inc"
+}
+#endif
+
 } // namespace
 
+#if BH_LIKE_MISSING
+void bh_launch_like_sites_m(const LikeKernelArgs &a, const LikeSiteXArgs &sites, hipStream_t stream)
+{
+    size_t lds = 0;
+    const bool small = bh_like_small_form(a, &lds);
+    if (small) hipLaunchKernelGGL(like_small_sites_m_kernel, dim3((a.B + 3) / 4), dim3(256), 0, stream, a, sites);
+    else hipLaunchKernelGGL(like_sites_m_kernel, dim3(a.B), dim3(256), lds, stream, a, sites);
+}
+#else
 static void launch_like(const LikeKernelArgs &a, const LikeSiteArgs *sites, hipStream_t stream, const LikeSiteXArgs *sx = nullptr)
 {
     size_t lds = 0;
-    for (int t = 0; t < a.nt; ++t)
-        if (a.t[t].law == 3 && a.t[t].quad == nullptr && (size_t)a.t[t].n * sizeof(double) > lds)
-            lds = (size_t)a.t[t].n * sizeof(double);
-    // every target fits one wavefront -- or comes with its sums already formed by the forward kernel (a receiver function's fused
-    // likelihood: nothing of its trace is read here) -- and a Gauss law has its slab sums from the MFMA contraction
-    bool small = true;
-    for (int t = 0; t < a.nt; ++t)
-        small = small && (a.t[t].n <= 64 || (a.t[t].pre != nullptr && a.t[t].law != 3)) && !(a.t[t].law == 3 && a.t[t].quad == nullptr);
+    const bool small = bh_like_small_form(a, &lds); // (bh_device.h: shared with like_kernel_m.hip)
     if (sx != nullptr) { // (n = the capacity of the target's columns: a site's own count is at most that)
         if (small) hipLaunchKernelGGL(like_small_sites_x_kernel, dim3((a.B + 3) / 4), dim3(256), 0, stream, a, *sx);
         else hipLaunchKernelGGL(like_sites_x_kernel, dim3(a.B), dim3(256), lds, stream, a, *sx);
@@ -161,3 +183,4 @@ void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t s
 {
     hipLaunchKernelGGL(probe_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, op, n, in, out);
 }
+#endif

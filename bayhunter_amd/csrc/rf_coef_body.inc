@@ -131,6 +131,9 @@
     // carries the flag instead of relying on the propagation
     if (nf != 0.0) bad = 1.0;
     if (SITES && off_table) bad = 1.0;
+#if BH_RF_MISSING
+    if (SITES && !off_table && S.n[(size_t)S.site[ib] * S.ld] == 0) bad = 2.0; // the model's site lacks this target: absent, not bad
+#endif
     rec[0] = (double)nlay; rec[1] = p; rec[2] = do_decomp; rec[3] = bad;
     rec[4] = m11; rec[5] = m12; rec[6] = m21; rec[7] = m22;
     rec[REC_HEAD + 40 * (size_t)Lmax] = (im == 0.0) ? 1.0 : 0.0;

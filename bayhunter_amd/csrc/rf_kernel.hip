@@ -25,8 +25,19 @@
 #include "bh_tuning.h"
 #include <cmath>
 #include <cstdlib>
+// BH_RF_MISSING (rf_kernel_m.hip): the builds for sites that lack a receiver-function target (bh_sites_set_missing,
+// include/bh_engine_sites_missing.h) -- the site-indexed coefficient kernels, which mark the record of such a model absent, the
+// synthesis kernels, whose workgroup leaves on that mark, and their launcher bh_launch_rf_m; nothing else of this file.
+#ifndef BH_RF_MISSING
+#define BH_RF_MISSING 0
+#endif
 
 namespace {
+#if BH_RF_MISSING
+typedef RfSiteMArgs RfSiteT; // (with the count of every site for the target: RfSiteMArgs::n)
+#else
+typedef RfSiteArgs RfSiteT;
+#endif
 // w / a beyond which the Gauss low-pass exp(-(w/a)^2 / 4) is below RF_CUT = 1e-17: 2 sqrt(17 ln 10)
 constexpr double RF_CUT_WA = 12.5132;
 
@@ -375,13 +386,15 @@ __device__ __forceinline__ cd rf_one_frequency(const double *__restrict__ rec, i
 }
 
 // The coefficient record, one lane per model (body: rf_coef_body.inc; SITES: the site-indexed p and nsv of bh_sites_set_rf)
+#if !BH_RF_MISSING
 __global__ __launch_bounds__(256) void rf_coef_kernel(RfKernelArgs A)
 {
     constexpr bool SITES = false;
     const RfSiteArgs S{};
 #include "rf_coef_body.inc"
 }
-__global__ __launch_bounds__(256) void rf_coef_sites_kernel(RfKernelArgs A, RfSiteArgs S)
+#endif
+__global__ __launch_bounds__(256) void rf_coef_sites_kernel(RfKernelArgs A, RfSiteT S)
 {
     constexpr bool SITES = true;
 #include "rf_coef_body.inc"
@@ -394,7 +407,7 @@ __global__ __launch_bounds__(256) void rf_coef_sites_kernel(RfKernelArgs A, RfSi
 // direct-wave delay is summed by the model's first lane in layer order.  (The Nyquist bin is the synthesis kernel's.)
 // SITES: as in rf_coef_body.inc -- p becomes a value per model (with LP = 16 a wavefront holds four models); the first lane reads nsv.
 template <int LP, bool SITES>
-__device__ __forceinline__ void rf_coef_layers_body(const RfKernelArgs &A, const RfSiteArgs &S)
+__device__ __forceinline__ void rf_coef_layers_body(const RfKernelArgs &A, const RfSiteT &S)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int ibr = t / LP, l = t % LP, lane = threadIdx.x & 63, lbase = lane - l;
@@ -528,19 +541,24 @@ __device__ __forceinline__ void rf_coef_layers_body(const RfKernelArgs &A, const
         nfall += nonfinite(ru) + nonfinite(hm);
         if (nfall != 0.0) bad = 1.0;
         if (SITES && off_table) bad = 1.0;
+#if BH_RF_MISSING
+        if (SITES && !off_table && S.n[(size_t)site * S.ld] == 0) bad = 2.0; // the model's site lacks this target: absent, not bad
+#endif
         rec[0] = (double)nlay; rec[1] = p; rec[2] = do_decomp; rec[3] = bad;
         rec[4] = m11; rec[5] = m12; rec[6] = m21; rec[7] = m22;
         rec[REC_HEAD + 40 * (size_t)Lmax] = (imall + imag_mass(ru) == 0.0 && nfall == 0.0) ? 1.0 : 0.0;
     }
 }
 
+#if !BH_RF_MISSING
 template <int LP>
 __global__ __launch_bounds__(256) void rf_coef_layers_kernel(RfKernelArgs A)
 {
     rf_coef_layers_body<LP, false>(A, RfSiteArgs{});
 }
+#endif
 template <int LP>
-__global__ __launch_bounds__(256) void rf_coef_layers_sites_kernel(RfKernelArgs A, RfSiteArgs S)
+__global__ __launch_bounds__(256) void rf_coef_layers_sites_kernel(RfKernelArgs A, RfSiteT S)
 {
     rf_coef_layers_body<LP, true>(A, S);
 }
@@ -548,13 +566,15 @@ __global__ __launch_bounds__(256) void rf_coef_layers_sites_kernel(RfKernelArgs 
 // the start gate, when two dispersion wavefronts of 208 registers sit on every SIMD -- the 124-register build could
 // only start where such wavefronts have ended (3.4 ms later), right before the synthesis kernel that waits for it; this
 // one becomes resident beside them and is long done when the first synthesis workgroup finds room.
+#if !BH_RF_MISSING
 template <int LP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void rf_coef_layers_kernel_small(RfKernelArgs A)
 {
     rf_coef_layers_body<LP, false>(A, RfSiteArgs{});
 }
+#endif
 template <int LP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void rf_coef_layers_sites_kernel_small(RfKernelArgs A, RfSiteArgs S)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void rf_coef_layers_sites_kernel_small(RfKernelArgs A, RfSiteT S)
 {
     rf_coef_layers_body<LP, true>(A, S);
 }
@@ -588,6 +608,15 @@ __device__ __forceinline__ void rf_synth_body(const RfKernelArgs &A, int logm, i
     double2 *tw1 = tw0 + 64;                               // [max(1, N/128)]  w^(64 q)
     const int ib = blockIdx.x;
     const int nthr = blockDim.x; // 256 (four wavefronts) or 128
+#if BH_RF_MISSING
+    // The model's site lacks this target (the coefficient stage's mark; uniform over the workgroup, read before any barrier):
+    // its columns are zeros and the workgroup leaves -- no recursion, no transform.  (A site call writes the trace, never the sums.)
+    if (A.coef[(size_t)ib * rec_doubles(A.Lmax) + 3] == 2.0) {
+        double *zero = A.rf + (size_t)ib * A.ldr;
+        for (int i = (int)threadIdx.x; i < A.nkeep; i += nthr) zero[i] = 0.0;
+        return;
+    }
+#endif
     // Which wavefront takes the bins of the last, partly filled pass rotates with the workgroup (553 bins are 3 + 2 + 2 + 2
     // passes of 64 lanes: without the rotation the same hardware wave slot of every workgroup carries the third pass)
     const int rot = (blockIdx.x * 64) & (nthr - 1);
@@ -717,6 +746,12 @@ __device__ __forceinline__ void rf_synth_body(const RfKernelArgs &A, int logm, i
 }
 // Two register budgets of the same text: 4 wavefronts per SIMD (128 VGPRs, a few spilled) and 3 (168, none);
 // bh_launch_rf picks (BH_RF_WAVES overrides, for measurements).
+#if BH_RF_MISSING
+// (the builds whose workgroup leaves when its record is marked absent: names of their own, for kernel traces)
+#define rf_synth_kernel rf_synth_m_kernel
+#define rf_synth_kernel_w3 rf_synth_m_kernel_w3
+#define rf_synth_kernel_long rf_synth_m_kernel_long
+#endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void rf_synth_kernel(RfKernelArgs A, int logm, int jcut)
 {
     rf_synth_body<false>(A, logm, jcut);
@@ -731,6 +766,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     rf_synth_body<true>(A, logm, jcut);
 }
 
+#if !BH_RF_MISSING
 // Probe of the elementary functions above (bh_probe_math ops 11-16): the same inlined text, built with this file's flags,
 // so that the tests measure the very functions the synthesis kernel calls.  csqrt_f reads and writes pairs (re, im).
 __global__ __launch_bounds__(256) void rf_probe_kernel(int op, int n, const double *__restrict__ in, double *__restrict__ out)
@@ -755,8 +791,11 @@ __global__ __launch_bounds__(256) void rf_probe_kernel(int op, int n, const doub
     }
 }
 
+#endif
+
 } // namespace
 
+#if !BH_RF_MISSING
 int bh_launch_rf_probe(int op, int n, const double *in, double *out, hipStream_t stream)
 {
     if (op < 11 || op > 16 || (op == 16 && (n & 1))) return -1;
@@ -771,8 +810,17 @@ size_t bh_rf_lds_bytes(int nsamp)
     return (size_t)(nsamp / 2) * 16 + 16 + 64 * 16 + (size_t)(nsamp >= 128 ? nsamp / 128 : 1) * 16;
 }
 
+#endif
+
+#if BH_RF_MISSING
+int bh_launch_rf_m(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteMArgs &msites)
+#else
 int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs *sites)
+#endif
 {
+#if BH_RF_MISSING
+    const RfSiteMArgs *sites = &msites; // (this build has site kernels only)
+#endif
     RfKernelArgs a = a_in;
     const BhTuning &tun = bh_tuning(); // (experiment switches, bh_tuning.h)
     a.no_realc = tun.rf_no_realc != 0 ? 1 : 0;
@@ -795,7 +843,7 @@ int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs 
         if (!bh_allow_big_lds(&allowed, k, 2, (int)BH_RF_MAX_LDS)) return -1;
     }
     if (sites) { // (the same choice of build, each with its site variant)
-        const RfSiteArgs s = *sites;
+        const RfSiteT s = *sites;
         if (a.Lmax <= 16 && a.coef_small)
             hipLaunchKernelGGL((rf_coef_layers_sites_kernel_small<16>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a, s);
         else if (a.Lmax <= 32 && a.coef_small)
@@ -806,7 +854,9 @@ int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs 
             hipLaunchKernelGGL((rf_coef_layers_sites_kernel<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a, s);
         else
             hipLaunchKernelGGL(rf_coef_sites_kernel, dim3((a.B + 255) / 256), dim3(256), 0, stream, a, s);
-    } else if (a.Lmax <= 16 && a.coef_small)
+    }
+#if !BH_RF_MISSING
+    else if (a.Lmax <= 16 && a.coef_small)
         hipLaunchKernelGGL((rf_coef_layers_kernel_small<16>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a);
     else if (a.Lmax <= 32 && a.coef_small)
         hipLaunchKernelGGL((rf_coef_layers_kernel_small<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a);
@@ -816,6 +866,7 @@ int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs 
         hipLaunchKernelGGL((rf_coef_layers_kernel<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL(rf_coef_kernel, dim3((a.B + 255) / 256), dim3(256), 0, stream, a);
+#endif
     // Spectral cut-off.  Every bin carries the Gauss low-pass exp(-w^2 / (4 a^2)) (greens.cpp:343-398); where that
     // factor is below RF_CUT = 1e-17 the bin is below 1e-17 of the pass band (|R/Z| is of order one): a tenth of the
     // rounding unit (2^-53 = 1.1e-16) of the sums the transform forms, i.e. it is lost in the reference's own additions.

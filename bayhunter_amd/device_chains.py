@@ -42,7 +42,7 @@ import numpy as np
 from .chains import ChainBatch, DEFAULT_INITPARAMS, DEFAULT_PRIORS, _is_fixed
 from .engine import BH_CHAIN_MAXDEPTH, BH_CHAIN_MAXLAYERS, ChainConfig, ChainState, EngineError
 from .Targets import JointTarget
-from .sites import SiteTargets, window_site_map
+from .sites import SiteTargets, gather_slots, scatter_slots, window_site_map
 
 
 def auto_spec_depth(nchains, budget=None):
@@ -100,7 +100,10 @@ class DeviceChains(object):
         site s is chain s*nchains + c (plus chain_offset) and walks exactly the trajectory of a one-site
         DeviceChains(site s, nchains, chain_offset=s*nchains) with the same seed; every model of a window is compared with
         its own site's data (Engine.evaluate_sites_dev).  Tempering ladders must lie within one site; `dist` is refused
-        (spread sites over GPUs by giving each process its own sites)."""
+        (spread sites over GPUs by giving each process its own sites).  SiteTargets(missing=True): a site's chains walk the
+        one-site run over the targets the site HAS -- the noise parameters of a slot it lacks are never proposed (a mask per
+        chain goes to the proposal kernels) --, `samples(site=s)` and the saved files hold the noise and misfit columns of
+        the site's own targets; `samples()` of all chains is in the slot layout."""
         import torch
         self.torch = torch
         self.sites = targets if isinstance(targets, SiteTargets) else None
@@ -162,9 +165,20 @@ class DeviceChains(object):
                             arith=self.arith if self.arith is not None else self.targets.engine.swd_arith(),
                             trials=self.TRIALS)   # (the windows' count: the initial likelihoods are the windows' bits)
                  for s in range(self.nsites)]
-        self.noisepriors = hosts[0].noisepriors
-        if any(h.noisepriors != self.noisepriors for h in hosts):
-            raise EngineError("the sites' noise priors differ")
+        self.present = None if self.sites is None or not self.sites.missing else self.sites.present
+        if self.present is None:
+            self.noisepriors = hosts[0].noisepriors
+            if any(h.noisepriors != self.noisepriors for h in hosts):
+                raise EngineError("the sites' noise priors differ")
+        else:   # slot by slot, among the sites that have the slot (a site's own list holds its present targets' only)
+            self.noisepriors = [None] * (2 * self.nt)
+            for s, h in enumerate(hosts):
+                for j, i in enumerate(np.flatnonzero(self.present[s])):
+                    for k in (0, 1):
+                        if self.noisepriors[2 * i + k] is None:
+                            self.noisepriors[2 * i + k] = h.noisepriors[2 * j + k]
+                        elif self.noisepriors[2 * i + k] != h.noisepriors[2 * j + k]:
+                            raise EngineError("the sites' noise priors differ")
         host_chains = [ch for h in hosts for ch in h.chains]
         self.targets._register()  # constant target data + laws (+ the site table) live on the device from here on
 
@@ -208,8 +222,10 @@ class DeviceChains(object):
             n = m.size // 2
             n0[c] = n
             vs0[:n, c], z0[:n, c] = m[:n], m[n:]
-            noise0[:, c] = ch.currentnoise
-            mis0[:, c] = ch.currentmisfits
+            if self.present is None:
+                noise0[:, c], mis0[:, c] = ch.currentnoise, ch.currentmisfits
+            else:   # the site's own layout into the slot layout
+                noise0[:, c], mis0[:, c] = scatter_slots(self.present[c // self.C_site], ch.currentnoise, ch.currentmisfits)
             like0[c], vpvs0[c] = ch.currentlikelihood, ch.currentvpvs
             pd0[:, c] = ch.propdist
         t["n"] = torch.from_numpy(n0).to(dev)
@@ -229,6 +245,11 @@ class DeviceChains(object):
                     if np.unique(of[self.ladder == lid]).size > 1:
                         raise EngineError("tempering ladder %d spans sites: every ladder must lie within one site" % lid)
             self.site_map = torch.from_numpy(window_site_map(self.C_site, self.nsites, self.ld)).to(dev)
+        # (missing=True) per chain, bit i set: the chain's site lacks slot i -- its noise parameters are not free there
+        self.absent = None
+        if self.present is not None:
+            bits = ((~self.present).astype(np.int64) << np.arange(nt)).sum(axis=1).astype(np.uint8)
+            self.absent = torch.from_numpy(np.repeat(bits, self.C_site)).to(dev)
         ld = self.ld                                      # node j of chain c in column j*C + c
         for k in ("pn", "move", "valid", "lay_n"):
             t[k] = torch.zeros(ld, **i32)
@@ -288,7 +309,8 @@ class DeviceChains(object):
                 self._hint = int(self.torch.ceil(t["n"].double().mean()).item())
         w = self.window()
         B = Cn * ((1 << w) - 1)
-        e.chain_propose_window(self.cfg, self.state, Cn, self.iiter, w, self.ld)
+        e.chain_propose_window(self.cfg, self.state, Cn, self.iiter, w, self.ld,
+                               absent=None if self.absent is None else self.absent.data_ptr())
         e.set_typical_layers(self._hint)       # (for this call only: the engine is shared with other callers)
         prev = e.swd_search() if self.search is not None else None
         if prev is not None and prev != self.search:
@@ -380,6 +402,8 @@ class DeviceChains(object):
         """Thinned samples: dict of arrays with leading axes [nsnap, C]; `models` in the reference's row layout
         [vs_1..vs_n NaN.., z_1..z_n NaN..] (2*maxlayers wide).
         site (SiteTargets): the columns of that site only (its nchains chains; cold_only: its ladders), else all.
+        SiteTargets(missing=True): a site's `noise` and `misfits` are in its OWN layout -- the columns of the targets it has,
+        as its one-site run returns them; without `site` they are in the slot layout (0 where a site lacks the slot).
         gather: all chains of a sharded job (global chain order) instead of this rank's, on every rank.
         cold_only (tempered runs): one column per LADDER -- at every snapshot the state of the chain holding
         beta = 1; implies gather (the cold chain of a ladder moves between chains, hence between ranks);
@@ -407,7 +431,10 @@ class DeviceChains(object):
                 raise EngineError("samples(site=...) needs DeviceChains over SiteTargets")
             if not 0 <= int(site) < self.nsites:
                 raise IndexError("site %d of %d" % (site, self.nsites))
-            return self._site_block(out, int(site), phase, cold_only, gather)
+            out = self._site_block(out, int(site), phase, cold_only, gather)
+            if self.present is not None:
+                out["noise"], out["misfits"] = gather_slots(self.present[int(site)], out["noise"], out["misfits"])
+            return out
         if not (gather or cold_only):
             return out
         from .parallel import gather_chain_axis, cold_samples

@@ -149,6 +149,9 @@ def load_library():
     L.bh_sites_set_rf.argtypes = [vp, C.c_int, vp, vp]
     L.bh_sites_set_x.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_sites_set_x_all.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.bh_sites_set_missing.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.bh_chain_propose_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, vp]
+    L.bh_chain_propose_window_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp]
     L.bh_evaluate_sites.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                     C.c_ssize_t, C.c_ssize_t, vp, vp, vp, vp, vp, vp]
     L.bh_chain_propose.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int]
@@ -167,7 +170,8 @@ def load_library():
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
-                 "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all"):
+                 "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all",
+                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites"):
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -196,6 +200,8 @@ SITE_RF_SYMBOLS = ("bh_sites_set_rf",)
 SITE_X_SYMBOLS = ("bh_sites_set_x",)
 # include/bh_engine_sites_x_all.h: ... on every dispersion target (group velocities, higher modes)
 SITE_X_ALL_SYMBOLS = ("bh_sites_set_x_all",)
+# include/bh_engine_sites_missing.h: sites that lack some of the targets
+SITE_MISSING_SYMBOLS = ("bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites")
 # include/bh_engine_posterior.h: posterior velocity-depth summaries of many sites (bayhunter_amd/posterior.py)
 POSTERIOR_SYMBOLS = ("bh_posterior_create", "bh_posterior_destroy", "bh_posterior_load", "bh_posterior_columns",
                      "bh_posterior_hist", "bh_posterior_interfaces")
@@ -564,6 +570,12 @@ class Engine(object):
         targets may differ from site to site in their periods and counts as well; same arrays, same lifetime."""
         self._set_sites_x(self._L.bh_sites_set_x_all, n, x, yobs, yerr)
 
+    def set_sites_missing(self, n, x, yobs, yerr=None):
+        """set_sites_x_all where a count may be 0: that site lacks that target (bh_sites_set_missing) -- nothing of it is
+        computed, read or added for the site's models.  Same arrays, same lifetime; with a receiver-function target
+        set_sites_rf must follow."""
+        self._set_sites_x(self._L.bh_sites_set_missing, n, x, yobs, yerr)
+
     def _set_sites_x(self, entry, n, x, yobs, yerr):
         """set_sites_x / set_sites_x_all: the arrays checked and handed to entry point `entry`"""
         n = np.ascontiguousarray(n, dtype=np.int32)
@@ -678,8 +690,13 @@ class Engine(object):
         if rc != BH_OK:
             raise EngineError("bh_chain_accept failed (%d)" % rc)
 
-    def chain_propose_window(self, cfg, state, C_, iiter, depth, ld):
-        rc = self._L.bh_chain_propose_window(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth), int(ld))
+    def chain_propose_window(self, cfg, state, C_, iiter, depth, ld, absent=None):
+        """absent: None, or the device pointer of uint8 [C] -- bit t set: the chain's site lacks target t (bh_chain_propose_window_sites)"""
+        if absent is not None:
+            rc = self._L.bh_chain_propose_window_sites(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth),
+                                                       int(ld), absent)
+        else:
+            rc = self._L.bh_chain_propose_window(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth), int(ld))
         if rc != BH_OK:
             raise EngineError("bh_chain_propose_window failed (%d)" % rc)
 

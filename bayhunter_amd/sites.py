@@ -9,7 +9,10 @@ near-surface velocity nsv of the receiver functions may differ between sites as 
 include/bh_engine_sites_rf.h): they enter only the coefficient stage of the forward model.  So may the periods of the
 dispersion curves and their number (per_site_x=True, include/bh_engine_sites_x.h): every model is then searched at the
 periods of its own site, as a one-site run searches it.  per_site_x="all" extends that from fundamental-mode phase
-velocities to every dispersion target -- group velocities and higher modes (include/bh_engine_sites_x_all.h).
+velocities to every dispersion target -- group velocities and higher modes (include/bh_engine_sites_x_all.h).  And a station need
+not have every target of the array (missing=True, include/bh_engine_sites_missing.h): the targets become SLOTS, a site gives None
+in the slots it lacks, and each of its models is evaluated -- and each of its chains walks -- as in a one-site run over the targets
+the site has.
 """
 import numpy as np
 
@@ -27,6 +30,36 @@ def window_site_map(nchains, nsites, ld):
     C = nsites * nchains chains, site s holding chains s*nchains .. (s+1)*nchains - 1): int32 [ld]."""
     C = int(nsites) * int(nchains)
     return ((np.arange(int(ld), dtype=np.int64) % C) // int(nchains)).astype(np.int32)
+
+
+# what the noise entries of a slot a site lacks hold in the slot layout (never proposed, never checked, never read)
+ABSENT_NOISE = 0.0
+
+
+def slot_columns(present):
+    """The columns of a site's OWN layout inside the slot layout, from its row `present[nslots]` of booleans: (noise columns --
+    two per present slot, in order --, misfit columns -- one per present slot, then the joint misfit's)."""
+    present = np.asarray(present, dtype=bool)
+    idx = np.flatnonzero(present)
+    return np.column_stack((2 * idx, 2 * idx + 1)).ravel(), np.concatenate((idx, [present.size]))
+
+
+def scatter_slots(present, noise, misfits):
+    """A site's own noise[..., 2k] and misfits[..., k + 1] (k = the targets it has) in the slot layout: (noise[..., 2 nslots] with
+    ABSENT_NOISE in the slots it lacks, misfits[..., nslots + 1] with 0 there); the joint misfit stays last."""
+    ncol, mcol = slot_columns(present)
+    noise, misfits = np.asarray(noise, dtype=float), np.asarray(misfits, dtype=float)
+    nslots = np.asarray(present).size
+    on = np.full(noise.shape[:-1] + (2 * nslots,), ABSENT_NOISE)
+    om = np.zeros(misfits.shape[:-1] + (nslots + 1,))
+    on[..., ncol], om[..., mcol] = noise, misfits
+    return on, om
+
+
+def gather_slots(present, noise, misfits):
+    """The inverse of scatter_slots: the site's own columns of noise[..., 2 nslots] and misfits[..., nslots + 1]."""
+    ncol, mcol = slot_columns(present)
+    return np.asarray(noise)[..., ncol], np.asarray(misfits)[..., mcol]
 
 
 def _bits(a):
@@ -57,9 +90,24 @@ class SiteTargets(object):
     per_site_x="all": as True, for EVERY dispersion target -- phase or group velocity, modes 1 to 3, Rayleigh or Love, flat or
     flattened: group-velocity and higher-mode targets may differ in their periods and their number as well (a station's group
     curve has its own usable band just as its phase curve has).  A group velocity's two roots per period and the mode loop
-    are searched at the model's own site's periods -- the bits of a one-site run.  Receiver functions still share x."""
+    are searched at the model's own site's periods -- the bits of a one-site run.  Receiver functions still share x.
 
-    def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False):
+    missing=True (needs per_site_x="all"): a site may LACK some of the array's targets.  Every site is then a sequence of the
+    same length, target or None: position i is SLOT i, which has one class, one plugin parameter set and one noise law wherever
+    it is present (the checks above, among the sites that have it); every slot is present at one site or more and every site has
+    one target or more.  `ntargets` and `targets` describe the slots (a slot's descriptor is that of the first site that has
+    it), noise and misfits of `evaluate_batch` are in the slot layout; `site(s)` is the JointTarget of the targets site s HAS --
+    the one-site run its models and chains reproduce.  For a slot the model's site lacks nothing is added to logL or the joint
+    misfit, its misfit is 0, it never sets err, its synthetics are zeros and its forward model is not run.  Refused: the Gauss
+    law on a slot that some site lacks (the contraction gathers every site's rows)."""
+
+    def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False, missing=False):
+        self.missing = bool(missing)
+        self._slots = None
+        if self.missing:
+            if per_site_x != "all":
+                raise ValueError("missing=True needs per_site_x=\"all\" (the table of counts it extends)")
+            jointtargets = self._take_slots(jointtargets)
         self._sites = [jt if isinstance(jt, JointTarget) else JointTarget(jt) for jt in jointtargets]
         if not self._sites:
             raise ValueError("SiteTargets needs at least one site")
@@ -76,6 +124,35 @@ class SiteTargets(object):
                 jt._engine = engine
         self._registered = None
 
+    def _take_slots(self, sites):
+        """missing=True: the sites as rows of slots (self._slots[s][i]: target or None), checked for shape; returns every site's
+        present targets"""
+        slots = [list(jt.targets) if isinstance(jt, JointTarget) else list(jt) for jt in sites]
+        if not slots:
+            raise ValueError("SiteTargets needs at least one site")
+        nslots = len(slots[0])
+        for s, row in enumerate(slots):
+            if len(row) != nslots:
+                raise ValueError("site %d gives %d slots, site 0 gives %d (None marks a target the site lacks)" % (s, len(row), nslots))
+            if all(t is None for t in row):
+                raise ValueError("site %d has no target (every slot None)" % s)
+        for i in range(nslots):
+            if all(row[i] is None for row in slots):
+                raise ValueError("slot %d is present at no site" % i)
+        self._slots = slots
+        return [[t for t in row if t is not None] for row in slots]
+
+    @property
+    def present(self):
+        """bool [nsites, ntargets]: site s has the target of slot i (all True without missing=True)"""
+        if self._slots is None:
+            return np.ones((self.nsites, self.ntargets), dtype=bool)
+        return np.array([[t is not None for t in row] for row in self._slots], dtype=bool)
+
+    def _slot_rows(self):
+        """every site's targets by slot (None: the site lacks it)"""
+        return self._slots if self._slots is not None else [jt.targets for jt in self._sites]
+
     # ---- the JointTarget surface the chain drivers use -----------------------------------------------
     @property
     def engine(self):
@@ -88,12 +165,15 @@ class SiteTargets(object):
 
     @property
     def targets(self):
-        """site 0's targets (the target structure every site shares)"""
+        """site 0's targets (the target structure every site shares); missing=True: every slot's target at the first site that
+        has it"""
+        if self._slots is not None:
+            return [next(row[i] for row in self._slots if row[i] is not None) for i in range(len(self._slots[0]))]
         return self._sites[0].targets
 
     @property
     def ntargets(self):
-        return self._sites[0].ntargets
+        return len(self._slots[0]) if self._slots is not None else self._sites[0].ntargets
 
     @property
     def nsites(self):
@@ -104,54 +184,72 @@ class SiteTargets(object):
         return list(self._names)
 
     def site(self, s):
-        """the JointTarget of site s"""
+        """the JointTarget of site s (missing=True: of the targets it has -- the one-site run)"""
         return self._sites[int(s)]
 
     # ---- checks and registration -------------------------------------------------------------------
     def check(self):
-        """Raise ValueError unless every site shares site 0's target structure (class docstring)."""
+        """Raise ValueError unless every site shares site 0's target structure (class docstring); missing=True: unless every
+        slot is one target structure among the sites that have it."""
+        if self._slots is not None:
+            return self._check_slots()
         ref = self._sites[0]
         for s, jt in enumerate(self._sites):
             who = "site %d (%s)" % (s, self._names[s])
             if jt.ntargets != ref.ntargets:
                 raise ValueError("%s has %d targets, site 0 has %d" % (who, jt.ntargets, ref.ntargets))
             for i, (t, t0) in enumerate(zip(jt.targets, ref.targets)):
-                what = "%s, target %d (%s)" % (who, i, t.ref)
-                if not t.engine_backed():
-                    raise ValueError("%s: a user plugin; a site set takes engine-backed targets only" % what)
-                if type(t) is not type(t0):
-                    raise ValueError("%s is a %s, site 0's is a %s" % (what, type(t).__name__, type(t0).__name__))
-                x, x0 = np.asarray(t.obsdata.x, dtype=float), np.asarray(t0.obsdata.x, dtype=float)
-                same_x = x.shape == x0.shape and _bits(x) == _bits(x0)
-                site_x = self.per_site_x and isinstance(t.moddata.plugin, SurfDisp) and isinstance(t0.moddata.plugin, SurfDisp)
-                if not same_x and not site_x:
-                    raise ValueError("%s: x differs from site 0's (sites share x bit for bit)" % what)
-                if site_x:
-                    self._check_site_x(what, t, x, same_x)
-                if np.size(t.obsdata.y) != x.size:
-                    raise ValueError("%s: y has %d values for %d samples" % (what, np.size(t.obsdata.y), x.size))
-                p, p0 = t.moddata.plugin, t0.moddata.plugin
-                if type(p) is not type(p0):
-                    raise ValueError("%s: plugin %s, site 0's is %s" % (what, type(p).__name__, type(p0).__name__))
-                if isinstance(p, SurfDisp):
-                    a = (p.wavetype, p.veltype, p.modelparams["mode"], p.modelparams["flsph"])
-                    a0 = (p0.wavetype, p0.veltype, p0.modelparams["mode"], p0.modelparams["flsph"])
-                    if a != a0:
-                        raise ValueError("%s: dispersion parameters (wave, velocity, mode, flsph) %r, site 0's %r" % (what, a, a0))
-                elif isinstance(p, RFminiModRF):
-                    a, a0 = p._call_args(), p0._call_args()
-                    if self.per_site_rf:
-                        a, a0 = [{k: v for k, v in d.items() if k not in SITE_RF_ARGS} for d in (a, a0)]
-                    if a != a0:
-                        raise ValueError("%s: receiver-function parameters %r, site 0's %r" % (what, a, a0))
-                law, law0 = t.law(), t0.law()
-                if law != law0:
-                    raise ValueError("%s: noise law %r, site 0's %r" % (what, law, law0))
-                if law == "gauss":
-                    v, v0 = t.valuation, t0.valuation
-                    if (np.shape(v.corr_inv) != np.shape(v0.corr_inv) or _bits(v.corr_inv) != _bits(v0.corr_inv)
-                            or _bits(v.logcorr_det) != _bits(v0.logcorr_det)):
-                        raise ValueError("%s: Gauss law with another R^-1 / ln|R| than site 0's (sites share corr)" % what)
+                self._check_target("%s, target %d (%s)" % (who, i, t.ref), t, t0, "site 0")
+
+    def _check_slots(self):
+        """missing=True: the checks of `check` slot by slot, every site that has the slot against the first one that has it"""
+        for i in range(self.ntargets):
+            have = [s for s, row in enumerate(self._slots) if row[i] is not None]
+            t0 = self._slots[have[0]][i]
+            for s in have:
+                t = self._slots[s][i]
+                what = "site %d (%s), slot %d (%s)" % (s, self._names[s], i, getattr(t, "ref", "?"))
+                self._check_target(what, t, t0, "site %d" % have[0])
+                if len(have) < self.nsites and t.law() == "gauss":
+                    raise ValueError("%s: Gauss law on a slot that some site lacks (the contraction gathers every site's rows)" % what)
+
+    def _check_target(self, what, t, t0, whose):
+        """target t (`what`, for the messages) against the target t0 of site `whose` it must share its structure with"""
+        if not t.engine_backed():
+            raise ValueError("%s: a user plugin; a site set takes engine-backed targets only" % what)
+        if type(t) is not type(t0):
+            raise ValueError("%s is a %s, %s's is a %s" % (what, type(t).__name__, whose, type(t0).__name__))
+        x, x0 = np.asarray(t.obsdata.x, dtype=float), np.asarray(t0.obsdata.x, dtype=float)
+        same_x = x.shape == x0.shape and _bits(x) == _bits(x0)
+        site_x = self.per_site_x and isinstance(t.moddata.plugin, SurfDisp) and isinstance(t0.moddata.plugin, SurfDisp)
+        if not same_x and not site_x:
+            raise ValueError("%s: x differs from %s's (sites share x bit for bit)" % (what, whose))
+        if site_x:
+            self._check_site_x(what, t, x, same_x)
+        if np.size(t.obsdata.y) != x.size:
+            raise ValueError("%s: y has %d values for %d samples" % (what, np.size(t.obsdata.y), x.size))
+        p, p0 = t.moddata.plugin, t0.moddata.plugin
+        if type(p) is not type(p0):
+            raise ValueError("%s: plugin %s, %s's is %s" % (what, type(p).__name__, whose, type(p0).__name__))
+        if isinstance(p, SurfDisp):
+            a = (p.wavetype, p.veltype, p.modelparams["mode"], p.modelparams["flsph"])
+            a0 = (p0.wavetype, p0.veltype, p0.modelparams["mode"], p0.modelparams["flsph"])
+            if a != a0:
+                raise ValueError("%s: dispersion parameters (wave, velocity, mode, flsph) %r, %s's %r" % (what, a, whose, a0))
+        elif isinstance(p, RFminiModRF):
+            a, a0 = p._call_args(), p0._call_args()
+            if self.per_site_rf:
+                a, a0 = [{k: v for k, v in d.items() if k not in SITE_RF_ARGS} for d in (a, a0)]
+            if a != a0:
+                raise ValueError("%s: receiver-function parameters %r, %s's %r" % (what, a, whose, a0))
+        law, law0 = t.law(), t0.law()
+        if law != law0:
+            raise ValueError("%s: noise law %r, %s's %r" % (what, law, whose, law0))
+        if law == "gauss":
+            v, v0 = t.valuation, t0.valuation
+            if (np.shape(v.corr_inv) != np.shape(v0.corr_inv) or _bits(v.corr_inv) != _bits(v0.corr_inv)
+                    or _bits(v.logcorr_det) != _bits(v0.logcorr_det)):
+                raise ValueError("%s: Gauss law with another R^-1 / ln|R| than %s's (sites share corr)" % (what, whose))
 
     def _check_site_x(self, what, t, x, same_x):
         """what the engine refuses of a dispersion target registered with periods per site (include/bh_engine_sites_x.h; with
@@ -171,16 +269,19 @@ class SiteTargets(object):
     def site_x_arrays(self):
         """(n[S, nt] int32, x[S, ldy], yobs[S, ldy], yerr[S, ldy] or None) for Engine.set_sites_x: the samples of every (site,
         target) and every site's x, observed data and errors in ymod's column layout, where a target's columns are as many as
-        its largest count over the sites; beyond a site's own count x and yobs hold 0 and yerr 1 (unread)."""
+        its largest count over the sites; beyond a site's own count x and yobs hold 0 and yerr 1 (unread).  missing=True
+        (Engine.set_sites_missing): count 0 and those placeholders throughout for a slot the site lacks."""
         S, nt = self.nsites, self.ntargets
-        n = np.array([[np.size(t.obsdata.x) for t in jt.targets] for jt in self._sites], dtype=np.int32).reshape(S, nt)
+        n = self._counts()
         cap = n.max(axis=0)
         off = np.concatenate([[0], np.cumsum(cap)]).astype(int)
         scaled = any(LAWS[t.law()] == LAWS["nocorr_scalederr"] for t in self.targets)
         x, yobs = np.zeros((S, off[-1])), np.zeros((S, off[-1]))
         yerr = np.ones((S, off[-1])) if scaled else None
-        for s, jt in enumerate(self._sites):
-            for i, t in enumerate(jt.targets):
+        for s, row in enumerate(self._slot_rows()):
+            for i, t in enumerate(row):
+                if t is None:
+                    continue
                 c = slice(off[i], off[i] + n[s, i])
                 x[s, c] = np.asarray(t.obsdata.x, dtype=float).ravel()
                 yobs[s, c] = np.asarray(t.obsdata.y, dtype=float).ravel()
@@ -188,13 +289,18 @@ class SiteTargets(object):
                     yerr[s, c] = np.asarray(t.obsdata.yerr, dtype=float).ravel()
         return n, x, yobs, yerr
 
+    def _counts(self):
+        """int32 [nsites, ntargets]: the samples of every (site, target); 0 where the site lacks the slot"""
+        return np.array([[0 if t is None else np.size(t.obsdata.x) for t in row] for row in self._slot_rows()],
+                        dtype=np.int32).reshape(self.nsites, self.ntargets)
+
     def _capacity_descs(self):
         """site 0's descriptors; a fundamental-mode phase-velocity target's n is the largest count of any site and its x, yobs
         (and yerr) placeholders of that length -- the site path reads the tables, never these.  Group-velocity and higher-mode
         targets keep site 0's x, which every site shares: the engine checks the table against it, and a group velocity's
         second roots are searched at the descriptor's periods.  per_site_x="all": every dispersion target gets the capacity
         and placeholders -- all of them are searched at the table's periods."""
-        n = np.array([[np.size(t.obsdata.x) for t in jt.targets] for jt in self._sites])
+        n = self._counts()
         descs = []
         for i, t in enumerate(self.targets):
             d = t.engine_desc()
@@ -222,9 +328,9 @@ class SiteTargets(object):
         model's top-layer vs) in the columns of its receiver-function targets, 0 elsewhere (Engine.set_sites_rf)"""
         S, nt = self.nsites, self.ntargets
         p, nsv = np.zeros((S, nt)), np.zeros((S, nt))
-        for s, jt in enumerate(self._sites):
-            for i, t in enumerate(jt.targets):
-                if isinstance(t.moddata.plugin, RFminiModRF):
+        for s, row in enumerate(self._slot_rows()):
+            for i, t in enumerate(row):
+                if t is not None and isinstance(t.moddata.plugin, RFminiModRF):
                     a = t.moddata.plugin._call_args()
                     p[s, i], nsv[s, i] = float(a["p"]), float(a["nsv"])
         return p, nsv
@@ -245,7 +351,9 @@ class SiteTargets(object):
         if self._registered != sig or e._owner is not self:
             if self.per_site_x:
                 e.set_targets(self._capacity_descs())
-                if self.per_site_x == "all":
+                if self.missing:
+                    e.set_sites_missing(*self.site_x_arrays())
+                elif self.per_site_x == "all":
                     e.set_sites_x_all(*self.site_x_arrays())
                 else:
                     e.set_sites_x(*self.site_x_arrays())
@@ -253,7 +361,7 @@ class SiteTargets(object):
                 e.set_targets([t.engine_desc() for t in self.targets])
                 yobs, yerr = self.site_arrays()
                 e.set_sites(yobs, yerr)
-            if self.per_site_rf:
+            if self.per_site_rf or self.missing:   # (missing: the coefficient stage finds the model's site through this table)
                 e.set_sites_rf(*self.site_rf_arrays())
             e._owner = self
             self._registered = sig
@@ -261,6 +369,7 @@ class SiteTargets(object):
             self._held = [(t.obsdata.x, t.obsdata.y, t.obsdata.yerr) for jt in self._sites for t in jt.targets]
 
     def evaluate_batch(self, nlay, h, vp, vs, noise, site, rho=None, layout="layer_major", want_ymod=False):
-        """B models, model b compared with site site[b]: returns (logL[B], misfits[B, nt+1], err[B][, ymod])."""
+        """B models, model b compared with site site[b]: returns (logL[B], misfits[B, nt+1], err[B][, ymod]).  missing=True:
+        noise and misfits in the slot layout (`scatter_slots`)."""
         self._register()
         return self.engine.evaluate_sites(nlay, h, vp, vs, noise, site, rho=rho, layout=layout, want_ymod=want_ymod)
