@@ -35,17 +35,45 @@
 #ifndef BH_CHAIN_ABSENT
 #define BH_CHAIN_ABSENT 0
 #endif
-#if BH_CHAIN_ABSENT
+// BH_CHAIN_PRIORS (chain_kernel_p.hip): the builds of all four kernels for chains that run under their own site's priors and
+// sampler settings (include/bh_engine_sites_priors.h) and their entry points only.  They take a table of bh_chain_prior records
+// and prior_of[C]; every station field -- ST.<field>, BH_NLO / BH_NHI below -- is read from the chain's record, which a kernel
+// fetches ONCE per chain at its top: the scalars into registers, the noise bounds (indexed by a loop variable: as a private
+// array they would live in scratch memory) into LDS.  The propose kernels take the absent mask as well (NULL: none absent).
+#ifndef BH_CHAIN_PRIORS
+#define BH_CHAIN_PRIORS 0
+#endif
+#if BH_CHAIN_PRIORS
+#include "../../include/bh_engine_sites_priors.h"
+#define ST pr
+#define BH_NLO(i) pr.nb[(i) * pr.stride]
+#define BH_NHI(i) pr.nb[(2 * BH_MAX_TARGETS + (i)) * pr.stride]
+#define BH_NOISE_FREE(i) (BH_NLO(i) != BH_NHI(i) && ((absent >> ((i) >> 1)) & 1u) == 0u)
+#define BH_PRIOR_OK (!pr.bad)
+#define BH_SITE_PARAM , unsigned absent, const Prior &pr
+#define BH_SITE_ARG(c) , (absent_of != nullptr ? (unsigned)absent_of[c] : 0u), pr
+#define BH_SITE_KPARAM , const uint8_t *absent_of, const bh_chain_prior *priors, int NP, const int32_t *prior_of
+#define BH_ACCEPT_KPARAM , const bh_chain_prior *priors, int NP, const int32_t *prior_of
+#elif BH_CHAIN_ABSENT
 #include "../../include/bh_engine_sites_missing.h"
+#define ST cfg
+#define BH_NLO(i) cfg.noise_lo[i]
+#define BH_NHI(i) cfg.noise_hi[i]
 #define BH_NOISE_FREE(i) (cfg.noise_lo[i] != cfg.noise_hi[i] && ((absent >> ((i) >> 1)) & 1u) == 0u)
-#define BH_ABSENT_PARAM , unsigned absent
-#define BH_ABSENT_ARG(c) , (unsigned)absent_of[c]
-#define BH_ABSENT_KPARAM , const uint8_t *absent_of
+#define BH_PRIOR_OK true
+#define BH_SITE_PARAM , unsigned absent
+#define BH_SITE_ARG(c) , (unsigned)absent_of[c]
+#define BH_SITE_KPARAM , const uint8_t *absent_of
 #else
+#define ST cfg
+#define BH_NLO(i) cfg.noise_lo[i]
+#define BH_NHI(i) cfg.noise_hi[i]
 #define BH_NOISE_FREE(i) (cfg.noise_lo[i] != cfg.noise_hi[i])
-#define BH_ABSENT_PARAM
-#define BH_ABSENT_ARG(c)
-#define BH_ABSENT_KPARAM
+#define BH_PRIOR_OK true
+#define BH_SITE_PARAM
+#define BH_SITE_ARG(c)
+#define BH_SITE_KPARAM
+#define BH_ACCEPT_KPARAM
 #endif
 
 namespace {
@@ -136,6 +164,45 @@ struct Params {
     double vpvs;
     double *vs, *z, *noise, *h;
 };
+#if BH_CHAIN_PRIORS
+// A chain's record as a propose kernel holds it: the scalars by value, the noise bounds in LDS -- entry i of the lower bounds at
+// nb[i * stride], of the upper bounds at nb[(2 BH_MAX_TARGETS + i) * stride] (entry-major: the chains of a wavefront read
+// neighbouring words).  bad: prior_of out of range -- nothing of the table was read, every proposal is invalid.
+struct Prior {
+    int layermin, layermax;
+    double vsmin, vsmax, zmin, zmax, thickmin, lvz, hvz, vpvsmin, vpvsmax, mantle_vs, mantle_vpvs;
+    const double *nb;
+    int stride;
+    bool bad;
+};
+// Fetch record k: the scalars into pr, the noise bounds into nb (entries first, first + step, ..: the lanes of a chain share the
+// copy).  k outside [0, NP): no read of the table; a record under which nothing is free, and pr.bad.
+__device__ __forceinline__ void fetch_prior(Prior &pr, const bh_chain_prior *priors, int NP, int k, double *nb, int stride, int first,
+                                            int step)
+{
+    pr.nb = nb;
+    pr.stride = stride;
+    pr.bad = k < 0 || k >= NP;
+    if (pr.bad) {
+        pr.layermin = pr.layermax = 0;
+        pr.vsmin = pr.vsmax = pr.zmin = pr.zmax = pr.thickmin = pr.vpvsmin = pr.vpvsmax = pr.mantle_vpvs = 0.0;
+        pr.lvz = pr.hvz = pr.mantle_vs = -1.0;
+        for (int i = first; i < 4 * BH_MAX_TARGETS; i += step) nb[i * stride] = 0.0;
+        return;
+    }
+    const bh_chain_prior *__restrict__ r = priors + k;
+    pr.layermin = r->layermin; pr.layermax = r->layermax;
+    pr.vsmin = r->vsmin; pr.vsmax = r->vsmax; pr.zmin = r->zmin; pr.zmax = r->zmax;
+    pr.thickmin = r->thickmin; pr.lvz = r->lvz; pr.hvz = r->hvz;
+    pr.vpvsmin = r->vpvsmin; pr.vpvsmax = r->vpvsmax; pr.mantle_vs = r->mantle_vs; pr.mantle_vpvs = r->mantle_vpvs;
+    for (int i = first; i < 4 * BH_MAX_TARGETS; i += step) // (noise_hi follows noise_lo in the record)
+        nb[i * stride] = i < 2 * BH_MAX_TARGETS ? r->noise_lo[i] : r->noise_hi[i - 2 * BH_MAX_TARGETS];
+}
+// what the accept kernels read of a record
+struct AcceptPrior {
+    double vsmin, vsmax, acc_lo, acc_hi;
+};
+#endif
 // LDS record of one tree node (doubles): [0] n  [1] valid  [2] vp/vs  [3 .. 3+2nt) noise  then vs[ML+1], z[ML+1], h[ML+1]
 __host__ __device__ inline int node_rec_doubles(int nt, int ML) { return 3 + 2 * nt + 3 * (ML + 1); }
 
@@ -219,13 +286,13 @@ __device__ __forceinline__ int nearest_nucleus(const double *__restrict__ z, int
 // iteration `iiter`, into column node*C + c of the proposal arrays (leading dimension ldp).
 // `P` brings the storage; `lds_from` as in load_base.
 __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const bh_chain_state &S, int C, size_t ldp, int c, int iiter,
-                                             int from_node, int node, Params &P, const double *lds_from, bool *valid_out, const Draws &d BH_ABSENT_PARAM)
+                                             int from_node, int node, Params &P, const double *lds_from, bool *valid_out, const Draws &d BH_SITE_PARAM)
 {
     const int ML = cfg.maxlayers, nt = cfg.nt;
     // ---- which modification (SingleChain.py:512-517, :596-599) ---------------------------------
     int nnoise = 0;
     for (int i = 0; i < 2 * nt; ++i) nnoise += BH_NOISE_FREE(i);
-    const bool vpvs_free = cfg.vpvsmin != cfg.vpvsmax;
+    const bool vpvs_free = ST.vpvsmin != ST.vpvsmax;
     const bool early = (double)iiter < (-(double)cfg.iter_burnin + (double)cfg.iterations * 0.01);
     int moves[6], nm = 0;
     moves[nm++] = MV_VS;
@@ -246,7 +313,7 @@ __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const b
     int n = P.n;
     double vpvs = P.vpvs;
     double dvs2 = 0.0;
-    bool valid = true;
+    bool valid = BH_PRIOR_OK;
     if (mv == MV_VS) {
         int ind = (int)(d.u_index * n);
         if (ind >= n) ind = n - 1;
@@ -256,10 +323,14 @@ __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const b
         if (ind >= n) ind = n - 1;
         z[ind] = z[ind] + d.normal * S.propdist[1 * (size_t)C + c];
     } else if (mv == MV_BIRTH) {
-        const double zb = cfg.zmin + d.u_z * (cfg.zmax - cfg.zmin);
+        const double zb = ST.zmin + d.u_z * (ST.zmax - ST.zmin);
         const int near = nearest_nucleus(z, n, zb);
         const double vb = vs[near] + d.normal * S.propdist[2 * (size_t)C + c];
         dvs2 = (vb - vs[near]) * (vb - vs[near]);
+        // (BH_CHAIN_PRIORS: ML is the largest capacity among the call's records.  A chain whose own layermax + 1 is smaller takes
+        // the else branch where its one-site run stops here, and fails `layermodel <= layermax` below instead: valid = 0, the same
+        // move and dvs2 -- computed above, before either check -- and, as for every invalid proposal, the model it started from
+        // reloaded into the lay_* columns.  Its n never exceeds its own capacity, since no such birth is ever accepted.)
         if (n >= ML) valid = false; // would exceed the layer prior anyway
         else {
             vs[n] = vb;
@@ -291,10 +362,10 @@ __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const b
             }
         noise[idx] = noise[idx] + d.normal * S.propdist[3 * (size_t)C + c];
         for (int i = 0; i < 2 * nt; ++i)
-            if (BH_NOISE_FREE(i) && (noise[i] < cfg.noise_lo[i] || noise[i] > cfg.noise_hi[i])) valid = false;
+            if (BH_NOISE_FREE(i) && (noise[i] < BH_NLO(i) || noise[i] > BH_NHI(i))) valid = false;
     } else {
         vpvs = vpvs + d.normal * S.propdist[4 * (size_t)C + c];
-        if (vpvs < cfg.vpvsmin || vpvs > cfg.vpvsmax) valid = false;
+        if (vpvs < ST.vpvsmin || vpvs > ST.vpvsmax) valid = false;
     }
     // nuclei sorted by depth (:315-328); insertion sort is stable like the reference's argsort use
     double ztop = n > 0 ? z[0] : 0.0; // largest depth so far = z[i - 1] once the first i nuclei are in order
@@ -321,7 +392,7 @@ __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const b
     layer_thicknesses(P, h);
     if (valid && (mv <= MV_DEATH)) {
         const int layermodel = n - 1;
-        if (!(layermodel >= cfg.layermin && layermodel <= cfg.layermax)) valid = false;
+        if (!(layermodel >= ST.layermin && layermodel <= ST.layermax)) valid = false;
         // (every layer is looked at, no early exit: the tests have no side effects and the reads can be in flight together)
         const double *__restrict__ rh = h, *__restrict__ rv = vs;
         double zc = 0.0, vi = n > 0 ? rv[0] : 0.0;
@@ -330,13 +401,13 @@ __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const b
         for (int i = 0; i < n; ++i) {
             const double hi = rh[i];
             const double vn = (i + 1 < n) ? rv[i + 1] : 0.0;
-            if (i < n - 1 && hi < cfg.thickmin) ok = false;
-            if (vi < cfg.vsmin || vi > cfg.vsmax) ok = false;
+            if (i < n - 1 && hi < ST.thickmin) ok = false;
+            if (vi < ST.vsmin || vi > ST.vsmax) ok = false;
             zc += hi;
-            if (zc < cfg.zmin || zc > cfg.zmax) ok = false;
+            if (zc < ST.zmin || zc > ST.zmax) ok = false;
             if (i + 1 < n) {
-                if (cfg.lvz >= 0.0 && !(vn - vi * (1 - cfg.lvz) > 0)) ok = false;
-                if (cfg.hvz >= 0.0 && !(vi * (1 + cfg.hvz) - vn > 0)) ok = false;
+                if (ST.lvz >= 0.0 && !(vn - vi * (1 - ST.lvz) > 0)) ok = false;
+                if (ST.hvz >= 0.0 && !(vi * (1 + ST.hvz) - vn > 0)) ok = false;
             }
             vi = vn;
         }
@@ -367,12 +438,12 @@ __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const b
 #pragma unroll 4
         for (int i = 0; i < n; ++i) {
             const double vi = rv[i], zi = rz[i], hi = rh[i];
-            if (cfg.mantle_vs > 0.0 && vi >= cfg.mantle_vs) deep = true;
+            if (ST.mantle_vs > 0.0 && vi >= ST.mantle_vs) deep = true;
             S.pvs[(size_t)i * ldp + col] = vi;
             S.pz[(size_t)i * ldp + col] = zi;
             S.lay_h[(size_t)i * ldp + col] = hi;
             S.lay_vs[(size_t)i * ldp + col] = vi;
-            const double vpi = vi * (deep ? cfg.mantle_vpvs : vpvs);
+            const double vpi = vi * (deep ? ST.mantle_vpvs : vpvs);
             S.lay_vp[(size_t)i * ldp + col] = vpi;
             if (S.lay_rho != nullptr) S.lay_rho[(size_t)i * ldp + col] = vpi * 0.32 + 0.77; // as rho_from_vp_kernel (Targets.py:319)
         }
@@ -381,15 +452,21 @@ __device__ __forceinline__ void propose_node(const bh_chain_config &cfg, const b
 }
 
 // lane = chain, one proposal per chain (depth 1; ldp = C)
-__global__ void chain_propose_kernel(bh_chain_config cfg, bh_chain_state S, int C, int iiter BH_ABSENT_KPARAM)
+__global__ void chain_propose_kernel(bh_chain_config cfg, bh_chain_state S, int C, int iiter BH_SITE_KPARAM)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     double vs[BH_CHAIN_MAXLAYERS + 1], z[BH_CHAIN_MAXLAYERS + 1], h[BH_CHAIN_MAXLAYERS + 1], noise[2 * BH_MAX_TARGETS];
     Params P;
     P.vs = vs; P.z = z; P.h = h; P.noise = noise;
+#if BH_CHAIN_PRIORS
+    // the lane's record: its noise bounds in the lane's own column of nb (written and read by this lane only: no barrier)
+    __shared__ double nb[4 * BH_MAX_TARGETS * 64];
+    Prior pr;
+    fetch_prior(pr, priors, NP, prior_of[c], nb + threadIdx.x, 64, 0, 1);
+#endif
     bool valid;
-    propose_node(cfg, S, C, (size_t)C, c, iiter, -1, 0, P, nullptr, &valid, get_draws(cfg, S, c, C, iiter, 0) BH_ABSENT_ARG(c));
+    propose_node(cfg, S, C, (size_t)C, c, iiter, -1, 0, P, nullptr, &valid, get_draws(cfg, S, c, C, iiter, 0) BH_SITE_ARG(c));
 }
 
 // Speculative window: T = 2^(depth-1) lanes per chain (64 / T chains per single-wavefront workgroup); level k of the
@@ -399,7 +476,7 @@ __global__ void chain_propose_kernel(bh_chain_config cfg, bh_chain_state S, int 
 // levels (round 3, first form: state through global memory and __syncthreads -- 128 us per launch at depth 7, 7 % of a
 // c4 launch).  A workgroup is one wavefront: its LDS operations execute in order, the barrier only pins the compiler.
 __global__ __launch_bounds__(64) void chain_propose_window_kernel(bh_chain_config cfg, bh_chain_state S, int C, size_t ldp,
-                                                                   int iiter, int depth BH_ABSENT_KPARAM)
+                                                                   int iiter, int depth BH_SITE_KPARAM)
 {
     extern __shared__ __align__(16) double tree[];
     const int T = 1 << (depth - 1);
@@ -411,6 +488,18 @@ __global__ __launch_bounds__(64) void chain_propose_window_kernel(bh_chain_confi
     const int nt = cfg.nt, ML = cfg.maxlayers;
     const int RS = node_rec_doubles(nt, ML) | 1; // odd stride: neighbouring nodes start in different banks
     double *mine = tree + (size_t)slot * N * RS;  // this chain's records
+#if BH_CHAIN_PRIORS
+    // The chains of a wavefront can belong to different sites (64 / T of them, site boundaries anywhere): the record is a per-lane
+    // value.  Every lane fetches its chain's scalars; the chain's lanes share the copy of its noise bounds behind the tree.
+    double *nbw = tree + (size_t)per_wg * N * RS;
+    Prior pr;
+    {
+        fetch_prior(pr, priors, NP, c < C ? prior_of[c] : -1, nbw + slot, per_wg, p, T);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+#endif
     // The draws of iteration iiter + k are the same for every node of level k: lane k of the chain computes them (four Philox
     // blocks, a logarithm, a square root and a cosine: 3 us when every level did it for itself, 21 of the kernel's 70 us at
     // depth 7), the level's lanes fetch them.  (2^(depth-1) >= depth: the chain has a lane for every level.)
@@ -440,7 +529,7 @@ __global__ __launch_bounds__(64) void chain_propose_window_kernel(bh_chain_confi
             P.z = P.vs + (ML + 1);
             P.h = P.z + (ML + 1);
             bool valid;
-            propose_node(cfg, S, C, ldp, c, iiter + k, from, node, P, from >= 0 ? mine + (size_t)from * RS : nullptr, &valid, d BH_ABSENT_ARG(c));
+            propose_node(cfg, S, C, ldp, c, iiter + k, from, node, P, from >= 0 ? mine + (size_t)from * RS : nullptr, &valid, d BH_SITE_ARG(c));
             rec[0] = (double)P.n;
             rec[1] = valid ? 1.0 : 0.0;
             rec[2] = P.vpvs;
@@ -454,10 +543,15 @@ __global__ __launch_bounds__(64) void chain_propose_window_kernel(bh_chain_confi
 #if !BH_CHAIN_ABSENT
 // lane = chain: walk the realised path through the window's tree (depth 1: the plain accept step)
 __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C, size_t ldp, int iiter, int depth,
-                                    const double *logL, const double *misfits)
+                                    const double *logL, const double *misfits BH_ACCEPT_KPARAM)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
+#if BH_CHAIN_PRIORS
+    const int rec = prior_of[c];
+    if (rec < 0 || rec >= NP) return; // out of range: nothing of the table is read, the chain's state stays as it was
+    const AcceptPrior pr = {priors[rec].vsmin, priors[rec].vsmax, priors[rec].acc_lo, priors[rec].acc_hi};
+#endif
     const int nt = cfg.nt;
     int node = 0, last = -1;
     double cur = S.like[c];
@@ -475,7 +569,7 @@ __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C
             double alpha;
             if (mv == MV_BIRTH || mv == MV_DEATH) { // Bodin et al. (2012), SingleChain.py:468-485
                 const double theta = S.propdist[2 * (size_t)C + c];
-                const double dv = cfg.vsmax - cfg.vsmin;
+                const double dv = ST.vsmax - ST.vsmin;
                 const double Bt = S.dvs2[col] / (2. * (theta * theta));
                 if (mv == MV_BIRTH) alpha = log((theta * sqrt(2 * M_PI)) / dv) + Bt + dl;
                 else alpha = log(dv / (theta * sqrt(2 * M_PI))) - Bt + dl;
@@ -498,10 +592,10 @@ __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C
                     for (int i = 0; i < 5; ++i) {
                         const double rate = S.accepted[i * (size_t)C + c] / S.proposed[i * (size_t)C + c] * 100;
                         double pd = S.propdist[i * (size_t)C + c];
-                        if (rate < cfg.acc_lo) {
+                        if (rate < ST.acc_lo) {
                             pd = pd * 0.95;
                             if (pd < 0.001) pd = 0.001;
-                        } else if (rate > cfg.acc_hi) {
+                        } else if (rate > ST.acc_hi) {
                             pd = pd * 1.05;
                         }
                         S.propdist[i * (size_t)C + c] = pd;
@@ -520,6 +614,8 @@ __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C
         }
         // rows beyond n are kept at zero: the state arrays are then a function of the trajectory alone, not of how
         // it was cut into windows (only the last accepted proposal of a window is written)
+        // (BH_CHAIN_PRIORS: up to the SHARED capacity, which may exceed the chain's own layermax + 1 -- rows the chain's one-site
+        // run does not have; they hold zeros from the start and nothing reads a row beyond n)
         for (int i = n; i < cfg.maxlayers; ++i) {
             S.vs[(size_t)i * C + c] = 0.0;
             S.z[(size_t)i * C + c] = 0.0;
@@ -538,10 +634,15 @@ __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C
 // evaluation per level (24 -> 9 us at depth 7); the counters of the five proposal types sit in lanes 0..4 and are written
 // back once; the committed model is copied one layer per lane.
 __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config cfg, bh_chain_state S, int C, size_t ldp, int iiter, int depth,
-                                                                  const double *logL, const double *misfits)
+                                                                  const double *logL, const double *misfits BH_ACCEPT_KPARAM)
 {
     const int c = (int)blockIdx.x, lane = (int)threadIdx.x;
     if (c >= C) return;
+#if BH_CHAIN_PRIORS
+    const int rec = prior_of[c]; // a wavefront is one chain: the record is wave-uniform here
+    if (rec < 0 || rec >= NP) return;
+    const AcceptPrior pr = {priors[rec].vsmin, priors[rec].vsmax, priors[rec].acc_lo, priors[rec].acc_hi};
+#endif
     const int nt = cfg.nt, N = (1 << depth) - 1;
     int valid0 = 0, valid1 = 0, mv0 = 0, mv1 = 0;
     double like0 = 0.0, like1 = 0.0, dv0 = 0.0, dv1 = 0.0;
@@ -575,7 +676,7 @@ __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config
             const double dl = (S.beta ? beta * (like - cur) : like - cur);
             double alpha;
             if (mv == MV_BIRTH || mv == MV_DEATH) { // Bodin et al. (2012), SingleChain.py:468-485
-                const double dv = cfg.vsmax - cfg.vsmin;
+                const double dv = ST.vsmax - ST.vsmin;
                 const double Bt = (hi ? db : da) / (2. * (theta * theta));
                 if (mv == MV_BIRTH) alpha = log((theta * sqrt(2 * M_PI)) / dv) + Bt + dl;
                 else alpha = log(dv / (theta * sqrt(2 * M_PI))) - Bt + dl;
@@ -595,10 +696,10 @@ __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config
                 if (all && lane < 5) {
                     const double rate = acc / prop * 100;
                     double pd = S.propdist[lane * (size_t)C + c];
-                    if (rate < cfg.acc_lo) {
+                    if (rate < ST.acc_lo) {
                         pd = pd * 0.95;
                         if (pd < 0.001) pd = 0.001;
-                    } else if (rate > cfg.acc_hi) {
+                    } else if (rate > ST.acc_hi) {
                         pd = pd * 1.05;
                     }
                     S.propdist[lane * (size_t)C + c] = pd;
@@ -634,6 +735,74 @@ __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config
 } // namespace
 
 extern "C" {
+
+#if BH_CHAIN_PRIORS
+static int window_args_ok(const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter, int depth, ptrdiff_t ld,
+                          const bh_chain_prior *priors, int P, const int32_t *prior_of)
+{
+    if (!cfg || !state || C < 0 || cfg->maxlayers > BH_CHAIN_MAXLAYERS || cfg->nt > BH_MAX_TARGETS) return 0;
+    if (depth < 1 || depth > BH_CHAIN_MAXDEPTH || ld < (ptrdiff_t)C * ((1 << depth) - 1)) return 0;
+    if (!priors || !prior_of || P < 1) return 0;
+    for (int k = 0; k + 1 < depth; ++k)
+        if ((iiter + k) % 1000 == 0) return 0; // an adaptation iteration must be the last of its window
+    return 1;
+}
+
+int bh_chain_propose_window_priors(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
+                                   int depth, ptrdiff_t ld, const bh_chain_prior *priors, int P, const int32_t *prior_of,
+                                   const uint8_t *absent)
+{
+    if (!window_args_ok(cfg, state, C, iiter, depth, ld, priors, P, prior_of)) return BH_EINVAL;
+    if (C == 0) return BH_OK;
+    if (depth == 1 && ld == C) {
+        hipLaunchKernelGGL(chain_propose_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, iiter, absent,
+                           priors, P, prior_of);
+    } else {
+        const int per_wg = 64 >> (depth - 1);
+        // the tree, then the noise bounds of the workgroup's chains
+        const size_t lds = ((size_t)per_wg * ((1 << depth) - 1) * (node_rec_doubles(cfg->nt, cfg->maxlayers) | 1) +
+                            (size_t)per_wg * 4 * BH_MAX_TARGETS) * sizeof(double);
+        if (lds > 160 * 1024) return BH_EUNSUPPORTED;
+        if (lds > 64 * 1024) {
+            static std::atomic<unsigned long long> big{0};
+            const void *k[1] = {reinterpret_cast<const void *>(chain_propose_window_kernel)};
+            if (!bh_allow_big_lds(&big, k, 1, 160 * 1024)) return BH_EHIP;
+        }
+        hipLaunchKernelGGL(chain_propose_window_kernel, dim3((C + per_wg - 1) / per_wg), dim3(64), lds, (hipStream_t)stream, *cfg,
+                           *state, C, (size_t)ld, iiter, depth, absent, priors, P, prior_of);
+    }
+    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+}
+
+int bh_chain_propose_priors(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
+                            const bh_chain_prior *priors, int P, const int32_t *prior_of, const uint8_t *absent)
+{
+    return bh_chain_propose_window_priors(stream, cfg, state, C, iiter, 1, C, priors, P, prior_of, absent);
+}
+
+int bh_chain_accept_window_priors(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
+                                  int depth, ptrdiff_t ld, const double *logL, const double *misfits,
+                                  const bh_chain_prior *priors, int P, const int32_t *prior_of)
+{
+    if (!window_args_ok(cfg, state, C, iiter, depth, ld, priors, P, prior_of) || !logL || !misfits) return BH_EINVAL;
+    if (C == 0) return BH_OK;
+    if (depth > 1) // a wavefront per chain
+        hipLaunchKernelGGL(chain_accept_window_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld, iiter, depth,
+                           logL, misfits, priors, P, prior_of);
+    else
+        hipLaunchKernelGGL(chain_accept_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld,
+                           iiter, depth, logL, misfits, priors, P, prior_of);
+    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+}
+
+int bh_chain_accept_priors(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
+                           const double *logL, const double *misfits, const bh_chain_prior *priors, int P,
+                           const int32_t *prior_of)
+{
+    return bh_chain_accept_window_priors(stream, cfg, state, C, iiter, 1, C, logL, misfits, priors, P, prior_of);
+}
+
+#else // the entry points without a table of priors
 
 #if BH_CHAIN_ABSENT
 int bh_chain_propose_window_sites(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
@@ -708,5 +877,7 @@ int bh_chain_accept(void *stream, const bh_chain_config *cfg, const bh_chain_sta
 }
 
 #endif
+
+#endif // BH_CHAIN_PRIORS
 
 } // extern "C"

@@ -40,7 +40,7 @@ import os.path as op
 import numpy as np
 
 from .chains import ChainBatch, DEFAULT_INITPARAMS, DEFAULT_PRIORS, _is_fixed
-from .engine import BH_CHAIN_MAXDEPTH, BH_CHAIN_MAXLAYERS, ChainConfig, ChainState, EngineError
+from .engine import BH_CHAIN_MAXDEPTH, BH_CHAIN_MAXLAYERS, ChainConfig, ChainPrior, ChainState, EngineError
 from .Targets import JointTarget
 from .sites import SiteTargets, gather_slots, scatter_slots, window_site_map
 
@@ -59,11 +59,86 @@ def auto_spec_depth(nchains, budget=None):
     return d
 
 
+# initparams the sites of one run must share: the chains advance in lock step (iter_*), are thinned together (maxmodels), share the
+# Gauss law's R^-1 (rcond) and are saved below one root (savepath).  Every other key, and every modelpriors key, may differ per site.
+SHARED_INITPARAMS = ("iter_burnin", "iter_main", "maxmodels", "rcond", "savepath")
+SITE_INITPARAMS = ("propdist", "acceptance", "thickmin", "lvz", "hvz")
+
+
+def _same(a, b):
+    if a is None or b is None:
+        return a is b
+    return bool(np.array_equal(np.asarray(a), np.asarray(b)))
+
+
+def site_dicts(initparams, modelpriors, nsites, with_sites):
+    """The merged (initparams, modelpriors) of every site and whether any two sites differ in what the sampler reads.
+    Each argument is one dict (or None) for all sites or a sequence of `nsites` dicts; every dict is merged over the defaults.
+    ValueError: a sequence without SiteTargets, of another length than the sites, or sites that differ in a SHARED_INITPARAMS
+    key; EngineError: a site's priors['layers'][1] + 1 beyond BH_CHAIN_MAXLAYERS."""
+    def spread(arg, defaults, what):
+        if isinstance(arg, (list, tuple)):
+            if not with_sites:
+                raise ValueError("a sequence of %s dicts needs SiteTargets (one dict per site)" % what)
+            if len(arg) != nsites:
+                raise ValueError("%d %s dicts for %d sites" % (len(arg), what, nsites))
+            given = list(arg)
+        else:
+            given = [arg] * nsites
+        out = []
+        for g in given:
+            d = dict(defaults)
+            d.update(g or {})
+            out.append(d)
+        return out
+
+    ips = spread(initparams, DEFAULT_INITPARAMS, "initparams")
+    prs = spread(modelpriors, DEFAULT_PRIORS, "modelpriors")
+    for s in range(1, nsites):
+        for key in SHARED_INITPARAMS:
+            if not _same(ips[s].get(key), ips[0].get(key)):
+                raise ValueError("initparams[%r] of site %d is %r, site 0's %r: the sites of one run share it"
+                                 % (key, s, ips[s].get(key), ips[0].get(key)))
+    for s, pr in enumerate(prs):
+        if int(pr["layers"][1]) + 1 > BH_CHAIN_MAXLAYERS:
+            raise EngineError("%spriors['layers'][1] + 1 = %d exceeds BH_CHAIN_MAXLAYERS = %d"
+                              % ("site %d: " % s if with_sites else "", int(pr["layers"][1]) + 1, BH_CHAIN_MAXLAYERS))
+    differ = any(not _same(prs[s].get(k), prs[0].get(k)) for s in range(1, nsites) for k in set(prs[0]) | set(prs[s])) or \
+        any(not _same(ips[s].get(k), ips[0].get(k)) for s in range(1, nsites) for k in SITE_INITPARAMS)
+    return ips, prs, differ
+
+
+def set_station_fields(rec, ip, pr, noisepriors):
+    """Fill the station fields of a ChainConfig or a ChainPrior (they carry the same names) from merged initparams `ip`, merged
+    priors `pr` and the list of noise priors (corr, sigma per target): a fixed prior as lo == hi, None as -1."""
+    rec.layermin, rec.layermax = int(pr["layers"][0]), int(pr["layers"][1])
+    (rec.vsmin, rec.vsmax), (rec.zmin, rec.zmax) = pr["vs"], pr["z"]
+    rec.thickmin = ip["thickmin"]
+    rec.lvz = -1.0 if ip["lvz"] is None else ip["lvz"]
+    rec.hvz = -1.0 if ip["hvz"] is None else ip["hvz"]
+    if _is_fixed(pr["vpvs"]):
+        rec.vpvsmin = rec.vpvsmax = float(pr["vpvs"])
+    else:
+        rec.vpvsmin, rec.vpvsmax = pr["vpvs"]
+    if pr["mantle"] is None:
+        rec.mantle_vs, rec.mantle_vpvs = -1.0, 0.0
+    else:
+        rec.mantle_vs, rec.mantle_vpvs = pr["mantle"]
+    rec.acc_lo, rec.acc_hi = ip["acceptance"]
+    for i, p in enumerate(noisepriors):
+        if _is_fixed(p):
+            rec.noise_lo[i] = rec.noise_hi[i] = float(p)
+        else:
+            rec.noise_lo[i], rec.noise_hi[i] = p
+    return rec
+
+
 class DeviceChains(object):
     TRIALS = 32  # trials per round of the trial-per-lane kernel in every evaluation call of the chains (windows and initial state)
 
     def __init__(self, targets, nchains, initparams=None, modelpriors=None, seed=0, device=None, inject=False,
-                 betas=None, ladder=None, swap_every=0, dist=None, chain_offset=None, spec_depth=None, search="fast", arith="fast"):
+                 betas=None, ladder=None, swap_every=0, dist=None, chain_offset=None, spec_depth=None, search="fast", arith="fast",
+                 prior_table=False):
         """`nchains` chains on THIS rank.  Sharded jobs (one process per GPU, `dist` = an initialised
         torch.distributed): `seed` is the JOB's seed, the same on every rank; the chains are numbered globally
         (`chain_offset` = global index of this rank's first chain, default: ranks own consecutive blocks in rank
@@ -103,10 +178,25 @@ class DeviceChains(object):
         (spread sites over GPUs by giving each process its own sites).  SiteTargets(missing=True): a site's chains walk the
         one-site run over the targets the site HAS -- the noise parameters of a slot it lacks are never proposed (a mask per
         chain goes to the proposal kernels) --, `samples(site=s)` and the saved files hold the noise and misfit columns of
-        the site's own targets; `samples()` of all chains is in the slot layout."""
+        the site's own targets; `samples()` of all chains is in the slot layout.
+        Priors per site: with SiteTargets, `initparams` and `modelpriors` may each be a sequence of one dict per site (each merged
+        over the defaults).  Every modelpriors key and the initparams propdist / acceptance / thickmin / lvz / hvz may differ;
+        SHARED_INITPARAMS must agree (ValueError).  A site's chains then run under the site's own record of a table
+        (include/bh_engine_sites_priors.h) and walk the one-site run made with the site's dicts, bit for bit; the arrays have the
+        rows of the largest `layers` maximum, `samples(site=s)`, the saved chain files and <name>_config.pkl the site's own row
+        width, priors and initparams.  The sites still share every slot's installed noise law (SiteTargets.check).  Sites whose
+        merged dicts agree, or one dict, take the calls without a table exactly as before; prior_table=True forces the table
+        (for measurements).  `self.priors` / `self.initparams` are site 0's; `self.site_priors` / `self.site_initparams` every
+        site's."""
+        self.sites = targets if isinstance(targets, SiteTargets) else None
+        self.nsites = 1 if self.sites is None else self.sites.nsites
+        # (checked before anything touches the GPU)
+        self.site_initparams, self.site_priors, differ = site_dicts(initparams, modelpriors, self.nsites, self.sites is not None)
+        if prior_table and self.sites is None:
+            raise ValueError("prior_table=True needs SiteTargets")
+        self.prior_table = bool(differ or prior_table)
         import torch
         self.torch = torch
-        self.sites = targets if isinstance(targets, SiteTargets) else None
         if self.sites is not None and dist is not None:
             raise EngineError("DeviceChains with SiteTargets does not shard: give each process its own sites instead of dist")
         self.targets = targets if isinstance(targets, (JointTarget, SiteTargets)) else JointTarget(targets)
@@ -124,18 +214,13 @@ class DeviceChains(object):
             device = self.engine.device
         if int(device) != int(self.engine.device):
             raise EngineError("DeviceChains(device=%d) but the targets' engine runs on GPU %d" % (device, self.engine.device))
-        self.priors = dict(DEFAULT_PRIORS)
-        self.priors.update(modelpriors or {})
-        self.initparams = dict(DEFAULT_INITPARAMS)
-        self.initparams.update(initparams or {})
+        self.initparams, self.priors = self.site_initparams[0], self.site_priors[0]
         ip, pr = self.initparams, self.priors
         self.C_site = int(nchains)                        # chains per site (sites: S blocks of them, site after site)
-        self.nsites = 1 if self.sites is None else self.sites.nsites
         self.C = self.C_site * self.nsites
         self.nt = self.targets.ntargets
-        self.ML = int(pr["layers"][1]) + 1
-        if self.ML > BH_CHAIN_MAXLAYERS:
-            raise EngineError("priors['layers'][1] + 1 = %d exceeds BH_CHAIN_MAXLAYERS = %d" % (self.ML, BH_CHAIN_MAXLAYERS))
+        self.site_ML = [int(p["layers"][1]) + 1 for p in self.site_priors]   # a site's own row capacity
+        self.ML = max(self.site_ML)                       # rows of the arrays: the largest
         self.iter_phase1, self.iter_phase2 = int(ip["iter_burnin"]), int(ip["iter_main"])
         self.iterations = self.iter_phase1 + self.iter_phase2
         self.iiter = -self.iter_phase1
@@ -160,13 +245,22 @@ class DeviceChains(object):
         # ---- initial state through the reference-order host code --------------------------------
         # (sites: one ChainBatch per site, on that site's targets, with the seeds of its global chain numbers)
         hosts = [ChainBatch(self.targets if self.sites is None else self.sites.site(s),
-                            chain_seeds(seed, off + s * self.C_site, self.C_site), ip, pr,
+                            chain_seeds(seed, off + s * self.C_site, self.C_site), self.site_initparams[s], self.site_priors[s],
                             search=self.search if self.search is not None else self.targets.engine.swd_search(),
                             arith=self.arith if self.arith is not None else self.targets.engine.swd_arith(),
                             trials=self.TRIALS)   # (the windows' count: the initial likelihoods are the windows' bits)
                  for s in range(self.nsites)]
         self.present = None if self.sites is None or not self.sites.missing else self.sites.present
-        if self.present is None:
+        if self.prior_table:   # per site, in the slot layout; a slot the site lacks: fixed (and masked by `absent`)
+            self.noisepriors = None
+            self.site_noisepriors = []
+            for s, h in enumerate(hosts):
+                have = np.arange(self.nt) if self.present is None else np.flatnonzero(self.present[s])
+                row = [0.0] * (2 * self.nt)
+                for j, i in enumerate(have):
+                    row[2 * i], row[2 * i + 1] = h.noisepriors[2 * j], h.noisepriors[2 * j + 1]
+                self.site_noisepriors.append(row)
+        elif self.present is None:
             self.noisepriors = hosts[0].noisepriors
             if any(h.noisepriors != self.noisepriors for h in hosts):
                 raise EngineError("the sites' noise priors differ")
@@ -184,26 +278,14 @@ class DeviceChains(object):
 
         cfg = ChainConfig()
         cfg.nt, cfg.maxlayers = self.nt, self.ML
-        cfg.layermin, cfg.layermax = int(pr["layers"][0]), int(pr["layers"][1])
         cfg.iter_burnin, cfg.iterations = self.iter_phase1, self.iterations
-        (cfg.vsmin, cfg.vsmax), (cfg.zmin, cfg.zmax) = pr["vs"], pr["z"]
-        cfg.thickmin = ip["thickmin"]
-        cfg.lvz = -1.0 if ip["lvz"] is None else ip["lvz"]
-        cfg.hvz = -1.0 if ip["hvz"] is None else ip["hvz"]
-        if _is_fixed(pr["vpvs"]):
-            cfg.vpvsmin = cfg.vpvsmax = float(pr["vpvs"])
+        records = None
+        if self.prior_table:    # the station fields of cfg are not read: every chain has its site's record
+            records = (ChainPrior * self.nsites)()
+            for s in range(self.nsites):
+                set_station_fields(records[s], self.site_initparams[s], self.site_priors[s], self.site_noisepriors[s])
         else:
-            cfg.vpvsmin, cfg.vpvsmax = pr["vpvs"]
-        if pr["mantle"] is None:
-            cfg.mantle_vs, cfg.mantle_vpvs = -1.0, 0.0
-        else:
-            cfg.mantle_vs, cfg.mantle_vpvs = pr["mantle"]
-        cfg.acc_lo, cfg.acc_hi = ip["acceptance"]
-        for i, p in enumerate(self.noisepriors):
-            if _is_fixed(p):
-                cfg.noise_lo[i] = cfg.noise_hi[i] = float(p)
-            else:
-                cfg.noise_lo[i], cfg.noise_hi[i] = p
+            set_station_fields(cfg, ip, pr, self.noisepriors)
         cfg.seed = int(seed) & (2 ** 64 - 1)
         cfg.chain_offset = off
         self.cfg = cfg
@@ -250,6 +332,11 @@ class DeviceChains(object):
         if self.present is not None:
             bits = ((~self.present).astype(np.int64) << np.arange(nt)).sum(axis=1).astype(np.uint8)
             self.absent = torch.from_numpy(np.repeat(bits, self.C_site)).to(dev)
+        # (priors per site) the table of records and, per chain, its site's record
+        self.prior_records = self.prior_of = None
+        if records is not None:
+            self.prior_records = torch.from_numpy(np.frombuffer(records, dtype=np.uint8).copy()).to(dev)
+            self.prior_of = torch.from_numpy(np.repeat(np.arange(self.nsites, dtype=np.int32), self.C_site)).to(dev)
         ld = self.ld                                      # node j of chain c in column j*C + c
         for k in ("pn", "move", "valid", "lay_n"):
             t[k] = torch.zeros(ld, **i32)
@@ -309,8 +396,12 @@ class DeviceChains(object):
                 self._hint = int(self.torch.ceil(t["n"].double().mean()).item())
         w = self.window()
         B = Cn * ((1 << w) - 1)
-        e.chain_propose_window(self.cfg, self.state, Cn, self.iiter, w, self.ld,
-                               absent=None if self.absent is None else self.absent.data_ptr())
+        absent = None if self.absent is None else self.absent.data_ptr()
+        if self.prior_records is not None:
+            e.chain_propose_window_priors(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.prior_records.data_ptr(),
+                                          self.nsites, self.prior_of.data_ptr(), absent=absent)
+        else:
+            e.chain_propose_window(self.cfg, self.state, Cn, self.iiter, w, self.ld, absent=absent)
         e.set_typical_layers(self._hint)       # (for this call only: the engine is shared with other callers)
         prev = e.swd_search() if self.search is not None else None
         if prev is not None and prev != self.search:
@@ -337,7 +428,11 @@ class DeviceChains(object):
             if prev_arith is not None and prev_arith != self.arith:
                 e.set_swd_arith(prev_arith)
             e.set_swd_trials(prev_trials)
-        e.chain_accept_window(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(), self.mis.data_ptr())
+        if self.prior_records is not None:
+            e.chain_accept_window_priors(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(), self.mis.data_ptr(),
+                                         self.prior_records.data_ptr(), self.nsites, self.prior_of.data_ptr())
+        else:
+            e.chain_accept_window(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(), self.mis.data_ptr())
         self.iiter += w
         self.launches += 1
         if self.swap_every > 0 and t["beta"] is not None and self.iiter % self.swap_every == 0:
@@ -401,7 +496,9 @@ class DeviceChains(object):
     def samples(self, phase="p2", cold_only=False, gather=False, site=None):
         """Thinned samples: dict of arrays with leading axes [nsnap, C]; `models` in the reference's row layout
         [vs_1..vs_n NaN.., z_1..z_n NaN..] (2*maxlayers wide).
-        site (SiteTargets): the columns of that site only (its nchains chains; cold_only: its ladders), else all.
+        site (SiteTargets): the columns of that site only (its nchains chains; cold_only: its ladders), else all.  With priors
+        per site its `models` have the site's own row width, 2*(its layers maximum + 1), as its one-site run returns them;
+        without `site` they have the shared width.
         SiteTargets(missing=True): a site's `noise` and `misfits` are in its OWN layout -- the columns of the targets it has,
         as its one-site run returns them; without `site` they are in the slot layout (0 where a site lacks the slot).
         gather: all chains of a sharded job (global chain order) instead of this rank's, on every rank.
@@ -432,6 +529,7 @@ class DeviceChains(object):
             if not 0 <= int(site) < self.nsites:
                 raise IndexError("site %d of %d" % (site, self.nsites))
             out = self._site_block(out, int(site), phase, cold_only, gather)
+            out["models"] = out["models"][..., :2 * self.site_ML[int(site)]]   # (n <= the site's capacity: only NaN padding goes)
             if self.present is not None:
                 out["noise"], out["misfits"] = gather_slots(self.present[int(site)], out["noise"], out["misfits"])
             return out
@@ -508,7 +606,7 @@ class DeviceChains(object):
                     continue
                 smp = self.samples(tag, cold_only=tempered, gather=True, site=s)
                 write_chain_files(datapath, tag, smp, smp["ladder"] if tempered else smp["chain_id"])
-            ip = dict(self.initparams, station=name, savepath=op.join(root, name))
-            save_config(self.sites.site(s), op.join(datapath, "%s_config.pkl" % name), priors=self.priors, initparams=ip)
+            ip = dict(self.site_initparams[s], station=name, savepath=op.join(root, name))
+            save_config(self.sites.site(s), op.join(datapath, "%s_config.pkl" % name), priors=self.site_priors[s], initparams=ip)
             out.append(datapath)
         return out

@@ -72,6 +72,16 @@ class ChainConfig(C.Structure):
                 ("seed", C.c_uint64), ("chain_offset", C.c_int64)]
 
 
+class ChainPrior(C.Structure):
+    """bh_chain_prior of include/bh_engine_sites_priors.h: the fields of bh_chain_config that belong to a station"""
+    _fields_ = [("layermin", C.c_int32), ("layermax", C.c_int32),
+                ("vsmin", C.c_double), ("vsmax", C.c_double), ("zmin", C.c_double), ("zmax", C.c_double),
+                ("thickmin", C.c_double), ("lvz", C.c_double), ("hvz", C.c_double),
+                ("vpvsmin", C.c_double), ("vpvsmax", C.c_double), ("mantle_vs", C.c_double), ("mantle_vpvs", C.c_double),
+                ("acc_lo", C.c_double), ("acc_hi", C.c_double),
+                ("noise_lo", C.c_double * (2 * BH_MAX_TARGETS)), ("noise_hi", C.c_double * (2 * BH_MAX_TARGETS))]
+
+
 CHAIN_STATE_FIELDS = ("n", "vs", "z", "vpvs", "noise", "like", "misfits", "propdist", "proposed", "accepted", "naccepted",
                       "beta", "pn", "move", "valid", "pvs", "pz", "pvpvs", "pnoise", "dvs2", "lay_n", "lay_h", "lay_vp", "lay_vs",
                       "inject", "lay_rho")
@@ -152,6 +162,11 @@ def load_library():
     L.bh_sites_set_missing.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_chain_propose_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, vp]
     L.bh_chain_propose_window_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp]
+    _cc, _cs, _cp = C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_void_p   # (the table of records is a device pointer)
+    L.bh_chain_propose_priors.argtypes = [vp, _cc, _cs, C.c_int, C.c_int, _cp, C.c_int, vp, vp]
+    L.bh_chain_propose_window_priors.argtypes = [vp, _cc, _cs, C.c_int, C.c_int, C.c_int, C.c_ssize_t, _cp, C.c_int, vp, vp]
+    L.bh_chain_accept_priors.argtypes = [vp, _cc, _cs, C.c_int, C.c_int, vp, vp, _cp, C.c_int, vp]
+    L.bh_chain_accept_window_priors.argtypes = [vp, _cc, _cs, C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp, vp, _cp, C.c_int, vp]
     L.bh_evaluate_sites.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                     C.c_ssize_t, C.c_ssize_t, vp, vp, vp, vp, vp, vp]
     L.bh_chain_propose.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int]
@@ -171,7 +186,7 @@ def load_library():
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
                  "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all",
-                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites"):
+                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_PRIORS_SYMBOLS:
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -202,6 +217,9 @@ SITE_X_SYMBOLS = ("bh_sites_set_x",)
 SITE_X_ALL_SYMBOLS = ("bh_sites_set_x_all",)
 # include/bh_engine_sites_missing.h: sites that lack some of the targets
 SITE_MISSING_SYMBOLS = ("bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites")
+# include/bh_engine_sites_priors.h: chains under their own site's priors and sampler settings
+SITE_PRIORS_SYMBOLS = ("bh_chain_propose_priors", "bh_chain_propose_window_priors", "bh_chain_accept_priors",
+                       "bh_chain_accept_window_priors")
 # include/bh_engine_posterior.h: posterior velocity-depth summaries of many sites (bayhunter_amd/posterior.py)
 POSTERIOR_SYMBOLS = ("bh_posterior_create", "bh_posterior_destroy", "bh_posterior_load", "bh_posterior_columns",
                      "bh_posterior_hist", "bh_posterior_interfaces")
@@ -699,6 +717,21 @@ class Engine(object):
             rc = self._L.bh_chain_propose_window(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth), int(ld))
         if rc != BH_OK:
             raise EngineError("bh_chain_propose_window failed (%d)" % rc)
+
+    def chain_propose_window_priors(self, cfg, state, C_, iiter, depth, ld, priors, nprior, prior_of, absent=None):
+        """bh_chain_propose_window_priors.  priors: device pointer of `nprior` ChainPrior records; prior_of: device pointer of
+        int32 [C], the record of each chain; absent: as in chain_propose_window (None: every target present)"""
+        rc = self._L.bh_chain_propose_window_priors(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth),
+                                                    int(ld), priors, int(nprior), prior_of, absent)
+        if rc != BH_OK:
+            raise EngineError("bh_chain_propose_window_priors failed (%d)" % rc)
+
+    def chain_accept_window_priors(self, cfg, state, C_, iiter, depth, ld, logL, misfits, priors, nprior, prior_of):
+        """bh_chain_accept_window_priors (arguments as chain_propose_window_priors)"""
+        rc = self._L.bh_chain_accept_window_priors(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth),
+                                                   int(ld), logL, misfits, priors, int(nprior), prior_of)
+        if rc != BH_OK:
+            raise EngineError("bh_chain_accept_window_priors failed (%d)" % rc)
 
     def chain_accept_window(self, cfg, state, C_, iiter, depth, ld, logL, misfits):
         rc = self._L.bh_chain_accept_window(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth), int(ld),
