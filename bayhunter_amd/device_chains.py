@@ -19,7 +19,9 @@ state changes: proposal-width adaptation (every 1000th iteration), snapshots, te
 Random numbers are counter-based (Philox4x32-10) on the device, so a run is reproducible from
 `seed` but is NOT the reference's Mersenne-Twister trajectory: `ChainBatch` is the draw-for-draw
 replay of the reference, this class is the throughput mode.  The proposal / validity / acceptance
-arithmetic is the same and is tested against an independent numpy restatement with injected draws
+arithmetic is the same.  It is tested twice: kernel by kernel against tests/chain_ref.py, a numpy
+restatement of the reference's step that imports nothing of this package (tests/test_gpu_chain_kernels.py),
+and as whole trajectories against `ChainBatch`, the replay, with the same injected draws
 (tests/test_gpu_device_chains.py).
 
 The initial state (initial models, noise, covariance-law selection, first likelihood) is produced by

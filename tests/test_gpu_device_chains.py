@@ -1,6 +1,8 @@
 """Device-resident chain step (bayhunter_amd/device_chains.py, csrc/chain_kernel.hip) against the
 host chain driver that replays the reference draw for draw (bayhunter_amd/chains.py, itself pinned to
-recorded reference runs in test_gpu_chains.py).
+recorded reference runs in test_gpu_chains.py): whole trajectories of the device against the replay.
+(The restatement that stands apart from the package's sampler code is tests/chain_ref.py; the kernels are
+compared with it decision by decision in tests/test_gpu_chain_kernels.py.)
 
 The host driver's RandomState is replaced by an object handing out the SAME six draws per iteration
 the device kernel uses (tests/philox_ref.py), so both must walk the same trajectory:
