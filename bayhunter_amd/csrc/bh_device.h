@@ -360,6 +360,25 @@ struct GaussSiteArgs {
 };
 void bh_launch_gauss_quad_sites(int B, int n, int ldy, const double *ymod, const double *yobs, const GaussSiteArgs &sites,
                                 const double *rinv, int nsplit, double *partial, hipStream_t stream);
+// Correlation classes of a Gauss-law target (bh_sites_set_gauss, include/bh_engine_sites_gauss.h): the sites that fix the same noise
+// correlation share one R^-1 -- class c's is rinv + c * n * n --, and a model's class is class_of[site[b]] (-1: its site lacks the
+// target; a site out of range has none either).  The contraction's builds of gauss_kernel_c.hip group the rows on the device, class
+// by class, into tiles of one class each: perm[row_start[c] ... row_start[c + 1]) are the rows of class c (in no fixed order: an
+// output row depends on its own residual row, the matrix and the fixed k order only), tile_start[c] the first tile of class c.
+struct GaussClassArgs {
+    const int32_t *class_of;   // device [nsites]
+    int nclass;
+    const int32_t *row_start;  // device [nclass + 1]: prefix of the classes' row counts
+    const int32_t *tile_start; // device [nclass + 1]: prefix of the classes' tile counts
+    const int32_t *perm;       // device [B]: the rows, class by class
+};
+// int32 words of the grouping's work space: count, cursor [nclass], row_start, tile_start [nclass + 1], perm [B]
+inline size_t bh_gauss_class_work_words(int B, int nclass) { return 4 * (size_t)nclass + 2 + (size_t)B; }
+// bh_launch_gauss_quad_sites with the matrix of every row's class: same form, slabs and layout of `partial` as for (B, n) there
+// (bh_gauss_nsplit), so the likelihood kernel sums the same slabs in the same order; the rows of no class get zeros.
+void bh_launch_gauss_quad_classes(int B, int n, int ldy, const double *ymod, const double *yobs, const GaussSiteArgs &sites,
+                                  const int32_t *class_of, int nclass, const double *rinv, int nsplit, double *partial,
+                                  int32_t *work, hipStream_t stream);
 struct LikeKernelArgs {
     int B, nt, ldy;
     const double *ymod; // [B][ldy]
@@ -407,6 +426,15 @@ void bh_launch_like_sites_x(const LikeKernelArgs &a, const LikeSiteXArgs &sites,
 // BH_LIKE_MISSING).  Such a target is skipped -- nothing of noise, yobs, ymod or its failure flag is read, nothing is added to logL
 // or to the joint misfit, its own misfit is 0 -- so the sums are those of the present targets in their order.
 void bh_launch_like_sites_m(const LikeKernelArgs &a, const LikeSiteXArgs &sites, hipStream_t stream);
+// ... and a Gauss-law target's ln|R| (and, for the in-kernel mat-vec, R^-1) is that of the site's correlation class
+// (bh_sites_set_gauss; like_kernel_c.hip, like_kernel.hip compiled with BH_LIKE_CLASSES on top of BH_LIKE_MISSING).  Per target of
+// the call: class_of[t] null = no class table, the descriptor's values.  A class of -1 goes with a count of 0: skipped as above.
+struct LikeClassArgs {
+    const int32_t *class_of[8]; // device [nsites]
+    const double *rinv[8];      // device [nclass][n][n]
+    const double *logdet[8];    // device [nclass]
+};
+void bh_launch_like_sites_c(const LikeKernelArgs &a, const LikeSiteXArgs &sites, const LikeClassArgs &classes, hipStream_t stream);
 
 void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 

@@ -10,6 +10,7 @@
 #include "../../include/bh_engine_sites_x.h"
 #include "../../include/bh_engine_sites_x_all.h"
 #include "../../include/bh_engine_sites_missing.h"
+#include "../../include/bh_engine_sites_gauss.h"
 #include "bh_device.h"
 
 #include <algorithm>
@@ -103,6 +104,10 @@ struct TargetHost {
     DevBuf x60, vel60; // > 60 periods: the 60-point grid the forward model runs on + its output
     int kfwd = 0;      // periods the forward model computes (n, or 60 when n > 60)
     double logdet_extra = 0.0;
+    // correlation classes of a Gauss-law target (bh_sites_set_gauss, include/bh_engine_sites_gauss.h); part of the site table
+    int gc_nclass = 0;                   // 0: no class table, every site takes the descriptor's matrix
+    DevBuf gc_rinv, gc_logdet, gc_class; // [nclass][n][n], [nclass], int32 [nsites]
+    bool site_lacks = false;             // the count table in force has a site with count 0 for this target
 };
 
 } // namespace
@@ -147,6 +152,11 @@ struct bh_engine {
     bool site_x_all = false;                  // ... registered by bh_sites_set_x_all: group velocities' second roots at a site's own periods
     bool site_missing = false;                // ... registered by bh_sites_set_missing: a count may be 0 (the site lacks the target)
     DevBuf site_xn, site_xper;                // [nsites][nt] sample counts (int32), [nsites][ldy] periods in ymod's column layout
+    std::vector<int32_t> site_xn_host;        // ... the counts as registered (bh_sites_set_gauss checks its classes against them)
+    // sites with their own Gauss-law noise correlation (bh_sites_set_gauss, include/bh_engine_sites_gauss.h)
+    bool site_missing_gauss = false;          // registered by bh_sites_set_missing_gauss: a Gauss-law target some site lacks needs its class table
+    DevBuf gc_xn;                             // [nsites][nt] the descriptors' counts: the count table of a class call where none is registered
+    DevBuf gc_work;                           // the grouping's work space of a call (bh_gauss_class_work_words)
     // instrumentation
     bool timing = false, counting = false;
     bool no_mfma = false; // BH_NO_MFMA env: Gauss law through the in-kernel mat-vec (A/B testing)
@@ -222,7 +232,18 @@ void release(DevBuf &b)
 // every device buffer a registered target owns
 void release_target(TargetHost &t)
 {
-    for (DevBuf *b : {&t.x, &t.yobs, &t.yerr_scaled, &t.rinv, &t.quad, &t.sums, &t.x60, &t.vel60}) release(*b);
+    for (DevBuf *b : {&t.x, &t.yobs, &t.yerr_scaled, &t.rinv, &t.quad, &t.sums, &t.x60, &t.vel60, &t.gc_rinv, &t.gc_logdet, &t.gc_class}) release(*b);
+    t.gc_nclass = 0;
+}
+
+// the correlation classes of every target (they belong to the site table: whatever registers or extends it drops them)
+void release_gauss_classes(bh_engine *e)
+{
+    for (auto &t : e->targets) {
+        for (DevBuf *b : {&t.gc_rinv, &t.gc_logdet, &t.gc_class}) release(*b);
+        t.gc_nclass = 0;
+    }
+    release(e->gc_xn);
 }
 
 // the site table's buffers (they belong to the registered targets: bh_targets_set and bh_engine_destroy release them)
@@ -231,7 +252,10 @@ void release_sites(bh_engine *e)
     for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx, &e->site_p, &e->site_nsv, &e->site_xn, &e->site_xper}) release(*b);
     e->nsites = 0;
     e->site_rf = false;
-    e->site_x = e->site_x_all = e->site_missing = false;
+    e->site_x = e->site_x_all = e->site_missing = e->site_missing_gauss = false;
+    e->site_xn_host.clear();
+    release_gauss_classes(e);
+    for (auto &t : e->targets) t.site_lacks = false;
 }
 
 // Targets.py:124-128, the nocorr_scalederr law: out = yerr / min(yerr), returns ln prod(out) (bh_targets_set, bh_sites_set)
@@ -591,7 +615,11 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
 enum EvalRole { ROLE_NONE, ROLE_SWD, ROLE_SWD60, ROLE_RF };
 // The likelihood launcher of a fused call: bh_launch_like, bh_launch_like_sites, bh_launch_like_sites_x (a site's own sample counts)
 // (LIKE_SITES_M: bh_launch_like_sites_m, counts that may be 0)
-enum EvalLike { LIKE_PLAIN, LIKE_SITES, LIKE_SITES_X, LIKE_SITES_M };
+// (LIKE_SITES_C: bh_launch_like_sites_c, a Gauss-law target's ln|R| and R^-1 from its table of correlation classes)
+enum EvalLike { LIKE_PLAIN, LIKE_SITES, LIKE_SITES_X, LIKE_SITES_M, LIKE_SITES_C };
+// The contraction of a Gauss-law target: with the descriptor's data and matrix, with every model's site's data, or with the matrix
+// of every model's correlation class as well (bh_sites_set_gauss)
+enum EvalGauss { GAUSS_PLAIN, GAUSS_SITES, GAUSS_CLASSES };
 
 // What one fused call (bh_evaluate_batch, bh_evaluate_sites) does: everything its steps would otherwise decide.
 struct EvalPlan {
@@ -606,6 +634,8 @@ struct EvalPlan {
     bool x_table, rf_table;     // the site table's periods (bh_sites_set_x) / receiver-function parameters (bh_sites_set_rf) are in force
     bool missing;               // the table's counts may be 0 (bh_sites_set_missing): the receiver-function and likelihood builds that skip
     bool rf_needs_table;        // ... and a receiver-function target is registered without bh_sites_set_rf: the call is refused
+    EvalGauss gauss[BH_MAX_TARGETS]; // (read for the Gauss-law targets)
+    bool gauss_needs_table;     // bh_sites_set_missing_gauss, and a Gauss-law target some site lacks has no class table: the call is refused
     EvalLike like;
     bool err_zero_always;       // bh_tuning.h err_memset: the failure flags are zeroed on every call
 };
@@ -663,6 +693,15 @@ EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
     p.missing = p.x_table && e->site_missing;
     p.rf_needs_table = p.missing && have_rf && !p.rf_table;
     p.like = p.missing ? LIKE_SITES_M : (p.x_table ? LIKE_SITES_X : (sites ? LIKE_SITES : LIKE_PLAIN));
+    // (sites with their own noise correlation, bh_sites_set_gauss: a target with a class table is contracted class by class, and
+    // the likelihood build that reads ln|R| of the model's class serves the call)
+    for (int t = 0; t < p.nt; ++t) {
+        const TargetHost &T = e->targets[(size_t)t];
+        p.gauss[t] = !sites ? GAUSS_PLAIN : (T.gc_nclass > 0 ? GAUSS_CLASSES : GAUSS_SITES);
+        if (T.d.law != BH_LAW_GAUSS) continue;
+        if (p.gauss[t] == GAUSS_CLASSES) p.like = LIKE_SITES_C;
+        else if (sites && e->site_missing_gauss && T.site_lacks) p.gauss_needs_table = true;
+    }
     p.err_zero_always = tun.err_memset != 0;
     return p;
 }
@@ -1250,7 +1289,7 @@ int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, pt
 // of each model's site from the site table.  fused: the target's likelihood comes from the sums of this call's synthesis launch
 // (EvalPlan::rf_fused), not from ymod
 int prepare_like_target(bh_engine *e, hipStream_t st, int B, int ldy, const double *ymod_d, TargetHost &T,
-                        LikeTargetDev &L, bool fused, const int32_t *site)
+                        LikeTargetDev &L, bool fused, const int32_t *site, EvalGauss how)
 {
     L.law = T.d.law; L.n = T.d.n; L.off = T.off;
     L.yobs = (const double *)T.yobs.p;
@@ -1264,8 +1303,13 @@ int prepare_like_target(bh_engine *e, hipStream_t st, int B, int ldy, const doub
         const int nsplit = bh_gauss_nsplit(B, T.d.n);
         int rc = ensure(e, T.quad, (size_t)B * nsplit * sizeof(double));
         if (rc) return rc;
+        if (how == GAUSS_CLASSES && (rc = ensure(e, e->gc_work, bh_gauss_class_work_words(B, T.gc_nclass) * sizeof(int32_t)))) return rc;
         ev_begin(e, 2, st);
-        if (site) {
+        if (how == GAUSS_CLASSES) { // (grouping launches + the contraction over tiles of one class each)
+            const GaussSiteArgs gs{site, e->nsites, ldy};
+            bh_launch_gauss_quad_classes(B, T.d.n, ldy, ymod_d + T.off, (const double *)e->site_yobs.p + T.off, gs, (const int32_t *)T.gc_class.p,
+                                         T.gc_nclass, (const double *)T.gc_rinv.p, nsplit, (double *)T.quad.p, (int32_t *)e->gc_work.p, st);
+        } else if (site) {
             const GaussSiteArgs gs{site, e->nsites, ldy};
             bh_launch_gauss_quad_sites(B, T.d.n, ldy, ymod_d + T.off, (const double *)e->site_yobs.p + T.off, gs, L.rinv, nsplit,
                                        (double *)T.quad.p, st);
@@ -1470,7 +1514,7 @@ void bh_engine_destroy(bh_engine *e)
     (void)hipStreamSynchronize(e->stream);
     for (DevBuf *b : {&e->nlay, &e->h, &e->vp, &e->vs, &e->rho, &e->qp, &e->qs, &e->periods, &e->vel,
                       &e->errb, &e->rf, &e->coef, &e->ymod, &e->noise, &e->logL, &e->misfits,
-                      &e->err_t, &e->probe_in, &e->probe_out, &e->counter, &e->sph, &e->perm, &e->board, &e->nevhi, &e->guard, &e->rfz, &e->gfirst, &e->nevhi2})
+                      &e->err_t, &e->probe_in, &e->probe_out, &e->counter, &e->sph, &e->perm, &e->board, &e->nevhi, &e->guard, &e->rfz, &e->gfirst, &e->nevhi2, &e->gc_work})
         release(*b);
     for (auto &t : e->targets) {
         release_target(t);
@@ -1791,6 +1835,7 @@ int eval_args_ok(bh_engine *e, const EvalPlan &p, bool host, const EvalCall &c)
     if (p.nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
     if (p.no_forward) return fail(e, BH_EINVAL, "a BH_TARGET_USER target has no forward model: use bh_loglike_batch");
     if (p.rf_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_missing with a receiver-function target needs bh_sites_set_rf");
+    if (p.gauss_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_missing_gauss with a Gauss-law target that a site lacks needs the table of bh_sites_set_gauss");
     if (!c.m.nlay || !c.m.h || !c.m.vp || !c.m.vs || !c.la.noise || !c.la.logL || !c.la.misfits || !c.la.err) return fail(e, BH_EINVAL, "null argument");
     if (c.site && host)
         for (int b = 0; b < p.B; ++b)
@@ -1906,14 +1951,29 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
 
 // The likelihood of every model from the synthetics (or the sums of the targets in `fused`) and the failure flags, by launcher
 // `like`.  site: of every model, or null (LIKE_PLAIN)
-int run_like(bh_engine *e, hipStream_t st, LikeKernelArgs la, const bool *fused, EvalLike like, const int32_t *site)
+int run_like(bh_engine *e, hipStream_t st, LikeKernelArgs la, const bool *fused, EvalLike like, const int32_t *site, const EvalGauss *gauss)
 {
     int rc;
     for (int t = 0; t < la.nt; ++t)
-        if ((rc = prepare_like_target(e, st, la.B, la.ldy, la.ymod, e->targets[(size_t)t], la.t[t], fused[t], site))) return rc;
+        if ((rc = prepare_like_target(e, st, la.B, la.ldy, la.ymod, e->targets[(size_t)t], la.t[t], fused[t], site, gauss[t]))) return rc;
     LikeSiteXArgs lx{};
     lx.site = site; lx.nsites = e->nsites; lx.yobs = (const double *)e->site_yobs.p; lx.yerr_scaled = (const double *)e->site_yerr.p;
     lx.logdet_extra = (const double *)e->site_logdet.p; lx.n = (const int32_t *)e->site_xn.p;
+    if (like == LIKE_SITES_C) { // (the count table: the registered one, or the descriptors' counts where the call has none)
+        LikeClassArgs lc{};
+        for (int t = 0; t < la.nt; ++t) {
+            const TargetHost &T = e->targets[(size_t)t];
+            if (gauss[t] != GAUSS_CLASSES || T.d.law != BH_LAW_GAUSS) continue;
+            lc.class_of[t] = (const int32_t *)T.gc_class.p;
+            lc.rinv[t] = (const double *)T.gc_rinv.p;
+            lc.logdet[t] = (const double *)T.gc_logdet.p;
+        }
+        if (!e->site_x) lx.n = (const int32_t *)e->gc_xn.p;
+        ev_begin(e, 2, st);
+        bh_launch_like_sites_c(la, lx, lc, st);
+        ev_end(e, 2, st);
+        return BH_OK;
+    }
     ev_begin(e, 2, st);
     if (like == LIKE_SITES_M) bh_launch_like_sites_m(la, lx, st); // (... of which some may be 0)
     else if (like == LIKE_SITES_X) bh_launch_like_sites_x(la, lx, st); // (a site's own sample counts)
@@ -1942,7 +2002,7 @@ int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const in
     HIPCHK(e, hipSetDevice(e->device));
     if ((rc = stage_eval_inputs(e, host, B, c)) || (rc = size_eval_workspaces(e, p, c))) return rc;
     call_begin(e, c.st);
-    if ((rc = run_forward(e, p, c)) || (rc = run_like(e, c.st, c.la, p.rf_fused, p.like, c.site))) return rc;
+    if ((rc = run_forward(e, p, c)) || (rc = run_like(e, c.st, c.la, p.rf_fused, p.like, c.site, p.gauss))) return rc;
     call_end(e, c.st);
     HIPCHK(e, hipGetLastError());
     if (!host) return BH_OK;
@@ -2014,7 +2074,8 @@ int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yer
 // bh_sites_set_x, bh_sites_set_x_all and bh_sites_set_missing (who: the entry point's name, for the messages).  all: per-site
 // periods and counts on group-velocity and higher-mode targets are accepted -- the one check bh_sites_set_x_all skips.  missing
 // (with all): a count of 0 is accepted on any target -- the site lacks it -- but every site has a target and every target a site.
-static int sites_register_x(bh_engine *e, const char *who, bool all, bool missing, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+// missing_gauss (with missing): ... on a Gauss-law target as well -- the one check bh_sites_set_missing_gauss skips.
+static int sites_register_x(bh_engine *e, const char *who, bool all, bool missing, bool missing_gauss, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
     if (!e) return BH_EINVAL;
     const std::string w(who);
@@ -2038,7 +2099,7 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, bool missin
                 lacks = lacks || n[s * nt + t] == 0;
             }
             if (!any) return fail(e, BH_EINVAL, (w + ": a target no site has (every count 0)").c_str());
-            if (lacks && e->targets[(size_t)t].d.law == BH_LAW_GAUSS)
+            if (lacks && !missing_gauss && e->targets[(size_t)t].d.law == BH_LAW_GAUSS)
                 return fail(e, BH_EUNSUPPORTED, (w + ": a Gauss-law target that a site lacks (the contraction gathers every site's rows)").c_str());
         }
     }
@@ -2090,22 +2151,78 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, bool missin
     e->site_x = true;
     e->site_x_all = all;
     e->site_missing = missing;
+    e->site_missing_gauss = missing_gauss;
+    e->site_xn_host.assign(n, n + S * nt);
+    for (int t = 0; t < nt; ++t)
+        for (size_t s = 0; s < S; ++s)
+            if (n[s * nt + t] == 0) e->targets[(size_t)t].site_lacks = true;
     return BH_OK;
 }
 
 int bh_sites_set_x(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_x", false, false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_x", false, false, false, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_x_all(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_x_all", true, false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_x_all", true, false, false, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_missing(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_missing", true, true, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_missing", true, true, false, nsites, n, x, yobs, yerr);
+}
+
+int bh_sites_set_missing_gauss(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+{
+    return sites_register_x(e, "bh_sites_set_missing_gauss", true, true, true, nsites, n, x, yobs, yerr);
+}
+
+int bh_sites_set_gauss(bh_engine *e, int target, int nsites, int nclass, const int32_t *class_of, const double *rinv, const double *logdet_r)
+{
+    if (!e) return BH_EINVAL;
+    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (nsites != e->nsites) return fail(e, BH_EINVAL, "bh_sites_set_gauss: nsites differs from the site table's");
+    if (target < 0 || target >= e->nt || e->targets[(size_t)target].d.law != BH_LAW_GAUSS)
+        return fail(e, BH_EINVAL, "bh_sites_set_gauss: not a BH_LAW_GAUSS target");
+    if (nclass < 1) return fail(e, BH_EINVAL, "bh_sites_set_gauss: nclass must be at least 1");
+    if (!class_of || !rinv || !logdet_r) return fail(e, BH_EINVAL, "null argument");
+    TargetHost &T = e->targets[(size_t)target];
+    const size_t nn = (size_t)T.d.n * (size_t)T.d.n, S = (size_t)nsites, nt = (size_t)e->nt;
+    if ((size_t)nclass > BH_SITES_GAUSS_MAXBYTES / sizeof(double) / nn)
+        return fail(e, BH_EUNSUPPORTED, "bh_sites_set_gauss: the matrices take more than BH_SITES_GAUSS_MAXBYTES (1 GiB)");
+    if (nclass > BH_SITES_GAUSS_MAXCLASSES) return fail(e, BH_EUNSUPPORTED, "bh_sites_set_gauss: more than BH_SITES_GAUSS_MAXCLASSES (4096) classes");
+    for (size_t s = 0; s < S; ++s) {
+        const int c = class_of[s];
+        if (c < -1 || c >= nclass) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a class index outside [-1, nclass)");
+        const bool has = e->site_xn_host.empty() || e->site_xn_host[s * nt + (size_t)target] != 0; // (bh_sites_set: every site has every target)
+        if (has && c < 0) return fail(e, BH_EINVAL, "bh_sites_set_gauss: class -1 for a site that has the target");
+        if (!has && c >= 0) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a class for a site that lacks the target (count 0)");
+    }
+    for (size_t i = 0; i < (size_t)nclass * nn; ++i)
+        if (!std::isfinite(rinv[i])) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a non-finite value in rinv");
+    for (int c = 0; c < nclass; ++c)
+        if (!std::isfinite(logdet_r[c])) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a non-finite value in logdet_r");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    T.gc_nclass = 0;
+    int rc;
+    if ((rc = ensure(e, T.gc_rinv, (size_t)nclass * nn * sizeof(double))) || (rc = ensure(e, T.gc_logdet, (size_t)nclass * sizeof(double))) ||
+        (rc = ensure(e, T.gc_class, S * sizeof(int32_t))))
+        return rc;
+    HIPCHK(e, hipMemcpy(T.gc_rinv.p, rinv, (size_t)nclass * nn * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(T.gc_logdet.p, logdet_r, (size_t)nclass * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(T.gc_class.p, class_of, S * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!e->site_x && !e->gc_xn.p) { // no count table in force: the likelihood build of the class calls reads the descriptors' counts
+        std::vector<int32_t> cnt(S * nt);
+        for (size_t s = 0; s < S; ++s)
+            for (size_t t = 0; t < nt; ++t) cnt[s * nt + t] = e->targets[t].d.n;
+        if ((rc = ensure(e, e->gc_xn, S * nt * sizeof(int32_t)))) return rc;
+        HIPCHK(e, hipMemcpy(e->gc_xn.p, cnt.data(), S * nt * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    T.gc_nclass = nclass;
+    return BH_OK;
 }
 
 int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const double *nsv)
@@ -2125,6 +2242,7 @@ int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const d
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->site_rf = false;
+    release_gauss_classes(e); // (every entry point that registers or extends the site table drops the correlation classes)
     int rc;
     if ((rc = ensure(e, e->site_p, n * sizeof(double))) || (rc = ensure(e, e->site_nsv, n * sizeof(double)))) return rc;
     HIPCHK(e, hipMemcpy(e->site_p.p, p_s_per_deg, n * sizeof(double), hipMemcpyHostToDevice));
@@ -2177,7 +2295,8 @@ int bh_loglike_batch(bh_engine *e, int memspace, void *stream, int B, const doub
     }
     call_begin(e, st);
     const bool unfused[BH_MAX_TARGETS] = {}; // (the caller's synthetics)
-    if ((rc = run_like(e, st, la, unfused, LIKE_PLAIN, nullptr))) return rc;
+    const EvalGauss plain[BH_MAX_TARGETS] = {};
+    if ((rc = run_like(e, st, la, unfused, LIKE_PLAIN, nullptr, plain))) return rc;
     call_end(e, st);
     HIPCHK(e, hipGetLastError());
     if (!host) return BH_OK;

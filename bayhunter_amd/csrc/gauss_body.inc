@@ -6,14 +6,22 @@
     __shared__ double Dt[KT][LDT]; // residuals, [k][model]
     __shared__ double Rt[KT][LDT]; // R^-1 tile, [k][col]
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
+#if BH_GAUSS_CLASSES
+    // CLASSES (gauss_kernel_c.hip): the workgroup's rows are a tile of ONE correlation class, its models read through the permutation
+    // (BH_GAUSS_ROW), rinv that class's matrix; a workgroup beyond the last tile leaves at once (uniform: before any barrier)
+    const ClassTile tile = class_tile(G, blockIdx.x, 64);
+    if (tile.cls < 0) return;
+    const double *rinv = rinv_all + (size_t)tile.cls * n * n;
+#else
     const int m0 = blockIdx.x * 64;
+#endif
     const int c_begin = blockIdx.y * cols_per_split;
     const int c_end = min(n, c_begin + cols_per_split);
     const int fi = l & 15, fk = l >> 4; // fragment coordinates
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
 
     // staging coordinates: D tile: thread -> model tid/4, 8 consecutive k; R^-1 tile: thread -> row tid/8, 8 consecutive columns
-    const int d_mdl = tid >> 2, d_kq = (tid & 3) * 8, d_gb = m0 + d_mdl;
+    const int d_mdl = tid >> 2, d_kq = (tid & 3) * 8, d_gb = BH_GAUSS_ROW(d_mdl);
     const int r_kr = tid >> 3, r_cq = (tid & 7) * 8;
     const double *yo_d = (SITES && d_gb < B) ? site_row(yobs, S, d_gb) : yobs; // observed data of the staged model
     for (int jt = c_begin; jt < c_end; jt += 64) {
@@ -58,7 +66,7 @@
         // epilogue: c[b][r] = V[model 16w + fk + 4r][col jt + 16b + fi]; fold in D of the same entry
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int gb = m0 + w * 16 + fk + 4 * r;
+            const int gb = BH_GAUSS_ROW(w * 16 + fk + 4 * r);
             const double *yo = (SITES && gb < B) ? site_row(yobs, S, gb) : yobs;
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
@@ -74,6 +82,6 @@
         v += __shfl_xor(v, 2);
         v += __shfl_xor(v, 4);
         v += __shfl_xor(v, 8);
-        const int gb = m0 + w * 16 + fk + 4 * r;
+        const int gb = BH_GAUSS_ROW(w * 16 + fk + 4 * r);
         if (fi == 0 && gb < B) partial[(size_t)gb * nsplit + blockIdx.y] = v;
     }

@@ -8,11 +8,20 @@
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
     const int wm = w >> 1, wn = w & 1;
     const int fi = l & 15, fk = l >> 4;
+#if BH_GAUSS_CLASSES
+    // CLASSES (gauss_kernel_c.hip): the workgroup's rows are a tile of ONE correlation class, its models read through the permutation
+    // (BH_GAUSS_ROW), rinv that class's matrix; a workgroup beyond the last tile leaves at once (uniform: before any barrier)
+    const ClassTile tile = class_tile(G, blockIdx.x, BM);
+    if (tile.cls < 0) return;
+    const double *__restrict__ rinv = rinv_all + (size_t)tile.cls * n * n;
+    const int c0 = blockIdx.y * BN;
+#else
     const int m0 = blockIdx.x * BM, c0 = blockIdx.y * BN;
+#endif
     // staging coordinates
     const int d_mdl = tid >> 2, d_kq = (tid & 3) * NPT;                           // residuals: model, NPT consecutive k
     const int r_row = tid / (BN / NPT), r_cq = (tid % (BN / NPT)) * NPT;          // R^-1: k row, NPT consecutive columns
-    const int d_gb = m0 + d_mdl;
+    const int d_gb = BH_GAUSS_ROW(d_mdl);
     const bool d_ok = d_gb < B;
     const double *yrow = ymod + (size_t)(d_ok ? d_gb : 0) * ldy;
     const double *yo_d = (SITES && d_ok) ? site_row(yobs, S, d_gb) : yobs; // observed data of the staged model
@@ -74,7 +83,7 @@
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int gb = m0 + wm * 32 + rb * 16 + fk + 4 * r;
+            const int gb = BH_GAUSS_ROW(wm * 32 + rb * 16 + fk + 4 * r);
             const double *yo = (SITES && gb < B) ? site_row(yobs, S, gb) : yobs;
             double v = 0.0;
 #pragma unroll

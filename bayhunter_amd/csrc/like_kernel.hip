@@ -21,6 +21,12 @@
 #ifndef BH_LIKE_MISSING
 #define BH_LIKE_MISSING 0
 #endif
+// BH_LIKE_CLASSES (like_kernel_c.hip, on top of BH_LIKE_MISSING): the builds for sites with their own Gauss-law noise correlation
+// (bh_sites_set_gauss, include/bh_engine_sites_gauss.h) -- the two kernels of BH_LIKE_MISSING with ln|R| and R^-1 of a Gauss-law
+// target from the table of correlation classes -- and their launcher only.
+#ifndef BH_LIKE_CLASSES
+#define BH_LIKE_CLASSES 0
+#endif
 
 namespace {
 
@@ -53,6 +59,22 @@ __device__ __forceinline__ LikeTargetDev site_target(LikeTargetDev T, const Like
     T.n = S.n[(size_t)site * nt + t];
     return T;
 }
+
+#if BH_LIKE_CLASSES
+// ... of a site with its own noise correlation: a Gauss-law target with a class table takes ln|R| and (the in-kernel mat-vec) R^-1
+// of the site's class; a class of -1 goes with a count of 0, and that target is skipped before either is read
+__device__ __forceinline__ LikeTargetDev class_target(LikeTargetDev T, const LikeClassArgs &G, int site, int t)
+{
+    if (T.law == 3 && G.class_of[t] != nullptr) {
+        const int c = G.class_of[t][site];
+        if (c >= 0) {
+            T.logdet_extra = G.logdet[t][c];
+            T.rinv = G.rinv[t] + (size_t)c * T.n * T.n;
+        }
+    }
+    return T;
+}
+#endif
 
 #if !BH_LIKE_MISSING
 __global__ __launch_bounds__(256) void like_kernel(LikeKernelArgs A)
@@ -132,6 +154,17 @@ __global__ void probe_kernel(int op, int n, const double *in, double *out)
     out[i] = r;
 }
 
+#elif BH_LIKE_CLASSES
+__global__ __launch_bounds__(256) void like_sites_c_kernel(LikeKernelArgs A, LikeSiteXArgs S, LikeClassArgs G)
+{
+    constexpr bool SITES = true;
+#include "like_body.inc"
+}
+__global__ __launch_bounds__(256) void like_small_sites_c_kernel(LikeKernelArgs A, LikeSiteXArgs S, LikeClassArgs G)
+{
+    constexpr bool SITES = true;
+#include "like_small_body.inc"
+}
 #else
 // the kernels of the site-count table where a count may be 0: that target is skipped (like_body.inc, like_small_body.inc)
 __global__ __launch_bounds__(256) void like_sites_m_kernel(LikeKernelArgs A, LikeSiteXArgs S)
@@ -148,7 +181,15 @@ __global__ __launch_bounds__(256) void like_small_sites_m_kernel(LikeKernelArgs 
 
 } // namespace
 
-#if BH_LIKE_MISSING
+#if BH_LIKE_CLASSES
+void bh_launch_like_sites_c(const LikeKernelArgs &a, const LikeSiteXArgs &sites, const LikeClassArgs &classes, hipStream_t stream)
+{
+    size_t lds = 0;
+    const bool small = bh_like_small_form(a, &lds);
+    if (small) hipLaunchKernelGGL(like_small_sites_c_kernel, dim3((a.B + 3) / 4), dim3(256), 0, stream, a, sites, classes);
+    else hipLaunchKernelGGL(like_sites_c_kernel, dim3(a.B), dim3(256), lds, stream, a, sites, classes);
+}
+#elif BH_LIKE_MISSING
 void bh_launch_like_sites_m(const LikeKernelArgs &a, const LikeSiteXArgs &sites, hipStream_t stream)
 {
     size_t lds = 0;

@@ -160,6 +160,8 @@ def load_library():
     L.bh_sites_set_x.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_sites_set_x_all.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_sites_set_missing.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.bh_sites_set_missing_gauss.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.bh_sites_set_gauss.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.bh_chain_propose_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, vp]
     L.bh_chain_propose_window_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp]
     _cc, _cs, _cp = C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_void_p   # (the table of records is a device pointer)
@@ -186,7 +188,7 @@ def load_library():
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
                  "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all",
-                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_PRIORS_SYMBOLS:
+                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_GAUSS_SYMBOLS + SITE_PRIORS_SYMBOLS:
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -217,6 +219,8 @@ SITE_X_SYMBOLS = ("bh_sites_set_x",)
 SITE_X_ALL_SYMBOLS = ("bh_sites_set_x_all",)
 # include/bh_engine_sites_missing.h: sites that lack some of the targets
 SITE_MISSING_SYMBOLS = ("bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites")
+# include/bh_engine_sites_gauss.h: a Gauss-law noise correlation per site
+SITE_GAUSS_SYMBOLS = ("bh_sites_set_gauss", "bh_sites_set_missing_gauss")
 # include/bh_engine_sites_priors.h: chains under their own site's priors and sampler settings
 SITE_PRIORS_SYMBOLS = ("bh_chain_propose_priors", "bh_chain_propose_window_priors", "bh_chain_accept_priors",
                        "bh_chain_accept_window_priors")
@@ -593,6 +597,25 @@ class Engine(object):
         computed, read or added for the site's models.  Same arrays, same lifetime; with a receiver-function target
         set_sites_rf must follow."""
         self._set_sites_x(self._L.bh_sites_set_missing, n, x, yobs, yerr)
+
+    def set_sites_missing_gauss(self, n, x, yobs, yerr=None):
+        """set_sites_missing that accepts a Gauss-law target which some site lacks (bh_sites_set_missing_gauss); such a target
+        then needs its table of correlation classes (set_sites_gauss, the lacking sites in class -1) before evaluate_sites."""
+        self._set_sites_x(self._L.bh_sites_set_missing_gauss, n, x, yobs, yerr)
+
+    def set_sites_gauss(self, target, class_of, rinv, logdet_r):
+        """The noise-correlation classes of Gauss-law target `target` for the site table in force (bh_sites_set_gauss):
+        class_of[nsites] int32, the class of every site (-1: the site lacks the target); rinv[nclass, n, n] and logdet_r[nclass],
+        R^-1 and ln|R| of every class.  evaluate_sites then contracts every model with its site's class's matrix.  Register it
+        last: set_targets and every other set_sites* drop it."""
+        class_of = np.ascontiguousarray(class_of, dtype=np.int32)
+        rinv, logdet_r = _f64(rinv), _f64(logdet_r)
+        if class_of.ndim != 1:
+            raise ValueError("class_of must have shape (nsites,)")
+        if rinv.ndim != 3 or rinv.shape[1] != rinv.shape[2] or logdet_r.shape != rinv.shape[:1]:
+            raise ValueError("rinv must have shape (nclass, n, n) and logdet_r (nclass,)")
+        self._check(self._L.bh_sites_set_gauss(self._h, int(target), class_of.shape[0], rinv.shape[0], _ptr(class_of), _ptr(rinv),
+                                               _ptr(logdet_r)))
 
     def _set_sites_x(self, entry, n, x, yobs, yerr):
         """set_sites_x / set_sites_x_all: the arrays checked and handed to entry point `entry`"""

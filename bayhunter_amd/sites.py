@@ -12,7 +12,8 @@ periods of its own site, as a one-site run searches it.  per_site_x="all" extend
 velocities to every dispersion target -- group velocities and higher modes (include/bh_engine_sites_x_all.h).  And a station need
 not have every target of the array (missing=True, include/bh_engine_sites_missing.h): the targets become SLOTS, a site gives None
 in the slots it lacks, and each of its models is evaluated -- and each of its chains walks -- as in a one-site run over the targets
-the site has.
+the site has.  The fixed noise correlation of a Gauss-law target -- a receiver function's usual configuration -- may differ between
+sites too (per_site_corr=True, include/bh_engine_sites_gauss.h): the sites' matrices R^-1 are registered once per distinct value.
 """
 import numpy as np
 
@@ -98,11 +99,19 @@ class SiteTargets(object):
     one target or more.  `ntargets` and `targets` describe the slots (a slot's descriptor is that of the first site that has
     it), noise and misfits of `evaluate_batch` are in the slot layout; `site(s)` is the JointTarget of the targets site s HAS --
     the one-site run its models and chains reproduce.  For a slot the model's site lacks nothing is added to logL or the joint
-    misfit, its misfit is 0, it never sets err, its synthetics are zeros and its forward model is not run.  Refused: the Gauss
-    law on a slot that some site lacks (the contraction gathers every site's rows)."""
+    misfit, its misfit is 0, it never sets err, its synthetics are zeros and its forward model is not run.  Refused without per_site_corr:
+    the Gauss law on a slot that some site lacks.
 
-    def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False, missing=False):
+    per_site_corr=True: the sites' Gauss-law targets may differ in corr_inv / logcorr_det -- every station fixes its own noise
+    correlation -- provided the shapes are equal (the sample count stays shared).  The sites' matrices are deduplicated by their
+    bits into correlation CLASSES and one table per Gauss-law target is registered (`gauss_class_arrays`,
+    Engine.set_sites_gauss); each model is contracted with its own site's matrix, the bits of its one-site evaluation in a
+    batch of the same size.  With missing=True a Gauss-law slot may then be absent at some sites (class -1).  Still refused: a
+    Gauss-law dispersion target with periods per site; sites whose installed laws differ ('gauss' against 'exp')."""
+
+    def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False, missing=False, per_site_corr=False):
         self.missing = bool(missing)
+        self.per_site_corr = bool(per_site_corr)
         self._slots = None
         if self.missing:
             if per_site_x != "all":
@@ -210,7 +219,7 @@ class SiteTargets(object):
                 t = self._slots[s][i]
                 what = "site %d (%s), slot %d (%s)" % (s, self._names[s], i, getattr(t, "ref", "?"))
                 self._check_target(what, t, t0, "site %d" % have[0])
-                if len(have) < self.nsites and t.law() == "gauss":
+                if len(have) < self.nsites and t.law() == "gauss" and not self.per_site_corr:
                     raise ValueError("%s: Gauss law on a slot that some site lacks (the contraction gathers every site's rows)" % what)
 
     def _check_target(self, what, t, t0, whose):
@@ -247,7 +256,11 @@ class SiteTargets(object):
             raise ValueError("%s: noise law %r, %s's %r" % (what, law, whose, law0))
         if law == "gauss":
             v, v0 = t.valuation, t0.valuation
-            if (np.shape(v.corr_inv) != np.shape(v0.corr_inv) or _bits(v.corr_inv) != _bits(v0.corr_inv)
+            if self.per_site_corr:
+                if np.shape(v.corr_inv) != np.shape(v0.corr_inv):
+                    raise ValueError("%s: Gauss law with R^-1 of shape %r, %s's %r (sites share the sample count)"
+                                     % (what, np.shape(v.corr_inv), whose, np.shape(v0.corr_inv)))
+            elif (np.shape(v.corr_inv) != np.shape(v0.corr_inv) or _bits(v.corr_inv) != _bits(v0.corr_inv)
                     or _bits(v.logcorr_det) != _bits(v0.logcorr_det)):
                 raise ValueError("%s: Gauss law with another R^-1 / ln|R| than %s's (sites share corr)" % (what, whose))
 
@@ -335,6 +348,30 @@ class SiteTargets(object):
                     p[s, i], nsv[s, i] = float(a["p"]), float(a["nsv"])
         return p, nsv
 
+    def gauss_class_arrays(self):
+        """per_site_corr=True: {slot: (class_of[S] int32, rinv[nclass, n, n], logdet_r[nclass])} for Engine.set_sites_gauss, one
+        entry per Gauss-law slot.  The sites' (corr_inv, logcorr_det) are deduplicated by their bits, classes numbered in the
+        order of their first site; -1: the site lacks the slot."""
+        out = {}
+        for i, t0 in enumerate(self.targets):
+            if t0.law() != "gauss":
+                continue
+            seen, class_of, rinv, logdet = {}, [], [], []
+            for row in self._slot_rows():
+                t = row[i]
+                if t is None:
+                    class_of.append(-1)
+                    continue
+                v = t.valuation
+                key = (_bits(v.corr_inv), _bits(v.logcorr_det))
+                if key not in seen:
+                    seen[key] = len(rinv)
+                    rinv.append(np.asarray(v.corr_inv, dtype=np.float64))
+                    logdet.append(float(v.logcorr_det))
+                class_of.append(seen[key])
+            out[i] = (np.array(class_of, dtype=np.int32), np.stack(rinv), np.array(logdet, dtype=np.float64))
+        return out
+
     def _signature(self):
         """What the registration depends on, by identity as JointTarget._signature: every site's targets, plugins and laws,
         and the arrays of its x, y and yerr (O(sites x targets) per call; replacing an array re-registers)."""
@@ -351,7 +388,9 @@ class SiteTargets(object):
         if self._registered != sig or e._owner is not self:
             if self.per_site_x:
                 e.set_targets(self._capacity_descs())
-                if self.missing:
+                if self.missing and self.per_site_corr:
+                    e.set_sites_missing_gauss(*self.site_x_arrays())
+                elif self.missing:
                     e.set_sites_missing(*self.site_x_arrays())
                 elif self.per_site_x == "all":
                     e.set_sites_x_all(*self.site_x_arrays())
@@ -363,6 +402,9 @@ class SiteTargets(object):
                 e.set_sites(yobs, yerr)
             if self.per_site_rf or self.missing:   # (missing: the coefficient stage finds the model's site through this table)
                 e.set_sites_rf(*self.site_rf_arrays())
+            if self.per_site_corr:                 # (last: every other registration drops the classes)
+                for i, (class_of, rinv, logdet) in sorted(self.gauss_class_arrays().items()):
+                    e.set_sites_gauss(i, class_of, rinv, logdet)
             e._owner = self
             self._registered = sig
             # the arrays the signature names stay alive while it is in force: their ids cannot be handed to replacements
