@@ -337,6 +337,23 @@ struct RfSiteMArgs : RfSiteArgs {
     const int32_t *n; // device [nsites][ld], already offset to the target's column
 };
 int bh_launch_rf_m(const RfKernelArgs &a, hipStream_t stream, const RfSiteMArgs &sites);
+// Sites with their own receiver-function time axis and Gauss filter (bh_sites_set_rf_axis, include/bh_engine_sites_rf_axis.h): the
+// builds of rf_kernel_t.hip (rf_kernel.hip compiled with BH_RF_SITEAXIS on top of BH_RF_MISSING).  A workgroup of the synthesis
+// kernel is one model: it reads its model's site and that site's record, and runs the transform of the site's own length with the
+// site's own sampling, shift, filter width and cut; the site's n samples (RfSiteMArgs::n) are followed by zeros up to the column's
+// capacity RfKernelArgs::nkeep.  logm and jcut are formed on the host with bh_launch_rf's expressions (bh_rf_axis_record).
+struct RfAxisRec {
+    double fsamp, tshift, gauss;
+    int32_t nsamp, logm, jcut; // jcut: the first bin not formed, nsamp / 2 + 1 where the filter keeps them all (the rf_no_cut switch overrides it at launch)
+    int32_t pad;
+};
+struct RfSiteTArgs : RfSiteMArgs {
+    const RfAxisRec *axis; // device [nsites][ld], already offset to the target's column
+    int nsamp_max;         // the largest nsamp of the column: the LDS of every workgroup
+};
+RfAxisRec bh_rf_axis_record(int nsamp, double fsamp, double tshift, double gauss);
+// -1 when nsamp_max does not fit a workgroup's LDS (the table is refused beyond 16384 samples before it gets here)
+int bh_launch_rf_t(const RfKernelArgs &a, hipStream_t stream, const RfSiteTArgs &sites);
 // bh_probe_math ops 11-16: the synthesis kernel's own elementary functions (include/bh_engine_debug.h); -1 for another op
 int bh_launch_rf_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 

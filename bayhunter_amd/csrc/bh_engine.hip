@@ -11,6 +11,7 @@
 #include "../../include/bh_engine_sites_x_all.h"
 #include "../../include/bh_engine_sites_missing.h"
 #include "../../include/bh_engine_sites_gauss.h"
+#include "../../include/bh_engine_sites_rf_axis.h"
 #include "bh_device.h"
 
 #include <algorithm>
@@ -108,6 +109,8 @@ struct TargetHost {
     int gc_nclass = 0;                   // 0: no class table, every site takes the descriptor's matrix
     DevBuf gc_rinv, gc_logdet, gc_class; // [nclass][n][n], [nclass], int32 [nsites]
     bool site_lacks = false;             // the count table in force has a site with count 0 for this target
+    bool rf_own_counts = false;          // receiver function: the count table in force (bh_sites_set_axes) has a count that is neither 0 nor the descriptor's
+    int axis_nsamp_max = 0;              // receiver function: the largest nsamp of the column of bh_sites_set_rf_axis
 };
 
 } // namespace
@@ -147,6 +150,9 @@ struct bh_engine {
     // receiver-function parameters per site (bh_sites_set_rf, include/bh_engine_sites_rf.h): part of the site table
     bool site_rf = false;
     DevBuf site_p, site_nsv;                  // [nsites][nt]: p (s/deg) and nsv of every site, read in the RF columns only
+    // receiver-function time axis and Gauss filter per site (bh_sites_set_rf_axis, include/bh_engine_sites_rf_axis.h): part of that table
+    bool site_rf_axis = false;
+    DevBuf site_axis;                         // [nsites][nt] RfAxisRec, read in the RF columns only
     // dispersion periods per site (bh_sites_set_x, include/bh_engine_sites_x.h): registered together with the site table
     bool site_x = false;
     bool site_x_all = false;                  // ... registered by bh_sites_set_x_all: group velocities' second roots at a site's own periods
@@ -249,13 +255,16 @@ void release_gauss_classes(bh_engine *e)
 // the site table's buffers (they belong to the registered targets: bh_targets_set and bh_engine_destroy release them)
 void release_sites(bh_engine *e)
 {
-    for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx, &e->site_p, &e->site_nsv, &e->site_xn, &e->site_xper}) release(*b);
+    for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx, &e->site_p, &e->site_nsv, &e->site_xn, &e->site_xper, &e->site_axis}) release(*b);
     e->nsites = 0;
-    e->site_rf = false;
+    e->site_rf = e->site_rf_axis = false;
     e->site_x = e->site_x_all = e->site_missing = e->site_missing_gauss = false;
     e->site_xn_host.clear();
     release_gauss_classes(e);
-    for (auto &t : e->targets) t.site_lacks = false;
+    for (auto &t : e->targets) {
+        t.site_lacks = t.rf_own_counts = false;
+        t.axis_nsamp_max = 0;
+    }
 }
 
 // Targets.py:124-128, the nocorr_scalederr law: out = yerr / min(yerr), returns ln prod(out) (bh_targets_set, bh_sites_set)
@@ -634,6 +643,10 @@ struct EvalPlan {
     bool x_table, rf_table;     // the site table's periods (bh_sites_set_x) / receiver-function parameters (bh_sites_set_rf) are in force
     bool missing;               // the table's counts may be 0 (bh_sites_set_missing): the receiver-function and likelihood builds that skip
     bool rf_needs_table;        // ... and a receiver-function target is registered without bh_sites_set_rf: the call is refused
+    bool rf_axis;               // the sites' own time axes and filters (bh_sites_set_rf_axis) are in force: the builds of bh_launch_rf_t
+    bool rf_axis_needs_table;   // a receiver function's counts differ from its descriptor's (bh_sites_set_axes) without that table: refused
+    bool rf_axis_gauss_needs_table; // ... under the Gauss law without the target's class table (bh_sites_set_gauss): refused
+    bool rf_axis_no_mfma;       // ... under the Gauss law with the BH_NO_MFMA in-kernel mat-vec: refused
     EvalGauss gauss[BH_MAX_TARGETS]; // (read for the Gauss-law targets)
     bool gauss_needs_table;     // bh_sites_set_missing_gauss, and a Gauss-law target some site lacks has no class table: the call is refused
     EvalLike like;
@@ -692,15 +705,21 @@ EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
     // (sites that lack targets, bh_sites_set_missing: the coefficient stage looks the model's site up in the count table)
     p.missing = p.x_table && e->site_missing;
     p.rf_needs_table = p.missing && have_rf && !p.rf_table;
+    // (sites with their own time axis and filter, bh_sites_set_rf_axis: the synthesis kernel reads its model's site's record)
+    p.rf_axis = p.rf_table && p.x_table && e->site_rf_axis;
     p.like = p.missing ? LIKE_SITES_M : (p.x_table ? LIKE_SITES_X : (sites ? LIKE_SITES : LIKE_PLAIN));
     // (sites with their own noise correlation, bh_sites_set_gauss: a target with a class table is contracted class by class, and
     // the likelihood build that reads ln|R| of the model's class serves the call)
     for (int t = 0; t < p.nt; ++t) {
         const TargetHost &T = e->targets[(size_t)t];
         p.gauss[t] = !sites ? GAUSS_PLAIN : (T.gc_nclass > 0 ? GAUSS_CLASSES : GAUSS_SITES);
+        if (sites && T.rf_own_counts && !p.rf_axis) p.rf_axis_needs_table = true;
         if (T.d.law != BH_LAW_GAUSS) continue;
         if (p.gauss[t] == GAUSS_CLASSES) p.like = LIKE_SITES_C;
         else if (sites && e->site_missing_gauss && T.site_lacks) p.gauss_needs_table = true;
+        else if (sites && T.rf_own_counts) p.rf_axis_gauss_needs_table = true; // (the descriptor's matrix is the capacity's, no site's)
+        // (the mat-vec's row stride is the site's n, the class matrices -- a site's in the corner of a zero matrix -- have the capacity's)
+        if (sites && T.rf_own_counts && e->no_mfma) p.rf_axis_no_mfma = true;
     }
     p.err_zero_always = tun.err_memset != 0;
     return p;
@@ -1256,6 +1275,7 @@ struct RfJob {
     const double *yobs; double *sums;
     const RfSiteArgs *sites;
     const RfSiteMArgs *msites; // sites that may lack the target (bh_sites_set_missing): the builds of bh_launch_rf_m, or null
+    const RfSiteTArgs *tsites; // sites with their own time axis and filter (bh_sites_set_rf_axis): the builds of bh_launch_rf_t, or null
 };
 
 int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl, ptrdiff_t sb, const RfJob &j, const RfPlace &where)
@@ -1270,14 +1290,14 @@ int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, pt
     a.p_s_per_deg = j.p; a.gauss = j.gauss; a.fsamp = j.fsamp; a.tshift = j.tshift; a.nsv = j.nsv;
     a.coef = (double *)e->coef.p; a.rf = j.rf; a.ldr = j.ldr;
     a.yobs = j.yobs; a.sums = j.sums; // (fused likelihood: the sums instead of the trace)
-    if (bh_rf_lds_bytes(j.nsamp) > BH_RF_MAX_LDS) { // a trace longer than a workgroup's LDS holds: the spectra go through a workspace
+    if (!j.tsites && bh_rf_lds_bytes(j.nsamp) > BH_RF_MAX_LDS) { // a trace longer than a workgroup's LDS holds: the spectra go through a workspace
         if ((rc = ensure(e, e->rfz, (size_t)B * (size_t)(j.nsamp / 2) * 2 * sizeof(double)))) return rc;
         a.zwork = (double *)e->rfz.p;
     }
     a.lds_min = where.lds_min;
     a.coef_small = where.coef_small;
     ev_begin(e, 1, st);
-    const int lrc = j.msites ? bh_launch_rf_m(a, st, *j.msites) : bh_launch_rf(a, st, j.sites);
+    const int lrc = j.tsites ? bh_launch_rf_t(a, st, *j.tsites) : j.msites ? bh_launch_rf_m(a, st, *j.msites) : bh_launch_rf(a, st, j.sites);
     ev_end(e, 1, st);
     if (lrc != 0) return fail(e, BH_EUNSUPPORTED, "receiver function: nsamp above 262144 is not supported");
     HIPCHK(e, hipGetLastError());
@@ -1835,7 +1855,10 @@ int eval_args_ok(bh_engine *e, const EvalPlan &p, bool host, const EvalCall &c)
     if (p.nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
     if (p.no_forward) return fail(e, BH_EINVAL, "a BH_TARGET_USER target has no forward model: use bh_loglike_batch");
     if (p.rf_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_missing with a receiver-function target needs bh_sites_set_rf");
+    if (p.rf_axis_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_axes with a receiver-function count that differs from its descriptor's needs the table of bh_sites_set_rf_axis");
     if (p.gauss_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_missing_gauss with a Gauss-law target that a site lacks needs the table of bh_sites_set_gauss");
+    if (p.rf_axis_gauss_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_axes with a Gauss-law receiver function whose counts differ from its descriptor's needs the table of bh_sites_set_gauss (every site's matrix padded to the capacity)");
+    if (p.rf_axis_no_mfma) return fail(e, BH_EUNSUPPORTED, "BH_NO_MFMA: the in-kernel mat-vec does not serve a Gauss-law receiver function with per-site counts (bh_sites_set_axes)");
     if (!c.m.nlay || !c.m.h || !c.m.vp || !c.m.vs || !c.la.noise || !c.la.logL || !c.la.misfits || !c.la.err) return fail(e, BH_EINVAL, "null argument");
     if (c.site && host)
         for (int b = 0; b < p.B; ++b)
@@ -1941,9 +1964,16 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
             static_cast<RfSiteArgs &>(rm) = rs;
             rm.n = (const int32_t *)e->site_xn.p + t;
         }
+        RfSiteTArgs ra{};
+        if (p.rf_axis) {
+            static_cast<RfSiteArgs &>(ra) = rs;
+            ra.n = (const int32_t *)e->site_xn.p + t;
+            ra.axis = (const RfAxisRec *)e->site_axis.p + t;
+            ra.nsamp_max = T.axis_nsamp_max;
+        }
         const RfJob job{d.p_s_per_deg, d.gauss, d.nsamp, d.fsamp, d.tshift, d.nsv, d.waveno, d.n, c.ymod + T.off, ldy,
                         p.rf_fused[t] ? (const double *)T.yobs.p : nullptr, p.rf_fused[t] ? (double *)T.sums.p : nullptr, p.rf_table ? &rs : nullptr,
-                        p.missing ? &rm : nullptr};
+                        p.missing ? &rm : nullptr, p.rf_axis ? &ra : nullptr};
         if ((rc = launch_rf(e, rst, B, c.Lmax, c.m, c.sl, c.sb, job, where))) return rc;
     }
     return p.fork ? wait_for(e, e->ev_join, e->aux, st) : BH_OK;
@@ -2075,7 +2105,8 @@ int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yer
 // periods and counts on group-velocity and higher-mode targets are accepted -- the one check bh_sites_set_x_all skips.  missing
 // (with all): a count of 0 is accepted on any target -- the site lacks it -- but every site has a target and every target a site.
 // missing_gauss (with missing): ... on a Gauss-law target as well -- the one check bh_sites_set_missing_gauss skips.
-static int sites_register_x(bh_engine *e, const char *who, bool all, bool missing, bool missing_gauss, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+// axes (with missing_gauss): a receiver function's count may be 0 or 1 .. its descriptor's n -- the one check bh_sites_set_axes skips.
+static int sites_register_x(bh_engine *e, const char *who, bool all, bool missing, bool missing_gauss, bool axes, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
     if (!e) return BH_EINVAL;
     const std::string w(who);
@@ -2106,9 +2137,12 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, bool missin
     for (int t = 0; t < nt; ++t) {
         const TargetHost &T = e->targets[(size_t)t];
         const bh_target_desc &d = T.d;
-        if (d.kind != BH_TARGET_SWD) { // (a receiver function's x is its descriptor's time axis: shared)
-            for (size_t s = 0; s < S; ++s)
+        if (d.kind != BH_TARGET_SWD) { // (a receiver function's x is its descriptor's time axis: shared, but for bh_sites_set_axes)
+            for (size_t s = 0; s < S; ++s) {
+                if (axes && d.kind == BH_TARGET_RF && n[s * nt + t] >= 0 && n[s * nt + t] <= d.n) continue;
+                if (axes && d.kind == BH_TARGET_RF) return fail(e, BH_EINVAL, (w + ": a receiver function's sample count is below 0 or above its descriptor's n (the capacity)").c_str());
                 if (n[s * nt + t] != d.n && !(missing && n[s * nt + t] == 0)) return fail(e, BH_EINVAL, (w + ": the sample count of a target that is no dispersion curve differs from its descriptor's").c_str());
+            }
             continue;
         }
         if (d.law == BH_LAW_GAUSS) return fail(e, BH_EINVAL, (w + ": a dispersion target with the Gauss law (its R^-1 depends on the sample count)").c_str());
@@ -2156,27 +2190,33 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, bool missin
     for (int t = 0; t < nt; ++t)
         for (size_t s = 0; s < S; ++s)
             if (n[s * nt + t] == 0) e->targets[(size_t)t].site_lacks = true;
+            else if (e->targets[(size_t)t].d.kind == BH_TARGET_RF && n[s * nt + t] != e->targets[(size_t)t].d.n) e->targets[(size_t)t].rf_own_counts = true;
     return BH_OK;
 }
 
 int bh_sites_set_x(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_x", false, false, false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_x", false, false, false, false, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_x_all(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_x_all", true, false, false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_x_all", true, false, false, false, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_missing(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_missing", true, true, false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_missing", true, true, false, false, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_missing_gauss(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_missing_gauss", true, true, true, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_missing_gauss", true, true, true, false, nsites, n, x, yobs, yerr);
+}
+
+int bh_sites_set_axes(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+{
+    return sites_register_x(e, "bh_sites_set_axes", true, true, true, true, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_gauss(bh_engine *e, int target, int nsites, int nclass, const int32_t *class_of, const double *rinv, const double *logdet_r)
@@ -2241,13 +2281,55 @@ int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const d
     }
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    e->site_rf = false;
+    e->site_rf = e->site_rf_axis = false; // (the axis table belongs to this one)
     release_gauss_classes(e); // (every entry point that registers or extends the site table drops the correlation classes)
     int rc;
     if ((rc = ensure(e, e->site_p, n * sizeof(double))) || (rc = ensure(e, e->site_nsv, n * sizeof(double)))) return rc;
     HIPCHK(e, hipMemcpy(e->site_p.p, p_s_per_deg, n * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(e, hipMemcpy(e->site_nsv.p, nsv, n * sizeof(double), hipMemcpyHostToDevice));
     e->site_rf = true;
+    return BH_OK;
+}
+
+int bh_sites_set_rf_axis(bh_engine *e, int nsites, const int32_t *nsamp, const double *fsamp, const double *tshift, const double *gauss)
+{
+    if (!e) return BH_EINVAL;
+    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (!e->site_x) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: no count table registered (bh_sites_set_axes)");
+    if (!e->site_rf) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis needs the table of bh_sites_set_rf (the coefficient stage finds the model's site through it)");
+    if (nsites != e->nsites) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: nsites differs from the site table's");
+    if (!nsamp || !fsamp || !tshift || !gauss) return fail(e, BH_EINVAL, "null argument");
+    const int nt = e->nt;
+    const size_t S = (size_t)nsites;
+    std::vector<RfAxisRec> recs(S * (size_t)nt, RfAxisRec{1.0, 0.0, 1.0, 4, 1, 3, 0}); // (other targets' and absent pairs' entries: never read)
+    std::vector<int> nmax((size_t)nt, 0);
+    for (int t = 0; t < nt; ++t) {
+        if (e->targets[(size_t)t].d.kind != BH_TARGET_RF) continue;
+        for (size_t s = 0; s < S; ++s) {
+            const size_t i = s * (size_t)nt + (size_t)t;
+            const int cnt = e->site_xn_host[i];
+            if (cnt == 0) continue; // (the site lacks the target)
+            const int ns = nsamp[i];
+            if (ns < 4 || (ns & (ns - 1)) != 0) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: nsamp must be a power of two >= 4");
+            if (ns > BH_SITES_RF_AXIS_MAX_NSAMP)
+                return fail(e, BH_EUNSUPPORTED, "bh_sites_set_rf_axis: nsamp above 16384 (the HBM-workspace build stays on the shared axis)");
+            if (ns < cnt) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: nsamp below the site's sample count");
+            if (!std::isfinite(fsamp[i]) || !(fsamp[i] > 0.0) || !std::isfinite(gauss[i]) || !(gauss[i] > 0.0))
+                return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: fsamp and gauss must be finite and > 0");
+            if (!std::isfinite(tshift[i])) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: a non-finite tshift");
+            recs[i] = bh_rf_axis_record(ns, fsamp[i], tshift[i], gauss[i]);
+            nmax[(size_t)t] = std::max(nmax[(size_t)t], ns);
+        }
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->site_rf_axis = false;
+    release_gauss_classes(e); // (every entry point that registers or extends the site table drops the correlation classes)
+    int rc;
+    if ((rc = ensure(e, e->site_axis, recs.size() * sizeof(RfAxisRec)))) return rc;
+    HIPCHK(e, hipMemcpy(e->site_axis.p, recs.data(), recs.size() * sizeof(RfAxisRec), hipMemcpyHostToDevice));
+    for (int t = 0; t < nt; ++t) e->targets[(size_t)t].axis_nsamp_max = nmax[(size_t)t];
+    e->site_rf_axis = true;
     return BH_OK;
 }
 

@@ -31,9 +31,21 @@
 #ifndef BH_RF_MISSING
 #define BH_RF_MISSING 0
 #endif
+// BH_RF_SITEAXIS (rf_kernel_t.hip, on top of BH_RF_MISSING): the builds for sites with their own time axis and Gauss filter
+// (bh_sites_set_rf_axis, include/bh_engine_sites_rf_axis.h) -- the coefficient kernels of BH_RF_MISSING, the synthesis kernels whose
+// workgroup takes nsamp, fsamp, tshift, gauss, the sample count, logm and jcut from its model's site, and their launcher
+// bh_launch_rf_t; nothing else of this file.
+#ifndef BH_RF_SITEAXIS
+#define BH_RF_SITEAXIS 0
+#endif
+#if BH_RF_SITEAXIS && !BH_RF_MISSING
+#error "BH_RF_SITEAXIS builds on BH_RF_MISSING"
+#endif
 
 namespace {
-#if BH_RF_MISSING
+#if BH_RF_SITEAXIS
+typedef RfSiteTArgs RfSiteT; // (... and the axis record of every site for the target: RfSiteTArgs::axis)
+#elif BH_RF_MISSING
 typedef RfSiteMArgs RfSiteT; // (with the count of every site for the target: RfSiteMArgs::n)
 #else
 typedef RfSiteArgs RfSiteT;
@@ -597,8 +609,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) voi
 // GLOBALZ: the half-length spectrum lives in the model's slice of A.zwork (HBM / L2) instead of LDS -- traces longer than a
 // workgroup's LDS holds (nsamp > 16384).  Same bins, same butterflies, same order; a workgroup's barrier orders its own
 // global accesses (all its wavefronts share the CU's cache).
+// BH_RF_SITEAXIS: A, logm and jcut are the model's site's (rf_synth_t_entry below); ncap = the capacity of the trace's columns, which
+// the workgroup fills with zeros beyond the A.nkeep samples of its site.
+#if BH_RF_SITEAXIS
+template <bool GLOBALZ = false>
+__device__ __forceinline__ void rf_synth_body(const RfKernelArgs &A, int logm, int jcut, int ncap)
+#else
 template <bool GLOBALZ = false>
 __device__ __forceinline__ void rf_synth_body(const RfKernelArgs &A, int logm, int jcut)
+#endif
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int N = A.nsamp, M = N / 2;
@@ -613,7 +632,11 @@ __device__ __forceinline__ void rf_synth_body(const RfKernelArgs &A, int logm, i
     // its columns are zeros and the workgroup leaves -- no recursion, no transform.  (A site call writes the trace, never the sums.)
     if (A.coef[(size_t)ib * rec_doubles(A.Lmax) + 3] == 2.0) {
         double *zero = A.rf + (size_t)ib * A.ldr;
+#if BH_RF_SITEAXIS
+        for (int i = (int)threadIdx.x; i < ncap; i += nthr) zero[i] = 0.0; // (A.nkeep is the site's count here: 0)
+#else
         for (int i = (int)threadIdx.x; i < A.nkeep; i += nthr) zero[i] = 0.0;
+#endif
         return;
     }
 #endif
@@ -680,6 +703,7 @@ __device__ __forceinline__ void rf_synth_body(const RfKernelArgs &A, int logm, i
     }
     const double scale = 1.0 / (double)N;
     const int shift = 32 - logm;
+#if !BH_RF_SITEAXIS // (a site call writes the trace, never the sums: the branch is left out of the site-axis builds)
     if (A.sums != nullptr && nthr == 256) {
         // Fused likelihood: the kept samples never leave the CU.  The sums are formed exactly as like_kernel forms them
         // from a stored trace -- thread t takes samples t, t + 256, ... in order, a butterfly per wavefront, the four
@@ -737,15 +761,50 @@ __device__ __forceinline__ void rf_synth_body(const RfKernelArgs &A, int logm, i
 #undef BH_NOFUSE
         return;
     }
+#endif
     double *out = A.rf + (size_t)ib * A.ldr;
     for (int m = tid; 2 * m < A.nkeep; m += nthr) {
         const double2 v = z[(int)(__brev((unsigned)m) >> shift)];
         out[2 * m] = scale * v.x;
         if (2 * m + 1 < A.nkeep) out[2 * m + 1] = scale * v.y;
     }
+#if BH_RF_SITEAXIS
+    for (int i = A.nkeep + tid; i < ncap; i += nthr) out[i] = 0.0; // the columns beyond the site's own samples
+#endif
 }
 // Two register budgets of the same text: 4 wavefronts per SIMD (128 VGPRs, a few spilled) and 3 (168, none);
 // bh_launch_rf picks (BH_RF_WAVES overrides, for measurements).
+#if BH_RF_SITEAXIS
+// One model of a site-axis launch.  The site index and the site's record are uniform over the workgroup (ib is the workgroup's
+// index: scalar loads) and read before any barrier.  A site out of range has no record: its columns get NaN (the likelihood fails
+// the model in band, as the coefficient stage's bad mark does in the other builds) and the workgroup leaves.
+__device__ __forceinline__ void rf_synth_t_entry(RfKernelArgs A, const RfSiteT &S, int no_cut)
+{
+    const int ib = blockIdx.x, ncap = A.nkeep;
+    const int site = S.site[ib];
+    const bool off_table = site < 0 || site >= S.nsites;
+    // (the record is read before the first store of the kernel, so that the loads stay scalar; off the table: row 0, unused)
+    const size_t row = off_table ? 0 : (size_t)site * S.ld;
+    const RfAxisRec r = S.axis[row];
+    const int nown = S.n[row];
+    if (off_table) {
+        double *o = A.rf + (size_t)ib * A.ldr;
+        for (int i = (int)threadIdx.x; i < ncap; i += (int)blockDim.x) o[i] = __longlong_as_double(0x7ff8000000000000ll);
+        return;
+    }
+    A.nsamp = r.nsamp; A.fsamp = r.fsamp; A.tshift = r.tshift; A.gauss = r.gauss;
+    A.nkeep = nown;
+    rf_synth_body<false>(A, r.logm, no_cut ? r.nsamp / 2 + 1 : r.jcut, ncap);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void rf_synth_t_kernel(RfKernelArgs A, RfSiteT S, int no_cut)
+{
+    rf_synth_t_entry(A, S, no_cut);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void rf_synth_t_kernel_w3(RfKernelArgs A, RfSiteT S, int no_cut)
+{
+    rf_synth_t_entry(A, S, no_cut);
+}
+#else
 #if BH_RF_MISSING
 // (the builds whose workgroup leaves when its record is marked absent: names of their own, for kernel traces)
 #define rf_synth_kernel rf_synth_m_kernel
@@ -765,6 +824,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 {
     rf_synth_body<true>(A, logm, jcut);
 }
+#endif
 
 #if !BH_RF_MISSING
 // Probe of the elementary functions above (bh_probe_math ops 11-16): the same inlined text, built with this file's flags,
@@ -812,25 +872,46 @@ size_t bh_rf_lds_bytes(int nsamp)
 
 #endif
 
-#if BH_RF_MISSING
+#if BH_RF_SITEAXIS
+// logm and jcut of one site's axis: the expressions of the launcher below
+RfAxisRec bh_rf_axis_record(int nsamp, double fsamp, double tshift, double gauss)
+{
+    const int half = nsamp / 2;
+    int logm = 0;
+    while ((1 << logm) < half) ++logm;
+    const double dw = 2.0 * M_PI * fsamp / nsamp;
+    const double jc = std::floor(RF_CUT_WA * gauss / dw) + 1.0;
+    const int jcut = !(jc < (double)half) ? half + 1 : (int)jc;
+    return RfAxisRec{fsamp, tshift, gauss, nsamp, logm, jcut, 0};
+}
+
+int bh_launch_rf_t(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteTArgs &msites)
+#elif BH_RF_MISSING
 int bh_launch_rf_m(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteMArgs &msites)
 #else
 int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs *sites)
 #endif
 {
 #if BH_RF_MISSING
-    const RfSiteMArgs *sites = &msites; // (this build has site kernels only)
+    const RfSiteT *sites = &msites; // (this build has site kernels only)
 #endif
     RfKernelArgs a = a_in;
     const BhTuning &tun = bh_tuning(); // (experiment switches, bh_tuning.h)
     a.no_realc = tun.rf_no_realc != 0 ? 1 : 0;
     a.no_rot = tun.rf_no_rot != 0 ? 1 : 0;
     const int nthr = (tun.rf_threads == 128) ? 128 : 256;
+#if BH_RF_SITEAXIS
+    // every workgroup holds the LDS of the column's longest trace: a site's own tables lie inside it (bh_rf_lds_bytes grows with nsamp)
+    size_t lds = bh_rf_lds_bytes(msites.nsamp_max);
+    const bool longtrace = false;
+    if (lds > BH_RF_MAX_LDS) return -1;
+#else
     const int half = a.nsamp / 2;
     int logm = 0;
     while ((1 << logm) < half) ++logm;
     size_t lds = bh_rf_lds_bytes(a.nsamp); // half-length complex spectrum + Nyquist bin + two twiddle tables
     const bool longtrace = lds > BH_RF_MAX_LDS;
+#endif
     if (longtrace) {
         if (a.zwork == nullptr || a.nsamp > BH_RF_MAX_NSAMP) return -1;
         lds -= (size_t)(a.nsamp / 2) * 16; // (the spectrum is in the workspace)
@@ -839,7 +920,11 @@ int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs 
     if (lds < (size_t)a.lds_min) lds = (size_t)a.lds_min;
     if (lds > 64 * 1024) { // beyond the default dynamic-LDS limit: a workgroup may take the CU's whole 160 KB
         static std::atomic<unsigned long long> allowed{0};
+#if BH_RF_SITEAXIS
+        const void *k[2] = {reinterpret_cast<const void *>(rf_synth_t_kernel), reinterpret_cast<const void *>(rf_synth_t_kernel_w3)};
+#else
         const void *k[2] = {reinterpret_cast<const void *>(rf_synth_kernel), reinterpret_cast<const void *>(rf_synth_kernel_w3)};
+#endif
         if (!bh_allow_big_lds(&allowed, k, 2, (int)BH_RF_MAX_LDS)) return -1;
     }
     if (sites) { // (the same choice of build, each with its site variant)
@@ -874,6 +959,14 @@ int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs 
     // a = 2.5, 20 Hz, nsamp 2048 that is every bin above 5.0 Hz: 510 of 1025 are computed, 8 passes of 64 lanes per model
     // (round 2 cut at 1e-30: 678 bins, 11 passes).  tests/test_gpu_rf.py compares with the uncut transform (1e-13).
     const bool no_cut = tun.rf_no_cut != 0; // (tests flip it with bh_engine_set_tuning)
+#if BH_RF_SITEAXIS
+    // (the sites' jcut are in their records, formed by bh_rf_axis_record; the switch reaches the kernel as an argument)
+    if (tun.rf_waves == 3)
+        hipLaunchKernelGGL(rf_synth_t_kernel_w3, dim3(a.B), dim3(nthr), lds, stream, a, msites, no_cut ? 1 : 0);
+    else
+        hipLaunchKernelGGL(rf_synth_t_kernel, dim3(a.B), dim3(nthr), lds, stream, a, msites, no_cut ? 1 : 0);
+    return 0;
+#else
     const double dw = 2.0 * M_PI * a.fsamp / a.nsamp;
     const double jc = std::floor(RF_CUT_WA * a.gauss / dw) + 1.0;
     const int jcut = (no_cut || !(jc < (double)half)) ? half + 1 : (int)jc;
@@ -884,4 +977,5 @@ int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs 
     else
         hipLaunchKernelGGL(rf_synth_kernel, dim3(a.B), dim3(nthr), lds, stream, a, logm, jcut);
     return 0;
+#endif
 }

@@ -162,6 +162,8 @@ def load_library():
     L.bh_sites_set_missing.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_sites_set_missing_gauss.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_sites_set_gauss.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.bh_sites_set_axes.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.bh_sites_set_rf_axis.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_chain_propose_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, vp]
     L.bh_chain_propose_window_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp]
     _cc, _cs, _cp = C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_void_p   # (the table of records is a device pointer)
@@ -188,7 +190,7 @@ def load_library():
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
                  "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all",
-                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_GAUSS_SYMBOLS + SITE_PRIORS_SYMBOLS:
+                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_GAUSS_SYMBOLS + SITE_PRIORS_SYMBOLS + SITE_RF_AXIS_SYMBOLS:
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -221,6 +223,8 @@ SITE_X_ALL_SYMBOLS = ("bh_sites_set_x_all",)
 SITE_MISSING_SYMBOLS = ("bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites")
 # include/bh_engine_sites_gauss.h: a Gauss-law noise correlation per site
 SITE_GAUSS_SYMBOLS = ("bh_sites_set_gauss", "bh_sites_set_missing_gauss")
+# include/bh_engine_sites_rf_axis.h: a receiver-function time axis and Gauss filter per site
+SITE_RF_AXIS_SYMBOLS = ("bh_sites_set_axes", "bh_sites_set_rf_axis")
 # include/bh_engine_sites_priors.h: chains under their own site's priors and sampler settings
 SITE_PRIORS_SYMBOLS = ("bh_chain_propose_priors", "bh_chain_propose_window_priors", "bh_chain_accept_priors",
                        "bh_chain_accept_window_priors")
@@ -602,6 +606,23 @@ class Engine(object):
         """set_sites_missing that accepts a Gauss-law target which some site lacks (bh_sites_set_missing_gauss); such a target
         then needs its table of correlation classes (set_sites_gauss, the lacking sites in class -1) before evaluate_sites."""
         self._set_sites_x(self._L.bh_sites_set_missing_gauss, n, x, yobs, yerr)
+
+    def set_sites_axes(self, n, x, yobs, yerr=None):
+        """set_sites_missing_gauss where a receiver function's count may be 0 or 1 .. its descriptor's n, the capacity of its
+        columns (bh_sites_set_axes).  A count that differs from the descriptor's then needs set_sites_rf and set_sites_rf_axis
+        before evaluate_sites -- and, Gauss law, the padded class table of set_sites_gauss."""
+        self._set_sites_x(self._L.bh_sites_set_axes, n, x, yobs, yerr)
+
+    def set_sites_rf_axis(self, nsamp, fsamp, tshift, gauss):
+        """The receiver-function transform length nsamp (int32), sampling rate fsamp (Hz), time shift tshift (s) and Gauss width
+        gauss of every site (bh_sites_set_rf_axis): arrays [nsites, ntargets], read in the columns of receiver-function targets
+        only.  evaluate_sites then synthesises a model's trace on its site's own axis.  Register it after set_sites_rf, which
+        drops it as set_sites* and set_targets do, and before set_sites_gauss."""
+        nsamp = np.ascontiguousarray(nsamp, dtype=np.int32)
+        fsamp, tshift, gauss = _f64(fsamp), _f64(tshift), _f64(gauss)
+        if nsamp.ndim != 2 or nsamp.shape[1] != self.ntargets or any(a.shape != nsamp.shape for a in (fsamp, tshift, gauss)):
+            raise ValueError("nsamp, fsamp, tshift and gauss must have shape (nsites, %d)" % self.ntargets)
+        self._check(self._L.bh_sites_set_rf_axis(self._h, nsamp.shape[0], _ptr(nsamp), _ptr(fsamp), _ptr(tshift), _ptr(gauss)))
 
     def set_sites_gauss(self, target, class_of, rinv, logdet_r):
         """The noise-correlation classes of Gauss-law target `target` for the site table in force (bh_sites_set_gauss):

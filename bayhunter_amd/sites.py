@@ -14,6 +14,8 @@ not have every target of the array (missing=True, include/bh_engine_sites_missin
 in the slots it lacks, and each of its models is evaluated -- and each of its chains walks -- as in a one-site run over the targets
 the site has.  The fixed noise correlation of a Gauss-law target -- a receiver function's usual configuration -- may differ between
 sites too (per_site_corr=True, include/bh_engine_sites_gauss.h): the sites' matrices R^-1 are registered once per distinct value.
+And so may a receiver function's time axis and Gauss filter (per_site_rf="all", include/bh_engine_sites_rf_axis.h): window, sampling
+rate, sample count and filter width are then a station's own, and each model's trace is synthesised on its site's axis.
 """
 import numpy as np
 
@@ -69,6 +71,10 @@ def _bits(a):
 
 # the receiver-function call arguments that may differ between sites with per_site_rf=True (RFminiModRF._call_args)
 SITE_RF_ARGS = ("p", "nsv")
+# ... and with per_site_rf="all": everything but the wave type
+SITE_RF_AXIS_ARGS = SITE_RF_ARGS + ("gauss", "nsamp", "fsamp", "tshift", "nkeep")
+# the longest transform of a site with per_site_rf="all" (include/bh_engine_sites_rf_axis.h: BH_SITES_RF_AXIS_MAX_NSAMP)
+SITE_RF_AXIS_MAX_NSAMP = 16384
 
 
 class SiteTargets(object):
@@ -92,6 +98,14 @@ class SiteTargets(object):
     flattened: group-velocity and higher-mode targets may differ in their periods and their number as well (a station's group
     curve has its own usable band just as its phase curve has).  A group velocity's two roots per period and the mode loop
     are searched at the model's own site's periods -- the bits of a one-site run.  Receiver functions still share x.
+
+    per_site_rf="all" (needs per_site_x="all"): as True, and the receiver functions of the sites may differ in their time axis x as
+    well -- hence in nsamp, fsamp, tshift and the number of samples -- and in the filter width `gauss`; only the wave type and the
+    noise law must match.  Each model's trace is then synthesised on its own site's axis with its own site's filter, the bits of a
+    one-site run over the site's samples; in the synthetics a site's samples are followed by zeros up to the largest count of any
+    site.  A site's transform has at most 16384 points (8192 observed samples).  Under the Gauss law the shapes of corr_inv follow
+    the sample counts; sites whose counts differ then need per_site_corr=True (`gauss_class_arrays` embeds every site's matrix
+    in a zero matrix of the capacity).
 
     missing=True (needs per_site_x="all"): a site may LACK some of the array's targets.  Every site is then a sequence of the
     same length, target or None: position i is SLOT i, which has one class, one plugin parameter set and one noise law wherever
@@ -124,7 +138,11 @@ class SiteTargets(object):
         if len(self._names) != len(self._sites) or len(set(self._names)) != len(self._names):
             raise ValueError("names must be %d distinct names, one per site" % len(self._sites))
         self._engine = engine
-        self.per_site_rf = bool(per_site_rf)
+        if isinstance(per_site_rf, str) and per_site_rf != "all":
+            raise ValueError("per_site_rf is False, True or \"all\", not %r" % (per_site_rf,))
+        self.per_site_rf = "all" if isinstance(per_site_rf, str) else bool(per_site_rf)
+        if self.per_site_rf == "all" and per_site_x != "all":
+            raise ValueError("per_site_rf=\"all\" needs per_site_x=\"all\" (the table of counts it extends)")
         if isinstance(per_site_x, str) and per_site_x != "all":
             raise ValueError("per_site_x is False, True or \"all\", not %r" % (per_site_x,))
         self.per_site_x = "all" if isinstance(per_site_x, str) else bool(per_site_x)
@@ -231,10 +249,15 @@ class SiteTargets(object):
         x, x0 = np.asarray(t.obsdata.x, dtype=float), np.asarray(t0.obsdata.x, dtype=float)
         same_x = x.shape == x0.shape and _bits(x) == _bits(x0)
         site_x = self.per_site_x and isinstance(t.moddata.plugin, SurfDisp) and isinstance(t0.moddata.plugin, SurfDisp)
-        if not same_x and not site_x:
+        site_axis = (self.per_site_rf == "all" and isinstance(t.moddata.plugin, RFminiModRF)
+                     and isinstance(t0.moddata.plugin, RFminiModRF))
+        if not same_x and not site_x and not site_axis:
             raise ValueError("%s: x differs from %s's (sites share x bit for bit)" % (what, whose))
         if site_x:
             self._check_site_x(what, t, x, same_x)
+        if site_axis and t.moddata.plugin.nsamp > SITE_RF_AXIS_MAX_NSAMP:
+            raise ValueError("%s: %d samples need a transform of %d points; a site has at most %d with per_site_rf=\"all\""
+                             % (what, x.size, t.moddata.plugin.nsamp, SITE_RF_AXIS_MAX_NSAMP))
         if np.size(t.obsdata.y) != x.size:
             raise ValueError("%s: y has %d values for %d samples" % (what, np.size(t.obsdata.y), x.size))
         p, p0 = t.moddata.plugin, t0.moddata.plugin
@@ -248,7 +271,8 @@ class SiteTargets(object):
         elif isinstance(p, RFminiModRF):
             a, a0 = p._call_args(), p0._call_args()
             if self.per_site_rf:
-                a, a0 = [{k: v for k, v in d.items() if k not in SITE_RF_ARGS} for d in (a, a0)]
+                free = SITE_RF_AXIS_ARGS if self.per_site_rf == "all" else SITE_RF_ARGS
+                a, a0 = [{k: v for k, v in d.items() if k not in free} for d in (a, a0)]
             if a != a0:
                 raise ValueError("%s: receiver-function parameters %r, %s's %r" % (what, a, whose, a0))
         law, law0 = t.law(), t0.law()
@@ -257,7 +281,7 @@ class SiteTargets(object):
         if law == "gauss":
             v, v0 = t.valuation, t0.valuation
             if self.per_site_corr:
-                if np.shape(v.corr_inv) != np.shape(v0.corr_inv):
+                if np.shape(v.corr_inv) != np.shape(v0.corr_inv) and not site_axis:
                     raise ValueError("%s: Gauss law with R^-1 of shape %r, %s's %r (sites share the sample count)"
                                      % (what, np.shape(v.corr_inv), whose, np.shape(v0.corr_inv)))
             elif (np.shape(v.corr_inv) != np.shape(v0.corr_inv) or _bits(v.corr_inv) != _bits(v0.corr_inv)
@@ -317,6 +341,17 @@ class SiteTargets(object):
         descs = []
         for i, t in enumerate(self.targets):
             d = t.engine_desc()
+            if d["kind"] == _engine.TARGET_RF and self.per_site_rf == "all":
+                # (a receiver function's columns hold the largest count too; nsamp is the largest transform of any site, the other
+                # axis values and the Gauss law's matrix are placeholders: the site path reads the tables)
+                cap = int(n[:, i].max())
+                d["n"] = cap
+                d["yobs"] = np.zeros(cap)
+                d["nsamp"] = max(int(row[i].moddata.plugin.nsamp) for row in self._slot_rows() if row[i] is not None)
+                if "yerr" in d:
+                    d["yerr"] = np.ones(cap)
+                if "rinv" in d and self.per_site_corr:   # (without it every site shares the descriptor's matrix, of one size)
+                    d["rinv"], d["logdet_r"] = np.eye(cap), 0.0
             if d["kind"] == _engine.TARGET_SWD and (self.per_site_x == "all" or (d["igr"] == 0 and d["mode"] <= 1)):
                 cap = int(n[:, i].max())
                 d["n"] = cap
@@ -348,11 +383,28 @@ class SiteTargets(object):
                     p[s, i], nsv[s, i] = float(a["p"]), float(a["nsv"])
         return p, nsv
 
+    def site_rf_axis_arrays(self):
+        """(nsamp[S, nt] int32, fsamp[S, nt], tshift[S, nt], gauss[S, nt]): every site's receiver-function transform length,
+        sampling rate (Hz), time shift (s) and Gauss width in the columns of its receiver-function targets; placeholders (4, 1, 0,
+        1: never read) elsewhere and where the site lacks the slot (Engine.set_sites_rf_axis)"""
+        S, nt = self.nsites, self.ntargets
+        nsamp = np.full((S, nt), 4, dtype=np.int32)
+        fsamp, tshift, gauss = np.ones((S, nt)), np.zeros((S, nt)), np.ones((S, nt))
+        for s, row in enumerate(self._slot_rows()):
+            for i, t in enumerate(row):
+                if t is not None and isinstance(t.moddata.plugin, RFminiModRF):
+                    a = t.moddata.plugin._call_args()
+                    nsamp[s, i], fsamp[s, i], tshift[s, i], gauss[s, i] = a["nsamp"], a["fsamp"], a["tshift"], a["gauss"]
+        return nsamp, fsamp, tshift, gauss
+
     def gauss_class_arrays(self):
         """per_site_corr=True: {slot: (class_of[S] int32, rinv[nclass, n, n], logdet_r[nclass])} for Engine.set_sites_gauss, one
         entry per Gauss-law slot.  The sites' (corr_inv, logcorr_det) are deduplicated by their bits, classes numbered in the
-        order of their first site; -1: the site lacks the slot."""
+        order of their first site; -1: the site lacks the slot.  per_site_rf="all": n is the slot's capacity, a site's own matrix
+        sits in the top-left corner of a zero matrix of that size (the residuals beyond its samples are exact zeros), and the
+        classes are deduplicated by (bits, own size)."""
         out = {}
+        caps = self._counts().max(axis=0)
         for i, t0 in enumerate(self.targets):
             if t0.law() != "gauss":
                 continue
@@ -363,10 +415,14 @@ class SiteTargets(object):
                     class_of.append(-1)
                     continue
                 v = t.valuation
-                key = (_bits(v.corr_inv), _bits(v.logcorr_det))
+                own = np.asarray(v.corr_inv, dtype=np.float64)
+                key = (_bits(own), _bits(v.logcorr_det), own.shape)
                 if key not in seen:
                     seen[key] = len(rinv)
-                    rinv.append(np.asarray(v.corr_inv, dtype=np.float64))
+                    if own.shape[0] < caps[i]:
+                        own, corner = np.zeros((caps[i], caps[i])), own
+                        own[:corner.shape[0], :corner.shape[1]] = corner
+                    rinv.append(own)
                     logdet.append(float(v.logcorr_det))
                 class_of.append(seen[key])
             out[i] = (np.array(class_of, dtype=np.int32), np.stack(rinv), np.array(logdet, dtype=np.float64))
@@ -388,7 +444,9 @@ class SiteTargets(object):
         if self._registered != sig or e._owner is not self:
             if self.per_site_x:
                 e.set_targets(self._capacity_descs())
-                if self.missing and self.per_site_corr:
+                if self.per_site_rf == "all":
+                    e.set_sites_axes(*self.site_x_arrays())
+                elif self.missing and self.per_site_corr:
                     e.set_sites_missing_gauss(*self.site_x_arrays())
                 elif self.missing:
                     e.set_sites_missing(*self.site_x_arrays())
@@ -402,6 +460,8 @@ class SiteTargets(object):
                 e.set_sites(yobs, yerr)
             if self.per_site_rf or self.missing:   # (missing: the coefficient stage finds the model's site through this table)
                 e.set_sites_rf(*self.site_rf_arrays())
+            if self.per_site_rf == "all":
+                e.set_sites_rf_axis(*self.site_rf_axis_arrays())
             if self.per_site_corr:                 # (last: every other registration drops the classes)
                 for i, (class_of, rinv, logdet) in sorted(self.gauss_class_arrays().items()):
                     e.set_sites_gauss(i, class_of, rinv, logdet)
