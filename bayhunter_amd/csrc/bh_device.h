@@ -452,6 +452,16 @@ struct LikeClassArgs {
     const double *logdet[8];    // device [nclass]
 };
 void bh_launch_like_sites_c(const LikeKernelArgs &a, const LikeSiteXArgs &sites, const LikeClassArgs &classes, hipStream_t stream);
+// ... and every target's noise law is that of the model's site (bh_sites_set_laws, include/bh_engine_sites_laws.h; like_kernel_l.hip,
+// like_kernel.hip compiled with BH_LIKE_LAWS on top of BH_LIKE_CLASSES).  LikeTargetDev::law of target t becomes law[site * nt + t]
+// before the site's and the class's data are looked up, so law-1 and law-3 data are read by the site's law; the descriptor's law
+// still decides the launch form and the LDS (bh_like_small_form).  An entry where the count is 0 is not read.  Law 3 stands only on
+// a target whose descriptor is under law 3; LikeSiteXArgs::yerr_scaled / logdet_extra hold law-1 data wherever the TABLE says 1.
+struct LikeLawArgs {
+    const int32_t *law; // device [nsites][nt]
+};
+void bh_launch_like_sites_l(const LikeKernelArgs &a, const LikeSiteXArgs &sites, const LikeClassArgs &classes, const LikeLawArgs &laws,
+                            hipStream_t stream);
 
 void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 

@@ -12,6 +12,7 @@
 #include "../../include/bh_engine_sites_missing.h"
 #include "../../include/bh_engine_sites_gauss.h"
 #include "../../include/bh_engine_sites_rf_axis.h"
+#include "../../include/bh_engine_sites_laws.h"
 #include "bh_device.h"
 
 #include <algorithm>
@@ -109,6 +110,7 @@ struct TargetHost {
     int gc_nclass = 0;                   // 0: no class table, every site takes the descriptor's matrix
     DevBuf gc_rinv, gc_logdet, gc_class; // [nclass][n][n], [nclass], int32 [nsites]
     bool site_lacks = false;             // the count table in force has a site with count 0 for this target
+    bool law_other = false;              // the law table in force (bh_sites_set_laws) has a present site under another law than BH_LAW_GAUSS (read for a Gauss-law target)
     bool rf_own_counts = false;          // receiver function: the count table in force (bh_sites_set_axes) has a count that is neither 0 nor the descriptor's
     int axis_nsamp_max = 0;              // receiver function: the largest nsamp of the column of bh_sites_set_rf_axis
 };
@@ -163,6 +165,10 @@ struct bh_engine {
     bool site_missing_gauss = false;          // registered by bh_sites_set_missing_gauss: a Gauss-law target some site lacks needs its class table
     DevBuf gc_xn;                             // [nsites][nt] the descriptors' counts: the count table of a class call where none is registered
     DevBuf gc_work;                           // the grouping's work space of a call (bh_gauss_class_work_words)
+    // sites with their own noise law (bh_sites_set_laws, include/bh_engine_sites_laws.h): part of the count table
+    bool site_laws = false;                   // the law table is in force
+    DevBuf law_tab, law_yerr, law_logdet;     // int32 [nsites][nt] (0 where the count is 0); the law-1 tables by the TABLE's law: [nsites][ldy], [nsites][nt]
+    std::vector<int32_t> site_law_host;       // ... the laws as registered (bh_sites_set_gauss checks its classes against them)
     // instrumentation
     bool timing = false, counting = false;
     bool no_mfma = false; // BH_NO_MFMA env: Gauss law through the in-kernel mat-vec (A/B testing)
@@ -252,6 +258,17 @@ void release_gauss_classes(bh_engine *e)
     release(e->gc_xn);
 }
 
+// the law table (it belongs to the count table: whatever registers or extends the site table drops it) and, with it, the correlation
+// classes, which were checked against it
+void release_laws(bh_engine *e)
+{
+    for (DevBuf *b : {&e->law_tab, &e->law_yerr, &e->law_logdet}) release(*b);
+    e->site_laws = false;
+    e->site_law_host.clear();
+    for (auto &t : e->targets) t.law_other = false;
+    release_gauss_classes(e);
+}
+
 // the site table's buffers (they belong to the registered targets: bh_targets_set and bh_engine_destroy release them)
 void release_sites(bh_engine *e)
 {
@@ -260,7 +277,7 @@ void release_sites(bh_engine *e)
     e->site_rf = e->site_rf_axis = false;
     e->site_x = e->site_x_all = e->site_missing = e->site_missing_gauss = false;
     e->site_xn_host.clear();
-    release_gauss_classes(e);
+    release_laws(e);
     for (auto &t : e->targets) {
         t.site_lacks = t.rf_own_counts = false;
         t.axis_nsamp_max = 0;
@@ -625,7 +642,8 @@ enum EvalRole { ROLE_NONE, ROLE_SWD, ROLE_SWD60, ROLE_RF };
 // The likelihood launcher of a fused call: bh_launch_like, bh_launch_like_sites, bh_launch_like_sites_x (a site's own sample counts)
 // (LIKE_SITES_M: bh_launch_like_sites_m, counts that may be 0)
 // (LIKE_SITES_C: bh_launch_like_sites_c, a Gauss-law target's ln|R| and R^-1 from its table of correlation classes)
-enum EvalLike { LIKE_PLAIN, LIKE_SITES, LIKE_SITES_X, LIKE_SITES_M, LIKE_SITES_C };
+// (LIKE_SITES_L: bh_launch_like_sites_l, every target's law from the table of bh_sites_set_laws)
+enum EvalLike { LIKE_PLAIN, LIKE_SITES, LIKE_SITES_X, LIKE_SITES_M, LIKE_SITES_C, LIKE_SITES_L };
 // The contraction of a Gauss-law target: with the descriptor's data and matrix, with every model's site's data, or with the matrix
 // of every model's correlation class as well (bh_sites_set_gauss)
 enum EvalGauss { GAUSS_PLAIN, GAUSS_SITES, GAUSS_CLASSES };
@@ -649,6 +667,8 @@ struct EvalPlan {
     bool rf_axis_no_mfma;       // ... under the Gauss law with the BH_NO_MFMA in-kernel mat-vec: refused
     EvalGauss gauss[BH_MAX_TARGETS]; // (read for the Gauss-law targets)
     bool gauss_needs_table;     // bh_sites_set_missing_gauss, and a Gauss-law target some site lacks has no class table: the call is refused
+    bool laws;                  // the sites' own noise laws (bh_sites_set_laws) are in force: the likelihood builds of bh_launch_like_sites_l
+    bool law_gauss_needs_table; // ... and a Gauss-law target with a present site under another law has no class table: the call is refused
     EvalLike like;
     bool err_zero_always;       // bh_tuning.h err_memset: the failure flags are zeroed on every call
 };
@@ -720,6 +740,16 @@ EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
         else if (sites && T.rf_own_counts) p.rf_axis_gauss_needs_table = true; // (the descriptor's matrix is the capacity's, no site's)
         // (the mat-vec's row stride is the site's n, the class matrices -- a site's in the corner of a zero matrix -- have the capacity's)
         if (sites && T.rf_own_counts && e->no_mfma) p.rf_axis_no_mfma = true;
+    }
+    // (sites with their own noise law, bh_sites_set_laws: the likelihood build that reads the law of (site, target) serves the call,
+    // with or without class tables; the rows of a site under another law on a Gauss-law target must be in no tile of the contraction)
+    p.laws = p.x_table && e->site_laws;
+    if (p.laws) {
+        p.like = LIKE_SITES_L;
+        for (int t = 0; t < p.nt; ++t) {
+            const TargetHost &T = e->targets[(size_t)t];
+            if (T.d.law == BH_LAW_GAUSS && T.law_other && p.gauss[t] != GAUSS_CLASSES) p.law_gauss_needs_table = true;
+        }
     }
     p.err_zero_always = tun.err_memset != 0;
     return p;
@@ -1857,6 +1887,7 @@ int eval_args_ok(bh_engine *e, const EvalPlan &p, bool host, const EvalCall &c)
     if (p.rf_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_missing with a receiver-function target needs bh_sites_set_rf");
     if (p.rf_axis_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_axes with a receiver-function count that differs from its descriptor's needs the table of bh_sites_set_rf_axis");
     if (p.gauss_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_missing_gauss with a Gauss-law target that a site lacks needs the table of bh_sites_set_gauss");
+    if (p.law_gauss_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_laws with a Gauss-law target that has a site under another law needs the table of bh_sites_set_gauss (that site in class -1)");
     if (p.rf_axis_gauss_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_axes with a Gauss-law receiver function whose counts differ from its descriptor's needs the table of bh_sites_set_gauss (every site's matrix padded to the capacity)");
     if (p.rf_axis_no_mfma) return fail(e, BH_EUNSUPPORTED, "BH_NO_MFMA: the in-kernel mat-vec does not serve a Gauss-law receiver function with per-site counts (bh_sites_set_axes)");
     if (!c.m.nlay || !c.m.h || !c.m.vp || !c.m.vs || !c.la.noise || !c.la.logL || !c.la.misfits || !c.la.err) return fail(e, BH_EINVAL, "null argument");
@@ -1989,7 +2020,7 @@ int run_like(bh_engine *e, hipStream_t st, LikeKernelArgs la, const bool *fused,
     LikeSiteXArgs lx{};
     lx.site = site; lx.nsites = e->nsites; lx.yobs = (const double *)e->site_yobs.p; lx.yerr_scaled = (const double *)e->site_yerr.p;
     lx.logdet_extra = (const double *)e->site_logdet.p; lx.n = (const int32_t *)e->site_xn.p;
-    if (like == LIKE_SITES_C) { // (the count table: the registered one, or the descriptors' counts where the call has none)
+    if (like == LIKE_SITES_C || like == LIKE_SITES_L) { // (the count table: the registered one, or the descriptors' counts where the call has none)
         LikeClassArgs lc{};
         for (int t = 0; t < la.nt; ++t) {
             const TargetHost &T = e->targets[(size_t)t];
@@ -2000,7 +2031,14 @@ int run_like(bh_engine *e, hipStream_t st, LikeKernelArgs la, const bool *fused,
         }
         if (!e->site_x) lx.n = (const int32_t *)e->gc_xn.p;
         ev_begin(e, 2, st);
-        bh_launch_like_sites_c(la, lx, lc, st);
+        if (like == LIKE_SITES_L) { // (the law-1 tables formed by the table's laws; a law table comes with a count table)
+            lx.yerr_scaled = (const double *)e->law_yerr.p;
+            lx.logdet_extra = (const double *)e->law_logdet.p;
+            const LikeLawArgs lw{(const int32_t *)e->law_tab.p};
+            bh_launch_like_sites_l(la, lx, lc, lw, st);
+        } else {
+            bh_launch_like_sites_c(la, lx, lc, st);
+        }
         ev_end(e, 2, st);
         return BH_OK;
     }
@@ -2237,6 +2275,12 @@ int bh_sites_set_gauss(bh_engine *e, int target, int nsites, int nclass, const i
         const int c = class_of[s];
         if (c < -1 || c >= nclass) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a class index outside [-1, nclass)");
         const bool has = e->site_xn_host.empty() || e->site_xn_host[s * nt + (size_t)target] != 0; // (bh_sites_set: every site has every target)
+        if (has && e->site_laws) { // (bh_sites_set_laws: a class exactly for the sites under the Gauss law on this target)
+            const bool gauss = e->site_law_host[s * nt + (size_t)target] == BH_LAW_GAUSS;
+            if (gauss && c < 0) return fail(e, BH_EINVAL, "bh_sites_set_gauss: class -1 for a site under the Gauss law on the target (bh_sites_set_laws)");
+            if (!gauss && c >= 0) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a class for a site under another law than BH_LAW_GAUSS on the target (bh_sites_set_laws)");
+            continue;
+        }
         if (has && c < 0) return fail(e, BH_EINVAL, "bh_sites_set_gauss: class -1 for a site that has the target");
         if (!has && c >= 0) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a class for a site that lacks the target (count 0)");
     }
@@ -2265,6 +2309,56 @@ int bh_sites_set_gauss(bh_engine *e, int target, int nsites, int nclass, const i
     return BH_OK;
 }
 
+int bh_sites_set_laws(bh_engine *e, int nsites, const int32_t *law, const double *yerr)
+{
+    if (!e) return BH_EINVAL;
+    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (!e->site_x || !e->site_missing_gauss)
+        return fail(e, BH_EINVAL, "bh_sites_set_laws: no count table registered that accepts a Gauss-law target some site lacks (bh_sites_set_missing_gauss, bh_sites_set_axes)");
+    if (nsites != e->nsites) return fail(e, BH_EINVAL, "bh_sites_set_laws: nsites differs from the site table's");
+    if (!law) return fail(e, BH_EINVAL, "null argument");
+    const int nt = e->nt, ldy = e->ldy;
+    const size_t S = (size_t)nsites;
+    std::vector<int32_t> lw(S * nt, 0); // (0 where the count is 0: the caller's entry is not read)
+    std::vector<double> se(S * ldy, 1.0), ld(S * nt, 0.0);
+    std::vector<char> other((size_t)nt, 0);
+    for (size_t s = 0; s < S; ++s)
+        for (int t = 0; t < nt; ++t) {
+            const TargetHost &T = e->targets[(size_t)t];
+            const int ns = e->site_xn_host[s * nt + t];
+            if (ns == 0) continue; // (the site lacks the target)
+            const int l = law[s * nt + t];
+            if (l != BH_LAW_NOCORR && l != BH_LAW_NOCORR_SCALED && l != BH_LAW_EXP && l != BH_LAW_GAUSS)
+                return fail(e, BH_EINVAL, "bh_sites_set_laws: an unknown noise law");
+            if (l == BH_LAW_GAUSS && T.d.law != BH_LAW_GAUSS)
+                return fail(e, BH_EINVAL, "bh_sites_set_laws: BH_LAW_GAUSS on a target whose descriptor is not BH_LAW_GAUSS (the descriptor owns the contraction's shape and workspace)");
+            if (l == BH_LAW_NOCORR_SCALED) { // Targets.py:124-128, over the site's own samples
+                if (!yerr) return fail(e, BH_EINVAL, "bh_sites_set_laws: a BH_LAW_NOCORR_SCALED pair needs yerr");
+                for (int i = 0; i < ns; ++i) {
+                    const double v = yerr[s * ldy + T.off + i];
+                    if (!std::isfinite(v) || !(v > 0.0)) return fail(e, BH_EINVAL, "bh_sites_set_laws: an error that is not finite and positive under BH_LAW_NOCORR_SCALED");
+                }
+                ld[s * nt + t] = scaled_errors(yerr + s * ldy + T.off, ns, se.data() + s * ldy + T.off);
+            }
+            if (l != BH_LAW_GAUSS) other[(size_t)t] = 1;
+            lw[s * nt + t] = l;
+        }
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    release_laws(e); // (and the class tables, which were checked against the laws in force before)
+    int rc;
+    if ((rc = ensure(e, e->law_tab, S * nt * sizeof(int32_t))) || (rc = ensure(e, e->law_yerr, S * ldy * sizeof(double))) ||
+        (rc = ensure(e, e->law_logdet, S * nt * sizeof(double))))
+        return rc;
+    HIPCHK(e, hipMemcpy(e->law_tab.p, lw.data(), S * nt * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->law_yerr.p, se.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->law_logdet.p, ld.data(), S * nt * sizeof(double), hipMemcpyHostToDevice));
+    for (int t = 0; t < nt; ++t) e->targets[(size_t)t].law_other = other[(size_t)t] != 0;
+    e->site_law_host = lw;
+    e->site_laws = true;
+    return BH_OK;
+}
+
 int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const double *nsv)
 {
     if (!e) return BH_EINVAL;
@@ -2282,7 +2376,7 @@ int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const d
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->site_rf = e->site_rf_axis = false; // (the axis table belongs to this one)
-    release_gauss_classes(e); // (every entry point that registers or extends the site table drops the correlation classes)
+    release_laws(e); // (every entry point that registers or extends the site table drops the law table and the correlation classes)
     int rc;
     if ((rc = ensure(e, e->site_p, n * sizeof(double))) || (rc = ensure(e, e->site_nsv, n * sizeof(double)))) return rc;
     HIPCHK(e, hipMemcpy(e->site_p.p, p_s_per_deg, n * sizeof(double), hipMemcpyHostToDevice));
@@ -2324,7 +2418,7 @@ int bh_sites_set_rf_axis(bh_engine *e, int nsites, const int32_t *nsamp, const d
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->site_rf_axis = false;
-    release_gauss_classes(e); // (every entry point that registers or extends the site table drops the correlation classes)
+    release_laws(e); // (every entry point that registers or extends the site table drops the law table and the correlation classes)
     int rc;
     if ((rc = ensure(e, e->site_axis, recs.size() * sizeof(RfAxisRec)))) return rc;
     HIPCHK(e, hipMemcpy(e->site_axis.p, recs.data(), recs.size() * sizeof(RfAxisRec), hipMemcpyHostToDevice));

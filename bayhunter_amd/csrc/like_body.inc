@@ -27,7 +27,9 @@
         failed = failed || (S.n[(size_t)site * A.nt + t] != 0 && A.err_t[(size_t)t * A.B + ib] != 0);
 #endif
     for (int t = 0; t < A.nt && !failed; ++t) {
-#if BH_LIKE_CLASSES
+#if BH_LIKE_LAWS
+        const LikeTargetDev T = class_target(site_target(law_target(A.t[t], W, site, A.nt, t), S, site, A.ldy, A.nt, t), G, site, t); // (like_kernel_l.hip)
+#elif BH_LIKE_CLASSES
         const LikeTargetDev T = class_target(site_target(A.t[t], S, site, A.ldy, A.nt, t), G, site, t); // (like_kernel_c.hip)
 #else
         const LikeTargetDev T = SITES ? site_target(A.t[t], S, site, A.ldy, A.nt, t) : A.t[t];

@@ -27,6 +27,15 @@
 #ifndef BH_LIKE_CLASSES
 #define BH_LIKE_CLASSES 0
 #endif
+// BH_LIKE_LAWS (like_kernel_l.hip, on top of BH_LIKE_CLASSES): the builds for sites with their own noise LAW (bh_sites_set_laws,
+// include/bh_engine_sites_laws.h) -- the two kernels of BH_LIKE_CLASSES with every target's law from the table law[site][target] --
+// and their launcher only.  A law is uniform over a model's lanes: in the workgroup form one workgroup is one model, so the
+// barriers of block_sum that sit under T.law conditions (and those of the in-kernel mat-vec) stay uniform; in the small form one
+// wavefront is one model, and that form has no barrier.  The sums s0, s1, sw, d0, dn are formed in the order they have under any
+// law and the law only selects among them: a model gets the bits of a launch whose descriptors hold its site's laws.
+#ifndef BH_LIKE_LAWS
+#define BH_LIKE_LAWS 0
+#endif
 
 namespace {
 
@@ -72,6 +81,16 @@ __device__ __forceinline__ LikeTargetDev class_target(LikeTargetDev T, const Lik
             T.rinv = G.rinv[t] + (size_t)c * T.n * T.n;
         }
     }
+    return T;
+}
+#endif
+
+#if BH_LIKE_LAWS
+// ... of a site with its own noise law: the law of (site, target) from the table, set BEFORE site_target / class_target so that
+// they read the law-1 tables and the class's ln|R| / R^-1 by the site's law (a count of 0 is skipped before the law is used)
+__device__ __forceinline__ LikeTargetDev law_target(LikeTargetDev T, const LikeLawArgs &W, int site, int nt, int t)
+{
+    T.law = W.law[(size_t)site * nt + t];
     return T;
 }
 #endif
@@ -154,6 +173,17 @@ __global__ void probe_kernel(int op, int n, const double *in, double *out)
     out[i] = r;
 }
 
+#elif BH_LIKE_LAWS
+__global__ __launch_bounds__(256) void like_sites_l_kernel(LikeKernelArgs A, LikeSiteXArgs S, LikeClassArgs G, LikeLawArgs W)
+{
+    constexpr bool SITES = true;
+#include "like_body.inc"
+}
+__global__ __launch_bounds__(256) void like_small_sites_l_kernel(LikeKernelArgs A, LikeSiteXArgs S, LikeClassArgs G, LikeLawArgs W)
+{
+    constexpr bool SITES = true;
+#include "like_small_body.inc"
+}
 #elif BH_LIKE_CLASSES
 __global__ __launch_bounds__(256) void like_sites_c_kernel(LikeKernelArgs A, LikeSiteXArgs S, LikeClassArgs G)
 {
@@ -181,7 +211,16 @@ __global__ __launch_bounds__(256) void like_small_sites_m_kernel(LikeKernelArgs 
 
 } // namespace
 
-#if BH_LIKE_CLASSES
+#if BH_LIKE_LAWS
+void bh_launch_like_sites_l(const LikeKernelArgs &a, const LikeSiteXArgs &sites, const LikeClassArgs &classes, const LikeLawArgs &laws,
+                            hipStream_t stream)
+{
+    size_t lds = 0;
+    const bool small = bh_like_small_form(a, &lds); // (by the descriptors: a Gauss-law descriptor owns the contraction's workspace and the LDS)
+    if (small) hipLaunchKernelGGL(like_small_sites_l_kernel, dim3((a.B + 3) / 4), dim3(256), 0, stream, a, sites, classes, laws);
+    else hipLaunchKernelGGL(like_sites_l_kernel, dim3(a.B), dim3(256), lds, stream, a, sites, classes, laws);
+}
+#elif BH_LIKE_CLASSES
 void bh_launch_like_sites_c(const LikeKernelArgs &a, const LikeSiteXArgs &sites, const LikeClassArgs &classes, hipStream_t stream)
 {
     size_t lds = 0;

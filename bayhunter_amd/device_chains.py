@@ -186,8 +186,8 @@ class DeviceChains(object):
         SHARED_INITPARAMS must agree (ValueError).  A site's chains then run under the site's own record of a table
         (include/bh_engine_sites_priors.h) and walk the one-site run made with the site's dicts, bit for bit; the arrays have the
         rows of the largest `layers` maximum, `samples(site=s)`, the saved chain files and <name>_config.pkl the site's own row
-        width, priors and initparams.  The sites still share every slot's installed noise law (SiteTargets.check).  Sites whose
-        merged dicts agree, or one dict, take the calls without a table exactly as before; prior_table=True forces the table
+        width, priors and initparams.  The sites share every slot's installed noise law (SiteTargets.check) unless the set was
+        made with per_site_law=True, which gives every (site, slot) the law its own priors install.  Sites whose merged dicts agree, or one dict, take the calls without a table exactly as before; prior_table=True forces the table
         (for measurements).  `self.priors` / `self.initparams` are site 0's; `self.site_priors` / `self.site_initparams` every
         site's."""
         self.sites = targets if isinstance(targets, SiteTargets) else None

@@ -164,6 +164,7 @@ def load_library():
     L.bh_sites_set_gauss.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.bh_sites_set_axes.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.bh_sites_set_rf_axis.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.bh_sites_set_laws.argtypes = [vp, C.c_int, vp, vp]
     L.bh_chain_propose_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, vp]
     L.bh_chain_propose_window_sites.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp]
     _cc, _cs, _cp = C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_void_p   # (the table of records is a device pointer)
@@ -190,7 +191,7 @@ def load_library():
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
                  "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all",
-                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_GAUSS_SYMBOLS + SITE_PRIORS_SYMBOLS + SITE_RF_AXIS_SYMBOLS:
+                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_GAUSS_SYMBOLS + SITE_PRIORS_SYMBOLS + SITE_RF_AXIS_SYMBOLS + SITE_LAWS_SYMBOLS:
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -225,6 +226,8 @@ SITE_MISSING_SYMBOLS = ("bh_sites_set_missing", "bh_chain_propose_sites", "bh_ch
 SITE_GAUSS_SYMBOLS = ("bh_sites_set_gauss", "bh_sites_set_missing_gauss")
 # include/bh_engine_sites_rf_axis.h: a receiver-function time axis and Gauss filter per site
 SITE_RF_AXIS_SYMBOLS = ("bh_sites_set_axes", "bh_sites_set_rf_axis")
+# include/bh_engine_sites_laws.h: a noise law per (site, target)
+SITE_LAWS_SYMBOLS = ("bh_sites_set_laws",)
 # include/bh_engine_sites_priors.h: chains under their own site's priors and sampler settings
 SITE_PRIORS_SYMBOLS = ("bh_chain_propose_priors", "bh_chain_propose_window_priors", "bh_chain_accept_priors",
                        "bh_chain_accept_window_priors")
@@ -623,6 +626,22 @@ class Engine(object):
         if nsamp.ndim != 2 or nsamp.shape[1] != self.ntargets or any(a.shape != nsamp.shape for a in (fsamp, tshift, gauss)):
             raise ValueError("nsamp, fsamp, tshift and gauss must have shape (nsites, %d)" % self.ntargets)
         self._check(self._L.bh_sites_set_rf_axis(self._h, nsamp.shape[0], _ptr(nsamp), _ptr(fsamp), _ptr(tshift), _ptr(gauss)))
+
+    def set_sites_laws(self, law, yerr=None):
+        """The noise law of every (site, target) for the count table in force (bh_sites_set_laws): law[nsites, ntargets] int32
+        (LAW_NOCORR .. LAW_GAUSS; an entry where the site's count is 0 is not read; LAW_GAUSS only on a target whose descriptor
+        is LAW_GAUSS) and yerr[nsites, ldy], the sites' errors in the count table's layout, read where the law is
+        LAW_NOCORR_SCALED (None: no such pair).  evaluate_sites then evaluates every model under its own site's laws.  Register
+        it after set_sites_missing_gauss / set_sites_axes and the receiver-function tables, which drop it as set_targets does,
+        and before set_sites_gauss, which it drops: the classes are checked against the laws (-1 for a site under another law)."""
+        law = np.ascontiguousarray(law, dtype=np.int32)
+        if law.ndim != 2 or law.shape[1] != self.ntargets:
+            raise ValueError("law must have shape (nsites, %d)" % self.ntargets)
+        if yerr is not None:
+            yerr = _f64(yerr)
+            if yerr.shape != (law.shape[0], self.ldy):
+                raise ValueError("yerr must have shape (nsites, %d)" % self.ldy)
+        self._check(self._L.bh_sites_set_laws(self._h, law.shape[0], _ptr(law), _ptr(yerr)))
 
     def set_sites_gauss(self, target, class_of, rinv, logdet_r):
         """The noise-correlation classes of Gauss-law target `target` for the site table in force (bh_sites_set_gauss):

@@ -16,6 +16,8 @@ the site has.  The fixed noise correlation of a Gauss-law target -- a receiver f
 sites too (per_site_corr=True, include/bh_engine_sites_gauss.h): the sites' matrices R^-1 are registered once per distinct value.
 And so may a receiver function's time axis and Gauss filter (per_site_rf="all", include/bh_engine_sites_rf_axis.h): window, sampling
 rate, sample count and filter width are then a station's own, and each model's trace is synthesised on its site's axis.
+Last, the installed noise LAW of a slot may differ between sites (per_site_law=True, include/bh_engine_sites_laws.h): the sampler
+installs a target's law from the station's own priors and data, so stations with their own priors differ in them.
 """
 import numpy as np
 
@@ -63,6 +65,14 @@ def gather_slots(present, noise, misfits):
     """The inverse of scatter_slots: the site's own columns of noise[..., 2 nslots] and misfits[..., nslots + 1]."""
     ncol, mcol = slot_columns(present)
     return np.asarray(noise)[..., ncol], np.asarray(misfits)[..., mcol]
+
+
+def _law_or_none(t):
+    """t.law(), or None while no law is installed (the sampler installs it)"""
+    try:
+        return t.law()
+    except RuntimeError:
+        return None
 
 
 def _bits(a):
@@ -121,11 +131,27 @@ class SiteTargets(object):
     bits into correlation CLASSES and one table per Gauss-law target is registered (`gauss_class_arrays`,
     Engine.set_sites_gauss); each model is contracted with its own site's matrix, the bits of its one-site evaluation in a
     batch of the same size.  With missing=True a Gauss-law slot may then be absent at some sites (class -1).  Still refused: a
-    Gauss-law dispersion target with periods per site; sites whose installed laws differ ('gauss' against 'exp')."""
+    Gauss-law dispersion target with periods per site; without per_site_law, sites whose installed laws differ ('gauss' against
+    'exp').
 
-    def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False, missing=False, per_site_corr=False):
+    per_site_law=True (needs missing=True): the sites' installed noise laws may differ slot by slot -- error bars at one station
+    and none at another ('nocorr_scalederr' / 'nocorr'), a correlation ranged at one and fixed at its neighbour ('exp' /
+    'gauss').  One table of laws (`site_law_arrays`, Engine.set_sites_laws) is registered after the count and
+    receiver-function tables and before the correlation classes; each model is evaluated under its own site's laws, the bits of
+    an evaluation of the same batch in which every site has them.  A slot's descriptor is then that of the first site that has
+    it under the Gauss law, if any (the descriptor owns the contraction's shape), else of the first site that has it; Gauss
+    matrices are compared among the Gauss sites only, and the sites under another law are in class -1 of `gauss_class_arrays`.
+    The flag SWITCHES per_site_corr ON: a Gauss-law slot with a site under another law needs the class table in any case, and
+    stations that differ in their laws fix their correlations independently.  Still refused: the Gauss law on a dispersion
+    target (periods per site)."""
+
+    def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False, missing=False, per_site_corr=False,
+                 per_site_law=False):
         self.missing = bool(missing)
-        self.per_site_corr = bool(per_site_corr)
+        self.per_site_law = bool(per_site_law)
+        if self.per_site_law and not self.missing:
+            raise ValueError("per_site_law=True needs missing=True (the table of counts it extends)")
+        self.per_site_corr = bool(per_site_corr) or self.per_site_law
         self._slots = None
         if self.missing:
             if per_site_x != "all":
@@ -195,8 +221,18 @@ class SiteTargets(object):
         """site 0's targets (the target structure every site shares); missing=True: every slot's target at the first site that
         has it"""
         if self._slots is not None:
-            return [next(row[i] for row in self._slots if row[i] is not None) for i in range(len(self._slots[0]))]
+            return [self._slots[self._slot_site(i)][i] for i in range(len(self._slots[0]))]
         return self._sites[0].targets
+
+    def _slot_site(self, i):
+        """the site whose target describes slot i: the first that has it; per_site_law=True: the first that has it under the
+        Gauss law, if any (the descriptor owns the contraction's shape and workspace)"""
+        have = [s for s, row in enumerate(self._slots) if row[i] is not None]
+        if self.per_site_law:
+            for s in have:
+                if _law_or_none(self._slots[s][i]) == "gauss":
+                    return s
+        return have[0]
 
     @property
     def ntargets(self):
@@ -232,11 +268,12 @@ class SiteTargets(object):
         """missing=True: the checks of `check` slot by slot, every site that has the slot against the first one that has it"""
         for i in range(self.ntargets):
             have = [s for s, row in enumerate(self._slots) if row[i] is not None]
-            t0 = self._slots[have[0]][i]
+            first = self._slot_site(i)
+            t0 = self._slots[first][i]
             for s in have:
                 t = self._slots[s][i]
                 what = "site %d (%s), slot %d (%s)" % (s, self._names[s], i, getattr(t, "ref", "?"))
-                self._check_target(what, t, t0, "site %d" % have[0])
+                self._check_target(what, t, t0, "site %d" % first)
                 if len(have) < self.nsites and t.law() == "gauss" and not self.per_site_corr:
                     raise ValueError("%s: Gauss law on a slot that some site lacks (the contraction gathers every site's rows)" % what)
 
@@ -276,9 +313,9 @@ class SiteTargets(object):
             if a != a0:
                 raise ValueError("%s: receiver-function parameters %r, %s's %r" % (what, a, whose, a0))
         law, law0 = t.law(), t0.law()
-        if law != law0:
+        if law != law0 and not self.per_site_law:
             raise ValueError("%s: noise law %r, %s's %r" % (what, law, whose, law0))
-        if law == "gauss":
+        if law == "gauss" and law0 == "gauss":   # (per_site_law: t0 is the slot's first Gauss site -- among the Gauss sites only)
             v, v0 = t.valuation, t0.valuation
             if self.per_site_corr:
                 if np.shape(v.corr_inv) != np.shape(v0.corr_inv) and not site_axis:
@@ -313,6 +350,8 @@ class SiteTargets(object):
         cap = n.max(axis=0)
         off = np.concatenate([[0], np.cumsum(cap)]).astype(int)
         scaled = any(LAWS[t.law()] == LAWS["nocorr_scalederr"] for t in self.targets)
+        if self.per_site_law:   # (yerr exactly in the (site, slot) cells under that law, by the site's own law)
+            scaled = bool((self.site_law_arrays() == LAWS["nocorr_scalederr"]).any())
         x, yobs = np.zeros((S, off[-1])), np.zeros((S, off[-1]))
         yerr = np.ones((S, off[-1])) if scaled else None
         for s, row in enumerate(self._slot_rows()):
@@ -325,6 +364,13 @@ class SiteTargets(object):
                 if scaled and LAWS[t.law()] == LAWS["nocorr_scalederr"]:
                     yerr[s, c] = np.asarray(t.obsdata.yerr, dtype=float).ravel()
         return n, x, yobs, yerr
+
+    def site_law_arrays(self):
+        """int32 [nsites, ntargets]: the installed noise law of every (site, slot) (Engine.set_sites_laws); where the site lacks the
+        slot the slot descriptor's law, which is not read"""
+        desc = [LAWS[t.law()] for t in self.targets]
+        return np.array([[desc[i] if t is None else LAWS[t.law()] for i, t in enumerate(row)] for row in self._slot_rows()],
+                        dtype=np.int32).reshape(self.nsites, self.ntargets)
 
     def _counts(self):
         """int32 [nsites, ntargets]: the samples of every (site, target); 0 where the site lacks the slot"""
@@ -411,7 +457,7 @@ class SiteTargets(object):
             seen, class_of, rinv, logdet = {}, [], [], []
             for row in self._slot_rows():
                 t = row[i]
-                if t is None:
+                if t is None or t.law() != "gauss":   # (per_site_law: a site under another law belongs to no class either)
                     class_of.append(-1)
                     continue
                 v = t.valuation
@@ -444,16 +490,17 @@ class SiteTargets(object):
         if self._registered != sig or e._owner is not self:
             if self.per_site_x:
                 e.set_targets(self._capacity_descs())
+                tables = self.site_x_arrays()
                 if self.per_site_rf == "all":
-                    e.set_sites_axes(*self.site_x_arrays())
+                    e.set_sites_axes(*tables)
                 elif self.missing and self.per_site_corr:
-                    e.set_sites_missing_gauss(*self.site_x_arrays())
+                    e.set_sites_missing_gauss(*tables)
                 elif self.missing:
-                    e.set_sites_missing(*self.site_x_arrays())
+                    e.set_sites_missing(*tables)
                 elif self.per_site_x == "all":
-                    e.set_sites_x_all(*self.site_x_arrays())
+                    e.set_sites_x_all(*tables)
                 else:
-                    e.set_sites_x(*self.site_x_arrays())
+                    e.set_sites_x(*tables)
             else:
                 e.set_targets([t.engine_desc() for t in self.targets])
                 yobs, yerr = self.site_arrays()
@@ -462,6 +509,8 @@ class SiteTargets(object):
                 e.set_sites_rf(*self.site_rf_arrays())
             if self.per_site_rf == "all":
                 e.set_sites_rf_axis(*self.site_rf_axis_arrays())
+            if self.per_site_law:                  # (after the count and receiver-function tables, before the classes it drops)
+                e.set_sites_laws(self.site_law_arrays(), tables[3])   # (the errors of the count-table call)
             if self.per_site_corr:                 # (last: every other registration drops the classes)
                 for i, (class_of, rinv, logdet) in sorted(self.gauss_class_arrays().items()):
                     e.set_sites_gauss(i, class_of, rinv, logdet)
