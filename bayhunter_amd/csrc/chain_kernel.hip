@@ -43,6 +43,18 @@
 #ifndef BH_CHAIN_PRIORS
 #define BH_CHAIN_PRIORS 0
 #endif
+// BH_CHAIN_RECORD (chain_kernel_r.hip; with BH_CHAIN_PRIORS: chain_kernel_pr.hip): the build of chain_accept_window_kernel that
+// writes the chains' thinned samples on its way (include/bh_engine_chain_record.h) and its entry point only.  The walk is the text
+// below, once; the build adds the write of a due snapshot row at the top of a level and nothing else.
+#ifndef BH_CHAIN_RECORD
+#define BH_CHAIN_RECORD 0
+#endif
+#if BH_CHAIN_RECORD
+#include "../../include/bh_engine_chain_record.h"
+#define BH_RECORD_KPARAM , bh_chain_record store, int due, int due_step
+#else
+#define BH_RECORD_KPARAM
+#endif
 #if BH_CHAIN_PRIORS
 #include "../../include/bh_engine_sites_priors.h"
 #define ST pr
@@ -105,6 +117,7 @@ __device__ __forceinline__ double u01(uint32_t hi, uint32_t lo) // [0, 1), 53 bi
     return (double)((((uint64_t)hi << 32) | lo) >> 11) * (1.0 / 9007199254740992.0);
 }
 
+#if !BH_CHAIN_RECORD
 // the draws one iteration of one chain may need
 struct Draws {
     double u_move, u_index, u_z, u_accept, u_noise, normal;
@@ -140,6 +153,7 @@ __device__ Draws get_draws(const bh_chain_config &cfg, const bh_chain_state &S, 
     d.normal = sqrt(-2.0 * log(a)) * cospi(2.0 * bq); // Box-Muller
     return d;
 }
+#endif
 
 #if !BH_CHAIN_ABSENT
 // the accept step's draw alone (the same bits as get_draws(...).u_accept, without the other five)
@@ -206,6 +220,7 @@ struct AcceptPrior {
 // LDS record of one tree node (doubles): [0] n  [1] valid  [2] vp/vs  [3 .. 3+2nt) noise  then vs[ML+1], z[ML+1], h[ML+1]
 __host__ __device__ inline int node_rec_doubles(int nt, int ML) { return 3 + 2 * nt + 3 * (ML + 1); }
 
+#if !BH_CHAIN_RECORD
 // The state a tree node's proposal starts from: the proposal of the nearest ancestor that is entered through
 // its "accepted" edge (and was valid), else the chain's current state.  node < 0: the chain's current state.
 // lds_from: the LDS record of `from_node` when the window kernel keeps the tree there (same values as the global copy)
@@ -539,8 +554,9 @@ __global__ __launch_bounds__(64) void chain_propose_window_kernel(bh_chain_confi
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 }
+#endif
 
-#if !BH_CHAIN_ABSENT
+#if !BH_CHAIN_ABSENT && !BH_CHAIN_RECORD
 // lane = chain: walk the realised path through the window's tree (depth 1: the plain accept step)
 __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C, size_t ldp, int iiter, int depth,
                                     const double *logL, const double *misfits BH_ACCEPT_KPARAM)
@@ -626,6 +642,43 @@ __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C
         for (int i = 0; i <= nt; ++i) S.misfits[(size_t)i * C + c] = misfits[col * (nt + 1) + i];
     }
 }
+#endif
+
+#if !BH_CHAIN_ABSENT
+#if BH_CHAIN_RECORD
+// One snapshot row of chain c (bh_engine_chain_record.h): the chain's state before the level that is about to be decided.  from < 0:
+// nothing accepted so far in this window -- the state arrays, which the kernel commits to only after its loop; else the proposal
+// column of node `from`, the last one accepted, with `cur` = its logL.  Called by the whole wavefront with wave-uniform arguments:
+// lane j writes element j of the model row (2 maxlayers <= 64 contiguous floats), stride loops the noise and the misfits, lane 0 the
+// scalars.  float64 -> float32 by the cast (round to nearest, what the host's astype does).  Never a row >= store.rows.
+__device__ __forceinline__ void record_row(const bh_chain_config &cfg, const bh_chain_state &S, const bh_chain_record &store, int C,
+                                           size_t ldp, int c, int lane, int from, double cur, const double *misfits, long long row)
+{
+    if (row < 0 || row >= (long long)store.rows) return;
+    const int nt = cfg.nt, ML = cfg.maxlayers;
+    const size_t at = (size_t)row * C + c, col = (size_t)(from < 0 ? 0 : from) * C + c;
+    int n = from < 0 ? S.n[c] : S.pn[col];
+    n = n < 0 ? 0 : (n > ML ? ML : n); // (a state that is not a chain's: no read beyond the arrays' rows)
+    if (lane < 2 * ML) {
+        float v = __int_as_float(0x7fc00000); // NaN padding
+        if (lane < 2 * n) {
+            const bool depth_part = lane >= n;
+            const size_t i = (size_t)(depth_part ? lane - n : lane);
+            v = from < 0 ? (float)(depth_part ? S.z : S.vs)[i * C + c] : (float)(depth_part ? S.pz : S.pvs)[i * ldp + col];
+        }
+        store.models[at * (size_t)(2 * ML) + lane] = v;
+    }
+    for (int i = lane; i < 2 * nt; i += 64)
+        store.noise[at * (size_t)(2 * nt) + i] = (float)(from < 0 ? S.noise[(size_t)i * C + c] : S.pnoise[col * 2 * nt + i]);
+    for (int i = lane; i <= nt; i += 64)
+        store.misfits[at * (size_t)(nt + 1) + i] = (float)(from < 0 ? S.misfits[(size_t)i * C + c] : misfits[col * (nt + 1) + i]);
+    if (lane == 0) {
+        store.likes[at] = (float)cur;
+        store.vpvs[at] = (float)(from < 0 ? S.vpvs[c] : S.pvpvs[col]);
+        if (store.beta != nullptr) store.beta[at] = S.beta ? S.beta[c] : 1.0;
+    }
+}
+#endif
 
 // A wavefront per chain: walk the realised path through the window's tree (depth > 1).  Same decisions and the same bits as
 // `depth` rounds of chain_accept_kernel; what differs is where the operands wait: the tree's per-node values (valid, move,
@@ -634,12 +687,21 @@ __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C
 // evaluation per level (24 -> 9 us at depth 7); the counters of the five proposal types sit in lanes 0..4 and are written
 // back once; the committed model is copied one layer per lane.
 __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config cfg, bh_chain_state S, int C, size_t ldp, int iiter, int depth,
-                                                                  const double *logL, const double *misfits BH_ACCEPT_KPARAM)
+                                                                  const double *logL, const double *misfits BH_ACCEPT_KPARAM BH_RECORD_KPARAM)
 {
     const int c = (int)blockIdx.x, lane = (int)threadIdx.x;
     if (c >= C) return;
+#if BH_CHAIN_RECORD
+    // `due`: the next level of the window at which a snapshot is due (the host's count of the first; then every due_step levels),
+    // `row`: the row it goes to
+    long long row = (long long)store.row0;
+#endif
 #if BH_CHAIN_PRIORS
     const int rec = prior_of[c]; // a wavefront is one chain: the record is wave-uniform here
+#if BH_CHAIN_RECORD
+    if (rec < 0 || rec >= NP) // the chain keeps its state: that state is what its due rows hold
+        for (; due < depth; due += due_step) record_row(cfg, S, store, C, ldp, c, lane, -1, S.like[c], misfits, row++);
+#endif
     if (rec < 0 || rec >= NP) return;
     const AcceptPrior pr = {priors[rec].vsmin, priors[rec].vsmax, priors[rec].acc_lo, priors[rec].acc_hi};
 #endif
@@ -662,6 +724,12 @@ __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config
     long long nacc = (long long)S.naccepted[c];
     int node = 0, last = -1;
     for (int k = 0; k < depth; ++k) {
+#if BH_CHAIN_RECORD
+        if (k == due) { // (wave-uniform, as are last and cur)
+            record_row(cfg, S, store, C, ldp, c, lane, last, cur, misfits, row++);
+            due += due_step;
+        }
+#endif
         const int src = node & 63;
         const bool hi = node >= 64;
         const int va = __shfl(valid0, src), vb = __shfl(valid1, src), ma = __shfl(mv0, src), mb = __shfl(mv1, src);
@@ -736,7 +804,47 @@ __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config
 
 extern "C" {
 
+#if BH_CHAIN_RECORD
+// the window accept calls with a store: always the wavefront-per-chain kernel
 #if BH_CHAIN_PRIORS
+int bh_chain_accept_window_priors_record(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
+                                         int depth, ptrdiff_t ld, const double *logL, const double *misfits,
+                                         const bh_chain_prior *priors, int P, const int32_t *prior_of, const bh_chain_record *rec)
+#else
+int bh_chain_accept_window_record(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
+                                  int depth, ptrdiff_t ld, const double *logL, const double *misfits, const bh_chain_record *rec)
+#endif
+{
+    if (!cfg || !state || C < 0 || !logL || !misfits) return BH_EINVAL;
+    if (cfg->maxlayers < 0 || cfg->maxlayers > BH_CHAIN_MAXLAYERS || cfg->nt < 0 || cfg->nt > BH_MAX_TARGETS) return BH_EINVAL;
+    if (depth < 1 || depth > BH_CHAIN_MAXDEPTH || ld < (ptrdiff_t)C * ((1 << depth) - 1)) return BH_EINVAL;
+#if BH_CHAIN_PRIORS
+    if (!priors || !prior_of || P < 1) return BH_EINVAL;
+#endif
+    for (int k = 0; k + 1 < depth; ++k)
+        if ((iiter + k) % 1000 == 0) return BH_EINVAL; // an adaptation iteration must be the last of its window
+    if (!rec || !rec->models || !rec->likes || !rec->vpvs || !rec->misfits || !rec->noise) return BH_EINVAL;
+    if (rec->thinning < 1 || rec->row0 < 0) return BH_EINVAL;
+    // the first due level: iiter + first = 0 mod thinning (non-negative residue); m due levels in the window
+    const int64_t res = (((int64_t)iiter % rec->thinning) + rec->thinning) % rec->thinning;
+    const int64_t first = res == 0 ? 0 : rec->thinning - res;
+    const int64_t m = first >= depth ? 0 : 1 + ((int64_t)depth - 1 - first) / rec->thinning;
+    if (rec->row0 > rec->rows - m) return BH_EINVAL;
+    if (C == 0) return BH_OK;
+    // (a step beyond the deepest window means "no further one": thinning itself need not fit an int)
+    const int due = (int)(first < depth ? first : depth);
+    const int due_step = (int)(rec->thinning <= BH_CHAIN_MAXDEPTH ? rec->thinning : BH_CHAIN_MAXDEPTH + 1);
+#if BH_CHAIN_PRIORS
+    hipLaunchKernelGGL(chain_accept_window_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld, iiter, depth,
+                       logL, misfits, priors, P, prior_of, *rec, due, due_step);
+#else
+    hipLaunchKernelGGL(chain_accept_window_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld, iiter, depth,
+                       logL, misfits, *rec, due, due_step);
+#endif
+    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+}
+
+#elif BH_CHAIN_PRIORS
 static int window_args_ok(const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter, int depth, ptrdiff_t ld,
                           const bh_chain_prior *priors, int P, const int32_t *prior_of)
 {

@@ -34,6 +34,12 @@ the fly: every `thinning`-th iteration the current state of all chains is copied
 same estimator without storing what would be thinned away.  (One difference: the reference's
 main-phase file starts with the first model ACCEPTED at iteration >= 0; here the main phase starts
 with the model that is current at iteration 0.)
+
+record="host" takes those snapshots on the host: run() ends every window at a snapshot iteration, waits for the GPU and copies the
+state out -- with thinning 1 (the reference's defaults: maxmodels 50000 for 2048 iterations) every launch is one iteration and
+ends in a synchronisation.  record="device" leaves them to the accept kernel, which knows the chain's state before every
+iteration of its window (include/bh_engine_chain_record.h): the rows go into a store on the GPU, windows are cut at
+adaptations and exchanges only and nothing waits; samples() / save() read the store once and return the same arrays, bit for bit.
 """
 import ctypes as C
 import os
@@ -42,7 +48,7 @@ import os.path as op
 import numpy as np
 
 from .chains import ChainBatch, DEFAULT_INITPARAMS, DEFAULT_PRIORS, _is_fixed
-from .engine import BH_CHAIN_MAXDEPTH, BH_CHAIN_MAXLAYERS, ChainConfig, ChainPrior, ChainState, EngineError
+from .engine import BH_CHAIN_MAXDEPTH, BH_CHAIN_MAXLAYERS, ChainConfig, ChainPrior, ChainRecord, ChainState, EngineError
 from .Targets import JointTarget
 from .sites import SiteTargets, gather_slots, scatter_slots, window_site_map
 
@@ -59,6 +65,25 @@ def auto_spec_depth(nchains, budget=None):
     while d < BH_CHAIN_MAXDEPTH and nchains * ((1 << (d + 1)) - 1) <= budget:
         d += 1
     return d
+
+
+def snapshot_count(lo, hi, thinning):
+    """The snapshots due in [lo, hi): the iterations i with i % thinning == 0 (Python's non-negative residue: i is negative
+    during the burn-in) -- run()'s rule."""
+    lo, hi, thinning = int(lo), int(hi), int(thinning)
+    if thinning < 1:
+        raise ValueError("thinning must be >= 1")
+    if hi <= lo:
+        return 0
+    return -((-hi) // thinning) + ((-lo) // thinning)      # ceil(hi / thinning) - ceil(lo / thinning)
+
+
+def record_rows(iter_burnin, iter_main, thinning):
+    """(rows of phase 1, rows of phase 2) a run takes: the snapshots due in [-iter_burnin, 0) and in [0, iter_main)"""
+    return snapshot_count(-int(iter_burnin), 0, thinning), snapshot_count(0, int(iter_main), thinning)
+
+
+RECORD_MODES = ("host", "device")
 
 
 # initparams the sites of one run must share: the chains advance in lock step (iter_*), are thinned together (maxmodels), share the
@@ -140,7 +165,7 @@ class DeviceChains(object):
 
     def __init__(self, targets, nchains, initparams=None, modelpriors=None, seed=0, device=None, inject=False,
                  betas=None, ladder=None, swap_every=0, dist=None, chain_offset=None, spec_depth=None, search="fast", arith="fast",
-                 prior_table=False):
+                 prior_table=False, record="host"):
         """`nchains` chains on THIS rank.  Sharded jobs (one process per GPU, `dist` = an initialised
         torch.distributed): `seed` is the JOB's seed, the same on every rank; the chains are numbered globally
         (`chain_offset` = global index of this rank's first chain, default: ranks own consecutive blocks in rank
@@ -189,7 +214,16 @@ class DeviceChains(object):
         width, priors and initparams.  The sites share every slot's installed noise law (SiteTargets.check) unless the set was
         made with per_site_law=True, which gives every (site, slot) the law its own priors install.  Sites whose merged dicts agree, or one dict, take the calls without a table exactly as before; prior_table=True forces the table
         (for measurements).  `self.priors` / `self.initparams` are site 0's; `self.site_priors` / `self.site_initparams` every
-        site's."""
+        site's.
+        record: "host" (default) -- run() copies the chains' state out at every `thinning`-th iteration, and its windows end
+        there; "device" -- the accept kernel writes those rows into a store on the GPU (rows of both phases, allocated here:
+        EngineError if it does not fit the free memory), run() cuts no window and waits for nothing, `samples()` and `save()`
+        return what they return with "host", bit for bit, and `samples_dev()` hands the rows to the posterior kernels where they
+        lie.  A bare `iterate()` loop outside run() records as well, by the same rule, while iiter < iter_main.  Sharded runs
+        keep the host gather of `samples()`."""
+        if record not in RECORD_MODES:      # (checked before anything touches the GPU)
+            raise ValueError("record must be 'host' or 'device', not %r" % (record,))
+        self.record = record
         self.sites = targets if isinstance(targets, SiteTargets) else None
         self.nsites = 1 if self.sites is None else self.sites.nsites
         # (checked before anything touches the GPU)
@@ -357,6 +391,9 @@ class DeviceChains(object):
             v = t[k[0]]
             setattr(st, k[0], None if v is None else v.data_ptr())
         self.state = st
+        self.store = self._rec = None
+        if self.record == "device":
+            self._allocate_store(betas is not None)
         torch.cuda.synchronize(dev)
         self._ext_stream = torch.cuda.ExternalStream(int(self.engine.stream), device=dev)   # the engine's stream, for torch work
         # replica exchange on the device (one rank, or RCCL): the ladder of every chain of the job is static
@@ -370,6 +407,25 @@ class DeviceChains(object):
                 self._dev_exchange = DeviceExchange(ladder_all, self.seed, mine, dev, self.rank_counts)
         self.snap = {"p1": [], "p2": []}
 
+    def _allocate_store(self, tempered):
+        """the device store of record="device": every row of both phases (include/bh_engine_chain_record.h)"""
+        torch, Cn, ML, nt = self.torch, self.C, self.ML, self.nt
+        rows = sum(record_rows(self.iter_phase1, self.iter_phase2, self.thinning))
+        shapes = dict(models=(rows, Cn, 2 * ML), likes=(rows, Cn), vpvs=(rows, Cn), misfits=(rows, Cn, nt + 1), noise=(rows, Cn, 2 * nt))
+        need = 4 * sum(int(np.prod(sh)) for sh in shapes.values()) + (8 * rows * Cn if tempered else 0)
+        free = torch.cuda.mem_get_info(self.dev)[0]
+        if need > free:
+            raise EngineError("record='device': the store of %d rows x %d chains takes %.2f GiB, %.2f GiB are free on GPU %d "
+                              "(maxmodels = %s gives thinning %d: lower maxmodels, or record='host')"
+                              % (rows, Cn, need / 2.0 ** 30, free / 2.0 ** 30, self.dev.index, self.initparams["maxmodels"], self.thinning))
+        self.store = {k: torch.empty(sh, dtype=torch.float32, device=self.dev) for k, sh in shapes.items()}
+        self.store["beta"] = torch.empty((rows, Cn), dtype=torch.float64, device=self.dev) if tempered else None
+        rec = ChainRecord()
+        for k, v in self.store.items():
+            setattr(rec, k, None if v is None else v.data_ptr())
+        rec.rows, rec.thinning, rec.row0 = rows, self.thinning, 0
+        self._rec = rec
+
     def window(self):
         """Iterations the next launch may cover: the speculation depth, cut where something outside a chain's own
         state changes -- the proposal-width adaptation (an iteration with iiter % 1000 == 0 is the last of its
@@ -378,7 +434,7 @@ class DeviceChains(object):
         w = min(self.depth, self.iter_phase2 - i, (-i) % 1000 + 1)
         if self.swap_every > 0 and self.t["beta"] is not None:
             w = min(w, self.swap_every - i % self.swap_every)
-        if self.snap_in_run:
+        if self.snap_in_run and self._rec is None:     # (the device record: the accept kernel takes the snapshots inside the window)
             w = min(w, self.thinning - i % self.thinning)
         return max(1, w)
 
@@ -386,7 +442,9 @@ class DeviceChains(object):
     HINT_EVERY = 64
 
     def iterate(self):
-        """Advance every chain by `window()` iterations (1 with spec_depth = 1); returns that number."""
+        """Advance every chain by `window()` iterations (1 with spec_depth = 1); returns that number.
+        record="device": the snapshots due inside the window are written by the accept kernel, in run() and in a bare loop of
+        iterate() alike (while iiter < iter_main: the store has the rows of a run)."""
         e, t, Cn = self.engine, self.t, self.C
         # transdimensional chains: the dispersion kernel's lane groups and LDS rows are sized for the models the chains
         # hold NOW (typically 5-7 layers in arrays of 21), refreshed every HINT_EVERY launches (one small read-back; run()
@@ -430,7 +488,17 @@ class DeviceChains(object):
             if prev_arith is not None and prev_arith != self.arith:
                 e.set_swd_arith(prev_arith)
             e.set_swd_trials(prev_trials)
-        if self.prior_records is not None:
+        rec = self._rec if self.iiter < self.iter_phase2 else None
+        if rec is not None:
+            rec.row0 = snapshot_count(-self.iter_phase1, self.iiter, self.thinning)
+            if self.prior_records is not None:
+                e.chain_accept_window_priors_record(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(),
+                                                    self.mis.data_ptr(), self.prior_records.data_ptr(), self.nsites,
+                                                    self.prior_of.data_ptr(), rec)
+            else:
+                e.chain_accept_window_record(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(),
+                                             self.mis.data_ptr(), rec)
+        elif self.prior_records is not None:
             e.chain_accept_window_priors(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(), self.mis.data_ptr(),
                                          self.prior_records.data_ptr(), self.nsites, self.prior_of.data_ptr())
         else:
@@ -479,7 +547,7 @@ class DeviceChains(object):
         self.snap_in_run = True
         try:
             while self.iiter < self.iter_phase2:
-                if self.iiter % self.thinning == 0:
+                if self._rec is None and self.iiter % self.thinning == 0:
                     self._snapshot()
                 before = self.iiter
                 self.iterate()
@@ -507,24 +575,8 @@ class DeviceChains(object):
         cold_only (tempered runs): one column per LADDER -- at every snapshot the state of the chain holding
         beta = 1; implies gather (the cold chain of a ladder moves between chains, hence between ranks);
         the ladder ids are returned as out["ladder"]."""
-        S = self.snap[phase]
-        ns, Cn, ML = len(S), self.C, self.ML
-        models = np.full((ns, Cn, 2 * ML), np.nan, dtype=np.float32)
-        j = np.arange(2 * ML)[:, None]                               # position inside a reference row
-        for i, r in enumerate(S):
-            n = r["n"][None, :].astype(np.int64)                      # [1, C]
-            # reference rows hold the n vs values first, then the n depths, then NaN padding
-            both = np.vstack((r["vs"], r["z"]))                       # [2*ML, C]: vs rows, then z rows
-            src = np.where(j < n, j, ML + (j - n))                    # row of `both` feeding position j
-            row = np.take_along_axis(both, np.clip(src, 0, 2 * ML - 1), axis=0)
-            models[i] = np.where(j < 2 * n, row, np.nan).T
-        out = dict(models=models)
-        for k in ("like", "vpvs"):
-            out[k + "s" if k == "like" else k] = np.array([r[k] for r in S], dtype=np.float32).reshape(ns, Cn)
-        out["misfits"] = np.array([r["misfits"].T for r in S], dtype=np.float32).reshape(ns, Cn, self.nt + 1)
-        out["noise"] = np.array([r["noise"].T for r in S], dtype=np.float32).reshape(ns, Cn, 2 * self.nt)
-        if ns and S[0]["beta"] is not None:
-            out["beta"] = np.array([r["beta"] for r in S]).reshape(ns, Cn)   # cold samples: out["beta"] == 1
+        Cn = self.C
+        out = self._host_rows(phase) if self._rec is None else self._store_rows(phase)
         if site is not None:
             if self.sites is None:
                 raise EngineError("samples(site=...) needs DeviceChains over SiteTargets")
@@ -549,6 +601,70 @@ class DeviceChains(object):
             out.pop("chain_id")
             ids, out = cold_samples(out, ladder)
             out["ladder"] = ids
+        return out
+
+    def nsamples(self, phase="p2"):
+        """snapshots of `phase` taken so far"""
+        if self._rec is None:
+            return len(self.snap[phase])
+        lo, hi = self._store_range(phase)
+        return hi - lo
+
+    def _store_range(self, phase):
+        """rows [lo, hi) of the device store that hold the snapshots of `phase` taken so far (up to the current iiter)"""
+        if phase not in ("p1", "p2"):
+            raise KeyError(phase)
+        r1 = record_rows(self.iter_phase1, self.iter_phase2, self.thinning)[0]
+        done = snapshot_count(-self.iter_phase1, min(self.iiter, self.iter_phase2), self.thinning)
+        return (0, min(done, r1)) if phase == "p1" else (r1, max(done, r1))
+
+    def _store_rows(self, phase):
+        """the rows of samples() from the device store: one copy per array"""
+        lo, hi = self._store_range(phase)
+        self.engine.synchronize()
+        out = {k: self.store[k][lo:hi].cpu().numpy() for k in ("models", "likes", "vpvs", "misfits", "noise")}
+        if hi > lo and self.store["beta"] is not None:
+            out["beta"] = self.store["beta"][lo:hi].cpu().numpy()
+        return out
+
+    def samples_dev(self, phase="p2"):
+        """record="device": the snapshots of `phase` taken so far where the accept kernel wrote them -- a dict of torch views of
+        the store, models [rows, C, 2*maxlayers], likes / vpvs [rows, C], misfits [rows, C, nt+1], noise [rows, C, 2nt] (float32,
+        all chains, shared row width and slot layout), tempered runs also beta [rows, C] (float64); and, for the posterior kernels,
+        models2d = the [rows*C, 2*maxlayers] view of the models and site = int32 [rows*C], every row's site index:
+        posterior_models(d["models2d"], site=d["site"], nsites=...) summarises them without a host copy.  Waits for the engine's
+        stream (the posterior kernels run on torch's).  Tempered runs: the rows of ALL chains -- selecting the chains that hold
+        beta = 1 is not done on the device; use samples(cold_only=True)."""
+        if self._rec is None:
+            raise EngineError("samples_dev() needs DeviceChains(record='device')")
+        lo, hi = self._store_range(phase)
+        self.engine.synchronize()
+        out = {k: v[lo:hi] for k, v in self.store.items() if v is not None}
+        out["models2d"] = out["models"].reshape((hi - lo) * self.C, 2 * self.ML)
+        of = self.torch.arange(self.C, dtype=self.torch.int32, device=self.dev) // self.C_site
+        out["site"] = of.repeat(hi - lo)
+        return out
+
+    def _host_rows(self, phase):
+        """the rows of samples() from the host snapshots of run()"""
+        S = self.snap[phase]
+        ns, Cn, ML = len(S), self.C, self.ML
+        models = np.full((ns, Cn, 2 * ML), np.nan, dtype=np.float32)
+        j = np.arange(2 * ML)[:, None]                               # position inside a reference row
+        for i, r in enumerate(S):
+            n = r["n"][None, :].astype(np.int64)                      # [1, C]
+            # reference rows hold the n vs values first, then the n depths, then NaN padding
+            both = np.vstack((r["vs"], r["z"]))                       # [2*ML, C]: vs rows, then z rows
+            src = np.where(j < n, j, ML + (j - n))                    # row of `both` feeding position j
+            row = np.take_along_axis(both, np.clip(src, 0, 2 * ML - 1), axis=0)
+            models[i] = np.where(j < 2 * n, row, np.nan).T
+        out = dict(models=models)
+        for k in ("like", "vpvs"):
+            out[k + "s" if k == "like" else k] = np.array([r[k] for r in S], dtype=np.float32).reshape(ns, Cn)
+        out["misfits"] = np.array([r["misfits"].T for r in S], dtype=np.float32).reshape(ns, Cn, self.nt + 1)
+        out["noise"] = np.array([r["noise"].T for r in S], dtype=np.float32).reshape(ns, Cn, 2 * self.nt)
+        if ns and S[0]["beta"] is not None:
+            out["beta"] = np.array([r["beta"] for r in S]).reshape(ns, Cn)   # cold samples: out["beta"] == 1
         return out
 
     def _site_block(self, allcols, s, phase, cold_only, gather):
@@ -576,7 +692,7 @@ class DeviceChains(object):
         savepath = op.join(savepath or self.initparams["savepath"], "data")
         tempered = self.t["beta"] is not None
         for tag in ("p1", "p2"):
-            if not self.snap[tag]:
+            if not self.nsamples(tag):
                 continue
             s = self.samples(tag, cold_only=tempered, gather=True)      # collective: every rank takes part
             if self.rank == 0:
@@ -604,7 +720,7 @@ class DeviceChains(object):
         for s, name in enumerate(self.sites.names):
             datapath = op.join(root, name, "data")
             for tag in ("p1", "p2"):
-                if not self.snap[tag]:
+                if not self.nsamples(tag):
                     continue
                 smp = self.samples(tag, cold_only=tempered, gather=True, site=s)
                 write_chain_files(datapath, tag, smp, smp["ladder"] if tempered else smp["chain_id"])

@@ -92,6 +92,12 @@ class ChainState(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in CHAIN_STATE_FIELDS]
 
 
+class ChainRecord(C.Structure):
+    """bh_chain_record of include/bh_engine_chain_record.h: the device store of thinned samples (the arrays are device pointers)"""
+    _fields_ = [("models", C.c_void_p), ("likes", C.c_void_p), ("vpvs", C.c_void_p), ("misfits", C.c_void_p), ("noise", C.c_void_p),
+                ("beta", C.c_void_p), ("rows", C.c_int64), ("thinning", C.c_int64), ("row0", C.c_int64)]
+
+
 _lib = None
 
 
@@ -172,6 +178,9 @@ def load_library():
     L.bh_chain_propose_window_priors.argtypes = [vp, _cc, _cs, C.c_int, C.c_int, C.c_int, C.c_ssize_t, _cp, C.c_int, vp, vp]
     L.bh_chain_accept_priors.argtypes = [vp, _cc, _cs, C.c_int, C.c_int, vp, vp, _cp, C.c_int, vp]
     L.bh_chain_accept_window_priors.argtypes = [vp, _cc, _cs, C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp, vp, _cp, C.c_int, vp]
+    _cr = C.POINTER(ChainRecord)
+    L.bh_chain_accept_window_record.argtypes = [vp, _cc, _cs, C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp, vp, _cr]
+    L.bh_chain_accept_window_priors_record.argtypes = [vp, _cc, _cs, C.c_int, C.c_int, C.c_int, C.c_ssize_t, vp, vp, _cp, C.c_int, vp, _cr]
     L.bh_evaluate_sites.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                     C.c_ssize_t, C.c_ssize_t, vp, vp, vp, vp, vp, vp]
     L.bh_chain_propose.argtypes = [vp, C.POINTER(ChainConfig), C.POINTER(ChainState), C.c_int, C.c_int]
@@ -191,7 +200,7 @@ def load_library():
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
                  "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all",
-                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_GAUSS_SYMBOLS + SITE_PRIORS_SYMBOLS + SITE_RF_AXIS_SYMBOLS + SITE_LAWS_SYMBOLS:
+                 "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_GAUSS_SYMBOLS + SITE_PRIORS_SYMBOLS + SITE_RF_AXIS_SYMBOLS + SITE_LAWS_SYMBOLS + CHAIN_RECORD_SYMBOLS:
         getattr(L, name).restype = C.c_int
     if L.bh_abi_version() != 10:
         raise EngineError("ABI version mismatch")
@@ -231,6 +240,8 @@ SITE_LAWS_SYMBOLS = ("bh_sites_set_laws",)
 # include/bh_engine_sites_priors.h: chains under their own site's priors and sampler settings
 SITE_PRIORS_SYMBOLS = ("bh_chain_propose_priors", "bh_chain_propose_window_priors", "bh_chain_accept_priors",
                        "bh_chain_accept_window_priors")
+# include/bh_engine_chain_record.h: the window accept calls that write the chains' thinned samples on the device
+CHAIN_RECORD_SYMBOLS = ("bh_chain_accept_window_record", "bh_chain_accept_window_priors_record")
 # include/bh_engine_posterior.h: posterior velocity-depth summaries of many sites (bayhunter_amd/posterior.py)
 POSTERIOR_SYMBOLS = ("bh_posterior_create", "bh_posterior_destroy", "bh_posterior_load", "bh_posterior_columns",
                      "bh_posterior_hist", "bh_posterior_interfaces")
@@ -795,6 +806,20 @@ class Engine(object):
                                                    int(ld), logL, misfits, priors, int(nprior), prior_of)
         if rc != BH_OK:
             raise EngineError("bh_chain_accept_window_priors failed (%d)" % rc)
+
+    def chain_accept_window_record(self, cfg, state, C_, iiter, depth, ld, logL, misfits, rec):
+        """bh_chain_accept_window_record.  rec: a ChainRecord (include/bh_engine_chain_record.h)"""
+        rc = self._L.bh_chain_accept_window_record(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth), int(ld),
+                                                   logL, misfits, C.byref(rec))
+        if rc != BH_OK:
+            raise EngineError("bh_chain_accept_window_record failed (%d)" % rc)
+
+    def chain_accept_window_priors_record(self, cfg, state, C_, iiter, depth, ld, logL, misfits, priors, nprior, prior_of, rec):
+        """bh_chain_accept_window_priors_record (arguments as chain_accept_window_priors, then the ChainRecord)"""
+        rc = self._L.bh_chain_accept_window_priors_record(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth),
+                                                          int(ld), logL, misfits, priors, int(nprior), prior_of, C.byref(rec))
+        if rc != BH_OK:
+            raise EngineError("bh_chain_accept_window_priors_record failed (%d)" % rc)
 
     def chain_accept_window(self, cfg, state, C_, iiter, depth, ld, logL, misfits):
         rc = self._L.bh_chain_accept_window(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth), int(ld),

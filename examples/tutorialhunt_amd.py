@@ -23,6 +23,8 @@ ap.add_argument("--device-chains", type=int, default=0)
 ap.add_argument("--burnin", type=int, default=2048 * 4)
 ap.add_argument("--main", type=int, default=2048 * 2)
 ap.add_argument("--out", default="results")
+ap.add_argument("--record", choices=("device", "host"), default="device",
+                help="device chains: where the thinned samples are taken (device: by the accept kernel, no wait per snapshot)")
 args = ap.parse_args()
 
 obs = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "st3")
@@ -44,7 +46,7 @@ initparams = dict(nchains=args.chains, iter_burnin=args.burnin, iter_main=args.m
                   maxmodels=5000)
 
 if args.device_chains > 0:
-    chains = bh.DeviceChains(targets, args.device_chains, initparams, priors, seed=1).run()
+    chains = bh.DeviceChains(targets, args.device_chains, initparams, priors, seed=1, record=args.record).run()
     path = chains.save()
     like = chains.state_host()["like"]
 else:
