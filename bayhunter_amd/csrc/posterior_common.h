@@ -1,0 +1,126 @@
+// bayhunter_amd/csrc/posterior_common.h -- what posterior_kernel.hip and posterior_scalars_kernel.hip share: the handle, its
+// device buffers, the work items, the ordered keys and the bin rule.
+#ifndef BH_POSTERIOR_COMMON_H
+#define BH_POSTERIOR_COMMON_H
+
+#include "bh_device.h"
+#include "../../include/bh_engine_posterior.h"
+
+#include <climits>
+#include <string>
+#include <vector>
+
+#define POST_CHUNK 8192  // rows per workgroup of a column pass (< 2^16: the radix pass's 16-bit LDS counters)
+
+namespace bhpost {
+
+struct PostWork {
+    int32_t site, pad;
+    int64_t r0, r1;
+};
+
+__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << __lane_id()) - 1ull; }
+
+// ctr[key] += 1 for every lane with `on`, one atomic per distinct key of the wavefront; returns the lane's old value +
+// its rank among the lanes of its key.  Every lane of the wavefront must call it.
+__device__ inline unsigned long long agg_add(unsigned long long *ctr, int key, bool on)
+{
+    unsigned long long res = 0, pending = __ballot(on);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const int lkey = __shfl(key, leader);
+        const bool mine = on && key == lkey && ((pending >> __lane_id()) & 1ull);
+        const unsigned long long m = __ballot(mine);
+        unsigned long long base = 0;
+        if (__lane_id() == leader) base = atomicAdd(&ctr[lkey], (unsigned long long)__popcll(m));
+        base = __shfl(base, leader);
+        if (mine) res = base + (unsigned long long)__popcll(m & lanes_below());
+        pending &= ~m;
+    }
+    return res;
+}
+
+__device__ __forceinline__ unsigned long long okey(double v, bool k32)
+{
+    if (k32) {
+        const unsigned u = __float_as_uint((float)v);
+        return (u >> 31) ? (unsigned long long)(~u) : (unsigned long long)(u | 0x80000000u);
+    }
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+// exponent of the lowest set bit of v (INT_MAX for 0)
+__device__ __forceinline__ int low_bit(double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const int ex = (int)((u >> 52) & 0x7ff);
+    unsigned long long m = u & 0xfffffffffffffull;
+    if (ex) m |= 1ull << 52;
+    if (!m) return INT_MAX;
+    return (ex ? ex - 1075 : -1074) + __ffsll((long long)m) - 1;
+}
+
+// bin of v over e[0..nb]: searchsorted(e, v, 'right') - 1, the last edge into the last bin; -1 / nb outside
+__device__ __forceinline__ int find_bin(const double *e, int nb, double v)
+{
+    int lo = 0, hi = nb + 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] <= v) lo = mid + 1;
+        else hi = mid;
+    }
+    return (v == e[nb]) ? nb - 1 : lo - 1;
+}
+
+struct Dev {
+    void *p = nullptr;
+    ~Dev() { if (p) (void)hipFree(p); }
+    template <typename U> U *as() const { return (U *)p; }
+};
+
+// a scalar set (include/bh_engine_posterior_scalars.h): Q float64 columns over the loaded rows, val[q * nrows + r], NaN = masked
+struct ScalarSet {
+    int Q = 0;
+    Dev val;
+};
+
+} // namespace bhpost
+
+struct bh_posterior {
+    bh_engine *e = nullptr;
+    int device = 0;
+    hipStream_t st = nullptr;
+    int elem = 8, ML = 0, S = 0;
+    int64_t nrows = 0, ninput = 0;
+    bool keys32 = false;
+    std::vector<int64_t> off;             // [S+1]: site s holds rows [off[s], off[s+1])
+    std::vector<bhpost::PostWork> work;   // column-pass work items (site, chunk of its rows)
+    bhpost::Dev pn, psite, pvs, pd, pdi, dwork;
+    bool keep_rows = false;               // bh_posterior_keep_rows: the next load keeps porig and pzd
+    bool has_rows = false;                // ... and the last one did
+    bhpost::Dev porig, pzd;               // the row's index in the loaded input; zd_j in the row's dtype (the scalar sets)
+    bhpost::ScalarSet sets[2];            // BH_SCALARS_MOHO, BH_SCALARS_USER
+};
+
+namespace bhpost {
+
+inline int pfail(bh_posterior *p, int code, const std::string &what) { return bh_engine_fail_internal(p->e, code, what.c_str()); }
+
+#define PCHK(p, call)                                                                           \
+    do {                                                                                        \
+        hipError_t _he = (call);                                                                \
+        if (_he != hipSuccess) return bhpost::pfail((p), BH_EHIP, std::string(#call ": ") + hipGetErrorString(_he)); \
+    } while (0)
+
+inline int alloc(bh_posterior *p, Dev &b, size_t bytes)
+{
+    if (b.p) { (void)hipFree(b.p); b.p = nullptr; }
+    if (!bytes) bytes = 8;
+    hipError_t he = hipMalloc(&b.p, bytes);
+    if (he != hipSuccess) { b.p = nullptr; return pfail(p, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
+    return BH_OK;
+}
+
+} // namespace bhpost
+#endif

@@ -15,8 +15,7 @@
 //   hist    : counts over the caller's vs edges (binary search, 'right', last edge to the last bin) and depth bins;
 //             in LDS when every site has at most 256 vs bins, else straight to global atomics.
 // -ffp-contract=off (Makefile) keeps (z_j + z_{j+1}) / 2 and the cumulative sums rounded as numpy rounds them.
-#include "bh_device.h"
-#include "../../include/bh_engine_posterior.h"
+#include "posterior_common.h"
 
 #include <algorithm>
 #include <climits>
@@ -25,37 +24,12 @@
 #include <string>
 #include <vector>
 
-#define POST_CHUNK 8192  // rows per workgroup of a column pass (< 2^16: the radix pass's 16-bit LDS counters)
 #define POST_HIST_LDS_BINS 256
 #define POST_IFACE_LDS_BINS 4096
 
+using namespace bhpost;
+
 namespace {
-
-struct PostWork {
-    int32_t site, pad;
-    int64_t r0, r1;
-};
-
-__device__ __forceinline__ unsigned long long lanes_below() { return (1ull << __lane_id()) - 1ull; }
-
-// ctr[key] += 1 for every lane with `on`, one atomic per distinct key of the wavefront; returns the lane's old value +
-// its rank among the lanes of its key.  Every lane of the wavefront must call it.
-__device__ unsigned long long agg_add(unsigned long long *ctr, int key, bool on)
-{
-    unsigned long long res = 0, pending = __ballot(on);
-    while (pending) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const int lkey = __shfl(key, leader);
-        const bool mine = on && key == lkey && ((pending >> __lane_id()) & 1ull);
-        const unsigned long long m = __ballot(mine);
-        unsigned long long base = 0;
-        if (__lane_id() == leader) base = atomicAdd(&ctr[lkey], (unsigned long long)__popcll(m));
-        base = __shfl(base, leader);
-        if (mine) res = base + (unsigned long long)__popcll(m & lanes_below());
-        pending &= ~m;
-    }
-    return res;
-}
 
 // n >= 1 layers, 0 = NaN only, -1 = the non-NaN values are not a prefix of even length
 template <typename T>
@@ -99,11 +73,12 @@ __global__ void __launch_bounds__(256) post_count_kernel(int64_t N, int W, int64
 }
 
 // the kept rows to their site's slice: n, vs (row dtype), d (float64: the step model's depths), di (float32 rows: the
-// interface depths in float32, _replace_zvnoi_h; float64 rows use d)
+// interface depths in float32, _replace_zvnoi_h; float64 rows use d); for the scalar sets (posterior_scalars_kernel.hip) the
+// row's index in the input and its zd_j in the row's dtype, where the handle asks for them (bh_posterior_keep_rows)
 template <typename T>
 __global__ void __launch_bounds__(256) post_scatter_kernel(int64_t N, int W, int64_t ld, const T *models, const int32_t *site,
                                                            int S, int ML, unsigned long long *cursor, int32_t *pn,
-                                                           int32_t *psite, T *pvs, double *pd, float *pdi)
+                                                           int32_t *psite, T *pvs, double *pd, float *pdi, int64_t *porig, T *pzd)
 {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int s = -1, n = 0;
@@ -118,6 +93,7 @@ __global__ void __launch_bounds__(256) post_scatter_kernel(int64_t N, int W, int
     if (!on) return;
     pn[pos] = n;
     psite[pos] = s;
+    if (porig) porig[pos] = r;   // (bh_posterior_keep_rows)
     T *vs = pvs + pos * ML;
     double *d = pd + pos * ML;
     for (int j = 0; j < n; ++j) vs[j] = row[j];
@@ -130,6 +106,7 @@ __global__ void __launch_bounds__(256) post_scatter_kernel(int64_t N, int W, int
         const double h = (double)zd - (double)zprev; // numpy: z_disc - concatenate(([0], z_disc[:-1])) is float64
         dsum = j ? dsum + h : h;
         d[j] = dsum;
+        if (pzd) pzd[pos * ML + j] = zd;
         if (pdi) {
             const float hf = (float)h;               // written back into the float32 model row
             isum = j ? isum + hf : hf;
@@ -148,27 +125,6 @@ __device__ __forceinline__ double sample(int n, const T *vs, const double *d, do
     double v = (double)vs[0];
     for (int j = 1; j < n; ++j) v = k == j ? (double)vs[j] : v;
     return v;
-}
-
-__device__ __forceinline__ unsigned long long okey(double v, bool k32)
-{
-    if (k32) {
-        const unsigned u = __float_as_uint((float)v);
-        return (u >> 31) ? (unsigned long long)(~u) : (unsigned long long)(u | 0x80000000u);
-    }
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-// exponent of the lowest set bit of v (INT_MAX for 0)
-__device__ __forceinline__ int low_bit(double v)
-{
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const int ex = (int)((u >> 52) & 0x7ff);
-    unsigned long long m = u & 0xfffffffffffffull;
-    if (ex) m |= 1ull << 52;
-    if (!m) return INT_MAX;
-    return (ex ? ex - 1075 : -1074) + __ffsll((long long)m) - 1;
 }
 
 struct ColArgs {
@@ -315,18 +271,6 @@ __global__ void __launch_bounds__(64) post_next_kernel(ColArgs a, int k32, const
     atomicMin(&next[c], nx);
 }
 
-// bin of v over e[0..nb]: searchsorted(e, v, 'right') - 1, the last edge into the last bin; -1 / nb outside
-__device__ __forceinline__ int find_bin(const double *e, int nb, double v)
-{
-    int lo = 0, hi = nb + 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (e[mid] <= v) lo = mid + 1;
-        else hi = mid;
-    }
-    return (v == e[nb]) ? nb - 1 : lo - 1;
-}
-
 struct HistArgs {
     const int32_t *dbin;
     int ND;
@@ -426,44 +370,9 @@ __global__ void __launch_bounds__(256) post_iface_kernel(int64_t nrows, const in
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 
-struct Dev {
-    void *p = nullptr;
-    ~Dev() { if (p) (void)hipFree(p); }
-    template <typename U> U *as() const { return (U *)p; }
-};
-
 } // namespace
 
-struct bh_posterior {
-    bh_engine *e = nullptr;
-    int device = 0;
-    hipStream_t st = nullptr;
-    int elem = 8, ML = 0, S = 0;
-    int64_t nrows = 0;
-    bool keys32 = false;
-    std::vector<int64_t> off;     // [S+1]: site s holds rows [off[s], off[s+1])
-    std::vector<PostWork> work;   // column-pass work items (site, chunk of its rows)
-    Dev pn, psite, pvs, pd, pdi, dwork;
-};
-
 namespace {
-
-int pfail(bh_posterior *p, int code, const std::string &what) { return bh_engine_fail_internal(p->e, code, what.c_str()); }
-
-#define PCHK(p, call)                                                                           \
-    do {                                                                                        \
-        hipError_t _he = (call);                                                                \
-        if (_he != hipSuccess) return pfail((p), BH_EHIP, std::string(#call ": ") + hipGetErrorString(_he)); \
-    } while (0)
-
-int alloc(bh_posterior *p, Dev &b, size_t bytes)
-{
-    if (b.p) { (void)hipFree(b.p); b.p = nullptr; }
-    if (!bytes) bytes = 8;
-    hipError_t he = hipMalloc(&b.p, bytes);
-    if (he != hipSuccess) { b.p = nullptr; return pfail(p, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-    return BH_OK;
-}
 
 bool grid_ok(const double *dep, int D)
 {
@@ -579,12 +488,21 @@ int bh_posterior_load(bh_posterior *p, int memspace, void *stream, int elem_byte
     p->ML = ML;
     p->S = S;
     p->nrows = p->off[S];
+    p->ninput = N;
+    for (ScalarSet &ss : p->sets) {  // the sets belong to the rows of the load before
+        ss.Q = 0;
+        if (ss.val.p) { (void)hipFree(ss.val.p); ss.val.p = nullptr; }
+    }
     p->keys32 = elem_bytes == 4 || (unsigned)hc[2 * S + 1] == 0u;
     const size_t nr = (size_t)p->nrows;
     if ((rc = alloc(p, p->pn, nr * 4))) return rc;
     if ((rc = alloc(p, p->psite, nr * 4))) return rc;
     if ((rc = alloc(p, p->pvs, nr * ML * eb))) return rc;
     if ((rc = alloc(p, p->pd, nr * ML * 8))) return rc;
+    p->has_rows = false;
+    for (Dev *b : {&p->porig, &p->pzd})   // kept only for the scalar sets: no memory and no writes otherwise
+        if (b->p) { (void)hipFree(b->p); b->p = nullptr; }
+    if (p->keep_rows && ((rc = alloc(p, p->porig, nr * 8)) || (rc = alloc(p, p->pzd, nr * ML * eb)))) return rc;
     if (elem_bytes == 4) { if ((rc = alloc(p, p->pdi, nr * ML * 4))) return rc; }
     else if (p->pdi.p) { (void)hipFree(p->pdi.p); p->pdi.p = nullptr; }
     // the cursors: each site's first slot
@@ -593,10 +511,10 @@ int bh_posterior_load(bh_posterior *p, int memspace, void *stream, int elem_byte
     if (N) {
         if (elem_bytes == 4)
             post_scatter_kernel<float><<<nblk, 256, 0, p->st>>>(N, W, ld, (const float *)m, sd, S, ML, c, p->pn.as<int32_t>(),
-                p->psite.as<int32_t>(), p->pvs.as<float>(), p->pd.as<double>(), p->pdi.as<float>());
+                p->psite.as<int32_t>(), p->pvs.as<float>(), p->pd.as<double>(), p->pdi.as<float>(), p->porig.as<int64_t>(), p->pzd.as<float>());
         else
             post_scatter_kernel<double><<<nblk, 256, 0, p->st>>>(N, W, ld, (const double *)m, sd, S, ML, c, p->pn.as<int32_t>(),
-                p->psite.as<int32_t>(), p->pvs.as<double>(), p->pd.as<double>(), nullptr);
+                p->psite.as<int32_t>(), p->pvs.as<double>(), p->pd.as<double>(), nullptr, p->porig.as<int64_t>(), p->pzd.as<double>());
         PCHK(p, hipGetLastError());
     }
     p->work.clear();
@@ -607,6 +525,7 @@ int bh_posterior_load(bh_posterior *p, int memspace, void *stream, int elem_byte
     if (!p->work.empty())
         PCHK(p, hipMemcpyAsync(p->dwork.p, p->work.data(), p->work.size() * sizeof(PostWork), hipMemcpyHostToDevice, p->st));
     PCHK(p, hipStreamSynchronize(p->st));
+    p->has_rows = p->keep_rows;
     return BH_OK;
 }
 

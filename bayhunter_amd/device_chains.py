@@ -627,23 +627,87 @@ class DeviceChains(object):
             out["beta"] = self.store["beta"][lo:hi].cpu().numpy()
         return out
 
-    def samples_dev(self, phase="p2"):
+    def samples_dev(self, phase="p2", cold_only=False, exclude_chains=()):
         """record="device": the snapshots of `phase` taken so far where the accept kernel wrote them -- a dict of torch views of
         the store, models [rows, C, 2*maxlayers], likes / vpvs [rows, C], misfits [rows, C, nt+1], noise [rows, C, 2nt] (float32,
         all chains, shared row width and slot layout), tempered runs also beta [rows, C] (float64); and, for the posterior kernels,
         models2d = the [rows*C, 2*maxlayers] view of the models and site = int32 [rows*C], every row's site index:
         posterior_models(d["models2d"], site=d["site"], nsites=...) summarises them without a host copy.  Waits for the engine's
-        stream (the posterior kernels run on torch's).  Tempered runs: the rows of ALL chains -- selecting the chains that hold
-        beta = 1 is not done on the device; use samples(cold_only=True)."""
+        stream (the posterior kernels run on torch's).
+        cold_only (tempered runs): the rows that are no posterior samples -- at every snapshot every chain but the one holding
+        beta = 1 in its ladder (the first of the largest beta, as samples(cold_only=True) picks it) -- get site = -1, which the
+        posterior kernels leave out and count as dropped.  exclude_chains: chain numbers (outliers) whose rows get site = -1 too.
+        Both are formed on the device; the views of the store still hold every row."""
         if self._rec is None:
             raise EngineError("samples_dev() needs DeviceChains(record='device')")
+        torch = self.torch
         lo, hi = self._store_range(phase)
         self.engine.synchronize()
         out = {k: v[lo:hi] for k, v in self.store.items() if v is not None}
         out["models2d"] = out["models"].reshape((hi - lo) * self.C, 2 * self.ML)
-        of = self.torch.arange(self.C, dtype=self.torch.int32, device=self.dev) // self.C_site
-        out["site"] = of.repeat(hi - lo)
+        of = torch.arange(self.C, dtype=torch.int32, device=self.dev) // self.C_site
+        site = of.repeat(hi - lo)
+        exclude = np.atleast_1d(np.asarray(exclude_chains, dtype=np.int64)) - self.chain_offset
+        if exclude.size and (exclude.min() < 0 or exclude.max() >= self.C):
+            raise IndexError("exclude_chains: chain numbers %d..%d" % (self.chain_offset, self.chain_offset + self.C - 1))
+        if (cold_only and "beta" in out) or exclude.size:
+            keep = torch.ones((hi - lo, self.C), dtype=torch.bool, device=self.dev)
+            if cold_only and "beta" in out:
+                keep &= self._cold_mask(out["beta"])
+            if exclude.size:
+                keep[:, torch.from_numpy(exclude).to(self.dev)] = False
+            site = torch.where(keep.reshape(-1), site, torch.full_like(site, -1))
+        out["site"] = site
         return out
+
+    def _cold_mask(self, beta):
+        """bool [rows, C]: at every snapshot, the chain of every ladder that cold_samples() picks (the first of the largest beta)"""
+        torch = self.torch
+        if self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1:
+            raise EngineError("samples_dev(cold_only=True) does not follow ladders across ranks: use samples(cold_only=True)")
+        rows, Cn = beta.shape
+        lad = torch.from_numpy(np.unique(self.ladder, return_inverse=True)[1].astype(np.int64)).to(self.dev)
+        nl = int(lad.max().item()) + 1 if Cn else 0
+        idx = lad.expand(rows, Cn)
+        top = torch.full((rows, nl), -np.inf, dtype=beta.dtype, device=self.dev).scatter_reduce(1, idx, beta, "amax")
+        chain = torch.arange(Cn, dtype=torch.int64, device=self.dev).expand(rows, Cn)
+        cand = torch.where(beta == top.gather(1, idx), chain, torch.full_like(chain, Cn))
+        first = torch.full((rows, nl), Cn, dtype=torch.int64, device=self.dev).scatter_reduce(1, idx, cand, "amin")
+        return chain == first.gather(1, idx)
+
+    def _posterior_rows(self, phase, cold_only, exclude_chains):
+        if self._rec is None:
+            raise EngineError("samples_dev() needs DeviceChains(record='device')")
+        if cold_only is None:
+            cold_only = self.ladder is not None
+        return self.samples_dev(phase, cold_only=cold_only, exclude_chains=exclude_chains)
+
+    def posterior_moho(self, moho=None, mohovs=4.2, bins=50, phase="p2", cold_only=None, exclude_chains=()):
+        """record="device": bayhunter_amd.posterior_moho of every site's recorded rows, straight from the device store (one dict
+        per site; one dict without SiteTargets).  moho None: every site's own priors['z'], the reference's default.  cold_only
+        (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        from .posterior import posterior_moho
+        d = self._posterior_rows(phase, cold_only, exclude_chains)
+        if moho is None:
+            moho = [tuple(float(v) for v in p["z"]) for p in self.site_priors]
+        with self.torch.cuda.device(self.dev):
+            r = posterior_moho(d["models2d"], site=d["site"], moho=moho, mohovs=mohovs, bins=bins, engine=self.engine,
+                               nsites=self.nsites)
+        return r if self.sites is not None else r[0]
+
+    def posterior_scalars(self, bins=20, nlayers=True, phase="p2", cold_only=None, exclude_chains=()):
+        """record="device": bayhunter_amd.posterior_scalars of every site's recorded rows with the store's likes, vpvs, misfits
+        [nt+1] and noise [2nt] as columns (slot layout), straight from the device store (one dict per site; one dict without
+        SiteTargets).  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        from .posterior import posterior_scalars
+        d = self._posterior_rows(phase, cold_only, exclude_chains)
+        n = d["models2d"].shape[0]
+        cols = dict(likes=d["likes"].reshape(n), vpvs=d["vpvs"].reshape(n), misfits=d["misfits"].reshape(n, self.nt + 1),
+                    noise=d["noise"].reshape(n, 2 * self.nt))
+        with self.torch.cuda.device(self.dev):
+            r = posterior_scalars(d["models2d"], cols, site=d["site"], bins=bins, nlayers=nlayers, engine=self.engine,
+                                  nsites=self.nsites)
+        return r if self.sites is not None else r[0]
 
     def _host_rows(self, phase):
         """the rows of samples() from the host snapshots of run()"""

@@ -196,6 +196,15 @@ def load_library():
     L.bh_posterior_interfaces.argtypes = [vp, C.c_int, vp, vp]
     for name in ("bh_posterior_create", "bh_posterior_load", "bh_posterior_columns", "bh_posterior_hist", "bh_posterior_interfaces"):
         getattr(L, name).restype = C.c_int
+    L.bh_posterior_keep_rows.argtypes = [vp, C.c_int]
+    L.bh_posterior_moho.argtypes = [vp, vp, vp, vp, vp]
+    L.bh_posterior_attach.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int64, vp, C.c_int]
+    L.bh_posterior_scalar_cols.argtypes = [vp, C.c_int, vp]
+    L.bh_posterior_scalar_stats.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.bh_posterior_scalar_hist.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    L.bh_posterior_scalar_hist2d.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    for name in POSTERIOR_SCALARS_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
@@ -245,6 +254,10 @@ CHAIN_RECORD_SYMBOLS = ("bh_chain_accept_window_record", "bh_chain_accept_window
 # include/bh_engine_posterior.h: posterior velocity-depth summaries of many sites (bayhunter_amd/posterior.py)
 POSTERIOR_SYMBOLS = ("bh_posterior_create", "bh_posterior_destroy", "bh_posterior_load", "bh_posterior_columns",
                      "bh_posterior_hist", "bh_posterior_interfaces")
+# include/bh_engine_posterior_scalars.h: per-site posteriors of Moho depth, crustal vs and scalar columns (bayhunter_amd/posterior.py)
+POSTERIOR_SCALARS_SYMBOLS = ("bh_posterior_keep_rows", "bh_posterior_moho", "bh_posterior_attach", "bh_posterior_scalar_cols", "bh_posterior_scalar_stats",
+                             "bh_posterior_scalar_hist", "bh_posterior_scalar_hist2d")
+SCALARS_MOHO, SCALARS_USER = 0, 1   # BH_SCALARS_MOHO, BH_SCALARS_USER
 
 
 def _f64(a):

@@ -8,6 +8,10 @@ stdminmax, mode, minmisfit) plus `count`, `mode_valid` and `invalid_rows`; `post
 Exactness ("Posterior summaries"): min, max, median, counts, histograms and mode are the reference's bits.
 The mean and std come from exact integer sums formed on the device (every interpolated vs is an integer multiple of the
 column's lowest set bit); they are rounded here from Python integers, within one rounding of the exact values.
+
+`posterior_moho` and `posterior_scalars` (include/bh_engine_posterior_scalars.h) return per site the numbers of the
+reference's plot_moho_crustvel_tradeoff and plot_posterior_likes / _misfits / _nlayers / _vpvs / _noise / _others: Moho
+depth, crustal vs and any scalar column attached to the rows, with the same exactness.
 """
 import ctypes as C
 import math
@@ -91,7 +95,8 @@ def stepmodel(row):
 class _Loaded(object):
     """Rows loaded into a bh_posterior handle (one per call of the public functions)."""
 
-    def __init__(self, models, site, engine, nsites=None):
+    def __init__(self, models, site, engine, nsites=None, scalars=False):
+        """scalars: the load keeps what the scalar sets need (bh_posterior_keep_rows)"""
         self.eng = engine if engine is not None else E.default_engine(0)
         L = self.eng._L
         self._L = L
@@ -99,6 +104,8 @@ class _Loaded(object):
         self.eng._check(L.bh_posterior_create(self.eng._h, C.byref(h)))
         self._p = h
         self._keep = []
+        if scalars:
+            self.eng._check(L.bh_posterior_keep_rows(h, 1))
         try:
             import torch
             is_t = isinstance(models, torch.Tensor)
@@ -195,6 +202,73 @@ class _Loaded(object):
         counts = np.zeros((self.S, edges.size - 1), np.uint32)
         self.eng._check(self._L.bh_posterior_interfaces(self._p, edges.size, _ptr(edges), _ptr(counts)))
         return counts
+
+    # ---- scalar sets (include/bh_engine_posterior_scalars.h) ----
+
+    def moho(self, lo, hi, mohovs):
+        lo, hi, mohovs = (np.ascontiguousarray(v, np.float64) for v in (lo, hi, mohovs))
+        found = np.zeros(self.S, np.int64)
+        self.eng._check(self._L.bh_posterior_moho(self._p, _ptr(lo), _ptr(hi), _ptr(mohovs), _ptr(found)))
+        return found
+
+    def attach(self, values, nlayers):
+        """values: None or a 2-D float32/float64 array or device tensor, one value row per loaded input row"""
+        if values is None:
+            self.eng._check(self._L.bh_posterior_attach(self._p, E.HOST, None, 8, 0, 0, None, int(bool(nlayers))))
+            return
+        if isinstance(values, np.ndarray):
+            values = np.ascontiguousarray(values)
+            mem, stream, ptr = E.HOST, None, _ptr(values)
+            ld, elem = values.shape[1], values.itemsize
+        else:
+            import torch
+            if values.stride(1) != 1:
+                values = values.contiguous()
+            mem, stream = E.DEVICE, C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
+            ptr, ld, elem = C.c_void_p(values.data_ptr()), values.stride(0), values.element_size()
+        if values.shape[0] != self.N:
+            raise ValueError("one value row per model row")
+        self.eng._check(self._L.bh_posterior_attach(self._p, mem, stream, elem, values.shape[1], ld, ptr, int(bool(nlayers))))
+
+    def scalar_stats(self, which, median=True):
+        q = np.zeros(1, np.int32)
+        self.eng._check(self._L.bh_posterior_scalar_cols(self._p, which, _ptr(q)))
+        S, Q = self.S, int(q[0])
+        out = dict(count=np.zeros((S, Q), np.int64), nan=np.zeros((S, Q), np.int64), kmin=np.zeros((S, Q), np.uint64),
+                   kmax=np.zeros((S, Q), np.uint64), scale=np.zeros((S, Q), np.int32), x0=np.zeros((S, Q), np.int64),
+                   exact=np.zeros((S, Q), np.int32), sums=np.zeros((S, Q, 6), np.uint64),
+                   median=np.zeros((S, Q, 2), np.uint64) if median else None)
+        self.eng._check(self._L.bh_posterior_scalar_stats(self._p, which, _ptr(out["count"]), _ptr(out["nan"]), _ptr(out["kmin"]),
+                                                          _ptr(out["kmax"]), _ptr(out["scale"]), _ptr(out["x0"]),
+                                                          _ptr(out["exact"]), _ptr(out["sums"]), _ptr(out["median"])))
+        out["min"] = _keys_to_values(out["kmin"], False).reshape(S, Q)
+        out["max"] = _keys_to_values(out["kmax"], False).reshape(S, Q)
+        if median:
+            out["med"] = _keys_to_values(out["median"].reshape(-1), False).reshape(S, Q, 2)
+        return out
+
+    @staticmethod
+    def _edges(edges_per_site):
+        nb = np.array([len(e) - 1 for e in edges_per_site], np.int64)
+        off = np.concatenate(([0], np.cumsum(nb + 1))).astype(np.int64)
+        return nb, off, np.ascontiguousarray(np.concatenate([np.asarray(e, np.float64) for e in edges_per_site]), np.float64)
+
+    def scalar_hist(self, which, col, edges_per_site):
+        nb, off, edges = self._edges(edges_per_site)
+        counts = np.zeros(int(nb.sum()), np.uint32)
+        self.eng._check(self._L.bh_posterior_scalar_hist(self._p, which, int(col), _ptr(off), _ptr(edges), _ptr(counts)))
+        co = np.concatenate(([0], np.cumsum(nb)))
+        return [counts[co[s]:co[s + 1]] for s in range(self.S)]
+
+    def scalar_hist2d(self, which, colx, coly, xedges_per_site, yedges_per_site, argmax=True):
+        nx, xoff, xe = self._edges(xedges_per_site)
+        ny, yoff, ye = self._edges(yedges_per_site)
+        counts = np.zeros(int(np.sum(nx * ny)), np.uint32)
+        am = np.zeros(self.S, np.int64) if argmax else None
+        self.eng._check(self._L.bh_posterior_scalar_hist2d(self._p, which, int(colx), int(coly), _ptr(xoff), _ptr(xe), _ptr(yoff),
+                                                           _ptr(ye), _ptr(counts), _ptr(am)))
+        co = np.concatenate(([0], np.cumsum(nx * ny)))
+        return [counts[co[s]:co[s + 1]].reshape(nx[s], ny[s]) for s in range(self.S)], am
 
 
 def _mean_std(n, sums, scale, x0):
@@ -326,4 +400,195 @@ def posterior_hist2d(models, site=None, dep_int=None, vs_edges=None, dep_edges=N
         ld.close()
     out = [dict(counts=counts[s], vs_edges=vs_e[s], dep_edges=depbins, samples=samples, interfaces=inter[s],
                 count=int(ld.rows[s]), invalid_rows=int(ld.invalid[s])) for s in range(S)]
+    return out[0] if site is None else out
+
+
+# ---- Moho depth, crustal velocity and scalar columns (include/bh_engine_posterior_scalars.h) ----------------------------
+
+MOHO_COLUMNS = ("moho", "vslast", "vscrust", "vsjump")
+MOHOVS = 4.2  # km/s: the reference's default of the vs that marks the mantle
+
+
+def moho_edges(vmin, vmax, bins=50):
+    """The float64 edges matplotlib's hist / hist2d (numpy.histogram, numpy.histogram2d) form for data of that min and max:
+    `bins` equal bins over [min, max], [min - 0.5, max + 0.5] where they are equal, [0, 1] where there is no data."""
+    if vmin is None or np.isnan(vmin):
+        return np.histogram_bin_edges(np.zeros(0), bins)
+    return np.histogram_bin_edges(np.array([vmin, vmax], np.float64), bins)
+
+
+def scalar_edges(vmin, vmax, dtype, bins=20, nlayers=False):
+    """The edges of the reference's scalar posterior plots (_plot_posterior_distribution) for a column of that dtype, min
+    and max: numpy.histogram_bin_edges of the data; for nlayers arange(min, max + 2) - 0.5; for a constant column the
+    reference's placeholder [m - 1, m - 0.1, m + 0.1, m + 1]; [0, 1] where there is no data."""
+    if vmin is None or np.isnan(vmin):
+        return np.histogram_bin_edges(np.zeros(0, dtype), bins)
+    if nlayers:
+        return np.arange(vmin, vmax + 2) - 0.5
+    if vmin == vmax:
+        m = float(vmin)
+        return np.array([m - 1, m - 0.1, m + 0.1, m + 1])
+    return np.histogram_bin_edges(np.array([vmin, vmax], dtype), bins)
+
+
+def median_of_middles(a, b, n, dtype=np.float64):
+    """numpy.median of n values whose two middle ones (ranks (n-1)//2 and (n-1)//2 + 1) are a and b, in `dtype`."""
+    a, b = dtype(a), dtype(b)
+    if n % 2:
+        return a
+    with np.errstate(over="ignore"):
+        return (a + b) / dtype(2)
+
+
+def _per_site(v, S, width, what):
+    v = np.asarray(v, np.float64)
+    if v.shape == (width,) or v.shape == ():
+        v = np.broadcast_to(v, (S,) + v.shape)
+    if v.shape != ((S, width) if width else (S,)):
+        raise ValueError("%s: one %s or one per site" % (what, "pair" if width else "value"))
+    return np.ascontiguousarray(v)
+
+
+def _stat_dict(st, s, q, dtype=np.float64):
+    n = int(st["count"][s, q])
+    if not n:
+        return dict(median=np.nan, mean=np.nan, std=np.nan, min=np.nan, max=np.nan)
+    mean, std = _mean_std(n, st["sums"][s, q], st["scale"][s, q], st["x0"][s, q])
+    return dict(median=median_of_middles(st["med"][s, q, 0], st["med"][s, q, 1], n, dtype), mean=mean, std=std,
+                min=dtype(st["min"][s, q]), max=dtype(st["max"][s, q]))
+
+
+def posterior_moho(models, site=None, moho=None, mohovs=MOHOVS, bins=50, engine=None, nsites=None):
+    """The numbers of the reference's plot_moho_crustvel_tradeoff for every site: a list of dicts (one dict when site is
+    None).  moho = (lo, hi) km, or one pair per site: the depth range in which an interface can be the Moho (0 <= lo < hi);
+    mohovs (one, or one per site): the Moho is the first interface inside the range below which vs exceeds it.
+    Keys: rows, count (the rows with a Moho), invalid_rows, dropped (device rows with a site index out of range, e.g. -1:
+    left out; the total of the call); moho, vslast (vs of the last crustal layer), vscrust (the mean
+    crustal vs above the Moho), vsjump (the vs step at the Moho): each a dict of median, mean, std, min, max; hist: name ->
+    (counts [bins], edges); hist2d: vslast / vscrust / vsjump -> (counts [bins, bins], xedges, yedges) against moho; mode:
+    the same names -> (x, y), the centres of the first largest cell.  A site without a Moho row has count 0, NaN statistics
+    and empty histograms over [0, 1]."""
+    if moho is None:
+        raise ValueError("moho=(lo, hi) is needed: the reference's default is the station's priors['z']")
+    ld = _Loaded(models, site, engine, nsites, scalars=True)
+    try:
+        S = ld.S
+        rng = _per_site(moho, S, 2, "moho")
+        mv = _per_site(mohovs, S, 0, "mohovs")
+        found = ld.moho(rng[:, 0], rng[:, 1], mv)
+        st = ld.scalar_stats(E.SCALARS_MOHO)
+        edges = [[moho_edges(st["min"][s, q], st["max"][s, q], bins) if found[s] else moho_edges(None, None, bins)
+                  for s in range(S)] for q in range(4)]
+        h1 = [ld.scalar_hist(E.SCALARS_MOHO, q, edges[q]) for q in range(4)]
+        h2 = [ld.scalar_hist2d(E.SCALARS_MOHO, q, 0, edges[q], edges[0]) for q in (1, 2, 3)]
+    finally:
+        ld.close()
+    out = []
+    for s in range(S):
+        r = dict(rows=int(ld.rows[s]), count=int(found[s]), invalid_rows=int(ld.invalid[s]), dropped=ld.dropped, hist={}, hist2d={},
+                 mode={})
+        for q, name in enumerate(MOHO_COLUMNS):
+            r[name] = _stat_dict(st, s, q)
+            r["hist"][name] = (h1[q][s].astype(np.int64), edges[q][s])
+        for i, q in enumerate((1, 2, 3)):
+            name = MOHO_COLUMNS[q]
+            counts, am = h2[i]
+            xe, ye = edges[q][s], edges[0][s]
+            r["hist2d"][name] = (counts[s].astype(np.int64), xe, ye)
+            if found[s]:
+                xi, yi = divmod(int(am[s]), ye.size - 1)
+                r["mode"][name] = (((xe[:-1] + xe[1:]) / 2.)[xi], ((ye[:-1] + ye[1:]) / 2.)[yi])
+            else:
+                r["mode"][name] = (np.nan, np.nan)
+        out.append(r)
+    return out[0] if site is None else out
+
+
+def _stack_columns(columns, N):
+    """(values [N, Q] or None, [(name, index or None, numpy dtype)]): the columns side by side in one array or device tensor"""
+    try:
+        import torch
+    except ImportError:
+        torch = None
+    parts, layout = [], []
+    for name, v in columns.items():
+        is_t = torch is not None and isinstance(v, torch.Tensor)
+        if is_t:
+            if v.dtype not in (torch.float32, torch.float64):
+                raise ValueError("column %r must be float32 or float64" % name)
+            dt = np.float32 if v.dtype == torch.float32 else np.float64
+        else:
+            v = np.asarray(v)
+            if v.dtype not in (np.float32, np.float64):
+                v = v.astype(np.float64)
+            dt = v.dtype.type
+        if v.ndim not in (1, 2) or v.shape[0] != N:
+            raise ValueError("column %r must be [N] or [N, k] with one row per model row" % name)
+        if v.ndim == 1:
+            layout.append((name, None, dt))
+            parts.append(v[:, None])
+        else:
+            layout += [(name, i, dt) for i in range(v.shape[1])]
+            parts.append(v)
+    if not parts:
+        return None, layout
+    if len(layout) > 64:
+        raise ValueError("at most 64 scalar columns in one call (BH_SCALARS_MAXCOLS)")
+    wide = any(dt is np.float64 for _, _, dt in layout)
+    tens = [p for p in parts if not isinstance(p, np.ndarray)]
+    if tens:   # any device column: all of them on the device (float32 widens exactly)
+        tdt = torch.float64 if wide else torch.float32
+        parts = [(torch.from_numpy(np.ascontiguousarray(p)) if isinstance(p, np.ndarray) else p).to(device=tens[0].device, dtype=tdt)
+                 for p in parts]
+        return (parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)), layout
+    ndt = np.float64 if wide else np.float32
+    return np.concatenate([p.astype(ndt, copy=False) for p in parts], axis=1), layout
+
+
+def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=None, nsites=None):
+    """The numbers of the reference's plot_posterior_likes / _misfits / _nlayers / _vpvs / _noise / _others for every site: a
+    list of dicts (one dict when site is None), name -> statistics.  columns: a dict name -> [N] or [N, k] values (float32 or
+    float64; numpy arrays or device tensors), one row per model row; a [N, k] column gives a list of k statistics.  With
+    nlayers, the key "nlayers" holds the number of layers n - 1 of the rows.  Statistics: median (numpy's for the column's
+    dtype), mean, std, min, max, count, nan (the rows whose value is NaN: they are left out of this column only), constant,
+    hist = (counts, edges) and mode (the centre of the first largest bin).  Edges are numpy.histogram_bin_edges(data, bins) in
+    the column's dtype; nlayers has the reference's arange(min, max + 2) - 0.5.  constant = (min == max): the column gets the
+    reference's placeholder edges [m - 1, m - 0.1, m + 0.1, m + 1].  (The reference tests np.std(data) == 0 instead, which
+    numpy's own rounding of the mean can miss on a constant column; min == max cannot.)  The dict also holds rows,
+    invalid_rows and dropped (as posterior_moho); a column of one of these names, or "nlayers" beside the built-in one, is a
+    ValueError."""
+    taken = [k for k in columns if k in ("rows", "invalid_rows", "dropped") or (nlayers and k == "nlayers")]
+    if taken:
+        raise ValueError("column name %r is a key of the result itself: give the column another name" % (taken[0],))
+    ld = _Loaded(models, site, engine, nsites, scalars=True)
+    try:
+        S = ld.S
+        values, layout = _stack_columns(columns, ld.N)
+        if nlayers:
+            layout = layout + [("nlayers", None, np.float64)]
+        if not layout:
+            raise ValueError("no column and no nlayers: nothing to summarise")
+        ld.attach(values, nlayers)
+        st = ld.scalar_stats(E.SCALARS_USER)
+        Q = len(layout)
+        edges = [[scalar_edges(st["min"][s, q], st["max"][s, q], layout[q][2], bins, nlayers and q == Q - 1)
+                  if st["count"][s, q] else scalar_edges(None, None, layout[q][2], bins) for s in range(S)] for q in range(Q)]
+        hists = [ld.scalar_hist(E.SCALARS_USER, q, edges[q]) for q in range(Q)]
+    finally:
+        ld.close()
+    out = []
+    for s in range(S):
+        r = dict(rows=int(ld.rows[s]), invalid_rows=int(ld.invalid[s]), dropped=ld.dropped)
+        for q, (name, idx, dt) in enumerate(layout):
+            d = _stat_dict(st, s, q, dt)
+            n = int(st["count"][s, q])
+            e = edges[q][s]
+            cnt = hists[q][s].astype(np.int64)
+            d.update(count=n, nan=int(st["nan"][s, q]), constant=bool(n and st["min"][s, q] == st["max"][s, q]), hist=(cnt, e),
+                     mode=((e[:-1] + e[1:]) / 2.)[np.argmax(cnt)] if n else np.nan)
+            if idx is None:
+                r[name] = d
+            else:
+                r.setdefault(name, []).append(d)
+        out.append(r)
     return out[0] if site is None else out

@@ -186,3 +186,48 @@ def posterior_from_storage(datapaths, dep_int=None, engine=None):
         start += len(m)
     mis = None if any(x is None for x in misfits) else np.concatenate(misfits)
     return posterior_models(rows, site=site, dep_int=dep_int, misfits=mis, engine=engine, nsites=len(datapaths))
+
+
+class _PriorsUnpickler(pickle.Unpickler):
+    """Reads <station>_config.pkl where the reference is not installed: a class that cannot be imported (the reference's
+    targets) becomes an empty stand-in -- only the plain dicts of the file are used."""
+
+    def find_class(self, module, name):
+        try:
+            return pickle.Unpickler.find_class(self, module, name)
+        except (ImportError, AttributeError):
+            return type(str(name), (object,), {})
+
+
+def saved_priors(datapath):
+    """The `priors` dict of the one *_config.pkl in a station's data folder (save_config)."""
+    files = sorted(glob.glob(op.join(datapath, "*_config.pkl")))
+    if len(files) != 1:
+        raise IOError("%s: expected one *_config.pkl, found %d" % (datapath, len(files)))
+    with open(files[0], "rb") as f:
+        return _PriorsUnpickler(f).load()["priors"]
+
+
+def _stack_sites(arrays):
+    """rows of many sites under each other, padded with NaN to the widest, and every row's site index"""
+    W = max(a.shape[1] for a in arrays)
+    rows = np.full((sum(len(a) for a in arrays), W), np.nan)
+    site = np.zeros(len(rows), np.int32)
+    start = 0
+    for s, a in enumerate(arrays):
+        rows[start:start + len(a), :a.shape[1]] = a
+        site[start:start + len(a)] = s
+        start += len(a)
+    return rows, site
+
+
+def moho_from_storage(datapaths, moho=None, mohovs=4.2, bins=50, engine=None):
+    """Moho depth and crustal velocity posteriors of many sites in one GPU call (bayhunter_amd.posterior.posterior_moho, the
+    numbers of the reference's plot_moho_crustvel_tradeoff): datapaths[s] is site s's data directory after
+    save_final_distribution (c_models.npy).  moho: (lo, hi) km, one pair per site, or None -- then every site's range is its
+    saved priors['z'] (<station>_config.pkl in the same folder), the reference's default.  Returns one dict per site."""
+    from .posterior import posterior_moho
+    if moho is None:
+        moho = [tuple(float(v) for v in saved_priors(p)["z"]) for p in datapaths]
+    rows, site = _stack_sites([np.load(op.join(p, "c_models.npy")) for p in datapaths])
+    return posterior_moho(rows, site=site, moho=moho, mohovs=mohovs, bins=bins, engine=engine, nsites=len(datapaths))
