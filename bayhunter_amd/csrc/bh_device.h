@@ -206,9 +206,21 @@ struct PairOrderTarget {
                               // wavefronts that run on XCD x (workgroup index mod 8); the value = wavefronts of this target per workgroup (4, or 2
                               // where two targets alternate): every XCD's L2 then sees an eighth of the model arrays
 };
+// The words a dispersion call wants zero before its kernels run -- the guard's head (bh_engine.hip guard_space), the per-target
+// failure flags, the counters -- where the ordering launch that precedes them zeroes them (the call's prologue: no fill
+// dispatches of their own).  A count of 0: nothing to zero there.
+struct SwdFills {
+    int32_t *guard = nullptr;
+    int32_t *err = nullptr;
+    unsigned long long *counter = nullptr;
+    int nguard = 0, nerr = 0, ncounter = 0; // words
+};
 bool bh_pair_order_fits(int B);
-void bh_launch_pair_order(int B, int Lmax, const int32_t *nlay, const double *vs, ptrdiff_t sl, ptrdiff_t sb, int nt,
-                          const PairOrderTarget *tg, hipStream_t stream);
+// The order of nt targets (0: the launch only zeroes) and the fills, one launch: a workgroup per XCD block where every target's
+// order is blocked (PairOrderTarget::xcd and the divisibilities it stands for), else one workgroup.
+// Returns the workgroups launched (8 or 1).
+int bh_launch_pair_order(int B, int Lmax, const int32_t *nlay, const double *vs, ptrdiff_t sl, ptrdiff_t sb, int nt,
+                         const PairOrderTarget *tg, const SwdFills &fills, hipStream_t stream);
 struct SwdLaunchInfo {
     unsigned workgroups; // of the launch (what SwdMultiArgs::started is advanced by)
     long waves;          // wavefronts that do work

@@ -135,6 +135,7 @@ struct bh_engine {
     int last_swd_kernel = -1;              // bh_engine_last_swd_kernel
     bh_swd_launch swd_launches[3 * BH_MAX_TARGETS]{}; // bh_engine_last_swd_launches: of the most recent call with dispersion targets
     int n_swd_launches = 0;
+    int last_swd_order[3] = {0, 0, 0};     // bh_engine_last_swd_order: the plan's order, the ordering launch's workgroups, its fills
     int err_t_nt = -1, err_t_B = -1;       // layout for which err_t's untouched rows are known to be zero
     std::string err;
     // staging / workspace
@@ -415,14 +416,20 @@ struct SwdJob {
     SwdSiteJob sx{}; // periods per site (bh_evaluate_sites with a table of bh_sites_set_x)
 };
 
-int swd_counter(bh_engine *e, hipStream_t st, unsigned long long **out)
+// prologue: null, or the fills of the call's ordering launch (SwdPlan::prologue), which then zeroes the counters
+int swd_counter(bh_engine *e, hipStream_t st, SwdFills *prologue, unsigned long long **out)
 {
     *out = nullptr;
     if (!e->counting) return BH_OK;
     int rc = ensure(e, e->counter, BH_DEBUG_WORDS * sizeof(unsigned long long));
     if (rc) return rc;
     if (!e->neval_pending) {
-        HIPCHK(e, hipMemsetAsync(e->counter.p, 0, BH_COUNTER_WORDS * sizeof(unsigned long long), st));
+        if (prologue) {
+            prologue->counter = (unsigned long long *)e->counter.p;
+            prologue->ncounter = BH_COUNTER_WORDS;
+        } else {
+            HIPCHK(e, hipMemsetAsync(e->counter.p, 0, BH_COUNTER_WORDS * sizeof(unsigned long long), st));
+        }
         e->neval_pending = true;
     }
     *out = (unsigned long long *)e->counter.p;
@@ -430,9 +437,10 @@ int swd_counter(bh_engine *e, hipStream_t st, unsigned long long **out)
 }
 
 // The guard of the short refinement (SearchT, swd_common.h): work space = three blocks of BH_MAX_TARGETS counts (GUARD_HEAD = 24 words, below) followed by one
-// list of B model indices per target.
+// list of B model indices per target.  prologue: null, or the fills of the call's ordering launch (SwdPlan::prologue), which then
+// zeroes the head's words.
 constexpr int GUARD_HEAD = 24;
-int guard_space(bh_engine *e, hipStream_t st, int B, int32_t **counts, int32_t **lists)
+int guard_space(bh_engine *e, hipStream_t st, int B, SwdFills *prologue, int32_t **counts, int32_t **lists)
 {
     const size_t need = ((size_t)GUARD_HEAD + (size_t)BH_MAX_TARGETS * (size_t)(B + 4)) * sizeof(int32_t);
     if (need > e->guard.cap) { // (a new buffer: carry the cumulative counts over on the host side)
@@ -450,7 +458,13 @@ int guard_space(bh_engine *e, hipStream_t st, int B, int32_t **counts, int32_t *
     *lists = (int32_t *)e->guard.p + GUARD_HEAD;
     // words [0, 8): this call's lists' lengths (re-run launch); [8, 16): this call's models restarted in place (group kernel,
     // one model per wavefront); [16, 24): cumulative since the buffer was made
-    HIPCHK(e, hipMemsetAsync(e->guard.p, 0, (e->guard_fresh ? GUARD_HEAD : 2 * BH_MAX_TARGETS) * sizeof(int32_t), st));
+    const int words = e->guard_fresh ? GUARD_HEAD : 2 * BH_MAX_TARGETS;
+    if (prologue) {
+        prologue->guard = (int32_t *)e->guard.p;
+        prologue->nguard = words;
+    } else {
+        HIPCHK(e, hipMemsetAsync(e->guard.p, 0, (size_t)words * sizeof(int32_t), st));
+    }
     e->guard_fresh = false;
     return BH_OK;
 }
@@ -463,7 +477,7 @@ bool takes_fast(int search, const SwdJob &J)
 
 // processing order of the models: the caller's; deepest first (models of more than Lcut layers a class of their own:
 // SwdMultiArgs::split); by predicted search length (trial-per-lane kernel, PairOrderTarget); paired over the SIMDs (SwdPairWork)
-enum SwdOrder { ORDER_NONE, ORDER_DEPTH, ORDER_LENGTH, ORDER_PAIR };
+enum SwdOrder { ORDER_NONE = BH_ORDER_NONE, ORDER_DEPTH = BH_ORDER_DEPTH, ORDER_LENGTH = BH_ORDER_LENGTH, ORDER_PAIR = BH_ORDER_PAIR }; // (bh_engine_last_swd_order)
 
 // What the launches of one dispersion call do.  The call's targets are its jobs with K > 0, in job order.
 struct SwdPlan {
@@ -475,6 +489,9 @@ struct SwdPlan {
     int kernel;                        // BH_KERNEL_LEAN / GROUP / LANE
     int G, lean_trials;                // lanes per model; trials per round of the trial-per-lane kernel (>= 4: it runs)
     int order, Lcut;                   // SwdOrder; Lcut < Lmax: two depth classes
+    bool prologue;                     // an ordering launch of bh_launch_pair_order precedes the dispersion launch: IT zeroes the guard's
+                                       // head, the failure flags and the counters (SwdFills) and nothing else of the call fills them;
+                                       // false: guard_space, run_forward and swd_counter enqueue their own fills
     int len_mpw, len_xcd;              // ORDER_LENGTH: models per wavefront and wavefronts per workgroup of the XCD blocks (0: none)
     bool sitex;                        // periods per model (SwdSiteJob): LDS rows of periods per model, no one-lane-per-evaluation kernel
     bool any_fast, farith, adapt_ok;   // some target takes the short refinement; its fast arithmetic; kernel may size lanes per model
@@ -605,6 +622,7 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
             if (shallow_bulk) p.Lcut = p.typ_layers + 2;
         }
     }
+    p.prologue = p.order == ORDER_LENGTH || p.order == ORDER_PAIR;
     // trials per round and sequence of every target
     p.any_fast = nfast > 0;
     p.farith = e->swd_arith == BH_ARITH_FAST;
@@ -815,6 +833,8 @@ struct SwdCall {
     const int32_t *pair_perm[2] = {};    // ORDER_PAIR: the order of target 0 / 1 (SwdTarget::perm)
     unsigned long long *counter = nullptr;
     int32_t *gcounts = nullptr, *glists = nullptr; // the guard of the short refinement (guard_space)
+    SwdFills fills{};                    // p.prologue: what the ordering launch zeroes
+    int order_wgs = 0;                   // workgroups of the ordering launch (0: none)
     SwdSiteXArgs sx{};                   // p.sitex: the period table with the launch's targets (launch_swd_multi)
     int prio_low = 0;                    // the main launch's SwdMultiArgs::prio_low (EvalPlan::prio_low)
     SwdLaunchInfo info{};                // of the group or trial-per-lane kernel's main launch (workgroups == 0: none)
@@ -1012,15 +1032,15 @@ int launch_swd_rerun(bh_engine *e, hipStream_t st, const SwdMultiArgs &main, int
 
 // The SIMD-pairing order (SwdPairWork) of the group kernel's launch c.g: c.pair_perm.  Placement tables are rebuilt when the
 // launch's wavefront counts change; where they cannot be made the order is the plain sorted one, where work space cannot be
-// allocated the models keep the caller's order.
+// allocated, or the launch is not one the order is defined for, the models keep the caller's order.
 int pair_models(SwdCall &c)
 {
     SwdPairWork &pw = c.e->pairwork;
     const SwdGroupPlan &g = c.g;
     const int nt = c.p.ntargets, B = c.B;
     const int *n = g.pair_waves;
-    bool ok = true, geom = true;
-    if (pw.key_n0 != n[0] || pw.key_n1 != n[1]) { // (rare: the batch shape changed)
+    bool ok = g.pair, geom = true; // (not in a two-dimensional grid: the caller's order)
+    if (ok && (pw.key_n0 != n[0] || pw.key_n1 != n[1])) { // (rare: the batch shape changed)
         std::vector<int32_t> rank[2];
         geom = build_slot_ranks(n[0], n[1], pw.ncu, rank); // false: placement unknown -> plain sorted order
         for (int t = 0; ok && geom && t < nt; ++t) {
@@ -1047,13 +1067,12 @@ int pair_models(SwdCall &c)
         }
         pw.cap_perm = ok ? B + B / 4 + 64 : 0;
     }
-    if (ok) {
-        PairOrderTarget tg[2];
-        for (int t = 0; t < nt; ++t) tg[t] = PairOrderTarget{g.pair_mpw[t], n[t], geom ? pw.slot_rank[t] : nullptr, pw.perm[t]};
-        const SwdTarget t0 = swd_target(c, c.p.job[0]); // (its S velocities predict the search lengths: flattened for flsph = 1)
-        bh_launch_pair_order(B, c.Lmax, c.m.nlay, t0.vs, t0.sl, t0.sb, nt, tg, c.st);
-        for (int t = 0; t < nt; ++t) c.pair_perm[t] = pw.perm[t];
-    }
+    // (the launch is the call's prologue, SwdPlan::prologue: where there is no order to compute it still zeroes the fills)
+    PairOrderTarget tg[2] = {};
+    for (int t = 0; ok && t < nt; ++t) tg[t] = PairOrderTarget{g.pair_mpw[t], n[t], geom ? pw.slot_rank[t] : nullptr, pw.perm[t]};
+    const SwdTarget t0 = swd_target(c, c.p.job[0]); // (its S velocities predict the search lengths: flattened for flsph = 1)
+    c.order_wgs = bh_launch_pair_order(B, c.Lmax, c.m.nlay, t0.vs, t0.sl, t0.sb, ok ? nt : 0, tg, c.fills, c.st);
+    for (int t = 0; ok && t < nt; ++t) c.pair_perm[t] = pw.perm[t];
     (void)hipGetLastError();
     return BH_OK;
 }
@@ -1063,16 +1082,17 @@ int order_models(SwdCall &c)
 {
     const SwdPlan &p = c.p;
     if (p.order == ORDER_NONE) return BH_OK;
-    if (p.order == ORDER_PAIR) return c.g.pair ? pair_models(c) : BH_OK; // (not in a two-dimensional grid: the caller's order)
+    if (p.order == ORDER_PAIR) return pair_models(c);
     bh_engine *e = c.e;
     int rc;
     if ((rc = ensure(e, e->perm, ((size_t)c.B + 4) * sizeof(int32_t)))) return rc;
     int32_t *perm = (int32_t *)e->perm.p;
     if (p.order == ORDER_LENGTH) {
         const PairOrderTarget tg{p.len_mpw, c.B / p.len_mpw, nullptr, perm + 4, p.len_xcd};
-        bh_launch_pair_order(c.B, c.Lmax, c.m.nlay, c.m.vs, c.sl, c.sb, 1, &tg, c.st);
+        c.order_wgs = bh_launch_pair_order(c.B, c.Lmax, c.m.nlay, c.m.vs, c.sl, c.sb, 1, &tg, c.fills, c.st);
     } else {
         bh_launch_order(c.B, c.m.nlay, perm + 4, p.Lcut, perm, c.st);
+        c.order_wgs = 1;
         c.split = (p.Lcut < c.Lmax) ? perm : nullptr;
     }
     c.perm = perm + 4;
@@ -1098,7 +1118,7 @@ int launch_swd_lanes(SwdCall &c, SwdMultiArgs &ra)
     for (int t = 0; t < n; ++t) lane_waves += (long)((B + 63) / 64) * p.look[t];
     e->guard_last = p.any_fast;
     ra.B = B; ra.Lmax = c.Lmax; ra.nlay = c.m.nlay; ra.neval = c.counter; ra.counted = e->swd_scan;
-    if (p.any_fast && ((rc = guard_space(e, c.st, B, &c.gcounts, &c.glists)) || (rc = swd_board(e, c.st, &ra.board)))) return rc;
+    if (p.any_fast && (rc = swd_board(e, c.st, &ra.board))) return rc;
     e->last_swd_kernel = BH_KERNEL_LANE;
     ev_begin(e, 0, c.st);
     if (fork && (rc = wait_for(e, e->ev_fork2, c.st, e->aux2))) return rc;
@@ -1173,7 +1193,6 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
     }
     e->guard_last = p.any_fast;
     if (p.any_fast) {
-        if ((rc = guard_space(e, c.st, B, &c.gcounts, &c.glists))) return rc;
         for (int t = 0; t < a.ntargets; ++t)
             if (a.t[t].igr == BH_VEL_PHASE) {
                 a.t[t].gcount = c.gcounts + t;
@@ -1251,18 +1270,26 @@ int launch_second_roots(const SwdCall &c)
     return BH_OK;
 }
 
+// The plan of a call's dispersion jobs on the staged batch m (no dispersion job: a plan without targets, order or prologue)
+SwdPlan plan_swd_call(const bh_engine *e, int B, int Lmax, const Staged &m, int njobs, const SwdJob *jobs)
+{
+    return plan_swd(e, B, Lmax, m.typ_layers > 0 ? m.typ_layers : e->hint_layers, njobs, jobs);
+}
+
 // All dispersion targets of one call: the plan, the flattened copies and the order it needs, then its launches -- the group or
 // trial-per-lane kernel (one launch for all targets) or one lane per model (a launch per target) -- the re-run of the models
 // the guard of the short refinement fired on, and the second roots of split group velocities.
-// prio_low: SwdMultiArgs::prio_low of the main launch.  main: null, or where the SwdLaunchInfo of the call's main launch goes
-// once the call has dispersion targets (workgroups == 0: not a launch of the group or trial-per-lane kernel).
-int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl,
-                    ptrdiff_t sb, int njobs, const SwdJob *jobs, int prio_low, SwdLaunchInfo *main)
+// p: the call's plan (plan_swd_call).  fills: where p.prologue, what the caller leaves to the ordering launch to zero (the guard's
+// head and the counters are added here).  prio_low: SwdMultiArgs::prio_low of the main launch.  main: null, or where the
+// SwdLaunchInfo of the call's main launch goes once the call has dispersion targets (workgroups == 0: not a launch of the group
+// or trial-per-lane kernel).
+int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl, ptrdiff_t sb, int njobs,
+                    const SwdJob *jobs, const SwdPlan &p, const SwdFills &fills, int prio_low, SwdLaunchInfo *main)
 {
     if (B == 0 || njobs == 0) return BH_OK;
-    const SwdPlan p = plan_swd(e, B, Lmax, m.typ_layers > 0 ? m.typ_layers : e->hint_layers, njobs, jobs);
     SwdCall c{e, st, B, Lmax, m, sl, sb, jobs, p};
     c.prio_low = prio_low;
+    c.fills = fills;
     if (p.kernel == BH_KERNEL_GROUP) {
         c.g = plan_group(e, p, B, Lmax, jobs);
         if (!c.g.fits) return fail(e, BH_EINVAL, "model too deep for LDS");
@@ -1283,7 +1310,14 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
         bh_launch_sphere(B, Lmax, m.nlay, m.h, m.vp, m.vs, m.rho, sl, sb, base, base + ne, base + 2 * ne, base + 3 * ne, base + 4 * ne, st);
         c.sph = base;
     }
-    if ((rc = swd_counter(e, st, &c.counter)) || (rc = order_models(c))) return rc;
+    // the call's fills: the ordering launch's where the plan has one (SwdPlan::prologue), else dispatches of their own
+    SwdFills *const prologue = p.prologue ? &c.fills : nullptr;
+    if ((rc = swd_counter(e, st, prologue, &c.counter))) return rc;
+    if (p.any_fast && (rc = guard_space(e, st, B, prologue, &c.gcounts, &c.glists))) return rc;
+    if ((rc = order_models(c))) return rc;
+    e->last_swd_order[0] = p.order;
+    e->last_swd_order[1] = c.order_wgs;
+    e->last_swd_order[2] = !p.prologue ? 0 : (c.fills.nguard > 0 ? BH_FILL_GUARD : 0) | (c.fills.nerr > 0 ? BH_FILL_FLAGS : 0) | (c.fills.ncounter > 0 ? BH_FILL_COUNTERS : 0);
     SwdMultiArgs a{};
     rc = p.kernel == BH_KERNEL_LANE ? launch_swd_lanes(c, a) : launch_swd_multi(c, a);
     if (main) *main = c.info;
@@ -1504,6 +1538,12 @@ int bh_engine_set_swd_arith(bh_engine *e, int arith)
 }
 int bh_engine_get_swd_arith(const bh_engine *e) { return e ? e->swd_arith : 0; }
 int bh_engine_last_swd_kernel(const bh_engine *e) { return e ? e->last_swd_kernel : -1; }
+int bh_engine_last_swd_order(const bh_engine *e, int *workgroups, int *fills)
+{
+    if (workgroups) *workgroups = e ? e->last_swd_order[1] : 0;
+    if (fills) *fills = e ? e->last_swd_order[2] : 0;
+    return e ? e->last_swd_order[0] : -1;
+}
 int bh_engine_last_swd_launches(const bh_engine *e, bh_swd_launch *out, int max, int *n)
 {
     if (!e || !n || max < 0 || (max > 0 && !out)) return BH_EINVAL;
@@ -1715,7 +1755,7 @@ int bh_swd_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax, cons
         job.periods_dev = (const double *)e->periods.p; job.vel = (double *)e->vel.p; job.err = (int32_t *)e->errb.p;
     }
     call_begin(e, st);
-    rc = launch_swd_jobs(e, st, B, Lmax, m, sl, sb, 1, &job, 0, nullptr);
+    rc = launch_swd_jobs(e, st, B, Lmax, m, sl, sb, 1, &job, plan_swd_call(e, B, Lmax, m, 1, &job), SwdFills{}, 0, nullptr);
     call_end(e, st);
     if (rc || !host) return rc;
     HIPCHK(e, hipMemcpyAsync(vel, e->vel.p, (size_t)B * K * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1947,13 +1987,6 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
     const int B = p.B, nt = p.nt, ldy = p.ldy;
     hipStream_t st = c.st, rst = p.fork ? e->aux : st;
     int rc;
-    // per-target failure flags [nt][B]: the dispersion kernels write every entry of their target's row on every call,
-    // nothing writes the rows of the other targets -- they are zeroed once per (nt, B) layout, not once per call
-    if (p.err_zero_always || e->err_t_nt != nt || e->err_t_B != B) {
-        HIPCHK(e, hipMemsetAsync(e->err_t.p, 0, (size_t)nt * B * sizeof(int32_t), st));
-        e->err_t_nt = nt;
-        e->err_t_B = B;
-    }
     SwdJob jobs[BH_MAX_TARGETS];
     int njobs = 0;
     const SwdSiteXArgs xtab{c.site, e->nsites, nt, ldy, (const int32_t *)e->site_xn.p, (const double *)e->site_xper.p, {}, {}};
@@ -1968,6 +2001,21 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
             jobs[njobs++] = SwdJob{T.kfwd, d.iwave, d.igr, T.kfwd, (const double *)T.x60.p, (double *)T.vel60.p, errp, d.mode, d.flsph};
         }
     }
+    // per-target failure flags [nt][B]: the dispersion kernels write every entry of their target's row on every call,
+    // nothing writes the rows of the other targets -- they are zeroed once per (nt, B) layout, not once per call; by the dispersion
+    // call's ordering launch where its plan has one (the receiver-function launches beside it neither read nor write the flags)
+    const SwdPlan sp = plan_swd_call(e, B, c.Lmax, c.m, njobs, jobs);
+    SwdFills fills{};
+    if (p.err_zero_always || e->err_t_nt != nt || e->err_t_B != B) {
+        if (sp.prologue) {
+            fills.err = (int32_t *)e->err_t.p;
+            fills.nerr = nt * B;
+        } else {
+            HIPCHK(e, hipMemsetAsync(e->err_t.p, 0, (size_t)nt * B * sizeof(int32_t), st));
+        }
+        e->err_t_nt = nt;
+        e->err_t_B = B;
+    }
     if (p.fork && (rc = wait_for(e, e->ev_fork, st, e->aux))) return rc;
     if (e->started != nullptr && e->started_expected > 0x70000000u) { // (the counter is cumulative: rewind it long before it wraps)
         HIPCHK(e, hipStreamSynchronize(st));
@@ -1976,7 +2024,7 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
         e->started_expected = 0;
     }
     SwdLaunchInfo swd{};
-    if ((rc = launch_swd_jobs(e, st, B, c.Lmax, c.m, c.sl, c.sb, njobs, jobs, p.prio_low, &swd))) return rc;
+    if ((rc = launch_swd_jobs(e, st, B, c.Lmax, c.m, c.sl, c.sb, njobs, jobs, sp, fills, p.prio_low, &swd))) return rc;
     const bool gate = p.want_gate && swd.workgroups > 0;
     if (gate)
         HIPCHK(e, hipStreamWaitValue32(e->aux, e->started, e->started_expected - swd.workgroups + gate_need(swd), hipStreamWaitValueGte, 0xffffffffu));

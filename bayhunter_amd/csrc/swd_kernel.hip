@@ -294,23 +294,225 @@ __global__ __launch_bounds__(1024) void order_kernel(int B, const int32_t *nlay,
     }
 }
 
-// ---- processing order by predicted search length, paired over the SIMDs (one workgroup) ----------------------------
+// ---- processing order by predicted search length, paired over the SIMDs ----------------------------------------------
 // Predicted length of a model's root search: the range of its S velocities (the search walks from the phase velocity of
 // one period to that of the next in steps of dc: the longer the walk, the more secular evaluations; correlation with the
 // evaluations counted by the oracle on bench.py's models: 0.94 Rayleigh, 0.81 Love).  Models sorted by it (bucket sort,
-// 1024 buckets, longest first); wavefront `wid` of a target takes the group of rank slot_rank[wid] -- the ranks come
+// longest first); wavefront `wid` of a target takes the group of rank slot_rank[wid] -- the ranks come
 // from order_models (bh_engine.hip), which knows which wavefronts share a SIMD.  A batch of mixed depths is ordered by depth instead
 // (deepest first, as order_kernel does): wavefronts of one depth matter more there.
+//   The launch is also the PROLOGUE of the dispersion call it precedes: it zeroes the words of SwdFills, which had fill
+// dispatches of their own before (each a dispatch and a dispatch-to-dispatch gap in front of the dispersion kernel).
+//   Two kernels, picked by bh_launch_pair_order: pair_order_blocked_kernel, a workgroup per XCD block, where every target's
+// order is blocked (PairOrderTarget::xcd); pair_order_kernel, one workgroup over the whole batch, for every other batch.
 constexpr int PAIR_BUCKETS = 1024;
 constexpr int PAIR_MAX_B = 12288; // models the sorted list holds in LDS
+constexpr int PAIR_BLOCKS = 8;    // blocks of a blocked order: one per XCD
+constexpr int BLOCK_BUCKETS = PAIR_BUCKETS / PAIR_BLOCKS; // buckets of a block's sort
+constexpr int BLOCK_MAX_PER = PAIR_MAX_B / PAIR_BLOCKS;   // models of a block
+
+// thread `tid` of `nthreads` zeroes its share of the call's fills
+__device__ __forceinline__ void prologue_fills(const SwdFills &f, int tid, int nthreads)
+{
+    for (int i = tid; i < f.nguard; i += nthreads) f.guard[i] = 0;
+    for (int i = tid; i < f.nerr; i += nthreads) f.err[i] = 0;
+    for (int i = tid; i < f.ncounter; i += nthreads) f.counter[i] = 0ull;
+}
+
+// Layer count (clamped to 1 .. Lmax, into n) and predicted cost (non-negative binary32) of model b.  Which layers are loaded does
+// not depend on the count, and sixteen loads are in flight together: the count and the velocities of arrays of up to sixteen
+// layers arrive in ONE memory latency (a loop over the model's own layers waits for the count first, then for every layer in
+// turn).  A layer beyond the model's is loaded (inside the array: the index is clamped to Lmax - 1) and left out.
+__device__ __forceinline__ float pair_cost(const int32_t *nlay, const double *vs, ptrdiff_t sl, ptrdiff_t sb, int b, int Lmax, int &n)
+{
+    float lo = 1e30f, hi = -1e30f;
+    const double *col = vs + (ptrdiff_t)b * sb;
+    const int nraw = nlay[b];
+    auto sixteen = [&](int l0) { // layers l0 ... l0 + 15
+        double v[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int l = l0 + k < Lmax ? l0 + k : Lmax - 1;
+            v[k] = col[(ptrdiff_t)l * sl];
+        }
+        __builtin_amdgcn_sched_barrier(0); // (the loads first: nothing that waits for the count moves in front of them)
+        const int nl = nraw < 1 ? 1 : (nraw > Lmax ? Lmax : nraw);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const float f = (float)v[k];
+            if (l0 + k < nl) {
+                lo = f < lo ? f : lo;
+                hi = f > hi ? f : hi;
+            }
+        }
+    };
+    sixteen(0); // (outside the loop: a loop's entry would wait for the loads issued so far)
+    for (int l0 = 16; l0 < Lmax; l0 += 16) sixteen(l0);
+    n = nraw < 1 ? 1 : (nraw > Lmax ? Lmax : nraw);
+    const float c = hi - lo;
+    return (c >= 0.0f && c < 1e30f) ? c : 0.0f; // (NaN / absurd models: anywhere)
+}
+
+// Workgroup x orders block x of the batch, models [x per, (x + 1) per) with per = B / 8, and writes that block's slice of every
+// target's order: the wavefronts that run on XCD x (PairOrderTarget::xcd) take the block's groups, longest first.  PT models per
+// thread: one for blocks of up to 1024 models, two beyond.
+//   The bucket scale comes from the BLOCK's own shortest and longest prediction (one workgroup over the batch took the
+// batch's): a block's buckets are no coarser for it, and no workgroup needs another's extremes.
+//   A batch of mixed depths is not blocked: it gets ONE order over the whole batch, deepest first, as pair_order_kernel gives it.
+// Whether the depths are mixed only the device knows, so every workgroup reads the batch's layer counts (beside its own models'
+// velocities, in the same memory latency); for mixed depths it counts the depths of the batch and of the blocks before its own,
+// which is where its models go in the batch's order -- no workgroup waits for another.  Scheduling only: every order gives the same bits.
+template <int PT>
+__global__ __launch_bounds__(1024) void pair_order_blocked_kernel(int B, int Lmax, const int32_t *nlay, const double *vs, ptrdiff_t sl,
+                                                                  ptrdiff_t sb, int nt, PairOrderTarget t0, PairOrderTarget t1, SwdFills fills)
+{
+    __shared__ int bin[BLOCK_BUCKETS];
+    __shared__ int sorted[BLOCK_MAX_PER];
+    __shared__ unsigned cmin_bits, cmax_bits;
+    __shared__ int nmin, nmax, half_sum;
+    __shared__ int deeper[BH_MAX_LAYERS + 2], before[BH_MAX_LAYERS + 2]; // mixed depths: per depth, where this block's models go
+    const int tid = threadIdx.x, nth = blockDim.x, x = blockIdx.x; // (at least BLOCK_BUCKETS threads)
+    const int per = B / PAIR_BLOCKS;
+    prologue_fills(fills, x * nth + tid, PAIR_BLOCKS * nth);
+    if (tid < BLOCK_BUCKETS) bin[tid] = 0;
+    if (tid == 0) {
+        cmin_bits = 0x7f800000u; // +inf
+        cmax_bits = 0u;
+        nmin = BH_MAX_LAYERS + 1;
+        nmax = 0;
+    }
+    __syncthreads();
+    float cost[PT]; // of this thread's models x per + tid + nth i
+    int depth[PT];
+    {
+        unsigned tcmin = 0x7f800000u, tcmax = 0u;
+        int tnmin = BH_MAX_LAYERS + 1, tnmax = 0;
+        // the layer counts of the BATCH, this thread's share (at most 8 PT: the launch has a thread for every model of a block):
+        // loaded in front of the velocities, looked at after them
+        int nb[8 * PT];
+#pragma unroll
+        for (int k = 0; k < 8 * PT; ++k) {
+            const int j = tid + nth * k;
+            nb[k] = nlay[j < B ? j : B - 1];
+        }
+#pragma unroll
+        for (int i = 0; i < PT; ++i) {
+            const int j = tid + nth * i;
+            cost[i] = 0.0f;
+            depth[i] = 1;
+            if (j >= per) continue;
+            const int b = x * per + j;
+            int n;
+            cost[i] = pair_cost(nlay, vs, sl, sb, b, Lmax, n);
+            depth[i] = n;
+            const unsigned cb = __float_as_uint(cost[i]); // (non-negative: the bit pattern orders like the value)
+            tcmin = cb < tcmin ? cb : tcmin;
+            tcmax = cb > tcmax ? cb : tcmax;
+        }
+#pragma unroll
+        for (int k = 0; k < 8 * PT; ++k) { // the depth range of the batch
+            const int n = nb[k] < 1 ? 1 : (nb[k] > Lmax ? Lmax : nb[k]);
+            tnmin = n < tnmin ? n : tnmin;
+            tnmax = n > tnmax ? n : tnmax;
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            tcmin = min(tcmin, (unsigned)__shfl_xor((int)tcmin, off));
+            tcmax = max(tcmax, (unsigned)__shfl_xor((int)tcmax, off));
+            tnmin = min(tnmin, __shfl_xor(tnmin, off));
+            tnmax = max(tnmax, __shfl_xor(tnmax, off));
+        }
+        if ((tid & (BH_WAVE - 1)) == 0) {
+            atomicMin(&cmin_bits, tcmin);
+            atomicMax(&cmax_bits, tcmax);
+            atomicMin(&nmin, tnmin);
+            atomicMax(&nmax, tnmax);
+        }
+    }
+    __syncthreads();
+    if (nmin != nmax) { // mixed depths (the same in every workgroup): this block's part of the batch's order by depth
+        const int nbin = BH_MAX_LAYERS + 2, dmax = Lmax < BH_MAX_LAYERS + 1 ? Lmax : BH_MAX_LAYERS + 1;
+        for (int i = tid; i < nbin; i += nth) deeper[i] = before[i] = 0;
+        __syncthreads();
+        for (int j = tid; j < B; j += nth) { // per depth: the models of the batch, and those in the blocks before this one
+            int n = nlay[j];
+            n = n < 1 ? 1 : (n > dmax ? dmax : n);
+            atomicAdd(&deeper[n], 1);
+            if (j < x * per) atomicAdd(&before[n], 1);
+        }
+        __syncthreads();
+        if (tid == 0) { // deepest first: a depth starts behind every deeper model, this block's share of it behind the earlier blocks'
+            int acc = 0;
+            for (int n = dmax; n >= 1; --n) {
+                const int c = deeper[n];
+                deeper[n] = acc + before[n];
+                acc += c;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < PT; ++i) {
+            const int j = tid + nth * i;
+            if (j >= per) continue;
+            const int n = depth[i] > dmax ? dmax : depth[i];
+            const int pos = atomicAdd(&deeper[n], 1); // (order inside a depth is arbitrary)
+            t0.perm[pos] = x * per + j;
+            if (nt > 1) t1.perm[pos] = x * per + j;
+        }
+        return;
+    }
+    const float cmin = __uint_as_float(cmin_bits), cmax = __uint_as_float(cmax_bits);
+    const float scale = (cmax > cmin) ? (float)(BLOCK_BUCKETS - 1) / (cmax - cmin) : 0.0f;
+    int bucket[PT];
+#pragma unroll
+    for (int i = 0; i < PT; ++i) {
+        const int k = (int)((cmax - cost[i]) * scale); // longest first
+        bucket[i] = k < 0 ? 0 : (k > BLOCK_BUCKETS - 1 ? BLOCK_BUCKETS - 1 : k);
+        if (tid + nth * i < per) atomicAdd(&bin[bucket[i]], 1);
+    }
+    __syncthreads();
+    // exclusive scan of the buckets, one per thread of the first two wavefronts: by shuffles, then the first one's sum
+    int mine = 0, acc = 0;
+    if (tid < BLOCK_BUCKETS) {
+        const int lane = tid & (BH_WAVE - 1);
+        mine = acc = bin[tid];
+        for (int off = 1; off < BH_WAVE; off <<= 1) {
+            const int o = __shfl_up(acc, off);
+            if (lane >= off) acc += o;
+        }
+        if (tid == BH_WAVE - 1) half_sum = acc;
+    }
+    __syncthreads();
+    if (tid < BLOCK_BUCKETS) bin[tid] = (tid >= BH_WAVE ? half_sum : 0) + acc - mine; // start offset of the bucket
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < PT; ++i)
+        if (tid + nth * i < per) sorted[atomicAdd(&bin[bucket[i]], 1)] = tid + nth * i; // (order inside a bucket is arbitrary)
+    __syncthreads();
+    for (int t = 0; t < nt; ++t) {
+        const PairOrderTarget T = t == 0 ? t0 : t1;
+#pragma unroll
+        for (int i = 0; i < PT; ++i) {
+            const int j = tid + nth * i;
+            if (j >= per) continue;
+            // the block's q-th group goes to the wavefront that runs on XCD x as that XCD's q-th wavefront of the target
+            const int q = j / T.mpw, m = j - q * T.mpw;
+            const int wid = (T.xcd == 2) ? (((q >> 1) << 4) | (x << 1) | (q & 1)) : (((q >> 2) << 5) | (x << 2) | (q & 3));
+            T.perm[wid * T.mpw + m] = x * per + sorted[j];
+        }
+    }
+}
+
+// One workgroup over the whole batch: orders that are not blocked, and every batch beside them (nt = 0: the fills alone).
 __global__ __launch_bounds__(1024) void pair_order_kernel(int B, int Lmax, const int32_t *nlay, const double *vs, ptrdiff_t sl, ptrdiff_t sb,
-                                                          int nt, PairOrderTarget t0, PairOrderTarget t1)
+                                                          int nt, PairOrderTarget t0, PairOrderTarget t1, SwdFills fills)
 {
     __shared__ int bin[PAIR_BUCKETS];
     __shared__ int sorted[PAIR_MAX_B];
     __shared__ unsigned cmin_bits, cmax_bits;
     __shared__ int nmin, nmax;
     const int tid = threadIdx.x;
+    prologue_fills(fills, tid, 1024);
+    if (nt == 0) return;
     for (int i = tid; i < PAIR_BUCKETS; i += 1024) bin[i] = 0;
     if (tid == 0) {
         cmin_bits = 0x7f800000u; // +inf
@@ -366,15 +568,12 @@ __global__ __launch_bounds__(1024) void pair_order_kernel(int B, int Lmax, const
     }
     __syncthreads();
     const bool ragged = nmin != nmax;
-    const bool blocked = !ragged && t0.xcd > 0; // (the launcher checked the divisibilities)
-    const int per = B / 8;                      // models of a block
     const float cmin = __uint_as_float(cmin_bits), cmax = __uint_as_float(cmax_bits);
     const float scale = (cmax > cmin) ? (float)(PAIR_BUCKETS - 1) / (cmax - cmin) : 0.0f;
     auto bucket = [&](int i) { // of this thread's i-th model
         if (ragged) return (nmax - depth[i]) < PAIR_BUCKETS ? (nmax - depth[i]) : PAIR_BUCKETS - 1; // deepest first
         int k = (int)((cmax - cost[i]) * scale); // longest first
         k = k < 0 ? 0 : (k > PAIR_BUCKETS - 1 ? PAIR_BUCKETS - 1 : k);
-        if (blocked) k = ((tid + 1024 * i) / per) * (PAIR_BUCKETS / 8) + (k >> 3); // block-major: eight sorted lists one after the other
         return k;
     };
 #pragma unroll
@@ -415,11 +614,6 @@ __global__ __launch_bounds__(1024) void pair_order_kernel(int B, int Lmax, const
             const int wid = pos / T.mpw, m = pos - wid * T.mpw;
             int src = pos; // the last (possibly partly filled) wavefront and mixed-depth batches: sorted order as it is
             if (!ragged && T.slot_rank != nullptr && wid < T.nwaves - 1) src = T.slot_rank[wid] * T.mpw + m;
-            if (blocked) { // wavefront wid runs on XCD x as that XCD's q-th wavefront of the target: the q-th group of block x
-                const int x = (T.xcd == 2) ? (wid >> 1) & 7 : (wid >> 2) & 7;
-                const int q = (T.xcd == 2) ? (((wid >> 4) << 1) | (wid & 1)) : (((wid >> 5) << 2) | (wid & 3));
-                src = x * per + q * T.mpw + m;
-            }
             T.perm[pos] = sorted[src];
         }
     }
@@ -547,10 +741,29 @@ void bh_launch_order(int B, const int32_t *nlay, int32_t *perm, int Lcut, int32_
     hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, stream, B, nlay, perm, Lcut, split);
 }
 
-void bh_launch_pair_order(int B, int Lmax, const int32_t *nlay, const double *vs, ptrdiff_t sl, ptrdiff_t sb, int nt,
-                          const PairOrderTarget *tg, hipStream_t stream)
+int bh_launch_pair_order(int B, int Lmax, const int32_t *nlay, const double *vs, ptrdiff_t sl, ptrdiff_t sb, int nt,
+                         const PairOrderTarget *tg, const SwdFills &fills, hipStream_t stream)
 {
-    hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), 0, stream, B, Lmax, nlay, vs, sl, sb, nt, tg[0], tg[nt > 1 ? 1 : 0]);
+    // blocked: every target's wavefronts divide over the XCD blocks (what the plan that set PairOrderTarget::xcd has checked;
+    // checked again here, since the blocked kernel's stores rely on it)
+    bool blocked = nt > 0 && B > 0 && B <= PAIR_MAX_B && B % PAIR_BLOCKS == 0;
+    for (int t = 0; blocked && t < nt; ++t) {
+        const PairOrderTarget &T = tg[t];
+        blocked = (T.xcd == 2 || T.xcd == 4) && T.mpw > 0 && T.nwaves > 0 && (long)T.mpw * T.nwaves == B && T.nwaves % (PAIR_BLOCKS * T.xcd) == 0;
+    }
+    PairOrderTarget a = nt > 0 ? tg[0] : PairOrderTarget{}, b = nt > 1 ? tg[1] : a;
+    if (!blocked) {
+        hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), 0, stream, B, Lmax, nlay, vs, sl, sb, nt, a, b, fills);
+        return 1;
+    }
+    const int per = B / PAIR_BLOCKS;
+    if (per <= 1024) { // one model per thread, whole wavefronts, at least a thread per bucket
+        const int threads = per <= BLOCK_BUCKETS ? BLOCK_BUCKETS : (per + BH_WAVE - 1) / BH_WAVE * BH_WAVE;
+        hipLaunchKernelGGL(pair_order_blocked_kernel<1>, dim3(PAIR_BLOCKS), dim3(threads), 0, stream, B, Lmax, nlay, vs, sl, sb, nt, a, b, fills);
+    } else {
+        hipLaunchKernelGGL(pair_order_blocked_kernel<2>, dim3(PAIR_BLOCKS), dim3(1024), 0, stream, B, Lmax, nlay, vs, sl, sb, nt, a, b, fills);
+    }
+    return PAIR_BLOCKS;
 }
 bool bh_pair_order_fits(int B) { return B <= PAIR_MAX_B; }
 

@@ -135,6 +135,7 @@ def load_library():
     L.bh_engine_set_swd_arith.argtypes = [vp, C.c_int]
     L.bh_engine_last_swd_kernel.argtypes = [vp]
     L.bh_engine_last_swd_launches.argtypes = [vp, C.POINTER(SwdLaunch), C.c_int, C.POINTER(C.c_int)]
+    L.bh_engine_last_swd_order.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bh_engine_set_swd_trials.argtypes = [vp, C.c_int]
     L.bh_engine_get_swd_trials.argtypes = [vp]
     L.bh_engine_get_swd_arith.argtypes = [vp]
@@ -226,6 +227,7 @@ EXPORTED_SYMBOLS = ("bh_abi_version", "bh_engine_create", "bh_engine_destroy", "
                     "bh_chain_propose", "bh_chain_accept", "bh_chain_propose_window", "bh_chain_accept_window")
 # include/bh_engine_debug.h: measurement, diagnostics, experiment switches (bench.py, tools/, tests)
 DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_last_swd_kernel", "bh_engine_last_swd_launches",
+                 "bh_engine_last_swd_order",
                  "bh_engine_set_swd_scan",
                  "bh_engine_get_swd_scan", "bh_engine_set_tuning",
                  "bh_engine_get_tuning", "bh_probe_math", "bh_engine_set_instrumentation", "bh_timing_reset",
@@ -414,6 +416,15 @@ class Engine(object):
                      key=tuple(r.key), two_classes=bool(r.two_classes), interleaved=bool(r.interleaved),
                      pair_order=bool(r.pair_order), restart=bool(r.restart), grid_x=int(r.grid_x), fair=int(r.fair))
                 for r in out[:n.value]]
+
+    def last_swd_order(self):
+        """How the most recent call with dispersion targets ordered its models (bh_engine_last_swd_order): (order, workgroups,
+        fills) -- "none" / "depth" / "length" / "pair"; workgroups of the ordering launch (0: none, 1, or 8: one per XCD block);
+        the set of what that launch zeroed for the call, of "guard", "flags", "counters"."""
+        wg, fills = C.c_int(0), C.c_int(0)
+        order = self._L.bh_engine_last_swd_order(self._h, C.byref(wg), C.byref(fills))
+        return ({0: "none", 1: "depth", 2: "length", 3: "pair"}.get(order), int(wg.value),
+                {n for b, n in ((1, "guard"), (2, "flags"), (4, "counters")) if fills.value & b})
 
     def swd_arith(self):
         return "fast" if self._L.bh_engine_get_swd_arith(self._h) == ARITH_FAST else "exact"

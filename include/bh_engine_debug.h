@@ -59,6 +59,22 @@ typedef struct {
 #define BH_SWD_SECOND 2
 int bh_engine_last_swd_launches(const bh_engine *e, bh_swd_launch *out, int max, int *n);
 
+/* How the most recent call with dispersion targets ordered its models (diagnostic; scheduling only, -1: no engine).  Returns the
+ * plan's order: BH_ORDER_NONE the caller's, BH_ORDER_DEPTH deepest first, BH_ORDER_LENGTH by predicted search length (the
+ * trial-per-lane kernel), BH_ORDER_PAIR by predicted search length, paired over the SIMDs (the group kernel).
+ * *workgroups: of the launch that computed it -- 0 none, 1 one workgroup over the batch, 8 one per XCD block of a blocked order.
+ * *fills: what that launch zeroed for the call in place of fill dispatches of their own (BH_ORDER_LENGTH and BH_ORDER_PAIR: the
+ * launch is the call's prologue) -- a sum of BH_FILL_GUARD (the head of the short refinement's guard lists), BH_FILL_FLAGS (the
+ * per-target failure flags: once per layout of the call) and BH_FILL_COUNTERS (the evaluation counters, when counting is on). */
+#define BH_ORDER_NONE 0
+#define BH_ORDER_DEPTH 1
+#define BH_ORDER_LENGTH 2
+#define BH_ORDER_PAIR 3
+#define BH_FILL_GUARD 1
+#define BH_FILL_FLAGS 2
+#define BH_FILL_COUNTERS 4
+int bh_engine_last_swd_order(const bh_engine *e, int *workgroups, int *fills);
+
 /* The bracket scan of Love targets (any root refinement).  Results never depend on this setting.
  * getsol's scan (surfdisp96.f:437-460) evaluates every step of its grid until the secular function changes sign.  For Love
  * waves the number of sign changes below a trial velocity is read off the recursion that evaluates the function (a Sturm
