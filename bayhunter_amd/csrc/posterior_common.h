@@ -1,5 +1,5 @@
-// bayhunter_amd/csrc/posterior_common.h -- what posterior_kernel.hip and posterior_scalars_kernel.hip share: the handle, its
-// device buffers, the work items, the ordered keys and the bin rule.
+// bayhunter_amd/csrc/posterior_common.h -- what posterior_kernel.hip, posterior_scalars_kernel.hip and posterior_datafit_kernel.hip
+// share: the handle, its device buffers, the work items, the ordered keys and the bin rule.
 #ifndef BH_POSTERIOR_COMMON_H
 #define BH_POSTERIOR_COMMON_H
 
@@ -83,7 +83,20 @@ struct Dev {
 struct ScalarSet {
     int Q = 0;
     Dev val;
+    // what the last bh_posterior_scalar_stats of the set found (empty: none since the set was formed): every (site, column)'s
+    // count and every column's "not float32-exact" flag -- bh_posterior_scalar_quantiles checks its ranks and sizes its keys by them
+    std::vector<int64_t> count;
+    std::vector<int32_t> nf;
+    void drop()
+    {
+        Q = 0;
+        count.clear();
+        nf.clear();
+    }
 };
+
+// the handle's slot of a set id (include/bh_engine_posterior_datafit.h: MOHO 0, USER 1, DATA 3); -1: no such set
+inline int set_slot(int set) { return set == 0 ? 0 : set == 1 ? 1 : set == 3 ? 2 : -1; }
 
 } // namespace bhpost
 
@@ -100,7 +113,14 @@ struct bh_posterior {
     bool keep_rows = false;               // bh_posterior_keep_rows: the next load keeps porig and pzd
     bool has_rows = false;                // ... and the last one did
     bhpost::Dev porig, pzd;               // the row's index in the loaded input; zd_j in the row's dtype (the scalar sets)
-    bhpost::ScalarSet sets[2];            // BH_SCALARS_MOHO, BH_SCALARS_USER
+    bhpost::ScalarSet sets[3];            // BH_SCALARS_MOHO, BH_SCALARS_USER, BH_SCALARS_DATA (bhpost::set_slot)
+    int data_ldy = 0;                     // bh_posterior_data_fill: the columns of the set being filled, the rows filled so far,
+    int64_t data_filled = -1;             // (-1: no fill under way) and the failed rows per site
+    bhpost::Dev data_failed;
+    bhpost::Dev data_tab;                 // ... and its tables (ncol, the columns' target and index in it), uploaded by the call that starts it
+    std::vector<int32_t> data_ncol;       // (the host copy: the following calls must bring the same table)
+    bhpost::Dev mantle_tab;               // bh_posterior_layers: the last mantle table on the device, and the host copy it is compared with
+    std::vector<double> mantle_host;
 };
 
 namespace bhpost {

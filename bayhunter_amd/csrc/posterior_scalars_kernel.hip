@@ -15,7 +15,7 @@
 // LDS: 24 KiB (hist), 32 KiB (hist2d), 1 KiB (radix) per 256-lane workgroup -- several workgroups per CU beside each other.
 // -ffp-contract=off (Makefile): no product of the crustal mean is contracted into its sum.
 #include "posterior_common.h"
-#include "../../include/bh_engine_posterior_scalars.h"
+#include "../../include/bh_engine_posterior_datafit.h"
 
 #include <algorithm>
 #include <cmath>
@@ -390,11 +390,13 @@ __global__ void __launch_bounds__(256) sc_argmax_kernel(const int64_t *cnt_off, 
 int get_set(bh_posterior *p, int set, ScalarSet **out)
 {
     if (p->S < 1) return pfail(p, BH_EINVAL, "no rows loaded (bh_posterior_load)");
-    if (set != BH_SCALARS_MOHO && set != BH_SCALARS_USER) return pfail(p, BH_EINVAL, "no such scalar set");
-    if (p->sets[set].Q < 1)
-        return pfail(p, BH_EINVAL, set == BH_SCALARS_MOHO ? "the MOHO set does not exist yet (bh_posterior_moho)"
-                                                          : "the USER set does not exist yet (bh_posterior_attach)");
-    *out = &p->sets[set];
+    const int slot = set_slot(set);
+    if (slot < 0) return pfail(p, BH_EINVAL, "no such scalar set");
+    if (p->sets[slot].Q < 1)
+        return pfail(p, BH_EINVAL, slot == 0   ? "the MOHO set does not exist yet (bh_posterior_moho)"
+                                   : slot == 1 ? "the USER set does not exist yet (bh_posterior_attach)"
+                                               : "the DATA set does not exist yet (bh_posterior_data_fill over all rows)");
+    *out = &p->sets[slot];
     return BH_OK;
 }
 
@@ -483,7 +485,7 @@ int bh_posterior_moho(bh_posterior *p, const double *lo, const double *hi, const
     }
     PCHK(p, hipSetDevice(p->device));
     ScalarSet &ss = p->sets[BH_SCALARS_MOHO];
-    ss.Q = 0;
+    ss.drop();
     const size_t nr = (size_t)p->nrows;
     Dev dpar, dfound;
     if ((rc = alloc(p, ss.val, nr * 4 * 8)) || (rc = alloc(p, dpar, (size_t)S * 3 * 8)) || (rc = alloc(p, dfound, (size_t)S * 8)))
@@ -527,7 +529,7 @@ int bh_posterior_attach(bh_posterior *p, int memspace, void *stream, int elem_by
     const bool host = memspace != BH_DEVICE;
     p->st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(p->e);
     ScalarSet &ss = p->sets[BH_SCALARS_USER];
-    ss.Q = 0;
+    ss.drop();
     const int ncols = Q + (with_nlayers ? 1 : 0);
     const size_t nr = (size_t)p->nrows, eb = (size_t)elem_bytes;
     Dev dv;
@@ -602,6 +604,8 @@ int bh_posterior_scalar_stats(bh_posterior *p, int set, int64_t *count, int64_t 
     PCHK(p, hipMemcpyAsync(low.data(), dlow.p, ncol * 4, hipMemcpyDeviceToHost, p->st));
     PCHK(p, hipMemcpyAsync(nf.data(), dnf.p, (size_t)Q * 4, hipMemcpyDeviceToHost, p->st));
     PCHK(p, hipStreamSynchronize(p->st));
+    ss->count.assign(count, count + ncol);   // (for bh_posterior_scalar_quantiles)
+    ss->nf.assign(nf.begin(), nf.end());
     // the fixed-point scale of every column: the lowest set bit, raised until |X| < 2^62 (as bh_posterior_columns)
     for (size_t c = 0; c < ncol; ++c) {
         if (count[c] == 0) { scale[c] = 0; x0[c] = 0; exact[c] = 1; continue; }

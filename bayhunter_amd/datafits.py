@@ -1,0 +1,449 @@
+"""Posterior data fits of many sites on the GPU (include/bh_engine_posterior_datafit.h).
+
+`posterior_datafits` answers, for every station of a many-station run in one call, what BayHunter's
+PlotFromStorage.plot_bestdatafits / plot_bestmodels answer one model at a time -- the model of least joint misfit of every
+chain, turned back into layers and run through every target's forward model -- and one step more: the posterior predictive
+band, i.e. count, min, max, median, mean, std and any quantiles of the synthetic data at every period and time sample over
+the station's WHOLE posterior.  The rows go through bh_posterior_layers -> bh_evaluate_sites -> bh_posterior_data_fill in
+forward batches of a fixed size; the synthetics become the scalar set DATA, whose per-site column passes are those of
+`posterior_scalars`, and bh_posterior_scalar_quantiles selects all the ranks of a column in one read per radix pass.
+
+Exactness: the layers are the reference's Model.get_vp_vs_h and rho = vp * 0.32 + 0.77 in the dtypes numpy
+computes them in; count, min, max, median and the order statistics are bit-exact functions of the synthetics; the quantiles
+are numpy.quantile(..., method="linear") of them; mean and std come from exact integer sums.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import engine as E
+from .posterior import _Loaded, _keys_to_values, _mean_std, _ptr, median_of_middles
+
+DEFAULT_QUANTILES = (0.025, 0.16, 0.5, 0.84, 0.975)
+DEFAULT_MAX_BYTES = 1 << 31   # of the DATA set of one group of sites
+DEFAULT_BATCH = 16384         # rows of one forward batch
+
+
+# ---- the pure parts: quantile formula, planner -----------------------------------------------------------------------------
+
+def quantile_rank(n, p):
+    """(k, g) of numpy.quantile(..., method="linear") over n values: the virtual index (n - 1) * p in float64, its floor and
+    the remainder; the result interpolates the order statistics k and k + 1 (k + 1 = k at the last rank)."""
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("quantiles must be in [0, 1]")
+    if n < 1:
+        return 0, 0.0
+    vi = np.float64(n - 1) * np.float64(p)
+    k = math.floor(vi)
+    if k >= n - 1:
+        return n - 1, 0.0
+    return int(k), float(vi - np.float64(k))
+
+
+def quantile_lerp(a, b, g):
+    """numpy's interpolation between the order statistics a <= b at remainder g: a + (b - a) * g, and b - (b - a) * (1 - g)
+    where g >= 0.5 (float64)."""
+    a, b, g = np.float64(a), np.float64(b), np.float64(g)
+    d = b - a
+    return b - d * (np.float64(1) - g) if g >= 0.5 else a + d * g
+
+
+def plan_site_groups(rows, ldy, max_bytes):
+    """Sites 0..S-1 with rows[s] rows each into consecutive groups [(s0, s1), ...] whose DATA sets (ldy * rows * 8 bytes) stay
+    within max_bytes; a site is never split, so a site that alone exceeds the budget is a group of its own."""
+    rows = [int(r) for r in rows]
+    if ldy < 1 or max_bytes < 1 or any(r < 0 for r in rows):
+        raise ValueError("ldy and max_bytes must be positive, rows non-negative")
+    groups, s0, used = [], 0, 0
+    for s, r in enumerate(rows):
+        need = r * ldy * 8
+        if s > s0 and used + need > max_bytes:
+            groups.append((s0, s))
+            s0, used = s, 0
+        used += need
+    if rows:
+        groups.append((s0, len(rows)))
+    return groups
+
+
+def plan_batches(nrows, batch):
+    """The loaded rows 0..nrows-1 as consecutive forward batches [(r0, r1), ...] of `batch` rows (the last one shorter)."""
+    if batch < 1 or nrows < 0:
+        raise ValueError("batch must be positive, nrows non-negative")
+    return [(r0, min(r0 + batch, nrows)) for r0 in range(0, nrows, batch)]
+
+
+# ---- the handle's calls ----------------------------------------------------------------------------------------------------
+
+def _is_tensor(a):
+    try:
+        import torch
+        return isinstance(a, torch.Tensor)
+    except ImportError:
+        return False
+
+
+def _per_row(a, N, what, ints=False):
+    """one value per input row as (memspace, stream, pointer, stride, element bytes, the array kept alive)"""
+    if _is_tensor(a):
+        import torch
+        a = a.reshape(N)
+        if ints:
+            a = a.to(torch.int32)
+        elif a.dtype not in (torch.float32, torch.float64):
+            a = a.to(torch.float64)
+        return E.DEVICE, C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream), C.c_void_p(a.data_ptr()), a.stride(0) if N else 1, \
+            a.element_size(), a
+    a = np.asarray(a)
+    if a.size != N:
+        raise ValueError("%s: one value per model row" % what)
+    a = a.reshape(N)
+    if ints:
+        a = np.ascontiguousarray(a, np.int32)
+    elif a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    a = np.ascontiguousarray(a)
+    return E.HOST, None, _ptr(a), 1, a.itemsize, a
+
+
+class _DataLoaded(_Loaded):
+    """_Loaded with the calls of include/bh_engine_posterior_datafit.h"""
+
+    def __init__(self, models, site, engine, nsites=None):
+        _Loaded.__init__(self, models, site, engine, nsites, scalars=True)
+        self.nrows = int(self.rows.sum())
+
+    def layers(self, r0, r1, vpvs, mantle_vs, mantle_vpvs, out, stride_l):
+        """vpvs: the tuple of _per_row; out: dict of device tensors nlay, h, vp, vs, rho, site"""
+        mem, stream, ptr, stride, elem, _ = vpvs
+        p = lambda k: C.c_void_p(out[k].data_ptr())
+        self.eng._check(self._L.bh_posterior_layers(self._p, r0, r1, mem, stream, elem, stride, ptr, _ptr(mantle_vs), _ptr(mantle_vpvs),
+                                                    p("nlay"), p("h"), p("vp"), p("vs"), p("rho"), stride_l, p("site")))
+
+    def best(self, nchains, chain, misfits):
+        cm, cs, cp, cst, _, ckeep = _per_row(chain, self.N, "chain", ints=True)
+        mm, ms, mp, mst, mel, mkeep = _per_row(misfits, self.N, "misfits")
+        if cm != mm:                                   # one memspace per call: the host one comes to the device
+            import torch
+            dev = (ckeep if cm == E.DEVICE else mkeep).device
+            if cm == E.HOST:
+                cm, cs, cp, cst, _, ckeep = _per_row(torch.from_numpy(ckeep).to(dev), self.N, "chain", ints=True)
+            else:
+                mm, ms, mp, mst, mel, mkeep = _per_row(torch.from_numpy(mkeep).to(dev), self.N, "misfits")
+        best = np.zeros((self.S, nchains), np.int64)
+        pos = np.zeros((self.S, nchains), np.int64)
+        self.eng._check(self._L.bh_posterior_best(self._p, int(nchains), cm, cs, cp, cst, mel, mp, mst, _ptr(best), _ptr(pos)))
+        return best, pos
+
+    def data_fill(self, stream, r0, nb, ldy, ymod, err, ncol):
+        ncol = np.ascontiguousarray(ncol, np.int32)
+        failed = np.zeros(self.S, np.int64)
+        self.eng._check(self._L.bh_posterior_data_fill(self._p, stream, r0, nb, ldy, C.c_void_p(ymod.data_ptr()) if ymod is not None else None,
+                                                       C.c_void_p(err.data_ptr()) if err is not None else None, ncol.shape[1],
+                                                       _ptr(ncol), _ptr(failed)))
+        return failed
+
+    def quantile_keys(self, which, rank):
+        """rank uint32 [S, Q, R] -> (lower, upper) float64 [S, Q, R]: the order statistics rank and rank + 1"""
+        rank = np.ascontiguousarray(rank, np.uint32)
+        lo, up = np.zeros(rank.shape, np.uint64), np.zeros(rank.shape, np.uint64)
+        self.eng._check(self._L.bh_posterior_scalar_quantiles(self._p, which, rank.shape[2], _ptr(rank), _ptr(lo), _ptr(up)))
+        return lo, up
+
+    def gather(self, which, pos, Q):
+        pos = np.ascontiguousarray(pos, np.int64)
+        out = np.zeros((pos.size, Q))
+        self.eng._check(self._L.bh_posterior_scalar_gather(self._p, which, pos.size, _ptr(pos), _ptr(out)))
+        return out
+
+
+def set_quantiles(ld, which, count, quantiles):
+    """numpy.quantile(column values, quantiles, method="linear") of every (site, column) of a set whose scalar_stats gave
+    `count` [S, Q]: float64 [S, Q, R], NaN where the count is 0.  More than 8 quantiles go in several calls."""
+    S, Q = count.shape
+    qs = [float(q) for q in quantiles]
+    out = np.full((S, Q, len(qs)), np.nan)
+    for i0 in range(0, len(qs), E.QUANTILES_MAXRANKS):
+        part = qs[i0:i0 + E.QUANTILES_MAXRANKS]
+        rank = np.zeros((S, Q, len(part)), np.uint32)
+        g = np.zeros((S, Q, len(part)))
+        memo = {}
+        for s in range(S):
+            for q in range(Q):
+                n = int(count[s, q])
+                if n not in memo:
+                    memo[n] = [quantile_rank(n, p) for p in part]
+                for r, (k, gg) in enumerate(memo[n]):
+                    rank[s, q, r], g[s, q, r] = k, gg
+        lo, up = ld.quantile_keys(which, rank)
+        a = _keys_to_values(lo.reshape(-1), False).reshape(lo.shape)
+        b = _keys_to_values(up.reshape(-1), False).reshape(up.shape)
+        d = b - a
+        with np.errstate(invalid="ignore", over="ignore"):
+            v = np.where(g >= 0.5, b - d * (1.0 - g), a + d * g)
+        out[:, :, i0:i0 + len(part)] = np.where(count[:, :, None] > 0, v, np.nan)
+    return out
+
+
+class _Clock(object):
+    """seconds per phase into a dict (tools/gpu_posterior_datafits_perf.py), the device drained at every lap; nothing without one"""
+
+    def __init__(self, into, dev):
+        import time
+        self.into, self.dev, self.now = into, dev, time.perf_counter
+        self.t = self.now()
+
+    def lap(self, name):
+        if self.into is None:
+            return
+        import torch
+        torch.cuda.synchronize(self.dev)
+        t = self.now()
+        self.into[name] = self.into.get(name, 0.0) + (t - self.t)
+        self.t = t
+
+
+class _Forward(object):
+    """The device buffers of one forward batch and the loop rows -> layers -> bh_evaluate_sites -> DATA set."""
+
+    def __init__(self, eng, dev, B, ML, nt, ldy):
+        import torch
+        self.eng, self.dev, self.B, self.ML, self.nt, self.ldy = eng, dev, B, ML, nt, ldy
+        self.stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        self.buf = dict(nlay=z(B, torch.int32), site=z(B, torch.int32), err=z(B, torch.int32), logL=z(B, torch.float64),
+                        misf=z((B, nt + 1), torch.float64), ymod=z((B, ldy), torch.float64),
+                        noise=torch.tensor([0.0, 1.0] * nt, dtype=torch.float64, device=dev).repeat(B, 1).contiguous())
+        for k in ("h", "vp", "vs", "rho"):
+            self.buf[k] = z((ML, B), torch.float64)
+        torch.cuda.synchronize(dev)
+
+    def fill(self, ld, vpvs, mantle_vs, mantle_vpvs, s0, ncol, clock=None):
+        """Form the DATA set of the loaded rows; site indices of the load + s0 are the targets' sites.  Returns failed[S]."""
+        buf, B, ML = self.buf, self.B, self.ML
+        ptr = lambda k: C.c_void_p(buf[k].data_ptr())
+        failed = np.zeros(ld.S, np.int64)
+        if ld.nrows == 0:
+            failed = ld.data_fill(self.stream, 0, 0, self.ldy, None, None, ncol)
+        for r0, r1 in plan_batches(ld.nrows, B):
+            nb = r1 - r0
+            ld.layers(r0, r1, vpvs, mantle_vs, mantle_vpvs, buf, B)
+            if s0:
+                buf["site"][:nb] += s0
+            if clock is not None:
+                clock.lap("layers")
+            self.eng.evaluate_sites_dev(nb, ML, ptr("nlay"), ptr("h"), ptr("vp"), ptr("vs"), ptr("rho"), B, 1, ptr("site"), ptr("noise"),
+                                        ptr("logL"), ptr("misf"), ptr("err"), ymod=ptr("ymod"), stream=self.stream)
+            if clock is not None:
+                clock.lap("forward")
+            failed = ld.data_fill(self.stream, r0, nb, self.ldy, buf["ymod"], buf["err"], ncol)
+            if clock is not None:
+                clock.lap("fill")
+        return failed
+
+
+# ---- the public call ---------------------------------------------------------------------------------------------------------
+
+def best_rows(models, site, chain, misfits, nsites, engine=None):
+    """int64 [nsites, nchains]: the row of the first least misfit of every (site, chain) (bh_posterior_best alone: nothing goes
+    through a forward model), -1 where the pair has no row; nchains = the largest chain id + 1"""
+    N = models.shape[0]
+    nchains = max(int(_host(chain).reshape(N).max()) + 1, 1) if N else 1
+    ld = _DataLoaded(models, site, engine, nsites)
+    try:
+        return ld.best(nchains, chain, misfits)[0]
+    finally:
+        ld.close()
+
+
+def _as_sites(targets, engine):
+    from .sites import SiteTargets
+    if isinstance(targets, SiteTargets):
+        if engine is not None and targets._engine is None:
+            targets._engine = engine
+        return targets, True
+    return SiteTargets([targets], engine=engine), False
+
+
+def _mantle_arrays(mantle, S):
+    """None, one (vs, vpvs) pair or one pair / None per site -> (mantle_vs[S], mantle_vpvs[S]) or (None, None)"""
+    if mantle is None:
+        return None, None
+    m = list(mantle)
+    if len(m) == 2 and not isinstance(m[0], (tuple, list, np.ndarray, type(None))):
+        m = [m] * S
+    if len(m) != S:
+        raise ValueError("mantle: one (vs, vpvs) pair or one per site")
+    mv, mk = np.full(S, -1.0), np.zeros(S)
+    for s, pair in enumerate(m):
+        if pair is not None:
+            mv[s], mk[s] = float(pair[0]), float(pair[1])
+    return mv, mk
+
+
+def _take(a, idx):
+    """rows idx (numpy int64) of a numpy array or device tensor"""
+    if _is_tensor(a):
+        import torch
+        return a[torch.from_numpy(idx).to(a.device)]
+    return np.asarray(a)[idx]
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if _is_tensor(a) else np.asarray(a)
+
+
+def posterior_datafits(targets, models, vpvs, site=None, chain=None, misfits=None, noise=None, quantiles=DEFAULT_QUANTILES,
+                       mantle=None, engine=None, nsites=None, max_bytes=DEFAULT_MAX_BYTES):
+    """Best fits per chain and the posterior predictive band of every datum, for every site: a list of dicts (one dict where
+    `targets` is a JointTarget).
+
+    targets: a JointTarget (one site) or a SiteTargets with any of its flags; the call registers it on its engine and evaluates
+    through bh_evaluate_sites on device pointers.  models: rows [vs_1..vs_n, z_1..z_n, NaN...] (float32 / float64; numpy array or
+    device tensor) and vpvs one value per row, as for posterior_moho; site: every row's site index (device rows with an index
+    out of range, e.g. -1, are left out).  mantle: None, one (mantle_vs, mantle_vpvs) pair or one pair / None per site: the
+    reference's mantle rule for vp.  noise only feeds the likelihood, which the call discards: every evaluation runs with corr 0
+    and sigma 1, and a given `noise` is not read.
+
+    Every dict holds rows (the site's rows), failed (the rows whose forward model failed: they are masked in every column) and,
+    per target reference ("rdispph", "prf", ...; under missing=True the site's own targets): x, obs, and per datum count, nan (the
+    masked rows), min, max, median, mean, std and quantiles [R, n] (numpy.quantile, method "linear", of the site's synthetics; NaN where count is
+    0).  With chain (int, 0 <= chain) and misfits (the joint misfit) per row: best = a list, per chain that has rows, of dicts
+    chain, row (index into `models`; the first least misfit, numpy.argmin), misfit, model (the row), vpvs and data (target
+    reference -> synthetics; NaN where that model's forward run failed), and thebest = the first of them with the least misfit.
+
+    The DATA set takes ldy * rows * 8 bytes of device memory: where that exceeds max_bytes the sites are split into groups
+    (`plan_site_groups`; sites are independent) that are loaded one after the other; `batch` rows go through the forward
+    kernels at a time (`plan_batches`; DEFAULT_BATCH).
+
+    What leaves the device when the rows are device tensors: `site` comes to the host once (N int32: the rows per site, which
+    the planner of the groups needs), and so do `chain` and `misfits` where given (the number of chains, the misfits of the result
+    dicts), and the rows of the best fits; models, vpvs and all synthetics stay where they are.
+
+    The engine's search and arithmetic settings are the caller's.  With the engine's defaults (the short refinement, the fast
+    arithmetic) the dispersion columns carry the documented 2e-6 relative deviation of the short refinement from the
+    reference's root search; select set_swd_search("reference") and set_swd_arith("exact") for the reference's bits."""
+    return _datafits(targets, models, vpvs, site, chain, misfits, quantiles, mantle, engine, nsites, max_bytes)
+
+
+def _datafits(targets, models, vpvs, site=None, chain=None, misfits=None, quantiles=DEFAULT_QUANTILES, mantle=None, engine=None,
+              nsites=None, max_bytes=DEFAULT_MAX_BYTES, batch=DEFAULT_BATCH, timing=None):
+    """posterior_datafits with the rows of a forward batch and a dict for the seconds per phase (tests, tools)"""
+    import torch
+    st, many = _as_sites(targets, engine)
+    eng = st.engine
+    st._register()
+    S, nt, ldy = st.nsites, st.ntargets, eng.ldy
+    if ldy > E.DATAFIT_MAXCOLS:
+        raise ValueError("%d data columns: at most %d (BH_DATAFIT_MAXCOLS)" % (ldy, E.DATAFIT_MAXCOLS))
+    if nsites is not None and int(nsites) != S:
+        raise ValueError("nsites=%d, the targets have %d sites" % (nsites, S))
+    ncol = st._counts()
+    cap = ncol.max(axis=0)
+    off = np.concatenate(([0], np.cumsum(cap))).astype(int)
+    if off[-1] != ldy:
+        raise ValueError("the targets' columns do not add up to the engine's ldy")
+    if not _is_tensor(vpvs):
+        vpvs = np.asarray(vpvs)
+    N = models.shape[0]
+    qs = tuple(float(q) for q in quantiles)
+    mv, mk = _mantle_arrays(mantle, S)
+    if (chain is None) != (misfits is None):
+        raise ValueError("chain and misfits go together")
+    # rows per site, for the groups
+    if site is None:
+        if S != 1:
+            raise ValueError("site is needed with more than one site")
+        per_site = np.array([N])
+        hsite = None
+    else:
+        hsite = _host(site).astype(np.int64).reshape(N)
+        ok = (hsite >= 0) & (hsite < S)
+        per_site = np.bincount(hsite[ok], minlength=S)
+    groups = plan_site_groups(per_site, ldy, int(max_bytes))
+    nchains = 0
+    if chain is not None:
+        hchain, hmis = _host(chain).reshape(N), _host(misfits).reshape(N)
+        nchains = max(int(hchain.max()) + 1, 1) if N else 1
+    dev = models.device if _is_tensor(models) else torch.device("cuda", eng.device)
+    out = [None] * S
+    clock = _Clock(timing, dev)
+    with torch.cuda.device(dev):
+        fw = _Forward(eng, dev, int(batch), models.shape[1] // 2, nt, ldy)
+        for s0, s1 in groups:
+            whole = (s0, s1) == (0, S)
+            if whole:
+                idx, gm, gv, gs, gc, gf = None, models, vpvs, site, chain, misfits
+            else:
+                idx = np.flatnonzero((hsite >= s0) & (hsite < s1))
+                gm, gv = _take(models, idx), _take(vpvs, idx)
+                gs = (hsite[idx] - s0).astype(np.int32)
+                if _is_tensor(models):
+                    gs = torch.from_numpy(gs).to(dev)
+                gc = None if chain is None else _take(chain, idx)
+                gf = None if misfits is None else _take(misfits, idx)
+            clock.lap("host")
+            ld = _DataLoaded(gm, gs, eng, s1 - s0)
+            clock.lap("load")
+            try:
+                G = s1 - s0
+                # vpvs on the device once: the layer calls read it batch after batch
+                gvt = gv if _is_tensor(gv) else torch.from_numpy(np.ascontiguousarray(np.asarray(gv).reshape(ld.N))).to(dev)
+                vt = _per_row(gvt, ld.N, "vpvs")
+                gmv, gmk = (None, None) if mv is None else (np.ascontiguousarray(mv[s0:s1]), np.ascontiguousarray(mk[s0:s1]))
+                best = pos = None
+                if chain is not None:
+                    best, pos = ld.best(nchains, gc, gf)
+                    clock.lap("best")
+                failed = fw.fill(ld, vt, gmv, gmk, s0, ncol[s0:s1], clock)
+                stt = ld.scalar_stats(E.SCALARS_DATA)
+                clock.lap("statistics")
+                qv = set_quantiles(ld, E.SCALARS_DATA, stt["count"], qs) if qs else np.zeros((G, ldy, 0))
+                clock.lap("quantiles")
+                bdata = None
+                if best is not None and (pos >= 0).any():
+                    bdata = ld.gather(E.SCALARS_DATA, pos[pos >= 0], ldy)
+            finally:
+                ld.close()
+            clock.lap("host")
+            taken = 0
+            for g in range(G):
+                s = s0 + g
+                n_rows = int(ld.rows[g])
+                r = dict(rows=n_rows, failed=int(failed[g]))
+                slots = st._slot_rows()[s]
+                for t, tgt in enumerate(slots):
+                    if tgt is None:
+                        continue
+                    c0, c1 = off[t], off[t] + int(ncol[s, t])
+                    cnt = stt["count"][g, c0:c1]
+                    d = dict(x=np.asarray(tgt.obsdata.x, dtype=float), obs=np.asarray(tgt.obsdata.y, dtype=float), count=cnt.copy(),
+                             nan=stt["nan"][g, c0:c1].copy())
+                    for k in ("min", "max", "median", "mean", "std"):
+                        d[k] = np.full(c1 - c0, np.nan)
+                    for j, q in enumerate(range(c0, c1)):
+                        n = int(cnt[j])
+                        if not n:
+                            continue
+                        d["min"][j], d["max"][j] = stt["min"][g, q], stt["max"][g, q]
+                        d["median"][j] = median_of_middles(stt["med"][g, q, 0], stt["med"][g, q, 1], n)
+                        d["mean"][j], d["std"][j] = _mean_std(n, stt["sums"][g, q], stt["scale"][g, q], stt["x0"][g, q])
+                    d["quantiles"] = np.ascontiguousarray(qv[g, c0:c1].T)
+                    r[tgt.ref] = d
+                if best is not None:
+                    r["best"] = []
+                    for c in range(nchains):
+                        if best[g, c] < 0:
+                            continue
+                        i = int(best[g, c]) if idx is None else int(idx[best[g, c]])
+                        row = bdata[taken]
+                        taken += 1
+                        r["best"].append(dict(chain=c, row=i, misfit=hmis[i], model=_host(models[i]), vpvs=_host(vpvs.reshape(N)[i])[()],
+                                              data={tgt.ref: row[off[t]:off[t] + int(ncol[s, t])].copy()
+                                                    for t, tgt in enumerate(slots) if tgt is not None}))
+                    mis = [b["misfit"] for b in r["best"]]
+                    r["thebest"] = r["best"][int(np.argmin(mis))] if mis else None
+                out[s] = r
+            clock.lap("host")
+    return out if many else out[0]

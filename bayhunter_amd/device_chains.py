@@ -709,6 +709,22 @@ class DeviceChains(object):
                                   nsites=self.nsites)
         return r if self.sites is not None else r[0]
 
+    def posterior_datafits(self, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), phase="p2", cold_only=None, exclude_chains=()):
+        """record="device": bayhunter_amd.posterior_datafits of every site's recorded rows, straight from the device store (one
+        dict per site; one dict without SiteTargets): the best fit of every chain -- the chain id is the row's column in the
+        store, misfits[..., -1] the joint misfit -- and the predictive band of every datum; every site's mantle rule is that of
+        its priors.  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        from .datafits import posterior_datafits
+        d = self._posterior_rows(phase, cold_only, exclude_chains)
+        n = d["models2d"].shape[0]
+        chain = self.torch.arange(self.C, dtype=self.torch.int32, device=self.dev).repeat(n // self.C if self.C else 0)
+        targets = self.sites if self.sites is not None else self.targets
+        mantle = [p.get("mantle") for p in self.site_priors]
+        with self.torch.cuda.device(self.dev):
+            return posterior_datafits(targets, d["models2d"], d["vpvs"].reshape(n), site=d["site"], chain=chain,
+                                      misfits=d["misfits"][..., -1].reshape(n), quantiles=quantiles, mantle=mantle,
+                                      engine=self.engine)
+
     def _host_rows(self, phase):
         """the rows of samples() from the host snapshots of run()"""
         S = self.snap[phase]

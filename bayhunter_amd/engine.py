@@ -206,6 +206,13 @@ def load_library():
     L.bh_posterior_scalar_hist2d.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     for name in POSTERIOR_SCALARS_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_posterior_layers.argtypes = [vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, vp]
+    L.bh_posterior_best.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp]
+    L.bh_posterior_data_fill.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int, vp, vp]
+    L.bh_posterior_scalar_quantiles.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    L.bh_posterior_scalar_gather.argtypes = [vp, C.c_int, C.c_int64, vp, vp]
+    for name in POSTERIOR_DATAFIT_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
@@ -260,6 +267,12 @@ POSTERIOR_SYMBOLS = ("bh_posterior_create", "bh_posterior_destroy", "bh_posterio
 POSTERIOR_SCALARS_SYMBOLS = ("bh_posterior_keep_rows", "bh_posterior_moho", "bh_posterior_attach", "bh_posterior_scalar_cols", "bh_posterior_scalar_stats",
                              "bh_posterior_scalar_hist", "bh_posterior_scalar_hist2d")
 SCALARS_MOHO, SCALARS_USER = 0, 1   # BH_SCALARS_MOHO, BH_SCALARS_USER
+# include/bh_engine_posterior_datafit.h: best fits per chain and posterior predictive bands per site (bayhunter_amd/datafits.py)
+POSTERIOR_DATAFIT_SYMBOLS = ("bh_posterior_layers", "bh_posterior_best", "bh_posterior_data_fill", "bh_posterior_scalar_quantiles",
+                             "bh_posterior_scalar_gather")
+SCALARS_DATA = 3                    # BH_SCALARS_DATA
+DATAFIT_MAXCOLS = 4096              # BH_DATAFIT_MAXCOLS
+QUANTILES_MAXRANKS = 8              # BH_QUANTILES_MAXRANKS
 
 
 def _f64(a):

@@ -199,13 +199,36 @@ class _PriorsUnpickler(pickle.Unpickler):
             return type(str(name), (object,), {})
 
 
-def saved_priors(datapath):
-    """The `priors` dict of the one *_config.pkl in a station's data folder (save_config)."""
+def _saved_config(datapath):
     files = sorted(glob.glob(op.join(datapath, "*_config.pkl")))
     if len(files) != 1:
         raise IOError("%s: expected one *_config.pkl, found %d" % (datapath, len(files)))
     with open(files[0], "rb") as f:
-        return _PriorsUnpickler(f).load()["priors"]
+        return _PriorsUnpickler(f).load()
+
+
+def saved_priors(datapath):
+    """The `priors` dict of the one *_config.pkl in a station's data folder (save_config)."""
+    return _saved_config(datapath)["priors"]
+
+
+def saved_targets(datapath):
+    """The targets of a station's *_config.pkl as this package's own targets: x, y, yerr, the plugin's parameters and the
+    mode / flsph are taken over from the saved objects (read without the reference installed).  The file does not say which noise
+    law the sampler installed: the targets get 'nocorr', which is enough for their forward models."""
+    from . import Targets as T
+    out = []
+    for t in _saved_config(datapath)["targets"]:
+        cls = getattr(T, type(t).__name__)
+        o = t.obsdata
+        new = cls(np.asarray(o.x, dtype=float), np.asarray(o.y, dtype=float), yerr=getattr(o, "yerr", None))
+        plug = getattr(getattr(t, "moddata", None), "plugin", None)
+        params = getattr(plug, "modelparams", None)
+        if params:
+            new.moddata.plugin.set_modelparams(**dict(params))
+        new.set_noise_law("nocorr")
+        out.append(new)
+    return out
 
 
 def _stack_sites(arrays):
@@ -231,3 +254,71 @@ def moho_from_storage(datapaths, moho=None, mohovs=4.2, bins=50, engine=None):
         moho = [tuple(float(v) for v in saved_priors(p)["z"]) for p in datapaths]
     rows, site = _stack_sites([np.load(op.join(p, "c_models.npy")) for p in datapaths])
     return posterior_moho(rows, site=site, moho=moho, mohovs=mohovs, bins=bins, engine=engine, nsites=len(datapaths))
+
+
+def station_slots(targets_per_station):
+    """(rows, missing): every station's targets as a row of slots, one slot per target reference in the order of first
+    appearance, None where the station lacks it; missing = some station lacks a slot (SiteTargets(missing=True) then)"""
+    refs = []
+    for tl in targets_per_station:
+        for t in tl:
+            if t.ref not in refs:
+                refs.append(t.ref)
+    rows = []
+    for tl in targets_per_station:
+        by_ref = {t.ref: t for t in tl}
+        if len(by_ref) != len(tl):
+            raise ValueError("a station has two targets of one reference")
+        rows.append([by_ref.get(r) for r in refs])
+    return rows, any(t is None for row in rows for t in row)
+
+
+def datafits_from_storage(datapaths, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), dev=0.05, engine=None):
+    """Best data fits and posterior predictive bands of many sites (bayhunter_amd.datafits.posterior_datafits, the numbers of the
+    reference's plot_bestdatafits and more): datapaths[s] is site s's data directory.  The best fits come from the main-phase
+    chain files c???_p2{models,vpvs,misfits}.npy, outlier chains (get_outliers with `dev`) left out as the reference's plot
+    leaves them out; the bands from c_models.npy / c_vpvs.npy (save_final_distribution).  Targets, priors and the mantle rule
+    are those of the saved <station>_config.pkl; stations whose configs differ in their targets become the slots of a
+    SiteTargets(missing=True) (`station_slots`).  Returns one dict per site; the `row` of a best fit counts the rows of its own
+    chain file (`chain` is the file's chain index)."""
+    from .datafits import posterior_datafits, best_rows
+    from .sites import SiteTargets
+    S = len(datapaths)
+    slots, missing = station_slots([saved_targets(p) for p in datapaths])
+    st = SiteTargets(slots, engine=engine, per_site_x="all", per_site_rf="all", missing=missing)
+    mantle = [saved_priors(p).get("mantle") for p in datapaths]
+    # the chain files of every station: the rows of the best fits
+    cm, cv, cf, cc, cs, crow = [], [], [], [], [], []
+    for s, p in enumerate(datapaths):
+        outliers = get_outliers(p, dev=dev)
+        for f in _chainfiles(p, 2, "models"):
+            ci = _chainidx(f)
+            if ci in outliers:
+                continue
+            m = np.load(f)
+            cm.append(m)
+            cv.append(np.load(f.replace("models", "vpvs")).reshape(len(m)))
+            cf.append(np.load(f.replace("models", "misfits")).reshape(len(m), -1)[:, -1])
+            cc.append(np.full(len(m), ci, np.int32))
+            cs.append(np.full(len(m), s, np.int32))
+            crow.append(np.arange(len(m)))
+    bands = [np.load(op.join(p, "c_models.npy")) for p in datapaths]
+    rows, site = _stack_sites(bands)
+    vpvs = np.concatenate([np.load(op.join(p, "c_vpvs.npy")).reshape(len(b)) for p, b in zip(datapaths, bands)])
+    out = posterior_datafits(st, rows, vpvs, site=site, quantiles=quantiles, mantle=mantle, engine=engine, nsites=S)
+    if cm:
+        brow, bsite = _stack_sites(cm)
+        bsite = np.concatenate(cs)
+        crow = np.concatenate(crow)
+        cv, cc, cf = np.concatenate(cv), np.concatenate(cc), np.concatenate(cf)
+        # the winners first (no forward model runs for that); only they go through the targets
+        win = best_rows(brow, bsite, cc, cf, S, engine=engine)
+        win = np.sort(win[win >= 0])
+        crow = crow[win]
+        best = posterior_datafits(st, brow[win], cv[win], site=bsite[win], chain=cc[win], misfits=cf[win], quantiles=(), mantle=mantle,
+                                  engine=engine, nsites=S)
+        for s in range(S):
+            for b in best[s]["best"]:
+                b["row"] = int(crow[b["row"]])
+            out[s]["best"], out[s]["thebest"] = best[s]["best"], best[s]["thebest"]
+    return out
