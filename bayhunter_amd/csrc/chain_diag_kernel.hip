@@ -1,0 +1,442 @@
+// bayhunter_amd/csrc/chain_diag_kernel.hip -- order statistics of the chains' recorded series (include/bh_engine_chain_diag.h).
+//
+// The tables are read where record="device" wrote them, [rows][C][Q]: a series is one (chain, column), its samples ld_t apart.
+// Nothing is transposed or copied; a value of a model table (the vs at a depth, the number of layers) is formed from its row
+// where it is needed.
+//
+// sum kernel : one workgroup per chain.  Thread (column q, strand s) adds the samples i = s (mod 16) of its column in ascending i
+//              into the accumulators of the two halves, a fixed tree combines the 16 strands.  Consecutive threads read consecutive
+//              columns of one row.  Mode 0: x0, S1, S1a, S1b, and the check of every value; mode 1, with the means the host formed
+//              in between: M2a, M2b.
+// lag kernel : one workgroup per (chain, column, block of BH_DIAG_LAGBLOCK lags).  It walks the series in tiles of BH_DIAG_TILE
+//              rows: e_i of the tile in LDS (2 KB), and behind it a ring of 2048 e's (16 KB) that holds the halo e_{i+k} of the
+//              block's lags -- every sample is read from memory once per workgroup.  Thread t owns the lags kb + t + 256 j, j < 4,
+//              in four FP64 registers and adds e_i * e_{i+k} in ascending i: e_i is one LDS address for the whole wavefront (a
+//              broadcast), e_{i+k} consecutive addresses in consecutive lanes (ds_read_b64, 32 lanes = one 256-B bank row: no
+//              conflict).  Rows at and beyond T are zeros in LDS: their products add +-0 to a sum that is never -0, so the bits
+//              are those of the sum over i < T-k.
+// medians    : one workgroup per chain, a radix selection (8 bits per pass, 256 LDS counters) on the ordered bit patterns.
+// -ffp-contract=off (Makefile): no product is contracted into a sum; that is part of the contract of the header.
+#include "bh_device.h"
+#include "../../include/bh_engine_chain_diag.h"
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#pragma clang fp contract(off)
+
+#define DIAG_RING 2048
+#define DIAG_BIG 0x1p480     // a value beyond it (or not finite) is refused: e_i * e_j and their sums then stay finite
+
+static_assert(BH_DIAG_LAGBLOCK + 3 * BH_DIAG_TILE <= DIAG_RING, "ring: the live rows of two neighbouring tiles and the rows being loaded");
+static_assert(BH_DIAG_LAGBLOCK == 4 * 256 && BH_DIAG_TILE == 256 && BH_DIAG_STRANDS == 16, "thread layout of the kernels");
+
+namespace {
+
+struct DiagArgs {
+    const void *x;
+    int64_t T, ld_t, ld_c;
+    int Q, L, ML, D;
+    const double *dep;   // device [D] (models)
+};
+
+// the value (t, c, q) of a table of series ...
+template <typename T, bool MODELS, bool CHECK>
+__device__ __forceinline__ double value(const DiagArgs &a, int c, int64_t t, int q, int &bad)
+{
+    const T *row = (const T *)a.x + t * a.ld_t + (int64_t)c * a.ld_c;
+    if (!MODELS) {
+        const double v = (double)row[q];
+        if (CHECK && !(fabs(v) <= DIAG_BIG)) bad |= 1;
+        return v;
+    }
+    // ... and of a table of model rows [vs_1..vs_n, z_1..z_n, NaN...]: vs[#{j : d_j <= dep[q]}] (the rule of bh_engine_posterior.h,
+    // posterior_kernel.hip), column D: n - 1
+    const int W = 2 * a.ML;
+    int cnt = 0, first = W;
+    for (int i = 0; i < W; ++i) {
+        const T v = row[i];
+        const bool nan = v != v;
+        cnt += nan ? 0 : 1;
+        first = (nan && i < first) ? i : first;
+        if (CHECK && !nan && !(fabs((double)v) <= DIAG_BIG)) bad |= 1;
+    }
+    if (cnt == 0 || cnt != first || (cnt & 1)) {
+        bad |= 2;
+        return 0.0;
+    }
+    const int n = cnt / 2;
+    if (q == a.D) return (double)(n - 1);
+    const double xq = a.dep[q];
+    const T *z = row + n;
+    T zprev = (T)0;
+    double dsum = 0.0;
+    int k = 0;
+    for (int j = 0; j < n - 1; ++j) {
+        const T zd = (z[j] + z[j + 1]) / (T)2;
+        const double h = (double)zd - (double)zprev;
+        dsum = j ? dsum + h : h;
+        k += dsum <= xq ? 1 : 0;
+        zprev = zd;
+    }
+    return (double)row[k];
+}
+
+__device__ __forceinline__ double strand_tree(const double (*p)[BH_DIAG_MAXCOLS], int q)
+{
+    return (((p[0][q] + p[1][q]) + (p[2][q] + p[3][q])) + ((p[4][q] + p[5][q]) + (p[6][q] + p[7][q]))) +
+           (((p[8][q] + p[9][q]) + (p[10][q] + p[11][q])) + ((p[12][q] + p[13][q]) + (p[14][q] + p[15][q])));
+}
+
+// MODE 0: out[c][q][4] = x0, S1, S1a, S1b;  MODE 1: out[c][q][2] = M2a, M2b with means[c][q][3] = m, ma, mb
+template <typename T, bool MODELS, int MODE>
+__global__ void __launch_bounds__(256) diag_sum_kernel(DiagArgs a, const double *means, double *out, int *flag)
+{
+    __shared__ double part[3][BH_DIAG_STRANDS][BH_DIAG_MAXCOLS];
+    const int c = blockIdx.x, Q = a.Q;
+    const int64_t Tn = a.T, h = Tn / 2;
+    int bad = 0;
+    for (int w = threadIdx.x; w < Q * BH_DIAG_STRANDS; w += 256) {
+        const int q = w % Q, s = w / Q;
+        const double x0 = value<T, MODELS, MODE == 0>(a, c, 0, q, bad);
+        const double ma = MODE ? means[((size_t)c * Q + q) * 3 + 1] : 0.0, mb = MODE ? means[((size_t)c * Q + q) * 3 + 2] : 0.0;
+        double A = 0.0, B = 0.0, M = 0.0;
+        for (int64_t i = s; i < Tn; i += BH_DIAG_STRANDS) {
+            const double d = value<T, MODELS, MODE == 0>(a, c, i, q, bad) - x0;
+            if (MODE == 0 && !(fabs(d) <= DIAG_BIG)) bad |= 1;
+            if (i < h) {
+                const double u = d - ma;
+                A += MODE ? u * u : d;
+            } else if (i >= Tn - h) {
+                const double u = d - mb;
+                B += MODE ? u * u : d;
+            } else {
+                M = d;
+            }
+        }
+        part[0][s][q] = A;
+        part[1][s][q] = B;
+        part[2][s][q] = M;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < Q) {
+        const int q = threadIdx.x;
+        const double A = strand_tree(part[0], q), B = strand_tree(part[1], q);
+        if (MODE == 0) {
+            double *o = out + ((size_t)c * Q + q) * 4;
+            int dummy = 0;
+            o[0] = value<T, MODELS, false>(a, c, 0, q, dummy);
+            o[1] = (Tn & 1) ? (A + part[2][h % BH_DIAG_STRANDS][q]) + B : A + B;
+            o[2] = A;
+            o[3] = B;
+        } else {
+            double *o = out + ((size_t)c * Q + q) * 2;
+            o[0] = A;
+            o[1] = B;
+        }
+    }
+    if (MODE == 0 && bad) atomicOr(flag, bad);
+}
+
+// P[c][q][k], k = kb .. min(kb + BH_DIAG_LAGBLOCK - 1, L), kb = blockIdx.z * BH_DIAG_LAGBLOCK
+template <typename T, bool MODELS>
+__global__ void __launch_bounds__(256) diag_lag_kernel(DiagArgs a, const double *means, double *P)
+{
+    __shared__ double ea[BH_DIAG_TILE];
+    __shared__ double ring[DIAG_RING];
+    const int c = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    const int kb = blockIdx.z * BH_DIAG_LAGBLOCK;
+    const int nl = min(BH_DIAG_LAGBLOCK, a.L + 1 - kb);   // the block's lags
+    const int nj = (nl + 255) / 256;
+    const int64_t Tn = a.T;
+    int dummy = 0;
+    const double x0 = value<T, MODELS, false>(a, c, 0, q, dummy);
+    const double m = means[((size_t)c * a.Q + q) * 3];
+    // rows [kb, kb + LAGBLOCK) of the ring; every tile then brings the TILE rows behind its halo
+    for (int r = tid; r < BH_DIAG_LAGBLOCK; r += 256) {
+        const int64_t j = (int64_t)kb + r;
+        ring[j & (DIAG_RING - 1)] = j < Tn ? (value<T, MODELS, false>(a, c, j, q, dummy) - x0) - m : 0.0;
+    }
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t t0 = 0; t0 < Tn - kb; t0 += BH_DIAG_TILE) {
+        const int64_t i = t0 + tid, j = t0 + kb + BH_DIAG_LAGBLOCK + tid;
+        const double ei = i < Tn ? (value<T, MODELS, false>(a, c, i, q, dummy) - x0) - m : 0.0;
+        const double ej = j < Tn ? (value<T, MODELS, false>(a, c, j, q, dummy) - x0) - m : 0.0;
+        __syncthreads();   // the tile before is done with ea
+        ea[tid] = ei;
+        ring[j & (DIAG_RING - 1)] = ej;
+        __syncthreads();
+        const int base = (int)((t0 + kb) & (DIAG_RING - 1)) + tid;
+#pragma unroll 4
+        for (int ii = 0; ii < BH_DIAG_TILE; ++ii) {
+            const double av = ea[ii];
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+                if (jj < nj) acc[jj] += av * ring[(base + ii + 256 * jj) & (DIAG_RING - 1)];
+        }
+    }
+    double *o = P + ((size_t)c * a.Q + q) * (size_t)(a.L + 1);
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        const int k = kb + tid + 256 * jj;
+        if (k <= a.L) o[k] = acc[jj];
+    }
+}
+
+template <typename T> struct KeyOf;
+template <> struct KeyOf<float> {
+    typedef unsigned K;
+    static __device__ __forceinline__ K key(float v)
+    {
+        const unsigned u = __float_as_uint(v);
+        return (u >> 31) ? ~u : (u | 0x80000000u);
+    }
+    static __device__ __forceinline__ double val(K k) { return (double)__uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
+};
+template <> struct KeyOf<double> {
+    typedef unsigned long long K;
+    static __device__ __forceinline__ K key(double v)
+    {
+        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+        return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+    }
+    static __device__ __forceinline__ double val(K k)
+    {
+        return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
+    }
+};
+
+// out[c][2]: the values of ranks (T-1)/2 and T/2 of chain c's column
+template <typename T>
+__global__ void __launch_bounds__(256) diag_median_kernel(DiagArgs a, double *out, int *flag)
+{
+    typedef typename KeyOf<T>::K K;
+    __shared__ unsigned hist[256];
+    __shared__ K s_prefix;
+    __shared__ unsigned long long s_rank;
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int64_t Tn = a.T;
+    const T *col = (const T *)a.x + (int64_t)c * a.ld_c;
+    int bad = 0;
+    for (int r = 0; r < 2; ++r) {
+        if (tid == 0) {
+            s_prefix = 0;
+            s_rank = (unsigned long long)(r ? Tn / 2 : (Tn - 1) / 2);
+        }
+        for (int pass = (int)sizeof(T) - 1; pass >= 0; --pass) {
+            const int shift = 8 * pass;
+            hist[tid] = 0;
+            __syncthreads();
+            const K prefix = s_prefix;
+            const K himask = pass == (int)sizeof(T) - 1 ? (K)0 : (K)(~(K)0 << (shift + 8));
+            for (int64_t i = tid; i < Tn; i += 256) {
+                const T v = col[i * a.ld_t];
+                if (r == 0 && pass == (int)sizeof(T) - 1 && !(fabs((double)v) <= 1.7976931348623157e308)) bad |= 1;
+                const K k = KeyOf<T>::key(v);
+                if ((k & himask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned long long rank = s_rank, cum = 0;
+                int d = 0;
+                for (; d < 255; ++d) {
+                    if (cum + hist[d] > rank) break;
+                    cum += hist[d];
+                }
+                s_prefix = prefix | ((K)d << shift);
+                s_rank = rank - cum;
+            }
+            __syncthreads();
+        }
+        if (tid == 0) out[2 * (size_t)c + r] = KeyOf<T>::val(s_prefix);
+        __syncthreads();
+    }
+    if (bad) atomicOr(flag, bad);
+}
+
+struct Buf {
+    void *p = nullptr;
+    ~Buf() { if (p) (void)hipFree(p); }
+    template <typename U> U *as() const { return (U *)p; }
+};
+
+int dfail(bh_engine *e, int code, const std::string &what) { return bh_engine_fail_internal(e, code, what.c_str()); }
+
+#define DCHK(e, call)                                                                                       \
+    do {                                                                                                    \
+        hipError_t _he = (call);                                                                            \
+        if (_he != hipSuccess) return dfail((e), BH_EHIP, std::string(#call ": ") + hipGetErrorString(_he)); \
+    } while (0)
+
+int dalloc(bh_engine *e, Buf &b, size_t bytes)
+{
+    hipError_t he = hipMalloc(&b.p, bytes ? bytes : 8);
+    if (he != hipSuccess) { b.p = nullptr; return dfail(e, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
+    return BH_OK;
+}
+
+// the table on the device: the caller's pointer, or a copy of the span a host table covers
+int table_on_device(bh_engine *e, hipStream_t st, bool host, int elem_bytes, int64_t T, int C, int64_t width, int64_t ld_t,
+                    int64_t ld_c, const void *x, Buf &copy, const void **dx)
+{
+    *dx = x;
+    if (!host) return BH_OK;
+    const size_t span = (size_t)((T - 1) * ld_t + (int64_t)(C - 1) * ld_c + width) * (size_t)elem_bytes;
+    int rc;
+    if ((rc = dalloc(e, copy, span))) return rc;
+    DCHK(e, hipMemcpyAsync(copy.p, x, span, hipMemcpyHostToDevice, st));
+    *dx = copy.p;
+    return BH_OK;
+}
+
+bool layout_ok(int64_t T, int C, int64_t width, int64_t ld_t, int64_t ld_c)
+{
+    if (T < 1 || C < 1 || ld_t < 1 || ld_c < width) return false;
+    // the span in elements stays below 2^60
+    const long double span = (long double)(T - 1) * (long double)ld_t + (long double)(C - 1) * (long double)ld_c + (long double)width;
+    return span < 1.152921504606846976e18L;
+}
+
+template <typename T, bool MODELS>
+int launch_all(bh_engine *e, hipStream_t st, const DiagArgs &a, int C, double *x0, double *s1, double *s1a, double *s1b, double *m2a,
+               double *m2b, double *p)
+{
+    int rc;
+    const size_t nser = (size_t)C * a.Q, np = nser * (size_t)(a.L + 1);
+    Buf dsum, dmean, dm2, dP, dflag;
+    if ((rc = dalloc(e, dsum, nser * 32)) || (rc = dalloc(e, dmean, nser * 24)) || (rc = dalloc(e, dm2, nser * 16)) ||
+        (rc = dalloc(e, dP, np * 8)) || (rc = dalloc(e, dflag, 8)))
+        return rc;
+    DCHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
+    diag_sum_kernel<T, MODELS, 0><<<dim3((unsigned)C), 256, 0, st>>>(a, nullptr, dsum.as<double>(), dflag.as<int>());
+    DCHK(e, hipGetLastError());
+    std::vector<double> hs(nser * 4), hm(nser * 3), h2(nser * 2);
+    int flag = 0;
+    DCHK(e, hipMemcpyAsync(hs.data(), dsum.p, nser * 32, hipMemcpyDeviceToHost, st));
+    DCHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
+    DCHK(e, hipStreamSynchronize(st));
+    if (flag & 2) return dfail(e, BH_EINVAL, "a model row's non-NaN values are not a non-empty prefix of even length");
+    if (flag & 1) return dfail(e, BH_EINVAL, "a value is not finite (or beyond 2^480)");
+    const int64_t h = a.T / 2;
+    for (size_t i = 0; i < nser; ++i) {
+        hm[3 * i] = hs[4 * i + 1] / (double)a.T;
+        hm[3 * i + 1] = h ? hs[4 * i + 2] / (double)h : 0.0;
+        hm[3 * i + 2] = h ? hs[4 * i + 3] / (double)h : 0.0;
+    }
+    DCHK(e, hipMemcpyAsync(dmean.p, hm.data(), nser * 24, hipMemcpyHostToDevice, st));
+    diag_sum_kernel<T, MODELS, 1><<<dim3((unsigned)C), 256, 0, st>>>(a, dmean.as<double>(), dm2.as<double>(), nullptr);
+    DCHK(e, hipGetLastError());
+    const unsigned nblk = (unsigned)(a.L / BH_DIAG_LAGBLOCK + 1);
+    diag_lag_kernel<T, MODELS><<<dim3((unsigned)C, (unsigned)a.Q, nblk), 256, 0, st>>>(a, dmean.as<double>(), dP.as<double>());
+    DCHK(e, hipGetLastError());
+    DCHK(e, hipMemcpyAsync(h2.data(), dm2.p, nser * 16, hipMemcpyDeviceToHost, st));
+    DCHK(e, hipMemcpyAsync(p, dP.p, np * 8, hipMemcpyDeviceToHost, st));
+    DCHK(e, hipStreamSynchronize(st));
+    for (size_t i = 0; i < nser; ++i) {
+        x0[i] = hs[4 * i];
+        s1[i] = hs[4 * i + 1];
+        s1a[i] = hs[4 * i + 2];
+        s1b[i] = hs[4 * i + 3];
+        m2a[i] = h2[2 * i];
+        m2b[i] = h2[2 * i + 1];
+    }
+    return BH_OK;
+}
+
+int diag_run(bh_engine *e, bool models, int memspace, void *stream, int elem_bytes, int64_t T, int C, int Q, int ML, int D,
+             int64_t ld_t, int64_t ld_c, const void *x, const double *dep, int L, double *x0, double *s1, double *s1a, double *s1b,
+             double *m2a, double *m2b, double *p)
+{
+    int rc;
+    if (!e) return BH_EINVAL;
+    if (elem_bytes != 4 && elem_bytes != 8) return dfail(e, BH_EINVAL, "the table must be float32 or float64");
+    if (!x || !x0 || !s1 || !s1a || !s1b || !m2a || !m2b || !p) return dfail(e, BH_EINVAL, "null argument");
+    if (L < 0 || L > BH_DIAG_MAXLAG) return dfail(e, BH_EINVAL, "maxlag must be 0..BH_DIAG_MAXLAG");
+    if (models) {
+        if (ML < 1 || ML > BH_POSTERIOR_MAXLAYERS) return dfail(e, BH_EINVAL, "row width 2*ML must be 2..64 (ML <= BH_POSTERIOR_MAXLAYERS)");
+        if (D < 0 || D > BH_DIAG_MAXDEPTHS || (D && !dep)) return dfail(e, BH_EINVAL, "depths: 0..BH_DIAG_MAXDEPTHS");
+        for (int j = 0; j < D; ++j)
+            if (!std::isfinite(dep[j]) || (j && !(dep[j] > dep[j - 1])))
+                return dfail(e, BH_EINVAL, "the depths must be finite and strictly ascending");
+        Q = D + 1;
+    } else if (Q < 1 || Q > BH_DIAG_MAXCOLS) {
+        return dfail(e, BH_EINVAL, "columns: 1..BH_DIAG_MAXCOLS per call");
+    }
+    const int64_t width = models ? 2 * ML : Q;
+    if (!layout_ok(T, C, width, ld_t, ld_c)) return dfail(e, BH_EINVAL, "bad T, C or leading dimensions");
+    DCHK(e, hipSetDevice(bh_engine_device_internal(e)));
+    const bool host = memspace != BH_DEVICE;
+    hipStream_t st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
+    Buf copy, ddep;
+    DiagArgs a;
+    if ((rc = table_on_device(e, st, host, elem_bytes, T, C, width, ld_t, ld_c, x, copy, &a.x))) return rc;
+    a.T = T; a.ld_t = ld_t; a.ld_c = ld_c; a.Q = Q; a.L = L; a.ML = ML; a.D = D; a.dep = nullptr;
+    if (models && D) {
+        if ((rc = dalloc(e, ddep, (size_t)D * 8))) return rc;
+        DCHK(e, hipMemcpyAsync(ddep.p, dep, (size_t)D * 8, hipMemcpyHostToDevice, st));
+        a.dep = ddep.as<double>();
+    }
+    if (models)
+        rc = elem_bytes == 4 ? launch_all<float, true>(e, st, a, C, x0, s1, s1a, s1b, m2a, m2b, p)
+                             : launch_all<double, true>(e, st, a, C, x0, s1, s1a, s1b, m2a, m2b, p);
+    else
+        rc = elem_bytes == 4 ? launch_all<float, false>(e, st, a, C, x0, s1, s1a, s1b, m2a, m2b, p)
+                             : launch_all<double, false>(e, st, a, C, x0, s1, s1a, s1b, m2a, m2b, p);
+    if (rc != BH_OK) (void)hipStreamSynchronize(st);   // (the buffers go with this frame)
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int bh_chain_diag_series(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t T, int C, int Q, int64_t ld_t,
+                         int64_t ld_c, const void *x, int L, double *x0, double *s1, double *s1a, double *s1b, double *m2a,
+                         double *m2b, double *p)
+{
+    return diag_run(e, false, memspace, stream, elem_bytes, T, C, Q, 0, 0, ld_t, ld_c, x, nullptr, L, x0, s1, s1a, s1b, m2a, m2b, p);
+}
+
+int bh_chain_diag_models(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t T, int C, int ML, int64_t ld_t,
+                         int64_t ld_c, const void *models, int D, const double *dep, int L, double *x0, double *s1, double *s1a,
+                         double *s1b, double *m2a, double *m2b, double *p)
+{
+    return diag_run(e, true, memspace, stream, elem_bytes, T, C, 0, ML, D, ld_t, ld_c, models, dep, L, x0, s1, s1a, s1b, m2a, m2b, p);
+}
+
+int bh_chain_diag_medians(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t T, int C, int64_t ld_t, int64_t ld_c,
+                          const void *x, double *lo, double *hi)
+{
+    int rc;
+    if (!e) return BH_EINVAL;
+    if (elem_bytes != 4 && elem_bytes != 8) return dfail(e, BH_EINVAL, "the table must be float32 or float64");
+    if (!x || !lo || !hi) return dfail(e, BH_EINVAL, "null argument");
+    if (!layout_ok(T, C, 1, ld_t, ld_c) || T >= ((int64_t)1 << 32)) return dfail(e, BH_EINVAL, "bad T, C or leading dimensions");
+    DCHK(e, hipSetDevice(bh_engine_device_internal(e)));
+    const bool host = memspace != BH_DEVICE;
+    hipStream_t st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
+    Buf copy, dout, dflag;
+    DiagArgs a;
+    if ((rc = table_on_device(e, st, host, elem_bytes, T, C, 1, ld_t, ld_c, x, copy, &a.x))) return rc;
+    a.T = T; a.ld_t = ld_t; a.ld_c = ld_c; a.Q = 1; a.L = 0; a.ML = 0; a.D = 0; a.dep = nullptr;
+    if ((rc = dalloc(e, dout, (size_t)C * 16)) || (rc = dalloc(e, dflag, 8))) return rc;
+    DCHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
+    if (elem_bytes == 4) diag_median_kernel<float><<<dim3((unsigned)C), 256, 0, st>>>(a, dout.as<double>(), dflag.as<int>());
+    else diag_median_kernel<double><<<dim3((unsigned)C), 256, 0, st>>>(a, dout.as<double>(), dflag.as<int>());
+    DCHK(e, hipGetLastError());
+    std::vector<double> ho((size_t)C * 2);
+    int flag = 0;
+    DCHK(e, hipMemcpyAsync(ho.data(), dout.p, (size_t)C * 16, hipMemcpyDeviceToHost, st));
+    DCHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
+    DCHK(e, hipStreamSynchronize(st));
+    if (flag) return dfail(e, BH_EINVAL, "a value is not finite");
+    for (int c = 0; c < C; ++c) {
+        lo[c] = ho[2 * (size_t)c];
+        hi[c] = ho[2 * (size_t)c + 1];
+    }
+    return BH_OK;
+}
+
+} // extern "C"

@@ -725,6 +725,35 @@ class DeviceChains(object):
                                       misfits=d["misfits"][..., -1].reshape(n), quantiles=quantiles, mantle=mantle,
                                       engine=self.engine)
 
+    def diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_chains=None):
+        """record="device": bayhunter_amd.diagnostics of every site's chains, straight from the time-ordered views of the device
+        store (one dict per site; one dict without SiteTargets): `outliers` -- the global numbers of the chains the reference's rule
+        (results.get_outliers, deviation `dev`) rejects, ready to pass as exclude_chains= to the posterior_* methods --, their
+        `scores`, and for likes, vpvs, misfits [nt+1], noise [2nt] (slot layout), nlayers and vs (at the depths `dep`, default
+        np.linspace(0, 100, 41)) the dict of diagnostics.convergence: split R-hat, ESS, tau, the flags and the per-chain numbers.
+        exclude_chains None: R-hat and ESS over the chains that are no outliers; a sequence of chain numbers overrides that.
+        maxlag: the largest lag of the autocorrelation sums, default min(T // 2, 1000).
+        EngineError: record="host" (no time-ordered store on the GPU), a tempered run (a ladder's cold state moves between chains:
+        no chain's series is a posterior series) and a sharded job of more than one rank (a site's chains lie on several GPUs)."""
+        if self._rec is None:
+            raise EngineError("diagnostics() needs DeviceChains(record='device'): record='host' keeps no time-ordered store of the "
+                              "chains on the GPU (results.diagnostics_from_storage reads saved folders)")
+        if self.t["beta"] is not None:
+            raise EngineError("diagnostics() of a tempered run: a ladder's cold state moves between chains, so no chain's recorded "
+                              "series is a series of posterior samples")
+        if self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1:
+            raise EngineError("diagnostics() of a sharded job (world size %d): the chains of a site lie on several ranks"
+                              % self.dist.get_world_size())
+        from .diagnostics import diagnose
+        d = self.samples_dev(phase)
+        if not d["likes"].shape[0]:
+            raise EngineError("diagnostics(): no snapshot of phase %r yet" % (phase,))
+        ids = self.chain_offset + np.arange(self.C, dtype=np.int64)
+        with self.torch.cuda.device(self.dev):
+            r = diagnose(d, np.arange(self.C) // self.C_site, ids, dev=dev, dep=dep, maxlag=maxlag, exclude_chains=exclude_chains,
+                         engine=self.engine)
+        return r if self.sites is not None else r[0]
+
     def _host_rows(self, phase):
         """the rows of samples() from the host snapshots of run()"""
         S = self.snap[phase]

@@ -1,0 +1,336 @@
+"""Convergence of every site's chains: outlier chains, split R-hat and effective sample size.
+
+The reference answers "which chains may be summarised, and have they converged?" with PlotFromStorage.get_outliers and the
+plot_iiter* trace plots a person reads for one station.  Here the numbers come per station and per parameter, from the
+time-ordered tables of the chains' thinned samples -- [rows][C][..], one column per chain, which is what record="device" writes
+(DeviceChains.samples_dev) and what the saved c???_p2*.npy files stack to.
+
+Three layers:
+
+chain_series_stats / chain_model_stats -- the GPU part (include/bh_engine_chain_diag.h).  Per series (chain c, column q) of T
+    samples x_i, in float64:  x0 = x_0,  d_i = x_i - x0,  h = T // 2,  the halves i < h and i >= T - h,
+        S1 = sum d_i,  S1a, S1b = the halves' sums,
+        m = S1 / T,  ma = S1a / h,  mb = S1b / h,
+        M2a = sum_{first half} (d_i - ma)^2,  M2b likewise,
+        P_k = sum_{i < T-k} e_i e_{i+k},  e_i = d_i - m,  k = 0..maxlag  (0 for k >= T),
+    every sum in an order that depends on (T, maxlag) only, so a series has the same bits wherever it stands.
+
+convergence -- pure numpy on those tables.  For a site with the kept chains c = 1..m, n = T, per column:
+    per chain   mean_c = x0 + S1 / n,   std_c = sqrt(P_0 / (n - 1)),
+                tau_c  = the estimator below with this chain alone (m = 1).
+    split R-hat over the 2m half chains:
+                W    = mean over the halves of M2 / (h - 1)
+                B/h  = the variance (ddof 1) of the 2m half means  x0 + S1a / h,  x0 + S1b / h
+                rhat = sqrt(((h - 1) / h * W + B/h) / W)
+    ESS (Stan's multi-chain estimator, on the unsplit chains):
+                W_n   = mean_c P_{c,0} / (n - 1)
+                B/n   = the variance (ddof 1) of the m chain means (0 for m = 1)
+                var+  = (n - 1) / n * W_n + B/n
+                rho_k = 1 - (W_n - mean_c P_{c,k} / n) / var+,      k = 0..maxlag
+                G_j   = rho_{2j} + rho_{2j+1},                       j = 0..(maxlag + 1) // 2 - 1   (Geyer's pairs)
+                cut   = the first j with G_j <= 0 (the number of pairs if there is none: then ess_truncated)
+                G_j   = min(G_j, G_{j-1}) for 0 < j < cut           (monotone)
+                tau   = -1 + 2 * sum_{j < cut} G_j
+                ess   = m n / max(tau, 1 / log10(m n))               (the cap at m n log10(m n))
+    constant: every kept chain has P_0 == 0 -- rhat, ess and tau are NaN (a fixed vpvs, a fixed correlation, an absent slot).
+    T < 4, no kept chain, or no pair (maxlag < 1, for ess and tau): NaN, not an error.
+
+outlier_chains -- the reference's rule (Plotting.get_outliers, results.get_outliers) per site: the chains whose median likelihood
+    deviates from the site's best chain's by more than `dev`.
+
+Not here: rank-normalised and folded R-hat, the ladders of tempered runs, chains spread over ranks.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import engine as E
+from .posterior import median_of_middles
+
+FIELDS = ("x0", "s1", "s1a", "s1b", "m2a", "m2b")
+
+
+def _is_tensor(a):
+    try:
+        import torch
+    except ImportError:
+        return False
+    return isinstance(a, torch.Tensor)
+
+
+def _table(values):
+    """(pointer, memspace, stream, elem_bytes, shape, strides in elements, keep-alive) of a [T][C] or [T][C][Q] table: a numpy
+    array or a device torch tensor, read where it lies when its last axis is contiguous (else copied once)"""
+    if _is_tensor(values):
+        import torch
+        if not values.is_cuda or values.dtype not in (torch.float32, torch.float64) or values.dim() not in (2, 3):
+            raise ValueError("a table is a [T][C] or [T][C][Q] float32/float64 array or device tensor")
+        if values.dim() == 3 and values.shape[2] > 1 and values.stride(2) != 1:
+            values = values.contiguous()
+        if min(values.stride()[:2]) < 1 and values.shape[0] > 1 and values.shape[1] > 1:
+            values = values.contiguous()
+        stream = C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
+        return C.c_void_p(values.data_ptr()), E.DEVICE, stream, values.element_size(), tuple(values.shape), tuple(values.stride()), values
+    a = np.asarray(values)
+    if a.dtype not in (np.float32, np.float64) or a.ndim not in (2, 3):
+        raise ValueError("a table is a [T][C] or [T][C][Q] float32/float64 array or device tensor")
+    st = a.strides
+    ok = all(s % a.itemsize == 0 and s > 0 for s in st[:2]) and (a.ndim == 2 or a.shape[2] == 1 or st[2] == a.itemsize)
+    if not ok:
+        a = np.ascontiguousarray(a)
+    strides = tuple(s // a.itemsize for s in a.strides)
+    return C.c_void_p(a.ctypes.data), E.HOST, None, a.itemsize, a.shape, strides, a
+
+
+def _engine(engine):
+    return engine if engine is not None else E.default_engine(0)
+
+
+def _outputs(Cn, Q, L):
+    out = {k: np.zeros((Cn, Q)) for k in FIELDS}
+    out["p"] = np.zeros((Cn, Q, L + 1))
+    return out
+
+
+def _lds(shape, strides, width):
+    """ld_t, ld_c of a table; an axis of length 1 has no stride of its own"""
+    T, Cn = shape[:2]
+    ld_c = strides[1] if Cn > 1 else width
+    ld_t = strides[0] if T > 1 else max(1, ld_c * Cn)
+    return int(ld_t), int(ld_c)
+
+
+def chain_series_stats(values, maxlag, engine=None):
+    """The sums of the module docstring for every series of a table values[t][c] or values[t][c][q] (float32 / float64; a numpy
+    array or a device torch tensor, strided views such as store["misfits"][lo:hi] included -- read where they lie, no copy):
+    dict of x0, s1, s1a, s1b, m2a, m2b [C][Q], p [C][Q][maxlag + 1] (float64), T and maxlag.  At most 64 columns go into one
+    engine call; wider tables take several.  EngineError: a value that is not finite."""
+    eng = _engine(engine)
+    ptr, mem, stream, elem, shape, strides, keep = _table(values)
+    T, Cn = int(shape[0]), int(shape[1])
+    Q = int(shape[2]) if len(shape) == 3 else 1
+    L = int(maxlag)
+    if T < 1 or Cn < 1 or Q < 1:
+        raise ValueError("an empty table")
+    ld_t, ld_c = _lds(shape, strides, Q)
+    out = _outputs(Cn, Q, L)
+    for q0 in range(0, Q, E.DIAG_MAXCOLS):
+        nq = min(E.DIAG_MAXCOLS, Q - q0)
+        part = out if nq == Q else _outputs(Cn, nq, L)
+        eng._check(eng._L.bh_chain_diag_series(eng._h, mem, stream, elem, T, Cn, nq, ld_t, ld_c, C.c_void_p(ptr.value + q0 * elem), L,
+                                               *[E._ptr(part[k]) for k in FIELDS + ("p",)]))
+        if part is not out:
+            for k in FIELDS + ("p",):
+                out[k][:, q0:q0 + nq] = part[k]
+    out["T"], out["maxlag"] = T, L
+    del keep
+    return out
+
+
+def chain_model_stats(models, dep, maxlag, engine=None):
+    """The same for the series derived from model rows models[t][c][2*ML] (the reference's row layout): column q < len(dep) the vs
+    at depth dep[q] (the rule of posterior_models), the last column nlayers = n - 1.  The values are formed in the kernel."""
+    eng = _engine(engine)
+    ptr, mem, stream, elem, shape, strides, keep = _table(models)
+    if len(shape) != 3 or shape[2] % 2:
+        raise ValueError("models: [T][C][2*ML]")
+    T, Cn, ML = int(shape[0]), int(shape[1]), int(shape[2]) // 2
+    dep = np.ascontiguousarray(dep, np.float64).reshape(-1)
+    D, L = dep.size, int(maxlag)
+    if T < 1 or Cn < 1:
+        raise ValueError("an empty table")
+    ld_t, ld_c = _lds(shape, strides, 2 * ML)
+    out = _outputs(Cn, D + 1, L)
+    eng._check(eng._L.bh_chain_diag_models(eng._h, mem, stream, elem, T, Cn, ML, ld_t, ld_c, ptr, D, E._ptr(dep), L,
+                                           *[E._ptr(out[k]) for k in FIELDS + ("p",)]))
+    out["T"], out["maxlag"] = T, L
+    del keep
+    return out
+
+
+def chain_medians(likes, engine=None):
+    """numpy.median of every chain's column of likes[t][c], in the table's dtype: on the GPU for a device tensor (a radix selection
+    of the two middle values, include/bh_engine_chain_diag.h), numpy.median itself for a numpy array."""
+    if not _is_tensor(likes):
+        a = np.asarray(likes)
+        if a.ndim != 2:
+            raise ValueError("likes: [T][C]")
+        return np.array([np.median(a[:, c]) for c in range(a.shape[1])], dtype=a.dtype)
+    eng = _engine(engine)
+    ptr, mem, stream, elem, shape, strides, keep = _table(likes)
+    if len(shape) != 2:
+        raise ValueError("likes: [T][C]")
+    T, Cn = int(shape[0]), int(shape[1])
+    ld_t, ld_c = _lds(shape, strides, 1)
+    lo, hi = np.zeros(Cn), np.zeros(Cn)
+    eng._check(eng._L.bh_chain_diag_medians(eng._h, mem, stream, elem, T, Cn, ld_t, ld_c, ptr, E._ptr(lo), E._ptr(hi)))
+    dtype = np.float32 if elem == 4 else np.float64
+    del keep
+    return np.array([median_of_middles(lo[c], hi[c], T, dtype) for c in range(Cn)], dtype=dtype)
+
+
+def outlier_scores(medians):
+    """1 - score of every chain against the best one, the three branches of the reference's rule"""
+    medians = np.asarray(medians)
+    maxlike = np.max(medians)
+    if maxlike > 0:
+        scores = medians / maxlike
+    elif maxlike < 0:
+        scores = maxlike / medians
+    else:
+        scores = np.ones_like(medians)
+    return 1 - scores
+
+
+def outlier_chains(likes, site_of_chain, dev=0.05, engine=None):
+    """The reference's outlier rule per site.  likes[t][c]: the chains' likelihood series (numpy or device tensor);
+    site_of_chain[c]: the chain's site.  Returns (outliers, scores): per site the positions c of its outlier chains (1 - score >
+    dev, strictly) and their 1 - score -- what results.get_outliers returns for the site's folder, with file numbers for c."""
+    med = chain_medians(likes, engine=engine)
+    site_of_chain = np.asarray(site_of_chain, dtype=np.int64)
+    if site_of_chain.shape != med.shape:
+        raise ValueError("site_of_chain: one site per chain")
+    S = int(site_of_chain.max()) + 1 if site_of_chain.size else 0
+    outliers, scores = [], []
+    for s in range(S):
+        idx = np.flatnonzero(site_of_chain == s)
+        if not idx.size:
+            outliers.append(idx)
+            scores.append(np.zeros(0))
+            continue
+        sc = outlier_scores(med[idx])
+        sel = np.where(sc > dev)
+        outliers.append(idx[sel])
+        scores.append(sc[sel])
+    return outliers, scores
+
+
+def geyer_tau(rho):
+    """(tau, cut, truncated) of an autocorrelation table rho[k], k = 0..L: Geyer's initial monotone sequence (module docstring)"""
+    rho = np.asarray(rho, dtype=np.float64)
+    npairs = rho.size // 2
+    if npairs < 1:
+        return np.nan, 0, True
+    G = rho[0:2 * npairs:2] + rho[1:2 * npairs:2]
+    bad = np.flatnonzero(~(G > 0))
+    cut = int(bad[0]) if bad.size else npairs
+    G = np.minimum.accumulate(G[:cut])
+    return -1.0 + 2.0 * float(np.sum(G)), cut, not bad.size
+
+
+def _ess_block(p, means, n):
+    """(tau, cut, truncated) of the chains with lag sums p[m][L+1] and means[m]"""
+    m = p.shape[0]
+    Wn = np.mean(p[:, 0]) / (n - 1)
+    Bn = np.var(means, ddof=1) if m > 1 else 0.0
+    varp = (n - 1) / n * Wn + Bn
+    rho = 1.0 - (Wn - np.mean(p, axis=0) / n) / varp
+    return geyer_tau(rho)
+
+
+def convergence(tables, site_of_chain, exclude=()):
+    """Split R-hat, ESS and per-chain summaries of every site from the tables of chain_series_stats / chain_model_stats (formulas:
+    module docstring).  site_of_chain[c]: the chain's site; exclude: positions c left out (outliers).  Returns one dict per site:
+    chains [m] (the kept positions), rhat, ess, tau [Q], cut [Q] (the Geyer cut, in pairs), ess_truncated, constant [Q] (bool),
+    mean, std, chain_tau [m][Q]."""
+    T, L = int(tables["T"]), int(tables["maxlag"])
+    Cn, Q = tables["x0"].shape
+    site_of_chain = np.asarray(site_of_chain, dtype=np.int64)
+    if site_of_chain.shape != (Cn,):
+        raise ValueError("site_of_chain: one site per chain")
+    drop = np.zeros(Cn, bool)
+    drop[np.asarray(exclude, dtype=np.int64).reshape(-1)] = True
+    S = int(site_of_chain.max()) + 1 if Cn else 0
+    n, h = T, T // 2
+    out = []
+    with np.errstate(all="ignore"):
+        for s in range(S):
+            idx = np.flatnonzero((site_of_chain == s) & ~drop)
+            m = idx.size
+            r = dict(chains=idx, rhat=np.full(Q, np.nan), ess=np.full(Q, np.nan), tau=np.full(Q, np.nan), cut=np.zeros(Q, np.int64),
+                     ess_truncated=np.zeros(Q, bool), constant=np.zeros(Q, bool),
+                     mean=np.full((m, Q), np.nan), std=np.full((m, Q), np.nan), chain_tau=np.full((m, Q), np.nan))
+            out.append(r)
+            if not m:
+                continue
+            x0, p = tables["x0"][idx], tables["p"][idx]
+            r["mean"][:] = x0 + tables["s1"][idx] / n
+            if n > 1:
+                r["std"][:] = np.sqrt(p[:, :, 0] / (n - 1))
+            r["constant"][:] = np.all(p[:, :, 0] == 0, axis=0)
+            if n < 4:
+                continue
+            for q in range(Q):
+                if r["constant"][q]:
+                    continue
+                W = np.mean(np.concatenate((tables["m2a"][idx, q], tables["m2b"][idx, q])) / (h - 1))
+                Bh = np.var(np.concatenate((x0[:, q] + tables["s1a"][idx, q] / h, x0[:, q] + tables["s1b"][idx, q] / h)), ddof=1)
+                r["rhat"][q] = np.sqrt(((h - 1) / h * W + Bh) / W)
+                tau, cut, trunc = _ess_block(p[:, q, :], r["mean"][:, q], n)
+                r["tau"][q], r["cut"][q], r["ess_truncated"][q] = tau, cut, trunc
+                r["ess"][q] = m * n / max(tau, 1.0 / np.log10(m * n))
+                for j in range(m):
+                    if p[j, q, 0] > 0:
+                        r["chain_tau"][j, q] = _ess_block(p[j:j + 1, q, :], r["mean"][j:j + 1, q], n)[0]
+    return out
+
+
+GROUPS = ("likes", "vpvs", "misfits", "noise", "nlayers", "vs")
+
+
+def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=None, exclude_chains=None, engine=None):
+    """Outliers and convergence of every site from the tables of a run: tables_of = dict of likes, vpvs [T][C], misfits [T][C][nt+1],
+    noise [T][C][2nt], models [T][C][2*ML] (numpy arrays or device tensors).  chain_ids[c]: the chain's number (what `outliers` and
+    exclude_chains hold).  One dict per site: outliers, scores, chain_ids, dep, maxlag, and for every name of GROUPS the dict of
+    convergence().  What DeviceChains.diagnostics and results.diagnostics_from_storage share."""
+    chain_ids = np.asarray(chain_ids, dtype=np.int64)
+    site_of_chain = np.asarray(site_of_chain, dtype=np.int64)
+    T = int(tables_of["likes"].shape[0])
+    dep = np.linspace(0, 100, 41) if dep is None else np.asarray(dep, dtype=np.float64)
+    L = min(T // 2, 1000) if maxlag is None else int(maxlag)
+    outl, scores = outlier_chains(tables_of["likes"], site_of_chain, dev=dev, engine=engine)
+    if exclude_chains is None:
+        exclude = np.concatenate(outl) if outl else np.zeros(0, np.int64)
+    else:
+        ex = np.atleast_1d(np.asarray(exclude_chains, dtype=np.int64))
+        pos = {int(c): i for i, c in enumerate(chain_ids)}
+        if any(int(c) not in pos for c in ex):
+            raise IndexError("exclude_chains: a chain number that is not one of the run's")
+        exclude = np.array([pos[int(c)] for c in ex], dtype=np.int64)
+    S = int(site_of_chain.max()) + 1
+    out = [dict(outliers=chain_ids[outl[s]], scores=scores[s], chain_ids=chain_ids[site_of_chain == s], dep=dep, maxlag=L)
+           for s in range(S)]
+    conv = {k: convergence(chain_series_stats(tables_of[k], L, engine=engine), site_of_chain, exclude)
+            for k in ("likes", "vpvs", "misfits", "noise")}
+    mt = chain_model_stats(tables_of["models"], dep, L, engine=engine)
+    D = dep.size
+    both = convergence(mt, site_of_chain, exclude)
+    for s in range(S):
+        for k in conv:
+            out[s][k] = conv[k][s]
+        out[s]["vs"] = {k: (v if k == "chains" else v[..., :D]) for k, v in both[s].items()}
+        out[s]["nlayers"] = {k: (v if k == "chains" else v[..., D]) for k, v in both[s].items()}
+        for k in GROUPS:
+            out[s][k]["chains"] = chain_ids[out[s][k]["chains"]]
+    return out
+
+
+def stack_chain_files(datapath):
+    """the c???_p2{likes,vpvs,misfits,noise,models}.npy of a folder as [T][C][..] tables, and the chains' file numbers"""
+    from .results import _chainfiles, _chainidx
+    files = _chainfiles(datapath, 2, "likes")
+    if not files:
+        raise IOError("%s: no c???_p2likes.npy" % datapath)
+    ids = np.array([_chainidx(f) for f in files], dtype=np.int64)
+    tabs = {}
+    for k in ("likes", "vpvs", "misfits", "noise", "models"):
+        cols = [np.load(f.replace("likes.npy", k + ".npy")) for f in files]
+        if len(set(len(c) for c in cols)) != 1:
+            raise ValueError("%s: chains of unequal length (%s)" % (datapath, k))
+        a = np.stack(cols, axis=1)
+        if k in ("likes", "vpvs"):
+            a = a.reshape(a.shape[0], a.shape[1])
+        elif a.ndim == 2:
+            a = a[:, :, None]
+        tabs[k] = np.ascontiguousarray(a)
+    return tabs, ids

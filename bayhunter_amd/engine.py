@@ -213,6 +213,13 @@ def load_library():
     L.bh_posterior_scalar_gather.argtypes = [vp, C.c_int, C.c_int64, vp, vp]
     for name in POSTERIOR_DATAFIT_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_chain_diag_series.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int,
+                                       vp, vp, vp, vp, vp, vp, vp]
+    L.bh_chain_diag_models.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
+                                       C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.bh_chain_diag_medians.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, vp, vp, vp]
+    for name in CHAIN_DIAG_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
@@ -273,6 +280,14 @@ POSTERIOR_DATAFIT_SYMBOLS = ("bh_posterior_layers", "bh_posterior_best", "bh_pos
 SCALARS_DATA = 3                    # BH_SCALARS_DATA
 DATAFIT_MAXCOLS = 4096              # BH_DATAFIT_MAXCOLS
 QUANTILES_MAXRANKS = 8              # BH_QUANTILES_MAXRANKS
+# include/bh_engine_chain_diag.h: the sums behind split R-hat and ESS of the chains' recorded series, and the medians of the
+# outlier rule (bayhunter_amd/diagnostics.py)
+CHAIN_DIAG_SYMBOLS = ("bh_chain_diag_series", "bh_chain_diag_models", "bh_chain_diag_medians")
+DIAG_MAXLAG = 2048                  # BH_DIAG_MAXLAG
+DIAG_MAXCOLS = 64                   # BH_DIAG_MAXCOLS
+DIAG_MAXDEPTHS = 63                 # BH_DIAG_MAXDEPTHS
+DIAG_TILE = 256                     # BH_DIAG_TILE
+DIAG_LAGBLOCK = 1024                # BH_DIAG_LAGBLOCK
 
 
 def _f64(a):

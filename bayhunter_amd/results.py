@@ -188,6 +188,22 @@ def posterior_from_storage(datapaths, dep_int=None, engine=None):
     return posterior_models(rows, site=site, dep_int=dep_int, misfits=mis, engine=engine, nsites=len(datapaths))
 
 
+def diagnostics_from_storage(datapaths, dep=None, maxlag=None, dev=0.05, exclude_chains=None, engine=None):
+    """Outlier chains, split R-hat and effective sample sizes of many sites from saved folders (bayhunter_amd.diagnostics, what
+    DeviceChains.diagnostics gives from the device store): datapaths[s] is site s's data directory; its main-phase chain files
+    c???_p2{likes,vpvs,misfits,noise,models}.npy -- per chain and time-ordered -- are stacked to [T][C][..] tables and go through
+    the same calls.  `outliers` and `exclude_chains` (None: the outliers; else one sequence for all sites) are file numbers.
+    ValueError: chains of unequal length.  Returns one dict per site."""
+    from .diagnostics import diagnose, stack_chain_files
+    out = []
+    for p in datapaths:
+        tabs, ids = stack_chain_files(p)
+        ex = None if exclude_chains is None else [c for c in np.atleast_1d(exclude_chains) if c in ids]
+        out.append(diagnose(tabs, np.zeros(ids.size, np.int64), ids, dev=dev, dep=dep, maxlag=maxlag, exclude_chains=ex,
+                            engine=engine)[0])
+    return out
+
+
 class _PriorsUnpickler(pickle.Unpickler):
     """Reads <station>_config.pkl where the reference is not installed: a class that cannot be imported (the reference's
     targets) becomes an empty stand-in -- only the plain dicts of the file are used."""
