@@ -16,9 +16,14 @@
 //              conflict).  Rows at and beyond T are zeros in LDS: their products add +-0 to a sum that is never -0, so the bits
 //              are those of the sum over i < T-k.
 // medians    : one workgroup per chain, a radix selection (8 bits per pass, 256 LDS counters) on the ordered bit patterns.
+// gathered   : the same kernel bodies for series that read another chain at every row (include/bh_engine_chain_diag_ladders.h):
+//              series k reads chain sel[t][k], one int load per value; the index is clamped before it addresses anything and a
+//              clamped one is flagged by the first pass.  Strands, tree and ring are the bodies' own, so the bits are those of the
+//              table gathered on the host.  The builds without a selection are the bodies with the chain fixed: as before.
 // -ffp-contract=off (Makefile): no product is contracted into a sum; that is part of the contract of the header.
 #include "bh_device.h"
 #include "../../include/bh_engine_chain_diag.h"
+#include "../../include/bh_engine_chain_diag_ladders.h"
 
 #include <cmath>
 #include <cstdint>
@@ -42,11 +47,28 @@ struct DiagArgs {
     const double *dep;   // device [D] (models)
 };
 
-// the value (t, c, q) of a table of series ...
-template <typename T, bool MODELS, bool CHECK>
-__device__ __forceinline__ double value(const DiagArgs &a, int c, int64_t t, int q, int &bad)
+// ... and of gathered series: series k reads chain sel[t*ld_sel + k] of the C chains at row t
+struct DiagSelArgs : DiagArgs {
+    const int32_t *sel;
+    int64_t ld_sel;
+    int C;
+};
+
+// the chain that series c reads at row t: c itself, or the selected one -- clamped into [0, C) before it is an address, flagged
+template <bool CHECK> __device__ __forceinline__ int chain_at(const DiagArgs &, int c, int64_t, int &) { return c; }
+template <bool CHECK> __device__ __forceinline__ int chain_at(const DiagSelArgs &a, int k, int64_t t, int &bad)
 {
-    const T *row = (const T *)a.x + t * a.ld_t + (int64_t)c * a.ld_c;
+    const int c = a.sel[t * a.ld_sel + k];
+    const int cc = min(max(c, 0), a.C - 1);
+    if (CHECK && cc != c) bad |= 4;
+    return cc;
+}
+
+// the value (t, c, q) of a table of series ...
+template <typename T, bool MODELS, bool CHECK, typename Args>
+__device__ __forceinline__ double value(const Args &a, int c, int64_t t, int q, int &bad)
+{
+    const T *row = (const T *)a.x + t * a.ld_t + (int64_t)chain_at<CHECK>(a, c, t, bad) * a.ld_c;
     if (!MODELS) {
         const double v = (double)row[q];
         if (CHECK && !(fabs(v) <= DIAG_BIG)) bad |= 1;
@@ -91,8 +113,8 @@ __device__ __forceinline__ double strand_tree(const double (*p)[BH_DIAG_MAXCOLS]
 }
 
 // MODE 0: out[c][q][4] = x0, S1, S1a, S1b;  MODE 1: out[c][q][2] = M2a, M2b with means[c][q][3] = m, ma, mb
-template <typename T, bool MODELS, int MODE>
-__global__ void __launch_bounds__(256) diag_sum_kernel(DiagArgs a, const double *means, double *out, int *flag)
+template <typename T, bool MODELS, int MODE, typename Args>
+__device__ __forceinline__ void diag_sum_body(const Args a, const double *means, double *out, int *flag)
 {
     __shared__ double part[3][BH_DIAG_STRANDS][BH_DIAG_MAXCOLS];
     const int c = blockIdx.x, Q = a.Q;
@@ -140,9 +162,21 @@ __global__ void __launch_bounds__(256) diag_sum_kernel(DiagArgs a, const double 
     if (MODE == 0 && bad) atomicOr(flag, bad);
 }
 
+template <typename T, bool MODELS, int MODE>
+__global__ void __launch_bounds__(256) diag_sum_kernel(DiagArgs a, const double *means, double *out, int *flag)
+{
+    diag_sum_body<T, MODELS, MODE>(a, means, out, flag);
+}
+
+template <typename T, bool MODELS, int MODE>
+__global__ void __launch_bounds__(256) diag_sum_sel_kernel(DiagSelArgs a, const double *means, double *out, int *flag)
+{
+    diag_sum_body<T, MODELS, MODE>(a, means, out, flag);
+}
+
 // P[c][q][k], k = kb .. min(kb + BH_DIAG_LAGBLOCK - 1, L), kb = blockIdx.z * BH_DIAG_LAGBLOCK
-template <typename T, bool MODELS>
-__global__ void __launch_bounds__(256) diag_lag_kernel(DiagArgs a, const double *means, double *P)
+template <typename T, bool MODELS, typename Args>
+__device__ __forceinline__ void diag_lag_body(const Args a, const double *means, double *P)
 {
     __shared__ double ea[BH_DIAG_TILE];
     __shared__ double ring[DIAG_RING];
@@ -185,6 +219,18 @@ __global__ void __launch_bounds__(256) diag_lag_kernel(DiagArgs a, const double 
     }
 }
 
+template <typename T, bool MODELS>
+__global__ void __launch_bounds__(256) diag_lag_kernel(DiagArgs a, const double *means, double *P)
+{
+    diag_lag_body<T, MODELS>(a, means, P);
+}
+
+template <typename T, bool MODELS>
+__global__ void __launch_bounds__(256) diag_lag_sel_kernel(DiagSelArgs a, const double *means, double *P)
+{
+    diag_lag_body<T, MODELS>(a, means, P);
+}
+
 template <typename T> struct KeyOf;
 template <> struct KeyOf<float> {
     typedef unsigned K;
@@ -209,8 +255,8 @@ template <> struct KeyOf<double> {
 };
 
 // out[c][2]: the values of ranks (T-1)/2 and T/2 of chain c's column
-template <typename T>
-__global__ void __launch_bounds__(256) diag_median_kernel(DiagArgs a, double *out, int *flag)
+template <typename T, typename Args>
+__device__ __forceinline__ void diag_median_body(const Args a, double *out, int *flag)
 {
     typedef typename KeyOf<T>::K K;
     __shared__ unsigned hist[256];
@@ -218,7 +264,7 @@ __global__ void __launch_bounds__(256) diag_median_kernel(DiagArgs a, double *ou
     __shared__ unsigned long long s_rank;
     const int c = blockIdx.x, tid = threadIdx.x;
     const int64_t Tn = a.T;
-    const T *col = (const T *)a.x + (int64_t)c * a.ld_c;
+    const T *x = (const T *)a.x;
     int bad = 0;
     for (int r = 0; r < 2; ++r) {
         if (tid == 0) {
@@ -232,7 +278,7 @@ __global__ void __launch_bounds__(256) diag_median_kernel(DiagArgs a, double *ou
             const K prefix = s_prefix;
             const K himask = pass == (int)sizeof(T) - 1 ? (K)0 : (K)(~(K)0 << (shift + 8));
             for (int64_t i = tid; i < Tn; i += 256) {
-                const T v = col[i * a.ld_t];
+                const T v = x[i * a.ld_t + (int64_t)chain_at<true>(a, c, i, bad) * a.ld_c];
                 if (r == 0 && pass == (int)sizeof(T) - 1 && !(fabs((double)v) <= 1.7976931348623157e308)) bad |= 1;
                 const K k = KeyOf<T>::key(v);
                 if ((k & himask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
@@ -254,6 +300,18 @@ __global__ void __launch_bounds__(256) diag_median_kernel(DiagArgs a, double *ou
         __syncthreads();
     }
     if (bad) atomicOr(flag, bad);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) diag_median_kernel(DiagArgs a, double *out, int *flag)
+{
+    diag_median_body<T>(a, out, flag);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) diag_median_sel_kernel(DiagSelArgs a, double *out, int *flag)
+{
+    diag_median_body<T>(a, out, flag);
 }
 
 struct Buf {
@@ -299,8 +357,56 @@ bool layout_ok(int64_t T, int C, int64_t width, int64_t ld_t, int64_t ld_c)
     return span < 1.152921504606846976e18L;
 }
 
-template <typename T, bool MODELS>
-int launch_all(bh_engine *e, hipStream_t st, const DiagArgs &a, int C, double *x0, double *s1, double *s1a, double *s1b, double *m2a,
+// the kernels of a call: without a selection (DiagArgs) and gathered (DiagSelArgs)
+template <typename T, bool MODELS, int MODE>
+void launch_sum(hipStream_t st, unsigned n, const DiagArgs &a, const double *means, double *out, int *flag)
+{
+    diag_sum_kernel<T, MODELS, MODE><<<dim3(n), 256, 0, st>>>(a, means, out, flag);
+}
+template <typename T, bool MODELS, int MODE>
+void launch_sum(hipStream_t st, unsigned n, const DiagSelArgs &a, const double *means, double *out, int *flag)
+{
+    diag_sum_sel_kernel<T, MODELS, MODE><<<dim3(n), 256, 0, st>>>(a, means, out, flag);
+}
+template <typename T, bool MODELS> void launch_lag(hipStream_t st, dim3 grid, const DiagArgs &a, const double *means, double *P)
+{
+    diag_lag_kernel<T, MODELS><<<grid, 256, 0, st>>>(a, means, P);
+}
+template <typename T, bool MODELS> void launch_lag(hipStream_t st, dim3 grid, const DiagSelArgs &a, const double *means, double *P)
+{
+    diag_lag_sel_kernel<T, MODELS><<<grid, 256, 0, st>>>(a, means, P);
+}
+template <typename T> void launch_median(hipStream_t st, unsigned n, const DiagArgs &a, double *out, int *flag)
+{
+    diag_median_kernel<T><<<dim3(n), 256, 0, st>>>(a, out, flag);
+}
+template <typename T> void launch_median(hipStream_t st, unsigned n, const DiagSelArgs &a, double *out, int *flag)
+{
+    diag_median_sel_kernel<T><<<dim3(n), 256, 0, st>>>(a, out, flag);
+}
+
+// the selection on the device: the caller's pointer, or a copy of the span a host table covers
+int sel_on_device(bh_engine *e, hipStream_t st, bool host, int64_t T, int K, int64_t ld_sel, const int32_t *sel, Buf &copy,
+                  const int32_t **dsel)
+{
+    *dsel = sel;
+    if (!host) return BH_OK;
+    const size_t span = (size_t)((T - 1) * ld_sel + K) * sizeof(int32_t);
+    int rc;
+    if ((rc = dalloc(e, copy, span))) return rc;
+    DCHK(e, hipMemcpyAsync(copy.p, sel, span, hipMemcpyHostToDevice, st));
+    *dsel = copy.as<int32_t>();
+    return BH_OK;
+}
+
+bool sel_ok(int64_t T, int K, const int32_t *sel, int64_t ld_sel)
+{
+    return K >= 1 && sel && ld_sel >= K && (long double)(T - 1) * (long double)ld_sel + (long double)K < 1.152921504606846976e18L;
+}
+
+// C: the series of the call (the chains, or the gathered series)
+template <typename T, bool MODELS, typename Args>
+int launch_all(bh_engine *e, hipStream_t st, const Args &a, int C, double *x0, double *s1, double *s1a, double *s1b, double *m2a,
                double *m2b, double *p)
 {
     int rc;
@@ -310,13 +416,14 @@ int launch_all(bh_engine *e, hipStream_t st, const DiagArgs &a, int C, double *x
         (rc = dalloc(e, dP, np * 8)) || (rc = dalloc(e, dflag, 8)))
         return rc;
     DCHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
-    diag_sum_kernel<T, MODELS, 0><<<dim3((unsigned)C), 256, 0, st>>>(a, nullptr, dsum.as<double>(), dflag.as<int>());
+    launch_sum<T, MODELS, 0>(st, (unsigned)C, a, nullptr, dsum.as<double>(), dflag.as<int>());
     DCHK(e, hipGetLastError());
     std::vector<double> hs(nser * 4), hm(nser * 3), h2(nser * 2);
     int flag = 0;
     DCHK(e, hipMemcpyAsync(hs.data(), dsum.p, nser * 32, hipMemcpyDeviceToHost, st));
     DCHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
     DCHK(e, hipStreamSynchronize(st));
+    if (flag & 4) return dfail(e, BH_EINVAL, "a selection index is outside [0, C)");
     if (flag & 2) return dfail(e, BH_EINVAL, "a model row's non-NaN values are not a non-empty prefix of even length");
     if (flag & 1) return dfail(e, BH_EINVAL, "a value is not finite (or beyond 2^480)");
     const int64_t h = a.T / 2;
@@ -326,10 +433,10 @@ int launch_all(bh_engine *e, hipStream_t st, const DiagArgs &a, int C, double *x
         hm[3 * i + 2] = h ? hs[4 * i + 3] / (double)h : 0.0;
     }
     DCHK(e, hipMemcpyAsync(dmean.p, hm.data(), nser * 24, hipMemcpyHostToDevice, st));
-    diag_sum_kernel<T, MODELS, 1><<<dim3((unsigned)C), 256, 0, st>>>(a, dmean.as<double>(), dm2.as<double>(), nullptr);
+    launch_sum<T, MODELS, 1>(st, (unsigned)C, a, dmean.as<double>(), dm2.as<double>(), nullptr);
     DCHK(e, hipGetLastError());
     const unsigned nblk = (unsigned)(a.L / BH_DIAG_LAGBLOCK + 1);
-    diag_lag_kernel<T, MODELS><<<dim3((unsigned)C, (unsigned)a.Q, nblk), 256, 0, st>>>(a, dmean.as<double>(), dP.as<double>());
+    launch_lag<T, MODELS>(st, dim3((unsigned)C, (unsigned)a.Q, nblk), a, dmean.as<double>(), dP.as<double>());
     DCHK(e, hipGetLastError());
     DCHK(e, hipMemcpyAsync(h2.data(), dm2.p, nser * 16, hipMemcpyDeviceToHost, st));
     DCHK(e, hipMemcpyAsync(p, dP.p, np * 8, hipMemcpyDeviceToHost, st));
@@ -345,9 +452,21 @@ int launch_all(bh_engine *e, hipStream_t st, const DiagArgs &a, int C, double *x
     return BH_OK;
 }
 
+template <typename Args>
+int launch_typed(bh_engine *e, hipStream_t st, bool models, int elem_bytes, const Args &a, int nser, double *x0, double *s1, double *s1a,
+                 double *s1b, double *m2a, double *m2b, double *p)
+{
+    if (models)
+        return elem_bytes == 4 ? launch_all<float, true>(e, st, a, nser, x0, s1, s1a, s1b, m2a, m2b, p)
+                               : launch_all<double, true>(e, st, a, nser, x0, s1, s1a, s1b, m2a, m2b, p);
+    return elem_bytes == 4 ? launch_all<float, false>(e, st, a, nser, x0, s1, s1a, s1b, m2a, m2b, p)
+                           : launch_all<double, false>(e, st, a, nser, x0, s1, s1a, s1b, m2a, m2b, p);
+}
+
+// gathered: K series that read chain sel[t*ld_sel + k] at row t (include/bh_engine_chain_diag_ladders.h); else sel is not looked at
 int diag_run(bh_engine *e, bool models, int memspace, void *stream, int elem_bytes, int64_t T, int C, int Q, int ML, int D,
              int64_t ld_t, int64_t ld_c, const void *x, const double *dep, int L, double *x0, double *s1, double *s1a, double *s1b,
-             double *m2a, double *m2b, double *p)
+             double *m2a, double *m2b, double *p, bool gathered = false, int K = 0, const int32_t *sel = nullptr, int64_t ld_sel = 0)
 {
     int rc;
     if (!e) return BH_EINVAL;
@@ -366,24 +485,23 @@ int diag_run(bh_engine *e, bool models, int memspace, void *stream, int elem_byt
     }
     const int64_t width = models ? 2 * ML : Q;
     if (!layout_ok(T, C, width, ld_t, ld_c)) return dfail(e, BH_EINVAL, "bad T, C or leading dimensions");
+    if (gathered && !sel_ok(T, K, sel, ld_sel)) return dfail(e, BH_EINVAL, "the selection: K >= 1 series, ld_sel >= K");
     DCHK(e, hipSetDevice(bh_engine_device_internal(e)));
     const bool host = memspace != BH_DEVICE;
     hipStream_t st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
-    Buf copy, ddep;
-    DiagArgs a;
+    Buf copy, ddep, csel;
+    DiagSelArgs a;
+    a.sel = nullptr; a.ld_sel = ld_sel; a.C = C;
     if ((rc = table_on_device(e, st, host, elem_bytes, T, C, width, ld_t, ld_c, x, copy, &a.x))) return rc;
+    if (gathered && (rc = sel_on_device(e, st, host, T, K, ld_sel, sel, csel, &a.sel))) return rc;
     a.T = T; a.ld_t = ld_t; a.ld_c = ld_c; a.Q = Q; a.L = L; a.ML = ML; a.D = D; a.dep = nullptr;
     if (models && D) {
         if ((rc = dalloc(e, ddep, (size_t)D * 8))) return rc;
         DCHK(e, hipMemcpyAsync(ddep.p, dep, (size_t)D * 8, hipMemcpyHostToDevice, st));
         a.dep = ddep.as<double>();
     }
-    if (models)
-        rc = elem_bytes == 4 ? launch_all<float, true>(e, st, a, C, x0, s1, s1a, s1b, m2a, m2b, p)
-                             : launch_all<double, true>(e, st, a, C, x0, s1, s1a, s1b, m2a, m2b, p);
-    else
-        rc = elem_bytes == 4 ? launch_all<float, false>(e, st, a, C, x0, s1, s1a, s1b, m2a, m2b, p)
-                             : launch_all<double, false>(e, st, a, C, x0, s1, s1a, s1b, m2a, m2b, p);
+    rc = gathered ? launch_typed(e, st, models, elem_bytes, a, K, x0, s1, s1a, s1b, m2a, m2b, p)
+                  : launch_typed(e, st, models, elem_bytes, (const DiagArgs &)a, C, x0, s1, s1a, s1b, m2a, m2b, p);
     if (rc != BH_OK) (void)hipStreamSynchronize(st);   // (the buffers go with this frame)
     return rc;
 }
@@ -406,37 +524,83 @@ int bh_chain_diag_models(bh_engine *e, int memspace, void *stream, int elem_byte
     return diag_run(e, true, memspace, stream, elem_bytes, T, C, 0, ML, D, ld_t, ld_c, models, dep, L, x0, s1, s1a, s1b, m2a, m2b, p);
 }
 
-int bh_chain_diag_medians(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t T, int C, int64_t ld_t, int64_t ld_c,
-                          const void *x, double *lo, double *hi)
+} // extern "C"
+
+namespace {
+
+int median_run(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t T, int C, int64_t ld_t, int64_t ld_c, const void *x,
+               double *lo, double *hi, bool gathered, int K, const int32_t *sel, int64_t ld_sel)
 {
     int rc;
     if (!e) return BH_EINVAL;
     if (elem_bytes != 4 && elem_bytes != 8) return dfail(e, BH_EINVAL, "the table must be float32 or float64");
     if (!x || !lo || !hi) return dfail(e, BH_EINVAL, "null argument");
     if (!layout_ok(T, C, 1, ld_t, ld_c) || T >= ((int64_t)1 << 32)) return dfail(e, BH_EINVAL, "bad T, C or leading dimensions");
+    if (gathered && !sel_ok(T, K, sel, ld_sel)) return dfail(e, BH_EINVAL, "the selection: K >= 1 series, ld_sel >= K");
     DCHK(e, hipSetDevice(bh_engine_device_internal(e)));
     const bool host = memspace != BH_DEVICE;
     hipStream_t st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
-    Buf copy, dout, dflag;
-    DiagArgs a;
+    Buf copy, dout, dflag, csel;
+    DiagSelArgs a;
+    a.sel = nullptr; a.ld_sel = ld_sel; a.C = C;
     if ((rc = table_on_device(e, st, host, elem_bytes, T, C, 1, ld_t, ld_c, x, copy, &a.x))) return rc;
+    if (gathered && (rc = sel_on_device(e, st, host, T, K, ld_sel, sel, csel, &a.sel))) return rc;
     a.T = T; a.ld_t = ld_t; a.ld_c = ld_c; a.Q = 1; a.L = 0; a.ML = 0; a.D = 0; a.dep = nullptr;
-    if ((rc = dalloc(e, dout, (size_t)C * 16)) || (rc = dalloc(e, dflag, 8))) return rc;
+    const int nser = gathered ? K : C;
+    if ((rc = dalloc(e, dout, (size_t)nser * 16)) || (rc = dalloc(e, dflag, 8))) return rc;
     DCHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
-    if (elem_bytes == 4) diag_median_kernel<float><<<dim3((unsigned)C), 256, 0, st>>>(a, dout.as<double>(), dflag.as<int>());
-    else diag_median_kernel<double><<<dim3((unsigned)C), 256, 0, st>>>(a, dout.as<double>(), dflag.as<int>());
+    if (gathered) {
+        if (elem_bytes == 4) launch_median<float>(st, (unsigned)nser, a, dout.as<double>(), dflag.as<int>());
+        else launch_median<double>(st, (unsigned)nser, a, dout.as<double>(), dflag.as<int>());
+    } else {
+        if (elem_bytes == 4) launch_median<float>(st, (unsigned)nser, (const DiagArgs &)a, dout.as<double>(), dflag.as<int>());
+        else launch_median<double>(st, (unsigned)nser, (const DiagArgs &)a, dout.as<double>(), dflag.as<int>());
+    }
     DCHK(e, hipGetLastError());
-    std::vector<double> ho((size_t)C * 2);
+    std::vector<double> ho((size_t)nser * 2);
     int flag = 0;
-    DCHK(e, hipMemcpyAsync(ho.data(), dout.p, (size_t)C * 16, hipMemcpyDeviceToHost, st));
+    DCHK(e, hipMemcpyAsync(ho.data(), dout.p, (size_t)nser * 16, hipMemcpyDeviceToHost, st));
     DCHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
     DCHK(e, hipStreamSynchronize(st));
+    if (flag & 4) return dfail(e, BH_EINVAL, "a selection index is outside [0, C)");
     if (flag) return dfail(e, BH_EINVAL, "a value is not finite");
-    for (int c = 0; c < C; ++c) {
+    for (int c = 0; c < nser; ++c) {
         lo[c] = ho[2 * (size_t)c];
         hi[c] = ho[2 * (size_t)c + 1];
     }
     return BH_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int bh_chain_diag_medians(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t T, int C, int64_t ld_t, int64_t ld_c,
+                          const void *x, double *lo, double *hi)
+{
+    return median_run(e, memspace, stream, elem_bytes, T, C, ld_t, ld_c, x, lo, hi, false, 0, nullptr, 0);
+}
+
+int bh_chain_diag_series_sel(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t T, int C, int Q, int64_t ld_t,
+                             int64_t ld_c, const void *x, int K, const int32_t *sel, int64_t ld_sel, int L, double *x0, double *s1,
+                             double *s1a, double *s1b, double *m2a, double *m2b, double *p)
+{
+    return diag_run(e, false, memspace, stream, elem_bytes, T, C, Q, 0, 0, ld_t, ld_c, x, nullptr, L, x0, s1, s1a, s1b, m2a, m2b, p,
+                    true, K, sel, ld_sel);
+}
+
+int bh_chain_diag_models_sel(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t T, int C, int ML, int64_t ld_t,
+                             int64_t ld_c, const void *models, int K, const int32_t *sel, int64_t ld_sel, int D, const double *dep,
+                             int L, double *x0, double *s1, double *s1a, double *s1b, double *m2a, double *m2b, double *p)
+{
+    return diag_run(e, true, memspace, stream, elem_bytes, T, C, 0, ML, D, ld_t, ld_c, models, dep, L, x0, s1, s1a, s1b, m2a, m2b, p,
+                    true, K, sel, ld_sel);
+}
+
+int bh_chain_diag_medians_sel(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t T, int C, int64_t ld_t,
+                              int64_t ld_c, const void *x, int K, const int32_t *sel, int64_t ld_sel, double *lo, double *hi)
+{
+    return median_run(e, memspace, stream, elem_bytes, T, C, ld_t, ld_c, x, lo, hi, true, K, sel, ld_sel);
 }
 
 } // extern "C"

@@ -754,6 +754,54 @@ class DeviceChains(object):
                          engine=self.engine)
         return r if self.sites is not None else r[0]
 
+    def ladder_diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_ladders=None):
+        """record="device", tempered runs: bayhunter_amd.diagnostics of every site's LADDERS, straight from the device store.  The
+        posterior series of a ladder is its cold series -- at every recorded row the state of the chain that holds the ladder's
+        largest beta (the first of them: what samples(cold_only=True) and save() pick); diagnostics.ladder_index finds that chain
+        on the GPU from the recorded betas and the sums read it where the rows lie, with the bits of diagnostics.diagnose on
+        samples(phase, cold_only=True).  One dict per site (one dict without SiteTargets), shaped as diagnostics() returns it with
+        ladders where chains were: `outliers` -- the ids of the ladders the reference's rule rejects on the cold series' median
+        likelihood --, `outlier_chains` -- the global chain numbers of all members of those ladders, ready to pass as
+        exclude_chains= to the posterior_* methods --, `scores`, `chain_ids` (the site's ladder ids), and the convergence dicts of
+        likes, vpvs, misfits, noise, nlayers and vs, whose `chains` are ladder ids; and `ladders` = dict of ids, members (global
+        chain numbers per ladder), moves (changes of the cold holder per ladder), and per chain of the site, in chain order:
+        chains (their global numbers), round_trips (cold -> hot -> cold excursions seen at the recorded rows), occupancy [.][R]
+        (rows spent on every rung) and cold_share = occupancy[:, 0] / T.
+        exclude_ladders None: R-hat and ESS over the ladders that are no outliers; a sequence of ladder ids overrides that.
+        EngineError: record="host", an untempered run (use diagnostics()), a sharded job of more than one rank (ladders are not
+        followed across ranks)."""
+        if self._rec is None:
+            raise EngineError("ladder_diagnostics() needs DeviceChains(record='device'): record='host' keeps no time-ordered store of "
+                              "the chains on the GPU (results.diagnostics_from_storage reads saved folders)")
+        if self.t["beta"] is None or self.ladder is None:
+            raise EngineError("ladder_diagnostics() of an untempered run: there are no ladders -- every chain's own series is a "
+                              "posterior series, use diagnostics()")
+        if self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1:
+            raise EngineError("ladder_diagnostics() does not follow ladders across ranks (world size %d): use "
+                              "samples(cold_only=True) or the saved folders" % self.dist.get_world_size())
+        from .diagnostics import diagnose, ladder_index
+        d = self.samples_dev(phase)
+        T = int(d["likes"].shape[0])
+        if not T:
+            raise EngineError("ladder_diagnostics(): no snapshot of phase %r yet" % (phase,))
+        with self.torch.cuda.device(self.dev):
+            idx = ladder_index(d["beta"], self.ladder, engine=self.engine)
+            ids = np.asarray(idx["ids"], dtype=np.int64)
+            site_of_ladder = np.array([m[0] // self.C_site for m in idx["members"]], dtype=np.int64)
+            r = diagnose(d, site_of_ladder, ids, dev=dev, dep=dep, maxlag=maxlag, exclude_chains=exclude_ladders, engine=self.engine,
+                         sel=idx["sel"])
+        pos = {int(l): k for k, l in enumerate(ids)}
+        for s, rs in enumerate(r):
+            ks = np.flatnonzero(site_of_ladder == s)
+            members = [self.chain_offset + idx["members"][k].astype(np.int64) for k in ks]
+            local = np.sort(np.concatenate([idx["members"][k] for k in ks]))      # the site's chains, in chain order
+            occ = idx["occupancy"][local]
+            rs["outlier_chains"] = (np.concatenate([self.chain_offset + idx["members"][pos[int(l)]].astype(np.int64) for l in rs["outliers"]])
+                                    if len(rs["outliers"]) else np.zeros(0, np.int64))
+            rs["ladders"] = dict(ids=ids[ks], members=members, moves=idx["moves"][ks], chains=self.chain_offset + local.astype(np.int64),
+                                 round_trips=idx["round_trips"][local], occupancy=occ, cold_share=occ[:, 0] / float(T))
+        return r if self.sites is not None else r[0]
+
     def _host_rows(self, phase):
         """the rows of samples() from the host snapshots of run()"""
         S = self.snap[phase]

@@ -38,7 +38,21 @@ convergence -- pure numpy on those tables.  For a site with the kept chains c = 
 outlier_chains -- the reference's rule (Plotting.get_outliers, results.get_outliers) per site: the chains whose median likelihood
     deviates from the site's best chain's by more than `dev`.
 
-Not here: rank-normalised and folded R-hat, the ladders of tempered runs, chains spread over ranks.
+Tempered runs (include/bh_engine_chain_diag_ladders.h): no chain's recorded series is a posterior series -- a ladder's cold state moves
+between its chains.  The posterior series of ladder k is its cold series: at row t the state of chain sel[t][k], the first chain of
+the ladder that holds its largest beta (parallel.cold_samples' pick).  ladder_index forms sel on the GPU from the recorded betas,
+with the numbers that say whether the ladder mixes; chain_series_stats, chain_model_stats, chain_medians and diagnose take sel= and
+then describe K series, one per ladder, that read chain sel[t][k] at row t from the tables where they lie.  Every output has the bits
+of the same call on the table gathered on the host, np.take_along_axis(x, sel, 1).  ladder_index, all in integers, with M(c) the
+chains of c's ladder:
+    rung[t][c]      = #{c' in M(c) : beta[t][c'] > beta[t][c]}       (0 is cold; ties share a rung)
+    sel[t][k]       = min{c in ladder k : rung[t][c] == 0}
+    hot             : no chain of M(c) has a smaller beta and rung[t][c] > 0
+    occupancy[c][r] = #{t : rung[t][c] == r}
+    round_trips[c]  = the cold -> hot -> cold excursions seen at the recorded rows
+    moves[k]        = #{t >= 1 : sel[t][k] != sel[t-1][k]}
+
+Not here: rank-normalised and folded R-hat, ladders spread over ranks, chains spread over ranks.
 """
 import ctypes as C
 
@@ -100,14 +114,98 @@ def _lds(shape, strides, width):
     return int(ld_t), int(ld_c)
 
 
-def chain_series_stats(values, maxlag, engine=None):
+def _sel_table(sel, T, Cn, mem):
+    """(pointer, K, ld_sel, keep-alive) of a selection sel[t][k]: int32, numpy for a numpy table and a device tensor for a device one,
+    read where it lies when its rows are contiguous"""
+    if mem == E.DEVICE:
+        import torch
+        if not _is_tensor(sel) or not sel.is_cuda:
+            raise ValueError("sel of a device table is a device tensor")
+        if sel.dim() != 2 or sel.shape[0] != T or sel.shape[1] < 1:
+            raise ValueError("sel: [T][K], K >= 1")
+        if sel.dtype != torch.int32:
+            sel = sel.to(torch.int32)
+        if (sel.shape[1] > 1 and sel.stride(1) != 1) or (T > 1 and sel.stride(0) < sel.shape[1]):
+            sel = sel.contiguous()
+        K = int(sel.shape[1])
+        return C.c_void_p(sel.data_ptr()), K, (int(sel.stride(0)) if T > 1 else K), sel
+    if _is_tensor(sel):
+        raise ValueError("sel of a numpy table is a numpy array")
+    a = np.asarray(sel)
+    if a.ndim != 2 or a.shape[0] != T or a.shape[1] < 1 or a.dtype.kind not in "iu":
+        raise ValueError("sel: [T][K] integers, K >= 1")
+    if a.dtype != np.int32:
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError("sel: an index beyond int32")
+        a = a.astype(np.int32)
+    K = int(a.shape[1])
+    if (K > 1 and a.strides[1] != 4) or (T > 1 and (a.strides[0] % 4 or a.strides[0] < 4 * K)):
+        a = np.ascontiguousarray(a)
+    return C.c_void_p(a.ctypes.data), K, (a.strides[0] // 4 if T > 1 else K), a
+
+
+def ladder_index(beta, ladder, engine=None):
+    """The cold chain of every ladder at every recorded row, and how the ladders mix (module docstring; bh_chain_ladder_index).
+    beta[t][c]: the recorded betas, float64, a numpy array or a device tensor (a strided view of the store is read where it lies);
+    ladder[c]: any integer ladder ids.  Dict of ids [K] (the sorted ladder ids, the order of sel's columns), members (per ladder
+    the positions of its chains), sel int32 [T][K] and rung int32 [T][C] (device tensors for a device beta, numpy otherwise),
+    occupancy int64 [C][R] (R = the largest ladder's size), round_trips int64 [C], moves int64 [K].  EngineError: a ladder of more
+    than 64 chains, a beta that is not finite."""
+    eng = _engine(engine)
+    ladder = np.asarray(ladder).reshape(-1)
+    ids, inv = np.unique(ladder, return_inverse=True)
+    inv = np.ascontiguousarray(inv.reshape(-1), dtype=np.int32)
+    Cn, K = int(inv.size), int(ids.size)
+    members = [np.flatnonzero(inv == k) for k in range(K)]
+    R = max(len(m) for m in members) if K else 0
+    if _is_tensor(beta):
+        import torch
+        if not beta.is_cuda or beta.dtype != torch.float64 or beta.dim() != 2:
+            raise ValueError("beta: a [T][C] float64 array or device tensor")
+        T = int(beta.shape[0])
+        if (beta.shape[1] > 1 and beta.stride(1) != 1) or (T > 1 and beta.stride(0) < beta.shape[1]):
+            beta = beta.contiguous()
+        ptr, mem, ld_t = C.c_void_p(beta.data_ptr()), E.DEVICE, (int(beta.stride(0)) if T > 1 else max(1, int(beta.shape[1])))
+        stream = C.c_void_p(torch.cuda.current_stream(beta.device).cuda_stream)
+        shape = tuple(beta.shape)
+    else:
+        beta = np.asarray(beta)
+        if beta.dtype != np.float64 or beta.ndim != 2:
+            raise ValueError("beta: a [T][C] float64 array or device tensor")
+        T = int(beta.shape[0])
+        if (beta.shape[1] > 1 and beta.strides[1] != 8) or (T > 1 and (beta.strides[0] % 8 or beta.strides[0] < 8 * beta.shape[1])):
+            beta = np.ascontiguousarray(beta)
+        ptr, mem, stream, ld_t = C.c_void_p(beta.ctypes.data), E.HOST, None, (beta.strides[0] // 8 if T > 1 else max(1, beta.shape[1]))
+        shape = beta.shape
+    if T < 1 or Cn < 1 or shape[1] != Cn:
+        raise ValueError("beta [T][C] and ladder [C]: T >= 1, one ladder id per chain")
+    if mem == E.DEVICE:
+        sel = torch.full((T, K), -1, dtype=torch.int32, device=beta.device)
+        rung = torch.full((T, Cn), -1, dtype=torch.int32, device=beta.device)
+        psel, prung = C.c_void_p(sel.data_ptr()), C.c_void_p(rung.data_ptr())
+    else:
+        sel, rung = np.full((T, K), -1, np.int32), np.full((T, Cn), -1, np.int32)
+        psel, prung = E._ptr(sel), E._ptr(rung)
+    occ, trips, moves = np.zeros((Cn, max(R, 1)), np.int64), np.zeros(Cn, np.int64), np.zeros(K, np.int64)
+    eng._check(eng._L.bh_chain_ladder_index(eng._h, mem, stream, T, Cn, ld_t, ptr, E._ptr(inv), K, R, psel, K, prung, Cn,
+                                            E._ptr(occ), E._ptr(trips), E._ptr(moves)))
+    del beta
+    return dict(ids=ids, members=members, sel=sel, rung=rung, occupancy=occ, round_trips=trips, moves=moves)
+
+
+def chain_series_stats(values, maxlag, engine=None, sel=None):
     """The sums of the module docstring for every series of a table values[t][c] or values[t][c][q] (float32 / float64; a numpy
     array or a device torch tensor, strided views such as store["misfits"][lo:hi] included -- read where they lie, no copy):
     dict of x0, s1, s1a, s1b, m2a, m2b [C][Q], p [C][Q][maxlag + 1] (float64), T and maxlag.  At most 64 columns go into one
-    engine call; wider tables take several.  EngineError: a value that is not finite."""
+    engine call; wider tables take several.  EngineError: a value that is not finite.
+    sel[t][k] (int32, numpy for a numpy table, a device tensor for a device one): the tables of K series instead, series (k, q)
+    reading chain sel[t][k] at row t (module docstring) -- the chain axis of every output is the series axis; elements of chains
+    not selected at a row are never read.  EngineError: an index outside [0, C)."""
     eng = _engine(engine)
     ptr, mem, stream, elem, shape, strides, keep = _table(values)
     T, Cn = int(shape[0]), int(shape[1])
+    if sel is not None:
+        return _series_sel(eng, ptr, mem, stream, elem, shape, strides, sel, int(maxlag))
     Q = int(shape[2]) if len(shape) == 3 else 1
     L = int(maxlag)
     if T < 1 or Cn < 1 or Q < 1:
@@ -127,9 +225,32 @@ def chain_series_stats(values, maxlag, engine=None):
     return out
 
 
-def chain_model_stats(models, dep, maxlag, engine=None):
+def _series_sel(eng, ptr, mem, stream, elem, shape, strides, sel, L):
+    """chain_series_stats of the K series of a selection"""
+    T, Cn = int(shape[0]), int(shape[1])
+    Q = int(shape[2]) if len(shape) == 3 else 1
+    if T < 1 or Cn < 1 or Q < 1:
+        raise ValueError("an empty table")
+    psel, K, ld_sel, keep = _sel_table(sel, T, Cn, mem)
+    ld_t, ld_c = _lds(shape, strides, Q)
+    out = _outputs(K, Q, L)
+    for q0 in range(0, Q, E.DIAG_MAXCOLS):
+        nq = min(E.DIAG_MAXCOLS, Q - q0)
+        part = out if nq == Q else _outputs(K, nq, L)
+        eng._check(eng._L.bh_chain_diag_series_sel(eng._h, mem, stream, elem, T, Cn, nq, ld_t, ld_c, C.c_void_p(ptr.value + q0 * elem),
+                                                   K, psel, ld_sel, L, *[E._ptr(part[k]) for k in FIELDS + ("p",)]))
+        if part is not out:
+            for k in FIELDS + ("p",):
+                out[k][:, q0:q0 + nq] = part[k]
+    out["T"], out["maxlag"] = T, L
+    del keep
+    return out
+
+
+def chain_model_stats(models, dep, maxlag, engine=None, sel=None):
     """The same for the series derived from model rows models[t][c][2*ML] (the reference's row layout): column q < len(dep) the vs
-    at depth dep[q] (the rule of posterior_models), the last column nlayers = n - 1.  The values are formed in the kernel."""
+    at depth dep[q] (the rule of posterior_models), the last column nlayers = n - 1.  The values are formed in the kernel.
+    sel: as in chain_series_stats -- series k reads the row of chain sel[t][k]."""
     eng = _engine(engine)
     ptr, mem, stream, elem, shape, strides, keep = _table(models)
     if len(shape) != 3 or shape[2] % 2:
@@ -140,6 +261,14 @@ def chain_model_stats(models, dep, maxlag, engine=None):
     if T < 1 or Cn < 1:
         raise ValueError("an empty table")
     ld_t, ld_c = _lds(shape, strides, 2 * ML)
+    if sel is not None:
+        psel, K, ld_sel, keep_sel = _sel_table(sel, T, Cn, mem)
+        out = _outputs(K, D + 1, L)
+        eng._check(eng._L.bh_chain_diag_models_sel(eng._h, mem, stream, elem, T, Cn, ML, ld_t, ld_c, ptr, K, psel, ld_sel, D,
+                                                   E._ptr(dep), L, *[E._ptr(out[k]) for k in FIELDS + ("p",)]))
+        out["T"], out["maxlag"] = T, L
+        del keep, keep_sel
+        return out
     out = _outputs(Cn, D + 1, L)
     eng._check(eng._L.bh_chain_diag_models(eng._h, mem, stream, elem, T, Cn, ML, ld_t, ld_c, ptr, D, E._ptr(dep), L,
                                            *[E._ptr(out[k]) for k in FIELDS + ("p",)]))
@@ -148,13 +277,21 @@ def chain_model_stats(models, dep, maxlag, engine=None):
     return out
 
 
-def chain_medians(likes, engine=None):
+def chain_medians(likes, engine=None, sel=None):
     """numpy.median of every chain's column of likes[t][c], in the table's dtype: on the GPU for a device tensor (a radix selection
-    of the two middle values, include/bh_engine_chain_diag.h), numpy.median itself for a numpy array."""
+    of the two middle values, include/bh_engine_chain_diag.h), numpy.median itself for a numpy array.
+    sel[t][k]: the medians of the K gathered columns likes[t][sel[t][k]] instead (module docstring)."""
     if not _is_tensor(likes):
         a = np.asarray(likes)
         if a.ndim != 2:
             raise ValueError("likes: [T][C]")
+        if sel is not None:
+            s = np.asarray(sel)
+            if s.ndim != 2 or s.shape[0] != a.shape[0] or s.dtype.kind not in "iu":
+                raise ValueError("sel: [T][K] integers")
+            if s.size and (s.min() < 0 or s.max() >= a.shape[1]):
+                raise IndexError("sel: an index outside [0, C)")
+            a = np.take_along_axis(a, s.astype(np.int64), 1)
         return np.array([np.median(a[:, c]) for c in range(a.shape[1])], dtype=a.dtype)
     eng = _engine(engine)
     ptr, mem, stream, elem, shape, strides, keep = _table(likes)
@@ -162,9 +299,16 @@ def chain_medians(likes, engine=None):
         raise ValueError("likes: [T][C]")
     T, Cn = int(shape[0]), int(shape[1])
     ld_t, ld_c = _lds(shape, strides, 1)
+    dtype = np.float32 if elem == 4 else np.float64
+    if sel is not None:
+        psel, K, ld_sel, keep_sel = _sel_table(sel, T, Cn, mem)
+        lo, hi = np.zeros(K), np.zeros(K)
+        eng._check(eng._L.bh_chain_diag_medians_sel(eng._h, mem, stream, elem, T, Cn, ld_t, ld_c, ptr, K, psel, ld_sel, E._ptr(lo),
+                                                    E._ptr(hi)))
+        del keep, keep_sel
+        return np.array([median_of_middles(lo[k], hi[k], T, dtype) for k in range(K)], dtype=dtype)
     lo, hi = np.zeros(Cn), np.zeros(Cn)
     eng._check(eng._L.bh_chain_diag_medians(eng._h, mem, stream, elem, T, Cn, ld_t, ld_c, ptr, E._ptr(lo), E._ptr(hi)))
-    dtype = np.float32 if elem == 4 else np.float64
     del keep
     return np.array([median_of_middles(lo[c], hi[c], T, dtype) for c in range(Cn)], dtype=dtype)
 
@@ -182,11 +326,12 @@ def outlier_scores(medians):
     return 1 - scores
 
 
-def outlier_chains(likes, site_of_chain, dev=0.05, engine=None):
+def outlier_chains(likes, site_of_chain, dev=0.05, engine=None, sel=None):
     """The reference's outlier rule per site.  likes[t][c]: the chains' likelihood series (numpy or device tensor);
     site_of_chain[c]: the chain's site.  Returns (outliers, scores): per site the positions c of its outlier chains (1 - score >
-    dev, strictly) and their 1 - score -- what results.get_outliers returns for the site's folder, with file numbers for c."""
-    med = chain_medians(likes, engine=engine)
+    dev, strictly) and their 1 - score -- what results.get_outliers returns for the site's folder, with file numbers for c.
+    sel: the rule on the K gathered series of chain_medians(sel=) instead; site_of_chain then holds one site per series."""
+    med = chain_medians(likes, engine=engine, sel=sel)
     site_of_chain = np.asarray(site_of_chain, dtype=np.int64)
     if site_of_chain.shape != med.shape:
         raise ValueError("site_of_chain: one site per chain")
@@ -278,17 +423,19 @@ def convergence(tables, site_of_chain, exclude=()):
 GROUPS = ("likes", "vpvs", "misfits", "noise", "nlayers", "vs")
 
 
-def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=None, exclude_chains=None, engine=None):
+def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=None, exclude_chains=None, engine=None, sel=None):
     """Outliers and convergence of every site from the tables of a run: tables_of = dict of likes, vpvs [T][C], misfits [T][C][nt+1],
     noise [T][C][2nt], models [T][C][2*ML] (numpy arrays or device tensors).  chain_ids[c]: the chain's number (what `outliers` and
     exclude_chains hold).  One dict per site: outliers, scores, chain_ids, dep, maxlag, and for every name of GROUPS the dict of
-    convergence().  What DeviceChains.diagnostics and results.diagnostics_from_storage share."""
+    convergence().  What DeviceChains.diagnostics and results.diagnostics_from_storage share.
+    sel[t][k] (ladder_index): the K cold series of a tempered run instead of the chains' own -- site_of_chain and chain_ids then
+    describe the K series (the ladders' sites and ids), and everything downstream sees tables of K series."""
     chain_ids = np.asarray(chain_ids, dtype=np.int64)
     site_of_chain = np.asarray(site_of_chain, dtype=np.int64)
     T = int(tables_of["likes"].shape[0])
     dep = np.linspace(0, 100, 41) if dep is None else np.asarray(dep, dtype=np.float64)
     L = min(T // 2, 1000) if maxlag is None else int(maxlag)
-    outl, scores = outlier_chains(tables_of["likes"], site_of_chain, dev=dev, engine=engine)
+    outl, scores = outlier_chains(tables_of["likes"], site_of_chain, dev=dev, engine=engine, sel=sel)
     if exclude_chains is None:
         exclude = np.concatenate(outl) if outl else np.zeros(0, np.int64)
     else:
@@ -300,9 +447,9 @@ def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=Non
     S = int(site_of_chain.max()) + 1
     out = [dict(outliers=chain_ids[outl[s]], scores=scores[s], chain_ids=chain_ids[site_of_chain == s], dep=dep, maxlag=L)
            for s in range(S)]
-    conv = {k: convergence(chain_series_stats(tables_of[k], L, engine=engine), site_of_chain, exclude)
+    conv = {k: convergence(chain_series_stats(tables_of[k], L, engine=engine, sel=sel), site_of_chain, exclude)
             for k in ("likes", "vpvs", "misfits", "noise")}
-    mt = chain_model_stats(tables_of["models"], dep, L, engine=engine)
+    mt = chain_model_stats(tables_of["models"], dep, L, engine=engine, sel=sel)
     D = dep.size
     both = convergence(mt, site_of_chain, exclude)
     for s in range(S):

@@ -220,6 +220,16 @@ def load_library():
     L.bh_chain_diag_medians.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, vp, vp, vp]
     for name in CHAIN_DIAG_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_chain_ladder_index.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int64, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp,
+                                        C.c_int64, vp, vp, vp]
+    L.bh_chain_diag_series_sel.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp,
+                                           C.c_int, vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.bh_chain_diag_models_sel.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp,
+                                           C.c_int, vp, C.c_int64, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.bh_chain_diag_medians_sel.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
+                                            C.c_int64, vp, vp]
+    for name in CHAIN_LADDER_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
@@ -288,6 +298,10 @@ DIAG_MAXCOLS = 64                   # BH_DIAG_MAXCOLS
 DIAG_MAXDEPTHS = 63                 # BH_DIAG_MAXDEPTHS
 DIAG_TILE = 256                     # BH_DIAG_TILE
 DIAG_LAGBLOCK = 1024                # BH_DIAG_LAGBLOCK
+# include/bh_engine_chain_diag_ladders.h: the cold series of tempered runs -- the chain that holds every ladder's largest beta at every
+# row, the ladders' mixing numbers, and the sums and medians of series that read that chain (bayhunter_amd/diagnostics.py)
+CHAIN_LADDER_SYMBOLS = ("bh_chain_ladder_index", "bh_chain_diag_series_sel", "bh_chain_diag_models_sel", "bh_chain_diag_medians_sel")
+LADDER_MAXRUNGS = 64                # BH_LADDER_MAXRUNGS
 
 
 def _f64(a):
