@@ -22,6 +22,7 @@
 //              table gathered on the host.  The builds without a selection are the bodies with the chain fixed: as before.
 // -ffp-contract=off (Makefile): no product is contracted into a sum; that is part of the contract of the header.
 #include "bh_device.h"
+#include "chain_diag_value.h"
 #include "../../include/bh_engine_chain_diag.h"
 #include "../../include/bh_engine_chain_diag_ladders.h"
 
@@ -75,35 +76,8 @@ __device__ __forceinline__ double value(const Args &a, int c, int64_t t, int q, 
         return v;
     }
     // ... and of a table of model rows [vs_1..vs_n, z_1..z_n, NaN...]: vs[#{j : d_j <= dep[q]}] (the rule of bh_engine_posterior.h,
-    // posterior_kernel.hip), column D: n - 1
-    const int W = 2 * a.ML;
-    int cnt = 0, first = W;
-    for (int i = 0; i < W; ++i) {
-        const T v = row[i];
-        const bool nan = v != v;
-        cnt += nan ? 0 : 1;
-        first = (nan && i < first) ? i : first;
-        if (CHECK && !nan && !(fabs((double)v) <= DIAG_BIG)) bad |= 1;
-    }
-    if (cnt == 0 || cnt != first || (cnt & 1)) {
-        bad |= 2;
-        return 0.0;
-    }
-    const int n = cnt / 2;
-    if (q == a.D) return (double)(n - 1);
-    const double xq = a.dep[q];
-    const T *z = row + n;
-    T zprev = (T)0;
-    double dsum = 0.0;
-    int k = 0;
-    for (int j = 0; j < n - 1; ++j) {
-        const T zd = (z[j] + z[j + 1]) / (T)2;
-        const double h = (double)zd - (double)zprev;
-        dsum = j ? dsum + h : h;
-        k += dsum <= xq ? 1 : 0;
-        zprev = zd;
-    }
-    return (double)row[k];
+    // posterior_kernel.hip), column D: n - 1 -- chain_diag_value.h, shared with the rank transform
+    return diag_model_value<T, CHECK>(row, a.ML, a.D, a.dep, q, DIAG_BIG, bad);
 }
 
 __device__ __forceinline__ double strand_tree(const double (*p)[BH_DIAG_MAXCOLS], int q)

@@ -725,7 +725,7 @@ class DeviceChains(object):
                                       misfits=d["misfits"][..., -1].reshape(n), quantiles=quantiles, mantle=mantle,
                                       engine=self.engine)
 
-    def diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_chains=None):
+    def diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_chains=None, rank=False):
         """record="device": bayhunter_amd.diagnostics of every site's chains, straight from the time-ordered views of the device
         store (one dict per site; one dict without SiteTargets): `outliers` -- the global numbers of the chains the reference's rule
         (results.get_outliers, deviation `dev`) rejects, ready to pass as exclude_chains= to the posterior_* methods --, their
@@ -733,6 +733,8 @@ class DeviceChains(object):
         np.linspace(0, 100, 41)) the dict of diagnostics.convergence: split R-hat, ESS, tau, the flags and the per-chain numbers.
         exclude_chains None: R-hat and ESS over the chains that are no outliers; a sequence of chain numbers overrides that.
         maxlag: the largest lag of the autocorrelation sums, default min(T // 2, 1000).
+        rank=True: every group's dict gains "rank" -- the rank-normalised and the folded split R-hat, the bulk and the tail ESS of
+        diagnostics.rank_convergence, the site's kept chains pooled on the GPU; with the default nothing of it runs.
         EngineError: record="host" (no time-ordered store on the GPU), a tempered run (a ladder's cold state moves between chains:
         no chain's series is a posterior series) and a sharded job of more than one rank (a site's chains lie on several GPUs)."""
         if self._rec is None:
@@ -751,10 +753,10 @@ class DeviceChains(object):
         ids = self.chain_offset + np.arange(self.C, dtype=np.int64)
         with self.torch.cuda.device(self.dev):
             r = diagnose(d, np.arange(self.C) // self.C_site, ids, dev=dev, dep=dep, maxlag=maxlag, exclude_chains=exclude_chains,
-                         engine=self.engine)
+                         engine=self.engine, rank=rank)
         return r if self.sites is not None else r[0]
 
-    def ladder_diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_ladders=None):
+    def ladder_diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_ladders=None, rank=False):
         """record="device", tempered runs: bayhunter_amd.diagnostics of every site's LADDERS, straight from the device store.  The
         posterior series of a ladder is its cold series -- at every recorded row the state of the chain that holds the ladder's
         largest beta (the first of them: what samples(cold_only=True) and save() pick); diagnostics.ladder_index finds that chain
@@ -769,7 +771,9 @@ class DeviceChains(object):
         (rows spent on every rung) and cold_share = occupancy[:, 0] / T.
         exclude_ladders None: R-hat and ESS over the ladders that are no outliers; a sequence of ladder ids overrides that.
         EngineError: record="host", an untempered run (use diagnostics()), a sharded job of more than one rank (ladders are not
-        followed across ranks)."""
+        followed across ranks).  ValueError: rank=True -- the ranks of cold series are not formed."""
+        if rank:
+            raise ValueError("ladder_diagnostics(rank=True): the ranks of the cold series of tempered runs are not formed")
         if self._rec is None:
             raise EngineError("ladder_diagnostics() needs DeviceChains(record='device'): record='host' keeps no time-ordered store of "
                               "the chains on the GPU (results.diagnostics_from_storage reads saved folders)")

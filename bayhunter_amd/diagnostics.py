@@ -52,7 +52,18 @@ chains of c's ladder:
     round_trips[c]  = the cold -> hot -> cold excursions seen at the recorded rows
     moves[k]        = #{t >= 1 : sel[t][k] != sel[t-1][k]}
 
-Not here: rank-normalised and folded R-hat, ladders spread over ranks, chains spread over ranks.
+Rank-normalised numbers (Vehtari et al. 2021; include/bh_engine_chain_rank.h): rank_series / rank_models turn every column of a
+table into three tables on the GPU, with the samples of a site's kept chains pooled per column (N = m T values, -0.0 as +0.0):
+    lt = #{w in pool : w < v},  eq = #{w in pool : w == v},  R2 = 2 lt + eq + 1   (twice the average rank; integers throughout)
+    z    = rank_table(N)[R2]  = normal_quantile((R2/2 - 3/8) / (N + 1/4))         (bulk)
+    zf   = the same of f = |v - numpy.median(pool)|                              (folded: spread instead of location)
+    tail = lt <= (N - 1) // 20,  lt <= 19 (N - 1) // 20                          (x <= q_0.05, x <= q_0.95 of numpy.quantile)
+rank_convergence feeds those tables to chain_series_stats and convergence, unchanged: rhat_bulk = the split R-hat of z, rhat_fold
+of zf, rhat the larger; ess_bulk the ESS of z, ess_tail the smaller of the ESS of the two indicators.  The ESS stays the package's:
+Stan's estimator on the UNSPLIT chains (`posterior` and ArviZ split every chain in two for the ESS as well; here only R-hat does).
+The normal scores are a host table (AS241), looked up on the device: the tables have the host's bits.
+
+Not here: ranks of the cold series of tempered runs (sel=), ladders spread over ranks, chains spread over ranks.
 """
 import ctypes as C
 
@@ -420,16 +431,233 @@ def convergence(tables, site_of_chain, exclude=()):
     return out
 
 
+# ---- rank-normalised diagnostics (module docstring; include/bh_engine_chain_rank.h) ----------------------------------------------
+# Wichura (1988), Algorithm AS241, PPND16: the coefficients of the three rational approximations, highest power first
+_AS241_A = (2.5090809287301226727e+3, 3.3430575583588128105e+4, 6.7265770927008700853e+4, 4.5921953931549871457e+4,
+            1.3731693765509461125e+4, 1.9715909503065514427e+3, 1.3314166789178437745e+2, 3.3871328727963666080e+0)
+_AS241_B = (5.2264952788528545610e+3, 2.8729085735721942674e+4, 3.9307895800092710610e+4, 2.1213794301586595867e+4,
+            5.3941960214247511077e+3, 6.8718700749205790830e+2, 4.2313330701600911252e+1, 1.0)
+_AS241_C = (7.74545014278341407640e-4, 2.27238449892691845833e-2, 2.41780725177450611770e-1, 1.27045825245236838258e+0,
+            3.64784832476320460504e+0, 5.76949722146069140550e+0, 4.63033784615654529590e+0, 1.42343711074968357734e+0)
+_AS241_D = (1.05075007164441684324e-9, 5.47593808499534494600e-4, 1.51986665636164571966e-2, 1.48103976427480074590e-1,
+            6.89767334985100004550e-1, 1.67638483018380384940e+0, 2.05319162663775882187e+0, 1.0)
+_AS241_E = (2.01033439929228813265e-7, 2.71155556874348757815e-5, 1.24266094738807843860e-3, 2.65321895265761230930e-2,
+            2.96560571828504891230e-1, 1.78482653991729133580e+0, 5.46378491116411436990e+0, 6.65790464350110377720e+0)
+_AS241_F = (2.04426310338993978564e-15, 1.42151175831644588870e-7, 1.84631831751005468180e-5, 7.86869131145613259100e-4,
+            1.48753612908506148525e-2, 1.36929880922735805310e-1, 5.99832206555887937690e-1, 1.0)
+
+
+def _horner(coef, r):
+    v = np.full_like(r, coef[0])
+    for c in coef[1:]:
+        v = v * r + c
+    return v
+
+
+def normal_quantile(p):
+    """The quantile function of the standard normal distribution, float64: Wichura's AS241 (PPND16, relative accuracy about 1e-16)
+    vectorised in numpy.  The definition of the normal scores of rank_table.  p outside (0, 1): NaN (0 and 1: -inf, +inf)."""
+    p = np.asarray(p, dtype=np.float64)
+    shape = p.shape
+    p = p.reshape(-1)
+    x = np.full(p.shape, np.nan)
+    with np.errstate(all="ignore"):
+        q = p - 0.5
+        mid = np.abs(q) <= 0.425
+        if mid.any():
+            qm = q[mid]
+            r = 0.180625 - qm * qm
+            x[mid] = _horner(_AS241_A, r) * qm / _horner(_AS241_B, r)
+        out = ~mid & (p > 0.0) & (p < 1.0)
+        if out.any():
+            po, qo = p[out], q[out]
+            r = np.sqrt(-np.log(np.where(qo <= 0.0, po, 1.0 - po)))
+            near = r <= 5.0
+            v = np.empty_like(r)
+            rn, rf = r[near] - 1.6, r[~near] - 5.0
+            v[near] = _horner(_AS241_C, rn) / _horner(_AS241_D, rn)
+            v[~near] = _horner(_AS241_E, rf) / _horner(_AS241_F, rf)
+            x[out] = np.where(qo < 0.0, -v, v)
+        x[p == 0.0] = -np.inf
+        x[p == 1.0] = np.inf
+    return x.reshape(shape)
+
+
+def rank_table(N):
+    """zt_N [2N + 1]: the normal score of twice-the-average-rank R2 in a pool of N, normal_quantile((R2/2 - 3/8) / (N + 1/4)).
+    R2 of an element lies in [2, 2N]; entries 0 and 1 are NaN and never read."""
+    N = int(N)
+    if N < 1:
+        raise ValueError("a pool of at least one value")
+    zt = normal_quantile((np.arange(2 * N + 1, dtype=np.float64) / 2.0 - 0.375) / (N + 0.25))
+    zt[:2] = np.nan
+    return zt
+
+
+def _rank_groups(group_of_chain, Cn, T):
+    """(group int32 [C], G, zt, zoff int64 [G]) of a grouping: one table per distinct pool size, shared by the groups of that size"""
+    group = np.asarray(group_of_chain)
+    if group.shape != (Cn,) or group.dtype.kind not in "iu":
+        raise ValueError("group_of_chain: one integer per chain, -1 for a chain left out")
+    group = np.ascontiguousarray(group, dtype=np.int32)
+    G = int(group.max()) + 1 if Cn else 0
+    if G < 1:
+        raise ValueError("group_of_chain: no chain is kept")
+    m = np.bincount(group[group >= 0], minlength=G)
+    zoff, parts, at, start = np.zeros(G, np.int64), [], {}, 0
+    for g in range(G):
+        N = int(m[g]) * T
+        if N < 1:
+            continue         # (an empty group: the engine refuses it)
+        if N not in at:
+            at[N] = start
+            parts.append(rank_table(N))
+            start += 2 * N + 1
+        zoff[g] = at[N]
+    zt = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(1)
+    return group, G, zt, zoff
+
+
+def _rank_outputs(mem, like, shape, folded, tail):
+    """z, zf, tail of a call: device tensors beside a device table, numpy arrays otherwise; and their pointers"""
+    T, Cn, Q = shape
+    if mem == E.DEVICE:
+        import torch
+        z = torch.empty((T, Cn, Q), dtype=torch.float64, device=like.device)
+        zf = torch.empty((T, Cn, Q), dtype=torch.float64, device=like.device) if folded else None
+        tl = torch.empty((T, Cn, 2 * Q), dtype=torch.float32, device=like.device) if tail else None
+        return z, zf, tl, [None if a is None else a.data_ptr() for a in (z, zf, tl)]
+    z = np.empty((T, Cn, Q))
+    zf = np.empty((T, Cn, Q)) if folded else None
+    tl = np.empty((T, Cn, 2 * Q), np.float32) if tail else None
+    return z, zf, tl, [None if a is None else a.ctypes.data for a in (z, zf, tl)]
+
+
+def rank_series(values, group_of_chain, engine=None, folded=True, tail=True):
+    """The rank transform of every column of a table values[t][c] or values[t][c][q] (float32 / float64, numpy or device tensor,
+    strided views read where they lie), pooled over the chains of a group: group_of_chain[c] in 0..G-1 (every group non-empty) is
+    the chain's pool -- its site; the chains of a pool need not be adjacent --, -1 leaves the chain out.  Returns (z, zf, tail)
+    (module docstring): z, zf float64 shaped as values, tail float32 [T][C][2Q] with (lo, hi) of column q at 2q, 2q + 1; device
+    tensors for a device table, numpy arrays for a numpy one; zf / tail None without folded / tail.  The chains left out hold 0.
+    EngineError: a value of a kept chain that is not finite, an empty group."""
+    eng = _engine(engine)
+    ptr, mem, stream, elem, shape, strides, keep = _table(values)
+    T, Cn = int(shape[0]), int(shape[1])
+    Q = int(shape[2]) if len(shape) == 3 else 1
+    if T < 1 or Cn < 1 or Q < 1:
+        raise ValueError("an empty table")
+    group, G, zt, zoff = _rank_groups(group_of_chain, Cn, T)
+    ld_t, ld_c = _lds(shape, strides, Q)
+    z, zf, tl, ptrs = _rank_outputs(mem, keep, (T, Cn, Q), folded, tail)
+    for q0 in range(0, Q, E.DIAG_MAXCOLS):
+        nq = min(E.DIAG_MAXCOLS, Q - q0)
+        outs = [None if a is None else C.c_void_p(a + q0 * w) for a, w in zip(ptrs, (8, 8, 8))]
+        eng._check(eng._L.bh_chain_rank_series(eng._h, mem, stream, elem, T, Cn, nq, ld_t, ld_c, C.c_void_p(ptr.value + q0 * elem),
+                                               G, E._ptr(group), E._ptr(zt), E._ptr(zoff), outs[0], outs[1], outs[2], Cn * Q, Q))
+    del keep
+    if len(shape) == 2:
+        z, zf = z.reshape(T, Cn), (None if zf is None else zf.reshape(T, Cn))
+    return z, zf, tl
+
+
+def rank_models(models, dep, group_of_chain, engine=None, folded=True, tail=True, columns=None):
+    """rank_series of the series derived from model rows models[t][c][2*ML] (chain_model_stats: column q < len(dep) the vs at depth
+    dep[q], the last column nlayers), the values formed in the kernel.  columns=(q0, nq): those nq of the len(dep) + 1 columns only."""
+    eng = _engine(engine)
+    ptr, mem, stream, elem, shape, strides, keep = _table(models)
+    if len(shape) != 3 or shape[2] % 2:
+        raise ValueError("models: [T][C][2*ML]")
+    T, Cn, ML = int(shape[0]), int(shape[1]), int(shape[2]) // 2
+    dep = np.ascontiguousarray(dep, np.float64).reshape(-1)
+    D = dep.size
+    q0, nq = (0, D + 1) if columns is None else (int(columns[0]), int(columns[1]))
+    if T < 1 or Cn < 1:
+        raise ValueError("an empty table")
+    if q0 < 0 or nq < 1 or q0 + nq > D + 1:
+        raise ValueError("columns: (q0, nq) within the len(dep) + 1 columns")
+    group, G, zt, zoff = _rank_groups(group_of_chain, Cn, T)
+    ld_t, ld_c = _lds(shape, strides, 2 * ML)
+    z, zf, tl, ptrs = _rank_outputs(mem, keep, (T, Cn, nq), folded, tail)
+    outs = [None if a is None else C.c_void_p(a) for a in ptrs]
+    eng._check(eng._L.bh_chain_rank_models(eng._h, mem, stream, elem, T, Cn, ML, ld_t, ld_c, ptr, D, E._ptr(dep), q0, nq, G,
+                                           E._ptr(group), E._ptr(zt), E._ptr(zoff), outs[0], outs[1], outs[2], Cn * nq, nq))
+    del keep
+    return z, zf, tl
+
+
+RANK_FIELDS = ("rhat_bulk", "rhat_fold", "rhat", "ess_bulk", "ess_tail_lo", "ess_tail_hi", "ess_tail", "ess_bulk_truncated",
+               "ess_tail_lo_truncated", "ess_tail_hi_truncated", "constant_bulk", "constant_fold", "constant_tail_lo",
+               "constant_tail_hi")
+
+
+def rank_summary(conv_z, conv_zf, conv_tail):
+    """The dict `rank` of one site from its convergence() dicts of the tables z [Q], zf [Q] and tail [2Q] (pure numpy): chains,
+    rhat_bulk, rhat_fold, rhat = the larger (NaN if either is), ess_bulk, ess_tail_lo, ess_tail_hi, ess_tail = the smaller (NaN
+    if either is), and of each the flags ess_*_truncated and constant_* [Q]."""
+    lo, hi = slice(0, None, 2), slice(1, None, 2)
+    return dict(chains=conv_z["chains"], rhat_bulk=conv_z["rhat"], rhat_fold=conv_zf["rhat"],
+                rhat=np.maximum(conv_z["rhat"], conv_zf["rhat"]), ess_bulk=conv_z["ess"],
+                ess_tail_lo=conv_tail["ess"][lo], ess_tail_hi=conv_tail["ess"][hi],
+                ess_tail=np.minimum(conv_tail["ess"][lo], conv_tail["ess"][hi]),
+                ess_bulk_truncated=conv_z["ess_truncated"], ess_tail_lo_truncated=conv_tail["ess_truncated"][lo],
+                ess_tail_hi_truncated=conv_tail["ess_truncated"][hi], constant_bulk=conv_z["constant"],
+                constant_fold=conv_zf["constant"], constant_tail_lo=conv_tail["constant"][lo],
+                constant_tail_hi=conv_tail["constant"][hi])
+
+
+def rank_convergence(values, site_of_chain, maxlag, exclude=(), dep=None, engine=None, budget_bytes=2 << 30):
+    """The rank-normalised numbers of every site (module docstring) from a table values[t][c] / values[t][c][q], or -- with dep --
+    from model rows (the columns of chain_model_stats): the pools are every site's kept chains (site_of_chain[c], without the
+    positions `exclude`), the rank tables go through chain_series_stats and convergence as they are.  The columns are walked in
+    chunks so that the rank tables alive at once (24 bytes per element and column) stay under budget_bytes.  One dict per site
+    (rank_summary); a site without a kept chain has NaN throughout.  The ESS is on the unsplit chains, as everywhere here."""
+    site_of_chain = np.asarray(site_of_chain, dtype=np.int64)
+    Cn = int(values.shape[1])
+    T = int(values.shape[0])
+    if site_of_chain.shape != (Cn,):
+        raise ValueError("site_of_chain: one site per chain")
+    drop = np.zeros(Cn, bool)
+    drop[np.asarray(exclude, dtype=np.int64).reshape(-1)] = True
+    kept_sites = np.unique(site_of_chain[~drop])
+    group = np.where(drop, -1, np.searchsorted(kept_sites, site_of_chain)).astype(np.int32)
+    if dep is not None:
+        dep = np.ascontiguousarray(dep, np.float64).reshape(-1)
+        Q = dep.size + 1
+    else:
+        Q = int(values.shape[2]) if len(values.shape) == 3 else 1
+    step = int(max(1, min(E.DIAG_MAXCOLS, int(budget_bytes) // max(1, 24 * T * Cn))))
+    L = int(maxlag)
+    parts = []
+    for q0 in range(0, Q, step):
+        nq = min(step, Q - q0)
+        if dep is not None:
+            z, zf, tl = rank_models(values, dep, group, engine=engine, columns=(q0, nq))
+        else:
+            v = values if len(values.shape) == 2 else values[:, :, q0:q0 + nq]
+            z, zf, tl = rank_series(v, group, engine=engine)
+        conv = [convergence(chain_series_stats(t, L, engine=engine), site_of_chain, exclude) for t in (z, zf, tl)]
+        del z, zf, tl
+        parts.append([rank_summary(a, b, c) for a, b, c in zip(*conv)])
+    return [{k: (parts[0][s][k] if k == "chains" else np.concatenate([np.atleast_1d(p[s][k]) for p in parts]))
+             for k in ("chains",) + RANK_FIELDS} for s in range(len(parts[0]))]
+
+
 GROUPS = ("likes", "vpvs", "misfits", "noise", "nlayers", "vs")
 
 
-def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=None, exclude_chains=None, engine=None, sel=None):
+def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=None, exclude_chains=None, engine=None, sel=None,
+             rank=False, rank_budget_bytes=2 << 30):
     """Outliers and convergence of every site from the tables of a run: tables_of = dict of likes, vpvs [T][C], misfits [T][C][nt+1],
     noise [T][C][2nt], models [T][C][2*ML] (numpy arrays or device tensors).  chain_ids[c]: the chain's number (what `outliers` and
     exclude_chains hold).  One dict per site: outliers, scores, chain_ids, dep, maxlag, and for every name of GROUPS the dict of
     convergence().  What DeviceChains.diagnostics and results.diagnostics_from_storage share.
     sel[t][k] (ladder_index): the K cold series of a tempered run instead of the chains' own -- site_of_chain and chain_ids then
-    describe the K series (the ladders' sites and ids), and everything downstream sees tables of K series."""
+    describe the K series (the ladders' sites and ids), and everything downstream sees tables of K series.
+    rank=True: every group's dict gains the key "rank", the dict of rank_convergence -- the kept chains of a site pooled after the
+    outlier rule or exclude_chains has decided who is kept; ValueError with sel (ranks of cold series are not formed).  With the
+    default nothing of it runs."""
+    if rank and sel is not None:
+        raise ValueError("rank=True with sel=: the ranks of the cold series of tempered runs are not formed")
     chain_ids = np.asarray(chain_ids, dtype=np.int64)
     site_of_chain = np.asarray(site_of_chain, dtype=np.int64)
     T = int(tables_of["likes"].shape[0])
@@ -459,6 +687,17 @@ def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=Non
         out[s]["nlayers"] = {k: (v if k == "chains" else v[..., D]) for k, v in both[s].items()}
         for k in GROUPS:
             out[s][k]["chains"] = chain_ids[out[s][k]["chains"]]
+    if rank:
+        rk = {k: rank_convergence(tables_of[k], site_of_chain, L, exclude, engine=engine, budget_bytes=rank_budget_bytes)
+              for k in ("likes", "vpvs", "misfits", "noise")}
+        rboth = rank_convergence(tables_of["models"], site_of_chain, L, exclude, dep=dep, engine=engine, budget_bytes=rank_budget_bytes)
+        for s in range(S):
+            for k in rk:
+                out[s][k]["rank"] = rk[k][s]
+            out[s]["vs"]["rank"] = {k: (v if k == "chains" else v[..., :D]) for k, v in rboth[s].items()}
+            out[s]["nlayers"]["rank"] = {k: (v if k == "chains" else v[..., D]) for k, v in rboth[s].items()}
+            for k in GROUPS:
+                out[s][k]["rank"]["chains"] = chain_ids[out[s][k]["rank"]["chains"]]
     return out
 
 

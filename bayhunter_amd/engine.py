@@ -230,6 +230,12 @@ def load_library():
                                             C.c_int64, vp, vp]
     for name in CHAIN_LADDER_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_chain_rank_series.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
+                                       vp, vp, vp, vp, vp, C.c_int64, C.c_int64]
+    L.bh_chain_rank_models.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
+                                       C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int64]
+    for name in CHAIN_RANK_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
@@ -302,6 +308,11 @@ DIAG_LAGBLOCK = 1024                # BH_DIAG_LAGBLOCK
 # row, the ladders' mixing numbers, and the sums and medians of series that read that chain (bayhunter_amd/diagnostics.py)
 CHAIN_LADDER_SYMBOLS = ("bh_chain_ladder_index", "bh_chain_diag_series_sel", "bh_chain_diag_models_sel", "bh_chain_diag_medians_sel")
 LADDER_MAXRUNGS = 64                # BH_LADDER_MAXRUNGS
+# include/bh_engine_chain_rank.h: the rank transform of the chains' series pooled per site -- normal scores of the average ranks, of
+# the folded ranks, and the tail indicators (bayhunter_amd/diagnostics.py: rank_series, rank_models, rank_convergence)
+CHAIN_RANK_SYMBOLS = ("bh_chain_rank_series", "bh_chain_rank_models")
+RANK_TILE = 4096                    # BH_RANK_TILE
+RANK_RADIXBITS = 8                  # BH_RANK_RADIXBITS
 
 
 def _f64(a):

@@ -188,11 +188,12 @@ def posterior_from_storage(datapaths, dep_int=None, engine=None):
     return posterior_models(rows, site=site, dep_int=dep_int, misfits=mis, engine=engine, nsites=len(datapaths))
 
 
-def diagnostics_from_storage(datapaths, dep=None, maxlag=None, dev=0.05, exclude_chains=None, engine=None):
+def diagnostics_from_storage(datapaths, dep=None, maxlag=None, dev=0.05, exclude_chains=None, engine=None, rank=False):
     """Outlier chains, split R-hat and effective sample sizes of many sites from saved folders (bayhunter_amd.diagnostics, what
     DeviceChains.diagnostics gives from the device store): datapaths[s] is site s's data directory; its main-phase chain files
     c???_p2{likes,vpvs,misfits,noise,models}.npy -- per chain and time-ordered -- are stacked to [T][C][..] tables and go through
     the same calls.  `outliers` and `exclude_chains` (None: the outliers; else one sequence for all sites) are file numbers.
+    rank=True: every group's dict gains "rank", the rank-normalised R-hat and the bulk and tail ESS (diagnostics.rank_convergence).
     ValueError: chains of unequal length.  Returns one dict per site."""
     from .diagnostics import diagnose, stack_chain_files
     out = []
@@ -200,7 +201,7 @@ def diagnostics_from_storage(datapaths, dep=None, maxlag=None, dev=0.05, exclude
         tabs, ids = stack_chain_files(p)
         ex = None if exclude_chains is None else [c for c in np.atleast_1d(exclude_chains) if c in ids]
         out.append(diagnose(tabs, np.zeros(ids.size, np.int64), ids, dev=dev, dep=dep, maxlag=maxlag, exclude_chains=ex,
-                            engine=engine)[0])
+                            engine=engine, rank=rank)[0])
     return out
 
 
