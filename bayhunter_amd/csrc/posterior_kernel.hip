@@ -16,6 +16,7 @@
 //             in LDS when every site has at most 256 vs bins, else straight to global atomics.
 // -ffp-contract=off (Makefile) keeps (z_j + z_{j+1}) / 2 and the cumulative sums rounded as numpy rounds them.
 #include "posterior_common.h"
+#include "../../include/bh_engine_posterior_quantiles.h"
 
 #include <algorithm>
 #include <climits>
@@ -26,6 +27,7 @@
 
 #define POST_HIST_LDS_BINS 256
 #define POST_IFACE_LDS_BINS 4096
+#define POST_MAXR BH_QUANTILES_MAXRANKS
 
 using namespace bhpost;
 
@@ -269,6 +271,144 @@ __global__ void __launch_bounds__(64) post_next_kernel(ColArgs a, int k32, const
     }
     atomicAdd(&nle[c], le);
     atomicMin(&next[c], nx);
+}
+
+// ---- several order statistics per column (include/bh_engine_posterior_quantiles.h) ------------------------------------------
+// The median's three kernels with R ranks per column: prefixes, ranks and counters at [column * R + rank].
+
+// the first rank of 0..r whose prefix above bit hs equals r's: it owns the counters r reads
+#define POST_LEAD(lead, p, r, R, hs)                                                       \
+    do {                                                                                   \
+        lead = r;                                                                          \
+        _Pragma("unroll") for (int r2 = POST_MAXR - 1; r2 >= 0; --r2)                      \
+            if (r2 < r && r2 < R && (hs >= 64 || ((p[r2] ^ p[r]) >> hs) == 0ull)) lead = r2; \
+    } while (0)
+
+// one pass of the multi-rank radix select: every (row, depth) is sampled once; its key is counted for the one owner whose
+// prefix it matches (the owners' prefixes differ, so there is at most one).  Rank 0 is always an owner, and while the ranks
+// have not parted it is the only one: its counters are the lane's private 16-bit pairs in LDS, as in post_radix_kernel.  A
+// rank that has left rank 0's prefix counts straight into its global counters.
+template <typename T>
+__global__ void __launch_bounds__(64) post_mradix_kernel(ColArgs a, int R, int k32, int shift, const unsigned long long *pref,
+                                                         unsigned *ghist)
+{
+    __shared__ unsigned h[128 * 64]; // [digit / 2][lane]: two 16-bit counters
+    const PostWork w = a.work[blockIdx.x];
+    const int lane = threadIdx.x;
+    const int j = blockIdx.y * 64 + lane;
+    const bool act = j < a.D;
+    for (int b = 0; b < 128; ++b) h[b * 64 + lane] = 0u; // a lane touches its own column only: no barrier
+    if (!act) return;
+    const size_t c = (size_t)w.site * a.D + j;
+    const double x = a.dep[j];
+    const int hs = shift + 8;
+    unsigned long long p[POST_MAXR];
+    unsigned own = 0u;
+#pragma unroll
+    for (int r = 0; r < POST_MAXR; ++r) p[r] = r < R ? pref[c * R + r] : 0ull;
+#pragma unroll
+    for (int r = 0; r < POST_MAXR; ++r) {
+        int lead;
+        POST_LEAD(lead, p, r, R, hs);
+        own |= (r < R && lead == r) ? 1u << r : 0u;
+    }
+    const T *pvs = (const T *)a.pvs;
+    unsigned *g = ghist + c * R * 256;
+    for (int64_t r = w.r0; r < w.r1; ++r) {
+        const double v = sample(a.pn[r], pvs + r * a.ML, a.pd + r * a.ML, x);
+        const unsigned long long k = okey(v, k32 != 0);
+        const unsigned dg = (unsigned)(k >> shift) & 255u;
+        int o = -1;
+#pragma unroll
+        for (int q = 0; q < POST_MAXR; ++q)
+            o = (((own >> q) & 1u) && (hs >= 64 || ((k ^ p[q]) >> hs) == 0ull)) ? q : o;
+        if (o == 0) h[(dg >> 1) * 64 + lane] += 1u << ((dg & 1u) * 16u);
+        else if (o > 0) atomicAdd(&g[o * 256 + dg], 1u);
+    }
+    for (int b = 0; b < 128; ++b) {
+        const unsigned v = h[b * 64 + lane];
+        if (v & 0xffffu) atomicAdd(&g[2 * b], v & 0xffffu);
+        if (v >> 16) atomicAdd(&g[2 * b + 1], v >> 16);
+    }
+}
+
+// one thread per column: per rank the digit holding it, read from the counters of the rank that owns them; then the counters
+// are cleared for the next pass
+__global__ void __launch_bounds__(256) post_mpick_kernel(size_t ncol, int R, int shift, unsigned *ghist, unsigned long long *pref,
+                                                         unsigned *rank)
+{
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncol) return;
+    const int hs = shift + 8;
+    unsigned long long p[POST_MAXR];
+    int dgs[POST_MAXR];
+    unsigned rest[POST_MAXR];
+#pragma unroll
+    for (int r = 0; r < POST_MAXR; ++r) p[r] = r < R ? pref[c * R + r] : 0ull;
+#pragma unroll
+    for (int r = 0; r < POST_MAXR; ++r) {
+        dgs[r] = -1;
+        rest[r] = 0u;
+        if (r >= R) continue;
+        int lead;
+        POST_LEAD(lead, p, r, R, hs);
+        const unsigned *g = ghist + (c * R + lead) * 256;
+        const unsigned k = rank[c * R + r];
+        unsigned cum = 0;
+        int dg = -1;
+        for (int b = 0; b < 256; ++b) {
+            const unsigned hb = g[b];
+            if (dg < 0 && k < cum + hb) dg = b;
+            if (dg < 0) cum += hb;
+        }
+        dgs[r] = dg;
+        rest[r] = k - cum;
+    }
+#pragma unroll
+    for (int r = 0; r < POST_MAXR; ++r) {
+        if (r >= R) continue;
+        unsigned *g = ghist + (c * R + r) * 256;
+        for (int b = 0; b < 256; ++b) g[b] = 0u;
+        if (dgs[r] < 0) continue; // a column without rows
+        rank[c * R + r] = rest[r];
+        pref[c * R + r] = p[r] | ((unsigned long long)dgs[r] << shift);
+    }
+}
+
+// per rank the number of keys <= the selected one, and the least key above it
+template <typename T>
+__global__ void __launch_bounds__(64) post_mnext_kernel(ColArgs a, int R, int k32, const unsigned long long *pref, unsigned *nle,
+                                                        unsigned long long *next)
+{
+    const PostWork w = a.work[blockIdx.x];
+    const int j = blockIdx.y * 64 + threadIdx.x;
+    if (j >= a.D) return;
+    const size_t c = (size_t)w.site * a.D + j;
+    const double x = a.dep[j];
+    const T *pvs = (const T *)a.pvs;
+    unsigned long long p[POST_MAXR], nx[POST_MAXR];
+    unsigned le[POST_MAXR];
+#pragma unroll
+    for (int r = 0; r < POST_MAXR; ++r) {
+        p[r] = r < R ? pref[c * R + r] : 0ull;
+        le[r] = 0u;
+        nx[r] = ~0ull;
+    }
+    for (int64_t r = w.r0; r < w.r1; ++r) {
+        const unsigned long long k = okey(sample(a.pn[r], pvs + r * a.ML, a.pd + r * a.ML, x), k32 != 0);
+#pragma unroll
+        for (int q = 0; q < POST_MAXR; ++q) {
+            if (q >= R) break; // (uniform)
+            le[q] += k <= p[q] ? 1u : 0u;
+            nx[q] = (k > p[q] && k < nx[q]) ? k : nx[q];
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < POST_MAXR; ++r) {
+        if (r >= R) continue;
+        atomicAdd(&nle[c * R + r], le[r]);
+        atomicMin(&next[c * R + r], nx[r]);
+    }
 }
 
 struct HistArgs {
@@ -634,6 +774,70 @@ int bh_posterior_columns(bh_posterior *p, int D, const double *dep, uint64_t *km
         }
     }
     PCHK(p, hipStreamSynchronize(p->st));
+    return BH_OK;
+}
+
+int bh_posterior_column_quantiles(bh_posterior *p, int D, const double *dep, int R, const uint32_t *rank, uint64_t *lower,
+                                  uint64_t *upper, int32_t *keys32)
+{
+    int rc;
+    if (!p) return BH_EINVAL;
+    if (p->S < 1) return pfail(p, BH_EINVAL, "no rows loaded (bh_posterior_load)");
+    if (R < 1 || R > POST_MAXR) return pfail(p, BH_EINVAL, "ranks per column: 1..BH_QUANTILES_MAXRANKS");
+    if (!dep || !rank || !lower || !upper) return pfail(p, BH_EINVAL, "null argument");
+    if (D < 1 || D > (1 << 20)) return pfail(p, BH_EINVAL, "depth grid: 1..2^20 points");
+    if (!grid_ok(dep, D)) return pfail(p, BH_EINVAL, "depth grid must be finite and strictly ascending");
+    const int S = p->S;
+    for (int s = 0; s < S; ++s) {
+        const int64_t n = p->off[s + 1] - p->off[s];
+        if (n >= (1ll << 32)) return pfail(p, BH_EUNSUPPORTED, "2^32 or more rows of one site");
+        for (int r = 0; r < R; ++r)
+            if ((int64_t)rank[(size_t)s * R + r] >= std::max<int64_t>(n, 1)) return pfail(p, BH_EINVAL, "a rank is not below its site's rows");
+    }
+    PCHK(p, hipSetDevice(p->device));
+    const size_t ncol = (size_t)S * D, nr = ncol * R;
+    Dev dd, dh, dpref, drank, dnle, dnext;
+    if ((rc = alloc(p, dd, (size_t)D * sizeof(double))) || (rc = alloc(p, dh, nr * 256 * 4)) || (rc = alloc(p, dpref, nr * 8)) ||
+        (rc = alloc(p, drank, nr * 4)) || (rc = alloc(p, dnle, nr * 4)) || (rc = alloc(p, dnext, nr * 8)))
+        return rc;
+    std::vector<unsigned> rk(nr);
+    for (size_t c = 0; c < ncol; ++c)
+        for (int r = 0; r < R; ++r) rk[c * R + r] = rank[(c / D) * R + r];
+    PCHK(p, hipMemcpyAsync(dd.p, dep, (size_t)D * sizeof(double), hipMemcpyHostToDevice, p->st));
+    PCHK(p, hipMemsetAsync(dh.p, 0, nr * 256 * 4, p->st));
+    PCHK(p, hipMemsetAsync(dpref.p, 0, nr * 8, p->st));
+    PCHK(p, hipMemsetAsync(dnle.p, 0, nr * 4, p->st));
+    PCHK(p, hipMemsetAsync(dnext.p, 0xff, nr * 8, p->st));
+    PCHK(p, hipMemcpyAsync(drank.p, rk.data(), nr * 4, hipMemcpyHostToDevice, p->st));
+    const ColArgs a = col_args(p, dd.as<double>(), D);
+    const dim3 grid((unsigned)p->work.size(), (unsigned)((D + 63) / 64));
+    const bool f = p->elem == 4;
+    const int k32 = p->keys32 ? 1 : 0;
+    if (!p->work.empty()) {
+        const unsigned pb = (unsigned)((ncol + 255) / 256);
+        for (int shift = (k32 ? 32 : 64) - 8; shift >= 0; shift -= 8) {
+            if (f) post_mradix_kernel<float><<<grid, 64, 0, p->st>>>(a, R, k32, shift, dpref.as<unsigned long long>(), dh.as<unsigned>());
+            else post_mradix_kernel<double><<<grid, 64, 0, p->st>>>(a, R, k32, shift, dpref.as<unsigned long long>(), dh.as<unsigned>());
+            post_mpick_kernel<<<pb, 256, 0, p->st>>>(ncol, R, shift, dh.as<unsigned>(), dpref.as<unsigned long long>(), drank.as<unsigned>());
+        }
+        if (f) post_mnext_kernel<float><<<grid, 64, 0, p->st>>>(a, R, k32, dpref.as<unsigned long long>(), dnle.as<unsigned>(), dnext.as<unsigned long long>());
+        else post_mnext_kernel<double><<<grid, 64, 0, p->st>>>(a, R, k32, dpref.as<unsigned long long>(), dnle.as<unsigned>(), dnext.as<unsigned long long>());
+        PCHK(p, hipGetLastError());
+    }
+    std::vector<uint64_t> pref(nr), next(nr);
+    std::vector<unsigned> nle(nr);
+    PCHK(p, hipMemcpyAsync(pref.data(), dpref.p, nr * 8, hipMemcpyDeviceToHost, p->st));
+    PCHK(p, hipMemcpyAsync(next.data(), dnext.p, nr * 8, hipMemcpyDeviceToHost, p->st));
+    PCHK(p, hipMemcpyAsync(nle.data(), dnle.p, nr * 4, hipMemcpyDeviceToHost, p->st));
+    PCHK(p, hipStreamSynchronize(p->st));
+    for (size_t i = 0; i < nr; ++i) {
+        const size_t s = i / ((size_t)D * R);
+        if (p->off[s + 1] == p->off[s]) { lower[i] = upper[i] = 0; continue; }
+        lower[i] = pref[i];
+        // rank + 1 is the selected key again while more keys than rank + 1 are <= it
+        upper[i] = ((uint64_t)nle[i] >= (uint64_t)rk[i] + 2u || next[i] == ~0ull) ? pref[i] : next[i];
+    }
+    if (keys32) *keys32 = k32;
     return BH_OK;
 }
 

@@ -13,41 +13,19 @@ computes them in; count, min, max, median and the order statistics are bit-exact
 are numpy.quantile(..., method="linear") of them; mean and std come from exact integer sums.
 """
 import ctypes as C
-import math
 
 import numpy as np
 
 from . import engine as E
 from .posterior import _Loaded, _keys_to_values, _mean_std, _ptr, median_of_middles
+from .posterior import quantile_lerp, quantile_rank, set_quantiles   # noqa: F401 (the quantile formula lives with _Loaded)
 
 DEFAULT_QUANTILES = (0.025, 0.16, 0.5, 0.84, 0.975)
 DEFAULT_MAX_BYTES = 1 << 31   # of the DATA set of one group of sites
 DEFAULT_BATCH = 16384         # rows of one forward batch
 
 
-# ---- the pure parts: quantile formula, planner -----------------------------------------------------------------------------
-
-def quantile_rank(n, p):
-    """(k, g) of numpy.quantile(..., method="linear") over n values: the virtual index (n - 1) * p in float64, its floor and
-    the remainder; the result interpolates the order statistics k and k + 1 (k + 1 = k at the last rank)."""
-    if not 0.0 <= p <= 1.0:
-        raise ValueError("quantiles must be in [0, 1]")
-    if n < 1:
-        return 0, 0.0
-    vi = np.float64(n - 1) * np.float64(p)
-    k = math.floor(vi)
-    if k >= n - 1:
-        return n - 1, 0.0
-    return int(k), float(vi - np.float64(k))
-
-
-def quantile_lerp(a, b, g):
-    """numpy's interpolation between the order statistics a <= b at remainder g: a + (b - a) * g, and b - (b - a) * (1 - g)
-    where g >= 0.5 (float64)."""
-    a, b, g = np.float64(a), np.float64(b), np.float64(g)
-    d = b - a
-    return b - d * (np.float64(1) - g) if g >= 0.5 else a + d * g
-
+# ---- the pure parts: planner (the quantile formula: posterior.quantile_rank, quantile_lerp) --------------------------------
 
 def plan_site_groups(rows, ldy, max_bytes):
     """Sites 0..S-1 with rows[s] rows each into consecutive groups [(s0, s1), ...] whose DATA sets (ldy * rows * 8 bytes) stay
@@ -144,46 +122,11 @@ class _DataLoaded(_Loaded):
                                                        _ptr(ncol), _ptr(failed)))
         return failed
 
-    def quantile_keys(self, which, rank):
-        """rank uint32 [S, Q, R] -> (lower, upper) float64 [S, Q, R]: the order statistics rank and rank + 1"""
-        rank = np.ascontiguousarray(rank, np.uint32)
-        lo, up = np.zeros(rank.shape, np.uint64), np.zeros(rank.shape, np.uint64)
-        self.eng._check(self._L.bh_posterior_scalar_quantiles(self._p, which, rank.shape[2], _ptr(rank), _ptr(lo), _ptr(up)))
-        return lo, up
-
     def gather(self, which, pos, Q):
         pos = np.ascontiguousarray(pos, np.int64)
         out = np.zeros((pos.size, Q))
         self.eng._check(self._L.bh_posterior_scalar_gather(self._p, which, pos.size, _ptr(pos), _ptr(out)))
         return out
-
-
-def set_quantiles(ld, which, count, quantiles):
-    """numpy.quantile(column values, quantiles, method="linear") of every (site, column) of a set whose scalar_stats gave
-    `count` [S, Q]: float64 [S, Q, R], NaN where the count is 0.  More than 8 quantiles go in several calls."""
-    S, Q = count.shape
-    qs = [float(q) for q in quantiles]
-    out = np.full((S, Q, len(qs)), np.nan)
-    for i0 in range(0, len(qs), E.QUANTILES_MAXRANKS):
-        part = qs[i0:i0 + E.QUANTILES_MAXRANKS]
-        rank = np.zeros((S, Q, len(part)), np.uint32)
-        g = np.zeros((S, Q, len(part)))
-        memo = {}
-        for s in range(S):
-            for q in range(Q):
-                n = int(count[s, q])
-                if n not in memo:
-                    memo[n] = [quantile_rank(n, p) for p in part]
-                for r, (k, gg) in enumerate(memo[n]):
-                    rank[s, q, r], g[s, q, r] = k, gg
-        lo, up = ld.quantile_keys(which, rank)
-        a = _keys_to_values(lo.reshape(-1), False).reshape(lo.shape)
-        b = _keys_to_values(up.reshape(-1), False).reshape(up.shape)
-        d = b - a
-        with np.errstate(invalid="ignore", over="ignore"):
-            v = np.where(g >= 0.5, b - d * (1.0 - g), a + d * g)
-        out[:, :, i0:i0 + len(part)] = np.where(count[:, :, None] > 0, v, np.nan)
-    return out
 
 
 class _Clock(object):

@@ -682,23 +682,48 @@ class DeviceChains(object):
             cold_only = self.ladder is not None
         return self.samples_dev(phase, cold_only=cold_only, exclude_chains=exclude_chains)
 
-    def posterior_moho(self, moho=None, mohovs=4.2, bins=50, phase="p2", cold_only=None, exclude_chains=()):
+    def posterior_models(self, dep_int=None, quantiles=None, phase="p2", cold_only=None, exclude_chains=()):
+        """record="device": bayhunter_amd.posterior_models of every site's recorded rows, straight from the device store (one dict
+        per site; one dict without SiteTargets): mean, median, minmax, stdminmax, mode and -- the joint misfit misfits[..., -1]
+        being in the store -- minmisfit of vs against depth; quantiles (numbers in [0, 1]) adds the credible band `quantiles`.
+        cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        from .posterior import posterior_models
+        d = self._posterior_rows(phase, cold_only, exclude_chains)
+        n = d["models2d"].shape[0]
+        with self.torch.cuda.device(self.dev):
+            r = posterior_models(d["models2d"], site=d["site"], dep_int=dep_int, misfits=d["misfits"][..., -1].reshape(n),
+                                 engine=self.engine, nsites=self.nsites, quantiles=quantiles)
+        return r if self.sites is not None else r[0]
+
+    def posterior_hist2d(self, dep_int=None, vs_edges=None, dep_edges=None, phase="p2", cold_only=None, exclude_chains=()):
+        """record="device": bayhunter_amd.posterior_hist2d of every site's recorded rows, straight from the device store (one dict
+        per site; one dict without SiteTargets): the 2-D posterior plot's vs-depth histogram and the histogram of interface
+        depths.  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        from .posterior import posterior_hist2d
+        d = self._posterior_rows(phase, cold_only, exclude_chains)
+        with self.torch.cuda.device(self.dev):
+            r = posterior_hist2d(d["models2d"], site=d["site"], dep_int=dep_int, vs_edges=vs_edges, dep_edges=dep_edges,
+                                 engine=self.engine, nsites=self.nsites)
+        return r if self.sites is not None else r[0]
+
+    def posterior_moho(self, moho=None, mohovs=4.2, bins=50, phase="p2", cold_only=None, exclude_chains=(), quantiles=None):
         """record="device": bayhunter_amd.posterior_moho of every site's recorded rows, straight from the device store (one dict
         per site; one dict without SiteTargets).  moho None: every site's own priors['z'], the reference's default.  cold_only
-        (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        (default: True on tempered runs) and exclude_chains as in samples_dev().  quantiles: as posterior_moho's."""
         from .posterior import posterior_moho
         d = self._posterior_rows(phase, cold_only, exclude_chains)
         if moho is None:
             moho = [tuple(float(v) for v in p["z"]) for p in self.site_priors]
         with self.torch.cuda.device(self.dev):
             r = posterior_moho(d["models2d"], site=d["site"], moho=moho, mohovs=mohovs, bins=bins, engine=self.engine,
-                               nsites=self.nsites)
+                               nsites=self.nsites, quantiles=quantiles)
         return r if self.sites is not None else r[0]
 
-    def posterior_scalars(self, bins=20, nlayers=True, phase="p2", cold_only=None, exclude_chains=()):
+    def posterior_scalars(self, bins=20, nlayers=True, phase="p2", cold_only=None, exclude_chains=(), quantiles=None):
         """record="device": bayhunter_amd.posterior_scalars of every site's recorded rows with the store's likes, vpvs, misfits
         [nt+1] and noise [2nt] as columns (slot layout), straight from the device store (one dict per site; one dict without
-        SiteTargets).  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        SiteTargets).  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev().  quantiles: as
+        posterior_scalars'."""
         from .posterior import posterior_scalars
         d = self._posterior_rows(phase, cold_only, exclude_chains)
         n = d["models2d"].shape[0]
@@ -706,7 +731,7 @@ class DeviceChains(object):
                     noise=d["noise"].reshape(n, 2 * self.nt))
         with self.torch.cuda.device(self.dev):
             r = posterior_scalars(d["models2d"], cols, site=d["site"], bins=bins, nlayers=nlayers, engine=self.engine,
-                                  nsites=self.nsites)
+                                  nsites=self.nsites, quantiles=quantiles)
         return r if self.sites is not None else r[0]
 
     def posterior_datafits(self, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), phase="p2", cold_only=None, exclude_chains=()):

@@ -213,6 +213,9 @@ def load_library():
     L.bh_posterior_scalar_gather.argtypes = [vp, C.c_int, C.c_int64, vp, vp]
     for name in POSTERIOR_DATAFIT_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_posterior_column_quantiles.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    for name in POSTERIOR_QUANTILES_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     L.bh_chain_diag_series.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int,
                                        vp, vp, vp, vp, vp, vp, vp]
     L.bh_chain_diag_models.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
@@ -296,6 +299,9 @@ POSTERIOR_DATAFIT_SYMBOLS = ("bh_posterior_layers", "bh_posterior_best", "bh_pos
 SCALARS_DATA = 3                    # BH_SCALARS_DATA
 DATAFIT_MAXCOLS = 4096              # BH_DATAFIT_MAXCOLS
 QUANTILES_MAXRANKS = 8              # BH_QUANTILES_MAXRANKS
+# include/bh_engine_posterior_quantiles.h: several order statistics of every (site, depth) column of the interpolated vs
+# (bayhunter_amd/posterior.py: posterior_models(quantiles=...))
+POSTERIOR_QUANTILES_SYMBOLS = ("bh_posterior_column_quantiles",)
 # include/bh_engine_chain_diag.h: the sums behind split R-hat and ESS of the chains' recorded series, and the medians of the
 # outlier rule (bayhunter_amd/diagnostics.py)
 CHAIN_DIAG_SYMBOLS = ("bh_chain_diag_series", "bh_chain_diag_models", "bh_chain_diag_medians")

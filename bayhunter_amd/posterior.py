@@ -45,6 +45,98 @@ def _keys_to_values(k, keys32):
     return u.view(np.float64)
 
 
+def quantile_rank(n, p):
+    """(k, g) of numpy.quantile(..., method="linear") over n values: the virtual index (n - 1) * p in float64, its floor and
+    the remainder; the result interpolates the order statistics k and k + 1 (k + 1 = k at the last rank)."""
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("quantiles must be in [0, 1]")
+    if n < 1:
+        return 0, 0.0
+    vi = np.float64(n - 1) * np.float64(p)
+    k = math.floor(vi)
+    if k >= n - 1:
+        return n - 1, 0.0
+    return int(k), float(vi - np.float64(k))
+
+
+def quantile_lerp(a, b, g):
+    """numpy's interpolation between the order statistics a <= b at remainder g: a + (b - a) * g, and b - (b - a) * (1 - g)
+    where g >= 0.5 (float64)."""
+    a, b, g = np.float64(a), np.float64(b), np.float64(g)
+    d = b - a
+    return b - d * (np.float64(1) - g) if g >= 0.5 else a + d * g
+
+
+def check_quantiles(quantiles):
+    """None, or the requested quantiles as a float64 array in the order given (duplicates allowed): a sequence of numbers in
+    [0, 1]; anything else is a ValueError.  Touches no engine."""
+    if quantiles is None:
+        return None
+    if isinstance(quantiles, (str, bytes)) or np.ndim(quantiles) != 1:
+        raise ValueError("quantiles must be a sequence of numbers in [0, 1]")
+    qs = []
+    for q in quantiles:
+        if isinstance(q, (bool, np.bool_)) or not isinstance(q, (int, float, np.integer, np.floating)):
+            raise ValueError("quantiles must be numbers in [0, 1], not %r" % (q,))
+        q = float(q)
+        if not 0.0 <= q <= 1.0:   # (a NaN fails both)
+            raise ValueError("quantiles must be in [0, 1], not %r" % (q,))
+        qs.append(q)
+    return np.array(qs, np.float64)
+
+
+def _lerp_keys(lo, up, keys32, g, have):
+    """numpy's linear interpolation at remainders g between the order statistics of the keys lo and up; NaN where not `have`"""
+    a = _keys_to_values(lo.reshape(-1), keys32).reshape(lo.shape)
+    b = _keys_to_values(up.reshape(-1), keys32).reshape(up.shape)
+    d = b - a
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.where(g >= 0.5, b - d * (1.0 - g), a + d * g)
+    return np.where(have, v, np.nan)
+
+
+def set_quantiles(ld, which, count, quantiles):
+    """numpy.quantile(column values, quantiles, method="linear") of every (site, column) of a set whose scalar_stats gave
+    `count` [S, Q]: float64 [S, Q, R], NaN where the count is 0.  More than 8 quantiles go in several calls."""
+    S, Q = count.shape
+    qs = [float(q) for q in quantiles]
+    out = np.full((S, Q, len(qs)), np.nan)
+    for i0 in range(0, len(qs), E.QUANTILES_MAXRANKS):
+        part = qs[i0:i0 + E.QUANTILES_MAXRANKS]
+        rank = np.zeros((S, Q, len(part)), np.uint32)
+        g = np.zeros((S, Q, len(part)))
+        memo = {}
+        for s in range(S):
+            for q in range(Q):
+                n = int(count[s, q])
+                if n not in memo:
+                    memo[n] = [quantile_rank(n, p) for p in part]
+                for r, (k, gg) in enumerate(memo[n]):
+                    rank[s, q, r], g[s, q, r] = k, gg
+        lo, up = ld.quantile_keys(which, rank)
+        out[:, :, i0:i0 + len(part)] = _lerp_keys(lo, up, False, g, count[:, :, None] > 0)
+    return out
+
+
+def column_quantiles(ld, dep, quantiles):
+    """numpy.quantile(column, quantiles, method="linear") of every (site, depth) column of the interpolated vs of the loaded
+    rows: float64 [S, R, D], NaN for a site without rows.  More than 8 quantiles go in several calls."""
+    S, D = ld.S, len(dep)
+    qs = [float(q) for q in quantiles]
+    out = np.full((S, len(qs), D), np.nan)
+    for i0 in range(0, len(qs), E.QUANTILES_MAXRANKS):
+        part = qs[i0:i0 + E.QUANTILES_MAXRANKS]
+        rank = np.zeros((S, len(part)), np.uint32)
+        g = np.zeros((S, len(part)))
+        for s in range(S):
+            for r, p in enumerate(part):
+                rank[s, r], g[s, r] = quantile_rank(int(ld.rows[s]), p)
+        lo, up, k32 = ld.column_quantile_keys(dep, rank)
+        v = _lerp_keys(lo, up, k32, g[:, None, :], (ld.rows > 0)[:, None, None])   # [S, D, R]
+        out[:, i0:i0 + len(part), :] = v.transpose(0, 2, 1)
+    return out
+
+
 def depth_bins(samples, edges):
     """numpy.histogram2d's depth bin of every sample (searchsorted 'right', the last edge into the last bin); -1 outside."""
     samples, edges = np.asarray(samples, np.float64), np.asarray(edges, np.float64)
@@ -184,6 +276,18 @@ class _Loaded(object):
         out["keys32"] = bool(k32[0])
         return out
 
+    def column_quantile_keys(self, dep, rank):
+        """rank uint32 [S, R] -> (lower, upper, keys32): the keys [S, D, R] of every column's order statistics rank and rank + 1
+        (include/bh_engine_posterior_quantiles.h)"""
+        dep = np.ascontiguousarray(dep, np.float64)
+        rank = np.ascontiguousarray(rank, np.uint32)
+        shape = (self.S, dep.size, rank.shape[1])
+        lo, up = np.zeros(shape, np.uint64), np.zeros(shape, np.uint64)
+        k32 = np.zeros(1, np.int32)
+        self.eng._check(self._L.bh_posterior_column_quantiles(self._p, dep.size, _ptr(dep), rank.shape[1], _ptr(rank), _ptr(lo),
+                                                              _ptr(up), _ptr(k32)))
+        return lo, up, bool(k32[0])
+
     def hist(self, dep, dbin, nd, edges_per_site, argmax=False):
         dep = np.ascontiguousarray(dep, np.float64)
         dbin = np.ascontiguousarray(dbin, np.int32)
@@ -246,6 +350,13 @@ class _Loaded(object):
         if median:
             out["med"] = _keys_to_values(out["median"].reshape(-1), False).reshape(S, Q, 2)
         return out
+
+    def quantile_keys(self, which, rank):
+        """rank uint32 [S, Q, R] -> (lower, upper) uint64 keys [S, Q, R]: the order statistics rank and rank + 1 of a set's columns"""
+        rank = np.ascontiguousarray(rank, np.uint32)
+        lo, up = np.zeros(rank.shape, np.uint64), np.zeros(rank.shape, np.uint64)
+        self.eng._check(self._L.bh_posterior_scalar_quantiles(self._p, which, rank.shape[2], _ptr(rank), _ptr(lo), _ptr(up)))
+        return lo, up
 
     @staticmethod
     def _edges(edges_per_site):
@@ -313,13 +424,21 @@ def _row(models, i):
     return np.asarray(r)
 
 
-def posterior_models(models, site=None, dep_int=None, misfits=None, engine=None, nsites=None):
+def posterior_models(models, site=None, dep_int=None, misfits=None, engine=None, nsites=None, quantiles=None):
     """get_singlemodels of every site: a list of dicts (one dict when site is None).  Keys: mean, median, minmax,
     stdminmax (each (values, dep_int)), mode ((vs_mode, dep_center); NaN and mode_valid False where the reference raises,
-    i.e. the site's vs range is below one 0.025 km/s bin), minmisfit (with misfits), count, mode_valid, invalid_rows."""
+    i.e. the site's vs range is below one 0.025 km/s bin), minmisfit (with misfits), count, mode_valid, invalid_rows.
+    quantiles: a sequence of numbers in [0, 1] (any order, duplicates allowed; anything else is a ValueError) adds the keys
+    quantiles = (values [R, D], dep_int) and q (the requested quantiles, float64): values[i, j] is numpy.quantile(column j, q[i],
+    method="linear") of the site's float64 column of interpolated vs -- the credible band of vs against depth -- NaN for a site
+    without rows (include/bh_engine_posterior_quantiles.h; the columns are never stored).  quantiles at 0.5 need not equal
+    `median` in the last bit for an even count: median is (a + b) / 2, numpy's quantile b - (b - a) * 0.5, of the same two
+    order statistics a <= b."""
+    qs = check_quantiles(quantiles)
     dep = default_dep_int() if dep_int is None else np.ascontiguousarray(dep_int, np.float64)
     ld = _Loaded(models, site, engine, nsites)
     try:
+        qv = column_quantiles(ld, dep, qs) if qs is not None else None
         col = ld.columns(dep, median=True)
         S, D = ld.S, dep.size
         vmin_s = np.array([col["min"][s].min() if ld.rows[s] else np.nan for s in range(S)])
@@ -364,6 +483,9 @@ def posterior_models(models, site=None, dep_int=None, misfits=None, engine=None,
             r["mode"] = (vs_center[am[s]], dep_center)
         else:
             r["mode"] = (np.full(D - 1, np.nan), dep_center)
+        if qs is not None:
+            r["quantiles"] = (qv[s], dep)
+            r["q"] = qs.copy()
         if groups is not None:
             mis, sidx = groups
             idx = np.flatnonzero(sidx == s)
@@ -458,7 +580,7 @@ def _stat_dict(st, s, q, dtype=np.float64):
                 min=dtype(st["min"][s, q]), max=dtype(st["max"][s, q]))
 
 
-def posterior_moho(models, site=None, moho=None, mohovs=MOHOVS, bins=50, engine=None, nsites=None):
+def posterior_moho(models, site=None, moho=None, mohovs=MOHOVS, bins=50, engine=None, nsites=None, quantiles=None):
     """The numbers of the reference's plot_moho_crustvel_tradeoff for every site: a list of dicts (one dict when site is
     None).  moho = (lo, hi) km, or one pair per site: the depth range in which an interface can be the Moho (0 <= lo < hi);
     mohovs (one, or one per site): the Moho is the first interface inside the range below which vs exceeds it.
@@ -467,7 +589,12 @@ def posterior_moho(models, site=None, moho=None, mohovs=MOHOVS, bins=50, engine=
     crustal vs above the Moho), vsjump (the vs step at the Moho): each a dict of median, mean, std, min, max; hist: name ->
     (counts [bins], edges); hist2d: vslast / vscrust / vsjump -> (counts [bins, bins], xedges, yedges) against moho; mode:
     the same names -> (x, y), the centres of the first largest cell.  A site without a Moho row has count 0, NaN statistics
-    and empty histograms over [0, 1]."""
+    and empty histograms over [0, 1].
+    quantiles: a sequence of numbers in [0, 1] (any order, duplicates allowed; anything else is a ValueError) adds to each of the
+    four dicts quantiles [R] = numpy.quantile(values, quantiles, method="linear") over the rows that have a Moho -- the credible
+    interval of the Moho depth -- NaN where count is 0.  quantiles at 0.5 need not equal median
+    in the last bit for an even count ((a + b) / 2 against numpy's b - (b - a) * 0.5 of the same two order statistics)."""
+    qs = check_quantiles(quantiles)
     if moho is None:
         raise ValueError("moho=(lo, hi) is needed: the reference's default is the station's priors['z']")
     ld = _Loaded(models, site, engine, nsites, scalars=True)
@@ -477,6 +604,7 @@ def posterior_moho(models, site=None, moho=None, mohovs=MOHOVS, bins=50, engine=
         mv = _per_site(mohovs, S, 0, "mohovs")
         found = ld.moho(rng[:, 0], rng[:, 1], mv)
         st = ld.scalar_stats(E.SCALARS_MOHO)
+        qv = set_quantiles(ld, E.SCALARS_MOHO, st["count"], qs) if qs is not None else None
         edges = [[moho_edges(st["min"][s, q], st["max"][s, q], bins) if found[s] else moho_edges(None, None, bins)
                   for s in range(S)] for q in range(4)]
         h1 = [ld.scalar_hist(E.SCALARS_MOHO, q, edges[q]) for q in range(4)]
@@ -489,6 +617,8 @@ def posterior_moho(models, site=None, moho=None, mohovs=MOHOVS, bins=50, engine=
                  mode={})
         for q, name in enumerate(MOHO_COLUMNS):
             r[name] = _stat_dict(st, s, q)
+            if qs is not None:
+                r[name]["quantiles"] = qv[s, q].copy()
             r["hist"][name] = (h1[q][s].astype(np.int64), edges[q][s])
         for i, q in enumerate((1, 2, 3)):
             name = MOHO_COLUMNS[q]
@@ -545,7 +675,7 @@ def _stack_columns(columns, N):
     return np.concatenate([p.astype(ndt, copy=False) for p in parts], axis=1), layout
 
 
-def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=None, nsites=None):
+def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=None, nsites=None, quantiles=None):
     """The numbers of the reference's plot_posterior_likes / _misfits / _nlayers / _vpvs / _noise / _others for every site: a
     list of dicts (one dict when site is None), name -> statistics.  columns: a dict name -> [N] or [N, k] values (float32 or
     float64; numpy arrays or device tensors), one row per model row; a [N, k] column gives a list of k statistics.  With
@@ -556,7 +686,13 @@ def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=
     reference's placeholder edges [m - 1, m - 0.1, m + 0.1, m + 1].  (The reference tests np.std(data) == 0 instead, which
     numpy's own rounding of the mean can miss on a constant column; min == max cannot.)  The dict also holds rows,
     invalid_rows and dropped (as posterior_moho); a column of one of these names, or "nlayers" beside the built-in one, is a
-    ValueError."""
+    ValueError.
+    quantiles: a sequence of numbers in [0, 1] (any order, duplicates allowed; anything else is a ValueError) adds to every
+    column's statistics, nlayers included, quantiles [R] float64 = numpy.quantile(values widened to float64, quantiles,
+    method="linear") over the column's non-NaN values, NaN where count is 0 -- whatever the column's dtype (numpy computes a
+    float32 column's quantile in float32; median keeps its per-dtype meaning).  quantiles at 0.5 need not equal median in the
+    last bit for an even count ((a + b) / 2 against numpy's b - (b - a) * 0.5 of the same two order statistics)."""
+    qs = check_quantiles(quantiles)
     taken = [k for k in columns if k in ("rows", "invalid_rows", "dropped") or (nlayers and k == "nlayers")]
     if taken:
         raise ValueError("column name %r is a key of the result itself: give the column another name" % (taken[0],))
@@ -570,6 +706,7 @@ def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=
             raise ValueError("no column and no nlayers: nothing to summarise")
         ld.attach(values, nlayers)
         st = ld.scalar_stats(E.SCALARS_USER)
+        qv = set_quantiles(ld, E.SCALARS_USER, st["count"], qs) if qs is not None else None
         Q = len(layout)
         edges = [[scalar_edges(st["min"][s, q], st["max"][s, q], layout[q][2], bins, nlayers and q == Q - 1)
                   if st["count"][s, q] else scalar_edges(None, None, layout[q][2], bins) for s in range(S)] for q in range(Q)]
@@ -586,6 +723,8 @@ def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=
             cnt = hists[q][s].astype(np.int64)
             d.update(count=n, nan=int(st["nan"][s, q]), constant=bool(n and st["min"][s, q] == st["max"][s, q]), hist=(cnt, e),
                      mode=((e[:-1] + e[1:]) / 2.)[np.argmax(cnt)] if n else np.nan)
+            if qs is not None:
+                d["quantiles"] = qv[s, q].copy()
             if idx is None:
                 r[name] = d
             else:

@@ -166,10 +166,11 @@ def save_final_distribution(datapath, maxmodels=200000, dev=0.05, rstate=None):
     return outliers
 
 
-def posterior_from_storage(datapaths, dep_int=None, engine=None):
+def posterior_from_storage(datapaths, dep_int=None, engine=None, quantiles=None):
     """Posterior velocity-depth summaries of many sites in one GPU call (bayhunter_amd.posterior.posterior_models):
     datapaths[s] is site s's data directory after save_final_distribution (c_models.npy; c_misfits.npy, its last column
-    the joint misfit, for `minmisfit`).  Rows of different widths are padded with NaN.  Returns one dict per site."""
+    the joint misfit, for `minmisfit`).  Rows of different widths are padded with NaN.  quantiles: as posterior_models' (the
+    credible band of vs against depth).  Returns one dict per site."""
     from .posterior import posterior_models
     models = [np.load(op.join(p, "c_models.npy")) for p in datapaths]
     misfits = []
@@ -185,7 +186,8 @@ def posterior_from_storage(datapaths, dep_int=None, engine=None):
         site[start:start + len(m)] = s
         start += len(m)
     mis = None if any(x is None for x in misfits) else np.concatenate(misfits)
-    return posterior_models(rows, site=site, dep_int=dep_int, misfits=mis, engine=engine, nsites=len(datapaths))
+    return posterior_models(rows, site=site, dep_int=dep_int, misfits=mis, engine=engine, nsites=len(datapaths),
+                            quantiles=quantiles)
 
 
 def diagnostics_from_storage(datapaths, dep=None, maxlag=None, dev=0.05, exclude_chains=None, engine=None, rank=False):
@@ -261,16 +263,18 @@ def _stack_sites(arrays):
     return rows, site
 
 
-def moho_from_storage(datapaths, moho=None, mohovs=4.2, bins=50, engine=None):
+def moho_from_storage(datapaths, moho=None, mohovs=4.2, bins=50, engine=None, quantiles=None):
     """Moho depth and crustal velocity posteriors of many sites in one GPU call (bayhunter_amd.posterior.posterior_moho, the
     numbers of the reference's plot_moho_crustvel_tradeoff): datapaths[s] is site s's data directory after
     save_final_distribution (c_models.npy).  moho: (lo, hi) km, one pair per site, or None -- then every site's range is its
-    saved priors['z'] (<station>_config.pkl in the same folder), the reference's default.  Returns one dict per site."""
+    saved priors['z'] (<station>_config.pkl in the same folder), the reference's default.  quantiles: as posterior_moho's (the
+    credible interval of the Moho depth).  Returns one dict per site."""
     from .posterior import posterior_moho
     if moho is None:
         moho = [tuple(float(v) for v in saved_priors(p)["z"]) for p in datapaths]
     rows, site = _stack_sites([np.load(op.join(p, "c_models.npy")) for p in datapaths])
-    return posterior_moho(rows, site=site, moho=moho, mohovs=mohovs, bins=bins, engine=engine, nsites=len(datapaths))
+    return posterior_moho(rows, site=site, moho=moho, mohovs=mohovs, bins=bins, engine=engine, nsites=len(datapaths),
+                          quantiles=quantiles)
 
 
 def station_slots(targets_per_station):
