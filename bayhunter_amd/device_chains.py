@@ -734,6 +734,29 @@ class DeviceChains(object):
                                   nsites=self.nsites, quantiles=quantiles)
         return r if self.sites is not None else r[0]
 
+    def posterior_covariance(self, dep_int=None, scalars=(), moho=None, mohovs=4.2, phase="p2", cold_only=None, exclude_chains=()):
+        """record="device": bayhunter_amd.posterior_covariance of every site's recorded rows, straight from the device store (one
+        dict per site; one dict without SiteTargets): mean, covariance and correlation of vs at the depths of dep_int.  scalars:
+        names of the store's columns to put beside the depths -- likes, vpvs, misfits [nt+1] and noise [2nt], as
+        posterior_scalars() takes them; or moho = (lo, hi) (True: every site's own priors['z']) with mohovs for the Moho depth and
+        the mean crustal vs -- one of the two.  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        from .posterior import posterior_covariance
+        d = self._posterior_rows(phase, cold_only, exclude_chains)
+        n = d["models2d"].shape[0]
+        shapes = dict(likes=(n,), vpvs=(n,), misfits=(n, self.nt + 1), noise=(n, 2 * self.nt))
+        if isinstance(scalars, str):
+            scalars = (scalars,)
+        unknown = [k for k in scalars if k not in shapes]
+        if unknown:
+            raise ValueError("scalars: %r is no column of the store (%s)" % (unknown[0], ", ".join(shapes)))
+        cols = {k: d[k].reshape(shapes[k]) for k in scalars} if len(scalars) else None
+        if moho is True:
+            moho = [tuple(float(v) for v in p["z"]) for p in self.site_priors]
+        with self.torch.cuda.device(self.dev):
+            r = posterior_covariance(d["models2d"], site=d["site"], dep_int=dep_int, columns=cols, moho=moho, mohovs=mohovs,
+                                     engine=self.engine, nsites=self.nsites)
+        return r if self.sites is not None else r[0]
+
     def posterior_datafits(self, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), phase="p2", cold_only=None, exclude_chains=()):
         """record="device": bayhunter_amd.posterior_datafits of every site's recorded rows, straight from the device store (one
         dict per site; one dict without SiteTargets): the best fit of every chain -- the chain id is the row's column in the

@@ -216,6 +216,10 @@ def load_library():
     L.bh_posterior_column_quantiles.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     for name in POSTERIOR_QUANTILES_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_posterior_cov.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.bh_posterior_cov_finish.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    for name in POSTERIOR_COV_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     L.bh_chain_diag_series.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int,
                                        vp, vp, vp, vp, vp, vp, vp]
     L.bh_chain_diag_models.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
@@ -302,6 +306,11 @@ QUANTILES_MAXRANKS = 8              # BH_QUANTILES_MAXRANKS
 # include/bh_engine_posterior_quantiles.h: several order statistics of every (site, depth) column of the interpolated vs
 # (bayhunter_amd/posterior.py: posterior_models(quantiles=...))
 POSTERIOR_QUANTILES_SYMBOLS = ("bh_posterior_column_quantiles",)
+# include/bh_engine_posterior_cov.h: per-site covariance and correlation of vs at depth and scalar columns
+# (bayhunter_amd/posterior.py: posterior_covariance)
+POSTERIOR_COV_SYMBOLS = ("bh_posterior_cov", "bh_posterior_cov_finish")
+COV_MAXCOLS = 256                   # BH_COV_MAXCOLS
+COV_LIMB_BITS = 14                  # BH_COV_LIMB_BITS
 # include/bh_engine_chain_diag.h: the sums behind split R-hat and ESS of the chains' recorded series, and the medians of the
 # outlier rule (bayhunter_amd/diagnostics.py)
 CHAIN_DIAG_SYMBOLS = ("bh_chain_diag_series", "bh_chain_diag_models", "bh_chain_diag_medians")

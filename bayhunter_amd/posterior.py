@@ -12,6 +12,9 @@ column's lowest set bit); they are rounded here from Python integers, within one
 `posterior_moho` and `posterior_scalars` (include/bh_engine_posterior_scalars.h) return per site the numbers of the
 reference's plot_moho_crustvel_tradeoff and plot_posterior_likes / _misfits / _nlayers / _vpvs / _noise / _others: Moho
 depth, crustal vs and any scalar column attached to the rows, with the same exactness.
+
+`posterior_covariance` (include/bh_engine_posterior_cov.h) returns per site the mean vector and the covariance and correlation
+matrices of the vs at the depths of dep_int, and of scalar columns beside them: how the depths of a profile vary together.
 """
 import ctypes as C
 import math
@@ -357,6 +360,21 @@ class _Loaded(object):
         lo, up = np.zeros(rank.shape, np.uint64), np.zeros(rank.shape, np.uint64)
         self.eng._check(self._L.bh_posterior_scalar_quantiles(self._p, which, rank.shape[2], _ptr(rank), _ptr(lo), _ptr(up)))
         return lo, up
+
+    def cov(self, dep, which=-1, cols=(), finished=True):
+        """bh_posterior_cov of the vs at dep and the columns cols of the set `which` (include/bh_engine_posterior_cov.h): a dict of
+        n, masked [S], L, x0, exact, s [S, P], raw [S, P (P + 1) / 2, 3] and, with finished, mean [S, P], cov, corr [S, P, P]"""
+        dep = np.ascontiguousarray(dep, np.float64)
+        cols = np.ascontiguousarray(cols, np.int32)
+        S, P = self.S, dep.size + cols.size
+        out = dict(n=np.zeros(S, np.int64), masked=np.zeros(S, np.int64), L=np.zeros((S, P), np.int32), x0=np.zeros((S, P), np.int64),
+                   exact=np.zeros((S, P), np.int32), s=np.zeros((S, P), np.uint64), raw=np.zeros((S, P * (P + 1) // 2, 3), np.uint64))
+        if finished:
+            out.update(mean=np.zeros((S, P)), cov=np.zeros((S, P, P)), corr=np.zeros((S, P, P)))
+        self.eng._check(self._L.bh_posterior_cov(self._p, dep.size, _ptr(dep), int(which), cols.size, _ptr(cols), _ptr(out["n"]),
+                                                 _ptr(out["masked"]), _ptr(out["L"]), _ptr(out["x0"]), _ptr(out["exact"]), _ptr(out["s"]),
+                                                 _ptr(out["raw"]), _ptr(out.get("mean")), _ptr(out.get("cov")), _ptr(out.get("corr"))))
+        return out
 
     @staticmethod
     def _edges(edges_per_site):
@@ -730,4 +748,60 @@ def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=
             else:
                 r.setdefault(name, []).append(d)
         out.append(r)
+    return out[0] if site is None else out
+
+
+# ---- covariance and correlation of vs with depth (include/bh_engine_posterior_cov.h) ---------------------------------------
+
+def posterior_covariance(models, site=None, dep_int=None, columns=None, moho=None, mohovs=MOHOVS, moho_columns=("moho", "vscrust"),
+                         engine=None, nsites=None):
+    """How a site's profile varies together: a list of dicts (one dict when site is None) with the mean vector and the
+    population covariance (ddof = 0, as std everywhere in this package) and correlation matrices of P columns -- the vs at the
+    depths of dep_int (default 0..100 km in 0.5 km steps; an empty dep_int leaves them out), then scalar columns of ONE set:
+    columns: as posterior_scalars', name -> [N] or [N, k] values, one row per model row (a [N, k] column gives the labels
+      name[0] .. name[k-1]); or
+    moho = (lo, hi) km, or one pair per site, with mohovs: as posterior_moho's -- the columns named by moho_columns (of moho,
+      vslast, vscrust, vsjump) are appended.
+    columns and moho together is a ValueError: one call takes its scalar columns from one set.  A row with NaN in any of the
+    scalar columns (a row without a Moho) is left out of the whole matrix (listwise deletion: the matrix stays a covariance).
+    Keys: dep, names (the P labels: the depths, then the column names), n (the rows used), masked (the rows left out), mean [P],
+    std [P] (the square root of cov's diagonal), cov [P, P], corr [P, P], exact [P] (bool: the column's values went into the
+    integer sums without rounding).  corr is NaN in the row and column of a constant column, as numpy.corrcoef leaves it; a site
+    without rows used has NaN everywhere.  The numbers are functions of exact integer sums formed on the device: the same bits
+    alone or among other sites, in any row order, on every repeat; each within 1 ulp of the exact rational.  The caller who wants
+    ddof = 1 multiplies cov by n / (n - 1)."""
+    if columns is not None and moho is not None:
+        raise ValueError("one call takes its scalar columns from one set: give columns or moho, not both")
+    dep = default_dep_int() if dep_int is None else np.ascontiguousarray(dep_int, np.float64).reshape(-1)
+    if moho is not None:
+        bad = [c for c in moho_columns if c not in MOHO_COLUMNS]
+        if bad or not len(moho_columns):
+            raise ValueError("moho_columns must name some of %r" % (MOHO_COLUMNS,))
+    ld = _Loaded(models, site, engine, nsites, scalars=columns is not None or moho is not None)
+    try:
+        S = ld.S
+        which, cols, names = -1, [], []
+        if columns is not None:
+            values, layout = _stack_columns(columns, ld.N)
+            if values is not None:
+                ld.attach(values, False)
+                which, cols = E.SCALARS_USER, list(range(len(layout)))
+                names = [name if idx is None else "%s[%d]" % (name, idx) for name, idx, _ in layout]
+        elif moho is not None:
+            rng = _per_site(moho, S, 2, "moho")
+            ld.moho(rng[:, 0], rng[:, 1], _per_site(mohovs, S, 0, "mohovs"))
+            which, cols, names = E.SCALARS_MOHO, [MOHO_COLUMNS.index(c) for c in moho_columns], list(moho_columns)
+        P = dep.size + len(cols)
+        if not 1 <= P <= E.COV_MAXCOLS:
+            raise ValueError("%d columns: a call takes 1 .. %d (BH_COV_MAXCOLS)" % (P, E.COV_MAXCOLS))
+        r = ld.cov(dep, which, cols)
+    finally:
+        ld.close()
+    labels = [float(d) for d in dep] + names
+    out = []
+    for s in range(S):
+        with np.errstate(invalid="ignore"):
+            std = np.sqrt(np.diagonal(r["cov"][s]))
+        out.append(dict(dep=dep, names=list(labels), n=int(r["n"][s]), masked=int(r["masked"][s]), mean=r["mean"][s].copy(), std=std,
+                        cov=r["cov"][s].copy(), corr=r["corr"][s].copy(), exact=r["exact"][s] != 0))
     return out[0] if site is None else out

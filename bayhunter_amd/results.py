@@ -277,6 +277,18 @@ def moho_from_storage(datapaths, moho=None, mohovs=4.2, bins=50, engine=None, qu
                           quantiles=quantiles)
 
 
+def covariance_from_storage(datapaths, dep_int=None, moho=None, mohovs=4.2, engine=None):
+    """Mean, covariance and correlation of vs with depth of many sites in one GPU call (bayhunter_amd.posterior.posterior_covariance):
+    datapaths[s] is site s's data directory after save_final_distribution (c_models.npy).  moho: None -- the vs at the depths of
+    dep_int alone; (lo, hi) km or one pair per site, or True for every site's saved priors['z'] -- the Moho depth and the mean
+    crustal vs are appended (rows without a Moho are then left out of the matrix).  Returns one dict per site."""
+    from .posterior import posterior_covariance
+    if moho is True:
+        moho = [tuple(float(v) for v in saved_priors(p)["z"]) for p in datapaths]
+    rows, site = _stack_sites([np.load(op.join(p, "c_models.npy")) for p in datapaths])
+    return posterior_covariance(rows, site=site, dep_int=dep_int, moho=moho, mohovs=mohovs, engine=engine, nsites=len(datapaths))
+
+
 def station_slots(targets_per_station):
     """(rows, missing): every station's targets as a row of slots, one slot per target reference in the order of first
     appearance, None where the station lacks it; missing = some station lacks a slot (SiteTargets(missing=True) then)"""
