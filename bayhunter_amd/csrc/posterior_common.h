@@ -1,5 +1,5 @@
-// bayhunter_amd/csrc/posterior_common.h -- what posterior_kernel.hip, posterior_scalars_kernel.hip and posterior_datafit_kernel.hip
-// share: the handle, its device buffers, the work items, the ordered keys and the bin rule.
+// bayhunter_amd/csrc/posterior_common.h -- what posterior_kernel.hip, posterior_scalars_kernel.hip, posterior_datafit_kernel.hip
+// and posterior_features_kernel.hip share: the handle, its device buffers, the work items, the ordered keys and the bin rule.
 #ifndef BH_POSTERIOR_COMMON_H
 #define BH_POSTERIOR_COMMON_H
 
@@ -95,8 +95,9 @@ struct ScalarSet {
     }
 };
 
-// the handle's slot of a set id (include/bh_engine_posterior_datafit.h: MOHO 0, USER 1, DATA 3); -1: no such set
-inline int set_slot(int set) { return set == 0 ? 0 : set == 1 ? 1 : set == 3 ? 2 : -1; }
+// the handle's slot of a set id (include/bh_engine_posterior_datafit.h: MOHO 0, USER 1, DATA 3; include/bh_engine_posterior_features.h:
+// FEATURES 4); -1: no such set
+inline int set_slot(int set) { return set == 0 ? 0 : set == 1 ? 1 : set == 3 ? 2 : set == 4 ? 3 : -1; }
 
 } // namespace bhpost
 
@@ -113,7 +114,7 @@ struct bh_posterior {
     bool keep_rows = false;               // bh_posterior_keep_rows: the next load keeps porig and pzd
     bool has_rows = false;                // ... and the last one did
     bhpost::Dev porig, pzd;               // the row's index in the loaded input; zd_j in the row's dtype (the scalar sets)
-    bhpost::ScalarSet sets[3];            // BH_SCALARS_MOHO, BH_SCALARS_USER, BH_SCALARS_DATA (bhpost::set_slot)
+    bhpost::ScalarSet sets[4];            // BH_SCALARS_MOHO, BH_SCALARS_USER, BH_SCALARS_DATA, BH_SCALARS_FEATURES (bhpost::set_slot)
     int data_ldy = 0;                     // bh_posterior_data_fill: the columns of the set being filled, the rows filled so far,
     int64_t data_filled = -1;             // (-1: no fill under way) and the failed rows per site
     bhpost::Dev data_failed;

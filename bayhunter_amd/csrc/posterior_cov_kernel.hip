@@ -13,6 +13,7 @@
 // The finished numbers are formed on the host with 128-bit integers (bh_posterior_cov_finish).
 #include "posterior_common.h"
 #include "../../include/bh_engine_posterior_cov.h"
+#include "../../include/bh_engine_posterior_features.h"
 
 #include <algorithm>
 #include <climits>
@@ -346,15 +347,17 @@ int bh_posterior_cov(bh_posterior *p, int D, const double *dep, int set, int Qc,
             return pfail(p, BH_EINVAL, "depth grid must be finite and strictly ascending");
     const ScalarSet *ss = nullptr;
     if (Qc) {
-        if (set != BH_SCALARS_MOHO && set != BH_SCALARS_USER) return pfail(p, BH_EINVAL, "scalar columns come from BH_SCALARS_MOHO or BH_SCALARS_USER");
+        if (set != BH_SCALARS_MOHO && set != BH_SCALARS_USER && set != BH_SCALARS_FEATURES)
+            return pfail(p, BH_EINVAL, "scalar columns come from BH_SCALARS_MOHO or BH_SCALARS_USER (or BH_SCALARS_FEATURES)");
         if (!p->has_rows) return pfail(p, BH_EINVAL, "the rows were loaded without bh_posterior_keep_rows");
         ss = &p->sets[set_slot(set)];
         if (ss->Q < 1)
-            return pfail(p, BH_EINVAL, set == BH_SCALARS_MOHO ? "the MOHO set does not exist yet (bh_posterior_moho)"
-                                                             : "the USER set does not exist yet (bh_posterior_attach)");
+            return pfail(p, BH_EINVAL, set == BH_SCALARS_MOHO   ? "the MOHO set does not exist yet (bh_posterior_moho)"
+                                       : set == BH_SCALARS_USER ? "the USER set does not exist yet (bh_posterior_attach)"
+                                                                : "the FEATURES set does not exist yet (bh_posterior_features)");
         for (int q = 0; q < Qc; ++q)
             if (cols[q] < 0 || cols[q] >= ss->Q) return pfail(p, BH_EINVAL, "column out of range");
-    } else if (set != -1 && set != BH_SCALARS_MOHO && set != BH_SCALARS_USER) {
+    } else if (set != -1 && set != BH_SCALARS_MOHO && set != BH_SCALARS_USER && set != BH_SCALARS_FEATURES) {
         return pfail(p, BH_EINVAL, "no such scalar set");
     }
     const int S = p->S, P = D + Qc;

@@ -395,7 +395,8 @@ int get_set(bh_posterior *p, int set, ScalarSet **out)
     if (p->sets[slot].Q < 1)
         return pfail(p, BH_EINVAL, slot == 0   ? "the MOHO set does not exist yet (bh_posterior_moho)"
                                    : slot == 1 ? "the USER set does not exist yet (bh_posterior_attach)"
-                                               : "the DATA set does not exist yet (bh_posterior_data_fill over all rows)");
+                                   : slot == 2 ? "the DATA set does not exist yet (bh_posterior_data_fill over all rows)"
+                                               : "the FEATURES set does not exist yet (bh_posterior_features)");
     *out = &p->sets[slot];
     return BH_OK;
 }

@@ -122,12 +122,6 @@ class _DataLoaded(_Loaded):
                                                        _ptr(ncol), _ptr(failed)))
         return failed
 
-    def gather(self, which, pos, Q):
-        pos = np.ascontiguousarray(pos, np.int64)
-        out = np.zeros((pos.size, Q))
-        self.eng._check(self._L.bh_posterior_scalar_gather(self._p, which, pos.size, _ptr(pos), _ptr(out)))
-        return out
-
 
 class _Clock(object):
     """seconds per phase into a dict (tools/gpu_posterior_datafits_perf.py), the device drained at every lap; nothing without one"""

@@ -719,6 +719,18 @@ class DeviceChains(object):
                                nsites=self.nsites, quantiles=quantiles)
         return r if self.sites is not None else r[0]
 
+    def posterior_features(self, features, bins=50, phase="p2", cold_only=None, exclude_chains=(), quantiles=None):
+        """record="device": bayhunter_amd.posterior_features of every site's recorded rows, straight from the device store (one dict
+        per site; one dict without SiteTargets): the posteriors of structural features of the layered models -- features: name ->
+        (kind, z0, z1[, c]), every number one value or one per site.  cold_only (default: True on tempered runs) and
+        exclude_chains as in samples_dev().  quantiles: as posterior_features'."""
+        from .posterior import posterior_features
+        d = self._posterior_rows(phase, cold_only, exclude_chains)
+        with self.torch.cuda.device(self.dev):
+            r = posterior_features(d["models2d"], features, site=d["site"], bins=bins, quantiles=quantiles, engine=self.engine,
+                                   nsites=self.nsites)
+        return r if self.sites is not None else r[0]
+
     def posterior_scalars(self, bins=20, nlayers=True, phase="p2", cold_only=None, exclude_chains=(), quantiles=None):
         """record="device": bayhunter_amd.posterior_scalars of every site's recorded rows with the store's likes, vpvs, misfits
         [nt+1] and noise [2nt] as columns (slot layout), straight from the device store (one dict per site; one dict without
@@ -734,12 +746,14 @@ class DeviceChains(object):
                                   nsites=self.nsites, quantiles=quantiles)
         return r if self.sites is not None else r[0]
 
-    def posterior_covariance(self, dep_int=None, scalars=(), moho=None, mohovs=4.2, phase="p2", cold_only=None, exclude_chains=()):
+    def posterior_covariance(self, dep_int=None, scalars=(), moho=None, mohovs=4.2, phase="p2", cold_only=None, exclude_chains=(),
+                             features=None):
         """record="device": bayhunter_amd.posterior_covariance of every site's recorded rows, straight from the device store (one
         dict per site; one dict without SiteTargets): mean, covariance and correlation of vs at the depths of dep_int.  scalars:
         names of the store's columns to put beside the depths -- likes, vpvs, misfits [nt+1] and noise [2nt], as
         posterior_scalars() takes them; or moho = (lo, hi) (True: every site's own priors['z']) with mohovs for the Moho depth and
-        the mean crustal vs -- one of the two.  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        the mean crustal vs; or features: name -> (kind, z0, z1[, c]) as posterior_features() takes them -- one of the three.  cold_only
+        (default: True on tempered runs) and exclude_chains as in samples_dev()."""
         from .posterior import posterior_covariance
         d = self._posterior_rows(phase, cold_only, exclude_chains)
         n = d["models2d"].shape[0]
@@ -754,7 +768,7 @@ class DeviceChains(object):
             moho = [tuple(float(v) for v in p["z"]) for p in self.site_priors]
         with self.torch.cuda.device(self.dev):
             r = posterior_covariance(d["models2d"], site=d["site"], dep_int=dep_int, columns=cols, moho=moho, mohovs=mohovs,
-                                     engine=self.engine, nsites=self.nsites)
+                                     engine=self.engine, nsites=self.nsites, features=features)
         return r if self.sites is not None else r[0]
 
     def posterior_datafits(self, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), phase="p2", cold_only=None, exclude_chains=()):

@@ -220,6 +220,9 @@ def load_library():
     L.bh_posterior_cov_finish.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in POSTERIOR_COV_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_posterior_features.argtypes = [vp, C.c_int, vp, vp, vp]
+    for name in POSTERIOR_FEATURES_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     L.bh_chain_diag_series.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int,
                                        vp, vp, vp, vp, vp, vp, vp]
     L.bh_chain_diag_models.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
@@ -311,6 +314,14 @@ POSTERIOR_QUANTILES_SYMBOLS = ("bh_posterior_column_quantiles",)
 POSTERIOR_COV_SYMBOLS = ("bh_posterior_cov", "bh_posterior_cov_finish")
 COV_MAXCOLS = 256                   # BH_COV_MAXCOLS
 COV_LIMB_BITS = 14                  # BH_COV_LIMB_BITS
+# include/bh_engine_posterior_features.h: structural features of the layered models as a scalar set
+# (bayhunter_amd/posterior.py: posterior_features)
+POSTERIOR_FEATURES_SYMBOLS = ("bh_posterior_features",)
+SCALARS_FEATURES = 4                # BH_SCALARS_FEATURES
+SCALARS_MAXCOLS = 64                # BH_SCALARS_MAXCOLS
+FEATURES_MAXKINDS = 64              # BH_FEATURES_MAXKINDS
+(FEATURE_VSMEAN, FEATURE_VSTIME, FEATURE_TTS, FEATURE_VSMIN, FEATURE_VSMAX, FEATURE_DROP, FEATURE_JUMP, FEATURE_ABOVE,
+ FEATURE_NIFACES) = range(9)        # BH_FEATURE_*
 # include/bh_engine_chain_diag.h: the sums behind split R-hat and ESS of the chains' recorded series, and the medians of the
 # outlier rule (bayhunter_amd/diagnostics.py)
 CHAIN_DIAG_SYMBOLS = ("bh_chain_diag_series", "bh_chain_diag_models", "bh_chain_diag_medians")

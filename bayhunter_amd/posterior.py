@@ -15,6 +15,11 @@ depth, crustal vs and any scalar column attached to the rows, with the same exac
 
 `posterior_covariance` (include/bh_engine_posterior_cov.h) returns per site the mean vector and the covariance and correlation
 matrices of the vs at the depths of dep_int, and of scalar columns beside them: how the depths of a profile vary together.
+
+`posterior_features` (include/bh_engine_posterior_features.h) returns per site the posteriors of structural features of the
+layered models themselves -- layer averages and travel times of a depth window, its slowest and fastest layer, its strongest
+velocity drop and jump, the first interface above a velocity, the number of interfaces -- each with the statistics of
+posterior_scalars and, where a feature may be absent, the posterior probability that it is there.
 """
 import ctypes as C
 import math
@@ -336,6 +341,25 @@ class _Loaded(object):
         if values.shape[0] != self.N:
             raise ValueError("one value row per model row")
         self.eng._check(self._L.bh_posterior_attach(self._p, mem, stream, elem, values.shape[1], ld, ptr, int(bool(nlayers))))
+
+    def features(self, kinds, par):
+        """bh_posterior_features: kinds int32 [F], par float64 [S, F, 3] (check_features) -> found int64 [S, ncols]"""
+        kinds = np.ascontiguousarray(kinds, np.int32)
+        par = np.ascontiguousarray(par, np.float64)
+        if par.shape != (self.S, kinds.size, 3):
+            raise ValueError("par must be [nsites][F][3]")
+        if kinds.size and not (0 <= kinds.min() and kinds.max() < len(FEATURE_KINDS)):
+            raise ValueError("kinds must be BH_FEATURE_* numbers")
+        found = np.zeros((self.S, sum(FEATURE_COLS[FEATURE_KINDS[k]] for k in kinds)), np.int64)
+        self.eng._check(self._L.bh_posterior_features(self._p, kinds.size, _ptr(kinds), _ptr(par), _ptr(found)))
+        return found
+
+    def gather(self, which, pos, Q):
+        """the values [len(pos), Q] of the loaded rows at the positions pos of a set of Q columns (bh_posterior_scalar_gather)"""
+        pos = np.ascontiguousarray(pos, np.int64)
+        out = np.zeros((pos.size, Q))
+        self.eng._check(self._L.bh_posterior_scalar_gather(self._p, which, pos.size, _ptr(pos), _ptr(out)))
+        return out
 
     def scalar_stats(self, which, median=True):
         q = np.zeros(1, np.int32)
@@ -754,34 +778,41 @@ def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=
 # ---- covariance and correlation of vs with depth (include/bh_engine_posterior_cov.h) ---------------------------------------
 
 def posterior_covariance(models, site=None, dep_int=None, columns=None, moho=None, mohovs=MOHOVS, moho_columns=("moho", "vscrust"),
-                         engine=None, nsites=None):
+                         engine=None, nsites=None, features=None):
     """How a site's profile varies together: a list of dicts (one dict when site is None) with the mean vector and the
     population covariance (ddof = 0, as std everywhere in this package) and correlation matrices of P columns -- the vs at the
     depths of dep_int (default 0..100 km in 0.5 km steps; an empty dep_int leaves them out), then scalar columns of ONE set:
     columns: as posterior_scalars', name -> [N] or [N, k] values, one row per model row (a [N, k] column gives the labels
       name[0] .. name[k-1]); or
     moho = (lo, hi) km, or one pair per site, with mohovs: as posterior_moho's -- the columns named by moho_columns (of moho,
-      vslast, vscrust, vsjump) are appended.
-    columns and moho together is a ValueError: one call takes its scalar columns from one set.  A row with NaN in any of the
-    scalar columns (a row without a Moho) is left out of the whole matrix (listwise deletion: the matrix stays a covariance).
+      vslast, vscrust, vsjump) are appended; or
+    features: as posterior_features', name -> (kind, z0, z1[, c]) -- every feature's columns are appended under the labels name,
+      or name.value / name.depth / name.jump for the kinds of two columns.
+    Two of columns, moho and features together is a ValueError: one call takes its scalar columns from one set.  A row with NaN
+    in any of the scalar columns (a row without a Moho, without the drop asked for) is left out of the whole matrix (listwise
+    deletion: the matrix stays a covariance).
     Keys: dep, names (the P labels: the depths, then the column names), n (the rows used), masked (the rows left out), mean [P],
     std [P] (the square root of cov's diagonal), cov [P, P], corr [P, P], exact [P] (bool: the column's values went into the
     integer sums without rounding).  corr is NaN in the row and column of a constant column, as numpy.corrcoef leaves it; a site
     without rows used has NaN everywhere.  The numbers are functions of exact integer sums formed on the device: the same bits
     alone or among other sites, in any row order, on every repeat; each within 1 ulp of the exact rational.  The caller who wants
     ddof = 1 multiplies cov by n / (n - 1)."""
-    if columns is not None and moho is not None:
-        raise ValueError("one call takes its scalar columns from one set: give columns or moho, not both")
+    if sum(v is not None for v in (columns, moho, features)) > 1:
+        raise ValueError("one call takes its scalar columns from one set: give columns, moho or features, not two of them")
     dep = default_dep_int() if dep_int is None else np.ascontiguousarray(dep_int, np.float64).reshape(-1)
     if moho is not None:
         bad = [c for c in moho_columns if c not in MOHO_COLUMNS]
         if bad or not len(moho_columns):
             raise ValueError("moho_columns must name some of %r" % (MOHO_COLUMNS,))
-    ld = _Loaded(models, site, engine, nsites, scalars=columns is not None or moho is not None)
+    ld = _Loaded(models, site, engine, nsites, scalars=columns is not None or moho is not None or features is not None)
     try:
         S = ld.S
         which, cols, names = -1, [], []
-        if columns is not None:
+        if features is not None:
+            kinds, par, names = check_features(features, S)
+            ld.features(kinds, par)
+            which, cols = E.SCALARS_FEATURES, list(range(len(names)))
+        elif columns is not None:
             values, layout = _stack_columns(columns, ld.N)
             if values is not None:
                 ld.attach(values, False)
@@ -804,4 +835,155 @@ def posterior_covariance(models, site=None, dep_int=None, columns=None, moho=Non
             std = np.sqrt(np.diagonal(r["cov"][s]))
         out.append(dict(dep=dep, names=list(labels), n=int(r["n"][s]), masked=int(r["masked"][s]), mean=r["mean"][s].copy(), std=std,
                         cov=r["cov"][s].copy(), corr=r["corr"][s].copy(), exact=r["exact"][s] != 0))
+    return out[0] if site is None else out
+
+
+# ---- structural features of the layered models (include/bh_engine_posterior_features.h) ------------------------------------
+
+FEATURE_KINDS = ("vsmean", "vstime", "tts", "vsmin", "vsmax", "drop", "jump", "above", "nifaces")   # BH_FEATURE_*, in order
+FEATURE_COLS = dict(vsmean=1, vstime=1, tts=1, vsmin=2, vsmax=2, drop=2, jump=2, above=1, nifaces=1)
+FEATURE_PARTS = dict(vsmin=("value", "depth"), vsmax=("value", "depth"), drop=("depth", "jump"), jump=("depth", "jump"))
+FEATURE_OPTIONAL = ("drop", "jump", "above")   # a row may lack them: they carry a probability
+_RESULT_KEYS = ("rows", "invalid_rows", "dropped")
+
+
+def check_features(features, S):
+    """The user's dict name -> (kind, z0, z1[, c]) as (kinds int32 [F], par float64 [S, F, 3], labels [ncols]) for
+    bh_posterior_features over S sites.  kind is one of FEATURE_KINDS; z0 < z1 (km) is the depth window; c is the threshold of
+    drop and jump (km/s, >= 0, default 0) and the velocity of above (needed there); the other kinds take no c.  Every number is a
+    scalar or a sequence of one value per site.  labels: the name for a kind of one column, name.value, name.depth (vsmin,
+    vsmax) or name.depth, name.jump (drop, jump) for a kind of two.  Pure host code; every refused input is a ValueError that names
+    the feature (and the site, where one site's value is at fault)."""
+    if not isinstance(features, dict) or not features:
+        raise ValueError("features must be a dict name -> (kind, z0, z1[, c]) with at least one entry")
+    if len(features) > E.FEATURES_MAXKINDS:
+        raise ValueError("features: %d features, a call takes at most %d" % (len(features), E.FEATURES_MAXKINDS))
+    S = int(S)
+    kinds, labels = [], []
+    par = np.zeros((S, len(features), 3))
+    for f, (name, spec) in enumerate(features.items()):
+        if not isinstance(name, str) or not name:
+            raise ValueError("feature %r: the name must be a non-empty string" % (name,))
+        if name in _RESULT_KEYS:
+            raise ValueError("feature %r: the name is a key of the result itself: give the feature another name" % (name,))
+        if isinstance(spec, (str, bytes)) or not hasattr(spec, "__len__") or len(spec) not in (3, 4):
+            raise ValueError("feature %r: expected (kind, z0, z1) or (kind, z0, z1, c)" % (name,))
+        kind = spec[0]
+        if not isinstance(kind, str) or kind not in FEATURE_KINDS:
+            raise ValueError("feature %r: unknown kind %r (one of %s)" % (name, kind, ", ".join(FEATURE_KINDS)))
+        if len(spec) == 4 and kind not in FEATURE_OPTIONAL:
+            raise ValueError("feature %r: kind %r takes no c" % (name, kind))
+        if len(spec) == 3 and kind == "above":
+            raise ValueError("feature %r: kind 'above' needs c, the velocity to exceed" % (name,))
+        vals = list(spec[1:]) + ([0.0] if len(spec) == 3 else [])
+        for i, (what, v) in enumerate(zip(("z0", "z1", "c"), vals)):
+            try:
+                v = np.asarray(v, np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("feature %r: %s must be a number or one number per site" % (name, what))
+            if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != S):
+                raise ValueError("feature %r: %s must be one number or one per site (%d sites), not shape %r" % (name, what, S, v.shape))
+            par[:, f, i] = v
+        for s in range(S):
+            z0, z1, c = par[s, f]
+            at = "feature %r, site %d" % (name, s)
+            if not (np.isfinite(z0) and np.isfinite(z1) and np.isfinite(c)):
+                raise ValueError("%s: z0, z1 and c must be finite" % at)
+            if z0 < 0:
+                raise ValueError("%s: z0 = %r lies below 0 km" % (at, z0))
+            if not z1 > z0:
+                raise ValueError("%s: the window needs z0 < z1, not [%r, %r]" % (at, z0, z1))
+            if kind in ("drop", "jump") and c < 0:
+                raise ValueError("%s: c = %r must not be negative (a %s is asked for by its size)" % (at, c, kind))
+        kinds.append(FEATURE_KINDS.index(kind))
+        labels += ["%s.%s" % (name, part) for part in FEATURE_PARTS[kind]] if kind in FEATURE_PARTS else [name]
+    if len(labels) > E.SCALARS_MAXCOLS:
+        raise ValueError("features: %d columns (feature %r is the first too many), a call takes at most %d (BH_SCALARS_MAXCOLS)"
+                         % (len(labels), labels[E.SCALARS_MAXCOLS].split(".")[0], E.SCALARS_MAXCOLS))
+    return np.array(kinds, np.int32), par, labels
+
+
+def posterior_features(models, features, site=None, bins=50, quantiles=None, engine=None, nsites=None):
+    """The posterior of structural features of every site's layered models: a list of dicts (one dict when site is None).
+    features: a dict name -> (kind, z0, z1[, c]); every number a scalar or a sequence of one value per site.  With the row's step
+    model (layer j from the interface above it to the one below, the last to infinity) and the window [z0, z1] km, the kinds are
+      vsmean   the thickness-weighted mean vs of the window            vstime  its time-averaged vs (z1 - z0) / tts (Vs30-style)
+      tts      the vertical S travel time through the window (s)       nifaces the number of interfaces inside the window
+      vsmin, vsmax  the slowest / fastest layer of the window: value and the depth where it starts inside the window
+      drop, jump    the strongest velocity decrease / increase across an interface inside the window, where it exceeds c (>= 0,
+                    default 0): depth and jump; a row without one has no value
+      above    the first interface inside the window below which vs exceeds c (sediment thickness with c a basement velocity; the
+               Moho rule with the Moho's parameters): depth
+    (the exact rules: include/bh_engine_posterior_features.h).  The dict holds rows, invalid_rows and dropped as posterior_moho's,
+    and per feature name a statistics dict for a kind of one column -- count, nan, median, mean, std, min, max, constant, hist =
+    (counts, edges), mode, and quantiles [R] where asked, as posterior_scalars' (edges: numpy.histogram_bin_edges(data, bins);
+    nifaces arange(min, max + 2) - 0.5) -- and for a kind of two {"depth": statistics, "value" | "jump": statistics, "hist2d":
+    (counts [bins, bins], xedges of the value or jump, yedges of the depth), "mode": (value or jump, depth), the centres of the first
+    largest cell}.  drop, jump and above add probability = count / rows: the posterior probability that the station has such a
+    feature (NaN for a site without rows)."""
+    qs = check_quantiles(quantiles)
+    ld = _Loaded(models, site, engine, nsites, scalars=True)
+    try:
+        S = ld.S
+        kinds, par, labels = check_features(features, S)
+        ld.features(kinds, par)
+        W = E.SCALARS_FEATURES
+        st = ld.scalar_stats(W)
+        qv = set_quantiles(ld, W, st["count"], qs) if qs is not None else None
+        Q = len(labels)
+        colkind = [FEATURE_KINDS[k] for k in kinds for _ in range(FEATURE_COLS[FEATURE_KINDS[k]])]
+        edges = [[scalar_edges(st["min"][s, q], st["max"][s, q], np.float64, bins, colkind[q] == "nifaces")
+                  if st["count"][s, q] else scalar_edges(None, None, np.float64, bins) for s in range(S)] for q in range(Q)]
+        hists = [ld.scalar_hist(W, q, edges[q]) for q in range(Q)]
+        e2, h2 = {}, {}
+        q = 0
+        for k in kinds:
+            kind = FEATURE_KINDS[k]
+            if kind in FEATURE_PARTS:
+                qx, qy = (q, q + 1) if FEATURE_PARTS[kind][0] != "depth" else (q + 1, q)     # x: value or jump, y: depth
+                both = [bool(st["count"][s, qx]) and bool(st["count"][s, qy]) for s in range(S)]
+                e2[q] = [[moho_edges(st["min"][s, c], st["max"][s, c], bins) if both[s] else moho_edges(None, None, bins)
+                          for s in range(S)] for c in (qx, qy)]
+                h2[q] = ld.scalar_hist2d(W, qx, qy, e2[q][0], e2[q][1])
+            q += FEATURE_COLS[kind]
+    finally:
+        ld.close()
+
+    def stats(s, q):
+        d = _stat_dict(st, s, q)
+        n = int(st["count"][s, q])
+        e = edges[q][s]
+        cnt = hists[q][s].astype(np.int64)
+        d.update(count=n, nan=int(st["nan"][s, q]), constant=bool(n and st["min"][s, q] == st["max"][s, q]), hist=(cnt, e),
+                 mode=((e[:-1] + e[1:]) / 2.)[np.argmax(cnt)] if n else np.nan)
+        if qs is not None:
+            d["quantiles"] = qv[s, q].copy()
+        return d
+
+    out = []
+    for s in range(S):
+        rows = int(ld.rows[s])
+        r = dict(rows=rows, invalid_rows=int(ld.invalid[s]), dropped=ld.dropped)
+        q = 0
+        for name, k in zip(features, kinds):
+            kind = FEATURE_KINDS[k]
+            if kind in FEATURE_PARTS:
+                d = {part: stats(s, q + i) for i, part in enumerate(FEATURE_PARTS[kind])}
+                counts, am = h2[q]
+                xe, ye = e2[q][0][s], e2[q][1][s]
+                d["hist2d"] = (counts[s].astype(np.int64), xe, ye)
+                if counts[s].any():
+                    xi, yi = divmod(int(am[s]), ye.size - 1)
+                    d["mode"] = (((xe[:-1] + xe[1:]) / 2.)[xi], ((ye[:-1] + ye[1:]) / 2.)[yi])
+                else:
+                    d["mode"] = (np.nan, np.nan)
+                n = d["depth"]["count"]
+            else:
+                d = stats(s, q)
+                n = d["count"]
+            if kind in FEATURE_OPTIONAL:
+                d["probability"] = n / rows if rows else np.nan
+            r[name] = d
+            q += FEATURE_COLS[kind]
+        out.append(r)
     return out[0] if site is None else out

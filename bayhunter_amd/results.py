@@ -277,6 +277,16 @@ def moho_from_storage(datapaths, moho=None, mohovs=4.2, bins=50, engine=None, qu
                           quantiles=quantiles)
 
 
+def features_from_storage(datapaths, features, bins=50, engine=None, quantiles=None):
+    """Posteriors of structural features of the layered models of many sites in one GPU call
+    (bayhunter_amd.posterior.posterior_features): datapaths[s] is site s's data directory after save_final_distribution
+    (c_models.npy).  features: name -> (kind, z0, z1[, c]), every number one value or one per site; bins and quantiles as
+    posterior_features'.  Returns one dict per site."""
+    from .posterior import posterior_features
+    rows, site = _stack_sites([np.load(op.join(p, "c_models.npy")) for p in datapaths])
+    return posterior_features(rows, features, site=site, bins=bins, quantiles=quantiles, engine=engine, nsites=len(datapaths))
+
+
 def covariance_from_storage(datapaths, dep_int=None, moho=None, mohovs=4.2, engine=None):
     """Mean, covariance and correlation of vs with depth of many sites in one GPU call (bayhunter_amd.posterior.posterior_covariance):
     datapaths[s] is site s's data directory after save_final_distribution (c_models.npy).  moho: None -- the vs at the depths of

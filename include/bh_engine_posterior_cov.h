@@ -8,7 +8,7 @@
  * tomography node needs beside the mean profile.
  *
  * Columns.  0..D-1 are the vs at dep[0..D) (bh_posterior_columns' sampling); D.. are the columns cols[0..Qc) of the set `set`
- * (BH_SCALARS_MOHO or BH_SCALARS_USER; -1 with Qc = 0 for none).  A row with NaN in ANY chosen scalar column is left out of the
+ * (BH_SCALARS_MOHO, BH_SCALARS_USER or BH_SCALARS_FEATURES of bh_engine_posterior_features.h; -1 with Qc = 0 for none).  A row with NaN in ANY chosen scalar column is left out of the
  * WHOLE matrix (listwise deletion: the matrix stays symmetric and positive semidefinite): n[site] rows are used, masked[site]
  * left out.  Scalar columns need rows loaded under bh_posterior_keep_rows, as the sets do.
  *
@@ -48,13 +48,13 @@ extern "C" {
 #define BH_COV_MAXCELLS (1u << 24)   /* nsites * P (P + 1) / 2 of one call */
 #define BH_COV_MAXROWS ((1 << 24) - 1) /* rows used per site: n < 2^24 keeps N_ij below 2^104 */
 
-/* dep: host [D], finite, strictly ascending (D may be 0).  set: BH_SCALARS_MOHO / BH_SCALARS_USER, or -1 with Qc = 0.  cols: host
+/* dep: host [D], finite, strictly ascending (D may be 0).  set: BH_SCALARS_MOHO / BH_SCALARS_USER / BH_SCALARS_FEATURES, or -1 with Qc = 0.  cols: host
  * [Qc], each a column of the set.  1 <= D + Qc <= BH_COV_MAXCOLS.  Outputs, all host, any may be NULL:
  *   n, masked: int64 [nsites]                        L: int32 [nsites][P]    x0: int64 [nsites][P]    exact: int32 [nsites][P]
  *   s: uint64 [nsites][P]                            raw: uint64 [nsites][P (P + 1) / 2][3], pairs i <= j row-major
  *   mean: float64 [nsites][P]                        cov, corr: float64 [nsites][P][P], full and symmetric
  * BH_EINVAL: a handle without loaded rows, D or Qc negative, P outside 1 .. BH_COV_MAXCOLS, a null dep or cols where needed, a dep
- * that is not finite and strictly ascending, a set that is not MOHO / USER or was not formed, set -1 with Qc > 0, a column outside
+ * that is not finite and strictly ascending, a set that is not MOHO / USER / FEATURES or was not formed, set -1 with Qc > 0, a column outside
  * the set, scalar columns on rows loaded without bh_posterior_keep_rows, nsites * P (P + 1) / 2 above BH_COV_MAXCELLS, a value
  * that is not finite.  BH_EUNSUPPORTED: more than BH_COV_MAXROWS rows of one site. */
 int bh_posterior_cov(bh_posterior *p, int D, const double *dep, int set, int Qc, const int32_t *cols, int64_t *n,
