@@ -1,5 +1,5 @@
-// bayhunter_amd/csrc/posterior_common.h -- what posterior_kernel.hip, posterior_scalars_kernel.hip, posterior_datafit_kernel.hip
-// and posterior_features_kernel.hip share: the handle, its device buffers, the work items, the ordered keys and the bin rule.
+// bayhunter_amd/csrc/posterior_common.h -- what posterior_kernel.hip, posterior_scalars_kernel.hip, posterior_datafit_kernel.hip,
+// posterior_features_kernel.hip and posterior_classes_kernel.hip share: the handle, its device buffers, the work items, the ordered keys and the bin rule.
 #ifndef BH_POSTERIOR_COMMON_H
 #define BH_POSTERIOR_COMMON_H
 

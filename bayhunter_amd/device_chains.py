@@ -682,60 +682,113 @@ class DeviceChains(object):
             cold_only = self.ladder is not None
         return self.samples_dev(phase, cold_only=cold_only, exclude_chains=exclude_chains)
 
-    def posterior_models(self, dep_int=None, quantiles=None, phase="p2", cold_only=None, exclude_chains=()):
+    def _class_rows(self, classes, phase, cold_only, exclude_chains):
+        """classes= of the posterior_* methods: the dict must stem from the same selection of the store's rows"""
+        if classes is None:
+            return None
+        if cold_only is None:
+            cold_only = self.ladder is not None
+        sel = (phase, bool(cold_only), tuple(int(c) for c in np.atleast_1d(np.asarray(exclude_chains, dtype=np.int64))))
+        if not isinstance(classes, dict) or "selection" not in classes:
+            raise ValueError("classes must be the dict DeviceChains.posterior_classes returned")
+        if tuple(classes["selection"]) != sel:
+            raise ValueError("classes was formed with (phase, cold_only, exclude_chains) = %r, this call asks for %r: classify "
+                             "the same rows" % (tuple(classes["selection"]), sel))
+        return classes
+
+    def posterior_classes(self, classes, features=None, moho=None, mohovs=4.2, scalars=(), phase="p2", cold_only=None, exclude_chains=()):
+        """record="device": bayhunter_amd.posterior_classes of every site's recorded rows where they lie in the device store: every
+        row's class by a rule over its scalar columns -- classes: name -> list of (label, lo, hi), (label, "has"), (label, "lacks"),
+        the first class that holds taking the row.  Labels: those of features (name -> (kind, z0, z1[, c])); "moho", "vslast",
+        "vscrust", "vsjump" with moho = (lo, hi) (True: every site's own priors['z']) and mohovs; and of scalars, names of the store's
+        columns as posterior_covariance() takes them -- "likes", "vpvs", "misfits[i]", "noise[i]" -- and "nlayers".  cold_only
+        (default: True on tempered runs) and exclude_chains as in samples_dev().  The dict (cls, counts, probability, ...: see
+        bayhunter_amd.posterior_classes; cls and site are device tensors over the rows of samples_dev()) remembers the selection
+        (phase, cold_only, exclude_chains); classes= of the posterior_* methods takes it with the same selection only."""
+        from .posterior import posterior_classes
+        d = self._posterior_rows(phase, cold_only, exclude_chains)
+        n = d["models2d"].shape[0]
+        shapes = dict(likes=(n,), vpvs=(n,), misfits=(n, self.nt + 1), noise=(n, 2 * self.nt))
+        if isinstance(scalars, str):
+            scalars = (scalars,)
+        unknown = [k for k in scalars if k not in shapes and k != "nlayers"]
+        if unknown:
+            raise ValueError("scalars: %r is no column of the store (%s, nlayers)" % (unknown[0], ", ".join(shapes)))
+        cols = {k: d[k].reshape(shapes[k]) for k in scalars if k != "nlayers"}
+        if moho is True:
+            moho = [tuple(float(v) for v in p["z"]) for p in self.site_priors]
+        with self.torch.cuda.device(self.dev):
+            r = posterior_classes(d["models2d"], classes, site=d["site"], features=features, moho=moho, mohovs=mohovs,
+                                  columns=cols or None, nlayers="nlayers" in scalars, engine=self.engine, nsites=self.nsites)
+        if cold_only is None:
+            cold_only = self.ladder is not None
+        r["selection"] = (phase, bool(cold_only), tuple(int(c) for c in np.atleast_1d(np.asarray(exclude_chains, dtype=np.int64))))
+        return r
+
+    def posterior_models(self, dep_int=None, quantiles=None, phase="p2", cold_only=None, exclude_chains=(), classes=None):
         """record="device": bayhunter_amd.posterior_models of every site's recorded rows, straight from the device store (one dict
         per site; one dict without SiteTargets): mean, median, minmax, stdminmax, mode and -- the joint misfit misfits[..., -1]
         being in the store -- minmisfit of vs against depth; quantiles (numbers in [0, 1]) adds the credible band `quantiles`.
-        cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        cold_only (default: True on tempered runs) and exclude_chains as in samples_dev().  classes: the dict
+        posterior_classes() returned for the same phase, cold_only and exclude_chains: per site a dict class name -> that dict."""
+        classes = self._class_rows(classes, phase, cold_only, exclude_chains)
         from .posterior import posterior_models
         d = self._posterior_rows(phase, cold_only, exclude_chains)
         n = d["models2d"].shape[0]
         with self.torch.cuda.device(self.dev):
             r = posterior_models(d["models2d"], site=d["site"], dep_int=dep_int, misfits=d["misfits"][..., -1].reshape(n),
-                                 engine=self.engine, nsites=self.nsites, quantiles=quantiles)
+                                 engine=self.engine, nsites=self.nsites, quantiles=quantiles, classes=classes)
         return r if self.sites is not None else r[0]
 
-    def posterior_hist2d(self, dep_int=None, vs_edges=None, dep_edges=None, phase="p2", cold_only=None, exclude_chains=()):
+    def posterior_hist2d(self, dep_int=None, vs_edges=None, dep_edges=None, phase="p2", cold_only=None, exclude_chains=(), classes=None):
         """record="device": bayhunter_amd.posterior_hist2d of every site's recorded rows, straight from the device store (one dict
         per site; one dict without SiteTargets): the 2-D posterior plot's vs-depth histogram and the histogram of interface
-        depths.  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        depths.  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev().  classes: the dict
+        posterior_classes() returned for the same phase, cold_only and exclude_chains: per site a dict class name -> that dict."""
+        classes = self._class_rows(classes, phase, cold_only, exclude_chains)
         from .posterior import posterior_hist2d
         d = self._posterior_rows(phase, cold_only, exclude_chains)
         with self.torch.cuda.device(self.dev):
             r = posterior_hist2d(d["models2d"], site=d["site"], dep_int=dep_int, vs_edges=vs_edges, dep_edges=dep_edges,
-                                 engine=self.engine, nsites=self.nsites)
+                                 engine=self.engine, nsites=self.nsites, classes=classes)
         return r if self.sites is not None else r[0]
 
-    def posterior_moho(self, moho=None, mohovs=4.2, bins=50, phase="p2", cold_only=None, exclude_chains=(), quantiles=None):
+    def posterior_moho(self, moho=None, mohovs=4.2, bins=50, phase="p2", cold_only=None, exclude_chains=(), quantiles=None, classes=None):
         """record="device": bayhunter_amd.posterior_moho of every site's recorded rows, straight from the device store (one dict
         per site; one dict without SiteTargets).  moho None: every site's own priors['z'], the reference's default.  cold_only
-        (default: True on tempered runs) and exclude_chains as in samples_dev().  quantiles: as posterior_moho's."""
+        (default: True on tempered runs) and exclude_chains as in samples_dev().  quantiles: as posterior_moho's.  classes: the dict
+        posterior_classes() returned for the same phase, cold_only and exclude_chains: per site a dict class name -> that dict."""
+        classes = self._class_rows(classes, phase, cold_only, exclude_chains)
         from .posterior import posterior_moho
         d = self._posterior_rows(phase, cold_only, exclude_chains)
         if moho is None:
             moho = [tuple(float(v) for v in p["z"]) for p in self.site_priors]
         with self.torch.cuda.device(self.dev):
             r = posterior_moho(d["models2d"], site=d["site"], moho=moho, mohovs=mohovs, bins=bins, engine=self.engine,
-                               nsites=self.nsites, quantiles=quantiles)
+                               nsites=self.nsites, quantiles=quantiles, classes=classes)
         return r if self.sites is not None else r[0]
 
-    def posterior_features(self, features, bins=50, phase="p2", cold_only=None, exclude_chains=(), quantiles=None):
+    def posterior_features(self, features, bins=50, phase="p2", cold_only=None, exclude_chains=(), quantiles=None, classes=None):
         """record="device": bayhunter_amd.posterior_features of every site's recorded rows, straight from the device store (one dict
         per site; one dict without SiteTargets): the posteriors of structural features of the layered models -- features: name ->
         (kind, z0, z1[, c]), every number one value or one per site.  cold_only (default: True on tempered runs) and
-        exclude_chains as in samples_dev().  quantiles: as posterior_features'."""
+        exclude_chains as in samples_dev().  quantiles: as posterior_features'.  classes: the dict
+        posterior_classes() returned for the same phase, cold_only and exclude_chains: per site a dict class name -> that dict."""
+        classes = self._class_rows(classes, phase, cold_only, exclude_chains)
         from .posterior import posterior_features
         d = self._posterior_rows(phase, cold_only, exclude_chains)
         with self.torch.cuda.device(self.dev):
             r = posterior_features(d["models2d"], features, site=d["site"], bins=bins, quantiles=quantiles, engine=self.engine,
-                                   nsites=self.nsites)
+                                   nsites=self.nsites, classes=classes)
         return r if self.sites is not None else r[0]
 
-    def posterior_scalars(self, bins=20, nlayers=True, phase="p2", cold_only=None, exclude_chains=(), quantiles=None):
+    def posterior_scalars(self, bins=20, nlayers=True, phase="p2", cold_only=None, exclude_chains=(), quantiles=None, classes=None):
         """record="device": bayhunter_amd.posterior_scalars of every site's recorded rows with the store's likes, vpvs, misfits
         [nt+1] and noise [2nt] as columns (slot layout), straight from the device store (one dict per site; one dict without
         SiteTargets).  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev().  quantiles: as
-        posterior_scalars'."""
+        posterior_scalars'.  classes: the dict
+        posterior_classes() returned for the same phase, cold_only and exclude_chains: per site a dict class name -> that dict."""
+        classes = self._class_rows(classes, phase, cold_only, exclude_chains)
         from .posterior import posterior_scalars
         d = self._posterior_rows(phase, cold_only, exclude_chains)
         n = d["models2d"].shape[0]
@@ -743,17 +796,19 @@ class DeviceChains(object):
                     noise=d["noise"].reshape(n, 2 * self.nt))
         with self.torch.cuda.device(self.dev):
             r = posterior_scalars(d["models2d"], cols, site=d["site"], bins=bins, nlayers=nlayers, engine=self.engine,
-                                  nsites=self.nsites, quantiles=quantiles)
+                                  nsites=self.nsites, quantiles=quantiles, classes=classes)
         return r if self.sites is not None else r[0]
 
     def posterior_covariance(self, dep_int=None, scalars=(), moho=None, mohovs=4.2, phase="p2", cold_only=None, exclude_chains=(),
-                             features=None):
+                             features=None, classes=None):
         """record="device": bayhunter_amd.posterior_covariance of every site's recorded rows, straight from the device store (one
         dict per site; one dict without SiteTargets): mean, covariance and correlation of vs at the depths of dep_int.  scalars:
         names of the store's columns to put beside the depths -- likes, vpvs, misfits [nt+1] and noise [2nt], as
         posterior_scalars() takes them; or moho = (lo, hi) (True: every site's own priors['z']) with mohovs for the Moho depth and
         the mean crustal vs; or features: name -> (kind, z0, z1[, c]) as posterior_features() takes them -- one of the three.  cold_only
-        (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        (default: True on tempered runs) and exclude_chains as in samples_dev().  classes: the dict
+        posterior_classes() returned for the same phase, cold_only and exclude_chains: per site a dict class name -> that dict."""
+        classes = self._class_rows(classes, phase, cold_only, exclude_chains)
         from .posterior import posterior_covariance
         d = self._posterior_rows(phase, cold_only, exclude_chains)
         n = d["models2d"].shape[0]
@@ -768,7 +823,7 @@ class DeviceChains(object):
             moho = [tuple(float(v) for v in p["z"]) for p in self.site_priors]
         with self.torch.cuda.device(self.dev):
             r = posterior_covariance(d["models2d"], site=d["site"], dep_int=dep_int, columns=cols, moho=moho, mohovs=mohovs,
-                                     engine=self.engine, nsites=self.nsites, features=features)
+                                     engine=self.engine, nsites=self.nsites, features=features, classes=classes)
         return r if self.sites is not None else r[0]
 
     def posterior_datafits(self, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), phase="p2", cold_only=None, exclude_chains=()):

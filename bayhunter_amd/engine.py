@@ -223,6 +223,10 @@ def load_library():
     L.bh_posterior_features.argtypes = [vp, C.c_int, vp, vp, vp]
     for name in POSTERIOR_FEATURES_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_posterior_classes.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.bh_posterior_scalar_export.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp]
+    for name in POSTERIOR_CLASSES_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     L.bh_chain_diag_series.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int,
                                        vp, vp, vp, vp, vp, vp, vp]
     L.bh_chain_diag_models.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
@@ -322,6 +326,12 @@ SCALARS_MAXCOLS = 64                # BH_SCALARS_MAXCOLS
 FEATURES_MAXKINDS = 64              # BH_FEATURES_MAXKINDS
 (FEATURE_VSMEAN, FEATURE_VSTIME, FEATURE_TTS, FEATURE_VSMIN, FEATURE_VSMAX, FEATURE_DROP, FEATURE_JUMP, FEATURE_ABOVE,
  FEATURE_NIFACES) = range(9)        # BH_FEATURE_*
+# include/bh_engine_posterior_classes.h: every row's class by a rule over the scalar sets' columns, and a set's columns by input row
+# (bayhunter_amd/posterior.py: posterior_classes and classes=)
+POSTERIOR_CLASSES_SYMBOLS = ("bh_posterior_classes", "bh_posterior_scalar_export")
+CLASSES_MAX = 16                    # BH_CLASSES_MAX
+CLASS_MAXTERMS = 64                 # BH_CLASS_MAXTERMS
+CLASS_IN, CLASS_HAS, CLASS_LACKS = 0, 1, 2   # BH_CLASS_*
 # include/bh_engine_chain_diag.h: the sums behind split R-hat and ESS of the chains' recorded series, and the medians of the
 # outlier rule (bayhunter_amd/diagnostics.py)
 CHAIN_DIAG_SYMBOLS = ("bh_chain_diag_series", "bh_chain_diag_models", "bh_chain_diag_medians")

@@ -20,6 +20,10 @@ matrices of the vs at the depths of dep_int, and of scalar columns beside them: 
 layered models themselves -- layer averages and travel times of a depth window, its slowest and fastest layer, its strongest
 velocity drop and jump, the first interface above a velocity, the number of interfaces -- each with the statistics of
 posterior_scalars and, where a feature may be absent, the posterior probability that it is there.
+
+`posterior_classes` (include/bh_engine_posterior_classes.h) splits every site's rows into classes by a rule over those scalar
+columns -- a Moho at 30-36 km or at 36-45 km, a low-velocity zone that is there or not -- and `classes=` of the functions above
+summarises every class of every site on its own: the conditional posteriors of a bimodal station.
 """
 import ctypes as C
 import math
@@ -354,6 +358,39 @@ class _Loaded(object):
         self.eng._check(self._L.bh_posterior_features(self._p, kinds.size, _ptr(kinds), _ptr(par), _ptr(found)))
         return found
 
+    def classes(self, K, term_class, term_set, term_col, term_op, lo, hi, device=None):
+        """bh_posterior_classes -> (cls int32 [N]: a numpy array, or a tensor on `device` where given; counts int64 [S, K + 1])"""
+        tc, ts, tq, to = (np.ascontiguousarray(v, np.int32) for v in (term_class, term_set, term_col, term_op))
+        T = tc.size
+        lo, hi = (np.ascontiguousarray(v, np.float64).reshape(self.S, T) for v in (lo, hi))
+        counts = np.zeros((self.S, K + 1), np.int64)
+        if device is None:
+            cls = np.zeros(self.N, np.int32)
+            mem, stream, ptr = E.HOST, None, _ptr(cls)
+        else:
+            import torch
+            cls = torch.empty(self.N, dtype=torch.int32, device=device)
+            mem, stream, ptr = E.DEVICE, C.c_void_p(torch.cuda.current_stream(device).cuda_stream), C.c_void_p(cls.data_ptr())
+        self.eng._check(self._L.bh_posterior_classes(self._p, int(K), T, _ptr(tc), _ptr(ts), _ptr(tq), _ptr(to), _ptr(lo), _ptr(hi),
+                                                     mem, stream, ptr, _ptr(counts)))
+        return cls, counts
+
+    def export(self, which, device=None):
+        """bh_posterior_scalar_export: the set's columns by input row, float64 [N, Q] (NaN for a row the load left out): a numpy
+        array, or a tensor on `device` where given"""
+        q = np.zeros(1, np.int32)
+        self.eng._check(self._L.bh_posterior_scalar_cols(self._p, which, _ptr(q)))
+        Q = int(q[0])
+        if device is None:
+            out = np.zeros((self.N, Q))
+            mem, stream, ptr = E.HOST, None, _ptr(out)
+        else:
+            import torch
+            out = torch.empty((self.N, Q), dtype=torch.float64, device=device)
+            mem, stream, ptr = E.DEVICE, C.c_void_p(torch.cuda.current_stream(device).cuda_stream), C.c_void_p(out.data_ptr())
+        self.eng._check(self._L.bh_posterior_scalar_export(self._p, which, mem, stream, Q, ptr))
+        return out
+
     def gather(self, which, pos, Q):
         """the values [len(pos), Q] of the loaded rows at the positions pos of a set of Q columns (bh_posterior_scalar_gather)"""
         pos = np.ascontiguousarray(pos, np.int64)
@@ -466,7 +503,7 @@ def _row(models, i):
     return np.asarray(r)
 
 
-def posterior_models(models, site=None, dep_int=None, misfits=None, engine=None, nsites=None, quantiles=None):
+def posterior_models(models, site=None, dep_int=None, misfits=None, engine=None, nsites=None, quantiles=None, classes=None):
     """get_singlemodels of every site: a list of dicts (one dict when site is None).  Keys: mean, median, minmax,
     stdminmax (each (values, dep_int)), mode ((vs_mode, dep_center); NaN and mode_valid False where the reference raises,
     i.e. the site's vs range is below one 0.025 km/s bin), minmisfit (with misfits), count, mode_valid, invalid_rows.
@@ -475,7 +512,12 @@ def posterior_models(models, site=None, dep_int=None, misfits=None, engine=None,
     method="linear") of the site's float64 column of interpolated vs -- the credible band of vs against depth -- NaN for a site
     without rows (include/bh_engine_posterior_quantiles.h; the columns are never stored).  quantiles at 0.5 need not equal
     `median` in the last bit for an even count: median is (a + b) / 2, numpy's quantile b - (b - a) * 0.5, of the same two
-    order statistics a <= b."""
+    order statistics a <= b.
+    classes: the dict posterior_classes returned for the same rows: the result is then per site a dict class name -> the dict
+    described here, of the rows of that class alone (posterior_classes says how rows in no class are accounted for)."""
+    if classes is not None:
+        return _by_class(posterior_models, classes, models, site, dict(dep_int=dep_int, misfits=misfits, engine=engine, nsites=nsites,
+                                                                       quantiles=quantiles))
     qs = check_quantiles(quantiles)
     dep = default_dep_int() if dep_int is None else np.ascontiguousarray(dep_int, np.float64)
     ld = _Loaded(models, site, engine, nsites)
@@ -537,11 +579,16 @@ def posterior_models(models, site=None, dep_int=None, misfits=None, engine=None,
     return out[0] if site is None else out
 
 
-def posterior_hist2d(models, site=None, dep_int=None, vs_edges=None, dep_edges=None, engine=None, nsites=None):
+def posterior_hist2d(models, site=None, dep_int=None, vs_edges=None, dep_edges=None, engine=None, nsites=None, classes=None):
     """The 2-D posterior plot's numbers (_plot_bestmodels_hist) of every site: a list of dicts (one dict when site is
     None) with counts [nvs, ndep] of the vs sampled at `samples` over vs_edges x dep_edges (numpy.histogram2d), and
     interfaces [ndep] = numpy.histogram of the interface depths over dep_edges.  The defaults are the plot's
-    (hist2d_edges): dep_int None -> 0.5 km sampling of 0..100 km and 1 km depth bins; vs edges from each site's range."""
+    (hist2d_edges): dep_int None -> 0.5 km sampling of 0..100 km and 1 km depth bins; vs edges from each site's range.
+    classes: the dict posterior_classes returned for the same rows: the result is then per site a dict class name -> the dict
+    described here, of the rows of that class alone (posterior_classes says how rows in no class are accounted for)."""
+    if classes is not None:
+        return _by_class(posterior_hist2d, classes, models, site, dict(dep_int=dep_int, vs_edges=vs_edges, dep_edges=dep_edges,
+                                                                       engine=engine, nsites=nsites))
     samples, depbins, _ = hist2d_edges(None, None, dep_int)
     if dep_edges is not None:
         depbins = np.asarray(dep_edges, np.float64)
@@ -622,7 +669,7 @@ def _stat_dict(st, s, q, dtype=np.float64):
                 min=dtype(st["min"][s, q]), max=dtype(st["max"][s, q]))
 
 
-def posterior_moho(models, site=None, moho=None, mohovs=MOHOVS, bins=50, engine=None, nsites=None, quantiles=None):
+def posterior_moho(models, site=None, moho=None, mohovs=MOHOVS, bins=50, engine=None, nsites=None, quantiles=None, classes=None):
     """The numbers of the reference's plot_moho_crustvel_tradeoff for every site: a list of dicts (one dict when site is
     None).  moho = (lo, hi) km, or one pair per site: the depth range in which an interface can be the Moho (0 <= lo < hi);
     mohovs (one, or one per site): the Moho is the first interface inside the range below which vs exceeds it.
@@ -635,7 +682,12 @@ def posterior_moho(models, site=None, moho=None, mohovs=MOHOVS, bins=50, engine=
     quantiles: a sequence of numbers in [0, 1] (any order, duplicates allowed; anything else is a ValueError) adds to each of the
     four dicts quantiles [R] = numpy.quantile(values, quantiles, method="linear") over the rows that have a Moho -- the credible
     interval of the Moho depth -- NaN where count is 0.  quantiles at 0.5 need not equal median
-    in the last bit for an even count ((a + b) / 2 against numpy's b - (b - a) * 0.5 of the same two order statistics)."""
+    in the last bit for an even count ((a + b) / 2 against numpy's b - (b - a) * 0.5 of the same two order statistics).
+    classes: the dict posterior_classes returned for the same rows: the result is then per site a dict class name -> the dict
+    described here, of the rows of that class alone (posterior_classes says how rows in no class are accounted for)."""
+    if classes is not None and moho is not None:
+        return _by_class(posterior_moho, classes, models, site, dict(moho=moho, mohovs=mohovs, bins=bins, engine=engine, nsites=nsites,
+                                                                     quantiles=quantiles))
     qs = check_quantiles(quantiles)
     if moho is None:
         raise ValueError("moho=(lo, hi) is needed: the reference's default is the station's priors['z']")
@@ -717,7 +769,7 @@ def _stack_columns(columns, N):
     return np.concatenate([p.astype(ndt, copy=False) for p in parts], axis=1), layout
 
 
-def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=None, nsites=None, quantiles=None):
+def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=None, nsites=None, quantiles=None, classes=None):
     """The numbers of the reference's plot_posterior_likes / _misfits / _nlayers / _vpvs / _noise / _others for every site: a
     list of dicts (one dict when site is None), name -> statistics.  columns: a dict name -> [N] or [N, k] values (float32 or
     float64; numpy arrays or device tensors), one row per model row; a [N, k] column gives a list of k statistics.  With
@@ -733,7 +785,12 @@ def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=
     column's statistics, nlayers included, quantiles [R] float64 = numpy.quantile(values widened to float64, quantiles,
     method="linear") over the column's non-NaN values, NaN where count is 0 -- whatever the column's dtype (numpy computes a
     float32 column's quantile in float32; median keeps its per-dtype meaning).  quantiles at 0.5 need not equal median in the
-    last bit for an even count ((a + b) / 2 against numpy's b - (b - a) * 0.5 of the same two order statistics)."""
+    last bit for an even count ((a + b) / 2 against numpy's b - (b - a) * 0.5 of the same two order statistics).
+    classes: the dict posterior_classes returned for the same rows: the result is then per site a dict class name -> the dict
+    described here, of the rows of that class alone (posterior_classes says how rows in no class are accounted for)."""
+    if classes is not None:
+        return _by_class(posterior_scalars, classes, models, site, dict(columns=columns, bins=bins, nlayers=nlayers, engine=engine,
+                                                                        nsites=nsites, quantiles=quantiles))
     qs = check_quantiles(quantiles)
     taken = [k for k in columns if k in ("rows", "invalid_rows", "dropped") or (nlayers and k == "nlayers")]
     if taken:
@@ -778,7 +835,7 @@ def posterior_scalars(models, columns, site=None, bins=20, nlayers=True, engine=
 # ---- covariance and correlation of vs with depth (include/bh_engine_posterior_cov.h) ---------------------------------------
 
 def posterior_covariance(models, site=None, dep_int=None, columns=None, moho=None, mohovs=MOHOVS, moho_columns=("moho", "vscrust"),
-                         engine=None, nsites=None, features=None):
+                         engine=None, nsites=None, features=None, classes=None):
     """How a site's profile varies together: a list of dicts (one dict when site is None) with the mean vector and the
     population covariance (ddof = 0, as std everywhere in this package) and correlation matrices of P columns -- the vs at the
     depths of dep_int (default 0..100 km in 0.5 km steps; an empty dep_int leaves them out), then scalar columns of ONE set:
@@ -796,7 +853,13 @@ def posterior_covariance(models, site=None, dep_int=None, columns=None, moho=Non
     integer sums without rounding).  corr is NaN in the row and column of a constant column, as numpy.corrcoef leaves it; a site
     without rows used has NaN everywhere.  The numbers are functions of exact integer sums formed on the device: the same bits
     alone or among other sites, in any row order, on every repeat; each within 1 ulp of the exact rational.  The caller who wants
-    ddof = 1 multiplies cov by n / (n - 1)."""
+    ddof = 1 multiplies cov by n / (n - 1).
+    classes: the dict posterior_classes returned for the same rows: the result is then per site a dict class name -> the dict
+    described here, of the rows of that class alone (posterior_classes says how rows in no class are accounted for)."""
+    if classes is not None:
+        return _by_class(posterior_covariance, classes, models, site, dict(dep_int=dep_int, columns=columns, moho=moho, mohovs=mohovs,
+                                                                           moho_columns=moho_columns, engine=engine, nsites=nsites,
+                                                                           features=features))
     if sum(v is not None for v in (columns, moho, features)) > 1:
         raise ValueError("one call takes its scalar columns from one set: give columns, moho or features, not two of them")
     dep = default_dep_int() if dep_int is None else np.ascontiguousarray(dep_int, np.float64).reshape(-1)
@@ -903,7 +966,7 @@ def check_features(features, S):
     return np.array(kinds, np.int32), par, labels
 
 
-def posterior_features(models, features, site=None, bins=50, quantiles=None, engine=None, nsites=None):
+def posterior_features(models, features, site=None, bins=50, quantiles=None, engine=None, nsites=None, classes=None):
     """The posterior of structural features of every site's layered models: a list of dicts (one dict when site is None).
     features: a dict name -> (kind, z0, z1[, c]); every number a scalar or a sequence of one value per site.  With the row's step
     model (layer j from the interface above it to the one below, the last to infinity) and the window [z0, z1] km, the kinds are
@@ -920,7 +983,12 @@ def posterior_features(models, features, site=None, bins=50, quantiles=None, eng
     nifaces arange(min, max + 2) - 0.5) -- and for a kind of two {"depth": statistics, "value" | "jump": statistics, "hist2d":
     (counts [bins, bins], xedges of the value or jump, yedges of the depth), "mode": (value or jump, depth), the centres of the first
     largest cell}.  drop, jump and above add probability = count / rows: the posterior probability that the station has such a
-    feature (NaN for a site without rows)."""
+    feature (NaN for a site without rows).
+    classes: the dict posterior_classes returned for the same rows: the result is then per site a dict class name -> the dict
+    described here, of the rows of that class alone (posterior_classes says how rows in no class are accounted for)."""
+    if classes is not None:
+        return _by_class(posterior_features, classes, models, site, dict(features=features, bins=bins, quantiles=quantiles, engine=engine,
+                                                                         nsites=nsites))
     qs = check_quantiles(quantiles)
     ld = _Loaded(models, site, engine, nsites, scalars=True)
     try:
@@ -987,3 +1055,221 @@ def posterior_features(models, features, site=None, bins=50, quantiles=None, eng
             q += FEATURE_COLS[kind]
         out.append(r)
     return out[0] if site is None else out
+
+
+# ---- conditional posteriors: the rows of a site split into classes (include/bh_engine_posterior_classes.h) ---------------------
+
+CLASS_OPS = ("in", "has", "lacks")   # BH_CLASS_*, in order
+
+
+def check_classes(classes, S, labels):
+    """The user's rule as the arrays of bh_posterior_classes over S sites: (names [K], term_class, term_set, term_col, term_op
+    int32 [T], lo, hi float64 [S, T]).  classes: an ordered dict class name -> list of terms, the first class whose terms all hold
+    taking the row; a class with an empty list takes every row that is left.  A term is (label, lo, hi) -- the row has a value v
+    in the column and lo <= v < hi; lo and hi one number or one per site, -inf and inf allowed --, (label, "has") -- the row has a
+    value -- or (label, "lacks") -- it has none (NaN).  labels: a dict label -> (set, column), the columns the call has formed.
+    Pure host code; every refused input is a ValueError that names the class (and the site, where one site's value is at fault)."""
+    if not isinstance(classes, dict) or not classes:
+        raise ValueError("classes must be a dict name -> list of terms with at least one entry")
+    if len(classes) > E.CLASSES_MAX:
+        raise ValueError("classes: %d classes (class %r is the first too many), a call takes at most %d (BH_CLASSES_MAX)"
+                         % (len(classes), list(classes)[E.CLASSES_MAX], E.CLASSES_MAX))
+    S = int(S)
+    names, tc, ts, tq, to, los, his = [], [], [], [], [], [], []
+    for k, (name, terms) in enumerate(classes.items()):
+        if not isinstance(name, str) or not name:
+            raise ValueError("class %r: the name must be a non-empty string" % (name,))
+        if isinstance(terms, (str, bytes, dict)) or not hasattr(terms, "__len__"):
+            raise ValueError("class %r: expected a list of terms (label, lo, hi), (label, 'has') or (label, 'lacks')" % (name,))
+        for term in terms:
+            if isinstance(term, (str, bytes)) or not hasattr(term, "__len__") or len(term) not in (2, 3):
+                raise ValueError("class %r: a term is (label, lo, hi), (label, 'has') or (label, 'lacks'), not %r" % (name, term))
+            label = term[0]
+            if not isinstance(label, str) or label not in labels:
+                raise ValueError("class %r: %r is no column of this call (%s)" % (name, label, ", ".join(labels) or "none formed"))
+            if len(tc) == E.CLASS_MAXTERMS:
+                raise ValueError("class %r: its term on %r is the first beyond the %d terms a call takes (BH_CLASS_MAXTERMS)"
+                                 % (name, label, E.CLASS_MAXTERMS))
+            lo, hi = np.full(S, -np.inf), np.full(S, np.inf)
+            if len(term) == 2:
+                if not isinstance(term[1], str) or term[1] not in ("has", "lacks"):
+                    raise ValueError("class %r, column %r: a term of two is (label, 'has') or (label, 'lacks'), not %r"
+                                     % (name, label, term[1]))
+                op = CLASS_OPS.index(term[1])
+            else:
+                op = E.CLASS_IN
+                for what, dst, v in (("lo", lo, term[1]), ("hi", hi, term[2])):
+                    try:
+                        v = np.asarray(v, np.float64)
+                    except (TypeError, ValueError):
+                        raise ValueError("class %r, column %r: %s must be a number or one number per site" % (name, label, what))
+                    if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != S):
+                        raise ValueError("class %r, column %r: %s must be one number or one per site (%d sites), not shape %r"
+                                         % (name, label, what, S, v.shape))
+                    dst[:] = v
+                for s in range(S):
+                    at = "class %r, column %r, site %d" % (name, label, s)
+                    if np.isnan(lo[s]) or np.isnan(hi[s]):
+                        raise ValueError("%s: a bound is NaN" % at)
+                    if lo[s] > hi[s]:
+                        raise ValueError("%s: lo = %r lies above hi = %r" % (at, float(lo[s]), float(hi[s])))
+            tc.append(k)
+            ts.append(labels[label][0])
+            tq.append(labels[label][1])
+            to.append(op)
+            los.append(lo)
+            his.append(hi)
+        names.append(name)
+    if len(set(names)) != len(names):
+        raise ValueError("classes: a class name occurs twice")
+    T = len(tc)
+    lo = np.ascontiguousarray(np.array(los, np.float64).reshape(T, S).T)
+    hi = np.ascontiguousarray(np.array(his, np.float64).reshape(T, S).T)
+    return names, np.array(tc, np.int32), np.array(ts, np.int32), np.array(tq, np.int32), np.array(to, np.int32), lo, hi
+
+
+def _is_tensor(v):
+    try:
+        import torch
+    except ImportError:
+        return False
+    return isinstance(v, torch.Tensor)
+
+
+def posterior_classes(models, classes, site=None, features=None, moho=None, mohovs=MOHOVS, columns=None, nlayers=False, engine=None,
+                      nsites=None, return_columns=False):
+    """Split every site's rows into classes by a rule over their scalar columns, on the device: what a bimodal posterior needs
+    before it is summarised -- a mean over two Moho candidates describes a model no chain sampled.
+    classes: an ordered dict class name -> list of terms (check_classes): (label, lo, hi), (label, "has"), (label, "lacks"); the
+    first class whose terms all hold takes the row.  The labels are those of the sources given, any of them at once:
+      features: as posterior_features' -- the labels check_features returns (name, name.depth, name.jump, name.value);
+      moho = (lo, hi) or one pair per site, with mohovs: as posterior_moho's -- "moho", "vslast", "vscrust", "vsjump";
+      columns: as posterior_scalars', one value row per model row -- name, or name[0] .. name[k-1] for a [N, k] column; nlayers:
+        "nlayers".
+    Returns a dict: names [K]; cls int32 [N], every input row's class in the input's order, -1 for a row in no class and for a
+    row the load leaves out (a NaN row, a malformed row, a device row whose site is out of range) -- a numpy array for numpy rows, a
+    device tensor for a device tensor; counts [S, K], unclassified [S], rows [S] (counts.sum(1) + unclassified == rows);
+    probability [S, K] = counts / rows (NaN for a site without rows); nclasses = K; site int32 [N] = site * K + cls, -1 where
+    either is negative, and nsites = S * K: every class of every site as a site of its own; with return_columns, columns: label
+    -> float64 [N], every source column by input row (NaN where the load left the row out).
+    The dict is what classes= of posterior_models, posterior_hist2d, posterior_moho, posterior_scalars, posterior_features and
+    posterior_covariance takes, with the same rows (and the same site, or None): the call then runs on the S * K virtual sites,
+    per-site arguments (moho, mohovs, the numbers of features) repeated for every class of the site and per-row arguments (misfits,
+    columns) passed through, and returns per site a dict class name -> the function's usual dict (a list over sites when site is
+    given).  The numbers of a class are those of the function called on the rows of that class alone, bit for bit.  Rows in no
+    class: numpy rows are removed before the load (rows, invalid_rows and dropped are those of the class's own rows); device
+    tensors stay where they are, these rows get site -1 and are counted in `dropped`, the total of the call.
+    cls and counts are predicates on float64 columns that are exact functions of the rows: the same bits alone or among other
+    sites, in any row order, from host or device memory, on every repeat."""
+    ld = _Loaded(models, site, engine, nsites, scalars=True)
+    try:
+        S = ld.S
+        labels, formed = {}, []
+
+        def take(new, which):
+            for i, lb in enumerate(new):
+                if lb in labels:
+                    raise ValueError("label %r names two columns of this call: rename the feature or the column" % (lb,))
+                labels[lb] = (which, i)
+            formed.append((which, list(new)))
+
+        if features is not None:
+            kinds, par, flabels = check_features(features, S)
+            take(flabels, E.SCALARS_FEATURES)
+        if moho is not None:
+            rng = _per_site(moho, S, 2, "moho")
+            mv = _per_site(mohovs, S, 0, "mohovs")
+            take(MOHO_COLUMNS, E.SCALARS_MOHO)
+        values, layout = _stack_columns(columns, ld.N) if columns is not None else (None, [])
+        if values is not None or nlayers:
+            take([name if idx is None else "%s[%d]" % (name, idx) for name, idx, _ in layout] + (["nlayers"] if nlayers else []),
+                 E.SCALARS_USER)
+        names, tc, ts, tq, to, lo, hi = check_classes(classes, S, labels)
+        if features is not None:
+            ld.features(kinds, par)
+        if moho is not None:
+            ld.moho(rng[:, 0], rng[:, 1], mv)
+        if values is not None or nlayers:
+            ld.attach(values, nlayers)
+        K = len(names)
+        dev = models.device if _is_tensor(models) else None
+        cls, cnt = ld.classes(K, tc, ts, tq, to, lo, hi, device=dev)
+        cols = None
+        if return_columns:
+            cols = {}
+            for which, lbs in formed:
+                tab = ld.export(which, device=dev)
+                for i, lb in enumerate(lbs):
+                    cols[lb] = tab[:, i]
+    finally:
+        ld.close()
+    rows = ld.rows.copy()
+    counts = cnt[:, :K].copy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        prob = np.where(rows[:, None] > 0, counts / rows[:, None].astype(np.float64), np.nan)
+    if dev is None:
+        st = np.zeros(ld.N, np.int32) if site is None else np.asarray(site).astype(np.int32)
+        vsite = np.where((st >= 0) & (cls >= 0), st * np.int32(K) + cls, np.int32(-1)).astype(np.int32)
+    else:
+        import torch
+        st = torch.zeros_like(cls) if site is None else torch.as_tensor(site, device=dev).to(torch.int32)
+        vsite = torch.where((st >= 0) & (cls >= 0), st * K + cls, torch.full_like(cls, -1)).to(torch.int32)
+    out = dict(names=names, cls=cls, counts=counts, unclassified=cnt[:, K].copy(), rows=rows, probability=prob, nclasses=K, site=vsite,
+               nsites=S * K)
+    if cols is not None:
+        out["columns"] = cols
+    return out
+
+
+def _repeat_features(features, S, K):
+    """the features dict with every number given per virtual site: each site's value K times"""
+    check_features(features, S)
+    return {name: (spec[0],) + tuple(np.repeat(np.broadcast_to(np.asarray(v, np.float64), (S,)), K) for v in spec[1:])
+            for name, spec in features.items()}
+
+
+def _rows_of(v, keep):
+    if v is None:
+        return None
+    if _is_tensor(v):
+        import torch
+        return v[torch.from_numpy(keep).to(v.device)]
+    return np.asarray(v)[keep]
+
+
+def _by_class(fn, classes, models, site, kw):
+    """fn(models, ...) over the virtual sites of a posterior_classes dict: per site a dict class name -> fn's dict"""
+    if not isinstance(classes, dict) or not all(k in classes for k in ("names", "site", "nclasses", "nsites")):
+        raise ValueError("classes must be the dict posterior_classes returned for these rows")
+    names, K = list(classes["names"]), int(classes["nclasses"])
+    S = int(classes["nsites"]) // K
+    vsite = classes["site"]
+    if len(models.shape) != 2 or int(vsite.shape[0]) != int(models.shape[0]):
+        raise ValueError("classes holds %d rows, models %d: the dict must stem from the same rows" % (int(vsite.shape[0]), int(models.shape[0])))
+    if site is None and S != 1:
+        raise ValueError("classes was formed over %d sites: give the same site index" % S)
+    if kw.get("nsites") is not None and int(kw["nsites"]) != S:
+        raise ValueError("classes was formed over %d sites, nsites is %d" % (S, int(kw["nsites"])))
+    kw = dict(kw)
+    if kw.get("moho") is not None:
+        kw["moho"] = np.repeat(_per_site(kw["moho"], S, 2, "moho"), K, axis=0)
+        kw["mohovs"] = np.repeat(_per_site(kw["mohovs"], S, 0, "mohovs"), K)
+    if kw.get("features") is not None:
+        kw["features"] = _repeat_features(kw["features"], S, K)
+    if _is_tensor(models):
+        import torch
+        vsite = torch.as_tensor(vsite, device=models.device)
+    else:
+        if _is_tensor(vsite):
+            vsite = vsite.detach().cpu().numpy()
+        models = np.asarray(models)
+        keep = np.asarray(vsite) >= 0   # the host load refuses a site out of range: the rows in no class go before it
+        models, vsite = models[keep], np.asarray(vsite)[keep]
+        if kw.get("misfits") is not None:
+            kw["misfits"] = _rows_of(kw["misfits"], keep)
+        if kw.get("columns") is not None:
+            kw["columns"] = {name: _rows_of(v, keep) for name, v in kw["columns"].items()}
+    kw["nsites"] = S * K
+    res = fn(models, site=vsite, **kw)
+    out = [{names[k]: res[s * K + k] for k in range(K)} for s in range(S)]
+    return out if site is not None else out[0]
