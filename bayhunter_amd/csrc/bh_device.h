@@ -368,6 +368,11 @@ RfAxisRec bh_rf_axis_record(int nsamp, double fsamp, double tshift, double gauss
 int bh_launch_rf_t(const RfKernelArgs &a, hipStream_t stream, const RfSiteTArgs &sites);
 // bh_probe_math ops 11-16: the synthesis kernel's own elementary functions (include/bh_engine_debug.h); -1 for another op
 int bh_launch_rf_probe(int op, int n, const double *in, double *out, hipStream_t stream);
+// bh_probe_math ops 17-23 and bh_probe_swd_secular: the dispersion kernels' fast arithmetic (swd_fa_probe.hip = swd_lean.hip built with
+// BH_SWD_PROBE); -1 for another op / for arguments the entry point refuses.  model: [4][mtop] doubles on the device (d, a, b, rho).
+int bh_launch_swd_fa_probe(int op, int n, const double *in, double *out, hipStream_t stream);
+int bh_launch_swd_secular_probe(int evaluator, int ifunc, int mmax, int mtop, const double *model, int n, const double *wvno,
+                                const double *omega, double *out, hipStream_t stream);
 
 struct LikeTargetDev {
     int law, n, off; // off: column offset of this target's samples inside a ymod row

@@ -2531,7 +2531,7 @@ int bh_loglike_batch(bh_engine *e, int memspace, void *stream, int B, const doub
 
 int bh_probe_math(bh_engine *e, int op, int n, const double *in, double *out)
 {
-    if (!e || n < 0 || !in || !out || op < 0 || op > 16 || (op == 16 && (n & 1))) return BH_EINVAL;
+    if (!e || n < 0 || !in || !out || op < 0 || op > 23 || (op == 16 && (n & 1))) return BH_EINVAL;
     if (n == 0) return BH_OK;
     int rc;
     HIPCHK(e, hipSetDevice(e->device));
@@ -2539,9 +2539,44 @@ int bh_probe_math(bh_engine *e, int op, int n, const double *in, double *out)
     if ((rc = ensure(e, e->probe_in, nin * sizeof(double)))) return rc;
     if ((rc = ensure(e, e->probe_out, (size_t)n * sizeof(double)))) return rc;
     HIPCHK(e, hipMemcpyAsync(e->probe_in.p, in, nin * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    if (op >= 11) bh_launch_rf_probe(op, n, (const double *)e->probe_in.p, (double *)e->probe_out.p, e->stream);
+    if (op >= 17) bh_launch_swd_fa_probe(op, n, (const double *)e->probe_in.p, (double *)e->probe_out.p, e->stream);
+    else if (op >= 11) bh_launch_rf_probe(op, n, (const double *)e->probe_in.p, (double *)e->probe_out.p, e->stream);
     else bh_launch_probe(op, n, (const double *)e->probe_in.p, (double *)e->probe_out.p, e->stream);
     HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(out, e->probe_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return BH_OK;
+}
+
+int bh_probe_swd_secular(bh_engine *e, int evaluator, int ifunc, int mmax, int mtop, const float *d, const float *a, const float *b,
+                         const float *rho, int n, const double *wvno, const double *omega, double *out)
+{
+    if (!e || !d || !a || !b || !rho || !wvno || !omega || !out || n < 0) return BH_EINVAL;
+    if (evaluator < 0 || evaluator > 2 || (ifunc != 1 && ifunc != 2) || mmax < 2 || mmax > mtop) return fail(e, BH_EINVAL, "bad evaluator, wave type or layer count");
+    if (evaluator == 2 ? mtop > 32 : mtop > BH_MAX_LAYERS) return fail(e, BH_EINVAL, "mtop beyond the evaluator's rows (2..32 lean, 2..100)");
+    if (n == 0) return BH_OK;
+    int rc;
+    HIPCHK(e, hipSetDevice(e->device));
+    const size_t nm = (size_t)4 * mtop, nin = nm + (size_t)2 * n;
+    if ((rc = ensure(e, e->probe_in, nin * sizeof(double)))) return rc;
+    if ((rc = ensure(e, e->probe_out, (size_t)n * sizeof(double)))) return rc;
+    std::vector<double> host(nin); // [4][mtop] model (binary32 values widened), wvno[n], omega[n]
+    for (int l = 0; l < mtop; ++l) {
+        host[l] = (double)d[l];
+        host[(size_t)mtop + l] = (double)a[l];
+        host[(size_t)2 * mtop + l] = (double)b[l];
+        host[(size_t)3 * mtop + l] = (double)rho[l];
+    }
+    for (int i = 0; i < n; ++i) {
+        host[nm + i] = wvno[i];
+        host[nm + n + i] = omega[i];
+    }
+    HIPCHK(e, hipMemcpyAsync(e->probe_in.p, host.data(), nin * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    const double *din = (const double *)e->probe_in.p;
+    if (bh_launch_swd_secular_probe(evaluator, ifunc, mmax, mtop, din, n, din + nm, din + nm + n, (double *)e->probe_out.p, e->stream) != 0)
+        return fail(e, BH_EINVAL, "secular probe refused");
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(e->stream)); // (before `host` goes, and before `out` is touched)
     HIPCHK(e, hipMemcpyAsync(out, e->probe_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return BH_OK;

@@ -9,10 +9,20 @@
 // units in the last place of the exactly rounded formula, i.e. it differs from the reference-exact evaluation by what that
 // evaluation's own rounding error is; about a third of its instructions.
 //
-// What that does to a search (SearchT, short refinement; swd_lean.hip).  Measured on the device over 10^8 (model, period,
+// THE CONTRACT is tests/test_gpu_swd_fa.py: every function of namespace fa probed on the device at a derived epsilon (see
+// sincos below), and the secular functions -- fa::rayleigh_secular / fa::love_secular and the lean kernel's lean_rayleigh /
+// lean_love, through bh_probe_swd_secular (include/bh_engine_debug.h) -- within 4 x an a priori first-order error bound of a
+// long-double reference (tests/swd_fa_ref.py; the bound is proven on the CPU against the reference's own binary64 arithmetic,
+// tests/test_swd_fa_ref.py) on models of 2 ... 32 layers, at uniform points, within 1e-6 ... 1e-12 of layer and half-space
+// velocities, with k == k_beta exactly, on a layer thick enough to poison, and at the corners of SearchT::init's bounds.
+// Measured there: worst error / bound 0.71 (Love) and 0.76 (Rayleigh), the same for both evaluators.
+//
+// What that does to a search (SearchT, short refinement; swd_lean.hip).  Surveyed on the device over 10^8 (model, period,
 // velocity) points of each wave type (tools/ubench/fadiff.hip), both values max-norm scaled (|f| <= 1): |f_fast - f_exact| is
 // below 1e-11 in 99.6 % of them and reaches 1.2e-8 -- the large ones where the trial velocity lies within ~1e-7 relative of a
-// layer velocity, where the REFERENCE's own k - k_beta cancels and its value is uncertain by as much.  A root moves by ~1e-13
+// layer velocity, where the REFERENCE's own k - k_beta cancels (and, on the evanescent side, its (1 - e^-2q) / 2) and its value
+// is uncertain by as much.  (The test's 1 628 points with a number from both, half of them within 1e-6 of a velocity: at most 4.0e-10, below 1e-11 in
+// 96.8 % (Love) and 99.1 % (Rayleigh) -- no contradiction.)  A root moves by ~1e-13
 // relative (tolerance of the path: 1e-5; the short refinement's own distance from the reference: 1.2e-6).  A scan's sign
 // pattern can differ from the exact evaluation's only where |f| at a grid point is smaller than that difference, i.e. where
 // a root lies within ~1e-8 of the grid point: the bracket then moves by one step around the same root (same velocity, same
@@ -52,9 +62,11 @@ __device__ __forceinline__ double rcp1(double x) // one step (~2^-45): scale fac
     return __builtin_fma(r, __builtin_fma(-x, r, 1.0), r);
 }
 
-// sin and cos of 0 <= x < 1e5 and exp(-x), 0 <= x <= 700: fdlibm's kernels on
-// [-pi/4, pi/4]; Taylor to r^12 on |r| <= ln 2 / 2), the polynomials summed by Estrin's scheme -- half the depth of the chain of
-// dependent operations, which is what two wavefronts per SIMD cannot hide.
+// sin and cos of 0 <= x <= 9e4 (the clamp of wave() / love_terms(): n <= 57296, where the two-part reduction still leaves
+// 4e-22) and exp(-x), 0 <= x <= 700: two-part Cody-Waite reductions, then fdlibm's kernels on [-pi/4, pi/4] (sin, cos) and the
+// Taylor series to r^12 on |r| <= ln 2 / 2 (exp), the polynomials summed by Estrin's scheme -- half the depth of the chain of
+// dependent operations, which is what two wavefronts per SIMD cannot hide.  Derived (tests/swd_fa_ref.py) and probed on the
+// device (tests/test_gpu_swd_fa.py): rcp 1 u, sqrt_rsqrt 2.5 u, sin / cos 3 u absolute, expneg 5 u, rcp1 2^-46 (u = 2^-53).
 __device__ __forceinline__ void sincos(double x, double &sn, double &cs)
 {
     const double n = __builtin_rint(x * 6.36619772367581382433e-01);

@@ -41,6 +41,12 @@
 #ifndef BH_SWD_SITEX
 #define BH_SWD_SITEX 0
 #endif
+// 1: the PROBE build (swd_fa_probe.hip includes this file): instead of the kernel and its launcher, the probes of the fast
+// arithmetic (bh_probe_math ops 17-23, bh_probe_swd_secular; include/bh_engine_debug.h) -- the functions of swd_fa.h and the
+// evaluators below as this file's flags compile them.  0: the builds this file always had, the same machine code.
+#ifndef BH_SWD_PROBE
+#define BH_SWD_PROBE 0
+#endif
 
 namespace {
 #include "swd_common.h"
@@ -114,6 +120,7 @@ __device__ __forceinline__ double lean_love(double wvno, double omega, const Lea
     return e1;
 }
 
+#if !BH_SWD_PROBE
 enum : int {
     PH_START = 0,      // a period's first round: the start value (trial 0) and the first J - 1 upward steps
     PH_SCAN = 1,       // J further steps of the scan
@@ -234,6 +241,7 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
             fb = (float)T.vs[o];
             fr = (float)T.rho[o];
         }
+        // (restated by swd_probe_secular_kernel below, evaluator 2: the binary32 values widened, the reciprocals by fa::rcp)
         mdl[idx] = (double)fd;
         mdl[LS + idx] = (double)fa_;
         mdl[2 * LS + idx] = (double)fb;
@@ -324,7 +332,7 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
     unsigned evals = 0;
     if (active) {
         omega = omg[0];
-        iom = fa::rcp(omega);
+        iom = fa::rcp(omega); // (restated by swd_probe_secular_kernel below, evaluator 2)
     }
     constexpr unsigned long long maskJ = (J >= 64) ? ~0ull : ((1ull << J) - 1ull);
     // THE NEXT PERIOD'S FIRST ROUND RIDES ALONG.  The estimate x that a round of clustered trials is centred on -- the inverse
@@ -905,8 +913,91 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
             atomicAdd(A.neval + (greason <= 4 ? 14 : 15), 1ull << (16 * ((greason - 1) & 3)));
     }
 }
+#else // BH_SWD_PROBE
+// ---- probes of the fast arithmetic (include/bh_engine_debug.h), one lane per input ------------------------------------------
+// bh_probe_math ops 17-23: the functions of namespace fa
+__global__ __launch_bounds__(256) void swd_probe_math_kernel(int op, int n, const double *__restrict__ in, double *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double x = in[i];
+    double s = 0.0, c = 0.0;
+    switch (op) {
+    case 17: out[i] = fa::rcp(x); break;
+    case 18: out[i] = fa::rcp1(x); break;
+    case 19: fa::sqrt_rsqrt(x, s, c); out[i] = s; break;
+    case 20: fa::sqrt_rsqrt(x, s, c); out[i] = c; break;
+    case 21: fa::sincos(x, s, c); out[i] = s; break;
+    case 22: fa::sincos(x, s, c); out[i] = c; break;
+    default: out[i] = fa::expneg(x); break;
+    }
+}
+
+constexpr int PROBE_TAB_PAD = (LIBM_TAB_BYTES + 15) & ~15;
+constexpr int PROBE_ROWS = 100, PROBE_LEAN_ROWS = 32; // the Fortran's layer limit (surfdisp96.f:59); the lean kernel's
+
+// bh_probe_swd_secular: ONE model (model[4][mtop]: d, a, b, rho, binary32-valued), lane i evaluates the secular function at
+// (wvno[i], omega[i]).  evaluator 0: the exact evaluators of swd_common.h with the libm tables staged in LDS as the kernels
+// stage them; 1: fa::rayleigh_secular / fa::love_secular over the same binary32 model (the lane kernel's FA builds);
+// 2: lean_rayleigh / lean_love over a LeanModel.  No water layer (llw = 1).  Every lane reads the one model of the workgroup
+// (an LDS broadcast); rows mmax .. mtop - 1 are staged as they come and never read by an evaluator.
+__global__ __launch_bounds__(BH_WAVE) void swd_probe_secular_kernel(int evaluator, int ifunc, int mmax, int mtop, const double *__restrict__ model,
+                                                                   int n, const double *__restrict__ wvno, const double *__restrict__ omega,
+                                                                   double *__restrict__ out)
+{
+    __shared__ __align__(16) unsigned char tabs[PROBE_TAB_PAD];
+    __shared__ float mf[PROBE_ROWS * BH_WAVE];        // row m: d, a, b, rho in columns 0..3 of ModelLds's [layer][BH_WAVE]
+    __shared__ double ml[7 * PROBE_LEAN_ROWS];        // LeanModel [7][mtop][1]
+    const int lane = threadIdx.x;
+    const LibmTabs LT = stage_libm_tables(tabs, lane, BH_WAVE);
+    for (int l = lane; l < mtop; l += BH_WAVE) {
+        const float fd = (float)model[l], fa_ = (float)model[mtop + l], fb = (float)model[2 * mtop + l], fr = (float)model[3 * mtop + l];
+        mf[l * BH_WAVE] = fd;
+        mf[l * BH_WAVE + 1] = fa_;
+        mf[l * BH_WAVE + 2] = fb;
+        mf[l * BH_WAVE + 3] = fr;
+        if (evaluator == 2) { // the kernel's own staging statements (swd_lean_kernel above: "mdl[idx] = (double)fd; ...")
+            ml[l] = (double)fd;
+            ml[mtop + l] = (double)fa_;
+            ml[2 * mtop + l] = (double)fb;
+            ml[3 * mtop + l] = (double)fr;
+            ml[4 * mtop + l] = fa::rcp((double)fa_);
+            ml[5 * mtop + l] = fa::rcp((double)fb);
+            ml[6 * mtop + l] = fa::rcp((double)fr);
+        }
+    }
+    __syncthreads();
+    const int i = blockIdx.x * BH_WAVE + lane;
+    if (i >= n) return;
+    const double k = wvno[i], om = omega[i];
+    double del;
+    if (evaluator == 2) {
+        LeanModel md;
+        md.p = ml;
+        md.S = 1;
+        md.LS = mtop;
+        const double iom = fa::rcp(om); // (swd_lean_kernel above: "iom = fa::rcp(omega)")
+        del = (ifunc == 2) ? lean_rayleigh(k, om, iom, md, mmax, mtop) : lean_love(k, om, md, mmax, mtop);
+    } else {
+        ModelLds md;
+        md.d = mf;
+        md.a = mf + 1;
+        md.b = mf + 2;
+        md.rho = mf + 3;
+        if (evaluator == 1) {
+            del = (ifunc == 2) ? fa::rayleigh_secular(k, om, md, mmax, 1, mtop) : fa::love_secular(k, om, md, mmax, 1, mtop);
+        } else {
+            DivRange dr;
+            dr.reset();
+            del = (ifunc == 2) ? rayleigh_secular<true>(k, om, md, mmax, 1, mtop, dr, LT) : love_secular<true>(k, om, md, mmax, 1, mtop, dr, LT);
+        }
+    }
+    out[i] = del;
+}
+#endif // BH_SWD_PROBE
 } // namespace
 
+#if !BH_SWD_PROBE
 // LDS of one workgroup (LEAN_WPB wavefronts, a private region each)
 // (sitex: the site-period builds keep a row of Kmax frequencies per model -- with 4 trials per round, 16 models per wavefront,
 // 60 periods and arrays of 16 layers that is 86 KB per workgroup instead of 58: more than a workgroup may ask for, the call
@@ -1000,3 +1091,24 @@ int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo
 #undef LEAN_LAUNCH
     return 0;
 }
+#else // BH_SWD_PROBE
+int bh_launch_swd_fa_probe(int op, int n, const double *in, double *out, hipStream_t stream)
+{
+    if (op < 17 || op > 23 || n < 0) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(swd_probe_math_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, op, n, in, out);
+    return 0;
+}
+
+// model: [4][mtop] on the device; -1 for what bh_probe_swd_secular refuses
+int bh_launch_swd_secular_probe(int evaluator, int ifunc, int mmax, int mtop, const double *model, int n, const double *wvno,
+                                const double *omega, double *out, hipStream_t stream)
+{
+    if (evaluator < 0 || evaluator > 2 || (ifunc != 1 && ifunc != 2) || mmax < 2 || mmax > mtop || n < 0) return -1;
+    if (mtop > (evaluator == 2 ? PROBE_LEAN_ROWS : PROBE_ROWS)) return -1;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(swd_probe_secular_kernel, dim3((n + BH_WAVE - 1) / BH_WAVE), dim3(BH_WAVE), 0, stream, evaluator, ifunc, mmax, mtop,
+                       model, n, wvno, omega, out);
+    return 0;
+}
+#endif // BH_SWD_PROBE

@@ -162,6 +162,7 @@ def load_library():
                                     C.c_ssize_t, C.c_ssize_t, vp, vp, vp, vp, vp]
     L.bh_loglike_batch.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.bh_probe_math.argtypes = [vp, C.c_int, C.c_int, _d, _d]
+    L.bh_probe_swd_secular.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, _d, _d, _d]
     L.bh_sites_set.argtypes = [vp, C.c_int, vp, vp]
     L.bh_sites_set_rf.argtypes = [vp, C.c_int, vp, vp]
     L.bh_sites_set_x.argtypes = [vp, C.c_int, vp, vp, vp, vp]
@@ -252,7 +253,7 @@ def load_library():
         getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
-                 "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_chain_propose", "bh_chain_accept",
+                 "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_probe_swd_secular", "bh_chain_propose", "bh_chain_accept",
                  "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all",
                  "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_GAUSS_SYMBOLS + SITE_PRIORS_SYMBOLS + SITE_RF_AXIS_SYMBOLS + SITE_LAWS_SYMBOLS + CHAIN_RECORD_SYMBOLS:
         getattr(L, name).restype = C.c_int
@@ -274,7 +275,7 @@ DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_e
                  "bh_engine_last_swd_order",
                  "bh_engine_set_swd_scan",
                  "bh_engine_get_swd_scan", "bh_engine_set_tuning",
-                 "bh_engine_get_tuning", "bh_probe_math", "bh_engine_set_instrumentation", "bh_timing_reset",
+                 "bh_engine_get_tuning", "bh_probe_math", "bh_probe_swd_secular", "bh_engine_set_instrumentation", "bh_timing_reset",
                  "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace")
 # include/bh_engine_sites.h: many stations at once (site-indexed observed data)
 SITE_SYMBOLS = ("bh_sites_set", "bh_evaluate_sites")
@@ -860,6 +861,26 @@ class Engine(object):
         x = _f64(x).ravel()
         out = np.zeros(x.size // 2 if op in (6, 7) else x.size)
         self._check(self._L.bh_probe_math(self._h, int(op), out.size, x.ctypes.data_as(_d), out.ctypes.data_as(_d)))
+        return out
+
+    def probe_swd_secular(self, evaluator, ifunc, mmax, d, a, b, rho, wvno, omega, out=None):
+        """bh_probe_swd_secular (include/bh_engine_debug.h): the secular function of ONE model (rows d, a, b, rho: binary32, mtop of
+        them, the first mmax the model) at the points (wvno[i], omega[i]).  evaluator 0 the exact arithmetic, 1 fa::*_secular,
+        2 lean_rayleigh / lean_love.  `out` (optional): the float64 array written to (left untouched by a refused call)."""
+        f = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in (d, a, b, rho)]
+        mtop = f[0].size
+        if any(x.size != mtop for x in f):
+            raise ValueError("d, a, b, rho must have the same length")
+        wvno, omega = _f64(wvno).ravel(), _f64(omega).ravel()
+        if wvno.size != omega.size:
+            raise ValueError("wvno and omega must have the same length")
+        if out is None:
+            out = np.zeros(wvno.size)
+        if out.dtype != np.float64 or out.size != wvno.size or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous float64 array of the points' length")
+        self._check(self._L.bh_probe_swd_secular(self._h, int(evaluator), int(ifunc), int(mmax), mtop, f[0].ctypes.data, f[1].ctypes.data,
+                                                 f[2].ctypes.data, f[3].ctypes.data, wvno.size, wvno.ctypes.data_as(_d),
+                                                 omega.ctypes.data_as(_d), out.ctypes.data_as(_d)))
         return out
 
     # -- device API (raw pointers; asynchronous) ---------------------------------------------

@@ -107,8 +107,30 @@ int bh_engine_get_tuning(bh_engine *e, const char *name, int *value);
  * Ops 11-16 run the receiver-function synthesis kernel's own fast functions (csrc/rf_kernel.hip, the same inlined text and
  * compile flags): 11 rcp_nr (1/x: hardware seed + one Newton step), 12 rsq_nr (1/sqrt(x), x > 0), 13 / 14 sin / cos of
  * sincos_cw (Cody-Waite reduction, meant for |x| < 2^20), 15 exp_cw (clamped to [-800, 800]; NaN passes through),
- * 16 csqrt_f (principal complex square root): in and out hold n / 2 pairs (re, im), n even.  BH_EINVAL for any other op. */
+ * 16 csqrt_f (principal complex square root): in and out hold n / 2 pairs (re, im), n even.
+ * Ops 17-23 run the dispersion kernels' fast arithmetic (namespace fa of csrc/swd_fa.h, compiled in csrc/swd_fa_probe.hip with the
+ * flags of the trial-per-lane kernel): 17 rcp (1/x: hardware seed + two Newton steps), 18 rcp1 (one step), 19 / 20 the s = sqrt(x)
+ * and rs = 1/sqrt(x) of sqrt_rsqrt (x > 0, normal), 21 / 22 sin / cos of sincos (0 <= x <= 9e4), 23 expneg: out = e^-in
+ * (0 <= in <= 700).  BH_EINVAL for any other op (negative, or 24 and beyond). */
 int bh_probe_math(bh_engine *e, int op, int n, const double *in, double *out);
+
+/* The secular function of ONE model at n points, evaluated by the dispersion kernels' own code (csrc/swd_fa_probe.hip): lane i
+ * returns the value at wavenumber wvno[i] and angular frequency omega[i] (host pointers).  ifunc: 1 Love, 2 Rayleigh.  The model
+ * is mtop rows of d, a, b, rho (thickness, vp, vs, density; binary32 as at the f2py boundary), the first mmax of them its layers
+ * (the last one the half-space); rows mmax .. mtop - 1 are the ragged filler of a batch and are read by no evaluator.  No water
+ * layer (llw = 1).  evaluator:
+ *   0  the exact evaluators of csrc/swd_common.h (rayleigh_secular<true> / love_secular<true>: the reference's operations, the
+ *      glibc-exact libm tables staged in LDS as the kernels stage them),
+ *   1  fa::rayleigh_secular / fa::love_secular (csrc/swd_fa.h): what the FA builds of the lane kernel call,
+ *   2  lean_rayleigh / lean_love over a LeanModel (csrc/swd_lean.hip: reciprocal rows by fa::rcp, a normalisation every second
+ *      layer): what the trial-per-lane kernel calls.
+ * Every evaluator returns the first entry of the surface vector scaled by the vector's max-norm (e1 / max(|e1|, |e2|) for Love,
+ * e[0] / max |e| for Rayleigh).  BH_EINVAL -- with `out` untouched -- for another evaluator or wave type, mmax < 2, mmax > mtop,
+ * mtop > 32 with evaluator 2 (the lean kernel's arrays) or > 100 (the Fortran's limit, surfdisp96.f:59) with the others.
+ * The group kernel's layer-parallel FA build (swd_group_kernel<FA>) is NOT probed: its evaluation is spread over the lanes of a
+ * group and cannot be separated from its kernel; it stays covered end to end (tests/test_gpu_swd_lean.py, test_gpu_swd.py). */
+int bh_probe_swd_secular(bh_engine *e, int evaluator, int ifunc, int mmax, int mtop, const float *d, const float *a, const float *b,
+                         const float *rho, int n, const double *wvno, const double *omega, double *out);
 
 /* Instrumentation (off by default; bench.py and the tests turn it on).
  *   timing:   HIP events are recorded on the stream the kernels are launched on, around each

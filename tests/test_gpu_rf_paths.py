@@ -103,8 +103,9 @@ def test_probe_csqrt(engine):
 
 
 def test_probe_rejects_unknown_ops(engine):
-    with pytest.raises(E.EngineError):
-        engine.probe_math(17, np.ones(4))
+    for op in (24, -1):                    # (17-23: the dispersion kernels' fast arithmetic, tests/test_gpu_swd_fa.py)
+        with pytest.raises(E.EngineError):
+            engine.probe_math(op, np.ones(4))
 
 
 # ---- coefficient paths --------------------------------------------------------------------------------------------------------
