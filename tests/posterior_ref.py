@@ -7,8 +7,11 @@ d_j = cumsum(zd_j - zd_{j-1}) in float64; the interface depths of the 2-D plot a
 the differences rounded to it.  vs at depth x = vs[#{j : d_j <= x}].
 """
 from fractions import Fraction
+import math
 
 import numpy as np
+
+NO_BIT = np.iinfo(np.int32).max   # low_bit of 0.0: it has no set bit
 
 
 def split(models):
@@ -106,6 +109,68 @@ def exact_mean_std(col):
     n = len(fr)
     m = sum(fr) / n
     return m, sum((f - m) ** 2 for f in fr) / n
+
+
+def low_bit(v):
+    """The exponent of the lowest set bit of every float64 value (NO_BIT for +-0): v is an odd multiple of 2^low_bit."""
+    m, e = np.frexp(np.asarray(v, np.float64))                    # |m| in [0.5, 1): m * 2^53 is an integer
+    mi = np.ldexp(np.abs(m), 53).astype(np.int64)
+    tz = np.frexp((mi & -mi).astype(np.float64))[1] - 1           # trailing zeros (a power of two converts exactly)
+    return np.where(mi == 0, NO_BIT, e.astype(np.int64) - 53 + tz)
+
+
+def scale_rule(vsi):
+    """The fixed-point rule of include/bh_engine_posterior.h for every column of vsi [N, D], N >= 1: (scale, x0, exact), lists of
+    Python ints.  scale = the lowest set bit of the column, raised to ea - 62 where max|v| < 2^ea would not stay below 2^62 (exact
+    = 0 then); a column of zeros has scale 0; x0 = rint(min * 2^-scale)."""
+    vsi = np.asarray(vsi, np.float64)
+    low = low_bit(vsi).min(0)
+    vmn = vsi.min(0)
+    amax = np.maximum(np.abs(vmn), np.abs(vsi.max(0)))
+    scale, x0, exact = [], [], []
+    for j in range(vsi.shape[1]):
+        L, ex = 0, 1
+        if amax[j] > 0:
+            ea = math.frexp(amax[j])[1]
+            L, ex = max(int(low[j]), ea - 62), int(low[j] >= ea - 62)
+        scale.append(L)
+        exact.append(ex)
+        x0.append(int(Fraction(float(vmn[j])) * Fraction(2) ** -L) if ex else int(np.rint(np.ldexp(vmn[j], -L))))
+    return scale, x0, exact
+
+
+def _colsum(u):
+    """Exact column sums of a uint64 array (fewer than 2^32 rows) as Python ints."""
+    lo = (u & np.uint64(0xffffffff)).sum(0, dtype=np.uint64)
+    hi = (u >> np.uint64(32)).sum(0, dtype=np.uint64)
+    return [int(a) + (int(b) << 32) for a, b in zip(lo, hi)]
+
+
+def int_sums(vsi, scale, x0):
+    """Per column (sum(Y), sum(Y * Y)) as Python ints, Y = rint(v * 2^-scale) - x0 (an integer in [0, 2^63))."""
+    vsi = np.asarray(vsi, np.float64)
+    X = np.rint(np.ldexp(vsi, -np.asarray(scale, np.int32)[None, :])).astype(np.int64)   # |X| < 2^62: exact in int64
+    Y = X - np.asarray(x0, np.int64)[None, :]
+    assert (Y >= 0).all()
+    Y = Y.astype(np.uint64)
+    a, b = Y & np.uint64(0xffffffff), Y >> np.uint64(32)          # Y = a + b 2^32: a^2, a b and b^2 fit 64 bits
+    s1 = _colsum(Y)
+    aa, ab, bb = _colsum(a * a), _colsum(a * b), _colsum(b * b)
+    return s1, [p + (q << 33) + (r << 64) for p, q, r in zip(aa, ab, bb)]
+
+
+def exact_mean(n, s1, scale, x0):
+    """The exact mean of a column from sum(Y): a Fraction."""
+    return Fraction(s1 + n * x0, n) * Fraction(2) ** scale
+
+
+def exact_std(n, s1, s2, scale, bits=100):
+    """The population std of a column from its integer sums, as a Fraction carried to `bits` bits: floor(sqrt(V) 2^k) / 2^k
+    with V = n sum(Y^2) - sum(Y)^2 = n^2 var 2^(-2 scale), below the exact value by less than 2^-bits of it."""
+    V = n * s2 - s1 * s1
+    assert V >= 0
+    k = max(0, bits - V.bit_length() // 2 + 1)
+    return Fraction(math.isqrt(V << (2 * k)), n << k) * Fraction(2) ** scale
 
 
 def singlemodels(models, dep):

@@ -97,3 +97,74 @@ def test_restatement_rejects_a_row_that_is_not_a_prefix():
     m = np.array([[3.0, 4.0, 1.0, 5.0], [3.0, np.nan, 1.0, np.nan]])
     with pytest.raises(ValueError):
         R.split(m)
+
+
+# ---- the exact integer sums, the scale rule and the extended-precision std (the oracle of tests/test_gpu_posterior_paths.py) ----
+
+def _ulp_apart(got, want):
+    """|got - want| in ulps of the larger of the two, `want` a Fraction."""
+    from fractions import Fraction
+    return abs(Fraction(got) - want) / Fraction(math.ulp(max(got, float(want))))
+
+
+@pytest.mark.parametrize("key", KEYS)
+def test_integer_sums_give_the_exact_mean_and_std_of_the_golden_columns(G, key):
+    from bayhunter_amd.posterior import _mean_std
+    vsi = G[key + "_vsi"]
+    n, D = vsi.shape
+    scale, x0, exact = R.scale_rule(vsi)
+    assert all(exact)
+    low = R.low_bit(vsi)
+    assert scale == [int(v) for v in low.min(0)]
+    s1, s2 = R.int_sums(vsi, scale, x0)
+    if key != "f64":
+        assert max(s1) < n << 25              # float32 values: every Y is below 2^25
+    for j in range(D):
+        mean, std = R.exact_mean(n, s1[j], scale[j], x0[j]), R.exact_std(n, s1[j], s2[j], scale[j])
+        assert abs(G[key + "_mean"][j] - float(mean)) <= 1e-13 * abs(float(mean))
+        assert abs(G[key + "_std"][j] - float(std)) <= 1e-13 * float(std)
+        m, s = _mean_std(n, [s1[j] & 0xffffffff, s1[j] >> 32] + [(s2[j] >> (32 * i)) & 0xffffffff for i in range(4)], scale[j], x0[j])
+        assert m == float(mean)                # int / int is correctly rounded
+        assert (s == 0.0) if std == 0 else _ulp_apart(s, std) <= 1
+    for j in range(0, D, 10):                  # ... and the sums are those of the values themselves
+        m, var = R.exact_mean_std(vsi[:, j])
+        assert m == R.exact_mean(n, s1[j], scale[j], x0[j])
+        std = R.exact_std(n, s1[j], s2[j], scale[j])
+        assert std * std <= var and var * (1 - 2.0 ** -98) <= std * std * (1 + 2.0 ** -98)
+
+
+def test_scale_rule_and_sums_of_hand_made_columns():
+    from fractions import Fraction
+    z = np.zeros((5, 1))
+    assert R.low_bit(z).min() == R.NO_BIT
+    assert R.scale_rule(z) == ([0], [0], [1])
+    assert R.int_sums(z, [0], [0]) == ([0], [0])
+    assert R.exact_std(5, 0, 0, 0) == 0
+    assert [int(v) for v in R.low_bit(np.array([1.0, 3.0, 0.75, -6.0, 2.0 ** -1074, 2.0 ** -1060 * 3]))] == [0, 0, -2, 1, -1074, -1060]
+    # 4.0 beside 2^-70: the scale is raised until 4.0 * 2^-scale < 2^62, and 2^-70 rounds to 0
+    c = np.array([[4.0], [2.0 ** -70], [4.0]])
+    assert R.scale_rule(c) == ([-59], [0], [0])
+    s1, s2 = R.int_sums(c, [-59], [0])
+    assert (s1, s2) == ([2 << 61], [2 << 122])
+    assert R.exact_mean(3, s1[0], -59, 0) == Fraction(8, 3)
+    assert float(R.exact_std(3, s1[0], s2[0], -59)) == math.sqrt(32 / 9.)
+    # two values one ulp apart: Y is 0 or 1, the mean lies between them and the std is half an ulp (or sqrt(2) / 3 of it)
+    a = 3.3
+    b = np.nextafter(a, 4.0)
+    u = Fraction(b) - Fraction(a)
+    c = np.array([[a, a], [b, b], [a, b]])
+    scale, x0, exact = R.scale_rule(c)
+    assert scale == [-51, -51] and exact == [1, 1] and x0 == [int(Fraction(a) / u)] * 2
+    s1, s2 = R.int_sums(c, scale, x0)
+    assert (s1, s2) == ([1, 2], [1, 2])
+    assert R.exact_mean(3, 2, -51, x0[0]) == Fraction(a) + 2 * u / 3
+    assert R.exact_std(2, 1, 1, -51) == u / 2
+    std = R.exact_std(3, 1, 1, -51)
+    assert std * std <= 2 * u * u / 9 <= std * std * (1 + Fraction(1, 1 << 98))
+    # large offsets: Y up to 2^62 - 1 uses every limb
+    c = np.array([[-2.0 ** 61], [2.0 ** 61 - 512.0], [1.0]])
+    scale, x0, exact = R.scale_rule(c)
+    assert (scale, x0, exact) == ([0], [-1 << 61], [1])
+    s1, s2 = R.int_sums(c, scale, x0)
+    ys = [0, (1 << 62) - 512, (1 << 61) + 1]
+    assert (s1, s2) == ([sum(ys)], [sum(y * y for y in ys)])
