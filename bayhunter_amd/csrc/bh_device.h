@@ -150,6 +150,12 @@ struct SwdMultiArgs {
     int restart;       // 1: in a launch of one model per wavefront a model the guard fires on starts again with the reference's
                        //    sequence in its own wavefront (the build with both sequences) instead of being listed for a re-run launch
     SwdTarget t[8];
+    // (behind everything else: the builds that do not read them keep the parent's argument layout and machine code)
+    int lean_prio;     // trial-per-lane kernel, a launch whose SIMDs each hold one Rayleigh and one Love wavefront: 0, or share | slice << 8 --
+                       //    the Rayleigh wavefront has the high issue priority in `share` of every eight time slices of 2^slice cycles, the
+                       //    Love wavefront in the others (swd_lean_kernel; the engine's decision, launch_swd_multi)
+    int lean_half;     // ... and a launch of exactly two workgroups per CU: a target's wavefronts per XCD in the FIRST pass of workgroups
+                       //    (CUs / 4), which says which Love position shares a SIMD with which Rayleigh position; 0: not known
 };
 // Dispersion periods per site (bh_sites_set_x, include/bh_engine_sites_x.h): an argument of its own of the SITE-PERIOD builds of
 // the dispersion kernels (swd_lean_x.hip, swd_group_x.hip: the same sources compiled with BH_SWD_SITEX), so that SwdMultiArgs

@@ -135,6 +135,7 @@ struct bh_engine {
     int last_swd_kernel = -1;              // bh_engine_last_swd_kernel
     bh_swd_launch swd_launches[3 * BH_MAX_TARGETS]{}; // bh_engine_last_swd_launches: of the most recent call with dispersion targets
     int n_swd_launches = 0;
+    const int32_t *last_swd_perm[2] = {nullptr, nullptr}; int last_swd_perm_n = 0; // bh_engine_last_swd_perm: what the ordering launch wrote (device)
     int last_swd_order[3] = {0, 0, 0};     // bh_engine_last_swd_order: the plan's order, the ordering launch's workgroups, its fills
     int err_t_nt = -1, err_t_B = -1;       // layout for which err_t's untouched rows are known to be zero
     std::string err;
@@ -1180,6 +1181,22 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
         a.counted = e->swd_scan;
         a.farith = p.farith ? 1 : 0;
         a.fast = p.any_fast ? 1 : 0;
+        // Issue priority shared out by the clock (swd_lean_kernel) where the dispatcher is known to put one Rayleigh and one
+        // Love wavefront on every SIMD: two targets with the same wavefront count in workgroups of four, more than one and at most
+        // two workgroups per CU (the second pass sits one SIMD on, build_slot_ranks).  Every other launch: as dispatched.
+        // Exactly two workgroups per CU (c2 at B = 4096 on 256 CUs): which positions share a SIMD is known too (lean_half), and
+        // the Love wavefront beside the Rayleigh wavefront of rank r takes the Love group of the opposite rank.
+        a.lean_prio = a.lean_half = 0;
+        const BhTuning &tun = bh_tuning();
+        if (p.ntargets == 2 && p.look[0] == 16 && p.look[1] == 16 && !p.sitex && a.t[0].iwave != a.t[1].iwave) { // (the build: swd_lean_kernel<16, ., true>)
+            const int mpw = BH_WAVE / p.look[0];
+            const long waves = 2L * ((B + mpw - 1) / mpw), wgs = (waves + 3) / 4, ncu = e->pairwork.ncu;
+            if (ncu > 0 && wgs > ncu && wgs <= 2 * ncu && waves % 4 == 0) {
+                const int slice = tun.swd_lean_slice >= 8 && tun.swd_lean_slice <= 24 ? tun.swd_lean_slice : LEAN_PRIO_SLICE;
+                if (tun.swd_lean_share > 0 && tun.swd_lean_share <= 8) a.lean_prio = tun.swd_lean_share | (slice << 8);
+                if (wgs == 2 * ncu && ncu % 32 == 0 && tun.swd_lean_no_half == 0) a.lean_half = (int)(ncu / 4);
+            }
+        }
     } else {
         for (int t = 0; t < 2; ++t) a.t[t].perm = c.pair_perm[t];
         set_group_args(a, c.g);
@@ -1205,7 +1222,7 @@ int launch_swd_multi(SwdCall &c, SwdMultiArgs &a)
         SwdLaneBuild lb{};
         if ((p.sitex ? bh_launch_swd_lean_x(a, c.sx, c.st, &c.info, &lb) : bh_launch_swd_lean(a, c.st, &c.info, &lb)) != 0)
             return fail(e, BH_EINVAL, "model too deep for LDS");
-        note_launch(e, BH_KERNEL_LEAN, BH_SWD_MAIN, lb.key, false, p.ntargets == 2, false, false, lb.grid_x, 0);
+        note_launch(e, BH_KERNEL_LEAN, BH_SWD_MAIN, lb.key, false, p.ntargets == 2, false, false, lb.grid_x, a.lean_prio >> 8);
     } else {
         if (!p.sitex) bh_launch_swd_group(a, c.g, c.st);
         else if (!bh_launch_swd_group_x(a, c.g, c.sx, c.st)) return fail(e, BH_EUNSUPPORTED, "no site-period build of this dispersion launch");
@@ -1316,6 +1333,8 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
     if (p.any_fast && (rc = guard_space(e, st, B, prologue, &c.gcounts, &c.glists))) return rc;
     if ((rc = order_models(c))) return rc;
     e->last_swd_order[0] = p.order;
+    for (int t = 0; t < 2; ++t) e->last_swd_perm[t] = p.order == ORDER_NONE ? nullptr : (c.pair_perm[t] != nullptr ? c.pair_perm[t] : c.perm);
+    e->last_swd_perm_n = B;
     e->last_swd_order[1] = c.order_wgs;
     e->last_swd_order[2] = !p.prologue ? 0 : (c.fills.nguard > 0 ? BH_FILL_GUARD : 0) | (c.fills.nerr > 0 ? BH_FILL_FLAGS : 0) | (c.fills.ncounter > 0 ? BH_FILL_COUNTERS : 0);
     SwdMultiArgs a{};
@@ -1538,6 +1557,15 @@ int bh_engine_set_swd_arith(bh_engine *e, int arith)
 }
 int bh_engine_get_swd_arith(const bh_engine *e) { return e ? e->swd_arith : 0; }
 int bh_engine_last_swd_kernel(const bh_engine *e) { return e ? e->last_swd_kernel : -1; }
+int bh_engine_last_swd_perm(bh_engine *e, int target, int32_t *out, int n)
+{
+    if (!e || !out || target < 0 || target > 1 || n < 0) return BH_EINVAL;
+    if (e->last_swd_perm[target] == nullptr) return 0;
+    if (n < e->last_swd_perm_n) return BH_EINVAL;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    HIPCHK(e, hipMemcpy(out, e->last_swd_perm[target], (size_t)e->last_swd_perm_n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return e->last_swd_perm_n;
+}
 int bh_engine_last_swd_order(const bh_engine *e, int *workgroups, int *fills)
 {
     if (workgroups) *workgroups = e ? e->last_swd_order[1] : 0;

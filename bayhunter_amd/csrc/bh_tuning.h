@@ -41,6 +41,9 @@
     X(swd_rerun_wgs,     "BH_SWD_RERUN_WGS",    256, "workgroups per target of the re-run launch of guarded models, striding over the list (0 = one wavefront per model of the batch, as before round 6)") \
     X(swd_gsplit,        "BH_SWD_GSPLIT",  16777216, "group velocities (fundamental mode): calls of up to this many (model, period) pairs per target -- 2^24, the most the launch indexes -- run the chain of first roots and the second roots as two launches (0 = one search after the other in one launch)") \
     X(swd_lean_flip,     "BH_SWD_LEAN_FLIP",    256, "trial-per-lane kernel, two targets: 256 = the second target takes the models in the opposite order (0: the same order); + n: the targets of a wavefront pair swap with bit n-1 of the workgroup index") \
+    X(swd_lean_share,    "BH_SWD_LEAN_SHARE",     7, "trial-per-lane kernel, one Rayleigh and one Love wavefront per SIMD: eighths of the time the Rayleigh wavefront has the high issue priority, 1..8 (0: no priorities, the older wavefront is served first)") \
+    X(swd_lean_slice,    "BH_SWD_LEAN_SLICE",     0, "... log2 of the time slice in cycles, 8..24 (0 = LEAN_PRIO_SLICE)")                            \
+    X(swd_lean_no_half,  "BH_SWD_LEAN_NO_HALF",   0, "flag: trial-per-lane kernel: the opposite order of the second target does not follow the dispatcher's two passes of workgroups") \
     X(no_order,          "BH_NO_ORDER",           0, "flag: models processed in the caller's order")                                                 \
     X(no_overlap,        "BH_NO_OVERLAP",         0, "flag: receiver function after the dispersion kernel, not beside it")                           \
     X(no_started,        "BH_NO_STARTED",         0, "flag: no start gate (stream memory operation) for the receiver-function stream")               \
@@ -58,6 +61,10 @@
     X(rf_threads,        "BH_RF_THREADS",         0, "threads of a synthesis workgroup: 128 (0 = 256)")                                              \
     X(rf_waves,          "BH_RF_WAVES",           0, "register budget of the synthesis kernel: 3 wavefronts per SIMD (0 = 4)")                       \
     X(debug_plan,        "BH_DEBUG_PLAN",         0, "flag: print launch plans to stderr")
+
+// swd_lean_kernel's launches of one Rayleigh and one Love wavefront per SIMD (c2: 4096 models on 256 CUs; tools/gpu_lean_schedule.py):
+constexpr int LEAN_PRIO_SLICE = 16;       // log2 cycles of a slice of the priority schedule: shares 7 / 8, slices 2^15 .. 2^17 0.601-0.602 ms
+                                          // (6 / 8: 0.614; 2^14: 0.609; 2^18: 0.618; no priorities: 0.637)
 
 struct BhTuning {
 #define X(field, env, dflt, doc) int field = dflt;

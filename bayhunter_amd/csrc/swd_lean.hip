@@ -161,7 +161,9 @@ constexpr int LEAN_WPB = 4; // wavefronts per workgroup: independent (no barrier
 // CNT: the build with the evaluation counters and the round clocks (launches with A.neval set: bh_engine_set_instrumentation's
 // `counting`).  The counters cost 12 registers; without them the <16> build needs 197 (200 allocated), so that an 88-register
 // receiver-function wavefront fits beside the two dispersion wavefronts of a SIMD (2 x 200 + 88 <= 512).
-template <int J, bool CNT>
+// PAIRED: the build for launches of one Rayleigh and one Love wavefront per SIMD (A.lean_prio / A.lean_half, see below; 16 trials,
+// periods of the call): only it reads the two words and carries the priority schedule -- every other launch runs the build it always had.
+template <int J, bool CNT, bool PAIRED = false>
 #if BH_SWD_SITEX
 __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiArgs A, int wave_lds, int flip, SwdSiteXArgs X)
 #else
@@ -187,7 +189,12 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
         if ((flip & 256) && ty == 1) {
             if (flip & 2048) { // inside the wavefront's XCD (the models may be ordered per XCD, bh_launch_pair_order): its q-th wavefront of the
                                // target takes the (Q - 1 - q)-th group
-                const int x = (wid >> 1) & 7, q = ((wid >> 4) << 1) | (wid & 1), qr = A.wg_n1 / 8 - 1 - q;
+                // A launch of two workgroups per CU (A.lean_half = H positions per pass): the second workgroup of a CU sits one SIMD on
+                // (build_slot_ranks, bh_engine.hip), so Love position p < H shares its SIMD with Rayleigh position p + H, and p >= H
+                // with (p - H) ^ 1 -- the per-wavefront records of the counting build show exactly these pairs -- and the group it
+                // takes is the opposite of THAT rank.  (Q - 1 - q pairs the long halves of both targets with each other.)
+                const int x = (wid >> 1) & 7, q = ((wid >> 4) << 1) | (wid & 1), Q = A.wg_n1 / 8, H = PAIRED ? A.lean_half : 0;
+                const int qr = (2 * H != Q) ? Q - 1 - q : (q < H ? H - 1 - q : Q - 1 - ((q - H) ^ 1));
                 wid = ((qr >> 1) << 4) + 2 * x + (qr & 1);
             } else {
                 wid = A.wg_n1 - 1 - wid;
@@ -356,8 +363,22 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
     unsigned nrounds = 0;
     long long t_eval = 0;
     const long long t_start = ((CNT && A.neval != nullptr)) ? clock64() : 0;
+    const unsigned long long w_start = ((CNT && A.neval != nullptr)) ? wall_clock64() : 0ull;
+    // ISSUE PRIORITY BY THE CLOCK.  Two wavefronts share a SIMD, and at equal priority the hardware serves the older one first: it
+    // runs at the pace of a wavefront alone, the younger one at six tenths of that, and once the older has finished the younger
+    // has the SIMD to itself for the rest of the launch -- nearly half of it, at the throughput of one wavefront instead of the
+    // 1.6 of two (the per-wavefront records of the counting build, tools/gpu_lean_schedule.py).  Where the engine knows that
+    // every SIMD holds one Rayleigh and one Love wavefront (A.lean_prio), the two take the high priority in turn, by time slices
+    // of the shader clock they share: the Rayleigh wavefront, which has the more work, in `share` of every eight slices, the Love
+    // wavefront in the others, so that both stay resident until close to the end.  Scheduling only.
+    const int prio_share = PAIRED ? (A.lean_prio & 15) : 0, prio_slice = PAIRED ? (A.lean_prio >> 8) : 0;
     while (__ballot(active) != 0ull) {
         ++nrounds;
+        if (PAIRED && prio_share != 0) {
+            const bool first = ((unsigned)(__builtin_readcyclecounter() >> prio_slice) & 7u) < (unsigned)prio_share;
+            if (first == (ifunc == 2)) __builtin_amdgcn_s_setprio(2);
+            else __builtin_amdgcn_s_setprio(0);
+        }
         // ---- this lane's trial velocity (and frequency)
         double cev = c1, cprev = c1; // cprev: the grid point before a scan trial
         double om_l = omega, iom_l = iom;
@@ -906,8 +927,19 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
             atomicAdd(A.neval + o, (unsigned long long)nrounds);
             atomicAdd(A.neval + o + 1, (unsigned long long)(clock64() - t_start));
             atomicMax(A.neval + o + 2, (unsigned long long)nrounds);
-            atomicAdd(A.neval + 7, 1ull);
+            const unsigned long long widx = atomicAdd(A.neval + 7, 1ull);
             atomicAdd(A.neval + (ifunc == 2 ? 12 : 13), (unsigned long long)t_eval); // cycles inside the secular evaluations
+            if (widx < BH_TRACE_WAVES) { // one record per wavefront, swd_group_kernel's layout (tools/gpu_lean_schedule.py): where it ran, how long, its rounds
+                unsigned long long *rec = A.neval + BH_COUNTER_WORDS + 4 * widx;
+                unsigned hwid, xcc;
+                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+                hwid = (hwid & 0xffffu) | ((xcc & 0xfu) << 16);
+                rec[0] = w_start;
+                rec[1] = wall_clock64();
+                rec[2] = ((unsigned long long)(clock64() - t_start) & 0xffffffffffull) | ((unsigned long long)(unsigned)(blockIdx.x * LEAN_WPB + wave) << 40); // cycles | grid wavefront index << 40
+                rec[3] = (unsigned long long)nrounds | ((unsigned long long)ifunc << 32) | ((unsigned long long)hwid << 36);
+            }
         }
         if (writer && guard && greason >= 1 && greason <= 7) // guard reasons, 16 bits each: 1 .. 4 in word 14, 5 .. 7 in word 15
             atomicAdd(A.neval + (greason <= 4 ? 14 : 15), 1ull << (16 * ((greason - 1) & 3)));
@@ -1080,6 +1112,13 @@ int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo
         if (cnt) hipLaunchKernelGGL((swd_lean_kernel<JJ, true>), grid, block, lds, stream, a, (int)wave_lds, flip);                 \
         else hipLaunchKernelGGL((swd_lean_kernel<JJ, false>), grid, block, lds, stream, a, (int)wave_lds, flip);                    \
     } while (0)
+#endif
+#if !BH_SWD_SITEX
+    if (J == 16 && (a.lean_prio != 0 || a.lean_half != 0)) { // one Rayleigh and one Love wavefront per SIMD (the engine's decision, launch_swd_multi)
+        if (cnt) hipLaunchKernelGGL((swd_lean_kernel<16, true, true>), grid, block, lds, stream, a, (int)wave_lds, flip);
+        else hipLaunchKernelGGL((swd_lean_kernel<16, false, true>), grid, block, lds, stream, a, (int)wave_lds, flip);
+        return 0;
+    }
 #endif
     switch (J) {
     case 4: LEAN_LAUNCH(4); break;

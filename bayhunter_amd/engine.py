@@ -136,6 +136,7 @@ def load_library():
     L.bh_engine_last_swd_kernel.argtypes = [vp]
     L.bh_engine_last_swd_launches.argtypes = [vp, C.POINTER(SwdLaunch), C.c_int, C.POINTER(C.c_int)]
     L.bh_engine_last_swd_order.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bh_engine_last_swd_perm.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), C.c_int]
     L.bh_engine_set_swd_trials.argtypes = [vp, C.c_int]
     L.bh_engine_get_swd_trials.argtypes = [vp]
     L.bh_engine_get_swd_arith.argtypes = [vp]
@@ -272,7 +273,7 @@ EXPORTED_SYMBOLS = ("bh_abi_version", "bh_engine_create", "bh_engine_destroy", "
                     "bh_chain_propose", "bh_chain_accept", "bh_chain_propose_window", "bh_chain_accept_window")
 # include/bh_engine_debug.h: measurement, diagnostics, experiment switches (bench.py, tools/, tests)
 DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_last_swd_kernel", "bh_engine_last_swd_launches",
-                 "bh_engine_last_swd_order",
+                 "bh_engine_last_swd_order", "bh_engine_last_swd_perm",
                  "bh_engine_set_swd_scan",
                  "bh_engine_get_swd_scan", "bh_engine_set_tuning",
                  "bh_engine_get_tuning", "bh_probe_math", "bh_probe_swd_secular", "bh_engine_set_instrumentation", "bh_timing_reset",
@@ -515,6 +516,15 @@ class Engine(object):
         order = self._L.bh_engine_last_swd_order(self._h, C.byref(wg), C.byref(fills))
         return ({0: "none", 1: "depth", 2: "length", 3: "pair"}.get(order), int(wg.value),
                 {n for b, n in ((1, "guard"), (2, "flags"), (4, "counters")) if fills.value & b})
+
+    def last_swd_perm(self, target, B):
+        """The processing order the most recent call with dispersion targets computed for target 0 / 1 of its launch
+        (bh_engine_last_swd_perm): int32 [B], or None where it kept the caller's order."""
+        out = np.zeros(int(B), dtype=np.int32)
+        n = self._L.bh_engine_last_swd_perm(self._h, int(target), out.ctypes.data_as(C.POINTER(C.c_int32)), int(B))
+        if n < 0:
+            self._check(n)
+        return out[:n] if n > 0 else None
 
     def swd_arith(self):
         return "fast" if self._L.bh_engine_get_swd_arith(self._h) == ARITH_FAST else "exact"

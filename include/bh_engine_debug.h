@@ -48,7 +48,8 @@ int bh_engine_last_swd_kernel(const bh_engine *e);
  *   BH_KERNEL_LANE   IFUNC, LOOK, WPB, FAST, SIMPLE, FA     (swd_kernel)
  *   BH_KERNEL_LEAN   J, CNT, 0, 0, 0, 0                     (swd_lean_kernel)
  * and the launch's features: two depth classes, two targets interleaved in one grid, the SIMD-pairing order of the models,
- * restart in place of guarded models, workgroups in x, the lane kernel's priority time slice (log2 cycles; 0 = none).
+ * restart in place of guarded models, workgroups in x, the priority time slice of the lane kernel and of the trial-per-lane
+ * kernel's launches of one Rayleigh and one Love wavefront per SIMD (log2 cycles; 0 = none).
  * Writes at most `max` records and returns their number in *n. */
 typedef struct {
     int family, role, key[6];
@@ -74,6 +75,10 @@ int bh_engine_last_swd_launches(const bh_engine *e, bh_swd_launch *out, int max,
 #define BH_FILL_FLAGS 2
 #define BH_FILL_COUNTERS 4
 int bh_engine_last_swd_order(const bh_engine *e, int *workgroups, int *fills);
+/* The processing order the most recent call with dispersion targets computed for target 0 / 1 of its launch (diagnostic): entry
+ * w * m + i of out[0 .. B) is the model that wavefront w of the target takes as its i-th (m models per wavefront).  Returns B, 0
+ * where the call kept the caller's order (BH_ORDER_NONE), a negative BH_E* for a bad argument (n < B).  Waits for the stream. */
+int bh_engine_last_swd_perm(bh_engine *e, int target, int32_t *out, int n);
 
 /* The bracket scan of Love targets (any root refinement).  Results never depend on this setting.
  * getsol's scan (surfdisp96.f:437-460) evaluates every step of its grid until the secular function changes sign.  For Love
