@@ -44,6 +44,7 @@
     X(swd_lean_share,    "BH_SWD_LEAN_SHARE",     7, "trial-per-lane kernel, one Rayleigh and one Love wavefront per SIMD: eighths of the time the Rayleigh wavefront has the high issue priority, 1..8 (0: no priorities, the older wavefront is served first)") \
     X(swd_lean_slice,    "BH_SWD_LEAN_SLICE",     0, "... log2 of the time slice in cycles, 8..24 (0 = LEAN_PRIO_SLICE)")                            \
     X(swd_lean_no_half,  "BH_SWD_LEAN_NO_HALF",   0, "flag: trial-per-lane kernel: the opposite order of the second target does not follow the dispatcher's two passes of workgroups") \
+    X(swd_lean_no_skip,  "BH_SWD_LEAN_NO_SKIP",   0, "flag: trial-per-lane kernel: a Love target's first period scans every round from its start value, also the rounds below the model's slowest S velocity, where its function has no sign change") \
     X(no_order,          "BH_NO_ORDER",           0, "flag: models processed in the caller's order")                                                 \
     X(no_overlap,        "BH_NO_OVERLAP",         0, "flag: receiver function after the dispersion kernel, not beside it")                           \
     X(no_started,        "BH_NO_STARTED",         0, "flag: no start gate (stream memory operation) for the receiver-function stream")               \

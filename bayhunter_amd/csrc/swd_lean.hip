@@ -341,6 +341,58 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
         omega = omg[0];
         iom = fa::rcp(omega); // (restated by swd_probe_secular_kernel below, evaluator 2)
     }
+    // LOVE'S FIRST PERIOD RESUMES ITS SCAN NEXT TO THE SLOWEST S VELOCITY.  The first period's scan walks up from cm, 0.79 x the
+    // slowest S velocity vmin of the model (half-space included) -- but below vmin the Love function AS COMPUTED HERE has no sign
+    // change: with c < vs(i) every layer is evanescent, love_terms gives cosq = 0.5 + hf > 0, sn = 0.5 - hf >= 0 (expneg <= 1) and
+    // y, z >= 0, the half-space gives e1 = rho rb > 0, e2 = ib^2 > 0, and every love_step is a sum of products of positive numbers
+    // over a positive norm: nothing cancels, the sign is certain.  So the m whole rounds of that scan whose points all lie below
+    // vmin are not run: the search starts in the state it has after them -- c1 = b_m, the grid rebased as the rounds do it
+    // (b_1 = fma(J - 1, dc, cm), b_j+1 = fma(J, dc, b_j): the same m fused operations, so every later grid point has the bits it had),
+    // PH_SCAN, upward, start value positive (s1stneg = false; del1: any positive number), no point before c1.
+    //   * m is the largest count for which the first TWO trials of the resumed round, fma(1 | 2, dc, b_m), lie at or below
+    //     vmin - dc.  Both are certified positive and no other event can lie there (a half-space velocity or betmx is >= vmin,
+    //     cev >= cm), so the round's first event is at trial >= 2: c1, del1, cp, delp are all taken from evaluated lanes (ns >= 2 in
+    //     the scan's stage below) before anything reads them, and a bracket's third point is the one it always had.
+    //   * Nothing may be skipped that would have fired the guard: on a scan point that is a value that is not a number or is
+    //     below fa::SIGN_FLOOR.  Every skipped point and the two leading ones have cm <= c <= vmin - dc, k = omega / c.
+    //     Not a number comes only from q = d rb >= 9e4 (love_terms), and rb^2 = (k + kb)(k - kb) <= k^2, k <= omega / cm:
+    //     dmax omega <= 4.5e4 cm rules it out (half the limit: the roundings of rcp, sqrt_rsqrt and the products are 1e-15).
+    //     The value: with t = e1 / e2 and mu = rho vs^2 the half-space starts at t = mu rb and a layer maps t to
+    //     (mu rb tau + t) / (t tau / (mu rb) + 1), tau = sn / cosq in [0, 1), which lies between t and mu rb -- so t never leaves
+    //     the range of mu_i rb_i over the layers, and what love_step's max-norm returns is min(1, t).  rb_i^2 >= k^2 -
+    //     omega^2 / vmin^2 = omega^2 (vmin - c)(vmin + c) / (c vmin)^2 >= omega^2 dc vmin / vmin^4 at c <= vmin - dc, so
+    //     min(1, t) >= min(1, mumin omega sqrt(dc / vmin^3)).  Asked for: that bound >= 1e-9, a thousand floors, compared as
+    //     squares -- the bound drops the factor (vmin + c) / vmin (1.8 where cm = 0.79 vmin), the rounding of vmin - dc is 2e-12 of
+    //     dc at most, and the computed value differs from the exact one by a few 1e-16 relative per layer (positive terms only):
+    //     all of it a dozen orders of magnitude inside that margin.  A model of one layer returns the half-space's unscaled
+    //     rho rb: not skipped.
+    // Where a condition fails m = 0: the scan as it always was.  Rayleigh has no such certificate (the compound matrix is not
+    // sign-definite below the slowest velocity) and takes none of this.  Scheduling only: flip & 8192 (swd_lean_no_skip) turns it off.
+    if (ifunc == 1 && !(flip & 8192) && active && mmax >= 2) {
+        double vmin = md.Bv(0), mumin = md.R(0) * (md.Bv(0) * md.Bv(0)), dmax = 0.0;
+        for (int i = 1; i < mmax; ++i) {
+            const double bi = md.Bv(i);
+            vmin = fmin(vmin, bi);
+            mumin = fmin(mumin, md.R(i) * (bi * bi));
+            dmax = fmax(dmax, md.D(i - 1));
+        }
+        const double lim = vmin - dc;
+        if (omega > 0.0 && dmax * omega <= 4.5e4 * cm && (mumin * mumin) * ((omega * omega) * dc) >= 1.0e-18 * (vmin * vmin * vmin)) {
+            double b = cm;
+            int m = 0;
+            for (;;) {
+                const double bn = __builtin_fma((double)(m == 0 ? J - 1 : J), dc, b);
+                if (!(__builtin_fma(2.0, dc, bn) <= lim)) break;
+                b = bn;
+                ++m;
+            }
+            if (m > 0) {
+                c1 = b;
+                del1 = 1.0;
+                ph = PH_SCAN;
+            }
+        }
+    }
     constexpr unsigned long long maskJ = (J >= 64) ? ~0ull : ((1ull << J) - 1ull);
     // THE NEXT PERIOD'S FIRST ROUND RIDES ALONG.  The estimate x that a round of clustered trials is centred on -- the inverse
     // quadratic point through the bracket's ends and the grid point before them -- is within 2e-7 |x| of the root in 99.9 %
@@ -1095,6 +1147,7 @@ int bh_launch_swd_lean(const SwdMultiArgs &a0, hipStream_t stream, SwdLaunchInfo
     }
     int flip = bh_tuning().swd_lean_flip;
     if (a.ntargets == 2 && nw[0] == nw[1] && nw[1] % 16 == 0) flip |= 2048; // (the opposite order can stay inside the XCDs)
+    if (bh_tuning().swd_lean_no_skip != 0) flip |= 8192;                            // (Love's first period scans from cm, see the kernel)
     const int J = a.t[0].look; // (one trial count per launch: the kernel is compiled per count)
     for (int t = 1; t < a.ntargets; ++t)
         if (a.t[t].look != J) return -1;

@@ -24,23 +24,58 @@ f32 = np.float32
 DC = float(f32(0.005))
 
 
-def counted_rounds(nlay, h, vp, vs, rho, periods, iwave, lanes=16, cluster=2):
-    """rounds[B] (0 for a model whose search fails), steps[B, K]: grid steps from every period's start value to its sign change"""
+def start_values(nlay, vp, vs):
+    """cm[B]: the first period's start value, 0.9 x 0.95 x the Rayleigh velocity of the slowest layer (binary32)"""
     from oracle import oracle as O
-    B = nlay.size
-    with O.swd_search(2):
-        vel, err, _ = O.swd_batch(nlay, h.T, vp.T, vs.T, rho.T, periods, iwave, 0, mode=1)
-    cm = np.zeros(B)
-    for b in range(B):
+    cm = np.zeros(nlay.size)
+    for b in range(nlay.size):
         n = int(nlay[b])
         j = int(np.argmin(np.where(vs[:n, b] > 0.01, vs[:n, b], vp[:n, b])))
         c = f32(vp[j, b]) if vs[j, b] <= 0.01 else f32(O.gtsolh(vp[j, b], vs[j, b]))
         cm[b] = float(f32(0.90) * (f32(0.95) * c))
+    return cm
+
+
+def love_skip_rounds(nlay, h, vp, vs, rho, periods, lanes=16):
+    """m[B]: the whole rounds of the first period's Love scan that the kernel does not run -- all their grid points lie below the
+    model's slowest S velocity vmin, where the Love function has no sign change (swd_lean.hip; restated and held against the
+    reference's function in tests/test_love_scan_certificate.py).  The rounds rebase the grid, b_1 = cm + (lanes - 1) dc,
+    b_j+1 = b_j + lanes dc (n dc is exact in binary64: the kernel's fused operation); m is the largest count with
+    b_m + 2 dc <= vmin - dc, and 0 where the model alone does not bound the skipped values away from the guard's rules."""
+    cm, om, m = start_values(nlay, vp, vs), 2.0 * np.pi / float(periods[0]), np.zeros(nlay.size, np.int64)
+    for i in range(nlay.size):
+        n = int(nlay[i])
+        if n < 2:
+            continue
+        b, r, d = [x[:n, i].astype(f32).astype(float) for x in (vs, rho, h)]
+        vmin, mumin, dmax = b.min(), (r * (b * b)).min(), d[:n - 1].max()
+        if not (om > 0.0 and dmax * om <= 4.5e4 * cm[i] and (mumin * mumin) * ((om * om) * DC) >= 1.0e-18 * (vmin * vmin * vmin)):
+            continue
+        bm = cm[i]
+        while True:
+            bn = (lanes - 1 if m[i] == 0 else lanes) * DC + bm
+            if not (2.0 * DC + bn <= vmin - DC):
+                break
+            bm, m[i] = bn, m[i] + 1
+    return m
+
+
+def counted_rounds(nlay, h, vp, vs, rho, periods, iwave, lanes=16, cluster=2, love_skip=False):
+    """rounds[B] (0 for a model whose search fails), steps[B, K]: grid steps from every period's start value to its sign change.
+    love_skip: a Love target's rounds without those of love_skip_rounds, as the kernel runs them (off by default: the figures of
+    profiles/lean_schedule_model.txt and the golden fixture of tests/test_lean_schedule_model.py count every round of the scan)"""
+    from oracle import oracle as O
+    with O.swd_search(2):
+        vel, err, _ = O.swd_batch(nlay, h.T, vp.T, vs.T, rho.T, periods, iwave, 0, mode=1)
+    cm = start_values(nlay, vp, vs)
     ride = lanes - cluster
     steps = np.zeros_like(vel)
     steps[:, 0] = np.ceil((vel[:, 0] - cm) / DC)
     steps[:, 1:] = np.ceil((vel[:, 1:] - (vel[:, :-1] - 1.5 * DC)) / DC)
-    return rounds_from_steps(steps, lanes, ride) * (err == 0), steps
+    rounds = rounds_from_steps(steps, lanes, ride)
+    if love_skip and iwave == 1:
+        rounds = rounds - love_skip_rounds(nlay, h, vp, vs, rho, periods, lanes)
+    return rounds * (err == 0), steps
 
 
 def rounds_from_steps(steps, lanes=16, ride=14):

@@ -20,7 +20,7 @@ TURNS = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 B = 4096
 nlay, h, vp, vs, rho = synth_models(np.random.RandomState(SEED), B, 10, lvz_frac=0.1)
 RR, _ = S.counted_rounds(nlay, h, vp, vs, rho, SWD_PERIODS, 2)
-RL, _ = S.counted_rounds(nlay, h, vp, vs, rho, SWD_PERIODS, 1)
+RL, _ = S.counted_rounds(nlay, h, vp, vs, rho, SWD_PERIODS, 1, love_skip=not os.environ.get("BH_SWD_LEAN_NO_SKIP"))  # (as the kernel runs them)
 
 
 def host_perm(key):
