@@ -85,6 +85,49 @@ def record_rows(iter_burnin, iter_main, thinning):
 
 RECORD_MODES = ("host", "device")
 
+# DeviceChains(ladder_adapt=): sweeps per adaptation window, gain and decay of the gain (kappa = rate * lag / (n + lag) at the n-th
+# adaptation).  The values of the study on the idealised sampler (tests/test_ladder_sweep_ref.py).
+LADDER_ADAPT_DEFAULTS = dict(every=20, rate=0.5, lag=50.0)
+
+
+def ladder_adapt_options(ladder_adapt, betas, ladder, swap_every, dist=None):
+    """The merged options of DeviceChains(ladder_adapt=), checked without a GPU: None stays None.  ValueError: an unknown key, `every`
+    not an even integer >= 0, rate outside (0, 1), lag <= 0, no betas or swap_every == 0, with every > 0 a ladder whose betas
+    are not distinct.  EngineError: a job of more than one rank, BH_PT_HOST_EXCHANGE=1."""
+    if ladder_adapt is None:
+        return None
+    if not isinstance(ladder_adapt, dict):
+        raise ValueError("ladder_adapt must be None or a dict with keys of %s" % (sorted(LADDER_ADAPT_DEFAULTS),))
+    unknown = sorted(set(ladder_adapt) - set(LADDER_ADAPT_DEFAULTS))
+    if unknown:
+        raise ValueError("ladder_adapt: unknown key %r (known: %s)" % (unknown[0], sorted(LADDER_ADAPT_DEFAULTS)))
+    opt = dict(LADDER_ADAPT_DEFAULTS)
+    opt.update(ladder_adapt)
+    every = opt["every"]
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 0 or every % 2:
+        raise ValueError("ladder_adapt['every'] must be an even integer >= 0 (both parities fall into every window), not %r" % (every,))
+    opt["every"] = int(every)
+    opt["rate"], opt["lag"] = float(opt["rate"]), float(opt["lag"])
+    if not 0.0 < opt["rate"] < 1.0:
+        raise ValueError("ladder_adapt['rate'] must lie in (0, 1), not %r" % (opt["rate"],))
+    if not (opt["lag"] > 0.0 and np.isfinite(opt["lag"])):
+        raise ValueError("ladder_adapt['lag'] must be > 0, not %r" % (opt["lag"],))
+    if betas is None or int(swap_every) <= 0:
+        raise ValueError("ladder_adapt needs a tempered run: betas and swap_every > 0")
+    if opt["every"] > 0:
+        b = np.asarray(betas, dtype=np.float64).ravel()
+        lad = np.zeros(b.size, dtype=np.int64) if ladder is None else np.asarray(ladder, dtype=np.int64).ravel()
+        if lad.size != b.size:
+            raise ValueError("ladder_adapt: %d betas for %d ladder ids" % (b.size, lad.size))
+        for lid in np.unique(lad):
+            if np.unique(b[lad == lid]).size != np.count_nonzero(lad == lid):
+                raise ValueError("ladder_adapt: the betas of ladder %d are not distinct (an adapted ladder is strictly ordered)" % lid)
+    if dist is not None and dist.is_initialized() and dist.get_world_size() > 1:
+        raise EngineError("ladder_adapt: ladders are not adapted across ranks (world size %d)" % dist.get_world_size())
+    if os.environ.get("BH_PT_HOST_EXCHANGE", "0") == "1":
+        raise EngineError("ladder_adapt: the sweep kernel runs on the GPU; BH_PT_HOST_EXCHANGE=1 asks for the host exchange")
+    return opt
+
 
 # initparams the sites of one run must share: the chains advance in lock step (iter_*), are thinned together (maxmodels), share the
 # Gauss law's R^-1 (rcond) and are saved below one root (savepath).  Every other key, and every modelpriors key, may differ per site.
@@ -165,7 +208,7 @@ class DeviceChains(object):
 
     def __init__(self, targets, nchains, initparams=None, modelpriors=None, seed=0, device=None, inject=False,
                  betas=None, ladder=None, swap_every=0, dist=None, chain_offset=None, spec_depth=None, search="fast", arith="fast",
-                 prior_table=False, record="host"):
+                 prior_table=False, record="host", ladder_adapt=None):
         """`nchains` chains on THIS rank.  Sharded jobs (one process per GPU, `dist` = an initialised
         torch.distributed): `seed` is the JOB's seed, the same on every rank; the chains are numbered globally
         (`chain_offset` = global index of this rank's first chain, default: ranks own consecutive blocks in rank
@@ -220,10 +263,20 @@ class DeviceChains(object):
         EngineError if it does not fit the free memory), run() cuts no window and waits for nothing, `samples()` and `save()`
         return what they return with "host", bit for bit, and `samples_dev()` hands the rows to the posterior kernels where they
         lie.  A bare `iterate()` loop outside run() records as well, by the same rule, while iiter < iter_main.  Sharded runs
-        keep the host gather of `samples()`."""
+        keep the host gather of `samples()`.
+        ladder_adapt: None (default) -- the exchange sweeps are `parallel.DeviceExchange`'s, nothing is counted per pair.  A dict,
+        merged over LADDER_ADAPT_DEFAULTS (every = 20, rate = 0.5, lag = 50) -- the sweeps are one kernel each
+        (`parallel.KernelExchange`, include/bh_engine_chain_ladder_sweep.h): the same decisions, counted per neighbouring pair of
+        rungs (`ladder_swaps()`), and during the burn-in the interior temperatures of every ladder of three or more chains move
+        after every `every` sweeps so that the pairs' acceptance rates equalise; a ladder's largest and smallest beta never change.
+        `every` = 0 counts and never adapts (the run is then the run without ladder_adapt, bit for bit).  A sweep after a window
+        that ends at iiter <= 0 belongs to the burn-in; the temperatures are frozen from the first main-phase iteration on --
+        adapting while sampling would break detailed balance, what the burn-in adapts is discarded with it.  ValueError /
+        EngineError: `ladder_adapt_options`."""
         if record not in RECORD_MODES:      # (checked before anything touches the GPU)
             raise ValueError("record must be 'host' or 'device', not %r" % (record,))
         self.record = record
+        self.ladder_adapt = ladder_adapt_options(ladder_adapt, betas, ladder, swap_every, dist)
         self.sites = targets if isinstance(targets, SiteTargets) else None
         self.nsites = 1 if self.sites is None else self.sites.nsites
         # (checked before anything touches the GPU)
@@ -399,7 +452,13 @@ class DeviceChains(object):
         # replica exchange on the device (one rank, or RCCL): the ladder of every chain of the job is static
         if betas is not None and self.swap_every > 0:
             on_gpu = dist is None or not dist.is_initialized() or dist.get_world_size() == 1 or dist.get_backend() == "nccl"
-            if on_gpu and os.environ.get("BH_PT_HOST_EXCHANGE", "0") != "1":
+            if self.ladder_adapt is not None:       # (one rank: ladder_adapt_options)
+                from .parallel import KernelExchange
+                with torch.cuda.stream(self._ext_stream):
+                    self._dev_exchange = KernelExchange(self.engine, self.ladder, self.seed, dev, rate=self.ladder_adapt["rate"],
+                                                        lag=self.ladder_adapt["lag"])
+                self._betas0 = np.asarray(betas, dtype=np.float64).copy()
+            elif on_gpu and os.environ.get("BH_PT_HOST_EXCHANGE", "0") != "1":
                 from .parallel import DeviceExchange, gather_chain_axis
                 ladder_all = gather_chain_axis(self.ladder, 0, dist, int(device))
                 start = int(sum(self.rank_counts[:self.rank]))         # position of this rank's block in gather order
@@ -512,7 +571,17 @@ class DeviceChains(object):
     def exchange(self):
         """One replica-exchange sweep (the only step of a sharded job with a collective).  On the GPU (one rank, or
         RCCL) it is enqueued on the engine's stream like an iteration (`parallel.DeviceExchange`); with a CPU
-        process group (gloo) the gathered values go through the host (`parallel.tempering_exchange`)."""
+        process group (gloo) the gathered values go through the host (`parallel.tempering_exchange`).  With ladder_adapt it
+        is one kernel (`parallel.KernelExchange`), which also counts per pair of rungs and, in the burn-in, adapts the ladders."""
+        if self.ladder_adapt is not None:
+            # a sweep after a window that ends at iiter <= 0 is the burn-in's; the last of every `every` of them adapts
+            phase = 0 if self.iiter <= 0 else 1
+            every = self.ladder_adapt["every"]
+            adapt = phase == 0 and every > 0 and (self.sweep + 1) % every == 0
+            with self.torch.cuda.stream(self._ext_stream):
+                self._dev_exchange.sweep(self.t["like"], self.t["beta"], self.sweep, phase=phase, adapt=adapt)
+            self.sweep += 1
+            return
         if self._dev_exchange is not None:
             with self.torch.cuda.stream(self._ext_stream):
                 self._dev_exchange.sweep(self.t["like"], self.t["beta"], self.sweep, self.dist)
@@ -530,6 +599,40 @@ class DeviceChains(object):
     def nswaps(self):
         """accepted swaps so far (all ranks)"""
         return self._nswaps_host + (int(self._dev_exchange.nacc.item()) if self._dev_exchange is not None else 0)
+
+    def ladder_swaps(self):
+        """What the exchange sweeps of a run with ladder_adapt proposed and accepted, per neighbouring pair of rungs, and where
+        the adaptation left the temperatures.  One dict (SiteTargets: a list of one dict per site, with the site's ladders) of
+        `ids` -- the ladder ids --, `members` -- global chain numbers per ladder --, and per ladder of R chains: `betas0` and
+        `betas` [R], descending -- the rung values the run started with and holds now --, `proposed` and `accepted` int64
+        [2][R-1] -- burn-in, then main phase; pair r is rungs (r, r+1), rung 0 the coldest --, `rate` = accepted / proposed (NaN
+        where nothing was proposed); `adaptations` and `skipped` int64 per ladder: the adaptation sweeps that moved the ladder and
+        those that left it (a pair without a proposal in the window, or new values out of order).  Waits for the enqueued work.
+        EngineError: a run without ladder_adapt."""
+        if self.ladder_adapt is None:
+            raise EngineError("ladder_swaps() needs DeviceChains(ladder_adapt=...): the default exchange counts accepted swaps only "
+                              "(nswaps)")
+        ex = self._dev_exchange
+        got = ex.plan.read()
+        start = ex.plan.start
+        out = []
+        for s in range(self.nsites):
+            ks = [k for k in range(ex.plan.K) if ex.plan.members[k][0] // self.C_site == s]
+            d = dict(ids=ex.lids[ks].astype(np.int64), members=[self.chain_offset + ex.plan.members[k].astype(np.int64) for k in ks],
+                     betas0=[], betas=[], proposed=[], accepted=[], rate=[],
+                     adaptations=got["adaptations"][ks], skipped=got["skipped"][ks])
+            for k in ks:
+                lo, hi = int(start[k]), int(start[k + 1])
+                b0 = np.sort(self._betas0[ex.plan.members[k]])[::-1].copy()
+                d["betas0"].append(b0)
+                d["betas"].append(got["rung_beta"][lo:hi].copy() if ex.nsweeps else b0.copy())
+                prop, acc = got["proposed"][:, lo:hi - 1].copy(), got["accepted"][:, lo:hi - 1].copy()
+                d["proposed"].append(prop)
+                d["accepted"].append(acc)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    d["rate"].append(acc / prop.astype(np.float64))
+            out.append(d)
+        return out if self.sites is not None else out[0]
 
     def _snapshot(self):
         self.engine.synchronize()

@@ -246,6 +246,12 @@ def load_library():
                                             C.c_int64, vp, vp]
     for name in CHAIN_LADDER_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_ladder_sweep_create.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(vp)]
+    L.bh_ladder_sweep_run.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double]
+    L.bh_ladder_sweep_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.bh_ladder_sweep_destroy.argtypes = [vp, vp]
+    for name in LADDER_SWEEP_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     L.bh_chain_rank_series.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
                                        vp, vp, vp, vp, vp, C.c_int64, C.c_int64]
     L.bh_chain_rank_models.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
@@ -346,6 +352,9 @@ DIAG_LAGBLOCK = 1024                # BH_DIAG_LAGBLOCK
 # row, the ladders' mixing numbers, and the sums and medians of series that read that chain (bayhunter_amd/diagnostics.py)
 CHAIN_LADDER_SYMBOLS = ("bh_chain_ladder_index", "bh_chain_diag_series_sel", "bh_chain_diag_models_sel", "bh_chain_diag_medians_sel")
 LADDER_MAXRUNGS = 64                # BH_LADDER_MAXRUNGS
+# include/bh_engine_chain_ladder_sweep.h: the swap sweep of tempered chains as one kernel, with the counts per neighbouring pair of
+# rungs and the adaptation of the interior temperatures (LadderSweep below; bayhunter_amd/parallel.py: KernelExchange)
+LADDER_SWEEP_SYMBOLS = ("bh_ladder_sweep_create", "bh_ladder_sweep_run", "bh_ladder_sweep_read", "bh_ladder_sweep_destroy")
 # include/bh_engine_chain_rank.h: the rank transform of the chains' series pooled per site -- normal scores of the average ranks, of
 # the folded ranks, and the tail indicators (bayhunter_amd/diagnostics.py: rank_series, rank_models, rank_convergence)
 CHAIN_RANK_SYMBOLS = ("bh_chain_rank_series", "bh_chain_rank_models")
@@ -372,6 +381,62 @@ def pack_models(models, Lmax=None):
         for a, v in zip(out, m):
             a[:nlay[b], b] = v
     return nlay, out[0], out[1], out[2], out[3]
+
+
+class LadderSweep(object):
+    """A plan of include/bh_engine_chain_ladder_sweep.h: the ladders of C chains, with the counters of their sweeps on the device.
+    `ladder[c]` in 0..K-1, every id used.  The sorted layout of `logu`, of the counters and of the rung betas: ladder after ladder
+    in ascending id, rung 0 the coldest; `start[k] + r` is rung r of ladder k and the pair (r, r+1)."""
+
+    def __init__(self, engine, ladder, K=None):
+        lad = np.ascontiguousarray(ladder, dtype=np.int32)
+        if lad.ndim != 1 or lad.size < 1:
+            raise ValueError("ladder must be a sequence of one id per chain")
+        self.engine, self.C = engine, int(lad.size)
+        self.K = int(lad.max()) + 1 if K is None else int(K)
+        self._h = None
+        h = C.c_void_p()
+        engine._check(engine._L.bh_ladder_sweep_create(engine._h, self.C, _ptr(lad), self.K, C.byref(h)))
+        self._h = h
+        self.ladder = lad.astype(np.int64)
+        counts = np.bincount(self.ladder, minlength=self.K)
+        self.start = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+        self.members = [np.flatnonzero(self.ladder == k) for k in range(self.K)]
+
+    def _f64_dev(self, t, name):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == self.engine.device and t.dtype == torch.float64
+                and t.is_contiguous() and t.numel() == self.C):
+            raise ValueError("%s must be a contiguous float64 tensor of %d elements on GPU %d" % (name, self.C, self.engine.device))
+        return t.data_ptr()
+
+    def run(self, like, beta, logu, parity, phase, adapt=0, kappa=0.0, stream=None):
+        """Enqueue one sweep (stream None: the engine's): `beta` is updated in place, nothing waits.  `like`, `beta`, `logu`:
+        float64 device tensors [C], logu in the sorted layout.  adapt with phase 1 is refused (BH_EINVAL)."""
+        e = self.engine
+        e._check(e._L.bh_ladder_sweep_run(e._h, self._h, stream, self._f64_dev(like, "like"), self._f64_dev(beta, "beta"),
+                                          self._f64_dev(logu, "logu"), int(parity), int(phase), int(adapt), float(kappa)))
+
+    def read(self):
+        """Wait for the last sweep; dict of proposed, accepted (int64 [2][C]: phase, position), rung_beta (float64 [C], zeros before
+        the first sweep), adaptations, skipped (int64 [K])."""
+        e = self.engine
+        out = dict(proposed=np.zeros((2, self.C), dtype=np.int64), accepted=np.zeros((2, self.C), dtype=np.int64),
+                   rung_beta=np.zeros(self.C), adaptations=np.zeros(self.K, dtype=np.int64), skipped=np.zeros(self.K, dtype=np.int64))
+        e._check(e._L.bh_ladder_sweep_read(e._h, self._h, _ptr(out["proposed"]), _ptr(out["accepted"]), _ptr(out["rung_beta"]),
+                                           _ptr(out["adaptations"]), _ptr(out["skipped"])))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.engine, "_h", None):
+            self.engine._L.bh_ladder_sweep_destroy(self.engine._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Engine(object):

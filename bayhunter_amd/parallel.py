@@ -227,6 +227,58 @@ class DeviceExchange(object):
         beta.copy_(out[self.mine].to(beta.dtype))
 
 
+class KernelExchange(object):
+    """`DeviceExchange` as one kernel per sweep (include/bh_engine_chain_ladder_sweep.h, engine.LadderSweep), for the chains of one
+    rank: the same log-uniforms, hence the decisions of `ladder_swap_betas`, with what every neighbouring pair of rungs proposed and
+    accepted counted on the device, and -- where the caller asks for it -- the adaptation of the ladders' interior temperatures.
+    The log-uniforms depend on (seed, ladder, sweep) only: those of CHUNK sweeps go up in one pinned copy."""
+
+    CHUNK = 64
+
+    def __init__(self, engine, ladder, seed, device, rate=0.5, lag=50.0):
+        import torch
+        from .engine import LadderSweep
+        self.torch, self.dev, self.seed = torch, device, int(seed)
+        self.rate, self.lag = float(rate), float(lag)
+        lad = np.asarray(ladder, dtype=np.int64)
+        self.N = lad.size
+        self.lids, inv, self.counts = np.unique(lad, return_inverse=True, return_counts=True)    # sorted ids: the sorted layout
+        self.plan = LadderSweep(engine, inv.astype(np.int32), K=self.lids.size)
+        self.nsweeps = self.nadapt = 0
+        self._logu, self._first = None, 0            # the uploaded log-uniforms [CHUNK][N] of the sweeps from _first on
+
+    _log_uniforms = DeviceExchange._log_uniforms     # (reads seed, N, lids, counts)
+
+    def _logu_of(self, sweep):
+        if self._logu is None or not self._first <= sweep < self._first + self.CHUNK:
+            host = np.stack([self._log_uniforms(s) for s in range(sweep, sweep + self.CHUNK)])
+            # a fresh pinned buffer per chunk: torch's host allocator reuses it only after the copy that reads it has completed
+            self._logu = self.torch.from_numpy(host).pin_memory().to(self.dev, non_blocking=True)
+            self._first = sweep
+        return self._logu[sweep - self._first]
+
+    def kappa(self):
+        """the gain of the next adaptation: rate * lag / (n + lag) after n adaptation sweeps"""
+        return self.rate * self.lag / (self.nadapt + self.lag)
+
+    def sweep(self, like, beta, sweep, dist=None, phase=0, adapt=False):
+        """Enqueue sweep number `sweep` on the CURRENT torch stream: `like`, `beta` = the chains' float64 device tensors; `beta` is
+        updated in place.  phase: 0 burn-in, 1 main phase (the counters are kept per phase); adapt: this sweep ends an adaptation
+        window (phase 0 only)."""
+        sweep = int(sweep)
+        logu = self._logu_of(sweep)
+        stream = self.torch.cuda.current_stream(self.dev).cuda_stream
+        self.plan.run(like, beta, logu, sweep % 2, phase, int(bool(adapt)), self.kappa() if adapt else 0.0, stream=stream)
+        self.nsweeps += 1
+        if adapt:
+            self.nadapt += 1
+
+    @property
+    def nacc(self):
+        """accepted swaps so far, both phases (a 0-dim int64 tensor like DeviceExchange.nacc; waits for the enqueued sweeps)"""
+        return self.torch.tensor(int(self.plan.read()["accepted"].sum()), dtype=self.torch.int64)
+
+
 # ---- sharded chains: global numbering, result gather, cold-chain assembly -------------------------
 def rank_chain_counts(n_local, dist=None, device=None):
     """Chains held by every rank of the job (one small all-gather; rank order)."""
