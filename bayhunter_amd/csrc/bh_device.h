@@ -488,6 +488,65 @@ void bh_launch_like_sites_l(const LikeKernelArgs &a, const LikeSiteXArgs &sites,
 
 void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 
+// ---- the site table's part of a fused call (bh_engine.hip: SiteTable, plan_eval; DESIGN.md "The site table") ----
+// How far the registered table lets the sites differ: every level admits what the one before it admits, and one thing more.
+enum SiteLevel {
+    SITES_NONE,          // no table
+    SITES_SHARED,        // bh_sites_set: observed data per site; counts and periods are the descriptors'
+    SITES_X,             // bh_sites_set_x: + counts and periods per site on fundamental-mode phase-velocity targets
+    SITES_X_ALL,         // bh_sites_set_x_all: + on group-velocity and higher-mode targets
+    SITES_MISSING,       // bh_sites_set_missing: + a count of 0, the site lacks the target
+    SITES_MISSING_GAUSS, // bh_sites_set_missing_gauss: + on a Gauss-law target
+    SITES_AXES           // bh_sites_set_axes: + a receiver function's count anywhere in 0 .. its descriptor's n
+};
+// The likelihood launcher of a fused call: bh_launch_like, _sites, _sites_x (a site's own sample counts), _sites_m (counts that may
+// be 0), _sites_c (a Gauss-law target's ln|R| and R^-1 from its correlation classes), _sites_l (every target's law from the law table)
+enum EvalLike { LIKE_PLAIN, LIKE_SITES, LIKE_SITES_X, LIKE_SITES_M, LIKE_SITES_C, LIKE_SITES_L };
+// The contraction of a Gauss-law target: with the descriptor's data and matrix, with every model's site's data, or with the matrix
+// of every model's correlation class as well (bh_sites_set_gauss)
+enum EvalGauss { GAUSS_PLAIN, GAUSS_SITES, GAUSS_CLASSES };
+// Why a fused call is refused, in the order of precedence (bh_plan_sites reports the first that holds)
+enum SiteRefusal {
+    REFUSE_NONE,
+    REFUSE_NO_FORWARD,           // a target has no forward model to run
+    REFUSE_RF_NEEDS_TABLE,       // counts that may be 0, a receiver-function target, no bh_sites_set_rf
+    REFUSE_RF_AXIS_NEEDS_TABLE,  // a receiver function's counts differ from its descriptor's, no bh_sites_set_rf_axis
+    REFUSE_GAUSS_NEEDS_TABLE,    // a Gauss-law target some site lacks has no class table
+    REFUSE_LAW_GAUSS_NEEDS_TABLE,     // the law table has a present site under another law on a Gauss-law target without class table
+    REFUSE_RF_AXIS_GAUSS_NEEDS_TABLE, // a Gauss-law receiver function with its own counts has no class table
+    REFUSE_RF_AXIS_NO_MFMA       // ... or runs the BH_NO_MFMA in-kernel mat-vec
+};
+// What bh_plan_sites is asked: the call, the table in force and, per registered target, what the tables say of it.
+struct SitePlanAsk {
+    bool sites;              // bh_evaluate_sites (false: bh_evaluate_batch, which reads no table)
+    int level;               // SiteLevel
+    bool rf, rf_axis, laws;  // the tables of bh_sites_set_rf, bh_sites_set_rf_axis, bh_sites_set_laws are in force
+    bool no_mfma;            // the Gauss law runs the in-kernel mat-vec (BH_NO_MFMA)
+    int nt;
+    struct Target {
+        int kind, law;       // the descriptor's
+        bool lacks;          // a site has count 0 for the target
+        bool rf_own_counts;  // receiver function: a count is neither 0 nor the descriptor's
+        bool law_other;      // the law table has a present site under another law than BH_LAW_GAUSS
+        bool classes;        // the target has a class table (bh_sites_set_gauss)
+    } t[8]; // (BH_MAX_TARGETS, as LikeKernelArgs::t)
+};
+// The site part of a fused call's plan: which tables its launches read, and the one refusal.
+struct SitePlan {
+    bool x_table, rf_table;  // the table's periods and counts (bh_sites_set_x) / receiver-function parameters (bh_sites_set_rf) are in force
+    bool x_all;              // ... the periods of group-velocity targets too: their second roots read the table (bh_sites_set_x_all)
+    bool missing;            // the table's counts may be 0: the receiver-function and likelihood builds that skip
+    bool rf_axis;            // the sites' own time axes and filters are in force: the builds of bh_launch_rf_t
+    bool laws;               // the sites' own noise laws are in force
+    EvalLike like;
+    EvalGauss gauss[8];      // (read for the Gauss-law targets)
+    bool desc_counts;        // LIKE_SITES_C without a registered count table: the likelihood reads the descriptors' counts as one
+    int refusal, code;       // SiteRefusal and its error code (BH_OK: none)
+};
+// Pure: no HIP call, no engine.  The precedence among the refusals is the order of SiteRefusal.
+SitePlan bh_plan_sites(const SitePlanAsk &q);
+const char *bh_site_refusal_text(int refusal); // the message of a SiteRefusal ("" for REFUSE_NONE)
+
 // out = [val n][bound n][certified n]
 
 // the engine as other translation units reach it (bh_engine.hip; posterior_kernel.hip, include/bh_engine_posterior.h)

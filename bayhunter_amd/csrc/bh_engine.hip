@@ -106,13 +106,88 @@ struct TargetHost {
     DevBuf x60, vel60; // > 60 periods: the 60-point grid the forward model runs on + its output
     int kfwd = 0;      // periods the forward model computes (n, or 60 when n > 60)
     double logdet_extra = 0.0;
-    // correlation classes of a Gauss-law target (bh_sites_set_gauss, include/bh_engine_sites_gauss.h); part of the site table
-    int gc_nclass = 0;                   // 0: no class table, every site takes the descriptor's matrix
-    DevBuf gc_rinv, gc_logdet, gc_class; // [nclass][n][n], [nclass], int32 [nsites]
-    bool site_lacks = false;             // the count table in force has a site with count 0 for this target
-    bool law_other = false;              // the law table in force (bh_sites_set_laws) has a present site under another law than BH_LAW_GAUSS (read for a Gauss-law target)
-    bool rf_own_counts = false;          // receiver function: the count table in force (bh_sites_set_axes) has a count that is neither 0 nor the descriptor's
-    int axis_nsamp_max = 0;              // receiver function: the largest nsamp of the column of bh_sites_set_rf_axis
+};
+
+void release(DevBuf &b)
+{
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+}
+
+// ---- the site table: everything the bh_sites_set* entry points register for the targets of bh_targets_set ----
+// What the tables in force say of one registered target
+struct SiteTarget {
+    bool lacks = false;            // the count table has a site with count 0 for this target
+    bool rf_own_counts = false;    // receiver function: the count table (bh_sites_set_axes) has a count that is neither 0 nor the descriptor's
+    bool law_other = false;        // the law table has a present site under another law than BH_LAW_GAUSS (read for a Gauss-law target)
+    int axis_nsamp_max = 0;        // receiver function: the largest nsamp of the column of bh_sites_set_rf_axis
+    int nclass = 0;                // correlation classes of a Gauss-law target (bh_sites_set_gauss); 0: none, every site takes the descriptor's matrix
+    DevBuf rinv, logdet, class_of; // [nclass][n][n], [nclass], int32 [nsites]
+};
+
+// The parts of the table, each registered on top of the one before it
+enum SitePart { PART_COUNTS, PART_RF, PART_RF_AXIS, PART_LAWS, PART_CLASSES };
+
+struct SiteTable {
+    SiteLevel level = SITES_NONE;   // what the counts (bh_sites_set, bh_sites_set_x ... bh_sites_set_axes) let the sites differ in
+    int nsites = 0;
+    DevBuf yobs, yerr, logdet;      // observed data: [nsites][ldy], [nsites][ldy] (law-1 columns), [nsites][nt]
+    DevBuf idx;                     // host calls: the site index of every model, staged
+    DevBuf xn, xper;                // level >= SITES_X: [nsites][nt] sample counts (int32), [nsites][ldy] periods in ymod's column layout
+    std::vector<int32_t> xn_host;   // ... the counts as registered (the later parts are checked against them)
+    bool rf = false;                // receiver-function parameters per site (bh_sites_set_rf) are in force
+    DevBuf p, nsv;                  // [nsites][nt]: p (s/deg) and nsv of every site, read in the RF columns only
+    bool rf_axis = false;           // receiver-function time axis and Gauss filter per site (bh_sites_set_rf_axis) are in force
+    DevBuf axis;                    // [nsites][nt] RfAxisRec, read in the RF columns only
+    bool laws = false;              // noise law per site (bh_sites_set_laws) is in force
+    DevBuf law, law_yerr, law_logdet; // int32 [nsites][nt] (0 where the count is 0); the law-1 tables by the TABLE's law: [nsites][ldy], [nsites][nt]
+    std::vector<int32_t> law_host;  // ... the laws as registered (bh_sites_set_gauss checks its classes against them)
+    DevBuf desc_n;                  // [nsites][nt] the descriptors' counts: the count table of a class call below SITES_X
+    DevBuf class_work;              // the grouping's work space of a call (bh_gauss_class_work_words)
+    SiteTarget t[BH_MAX_TARGETS];
+
+    // The one invalidation rule.  `part` is being registered anew -- out of force until its entry point has succeeded -- and what
+    // was registered on top of it goes with it:
+    //     counts (the shared table of bh_sites_set included)   drop   rf, axis, laws, classes: everything
+    //     rf                                                   drops  axis, laws, classes
+    //     axis                                                 drops  laws, classes
+    //     laws                                                 drop   classes (they were checked against the laws)
+    //     classes of target `target`                           drop   nothing else
+    // Every line down to the laws is the line below it and one part more: those cases fall through.  The table belongs to the
+    // registered targets: bh_targets_set and bh_engine_destroy drop it as a whole.
+    void drop(SitePart part, int target = -1)
+    {
+        switch (part) {
+        case PART_COUNTS:
+            for (DevBuf *b : {&yobs, &yerr, &logdet, &idx, &xn, &xper, &p, &nsv, &axis}) release(*b);
+            level = SITES_NONE;
+            nsites = 0;
+            xn_host.clear();
+            for (SiteTarget &T : t) T.lacks = T.rf_own_counts = false;
+            [[fallthrough]];
+        case PART_RF:
+            rf = false;
+            [[fallthrough]];
+        case PART_RF_AXIS:
+            rf_axis = false;
+            for (SiteTarget &T : t) T.axis_nsamp_max = 0;
+            [[fallthrough]];
+        case PART_LAWS:
+            for (DevBuf *b : {&law, &law_yerr, &law_logdet}) release(*b);
+            laws = false;
+            law_host.clear();
+            for (SiteTarget &T : t) T.law_other = false;
+            for (SiteTarget &T : t) {
+                for (DevBuf *b : {&T.rinv, &T.logdet, &T.class_of}) release(*b);
+                T.nclass = 0;
+            }
+            release(desc_n);
+            break;
+        case PART_CLASSES: // (of one target; its buffers serve the registration that follows)
+            t[target].nclass = 0;
+        }
+    }
 };
 
 } // namespace
@@ -147,30 +222,7 @@ struct bh_engine {
     int nt = 0;
     int ldy = 0;
     std::vector<TargetHost> targets;
-    // site table (bh_sites_set, include/bh_engine_sites.h): observed data of nsites stations for the registered targets
-    int nsites = 0;
-    DevBuf site_yobs, site_yerr, site_logdet; // [nsites][ldy], [nsites][ldy] (law-1 columns), [nsites][nt]
-    DevBuf site_idx;                          // host calls: the site index of every model, staged
-    // receiver-function parameters per site (bh_sites_set_rf, include/bh_engine_sites_rf.h): part of the site table
-    bool site_rf = false;
-    DevBuf site_p, site_nsv;                  // [nsites][nt]: p (s/deg) and nsv of every site, read in the RF columns only
-    // receiver-function time axis and Gauss filter per site (bh_sites_set_rf_axis, include/bh_engine_sites_rf_axis.h): part of that table
-    bool site_rf_axis = false;
-    DevBuf site_axis;                         // [nsites][nt] RfAxisRec, read in the RF columns only
-    // dispersion periods per site (bh_sites_set_x, include/bh_engine_sites_x.h): registered together with the site table
-    bool site_x = false;
-    bool site_x_all = false;                  // ... registered by bh_sites_set_x_all: group velocities' second roots at a site's own periods
-    bool site_missing = false;                // ... registered by bh_sites_set_missing: a count may be 0 (the site lacks the target)
-    DevBuf site_xn, site_xper;                // [nsites][nt] sample counts (int32), [nsites][ldy] periods in ymod's column layout
-    std::vector<int32_t> site_xn_host;        // ... the counts as registered (bh_sites_set_gauss checks its classes against them)
-    // sites with their own Gauss-law noise correlation (bh_sites_set_gauss, include/bh_engine_sites_gauss.h)
-    bool site_missing_gauss = false;          // registered by bh_sites_set_missing_gauss: a Gauss-law target some site lacks needs its class table
-    DevBuf gc_xn;                             // [nsites][nt] the descriptors' counts: the count table of a class call where none is registered
-    DevBuf gc_work;                           // the grouping's work space of a call (bh_gauss_class_work_words)
-    // sites with their own noise law (bh_sites_set_laws, include/bh_engine_sites_laws.h): part of the count table
-    bool site_laws = false;                   // the law table is in force
-    DevBuf law_tab, law_yerr, law_logdet;     // int32 [nsites][nt] (0 where the count is 0); the law-1 tables by the TABLE's law: [nsites][ldy], [nsites][nt]
-    std::vector<int32_t> site_law_host;       // ... the laws as registered (bh_sites_set_gauss checks its classes against them)
+    SiteTable sites;                       // what the bh_sites_set* entry points registered for them
     // instrumentation
     bool timing = false, counting = false;
     bool no_mfma = false; // BH_NO_MFMA env: Gauss law through the in-kernel mat-vec (A/B testing)
@@ -196,6 +248,76 @@ struct bh_engine {
     uint64_t last_neval = 0;
     bool neval_pending = false;
 };
+
+// ---- the site part of a fused call's plan (bh_device.h): pure, no HIP call, no engine (tests/test_site_plan.py) ----
+static_assert(BH_MAX_TARGETS == 8, "SitePlanAsk::t, SitePlan::gauss");
+namespace {
+const struct { int code; const char *text; } SITE_REFUSALS[] = { // by SiteRefusal
+    {BH_OK, ""},
+    {BH_EINVAL, "a BH_TARGET_USER target has no forward model: use bh_loglike_batch"},
+    {BH_EINVAL, "bh_sites_set_missing with a receiver-function target needs bh_sites_set_rf"},
+    {BH_EINVAL, "bh_sites_set_axes with a receiver-function count that differs from its descriptor's needs the table of bh_sites_set_rf_axis"},
+    {BH_EINVAL, "bh_sites_set_missing_gauss with a Gauss-law target that a site lacks needs the table of bh_sites_set_gauss"},
+    {BH_EINVAL, "bh_sites_set_laws with a Gauss-law target that has a site under another law needs the table of bh_sites_set_gauss (that site in class -1)"},
+    {BH_EINVAL, "bh_sites_set_axes with a Gauss-law receiver function whose counts differ from its descriptor's needs the table of bh_sites_set_gauss (every site's matrix padded to the capacity)"},
+    {BH_EUNSUPPORTED, "BH_NO_MFMA: the in-kernel mat-vec does not serve a Gauss-law receiver function with per-site counts (bh_sites_set_axes)"},
+};
+} // namespace
+const char *bh_site_refusal_text(int refusal)
+{
+    return (refusal >= 0 && refusal <= REFUSE_RF_AXIS_NO_MFMA) ? SITE_REFUSALS[refusal].text : "";
+}
+
+SitePlan bh_plan_sites(const SitePlanAsk &q)
+{
+    SitePlan p{};
+    bool have_rf = false, no_forward = false;
+    for (int t = 0; t < q.nt; ++t) {
+        have_rf = have_rf || q.t[t].kind == BH_TARGET_RF;
+        no_forward = no_forward || (q.t[t].kind != BH_TARGET_SWD && q.t[t].kind != BH_TARGET_RF);
+    }
+    // (periods per site: every dispersion job reads its models' periods and counts from the table)
+    p.x_table = q.sites && q.level >= SITES_X;
+    p.x_all = p.x_table && q.level >= SITES_X_ALL;
+    // (sites with their own p / nsv: the coefficient kernels read them from the table, column t)
+    p.rf_table = q.sites && q.rf;
+    // (sites that lack targets: the coefficient stage looks the model's site up in the count table)
+    p.missing = p.x_table && q.level >= SITES_MISSING;
+    // (sites with their own time axis and filter: the synthesis kernel reads its model's site's record)
+    p.rf_axis = p.rf_table && p.x_table && q.rf_axis;
+    // (sites with their own noise law: the likelihood build that reads the law of (site, target) serves the call, with or without
+    // class tables; the rows of a site under another law on a Gauss-law target must be in no tile of the contraction)
+    p.laws = p.x_table && q.laws;
+    p.like = p.missing ? LIKE_SITES_M : (p.x_table ? LIKE_SITES_X : (q.sites ? LIKE_SITES : LIKE_PLAIN));
+    // (sites with their own noise correlation: a target with a class table is contracted class by class, and the likelihood build
+    // that reads ln|R| of the model's class serves the call)
+    bool own_no_axis = false, lacked_gauss = false, other_law_gauss = false, own_gauss = false, own_no_mfma = false;
+    for (int t = 0; t < q.nt; ++t) {
+        const SitePlanAsk::Target &T = q.t[t];
+        const bool own = q.sites && T.rf_own_counts;
+        p.gauss[t] = !q.sites ? GAUSS_PLAIN : (T.classes ? GAUSS_CLASSES : GAUSS_SITES);
+        own_no_axis = own_no_axis || (own && !p.rf_axis);
+        if (T.law != BH_LAW_GAUSS) continue;
+        if (p.gauss[t] == GAUSS_CLASSES) p.like = LIKE_SITES_C;
+        else if (q.sites && q.level >= SITES_MISSING_GAUSS && T.lacks) lacked_gauss = true;
+        else if (own) own_gauss = true; // (the descriptor's matrix is the capacity's, no site's)
+        // (the mat-vec's row stride is the site's n, the class matrices -- a site's in the corner of a zero matrix -- have the capacity's)
+        own_no_mfma = own_no_mfma || (own && q.no_mfma);
+        other_law_gauss = other_law_gauss || (p.laws && T.law_other && p.gauss[t] != GAUSS_CLASSES);
+    }
+    if (p.laws) p.like = LIKE_SITES_L;
+    p.desc_counts = p.like == LIKE_SITES_C && !p.x_table;
+    p.refusal = no_forward                               ? REFUSE_NO_FORWARD
+                : (p.missing && have_rf && !p.rf_table) ? REFUSE_RF_NEEDS_TABLE
+                : own_no_axis                            ? REFUSE_RF_AXIS_NEEDS_TABLE
+                : lacked_gauss                           ? REFUSE_GAUSS_NEEDS_TABLE
+                : other_law_gauss                        ? REFUSE_LAW_GAUSS_NEEDS_TABLE
+                : own_gauss                              ? REFUSE_RF_AXIS_GAUSS_NEEDS_TABLE
+                : own_no_mfma                            ? REFUSE_RF_AXIS_NO_MFMA
+                                                         : REFUSE_NONE;
+    p.code = SITE_REFUSALS[p.refusal].code;
+    return p;
+}
 
 namespace {
 
@@ -235,55 +357,10 @@ int ensure(bh_engine *e, DevBuf &b, size_t bytes)
     return BH_OK;
 }
 
-void release(DevBuf &b)
-{
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-}
-
-// number of elements spanned by a strided [Lmax][B] view (strides must be positive)
 // every device buffer a registered target owns
 void release_target(TargetHost &t)
 {
-    for (DevBuf *b : {&t.x, &t.yobs, &t.yerr_scaled, &t.rinv, &t.quad, &t.sums, &t.x60, &t.vel60, &t.gc_rinv, &t.gc_logdet, &t.gc_class}) release(*b);
-    t.gc_nclass = 0;
-}
-
-// the correlation classes of every target (they belong to the site table: whatever registers or extends it drops them)
-void release_gauss_classes(bh_engine *e)
-{
-    for (auto &t : e->targets) {
-        for (DevBuf *b : {&t.gc_rinv, &t.gc_logdet, &t.gc_class}) release(*b);
-        t.gc_nclass = 0;
-    }
-    release(e->gc_xn);
-}
-
-// the law table (it belongs to the count table: whatever registers or extends the site table drops it) and, with it, the correlation
-// classes, which were checked against it
-void release_laws(bh_engine *e)
-{
-    for (DevBuf *b : {&e->law_tab, &e->law_yerr, &e->law_logdet}) release(*b);
-    e->site_laws = false;
-    e->site_law_host.clear();
-    for (auto &t : e->targets) t.law_other = false;
-    release_gauss_classes(e);
-}
-
-// the site table's buffers (they belong to the registered targets: bh_targets_set and bh_engine_destroy release them)
-void release_sites(bh_engine *e)
-{
-    for (DevBuf *b : {&e->site_yobs, &e->site_yerr, &e->site_logdet, &e->site_idx, &e->site_p, &e->site_nsv, &e->site_xn, &e->site_xper, &e->site_axis}) release(*b);
-    e->nsites = 0;
-    e->site_rf = e->site_rf_axis = false;
-    e->site_x = e->site_x_all = e->site_missing = e->site_missing_gauss = false;
-    e->site_xn_host.clear();
-    release_laws(e);
-    for (auto &t : e->targets) {
-        t.site_lacks = t.rf_own_counts = false;
-        t.axis_nsamp_max = 0;
-    }
+    for (DevBuf *b : {&t.x, &t.yobs, &t.yerr_scaled, &t.rinv, &t.quad, &t.sums, &t.x60, &t.vel60}) release(*b);
 }
 
 // Targets.py:124-128, the nocorr_scalederr law: out = yerr / min(yerr), returns ln prod(out) (bh_targets_set, bh_sites_set)
@@ -299,6 +376,7 @@ double scaled_errors(const double *yerr, int n, double *out)
     return std::log(prod);
 }
 
+// number of elements spanned by a strided [Lmax][B] view (strides must be positive)
 size_t span_elems(int B, int Lmax, ptrdiff_t sl, ptrdiff_t sb)
 {
     return (size_t)((ptrdiff_t)(Lmax - 1) * sl + (ptrdiff_t)(B - 1) * sb + 1);
@@ -405,6 +483,7 @@ int swd_supported(bh_engine *e, int K, int iwave, int &igr, int mode, int flsph)
 struct SwdSiteJob {
     const SwdSiteXArgs *tab; // the call's table (site, nsites, strides, n, x); col / off filled per launch
     int col, off;            // the job's registered target and its column offset in a row of x
+    bool all;                // the table holds the periods of group-velocity targets as well (SitePlan::x_all): their second roots read it
 };
 
 struct SwdJob {
@@ -658,42 +737,34 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
 // What a target does in a fused call: nothing (a BH_TARGET_USER target has no forward model), dispersion at its own periods,
 // dispersion on the 60-period grid followed by interpolation, or a receiver function.
 enum EvalRole { ROLE_NONE, ROLE_SWD, ROLE_SWD60, ROLE_RF };
-// The likelihood launcher of a fused call: bh_launch_like, bh_launch_like_sites, bh_launch_like_sites_x (a site's own sample counts)
-// (LIKE_SITES_M: bh_launch_like_sites_m, counts that may be 0)
-// (LIKE_SITES_C: bh_launch_like_sites_c, a Gauss-law target's ln|R| and R^-1 from its table of correlation classes)
-// (LIKE_SITES_L: bh_launch_like_sites_l, every target's law from the table of bh_sites_set_laws)
-enum EvalLike { LIKE_PLAIN, LIKE_SITES, LIKE_SITES_X, LIKE_SITES_M, LIKE_SITES_C, LIKE_SITES_L };
-// The contraction of a Gauss-law target: with the descriptor's data and matrix, with every model's site's data, or with the matrix
-// of every model's correlation class as well (bh_sites_set_gauss)
-enum EvalGauss { GAUSS_PLAIN, GAUSS_SITES, GAUSS_CLASSES };
-
 // What one fused call (bh_evaluate_batch, bh_evaluate_sites) does: everything its steps would otherwise decide.
 struct EvalPlan {
     int B, nt, ldy;
     EvalRole role[BH_MAX_TARGETS];
     bool rf_fused[BH_MAX_TARGETS]; // receiver function: the synthesis kernel writes the likelihood's sums, not the trace
     int nswd;                   // dispersion jobs of the call
-    bool no_forward;            // a target has no forward model to run: the call is refused
     bool fork;                  // the receiver functions run on the second stream, beside the dispersion launch
     bool want_gate;             // ... which waits for that launch's started workgroups (where the launch has any: gate_need)
     int prio_low;               // SwdMultiArgs::prio_low of the dispersion launch
-    bool x_table, rf_table;     // the site table's periods (bh_sites_set_x) / receiver-function parameters (bh_sites_set_rf) are in force
-    bool missing;               // the table's counts may be 0 (bh_sites_set_missing): the receiver-function and likelihood builds that skip
-    bool rf_needs_table;        // ... and a receiver-function target is registered without bh_sites_set_rf: the call is refused
-    bool rf_axis;               // the sites' own time axes and filters (bh_sites_set_rf_axis) are in force: the builds of bh_launch_rf_t
-    bool rf_axis_needs_table;   // a receiver function's counts differ from its descriptor's (bh_sites_set_axes) without that table: refused
-    bool rf_axis_gauss_needs_table; // ... under the Gauss law without the target's class table (bh_sites_set_gauss): refused
-    bool rf_axis_no_mfma;       // ... under the Gauss law with the BH_NO_MFMA in-kernel mat-vec: refused
-    EvalGauss gauss[BH_MAX_TARGETS]; // (read for the Gauss-law targets)
-    bool gauss_needs_table;     // bh_sites_set_missing_gauss, and a Gauss-law target some site lacks has no class table: the call is refused
-    bool laws;                  // the sites' own noise laws (bh_sites_set_laws) are in force: the likelihood builds of bh_launch_like_sites_l
-    bool law_gauss_needs_table; // ... and a Gauss-law target with a present site under another law has no class table: the call is refused
-    EvalLike like;
+    SitePlan sites;             // the site table's part (bh_plan_sites): the tables the launches read, the likelihood launcher, the refusal
     bool err_zero_always;       // bh_tuning.h err_memset: the failure flags are zeroed on every call
 };
 
+// What bh_plan_sites is asked about a fused call of engine e (sites: bh_evaluate_sites)
+SitePlanAsk site_plan_ask(const bh_engine *e, bool sites)
+{
+    const SiteTable &S = e->sites;
+    SitePlanAsk q{};
+    q.sites = sites; q.level = S.level; q.rf = S.rf; q.rf_axis = S.rf_axis; q.laws = S.laws; q.no_mfma = e->no_mfma; q.nt = e->nt;
+    for (int t = 0; t < q.nt; ++t) {
+        const bh_target_desc &d = e->targets[(size_t)t].d;
+        q.t[t] = SitePlanAsk::Target{d.kind, d.law, S.t[t].lacks, S.t[t].rf_own_counts, S.t[t].law_other, S.t[t].nclass > 0};
+    }
+    return q;
+}
+
 // The plan of one fused call, from the registered targets, the engine's settings, the experiment switches (bh_tuning.h) and the
-// site table's flags: no HIP call, no allocation, no write to the engine.  sites: bh_evaluate_sites; want_ymod: the caller asked
+// site table (its part: bh_plan_sites): no HIP call, no allocation, no write to the engine.  sites: bh_evaluate_sites; want_ymod: the caller asked
 // for the synthetics.
 EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
 {
@@ -715,8 +786,6 @@ EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
             // in LDS (like_kernel's order: the same bits) and writes four numbers per model instead of the trace.
             // (sites: the trace goes to the ymod workspace and the site-indexed likelihood kernel forms the sums)
             p.rf_fused[t] = !want_ymod && !sites && tun.rf_no_fuse == 0 && (d.law == BH_LAW_NOCORR || d.law == BH_LAW_EXP) && tun.rf_threads != 128;
-        } else {
-            p.no_forward = true;
         }
     }
     // The receiver-function kernels are independent of the dispersion kernel and write other columns
@@ -737,39 +806,7 @@ EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
     // (RF wavefronts move in beside the last dispersion wavefronts of a SIMD as its short ones end: the dispersion
     // wavefronts' unfavoured phase runs at priority 1 then, above the RF's 0)
     p.prio_low = p.want_gate ? e->swd_prio_low : 0;
-    // (periods per site, bh_sites_set_x: every dispersion job reads its models' periods and counts from the table)
-    p.x_table = sites && e->site_x;
-    // (sites with their own p / nsv, bh_sites_set_rf: the coefficient kernels read them from the table, column t)
-    p.rf_table = sites && e->site_rf;
-    // (sites that lack targets, bh_sites_set_missing: the coefficient stage looks the model's site up in the count table)
-    p.missing = p.x_table && e->site_missing;
-    p.rf_needs_table = p.missing && have_rf && !p.rf_table;
-    // (sites with their own time axis and filter, bh_sites_set_rf_axis: the synthesis kernel reads its model's site's record)
-    p.rf_axis = p.rf_table && p.x_table && e->site_rf_axis;
-    p.like = p.missing ? LIKE_SITES_M : (p.x_table ? LIKE_SITES_X : (sites ? LIKE_SITES : LIKE_PLAIN));
-    // (sites with their own noise correlation, bh_sites_set_gauss: a target with a class table is contracted class by class, and
-    // the likelihood build that reads ln|R| of the model's class serves the call)
-    for (int t = 0; t < p.nt; ++t) {
-        const TargetHost &T = e->targets[(size_t)t];
-        p.gauss[t] = !sites ? GAUSS_PLAIN : (T.gc_nclass > 0 ? GAUSS_CLASSES : GAUSS_SITES);
-        if (sites && T.rf_own_counts && !p.rf_axis) p.rf_axis_needs_table = true;
-        if (T.d.law != BH_LAW_GAUSS) continue;
-        if (p.gauss[t] == GAUSS_CLASSES) p.like = LIKE_SITES_C;
-        else if (sites && e->site_missing_gauss && T.site_lacks) p.gauss_needs_table = true;
-        else if (sites && T.rf_own_counts) p.rf_axis_gauss_needs_table = true; // (the descriptor's matrix is the capacity's, no site's)
-        // (the mat-vec's row stride is the site's n, the class matrices -- a site's in the corner of a zero matrix -- have the capacity's)
-        if (sites && T.rf_own_counts && e->no_mfma) p.rf_axis_no_mfma = true;
-    }
-    // (sites with their own noise law, bh_sites_set_laws: the likelihood build that reads the law of (site, target) serves the call,
-    // with or without class tables; the rows of a site under another law on a Gauss-law target must be in no tile of the contraction)
-    p.laws = p.x_table && e->site_laws;
-    if (p.laws) {
-        p.like = LIKE_SITES_L;
-        for (int t = 0; t < p.nt; ++t) {
-            const TargetHost &T = e->targets[(size_t)t];
-            if (T.d.law == BH_LAW_GAUSS && T.law_other && p.gauss[t] != GAUSS_CLASSES) p.law_gauss_needs_table = true;
-        }
-    }
+    p.sites = bh_plan_sites(site_plan_ask(e, sites));
     p.err_zero_always = tun.err_memset != 0;
     return p;
 }
@@ -1246,7 +1283,6 @@ int launch_second_roots(const SwdCall &c)
 {
     bh_engine *e = c.e;
     const int B = c.B;
-    const bool sitex = c.p.sitex && e->site_x_all;
     int J2 = 16; // trial lanes per search while all searches of the call still fit the chip at once (2048 wavefronts)
     {
         long searches = 0;
@@ -1277,7 +1313,8 @@ int launch_second_roots(const SwdCall &c)
         a.fair = waves <= 1024 ? -1 : (waves <= 2048 ? 18 : 12);
         a.nev_high = (double *)e->nevhi2.p + off[n];
         SwdLaneBuild lb{};
-        if (sitex) bh_launch_swd_second_x(a, tg.iwave, c.sx, t, (fork && (n & 1)) ? e->aux2 : c.st, &lb);
+        const SwdSiteJob &sx = c.jobs[c.p.job[t]].sx;
+        if (sx.tab != nullptr && sx.all) bh_launch_swd_second_x(a, tg.iwave, c.sx, t, (fork && (n & 1)) ? e->aux2 : c.st, &lb);
         else bh_launch_swd(a, tg.iwave, (fork && (n & 1)) ? e->aux2 : c.st, &lb);
         note_lane(e, BH_SWD_SECOND, lb);
         ++n;
@@ -1387,13 +1424,15 @@ int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, pt
     return BH_OK;
 }
 
-// Fill the likelihood descriptor of target t; for the Gauss law run the MFMA contraction first.
+// Fill the likelihood descriptor L of target t; for the Gauss law run the MFMA contraction first.
 // site: null, or the site index of every model (device; bh_evaluate_sites): the Gauss contraction reads the observed data
 // of each model's site from the site table.  fused: the target's likelihood comes from the sums of this call's synthesis launch
 // (EvalPlan::rf_fused), not from ymod
-int prepare_like_target(bh_engine *e, hipStream_t st, int B, int ldy, const double *ymod_d, TargetHost &T,
+int prepare_like_target(bh_engine *e, hipStream_t st, int B, int ldy, const double *ymod_d, int t,
                         LikeTargetDev &L, bool fused, const int32_t *site, EvalGauss how)
 {
+    TargetHost &T = e->targets[(size_t)t];
+    SiteTable &S = e->sites;
     L.law = T.d.law; L.n = T.d.n; L.off = T.off;
     L.yobs = (const double *)T.yobs.p;
     L.yerr_scaled = (const double *)T.yerr_scaled.p;
@@ -1406,15 +1445,15 @@ int prepare_like_target(bh_engine *e, hipStream_t st, int B, int ldy, const doub
         const int nsplit = bh_gauss_nsplit(B, T.d.n);
         int rc = ensure(e, T.quad, (size_t)B * nsplit * sizeof(double));
         if (rc) return rc;
-        if (how == GAUSS_CLASSES && (rc = ensure(e, e->gc_work, bh_gauss_class_work_words(B, T.gc_nclass) * sizeof(int32_t)))) return rc;
+        if (how == GAUSS_CLASSES && (rc = ensure(e, S.class_work, bh_gauss_class_work_words(B, S.t[t].nclass) * sizeof(int32_t)))) return rc;
         ev_begin(e, 2, st);
         if (how == GAUSS_CLASSES) { // (grouping launches + the contraction over tiles of one class each)
-            const GaussSiteArgs gs{site, e->nsites, ldy};
-            bh_launch_gauss_quad_classes(B, T.d.n, ldy, ymod_d + T.off, (const double *)e->site_yobs.p + T.off, gs, (const int32_t *)T.gc_class.p,
-                                         T.gc_nclass, (const double *)T.gc_rinv.p, nsplit, (double *)T.quad.p, (int32_t *)e->gc_work.p, st);
+            const GaussSiteArgs gs{site, S.nsites, ldy};
+            bh_launch_gauss_quad_classes(B, T.d.n, ldy, ymod_d + T.off, (const double *)S.yobs.p + T.off, gs, (const int32_t *)S.t[t].class_of.p,
+                                         S.t[t].nclass, (const double *)S.t[t].rinv.p, nsplit, (double *)T.quad.p, (int32_t *)S.class_work.p, st);
         } else if (site) {
-            const GaussSiteArgs gs{site, e->nsites, ldy};
-            bh_launch_gauss_quad_sites(B, T.d.n, ldy, ymod_d + T.off, (const double *)e->site_yobs.p + T.off, gs, L.rinv, nsplit,
+            const GaussSiteArgs gs{site, S.nsites, ldy};
+            bh_launch_gauss_quad_sites(B, T.d.n, ldy, ymod_d + T.off, (const double *)S.yobs.p + T.off, gs, L.rinv, nsplit,
                                        (double *)T.quad.p, st);
         } else {
             bh_launch_gauss_quad(B, T.d.n, ldy, ymod_d + T.off, L.yobs, L.rinv, nsplit, (double *)T.quad.p, st);
@@ -1632,12 +1671,11 @@ void bh_engine_destroy(bh_engine *e)
     (void)hipStreamSynchronize(e->stream);
     for (DevBuf *b : {&e->nlay, &e->h, &e->vp, &e->vs, &e->rho, &e->qp, &e->qs, &e->periods, &e->vel,
                       &e->errb, &e->rf, &e->coef, &e->ymod, &e->noise, &e->logL, &e->misfits,
-                      &e->err_t, &e->probe_in, &e->probe_out, &e->counter, &e->sph, &e->perm, &e->board, &e->nevhi, &e->guard, &e->rfz, &e->gfirst, &e->nevhi2, &e->gc_work})
+                      &e->err_t, &e->probe_in, &e->probe_out, &e->counter, &e->sph, &e->perm, &e->board, &e->nevhi, &e->guard, &e->rfz, &e->gfirst, &e->nevhi2})
         release(*b);
-    for (auto &t : e->targets) {
-        release_target(t);
-    }
-    release_sites(e);
+    for (auto &t : e->targets) release_target(t);
+    e->sites.drop(PART_COUNTS);
+    release(e->sites.class_work);
     for (auto &s : e->evsets)
         for (auto &ev : s.ev)
             if (ev) (void)hipEventDestroy(ev);
@@ -1828,10 +1866,8 @@ int bh_targets_set(bh_engine *e, int nt, const bh_target_desc *td)
     if (nt < 0 || nt > BH_MAX_TARGETS || (nt > 0 && !td)) return fail(e, BH_EINVAL, "nt must be 0..8");
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    for (auto &t : e->targets) {
-        release_target(t);
-    }
-    release_sites(e);
+    for (auto &t : e->targets) release_target(t);
+    e->sites.drop(PART_COUNTS);
     e->targets.clear();
     e->nt = 0;
     e->ldy = 0;
@@ -1951,17 +1987,11 @@ struct EvalCall {
 int eval_args_ok(bh_engine *e, const EvalPlan &p, bool host, const EvalCall &c)
 {
     if (p.nt < 1) return fail(e, BH_EINVAL, "no targets registered (bh_targets_set)");
-    if (p.no_forward) return fail(e, BH_EINVAL, "a BH_TARGET_USER target has no forward model: use bh_loglike_batch");
-    if (p.rf_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_missing with a receiver-function target needs bh_sites_set_rf");
-    if (p.rf_axis_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_axes with a receiver-function count that differs from its descriptor's needs the table of bh_sites_set_rf_axis");
-    if (p.gauss_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_missing_gauss with a Gauss-law target that a site lacks needs the table of bh_sites_set_gauss");
-    if (p.law_gauss_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_laws with a Gauss-law target that has a site under another law needs the table of bh_sites_set_gauss (that site in class -1)");
-    if (p.rf_axis_gauss_needs_table) return fail(e, BH_EINVAL, "bh_sites_set_axes with a Gauss-law receiver function whose counts differ from its descriptor's needs the table of bh_sites_set_gauss (every site's matrix padded to the capacity)");
-    if (p.rf_axis_no_mfma) return fail(e, BH_EUNSUPPORTED, "BH_NO_MFMA: the in-kernel mat-vec does not serve a Gauss-law receiver function with per-site counts (bh_sites_set_axes)");
+    if (p.sites.refusal != REFUSE_NONE) return fail(e, p.sites.code, bh_site_refusal_text(p.sites.refusal)); // (the first that holds: bh_plan_sites)
     if (!c.m.nlay || !c.m.h || !c.m.vp || !c.m.vs || !c.la.noise || !c.la.logL || !c.la.misfits || !c.la.err) return fail(e, BH_EINVAL, "null argument");
     if (c.site && host)
         for (int b = 0; b < p.B; ++b)
-            if (c.site[b] < 0 || c.site[b] >= e->nsites) return fail(e, BH_EINVAL, "site index out of range (bh_sites_set)");
+            if (c.site[b] < 0 || c.site[b] >= e->sites.nsites) return fail(e, BH_EINVAL, "site index out of range (bh_sites_set)");
     return BH_OK;
 }
 
@@ -1973,9 +2003,9 @@ int stage_eval_inputs(bh_engine *e, bool host, int B, EvalCall &c)
         if ((rc = stage_models(e, B, c.Lmax, c.sl, c.sb, c.m))) return rc;
         if ((rc = stage_like_io(e, c.st, c.la))) return rc;
         if (c.site) {
-            if ((rc = ensure(e, e->site_idx, (size_t)B * sizeof(int32_t)))) return rc;
-            HIPCHK(e, hipMemcpyAsync(e->site_idx.p, c.site, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
-            c.site = (const int32_t *)e->site_idx.p;
+            if ((rc = ensure(e, e->sites.idx, (size_t)B * sizeof(int32_t)))) return rc;
+            HIPCHK(e, hipMemcpyAsync(e->sites.idx.p, c.site, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, c.st));
+            c.site = (const int32_t *)e->sites.idx.p;
         }
         c.ymod = nullptr;
     }
@@ -2017,14 +2047,16 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
     int rc;
     SwdJob jobs[BH_MAX_TARGETS];
     int njobs = 0;
-    const SwdSiteXArgs xtab{c.site, e->nsites, nt, ldy, (const int32_t *)e->site_xn.p, (const double *)e->site_xper.p, {}, {}};
+    const SiteTable &S = e->sites;
+    const SitePlan &sp = p.sites;
+    const SwdSiteXArgs xtab{c.site, S.nsites, nt, ldy, (const int32_t *)S.xn.p, (const double *)S.xper.p, {}, {}};
     for (int t = 0; t < nt; ++t) {
         const TargetHost &T = e->targets[(size_t)t];
         const bh_target_desc &d = T.d;
         int32_t *errp = (int32_t *)e->err_t.p + (size_t)t * B;
         if (p.role[t] == ROLE_SWD) {
             jobs[njobs++] = SwdJob{d.n, d.iwave, d.igr, ldy, (const double *)T.x.p, c.ymod + T.off, errp, d.mode, d.flsph};
-            if (p.x_table) jobs[njobs - 1].sx = SwdSiteJob{&xtab, t, T.off};
+            if (sp.x_table) jobs[njobs - 1].sx = SwdSiteJob{&xtab, t, T.off, sp.x_all};
         } else if (p.role[t] == ROLE_SWD60) {
             jobs[njobs++] = SwdJob{T.kfwd, d.iwave, d.igr, T.kfwd, (const double *)T.x60.p, (double *)T.vel60.p, errp, d.mode, d.flsph};
         }
@@ -2032,10 +2064,10 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
     // per-target failure flags [nt][B]: the dispersion kernels write every entry of their target's row on every call,
     // nothing writes the rows of the other targets -- they are zeroed once per (nt, B) layout, not once per call; by the dispersion
     // call's ordering launch where its plan has one (the receiver-function launches beside it neither read nor write the flags)
-    const SwdPlan sp = plan_swd_call(e, B, c.Lmax, c.m, njobs, jobs);
+    const SwdPlan swp = plan_swd_call(e, B, c.Lmax, c.m, njobs, jobs);
     SwdFills fills{};
     if (p.err_zero_always || e->err_t_nt != nt || e->err_t_B != B) {
-        if (sp.prologue) {
+        if (swp.prologue) {
             fills.err = (int32_t *)e->err_t.p;
             fills.nerr = nt * B;
         } else {
@@ -2052,7 +2084,7 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
         e->started_expected = 0;
     }
     SwdLaunchInfo swd{};
-    if ((rc = launch_swd_jobs(e, st, B, c.Lmax, c.m, c.sl, c.sb, njobs, jobs, sp, fills, p.prio_low, &swd))) return rc;
+    if ((rc = launch_swd_jobs(e, st, B, c.Lmax, c.m, c.sl, c.sb, njobs, jobs, swp, fills, p.prio_low, &swd))) return rc;
     const bool gate = p.want_gate && swd.workgroups > 0;
     if (gate)
         HIPCHK(e, hipStreamWaitValue32(e->aux, e->started, e->started_expected - swd.workgroups + gate_need(swd), hipStreamWaitValueGte, 0xffffffffu));
@@ -2065,63 +2097,56 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
                              (const double *)T.x.p, c.ymod + T.off, ldy, st);
         if (p.role[t] != ROLE_RF) continue;
         RfSiteArgs rs{};
-        if (p.rf_table) rs = RfSiteArgs{c.site, e->nsites, nt, (const double *)e->site_p.p + t, (const double *)e->site_nsv.p + t};
+        if (sp.rf_table) rs = RfSiteArgs{c.site, S.nsites, nt, (const double *)S.p.p + t, (const double *)S.nsv.p + t};
         RfSiteMArgs rm{};
-        if (p.missing) {
+        if (sp.missing) {
             static_cast<RfSiteArgs &>(rm) = rs;
-            rm.n = (const int32_t *)e->site_xn.p + t;
+            rm.n = (const int32_t *)S.xn.p + t;
         }
         RfSiteTArgs ra{};
-        if (p.rf_axis) {
+        if (sp.rf_axis) {
             static_cast<RfSiteArgs &>(ra) = rs;
-            ra.n = (const int32_t *)e->site_xn.p + t;
-            ra.axis = (const RfAxisRec *)e->site_axis.p + t;
-            ra.nsamp_max = T.axis_nsamp_max;
+            ra.n = (const int32_t *)S.xn.p + t;
+            ra.axis = (const RfAxisRec *)S.axis.p + t;
+            ra.nsamp_max = S.t[t].axis_nsamp_max;
         }
         const RfJob job{d.p_s_per_deg, d.gauss, d.nsamp, d.fsamp, d.tshift, d.nsv, d.waveno, d.n, c.ymod + T.off, ldy,
-                        p.rf_fused[t] ? (const double *)T.yobs.p : nullptr, p.rf_fused[t] ? (double *)T.sums.p : nullptr, p.rf_table ? &rs : nullptr,
-                        p.missing ? &rm : nullptr, p.rf_axis ? &ra : nullptr};
+                        p.rf_fused[t] ? (const double *)T.yobs.p : nullptr, p.rf_fused[t] ? (double *)T.sums.p : nullptr, sp.rf_table ? &rs : nullptr,
+                        sp.missing ? &rm : nullptr, sp.rf_axis ? &ra : nullptr};
         if ((rc = launch_rf(e, rst, B, c.Lmax, c.m, c.sl, c.sb, job, where))) return rc;
     }
     return p.fork ? wait_for(e, e->ev_join, e->aux, st) : BH_OK;
 }
 
-// The likelihood of every model from the synthetics (or the sums of the targets in `fused`) and the failure flags, by launcher
-// `like`.  site: of every model, or null (LIKE_PLAIN)
-int run_like(bh_engine *e, hipStream_t st, LikeKernelArgs la, const bool *fused, EvalLike like, const int32_t *site, const EvalGauss *gauss)
+// The likelihood of every model from the synthetics (or the sums of the targets in `fused`) and the failure flags, by the launcher
+// and the tables of the site plan sp.  site: of every model, or null (LIKE_PLAIN)
+int run_like(bh_engine *e, hipStream_t st, LikeKernelArgs la, const bool *fused, const SitePlan &sp, const int32_t *site)
 {
+    const SiteTable &S = e->sites;
     int rc;
     for (int t = 0; t < la.nt; ++t)
-        if ((rc = prepare_like_target(e, st, la.B, la.ldy, la.ymod, e->targets[(size_t)t], la.t[t], fused[t], site, gauss[t]))) return rc;
+        if ((rc = prepare_like_target(e, st, la.B, la.ldy, la.ymod, t, la.t[t], fused[t], site, sp.gauss[t]))) return rc;
     LikeSiteXArgs lx{};
-    lx.site = site; lx.nsites = e->nsites; lx.yobs = (const double *)e->site_yobs.p; lx.yerr_scaled = (const double *)e->site_yerr.p;
-    lx.logdet_extra = (const double *)e->site_logdet.p; lx.n = (const int32_t *)e->site_xn.p;
-    if (like == LIKE_SITES_C || like == LIKE_SITES_L) { // (the count table: the registered one, or the descriptors' counts where the call has none)
-        LikeClassArgs lc{};
+    lx.site = site; lx.nsites = S.nsites; lx.yobs = (const double *)S.yobs.p; lx.yerr_scaled = (const double *)S.yerr.p;
+    lx.logdet_extra = (const double *)S.logdet.p;
+    lx.n = (const int32_t *)(sp.desc_counts ? S.desc_n.p : S.xn.p);
+    LikeClassArgs lc{};
+    if (sp.like == LIKE_SITES_C || sp.like == LIKE_SITES_L)
         for (int t = 0; t < la.nt; ++t) {
-            const TargetHost &T = e->targets[(size_t)t];
-            if (gauss[t] != GAUSS_CLASSES || T.d.law != BH_LAW_GAUSS) continue;
-            lc.class_of[t] = (const int32_t *)T.gc_class.p;
-            lc.rinv[t] = (const double *)T.gc_rinv.p;
-            lc.logdet[t] = (const double *)T.gc_logdet.p;
+            if (sp.gauss[t] != GAUSS_CLASSES || e->targets[(size_t)t].d.law != BH_LAW_GAUSS) continue;
+            lc.class_of[t] = (const int32_t *)S.t[t].class_of.p;
+            lc.rinv[t] = (const double *)S.t[t].rinv.p;
+            lc.logdet[t] = (const double *)S.t[t].logdet.p;
         }
-        if (!e->site_x) lx.n = (const int32_t *)e->gc_xn.p;
-        ev_begin(e, 2, st);
-        if (like == LIKE_SITES_L) { // (the law-1 tables formed by the table's laws; a law table comes with a count table)
-            lx.yerr_scaled = (const double *)e->law_yerr.p;
-            lx.logdet_extra = (const double *)e->law_logdet.p;
-            const LikeLawArgs lw{(const int32_t *)e->law_tab.p};
-            bh_launch_like_sites_l(la, lx, lc, lw, st);
-        } else {
-            bh_launch_like_sites_c(la, lx, lc, st);
-        }
-        ev_end(e, 2, st);
-        return BH_OK;
-    }
     ev_begin(e, 2, st);
-    if (like == LIKE_SITES_M) bh_launch_like_sites_m(la, lx, st); // (... of which some may be 0)
-    else if (like == LIKE_SITES_X) bh_launch_like_sites_x(la, lx, st); // (a site's own sample counts)
-    else if (like == LIKE_SITES) bh_launch_like_sites(la, lx, st);
+    if (sp.like == LIKE_SITES_L) { // (the law-1 tables formed by the table's laws; a law table comes with a count table)
+        lx.yerr_scaled = (const double *)S.law_yerr.p;
+        lx.logdet_extra = (const double *)S.law_logdet.p;
+        bh_launch_like_sites_l(la, lx, lc, LikeLawArgs{(const int32_t *)S.law.p}, st);
+    } else if (sp.like == LIKE_SITES_C) bh_launch_like_sites_c(la, lx, lc, st);
+    else if (sp.like == LIKE_SITES_M) bh_launch_like_sites_m(la, lx, st); // (counts of which some may be 0)
+    else if (sp.like == LIKE_SITES_X) bh_launch_like_sites_x(la, lx, st); // (a site's own sample counts)
+    else if (sp.like == LIKE_SITES) bh_launch_like_sites(la, lx, st);
     else bh_launch_like(la, st);
     ev_end(e, 2, st);
     return BH_OK;
@@ -2129,7 +2154,7 @@ int run_like(bh_engine *e, hipStream_t st, LikeKernelArgs la, const bool *fused,
 
 // bh_evaluate_batch (site == nullptr: exactly its launches) and bh_evaluate_sites (site = the caller's site index per model):
 // validate, stage the inputs, size the workspaces, run the plan's forward models and likelihood, copy the results back.
-// (The plan is pure and comes first: the validation refuses a call whose plan has a target without forward model.)
+// (The plan is pure and comes first: the validation refuses a call whose plan holds a refusal.)
 int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const int32_t *nlay, const double *h, const double *vp,
              const double *vs, const double *rho, ptrdiff_t sl, ptrdiff_t sb, const int32_t *site, const double *noise,
              double *logL, double *misfits, int32_t *err, double *ymod)
@@ -2146,7 +2171,7 @@ int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const in
     HIPCHK(e, hipSetDevice(e->device));
     if ((rc = stage_eval_inputs(e, host, B, c)) || (rc = size_eval_workspaces(e, p, c))) return rc;
     call_begin(e, c.st);
-    if ((rc = run_forward(e, p, c)) || (rc = run_like(e, c.st, c.la, p.rf_fused, p.like, c.site, p.gauss))) return rc;
+    if ((rc = run_forward(e, p, c)) || (rc = run_like(e, c.st, c.la, p.rf_fused, p.sites, c.site))) return rc;
     call_end(e, c.st);
     HIPCHK(e, hipGetLastError());
     if (!host) return BH_OK;
@@ -2175,7 +2200,8 @@ static int sites_register(bh_engine *e, int nsites, const int32_t *n, const doub
     const int nt = e->nt, ldy = e->ldy;
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    release_sites(e);
+    SiteTable &tab = e->sites;
+    tab.drop(PART_COUNTS);
     const size_t S = (size_t)nsites;
     std::vector<double> se(S * ldy, 1.0), ld(S * nt, 0.0), yo;
     if (n) yo.assign(S * ldy, 0.0);
@@ -2189,18 +2215,19 @@ static int sites_register(bh_engine *e, int nsites, const int32_t *n, const doub
             if (n) std::copy(yobs + s * ldy + T.off, yobs + s * ldy + T.off + ns, yo.data() + s * ldy + T.off);
         }
     int rc;
-    if ((rc = ensure(e, e->site_yobs, S * ldy * sizeof(double))) || (rc = ensure(e, e->site_yerr, S * ldy * sizeof(double))) ||
-        (rc = ensure(e, e->site_logdet, S * nt * sizeof(double)))) {
-        release_sites(e);
+    if ((rc = ensure(e, tab.yobs, S * ldy * sizeof(double))) || (rc = ensure(e, tab.yerr, S * ldy * sizeof(double))) ||
+        (rc = ensure(e, tab.logdet, S * nt * sizeof(double)))) {
+        tab.drop(PART_COUNTS);
         return rc;
     }
-    if (hipMemcpy(e->site_yobs.p, n ? yo.data() : yobs, S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(e->site_yerr.p, se.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(e->site_logdet.p, ld.data(), S * nt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        release_sites(e);
+    if (hipMemcpy(tab.yobs.p, n ? yo.data() : yobs, S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(tab.yerr.p, se.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(tab.logdet.p, ld.data(), S * nt * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        tab.drop(PART_COUNTS);
         return fail(e, BH_EHIP, "copy site table");
     }
-    e->nsites = nsites;
+    tab.nsites = nsites;
+    tab.level = SITES_SHARED;
     return BH_OK;
 }
 
@@ -2215,12 +2242,9 @@ int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yer
     return sites_register(e, nsites, nullptr, yobs, yerr);
 }
 
-// bh_sites_set_x, bh_sites_set_x_all and bh_sites_set_missing (who: the entry point's name, for the messages).  all: per-site
-// periods and counts on group-velocity and higher-mode targets are accepted -- the one check bh_sites_set_x_all skips.  missing
-// (with all): a count of 0 is accepted on any target -- the site lacks it -- but every site has a target and every target a site.
-// missing_gauss (with missing): ... on a Gauss-law target as well -- the one check bh_sites_set_missing_gauss skips.
-// axes (with missing_gauss): a receiver function's count may be 0 or 1 .. its descriptor's n -- the one check bh_sites_set_axes skips.
-static int sites_register_x(bh_engine *e, const char *who, bool all, bool missing, bool missing_gauss, bool axes, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
+// The count tables, bh_sites_set_x ... bh_sites_set_axes (who: the entry point's name, for the messages; level: what it registers,
+// SITES_X ... SITES_AXES).  Every level admits one thing more than the one before it, named below where it is checked.
+static int sites_register_x(bh_engine *e, const char *who, SiteLevel level, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
     if (!e) return BH_EINVAL;
     const std::string w(who);
@@ -2231,7 +2255,11 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, bool missin
     for (const auto &T : e->targets) scaled = scaled || T.d.law == BH_LAW_NOCORR_SCALED;
     if (scaled && !yerr) return fail(e, BH_EINVAL, "a BH_LAW_NOCORR_SCALED target needs yerr of every site");
     const size_t S = (size_t)nsites;
-    if (missing) {
+    const bool admits_any_dispersion = level >= SITES_X_ALL;        // per-site periods and counts on group-velocity and higher-mode targets
+    const bool admits_absent = level >= SITES_MISSING;              // a count of 0 -- the site lacks the target -- but every site has a target and every target a site
+    const bool admits_absent_gauss = level >= SITES_MISSING_GAUSS;  // ... on a Gauss-law target as well
+    const bool admits_rf_counts = level >= SITES_AXES;              // a receiver function's count may be 0 or 1 .. its descriptor's n
+    if (admits_absent) {
         for (size_t s = 0; s < S; ++s) {
             bool any = false;
             for (int t = 0; t < nt; ++t) any = any || n[s * nt + t] != 0;
@@ -2244,7 +2272,7 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, bool missin
                 lacks = lacks || n[s * nt + t] == 0;
             }
             if (!any) return fail(e, BH_EINVAL, (w + ": a target no site has (every count 0)").c_str());
-            if (lacks && !missing_gauss && e->targets[(size_t)t].d.law == BH_LAW_GAUSS)
+            if (lacks && !admits_absent_gauss && e->targets[(size_t)t].d.law == BH_LAW_GAUSS)
                 return fail(e, BH_EUNSUPPORTED, (w + ": a Gauss-law target that a site lacks (the contraction gathers every site's rows)").c_str());
         }
     }
@@ -2253,9 +2281,9 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, bool missin
         const bh_target_desc &d = T.d;
         if (d.kind != BH_TARGET_SWD) { // (a receiver function's x is its descriptor's time axis: shared, but for bh_sites_set_axes)
             for (size_t s = 0; s < S; ++s) {
-                if (axes && d.kind == BH_TARGET_RF && n[s * nt + t] >= 0 && n[s * nt + t] <= d.n) continue;
-                if (axes && d.kind == BH_TARGET_RF) return fail(e, BH_EINVAL, (w + ": a receiver function's sample count is below 0 or above its descriptor's n (the capacity)").c_str());
-                if (n[s * nt + t] != d.n && !(missing && n[s * nt + t] == 0)) return fail(e, BH_EINVAL, (w + ": the sample count of a target that is no dispersion curve differs from its descriptor's").c_str());
+                if (admits_rf_counts && d.kind == BH_TARGET_RF && n[s * nt + t] >= 0 && n[s * nt + t] <= d.n) continue;
+                if (admits_rf_counts && d.kind == BH_TARGET_RF) return fail(e, BH_EINVAL, (w + ": a receiver function's sample count is below 0 or above its descriptor's n (the capacity)").c_str());
+                if (n[s * nt + t] != d.n && !(admits_absent && n[s * nt + t] == 0)) return fail(e, BH_EINVAL, (w + ": the sample count of a target that is no dispersion curve differs from its descriptor's").c_str());
             }
             continue;
         }
@@ -2263,14 +2291,14 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, bool missin
         if (T.kfwd != d.n) return fail(e, BH_EUNSUPPORTED, (w + ": a dispersion target of more than 60 periods (the interpolation path)").c_str());
         for (size_t s = 0; s < S; ++s) {
             const int ns = n[s * nt + t];
-            if (missing && ns == 0) continue; // (the site lacks this curve)
+            if (admits_absent && ns == 0) continue; // (the site lacks this curve)
             if (ns < 1 || ns > d.n) return fail(e, BH_EINVAL, (w + ": a site's period count is below 1 or above the descriptor's n (the capacity)").c_str());
             for (int i = 0; i < ns; ++i) {
                 const double v = x[s * ldy + T.off + i];
                 if (!std::isfinite(v) || !(v > 0.0)) return fail(e, BH_EINVAL, (w + ": a period that is not finite and positive").c_str());
             }
         }
-        if (!all && (d.igr != BH_VEL_PHASE || d.mode > 1)) { // group velocities, higher modes: only with the descriptor's periods at every site
+        if (!admits_any_dispersion && (d.igr != BH_VEL_PHASE || d.mode > 1)) { // group velocities, higher modes: only with the descriptor's periods at every site
             std::vector<double> x0((size_t)d.n);
             HIPCHK(e, hipSetDevice(e->device));
             HIPCHK(e, hipMemcpy(x0.data(), T.x.p, (size_t)d.n * sizeof(double), hipMemcpyDeviceToHost));
@@ -2287,62 +2315,62 @@ static int sites_register_x(bh_engine *e, const char *who, bool all, bool missin
             const TargetHost &T = e->targets[(size_t)t];
             if (T.d.kind == BH_TARGET_SWD) std::copy(x + s * ldy + T.off, x + s * ldy + T.off + n[s * nt + t], xs.data() + s * ldy + T.off);
         }
-    if ((rc = ensure(e, e->site_xn, S * nt * sizeof(int32_t))) || (rc = ensure(e, e->site_xper, S * ldy * sizeof(double)))) {
-        release_sites(e);
+    SiteTable &tab = e->sites;
+    if ((rc = ensure(e, tab.xn, S * nt * sizeof(int32_t))) || (rc = ensure(e, tab.xper, S * ldy * sizeof(double)))) {
+        tab.drop(PART_COUNTS);
         return rc;
     }
-    if (hipMemcpy(e->site_xn.p, n, S * nt * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(e->site_xper.p, xs.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        release_sites(e);
+    if (hipMemcpy(tab.xn.p, n, S * nt * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(tab.xper.p, xs.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        tab.drop(PART_COUNTS);
         return fail(e, BH_EHIP, "copy site table");
     }
-    e->site_x = true;
-    e->site_x_all = all;
-    e->site_missing = missing;
-    e->site_missing_gauss = missing_gauss;
-    e->site_xn_host.assign(n, n + S * nt);
+    tab.level = level;
+    tab.xn_host.assign(n, n + S * nt);
     for (int t = 0; t < nt; ++t)
         for (size_t s = 0; s < S; ++s)
-            if (n[s * nt + t] == 0) e->targets[(size_t)t].site_lacks = true;
-            else if (e->targets[(size_t)t].d.kind == BH_TARGET_RF && n[s * nt + t] != e->targets[(size_t)t].d.n) e->targets[(size_t)t].rf_own_counts = true;
+            if (n[s * nt + t] == 0) tab.t[t].lacks = true;
+            else if (e->targets[(size_t)t].d.kind == BH_TARGET_RF && n[s * nt + t] != e->targets[(size_t)t].d.n) tab.t[t].rf_own_counts = true;
     return BH_OK;
 }
 
 int bh_sites_set_x(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_x", false, false, false, false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_x", SITES_X, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_x_all(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_x_all", true, false, false, false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_x_all", SITES_X_ALL, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_missing(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_missing", true, true, false, false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_missing", SITES_MISSING, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_missing_gauss(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_missing_gauss", true, true, true, false, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_missing_gauss", SITES_MISSING_GAUSS, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_axes(bh_engine *e, int nsites, const int32_t *n, const double *x, const double *yobs, const double *yerr)
 {
-    return sites_register_x(e, "bh_sites_set_axes", true, true, true, true, nsites, n, x, yobs, yerr);
+    return sites_register_x(e, "bh_sites_set_axes", SITES_AXES, nsites, n, x, yobs, yerr);
 }
 
 int bh_sites_set_gauss(bh_engine *e, int target, int nsites, int nclass, const int32_t *class_of, const double *rinv, const double *logdet_r)
 {
     if (!e) return BH_EINVAL;
-    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
-    if (nsites != e->nsites) return fail(e, BH_EINVAL, "bh_sites_set_gauss: nsites differs from the site table's");
+    if (e->sites.nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (nsites != e->sites.nsites) return fail(e, BH_EINVAL, "bh_sites_set_gauss: nsites differs from the site table's");
     if (target < 0 || target >= e->nt || e->targets[(size_t)target].d.law != BH_LAW_GAUSS)
         return fail(e, BH_EINVAL, "bh_sites_set_gauss: not a BH_LAW_GAUSS target");
     if (nclass < 1) return fail(e, BH_EINVAL, "bh_sites_set_gauss: nclass must be at least 1");
     if (!class_of || !rinv || !logdet_r) return fail(e, BH_EINVAL, "null argument");
-    TargetHost &T = e->targets[(size_t)target];
+    const TargetHost &T = e->targets[(size_t)target];
+    SiteTable &tab = e->sites;
+    SiteTarget &G = tab.t[target];
     const size_t nn = (size_t)T.d.n * (size_t)T.d.n, S = (size_t)nsites, nt = (size_t)e->nt;
     if ((size_t)nclass > BH_SITES_GAUSS_MAXBYTES / sizeof(double) / nn)
         return fail(e, BH_EUNSUPPORTED, "bh_sites_set_gauss: the matrices take more than BH_SITES_GAUSS_MAXBYTES (1 GiB)");
@@ -2350,9 +2378,9 @@ int bh_sites_set_gauss(bh_engine *e, int target, int nsites, int nclass, const i
     for (size_t s = 0; s < S; ++s) {
         const int c = class_of[s];
         if (c < -1 || c >= nclass) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a class index outside [-1, nclass)");
-        const bool has = e->site_xn_host.empty() || e->site_xn_host[s * nt + (size_t)target] != 0; // (bh_sites_set: every site has every target)
-        if (has && e->site_laws) { // (bh_sites_set_laws: a class exactly for the sites under the Gauss law on this target)
-            const bool gauss = e->site_law_host[s * nt + (size_t)target] == BH_LAW_GAUSS;
+        const bool has = tab.xn_host.empty() || tab.xn_host[s * nt + (size_t)target] != 0; // (bh_sites_set: every site has every target)
+        if (has && tab.laws) { // (bh_sites_set_laws: a class exactly for the sites under the Gauss law on this target)
+            const bool gauss = tab.law_host[s * nt + (size_t)target] == BH_LAW_GAUSS;
             if (gauss && c < 0) return fail(e, BH_EINVAL, "bh_sites_set_gauss: class -1 for a site under the Gauss law on the target (bh_sites_set_laws)");
             if (!gauss && c >= 0) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a class for a site under another law than BH_LAW_GAUSS on the target (bh_sites_set_laws)");
             continue;
@@ -2366,32 +2394,32 @@ int bh_sites_set_gauss(bh_engine *e, int target, int nsites, int nclass, const i
         if (!std::isfinite(logdet_r[c])) return fail(e, BH_EINVAL, "bh_sites_set_gauss: a non-finite value in logdet_r");
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    T.gc_nclass = 0;
+    tab.drop(PART_CLASSES, target);
     int rc;
-    if ((rc = ensure(e, T.gc_rinv, (size_t)nclass * nn * sizeof(double))) || (rc = ensure(e, T.gc_logdet, (size_t)nclass * sizeof(double))) ||
-        (rc = ensure(e, T.gc_class, S * sizeof(int32_t))))
+    if ((rc = ensure(e, G.rinv, (size_t)nclass * nn * sizeof(double))) || (rc = ensure(e, G.logdet, (size_t)nclass * sizeof(double))) ||
+        (rc = ensure(e, G.class_of, S * sizeof(int32_t))))
         return rc;
-    HIPCHK(e, hipMemcpy(T.gc_rinv.p, rinv, (size_t)nclass * nn * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(T.gc_logdet.p, logdet_r, (size_t)nclass * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(T.gc_class.p, class_of, S * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!e->site_x && !e->gc_xn.p) { // no count table in force: the likelihood build of the class calls reads the descriptors' counts
+    HIPCHK(e, hipMemcpy(G.rinv.p, rinv, (size_t)nclass * nn * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(G.logdet.p, logdet_r, (size_t)nclass * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(G.class_of.p, class_of, S * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (tab.level < SITES_X && !tab.desc_n.p) { // no count table in force: the likelihood build of the class calls reads the descriptors' counts
         std::vector<int32_t> cnt(S * nt);
         for (size_t s = 0; s < S; ++s)
             for (size_t t = 0; t < nt; ++t) cnt[s * nt + t] = e->targets[t].d.n;
-        if ((rc = ensure(e, e->gc_xn, S * nt * sizeof(int32_t)))) return rc;
-        HIPCHK(e, hipMemcpy(e->gc_xn.p, cnt.data(), S * nt * sizeof(int32_t), hipMemcpyHostToDevice));
+        if ((rc = ensure(e, tab.desc_n, S * nt * sizeof(int32_t)))) return rc;
+        HIPCHK(e, hipMemcpy(tab.desc_n.p, cnt.data(), S * nt * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    T.gc_nclass = nclass;
+    G.nclass = nclass;
     return BH_OK;
 }
 
 int bh_sites_set_laws(bh_engine *e, int nsites, const int32_t *law, const double *yerr)
 {
     if (!e) return BH_EINVAL;
-    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
-    if (!e->site_x || !e->site_missing_gauss)
+    if (e->sites.nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (e->sites.level < SITES_MISSING_GAUSS)
         return fail(e, BH_EINVAL, "bh_sites_set_laws: no count table registered that accepts a Gauss-law target some site lacks (bh_sites_set_missing_gauss, bh_sites_set_axes)");
-    if (nsites != e->nsites) return fail(e, BH_EINVAL, "bh_sites_set_laws: nsites differs from the site table's");
+    if (nsites != e->sites.nsites) return fail(e, BH_EINVAL, "bh_sites_set_laws: nsites differs from the site table's");
     if (!law) return fail(e, BH_EINVAL, "null argument");
     const int nt = e->nt, ldy = e->ldy;
     const size_t S = (size_t)nsites;
@@ -2401,7 +2429,7 @@ int bh_sites_set_laws(bh_engine *e, int nsites, const int32_t *law, const double
     for (size_t s = 0; s < S; ++s)
         for (int t = 0; t < nt; ++t) {
             const TargetHost &T = e->targets[(size_t)t];
-            const int ns = e->site_xn_host[s * nt + t];
+            const int ns = e->sites.xn_host[s * nt + t];
             if (ns == 0) continue; // (the site lacks the target)
             const int l = law[s * nt + t];
             if (l != BH_LAW_NOCORR && l != BH_LAW_NOCORR_SCALED && l != BH_LAW_EXP && l != BH_LAW_GAUSS)
@@ -2421,25 +2449,26 @@ int bh_sites_set_laws(bh_engine *e, int nsites, const int32_t *law, const double
         }
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    release_laws(e); // (and the class tables, which were checked against the laws in force before)
+    SiteTable &tab = e->sites;
+    tab.drop(PART_LAWS);
     int rc;
-    if ((rc = ensure(e, e->law_tab, S * nt * sizeof(int32_t))) || (rc = ensure(e, e->law_yerr, S * ldy * sizeof(double))) ||
-        (rc = ensure(e, e->law_logdet, S * nt * sizeof(double))))
+    if ((rc = ensure(e, tab.law, S * nt * sizeof(int32_t))) || (rc = ensure(e, tab.law_yerr, S * ldy * sizeof(double))) ||
+        (rc = ensure(e, tab.law_logdet, S * nt * sizeof(double))))
         return rc;
-    HIPCHK(e, hipMemcpy(e->law_tab.p, lw.data(), S * nt * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(e->law_yerr.p, se.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(e->law_logdet.p, ld.data(), S * nt * sizeof(double), hipMemcpyHostToDevice));
-    for (int t = 0; t < nt; ++t) e->targets[(size_t)t].law_other = other[(size_t)t] != 0;
-    e->site_law_host = lw;
-    e->site_laws = true;
+    HIPCHK(e, hipMemcpy(tab.law.p, lw.data(), S * nt * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(tab.law_yerr.p, se.data(), S * ldy * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(tab.law_logdet.p, ld.data(), S * nt * sizeof(double), hipMemcpyHostToDevice));
+    for (int t = 0; t < nt; ++t) tab.t[t].law_other = other[(size_t)t] != 0;
+    tab.law_host = lw;
+    tab.laws = true;
     return BH_OK;
 }
 
 int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const double *nsv)
 {
     if (!e) return BH_EINVAL;
-    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
-    if (nsites != e->nsites) return fail(e, BH_EINVAL, "bh_sites_set_rf: nsites differs from the site table's");
+    if (e->sites.nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (nsites != e->sites.nsites) return fail(e, BH_EINVAL, "bh_sites_set_rf: nsites differs from the site table's");
     if (!p_s_per_deg || !nsv) return fail(e, BH_EINVAL, "null argument");
     const int nt = e->nt;
     const size_t n = (size_t)nsites * (size_t)nt;
@@ -2451,23 +2480,23 @@ int bh_sites_set_rf(bh_engine *e, int nsites, const double *p_s_per_deg, const d
     }
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    e->site_rf = e->site_rf_axis = false; // (the axis table belongs to this one)
-    release_laws(e); // (every entry point that registers or extends the site table drops the law table and the correlation classes)
+    SiteTable &tab = e->sites;
+    tab.drop(PART_RF);
     int rc;
-    if ((rc = ensure(e, e->site_p, n * sizeof(double))) || (rc = ensure(e, e->site_nsv, n * sizeof(double)))) return rc;
-    HIPCHK(e, hipMemcpy(e->site_p.p, p_s_per_deg, n * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(e->site_nsv.p, nsv, n * sizeof(double), hipMemcpyHostToDevice));
-    e->site_rf = true;
+    if ((rc = ensure(e, tab.p, n * sizeof(double))) || (rc = ensure(e, tab.nsv, n * sizeof(double)))) return rc;
+    HIPCHK(e, hipMemcpy(tab.p.p, p_s_per_deg, n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(tab.nsv.p, nsv, n * sizeof(double), hipMemcpyHostToDevice));
+    tab.rf = true;
     return BH_OK;
 }
 
 int bh_sites_set_rf_axis(bh_engine *e, int nsites, const int32_t *nsamp, const double *fsamp, const double *tshift, const double *gauss)
 {
     if (!e) return BH_EINVAL;
-    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
-    if (!e->site_x) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: no count table registered (bh_sites_set_axes)");
-    if (!e->site_rf) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis needs the table of bh_sites_set_rf (the coefficient stage finds the model's site through it)");
-    if (nsites != e->nsites) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: nsites differs from the site table's");
+    if (e->sites.nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (e->sites.level < SITES_X) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: no count table registered (bh_sites_set_axes)");
+    if (!e->sites.rf) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis needs the table of bh_sites_set_rf (the coefficient stage finds the model's site through it)");
+    if (nsites != e->sites.nsites) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: nsites differs from the site table's");
     if (!nsamp || !fsamp || !tshift || !gauss) return fail(e, BH_EINVAL, "null argument");
     const int nt = e->nt;
     const size_t S = (size_t)nsites;
@@ -2477,7 +2506,7 @@ int bh_sites_set_rf_axis(bh_engine *e, int nsites, const int32_t *nsamp, const d
         if (e->targets[(size_t)t].d.kind != BH_TARGET_RF) continue;
         for (size_t s = 0; s < S; ++s) {
             const size_t i = s * (size_t)nt + (size_t)t;
-            const int cnt = e->site_xn_host[i];
+            const int cnt = e->sites.xn_host[i];
             if (cnt == 0) continue; // (the site lacks the target)
             const int ns = nsamp[i];
             if (ns < 4 || (ns & (ns - 1)) != 0) return fail(e, BH_EINVAL, "bh_sites_set_rf_axis: nsamp must be a power of two >= 4");
@@ -2493,13 +2522,13 @@ int bh_sites_set_rf_axis(bh_engine *e, int nsites, const int32_t *nsamp, const d
     }
     HIPCHK(e, hipSetDevice(e->device));
     HIPCHK(e, hipStreamSynchronize(e->stream));
-    e->site_rf_axis = false;
-    release_laws(e); // (every entry point that registers or extends the site table drops the law table and the correlation classes)
+    SiteTable &tab = e->sites;
+    tab.drop(PART_RF_AXIS);
     int rc;
-    if ((rc = ensure(e, e->site_axis, recs.size() * sizeof(RfAxisRec)))) return rc;
-    HIPCHK(e, hipMemcpy(e->site_axis.p, recs.data(), recs.size() * sizeof(RfAxisRec), hipMemcpyHostToDevice));
-    for (int t = 0; t < nt; ++t) e->targets[(size_t)t].axis_nsamp_max = nmax[(size_t)t];
-    e->site_rf_axis = true;
+    if ((rc = ensure(e, tab.axis, recs.size() * sizeof(RfAxisRec)))) return rc;
+    HIPCHK(e, hipMemcpy(tab.axis.p, recs.data(), recs.size() * sizeof(RfAxisRec), hipMemcpyHostToDevice));
+    for (int t = 0; t < nt; ++t) tab.t[t].axis_nsamp_max = nmax[(size_t)t];
+    tab.rf_axis = true;
     return BH_OK;
 }
 
@@ -2509,7 +2538,7 @@ int bh_evaluate_sites(bh_engine *e, int memspace, void *stream, int B, int Lmax,
                       double *logL, double *misfits, int32_t *err, double *ymod)
 {
     if (!e) return BH_EINVAL;
-    if (e->nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
+    if (e->sites.nsites < 1) return fail(e, BH_EINVAL, "no site table registered (bh_sites_set)");
     if (!site) return fail(e, BH_EINVAL, "null argument");
     return evaluate(e, memspace, stream, B, Lmax, nlay, h, vp, vs, rho, stride_l, stride_b, site, noise, logL, misfits, err, ymod);
 }
@@ -2547,8 +2576,7 @@ int bh_loglike_batch(bh_engine *e, int memspace, void *stream, int B, const doub
     }
     call_begin(e, st);
     const bool unfused[BH_MAX_TARGETS] = {}; // (the caller's synthetics)
-    const EvalGauss plain[BH_MAX_TARGETS] = {};
-    if ((rc = run_like(e, st, la, unfused, LIKE_PLAIN, nullptr, plain))) return rc;
+    if ((rc = run_like(e, st, la, unfused, SitePlan{}, nullptr))) return rc; // (LIKE_PLAIN, GAUSS_PLAIN)
     call_end(e, st);
     HIPCHK(e, hipGetLastError());
     if (!host) return BH_OK;

@@ -336,3 +336,66 @@ def test_fused_exponential_receiver_function_against_the_reference(engine, n, ns
     ok = e1 == 0
     assert ok.mean() > 0.8
     check((L1[ok], m1[ok], e1[ok]), descs, y2[ok], noise[ok], "fused RF exp n=%d" % n)
+
+
+# ---- the six launch paths of the likelihood, bit for bit against the build before the engine's site state became one SiteTable ----
+LAUNCH_PATHS = ("plain", "sites", "x", "missing", "classes", "laws")   # bh_launch_like, _sites, _sites_x, _sites_m, _sites_c, _sites_l
+LAUNCH_FORMS = {"small": 3, "workgroup": 65}                           # samples of the receiver function beside a curve of 3 periods
+
+
+def launch_path_outputs(eng, path, form, B):
+    """(logL, misfits, err) of B models over [Rayleigh phase velocities at 3 periods, scaled-error law; P receiver function of 3
+    or 65 samples, Gauss law] and three sites, through one launch path.  Site 1 has two periods ("x") or lacks the curve
+    ("missing" and up), has the second correlation class ("classes") and the nocorr law on its receiver function ("laws", where
+    site 0's curve is under the exponential law); model 3 of 5 names a site out of range (the device entry fails it in band)."""
+    from bayhunter_amd.synth import synth_models
+    from test_gpu_sites import eval_device
+    n = LAUNCH_FORMS[form]
+    rs = np.random.RandomState(100 * n + B)
+    ldy, per = 3 + n, np.array([5.0, 12.0, 30.0])
+    yobs = np.hstack([3.2 + 0.02 * per + rs.normal(0, 0.05, (3, 3)), rs.normal(0, 0.05, (3, n))])
+    yerr = rs.uniform(0.02, 0.06, (3, ldy))
+    mats = [gauss_matrix(kind, n) for kind in ("pinv", "random")]
+    descs = [dict(kind=E.TARGET_SWD, law=E.LAW_NOCORR_SCALED, n=3, x=per, yobs=yobs[0, :3], yerr=yerr[0, :3], iwave=2, igr=0),
+             dict(kind=E.TARGET_RF, law=E.LAW_GAUSS, n=n, yobs=yobs[0, 3:], waveno=0, p=6.4, gauss=2.5, tshift=5.0, nsamp=128,
+                  fsamp=5.0, rinv=mats[0][0], logdet_r=mats[0][1])]
+    nlay, h, vp, vs, rho = synth_models(rs, B, 10, ragged=True)
+    noise = np.column_stack([np.zeros(B), rs.uniform(0.02, 0.1, B), np.full(B, 0.92), rs.uniform(0.02, 0.1, B)])
+    site = np.array([1] if B == 1 else [0, 1, 2, 3, 1], dtype=np.int32)
+    eng.set_targets(descs)
+    if path == "plain":
+        return eng.evaluate_batch(nlay, h, vp, vs, noise, rho=rho)
+    cnt = np.array([[3, n], [2 if path == "x" else 0, n], [1, n]], dtype=np.int32)
+    x = np.zeros((3, ldy))
+    x[:, :3] = per
+    if path == "sites":
+        eng.set_sites(yobs, yerr)
+    else:
+        {"x": eng.set_sites_x, "missing": eng.set_sites_missing}.get(path, eng.set_sites_missing_gauss)(cnt, x, yobs, yerr)
+        eng.set_sites_rf(np.tile([0.0, 6.4], (3, 1)), np.zeros((3, 2)))
+    if path == "laws":
+        eng.set_sites_laws(np.array([[E.LAW_EXP, E.LAW_GAUSS], [0, E.LAW_NOCORR], [E.LAW_NOCORR_SCALED, E.LAW_GAUSS]], dtype=np.int32), yerr)
+    if path in ("classes", "laws"):
+        eng.set_sites_gauss(1, np.array([0, -1 if path == "laws" else 1, 0], dtype=np.int32), np.stack([m[0] for m in mats]),
+                            np.array([m[1] for m in mats]))
+    return eval_device(eng, (nlay, h, vp, vs, rho), noise, site, ldy)[:3]
+
+
+@pytest.mark.parametrize("B", [1, 5])
+@pytest.mark.parametrize("form", sorted(LAUNCH_FORMS))
+@pytest.mark.parametrize("path", LAUNCH_PATHS)
+def test_every_launch_path_keeps_the_recorded_bits(engine, path, form, B):
+    """tests/golden/like_paths_golden.npz holds what launch_path_outputs returned on an MI355X from the commit before run_like took
+    its launcher, tables and count source from the site plan and the SiteTable (recorded once with that build's library; not
+    from the code under test).  It also stands ready for a change of the kernels themselves."""
+    from conftest import golden
+    want = golden("like_paths_golden.npz")
+    got = launch_path_outputs(engine, path, form, B)
+    if B == 5 and path != "plain":
+        assert got[2][3] == 1 and got[0][3] == -1e15 and np.all(got[1][3] == 1e15), "the model of a site out of range"
+        assert np.all(got[2][[0, 1, 2, 4]] == 0)
+    if path in ("missing", "classes", "laws"):
+        assert got[1][-1, 0] == 0.0, "the misfit of the curve site 1 lacks"
+    for name, a in zip(("logL", "misfits", "err"), got):
+        w = want["%s_%s_%d_%s" % (path, form, B, name)]
+        assert a.dtype == w.dtype and a.shape == w.shape and a.tobytes() == w.tobytes(), "%s %s B=%d: %s" % (path, form, B, name)

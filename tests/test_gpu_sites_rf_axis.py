@@ -516,6 +516,31 @@ def test_gauss_law_refusals(engine):
         engine.set_tuning("no_mfma", before)
 
 
+def test_the_axis_table_drops_the_laws_and_the_classes(engine):
+    """bh_sites_set_rf_axis anew: the law table and the class tables registered on top of the axis table are gone -- the call is
+    refused for the class table it needs again, and a class of -1 for a site that has the target is no longer accepted"""
+    rs = np.random.RandomState(5)
+    spec = [((128, 40, 5.0, 2.0, 1.0), 0.90), ((128, 64, 5.0, 0.0, 2.5), 0.94)]
+    descs = gauss_sites(spec, rs)
+    B = 16
+    mods = models(rs, B, 10)
+    noise = np.tile([0.0, 0.05, 0.0, 0.05], (B, 1))
+    site = (np.arange(B) % 2).astype(np.int32)
+    class_of, rinv, logdet = padded_classes(spec, 64)
+    under_laws = np.array([class_of[0], -1], np.int32)            # site 1's trace under the nocorr law: no class
+    T = register(engine, descs)
+    engine.set_sites_laws(np.array([[E.LAW_NOCORR, E.LAW_GAUSS], [E.LAW_NOCORR, E.LAW_NOCORR]], np.int32))
+    engine.set_sites_gauss(1, under_laws, rinv, logdet)
+    assert (engine.evaluate_sites(*mods[:4], noise, site, rho=mods[4])[2] == 0).any()
+    engine.set_sites_rf_axis(T["nsamp"], T["fsamp"], T["tshift"], T["gauss"])
+    with pytest.raises(E.EngineError, match="bh_sites_set_gauss"):
+        engine.evaluate_sites(*mods[:4], noise, site, rho=mods[4])
+    with pytest.raises(E.EngineError, match="has the target"):
+        engine.set_sites_gauss(1, under_laws, rinv, logdet)
+    engine.set_sites_gauss(1, class_of, rinv, logdet)
+    assert (engine.evaluate_sites(*mods[:4], noise, site, rho=mods[4])[2] == 0).any()
+
+
 # ---- chains ------------------------------------------------------------------------------------------------
 PRIORS = dict(vpvs=(1.4, 2.1), layers=(1, 10), vs=(2, 5), z=(0, 60), rfnoise_corr=(0.35, 0.75),
               rfnoise_sigma=(1e-5, 0.05), swdnoise_corr=0., swdnoise_sigma=(1e-5, 0.1))
