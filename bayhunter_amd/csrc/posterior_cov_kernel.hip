@@ -11,7 +11,7 @@
 //              Lo.H into one accumulator, Lo.Lo.  At the end of the chunk the accumulators are converted to integers (exact) and
 //              meet the other chunks in 64-bit integer atomics; so do the column sums.  No floating-point atomics anywhere.
 // The finished numbers are formed on the host with 128-bit integers (bh_posterior_cov_finish).
-#include "posterior_common.h"
+#include "posterior_select.h"
 #include "../../include/bh_engine_posterior_cov.h"
 #include "../../include/bh_engine_posterior_features.h"
 
@@ -235,14 +235,6 @@ __global__ void __launch_bounds__(256) cov_contract_kernel(CovArgs a, const int3
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 
-double cov_key2d(uint64_t k)
-{
-    const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v;
-    std::memcpy(&v, &u, 8);
-    return v;
-}
-
 // rint(mx 2^-L) - rint(mn 2^-L) < 2^28 (both integers of at most 53 bits where L is at or above the lowest set bit: the difference
 // may round, never across 2^28)
 bool cov_fits(double mn, double mx, int L)
@@ -423,7 +415,7 @@ int bh_posterior_cov(bh_posterior *p, int D, const double *dep, int set, int Qc,
         xh[c] = 0;
         ex[c] = 1;
         if (nh[c / P] == 0) continue;
-        const double vmn = cov_key2d(kmin[c]), vmx = cov_key2d(kmax[c]);
+        const double vmn = key2d(kmin[c]), vmx = key2d(kmax[c]);
         if (!std::isfinite(vmn) || !std::isfinite(vmx))
             return pfail(p, BH_EINVAL, c % P < (size_t)D ? "a velocity is not finite" : "a value of a scalar column is not finite");
         if (vmn == 0.0 && vmx == 0.0) continue; // zeros only (no set bit: low is still what the memset left)

@@ -7,39 +7,21 @@
 //   fill    : ymod [nb][ldy] -> val[q * nrows + r] through an LDS tile of 64 x 64 float64, rows 65 apart: a wavefront reads 64
 //             consecutive q of a row (512 B) and writes 64 consecutive r of a column; the tile's ds_write_b64 are contiguous,
 //             its ds_read_b64 go 130 dwords apart -- lanes 0..31 to the even banks 0..62 of 64, one 2-bank pair each: no conflict
-//   mradix  : the radix select of posterior_scalars_kernel.hip for R ranks in one read of the column per pass: R x 256 LDS
-//             counters, a key counted for rank r where it matches r's prefix; ranks whose prefixes are equal share the counters
-//             of the first of them (pass 0 costs one LDS atomic per key whatever R is)
-//   mnext   : per rank the keys <= the selected one and the least key above it
+//   quantiles : the radix select of posterior_select.h for R ranks in one read of the column per pass
 // Chunks meet in integer atomics only, so the results are the same bits in every run, alone or among other sites.
-// LDS: 33 280 B (fill: 4 workgroups of 256 lanes beside each other on a CU's 160 KiB), 8 KiB (mradix).  No kernel uses scratch
+// LDS: 33 280 B (fill: 4 workgroups of 256 lanes beside each other on a CU's 160 KiB), 8 KiB (the select of 8 ranks).  No kernel uses scratch
 // (profiles/posterior_datafits_kernels.txt).  -ffp-contract=off (Makefile): rho's product is rounded before its sum.
-#include "posterior_common.h"
-#include "../../include/bh_engine_posterior_datafit.h"
+#include "posterior_select.h"
 
 #include <algorithm>
 #include <cstring>
 
 #define DF_THREADS 256
 #define DF_TILE 64
-#define DF_MAXR BH_QUANTILES_MAXRANKS
 
 using namespace bhpost;
 
 namespace {
-
-__device__ __forceinline__ double qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
-{
-    for (int o = 32; o; o >>= 1) { const unsigned long long u = __shfl_xor(v, o); v = u < v ? u : v; }
-    return v;
-}
 
 // one lane per row of [r0, r1): the layer rule (header)
 template <typename T, typename V>
@@ -178,149 +160,6 @@ __global__ void __launch_bounds__(DF_THREADS) df_fill_kernel(int64_t r0, int64_t
     }
 }
 
-struct SetArgs {
-    const PostWork *work;
-    const double *val;
-    int64_t nrows;
-    int Q;
-};
-
-// the first rank of 0..r whose prefix above bit hs equals r's: it owns the counters r reads
-#define DF_LEAD(lead, p, r, R, hs)                                                       \
-    do {                                                                                 \
-        lead = r;                                                                        \
-        _Pragma("unroll") for (int r2 = DF_MAXR - 1; r2 >= 0; --r2)                      \
-            if (r2 < r && r2 < R && (hs >= 64 || ((p[r2] ^ p[r]) >> hs) == 0ull)) lead = r2; \
-    } while (0)
-
-// pass `pass` of the multi-rank radix select: per (site, column, rank) the histogram of the 8-bit digit at kbits[q] - 8 * (pass +
-// 1) over the keys that match the rank's prefix above it
-__global__ void __launch_bounds__(DF_THREADS) df_mradix_kernel(SetArgs a, int R, const int *kbits, int pass,
-                                                               const unsigned long long *pref, unsigned *ghist)
-{
-    __shared__ unsigned h[DF_MAXR * 256];
-    const PostWork w = a.work[blockIdx.x];
-    const int q = blockIdx.y;
-    const int kb = kbits[q];
-    const int shift = kb - 8 * (pass + 1);
-    if (shift < 0) return; // (uniform over the workgroup: before the barriers)
-    const int hs = shift + 8;
-    const size_t c = (size_t)w.site * a.Q + q;
-    unsigned long long p[DF_MAXR];
-    bool own[DF_MAXR];
-#pragma unroll
-    for (int r = 0; r < DF_MAXR; ++r) p[r] = r < R ? pref[c * R + r] : 0ull;
-#pragma unroll
-    for (int r = 0; r < DF_MAXR; ++r) {
-        int lead;
-        DF_LEAD(lead, p, r, R, hs);
-        own[r] = r < R && lead == r;
-    }
-#pragma unroll
-    for (int r = 0; r < DF_MAXR; ++r)
-        if (r < R) h[r * 256 + threadIdx.x] = 0u;   // DF_THREADS == 256
-    __syncthreads();
-    const double *col = a.val + (int64_t)q * a.nrows;
-    for (int64_t i = w.r0 + threadIdx.x; i < w.r1; i += DF_THREADS) {
-        const double v = col[i];
-        if (v != v) continue;
-        const unsigned long long k = okey(v, kb == 32);
-        const unsigned dg = (unsigned)(k >> shift) & 255u;
-#pragma unroll
-        for (int r = 0; r < DF_MAXR; ++r)
-            if (own[r] && (hs >= 64 || ((k ^ p[r]) >> hs) == 0ull)) atomicAdd(&h[r * 256 + dg], 1u);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < DF_MAXR; ++r) {
-        if (!own[r]) continue;
-        const unsigned v = h[r * 256 + threadIdx.x];
-        if (v) atomicAdd(&ghist[(c * R + r) * 256 + threadIdx.x], v);
-    }
-}
-
-// one thread per (site, column): per rank the digit holding it, read from the counters of the rank that owns them; then the
-// counters are cleared for the next pass
-__global__ void __launch_bounds__(256) df_mpick_kernel(size_t ncol, int Q, int R, const int *kbits, int pass, unsigned *ghist,
-                                                       unsigned long long *pref, unsigned *rank)
-{
-    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncol) return;
-    const int shift = kbits[c % Q] - 8 * (pass + 1);
-    if (shift < 0) return;
-    const int hs = shift + 8;
-    unsigned long long p[DF_MAXR];
-    int dgs[DF_MAXR];
-    unsigned rest[DF_MAXR];
-#pragma unroll
-    for (int r = 0; r < DF_MAXR; ++r) p[r] = r < R ? pref[c * R + r] : 0ull;
-#pragma unroll
-    for (int r = 0; r < DF_MAXR; ++r) {
-        dgs[r] = -1;
-        rest[r] = 0u;
-        if (r >= R) continue;
-        int lead;
-        DF_LEAD(lead, p, r, R, hs);
-        const unsigned *g = ghist + (c * R + lead) * 256;
-        const unsigned k = rank[c * R + r];
-        unsigned cum = 0;
-        int dg = -1;
-        for (int b = 0; b < 256; ++b) {
-            const unsigned hb = g[b];
-            if (dg < 0 && k < cum + hb) dg = b;
-            if (dg < 0) cum += hb;
-        }
-        dgs[r] = dg;
-        rest[r] = k - cum;
-    }
-#pragma unroll
-    for (int r = 0; r < DF_MAXR; ++r) {
-        if (r >= R) continue;
-        unsigned *g = ghist + (c * R + r) * 256;
-        for (int b = 0; b < 256; ++b) g[b] = 0u;
-        if (dgs[r] < 0) continue; // a column without values
-        rank[c * R + r] = rest[r];
-        pref[c * R + r] = p[r] | ((unsigned long long)dgs[r] << shift);
-    }
-}
-
-// per rank the number of keys <= the selected one, and the least key above it
-__global__ void __launch_bounds__(DF_THREADS) df_mnext_kernel(SetArgs a, int R, const int *kbits, const unsigned long long *pref,
-                                                              unsigned *nle, unsigned long long *next)
-{
-    const PostWork w = a.work[blockIdx.x];
-    const int q = blockIdx.y;
-    const size_t c = (size_t)w.site * a.Q + q;
-    const double *col = a.val + (int64_t)q * a.nrows;
-    const bool k32 = kbits[q] == 32;
-    unsigned long long p[DF_MAXR], le[DF_MAXR], nx[DF_MAXR];
-#pragma unroll
-    for (int r = 0; r < DF_MAXR; ++r) {
-        p[r] = r < R ? pref[c * R + r] : 0ull;
-        le[r] = 0ull;
-        nx[r] = ~0ull;
-    }
-    for (int64_t i = w.r0 + threadIdx.x; i < w.r1; i += DF_THREADS) {
-        const double v = col[i];
-        if (v != v) continue;
-        const unsigned long long k = okey(v, k32);
-#pragma unroll
-        for (int r = 0; r < DF_MAXR; ++r) {
-            le[r] += k <= p[r] ? 1u : 0u;
-            nx[r] = (k > p[r] && k < nx[r]) ? k : nx[r];
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < DF_MAXR; ++r) {
-        if (r >= R) continue;   // (uniform)
-        const unsigned long long l = wave_sum(le[r]), n = wave_min(nx[r]);
-        if (__lane_id() == 0) {
-            if (l) atomicAdd(&nle[c * R + r], (unsigned)l);
-            atomicMin(&next[c * R + r], n);
-        }
-    }
-}
-
 // one lane per (row, column) of the gather
 __global__ void __launch_bounds__(256) df_gather_kernel(int64_t n, int Q, int64_t nrows, const double *val, const int64_t *pos,
                                                         double *out)
@@ -355,28 +194,6 @@ int to_device(bh_posterior *p, Dev &dv, bool host, const void *v, int64_t stride
     PCHK(p, hipMemcpyAsync(dv.p, v, n * eb, hipMemcpyHostToDevice, p->st));
     *out = dv.p;
     return BH_OK;
-}
-
-int get_set(bh_posterior *p, int set, ScalarSet **out)
-{
-    if (p->S < 1) return pfail(p, BH_EINVAL, "no rows loaded (bh_posterior_load)");
-    const int slot = set_slot(set);
-    if (slot < 0) return pfail(p, BH_EINVAL, "no such scalar set");
-    if (p->sets[slot].Q < 1) return pfail(p, BH_EINVAL, "the scalar set does not exist yet");
-    *out = &p->sets[slot];
-    return BH_OK;
-}
-
-uint64_t widen_key(uint64_t k32)
-{
-    const uint32_t k = (uint32_t)k32;
-    const uint32_t u = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    float f;
-    std::memcpy(&f, &u, 4);
-    const double d = (double)f;
-    uint64_t b;
-    std::memcpy(&b, &d, 8);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 } // namespace
@@ -559,66 +376,19 @@ int bh_posterior_scalar_quantiles(bh_posterior *p, int set, int R, const uint32_
     if (!p) return BH_EINVAL;
     ScalarSet *ss;
     if ((rc = get_set(p, set, &ss))) return rc;
-    if (R < 1 || R > DF_MAXR) return pfail(p, BH_EINVAL, "ranks per column: 1..BH_QUANTILES_MAXRANKS");
+    if (R < 1 || R > SELECT_MAXR) return pfail(p, BH_EINVAL, "ranks per column: 1..BH_QUANTILES_MAXRANKS");
     if (!rank || !lower || !upper) return pfail(p, BH_EINVAL, "null argument");
     const int Q = ss->Q;
-    const size_t ncol = (size_t)p->S * Q, nr = ncol * R;
+    const size_t ncol = (size_t)p->S * Q;
     if (ss->count.size() != ncol || ss->nf.size() != (size_t)Q)
         return pfail(p, BH_EINVAL, "bh_posterior_scalar_stats has not run on the set since it was formed");
     for (size_t c = 0; c < ncol; ++c)
         for (int r = 0; r < R; ++r)
             if ((int64_t)rank[c * R + r] >= std::max<int64_t>(ss->count[c], 1)) return pfail(p, BH_EINVAL, "a rank is not below its column's count");
     PCHK(p, hipSetDevice(p->device));
-    Dev dh, dpref, drank, dnle, dnext, dkb;
-    if ((rc = alloc(p, dh, nr * 256 * 4)) || (rc = alloc(p, dpref, nr * 8)) || (rc = alloc(p, drank, nr * 4)) ||
-        (rc = alloc(p, dnle, nr * 4)) || (rc = alloc(p, dnext, nr * 8)) || (rc = alloc(p, dkb, (size_t)Q * 4)))
-        return rc;
     std::vector<int> kb(Q);
-    int passes = 4;
-    for (int q = 0; q < Q; ++q) {
-        kb[q] = ss->nf[q] ? 64 : 32;
-        if (ss->nf[q]) passes = 8;
-    }
-    PCHK(p, hipMemsetAsync(dh.p, 0, nr * 256 * 4, p->st));
-    PCHK(p, hipMemsetAsync(dpref.p, 0, nr * 8, p->st));
-    PCHK(p, hipMemsetAsync(dnle.p, 0, nr * 4, p->st));
-    PCHK(p, hipMemsetAsync(dnext.p, 0xff, nr * 8, p->st));
-    PCHK(p, hipMemcpyAsync(drank.p, rank, nr * 4, hipMemcpyHostToDevice, p->st));
-    PCHK(p, hipMemcpyAsync(dkb.p, kb.data(), (size_t)Q * 4, hipMemcpyHostToDevice, p->st));
-    SetArgs a;
-    a.work = p->dwork.as<PostWork>();
-    a.val = ss->val.as<double>();
-    a.nrows = p->nrows;
-    a.Q = Q;
-    if (!p->work.empty()) {
-        const dim3 grid((unsigned)p->work.size(), (unsigned)Q);
-        const unsigned pb = (unsigned)((ncol + 255) / 256);
-        for (int pass = 0; pass < passes; ++pass) {
-            df_mradix_kernel<<<grid, DF_THREADS, 0, p->st>>>(a, R, dkb.as<int>(), pass, dpref.as<unsigned long long>(), dh.as<unsigned>());
-            df_mpick_kernel<<<pb, 256, 0, p->st>>>(ncol, Q, R, dkb.as<int>(), pass, dh.as<unsigned>(), dpref.as<unsigned long long>(),
-                                                   drank.as<unsigned>());
-        }
-        df_mnext_kernel<<<grid, DF_THREADS, 0, p->st>>>(a, R, dkb.as<int>(), dpref.as<unsigned long long>(), dnle.as<unsigned>(),
-                                                        dnext.as<unsigned long long>());
-        PCHK(p, hipGetLastError());
-    }
-    std::vector<uint64_t> pref(nr), next(nr);
-    std::vector<unsigned> nle(nr);
-    PCHK(p, hipMemcpyAsync(pref.data(), dpref.p, nr * 8, hipMemcpyDeviceToHost, p->st));
-    PCHK(p, hipMemcpyAsync(next.data(), dnext.p, nr * 8, hipMemcpyDeviceToHost, p->st));
-    PCHK(p, hipMemcpyAsync(nle.data(), dnle.p, nr * 4, hipMemcpyDeviceToHost, p->st));
-    PCHK(p, hipStreamSynchronize(p->st));
-    for (size_t c = 0; c < ncol; ++c)
-        for (int r = 0; r < R; ++r) {
-            const size_t i = c * R + r;
-            if (ss->count[c] == 0) { lower[i] = upper[i] = 0; continue; }
-            // rank + 1 is the selected key again while more keys than rank + 1 are <= it
-            const uint64_t up = (nle[i] >= rank[i] + 2u || next[i] == ~0ull) ? pref[i] : next[i];
-            const bool k32 = kb[c % Q] == 32;
-            lower[i] = k32 ? widen_key(pref[i]) : pref[i];
-            upper[i] = k32 ? widen_key(up) : up;
-        }
-    return BH_OK;
+    for (int q = 0; q < Q; ++q) kb[q] = ss->nf[q] ? 64 : 32;
+    return select_ranks(p, ncol, R, rank, ss->count.data(), kb, true, SetSelect{p, set_args(p, ss)}, lower, upper, 1);
 }
 
 int bh_posterior_scalar_gather(bh_posterior *p, int set, int64_t n, const int64_t *pos, double *out)

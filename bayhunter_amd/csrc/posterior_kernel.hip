@@ -9,13 +9,13 @@
 // integer atomics (min / max of ordered keys, counts, 64-bit limb sums), so the results are the same bits in every run.
 //   stats   : min, max and the lowest set bit of every column (for the fixed-point scale of the sums)
 //   moments : the 32-bit limbs of sum(Y) and sum(Y^2), Y = v * 2^-scale - X0 an integer (exact where scale allows)
-//   radix   : the median by radix select on the ordered key, 8 bits per pass (4 passes for float32 keys, 8 for float64);
-//             per-lane 256-bin histograms in LDS as pairs of 16-bit counters (CHUNK < 2^16), then one thread per column
-//             picks the digit.  A last pass finds the next key above the selected one (the upper middle of an even count).
+//   radix   : the median and the quantiles by the radix select of posterior_select.h on the ordered key, 8 bits per pass (4
+//             passes for float32 keys, 8 for float64); per-lane 256-bin histograms in LDS as pairs of 16-bit counters (CHUNK <
+//             2^16).  A last pass finds the next key above the selected one (the upper middle of an even count).
 //   hist    : counts over the caller's vs edges (binary search, 'right', last edge to the last bin) and depth bins;
 //             in LDS when every site has at most 256 vs bins, else straight to global atomics.
 // -ffp-contract=off (Makefile) keeps (z_j + z_{j+1}) / 2 and the cumulative sums rounded as numpy rounds them.
-#include "posterior_common.h"
+#include "posterior_select.h"
 #include "../../include/bh_engine_posterior_quantiles.h"
 
 #include <algorithm>
@@ -27,7 +27,6 @@
 
 #define POST_HIST_LDS_BINS 256
 #define POST_IFACE_LDS_BINS 4096
-#define POST_MAXR BH_QUANTILES_MAXRANKS
 
 using namespace bhpost;
 
@@ -198,9 +197,15 @@ __global__ void __launch_bounds__(64) post_moments_kernel(ColArgs a, const int32
     atomicAdd(&o[5], q3);
 }
 
-// one radix-select pass: per column the histogram of the 8-bit digit at `shift` over the keys that match the prefix above it
+// ---- the order statistics of a column (posterior_select.h): the column layout's radix and next pass -------------------------
+
+// the radix pass of ONE rank, written out, and the only radix pass ColSelect launches for NR = 1: col_radix_kernel<T, 1> is never
+// instantiated.  It has the same registers, LDS and occupancy and 12 instructions fewer, but put a posterior_models call of 64
+// sites x 200 000 rows 0.7 % above the spread of the parent's repeats (profiles/posterior_select_refactor.txt, sections 2 and
+// 3).  A copy kept on a difference this small: to re-test, launch col_radix_kernel<T, 1> from ColSelect::radix, run
+// tools/gpu_posterior_perf.py alternately on both builds, and delete this kernel if the two lie within each other's spread.
 template <typename T>
-__global__ void __launch_bounds__(64) post_radix_kernel(ColArgs a, int k32, int shift, const unsigned long long *pref,
+__global__ void __launch_bounds__(64) col_radix1_kernel(ColArgs a, int k32, int shift, const unsigned long long *pref,
                                                         unsigned *ghist)
 {
     __shared__ unsigned h[128 * 64]; // [digit / 2][lane]: two 16-bit counters
@@ -230,67 +235,13 @@ __global__ void __launch_bounds__(64) post_radix_kernel(ColArgs a, int k32, int 
     }
 }
 
-// one thread per column: the digit holding rank rank[c]; the histogram is cleared for the next pass
-__global__ void __launch_bounds__(256) post_pick_kernel(size_t ncol, int shift, unsigned *ghist, unsigned long long *pref,
-                                                        unsigned *rank)
-{
-    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncol) return;
-    unsigned *g = ghist + c * 256;
-    unsigned k = rank[c], cum = 0;
-    int dg = -1;
-    for (int b = 0; b < 256; ++b) {
-        const unsigned hb = g[b];
-        if (dg < 0 && k < cum + hb) dg = b;
-        if (dg < 0) cum += hb;
-        g[b] = 0u;
-    }
-    if (dg < 0) return; // a column without rows
-    rank[c] = k - cum;
-    pref[c] |= (unsigned long long)dg << shift;
-}
-
-// the number of keys <= the selected one, and the least key above it
-template <typename T>
-__global__ void __launch_bounds__(64) post_next_kernel(ColArgs a, int k32, const unsigned long long *pref, unsigned *nle,
-                                                       unsigned long long *next)
-{
-    const PostWork w = a.work[blockIdx.x];
-    const int j = blockIdx.y * 64 + threadIdx.x;
-    if (j >= a.D) return;
-    const size_t c = (size_t)w.site * a.D + j;
-    const double x = a.dep[j];
-    const unsigned long long p = pref[c];
-    const T *pvs = (const T *)a.pvs;
-    unsigned le = 0;
-    unsigned long long nx = ~0ull;
-    for (int64_t r = w.r0; r < w.r1; ++r) {
-        const unsigned long long k = okey(sample(a.pn[r], pvs + r * a.ML, a.pd + r * a.ML, x), k32 != 0);
-        le += k <= p ? 1u : 0u;
-        nx = (k > p && k < nx) ? k : nx;
-    }
-    atomicAdd(&nle[c], le);
-    atomicMin(&next[c], nx);
-}
-
-// ---- several order statistics per column (include/bh_engine_posterior_quantiles.h) ------------------------------------------
-// The median's three kernels with R ranks per column: prefixes, ranks and counters at [column * R + rank].
-
-// the first rank of 0..r whose prefix above bit hs equals r's: it owns the counters r reads
-#define POST_LEAD(lead, p, r, R, hs)                                                       \
-    do {                                                                                   \
-        lead = r;                                                                          \
-        _Pragma("unroll") for (int r2 = POST_MAXR - 1; r2 >= 0; --r2)                      \
-            if (r2 < r && r2 < R && (hs >= 64 || ((p[r2] ^ p[r]) >> hs) == 0ull)) lead = r2; \
-    } while (0)
-
-// one pass of the multi-rank radix select: every (row, depth) is sampled once; its key is counted for the one owner whose
-// prefix it matches (the owners' prefixes differ, so there is at most one).  Rank 0 is always an owner, and while the ranks
-// have not parted it is the only one: its counters are the lane's private 16-bit pairs in LDS, as in post_radix_kernel.  A
-// rank that has left rank 0's prefix counts straight into its global counters.
-template <typename T>
-__global__ void __launch_bounds__(64) post_mradix_kernel(ColArgs a, int R, int k32, int shift, const unsigned long long *pref,
-                                                         unsigned *ghist)
+// one pass of the radix select: every (row, depth) is sampled once; its key is counted by its 8-bit digit at `shift` for the one
+// owner whose prefix above it it matches.  Rank 0 is always an owner, and while the ranks have not parted it is the only one (a
+// call of one rank takes col_radix1_kernel): its counters are the lane's private 16-bit pairs in LDS.  A rank that has left rank 0's
+// prefix counts straight into its global counters.
+template <typename T, int NR>
+__global__ void __launch_bounds__(64) col_radix_kernel(ColArgs a, int Rarg, int k32, int shift, const unsigned long long *pref,
+                                                       unsigned *ghist)
 {
     __shared__ unsigned h[128 * 64]; // [digit / 2][lane]: two 16-bit counters
     const PostWork w = a.work[blockIdx.x];
@@ -299,29 +250,22 @@ __global__ void __launch_bounds__(64) post_mradix_kernel(ColArgs a, int R, int k
     const bool act = j < a.D;
     for (int b = 0; b < 128; ++b) h[b * 64 + lane] = 0u; // a lane touches its own column only: no barrier
     if (!act) return;
+    const int R = select_ranks_of<NR>(Rarg);
     const size_t c = (size_t)w.site * a.D + j;
     const double x = a.dep[j];
     const int hs = shift + 8;
-    unsigned long long p[POST_MAXR];
-    unsigned own = 0u;
-#pragma unroll
-    for (int r = 0; r < POST_MAXR; ++r) p[r] = r < R ? pref[c * R + r] : 0ull;
-#pragma unroll
-    for (int r = 0; r < POST_MAXR; ++r) {
-        int lead;
-        POST_LEAD(lead, p, r, R, hs);
-        own |= (r < R && lead == r) ? 1u << r : 0u;
-    }
+    unsigned long long p[NR];
+    load_prefixes<NR>(p, pref + c * R, R);
+    const unsigned own = owner_mask<NR>(p, R, hs);
     const T *pvs = (const T *)a.pvs;
     unsigned *g = ghist + c * R * 256;
     for (int64_t r = w.r0; r < w.r1; ++r) {
         const double v = sample(a.pn[r], pvs + r * a.ML, a.pd + r * a.ML, x);
         const unsigned long long k = okey(v, k32 != 0);
-        const unsigned dg = (unsigned)(k >> shift) & 255u;
+        const unsigned dg = key_digit(k, shift);
         int o = -1;
 #pragma unroll
-        for (int q = 0; q < POST_MAXR; ++q)
-            o = (((own >> q) & 1u) && (hs >= 64 || ((k ^ p[q]) >> hs) == 0ull)) ? q : o;
+        for (int q = 0; q < NR; ++q) o = (((own >> q) & 1u) && key_matches(k, p[q], hs)) ? q : o;
         if (o == 0) h[(dg >> 1) * 64 + lane] += 1u << ((dg & 1u) * 16u);
         else if (o > 0) atomicAdd(&g[o * 256 + dg], 1u);
     }
@@ -332,79 +276,37 @@ __global__ void __launch_bounds__(64) post_mradix_kernel(ColArgs a, int R, int k
     }
 }
 
-// one thread per column: per rank the digit holding it, read from the counters of the rank that owns them; then the counters
-// are cleared for the next pass
-__global__ void __launch_bounds__(256) post_mpick_kernel(size_t ncol, int R, int shift, unsigned *ghist, unsigned long long *pref,
-                                                         unsigned *rank)
-{
-    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncol) return;
-    const int hs = shift + 8;
-    unsigned long long p[POST_MAXR];
-    int dgs[POST_MAXR];
-    unsigned rest[POST_MAXR];
-#pragma unroll
-    for (int r = 0; r < POST_MAXR; ++r) p[r] = r < R ? pref[c * R + r] : 0ull;
-#pragma unroll
-    for (int r = 0; r < POST_MAXR; ++r) {
-        dgs[r] = -1;
-        rest[r] = 0u;
-        if (r >= R) continue;
-        int lead;
-        POST_LEAD(lead, p, r, R, hs);
-        const unsigned *g = ghist + (c * R + lead) * 256;
-        const unsigned k = rank[c * R + r];
-        unsigned cum = 0;
-        int dg = -1;
-        for (int b = 0; b < 256; ++b) {
-            const unsigned hb = g[b];
-            if (dg < 0 && k < cum + hb) dg = b;
-            if (dg < 0) cum += hb;
-        }
-        dgs[r] = dg;
-        rest[r] = k - cum;
-    }
-#pragma unroll
-    for (int r = 0; r < POST_MAXR; ++r) {
-        if (r >= R) continue;
-        unsigned *g = ghist + (c * R + r) * 256;
-        for (int b = 0; b < 256; ++b) g[b] = 0u;
-        if (dgs[r] < 0) continue; // a column without rows
-        rank[c * R + r] = rest[r];
-        pref[c * R + r] = p[r] | ((unsigned long long)dgs[r] << shift);
-    }
-}
-
 // per rank the number of keys <= the selected one, and the least key above it
-template <typename T>
-__global__ void __launch_bounds__(64) post_mnext_kernel(ColArgs a, int R, int k32, const unsigned long long *pref, unsigned *nle,
-                                                        unsigned long long *next)
+template <typename T, int NR>
+__global__ void __launch_bounds__(64) col_next_kernel(ColArgs a, int Rarg, int k32, const unsigned long long *pref, unsigned *nle,
+                                                      unsigned long long *next)
 {
     const PostWork w = a.work[blockIdx.x];
     const int j = blockIdx.y * 64 + threadIdx.x;
     if (j >= a.D) return;
+    const int R = select_ranks_of<NR>(Rarg);
     const size_t c = (size_t)w.site * a.D + j;
     const double x = a.dep[j];
     const T *pvs = (const T *)a.pvs;
-    unsigned long long p[POST_MAXR], nx[POST_MAXR];
-    unsigned le[POST_MAXR];
+    unsigned long long p[NR], nx[NR];
+    unsigned le[NR];
+    load_prefixes<NR>(p, pref + c * R, R);
 #pragma unroll
-    for (int r = 0; r < POST_MAXR; ++r) {
-        p[r] = r < R ? pref[c * R + r] : 0ull;
+    for (int r = 0; r < NR; ++r) {
         le[r] = 0u;
         nx[r] = ~0ull;
     }
     for (int64_t r = w.r0; r < w.r1; ++r) {
         const unsigned long long k = okey(sample(a.pn[r], pvs + r * a.ML, a.pd + r * a.ML, x), k32 != 0);
 #pragma unroll
-        for (int q = 0; q < POST_MAXR; ++q) {
+        for (int q = 0; q < NR; ++q) {
             if (q >= R) break; // (uniform)
             le[q] += k <= p[q] ? 1u : 0u;
             nx[q] = (k > p[q] && k < nx[q]) ? k : nx[q];
         }
     }
 #pragma unroll
-    for (int r = 0; r < POST_MAXR; ++r) {
+    for (int r = 0; r < NR; ++r) {
         if (r >= R) continue;
         atomicAdd(&nle[c * R + r], le[r]);
         atomicMin(&next[c * R + r], nx[r]);
@@ -541,6 +443,38 @@ int upload_grid(bh_posterior *p, Dev &d, const double *dep, int D)
     if ((rc = alloc(p, d, (size_t)D * sizeof(double)))) return rc;
     PCHK(p, hipMemcpyAsync(d.p, dep, (size_t)D * sizeof(double), hipMemcpyHostToDevice, p->st));
     return BH_OK;
+}
+
+// the launches of select_ranks over the depth columns: one key width kb for all of them
+struct ColSelect {
+    bh_posterior *p;
+    ColArgs a;
+    int kb;
+    dim3 grid() const { return dim3((unsigned)p->work.size(), (unsigned)((a.D + 63) / 64)); }
+    template <int NR>
+    void radix(int R, int pass, const SelectBufs &b) const
+    {
+        const int shift = kb - 8 * (pass + 1);
+        if constexpr (NR == 1) {
+            if (p->elem == 4) col_radix1_kernel<float><<<grid(), 64, 0, p->st>>>(a, kb == 32, shift, b.pref, b.ghist);
+            else col_radix1_kernel<double><<<grid(), 64, 0, p->st>>>(a, kb == 32, shift, b.pref, b.ghist);
+        } else if (p->elem == 4) col_radix_kernel<float, NR><<<grid(), 64, 0, p->st>>>(a, R, kb == 32, shift, b.pref, b.ghist);
+        else col_radix_kernel<double, NR><<<grid(), 64, 0, p->st>>>(a, R, kb == 32, shift, b.pref, b.ghist);
+    }
+    template <int NR>
+    void next(int R, const SelectBufs &b) const
+    {
+        if (p->elem == 4) col_next_kernel<float, NR><<<grid(), 64, 0, p->st>>>(a, R, kb == 32, b.pref, b.nle, b.next);
+        else col_next_kernel<double, NR><<<grid(), 64, 0, p->st>>>(a, R, kb == 32, b.pref, b.nle, b.next);
+    }
+};
+
+// every depth column's count: the rows of its site
+std::vector<int64_t> col_counts(const bh_posterior *p, int D)
+{
+    std::vector<int64_t> n((size_t)p->S * D);
+    for (size_t c = 0; c < n.size(); ++c) n[c] = p->off[c / D + 1] - p->off[c / D];
+    return n;
 }
 
 } // namespace
@@ -698,30 +632,10 @@ int bh_posterior_columns(bh_posterior *p, int D, const double *dep, uint64_t *km
     PCHK(p, hipMemcpyAsync(kmax, dmax.p, ncol * 8, hipMemcpyDeviceToHost, p->st));
     PCHK(p, hipMemcpyAsync(low.data(), dlow.p, ncol * 4, hipMemcpyDeviceToHost, p->st));
     PCHK(p, hipStreamSynchronize(p->st));
-    // the fixed-point scale of every column: the lowest set bit, raised until |X| < 2^62
-    auto key2d = [](uint64_t k) {
-        const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-        double v;
-        std::memcpy(&v, &u, 8);
-        return v;
-    };
-    for (size_t c = 0; c < ncol; ++c) {
-        const int s = (int)(c / D);
-        if (p->off[s + 1] == p->off[s]) { scale[c] = 0; x0[c] = 0; exact[c] = 1; continue; }
-        const double vmn = key2d(kmin[c]), vmx = key2d(kmax[c]);
-        const double amax = std::max(std::fabs(vmn), std::fabs(vmx));
-        if (!std::isfinite(amax)) return pfail(p, BH_EINVAL, "a velocity is not finite");
-        int L = 0;
-        if (amax > 0.0) {
-            int ea;
-            (void)std::frexp(amax, &ea); // amax < 2^ea
-            L = std::max(low[c], ea - 62);
-            exact[c] = low[c] >= ea - 62;
-        } else {
-            exact[c] = 1;
-        }
-        scale[c] = L;
-        x0[c] = (int64_t)std::nearbyint(std::ldexp(vmn, -L));
+    const std::vector<int64_t> count = col_counts(p, D);
+    for (size_t c = 0; c < ncol; ++c) {   // the fixed-point scale of every column
+        if (count[c] == 0) { scale[c] = 0; x0[c] = 0; exact[c] = 1; continue; }
+        if ((rc = scale_rule(p, kmin[c], kmax[c], low[c], "a velocity is not finite", &scale[c], &x0[c], &exact[c]))) return rc;
     }
     if ((rc = alloc(p, dsc, ncol * 4)) || (rc = alloc(p, dx0, ncol * 8)) || (rc = alloc(p, dsum, ncol * 48))) return rc;
     PCHK(p, hipMemcpyAsync(dsc.p, scale, ncol * 4, hipMemcpyHostToDevice, p->st));
@@ -734,44 +648,11 @@ int bh_posterior_columns(bh_posterior *p, int D, const double *dep, uint64_t *km
     }
     PCHK(p, hipMemcpyAsync(sums, dsum.p, ncol * 48, hipMemcpyDeviceToHost, p->st));
     *keys32 = p->keys32 ? 1 : 0;
-    if (median) {
-        Dev dh, dpref, drank, dnle, dnext;
-        if ((rc = alloc(p, dh, ncol * 256 * 4)) || (rc = alloc(p, dpref, ncol * 8)) || (rc = alloc(p, drank, ncol * 4)) ||
-            (rc = alloc(p, dnle, ncol * 4)) || (rc = alloc(p, dnext, ncol * 8)))
-            return rc;
-        std::vector<unsigned> rk(ncol);
-        for (size_t c = 0; c < ncol; ++c) {
-            const int64_t n = p->off[c / D + 1] - p->off[c / D];
-            rk[c] = n ? (unsigned)((n - 1) / 2) : 0u;
-        }
-        PCHK(p, hipMemsetAsync(dh.p, 0, ncol * 256 * 4, p->st));
-        PCHK(p, hipMemsetAsync(dpref.p, 0, ncol * 8, p->st));
-        PCHK(p, hipMemsetAsync(dnle.p, 0, ncol * 4, p->st));
-        PCHK(p, hipMemsetAsync(dnext.p, 0xff, ncol * 8, p->st));
-        PCHK(p, hipMemcpyAsync(drank.p, rk.data(), ncol * 4, hipMemcpyHostToDevice, p->st));
+    if (median) {   // the keys of ranks (n-1)/2 and (n-1)/2 + 1, in the width keys32 tells
+        std::vector<uint32_t> rk(ncol);
+        for (size_t c = 0; c < ncol; ++c) rk[c] = count[c] ? (uint32_t)((count[c] - 1) / 2) : 0u;
         const int kb = p->keys32 ? 32 : 64;
-        const unsigned pb = (unsigned)((ncol + 255) / 256);
-        if (!p->work.empty()) {
-            for (int shift = kb - 8; shift >= 0; shift -= 8) {
-                if (f) post_radix_kernel<float><<<grid, 64, 0, p->st>>>(a, p->keys32, shift, dpref.as<unsigned long long>(), dh.as<unsigned>());
-                else post_radix_kernel<double><<<grid, 64, 0, p->st>>>(a, p->keys32, shift, dpref.as<unsigned long long>(), dh.as<unsigned>());
-                post_pick_kernel<<<pb, 256, 0, p->st>>>(ncol, shift, dh.as<unsigned>(), dpref.as<unsigned long long>(), drank.as<unsigned>());
-            }
-            if (f) post_next_kernel<float><<<grid, 64, 0, p->st>>>(a, p->keys32, dpref.as<unsigned long long>(), dnle.as<unsigned>(), dnext.as<unsigned long long>());
-            else post_next_kernel<double><<<grid, 64, 0, p->st>>>(a, p->keys32, dpref.as<unsigned long long>(), dnle.as<unsigned>(), dnext.as<unsigned long long>());
-            PCHK(p, hipGetLastError());
-        }
-        std::vector<uint64_t> pref(ncol), next(ncol);
-        std::vector<unsigned> nle(ncol);
-        PCHK(p, hipMemcpyAsync(pref.data(), dpref.p, ncol * 8, hipMemcpyDeviceToHost, p->st));
-        PCHK(p, hipMemcpyAsync(next.data(), dnext.p, ncol * 8, hipMemcpyDeviceToHost, p->st));
-        PCHK(p, hipMemcpyAsync(nle.data(), dnle.p, ncol * 4, hipMemcpyDeviceToHost, p->st));
-        PCHK(p, hipStreamSynchronize(p->st));
-        for (size_t c = 0; c < ncol; ++c) {
-            median[2 * c] = pref[c];
-            // rank (n-1)/2 + 1 is the selected key again while more keys than (n-1)/2 + 1 are <= it
-            median[2 * c + 1] = (nle[c] >= rk[c] + 2u || next[c] == ~0ull) ? pref[c] : next[c];
-        }
+        if ((rc = select_ranks(p, ncol, 1, rk.data(), count.data(), {kb}, false, ColSelect{p, a, kb}, median, median + 1, 2))) return rc;
     }
     PCHK(p, hipStreamSynchronize(p->st));
     return BH_OK;
@@ -783,7 +664,7 @@ int bh_posterior_column_quantiles(bh_posterior *p, int D, const double *dep, int
     int rc;
     if (!p) return BH_EINVAL;
     if (p->S < 1) return pfail(p, BH_EINVAL, "no rows loaded (bh_posterior_load)");
-    if (R < 1 || R > POST_MAXR) return pfail(p, BH_EINVAL, "ranks per column: 1..BH_QUANTILES_MAXRANKS");
+    if (R < 1 || R > SELECT_MAXR) return pfail(p, BH_EINVAL, "ranks per column: 1..BH_QUANTILES_MAXRANKS");
     if (!dep || !rank || !lower || !upper) return pfail(p, BH_EINVAL, "null argument");
     if (D < 1 || D > (1 << 20)) return pfail(p, BH_EINVAL, "depth grid: 1..2^20 points");
     if (!grid_ok(dep, D)) return pfail(p, BH_EINVAL, "depth grid must be finite and strictly ascending");
@@ -795,49 +676,17 @@ int bh_posterior_column_quantiles(bh_posterior *p, int D, const double *dep, int
             if ((int64_t)rank[(size_t)s * R + r] >= std::max<int64_t>(n, 1)) return pfail(p, BH_EINVAL, "a rank is not below its site's rows");
     }
     PCHK(p, hipSetDevice(p->device));
-    const size_t ncol = (size_t)S * D, nr = ncol * R;
-    Dev dd, dh, dpref, drank, dnle, dnext;
-    if ((rc = alloc(p, dd, (size_t)D * sizeof(double))) || (rc = alloc(p, dh, nr * 256 * 4)) || (rc = alloc(p, dpref, nr * 8)) ||
-        (rc = alloc(p, drank, nr * 4)) || (rc = alloc(p, dnle, nr * 4)) || (rc = alloc(p, dnext, nr * 8)))
-        return rc;
-    std::vector<unsigned> rk(nr);
+    const size_t ncol = (size_t)S * D;
+    Dev dd;
+    if ((rc = alloc(p, dd, (size_t)D * sizeof(double)))) return rc;
+    std::vector<uint32_t> rk(ncol * R);
     for (size_t c = 0; c < ncol; ++c)
         for (int r = 0; r < R; ++r) rk[c * R + r] = rank[(c / D) * R + r];
     PCHK(p, hipMemcpyAsync(dd.p, dep, (size_t)D * sizeof(double), hipMemcpyHostToDevice, p->st));
-    PCHK(p, hipMemsetAsync(dh.p, 0, nr * 256 * 4, p->st));
-    PCHK(p, hipMemsetAsync(dpref.p, 0, nr * 8, p->st));
-    PCHK(p, hipMemsetAsync(dnle.p, 0, nr * 4, p->st));
-    PCHK(p, hipMemsetAsync(dnext.p, 0xff, nr * 8, p->st));
-    PCHK(p, hipMemcpyAsync(drank.p, rk.data(), nr * 4, hipMemcpyHostToDevice, p->st));
-    const ColArgs a = col_args(p, dd.as<double>(), D);
-    const dim3 grid((unsigned)p->work.size(), (unsigned)((D + 63) / 64));
-    const bool f = p->elem == 4;
-    const int k32 = p->keys32 ? 1 : 0;
-    if (!p->work.empty()) {
-        const unsigned pb = (unsigned)((ncol + 255) / 256);
-        for (int shift = (k32 ? 32 : 64) - 8; shift >= 0; shift -= 8) {
-            if (f) post_mradix_kernel<float><<<grid, 64, 0, p->st>>>(a, R, k32, shift, dpref.as<unsigned long long>(), dh.as<unsigned>());
-            else post_mradix_kernel<double><<<grid, 64, 0, p->st>>>(a, R, k32, shift, dpref.as<unsigned long long>(), dh.as<unsigned>());
-            post_mpick_kernel<<<pb, 256, 0, p->st>>>(ncol, R, shift, dh.as<unsigned>(), dpref.as<unsigned long long>(), drank.as<unsigned>());
-        }
-        if (f) post_mnext_kernel<float><<<grid, 64, 0, p->st>>>(a, R, k32, dpref.as<unsigned long long>(), dnle.as<unsigned>(), dnext.as<unsigned long long>());
-        else post_mnext_kernel<double><<<grid, 64, 0, p->st>>>(a, R, k32, dpref.as<unsigned long long>(), dnle.as<unsigned>(), dnext.as<unsigned long long>());
-        PCHK(p, hipGetLastError());
-    }
-    std::vector<uint64_t> pref(nr), next(nr);
-    std::vector<unsigned> nle(nr);
-    PCHK(p, hipMemcpyAsync(pref.data(), dpref.p, nr * 8, hipMemcpyDeviceToHost, p->st));
-    PCHK(p, hipMemcpyAsync(next.data(), dnext.p, nr * 8, hipMemcpyDeviceToHost, p->st));
-    PCHK(p, hipMemcpyAsync(nle.data(), dnle.p, nr * 4, hipMemcpyDeviceToHost, p->st));
-    PCHK(p, hipStreamSynchronize(p->st));
-    for (size_t i = 0; i < nr; ++i) {
-        const size_t s = i / ((size_t)D * R);
-        if (p->off[s + 1] == p->off[s]) { lower[i] = upper[i] = 0; continue; }
-        lower[i] = pref[i];
-        // rank + 1 is the selected key again while more keys than rank + 1 are <= it
-        upper[i] = ((uint64_t)nle[i] >= (uint64_t)rk[i] + 2u || next[i] == ~0ull) ? pref[i] : next[i];
-    }
-    if (keys32) *keys32 = k32;
+    const int kb = p->keys32 ? 32 : 64;
+    const ColSelect launch{p, col_args(p, dd.as<double>(), D), kb};
+    if ((rc = select_ranks(p, ncol, R, rk.data(), col_counts(p, D).data(), {kb}, false, launch, lower, upper, 1))) return rc;
+    if (keys32) *keys32 = p->keys32 ? 1 : 0;
     return BH_OK;
 }
 

@@ -8,13 +8,13 @@
 // ordered keys, 64-bit limb sums), so a site's results are the same bits in every run, alone or among other sites.
 //   stats   : count, NaN count, min, max, lowest set bit, float32-exactness of every (site, column)
 //   moments : the 32-bit limbs of sum(Y) and sum(Y^2), Y = v * 2^-scale - X0 (posterior_kernel.hip's encoding)
-//   radix   : the median by radix select on the ordered key, 8 bits per pass, 256 LDS counters per workgroup; a column of
+//   radix   : the median by the radix select of posterior_select.h on the ordered key, 8 bits per pass, 256 LDS counters; a column of
 //             float32-exact values has 32-bit keys (4 passes).  A last pass finds the next key above the selected one.
 //   hist    : numpy.histogram over per-site edges; edges and counters in LDS where a site has at most SC_LDS_BINS bins
 //   hist2d  : numpy.histogram2d of one column against another; in LDS where a site has at most SC_LDS_CELLS cells
 // LDS: 24 KiB (hist), 32 KiB (hist2d), 1 KiB (radix) per 256-lane workgroup -- several workgroups per CU beside each other.
 // -ffp-contract=off (Makefile): no product of the crustal mean is contracted into its sum.
-#include "posterior_common.h"
+#include "posterior_select.h"
 #include "../../include/bh_engine_posterior_datafit.h"
 
 #include <algorithm>
@@ -29,29 +29,6 @@
 using namespace bhpost;
 
 namespace {
-
-__device__ __forceinline__ double qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v)
-{
-    for (int o = 32; o; o >>= 1) { const unsigned long long u = __shfl_xor(v, o); v = u < v ? u : v; }
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
-{
-    for (int o = 32; o; o >>= 1) { const unsigned long long u = __shfl_xor(v, o); v = u > v ? u : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_min_i(int v)
-{
-    for (int o = 32; o; o >>= 1) { const int u = __shfl_xor(v, o); v = u < v ? u : v; }
-    return v;
-}
 
 // (double)vs_j * h_j of a row, h_j = (double)zd_j - (double)zd_{j-1}
 template <typename T>
@@ -126,13 +103,6 @@ __global__ void __launch_bounds__(256) sc_attach_kernel(int64_t nrows, const int
     if (with_nl) val[(int64_t)Q * nrows + r] = (double)(pn[r] - 1);
 }
 
-struct SetArgs {
-    const PostWork *work;
-    const double *val;
-    int64_t nrows;
-    int Q;
-};
-
 __global__ void __launch_bounds__(SC_THREADS) sc_stats_kernel(SetArgs a, unsigned long long *count, unsigned long long *nnan,
                                                               unsigned long long *kmin, unsigned long long *kmax, int *low,
                                                               int *not_f32)
@@ -202,82 +172,6 @@ __global__ void __launch_bounds__(SC_THREADS) sc_moments_kernel(SetArgs a, const
 #pragma unroll
     for (int i = 0; i < 6; ++i)
         if (s[i]) atomicAdd(&o[i], s[i]);
-}
-
-// pass `pass` of the radix select: per (site, column) the histogram of the 8-bit digit at kbits[q] - 8 * (pass + 1) over the
-// keys that match the prefix above it (columns with fewer passes sit the later ones out)
-__global__ void __launch_bounds__(SC_THREADS) sc_radix_kernel(SetArgs a, const int *kbits, int pass,
-                                                              const unsigned long long *pref, unsigned *ghist)
-{
-    __shared__ unsigned h[256];
-    const PostWork w = a.work[blockIdx.x];
-    const int q = blockIdx.y;
-    const int kb = kbits[q];
-    const int shift = kb - 8 * (pass + 1);
-    if (shift < 0) return; // (uniform over the workgroup: before the barriers)
-    h[threadIdx.x] = 0u;   // SC_THREADS == 256
-    __syncthreads();
-    const size_t c = (size_t)w.site * a.Q + q;
-    const double *col = a.val + (int64_t)q * a.nrows;
-    const unsigned long long p = pref[c];
-    const int hs = shift + 8;
-    for (int64_t r = w.r0 + threadIdx.x; r < w.r1; r += SC_THREADS) {
-        const double v = col[r];
-        if (v != v) continue;
-        const unsigned long long k = okey(v, kb == 32);
-        if (hs < 64 && ((k ^ p) >> hs) != 0ull) continue;
-        atomicAdd(&h[(unsigned)(k >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    const unsigned v = h[threadIdx.x];
-    if (v) atomicAdd(&ghist[c * 256 + threadIdx.x], v);
-}
-
-// one thread per (site, column): the digit holding rank rank[c]; the histogram is cleared for the next pass
-__global__ void __launch_bounds__(256) sc_pick_kernel(size_t ncol, int Q, const int *kbits, int pass, unsigned *ghist,
-                                                      unsigned long long *pref, unsigned *rank)
-{
-    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncol) return;
-    const int shift = kbits[c % Q] - 8 * (pass + 1);
-    if (shift < 0) return;
-    unsigned *g = ghist + c * 256;
-    unsigned k = rank[c], cum = 0;
-    int dg = -1;
-    for (int b = 0; b < 256; ++b) {
-        const unsigned hb = g[b];
-        if (dg < 0 && k < cum + hb) dg = b;
-        if (dg < 0) cum += hb;
-        g[b] = 0u;
-    }
-    if (dg < 0) return; // a column without values
-    rank[c] = k - cum;
-    pref[c] |= (unsigned long long)dg << shift;
-}
-
-// the number of keys <= the selected one, and the least key above it
-__global__ void __launch_bounds__(SC_THREADS) sc_next_kernel(SetArgs a, const int *kbits, const unsigned long long *pref,
-                                                             unsigned *nle, unsigned long long *next)
-{
-    const PostWork w = a.work[blockIdx.x];
-    const int q = blockIdx.y;
-    const size_t c = (size_t)w.site * a.Q + q;
-    const double *col = a.val + (int64_t)q * a.nrows;
-    const unsigned long long p = pref[c];
-    const bool k32 = kbits[q] == 32;
-    unsigned long long le = 0, nx = ~0ull;
-    for (int64_t r = w.r0 + threadIdx.x; r < w.r1; r += SC_THREADS) {
-        const double v = col[r];
-        if (v != v) continue;
-        const unsigned long long k = okey(v, k32);
-        le += k <= p ? 1u : 0u;
-        nx = (k > p && k < nx) ? k : nx;
-    }
-    le = wave_sum(le);
-    nx = wave_min(nx);
-    if (__lane_id() != 0) return;
-    if (le) atomicAdd(&nle[c], (unsigned)le);
-    atomicMin(&next[c], nx);
 }
 
 struct EdgeArgs {
@@ -387,30 +281,6 @@ __global__ void __launch_bounds__(256) sc_argmax_kernel(const int64_t *cnt_off, 
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 
-int get_set(bh_posterior *p, int set, ScalarSet **out)
-{
-    if (p->S < 1) return pfail(p, BH_EINVAL, "no rows loaded (bh_posterior_load)");
-    const int slot = set_slot(set);
-    if (slot < 0) return pfail(p, BH_EINVAL, "no such scalar set");
-    if (p->sets[slot].Q < 1)
-        return pfail(p, BH_EINVAL, slot == 0   ? "the MOHO set does not exist yet (bh_posterior_moho)"
-                                   : slot == 1 ? "the USER set does not exist yet (bh_posterior_attach)"
-                                   : slot == 2 ? "the DATA set does not exist yet (bh_posterior_data_fill over all rows)"
-                                               : "the FEATURES set does not exist yet (bh_posterior_features)");
-    *out = &p->sets[slot];
-    return BH_OK;
-}
-
-SetArgs set_args(bh_posterior *p, const ScalarSet *ss)
-{
-    SetArgs a;
-    a.work = p->dwork.as<PostWork>();
-    a.val = ss->val.as<double>();
-    a.nrows = p->nrows;
-    a.Q = ss->Q;
-    return a;
-}
-
 // per-site edges: offsets from 0, at least 2 finite ascending edges each; nb[s] = the bins
 int check_edges(bh_posterior *p, const int64_t *off, const double *edges, std::vector<int64_t> &nb)
 {
@@ -436,27 +306,6 @@ int upload_edges(bh_posterior *p, Dev &doff, Dev &ded, const int64_t *off, const
     PCHK(p, hipMemcpyAsync(doff.p, off, (size_t)(p->S + 1) * 8, hipMemcpyHostToDevice, p->st));
     PCHK(p, hipMemcpyAsync(ded.p, edges, ne * 8, hipMemcpyHostToDevice, p->st));
     return BH_OK;
-}
-
-double key2d(uint64_t k)
-{
-    const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v;
-    std::memcpy(&v, &u, 8);
-    return v;
-}
-
-// the 64-bit ordered key of the float32 value behind a 32-bit ordered key
-uint64_t widen_key(uint64_t k32)
-{
-    const uint32_t k = (uint32_t)k32;
-    const uint32_t u = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    float f;
-    std::memcpy(&f, &u, 4);
-    const double d = (double)f;
-    uint64_t b;
-    std::memcpy(&b, &d, 8);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 } // namespace
@@ -607,23 +456,10 @@ int bh_posterior_scalar_stats(bh_posterior *p, int set, int64_t *count, int64_t 
     PCHK(p, hipStreamSynchronize(p->st));
     ss->count.assign(count, count + ncol);   // (for bh_posterior_scalar_quantiles)
     ss->nf.assign(nf.begin(), nf.end());
-    // the fixed-point scale of every column: the lowest set bit, raised until |X| < 2^62 (as bh_posterior_columns)
-    for (size_t c = 0; c < ncol; ++c) {
+    for (size_t c = 0; c < ncol; ++c) {   // the fixed-point scale of every column
         if (count[c] == 0) { scale[c] = 0; x0[c] = 0; exact[c] = 1; continue; }
-        const double vmn = key2d(kmin[c]), vmx = key2d(kmax[c]);
-        const double amax = std::max(std::fabs(vmn), std::fabs(vmx));
-        if (!std::isfinite(amax)) return pfail(p, BH_EINVAL, "a value of a scalar column is not finite");
-        int L = 0;
-        if (amax > 0.0) {
-            int ea;
-            (void)std::frexp(amax, &ea); // amax < 2^ea
-            L = std::max(low[c], ea - 62);
-            exact[c] = low[c] >= ea - 62;
-        } else {
-            exact[c] = 1;
-        }
-        scale[c] = L;
-        x0[c] = (int64_t)std::nearbyint(std::ldexp(vmn, -L));
+        if ((rc = scale_rule(p, kmin[c], kmax[c], low[c], "a value of a scalar column is not finite", &scale[c], &x0[c], &exact[c])))
+            return rc;
     }
     if ((rc = alloc(p, dsc, ncol * 4)) || (rc = alloc(p, dx0, ncol * 8)) || (rc = alloc(p, dsum, ncol * 48))) return rc;
     PCHK(p, hipMemcpyAsync(dsc.p, scale, ncol * 4, hipMemcpyHostToDevice, p->st));
@@ -634,50 +470,12 @@ int bh_posterior_scalar_stats(bh_posterior *p, int set, int64_t *count, int64_t 
         PCHK(p, hipGetLastError());
     }
     PCHK(p, hipMemcpyAsync(sums, dsum.p, ncol * 48, hipMemcpyDeviceToHost, p->st));
-    if (median) {
-        Dev dh, dpref, drank, dnle, dnext, dkb;
-        if ((rc = alloc(p, dh, ncol * 256 * 4)) || (rc = alloc(p, dpref, ncol * 8)) || (rc = alloc(p, drank, ncol * 4)) ||
-            (rc = alloc(p, dnle, ncol * 4)) || (rc = alloc(p, dnext, ncol * 8)) || (rc = alloc(p, dkb, (size_t)Q * 4)))
-            return rc;
-        std::vector<unsigned> rk(ncol);
+    if (median) {   // the keys of ranks (n-1)/2 and (n-1)/2 + 1; a column of float32-exact values is selected on 32-bit keys
+        std::vector<uint32_t> rk(ncol);
         std::vector<int> kb(Q);
-        int passes = 4;
-        for (int q = 0; q < Q; ++q) {
-            kb[q] = nf[q] ? 64 : 32;
-            if (nf[q]) passes = 8;
-        }
-        for (size_t c = 0; c < ncol; ++c) rk[c] = count[c] ? (unsigned)((count[c] - 1) / 2) : 0u;
-        PCHK(p, hipMemsetAsync(dh.p, 0, ncol * 256 * 4, p->st));
-        PCHK(p, hipMemsetAsync(dpref.p, 0, ncol * 8, p->st));
-        PCHK(p, hipMemsetAsync(dnle.p, 0, ncol * 4, p->st));
-        PCHK(p, hipMemsetAsync(dnext.p, 0xff, ncol * 8, p->st));
-        PCHK(p, hipMemcpyAsync(drank.p, rk.data(), ncol * 4, hipMemcpyHostToDevice, p->st));
-        PCHK(p, hipMemcpyAsync(dkb.p, kb.data(), (size_t)Q * 4, hipMemcpyHostToDevice, p->st));
-        const unsigned pb = (unsigned)((ncol + 255) / 256);
-        if (!p->work.empty()) {
-            for (int pass = 0; pass < passes; ++pass) {
-                sc_radix_kernel<<<grid, SC_THREADS, 0, p->st>>>(a, dkb.as<int>(), pass, dpref.as<unsigned long long>(), dh.as<unsigned>());
-                sc_pick_kernel<<<pb, 256, 0, p->st>>>(ncol, Q, dkb.as<int>(), pass, dh.as<unsigned>(), dpref.as<unsigned long long>(),
-                                                      drank.as<unsigned>());
-            }
-            sc_next_kernel<<<grid, SC_THREADS, 0, p->st>>>(a, dkb.as<int>(), dpref.as<unsigned long long>(), dnle.as<unsigned>(),
-                                                           dnext.as<unsigned long long>());
-            PCHK(p, hipGetLastError());
-        }
-        std::vector<uint64_t> pref(ncol), next(ncol);
-        std::vector<unsigned> nle(ncol);
-        PCHK(p, hipMemcpyAsync(pref.data(), dpref.p, ncol * 8, hipMemcpyDeviceToHost, p->st));
-        PCHK(p, hipMemcpyAsync(next.data(), dnext.p, ncol * 8, hipMemcpyDeviceToHost, p->st));
-        PCHK(p, hipMemcpyAsync(nle.data(), dnle.p, ncol * 4, hipMemcpyDeviceToHost, p->st));
-        PCHK(p, hipStreamSynchronize(p->st));
-        for (size_t c = 0; c < ncol; ++c) {
-            if (count[c] == 0) { median[2 * c] = median[2 * c + 1] = 0; continue; }
-            // rank (n-1)/2 + 1 is the selected key again while more keys than (n-1)/2 + 1 are <= it
-            const uint64_t up = (nle[c] >= rk[c] + 2u || next[c] == ~0ull) ? pref[c] : next[c];
-            const bool k32 = kb[c % Q] == 32;
-            median[2 * c] = k32 ? widen_key(pref[c]) : pref[c];
-            median[2 * c + 1] = k32 ? widen_key(up) : up;
-        }
+        for (int q = 0; q < Q; ++q) kb[q] = nf[q] ? 64 : 32;
+        for (size_t c = 0; c < ncol; ++c) rk[c] = count[c] ? (uint32_t)((count[c] - 1) / 2) : 0u;
+        if ((rc = select_ranks(p, ncol, 1, rk.data(), count, kb, true, SetSelect{p, a}, median, median + 1, 2))) return rc;
     }
     PCHK(p, hipStreamSynchronize(p->st));
     return BH_OK;

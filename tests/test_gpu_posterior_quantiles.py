@@ -205,6 +205,52 @@ def test_the_middle_ranks_are_the_medians_keys(n, engine):
         assert np.array_equal(lo[0, :, 0], col["median"][0, :, 0]) and np.array_equal(up[0, :, 0], col["median"][0, :, 1])
 
 
+def test_two_ranks_on_both_layouts_beside_an_empty_and_a_one_row_site(engine):
+    """R = 2, the smallest call that takes the select's wide instantiation, over the depth columns and over a scalar set (a
+    float32-exact column and a float64 column with NaNs: both key widths in one call) of a site of 8193 rows (two chunks), an
+    empty site and a one-row site: numpy.sort's keys bit for bit, and the keys of the R = 1 calls of the same ranks"""
+    from bayhunter_amd import engine as E
+    from bayhunter_amd.posterior import _Loaded
+    rs = np.random.RandomState(8193)
+    counts = (8193, 0, 1)
+    m, dep = synth(rs, sum(counts), 6, "f32"), grid(65)
+    site = np.concatenate([np.full(n, s, np.int32) for s, n in enumerate(counts)])[rs.permutation(sum(counts))]
+    u = np.stack((rs.normal(0, 1, len(m)).astype(np.float32).astype(np.float64), rs.normal(5, 2, len(m)) + 1e-10), axis=1)
+    u[rs.randint(0, len(m), 300), 1] = np.nan
+    u[site == 2, 1] = np.nan                                    # the one-row site: a column without a value
+    crank = np.array([[17, 8192], [0, 0], [0, 0]], np.uint32)
+    ld = _Loaded(m, site, engine, 3, scalars=True)
+    try:
+        rc, lo, up, k32 = raw(ld, dep, crank)
+        ones = [raw(ld, dep, crank[:, r:r + 1]) for r in range(2)]
+        ld.attach(u, False)
+        cnt = ld.scalar_stats(E.SCALARS_USER)["count"]
+        srank = np.stack((cnt // 3, np.maximum(cnt - 1, 0)), axis=2).astype(np.uint32)
+        slo, sup = ld.quantile_keys(E.SCALARS_USER, srank)
+        sones = [ld.quantile_keys(E.SCALARS_USER, srank[:, :, r:r + 1]) for r in range(2)]
+    finally:
+        ld.close()
+    assert rc == 0 and k32 == 1
+    assert cnt[0, 0] == 8193 and 7800 < cnt[0, 1] < 8193 and not cnt[1].any() and [int(c) for c in cnt[2]] == [1, 0]
+    for s in range(3):
+        if not counts[s]:
+            assert not lo[s].any() and not up[s].any()
+            continue
+        wl, wu = want_keys(R.interp(m[site == s], dep), crank[s], True)
+        assert np.array_equal(lo[s], wl) and np.array_equal(up[s], wu), s
+    for s in range(3):
+        for q in range(2):
+            v = np.sort(u[site == s, q][~np.isnan(u[site == s, q])])
+            if not len(v):
+                assert not slo[s, q].any() and not sup[s, q].any()
+                continue
+            k = srank[s, q].astype(np.int64)
+            assert np.array_equal(slo[s, q], okeys(v[k], False)) and np.array_equal(sup[s, q], okeys(v[np.minimum(k + 1, len(v) - 1)], False)), (s, q)
+    for r in range(2):
+        assert ones[r][0] == 0 and np.array_equal(ones[r][1][:, :, 0], lo[:, :, r]) and np.array_equal(ones[r][2][:, :, 0], up[:, :, r])
+        assert np.array_equal(sones[r][0][:, :, 0], slo[:, :, r]) and np.array_equal(sones[r][1][:, :, 0], sup[:, :, r])
+
+
 # ---- independence -------------------------------------------------------------------------------------------------------
 
 def test_sites_among_others_alone_again_and_from_device_rows(engine):
