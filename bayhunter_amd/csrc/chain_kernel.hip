@@ -49,14 +49,17 @@
 #ifndef BH_CHAIN_RECORD
 #define BH_CHAIN_RECORD 0
 #endif
+// The launch plan of the entry points at the bottom (every build's: the headers of all twelve come with it) and node_rec_doubles.
+#include "chain_step.h"
+// What a build adds to its kernels' parameters (.._KPARAM) and, in its entry points, to their launches (.._KARG).
 #if BH_CHAIN_RECORD
-#include "../../include/bh_engine_chain_record.h"
 #define BH_RECORD_KPARAM , bh_chain_record store, int due, int due_step
+#define BH_RECORD_KARG , *rec, p.due, p.due_step
 #else
 #define BH_RECORD_KPARAM
+#define BH_RECORD_KARG
 #endif
 #if BH_CHAIN_PRIORS
-#include "../../include/bh_engine_sites_priors.h"
 #define ST pr
 #define BH_NLO(i) pr.nb[(i) * pr.stride]
 #define BH_NHI(i) pr.nb[(2 * BH_MAX_TARGETS + (i)) * pr.stride]
@@ -66,8 +69,9 @@
 #define BH_SITE_ARG(c) , (absent_of != nullptr ? (unsigned)absent_of[c] : 0u), pr
 #define BH_SITE_KPARAM , const uint8_t *absent_of, const bh_chain_prior *priors, int NP, const int32_t *prior_of
 #define BH_ACCEPT_KPARAM , const bh_chain_prior *priors, int NP, const int32_t *prior_of
+#define BH_SITE_KARG , absent, priors, P, prior_of
+#define BH_ACCEPT_KARG , priors, P, prior_of
 #elif BH_CHAIN_ABSENT
-#include "../../include/bh_engine_sites_missing.h"
 #define ST cfg
 #define BH_NLO(i) cfg.noise_lo[i]
 #define BH_NHI(i) cfg.noise_hi[i]
@@ -76,6 +80,7 @@
 #define BH_SITE_PARAM , unsigned absent
 #define BH_SITE_ARG(c) , (unsigned)absent_of[c]
 #define BH_SITE_KPARAM , const uint8_t *absent_of
+#define BH_SITE_KARG , absent
 #else
 #define ST cfg
 #define BH_NLO(i) cfg.noise_lo[i]
@@ -86,6 +91,8 @@
 #define BH_SITE_ARG(c)
 #define BH_SITE_KPARAM
 #define BH_ACCEPT_KPARAM
+#define BH_SITE_KARG
+#define BH_ACCEPT_KARG
 #endif
 
 namespace {
@@ -165,6 +172,27 @@ __device__ double get_accept_draw(const bh_chain_config &cfg, const bh_chain_sta
     ph.gen(cfg.seed, (uint32_t)(cfg.chain_offset + (int64_t)c), (uint32_t)iiter, 1u, q);
     return u01(q[2], q[3]);
 }
+
+// The accept decision, which the two accept kernels share.
+// log of the acceptance ratio of a birth or a death, Bodin et al. (2012) (SingleChain.py:468-485): theta = the birth/death proposal
+// width, dv = the width of the vs prior, dvs2 = the squared vs step of the proposal, dl = the (tempered) likelihood difference
+__device__ __forceinline__ double birth_death_alpha(bool birth, double theta, double dv, double dvs2, double dl)
+{
+    const double Bt = dvs2 / (2. * (theta * theta));
+    if (birth) return log((theta * sqrt(2 * M_PI)) / dv) + Bt + dl;
+    return log(dv / (theta * sqrt(2 * M_PI))) - Bt + dl;
+}
+// a proposal width after the adaptation (SingleChain.py:425-450): rate = the acceptance rate of its proposal type [%]
+__device__ __forceinline__ double adapted_width(double pd, double rate, double acc_lo, double acc_hi)
+{
+    if (rate < acc_lo) {
+        pd = pd * 0.95;
+        if (pd < 0.001) pd = 0.001;
+    } else if (rate > acc_hi) {
+        pd = pd * 1.05;
+    }
+    return pd;
+}
 #endif
 
 enum { MV_VS = 0, MV_Z = 1, MV_BIRTH = 2, MV_DEATH = 3, MV_NOISE = 4, MV_VPVS = 5 };
@@ -217,8 +245,7 @@ struct AcceptPrior {
     double vsmin, vsmax, acc_lo, acc_hi;
 };
 #endif
-// LDS record of one tree node (doubles): [0] n  [1] valid  [2] vp/vs  [3 .. 3+2nt) noise  then vs[ML+1], z[ML+1], h[ML+1]
-__host__ __device__ inline int node_rec_doubles(int nt, int ML) { return 3 + 2 * nt + 3 * (ML + 1); }
+// (the LDS record of one tree node: node_rec_doubles, chain_step.h)
 
 #if !BH_CHAIN_RECORD
 // The state a tree node's proposal starts from: the proposal of the nearest ancestor that is entered through
@@ -582,16 +609,9 @@ __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C
             S.proposed[pi * (size_t)C + c] += 1.0;
             const double like = logL[col];
             const double dl = (S.beta ? beta * (like - cur) : like - cur);
-            double alpha;
-            if (mv == MV_BIRTH || mv == MV_DEATH) { // Bodin et al. (2012), SingleChain.py:468-485
-                const double theta = S.propdist[2 * (size_t)C + c];
-                const double dv = ST.vsmax - ST.vsmin;
-                const double Bt = S.dvs2[col] / (2. * (theta * theta));
-                if (mv == MV_BIRTH) alpha = log((theta * sqrt(2 * M_PI)) / dv) + Bt + dl;
-                else alpha = log(dv / (theta * sqrt(2 * M_PI))) - Bt + dl;
-            } else {
-                alpha = dl;
-            }
+            double alpha = dl;
+            if (mv == MV_BIRTH || mv == MV_DEATH)
+                alpha = birth_death_alpha(mv == MV_BIRTH, S.propdist[2 * (size_t)C + c], ST.vsmax - ST.vsmin, S.dvs2[col], dl);
             if (log(u_accept) < alpha) {
                 accepted = true;
                 last = node;
@@ -607,14 +627,7 @@ __global__ void chain_accept_kernel(bh_chain_config cfg, bh_chain_state S, int C
                 if (all)
                     for (int i = 0; i < 5; ++i) {
                         const double rate = S.accepted[i * (size_t)C + c] / S.proposed[i * (size_t)C + c] * 100;
-                        double pd = S.propdist[i * (size_t)C + c];
-                        if (rate < ST.acc_lo) {
-                            pd = pd * 0.95;
-                            if (pd < 0.001) pd = 0.001;
-                        } else if (rate > ST.acc_hi) {
-                            pd = pd * 1.05;
-                        }
-                        S.propdist[i * (size_t)C + c] = pd;
+                        S.propdist[i * (size_t)C + c] = adapted_width(S.propdist[i * (size_t)C + c], rate, ST.acc_lo, ST.acc_hi);
                     }
             }
         }
@@ -742,15 +755,8 @@ __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config
             if (lane == pi) prop += 1.0;
             const double like = hi ? lb : la;
             const double dl = (S.beta ? beta * (like - cur) : like - cur);
-            double alpha;
-            if (mv == MV_BIRTH || mv == MV_DEATH) { // Bodin et al. (2012), SingleChain.py:468-485
-                const double dv = ST.vsmax - ST.vsmin;
-                const double Bt = (hi ? db : da) / (2. * (theta * theta));
-                if (mv == MV_BIRTH) alpha = log((theta * sqrt(2 * M_PI)) / dv) + Bt + dl;
-                else alpha = log(dv / (theta * sqrt(2 * M_PI))) - Bt + dl;
-            } else {
-                alpha = dl;
-            }
+            double alpha = dl;
+            if (mv == MV_BIRTH || mv == MV_DEATH) alpha = birth_death_alpha(mv == MV_BIRTH, theta, ST.vsmax - ST.vsmin, hi ? db : da, dl);
             if (log(u_accept) < alpha) {
                 accepted = true;
                 last = node;
@@ -763,14 +769,7 @@ __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config
                 const bool all = (__ballot(lane < 5 && prop != 0.0) & 0x1full) == 0x1full;
                 if (all && lane < 5) {
                     const double rate = acc / prop * 100;
-                    double pd = S.propdist[lane * (size_t)C + c];
-                    if (rate < ST.acc_lo) {
-                        pd = pd * 0.95;
-                        if (pd < 0.001) pd = 0.001;
-                    } else if (rate > ST.acc_hi) {
-                        pd = pd * 1.05;
-                    }
-                    S.propdist[lane * (size_t)C + c] = pd;
+                    S.propdist[lane * (size_t)C + c] = adapted_width(S.propdist[lane * (size_t)C + c], rate, ST.acc_lo, ST.acc_hi);
                 }
             }
         }
@@ -800,86 +799,81 @@ __global__ __launch_bounds__(64) void chain_accept_window_kernel(bh_chain_config
 
 #endif
 
+// ---- the entry points: ask, plan (bh_plan_chain_step, chain_step.hip: every rule is there), launch ---------------------------------
+// The two steps below take the arguments of all builds (null where the entry has none) for the ask; the one thing a build says for
+// itself is which kernels it has and what its .._KARG add to their argument lists.
+#if !BH_CHAIN_RECORD
+int propose_step(ChainEntry entry, void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter, int depth,
+                 ptrdiff_t ld, const uint8_t *absent, const bh_chain_prior *priors, int P, const int32_t *prior_of)
+{
+    ChainStepAsk q = chain_step_ask(entry, cfg, state, C, iiter, depth, ld);
+    chain_step_ask_table(q, absent, priors, P, prior_of);
+    const ChainStepPlan p = bh_plan_chain_step(q);
+    if (p.kernel == CHAIN_KERNEL_NONE) return p.code;
+    if (p.big_lds) {
+        static std::atomic<unsigned long long> big{0};
+        const void *k[1] = {reinterpret_cast<const void *>(chain_propose_window_kernel)};
+        if (!bh_allow_big_lds(&big, k, 1, 160 * 1024)) return BH_EHIP;
+    }
+    if (p.kernel == CHAIN_KERNEL_PROPOSE_LANE)
+        hipLaunchKernelGGL(chain_propose_kernel, dim3(p.grid), dim3(p.block), p.lds, (hipStream_t)stream, *cfg, *state, C,
+                           iiter BH_SITE_KARG);
+    else
+        hipLaunchKernelGGL(chain_propose_window_kernel, dim3(p.grid), dim3(p.block), p.lds, (hipStream_t)stream, *cfg, *state, C,
+                           (size_t)ld, iiter, depth BH_SITE_KARG);
+    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+}
+#endif
+
+#if !BH_CHAIN_ABSENT
+int accept_step(ChainEntry entry, void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter, int depth,
+                ptrdiff_t ld, const double *logL, const double *misfits, const bh_chain_prior *priors, int P, const int32_t *prior_of,
+                const bh_chain_record *rec)
+{
+    ChainStepAsk q = chain_step_ask(entry, cfg, state, C, iiter, depth, ld);
+    q.logL = logL != nullptr;
+    q.misfits = misfits != nullptr;
+    chain_step_ask_table(q, nullptr, priors, P, prior_of);
+    chain_step_ask_record(q, rec);
+    const ChainStepPlan p = bh_plan_chain_step(q);
+    if (p.kernel == CHAIN_KERNEL_NONE) return p.code;
+#if !BH_CHAIN_RECORD // (the builds with a store have the wavefront-per-chain kernel only, and the plan names no other for them)
+    if (p.kernel == CHAIN_KERNEL_ACCEPT_LANE)
+        hipLaunchKernelGGL(chain_accept_kernel, dim3(p.grid), dim3(p.block), p.lds, (hipStream_t)stream, *cfg, *state, C, (size_t)ld,
+                           iiter, depth, logL, misfits BH_ACCEPT_KARG);
+    else
+#endif
+        hipLaunchKernelGGL(chain_accept_window_kernel, dim3(p.grid), dim3(p.block), p.lds, (hipStream_t)stream, *cfg, *state, C,
+                           (size_t)ld, iiter, depth, logL, misfits BH_ACCEPT_KARG BH_RECORD_KARG);
+    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+}
+#endif
+
 } // namespace
 
 extern "C" {
 
-#if BH_CHAIN_RECORD
-// the window accept calls with a store: always the wavefront-per-chain kernel
-#if BH_CHAIN_PRIORS
+#if BH_CHAIN_RECORD && BH_CHAIN_PRIORS
 int bh_chain_accept_window_priors_record(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
                                          int depth, ptrdiff_t ld, const double *logL, const double *misfits,
                                          const bh_chain_prior *priors, int P, const int32_t *prior_of, const bh_chain_record *rec)
-#else
+{
+    return accept_step(CHAIN_ACCEPT_WINDOW_PRIORS_RECORD, stream, cfg, state, C, iiter, depth, ld, logL, misfits, priors, P, prior_of, rec);
+}
+
+#elif BH_CHAIN_RECORD
 int bh_chain_accept_window_record(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
                                   int depth, ptrdiff_t ld, const double *logL, const double *misfits, const bh_chain_record *rec)
-#endif
 {
-    if (!cfg || !state || C < 0 || !logL || !misfits) return BH_EINVAL;
-    if (cfg->maxlayers < 0 || cfg->maxlayers > BH_CHAIN_MAXLAYERS || cfg->nt < 0 || cfg->nt > BH_MAX_TARGETS) return BH_EINVAL;
-    if (depth < 1 || depth > BH_CHAIN_MAXDEPTH || ld < (ptrdiff_t)C * ((1 << depth) - 1)) return BH_EINVAL;
-#if BH_CHAIN_PRIORS
-    if (!priors || !prior_of || P < 1) return BH_EINVAL;
-#endif
-    for (int k = 0; k + 1 < depth; ++k)
-        if ((iiter + k) % 1000 == 0) return BH_EINVAL; // an adaptation iteration must be the last of its window
-    if (!rec || !rec->models || !rec->likes || !rec->vpvs || !rec->misfits || !rec->noise) return BH_EINVAL;
-    if (rec->thinning < 1 || rec->row0 < 0) return BH_EINVAL;
-    // the first due level: iiter + first = 0 mod thinning (non-negative residue); m due levels in the window
-    const int64_t res = (((int64_t)iiter % rec->thinning) + rec->thinning) % rec->thinning;
-    const int64_t first = res == 0 ? 0 : rec->thinning - res;
-    const int64_t m = first >= depth ? 0 : 1 + ((int64_t)depth - 1 - first) / rec->thinning;
-    if (rec->row0 > rec->rows - m) return BH_EINVAL;
-    if (C == 0) return BH_OK;
-    // (a step beyond the deepest window means "no further one": thinning itself need not fit an int)
-    const int due = (int)(first < depth ? first : depth);
-    const int due_step = (int)(rec->thinning <= BH_CHAIN_MAXDEPTH ? rec->thinning : BH_CHAIN_MAXDEPTH + 1);
-#if BH_CHAIN_PRIORS
-    hipLaunchKernelGGL(chain_accept_window_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld, iiter, depth,
-                       logL, misfits, priors, P, prior_of, *rec, due, due_step);
-#else
-    hipLaunchKernelGGL(chain_accept_window_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld, iiter, depth,
-                       logL, misfits, *rec, due, due_step);
-#endif
-    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+    return accept_step(CHAIN_ACCEPT_WINDOW_RECORD, stream, cfg, state, C, iiter, depth, ld, logL, misfits, nullptr, 0, nullptr, rec);
 }
 
 #elif BH_CHAIN_PRIORS
-static int window_args_ok(const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter, int depth, ptrdiff_t ld,
-                          const bh_chain_prior *priors, int P, const int32_t *prior_of)
-{
-    if (!cfg || !state || C < 0 || cfg->maxlayers > BH_CHAIN_MAXLAYERS || cfg->nt > BH_MAX_TARGETS) return 0;
-    if (depth < 1 || depth > BH_CHAIN_MAXDEPTH || ld < (ptrdiff_t)C * ((1 << depth) - 1)) return 0;
-    if (!priors || !prior_of || P < 1) return 0;
-    for (int k = 0; k + 1 < depth; ++k)
-        if ((iiter + k) % 1000 == 0) return 0; // an adaptation iteration must be the last of its window
-    return 1;
-}
-
 int bh_chain_propose_window_priors(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
                                    int depth, ptrdiff_t ld, const bh_chain_prior *priors, int P, const int32_t *prior_of,
                                    const uint8_t *absent)
 {
-    if (!window_args_ok(cfg, state, C, iiter, depth, ld, priors, P, prior_of)) return BH_EINVAL;
-    if (C == 0) return BH_OK;
-    if (depth == 1 && ld == C) {
-        hipLaunchKernelGGL(chain_propose_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, iiter, absent,
-                           priors, P, prior_of);
-    } else {
-        const int per_wg = 64 >> (depth - 1);
-        // the tree, then the noise bounds of the workgroup's chains
-        const size_t lds = ((size_t)per_wg * ((1 << depth) - 1) * (node_rec_doubles(cfg->nt, cfg->maxlayers) | 1) +
-                            (size_t)per_wg * 4 * BH_MAX_TARGETS) * sizeof(double);
-        if (lds > 160 * 1024) return BH_EUNSUPPORTED;
-        if (lds > 64 * 1024) {
-            static std::atomic<unsigned long long> big{0};
-            const void *k[1] = {reinterpret_cast<const void *>(chain_propose_window_kernel)};
-            if (!bh_allow_big_lds(&big, k, 1, 160 * 1024)) return BH_EHIP;
-        }
-        hipLaunchKernelGGL(chain_propose_window_kernel, dim3((C + per_wg - 1) / per_wg), dim3(64), lds, (hipStream_t)stream, *cfg,
-                           *state, C, (size_t)ld, iiter, depth, absent, priors, P, prior_of);
-    }
-    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+    return propose_step(CHAIN_PROPOSE_WINDOW_PRIORS, stream, cfg, state, C, iiter, depth, ld, absent, priors, P, prior_of);
 }
 
 int bh_chain_propose_priors(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
@@ -892,15 +886,7 @@ int bh_chain_accept_window_priors(void *stream, const bh_chain_config *cfg, cons
                                   int depth, ptrdiff_t ld, const double *logL, const double *misfits,
                                   const bh_chain_prior *priors, int P, const int32_t *prior_of)
 {
-    if (!window_args_ok(cfg, state, C, iiter, depth, ld, priors, P, prior_of) || !logL || !misfits) return BH_EINVAL;
-    if (C == 0) return BH_OK;
-    if (depth > 1) // a wavefront per chain
-        hipLaunchKernelGGL(chain_accept_window_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld, iiter, depth,
-                           logL, misfits, priors, P, prior_of);
-    else
-        hipLaunchKernelGGL(chain_accept_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld,
-                           iiter, depth, logL, misfits, priors, P, prior_of);
-    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+    return accept_step(CHAIN_ACCEPT_WINDOW_PRIORS, stream, cfg, state, C, iiter, depth, ld, logL, misfits, priors, P, prior_of, nullptr);
 }
 
 int bh_chain_accept_priors(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
@@ -910,67 +896,29 @@ int bh_chain_accept_priors(void *stream, const bh_chain_config *cfg, const bh_ch
     return bh_chain_accept_window_priors(stream, cfg, state, C, iiter, 1, C, logL, misfits, priors, P, prior_of);
 }
 
-#else // the entry points without a table of priors
-
-#if BH_CHAIN_ABSENT
+#elif BH_CHAIN_ABSENT
 int bh_chain_propose_window_sites(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
                                   int depth, ptrdiff_t ld, const uint8_t *absent)
-#else
-int bh_chain_propose_window(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
-                            int depth, ptrdiff_t ld)
-#endif
 {
-#if BH_CHAIN_ABSENT
-    if (!absent) return BH_EINVAL;
-#define BH_ABSENT_LAUNCH , absent
-#else
-#define BH_ABSENT_LAUNCH
-#endif
-    if (!cfg || !state || C < 0 || cfg->maxlayers > BH_CHAIN_MAXLAYERS || cfg->nt > BH_MAX_TARGETS) return BH_EINVAL;
-    if (depth < 1 || depth > BH_CHAIN_MAXDEPTH || ld < (ptrdiff_t)C * ((1 << depth) - 1)) return BH_EINVAL;
-    for (int k = 0; k + 1 < depth; ++k)
-        if ((iiter + k) % 1000 == 0) return BH_EINVAL; // an adaptation iteration must be the last of its window
-    if (C == 0) return BH_OK;
-    if (depth == 1 && ld == C) {
-        hipLaunchKernelGGL(chain_propose_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, iiter BH_ABSENT_LAUNCH);
-    } else {
-        const int per_wg = 64 >> (depth - 1);
-        const size_t lds = (size_t)per_wg * ((1 << depth) - 1) * (node_rec_doubles(cfg->nt, cfg->maxlayers) | 1) * sizeof(double);
-        if (lds > 160 * 1024) return BH_EUNSUPPORTED;
-        if (lds > 64 * 1024) {
-            static std::atomic<unsigned long long> big{0};
-            const void *k[1] = {reinterpret_cast<const void *>(chain_propose_window_kernel)};
-            if (!bh_allow_big_lds(&big, k, 1, 160 * 1024)) return BH_EHIP;
-        }
-        hipLaunchKernelGGL(chain_propose_window_kernel, dim3((C + per_wg - 1) / per_wg), dim3(64), lds, (hipStream_t)stream, *cfg,
-                           *state, C, (size_t)ld, iiter, depth BH_ABSENT_LAUNCH);
-    }
-    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+    return propose_step(CHAIN_PROPOSE_WINDOW_SITES, stream, cfg, state, C, iiter, depth, ld, absent, nullptr, 0, nullptr);
 }
-#undef BH_ABSENT_LAUNCH
 
-#if BH_CHAIN_ABSENT
 int bh_chain_propose_sites(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter, const uint8_t *absent)
 {
     return bh_chain_propose_window_sites(stream, cfg, state, C, iiter, 1, C, absent);
 }
+
 #else
+int bh_chain_propose_window(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
+                            int depth, ptrdiff_t ld)
+{
+    return propose_step(CHAIN_PROPOSE_WINDOW, stream, cfg, state, C, iiter, depth, ld, nullptr, nullptr, 0, nullptr);
+}
 
 int bh_chain_accept_window(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter, int depth,
                            ptrdiff_t ld, const double *logL, const double *misfits)
 {
-    if (!cfg || !state || C < 0 || !logL || !misfits) return BH_EINVAL;
-    if (depth < 1 || depth > BH_CHAIN_MAXDEPTH || ld < (ptrdiff_t)C * ((1 << depth) - 1)) return BH_EINVAL;
-    for (int k = 0; k + 1 < depth; ++k)
-        if ((iiter + k) % 1000 == 0) return BH_EINVAL;
-    if (C == 0) return BH_OK;
-    if (depth > 1) // a wavefront per chain
-        hipLaunchKernelGGL(chain_accept_window_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld, iiter, depth,
-                           logL, misfits);
-    else
-        hipLaunchKernelGGL(chain_accept_kernel, dim3((C + 63) / 64), dim3(64), 0, (hipStream_t)stream, *cfg, *state, C, (size_t)ld,
-                           iiter, depth, logL, misfits);
-    return hipGetLastError() == hipSuccess ? BH_OK : BH_EHIP;
+    return accept_step(CHAIN_ACCEPT_WINDOW, stream, cfg, state, C, iiter, depth, ld, logL, misfits, nullptr, 0, nullptr, nullptr);
 }
 
 int bh_chain_propose(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter)
@@ -983,9 +931,6 @@ int bh_chain_accept(void *stream, const bh_chain_config *cfg, const bh_chain_sta
 {
     return bh_chain_accept_window(stream, cfg, state, C, iiter, 1, C, logL, misfits);
 }
-
 #endif
-
-#endif // BH_CHAIN_PRIORS
 
 } // extern "C"

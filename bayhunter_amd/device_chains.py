@@ -83,6 +83,18 @@ def record_rows(iter_burnin, iter_main, thinning):
     return snapshot_count(-int(iter_burnin), 0, thinning), snapshot_count(0, int(iter_main), thinning)
 
 
+def window_entries(engine, table, rec):
+    """The propose and the accept entry of one window, by (a table of priors is present, the device record is active):
+    (propose method, its extra arguments, accept method, its extra arguments).  table: None, or (records pointer, records,
+    prior_of pointer); rec: None, or the ChainRecord of this window."""
+    propose = engine.chain_propose_window if table is None else engine.chain_propose_window_priors
+    accept = {(False, False): engine.chain_accept_window, (True, False): engine.chain_accept_window_priors,
+              (False, True): engine.chain_accept_window_record,
+              (True, True): engine.chain_accept_window_priors_record}[table is not None, rec is not None]
+    extra = () if table is None else tuple(table)
+    return propose, extra, accept, extra + (() if rec is None else (rec,))
+
+
 RECORD_MODES = ("host", "device")
 
 # DeviceChains(ladder_adapt=): sweeps per adaptation window, gain and decay of the gain (kappa = rate * lag / (n + lag) at the n-th
@@ -516,11 +528,12 @@ class DeviceChains(object):
         w = self.window()
         B = Cn * ((1 << w) - 1)
         absent = None if self.absent is None else self.absent.data_ptr()
-        if self.prior_records is not None:
-            e.chain_propose_window_priors(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.prior_records.data_ptr(),
-                                          self.nsites, self.prior_of.data_ptr(), absent=absent)
-        else:
-            e.chain_propose_window(self.cfg, self.state, Cn, self.iiter, w, self.ld, absent=absent)
+        rec = self._rec if self.iiter < self.iter_phase2 else None
+        if rec is not None:
+            rec.row0 = snapshot_count(-self.iter_phase1, self.iiter, self.thinning)
+        table = None if self.prior_records is None else (self.prior_records.data_ptr(), self.nsites, self.prior_of.data_ptr())
+        propose, propose_extra, accept, accept_extra = window_entries(e, table, rec)
+        propose(self.cfg, self.state, Cn, self.iiter, w, self.ld, *propose_extra, absent=absent)
         e.set_typical_layers(self._hint)       # (for this call only: the engine is shared with other callers)
         prev = e.swd_search() if self.search is not None else None
         if prev is not None and prev != self.search:
@@ -547,21 +560,7 @@ class DeviceChains(object):
             if prev_arith is not None and prev_arith != self.arith:
                 e.set_swd_arith(prev_arith)
             e.set_swd_trials(prev_trials)
-        rec = self._rec if self.iiter < self.iter_phase2 else None
-        if rec is not None:
-            rec.row0 = snapshot_count(-self.iter_phase1, self.iiter, self.thinning)
-            if self.prior_records is not None:
-                e.chain_accept_window_priors_record(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(),
-                                                    self.mis.data_ptr(), self.prior_records.data_ptr(), self.nsites,
-                                                    self.prior_of.data_ptr(), rec)
-            else:
-                e.chain_accept_window_record(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(),
-                                             self.mis.data_ptr(), rec)
-        elif self.prior_records is not None:
-            e.chain_accept_window_priors(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(), self.mis.data_ptr(),
-                                         self.prior_records.data_ptr(), self.nsites, self.prior_of.data_ptr())
-        else:
-            e.chain_accept_window(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(), self.mis.data_ptr())
+        accept(self.cfg, self.state, Cn, self.iiter, w, self.ld, self.logL.data_ptr(), self.mis.data_ptr(), *accept_extra)
         self.iiter += w
         self.launches += 1
         if self.swap_every > 0 and t["beta"] is not None and self.iiter % self.swap_every == 0:

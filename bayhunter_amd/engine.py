@@ -981,60 +981,45 @@ class Engine(object):
                                               sl, sb, site, noise, logL, misfits, err, ymod))
 
 
-    def chain_propose(self, cfg, state, C_, iiter):
-        rc = self._L.bh_chain_propose(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter))
+    def _chain(self, symbol, cfg, state, C_, iiter, *args, named=None):
+        """Call the chain-step entry point `symbol` with (stream, cfg, state, C, iiter, *args); an EngineError names it."""
+        rc = getattr(self._L, symbol)(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), *args)
         if rc != BH_OK:
-            raise EngineError("bh_chain_propose failed (%d)" % rc)
+            raise EngineError("%s failed (%d)" % (named or symbol, rc))
+
+    def chain_propose(self, cfg, state, C_, iiter):
+        self._chain("bh_chain_propose", cfg, state, C_, iiter)
 
     def chain_accept(self, cfg, state, C_, iiter, logL, misfits):
-        rc = self._L.bh_chain_accept(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), logL, misfits)
-        if rc != BH_OK:
-            raise EngineError("bh_chain_accept failed (%d)" % rc)
+        self._chain("bh_chain_accept", cfg, state, C_, iiter, logL, misfits)
 
     def chain_propose_window(self, cfg, state, C_, iiter, depth, ld, absent=None):
         """absent: None, or the device pointer of uint8 [C] -- bit t set: the chain's site lacks target t (bh_chain_propose_window_sites)"""
-        if absent is not None:
-            rc = self._L.bh_chain_propose_window_sites(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth),
-                                                       int(ld), absent)
+        if absent is not None:     # (the one method with two symbols: its error names the method's own either way)
+            self._chain("bh_chain_propose_window_sites", cfg, state, C_, iiter, int(depth), int(ld), absent, named="bh_chain_propose_window")
         else:
-            rc = self._L.bh_chain_propose_window(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth), int(ld))
-        if rc != BH_OK:
-            raise EngineError("bh_chain_propose_window failed (%d)" % rc)
+            self._chain("bh_chain_propose_window", cfg, state, C_, iiter, int(depth), int(ld))
 
     def chain_propose_window_priors(self, cfg, state, C_, iiter, depth, ld, priors, nprior, prior_of, absent=None):
         """bh_chain_propose_window_priors.  priors: device pointer of `nprior` ChainPrior records; prior_of: device pointer of
         int32 [C], the record of each chain; absent: as in chain_propose_window (None: every target present)"""
-        rc = self._L.bh_chain_propose_window_priors(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth),
-                                                    int(ld), priors, int(nprior), prior_of, absent)
-        if rc != BH_OK:
-            raise EngineError("bh_chain_propose_window_priors failed (%d)" % rc)
+        self._chain("bh_chain_propose_window_priors", cfg, state, C_, iiter, int(depth), int(ld), priors, int(nprior), prior_of, absent)
 
     def chain_accept_window_priors(self, cfg, state, C_, iiter, depth, ld, logL, misfits, priors, nprior, prior_of):
         """bh_chain_accept_window_priors (arguments as chain_propose_window_priors)"""
-        rc = self._L.bh_chain_accept_window_priors(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth),
-                                                   int(ld), logL, misfits, priors, int(nprior), prior_of)
-        if rc != BH_OK:
-            raise EngineError("bh_chain_accept_window_priors failed (%d)" % rc)
+        self._chain("bh_chain_accept_window_priors", cfg, state, C_, iiter, int(depth), int(ld), logL, misfits, priors, int(nprior), prior_of)
 
     def chain_accept_window_record(self, cfg, state, C_, iiter, depth, ld, logL, misfits, rec):
         """bh_chain_accept_window_record.  rec: a ChainRecord (include/bh_engine_chain_record.h)"""
-        rc = self._L.bh_chain_accept_window_record(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth), int(ld),
-                                                   logL, misfits, C.byref(rec))
-        if rc != BH_OK:
-            raise EngineError("bh_chain_accept_window_record failed (%d)" % rc)
+        self._chain("bh_chain_accept_window_record", cfg, state, C_, iiter, int(depth), int(ld), logL, misfits, C.byref(rec))
 
     def chain_accept_window_priors_record(self, cfg, state, C_, iiter, depth, ld, logL, misfits, priors, nprior, prior_of, rec):
         """bh_chain_accept_window_priors_record (arguments as chain_accept_window_priors, then the ChainRecord)"""
-        rc = self._L.bh_chain_accept_window_priors_record(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth),
-                                                          int(ld), logL, misfits, priors, int(nprior), prior_of, C.byref(rec))
-        if rc != BH_OK:
-            raise EngineError("bh_chain_accept_window_priors_record failed (%d)" % rc)
+        self._chain("bh_chain_accept_window_priors_record", cfg, state, C_, iiter, int(depth), int(ld), logL, misfits, priors, int(nprior),
+                    prior_of, C.byref(rec))
 
     def chain_accept_window(self, cfg, state, C_, iiter, depth, ld, logL, misfits):
-        rc = self._L.bh_chain_accept_window(self.stream, C.byref(cfg), C.byref(state), int(C_), int(iiter), int(depth), int(ld),
-                                            logL, misfits)
-        if rc != BH_OK:
-            raise EngineError("bh_chain_accept_window failed (%d)" % rc)
+        self._chain("bh_chain_accept_window", cfg, state, C_, iiter, int(depth), int(ld), logL, misfits)
 
 
 _default = {}

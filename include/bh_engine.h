@@ -324,7 +324,12 @@ int bh_chain_accept(void *stream, const bh_chain_config *cfg, const bh_chain_sta
  * [ld][2nt]).  One window = bh_chain_propose_window -> bh_evaluate_batch(B = N*C, stride_l = ld, stride_b = 1,
  * noise = pnoise) -> bh_chain_accept_window(logL [N*C], misfits [N*C][nt+1]), which walks the realised path.
  * An iteration with iiter % 1000 == 0 (proposal-width adaptation) must be the last of its window (BH_EINVAL
- * otherwise); state->inject, if used, holds [depth][6][C].  depth = 1, ld = C is bh_chain_propose / _accept. */
+ * otherwise); state->inject, if used, holds [depth][6][C].  depth = 1, ld = C is bh_chain_propose / _accept.
+ * BH_EINVAL (nothing launched), for all four calls alike: cfg or state NULL; C < 0; cfg->nt outside [0, BH_MAX_TARGETS] or
+ * cfg->maxlayers outside [0, BH_CHAIN_MAXLAYERS]; depth outside 1..BH_CHAIN_MAXDEPTH; ld < C (2^depth - 1); logL or misfits NULL
+ * (the accept calls); an adaptation iteration inside the window.  C == 0 with everything else in order is BH_OK.  (The range of nt
+ * and maxlayers is checked by every chain entry point since the rules were stated once, csrc/chain_step.hip: before, the propose
+ * calls let negative values pass and bh_chain_accept_window any value.  No other return changed.) */
 int bh_chain_propose_window(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
                             int depth, ptrdiff_t ld);
 int bh_chain_accept_window(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,

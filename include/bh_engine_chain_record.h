@@ -43,8 +43,9 @@ typedef struct bh_chain_record {
  * writes a row >= rows.  A chain whose prior_of is out of range keeps its state (as in bh_chain_accept_window_priors) and
  * that state is what its rows hold.
  * BH_EINVAL (nothing launched): what the calls without a store refuse (an adaptation iteration inside the window, ..); rec NULL;
- *   models, likes, vpvs, misfits or noise NULL; thinning < 1; row0 < 0; row0 + m > rows; cfg->maxlayers > BH_CHAIN_MAXLAYERS or
- *   cfg->nt > BH_MAX_TARGETS. */
+ *   models, likes, vpvs, misfits or noise NULL; thinning < 1; row0 < 0; row0 + m > rows; cfg->maxlayers outside
+ *   [0, BH_CHAIN_MAXLAYERS] or cfg->nt outside [0, BH_MAX_TARGETS] (these two calls always checked both bounds; every chain entry
+ *   point does now -- bh_engine.h -- and that is the one return that changed anywhere when the rules were stated once). */
 int bh_chain_accept_window_record(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
                                   int depth, ptrdiff_t ld, const double *logL, const double *misfits, const bh_chain_record *rec);
 int bh_chain_accept_window_priors_record(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,

@@ -52,7 +52,8 @@ int bh_sites_set_missing(bh_engine *e, int nsites, const int32_t *n, const doubl
  * definition.  The random streams do not depend on the number of targets, so a chain whose site has the same free parameters in
  * the same order as a one-site job draws that job's moves and parameters.  The noise entries of an absent target are carried
  * along unchanged.  bh_chain_accept / bh_chain_accept_window serve these chains as they are (they copy noise and misfits, no
- * more).  BH_EINVAL: what the plain entry points refuse; a null mask. */
+ * more).  BH_EINVAL: what the plain entry points refuse; a null mask.  (With the plain entry points, these now refuse a negative
+ * cfg->nt or cfg->maxlayers as well -- bh_engine.h; before, only values above the limits.) */
 int bh_chain_propose_sites(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
                            const uint8_t *absent);
 int bh_chain_propose_window_sites(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,

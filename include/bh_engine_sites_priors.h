@@ -45,7 +45,8 @@ typedef struct bh_chain_prior {
  * from goes to the evaluation.  The accept calls keep rows beyond n at zero up to cfg->maxlayers.
  * A chain whose prior_of is outside [0, P) reads nothing of the table: all its proposals are invalid (the evaluation sees the
  * model it holds) and the accept calls leave its state, counters included, as it was -- in band, like a site out of range.
- * BH_EINVAL: what the plain entry points refuse; null priors or prior_of; P < 1. */
+ * BH_EINVAL: what the plain entry points refuse; null priors or prior_of; P < 1.  (With the plain entry points, these now refuse
+ * a negative cfg->nt or cfg->maxlayers as well -- bh_engine.h; before, only values above the limits.) */
 int bh_chain_propose_priors(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
                             const bh_chain_prior *priors, int P, const int32_t *prior_of, const uint8_t *absent);
 int bh_chain_propose_window_priors(void *stream, const bh_chain_config *cfg, const bh_chain_state *state, int C, int iiter,
