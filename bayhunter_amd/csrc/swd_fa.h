@@ -5,7 +5,7 @@
 // normc) -- the same formulas, the same per-layer max-norm scaling -- evaluated with what the chip does quickly instead of
 // with the reference's rounding points: fused multiply-adds, reciprocals and square roots from the hardware seed
 // (v_rcp_f64 / v_rsq_f64) refined by Newton / Goldschmidt steps, sin / cos / exp from two-part Cody-Waite reductions and
-// polynomials, e^-(p+q) as a product of the two wave types' exponentials.  Every result is within a few
+// polynomials (their leaf terms one v_fma_f64 each: fma_leaf below), e^-(p+q) as a product of the two wave types' exponentials.  Every result is within a few
 // units in the last place of the exactly rounded formula, i.e. it differs from the reference-exact evaluation by what that
 // evaluation's own rounding error is; about a third of its instructions.
 //
@@ -67,20 +67,42 @@ __device__ __forceinline__ double rcp1(double x) // one step (~2^-45): scale fac
 // Taylor series to r^12 on |r| <= ln 2 / 2 (exp), the polynomials summed by Estrin's scheme -- half the depth of the chain of
 // dependent operations, which is what two wavefronts per SIMD cannot hide.  Derived (tests/swd_fa_ref.py) and probed on the
 // device (tests/test_gpu_swd_fa.py): rcp 1 u, sqrt_rsqrt 2.5 u, sin / cos 3 u absolute, expneg 5 u, rcp1 2^-46 (u = 2^-53).
+//
+// fma_leaf(z, C1, C0) = fma(z, C1, C0), a polynomial's leaf term of two constants, as ONE v_fma_f64 d, z, v[C1], s[C0]: one
+// constant in a VGPR pair, the other in an SGPR pair (the constant bus takes one scalar operand per instruction).  The value
+// is __builtin_fma's, bit for bit -- the same instruction (tests/test_gpu_lean_eval_bits.py).  Why it exists: from
+// __builtin_fma the compiler selects the two-address v_fmac_f64, whose addend is its destination, and so first copies the
+// VGPR-held constant with a v_mov_b64: one copy per leaf, six per sincos, four per expneg -- 20 of the 34 v_mov_b* of a Rayleigh
+// layer step, 10 of the 14 of a Love layer step (profiles/lean_eval_diet_isa.txt; c2's kernel 590 -> 582 us,
+// profiles/lean_eval_diet.txt).  expneg's fifth leaf adds 0.5, an inline constant: it had no copy, and through the helper it
+// would occupy a register pair (the 64-lane build went from 199 to 201 registers), so it stays a __builtin_fma.  There is no
+// other plain form to try: every spelling of the fused operation is the same llvm.fma call.  Whether the helper is still
+// needed: make its body `return __builtin_fma(z, c1, c0);` and run tools/lean_isa_counts.py -- if the v_mov_b* column of the two
+// layer loops stays where it is, the compiler has learnt to pick the three-address form, and the helper can go.
+__device__ __forceinline__ double fma_leaf(double z, double c1, double c0)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    double d;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(z), "v"(c1), "s"(c0));
+    return d;
+#else
+    return __builtin_fma(z, c1, c0);
+#endif
+}
 __device__ __forceinline__ void sincos(double x, double &sn, double &cs)
 {
     const double n = __builtin_rint(x * 6.36619772367581382433e-01);
     double r = __builtin_fma(-n, 1.57079632673412561417e+00, x);
     r = __builtin_fma(-n, 6.07710050650619224932e-11, r);
     const double z = r * r, z2 = z * z, z4 = z2 * z2;
-    const double s01 = __builtin_fma(z, 8.33333333332248946124e-03, -1.66666666666666324348e-01);
-    const double s23 = __builtin_fma(z, 2.75573137070700676789e-06, -1.98412698298579493134e-04);
-    const double s45 = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
+    const double s01 = fma_leaf(z, 8.33333333332248946124e-03, -1.66666666666666324348e-01);
+    const double s23 = fma_leaf(z, 2.75573137070700676789e-06, -1.98412698298579493134e-04);
+    const double s45 = fma_leaf(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
     const double ps = __builtin_fma(z4, s45, __builtin_fma(z2, s23, s01));
     const double s = __builtin_fma(r * z, ps, r);
-    const double c01 = __builtin_fma(z, -1.38888888888741095749e-03, 4.16666666666666019037e-02);
-    const double c23 = __builtin_fma(z, -2.75573143513906633035e-07, 2.48015872894767294178e-05);
-    const double c45 = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
+    const double c01 = fma_leaf(z, -1.38888888888741095749e-03, 4.16666666666666019037e-02);
+    const double c23 = fma_leaf(z, -2.75573143513906633035e-07, 2.48015872894767294178e-05);
+    const double c45 = fma_leaf(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
     const double pc = __builtin_fma(z4, c45, __builtin_fma(z2, c23, c01));
     const double c = __builtin_fma(z2, pc, __builtin_fma(z, -0.5, 1.0));
     const int q = (int)n & 3;
@@ -96,11 +118,11 @@ __device__ __forceinline__ double expneg(double x)
     r = __builtin_fma(-n, 1.90821492927058770002e-10, r);
     const double r2 = r * r, r4 = r2 * r2, r8 = r4 * r4;
     // p(r) = 1/2 + r/6 + r^2/24 + ... + r^10/12! (so that e^r = 1 + r + r^2 p)
-    const double p01 = __builtin_fma(r, 1.66666666666666666667e-01, 0.5);
-    const double p23 = __builtin_fma(r, 8.33333333333333333333e-03, 4.16666666666666666667e-02);
-    const double p45 = __builtin_fma(r, 1.98412698412698412698e-04, 1.38888888888888888889e-03);
-    const double p67 = __builtin_fma(r, 2.75573192239858906526e-06, 2.48015873015873015873e-05);
-    const double p89 = __builtin_fma(r, 2.50521083854417187751e-08, 2.75573192239858906526e-07);
+    const double p01 = __builtin_fma(r, 1.66666666666666666667e-01, 0.5); // (not fma_leaf: 0.5 is an inline constant, see there)
+    const double p23 = fma_leaf(r, 8.33333333333333333333e-03, 4.16666666666666666667e-02);
+    const double p45 = fma_leaf(r, 1.98412698412698412698e-04, 1.38888888888888888889e-03);
+    const double p67 = fma_leaf(r, 2.75573192239858906526e-06, 2.48015873015873015873e-05);
+    const double p89 = fma_leaf(r, 2.50521083854417187751e-08, 2.75573192239858906526e-07);
     const double p03 = __builtin_fma(r2, p23, p01), p47 = __builtin_fma(r2, p67, p45);
     const double p8a = __builtin_fma(r2, 2.08767569878680989792e-09, p89);
     const double p = __builtin_fma(r8, p8a, __builtin_fma(r4, p47, p03));
