@@ -1025,6 +1025,46 @@ class DeviceChains(object):
                                  round_trips=idx["round_trips"][local], occupancy=occ, cold_share=occ[:, 0] / float(T))
         return r if self.sites is not None else r[0]
 
+    def ladder_evidence(self, phase="p2", maxlag=None):
+        """record="device", tempered runs: the log-evidence of every site's ladders from the recorded rungs, straight from the
+        device store -- diagnostics.ladder_evidence on samples_dev(phase)'s likes and beta where they lie.  The hot rungs, which
+        the posterior methods leave out, are exactly the samples the marginal likelihood is estimated from: stepping stones in
+        both directions (`ss`, biased low, and `ss_rev`, biased high) and thermodynamic integration (`ti`, `ti2`), each
+        log Z(b_0) - log Z(b_min) of a ladder, Z(b) the integral of prior x L^b over the transdimensional prior -- the evidence
+        proper only for a ladder from beta = 1 down to beta = 0 (`complete`).  One dict per site (one dict without SiteTargets):
+        `ids` (the site's ladder ids), `members` (global chain numbers per ladder), `ladders` (per ladder the dict of
+        diagnostics.ladder_evidence: betas, mean, var, tau, ess, rhat, log_ratio, log_ratio_rev, ss, ss_err, ss_rev, ss_rev_err,
+        ti, ti2, ti_err, beta_min, complete), `logz` = the mean of `ss` over the site's ladders and `logz_spread` = their standard
+        deviation (ddof 1; NaN for one ladder): replicate ladders are the honest error bar, the per-ladder errors take the rung
+        series' ESS for a number of independent terms.  Saved folders hold the cold samples only: nothing of this is read from them.
+        EngineError: record="host", an untempered run, a sharded job of more than one rank (ladders are not followed across
+        ranks); and from the engine a phase in which ladder_adapt moved the betas ("change within the rows": the burn-in of an
+        adapting run -- the main phase holds them)."""
+        if self._rec is None:
+            raise EngineError("ladder_evidence() needs DeviceChains(record='device'): record='host' keeps no time-ordered store of "
+                              "the chains on the GPU, and saved folders hold the cold samples only")
+        if self.t["beta"] is None or self.ladder is None:
+            raise EngineError("ladder_evidence() of an untempered run: there are no ladders, and one temperature holds no evidence "
+                              "estimate")
+        if self.dist is not None and self.dist.is_initialized() and self.dist.get_world_size() > 1:
+            raise EngineError("ladder_evidence() does not follow ladders across ranks (world size %d)" % self.dist.get_world_size())
+        from .diagnostics import ladder_evidence
+        d = self.samples_dev(phase)
+        if not int(d["likes"].shape[0]):
+            raise EngineError("ladder_evidence(): no snapshot of phase %r yet" % (phase,))
+        with self.torch.cuda.device(self.dev):
+            ev = ladder_evidence(d["beta"], d["likes"], self.ladder, maxlag=maxlag, engine=self.engine)
+        ids = np.asarray(ev["ids"], dtype=np.int64)
+        site_of_ladder = np.array([m[0] // self.C_site for m in ev["members"]], dtype=np.int64)
+        out = []
+        for s in range(self.nsites):
+            ks = np.flatnonzero(site_of_ladder == s)
+            ss = np.array([ev["ladders"][k]["ss"] for k in ks], dtype=np.float64)
+            out.append(dict(ids=ids[ks], members=[self.chain_offset + ev["members"][k].astype(np.int64) for k in ks],
+                            ladders=[ev["ladders"][k] for k in ks], logz=float(np.mean(ss)) if ss.size else float("nan"),
+                            logz_spread=float(np.std(ss, ddof=1)) if ss.size > 1 else float("nan")))
+        return out if self.sites is not None else out[0]
+
     def _host_rows(self, phase):
         """the rows of samples() from the host snapshots of run()"""
         S = self.snap[phase]

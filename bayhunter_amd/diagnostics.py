@@ -63,9 +63,15 @@ of zf, rhat the larger; ess_bulk the ESS of z, ess_tail the smaller of the ESS o
 Stan's estimator on the UNSPLIT chains (`posterior` and ArviZ split every chain in two for the ESS as well; here only R-hat does).
 The normal scores are a host table (AS241), looked up on the device: the tables have the host's bits.
 
+The evidence of tempered runs (include/bh_engine_chain_ladder_evidence.h): ladder_holders finds, on the GPU, the chain that holds every
+rung of every ladder at every row -- hold[t][j], a sel= with one series per temperature --, and ladder_evidence forms from the
+recorded likes of the rung series the log ratios Z(b_{r-1}) / Z(b_r) of neighbouring rungs (stepping stones in both directions) and the
+thermodynamic integral, with errors from the rung series' ESS; formulas and caveats in its docstring.
+
 Not here: ranks of the cold series of tempered runs (sel=), ladders spread over ranks, chains spread over ranks.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -155,20 +161,20 @@ def _sel_table(sel, T, Cn, mem):
     return C.c_void_p(a.ctypes.data), K, (a.strides[0] // 4 if T > 1 else K), a
 
 
-def ladder_index(beta, ladder, engine=None):
-    """The cold chain of every ladder at every recorded row, and how the ladders mix (module docstring; bh_chain_ladder_index).
-    beta[t][c]: the recorded betas, float64, a numpy array or a device tensor (a strided view of the store is read where it lies);
-    ladder[c]: any integer ladder ids.  Dict of ids [K] (the sorted ladder ids, the order of sel's columns), members (per ladder
-    the positions of its chains), sel int32 [T][K] and rung int32 [T][C] (device tensors for a device beta, numpy otherwise),
-    occupancy int64 [C][R] (R = the largest ladder's size), round_trips int64 [C], moves int64 [K].  EngineError: a ladder of more
-    than 64 chains, a beta that is not finite."""
-    eng = _engine(engine)
+def _ladders(ladder):
+    """ids [K], the chains' positions among them [C] (int32), members per ladder, R of any integer ladder ids"""
     ladder = np.asarray(ladder).reshape(-1)
     ids, inv = np.unique(ladder, return_inverse=True)
     inv = np.ascontiguousarray(inv.reshape(-1), dtype=np.int32)
-    Cn, K = int(inv.size), int(ids.size)
-    members = [np.flatnonzero(inv == k) for k in range(K)]
-    R = max(len(m) for m in members) if K else 0
+    K = int(ids.size)
+    counts = np.bincount(inv, minlength=K)
+    members = np.split(np.argsort(inv, kind="stable"), np.cumsum(counts)[:-1]) if K else []      # ascending chains per ladder
+    return ids, inv, members, (int(counts.max()) if K else 0)
+
+
+def _beta_table(beta, Cn):
+    """(pointer, memspace, stream, T, ld_t, keep-alive) of the recorded betas [T][C]: float64, a numpy array or a device tensor, read
+    where it lies when its rows are contiguous (else copied once)"""
     if _is_tensor(beta):
         import torch
         if not beta.is_cuda or beta.dtype != torch.float64 or beta.dim() != 2:
@@ -190,7 +196,22 @@ def ladder_index(beta, ladder, engine=None):
         shape = beta.shape
     if T < 1 or Cn < 1 or shape[1] != Cn:
         raise ValueError("beta [T][C] and ladder [C]: T >= 1, one ladder id per chain")
+    return ptr, mem, stream, T, int(ld_t), beta
+
+
+def ladder_index(beta, ladder, engine=None):
+    """The cold chain of every ladder at every recorded row, and how the ladders mix (module docstring; bh_chain_ladder_index).
+    beta[t][c]: the recorded betas, float64, a numpy array or a device tensor (a strided view of the store is read where it lies);
+    ladder[c]: any integer ladder ids.  Dict of ids [K] (the sorted ladder ids, the order of sel's columns), members (per ladder
+    the positions of its chains), sel int32 [T][K] and rung int32 [T][C] (device tensors for a device beta, numpy otherwise),
+    occupancy int64 [C][R] (R = the largest ladder's size), round_trips int64 [C], moves int64 [K].  EngineError: a ladder of more
+    than 64 chains, a beta that is not finite."""
+    eng = _engine(engine)
+    ids, inv, members, R = _ladders(ladder)
+    Cn, K = int(inv.size), int(ids.size)
+    ptr, mem, stream, T, ld_t, beta = _beta_table(beta, Cn)
     if mem == E.DEVICE:
+        import torch
         sel = torch.full((T, K), -1, dtype=torch.int32, device=beta.device)
         rung = torch.full((T, Cn), -1, dtype=torch.int32, device=beta.device)
         psel, prung = C.c_void_p(sel.data_ptr()), C.c_void_p(rung.data_ptr())
@@ -202,6 +223,160 @@ def ladder_index(beta, ladder, engine=None):
                                             E._ptr(occ), E._ptr(trips), E._ptr(moves)))
     del beta
     return dict(ids=ids, members=members, sel=sel, rung=rung, occupancy=occ, round_trips=trips, moves=moves)
+
+
+def _hold_table(beta, mem, T, Cn):
+    """hold int32 [T][C] beside the betas: a device tensor for a device beta, numpy otherwise"""
+    if mem == E.DEVICE:
+        import torch
+        hold = torch.full((T, Cn), -1, dtype=torch.int32, device=beta.device)
+        return hold, C.c_void_p(hold.data_ptr())
+    hold = np.full((T, Cn), -1, np.int32)
+    return hold, E._ptr(hold)
+
+
+def ladder_holders(beta, ladder, engine=None):
+    """The chain that holds every rung of every ladder at every recorded row (include/bh_engine_chain_ladder_evidence.h;
+    bh_chain_ladder_holders).  beta, ladder: as in ladder_index.  Returns ids [K], members (per ladder the positions of its chains),
+    hold int32 [T][C] (a device tensor for a device beta, numpy otherwise) and rung_beta [C]: series j = start[k] + r is rung r of
+    ladder k -- the concatenated members number the series --, hold[t][j] the chain at that rung at row t, rung_beta[j] the beta
+    it holds, descending within a ladder.  hold is a sel= of chain_series_stats, chain_model_stats and chain_medians: the series
+    of every temperature, the cold ones (r = 0) among them.  EngineError: a ladder of more than 64 chains, a beta that is not
+    finite, tied betas in a ladder, betas that change within the rows."""
+    eng = _engine(engine)
+    ids, inv, members, R = _ladders(ladder)
+    Cn, K = int(inv.size), int(ids.size)
+    ptr, mem, stream, T, ld_t, beta = _beta_table(beta, Cn)
+    hold, phold = _hold_table(beta, mem, T, Cn)
+    rung_beta = np.zeros(Cn)
+    eng._check(eng._L.bh_chain_ladder_holders(eng._h, mem, stream, T, Cn, ld_t, ptr, E._ptr(inv), K, R, phold, Cn, E._ptr(rung_beta)))
+    del beta
+    return ids, members, hold, rung_beta
+
+
+EVIDENCE_SUMS = ("mx", "mn", "sf", "sf2", "sr", "sr2")
+
+
+def ladder_evidence_sums(beta, likes, ladder, engine=None):
+    """The engine call behind ladder_evidence (bh_chain_ladder_evidence): dict of ids, members, hold, rung_beta as ladder_holders
+    returns them, T, and per series j (float64 [C]) mx, mn -- the largest and smallest like of the rung's series --, sf, sf2, sr,
+    sr2 -- the sums of exp(Df (l - mx)), of its square, of exp(-Dr (l - mn)) and of its square over the series, Df / Dr the step of
+    beta to the colder / the hotter rung (0 at a ladder's ends), in the 16 strands of chain_series_stats."""
+    eng = _engine(engine)
+    ids, inv, members, R = _ladders(ladder)
+    Cn, K = int(inv.size), int(ids.size)
+    ptr, mem, stream, T, ld_t, beta = _beta_table(beta, Cn)
+    xptr, xmem, _, elem, shape, strides, keep = _table(likes)
+    if len(shape) != 2 or tuple(shape) != (T, Cn):
+        raise ValueError("likes: [T][C], the shape of beta")
+    if xmem != mem:
+        raise ValueError("beta and likes: both numpy arrays or both device tensors")
+    if mem == E.DEVICE and keep.device != beta.device:
+        raise ValueError("beta and likes lie on different devices")
+    ldx_t, ldx_c = _lds(shape, strides, 1)
+    hold, phold = _hold_table(beta, mem, T, Cn)
+    out = {k: np.zeros(Cn) for k in ("rung_beta",) + EVIDENCE_SUMS}
+    eng._check(eng._L.bh_chain_ladder_evidence(eng._h, mem, stream, T, Cn, ld_t, ptr, elem, ldx_t, ldx_c, xptr, E._ptr(inv), K, R,
+                                               phold, Cn, *[E._ptr(out[k]) for k in ("rung_beta",) + EVIDENCE_SUMS]))
+    del beta, keep
+    out.update(ids=ids, members=members, hold=hold, T=T)
+    return out
+
+
+def evidence_estimates(T, betas, sums, mean, var, ess):
+    """The estimates of one ladder of R rungs from its series' numbers, all Python floats (math.log, math.sqrt): betas [R] descending,
+    sums = dict of mx, mn, sf, sf2, sr, sr2 [R], mean, var, ess [R] of the rung series.  Formulas: ladder_evidence."""
+    R = len(betas)
+    b = [float(v) for v in betas]
+    s = {k: [float(v) for v in sums[k]] for k in EVIDENCE_SUMS}
+    U, V, N = [float(v) for v in mean], [float(v) for v in var], [float(v) for v in ess]
+    nan = float("nan")
+    n = float(T)
+
+    def log_or_nan(v):
+        return math.log(v) if v > 0.0 else nan
+
+    def root_or_nan(v):
+        return math.sqrt(v) if v >= 0.0 else nan
+
+    fwd, rev, vf, vr = [], [], 0.0, 0.0
+    for r in range(1, R):          # the pair (r - 1, r): forward from the hotter rung r, reverse from the colder rung r - 1
+        d = b[r - 1] - b[r]
+        fwd.append(log_or_nan(s["sf"][r] / n) + d * s["mx"][r])
+        rev.append(-(log_or_nan(s["sr"][r - 1] / n) - d * s["mn"][r - 1]))
+        vf += (n * s["sf2"][r] / (s["sf"][r] * s["sf"][r]) - 1.0) / N[r]
+        vr += (n * s["sr2"][r - 1] / (s["sr"][r - 1] * s["sr"][r - 1]) - 1.0) / N[r - 1]
+    ti = ti2 = 0.0
+    w = [0.0] * R
+    for r in range(1, R):
+        d = b[r - 1] - b[r]
+        ti += d * (U[r - 1] + U[r]) / 2.0
+        ti2 += d * d / 12.0 * (V[r - 1] - V[r])
+        w[r - 1] += d / 2.0
+        w[r] += d / 2.0
+    te = 0.0
+    for r in range(R):
+        if w[r] != 0.0:
+            te += w[r] * w[r] * V[r] / N[r]
+    ss, ss_rev = 0.0, 0.0
+    for v in fwd:
+        ss += v
+    for v in rev:
+        ss_rev += v
+    return dict(log_ratio=np.array(fwd, dtype=np.float64), log_ratio_rev=np.array(rev, dtype=np.float64), ss=ss, ss_err=root_or_nan(vf),
+                ss_rev=ss_rev, ss_rev_err=root_or_nan(vr), ti=ti, ti2=ti - ti2, ti_err=root_or_nan(te), beta_min=b[R - 1],
+                complete=b[R - 1] == 0.0)
+
+
+def ladder_evidence(beta, likes, ladder, maxlag=None, engine=None):
+    """The log-evidence of every tempering ladder from its recorded rungs (include/bh_engine_chain_ladder_evidence.h).
+
+    A ladder with the betas b_0 > b_1 > ... > b_{R-1} samples, at rung r, the density prior x L^b_r / Z(b_r), Z(b) the integral of
+    prior x L^b over the transdimensional prior; Z(1) is the evidence (marginal likelihood) and Z(0) = 1.  Every estimate below is
+    log Z(b_0) - log Z(b_min), b_min = b_{R-1}: the log-evidence proper only if the ladder starts at beta = 1 and ends at beta = 0
+    (`complete`; whether the sampler behaves at beta = 0 is not this function's matter).  Differences of these numbers between two
+    runs on the same data -- with and without a target, under two noise laws, vpvs fixed or free -- are log Bayes factors as far as
+    the ladders reach the same b_min.
+
+    beta [T][C] (float64) and likes [T][C] (float32 / float64): the recorded tables, numpy arrays or device tensors, strided views
+    of the store included, read where they lie as chain_series_stats reads them; ladder[c]: any integer ids.  The rung series --
+    series j = start[k] + r reads chain hold[t][j], the chain of ladder k at rung r, at row t -- come from ladder_evidence_sums;
+    their mean, variance and ESS from chain_series_stats(likes, maxlag, sel=hold) and convergence, one series each (maxlag default
+    min(T // 2, 1000)).  Returns dict of ids, members, hold, rung_beta, T, maxlag, the sums' arrays [C], and `ladders`: per ladder a
+    dict, all float64, D_r = b_{r-1} - b_r, l the rung's likes:
+        betas [R];  mean [R] = U_r = E_b_r[log L];  var [R] = V_r = P_0 / T;  tau, ess, rhat [R], ess_truncated [R] of the series
+        log_ratio [R-1]      log(Sf_r / T) + D_r mx_r = log mean_t exp(D_r l_r[t])            stepping stones from the hotter rung
+        log_ratio_rev [R-1]  -(log(Sr_{r-1} / T) - D_r mn_{r-1}) = -log mean_t exp(-D_r l_{r-1}[t])     ... from the colder rung
+        ss, ss_rev           their sums.  The forward estimate is biased low and the reverse high: the two bracket the value.
+        ss_err               sqrt(sum_r (T Sf2_r / Sf_r^2 - 1) / ess_r), ss_rev_err likewise: the relative variance of every mean
+                             with the rung series' ESS as the number of independent terms -- an approximation
+        ti                   sum_r D_r (U_{r-1} + U_r) / 2: thermodynamic integration of dlogZ/db = U, trapezoid
+        ti2                  ti - sum_r D_r^2 / 12 (V_{r-1} - V_r): its second-order correction with dU/db = V
+        ti_err               sqrt(sum_r w_r^2 V_r / ess_r), w the trapezoid weights
+        beta_min, complete = (beta_min == 0.0)
+    A ladder of one rung has empty ratios and zeros.  Saved folders hold the cold samples only: nothing of this can be read from
+    them.  EngineError: as ladder_holders, and a like that is not finite."""
+    eng = _engine(engine)
+    out = ladder_evidence_sums(beta, likes, ladder, engine=eng)
+    T, Cn = out["T"], int(out["rung_beta"].size)
+    L = min(T // 2, 1000) if maxlag is None else int(maxlag)
+    tables = chain_series_stats(likes, L, engine=eng, sel=out["hold"])
+    conv = convergence(tables, np.arange(Cn))
+    out["maxlag"], out["ladders"] = L, []
+    start = 0
+    for m in out["members"]:
+        js = range(start, start + len(m))
+        start += len(m)
+        stats = dict(mean=[conv[j]["mean"][0, 0] for j in js], var=[tables["p"][j, 0, 0] / T for j in js])
+        for k in ("tau", "ess", "rhat", "ess_truncated"):
+            stats[k] = [conv[j][k][0] for j in js]
+        d = evidence_estimates(T, out["rung_beta"][js.start:js.stop], {k: out[k][js.start:js.stop] for k in EVIDENCE_SUMS},
+                               stats["mean"], stats["var"], stats["ess"])
+        d["betas"] = out["rung_beta"][js.start:js.stop].copy()
+        for k, v in stats.items():
+            d[k] = np.array(v, dtype=bool if k == "ess_truncated" else np.float64)
+        out["ladders"].append(d)
+    return out
 
 
 def chain_series_stats(values, maxlag, engine=None, sel=None):

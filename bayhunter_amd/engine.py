@@ -246,6 +246,11 @@ def load_library():
                                             C.c_int64, vp, vp]
     for name in CHAIN_LADDER_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_chain_ladder_holders.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int64, vp, vp, C.c_int, C.c_int, vp, C.c_int64, vp]
+    L.bh_chain_ladder_evidence.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int64, vp, C.c_int, C.c_int64, C.c_int64, vp, vp,
+                                           C.c_int, C.c_int, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp]
+    for name in CHAIN_LADDER_EVIDENCE_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     L.bh_ladder_sweep_create.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(vp)]
     L.bh_ladder_sweep_run.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double]
     L.bh_ladder_sweep_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
@@ -352,6 +357,10 @@ DIAG_LAGBLOCK = 1024                # BH_DIAG_LAGBLOCK
 # row, the ladders' mixing numbers, and the sums and medians of series that read that chain (bayhunter_amd/diagnostics.py)
 CHAIN_LADDER_SYMBOLS = ("bh_chain_ladder_index", "bh_chain_diag_series_sel", "bh_chain_diag_models_sel", "bh_chain_diag_medians_sel")
 LADDER_MAXRUNGS = 64                # BH_LADDER_MAXRUNGS
+# include/bh_engine_chain_ladder_evidence.h: the chain that holds every rung of every ladder at every row, and the sums of the
+# evidence estimates over the rung series (bayhunter_amd/diagnostics.py: ladder_holders, ladder_evidence)
+CHAIN_LADDER_EVIDENCE_SYMBOLS = ("bh_chain_ladder_holders", "bh_chain_ladder_evidence")
+EVIDENCE_DROP = 512                 # BH_EVIDENCE_DROP
 # include/bh_engine_chain_ladder_sweep.h: the swap sweep of tempered chains as one kernel, with the counts per neighbouring pair of
 # rungs and the adaptation of the interior temperatures (LadderSweep below; bayhunter_amd/parallel.py: KernelExchange)
 LADDER_SWEEP_SYMBOLS = ("bh_ladder_sweep_create", "bh_ladder_sweep_run", "bh_ladder_sweep_read", "bh_ladder_sweep_destroy")
