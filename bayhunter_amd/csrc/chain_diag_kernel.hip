@@ -21,8 +21,10 @@
 //              clamped one is flagged by the first pass.  Strands, tree and ring are the bodies' own, so the bits are those of the
 //              table gathered on the host.  The builds without a selection are the bodies with the chain fixed: as before.
 // -ffp-contract=off (Makefile): no product is contracted into a sum; that is part of the contract of the header.
-#include "bh_device.h"
+#include "bh_hostkit.h"
+#include "bh_okey.h"
 #include "chain_diag_value.h"
+#include "chain_tables.h"
 #include "../../include/bh_engine_chain_diag.h"
 #include "../../include/bh_engine_chain_diag_ladders.h"
 
@@ -40,6 +42,8 @@ static_assert(BH_DIAG_LAGBLOCK + 3 * BH_DIAG_TILE <= DIAG_RING, "ring: the live 
 static_assert(BH_DIAG_LAGBLOCK == 4 * 256 && BH_DIAG_TILE == 256 && BH_DIAG_STRANDS == 16, "thread layout of the kernels");
 
 namespace {
+
+using namespace bhkit;
 
 struct DiagArgs {
     const void *x;
@@ -136,14 +140,8 @@ __device__ __forceinline__ void diag_sum_body(const Args a, const double *means,
     if (MODE == 0 && bad) atomicOr(flag, bad);
 }
 
-template <typename T, bool MODELS, int MODE>
-__global__ void __launch_bounds__(256) diag_sum_kernel(DiagArgs a, const double *means, double *out, int *flag)
-{
-    diag_sum_body<T, MODELS, MODE>(a, means, out, flag);
-}
-
-template <typename T, bool MODELS, int MODE>
-__global__ void __launch_bounds__(256) diag_sum_sel_kernel(DiagSelArgs a, const double *means, double *out, int *flag)
+template <typename T, bool MODELS, int MODE, typename Args>
+__global__ void __launch_bounds__(256) diag_sum_kernel(Args a, const double *means, double *out, int *flag)
 {
     diag_sum_body<T, MODELS, MODE>(a, means, out, flag);
 }
@@ -193,46 +191,17 @@ __device__ __forceinline__ void diag_lag_body(const Args a, const double *means,
     }
 }
 
-template <typename T, bool MODELS>
-__global__ void __launch_bounds__(256) diag_lag_kernel(DiagArgs a, const double *means, double *P)
+template <typename T, bool MODELS, typename Args>
+__global__ void __launch_bounds__(256) diag_lag_kernel(Args a, const double *means, double *P)
 {
     diag_lag_body<T, MODELS>(a, means, P);
 }
-
-template <typename T, bool MODELS>
-__global__ void __launch_bounds__(256) diag_lag_sel_kernel(DiagSelArgs a, const double *means, double *P)
-{
-    diag_lag_body<T, MODELS>(a, means, P);
-}
-
-template <typename T> struct KeyOf;
-template <> struct KeyOf<float> {
-    typedef unsigned K;
-    static __device__ __forceinline__ K key(float v)
-    {
-        const unsigned u = __float_as_uint(v);
-        return (u >> 31) ? ~u : (u | 0x80000000u);
-    }
-    static __device__ __forceinline__ double val(K k) { return (double)__uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
-};
-template <> struct KeyOf<double> {
-    typedef unsigned long long K;
-    static __device__ __forceinline__ K key(double v)
-    {
-        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-        return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-    }
-    static __device__ __forceinline__ double val(K k)
-    {
-        return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-    }
-};
 
 // out[c][2]: the values of ranks (T-1)/2 and T/2 of chain c's column
 template <typename T, typename Args>
 __device__ __forceinline__ void diag_median_body(const Args a, double *out, int *flag)
 {
-    typedef typename KeyOf<T>::K K;
+    typedef okey_t<T> K;
     __shared__ unsigned hist[256];
     __shared__ K s_prefix;
     __shared__ unsigned long long s_rank;
@@ -254,7 +223,7 @@ __device__ __forceinline__ void diag_median_body(const Args a, double *out, int 
             for (int64_t i = tid; i < Tn; i += 256) {
                 const T v = x[i * a.ld_t + (int64_t)chain_at<true>(a, c, i, bad) * a.ld_c];
                 if (r == 0 && pass == (int)sizeof(T) - 1 && !(fabs((double)v) <= 1.7976931348623157e308)) bad |= 1;
-                const K k = KeyOf<T>::key(v);
+                const K k = okey_of(v);
                 if ((k & himask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
             }
             __syncthreads();
@@ -270,112 +239,38 @@ __device__ __forceinline__ void diag_median_body(const Args a, double *out, int 
             }
             __syncthreads();
         }
-        if (tid == 0) out[2 * (size_t)c + r] = KeyOf<T>::val(s_prefix);
+        if (tid == 0) out[2 * (size_t)c + r] = okey_value(s_prefix);
         __syncthreads();
     }
     if (bad) atomicOr(flag, bad);
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) diag_median_kernel(DiagArgs a, double *out, int *flag)
+template <typename T, typename Args>
+__global__ void __launch_bounds__(256) diag_median_kernel(Args a, double *out, int *flag)
 {
     diag_median_body<T>(a, out, flag);
 }
 
-template <typename T>
-__global__ void __launch_bounds__(256) diag_median_sel_kernel(DiagSelArgs a, double *out, int *flag)
+// the bytes a host table and a host selection cover (checked: bh_chain_table_span, bh_chain_sel_span)
+size_t table_bytes(int elem_bytes, int64_t T, int C, int64_t width, int64_t ld_t, int64_t ld_c)
 {
-    diag_median_body<T>(a, out, flag);
+    return (size_t)((T - 1) * ld_t + (int64_t)(C - 1) * ld_c + width) * (size_t)elem_bytes;
 }
+size_t sel_bytes(int64_t T, int K, int64_t ld_sel) { return (size_t)((T - 1) * ld_sel + K) * sizeof(int32_t); }
 
-struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <typename U> U *as() const { return (U *)p; }
-};
-
-int dfail(bh_engine *e, int code, const std::string &what) { return bh_engine_fail_internal(e, code, what.c_str()); }
-
-#define DCHK(e, call)                                                                                       \
-    do {                                                                                                    \
-        hipError_t _he = (call);                                                                            \
-        if (_he != hipSuccess) return dfail((e), BH_EHIP, std::string(#call ": ") + hipGetErrorString(_he)); \
-    } while (0)
-
-int dalloc(bh_engine *e, Buf &b, size_t bytes)
+// the kernels of a call: without a selection (Args = DiagArgs) and gathered (DiagSelArgs)
+template <typename T, bool MODELS, int MODE, typename Args>
+void launch_sum(hipStream_t st, unsigned n, const Args &a, const double *means, double *out, int *flag)
 {
-    hipError_t he = hipMalloc(&b.p, bytes ? bytes : 8);
-    if (he != hipSuccess) { b.p = nullptr; return dfail(e, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-    return BH_OK;
+    diag_sum_kernel<T, MODELS, MODE, Args><<<dim3(n), 256, 0, st>>>(a, means, out, flag);
 }
-
-// the table on the device: the caller's pointer, or a copy of the span a host table covers
-int table_on_device(bh_engine *e, hipStream_t st, bool host, int elem_bytes, int64_t T, int C, int64_t width, int64_t ld_t,
-                    int64_t ld_c, const void *x, Buf &copy, const void **dx)
+template <typename T, bool MODELS, typename Args> void launch_lag(hipStream_t st, dim3 grid, const Args &a, const double *means, double *P)
 {
-    *dx = x;
-    if (!host) return BH_OK;
-    const size_t span = (size_t)((T - 1) * ld_t + (int64_t)(C - 1) * ld_c + width) * (size_t)elem_bytes;
-    int rc;
-    if ((rc = dalloc(e, copy, span))) return rc;
-    DCHK(e, hipMemcpyAsync(copy.p, x, span, hipMemcpyHostToDevice, st));
-    *dx = copy.p;
-    return BH_OK;
+    diag_lag_kernel<T, MODELS, Args><<<grid, 256, 0, st>>>(a, means, P);
 }
-
-bool layout_ok(int64_t T, int C, int64_t width, int64_t ld_t, int64_t ld_c)
+template <typename T, typename Args> void launch_median(hipStream_t st, unsigned n, const Args &a, double *out, int *flag)
 {
-    if (T < 1 || C < 1 || ld_t < 1 || ld_c < width) return false;
-    // the span in elements stays below 2^60
-    const long double span = (long double)(T - 1) * (long double)ld_t + (long double)(C - 1) * (long double)ld_c + (long double)width;
-    return span < 1.152921504606846976e18L;
-}
-
-// the kernels of a call: without a selection (DiagArgs) and gathered (DiagSelArgs)
-template <typename T, bool MODELS, int MODE>
-void launch_sum(hipStream_t st, unsigned n, const DiagArgs &a, const double *means, double *out, int *flag)
-{
-    diag_sum_kernel<T, MODELS, MODE><<<dim3(n), 256, 0, st>>>(a, means, out, flag);
-}
-template <typename T, bool MODELS, int MODE>
-void launch_sum(hipStream_t st, unsigned n, const DiagSelArgs &a, const double *means, double *out, int *flag)
-{
-    diag_sum_sel_kernel<T, MODELS, MODE><<<dim3(n), 256, 0, st>>>(a, means, out, flag);
-}
-template <typename T, bool MODELS> void launch_lag(hipStream_t st, dim3 grid, const DiagArgs &a, const double *means, double *P)
-{
-    diag_lag_kernel<T, MODELS><<<grid, 256, 0, st>>>(a, means, P);
-}
-template <typename T, bool MODELS> void launch_lag(hipStream_t st, dim3 grid, const DiagSelArgs &a, const double *means, double *P)
-{
-    diag_lag_sel_kernel<T, MODELS><<<grid, 256, 0, st>>>(a, means, P);
-}
-template <typename T> void launch_median(hipStream_t st, unsigned n, const DiagArgs &a, double *out, int *flag)
-{
-    diag_median_kernel<T><<<dim3(n), 256, 0, st>>>(a, out, flag);
-}
-template <typename T> void launch_median(hipStream_t st, unsigned n, const DiagSelArgs &a, double *out, int *flag)
-{
-    diag_median_sel_kernel<T><<<dim3(n), 256, 0, st>>>(a, out, flag);
-}
-
-// the selection on the device: the caller's pointer, or a copy of the span a host table covers
-int sel_on_device(bh_engine *e, hipStream_t st, bool host, int64_t T, int K, int64_t ld_sel, const int32_t *sel, Buf &copy,
-                  const int32_t **dsel)
-{
-    *dsel = sel;
-    if (!host) return BH_OK;
-    const size_t span = (size_t)((T - 1) * ld_sel + K) * sizeof(int32_t);
-    int rc;
-    if ((rc = dalloc(e, copy, span))) return rc;
-    DCHK(e, hipMemcpyAsync(copy.p, sel, span, hipMemcpyHostToDevice, st));
-    *dsel = copy.as<int32_t>();
-    return BH_OK;
-}
-
-bool sel_ok(int64_t T, int K, const int32_t *sel, int64_t ld_sel)
-{
-    return K >= 1 && sel && ld_sel >= K && (long double)(T - 1) * (long double)ld_sel + (long double)K < 1.152921504606846976e18L;
+    diag_median_kernel<T, Args><<<dim3(n), 256, 0, st>>>(a, out, flag);
 }
 
 // C: the series of the call (the chains, or the gathered series)
@@ -386,35 +281,35 @@ int launch_all(bh_engine *e, hipStream_t st, const Args &a, int C, double *x0, d
     int rc;
     const size_t nser = (size_t)C * a.Q, np = nser * (size_t)(a.L + 1);
     Buf dsum, dmean, dm2, dP, dflag;
-    if ((rc = dalloc(e, dsum, nser * 32)) || (rc = dalloc(e, dmean, nser * 24)) || (rc = dalloc(e, dm2, nser * 16)) ||
-        (rc = dalloc(e, dP, np * 8)) || (rc = dalloc(e, dflag, 8)))
+    if ((rc = alloc(e, dsum, nser * 32)) || (rc = alloc(e, dmean, nser * 24)) || (rc = alloc(e, dm2, nser * 16)) ||
+        (rc = alloc(e, dP, np * 8)) || (rc = alloc(e, dflag, 8)))
         return rc;
-    DCHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
+    BH_CHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
     launch_sum<T, MODELS, 0>(st, (unsigned)C, a, nullptr, dsum.as<double>(), dflag.as<int>());
-    DCHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     std::vector<double> hs(nser * 4), hm(nser * 3), h2(nser * 2);
     int flag = 0;
-    DCHK(e, hipMemcpyAsync(hs.data(), dsum.p, nser * 32, hipMemcpyDeviceToHost, st));
-    DCHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
-    DCHK(e, hipStreamSynchronize(st));
-    if (flag & 4) return dfail(e, BH_EINVAL, "a selection index is outside [0, C)");
-    if (flag & 2) return dfail(e, BH_EINVAL, "a model row's non-NaN values are not a non-empty prefix of even length");
-    if (flag & 1) return dfail(e, BH_EINVAL, "a value is not finite (or beyond 2^480)");
+    BH_CHK(e, hipMemcpyAsync(hs.data(), dsum.p, nser * 32, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipStreamSynchronize(st));
+    if (flag & 4) return fail(e, BH_EINVAL, "a selection index is outside [0, C)");
+    if (flag & 2) return fail(e, BH_EINVAL, "a model row's non-NaN values are not a non-empty prefix of even length");
+    if (flag & 1) return fail(e, BH_EINVAL, "a value is not finite (or beyond 2^480)");
     const int64_t h = a.T / 2;
     for (size_t i = 0; i < nser; ++i) {
         hm[3 * i] = hs[4 * i + 1] / (double)a.T;
         hm[3 * i + 1] = h ? hs[4 * i + 2] / (double)h : 0.0;
         hm[3 * i + 2] = h ? hs[4 * i + 3] / (double)h : 0.0;
     }
-    DCHK(e, hipMemcpyAsync(dmean.p, hm.data(), nser * 24, hipMemcpyHostToDevice, st));
+    BH_CHK(e, hipMemcpyAsync(dmean.p, hm.data(), nser * 24, hipMemcpyHostToDevice, st));
     launch_sum<T, MODELS, 1>(st, (unsigned)C, a, dmean.as<double>(), dm2.as<double>(), nullptr);
-    DCHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     const unsigned nblk = (unsigned)(a.L / BH_DIAG_LAGBLOCK + 1);
     launch_lag<T, MODELS>(st, dim3((unsigned)C, (unsigned)a.Q, nblk), a, dmean.as<double>(), dP.as<double>());
-    DCHK(e, hipGetLastError());
-    DCHK(e, hipMemcpyAsync(h2.data(), dm2.p, nser * 16, hipMemcpyDeviceToHost, st));
-    DCHK(e, hipMemcpyAsync(p, dP.p, np * 8, hipMemcpyDeviceToHost, st));
-    DCHK(e, hipStreamSynchronize(st));
+    BH_CHK(e, hipGetLastError());
+    BH_CHK(e, hipMemcpyAsync(h2.data(), dm2.p, nser * 16, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipMemcpyAsync(p, dP.p, np * 8, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipStreamSynchronize(st));
     for (size_t i = 0; i < nser; ++i) {
         x0[i] = hs[4 * i];
         s1[i] = hs[4 * i + 1];
@@ -443,35 +338,31 @@ int diag_run(bh_engine *e, bool models, int memspace, void *stream, int elem_byt
              double *m2a, double *m2b, double *p, bool gathered = false, int K = 0, const int32_t *sel = nullptr, int64_t ld_sel = 0)
 {
     int rc;
+    bh_chain_refusal no;
     if (!e) return BH_EINVAL;
-    if (elem_bytes != 4 && elem_bytes != 8) return dfail(e, BH_EINVAL, "the table must be float32 or float64");
-    if (!x || !x0 || !s1 || !s1a || !s1b || !m2a || !m2b || !p) return dfail(e, BH_EINVAL, "null argument");
-    if (L < 0 || L > BH_DIAG_MAXLAG) return dfail(e, BH_EINVAL, "maxlag must be 0..BH_DIAG_MAXLAG");
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(e, BH_EINVAL, "the table must be float32 or float64");
+    if (!x || !x0 || !s1 || !s1a || !s1b || !m2a || !m2b || !p) return fail(e, BH_EINVAL, "null argument");
+    if (L < 0 || L > BH_DIAG_MAXLAG) return fail(e, BH_EINVAL, "maxlag must be 0..BH_DIAG_MAXLAG");
     if (models) {
-        if (ML < 1 || ML > BH_POSTERIOR_MAXLAYERS) return dfail(e, BH_EINVAL, "row width 2*ML must be 2..64 (ML <= BH_POSTERIOR_MAXLAYERS)");
-        if (D < 0 || D > BH_DIAG_MAXDEPTHS || (D && !dep)) return dfail(e, BH_EINVAL, "depths: 0..BH_DIAG_MAXDEPTHS");
-        for (int j = 0; j < D; ++j)
-            if (!std::isfinite(dep[j]) || (j && !(dep[j] > dep[j - 1])))
-                return dfail(e, BH_EINVAL, "the depths must be finite and strictly ascending");
+        if ((no = bh_chain_model_table(ML, D, dep)).code) return fail(e, no.code, no.text);
         Q = D + 1;
     } else if (Q < 1 || Q > BH_DIAG_MAXCOLS) {
-        return dfail(e, BH_EINVAL, "columns: 1..BH_DIAG_MAXCOLS per call");
+        return fail(e, BH_EINVAL, "columns: 1..BH_DIAG_MAXCOLS per call");
     }
     const int64_t width = models ? 2 * ML : Q;
-    if (!layout_ok(T, C, width, ld_t, ld_c)) return dfail(e, BH_EINVAL, "bad T, C or leading dimensions");
-    if (gathered && !sel_ok(T, K, sel, ld_sel)) return dfail(e, BH_EINVAL, "the selection: K >= 1 series, ld_sel >= K");
-    DCHK(e, hipSetDevice(bh_engine_device_internal(e)));
-    const bool host = memspace != BH_DEVICE;
-    hipStream_t st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
+    if ((no = bh_chain_table_span(T, C, width, ld_t, ld_c)).code) return fail(e, no.code, no.text);
+    if (gathered && (no = bh_chain_sel_span(T, K, sel != nullptr, ld_sel)).code) return fail(e, no.code, no.text);
+    BH_CHK(e, hipSetDevice(bh_engine_device_internal(e)));
+    hipStream_t st = call_stream(e, memspace, stream);
     Buf copy, ddep, csel;
     DiagSelArgs a;
     a.sel = nullptr; a.ld_sel = ld_sel; a.C = C;
-    if ((rc = table_on_device(e, st, host, elem_bytes, T, C, width, ld_t, ld_c, x, copy, &a.x))) return rc;
-    if (gathered && (rc = sel_on_device(e, st, host, T, K, ld_sel, sel, csel, &a.sel))) return rc;
+    if ((rc = stage(e, st, memspace, x, table_bytes(elem_bytes, T, C, width, ld_t, ld_c), copy, &a.x))) return rc;
+    if (gathered && (rc = stage(e, st, memspace, sel, sel_bytes(T, K, ld_sel), csel, &a.sel))) return rc;
     a.T = T; a.ld_t = ld_t; a.ld_c = ld_c; a.Q = Q; a.L = L; a.ML = ML; a.D = D; a.dep = nullptr;
     if (models && D) {
-        if ((rc = dalloc(e, ddep, (size_t)D * 8))) return rc;
-        DCHK(e, hipMemcpyAsync(ddep.p, dep, (size_t)D * 8, hipMemcpyHostToDevice, st));
+        if ((rc = alloc(e, ddep, (size_t)D * 8))) return rc;
+        BH_CHK(e, hipMemcpyAsync(ddep.p, dep, (size_t)D * 8, hipMemcpyHostToDevice, st));
         a.dep = ddep.as<double>();
     }
     rc = gathered ? launch_typed(e, st, models, elem_bytes, a, K, x0, s1, s1a, s1b, m2a, m2b, p)
@@ -506,23 +397,24 @@ int median_run(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t
                double *lo, double *hi, bool gathered, int K, const int32_t *sel, int64_t ld_sel)
 {
     int rc;
+    bh_chain_refusal no;
     if (!e) return BH_EINVAL;
-    if (elem_bytes != 4 && elem_bytes != 8) return dfail(e, BH_EINVAL, "the table must be float32 or float64");
-    if (!x || !lo || !hi) return dfail(e, BH_EINVAL, "null argument");
-    if (!layout_ok(T, C, 1, ld_t, ld_c) || T >= ((int64_t)1 << 32)) return dfail(e, BH_EINVAL, "bad T, C or leading dimensions");
-    if (gathered && !sel_ok(T, K, sel, ld_sel)) return dfail(e, BH_EINVAL, "the selection: K >= 1 series, ld_sel >= K");
-    DCHK(e, hipSetDevice(bh_engine_device_internal(e)));
-    const bool host = memspace != BH_DEVICE;
-    hipStream_t st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(e, BH_EINVAL, "the table must be float32 or float64");
+    if (!x || !lo || !hi) return fail(e, BH_EINVAL, "null argument");
+    if ((no = bh_chain_table_span(T, C, 1, ld_t, ld_c)).code) return fail(e, no.code, no.text);
+    if (T >= ((int64_t)1 << 32)) return fail(e, BH_EINVAL, "bad T, C or leading dimensions");   // (the ranks are 32-bit counts)
+    if (gathered && (no = bh_chain_sel_span(T, K, sel != nullptr, ld_sel)).code) return fail(e, no.code, no.text);
+    BH_CHK(e, hipSetDevice(bh_engine_device_internal(e)));
+    hipStream_t st = call_stream(e, memspace, stream);
     Buf copy, dout, dflag, csel;
     DiagSelArgs a;
     a.sel = nullptr; a.ld_sel = ld_sel; a.C = C;
-    if ((rc = table_on_device(e, st, host, elem_bytes, T, C, 1, ld_t, ld_c, x, copy, &a.x))) return rc;
-    if (gathered && (rc = sel_on_device(e, st, host, T, K, ld_sel, sel, csel, &a.sel))) return rc;
+    if ((rc = stage(e, st, memspace, x, table_bytes(elem_bytes, T, C, 1, ld_t, ld_c), copy, &a.x))) return rc;
+    if (gathered && (rc = stage(e, st, memspace, sel, sel_bytes(T, K, ld_sel), csel, &a.sel))) return rc;
     a.T = T; a.ld_t = ld_t; a.ld_c = ld_c; a.Q = 1; a.L = 0; a.ML = 0; a.D = 0; a.dep = nullptr;
     const int nser = gathered ? K : C;
-    if ((rc = dalloc(e, dout, (size_t)nser * 16)) || (rc = dalloc(e, dflag, 8))) return rc;
-    DCHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
+    if ((rc = alloc(e, dout, (size_t)nser * 16)) || (rc = alloc(e, dflag, 8))) return rc;
+    BH_CHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
     if (gathered) {
         if (elem_bytes == 4) launch_median<float>(st, (unsigned)nser, a, dout.as<double>(), dflag.as<int>());
         else launch_median<double>(st, (unsigned)nser, a, dout.as<double>(), dflag.as<int>());
@@ -530,14 +422,14 @@ int median_run(bh_engine *e, int memspace, void *stream, int elem_bytes, int64_t
         if (elem_bytes == 4) launch_median<float>(st, (unsigned)nser, (const DiagArgs &)a, dout.as<double>(), dflag.as<int>());
         else launch_median<double>(st, (unsigned)nser, (const DiagArgs &)a, dout.as<double>(), dflag.as<int>());
     }
-    DCHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     std::vector<double> ho((size_t)nser * 2);
     int flag = 0;
-    DCHK(e, hipMemcpyAsync(ho.data(), dout.p, (size_t)nser * 16, hipMemcpyDeviceToHost, st));
-    DCHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
-    DCHK(e, hipStreamSynchronize(st));
-    if (flag & 4) return dfail(e, BH_EINVAL, "a selection index is outside [0, C)");
-    if (flag) return dfail(e, BH_EINVAL, "a value is not finite");
+    BH_CHK(e, hipMemcpyAsync(ho.data(), dout.p, (size_t)nser * 16, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipStreamSynchronize(st));
+    if (flag & 4) return fail(e, BH_EINVAL, "a selection index is outside [0, C)");
+    if (flag) return fail(e, BH_EINVAL, "a value is not finite");
     for (int c = 0; c < nser; ++c) {
         lo[c] = ho[2 * (size_t)c];
         hi[c] = ho[2 * (size_t)c + 1];

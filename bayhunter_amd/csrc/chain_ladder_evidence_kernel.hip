@@ -21,7 +21,8 @@
 //                   term at or below -512 is 0 by selection: the device library's exp is never called.
 // One stream synchronisation per BH_DEVICE call: the flags of both checking passes are read with the results.
 // -ffp-contract=off (Makefile): the FMAs of bh_libm.h are explicit, and no product is contracted into a sum.
-#include "bh_device.h"
+#include "bh_hostkit.h"
+#include "chain_tables.h"
 #define BH_HD __device__ __forceinline__
 #define BH_TAB static __device__ const
 #include "bh_libm.h"
@@ -42,6 +43,8 @@
 static_assert(BH_DIAG_STRANDS == 16 && EV_SERIES * 2 * BH_DIAG_STRANDS == 256, "thread layout of the sum kernel");
 
 namespace {
+
+using namespace bhkit;
 
 struct EvArgs {
     const double *beta;
@@ -220,27 +223,6 @@ __global__ void __launch_bounds__(256) ev_copy_hold_kernel(const int32_t *src, i
     }
 }
 
-struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <typename U> U *as() const { return (U *)p; }
-};
-
-int efail(bh_engine *e, int code, const std::string &what) { return bh_engine_fail_internal(e, code, what.c_str()); }
-
-#define ECHK(e, call)                                                                                       \
-    do {                                                                                                    \
-        hipError_t _he = (call);                                                                            \
-        if (_he != hipSuccess) return efail((e), BH_EHIP, std::string(#call ": ") + hipGetErrorString(_he)); \
-    } while (0)
-
-int ealloc(bh_engine *e, Buf &b, size_t bytes)
-{
-    hipError_t he = hipMalloc(&b.p, bytes ? bytes : 8);
-    if (he != hipSuccess) { b.p = nullptr; return efail(e, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-    return BH_OK;
-}
-
 struct EvCall {
     int memspace;
     int64_t T, ld_t;
@@ -255,7 +237,7 @@ struct EvCall {
     double *rung_beta, *mx, *mn, *sf, *sf2, *sr, *sr2;
 };
 
-int evidence_run(bh_engine *e, hipStream_t st, const EvCall &q, const std::vector<int32_t> &ladder, const std::vector<int32_t> &start,
+int evidence_run(bh_engine *e, hipStream_t st, const EvCall &q, const int32_t *ladder, const std::vector<int32_t> &start,
                  const std::vector<int32_t> &member)
 {
     int rc;
@@ -265,18 +247,11 @@ int evidence_run(bh_engine *e, hipStream_t st, const EvCall &q, const std::vecto
     const size_t n = (size_t)T * (size_t)C;
     Buf cbeta, cx, work;
     EvArgs a;
-    a.beta = q.beta; a.T = T; a.ld_t = q.ld_t; a.C = C; a.K = K; a.x = q.x; a.ldx_t = q.ldx_t; a.ldx_c = q.ldx_c;
-    if (host) {
-        const size_t span = ((size_t)(T - 1) * (size_t)q.ld_t + (size_t)C) * 8;
-        if ((rc = ealloc(e, cbeta, span))) return rc;
-        ECHK(e, hipMemcpyAsync(cbeta.p, q.beta, span, hipMemcpyHostToDevice, st));
-        a.beta = cbeta.as<double>();
-        if (q.sums) {
-            const size_t xspan = ((size_t)(T - 1) * (size_t)q.ldx_t + (size_t)(C - 1) * (size_t)q.ldx_c + 1) * (size_t)q.elem_bytes;
-            if ((rc = ealloc(e, cx, xspan))) return rc;
-            ECHK(e, hipMemcpyAsync(cx.p, q.x, xspan, hipMemcpyHostToDevice, st));
-            a.x = cx.p;
-        }
+    a.T = T; a.ld_t = q.ld_t; a.C = C; a.K = K; a.x = q.x; a.ldx_t = q.ldx_t; a.ldx_c = q.ldx_c;
+    if ((rc = stage(e, st, q.memspace, q.beta, ((size_t)(T - 1) * (size_t)q.ld_t + (size_t)C) * 8, cbeta, &a.beta))) return rc;
+    if (q.sums) {
+        const size_t xspan = ((size_t)(T - 1) * (size_t)q.ldx_t + (size_t)(C - 1) * (size_t)q.ldx_c + 1) * (size_t)q.elem_bytes;
+        if ((rc = stage(e, st, q.memspace, q.x, xspan, cx, &a.x))) return rc;
     }
     const int nby = (int)std::min<int64_t>((T + 3) / 4, EV_ROWBLOCKS);
     // one allocation: the ladders' tables, the flags of the two checking passes, the partials, the results, and the call's own hold
@@ -285,7 +260,7 @@ int evidence_run(bh_engine *e, hipStream_t st, const EvCall &q, const std::vecto
     const size_t o_lad = take((size_t)C * 4), o_start = take((size_t)(K + 1) * 4), o_mem = take((size_t)C * 4), o_edge = take((size_t)C),
                  o_flag = take(8), o_part = take((size_t)nby * 2 * C * 8), o_ext = take((size_t)C * 24), o_par = take((size_t)C * 32),
                  o_sum = take((size_t)C * 32), o_hold = take(n * 4);
-    if ((rc = ealloc(e, work, off))) return rc;
+    if ((rc = alloc(e, work, off))) return rc;
     char *w = work.as<char>();
     int *dflag = (int *)(w + o_flag);
     double *dpart = (double *)(w + o_part), *dext = (double *)(w + o_ext), *dpar = (double *)(w + o_par), *dsum = (double *)(w + o_sum);
@@ -294,19 +269,19 @@ int evidence_run(bh_engine *e, hipStream_t st, const EvCall &q, const std::vecto
         edge[start[k]] |= 1;
         edge[start[k + 1] - 1] |= 2;
     }
-    ECHK(e, hipMemcpyAsync(w + o_lad, ladder.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
-    ECHK(e, hipMemcpyAsync(w + o_start, start.data(), (size_t)(K + 1) * 4, hipMemcpyHostToDevice, st));
-    ECHK(e, hipMemcpyAsync(w + o_mem, member.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
-    ECHK(e, hipMemcpyAsync(w + o_edge, edge.data(), (size_t)C, hipMemcpyHostToDevice, st));
-    ECHK(e, hipMemsetAsync(dflag, 0, 8, st));
+    BH_CHK(e, hipMemcpyAsync(w + o_lad, ladder, (size_t)C * 4, hipMemcpyHostToDevice, st));
+    BH_CHK(e, hipMemcpyAsync(w + o_start, start.data(), (size_t)(K + 1) * 4, hipMemcpyHostToDevice, st));
+    BH_CHK(e, hipMemcpyAsync(w + o_mem, member.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
+    BH_CHK(e, hipMemcpyAsync(w + o_edge, edge.data(), (size_t)C, hipMemcpyHostToDevice, st));
+    BH_CHK(e, hipMemsetAsync(dflag, 0, 8, st));
     // hold starts as chain 0 everywhere: where tied betas leave an element without a writer, the later passes still read inside the
     // tables -- they run without waiting for the first pass's verdict, and the flags are read once, at the end
-    ECHK(e, hipMemsetAsync(w + o_hold, 0, n * 4, st));
+    BH_CHK(e, hipMemsetAsync(w + o_hold, 0, n * 4, st));
     a.ladder = (const int32_t *)(w + o_lad); a.start = (const int32_t *)(w + o_start); a.member = (const int32_t *)(w + o_mem);
     a.hold = (int32_t *)(w + o_hold);
     const unsigned nblk = (unsigned)std::min<size_t>((n + 255) / 256, 16384);     // the rest by the grid's stride
     ev_holder_kernel<<<dim3(nblk), 256, 0, st>>>(a, dflag);
-    ECHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     const dim3 grid((unsigned)((C + 63) / 64), (unsigned)nby);
     if (q.sums) {
         if (q.elem_bytes == 4) ev_extremes_kernel<float><<<grid, 256, 0, st>>>(a, dpart, dflag + 1);
@@ -317,33 +292,33 @@ int evidence_run(bh_engine *e, hipStream_t st, const EvCall &q, const std::vecto
         b.x = a.beta; b.ldx_t = a.ld_t; b.ldx_c = 1;
         ev_extremes_kernel<double><<<grid, 256, 0, st>>>(b, dpart, dflag + 1);
     }
-    ECHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     ev_extremes_finish_kernel<<<dim3((unsigned)((C + 63) / 64)), 64, 0, st>>>(a, dpart, nby, (const unsigned char *)(w + o_edge), dext, dpar);
-    ECHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     std::vector<double> ext((size_t)C * 3), sums((size_t)C * 4);
     if (q.sums) {
         const unsigned nb = (unsigned)((C + EV_SERIES - 1) / EV_SERIES);
         if (q.elem_bytes == 4) ev_sum_kernel<float><<<dim3(nb), 256, 0, st>>>(a, dpar, dsum);
         else ev_sum_kernel<double><<<dim3(nb), 256, 0, st>>>(a, dpar, dsum);
-        ECHK(e, hipGetLastError());
-        ECHK(e, hipMemcpyAsync(sums.data(), dsum, (size_t)C * 32, hipMemcpyDeviceToHost, st));
+        BH_CHK(e, hipGetLastError());
+        BH_CHK(e, hipMemcpyAsync(sums.data(), dsum, (size_t)C * 32, hipMemcpyDeviceToHost, st));
     }
     if (q.hold && !host) {      // (the kernel looks at the flags itself: a refusal leaves the caller's table as it is)
         ev_copy_hold_kernel<<<dim3(nblk), 256, 0, st>>>(a.hold, T, C, q.hold, q.ld_hold, dflag);
-        ECHK(e, hipGetLastError());
+        BH_CHK(e, hipGetLastError());
     }
     int flag[2] = {0, 0};
-    ECHK(e, hipMemcpyAsync(ext.data(), dext, (size_t)C * 24, hipMemcpyDeviceToHost, st));
-    ECHK(e, hipMemcpyAsync(flag, dflag, 8, hipMemcpyDeviceToHost, st));
-    ECHK(e, hipStreamSynchronize(st));
-    if (flag[0] & EV_BAD_BETA) return efail(e, BH_EINVAL, "a beta is not finite");
-    if (flag[0] & EV_TIE) return efail(e, BH_EINVAL, "tied betas: two chains of a ladder hold the same beta at some row");
-    if (flag[1] & EV_BAD_LIKE) return efail(e, BH_EINVAL, "a like is not finite");
+    BH_CHK(e, hipMemcpyAsync(ext.data(), dext, (size_t)C * 24, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipMemcpyAsync(flag, dflag, 8, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipStreamSynchronize(st));
+    if (flag[0] & EV_BAD_BETA) return fail(e, BH_EINVAL, "a beta is not finite");
+    if (flag[0] & EV_TIE) return fail(e, BH_EINVAL, "tied betas: two chains of a ladder hold the same beta at some row");
+    if (flag[1] & EV_BAD_LIKE) return fail(e, BH_EINVAL, "a like is not finite");
     if (flag[1] & EV_MOVED)
-        return efail(e, BH_EINVAL, "the betas of a ladder change within the rows (a phase in which the ladder adaptation moved them)");
+        return fail(e, BH_EINVAL, "the betas of a ladder change within the rows (a phase in which the ladder adaptation moved them)");
     if (q.hold && host) {
-        ECHK(e, hipMemcpy2DAsync(q.hold, (size_t)q.ld_hold * 4, a.hold, (size_t)C * 4, (size_t)C * 4, (size_t)T, hipMemcpyDeviceToHost, st));
-        ECHK(e, hipStreamSynchronize(st));
+        BH_CHK(e, hipMemcpy2DAsync(q.hold, (size_t)q.ld_hold * 4, a.hold, (size_t)C * 4, (size_t)C * 4, (size_t)T, hipMemcpyDeviceToHost, st));
+        BH_CHK(e, hipStreamSynchronize(st));
     }
     std::copy(ext.begin(), ext.begin() + C, q.rung_beta);
     if (q.sums) {
@@ -362,38 +337,23 @@ int evidence_run(bh_engine *e, hipStream_t st, const EvCall &q, const std::vecto
 int evidence_call(bh_engine *e, void *stream, const EvCall &q, const int32_t *ladder)
 {
     if (!e) return BH_EINVAL;
-    if (!q.beta || !ladder || !q.rung_beta || (!q.sums && !q.hold)) return efail(e, BH_EINVAL, "null argument");
-    if (q.sums && (!q.x || !q.mx || !q.mn || !q.sf || !q.sf2 || !q.sr || !q.sr2)) return efail(e, BH_EINVAL, "null argument");
-    if (q.sums && q.elem_bytes != 4 && q.elem_bytes != 8) return efail(e, BH_EINVAL, "the likes must be float32 or float64");
+    if (!q.beta || !ladder || !q.rung_beta || (!q.sums && !q.hold)) return fail(e, BH_EINVAL, "null argument");
+    if (q.sums && (!q.x || !q.mx || !q.mn || !q.sf || !q.sf2 || !q.sr || !q.sr2)) return fail(e, BH_EINVAL, "null argument");
+    if (q.sums && q.elem_bytes != 4 && q.elem_bytes != 8) return fail(e, BH_EINVAL, "the likes must be float32 or float64");
     const int64_t T = q.T;
     const int C = q.C, K = q.K;
     if (T < 1 || C < 1 || K < 1 || K > C || q.ld_t < C || (q.hold && q.ld_hold < C) || (q.sums && (q.ldx_t < 1 || q.ldx_c < 1)))
-        return efail(e, BH_EINVAL, "bad T, C, K or leading dimensions");
-    // the spans in elements stay below 2^40
-    const long double lim = 1099511627776.0L;
-    if ((long double)T * (long double)q.ld_t >= lim || (q.hold && (long double)T * (long double)q.ld_hold >= lim) ||
-        (q.sums && (long double)T * (long double)q.ldx_t + (long double)C * (long double)q.ldx_c >= lim))
-        return efail(e, BH_EINVAL, "bad T, C, K or leading dimensions");
-    std::vector<int32_t> lad(ladder, ladder + C), start(K + 1, 0), member(C);
-    for (int c = 0; c < C; ++c) {
-        if (lad[c] < 0 || lad[c] >= K) return efail(e, BH_EINVAL, "ladder ids must be 0..K-1");
-        ++start[lad[c] + 1];
-    }
-    int largest = 0;
-    for (int k = 0; k < K; ++k) {
-        if (!start[k + 1]) return efail(e, BH_EINVAL, "ladder ids must be 0..K-1, every id used");
-        largest = std::max(largest, (int)start[k + 1]);
-    }
-    if (largest > BH_LADDER_MAXRUNGS) return efail(e, BH_EUNSUPPORTED, "a ladder of more than BH_LADDER_MAXRUNGS chains");
-    if (q.R != largest) return efail(e, BH_EINVAL, "R must be the size of the largest ladder");
-    for (int k = 0; k < K; ++k) start[k + 1] += start[k];
-    std::vector<int32_t> fill(start.begin(), start.end() - 1);
-    for (int c = 0; c < C; ++c) member[fill[lad[c]]++] = c;
+        return fail(e, BH_EINVAL, "bad T, C, K or leading dimensions");
+    bh_chain_refusal no;
+    if ((no = bh_chain_ladder_span(T, q.ld_t, 0, 0)).code || (q.hold && (no = bh_chain_ladder_span(T, q.ld_hold, 0, 0)).code) ||
+        (q.sums && (no = bh_chain_ladder_span(T, q.ldx_t, C, q.ldx_c)).code))
+        return fail(e, no.code, no.text);
+    std::vector<int32_t> start(K + 1), member(C);
+    if ((no = bh_chain_ladder_groups(C, ladder, K, &q.R, start.data(), member.data(), nullptr)).code) return fail(e, no.code, no.text);
     hipError_t he = hipSetDevice(bh_engine_device_internal(e));
-    if (he != hipSuccess) return efail(e, BH_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
-    const bool host = q.memspace != BH_DEVICE;
-    hipStream_t st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
-    const int rc = evidence_run(e, st, q, lad, start, member);
+    if (he != hipSuccess) return fail(e, BH_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
+    hipStream_t st = call_stream(e, q.memspace, stream);
+    const int rc = evidence_run(e, st, q, ladder, start, member);
     if (rc != BH_OK) (void)hipStreamSynchronize(st);   // (the buffers go with that frame)
     return rc;
 }

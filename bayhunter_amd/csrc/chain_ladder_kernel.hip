@@ -13,7 +13,8 @@
 //                The three-state trip count is in a register, the occupancy counts in LDS ([R][64 lanes]: a lane's own column, no
 //                conflicts).
 // moves kernel : one lane per ladder walks sel in ascending t and counts the changes.
-#include "bh_device.h"
+#include "bh_hostkit.h"
+#include "chain_tables.h"
 #include "../../include/bh_engine_chain_diag_ladders.h"
 
 #include <algorithm>
@@ -22,6 +23,8 @@
 #include <vector>
 
 namespace {
+
+using namespace bhkit;
 
 struct LadderArgs {
     const double *beta;
@@ -126,87 +129,61 @@ __global__ void __launch_bounds__(64) ladder_moves_kernel(const int32_t *sel, in
     moves[k] = n;
 }
 
-struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <typename U> U *as() const { return (U *)p; }
-};
-
-int lfail(bh_engine *e, int code, const std::string &what) { return bh_engine_fail_internal(e, code, what.c_str()); }
-
-#define LCHK(e, call)                                                                                       \
-    do {                                                                                                    \
-        hipError_t _he = (call);                                                                            \
-        if (_he != hipSuccess) return lfail((e), BH_EHIP, std::string(#call ": ") + hipGetErrorString(_he)); \
-    } while (0)
-
-int lalloc(bh_engine *e, Buf &b, size_t bytes)
-{
-    hipError_t he = hipMalloc(&b.p, bytes ? bytes : 8);
-    if (he != hipSuccess) { b.p = nullptr; return lfail(e, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-    return BH_OK;
-}
-
-int ladder_run(bh_engine *e, int memspace, hipStream_t st, int64_t T, int C, int64_t ld_t, const double *beta,
-               const std::vector<int32_t> &ladder, const std::vector<int32_t> &start, const std::vector<int32_t> &member, int K, int R,
-               int32_t *sel, int64_t ld_sel, int32_t *rung, int64_t ld_rung, int64_t *occupancy, int64_t *round_trips, int64_t *moves)
+int ladder_run(bh_engine *e, int memspace, hipStream_t st, int64_t T, int C, int64_t ld_t, const double *beta, const int32_t *ladder,
+               const std::vector<int32_t> &start, const std::vector<int32_t> &member, int K, int R, int32_t *sel, int64_t ld_sel,
+               int32_t *rung, int64_t ld_rung, int64_t *occupancy, int64_t *round_trips, int64_t *moves)
 {
     int rc;
     const bool host = memspace != BH_DEVICE;
     const size_t n = (size_t)T * (size_t)C;
     Buf cbeta, dlad, dstart, dmem, dflag, dcode, dsel, drung, docc, dtrips, dmoves;
     LadderArgs a;
-    a.beta = beta; a.T = T; a.ld_t = ld_t; a.C = C; a.K = K;
-    if (host) {
-        const size_t span = ((size_t)(T - 1) * (size_t)ld_t + (size_t)C) * 8;
-        if ((rc = lalloc(e, cbeta, span))) return rc;
-        LCHK(e, hipMemcpyAsync(cbeta.p, beta, span, hipMemcpyHostToDevice, st));
-        a.beta = cbeta.as<double>();
-    }
-    if ((rc = lalloc(e, dlad, (size_t)C * 4)) || (rc = lalloc(e, dstart, (size_t)(K + 1) * 4)) || (rc = lalloc(e, dmem, (size_t)C * 4)) ||
-        (rc = lalloc(e, dflag, 8)) || (rc = lalloc(e, dcode, n)) || (rc = lalloc(e, docc, (size_t)C * R * 8)) ||
-        (rc = lalloc(e, dtrips, (size_t)C * 8)) || (rc = lalloc(e, dmoves, (size_t)K * 8)))
+    a.T = T; a.ld_t = ld_t; a.C = C; a.K = K;
+    if ((rc = stage(e, st, memspace, beta, ((size_t)(T - 1) * (size_t)ld_t + (size_t)C) * 8, cbeta, &a.beta))) return rc;
+    if ((rc = alloc(e, dlad, (size_t)C * 4)) || (rc = alloc(e, dstart, (size_t)(K + 1) * 4)) || (rc = alloc(e, dmem, (size_t)C * 4)) ||
+        (rc = alloc(e, dflag, 8)) || (rc = alloc(e, dcode, n)) || (rc = alloc(e, docc, (size_t)C * R * 8)) ||
+        (rc = alloc(e, dtrips, (size_t)C * 8)) || (rc = alloc(e, dmoves, (size_t)K * 8)))
         return rc;
-    LCHK(e, hipMemcpyAsync(dlad.p, ladder.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
-    LCHK(e, hipMemcpyAsync(dstart.p, start.data(), (size_t)(K + 1) * 4, hipMemcpyHostToDevice, st));
-    LCHK(e, hipMemcpyAsync(dmem.p, member.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
-    LCHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
+    BH_CHK(e, hipMemcpyAsync(dlad.p, ladder, (size_t)C * 4, hipMemcpyHostToDevice, st));
+    BH_CHK(e, hipMemcpyAsync(dstart.p, start.data(), (size_t)(K + 1) * 4, hipMemcpyHostToDevice, st));
+    BH_CHK(e, hipMemcpyAsync(dmem.p, member.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
+    BH_CHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
     a.ladder = dlad.as<int32_t>(); a.start = dstart.as<int32_t>(); a.member = dmem.as<int32_t>();
     const unsigned nblk = (unsigned)std::min<size_t>((n + 255) / 256, 16384);     // the rest by the grid's stride
     ladder_check_kernel<<<dim3(nblk), 256, 0, st>>>(a, dflag.as<int>());
-    LCHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     int flag = 0;
-    LCHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
-    LCHK(e, hipStreamSynchronize(st));
-    if (flag) return lfail(e, BH_EINVAL, "a beta is not finite");
+    BH_CHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipStreamSynchronize(st));
+    if (flag) return fail(e, BH_EINVAL, "a beta is not finite");
     // a host call's sel and rung: contiguous on the device, copied back row by row
     int32_t *ksel = sel, *krung = rung;
     int64_t kld_sel = ld_sel, kld_rung = ld_rung;
     if (host) {
-        if ((rc = lalloc(e, dsel, (size_t)T * K * 4))) return rc;
+        if ((rc = alloc(e, dsel, (size_t)T * K * 4))) return rc;
         ksel = dsel.as<int32_t>(); kld_sel = K;
         if (rung) {
-            if ((rc = lalloc(e, drung, n * 4))) return rc;
+            if ((rc = alloc(e, drung, n * 4))) return rc;
             krung = drung.as<int32_t>(); kld_rung = C;
         }
     }
     ladder_rung_kernel<<<dim3(nblk), 256, 0, st>>>(a, ksel, kld_sel, krung, kld_rung, dcode.as<unsigned char>());
-    LCHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     ladder_walk_kernel<<<dim3((unsigned)((C + 63) / 64)), 64, 0, st>>>(dcode.as<unsigned char>(), T, C, R, docc.as<unsigned long long>(),
                                                                       dtrips.as<unsigned long long>());
-    LCHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     ladder_moves_kernel<<<dim3((unsigned)((K + 63) / 64)), 64, 0, st>>>(ksel, kld_sel, T, K, dmoves.as<unsigned long long>());
-    LCHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     std::vector<int64_t> hocc((size_t)C * R), htrips(C), hmoves(K);
-    LCHK(e, hipMemcpyAsync(hocc.data(), docc.p, hocc.size() * 8, hipMemcpyDeviceToHost, st));
-    LCHK(e, hipMemcpyAsync(htrips.data(), dtrips.p, (size_t)C * 8, hipMemcpyDeviceToHost, st));
-    LCHK(e, hipMemcpyAsync(hmoves.data(), dmoves.p, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipMemcpyAsync(hocc.data(), docc.p, hocc.size() * 8, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipMemcpyAsync(htrips.data(), dtrips.p, (size_t)C * 8, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipMemcpyAsync(hmoves.data(), dmoves.p, (size_t)K * 8, hipMemcpyDeviceToHost, st));
     if (host) {
-        LCHK(e, hipMemcpy2DAsync(sel, (size_t)ld_sel * 4, ksel, (size_t)K * 4, (size_t)K * 4, (size_t)T, hipMemcpyDeviceToHost, st));
+        BH_CHK(e, hipMemcpy2DAsync(sel, (size_t)ld_sel * 4, ksel, (size_t)K * 4, (size_t)K * 4, (size_t)T, hipMemcpyDeviceToHost, st));
         if (rung)
-            LCHK(e, hipMemcpy2DAsync(rung, (size_t)ld_rung * 4, krung, (size_t)C * 4, (size_t)C * 4, (size_t)T, hipMemcpyDeviceToHost, st));
+            BH_CHK(e, hipMemcpy2DAsync(rung, (size_t)ld_rung * 4, krung, (size_t)C * 4, (size_t)C * 4, (size_t)T, hipMemcpyDeviceToHost, st));
     }
-    LCHK(e, hipStreamSynchronize(st));
+    BH_CHK(e, hipStreamSynchronize(st));
     std::copy(hocc.begin(), hocc.end(), occupancy);
     std::copy(htrips.begin(), htrips.end(), round_trips);
     std::copy(hmoves.begin(), hmoves.end(), moves);
@@ -222,34 +199,19 @@ int bh_chain_ladder_index(bh_engine *e, int memspace, void *stream, int64_t T, i
                           int64_t *occupancy, int64_t *round_trips, int64_t *moves)
 {
     if (!e) return BH_EINVAL;
-    if (!beta || !ladder || !sel || !occupancy || !round_trips || !moves) return lfail(e, BH_EINVAL, "null argument");
+    if (!beta || !ladder || !sel || !occupancy || !round_trips || !moves) return fail(e, BH_EINVAL, "null argument");
     if (T < 1 || C < 1 || K < 1 || K > C || ld_t < C || ld_sel < K || (rung && ld_rung < C))
-        return lfail(e, BH_EINVAL, "bad T, C, K or leading dimensions");
-    // the spans in elements stay below 2^40
-    const long double lim = 1099511627776.0L;
-    if ((long double)T * (long double)ld_t >= lim || (long double)T * (long double)ld_sel >= lim ||
-        (rung && (long double)T * (long double)ld_rung >= lim))
-        return lfail(e, BH_EINVAL, "bad T, C, K or leading dimensions");
-    std::vector<int32_t> lad(ladder, ladder + C), start(K + 1, 0), member(C);
-    for (int c = 0; c < C; ++c) {
-        if (lad[c] < 0 || lad[c] >= K) return lfail(e, BH_EINVAL, "ladder ids must be 0..K-1");
-        ++start[lad[c] + 1];
-    }
-    int largest = 0;
-    for (int k = 0; k < K; ++k) {
-        if (!start[k + 1]) return lfail(e, BH_EINVAL, "ladder ids must be 0..K-1, every id used");
-        largest = std::max(largest, (int)start[k + 1]);
-    }
-    if (largest > BH_LADDER_MAXRUNGS) return lfail(e, BH_EUNSUPPORTED, "a ladder of more than BH_LADDER_MAXRUNGS chains");
-    if (R != largest) return lfail(e, BH_EINVAL, "R must be the size of the largest ladder");
-    for (int k = 0; k < K; ++k) start[k + 1] += start[k];
-    std::vector<int32_t> fill(start.begin(), start.end() - 1);
-    for (int c = 0; c < C; ++c) member[fill[lad[c]]++] = c;
+        return fail(e, BH_EINVAL, "bad T, C, K or leading dimensions");
+    bh_chain_refusal no;
+    if ((no = bh_chain_ladder_span(T, ld_t, 0, 0)).code || (no = bh_chain_ladder_span(T, ld_sel, 0, 0)).code ||
+        (rung && (no = bh_chain_ladder_span(T, ld_rung, 0, 0)).code))
+        return fail(e, no.code, no.text);
+    std::vector<int32_t> start(K + 1), member(C);
+    if ((no = bh_chain_ladder_groups(C, ladder, K, &R, start.data(), member.data(), nullptr)).code) return fail(e, no.code, no.text);
     hipError_t he = hipSetDevice(bh_engine_device_internal(e));
-    if (he != hipSuccess) return lfail(e, BH_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
-    const bool host = memspace != BH_DEVICE;
-    hipStream_t st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
-    const int rc = ladder_run(e, memspace, st, T, C, ld_t, beta, lad, start, member, K, R, sel, ld_sel, rung, ld_rung, occupancy,
+    if (he != hipSuccess) return fail(e, BH_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(he));
+    hipStream_t st = call_stream(e, memspace, stream);
+    const int rc = ladder_run(e, memspace, st, T, C, ld_t, beta, ladder, start, member, K, R, sel, ld_sel, rung, ld_rung, occupancy,
                               round_trips, moves);
     if (rc != BH_OK) (void)hipStreamSynchronize(st);   // (the buffers go with that frame)
     return rc;

@@ -7,7 +7,8 @@
 // The two sums and the recurrence of the adaptation are serial, in ascending order (the order is the contract): every lane runs
 // them on the same LDS rows (same address in all lanes: a broadcast), so every lane holds the same bits and no result is passed on.
 // The betas are read before the first barrier and written after the last; ladders share no chain.
-#include "bh_device.h"
+#include "bh_hostkit.h"
+#include "chain_tables.h"
 #include "../../include/bh_engine_chain_ladder_sweep.h"
 
 #include <algorithm>
@@ -153,13 +154,7 @@ __global__ void __launch_bounds__(64) ladder_sweep_kernel(SweepArgs a)
     }
 }
 
-int sfail(bh_engine *e, int code, const std::string &what) { return bh_engine_fail_internal(e, code, what.c_str()); }
-
-#define SCHK(e, call)                                                                                       \
-    do {                                                                                                    \
-        hipError_t _he = (call);                                                                            \
-        if (_he != hipSuccess) return sfail((e), BH_EHIP, std::string(#call ": ") + hipGetErrorString(_he)); \
-    } while (0)
+using bhkit::fail;
 
 void release(bh_ladder_sweep *p)
 {
@@ -172,9 +167,9 @@ void release(bh_ladder_sweep *p)
 template <typename T> int zalloc(bh_engine *e, T *&p, size_t n)
 {
     hipError_t he = hipMalloc((void **)&p, n * sizeof(T));
-    if (he != hipSuccess) { p = nullptr; return sfail(e, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
+    if (he != hipSuccess) { p = nullptr; return fail(e, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
     he = hipMemset(p, 0, n * sizeof(T));
-    if (he != hipSuccess) return sfail(e, BH_EHIP, std::string("hipMemset: ") + hipGetErrorString(he));
+    if (he != hipSuccess) return fail(e, BH_EHIP, std::string("hipMemset: ") + hipGetErrorString(he));
     return BH_OK;
 }
 
@@ -185,25 +180,14 @@ extern "C" {
 int bh_ladder_sweep_create(bh_engine *e, int C, const int32_t *ladder, int K, bh_ladder_sweep **plan)
 {
     if (!e) return BH_EINVAL;
-    if (!ladder || !plan) return sfail(e, BH_EINVAL, "null argument");
-    if (C < 1 || K < 1 || K > C) return sfail(e, BH_EINVAL, "bad C or K");
-    std::vector<int32_t> start(K + 1, 0), member(C);
-    for (int c = 0; c < C; ++c) {
-        if (ladder[c] < 0 || ladder[c] >= K) return sfail(e, BH_EINVAL, "ladder ids must be 0..K-1");
-        ++start[ladder[c] + 1];
-    }
-    int largest = 0;
-    for (int k = 0; k < K; ++k) {
-        if (!start[k + 1]) return sfail(e, BH_EINVAL, "ladder ids must be 0..K-1, every id used");
-        largest = start[k + 1] > largest ? start[k + 1] : largest;
-    }
-    if (largest > BH_LADDER_MAXRUNGS) return sfail(e, BH_EUNSUPPORTED, "a ladder of more than BH_LADDER_MAXRUNGS chains");
-    for (int k = 0; k < K; ++k) start[k + 1] += start[k];
-    std::vector<int32_t> fill(start.begin(), start.end() - 1);
-    for (int c = 0; c < C; ++c) member[fill[ladder[c]]++] = c;
-    SCHK(e, hipSetDevice(bh_engine_device_internal(e)));
+    if (!ladder || !plan) return fail(e, BH_EINVAL, "null argument");
+    if (C < 1 || K < 1 || K > C) return fail(e, BH_EINVAL, "bad C or K");
+    std::vector<int32_t> start(K + 1), member(C);
+    const bh_chain_refusal no = bh_chain_ladder_groups(C, ladder, K, nullptr, start.data(), member.data(), nullptr);
+    if (no.code) return fail(e, no.code, no.text);
+    BH_CHK(e, hipSetDevice(bh_engine_device_internal(e)));
     bh_ladder_sweep *p = new (std::nothrow) bh_ladder_sweep;
-    if (!p) return sfail(e, BH_ENOMEM, "out of host memory");
+    if (!p) return fail(e, BH_ENOMEM, "out of host memory");
     p->C = C; p->K = K;
     int rc;
     if ((rc = zalloc(e, p->start, (size_t)K + 1)) || (rc = zalloc(e, p->member, (size_t)C)) ||
@@ -218,7 +202,7 @@ int bh_ladder_sweep_create(bh_engine *e, int C, const int32_t *ladder, int K, bh
     if (he == hipSuccess) he = hipDeviceSynchronize();     // (the zeros and the lists are there before any stream reads them)
     if (he != hipSuccess) {
         release(p);
-        return sfail(e, BH_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(he));
+        return fail(e, BH_EHIP, std::string("hipMemcpy: ") + hipGetErrorString(he));
     }
     *plan = p;
     return BH_OK;
@@ -228,10 +212,10 @@ int bh_ladder_sweep_run(bh_engine *e, bh_ladder_sweep *plan, void *stream, const
                         int parity, int phase, int adapt, double kappa)
 {
     if (!e) return BH_EINVAL;
-    if (!plan || !like || !beta || !logu) return sfail(e, BH_EINVAL, "null argument");
-    if ((parity != 0 && parity != 1) || (phase != 0 && phase != 1)) return sfail(e, BH_EINVAL, "parity and phase are 0 or 1");
-    if (adapt != 0 && phase == 1) return sfail(e, BH_EINVAL, "the temperatures of the main phase are frozen: adapt with phase 1");
-    SCHK(e, hipSetDevice(bh_engine_device_internal(e)));
+    if (!plan || !like || !beta || !logu) return fail(e, BH_EINVAL, "null argument");
+    if ((parity != 0 && parity != 1) || (phase != 0 && phase != 1)) return fail(e, BH_EINVAL, "parity and phase are 0 or 1");
+    if (adapt != 0 && phase == 1) return fail(e, BH_EINVAL, "the temperatures of the main phase are frozen: adapt with phase 1");
+    BH_CHK(e, hipSetDevice(bh_engine_device_internal(e)));
     hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
     SweepArgs a;
     a.C = plan->C; a.K = plan->K; a.start = plan->start; a.member = plan->member;
@@ -240,7 +224,7 @@ int bh_ladder_sweep_run(bh_engine *e, bh_ladder_sweep *plan, void *stream, const
     a.like = like; a.logu = logu; a.beta = beta;
     a.parity = parity; a.phase = phase; a.adapt = adapt; a.kappa = kappa;
     ladder_sweep_kernel<<<dim3((unsigned)plan->K), 64, 0, st>>>(a);
-    SCHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     plan->last = st;
     plan->ran = true;
     return BH_OK;
@@ -250,18 +234,18 @@ int bh_ladder_sweep_read(bh_engine *e, bh_ladder_sweep *plan, int64_t *proposed,
                          int64_t *adaptations, int64_t *skipped)
 {
     if (!e) return BH_EINVAL;
-    if (!plan) return sfail(e, BH_EINVAL, "null argument");
-    SCHK(e, hipSetDevice(bh_engine_device_internal(e)));
-    if (plan->ran) SCHK(e, hipStreamSynchronize(plan->last));
+    if (!plan) return fail(e, BH_EINVAL, "null argument");
+    BH_CHK(e, hipSetDevice(bh_engine_device_internal(e)));
+    if (plan->ran) BH_CHK(e, hipStreamSynchronize(plan->last));
     const size_t C = (size_t)plan->C, K = (size_t)plan->K;
     // into buffers of the call first: an error writes nothing to the outputs
     std::vector<int64_t> hp(2 * C), ha(2 * C), hn(K), hs(K);
     std::vector<double> hb(C);
-    SCHK(e, hipMemcpy(hp.data(), plan->proposed, 2 * C * 8, hipMemcpyDeviceToHost));
-    SCHK(e, hipMemcpy(ha.data(), plan->accepted, 2 * C * 8, hipMemcpyDeviceToHost));
-    SCHK(e, hipMemcpy(hb.data(), plan->rung_beta, C * 8, hipMemcpyDeviceToHost));
-    SCHK(e, hipMemcpy(hn.data(), plan->adaptations, K * 8, hipMemcpyDeviceToHost));
-    SCHK(e, hipMemcpy(hs.data(), plan->skipped, K * 8, hipMemcpyDeviceToHost));
+    BH_CHK(e, hipMemcpy(hp.data(), plan->proposed, 2 * C * 8, hipMemcpyDeviceToHost));
+    BH_CHK(e, hipMemcpy(ha.data(), plan->accepted, 2 * C * 8, hipMemcpyDeviceToHost));
+    BH_CHK(e, hipMemcpy(hb.data(), plan->rung_beta, C * 8, hipMemcpyDeviceToHost));
+    BH_CHK(e, hipMemcpy(hn.data(), plan->adaptations, K * 8, hipMemcpyDeviceToHost));
+    BH_CHK(e, hipMemcpy(hs.data(), plan->skipped, K * 8, hipMemcpyDeviceToHost));
     if (proposed) std::copy(hp.begin(), hp.end(), proposed);
     if (accepted) std::copy(ha.begin(), ha.end(), accepted);
     if (rung_beta) std::copy(hb.begin(), hb.end(), rung_beta);

@@ -19,8 +19,10 @@
 //   fold    : med from the two middle keys of a sorted segment, f = |v - med| -> 64-bit keys at the same positions, sorted
 //             again (8 passes), written as zf.
 // Every output is a function of integer counts: the order in which atomics land changes nothing.
-#include "bh_device.h"
+#include "bh_hostkit.h"
+#include "bh_okey.h"
 #include "chain_diag_value.h"
+#include "chain_tables.h"
 #include "../../include/bh_engine_chain_rank.h"
 
 #include <algorithm>
@@ -37,6 +39,8 @@
 static_assert(BH_RANK_RADIXBITS == 8 && RANK_TILE % 256 == 0, "a pass: 256 digits, 256 threads, tiles of whole steps");
 
 namespace {
+
+using namespace bhkit;
 
 // the pools of a call (device arrays)
 struct Pools {
@@ -55,29 +59,6 @@ struct RankArgs {
     const double *dep;          // device [D] (models)
     Pools p;
 };
-
-template <typename T> struct RankKey;
-template <> struct RankKey<float> {
-    typedef unsigned K;
-    static __device__ __forceinline__ K key(double v)
-    {
-        const unsigned u = __float_as_uint((float)v);
-        return (u >> 31) ? ~u : (u | 0x80000000u);
-    }
-};
-template <> struct RankKey<double> {
-    typedef unsigned long long K;
-    static __device__ __forceinline__ K key(double v)
-    {
-        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-        return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-    }
-};
-__device__ __forceinline__ double key_value(unsigned k) { return (double)__uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
-__device__ __forceinline__ double key_value(unsigned long long k)
-{
-    return __longlong_as_double((long long)((k >> 63) ? (k ^ 0x8000000000000000ull) : ~k));
-}
 
 // the tile of this workgroup: its segment, the positions [lo, hi) it covers and the segment's [s0, s1)
 struct Tile {
@@ -128,7 +109,7 @@ __global__ void __launch_bounds__(256) rank_check_kernel(RankArgs a, int Q, int 
 }
 
 template <typename T, bool MODELS>
-__global__ void __launch_bounds__(256) rank_extract_kernel(RankArgs a, int q, typename RankKey<T>::K *keys, unsigned *idx)
+__global__ void __launch_bounds__(256) rank_extract_kernel(RankArgs a, int q, okey_t<T> *keys, unsigned *idx)
 {
     const Tile t = tile_of(a.p, blockIdx.x);
     for (unsigned pos = t.lo + threadIdx.x; pos < t.hi; pos += 256) {
@@ -137,7 +118,7 @@ __global__ void __launch_bounds__(256) rank_extract_kernel(RankArgs a, int q, ty
         int dummy = 0;
         double v = MODELS ? diag_model_value<T, false>(row, a.ML, a.D, a.dep, q, RANK_FINITE, dummy) : (double)row[q];
         v = v == 0.0 ? 0.0 : v;      // -0.0 is +0.0
-        keys[pos] = RankKey<T>::key(v);
+        keys[pos] = okey_of((T)v);
         idx[pos] = elem;
     }
 }
@@ -293,9 +274,9 @@ __global__ void __launch_bounds__(256) rank_fold_kernel(Pools p, const K *keys, 
 {
     const Tile t = tile_of(p, blockIdx.x);
     const unsigned n = t.s1 - t.s0;
-    const double med = (key_value(keys[t.s0 + (n - 1) / 2]) + key_value(keys[t.s0 + n / 2])) * 0.5;
+    const double med = (okey_value(keys[t.s0 + (n - 1) / 2]) + okey_value(keys[t.s0 + n / 2])) * 0.5;
     for (unsigned pos = t.lo + threadIdx.x; pos < t.hi; pos += 256)
-        fkeys[pos] = RankKey<double>::key(fabs(key_value(keys[pos]) - med));
+        fkeys[pos] = okey64(fabs(okey_value(keys[pos]) - med));
 }
 
 // 0 in every output of the chains left out: one thread per (row, such chain)
@@ -312,35 +293,6 @@ __global__ void __launch_bounds__(256) rank_zero_kernel(const int *left, int nle
         if (zf) zf[at + q] = 0.0;
         if (tail) tail[2 * at + 2 * q] = tail[2 * at + 2 * q + 1] = 0.0f;
     }
-}
-
-struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-    template <typename U> U *as() const { return (U *)p; }
-};
-
-int rfail(bh_engine *e, int code, const std::string &what) { return bh_engine_fail_internal(e, code, what.c_str()); }
-
-#define RCHK(e, call)                                                                                       \
-    do {                                                                                                    \
-        hipError_t _he = (call);                                                                            \
-        if (_he != hipSuccess) return rfail((e), BH_EHIP, std::string(#call ": ") + hipGetErrorString(_he)); \
-    } while (0)
-
-int ralloc(bh_engine *e, Buf &b, size_t bytes)
-{
-    hipError_t he = hipMalloc(&b.p, bytes ? bytes : 8);
-    if (he != hipSuccess) { b.p = nullptr; return rfail(e, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-    return BH_OK;
-}
-
-template <typename U> int upload(bh_engine *e, hipStream_t st, Buf &b, const std::vector<U> &v)
-{
-    int rc;
-    if ((rc = ralloc(e, b, v.size() * sizeof(U)))) return rc;
-    if (!v.empty()) RCHK(e, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice, st));
-    return BH_OK;
 }
 
 // the scratch of one column and the sort of what lies in (k0, i0): `passes` stable passes, the result in (*kr, *ir)
@@ -371,22 +323,22 @@ int rank_all(bh_engine *e, hipStream_t st, const RankArgs &a, int q0, int nq, in
              const double *dzt, const int64_t *dzoff, const int *dleft, int nleft, double *z, double *zf, float *tail, int64_t ld_out_t,
              int64_t ld_out_c)
 {
-    typedef typename RankKey<T>::K K;
+    typedef okey_t<T> K;
     int rc;
     Buf dflag, kA, kB, iA, iB, dcounts, ddigit, sz, szf, stail;
-    if ((rc = ralloc(e, dflag, 8))) return rc;
-    RCHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
+    if ((rc = alloc(e, dflag, 8))) return rc;
+    BH_CHK(e, hipMemsetAsync(dflag.p, 0, 8, st));
     rank_check_kernel<T, MODELS><<<dim3(tiles), 256, 0, st>>>(a, Qcheck, dflag.as<int>());
-    RCHK(e, hipGetLastError());
+    BH_CHK(e, hipGetLastError());
     int flag = 0;
-    RCHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
-    RCHK(e, hipStreamSynchronize(st));
-    if (flag & 2) return rfail(e, BH_EINVAL, "a model row's non-NaN values are not a non-empty prefix of even length");
-    if (flag & 1) return rfail(e, BH_EINVAL, "a value of a kept chain is not finite");
+    BH_CHK(e, hipMemcpyAsync(&flag, dflag.p, 4, hipMemcpyDeviceToHost, st));
+    BH_CHK(e, hipStreamSynchronize(st));
+    if (flag & 2) return fail(e, BH_EINVAL, "a model row's non-NaN values are not a non-empty prefix of even length");
+    if (flag & 1) return fail(e, BH_EINVAL, "a value of a kept chain is not finite");
     if (!z && !zf && !tail) return BH_OK;
 
-    if ((rc = ralloc(e, kA, M * 8)) || (rc = ralloc(e, kB, M * 8)) || (rc = ralloc(e, iA, M * 4)) || (rc = ralloc(e, iB, M * 4)) ||
-        (rc = ralloc(e, dcounts, (size_t)tiles * 256 * 4)) || (rc = ralloc(e, ddigit, (size_t)G * 256 * 4)))
+    if ((rc = alloc(e, kA, M * 8)) || (rc = alloc(e, kB, M * 8)) || (rc = alloc(e, iA, M * 4)) || (rc = alloc(e, iB, M * 4)) ||
+        (rc = alloc(e, dcounts, (size_t)tiles * 256 * 4)) || (rc = alloc(e, ddigit, (size_t)G * 256 * 4)))
         return rc;
     // host outputs: one column at a time through [T][C] tables on the device (the chains left out stay 0 there)
     const size_t TC = (size_t)a.T * (size_t)a.C;
@@ -395,16 +347,16 @@ int rank_all(bh_engine *e, hipStream_t st, const RankArgs &a, int q0, int nq, in
     RankOut o;
     o.C = a.C; o.zt = dzt; o.zoff = dzoff;
     if (host) {
-        if (z) { if ((rc = ralloc(e, sz, TC * 8))) return rc; RCHK(e, hipMemsetAsync(sz.p, 0, TC * 8, st)); hz.resize(TC); }
-        if (zf) { if ((rc = ralloc(e, szf, TC * 8))) return rc; RCHK(e, hipMemsetAsync(szf.p, 0, TC * 8, st)); hzf.resize(TC); }
-        if (tail) { if ((rc = ralloc(e, stail, TC * 8))) return rc; RCHK(e, hipMemsetAsync(stail.p, 0, TC * 8, st)); htail.resize(TC * 2); }
+        if (z) { if ((rc = alloc(e, sz, TC * 8))) return rc; BH_CHK(e, hipMemsetAsync(sz.p, 0, TC * 8, st)); hz.resize(TC); }
+        if (zf) { if ((rc = alloc(e, szf, TC * 8))) return rc; BH_CHK(e, hipMemsetAsync(szf.p, 0, TC * 8, st)); hzf.resize(TC); }
+        if (tail) { if ((rc = alloc(e, stail, TC * 8))) return rc; BH_CHK(e, hipMemsetAsync(stail.p, 0, TC * 8, st)); htail.resize(TC * 2); }
         o.ld_t = a.C; o.ld_c = 1;
     } else {
         o.ld_t = ld_out_t; o.ld_c = ld_out_c;
         if (nleft) {
             const int64_t n = a.T * nleft;
             rank_zero_kernel<<<dim3((unsigned)((n + 255) / 256)), 256, 0, st>>>(dleft, nleft, a.T, nq, z, zf, tail, ld_out_t, ld_out_c);
-            RCHK(e, hipGetLastError());
+            BH_CHK(e, hipGetLastError());
         }
     }
     Sorter s;
@@ -436,12 +388,12 @@ int rank_all(bh_engine *e, hipStream_t st, const RankArgs &a, int q0, int nq, in
             o.q = host ? 0 : j;
             rank_write_kernel<unsigned long long><<<dim3(tiles), 256, 0, st>>>(a.p, fs, js, o);
         }
-        RCHK(e, hipGetLastError());
+        BH_CHK(e, hipGetLastError());
         if (host) {
-            if (z) RCHK(e, hipMemcpyAsync(hz.data(), sz.p, TC * 8, hipMemcpyDeviceToHost, st));
-            if (zf) RCHK(e, hipMemcpyAsync(hzf.data(), szf.p, TC * 8, hipMemcpyDeviceToHost, st));
-            if (tail) RCHK(e, hipMemcpyAsync(htail.data(), stail.p, TC * 8, hipMemcpyDeviceToHost, st));
-            RCHK(e, hipStreamSynchronize(st));
+            if (z) BH_CHK(e, hipMemcpyAsync(hz.data(), sz.p, TC * 8, hipMemcpyDeviceToHost, st));
+            if (zf) BH_CHK(e, hipMemcpyAsync(hzf.data(), szf.p, TC * 8, hipMemcpyDeviceToHost, st));
+            if (tail) BH_CHK(e, hipMemcpyAsync(htail.data(), stail.p, TC * 8, hipMemcpyDeviceToHost, st));
+            BH_CHK(e, hipStreamSynchronize(st));
             for (int64_t t = 0; t < a.T; ++t)
                 for (int c = 0; c < a.C; ++c) {
                     const size_t from = (size_t)t * (size_t)a.C + (size_t)c;
@@ -452,7 +404,7 @@ int rank_all(bh_engine *e, hipStream_t st, const RankArgs &a, int q0, int nq, in
                 }
         }
     }
-    RCHK(e, hipStreamSynchronize(st));
+    BH_CHK(e, hipStreamSynchronize(st));
     return BH_OK;
 }
 
@@ -461,35 +413,30 @@ int rank_run(bh_engine *e, bool models, int memspace, void *stream, int elem_byt
              const int64_t *zoff, double *z, double *zf, float *tail, int64_t ld_out_t, int64_t ld_out_c)
 {
     int rc;
+    bh_chain_refusal no;
     if (!e) return BH_EINVAL;
-    if (elem_bytes != 4 && elem_bytes != 8) return rfail(e, BH_EINVAL, "the table must be float32 or float64");
-    if (!x || !group) return rfail(e, BH_EINVAL, "null argument");
-    if ((z || zf) && (!zt || !zoff)) return rfail(e, BH_EINVAL, "z and zf need the table zt and its offsets zoff");
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(e, BH_EINVAL, "the table must be float32 or float64");
+    if (!x || !group) return fail(e, BH_EINVAL, "null argument");
+    if ((z || zf) && (!zt || !zoff)) return fail(e, BH_EINVAL, "z and zf need the table zt and its offsets zoff");
     if (models) {
-        if (ML < 1 || ML > BH_POSTERIOR_MAXLAYERS) return rfail(e, BH_EINVAL, "row width 2*ML must be 2..64 (ML <= BH_POSTERIOR_MAXLAYERS)");
-        if (D < 0 || D > BH_DIAG_MAXDEPTHS || (D && !dep)) return rfail(e, BH_EINVAL, "depths: 0..BH_DIAG_MAXDEPTHS");
-        for (int j = 0; j < D; ++j)
-            if (!std::isfinite(dep[j]) || (j && !(dep[j] > dep[j - 1])))
-                return rfail(e, BH_EINVAL, "the depths must be finite and strictly ascending");
-        if (q0 < 0 || nq < 1 || q0 > D || nq > D + 1 - q0) return rfail(e, BH_EINVAL, "columns: q0 .. q0 + nq - 1 within 0 .. D");
+        if ((no = bh_chain_model_table(ML, D, dep)).code) return fail(e, no.code, no.text);
+        if (q0 < 0 || nq < 1 || q0 > D || nq > D + 1 - q0) return fail(e, BH_EINVAL, "columns: q0 .. q0 + nq - 1 within 0 .. D");
     } else {
-        if (Q < 1 || Q > BH_DIAG_MAXCOLS) return rfail(e, BH_EINVAL, "columns: 1..BH_DIAG_MAXCOLS per call");
+        if (Q < 1 || Q > BH_DIAG_MAXCOLS) return fail(e, BH_EINVAL, "columns: 1..BH_DIAG_MAXCOLS per call");
         q0 = 0;
         nq = Q;
     }
     const int64_t width = models ? 2 * ML : Q;
-    if (T < 1 || C < 1 || ld_t < 1 || ld_c < width ||
-        !((long double)(T - 1) * (long double)ld_t + (long double)(C - 1) * (long double)ld_c + (long double)width < 1.152921504606846976e18L))
-        return rfail(e, BH_EINVAL, "bad T, C or leading dimensions");
-    if ((long double)T * (long double)C >= 4294967296.0L) return rfail(e, BH_EINVAL, "T * C must stay below 2^32");
+    if ((no = bh_chain_table_span(T, C, width, ld_t, ld_c)).code) return fail(e, no.code, no.text);
+    if ((long double)T * (long double)C >= 4294967296.0L) return fail(e, BH_EINVAL, "T * C must stay below 2^32");
     if ((z || zf || tail) &&
         (ld_out_t < 1 || ld_out_c < nq ||
          !((long double)(T - 1) * (long double)ld_out_t + (long double)(C - 1) * (long double)ld_out_c + (long double)nq < 5.76460752303423488e17L)))
-        return rfail(e, BH_EINVAL, "bad leading dimensions of the outputs");
-    if (G < 1 || G > C) return rfail(e, BH_EINVAL, "groups: 1 <= G <= C");
+        return fail(e, BH_EINVAL, "bad leading dimensions of the outputs");
+    if (G < 1 || G > C) return fail(e, BH_EINVAL, "groups: 1 <= G <= C");
     std::vector<int> m((size_t)G, 0), left;
     for (int c = 0; c < C; ++c) {
-        if (group[c] < -1 || group[c] >= G) return rfail(e, BH_EINVAL, "a group value outside [-1, G)");
+        if (group[c] < -1 || group[c] >= G) return fail(e, BH_EINVAL, "a group value outside [-1, G)");
         if (group[c] < 0) left.push_back(c); else ++m[(size_t)group[c]];
     }
     std::vector<unsigned> seg_base((size_t)G + 1, 0u);
@@ -497,10 +444,10 @@ int rank_run(bh_engine *e, bool models, int memspace, void *stream, int elem_byt
     std::vector<int64_t> hzoff((size_t)G, 0);
     size_t ztlen = 0;
     for (int g = 0; g < G; ++g) {
-        if (!m[(size_t)g]) return rfail(e, BH_EINVAL, "an empty group");
+        if (!m[(size_t)g]) return fail(e, BH_EINVAL, "an empty group");
         const uint64_t N = (uint64_t)m[(size_t)g] * (uint64_t)T;
         if (z || zf) {
-            if (zoff[g] < 0 || zoff[g] > ((int64_t)1 << 40)) return rfail(e, BH_EINVAL, "a zoff that does not fit (0 .. 2^40)");
+            if (zoff[g] < 0 || zoff[g] > ((int64_t)1 << 40)) return fail(e, BH_EINVAL, "a zoff that does not fit (0 .. 2^40)");
             hzoff[(size_t)g] = zoff[g];
             ztlen = std::max(ztlen, (size_t)zoff[g] + (size_t)(2 * N + 1));
         }
@@ -518,22 +465,17 @@ int rank_run(bh_engine *e, bool models, int memspace, void *stream, int elem_byt
     const size_t M = seg_base[(size_t)G];
     const unsigned tiles = (unsigned)blk_seg.size();
 
-    RCHK(e, hipSetDevice(bh_engine_device_internal(e)));
+    BH_CHK(e, hipSetDevice(bh_engine_device_internal(e)));
     const bool host = memspace != BH_DEVICE;
-    hipStream_t st = (!host && stream) ? (hipStream_t)stream : (hipStream_t)bh_engine_stream(e);
+    hipStream_t st = call_stream(e, memspace, stream);
     Buf copy, ddep, dbase, dm, dmoff, dblk0, dmember, dblkseg, dleft, dzt, dzoff;
     RankArgs a;
-    a.x = x;
-    if (host) {
-        const size_t span = (size_t)((T - 1) * ld_t + (int64_t)(C - 1) * ld_c + width) * (size_t)elem_bytes;
-        if ((rc = ralloc(e, copy, span))) return rc;
-        RCHK(e, hipMemcpyAsync(copy.p, x, span, hipMemcpyHostToDevice, st));
-        a.x = copy.p;
-    }
+    const size_t span = (size_t)((T - 1) * ld_t + (int64_t)(C - 1) * ld_c + width) * (size_t)elem_bytes;
+    if ((rc = stage(e, st, memspace, x, span, copy, &a.x))) return rc;
     a.T = T; a.ld_t = ld_t; a.ld_c = ld_c; a.C = C; a.ML = ML; a.D = D; a.dep = nullptr;
     if (models && D) {
-        if ((rc = ralloc(e, ddep, (size_t)D * 8))) return rc;
-        RCHK(e, hipMemcpyAsync(ddep.p, dep, (size_t)D * 8, hipMemcpyHostToDevice, st));
+        if ((rc = alloc(e, ddep, (size_t)D * 8))) return rc;
+        BH_CHK(e, hipMemcpyAsync(ddep.p, dep, (size_t)D * 8, hipMemcpyHostToDevice, st));
         a.dep = ddep.as<double>();
     }
     if ((rc = upload(e, st, dbase, seg_base)) || (rc = upload(e, st, dm, m)) || (rc = upload(e, st, dmoff, moff)) ||
@@ -541,8 +483,8 @@ int rank_run(bh_engine *e, bool models, int memspace, void *stream, int elem_byt
         (rc = upload(e, st, dleft, left)) || (rc = upload(e, st, dzoff, hzoff)))
         return rc;
     if (z || zf) {
-        if ((rc = ralloc(e, dzt, ztlen * 8))) return rc;
-        RCHK(e, hipMemcpyAsync(dzt.p, zt, ztlen * 8, hipMemcpyHostToDevice, st));
+        if ((rc = alloc(e, dzt, ztlen * 8))) return rc;
+        BH_CHK(e, hipMemcpyAsync(dzt.p, zt, ztlen * 8, hipMemcpyHostToDevice, st));
     }
     a.p.seg_base = dbase.as<unsigned>(); a.p.seg_m = dm.as<int>(); a.p.seg_moff = dmoff.as<int>(); a.p.seg_blk0 = dblk0.as<int>();
     a.p.member = dmember.as<int>(); a.p.blk_seg = dblkseg.as<int>();

@@ -3,7 +3,8 @@
 #ifndef BH_POSTERIOR_COMMON_H
 #define BH_POSTERIOR_COMMON_H
 
-#include "bh_device.h"
+#include "bh_hostkit.h"
+#include "bh_okey.h"
 #include "../../include/bh_engine_posterior.h"
 
 #include <climits>
@@ -40,15 +41,8 @@ __device__ inline unsigned long long agg_add(unsigned long long *ctr, int key, b
     return res;
 }
 
-__device__ __forceinline__ unsigned long long okey(double v, bool k32)
-{
-    if (k32) {
-        const unsigned u = __float_as_uint((float)v);
-        return (u >> 31) ? (unsigned long long)(~u) : (unsigned long long)(u | 0x80000000u);
-    }
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
+// the ordered key of v (bh_okey.h): of its float32 value where the column's values are float32-exact, else of the double
+__device__ __forceinline__ unsigned long long okey(double v, bool k32) { return k32 ? (unsigned long long)okey32((float)v) : okey64(v); }
 
 // exponent of the lowest set bit of v (INT_MAX for 0)
 __device__ __forceinline__ int low_bit(double v)
@@ -73,11 +67,7 @@ __device__ __forceinline__ int find_bin(const double *e, int nb, double v)
     return (v == e[nb]) ? nb - 1 : lo - 1;
 }
 
-struct Dev {
-    void *p = nullptr;
-    ~Dev() { if (p) (void)hipFree(p); }
-    template <typename U> U *as() const { return (U *)p; }
-};
+typedef bhkit::Buf Dev;
 
 // a scalar set (include/bh_engine_posterior_scalars.h): Q float64 columns over the loaded rows, val[q * nrows + r], NaN = masked
 struct ScalarSet {
@@ -126,21 +116,16 @@ struct bh_posterior {
 
 namespace bhpost {
 
-inline int pfail(bh_posterior *p, int code, const std::string &what) { return bh_engine_fail_internal(p->e, code, what.c_str()); }
+// the kit (bh_hostkit.h) through the handle's engine
+inline int pfail(bh_posterior *p, int code, const std::string &what) { return bhkit::fail(p->e, code, what); }
 
-#define PCHK(p, call)                                                                           \
-    do {                                                                                        \
-        hipError_t _he = (call);                                                                \
-        if (_he != hipSuccess) return bhpost::pfail((p), BH_EHIP, std::string(#call ": ") + hipGetErrorString(_he)); \
-    } while (0)
+#define PCHK(p, call) BH_CHK((p)->e, call)
 
+// (a buffer of the handle is allocated anew: what it held goes first)
 inline int alloc(bh_posterior *p, Dev &b, size_t bytes)
 {
     if (b.p) { (void)hipFree(b.p); b.p = nullptr; }
-    if (!bytes) bytes = 8;
-    hipError_t he = hipMalloc(&b.p, bytes);
-    if (he != hipSuccess) { b.p = nullptr; return pfail(p, BH_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(he)); }
-    return BH_OK;
+    return bhkit::alloc(p->e, b, bytes);
 }
 
 } // namespace bhpost

@@ -415,7 +415,7 @@ int bh_posterior_cov(bh_posterior *p, int D, const double *dep, int set, int Qc,
         xh[c] = 0;
         ex[c] = 1;
         if (nh[c / P] == 0) continue;
-        const double vmn = key2d(kmin[c]), vmx = key2d(kmax[c]);
+        const double vmn = okey64_value(kmin[c]), vmx = okey64_value(kmax[c]);
         if (!std::isfinite(vmn) || !std::isfinite(vmx))
             return pfail(p, BH_EINVAL, c % P < (size_t)D ? "a velocity is not finite" : "a value of a scalar column is not finite");
         if (vmn == 0.0 && vmx == 0.0) continue; // zeros only (no set bit: low is still what the memset left)

@@ -51,34 +51,15 @@ __device__ __forceinline__ int wave_min_i(int v)
     return v;
 }
 
-// the value behind a 64-bit ordered key
-inline double key2d(uint64_t k)
-{
-    const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v;
-    std::memcpy(&v, &u, 8);
-    return v;
-}
-
-// the 64-bit ordered key of the float32 value behind a 32-bit ordered key
-inline uint64_t widen_key(uint64_t k32)
-{
-    const uint32_t k = (uint32_t)k32;
-    const uint32_t u = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    float f;
-    std::memcpy(&f, &u, 4);
-    const double d = (double)f;
-    uint64_t b;
-    std::memcpy(&b, &d, 8);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+// the 64-bit ordered key of the float32 value behind a 32-bit ordered key (bh_okey.h)
+inline uint64_t widen_key(uint64_t k32) { return okey64((double)okey32_value((uint32_t)k32)); }
 
 // the fixed-point scale of a column with values, from its least and largest key and its lowest set bit: the lowest set bit,
 // raised until |X| < 2^62; x0 = the least value at that scale.  A value that is not finite is refused with the caller's text.
 inline int scale_rule(bh_posterior *p, uint64_t kmin, uint64_t kmax, int low, const char *not_finite, int32_t *scale, int64_t *x0,
                       int32_t *exact)
 {
-    const double vmn = key2d(kmin), vmx = key2d(kmax);
+    const double vmn = okey64_value(kmin), vmx = okey64_value(kmax);
     const double amax = std::max(std::fabs(vmn), std::fabs(vmx));
     if (!std::isfinite(amax)) return pfail(p, BH_EINVAL, not_finite);
     int L = 0;
