@@ -9,11 +9,11 @@ from .Targets import (ObservedData, ModeledData, Valuation, SingleTarget, JointT
                       RayleighDispersionPhase, RayleighDispersionGroup, LoveDispersionPhase,
                       LoveDispersionGroup, PReceiverFunction, SReceiverFunction, select_noise_laws)
 from .chains import ChainBatch, MCMC_Optimizer  # noqa: F401
-from .results import save_config, save_final_distribution, get_outliers, posterior_from_storage, moho_from_storage, features_from_storage, covariance_from_storage, datafits_from_storage, diagnostics_from_storage  # noqa: F401
+from .results import save_config, save_final_distribution, get_outliers, posterior_from_storage, moho_from_storage, features_from_storage, covariance_from_storage, datafits_from_storage, residuals_from_storage, diagnostics_from_storage  # noqa: F401
 from .sites import SiteTargets  # noqa: F401
 from .posterior import posterior_models, posterior_hist2d, posterior_moho, posterior_scalars, posterior_covariance, posterior_features, check_features, posterior_classes, check_classes  # noqa: F401
 
-from .datafits import posterior_datafits  # noqa: F401
+from .datafits import posterior_datafits, posterior_residuals  # noqa: F401
 from .diagnostics import chain_series_stats, chain_model_stats, convergence, outlier_chains  # noqa: F401
 
 

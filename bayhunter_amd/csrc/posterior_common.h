@@ -1,5 +1,5 @@
 // bayhunter_amd/csrc/posterior_common.h -- what posterior_kernel.hip, posterior_scalars_kernel.hip, posterior_datafit_kernel.hip,
-// posterior_features_kernel.hip and posterior_classes_kernel.hip share: the handle, its device buffers, the work items, the ordered keys and the bin rule.
+// posterior_features_kernel.hip, posterior_classes_kernel.hip and posterior_resid_kernel.hip share: the handle, its device buffers, the work items, the ordered keys and the bin rule.
 #ifndef BH_POSTERIOR_COMMON_H
 #define BH_POSTERIOR_COMMON_H
 
@@ -86,8 +86,8 @@ struct ScalarSet {
 };
 
 // the handle's slot of a set id (include/bh_engine_posterior_datafit.h: MOHO 0, USER 1, DATA 3; include/bh_engine_posterior_features.h:
-// FEATURES 4); -1: no such set
-inline int set_slot(int set) { return set == 0 ? 0 : set == 1 ? 1 : set == 3 ? 2 : set == 4 ? 3 : -1; }
+// FEATURES 4; include/bh_engine_posterior_resid.h: RESID 5); -1: no such set
+inline int set_slot(int set) { return set == 0 ? 0 : set == 1 ? 1 : set == 3 ? 2 : set == 4 ? 3 : set == 5 ? 4 : -1; }
 
 } // namespace bhpost
 
@@ -104,12 +104,23 @@ struct bh_posterior {
     bool keep_rows = false;               // bh_posterior_keep_rows: the next load keeps porig and pzd
     bool has_rows = false;                // ... and the last one did
     bhpost::Dev porig, pzd;               // the row's index in the loaded input; zd_j in the row's dtype (the scalar sets)
-    bhpost::ScalarSet sets[4];            // BH_SCALARS_MOHO, BH_SCALARS_USER, BH_SCALARS_DATA, BH_SCALARS_FEATURES (bhpost::set_slot)
+    bhpost::ScalarSet sets[5];            // BH_SCALARS_MOHO, BH_SCALARS_USER, BH_SCALARS_DATA, BH_SCALARS_FEATURES, BH_SCALARS_RESID (bhpost::set_slot)
     int data_ldy = 0;                     // bh_posterior_data_fill: the columns of the set being filled, the rows filled so far,
     int64_t data_filled = -1;             // (-1: no fill under way) and the failed rows per site
     bhpost::Dev data_failed;
     bhpost::Dev data_tab;                 // ... and its tables (ncol, the columns' target and index in it), uploaded by the call that starts it
     std::vector<int32_t> data_ncol;       // (the host copy: the following calls must bring the same table)
+    int resid_ldy = 0, resid_nt = 0, resid_L = 0;   // bh_posterior_resid_fill (include/bh_engine_posterior_resid.h): what the call that
+    int64_t resid_filled = -1;            // started the fill brought, the rows filled so far (-1: no fill under way), the failed rows
+    bhpost::Dev resid_failed;             // per site,
+    bhpost::Dev resid_tab;                // its int32 tables (ncol, every slot's first column), its float64 tables (yobs, then g
+    bhpost::Dev resid_obs;                // where given) and a host noise table's copy;
+    bhpost::Dev resid_noise;
+    std::vector<int32_t> resid_ncol;      // the host copies the following calls' tables are compared with, and the kind of the
+    std::vector<double> resid_host;       // noise table (memspace, element bytes, leading dimension)
+    bool resid_g = false;
+    int resid_nmem = 0, resid_nelem = 0;
+    int64_t resid_nld = 0;
     bhpost::Dev mantle_tab;               // bh_posterior_layers: the last mantle table on the device, and the host copy it is compared with
     std::vector<double> mantle_host;
 };

@@ -568,6 +568,7 @@ int bh_posterior_load(bh_posterior *p, int memspace, void *stream, int elem_byte
         if (ss.val.p) { (void)hipFree(ss.val.p); ss.val.p = nullptr; }
     }
     p->data_filled = -1;
+    p->resid_filled = -1;
     p->keys32 = elem_bytes == 4 || (unsigned)hc[2 * S + 1] == 0u;
     const size_t nr = (size_t)p->nrows;
     if ((rc = alloc(p, p->pn, nr * 4))) return rc;

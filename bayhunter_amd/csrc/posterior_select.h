@@ -91,7 +91,8 @@ inline int get_set(bh_posterior *p, int set, ScalarSet **out)
         return pfail(p, BH_EINVAL, slot == 0   ? "the MOHO set does not exist yet (bh_posterior_moho)"
                                    : slot == 1 ? "the USER set does not exist yet (bh_posterior_attach)"
                                    : slot == 2 ? "the DATA set does not exist yet (bh_posterior_data_fill over all rows)"
-                                               : "the FEATURES set does not exist yet (bh_posterior_features)");
+                                   : slot == 3 ? "the FEATURES set does not exist yet (bh_posterior_features)"
+                                               : "the RESID set does not exist yet (bh_posterior_resid_fill over all rows)");
     *out = &p->sets[slot];
     return BH_OK;
 }

@@ -8,6 +8,10 @@ the station's WHOLE posterior.  The rows go through bh_posterior_layers -> bh_ev
 forward batches of a fixed size; the synthetics become the scalar set DATA, whose per-site column passes are those of
 `posterior_scalars`, and bh_posterior_scalar_quantiles selects all the ranks of a column in one read per radix pass.
 
+`posterior_residuals` (include/bh_engine_posterior_resid.h) runs the same forward pass and keeps, instead of the
+synthetics, what their residuals say about the noise every row assumed -- amplitude against sigma, lag-1 correlation against corr,
+the autocorrelation function -- as the scalar set RESID; `posterior_datafits(residuals=)` forms both sets from one pass.
+
 Exactness: the layers are the reference's Model.get_vp_vs_h and rho = vp * 0.32 + 0.77 in the dtypes numpy
 computes them in; count, min, max, median and the order statistics are bit-exact functions of the synthetics; the quantiles
 are numpy.quantile(..., method="linear") of them; mean and std come from exact integer sums.
@@ -17,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import engine as E
-from .posterior import _Loaded, _keys_to_values, _mean_std, _ptr, median_of_middles
+from .posterior import _Loaded, _keys_to_values, _mean_std, _ptr, _stat_dict, median_of_middles
 from .posterior import quantile_lerp, quantile_rank, set_quantiles   # noqa: F401 (the quantile formula lives with _Loaded)
 
 DEFAULT_QUANTILES = (0.025, 0.16, 0.5, 0.84, 0.975)
@@ -27,15 +31,16 @@ DEFAULT_BATCH = 16384         # rows of one forward batch
 
 # ---- the pure parts: planner (the quantile formula: posterior.quantile_rank, quantile_lerp) --------------------------------
 
-def plan_site_groups(rows, ldy, max_bytes):
+def plan_site_groups(rows, ldy, max_bytes, extra=0):
     """Sites 0..S-1 with rows[s] rows each into consecutive groups [(s0, s1), ...] whose DATA sets (ldy * rows * 8 bytes) stay
-    within max_bytes; a site is never split, so a site that alone exceeds the budget is a group of its own."""
+    within max_bytes; a site is never split, so a site that alone exceeds the budget is a group of its own.  extra: the columns
+    of a set formed beside the DATA set (the RESID set), counted likewise; ldy may then be 0 (no DATA set)."""
     rows = [int(r) for r in rows]
-    if ldy < 1 or max_bytes < 1 or any(r < 0 for r in rows):
+    if ldy < 0 or extra < 0 or ldy + extra < 1 or max_bytes < 1 or any(r < 0 for r in rows):
         raise ValueError("ldy and max_bytes must be positive, rows non-negative")
     groups, s0, used = [], 0, 0
     for s, r in enumerate(rows):
-        need = r * ldy * 8
+        need = r * (ldy + extra) * 8
         if s > s0 and used + need > max_bytes:
             groups.append((s0, s))
             s0, used = s, 0
@@ -122,6 +127,41 @@ class _DataLoaded(_Loaded):
                                                        _ptr(ncol), _ptr(failed)))
         return failed
 
+    def resid_fill(self, stream, r0, nb, ldy, ymod, err, ncol, L, yobs, g, noise):
+        """bh_posterior_resid_fill (include/bh_engine_posterior_resid.h); noise: the tuple of _noise_rows; yobs, g: float64
+        [S, ldy], g may be None"""
+        ncol = np.ascontiguousarray(ncol, np.int32)
+        failed = np.zeros(self.S, np.int64)
+        mem, elem, nld, nptr, _ = noise
+        self.eng._check(self._L.bh_posterior_resid_fill(self._p, stream, r0, nb, ldy, C.c_void_p(ymod.data_ptr()) if ymod is not None else None,
+                                                        C.c_void_p(err.data_ptr()) if err is not None else None, ncol.shape[1],
+                                                        _ptr(ncol), int(L), _ptr(yobs), _ptr(g), mem, elem, nld, nptr, _ptr(failed)))
+        return failed
+
+
+def _noise_rows(noise, N, nt):
+    """the noise table, one row [>= 2 nt] of (corr, sigma) pairs per model row in the slot layout of samples(), as (memspace,
+    element bytes, leading dimension, pointer, the array kept alive); float32 / float64, numpy array or device tensor"""
+    if noise is None:
+        raise ValueError("noise is needed: one row of (corr, sigma) pairs per model row")
+    if _is_tensor(noise):
+        import torch
+        a = noise.reshape(N, -1) if N else noise.reshape(0, 2 * nt)
+        if a.dtype not in (torch.float32, torch.float64):
+            a = a.to(torch.float64)
+        if a.shape[1] < 2 * nt:
+            raise ValueError("noise: %d values per row, the targets need %d" % (a.shape[1], 2 * nt))
+        if N and (a.stride(1) != 1 or a.stride(0) < a.shape[1]):
+            a = a.contiguous()
+        return E.DEVICE, a.element_size(), (a.stride(0) if N > 1 else a.shape[1]), C.c_void_p(a.data_ptr()), a
+    a = np.asarray(noise)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    a = np.ascontiguousarray(a.reshape(N, -1) if N else a.reshape(0, 2 * nt))
+    if a.shape[1] < 2 * nt:
+        raise ValueError("noise: %d values per row, the targets need %d" % (a.shape[1], 2 * nt))
+    return E.HOST, a.itemsize, a.shape[1], _ptr(a), a
+
 
 class _Clock(object):
     """seconds per phase into a dict (tools/gpu_posterior_datafits_perf.py), the device drained at every lap; nothing without one"""
@@ -156,13 +196,20 @@ class _Forward(object):
             self.buf[k] = z((ML, B), torch.float64)
         torch.cuda.synchronize(dev)
 
-    def fill(self, ld, vpvs, mantle_vs, mantle_vpvs, s0, ncol, clock=None):
-        """Form the DATA set of the loaded rows; site indices of the load + s0 are the targets' sites.  Returns failed[S]."""
+    def fill(self, ld, vpvs, mantle_vs, mantle_vpvs, s0, ncol, clock=None, data=True, resid=None):
+        """Form the DATA set of the loaded rows (data), the RESID set (resid: a dict of L, yobs, g and noise, the tuple of
+        _noise_rows, for the loaded sites) or both from one forward pass; site indices of the load + s0 are the targets' sites.
+        Returns failed[S]."""
         buf, B, ML = self.buf, self.B, self.ML
         ptr = lambda k: C.c_void_p(buf[k].data_ptr())
         failed = np.zeros(ld.S, np.int64)
+        rfill = lambda r0, nb, ymod, err: ld.resid_fill(self.stream, r0, nb, self.ldy, ymod, err, ncol, resid["L"], resid["yobs"],
+                                                        resid["g"], resid["noise"])
         if ld.nrows == 0:
-            failed = ld.data_fill(self.stream, 0, 0, self.ldy, None, None, ncol)
+            if data:
+                failed = ld.data_fill(self.stream, 0, 0, self.ldy, None, None, ncol)
+            if resid is not None:
+                failed = rfill(0, 0, None, None)
         for r0, r1 in plan_batches(ld.nrows, B):
             nb = r1 - r0
             ld.layers(r0, r1, vpvs, mantle_vs, mantle_vpvs, buf, B)
@@ -174,9 +221,14 @@ class _Forward(object):
                                         ptr("logL"), ptr("misf"), ptr("err"), ymod=ptr("ymod"), stream=self.stream)
             if clock is not None:
                 clock.lap("forward")
-            failed = ld.data_fill(self.stream, r0, nb, self.ldy, buf["ymod"], buf["err"], ncol)
-            if clock is not None:
-                clock.lap("fill")
+            if data:
+                failed = ld.data_fill(self.stream, r0, nb, self.ldy, buf["ymod"], buf["err"], ncol)
+                if clock is not None:
+                    clock.lap("fill")
+            if resid is not None:
+                failed = rfill(r0, nb, buf["ymod"], buf["err"])
+                if clock is not None:
+                    clock.lap("residuals")
         return failed
 
 
@@ -232,7 +284,7 @@ def _host(a):
 
 
 def posterior_datafits(targets, models, vpvs, site=None, chain=None, misfits=None, noise=None, quantiles=DEFAULT_QUANTILES,
-                       mantle=None, engine=None, nsites=None, max_bytes=DEFAULT_MAX_BYTES):
+                       mantle=None, engine=None, nsites=None, max_bytes=DEFAULT_MAX_BYTES, residuals=None):
     """Best fits per chain and the posterior predictive band of every datum, for every site: a list of dicts (one dict where
     `targets` is a JointTarget).
 
@@ -260,13 +312,94 @@ def posterior_datafits(targets, models, vpvs, site=None, chain=None, misfits=Non
 
     The engine's search and arithmetic settings are the caller's.  With the engine's defaults (the short refinement, the fast
     arithmetic) the dispersion columns carry the documented 2e-6 relative deviation of the short refinement from the
-    reference's root search; select set_swd_search("reference") and set_swd_arith("exact") for the reference's bits."""
-    return _datafits(targets, models, vpvs, site, chain, misfits, quantiles, mantle, engine, nsites, max_bytes)
+    reference's root search; select set_swd_search("reference") and set_swd_arith("exact") for the reference's bits.
+
+    residuals: None, or a dict {"noise": ..., "maxlag": 10} (and "quantiles", default: those of this call) as posterior_residuals
+    takes them: every target's dict gains the key `residuals`, the dict posterior_residuals returns for it, formed from the same
+    forward pass.  With None nothing of it runs."""
+    return _datafits(targets, models, vpvs, site, chain, misfits, quantiles, mantle, engine, nsites, max_bytes, residuals=residuals)
+
+
+RESID_NAMES = ("bias", "rms", "sigma_ratio", "corr", "corr_excess")   # the columns of a slot before its autocorrelation function
+
+
+def posterior_residuals(targets, models, vpvs, noise, site=None, maxlag=10, quantiles=DEFAULT_QUANTILES, mantle=None, engine=None,
+                        nsites=None, max_bytes=DEFAULT_MAX_BYTES):
+    """Is the assumed noise the noise?  For every site the posterior of what the residuals of its models say about the noise law
+    the rows themselves carry: a list of dicts (one dict where `targets` is a JointTarget).  targets, models, vpvs, site, mantle,
+    engine, nsites and max_bytes as for posterior_datafits, whose forward pass this is (corr 0 and sigma 1; the likelihood is
+    discarded).  noise: one row [2 nt] per model row (float32 / float64; numpy array or device tensor), (corr, sigma) of slot t at
+    2t, 2t + 1 -- the slot layout of samples() -- read, unlike posterior_datafits', by bh_posterior_resid_fill
+    (include/bh_engine_posterior_resid.h), which forms per (row, slot) from e = ymod - yobs:
+      bias = mean e;  rms = sqrt(mean e^2), the reference's misfit;  sigma_ratio = sqrt(mean u^2) / sigma, about 1 where the noise
+      model is right;  corr, the row's own;  corr_excess = acf_1 - corr;  acf_l = sum u_i u_{i+l} / sum u_i^2 at the lags
+      l = 1 .. maxlag (at most 32), with u = e * g and g = 1 / sqrt(yerr / min yerr) where the slot's law is nocorr_scalederr,
+      else 1.
+    Every dict holds rows, failed (the rows whose forward model failed: NaN in every column) and per target reference ("rdispph",
+    "prf", ...; under missing=True the site's own targets) a dict of n, law (the one installed at the site), lags = 1 .. maxlag; for
+    each of bias, rms, sigma_ratio, corr, corr_excess a dict of count, nan, min, max, median, mean, std, quantiles [R]; acf: the same
+    keys with arrays [maxlag] and quantiles [R, maxlag]; acf_model [maxlag]: the curve the law implies at the posterior median r of
+    corr -- r^l (exp), r^(l^2) (gauss), 0 (nocorr, nocorr_scalederr); and acf_white95 = 1.96 / sqrt(n), the band a white
+    residual's acf stays in 95 % of the time.  Statistics are those of posterior_scalars on the same columns, bit for bit."""
+    return _datafits(targets, models, vpvs, site, None, None, quantiles, mantle, engine, nsites, max_bytes,
+                     residuals=dict(noise=noise, maxlag=maxlag), data=False)
+
+
+def _resid_tables(st):
+    """(yobs [S, ldy], g [S, ldy] or None, the law names [S][nt]): the observed data in the DATA set's column blocks, and
+    1 / sqrt(yerr / min yerr) where the (site, slot)'s installed law is nocorr_scalederr (the reference scales the variance by
+    that factor), 1 elsewhere; None where no slot is under that law"""
+    n = st._counts()
+    off = np.concatenate(([0], np.cumsum(n.max(axis=0)))).astype(int)
+    yobs, g, laws = np.zeros((st.nsites, off[-1])), None, []
+    for s, row in enumerate(st._slot_rows()):
+        laws.append([None if t is None else t.law() for t in row])
+        for i, t in enumerate(row):
+            if t is None:
+                continue
+            c = slice(off[i], off[i] + n[s, i])
+            yobs[s, c] = np.asarray(t.obsdata.y, dtype=float).ravel()
+            if laws[s][i] == "nocorr_scalederr":
+                if g is None:
+                    g = np.ones_like(yobs)
+                ye = np.asarray(t.obsdata.yerr, dtype=float).ravel()
+                g[s, c] = 1.0 / np.sqrt(ye / ye.min())
+    return yobs, g, laws
+
+
+def acf_model(law, r, L):
+    """the autocorrelation a noise law implies at the lags 1 .. L for the correlation r: r^l (exp), r^(l^2) (gauss), 0 (the
+    uncorrelated laws)"""
+    lags = np.arange(1, L + 1, dtype=np.float64)
+    if law == "exp":
+        return np.float64(r) ** lags
+    if law == "gauss":
+        return np.float64(r) ** (lags * lags)
+    return np.zeros(L)
+
+
+def _resid_dict(stt, qv, g, q0, L, n, law):
+    """one (site, slot)'s result from the statistics and quantiles [S, Q, R] of the RESID set; q0: the slot's first column"""
+    def col(q):
+        d = dict(count=int(stt["count"][g, q]), nan=int(stt["nan"][g, q]))
+        d.update(_stat_dict(stt, g, q))
+        d["quantiles"] = qv[g, q].copy()
+        return d
+    out = dict(n=int(n), law=law, lags=np.arange(1, L + 1))
+    for k, name in enumerate(RESID_NAMES):
+        out[name] = col(q0 + k)
+    lags = [col(q0 + E.RESID_FIXED + l) for l in range(L)]
+    out["acf"] = {k: np.array([d[k] for d in lags]) for k in ("count", "nan", "min", "max", "median", "mean", "std")}
+    out["acf"]["quantiles"] = np.ascontiguousarray(np.array([d["quantiles"] for d in lags]).reshape(L, -1).T)
+    out["acf_model"] = acf_model(law, out["corr"]["median"], L)
+    out["acf_white95"] = 1.96 / np.sqrt(n) if n else np.nan
+    return out
 
 
 def _datafits(targets, models, vpvs, site=None, chain=None, misfits=None, quantiles=DEFAULT_QUANTILES, mantle=None, engine=None,
-              nsites=None, max_bytes=DEFAULT_MAX_BYTES, batch=DEFAULT_BATCH, timing=None):
-    """posterior_datafits with the rows of a forward batch and a dict for the seconds per phase (tests, tools)"""
+              nsites=None, max_bytes=DEFAULT_MAX_BYTES, batch=DEFAULT_BATCH, timing=None, residuals=None, data=True):
+    """posterior_datafits with the rows of a forward batch and a dict for the seconds per phase (tests, tools); data=False: the
+    RESID set alone (posterior_residuals)"""
     import torch
     st, many = _as_sites(targets, engine)
     eng = st.engine
@@ -274,6 +407,26 @@ def _datafits(targets, models, vpvs, site=None, chain=None, misfits=None, quanti
     S, nt, ldy = st.nsites, st.ntargets, eng.ldy
     if ldy > E.DATAFIT_MAXCOLS:
         raise ValueError("%d data columns: at most %d (BH_DATAFIT_MAXCOLS)" % (ldy, E.DATAFIT_MAXCOLS))
+    RL = RQ = 0
+    if residuals is not None:
+        unknown = [k for k in residuals if k not in ("noise", "maxlag", "quantiles")]
+        if unknown:
+            raise ValueError("residuals: no key %r (noise, maxlag, quantiles)" % (unknown[0],))
+        RL = int(residuals.get("maxlag", 10))
+        if not 1 <= RL <= E.RESID_MAXLAG:
+            raise ValueError("maxlag: 1..%d (BH_RESID_MAXLAG)" % E.RESID_MAXLAG)
+        RQ = nt * (E.RESID_FIXED + RL)
+        if RQ > E.DATAFIT_MAXCOLS:
+            raise ValueError("%d residual columns: at most %d (BH_DATAFIT_MAXCOLS)" % (RQ, E.DATAFIT_MAXCOLS))
+        rqs = tuple(float(q) for q in residuals.get("quantiles", quantiles))
+        rnoise = residuals.get("noise")
+        if rnoise is None:
+            raise ValueError("residuals: noise is needed, one row of (corr, sigma) pairs per model row")
+        if not _is_tensor(rnoise):
+            rnoise = np.asarray(rnoise)
+        if rnoise.shape[0] != models.shape[0]:
+            raise ValueError("noise: one row per model row")
+        ryobs, rg, rlaws = _resid_tables(st)
     if nsites is not None and int(nsites) != S:
         raise ValueError("nsites=%d, the targets have %d sites" % (nsites, S))
     ncol = st._counts()
@@ -298,7 +451,7 @@ def _datafits(targets, models, vpvs, site=None, chain=None, misfits=None, quanti
         hsite = _host(site).astype(np.int64).reshape(N)
         ok = (hsite >= 0) & (hsite < S)
         per_site = np.bincount(hsite[ok], minlength=S)
-    groups = plan_site_groups(per_site, ldy, int(max_bytes))
+    groups = plan_site_groups(per_site, ldy if data else 0, int(max_bytes), extra=RQ)
     nchains = 0
     if chain is not None:
         hchain, hmis = _host(chain).reshape(N), _host(misfits).reshape(N)
@@ -312,6 +465,7 @@ def _datafits(targets, models, vpvs, site=None, chain=None, misfits=None, quanti
             whole = (s0, s1) == (0, S)
             if whole:
                 idx, gm, gv, gs, gc, gf = None, models, vpvs, site, chain, misfits
+                gn = rnoise if residuals is not None else None
             else:
                 idx = np.flatnonzero((hsite >= s0) & (hsite < s1))
                 gm, gv = _take(models, idx), _take(vpvs, idx)
@@ -320,6 +474,7 @@ def _datafits(targets, models, vpvs, site=None, chain=None, misfits=None, quanti
                     gs = torch.from_numpy(gs).to(dev)
                 gc = None if chain is None else _take(chain, idx)
                 gf = None if misfits is None else _take(misfits, idx)
+                gn = _take(rnoise, idx) if residuals is not None else None
             clock.lap("host")
             ld = _DataLoaded(gm, gs, eng, s1 - s0)
             clock.lap("load")
@@ -333,14 +488,24 @@ def _datafits(targets, models, vpvs, site=None, chain=None, misfits=None, quanti
                 if chain is not None:
                     best, pos = ld.best(nchains, gc, gf)
                     clock.lap("best")
-                failed = fw.fill(ld, vt, gmv, gmk, s0, ncol[s0:s1], clock)
-                stt = ld.scalar_stats(E.SCALARS_DATA)
-                clock.lap("statistics")
-                qv = set_quantiles(ld, E.SCALARS_DATA, stt["count"], qs) if qs else np.zeros((G, ldy, 0))
-                clock.lap("quantiles")
+                resid = None
+                if residuals is not None:
+                    resid = dict(L=RL, yobs=np.ascontiguousarray(ryobs[s0:s1]), g=None if rg is None else np.ascontiguousarray(rg[s0:s1]),
+                                 noise=_noise_rows(gn, ld.N, nt))
+                failed = fw.fill(ld, vt, gmv, gmk, s0, ncol[s0:s1], clock, data=data, resid=resid)
                 bdata = None
-                if best is not None and (pos >= 0).any():
-                    bdata = ld.gather(E.SCALARS_DATA, pos[pos >= 0], ldy)
+                if data:
+                    stt = ld.scalar_stats(E.SCALARS_DATA)
+                    clock.lap("statistics")
+                    qv = set_quantiles(ld, E.SCALARS_DATA, stt["count"], qs) if qs else np.zeros((G, ldy, 0))
+                    clock.lap("quantiles")
+                    if best is not None and (pos >= 0).any():
+                        bdata = ld.gather(E.SCALARS_DATA, pos[pos >= 0], ldy)
+                if residuals is not None:
+                    rstt = ld.scalar_stats(E.SCALARS_RESID)
+                    clock.lap("residual statistics")
+                    rqv = set_quantiles(ld, E.SCALARS_RESID, rstt["count"], rqs) if rqs else np.zeros((G, RQ, 0))
+                    clock.lap("residual quantiles")
             finally:
                 ld.close()
             clock.lap("host")
@@ -352,6 +517,12 @@ def _datafits(targets, models, vpvs, site=None, chain=None, misfits=None, quanti
                 slots = st._slot_rows()[s]
                 for t, tgt in enumerate(slots):
                     if tgt is None:
+                        continue
+                    rd = None
+                    if residuals is not None:
+                        rd = _resid_dict(rstt, rqv, g, t * (E.RESID_FIXED + RL), RL, int(ncol[s, t]), rlaws[s][t])
+                    if not data:
+                        r[tgt.ref] = rd
                         continue
                     c0, c1 = off[t], off[t] + int(ncol[s, t])
                     cnt = stt["count"][g, c0:c1]
@@ -367,6 +538,8 @@ def _datafits(targets, models, vpvs, site=None, chain=None, misfits=None, quanti
                         d["median"][j] = median_of_middles(stt["med"][g, q, 0], stt["med"][g, q, 1], n)
                         d["mean"][j], d["std"][j] = _mean_std(n, stt["sums"][g, q], stt["scale"][g, q], stt["x0"][g, q])
                     d["quantiles"] = np.ascontiguousarray(qv[g, c0:c1].T)
+                    if rd is not None:
+                        d["residuals"] = rd
                     r[tgt.ref] = d
                 if best is not None:
                     r["best"] = []

@@ -944,6 +944,20 @@ class DeviceChains(object):
                                       misfits=d["misfits"][..., -1].reshape(n), quantiles=quantiles, mantle=mantle,
                                       engine=self.engine)
 
+    def posterior_residuals(self, maxlag=10, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), phase="p2", cold_only=None, exclude_chains=()):
+        """record="device": bayhunter_amd.posterior_residuals of every site's recorded rows, straight from the device store (one
+        dict per site; one dict without SiteTargets): whether the residuals of the recorded models look like the noise each row
+        assumed -- the store's noise table [2nt] (slot layout) is read where it lies; every site's mantle rule is that of its
+        priors.  cold_only (default: True on tempered runs) and exclude_chains as in samples_dev()."""
+        from .datafits import posterior_residuals
+        d = self._posterior_rows(phase, cold_only, exclude_chains)
+        n = d["models2d"].shape[0]
+        targets = self.sites if self.sites is not None else self.targets
+        mantle = [p.get("mantle") for p in self.site_priors]
+        with self.torch.cuda.device(self.dev):
+            return posterior_residuals(targets, d["models2d"], d["vpvs"].reshape(n), d["noise"].reshape(n, 2 * self.nt), site=d["site"],
+                                       maxlag=maxlag, quantiles=quantiles, mantle=mantle, engine=self.engine)
+
     def diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_chains=None, rank=False):
         """record="device": bayhunter_amd.diagnostics of every site's chains, straight from the time-ordered views of the device
         store (one dict per site; one dict without SiteTargets): `outliers` -- the global numbers of the chains the reference's rule

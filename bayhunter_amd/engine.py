@@ -229,6 +229,10 @@ def load_library():
     L.bh_posterior_scalar_export.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int64, vp]
     for name in POSTERIOR_CLASSES_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_posterior_resid_fill.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int,
+                                          C.c_int64, vp, vp]
+    for name in POSTERIOR_RESID_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     L.bh_chain_diag_series.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int,
                                        vp, vp, vp, vp, vp, vp, vp]
     L.bh_chain_diag_models.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
@@ -345,6 +349,12 @@ POSTERIOR_CLASSES_SYMBOLS = ("bh_posterior_classes", "bh_posterior_scalar_export
 CLASSES_MAX = 16                    # BH_CLASSES_MAX
 CLASS_MAXTERMS = 64                 # BH_CLASS_MAXTERMS
 CLASS_IN, CLASS_HAS, CLASS_LACKS = 0, 1, 2   # BH_CLASS_*
+# include/bh_engine_posterior_resid.h: every row's residuals against the noise it assumed, as a scalar set
+# (bayhunter_amd/datafits.py: posterior_residuals)
+POSTERIOR_RESID_SYMBOLS = ("bh_posterior_resid_fill",)
+SCALARS_RESID = 5                   # BH_SCALARS_RESID
+RESID_MAXLAG = 32                   # BH_RESID_MAXLAG
+RESID_FIXED = 5                     # BH_RESID_FIXED
 # include/bh_engine_chain_diag.h: the sums behind split R-hat and ESS of the chains' recorded series, and the medians of the
 # outlier rule (bayhunter_amd/diagnostics.py)
 CHAIN_DIAG_SYMBOLS = ("bh_chain_diag_series", "bh_chain_diag_models", "bh_chain_diag_medians")

@@ -316,6 +316,46 @@ def station_slots(targets_per_station):
     return rows, any(t is None for row in rows for t in row)
 
 
+def residuals_from_storage(datapaths, maxlag=10, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), laws=None, engine=None):
+    """Whether the residuals of many sites' posterior models look like the noise they assumed
+    (bayhunter_amd.datafits.posterior_residuals): datapaths[s] is site s's data directory after save_final_distribution
+    (c_models.npy, c_vpvs.npy and c_noise.npy, the (corr, sigma) pairs of the station's own targets).  Targets, priors and the
+    mantle rule are those of the saved <station>_config.pkl, as for datafits_from_storage.  The file does not say which noise law
+    the sampler installed: laws, a dict target reference -> law name ("exp", "nocorr", "nocorr_scalederr") or the pair
+    ("gauss", corr) of Target.set_noise_law, names them (they decide `law`, `acf_model` and the weights of nocorr_scalederr);
+    references it leaves out count as "nocorr".  Returns one dict per site."""
+    from .datafits import posterior_residuals
+    from .sites import SiteTargets
+    S = len(datapaths)
+    per_station = [saved_targets(p) for p in datapaths]
+    for tl in per_station:
+        for t in tl:
+            law = (laws or {}).get(t.ref, "nocorr")
+            if isinstance(law, str):
+                t.set_noise_law(law)
+            else:
+                t.set_noise_law(law[0], corr=law[1])
+    slots, missing = station_slots(per_station)
+    st = SiteTargets(slots, engine=engine, per_site_x="all", per_site_rf="all", missing=missing)
+    mantle = [saved_priors(p).get("mantle") for p in datapaths]
+    bands = [np.load(op.join(p, "c_models.npy")) for p in datapaths]
+    rows, site = _stack_sites(bands)
+    vpvs = np.concatenate([np.load(op.join(p, "c_vpvs.npy")).reshape(len(b)) for p, b in zip(datapaths, bands)])
+    # every station's own (corr, sigma) pairs into the slot layout
+    refs = [next(t for t in col if t is not None).ref for col in zip(*slots)]
+    noise = np.zeros((len(rows), 2 * len(refs)))
+    noise[:, 1::2] = 1.0
+    start = 0
+    for p, b, tl in zip(datapaths, bands, per_station):
+        own = np.load(op.join(p, "c_noise.npy")).reshape(len(b), -1)
+        for k, t in enumerate(tl):
+            i = refs.index(t.ref)
+            noise[start:start + len(b), 2 * i:2 * i + 2] = own[:, 2 * k:2 * k + 2]
+        start += len(b)
+    return posterior_residuals(st, rows, vpvs, noise, site=site, maxlag=maxlag, quantiles=quantiles, mantle=mantle, engine=engine,
+                               nsites=S)
+
+
 def datafits_from_storage(datapaths, quantiles=(0.025, 0.16, 0.5, 0.84, 0.975), dev=0.05, engine=None):
     """Best data fits and posterior predictive bands of many sites (bayhunter_amd.datafits.posterior_datafits, the numbers of the
     reference's plot_bestdatafits and more): datapaths[s] is site s's data directory.  The best fits come from the main-phase
