@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "rf_plan.h"
 
 #define BH_WAVE 64
 // debug counter block of the dispersion kernels: BH_COUNTER_WORDS counters + 4 words per traced wavefront
@@ -324,10 +325,10 @@ struct RfKernelArgs {
     const double *yobs;
     double *sums;
     double *zwork; // traces beyond BH_RF_MAX_LDS: workspace [B][nsamp / 2] complex (16 bytes each) for the half-length spectra, else null
-    int lds_min;   // lower bound of the synthesis kernel's LDS request in bytes (0 = what the trace needs), see bh_engine.hip
-    int no_realc;  // experiment switch: 1 = always the general (complex-coefficient) recursion
-    int coef_small; // 1: the 96-register build of the coefficient kernel (fused call: resident beside the dispersion wavefronts)
-    int no_rot;    // experiment switch: 1 = no rotation of the bins over a workgroup's wavefronts
+    int lds_min;   // unused, 0 (the LDS request is the plan's, rf_plan.h); kept so that no kernel argument moves
+    int no_realc;  // experiment switch (RfPlan::no_realc): 1 = always the general (complex-coefficient) recursion
+    int coef_small; // unused, 0 (the coefficient kernel is the plan's); kept as lds_min
+    int no_rot;    // experiment switch (RfPlan::no_rot): 1 = no rotation of the bins over a workgroup's wavefronts
 };
 // Receiver-function parameters per site (bh_sites_set_rf, include/bh_engine_sites_rf.h): the coefficient kernels give a model of
 // site s the ray parameter p[s * ld] and near-surface velocity nsv[s * ld] instead of RfKernelArgs::p_s_per_deg / nsv (the
@@ -339,14 +340,13 @@ struct RfSiteArgs {
     const double *p, *nsv;  // device [nsites][ld], already offset to the target's column
 };
 size_t bh_rf_coef_doubles(int Lmax);
-// LDS of one workgroup of the synthesis kernel for traces of nsamp samples; a CU has 160 KB, one workgroup may use all
-constexpr size_t BH_RF_MAX_LDS = 160 * 1024;
-// Longer traces (nsamp > 16384) keep the half-length spectrum in an HBM workspace (RfKernelArgs::zwork) and run the same
-// butterflies there; the largest transform served (the second twiddle table, nsamp / 128 entries, stays in LDS)
-constexpr int BH_RF_MAX_NSAMP = 1 << 18;
-size_t bh_rf_lds_bytes(int nsamp);
-// 0, or -1 when the trace does not fit a workgroup's LDS; sites: null, or the site-indexed coefficient kernels
-int bh_launch_rf(const RfKernelArgs &a, hipStream_t stream, const RfSiteArgs *sites = nullptr);
+// The launch plan (rf_plan.h): the engine asks bh_plan_rf, refuses by the plan's code and text, sizes the coefficient record and --
+// by the plan -- the workspace, fills RfKernelArgs (the plan's switches included) and hands both to the launcher of the ask's build.
+// A launcher decides nothing: it asks for the LDS allowance where the plan says so and launches the coefficient and the synthesis
+// kernel the plan names, of its own translation unit.  BH_OK; BH_EHIP when the allowance fails (RF_REFUSE_ALLOWANCE has the text);
+// BH_EINVAL for a plan its build does not serve.  sites: null for RF_PLAIN, else the table; every build reads the base it needs.
+struct RfSiteTArgs;
+int bh_launch_rf(const RfPlan &p, const RfKernelArgs &a, const RfSiteTArgs *sites, hipStream_t stream); // RF_PLAIN, RF_SITES
 // Sites that lack a receiver-function target (bh_sites_set_missing, include/bh_engine_sites_missing.h): the builds of
 // rf_kernel_m.hip (rf_kernel.hip compiled with BH_RF_MISSING).  n[s * ld] is the sample count of site s for the target (0 or the
 // descriptor's): the coefficient stage marks the record of a model whose site has none ABSENT (rec[3] = 2, distinct from bad = 1),
@@ -354,24 +354,18 @@ int bh_launch_rf(const RfKernelArgs &a, hipStream_t stream, const RfSiteArgs *si
 struct RfSiteMArgs : RfSiteArgs {
     const int32_t *n; // device [nsites][ld], already offset to the target's column
 };
-int bh_launch_rf_m(const RfKernelArgs &a, hipStream_t stream, const RfSiteMArgs &sites);
+int bh_launch_rf_m(const RfPlan &p, const RfKernelArgs &a, const RfSiteTArgs *sites, hipStream_t stream); // RF_MISSING
 // Sites with their own receiver-function time axis and Gauss filter (bh_sites_set_rf_axis, include/bh_engine_sites_rf_axis.h): the
 // builds of rf_kernel_t.hip (rf_kernel.hip compiled with BH_RF_SITEAXIS on top of BH_RF_MISSING).  A workgroup of the synthesis
 // kernel is one model: it reads its model's site and that site's record, and runs the transform of the site's own length with the
 // site's own sampling, shift, filter width and cut; the site's n samples (RfSiteMArgs::n) are followed by zeros up to the column's
-// capacity RfKernelArgs::nkeep.  logm and jcut are formed on the host with bh_launch_rf's expressions (bh_rf_axis_record).
-struct RfAxisRec {
-    double fsamp, tshift, gauss;
-    int32_t nsamp, logm, jcut; // jcut: the first bin not formed, nsamp / 2 + 1 where the filter keeps them all (the rf_no_cut switch overrides it at launch)
-    int32_t pad;
-};
+// capacity RfKernelArgs::nkeep.  The site's record (RfAxisRec, rf_plan.h) carries logm and jcut, formed on the host by the function the
+// plan forms the shared axis's with (bh_rf_axis_cut).
 struct RfSiteTArgs : RfSiteMArgs {
     const RfAxisRec *axis; // device [nsites][ld], already offset to the target's column
-    int nsamp_max;         // the largest nsamp of the column: the LDS of every workgroup
+    int nsamp_max;         // the largest nsamp of the column: the LDS of every workgroup (RfAsk::nsamp)
 };
-RfAxisRec bh_rf_axis_record(int nsamp, double fsamp, double tshift, double gauss);
-// -1 when nsamp_max does not fit a workgroup's LDS (the table is refused beyond 16384 samples before it gets here)
-int bh_launch_rf_t(const RfKernelArgs &a, hipStream_t stream, const RfSiteTArgs &sites);
+int bh_launch_rf_t(const RfPlan &p, const RfKernelArgs &a, const RfSiteTArgs *sites, hipStream_t stream); // RF_SITEAXIS
 // bh_probe_math ops 11-16: the synthesis kernel's own elementary functions (include/bh_engine_debug.h); -1 for another op
 int bh_launch_rf_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 // bh_probe_math ops 17-23 and bh_probe_swd_secular: the dispersion kernels' fast arithmetic (swd_fa_probe.hip = swd_lean.hip built with

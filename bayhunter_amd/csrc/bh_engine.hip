@@ -200,7 +200,7 @@ struct bh_engine {
     hipStream_t aux2 = nullptr;            // second dispersion target of a lane-per-model call runs here, beside the first
     hipEvent_t ev_fork2 = nullptr, ev_join2 = nullptr;
     bool overlap_rf = true;                // BH_NO_OVERLAP env turns it off (A/B testing)
-    int rf_lds_beside_swd = 40 * 1024;     // BH_RF_LDS_BESIDE env (bytes; experiment switch), see rf_place
+    int rf_lds_beside_swd = 40 * 1024;     // BH_RF_LDS_BESIDE env (bytes; experiment switch), see bh_plan_rf
     // co-resident receiver function (the start gate: plan_eval, gate_need): the dispersion kernel counts its started workgroups here
     unsigned *started = nullptr;           // device word (signal memory where available), cumulative over launches
     unsigned started_expected = 0;         // value after every launch enqueued so far has started
@@ -820,30 +820,6 @@ unsigned gate_need(const SwdLaunchInfo &s)
     return s.workgroups < resident ? s.workgroups : resident;
 }
 
-// Where the workgroups of a receiver-function launch go: RfKernelArgs::lds_min and coef_small.
-struct RfPlace {
-    int lds_min = 0, coef_small = 0;
-};
-
-// The placement of a receiver-function launch.  beside_swd: it runs on the second stream of a forked call; gated: behind the
-// start gate (the gate was wanted, the dispersion launch had workgroups and bh_tuning.h rf_keep_floor is 0).
-//   Beside a dispersion launch (fused call, second stream): the synthesis workgroups must not take wave slots before
-// the dispersion kernel's wavefronts are resident -- that kernel counts on all of them being co-resident (one round
-// of wavefronts; displaced ones wait for a whole lifetime: 3.6 -> 7 ms measured when the 17.7 KB workgroups of
-// round 3 slipped into the 18 KB of LDS the dispersion wavefronts leave free on a CU).  Asking for more LDS than
-// that remainder keeps them out of CUs whose dispersion wavefronts are still running, as in round 2 (40 KB).
-// (with the start gate of plan_eval in force the LDS floor is not needed: RF workgroups are dispatched
-// after every dispersion wavefront is resident and only take what finished wavefronts have freed)
-RfPlace rf_place(bool beside_swd, bool gated, const BhTuning &tun, int rf_lds_beside_swd)
-{
-    RfPlace w;
-    if (!beside_swd) return w;
-    // (bh_tuning.h rf_lds_gated: LDS floor of the synthesis workgroups of a GATED fused call -- fewer of them per CU at a time)
-    w.lds_min = !gated ? rf_lds_beside_swd : (tun.rf_lds_gated > 0 ? tun.rf_lds_gated : 0);
-    w.coef_small = (gated && tun.rf_coef_big == 0) ? 1 : 0;
-    return w;
-}
-
 // The group kernel's launch of a call planned by plan_swd (BH_KERNEL_GROUP)
 SwdGroupPlan plan_group(const bh_engine *e, const SwdPlan &p, int B, int Lmax, const SwdJob *jobs)
 {
@@ -1385,7 +1361,7 @@ int launch_swd_jobs(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged 
 }
 
 // What one receiver-function launch synthesises: the descriptor's numbers, the output rows, the inputs of the fused
-// likelihood (yobs and sums, or null: the trace is written) and the site table (null: p and nsv as given).
+// likelihood (yobs and sums, or null: the trace is written), the build and the site table it reads (RF_PLAIN: none).
 struct RfJob {
     double p, gauss;
     int nsamp;
@@ -1393,33 +1369,38 @@ struct RfJob {
     int waveno, nkeep;
     double *rf; int ldr;
     const double *yobs; double *sums;
-    const RfSiteArgs *sites;
-    const RfSiteMArgs *msites; // sites that may lack the target (bh_sites_set_missing): the builds of bh_launch_rf_m, or null
-    const RfSiteTArgs *tsites; // sites with their own time axis and filter (bh_sites_set_rf_axis): the builds of bh_launch_rf_t, or null
+    RfBuild build;
+    RfSiteTArgs sites; // (a build reads the base it needs)
 };
 
-int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl, ptrdiff_t sb, const RfJob &j, const RfPlace &where)
+// The build of a fused call's receiver-function launches, by the tables its site plan has in force
+RfBuild rf_build(const SitePlan &sp)
+{
+    return sp.rf_axis ? RF_SITEAXIS : sp.missing ? RF_MISSING : sp.rf_table ? RF_SITES : RF_PLAIN;
+}
+
+// Ask, plan (bh_plan_rf, rf_plan.hip: every rule is there), launch.  beside_swd, gated: where the launch sits (RfAsk)
+int launch_rf(bh_engine *e, hipStream_t st, int B, int Lmax, const Staged &m, ptrdiff_t sl, ptrdiff_t sb, const RfJob &j, bool beside_swd, bool gated)
 {
     if (B == 0) return BH_OK;
-    int rc;
-    if ((rc = ensure(e, e->coef, (size_t)B * bh_rf_coef_doubles(Lmax) * sizeof(double)))) return rc;
-    RfKernelArgs a{};
+    const RfAsk q{B, Lmax, j.build, j.build == RF_SITEAXIS ? j.sites.nsamp_max : j.nsamp, j.fsamp, j.gauss, beside_swd, gated, e->rf_lds_beside_swd};
+    const RfPlan p = bh_plan_rf(q, bh_tuning());
+    if (p.code != BH_OK) return fail(e, p.code, bh_rf_refusal_text(p.refusal));
+    if (int rc = ensure(e, e->coef, (size_t)B * bh_rf_coef_doubles(Lmax) * sizeof(double))) return rc;
+    if (int rc = p.workspace ? ensure(e, e->rfz, p.work_bytes) : BH_OK) return rc;
+    RfKernelArgs a{}; // (lds_min and coef_small stay 0: unused)
     a.B = B; a.Lmax = Lmax; a.nsamp = j.nsamp; a.nkeep = j.nkeep; a.waveno = j.waveno;
-    a.nlay = m.nlay; a.h = m.h; a.vp = m.vp; a.vs = m.vs; a.rho = m.rho; a.qp = m.qp; a.qs = m.qs;
-    a.sl = sl; a.sb = sb;
+    a.nlay = m.nlay; a.h = m.h; a.vp = m.vp; a.vs = m.vs; a.rho = m.rho; a.qp = m.qp; a.qs = m.qs; a.sl = sl; a.sb = sb;
     a.p_s_per_deg = j.p; a.gauss = j.gauss; a.fsamp = j.fsamp; a.tshift = j.tshift; a.nsv = j.nsv;
     a.coef = (double *)e->coef.p; a.rf = j.rf; a.ldr = j.ldr;
     a.yobs = j.yobs; a.sums = j.sums; // (fused likelihood: the sums instead of the trace)
-    if (!j.tsites && bh_rf_lds_bytes(j.nsamp) > BH_RF_MAX_LDS) { // a trace longer than a workgroup's LDS holds: the spectra go through a workspace
-        if ((rc = ensure(e, e->rfz, (size_t)B * (size_t)(j.nsamp / 2) * 2 * sizeof(double)))) return rc;
-        a.zwork = (double *)e->rfz.p;
-    }
-    a.lds_min = where.lds_min;
-    a.coef_small = where.coef_small;
+    a.zwork = p.workspace ? (double *)e->rfz.p : nullptr;
+    a.no_realc = p.no_realc; a.no_rot = p.no_rot;
+    int (*const launcher[RF_BUILDS])(const RfPlan &, const RfKernelArgs &, const RfSiteTArgs *, hipStream_t) = {bh_launch_rf, bh_launch_rf, bh_launch_rf_m, bh_launch_rf_t};
     ev_begin(e, 1, st);
-    const int lrc = j.tsites ? bh_launch_rf_t(a, st, *j.tsites) : j.msites ? bh_launch_rf_m(a, st, *j.msites) : bh_launch_rf(a, st, j.sites);
+    const int lrc = launcher[j.build](p, a, j.build == RF_PLAIN ? nullptr : &j.sites, st);
     ev_end(e, 1, st);
-    if (lrc != 0) return fail(e, BH_EUNSUPPORTED, "receiver function: nsamp above 262144 is not supported");
+    if (lrc != BH_OK) return fail(e, lrc, lrc == BH_EHIP ? bh_rf_refusal_text(RF_REFUSE_ALLOWANCE) : "receiver function: a plan its build does not serve");
     HIPCHK(e, hipGetLastError());
     return BH_OK;
 }
@@ -1845,14 +1826,14 @@ int bh_rf_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax, const
     const bool host = (memspace != BH_DEVICE);
     hipStream_t st = (!host && stream) ? (hipStream_t)stream : e->stream;
     Staged m{nlay, h, vp, vs, rho, qp, qs};
-    RfJob job{p, gauss, nsamp, fsamp, tshift, nsv, waveno, nkeep, rf, nkeep, nullptr, nullptr, nullptr};
+    RfJob job{p, gauss, nsamp, fsamp, tshift, nsv, waveno, nkeep, rf, nkeep, nullptr, nullptr, RF_PLAIN, RfSiteTArgs{}};
     if (host) {
         if ((rc = stage_models(e, B, Lmax, sl, sb, m))) return rc;
         if ((rc = ensure(e, e->rf, (size_t)B * nkeep * sizeof(double)))) return rc;
         job.rf = (double *)e->rf.p;
     }
     call_begin(e, st);
-    rc = launch_rf(e, st, B, Lmax, m, sl, sb, job, RfPlace{}); // (not beside anything)
+    rc = launch_rf(e, st, B, Lmax, m, sl, sb, job, false, false); // (not beside anything)
     call_end(e, st);
     if (rc || !host) return rc;
     HIPCHK(e, hipMemcpyAsync(rf, e->rf.p, (size_t)B * nkeep * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -2088,7 +2069,6 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
     const bool gate = p.want_gate && swd.workgroups > 0;
     if (gate)
         HIPCHK(e, hipStreamWaitValue32(e->aux, e->started, e->started_expected - swd.workgroups + gate_need(swd), hipStreamWaitValueGte, 0xffffffffu));
-    const RfPlace where = rf_place(p.fork, gate && bh_tuning().rf_keep_floor == 0, bh_tuning(), e->rf_lds_beside_swd);
     for (int t = 0; t < nt; ++t) {
         TargetHost &T = e->targets[(size_t)t];
         const bh_target_desc &d = T.d;
@@ -2096,24 +2076,19 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
             bh_launch_interp(B, T.kfwd, (const double *)T.x60.p, (const double *)T.vel60.p, T.kfwd, d.n,
                              (const double *)T.x.p, c.ymod + T.off, ldy, st);
         if (p.role[t] != ROLE_RF) continue;
-        RfSiteArgs rs{};
-        if (sp.rf_table) rs = RfSiteArgs{c.site, S.nsites, nt, (const double *)S.p.p + t, (const double *)S.nsv.p + t};
-        RfSiteMArgs rm{};
-        if (sp.missing) {
-            static_cast<RfSiteArgs &>(rm) = rs;
-            rm.n = (const int32_t *)S.xn.p + t;
+        RfJob job{d.p_s_per_deg, d.gauss, d.nsamp, d.fsamp, d.tshift, d.nsv, d.waveno, d.n, c.ymod + T.off, ldy,
+                  p.rf_fused[t] ? (const double *)T.yobs.p : nullptr, p.rf_fused[t] ? (double *)T.sums.p : nullptr, rf_build(sp), RfSiteTArgs{}};
+        RfSiteTArgs &rs = job.sites; // (column t of the tables in force)
+        if (sp.rf_table) {
+            rs.site = c.site; rs.nsites = S.nsites; rs.ld = nt;
+            rs.p = (const double *)S.p.p + t; rs.nsv = (const double *)S.nsv.p + t;
         }
-        RfSiteTArgs ra{};
+        if (sp.missing || sp.rf_axis) rs.n = (const int32_t *)S.xn.p + t;
         if (sp.rf_axis) {
-            static_cast<RfSiteArgs &>(ra) = rs;
-            ra.n = (const int32_t *)S.xn.p + t;
-            ra.axis = (const RfAxisRec *)S.axis.p + t;
-            ra.nsamp_max = S.t[t].axis_nsamp_max;
+            rs.axis = (const RfAxisRec *)S.axis.p + t;
+            rs.nsamp_max = S.t[t].axis_nsamp_max;
         }
-        const RfJob job{d.p_s_per_deg, d.gauss, d.nsamp, d.fsamp, d.tshift, d.nsv, d.waveno, d.n, c.ymod + T.off, ldy,
-                        p.rf_fused[t] ? (const double *)T.yobs.p : nullptr, p.rf_fused[t] ? (double *)T.sums.p : nullptr, sp.rf_table ? &rs : nullptr,
-                        sp.missing ? &rm : nullptr, sp.rf_axis ? &ra : nullptr};
-        if ((rc = launch_rf(e, rst, B, c.Lmax, c.m, c.sl, c.sb, job, where))) return rc;
+        if ((rc = launch_rf(e, rst, B, c.Lmax, c.m, c.sl, c.sb, job, p.fork, gate))) return rc;
     }
     return p.fork ? wait_for(e, e->ev_join, e->aux, st) : BH_OK;
 }

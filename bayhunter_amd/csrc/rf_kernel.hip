@@ -22,7 +22,7 @@
 //                       four workgroups per CU);
 //                       only the first nkeep real samples are written (rfmini_modrf.py:142).
 #include "bh_device.h"
-#include "bh_tuning.h"
+#include "../../include/bh_engine.h"
 #include <cmath>
 #include <cstdlib>
 // BH_RF_MISSING (rf_kernel_m.hip): the builds for sites that lack a receiver-function target (bh_sites_set_missing,
@@ -50,9 +50,6 @@ typedef RfSiteMArgs RfSiteT; // (with the count of every site for the target: Rf
 #else
 typedef RfSiteArgs RfSiteT;
 #endif
-// w / a beyond which the Gauss low-pass exp(-(w/a)^2 / 4) is below RF_CUT = 1e-17: 2 sqrt(17 ln 10)
-constexpr double RF_CUT_WA = 12.5132;
-
 struct cd {
     double re, im;
 };
@@ -773,7 +770,7 @@ __device__ __forceinline__ void rf_synth_body(const RfKernelArgs &A, int logm, i
 #endif
 }
 // Two register budgets of the same text: 4 wavefronts per SIMD (128 VGPRs, a few spilled) and 3 (168, none);
-// bh_launch_rf picks (BH_RF_WAVES overrides, for measurements).
+// bh_plan_rf picks (BH_RF_WAVES overrides, for measurements).
 #if BH_RF_SITEAXIS
 // One model of a site-axis launch.  The site index and the site's record are uniform over the workgroup (ib is the workgroup's
 // index: scalar loads) and read before any barrier.  A site out of range has no record: its columns get NaN (the likelihood fails
@@ -864,118 +861,50 @@ int bh_launch_rf_probe(int op, int n, const double *in, double *out, hipStream_t
 }
 
 size_t bh_rf_coef_doubles(int Lmax) { return rec_doubles(Lmax); }
-
-size_t bh_rf_lds_bytes(int nsamp)
-{
-    return (size_t)(nsamp / 2) * 16 + 16 + 64 * 16 + (size_t)(nsamp >= 128 ? nsamp / 128 : 1) * 16;
-}
-
 #endif
 
+// ---- the launcher: the plan (bh_plan_rf, rf_plan.hip: every rule is there) names the kernels, the build launches them -------------
+// The one thing a build says for itself is which kernels it has, by RfCoefKernel and RfSynthKernel (null: none, no plan of the
+// build names it), and what its synthesis kernels take after RfKernelArgs.
+namespace {
 #if BH_RF_SITEAXIS
-// logm and jcut of one site's axis: the expressions of the launcher below
-RfAxisRec bh_rf_axis_record(int nsamp, double fsamp, double tshift, double gauss)
-{
-    const int half = nsamp / 2;
-    int logm = 0;
-    while ((1 << logm) < half) ++logm;
-    const double dw = 2.0 * M_PI * fsamp / nsamp;
-    const double jc = std::floor(RF_CUT_WA * gauss / dw) + 1.0;
-    const int jcut = !(jc < (double)half) ? half + 1 : (int)jc;
-    return RfAxisRec{fsamp, tshift, gauss, nsamp, logm, jcut, 0};
-}
-
-int bh_launch_rf_t(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteTArgs &msites)
-#elif BH_RF_MISSING
-int bh_launch_rf_m(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteMArgs &msites)
+#define BH_LAUNCH_RF bh_launch_rf_t
+// (the sites' logm and jcut are in their records, formed by bh_rf_axis_record; the rf_no_cut switch reaches the kernel as an argument)
+#define BH_RF_SYNTH_KARG RfSiteT(*sites), p.no_cut
+void (*const SYNTH[RF_SYNTH_KERNELS])(RfKernelArgs, RfSiteT, int) = {rf_synth_t_kernel, rf_synth_t_kernel_w3, nullptr};
 #else
-int bh_launch_rf(const RfKernelArgs &a_in, hipStream_t stream, const RfSiteArgs *sites)
-#endif
-{
 #if BH_RF_MISSING
-    const RfSiteT *sites = &msites; // (this build has site kernels only)
-#endif
-    RfKernelArgs a = a_in;
-    const BhTuning &tun = bh_tuning(); // (experiment switches, bh_tuning.h)
-    a.no_realc = tun.rf_no_realc != 0 ? 1 : 0;
-    a.no_rot = tun.rf_no_rot != 0 ? 1 : 0;
-    const int nthr = (tun.rf_threads == 128) ? 128 : 256;
-#if BH_RF_SITEAXIS
-    // every workgroup holds the LDS of the column's longest trace: a site's own tables lie inside it (bh_rf_lds_bytes grows with nsamp)
-    size_t lds = bh_rf_lds_bytes(msites.nsamp_max);
-    const bool longtrace = false;
-    if (lds > BH_RF_MAX_LDS) return -1;
+#define BH_LAUNCH_RF bh_launch_rf_m
 #else
-    const int half = a.nsamp / 2;
-    int logm = 0;
-    while ((1 << logm) < half) ++logm;
-    size_t lds = bh_rf_lds_bytes(a.nsamp); // half-length complex spectrum + Nyquist bin + two twiddle tables
-    const bool longtrace = lds > BH_RF_MAX_LDS;
+#define BH_LAUNCH_RF bh_launch_rf
 #endif
-    if (longtrace) {
-        if (a.zwork == nullptr || a.nsamp > BH_RF_MAX_NSAMP) return -1;
-        lds -= (size_t)(a.nsamp / 2) * 16; // (the spectrum is in the workspace)
-        a.lds_min = 0;
-    }
-    if (lds < (size_t)a.lds_min) lds = (size_t)a.lds_min;
-    if (lds > 64 * 1024) { // beyond the default dynamic-LDS limit: a workgroup may take the CU's whole 160 KB
+#define BH_RF_SYNTH_KARG p.logm, p.jcut
+void (*const SYNTH[RF_SYNTH_KERNELS])(RfKernelArgs, int, int) = {rf_synth_kernel, rf_synth_kernel_w3, rf_synth_kernel_long};
+#endif
+void (*const COEF_SITES[RF_COEF_KERNELS])(RfKernelArgs, RfSiteT) = {rf_coef_layers_sites_kernel_small<16>, rf_coef_layers_sites_kernel_small<32>,
+                                                                   rf_coef_layers_sites_kernel<16>, rf_coef_layers_sites_kernel<32>, rf_coef_sites_kernel};
+#if BH_RF_MISSING
+void (*const COEF[RF_COEF_KERNELS])(RfKernelArgs) = {}; // (this build has site kernels only)
+#else
+void (*const COEF[RF_COEF_KERNELS])(RfKernelArgs) = {rf_coef_layers_kernel_small<16>, rf_coef_layers_kernel_small<32>, rf_coef_layers_kernel<16>,
+                                                    rf_coef_layers_kernel<32>, rf_coef_kernel};
+#endif
+} // namespace
+
+// a: filled by the engine, the plan's switches included; sites: null (RF_PLAIN), or the table, of which a build reads the base it needs
+int BH_LAUNCH_RF(const RfPlan &p, const RfKernelArgs &a, const RfSiteTArgs *sites, hipStream_t stream)
+{
+    if (p.code != BH_OK || !SYNTH[p.synth] || !(sites ? (const void *)COEF_SITES[p.coef] : (const void *)COEF[p.coef]) || (p.workspace && !a.zwork))
+        return BH_EINVAL; // (a plan of another build, or one carried out without its workspace)
+    if (p.big_lds) {
         static std::atomic<unsigned long long> allowed{0};
-#if BH_RF_SITEAXIS
-        const void *k[2] = {reinterpret_cast<const void *>(rf_synth_t_kernel), reinterpret_cast<const void *>(rf_synth_t_kernel_w3)};
-#else
-        const void *k[2] = {reinterpret_cast<const void *>(rf_synth_kernel), reinterpret_cast<const void *>(rf_synth_kernel_w3)};
-#endif
-        if (!bh_allow_big_lds(&allowed, k, 2, (int)BH_RF_MAX_LDS)) return -1;
+        const void *k[2] = {reinterpret_cast<const void *>(SYNTH[RF_SYNTH_W4]), reinterpret_cast<const void *>(SYNTH[RF_SYNTH_W3])};
+        if (!bh_allow_big_lds(&allowed, k, 2, (int)BH_RF_MAX_LDS)) return BH_EHIP;
     }
-    if (sites) { // (the same choice of build, each with its site variant)
-        const RfSiteT s = *sites;
-        if (a.Lmax <= 16 && a.coef_small)
-            hipLaunchKernelGGL((rf_coef_layers_sites_kernel_small<16>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a, s);
-        else if (a.Lmax <= 32 && a.coef_small)
-            hipLaunchKernelGGL((rf_coef_layers_sites_kernel_small<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a, s);
-        else if (a.Lmax <= 16)
-            hipLaunchKernelGGL((rf_coef_layers_sites_kernel<16>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a, s);
-        else if (a.Lmax <= 32)
-            hipLaunchKernelGGL((rf_coef_layers_sites_kernel<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a, s);
-        else
-            hipLaunchKernelGGL(rf_coef_sites_kernel, dim3((a.B + 255) / 256), dim3(256), 0, stream, a, s);
-    }
-#if !BH_RF_MISSING
-    else if (a.Lmax <= 16 && a.coef_small)
-        hipLaunchKernelGGL((rf_coef_layers_kernel_small<16>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a);
-    else if (a.Lmax <= 32 && a.coef_small)
-        hipLaunchKernelGGL((rf_coef_layers_kernel_small<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a);
-    else if (a.Lmax <= 16)
-        hipLaunchKernelGGL((rf_coef_layers_kernel<16>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a);
-    else if (a.Lmax <= 32)
-        hipLaunchKernelGGL((rf_coef_layers_kernel<32>), dim3((a.B + 7) / 8), dim3(256), 0, stream, a);
+    if (sites)
+        hipLaunchKernelGGL(COEF_SITES[p.coef], dim3(p.coef_grid), dim3(256), 0, stream, a, RfSiteT(*sites));
     else
-        hipLaunchKernelGGL(rf_coef_kernel, dim3((a.B + 255) / 256), dim3(256), 0, stream, a);
-#endif
-    // Spectral cut-off.  Every bin carries the Gauss low-pass exp(-w^2 / (4 a^2)) (greens.cpp:343-398); where that
-    // factor is below RF_CUT = 1e-17 the bin is below 1e-17 of the pass band (|R/Z| is of order one): a tenth of the
-    // rounding unit (2^-53 = 1.1e-16) of the sums the transform forms, i.e. it is lost in the reference's own additions.
-    // Such bins are set to zero instead of being computed (the reference computes them and multiplies by ~0).  With
-    // a = 2.5, 20 Hz, nsamp 2048 that is every bin above 5.0 Hz: 510 of 1025 are computed, 8 passes of 64 lanes per model
-    // (round 2 cut at 1e-30: 678 bins, 11 passes).  tests/test_gpu_rf.py compares with the uncut transform (1e-13).
-    const bool no_cut = tun.rf_no_cut != 0; // (tests flip it with bh_engine_set_tuning)
-#if BH_RF_SITEAXIS
-    // (the sites' jcut are in their records, formed by bh_rf_axis_record; the switch reaches the kernel as an argument)
-    if (tun.rf_waves == 3)
-        hipLaunchKernelGGL(rf_synth_t_kernel_w3, dim3(a.B), dim3(nthr), lds, stream, a, msites, no_cut ? 1 : 0);
-    else
-        hipLaunchKernelGGL(rf_synth_t_kernel, dim3(a.B), dim3(nthr), lds, stream, a, msites, no_cut ? 1 : 0);
-    return 0;
-#else
-    const double dw = 2.0 * M_PI * a.fsamp / a.nsamp;
-    const double jc = std::floor(RF_CUT_WA * a.gauss / dw) + 1.0;
-    const int jcut = (no_cut || !(jc < (double)half)) ? half + 1 : (int)jc;
-    if (longtrace)
-        hipLaunchKernelGGL(rf_synth_kernel_long, dim3(a.B), dim3(256), lds, stream, a, logm, jcut);
-    else if (tun.rf_waves == 3)
-        hipLaunchKernelGGL(rf_synth_kernel_w3, dim3(a.B), dim3(nthr), lds, stream, a, logm, jcut);
-    else
-        hipLaunchKernelGGL(rf_synth_kernel, dim3(a.B), dim3(nthr), lds, stream, a, logm, jcut);
-    return 0;
-#endif
+        hipLaunchKernelGGL(COEF[p.coef], dim3(p.coef_grid), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(SYNTH[p.synth], dim3(a.B), dim3(p.block), p.lds, stream, a, BH_RF_SYNTH_KARG);
+    return BH_OK;
 }

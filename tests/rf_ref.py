@@ -47,7 +47,7 @@ reference's e^{i w t0}, the Gauss factor's constant), a sample of the trace sati
     |f^_n - f_n| <= (1/N) sum_k w_k (E_k + cut_k) + (log2 N + 4)(4u + eps_tw) (1/N) sum_k w_k |X_k| + ref_k
 
 with w_k = 1 for k = 0 and N/2 and 2 otherwise (each bin enters the real inverse transform once or as a conjugate pair), cut_k
-= |X_k| for the bins the kernel does not form (k >= jcut, bh_launch_rf), the second term the transform's own rounding (every
+= |X_k| for the bins the kernel does not form (k >= jcut, bh_rf_axis_cut), the second term the transform's own rounding (every
 output is a sum over log2 N radix-2 stages of butterflies whose partial sums are bounded by sum |X|, each stage a twiddle
 product and an addition: 4u + eps_tw, eps_tw = 4 eps_sin + 3u for the two-table twiddles; + 4 for the real-to-complex fold
 and the 1/N) and ref the reference's own error: the same analysis with the long double unit u_ld = 2^-64 in place of every
@@ -68,7 +68,7 @@ U = 2.0 ** -53
 U_LD = float(np.finfo(LD).eps) / 2.0
 PI = 4 * np.arctan(LD(1))
 R_EARTH = LD(6371)
-RF_CUT_WA = 12.5132                      # rf_kernel.hip: w / a beyond which the Gauss low-pass is below 1e-17
+RF_CUT_WA = 12.5132                      # csrc/rf_plan.hip: w / a beyond which the Gauss low-pass is below 1e-17
 SIN_RANGE = 2.0 ** 20                    # sincos_cw's documented argument range
 FACTOR = 4.0                             # tolerance = FACTOR x bound
 
@@ -241,7 +241,7 @@ def _finite(*mats):
 
 
 def jcut_of(nsamp, fsamp, gauss):
-    """bh_launch_rf's first bin not formed (N/2 + 1: all of them)"""
+    """bh_rf_axis_cut's first bin not formed (csrc/rf_plan.hip; N/2 + 1: all of them)"""
     half = nsamp // 2
     dw = 2.0 * np.pi * fsamp / nsamp
     jc = np.floor(RF_CUT_WA * gauss / dw) + 1.0
