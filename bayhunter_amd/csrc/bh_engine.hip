@@ -1765,6 +1765,22 @@ int bh_debug_trace(bh_engine *e, uint64_t *out, int nwaves)
     return BH_OK;
 }
 
+int bh_debug_guard_list(bh_engine *e, int target, int B, int32_t *out, int max, int *n)
+{
+    if (!e || !n || target < 0 || target >= BH_MAX_TARGETS || B < 0 || max < 0 || (max > 0 && !out)) return BH_EINVAL;
+    *n = 0;
+    if (!e->guard.p || e->guard_fresh || !e->guard_last) return BH_OK;
+    if (((size_t)GUARD_HEAD + (size_t)(target + 1) * (size_t)(B + 4)) * sizeof(int32_t) > e->guard.cap) return fail(e, BH_EINVAL, "not the last call's batch size");
+    int32_t cnt = 0;
+    HIPCHK(e, hipDeviceSynchronize()); // (the last call may have run on a caller's stream)
+    HIPCHK(e, hipMemcpy(&cnt, (int32_t *)e->guard.p + target, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt < 0 || cnt > B) return fail(e, BH_EINVAL, "not the last call's batch size");
+    const int m = cnt < max ? cnt : max;
+    if (m > 0) HIPCHK(e, hipMemcpy(out, (int32_t *)e->guard.p + GUARD_HEAD + (size_t)target * (size_t)(B + 4), (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    *n = m;
+    return BH_OK;
+}
+
 int bh_last_neval(bh_engine *e, uint64_t *neval)
 {
     if (!e || !neval) return BH_EINVAL;

@@ -135,6 +135,49 @@ enum : int {
 };
 
 __device__ __forceinline__ bool sign_neg(double x) { return __double_as_longlong(x) < 0; }
+// One flag of a model's search state: bit BIT of the lane's state word.  A `bool` that is carried round the loop is a lane mask in a
+// pair of scalar registers, and the search has more of them than the scalar file has room for beside the polynomials' constants
+// (49 of them were spilled to lanes of a vector register and fetched back round by round); a bit of a vector register costs an
+// AND where it is read.  Reads and writes like a bool.
+// ... and the small numbers of the state -- the phase, the refinement's round count, the count of sign changes below a special
+// velocity -- are fields of W bits from bit SH of the same word; they read and write like an int.
+template <int SH, int W>
+struct LeanField {
+    unsigned &w;
+    static constexpr unsigned M = (1u << W) - 1u;
+    __device__ __forceinline__ operator int() const { return (int)((w >> SH) & M); }
+    __device__ __forceinline__ LeanField &operator=(int v)
+    {
+        w = (w & ~(M << SH)) | (((unsigned)v & M) << SH);
+        return *this;
+    }
+    __device__ __forceinline__ LeanField &operator++()
+    {
+        w += 1u << SH; // (the callers' values stay below 2^W: the refinement ends at 16 rounds)
+        return *this;
+    }
+};
+// The direction of the scan, +1 or -1, as one bit (set: downward).
+template <unsigned BIT>
+struct LeanDir {
+    unsigned &w;
+    __device__ __forceinline__ operator int() const { return (w & BIT) != 0u ? -1 : +1; }
+    __device__ __forceinline__ LeanDir &operator=(int v)
+    {
+        w = v < 0 ? (w | BIT) : (w & ~BIT);
+        return *this;
+    }
+};
+template <unsigned BIT>
+struct LeanFlag {
+    unsigned &w;
+    __device__ __forceinline__ operator bool() const { return (w & BIT) != 0u; }
+    __device__ __forceinline__ LeanFlag &operator=(bool v)
+    {
+        w = v ? (w | BIT) : (w & ~BIT);
+        return *this;
+    }
+};
 // LDS ordering inside ONE wavefront: its LDS instructions execute in order; only the compiler must not reorder
 __device__ __forceinline__ void lean_wave_sync()
 {
@@ -201,19 +244,24 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
             }
         }
     }
+    // (the target is the wavefront's: its index and what is read through it live in scalar registers)
+    ty = __builtin_amdgcn_readfirstlane(ty);
+    wid = __builtin_amdgcn_readfirstlane(wid);
     const SwdTarget T = A.t[ty];
     constexpr int MPW = BH_WAVE / J; // models per wavefront
     if (wid * MPW >= A.B) return;
     const int g = lane / J, r = lane & (J - 1), lbase = lane & ~(J - 1);
     const int sidx = wid * MPW + g;
-    const bool valid = sidx < A.B;
+    unsigned stw = 0; // the flags of this lane's model (LeanFlag)
+    LeanFlag<1u << 9> valid{stw};
+    valid = sidx < A.B;
     const int32_t *perm = T.perm != nullptr ? T.perm : A.perm;
     const int ib = valid ? (perm ? perm[sidx] : sidx) : 0;
     extern __shared__ __align__(16) unsigned char smem_lean[];
     constexpr double dc = (double)0.005f, onea = (double)1.5f, twopi = 2.0 * 3.141592653589793, guard_rel = 3.0e-6;
 #if BH_SWD_SITEX
     // K: this lane's model's own count (0 for a site out of range: the model fails in band); Kcap: the columns of its output row
-    const int Lmax = A.Lmax, Kcap = T.K, ifunc = T.iwave, KE = (Kcap + 1) & ~1;
+    const int Lmax = A.Lmax, Kcap = T.K, ifunc = __builtin_amdgcn_readfirstlane(T.iwave), KE = (Kcap + 1) & ~1;
     const int Kown = valid ? bh_site_count(X, ty, ib, Kcap) : 0;
     const int K = Kown > 0 ? Kown : 0;
     double *omg_all = reinterpret_cast<double *>(smem_lean + (size_t)wave * wave_lds); // [MPW][KE]: 2 pi / period, a row per model
@@ -230,7 +278,7 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
         }
     }
 #else
-    const int Lmax = A.Lmax, K = T.K, ifunc = T.iwave;
+    const int Lmax = A.Lmax, K = __builtin_amdgcn_readfirstlane(T.K), ifunc = __builtin_amdgcn_readfirstlane(T.iwave);
     double *omg = reinterpret_cast<double *>(smem_lean + (size_t)wave * wave_lds); // [K]: 2 pi / period
     double *mdl = omg + ((K + 1) & ~1);                                            // [7][Lmax][MPW]
     const int LS = Lmax * MPW;
@@ -304,8 +352,11 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
         return n > 1 ? -1.0 : sp;
     };
     double *vel = T.vel + (size_t)ib * T.ldv;
-    const bool writer = valid && r == 0;
-    bool active = valid && K > 0 && sane, guard = false;
+    LeanFlag<1u << 10> writer{stw};
+    writer = valid && r == 0;
+    LeanFlag<1u << 0> active{stw};
+    LeanFlag<1u << 1> guard{stw};
+    active = valid && K > 0 && sane;
 #define LEAN_GUARD(n) do { guard = true; if (CNT) greason = (n); } while (0)
     int greason = 0; // (development aid: which rule fired the guard -- 1 water layer, 2 / 3 small start / scan value, 4 step probes, 5 bracket
                      //  probes, 6 a bracket that contains betmx with sign changes on both sides of it or next to it, 7 root at a bracket end or at betmx)
@@ -325,17 +376,23 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
         active = false;
     }
     // ---- search state, the same in every lane of the model
-    int k = 0, ph = PH_START, idir = +1, ifirst = 1, nref = 0;
+    int k = 0;
+    LeanField<12, 4> ph{stw};   // (PH_START = 0)
+    LeanField<16, 5> nref{stw}; // (at most 16)
+    LeanField<21, 1> ifirst{stw};
+    LeanDir<1u << 11> idir{stw};
+    ifirst = 1;
     double c1 = cm, clow = cm, del1 = 0.0, ck = 0.0, omega = 1.0, iom = 1.0;
-    bool s1stneg = false;
+    LeanFlag<1u << 2> s1stneg{stw};
     double cp = 0.0, delp = 0.0; // the grid point before c1 and its value (third point of the first estimate)
-    bool havep = false;
+    LeanFlag<1u << 3> havep{stw};
     double lo = 0.0, hi = 0.0, flo = 0.0, fhi = 0.0, p3 = 0.0, fp3 = 0.0, c3 = 0.0, wprev = 0.0;
-    bool have3 = false;
+    LeanFlag<1u << 4> have3{stw};
     double cell_lo = 0.0, cell_hi = 0.0, pb = 0.0, delb = 0.0;
-    bool pp_neg = false; // PH_SPECIAL -> PH_SPECIAL_B: the sign just above the special velocity
-    int sp_nb = 0;       // ... and the sign changes found below it
-    bool flo_neg = false, chk = false; // chk: this period's start value has been probed (PH_PROBE_START)
+    LeanFlag<1u << 5> pp_neg{stw}; // PH_SPECIAL -> PH_SPECIAL_B: the sign just above the special velocity
+    LeanField<22, 2> sp_nb{stw}; // ... and the sign changes found below it (0 or 1 where it is kept)
+    LeanFlag<1u << 6> flo_neg{stw};
+    LeanFlag<1u << 7> chk{stw}; // chk: this period's start value has been probed (PH_PROBE_START)
     unsigned evals = 0;
     if (active) {
         omega = omg[0];
@@ -423,12 +480,16 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
     // every SIMD holds one Rayleigh and one Love wavefront (A.lean_prio), the two take the high priority in turn, by time slices
     // of the shader clock they share: the Rayleigh wavefront, which has the more work, in `share` of every eight slices, the Love
     // wavefront in the others, so that both stay resident until close to the end.  Scheduling only.
-    const int prio_share = PAIRED ? (A.lean_prio & 15) : 0, prio_slice = PAIRED ? (A.lean_prio >> 8) : 0;
+    const int prio_share = PAIRED ? __builtin_amdgcn_readfirstlane(A.lean_prio & 15) : 0, prio_slice = PAIRED ? __builtin_amdgcn_readfirstlane(A.lean_prio >> 8) : 0;
+    // (the wave type as a number in ONE scalar register, 1 = Rayleigh: the empty statement keeps the compiler from turning it back
+    // into the lane mask of `ifunc == 2`, a register pair it held -- spilled -- through the whole loop)
+    int ray = __builtin_amdgcn_readfirstlane((ifunc == 2) ? 1 : 0);
+    asm("" : "+s"(ray));
     while (__ballot(active) != 0ull) {
         ++nrounds;
         if (PAIRED && prio_share != 0) {
-            const bool first = ((unsigned)(__builtin_readcyclecounter() >> prio_slice) & 7u) < (unsigned)prio_share;
-            if (first == (ifunc == 2)) __builtin_amdgcn_s_setprio(2);
+            const int first = ((unsigned)__builtin_amdgcn_readfirstlane((int)(__builtin_readcyclecounter() >> prio_slice)) & 7u) < (unsigned)prio_share ? 1 : 0;
+            if (first == ray) __builtin_amdgcn_s_setprio(2);
             else __builtin_amdgcn_s_setprio(0);
         }
         // ---- this lane's trial velocity (and frequency)
@@ -520,7 +581,7 @@ __global__ __launch_bounds__(BH_WAVE * LEAN_WPB) void swd_lean_kernel(SwdMultiAr
         if (!active || !(cev > 0.0)) cev = 1.0; // (finished or broken models compute on a harmless value)
         const long long te0 = ((CNT && A.neval != nullptr)) ? clock64() : 0;
         const double wvno = om_l * fa::rcp(cev);
-        const double del = (ifunc == 2) ? lean_rayleigh(wvno, om_l, iom_l, md, mmax, mtop) : lean_love(wvno, om_l, md, mmax, mtop);
+        const double del = (ray != 0) ? lean_rayleigh(wvno, om_l, iom_l, md, mmax, mtop) : lean_love(wvno, om_l, md, mmax, mtop);
         if ((CNT && A.neval != nullptr)) t_eval += clock64() - te0;
 
         // ---- the round's decision.  Signs and "not a number" travel as ballots; one event code per lane and a ballot give the

@@ -152,6 +152,7 @@ def load_library():
     L.bh_timing_steps.argtypes = [vp, C.c_int, _d, C.POINTER(C.c_int)]
     L.bh_last_neval.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.bh_debug_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.bh_debug_guard_list.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]
     L.bh_debug_trace.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
     L.bh_swd_batch.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_ssize_t,
                                C.c_ssize_t, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
@@ -268,7 +269,7 @@ def load_library():
     for name in CHAIN_RANK_SYMBOLS:
         getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
-                 "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
+                 "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_debug_guard_list", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_probe_swd_secular", "bh_chain_propose", "bh_chain_accept",
                  "bh_chain_propose_window", "bh_chain_accept_window", "bh_sites_set", "bh_evaluate_sites", "bh_sites_set_rf", "bh_sites_set_x", "bh_sites_set_x_all",
                  "bh_sites_set_missing", "bh_chain_propose_sites", "bh_chain_propose_window_sites") + SITE_GAUSS_SYMBOLS + SITE_PRIORS_SYMBOLS + SITE_RF_AXIS_SYMBOLS + SITE_LAWS_SYMBOLS + CHAIN_RECORD_SYMBOLS:
@@ -292,7 +293,7 @@ DEBUG_SYMBOLS = ("bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_e
                  "bh_engine_set_swd_scan",
                  "bh_engine_get_swd_scan", "bh_engine_set_tuning",
                  "bh_engine_get_tuning", "bh_probe_math", "bh_probe_swd_secular", "bh_engine_set_instrumentation", "bh_timing_reset",
-                 "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace")
+                 "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_debug_guard_list")
 # include/bh_engine_sites.h: many stations at once (site-indexed observed data)
 SITE_SYMBOLS = ("bh_sites_set", "bh_evaluate_sites")
 # include/bh_engine_sites_rf.h: receiver-function ray parameter and near-surface velocity per site
@@ -694,6 +695,14 @@ class Engine(object):
         out = (C.c_uint64 * (4 * max(n, 1)))()
         self._check(self._L.bh_debug_trace(self._h, out, n))
         return np.frombuffer(out, dtype=np.uint64).reshape(-1, 4)[:n].copy()
+
+    def guard_list(self, target, B):
+        """Development aid: the batch indices (int32, unordered) that the guard listed for the re-run launch of the most recent
+        dispersion call, for its target-th dispersion target; B: that call's batch size (bh_debug_guard_list)."""
+        out = np.zeros(max(int(B), 1), dtype=np.int32)
+        n = C.c_int(0)
+        self._check(self._L.bh_debug_guard_list(self._h, int(target), int(B), out.ctypes.data_as(C.POINTER(C.c_int32)), int(B), C.byref(n)))
+        return out[:n.value].copy()
 
     def last_neval(self):
         v = C.c_uint64(0)

@@ -163,6 +163,10 @@ int bh_debug_counters(bh_engine *e, uint64_t out[16]);
 /* development aid: one record of 4 words per traced wavefront of the last counted dispersion launch
  * (start, end [100 MHz ticks], core cycles, rounds | wave type << 32 | HW_ID << 36); counter [7] = wavefronts */
 int bh_debug_trace(bh_engine *e, uint64_t *out, int nwaves);
+/* development aid: the models (batch indices, in no particular order) that the guard of the short refinement listed for the
+ * re-run launch of the most recent dispersion call, for the target-th dispersion target of that call; B: that call's batch
+ * size.  Writes at most `max` entries and returns their number in *n. */
+int bh_debug_guard_list(bh_engine *e, int target, int B, int32_t *out, int max, int *n);
 
 
 #ifdef __cplusplus

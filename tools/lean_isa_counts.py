@@ -8,9 +8,12 @@
 The unit is compiled to assembly with the flags the Makefile builds its object with (the command is taken from
 `make -n UNIT.o`, so a per-file EXTRA is honoured), device side only; no GPU is needed.  For every kernel whose demangled name
 contains one of the -k strings the tool prints one row for the whole kernel and one per INNER loop (a backward branch to a label,
-with no other loop of --min-loop instructions or more inside), in the order of the listing: static instructions, VALU, SALU, LDS, v_mov_b*, v_cndmask*.
+with no other loop of --min-loop instructions or more inside), in the order of the listing: static instructions, VALU, SALU, LDS,
+v_mov_b*, v_cndmask*, conditional branches (s_cbranch*) and lane moves (v_readlane*, v_readfirstlane*, v_writelane*).  A loop that
+holds listed inner loops gets a row too, `round L - inner`: what of it lies OUTSIDE those inner loops -- in the lean kernel the
+round loop without the layer loops of the secular evaluations, i.e. the search's bookkeeping (trial velocities, round decision).
 
-It counts by instruction-class prefix only (v_ / s_ / ds_), names no opcode beyond the two move / select prefixes, and knows
+It counts by instruction-class prefix only (v_ / s_ / ds_), names no opcode beyond the move / select / branch / lane prefixes, and knows
 nothing of trip counts: a row is what the loop body holds, not what a launch issues.  The loops of the lean kernel, by size: the
 Rayleigh layer steps are the largest ones (~400 instructions), the Love layer step the next (~160).
 """
@@ -73,7 +76,7 @@ def functions(lines):
 
 
 def classify(body):
-    n = dict(instr=0, valu=0, salu=0, lds=0, mov=0, cnd=0)
+    n = dict(instr=0, valu=0, salu=0, lds=0, mov=0, cnd=0, cbr=0, lane=0)
     for l in body:
         if LABEL.match(l):
             continue
@@ -88,15 +91,20 @@ def classify(body):
                 n["mov"] += 1
             elif op.startswith("v_cndmask"):
                 n["cnd"] += 1
+            elif op.startswith(("v_readlane", "v_readfirstlane", "v_writelane")):
+                n["lane"] += 1
         elif op.startswith("s_"):
             n["salu"] += 1
+            if op.startswith("s_cbranch"):
+                n["cbr"] += 1
         elif op.startswith("ds_"):
             n["lds"] += 1
     return n
 
 
-def inner_loops(body, min_loop):
-    """[(label, first, last)]: the loops (a backward branch to a label) of at least min_loop instructions that hold no other such loop"""
+def loops(body, min_loop):
+    """([(label, first, last)] inner, [(label, first, last, [inner inside])] outer): the loops (a backward branch to a label) of at
+    least min_loop instructions that hold no other such loop, and the outermost loops that hold some of those"""
     at = {}
     for i, l in enumerate(body):
         m = LABEL.match(l)
@@ -113,7 +121,13 @@ def inner_loops(body, min_loop):
             best[lab] = (lab, a, b)
     # (loops below the size asked for do not count as loops: the layer steps hold waterfall loops of ten instructions)
     spans = sorted((s for s in best.values() if classify(body[s[1]:s[2] + 1])["instr"] >= min_loop), key=lambda s: s[1])
-    return [s for s in spans if not any(o is not s and s[1] <= o[1] and o[2] <= s[2] for o in spans)]
+    inner = [s for s in spans if not any(o is not s and s[1] <= o[1] and o[2] <= s[2] for o in spans)]
+    outer = []
+    for s in spans:
+        held = [i for i in inner if i is not s and s[1] <= i[1] and i[2] <= s[2]]
+        if held and not any(o is not s and o[1] <= s[1] and s[2] <= o[2] for o in spans):
+            outer.append(s + (held,))
+    return inner, outer
 
 
 def report(lines, wanted, min_loop):
@@ -127,8 +141,12 @@ def report(lines, wanted, min_loop):
         a, b = fn[sym]
         body = lines[a:b]
         rows.append((dn, "whole kernel", classify(body)))
-        for lab, la, lb in inner_loops(body, min_loop):
+        inner, outer = loops(body, min_loop)
+        for lab, la, lb in inner:
             rows.append((dn, "loop %s" % lab, classify(body[la:lb + 1])))
+        for lab, la, lb, held in outer:  # the outer loop without its listed inner loops
+            rest = [l for i, l in enumerate(body[la:lb + 1], la) if not any(a_ <= i <= b_ for _, a_, b_ in held)]
+            rows.append((dn, "round %s - inner" % lab, classify(rest)))
     return rows
 
 
@@ -143,10 +161,10 @@ def main():
     rows = report(assembly(a.src, a.unit), wanted, a.min_loop)
     if not rows:
         sys.exit("no kernel of %s matches %s" % (a.unit, wanted))
-    print("%-14s %6s %6s %6s %5s %8s %10s   %s" % ("part", "instr", "VALU", "SALU", "LDS", "v_mov_b*", "v_cndmask*", "kernel"))
+    print("%-24s %6s %6s %6s %5s %8s %10s %10s %10s   %s" % ("part", "instr", "VALU", "SALU", "LDS", "v_mov_b*", "v_cndmask*", "s_cbranch*", "lane moves", "kernel"))
     for dn, part, n in rows:
-        print("%-14s %6d %6d %6d %5d %8d %10d   %s" % (part, n["instr"], n["valu"], n["salu"], n["lds"], n["mov"], n["cnd"],
-                                                        re.sub(r"^void \(anonymous namespace\)::|\(.*$", "", dn)))
+        print("%-24s %6d %6d %6d %5d %8d %10d %10d %10d   %s" % (part, n["instr"], n["valu"], n["salu"], n["lds"], n["mov"], n["cnd"], n["cbr"], n["lane"],
+                                                                  re.sub(r"^void \(anonymous namespace\)::|\(.*$", "", dn)))
 
 
 if __name__ == "__main__":
