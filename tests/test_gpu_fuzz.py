@@ -8,7 +8,11 @@ HEAD` where a work tree is present) or -- on the GPU box, whose snapshot has no 
 new build walks new models, and a failure is reproduced with the printed seed.  Checked against the ORACLE's reference sequence
 (oracle/swd_oracle.c search mode 0, bit-identical to the compiled reference): failure flags, zero rows, 2.5e-6 -- for bh_swd_batch on
 sorted-velocity models with a low-velocity zone and on models drawn from a sampler's prior, and for the fused call's failure
-pattern."""
+pattern.
+
+The FIXED counterpart is tests/test_gpu_swd_hard_set.py: the models of the same prior on which the guard has to work (mined on the
+CPU with the oracle, tools/mine_hard_swd_models.py -> tests/golden/swd_hard_golden.npz), the same on every commit, where this
+test walks new ones."""
 import hashlib
 import os
 import subprocess
