@@ -958,7 +958,8 @@ class DeviceChains(object):
             return posterior_residuals(targets, d["models2d"], d["vpvs"].reshape(n), d["noise"].reshape(n, 2 * self.nt), site=d["site"],
                                        maxlag=maxlag, quantiles=quantiles, mantle=mantle, engine=self.engine)
 
-    def diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_chains=None, rank=False):
+    def diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_chains=None, rank=False, features=None, moho=None,
+                    mohovs=4.2):
         """record="device": bayhunter_amd.diagnostics of every site's chains, straight from the time-ordered views of the device
         store (one dict per site; one dict without SiteTargets): `outliers` -- the global numbers of the chains the reference's rule
         (results.get_outliers, deviation `dev`) rejects, ready to pass as exclude_chains= to the posterior_* methods --, their
@@ -968,6 +969,11 @@ class DeviceChains(object):
         maxlag: the largest lag of the autocorrelation sums, default min(T // 2, 1000).
         rank=True: every group's dict gains "rank" -- the rank-normalised and the folded split R-hat, the bulk and the tail ESS of
         diagnostics.rank_convergence, the site's kept chains pooled on the GPU; with the default nothing of it runs.
+        features (the dict of posterior_features, every number a scalar or one per site) and / or moho = (lo, hi) or one pair per
+        site, with mohovs (the feature "moho", posterior_moho's depth column): every site's dict gains "features", the dict of
+        diagnostics.feature_convergence -- R-hat, ESS and the Monte-Carlo standard error of every feature column (mcse_mean), the
+        probability that a row has it and its own error (presence, mcse_probability) -- from series the GPU forms out of the model
+        rows where they lie; with the defaults nothing of it runs.
         EngineError: record="host" (no time-ordered store on the GPU), a tempered run (a ladder's cold state moves between chains:
         no chain's series is a posterior series) and a sharded job of more than one rank (a site's chains lie on several GPUs)."""
         if self._rec is None:
@@ -986,10 +992,11 @@ class DeviceChains(object):
         ids = self.chain_offset + np.arange(self.C, dtype=np.int64)
         with self.torch.cuda.device(self.dev):
             r = diagnose(d, np.arange(self.C) // self.C_site, ids, dev=dev, dep=dep, maxlag=maxlag, exclude_chains=exclude_chains,
-                         engine=self.engine, rank=rank)
+                         engine=self.engine, rank=rank, features=features, moho=moho, mohovs=mohovs)
         return r if self.sites is not None else r[0]
 
-    def ladder_diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_ladders=None, rank=False):
+    def ladder_diagnostics(self, phase="p2", dep=None, maxlag=None, dev=0.05, exclude_ladders=None, rank=False, features=None,
+                           moho=None, mohovs=4.2):
         """record="device", tempered runs: bayhunter_amd.diagnostics of every site's LADDERS, straight from the device store.  The
         posterior series of a ladder is its cold series -- at every recorded row the state of the chain that holds the ladder's
         largest beta (the first of them: what samples(cold_only=True) and save() pick); diagnostics.ladder_index finds that chain
@@ -1003,6 +1010,8 @@ class DeviceChains(object):
         chains (their global numbers), round_trips (cold -> hot -> cold excursions seen at the recorded rows), occupancy [.][R]
         (rows spent on every rung) and cold_share = occupancy[:, 0] / T.
         exclude_ladders None: R-hat and ESS over the ladders that are no outliers; a sequence of ladder ids overrides that.
+        features, moho, mohovs: as diagnostics() -- "features" of every site from the feature series of the ladders' cold series,
+        read in place; its `chains` are ladder ids.
         EngineError: record="host", an untempered run (use diagnostics()), a sharded job of more than one rank (ladders are not
         followed across ranks).  ValueError: rank=True -- the ranks of cold series are not formed."""
         if rank:
@@ -1026,7 +1035,7 @@ class DeviceChains(object):
             ids = np.asarray(idx["ids"], dtype=np.int64)
             site_of_ladder = np.array([m[0] // self.C_site for m in idx["members"]], dtype=np.int64)
             r = diagnose(d, site_of_ladder, ids, dev=dev, dep=dep, maxlag=maxlag, exclude_chains=exclude_ladders, engine=self.engine,
-                         sel=idx["sel"])
+                         sel=idx["sel"], features=features, moho=moho, mohovs=mohovs)
         pos = {int(l): k for k, l in enumerate(ids)}
         for s, rs in enumerate(r):
             ks = np.flatnonzero(site_of_ladder == s)

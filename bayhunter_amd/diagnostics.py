@@ -68,6 +68,13 @@ rung of every ladder at every row -- hold[t][j], a sel= with one series per temp
 recorded likes of the rung series the log ratios Z(b_{r-1}) / Z(b_r) of neighbouring rungs (stepping stones in both directions) and the
 thermodynamic integral, with errors from the rung series' ESS; formulas and caveats in its docstring.
 
+Structural features (include/bh_engine_chain_diag_features.h): the numbers an array study publishes -- a Moho depth, a sediment
+thickness, the probability of a low-velocity zone -- are functionals of the model rows that posterior_features forms on rows which
+have lost their time order.  chain_feature_series forms the same columns, bit for bit, as series of every chain from the store where
+it lies: value (0 where a row lacks the feature), present (the indicator) and missing (the counts); feature_convergence gives every
+column R-hat, ESS and a Monte-Carlo standard error, with a stated rule for the rows that lack it (its docstring); diagnose takes
+features= / moho=.
+
 Not here: ranks of the cold series of tempered runs (sel=), ladders spread over ranks, chains spread over ranks.
 """
 import ctypes as C
@@ -817,11 +824,227 @@ def rank_convergence(values, site_of_chain, maxlag, exclude=(), dep=None, engine
              for k in ("chains",) + RANK_FIELDS} for s in range(len(parts[0]))]
 
 
+# ---- convergence of structural features (module docstring; include/bh_engine_chain_diag_features.h) ------------------------------
+
+def chain_feature_series(models, features, site_of_series, sel=None, engine=None, nsites=None):
+    """The structural features of every recorded model as time-ordered series (bh_chain_diag_features): models[t][c][2*ML], the
+    store's rows (float32 / float64, a numpy array or a device tensor, strided views read where they lie); features: the dict of
+    posterior.check_features, name -> (kind, z0, z1[, c]) with every number a scalar or one per site -- the same errors, the same
+    labels (name, name.depth, name.jump, name.value); site_of_series[k]: the site whose numbers series k takes (nsites: the number
+    of sites, default the largest site + 1).  sel[t][k] (ladder_index): K series that read chain sel[t][k] at row t instead of the
+    chains' own; rows of chains not selected at a row are never read.
+    Returns (value, present, missing, labels): value float64 [T][K][ncols] -- the column's value, +0.0 where the row lacks it --,
+    present float32 [T][K][ncols] -- 1 where the row has it --, device tensors for a device table and numpy arrays for a numpy one;
+    missing int64 [K][ncols], the rows of series k that lack column q; labels [ncols].  value and present hold, bit for bit, the
+    columns posterior_features / posterior_classes(return_columns=True) form for the same rows.
+    EngineError: a row that is no model, a value that is not finite, an index outside [0, C)."""
+    from .posterior import check_features
+    eng = _engine(engine)
+    ptr, mem, stream, elem, shape, strides, keep = _table(models)
+    if len(shape) != 3 or shape[2] % 2 or shape[2] < 2:
+        raise ValueError("models: [T][C][2*ML]")
+    T, Cn, ML = int(shape[0]), int(shape[1]), int(shape[2]) // 2
+    if T < 1 or Cn < 1:
+        raise ValueError("an empty table")
+    site = np.asarray(site_of_series)
+    if site.ndim != 1 or site.dtype.kind not in "iu" or (site.size and site.min() < 0):
+        raise ValueError("site_of_series: one site (an integer >= 0) per series")
+    S = (int(site.max()) + 1 if site.size else 0) if nsites is None else int(nsites)
+    if site.size and int(site.max()) >= S:
+        raise ValueError("site_of_series: a site beyond nsites")
+    kinds, par, labels = check_features(features, S)
+    ld_t, ld_c = _lds(shape, strides, 2 * ML)
+    if sel is not None:
+        psel, K, ld_sel, keep_sel = _sel_table(sel, T, Cn, mem)
+    else:
+        psel, K, ld_sel, keep_sel = None, Cn, 0, None
+    if site.shape != (K,):
+        raise ValueError("site_of_series: one site per series (%d)" % K)
+    site = np.ascontiguousarray(site, dtype=np.int32)
+    Q = len(labels)
+    if mem == E.DEVICE:
+        import torch
+        value = torch.empty((T, K, Q), dtype=torch.float64, device=keep.device)
+        present = torch.empty((T, K, Q), dtype=torch.float32, device=keep.device)
+        pv, pp = C.c_void_p(value.data_ptr()), C.c_void_p(present.data_ptr())
+    else:
+        value, present = np.empty((T, K, Q)), np.empty((T, K, Q), np.float32)
+        pv, pp = E._ptr(value), E._ptr(present)
+    missing = np.zeros((K, Q), np.int64)
+    eng._check(eng._L.bh_chain_diag_features(eng._h, mem, stream, elem, T, Cn, ML, ld_t, ld_c, ptr, K, psel, ld_sel, S, E._ptr(site),
+                                             len(kinds), E._ptr(kinds), E._ptr(par), pv, pp, K * Q, Q, E._ptr(missing)))
+    del keep, keep_sel
+    return value, present, missing, labels
+
+
+def _ascending_sum(v):
+    """the sum of v [m][Q] over its first axis, row after row in ascending order, starting from 0.0"""
+    acc = np.zeros(v.shape[1:])
+    for row in v:
+        acc = acc + row
+    return acc
+
+
+def pooled_sd(tables, idx):
+    """The deviation of every column pooled over the rows of the chains idx (ascending positions), from the tables of
+    chain_series_stats -- per chain c the mean mean_c = x0 + S1 / T and the sum of squares P_{c,0} about it, T equal:
+        g   = (sum_c mean_c) / m
+        sd  = sqrt((sum_c P_{c,0} + T * sum_c (mean_c - g)^2) / (m T - 1))
+    every sum over the m chains in ascending order from 0.0.  NaN for m T < 2."""
+    T, m = int(tables["T"]), len(idx)
+    Q = tables["x0"].shape[1]
+    if m * T < 2:
+        return np.full(Q, np.nan)
+    mean = tables["x0"][idx] + tables["s1"][idx] / T
+    g = _ascending_sum(mean) / m
+    dev = mean - g
+    return np.sqrt((_ascending_sum(tables["p"][idx, :, 0]) + T * _ascending_sum(dev * dev)) / (m * T - 1))
+
+
+_FEATURE_KEYS = ("rhat", "ess", "tau", "cut", "ess_truncated", "constant", "chain_tau", "chains")
+
+
+def feature_convergence(value, present, missing, site_of_series, maxlag, exclude=(), engine=None, rank=False, budget_bytes=2 << 30,
+                        labels=None):
+    """R-hat, ESS and Monte-Carlo standard errors of every feature column of every site, from the tables of chain_feature_series.
+    site_of_series[k]: the series' site; exclude: positions k left out (outliers).  The columns are walked in chunks so that the
+    tables formed here (8 bytes per element and column, 32 with rank) stay under budget_bytes; every table goes to
+    chain_series_stats, convergence and rank_convergence as it is.  One dict per site, all arrays over the Q columns; with the
+    site's kept series c = 1..m (ascending), T rows each:
+        labels        the columns' labels (where given)
+        chains [m]    the kept positions
+        missing [m][Q] (int64), complete [Q] = no kept row lacks the column,
+        probability [Q] = kept rows with a value / kept rows (m T)
+        presence      the convergence() dict of the indicator series `present`, and mcse_probability [Q] = sd(present) /
+                      sqrt(ess of present).  A column that is never lacking (or always) has a constant indicator: flagged
+                      `constant`, its numbers NaN as for any constant column.
+        mean [Q]      the conditional mean  m_q = (sum_c mean_c(value)) / (sum_c mean_c(present)),  mean_c = x0 + S1 / T of
+                      chain_series_stats, both sums over the kept series in ascending order from 0.0 (T cancels); NaN where no
+                      kept row has the column
+        rhat, ess, tau, cut, ess_truncated, constant [Q], chain_tau [m][Q]: the convergence() numbers of the series
+                      x = value                         where the column is complete at the site,
+                      x = present * (value - m_q)       otherwise -- elementwise in float64 (torch on device tables, numpy on
+                      host ones), the subtraction rounded before the product.
+                      This is the linearised ratio estimator: the conditional mean is a ratio of two chain averages, mu^ = sum_t
+                      I_t v_t / sum_t I_t, and mu^ - mu ~ sum_t I_t (v_t - mu) / (N p): its Monte-Carlo error is that of the
+                      mean of x, so R-hat and ESS of x answer for the number a study publishes, where R-hat of the rows that
+                      have the feature would drop the time order and ignore how presence itself mixes.
+        mcse_mean [Q] = sd(x) / (p_q sqrt(ess)),  p_q = 1 for a complete column and probability[q] otherwise;  sd = pooled_sd,
+                      the deviation of x over the kept rows (its docstring states the expression)
+    A column no kept row has: probability 0, mean NaN, constant True.  A site without a kept series: NaN throughout.
+    rank=True: `rank` = the rank_convergence dict of the value table, with NaN (and False flags) in the columns that are not
+    complete at the site, and presence["rank"] = that of `present`."""
+    tensor = _is_tensor(value)
+    if tensor != _is_tensor(present):
+        raise ValueError("value and present: both numpy arrays or both device tensors")
+    if len(value.shape) != 3 or tuple(value.shape) != tuple(present.shape):
+        raise ValueError("value and present: [T][K][Q] tables of one shape")
+    T, K, Q = (int(v) for v in value.shape)
+    missing = np.asarray(missing, dtype=np.int64)
+    site_of_series = np.asarray(site_of_series, dtype=np.int64)
+    if missing.shape != (K, Q) or site_of_series.shape != (K,):
+        raise ValueError("missing [K][Q] and site_of_series [K] describe the K series of the tables")
+    if labels is not None and len(labels) != Q:
+        raise ValueError("labels: one per column")
+    drop = np.zeros(K, bool)
+    drop[np.asarray(exclude, dtype=np.int64).reshape(-1)] = True
+    S = int(site_of_series.max()) + 1 if K else 0
+    kept = [np.flatnonzero((site_of_series == s) & ~drop) for s in range(S)]
+    complete = np.array([missing[idx].sum(axis=0) == 0 for idx in kept], dtype=bool).reshape(S, Q)
+    L = int(maxlag)
+    step = int(max(1, min(E.DIAG_MAXCOLS, int(budget_bytes) // max(1, (32 if rank else 8) * T * K))))
+    parts = []
+    for q0 in range(0, Q, step):
+        q1 = min(Q, q0 + step)
+        v, p = value[:, :, q0:q1], present[:, :, q0:q1]
+        whole = bool(complete[:, q0:q1].all())
+        tv = chain_series_stats(v, L if whole else 0, engine=engine)
+        tp = chain_series_stats(p, L, engine=engine)
+        mean_v, mean_p = tv["x0"] + tv["s1"] / T, tp["x0"] + tp["s1"] / T
+        with np.errstate(all="ignore"):
+            m = np.array([_ascending_sum(mean_v[idx]) / _ascending_sum(mean_p[idx]) if idx.size else np.full(q1 - q0, np.nan)
+                          for idx in kept]).reshape(S, q1 - q0)
+        if whole:
+            tx = tv
+        else:
+            # the linearised series of the columns that are not complete at the series' site; value itself elsewhere
+            lin = np.zeros((K, q1 - q0), bool)
+            shift = np.zeros((K, q1 - q0))
+            for s, idx in enumerate(kept):
+                lin[site_of_series == s] = ~complete[s, q0:q1]
+                shift[site_of_series == s] = np.where(np.isnan(m[s]), 0.0, m[s])
+            if tensor:
+                import torch
+                tl = torch.as_tensor(lin, device=value.device)
+                x = torch.where(tl, p.to(torch.float64) * (v - torch.as_tensor(shift, device=value.device)), v)
+            else:
+                x = np.where(lin, p.astype(np.float64) * (v - shift), v)
+            tx = chain_series_stats(x, L, engine=engine)
+            del x
+        cx, cp = convergence(tx, site_of_series, exclude), convergence(tp, site_of_series, exclude)
+        rk = rkp = None
+        if rank:
+            rk = rank_convergence(v, site_of_series, L, exclude, engine=engine, budget_bytes=budget_bytes)
+            rkp = rank_convergence(p, site_of_series, L, exclude, engine=engine, budget_bytes=budget_bytes)
+        part = []
+        for s, idx in enumerate(kept):
+            n = idx.size * T
+            r = {k: cx[s][k] for k in _FEATURE_KEYS}
+            r["missing"] = missing[idx, q0:q1]
+            r["complete"] = complete[s, q0:q1]
+            with np.errstate(all="ignore"):
+                prob = (n - r["missing"].sum(axis=0)) / float(n) if n else np.full(q1 - q0, np.nan)
+                r["probability"] = prob
+                r["mean"] = m[s]
+                pq = np.where(r["complete"], 1.0, prob)
+                r["mcse_mean"] = pooled_sd(tx, idx) / (pq * np.sqrt(r["ess"]))
+                r["presence"] = dict(cp[s])
+                r["presence"]["mcse_probability"] = pooled_sd(tp, idx) / np.sqrt(cp[s]["ess"])
+            if rank:
+                gone = ~r["complete"]
+                r["rank"] = {}
+                for k, a in rk[s].items():
+                    if k != "chains":
+                        a = a.copy()
+                        a[gone] = False if a.dtype == bool else np.nan
+                    r["rank"][k] = a
+                r["presence"]["rank"] = rkp[s]
+            part.append(r)
+        parts.append(part)
+
+    out = [_join_columns([p[s] for p in parts]) for s in range(S)]
+    if labels is not None:
+        for r in out:
+            r["labels"] = list(labels)
+    return out
+
+
+def _join_columns(dicts):
+    """the dicts of the column chunks of one site as one: `chains` once, a dict key by key, every array along its last axis"""
+    if len(dicts) == 1:
+        return dicts[0]
+    return {k: (v if k == "chains" else _join_columns([d[k] for d in dicts]) if isinstance(v, dict)
+                else np.concatenate([d[k] for d in dicts], axis=-1)) for k, v in dicts[0].items()}
+
+
+def moho_feature(features, moho, mohovs, S):
+    """The features dict of a call with moho= added: moho = (lo, hi) or one pair per site is the feature "moho": ("above", lo, hi,
+    mohovs) -- the column BH_MOHO_DEPTH of posterior_moho, bit for bit (include/bh_engine_posterior_features.h)."""
+    from .posterior import _per_site
+    features = dict(features) if features is not None else {}
+    if moho is not None:
+        if "moho" in features:
+            raise ValueError("moho= names its feature 'moho': rename the feature of that name")
+        rng = _per_site(moho, S, 2, "moho")
+        features["moho"] = ("above", rng[:, 0].copy(), rng[:, 1].copy(), _per_site(mohovs, S, 0, "mohovs"))
+    return features
+
+
 GROUPS = ("likes", "vpvs", "misfits", "noise", "nlayers", "vs")
 
 
 def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=None, exclude_chains=None, engine=None, sel=None,
-             rank=False, rank_budget_bytes=2 << 30):
+             rank=False, rank_budget_bytes=2 << 30, features=None, moho=None, mohovs=4.2):
     """Outliers and convergence of every site from the tables of a run: tables_of = dict of likes, vpvs [T][C], misfits [T][C][nt+1],
     noise [T][C][2nt], models [T][C][2*ML] (numpy arrays or device tensors).  chain_ids[c]: the chain's number (what `outliers` and
     exclude_chains hold).  One dict per site: outliers, scores, chain_ids, dep, maxlag, and for every name of GROUPS the dict of
@@ -830,7 +1053,13 @@ def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=Non
     describe the K series (the ladders' sites and ids), and everything downstream sees tables of K series.
     rank=True: every group's dict gains the key "rank", the dict of rank_convergence -- the kept chains of a site pooled after the
     outlier rule or exclude_chains has decided who is kept; ValueError with sel (ranks of cold series are not formed).  With the
-    default nothing of it runs."""
+    default nothing of it runs.
+    features (the dict of posterior_features: name -> (kind, z0, z1[, c]), every number a scalar or one per site) and / or
+    moho = (lo, hi) or one pair per site, with mohovs (the feature "moho": ("above", lo, hi, mohovs), posterior_moho's depth column
+    bit for bit): every site's dict gains the key "features", the dict of feature_convergence -- R-hat, ESS and the Monte-Carlo
+    standard error of every feature column over the site's kept chains, `chains` as chain numbers.  The series are formed on the
+    GPU from the model rows where they lie (chain_feature_series; with sel the cold series are read in place).  With the defaults
+    nothing of it runs and every dict has the keys it has without."""
     if rank and sel is not None:
         raise ValueError("rank=True with sel=: the ranks of the cold series of tempered runs are not formed")
     chain_ids = np.asarray(chain_ids, dtype=np.int64)
@@ -862,6 +1091,16 @@ def diagnose(tables_of, site_of_chain, chain_ids, dev=0.05, dep=None, maxlag=Non
         out[s]["nlayers"] = {k: (v if k == "chains" else v[..., D]) for k, v in both[s].items()}
         for k in GROUPS:
             out[s][k]["chains"] = chain_ids[out[s][k]["chains"]]
+    if features is not None or moho is not None:
+        fts = moho_feature(features, moho, mohovs, S)
+        value, present, missing, labels = chain_feature_series(tables_of["models"], fts, site_of_chain, sel=sel, engine=engine, nsites=S)
+        fc = feature_convergence(value, present, missing, site_of_chain, L, exclude, engine=engine, rank=rank,
+                                 budget_bytes=rank_budget_bytes, labels=labels)
+        del value, present
+        for s in range(S):
+            out[s]["features"] = fc[s]
+            for d in (fc[s], fc[s]["presence"]) + ((fc[s]["rank"], fc[s]["presence"]["rank"]) if rank else ()):
+                d["chains"] = chain_ids[d["chains"]]
     if rank:
         rk = {k: rank_convergence(tables_of[k], site_of_chain, L, exclude, engine=engine, budget_bytes=rank_budget_bytes)
               for k in ("likes", "vpvs", "misfits", "noise")}

@@ -268,6 +268,10 @@ def load_library():
                                        C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int64]
     for name in CHAIN_RANK_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_chain_diag_features.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, vp, C.c_int, vp,
+                                         C.c_int64, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int64, vp]
+    for name in CHAIN_DIAG_FEATURES_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_debug_guard_list", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_probe_swd_secular", "bh_chain_propose", "bh_chain_accept",
@@ -380,6 +384,9 @@ LADDER_SWEEP_SYMBOLS = ("bh_ladder_sweep_create", "bh_ladder_sweep_run", "bh_lad
 CHAIN_RANK_SYMBOLS = ("bh_chain_rank_series", "bh_chain_rank_models")
 RANK_TILE = 4096                    # BH_RANK_TILE
 RANK_RADIXBITS = 8                  # BH_RANK_RADIXBITS
+# include/bh_engine_chain_diag_features.h: the structural features of the store's model rows as time-ordered series, value and
+# presence (bayhunter_amd/diagnostics.py: chain_feature_series, feature_convergence)
+CHAIN_DIAG_FEATURES_SYMBOLS = ("bh_chain_diag_features",)
 
 
 def _f64(a):

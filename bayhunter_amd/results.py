@@ -190,20 +190,36 @@ def posterior_from_storage(datapaths, dep_int=None, engine=None, quantiles=None)
                             quantiles=quantiles)
 
 
-def diagnostics_from_storage(datapaths, dep=None, maxlag=None, dev=0.05, exclude_chains=None, engine=None, rank=False):
+def _site_features(features, moho, mohovs, S, s):
+    """features, moho, mohovs of site s of S: a number given per site takes the site's position"""
+    from .posterior import _per_site, check_features
+    if features is not None:
+        check_features(features, S)
+        features = {name: (spec[0],) + tuple(float(np.broadcast_to(np.asarray(v, np.float64), (S,))[s]) for v in spec[1:])
+                    for name, spec in features.items()}
+    if moho is not None:
+        moho, mohovs = tuple(_per_site(moho, S, 2, "moho")[s]), float(_per_site(mohovs, S, 0, "mohovs")[s])
+    return features, moho, mohovs
+
+
+def diagnostics_from_storage(datapaths, dep=None, maxlag=None, dev=0.05, exclude_chains=None, engine=None, rank=False, features=None,
+                             moho=None, mohovs=4.2):
     """Outlier chains, split R-hat and effective sample sizes of many sites from saved folders (bayhunter_amd.diagnostics, what
     DeviceChains.diagnostics gives from the device store): datapaths[s] is site s's data directory; its main-phase chain files
     c???_p2{likes,vpvs,misfits,noise,models}.npy -- per chain and time-ordered -- are stacked to [T][C][..] tables and go through
     the same calls.  `outliers` and `exclude_chains` (None: the outliers; else one sequence for all sites) are file numbers.
     rank=True: every group's dict gains "rank", the rank-normalised R-hat and the bulk and tail ESS (diagnostics.rank_convergence).
+    features, moho, mohovs: as DeviceChains.diagnostics -- every site's dict gains "features" (diagnostics.feature_convergence);
+    one folder is one site, and a number given per site takes the folder's position.
     ValueError: chains of unequal length.  Returns one dict per site."""
     from .diagnostics import diagnose, stack_chain_files
     out = []
-    for p in datapaths:
+    for s, p in enumerate(datapaths):
         tabs, ids = stack_chain_files(p)
         ex = None if exclude_chains is None else [c for c in np.atleast_1d(exclude_chains) if c in ids]
+        ft, mo, mv = _site_features(features, moho, mohovs, len(datapaths), s)
         out.append(diagnose(tabs, np.zeros(ids.size, np.int64), ids, dev=dev, dep=dep, maxlag=maxlag, exclude_chains=ex,
-                            engine=engine, rank=rank)[0])
+                            engine=engine, rank=rank, features=ft, moho=mo, mohovs=mv)[0])
     return out
 
 
