@@ -26,6 +26,7 @@ import numpy as np
 
 from . import engine as _engine
 from .rfmini_modrf import RFminiModRF
+from .surf96_ellip import SurfEllip
 from .surf96_modsw import SurfDisp
 
 logger = logging.getLogger()
@@ -56,6 +57,9 @@ class ModeledData(object):
             self.xlabel = "Time in s"
         elif ref in ("rdispph", "ldispph", "rdispgr", "ldispgr"):
             self.plugin = SurfDisp(obsx, ref)
+            self.xlabel = "Period in s"
+        elif ref == "rellip":
+            self.plugin = SurfEllip(obsx, ref)
             self.xlabel = "Period in s"
         else:
             logger.info("Please provide a forward modeling plugin for your target.\n"
@@ -299,6 +303,17 @@ class SReceiverFunction(SingleTarget):
         SingleTarget.__init__(self, x, y, "srf", yerr=yerr)
 
 
+class RayleighEllipticity(SingleTarget):
+    """Rayleigh-wave ellipticity (H/V) of the fundamental mode at periods x (bayhunter_amd/surf96_ellip.py).  Its noise priors are
+    `ellnoise_corr` / `ellnoise_sigma` -- the reference's mechanism for a user target's noiseref: the datum is dimensionless and
+    does not share the km/s sigma of the dispersion curves.  Not engine-backed: its synthetics come from one batched call of
+    its plugin and go to `bh_loglike_batch` (JointTarget.evaluate_batch); the fused call and the device chains do not run it."""
+    noiseref = "ell"
+
+    def __init__(self, x, y, yerr=None):
+        SingleTarget.__init__(self, x, y, "rellip", yerr=yerr)
+
+
 def select_noise_laws(targets, corrfix, noise_corr, rcond=None):
     """Choose each target's covariance law the way SingleChain.set_target_covariance does
     (src/SingleChain.py:159-205): correlation prior is a range -> exponential; fixed 0 ->
@@ -371,7 +386,7 @@ class JointTarget(object):
         for it, t in enumerate(self.targets):
             lo, hi = self._offsets[it], self._offsets[it + 1]
             p = t.moddata.plugin
-            if isinstance(p, SurfDisp):
+            if isinstance(p, (SurfDisp, SurfEllip)):   # one batched call each; a model it fails fails in band
                 _, y, err = p.run_models(nlay, h, vp, vs, rho)
                 ymod[:, lo:hi] = np.nan_to_num(y)
                 fail[it] = err

@@ -4,10 +4,11 @@ loaded when the first `Engine` is created."""
 from .engine import Engine, EngineError, default_engine, pack_models  # noqa: F401
 from .Models import Model, ModelMatrix  # noqa: F401
 from .surf96_modsw import SurfDisp  # noqa: F401
+from .surf96_ellip import SurfEllip  # noqa: F401
 from .rfmini_modrf import RFminiModRF  # noqa: F401
 from .Targets import (ObservedData, ModeledData, Valuation, SingleTarget, JointTarget,  # noqa: F401
                       RayleighDispersionPhase, RayleighDispersionGroup, LoveDispersionPhase,
-                      LoveDispersionGroup, PReceiverFunction, SReceiverFunction, select_noise_laws)
+                      LoveDispersionGroup, PReceiverFunction, SReceiverFunction, RayleighEllipticity, select_noise_laws)
 from .chains import ChainBatch, MCMC_Optimizer  # noqa: F401
 from .results import save_config, save_final_distribution, get_outliers, posterior_from_storage, moho_from_storage, features_from_storage, covariance_from_storage, datafits_from_storage, residuals_from_storage, diagnostics_from_storage  # noqa: F401
 from .sites import SiteTargets  # noqa: F401

@@ -291,6 +291,12 @@ class DeviceChains(object):
         self.ladder_adapt = ladder_adapt_options(ladder_adapt, betas, ladder, swap_every, dist)
         self.sites = targets if isinstance(targets, SiteTargets) else None
         self.nsites = 1 if self.sites is None else self.sites.nsites
+        if self.sites is None:   # (SiteTargets refuses it itself: "a user plugin")
+            from .Targets import RayleighEllipticity
+            for t in (targets.targets if isinstance(targets, JointTarget) else targets):
+                if isinstance(t, RayleighEllipticity):
+                    raise EngineError("DeviceChains does not run RayleighEllipticity: the device chains evaluate engine-backed "
+                                      "targets in one fused call, and the ellipticity is not part of it yet (ChainBatch runs it)")
         # (checked before anything touches the GPU)
         self.site_initparams, self.site_priors, differ = site_dicts(initparams, modelpriors, self.nsites, self.sites is not None)
         if prior_table and self.sites is None:

@@ -272,6 +272,10 @@ def load_library():
                                          C.c_int64, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int64, vp]
     for name in CHAIN_DIAG_FEATURES_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_swd_ellip.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_ssize_t, C.c_ssize_t, C.c_int, vp,
+                               C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+    for name in SWD_ELLIP_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_debug_guard_list", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_probe_swd_secular", "bh_chain_propose", "bh_chain_accept",
@@ -387,6 +391,10 @@ RANK_RADIXBITS = 8                  # BH_RANK_RADIXBITS
 # include/bh_engine_chain_diag_features.h: the structural features of the store's model rows as time-ordered series, value and
 # presence (bayhunter_amd/diagnostics.py: chain_feature_series, feature_convergence)
 CHAIN_DIAG_FEATURES_SYMBOLS = ("bh_chain_diag_features",)
+# include/bh_engine_swd_ellip.h: the Rayleigh ellipticity (H/V) of the fundamental mode from the compound vector at the root
+# (Engine.swd_ellip; bayhunter_amd/surf96_ellip.py)
+SWD_ELLIP_SYMBOLS = ("bh_swd_ellip",)
+ELLIP_MAXSTEPS = 3                  # nsteps of bh_swd_ellip: 0..3
 
 
 def _f64(a):
@@ -753,6 +761,34 @@ class Engine(object):
                                          int(igr), int(mode), int(flsph), _ptr(vel), _ptr(err)))
         return vel, err
 
+    def swd_ellip(self, nlay, h, vp, vs, rho, periods, vel=None, err=None, nsteps=2, layout="layer_major"):
+        """Rayleigh ellipticity of the fundamental mode (include/bh_engine_swd_ellip.h): hv = u_r / u_z at the surface, positive =
+        retrograde.  vel [B, K] and err [B] given: the phase velocities to start from; else the engine's own Rayleigh phase
+        search runs first (with the search and arithmetic it is set to).  nsteps: secant steps of the polish (0..3).
+        Returns a dict: hv [B, K], mismatch [B, K] (the relative difference of the two expressions of hv: a bound of its
+        error), c [B, K] (the velocity hv was evaluated at), vel [B, K], err [B], flag [B] (a step of the polish left the window of
+        1e-5 c, or a value is not a number).  A model without a root (err != 0) and an entry with vel <= 0 are zero rows."""
+        B, Lmax, sl, sb, nlay, (h, vp, vs, rho) = self._model_args(nlay, h, vp, vs, rho, layout)
+        periods = _f64(periods).reshape(-1)
+        K = periods.size
+        if (vel is None) != (err is None):
+            raise ValueError("vel and err go together")
+        have = vel is not None
+        if have:
+            vel = np.array(vel, dtype=np.float64, order="C")
+            err = np.array(err, dtype=np.int32, order="C")
+            if vel.shape != (B, K) or err.shape != (B,):
+                raise ValueError("vel must have shape (B, K) and err (B,)")
+        else:
+            vel = np.zeros((B, K))
+            err = np.zeros(B, dtype=np.int32)
+        hv, mis, cpol = np.zeros((B, K)), np.zeros((B, K)), np.zeros((B, K))
+        flag = np.zeros(B, dtype=np.int32)
+        self._check(self._L.bh_swd_ellip(self._h, HOST, None, B, Lmax, _ptr(nlay), _ptr(h), _ptr(vp), _ptr(vs), _ptr(rho), sl, sb,
+                                         K, _ptr(periods), int(have), _ptr(vel), _ptr(err), int(nsteps), _ptr(hv), _ptr(mis),
+                                         _ptr(cpol), _ptr(flag)))
+        return {"hv": hv, "mismatch": mis, "c": cpol, "vel": vel, "err": err, "flag": flag}
+
     def rf_batch(self, nlay, h, vp, vs, rho, p, gauss, nsamp, fsamp, tshift, waveno, nkeep,
                  nsv=0.0, qp=None, qs=None, layout="layer_major"):
         """Batched rfmini synrf.  Returns rf[B, nkeep]."""
@@ -998,6 +1034,12 @@ class Engine(object):
                       stream=None, mode=1, flsph=0):
         self._check(self._L.bh_swd_batch(self._h, DEVICE, stream, B, Lmax, nlay, h, vp, vs, rho, sl, sb,
                                          K, periods, iwave, igr, mode, flsph, vel, err))
+
+    def swd_ellip_dev(self, B, Lmax, nlay, h, vp, vs, rho, sl, sb, K, periods, vel, err, hv, flag, have_vel=False, nsteps=2,
+                      mismatch=None, cpol=None, stream=None):
+        """bh_swd_ellip on device pointers, enqueued on `stream` (None: the engine's); vel / err are written unless have_vel."""
+        self._check(self._L.bh_swd_ellip(self._h, DEVICE, stream, B, Lmax, nlay, h, vp, vs, rho, sl, sb, K, periods,
+                                         int(bool(have_vel)), vel, err, int(nsteps), hv, mismatch, cpol, flag))
 
     def rf_batch_dev(self, B, Lmax, nlay, h, vp, vs, rho, sl, sb, p, gauss, nsamp, fsamp, tshift,
                      waveno, nkeep, rf, stream=None, nsv=0.0, qp=None, qs=None):
