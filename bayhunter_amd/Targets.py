@@ -306,12 +306,30 @@ class SReceiverFunction(SingleTarget):
 class RayleighEllipticity(SingleTarget):
     """Rayleigh-wave ellipticity (H/V) of the fundamental mode at periods x (bayhunter_amd/surf96_ellip.py).  Its noise priors are
     `ellnoise_corr` / `ellnoise_sigma` -- the reference's mechanism for a user target's noiseref: the datum is dimensionless and
-    does not share the km/s sigma of the dispersion curves.  Not engine-backed: its synthetics come from one batched call of
-    its plugin and go to `bh_loglike_batch` (JointTarget.evaluate_batch); the fused call and the device chains do not run it."""
+    does not share the km/s sigma of the dispersion curves.
+
+    fused=False (default): not engine-backed -- its synthetics come from one batched call of its plugin and go to
+    `bh_loglike_batch` (JointTarget.evaluate_batch); the fused call, the device chains and the site sets do not run it.
+    fused=True: engine-backed (include/bh_engine_ellip_target.h) -- the engine registers the target with a forward model of its
+    own, the fused call computes it, beside a Rayleigh phase-velocity target at the same periods from THAT target's search, and
+    `DeviceChains` and `SiteTargets` take it.  The synthetics of a model that does not fail are the bits of the default route."""
     noiseref = "ell"
 
-    def __init__(self, x, y, yerr=None):
+    def __init__(self, x, y, yerr=None, fused=False):
         SingleTarget.__init__(self, x, y, "rellip", yerr=yerr)
+        self.fused = bool(fused)
+
+    def engine_backed(self):
+        return self.fused and isinstance(self.moddata.plugin, SurfEllip)
+
+    def engine_desc(self):
+        """A BH_TARGET_USER descriptor for `bh_targets_set`; fused=True: with the periods x and the plugin's nsteps / signed /
+        ratio beside it, from which `Engine.set_targets` calls `bh_targets_set_ellip`."""
+        d = SingleTarget.engine_desc(self)
+        if self.engine_backed():
+            p = self.moddata.plugin.modelparams
+            d.update(x=np.asarray(self.obsdata.x, dtype=float), nsteps=int(p["nsteps"]), signed=bool(p["signed"]), ratio=p["ratio"])
+        return d
 
 
 def select_noise_laws(targets, corrfix, noise_corr, rcond=None):

@@ -541,6 +541,24 @@ struct SitePlan {
 SitePlan bh_plan_sites(const SitePlanAsk &q);
 const char *bh_site_refusal_text(int refusal); // the message of a SiteRefusal ("" for REFUSE_NONE)
 
+// ---- the ellipticity target of a fused call (include/bh_engine_ellip_target.h; swd_ellip.hip, run_forward) ----
+// One BH_TARGET_ELLIP target: a lane per (model, period) reads its velocity from vel (row stride ldvel: the columns of the
+// dispersion target it shares the search with, or its own search's workspace), evaluates and polishes as bh_swd_ellip does, and
+// writes y = the header's transform of hv -- 0.0 where that is not finite -- to y (the target's columns of ymod, row stride ldy).
+// err_row: the target's row of err_t, which holds the search's failure flags when the kernel starts; a lane whose entry raises
+// bh_swd_ellip's flag, or whose y is not finite, ORs 1 into its model's word.
+struct EllipFusedArgs {
+    int B, Lmax, K, nsteps, is_signed, zh;
+    const int32_t *nlay;
+    const double *h, *vp, *vs, *rho; // device
+    ptrdiff_t sl, sb;
+    const double *periods;           // [K] device
+    const double *vel; int ldvel;
+    double *y; int ldy;
+    int32_t *err_row;
+};
+void bh_launch_ellip_fused(const EllipFusedArgs &a, hipStream_t stream);
+
 // out = [val n][bound n][certified n]
 
 // the engine as other translation units reach it (bh_engine.hip; posterior_kernel.hip, include/bh_engine_posterior.h)

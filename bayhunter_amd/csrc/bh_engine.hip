@@ -13,6 +13,7 @@
 #include "../../include/bh_engine_sites_gauss.h"
 #include "../../include/bh_engine_sites_rf_axis.h"
 #include "../../include/bh_engine_sites_laws.h"
+#include "../../include/bh_engine_ellip_target.h"
 #include "bh_device.h"
 
 #include <algorithm>
@@ -106,6 +107,13 @@ struct TargetHost {
     DevBuf x60, vel60; // > 60 periods: the 60-point grid the forward model runs on + its output
     int kfwd = 0;      // periods the forward model computes (n, or 60 when n > 60)
     double logdet_extra = 0.0;
+    // what the plan of an ellipticity target compares (bh_plan_ellip): the periods of a dispersion or ellipticity target as
+    // registered, and an id of their bit pattern among the registered targets (equal ids = equal bits; -1: none)
+    std::vector<double> x_host;
+    int xid = -1;
+    // BH_TARGET_ELLIP (bh_targets_set_ellip): the polish steps and the transform; the velocities of a search of its own
+    int ell_nsteps = 0, ell_signed = 0, ell_zh = 0;
+    DevBuf ell_vel;    // [B][n]
 };
 
 void release(DevBuf &b)
@@ -274,7 +282,7 @@ SitePlan bh_plan_sites(const SitePlanAsk &q)
     bool have_rf = false, no_forward = false;
     for (int t = 0; t < q.nt; ++t) {
         have_rf = have_rf || q.t[t].kind == BH_TARGET_RF;
-        no_forward = no_forward || (q.t[t].kind != BH_TARGET_SWD && q.t[t].kind != BH_TARGET_RF);
+        no_forward = no_forward || (q.t[t].kind != BH_TARGET_SWD && q.t[t].kind != BH_TARGET_RF && q.t[t].kind != BH_TARGET_ELLIP);
     }
     // (periods per site: every dispersion job reads its models' periods and counts from the table)
     p.x_table = q.sites && q.level >= SITES_X;
@@ -319,6 +327,24 @@ SitePlan bh_plan_sites(const SitePlanAsk &q)
     return p;
 }
 
+// ---- the ellipticity targets' part of a fused call's plan (include/bh_engine_ellip_target.h): pure, no HIP call, no engine ----
+extern "C" int bh_plan_ellip(int nt, const bh_ellip_plan_target *T, int x_table, int32_t *source)
+{
+    if (nt < 0 || nt > BH_MAX_TARGETS || (nt > 0 && (!T || !source))) return -1;
+    int own = 0;
+    for (int t = 0; t < nt; ++t) {
+        source[t] = -2;
+        if (T[t].kind != BH_TARGET_ELLIP) continue;
+        source[t] = -1;
+        for (int j = 0; j < nt && !x_table && source[t] < 0; ++j) // (under a period table target j runs at its sites' periods)
+            if (T[j].kind == BH_TARGET_SWD && T[j].iwave == BH_WAVE_RAYLEIGH && T[j].igr == BH_VEL_PHASE && T[j].mode <= 1 &&
+                T[j].flsph == 0 && T[j].n <= BH_MAX_PERIODS && T[j].n == T[t].n && T[j].xid >= 0 && T[j].xid == T[t].xid)
+                source[t] = j;
+        own += source[t] < 0;
+    }
+    return own;
+}
+
 namespace {
 
 int fail(bh_engine *e, int code, const char *what, hipError_t he = hipSuccess)
@@ -360,7 +386,7 @@ int ensure(bh_engine *e, DevBuf &b, size_t bytes)
 // every device buffer a registered target owns
 void release_target(TargetHost &t)
 {
-    for (DevBuf *b : {&t.x, &t.yobs, &t.yerr_scaled, &t.rinv, &t.quad, &t.sums, &t.x60, &t.vel60}) release(*b);
+    for (DevBuf *b : {&t.x, &t.yobs, &t.yerr_scaled, &t.rinv, &t.quad, &t.sums, &t.x60, &t.vel60, &t.ell_vel}) release(*b);
 }
 
 // Targets.py:124-128, the nocorr_scalederr law: out = yerr / min(yerr), returns ln prod(out) (bh_targets_set, bh_sites_set)
@@ -735,14 +761,16 @@ SwdPlan plan_swd(const bh_engine *e, int B, int Lmax, int typ_given, int njobs, 
 }
 
 // What a target does in a fused call: nothing (a BH_TARGET_USER target has no forward model), dispersion at its own periods,
-// dispersion on the 60-period grid followed by interpolation, or a receiver function.
-enum EvalRole { ROLE_NONE, ROLE_SWD, ROLE_SWD60, ROLE_RF };
+// dispersion on the 60-period grid followed by interpolation, a receiver function, or the ellipticity from the velocities of a
+// dispersion target of the call or of a search of its own (include/bh_engine_ellip_target.h).
+enum EvalRole { ROLE_NONE, ROLE_SWD, ROLE_SWD60, ROLE_RF, ROLE_ELLIP };
 // What one fused call (bh_evaluate_batch, bh_evaluate_sites) does: everything its steps would otherwise decide.
 struct EvalPlan {
     int B, nt, ldy;
     EvalRole role[BH_MAX_TARGETS];
     bool rf_fused[BH_MAX_TARGETS]; // receiver function: the synthesis kernel writes the likelihood's sums, not the trace
-    int nswd;                   // dispersion jobs of the call
+    int nswd;                   // dispersion jobs of the call: the dispersion targets' and the ellipticity targets' own searches
+    int ell_source[BH_MAX_TARGETS]; // ROLE_ELLIP: the target whose velocities and failure flags it reads, or -1: a search of its own (bh_plan_ellip)
     bool fork;                  // the receiver functions run on the second stream, beside the dispersion launch
     bool want_gate;             // ... which waits for that launch's started workgroups (where the launch has any: gate_need)
     int prio_low;               // SwdMultiArgs::prio_low of the dispersion launch
@@ -791,6 +819,21 @@ EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
     // The receiver-function kernels are independent of the dispersion kernel and write other columns
     // of ymod: they run on a second stream so that their (throughput-bound) wavefronts fill the issue
     // slots the (latency-bound) dispersion wavefronts leave idle.  fork -> [swd | rf] -> join -> like.
+    p.sites = bh_plan_sites(site_plan_ask(e, sites));
+    {
+        bh_ellip_plan_target q[BH_MAX_TARGETS];
+        bool any = false;
+        for (int t = 0; t < p.nt; ++t) {
+            const TargetHost &T = e->targets[(size_t)t];
+            q[t] = bh_ellip_plan_target{T.d.kind, T.d.iwave, T.d.igr, T.d.mode, T.d.flsph, T.d.n, T.xid};
+            any = any || T.d.kind == BH_TARGET_ELLIP;
+        }
+        if (any) { // (the ids of SWD targets compare the DESCRIPTORS' periods: not what target j runs at under a period table)
+            p.nswd += bh_plan_ellip(p.nt, q, p.sites.x_table, p.ell_source);
+            for (int t = 0; t < p.nt; ++t)
+                if (p.ell_source[t] != -2) p.role[t] = ROLE_ELLIP;
+        }
+    }
     p.fork = have_rf && p.nswd > 0 && e->overlap_rf;
     // Start gate.  The dispersion group kernel counts on ALL its wavefronts being co-resident (one round of wavefronts,
     // two per SIMD); an RF workgroup that takes a wave slot first displaces a dispersion wavefront for a whole lifetime
@@ -806,7 +849,6 @@ EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
     // (RF wavefronts move in beside the last dispersion wavefronts of a SIMD as its short ones end: the dispersion
     // wavefronts' unfavoured phase runs at priority 1 then, above the RF's 0)
     p.prio_low = p.want_gate ? e->swd_prio_low : 0;
-    p.sites = bh_plan_sites(site_plan_ask(e, sites));
     p.err_zero_always = tun.err_memset != 0;
     return p;
 }
@@ -1857,6 +1899,22 @@ int bh_rf_batch(bh_engine *e, int memspace, void *stream, int B, int Lmax, const
     return BH_OK;
 }
 
+// The id of the bit pattern of target i's periods (x_host) among targets 0 .. i-1 and itself: the id of the first with the same
+// bits, else one more than the largest
+static int period_id(const std::vector<TargetHost> &ts, int i, int upto = -1)
+{
+    const std::vector<double> &x = ts[(size_t)i].x_host;
+    int next = 0;
+    for (int j = 0; j < (upto < 0 ? i : upto); ++j) {
+        if (j == i) continue;
+        const TargetHost &o = ts[(size_t)j];
+        if (o.xid < 0) continue;
+        if (o.x_host.size() == x.size() && std::memcmp(o.x_host.data(), x.data(), x.size() * sizeof(double)) == 0) return o.xid;
+        next = std::max(next, o.xid + 1);
+    }
+    return next;
+}
+
 int bh_targets_set(bh_engine *e, int nt, const bh_target_desc *td)
 {
     if (!e) return BH_EINVAL;
@@ -1898,6 +1956,10 @@ int bh_targets_set(bh_engine *e, int nt, const bh_target_desc *td)
             rc = ensure(e, t.x, nb);
             if (!rc && hipMemcpy(t.x.p, d.x, nb, hipMemcpyHostToDevice) != hipSuccess) rc = fail(e, BH_EHIP, "copy x");
             t.kfwd = d.n;
+            if (!rc) {
+                t.x_host.assign(d.x, d.x + d.n);
+                t.xid = period_id(tmp, i);
+            }
             if (!rc && d.n > BH_MAX_PERIODS) {
                 // surf96_modsw.py:35-43: np.linspace(min, max, 60), velocities interpolated back (:119-122)
                 double lo = d.x[0], hi = d.x[0];
@@ -1936,6 +1998,34 @@ int bh_targets_set(bh_engine *e, int nt, const bh_target_desc *td)
     e->targets.swap(tmp);
     e->nt = nt;
     e->ldy = off;
+    e->err_t_nt = e->err_t_B = -1;
+    return BH_OK;
+}
+
+int bh_targets_set_ellip(bh_engine *e, int t, int K, const double *periods, int nsteps, int is_signed, int zh)
+{
+    if (!e) return BH_EINVAL;
+    if (t < 0 || t >= e->nt) return fail(e, BH_EINVAL, "bh_targets_set_ellip: no such target (bh_targets_set)");
+    if (e->sites.nsites > 0) return fail(e, BH_EINVAL, "bh_targets_set_ellip: a site table is in force (call it between bh_targets_set and bh_sites_set*)");
+    TargetHost &T = e->targets[(size_t)t];
+    if (T.d.kind != BH_TARGET_USER) return fail(e, BH_EINVAL, "bh_targets_set_ellip: the target is not a BH_TARGET_USER");
+    if (K != T.d.n) return fail(e, BH_EINVAL, "bh_targets_set_ellip: K differs from the target's n");
+    if (K < 1 || K > BH_MAX_PERIODS) return fail(e, BH_EINVAL, "bh_targets_set_ellip: K must be 1..60");
+    if (!periods) return fail(e, BH_EINVAL, "bh_targets_set_ellip: null periods");
+    for (int k = 0; k < K; ++k)
+        if (!std::isfinite(periods[k]) || !(periods[k] > 0.0)) return fail(e, BH_EINVAL, "bh_targets_set_ellip: a period that is not finite and positive");
+    if (nsteps < 0 || nsteps > 3) return fail(e, BH_EINVAL, "bh_targets_set_ellip: nsteps must be 0..3");
+    HIPCHK(e, hipSetDevice(e->device));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    int rc = ensure(e, T.x, (size_t)K * sizeof(double));
+    if (rc) return rc;
+    HIPCHK(e, hipMemcpy(T.x.p, periods, (size_t)K * sizeof(double), hipMemcpyHostToDevice));
+    T.x_host.assign(periods, periods + K);
+    T.xid = period_id(e->targets, t, e->nt);
+    T.ell_nsteps = nsteps; T.ell_signed = is_signed != 0; T.ell_zh = zh != 0;
+    T.d.kind = BH_TARGET_ELLIP;
+    T.d.iwave = BH_WAVE_RAYLEIGH; T.d.igr = BH_VEL_PHASE; T.d.mode = 1; T.d.flsph = 0; // (what its own search runs)
+    T.kfwd = K;
     e->err_t_nt = e->err_t_B = -1;
     return BH_OK;
 }
@@ -2032,6 +2122,7 @@ int size_eval_workspaces(bh_engine *e, const EvalPlan &p, EvalCall &c)
         TargetHost &T = e->targets[(size_t)t];
         if (p.role[t] == ROLE_SWD60 && (rc = ensure(e, T.vel60, (size_t)p.B * T.kfwd * sizeof(double)))) return rc;
         if (p.rf_fused[t] && (rc = ensure(e, T.sums, (size_t)p.B * 4 * sizeof(double)))) return rc;
+        if (p.role[t] == ROLE_ELLIP && p.ell_source[t] < 0 && (rc = ensure(e, T.ell_vel, (size_t)p.B * T.d.n * sizeof(double)))) return rc;
     }
     return BH_OK;
 }
@@ -2057,6 +2148,16 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
         } else if (p.role[t] == ROLE_SWD60) {
             jobs[njobs++] = SwdJob{T.kfwd, d.iwave, d.igr, T.kfwd, (const double *)T.x60.p, (double *)T.vel60.p, errp, d.mode, d.flsph};
         }
+    }
+    // (the ellipticity targets' own searches come after the dispersion targets' jobs: those keep their places in the launch and
+    // in the guard's statistics.  Under a period table the job reads the table's column of its target, which holds the periods
+    // every site shares.)
+    for (int t = 0; t < nt; ++t) {
+        if (p.role[t] != ROLE_ELLIP || p.ell_source[t] >= 0) continue;
+        const TargetHost &T = e->targets[(size_t)t];
+        jobs[njobs++] = SwdJob{T.d.n, BH_WAVE_RAYLEIGH, BH_VEL_PHASE, T.d.n, (const double *)T.x.p, (double *)T.ell_vel.p,
+                               (int32_t *)e->err_t.p + (size_t)t * B, 1, 0};
+        if (sp.x_table) jobs[njobs - 1].sx = SwdSiteJob{&xtab, t, T.off, sp.x_all};
     }
     // per-target failure flags [nt][B]: the dispersion kernels write every entry of their target's row on every call,
     // nothing writes the rows of the other targets -- they are zeroed once per (nt, B) layout, not once per call; by the dispersion
@@ -2105,6 +2206,27 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
             rs.nsamp_max = S.t[t].axis_nsamp_max;
         }
         if ((rc = launch_rf(e, rst, B, c.Lmax, c.m, c.sl, c.sb, job, p.fork, gate))) return rc;
+    }
+    // The ellipticities, on the call's stream behind the dispersion launches (the guard's re-run included: the velocities are
+    // final) and before the join.  Row t of err_t is written in full on every call: by the target's own search, or by a copy of
+    // the row of the target whose search it shares; the kernel ORs its own failures into it.
+    for (int t = 0; t < nt; ++t) {
+        if (p.role[t] != ROLE_ELLIP) continue;
+        const TargetHost &T = e->targets[(size_t)t];
+        const int j = p.ell_source[t];
+        int32_t *row = (int32_t *)e->err_t.p + (size_t)t * B;
+        if (j >= 0)
+            HIPCHK(e, hipMemcpyAsync(row, (const int32_t *)e->err_t.p + (size_t)j * B, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        EllipFusedArgs a{};
+        a.B = B; a.Lmax = c.Lmax; a.K = T.d.n; a.nsteps = T.ell_nsteps; a.is_signed = T.ell_signed; a.zh = T.ell_zh;
+        a.nlay = c.m.nlay; a.h = c.m.h; a.vp = c.m.vp; a.vs = c.m.vs; a.rho = c.m.rho;
+        a.sl = c.sl; a.sb = c.sb;
+        a.periods = (const double *)T.x.p;
+        a.vel = j >= 0 ? c.ymod + e->targets[(size_t)j].off : (const double *)T.ell_vel.p;
+        a.ldvel = j >= 0 ? ldy : T.d.n;
+        a.y = c.ymod + T.off; a.ldy = ldy;
+        a.err_row = row;
+        bh_launch_ellip_fused(a, st);
     }
     return p.fork ? wait_for(e, e->ev_join, e->aux, st) : BH_OK;
 }
@@ -2274,6 +2396,9 @@ static int sites_register_x(bh_engine *e, const char *who, SiteLevel level, int 
             for (size_t s = 0; s < S; ++s) {
                 if (admits_rf_counts && d.kind == BH_TARGET_RF && n[s * nt + t] >= 0 && n[s * nt + t] <= d.n) continue;
                 if (admits_rf_counts && d.kind == BH_TARGET_RF) return fail(e, BH_EINVAL, (w + ": a receiver function's sample count is below 0 or above its descriptor's n (the capacity)").c_str());
+                if (d.kind == BH_TARGET_ELLIP && n[s * nt + t] == 0) return fail(e, BH_EUNSUPPORTED, (w + ": an ellipticity target that a site lacks").c_str());
+                if (d.kind == BH_TARGET_ELLIP && n[s * nt + t] == d.n && std::memcmp(T.x_host.data(), x + s * ldy + T.off, (size_t)d.n * sizeof(double)) != 0)
+                    return fail(e, BH_EINVAL, (w + ": an ellipticity target's periods differ from its registered ones (every site shares them)").c_str());
                 if (n[s * nt + t] != d.n && !(admits_absent && n[s * nt + t] == 0)) return fail(e, BH_EINVAL, (w + ": the sample count of a target that is no dispersion curve differs from its descriptor's").c_str());
             }
             continue;
@@ -2304,7 +2429,7 @@ static int sites_register_x(bh_engine *e, const char *who, SiteLevel level, int 
     for (size_t s = 0; s < S; ++s)
         for (int t = 0; t < nt; ++t) {
             const TargetHost &T = e->targets[(size_t)t];
-            if (T.d.kind == BH_TARGET_SWD) std::copy(x + s * ldy + T.off, x + s * ldy + T.off + n[s * nt + t], xs.data() + s * ldy + T.off);
+            if (T.d.kind == BH_TARGET_SWD || T.d.kind == BH_TARGET_ELLIP) std::copy(x + s * ldy + T.off, x + s * ldy + T.off + n[s * nt + t], xs.data() + s * ldy + T.off);
         }
     SiteTable &tab = e->sites;
     if ((rc = ensure(e, tab.xn, S * nt * sizeof(int32_t))) || (rc = ensure(e, tab.xper, S * ldy * sizeof(double)))) {

@@ -101,11 +101,41 @@ struct EllipArgs {
     const int32_t *err;
     double *hv, *mismatch, *cpol;
     int32_t *flag; // zeroed before the launch
+    // the fused build (bh_launch_ellip_fused): vel is read with the row stride ldvel; hv is a target's columns of ymod, row stride ldy,
+    // and takes y = the transform of include/bh_engine_ellip_target.h; flag is the target's row of err_t, which holds err already
+    int ldvel, ldy, zh, is_signed;
 };
 
 // what a lane's pending evaluation is for
 enum : int { EL_F0 = 0, EL_F1 = 1, EL_LAST = 2 };
 
+// FUSED: the build of a fused call (bh_launch_ellip_fused).  One statement of the evaluation and the polish for both builds: they
+// differ in where a lane reads its velocity and in what `put` does with its result.
+template <bool FUSED>
+struct EllipOut {
+    const EllipArgs &A;
+    long long idx, row; // the lane's entry of the [B][K] arrays; of the fused build's output
+    bool &flagged;
+    // hv (mis, cp: mismatch and cpol where the caller asked for them)
+    __device__ __forceinline__ void put(double hv, double mis, double cp) const
+    {
+        if constexpr (FUSED) {
+            double y = A.zh ? 1.0 / hv : hv;
+            if (!A.is_signed) y = fabs(y);
+            if (!isfinite(y)) { // fails the model in band (SurfEllip.run_models), and the likelihood reads no NaN
+                y = 0.0;
+                flagged = true;
+            }
+            A.hv[row] = y;
+        } else {
+            A.hv[idx] = hv;
+            if (A.mismatch) A.mismatch[idx] = mis;
+            if (A.cpol) A.cpol[idx] = cp;
+        }
+    }
+};
+
+template <bool FUSED>
 __global__ __launch_bounds__(ELLIP_THREADS) void swd_ellip_kernel(EllipArgs A)
 {
     __shared__ __align__(16) unsigned char smem[ELLIP_LDS];
@@ -118,14 +148,12 @@ __global__ __launch_bounds__(ELLIP_THREADS) void swd_ellip_kernel(EllipArgs A)
     const int b = inrange ? (int)(idx / A.K) : 0;
     const int k = inrange ? (int)(idx % A.K) : 0;
     const int mmax = inrange ? A.nlay[b] : 1;
-    const double c = inrange ? A.vel[idx] : 0.0;
+    const double c = !inrange ? 0.0 : FUSED ? A.vel[(long long)b * A.ldvel + k] : A.vel[idx];
+    bool flagged = false;
+    const EllipOut<FUSED> out{A, idx, (long long)b * A.ldy + k, flagged};
     // no root: nothing is evaluated, the lane's outputs are zero
     bool live = inrange && A.err[b] == 0 && c > 0.0 && mmax >= 1 && mmax <= A.Lmax;
-    if (inrange && !live) {
-        A.hv[idx] = 0.0;
-        if (A.mismatch) A.mismatch[idx] = 0.0;
-        if (A.cpol) A.cpol[idx] = 0.0;
-    }
+    if (inrange && !live) out.put(0.0, 0.0, 0.0);
     ModelGlobal md;
     {
         const ptrdiff_t base = (ptrdiff_t)b * A.sb;
@@ -135,13 +163,10 @@ __global__ __launch_bounds__(ELLIP_THREADS) void swd_ellip_kernel(EllipArgs A)
     int mtop = live ? mmax : 1; // the wavefront's largest layer count = the loop bound of the recursion
     for (int off = 32; off > 0; off >>= 1) mtop = max(mtop, __shfl_xor(mtop, off));
 
-    bool flagged = false;
     const bool water = live && !((float)md.vs[0] > 0.0f);
     if (water) { // a water layer: not supported, reported in band
         const double qnan = __longlong_as_double(0x7ff8000000000000ll);
-        A.hv[idx] = qnan;
-        if (A.mismatch) A.mismatch[idx] = qnan;
-        if (A.cpol) A.cpol[idx] = c;
+        out.put(qnan, qnan, c);
         flagged = true;
         live = false;
     }
@@ -194,9 +219,7 @@ __global__ __launch_bounds__(ELLIP_THREADS) void swd_ellip_kernel(EllipArgs A)
                 hv = mis = __longlong_as_double(0x7ff8000000000000ll);
                 flagged = true;
             }
-            A.hv[idx] = hv;
-            if (A.mismatch) A.mismatch[idx] = mis;
-            if (A.cpol) A.cpol[idx] = ceval;
+            out.put(hv, mis, ceval);
             live = false;
         }
     }
@@ -204,6 +227,21 @@ __global__ __launch_bounds__(ELLIP_THREADS) void swd_ellip_kernel(EllipArgs A)
 }
 
 } // namespace
+
+// The ellipticity target of a fused call (bh_engine.hip: run_forward; bh_device.h), enqueued: nothing is staged or zeroed here
+void bh_launch_ellip_fused(const EllipFusedArgs &f, hipStream_t st)
+{
+    if (f.B <= 0 || f.K <= 0) return;
+    EllipArgs a{};
+    a.B = f.B; a.Lmax = f.Lmax; a.K = f.K; a.nsteps = f.nsteps;
+    a.nlay = f.nlay; a.h = f.h; a.vp = f.vp; a.vs = f.vs; a.rho = f.rho;
+    a.sl = f.sl; a.sb = f.sb;
+    a.periods = f.periods; a.vel = f.vel; a.err = f.err_row;
+    a.hv = f.y; a.flag = f.err_row;
+    a.ldvel = f.ldvel; a.ldy = f.ldy; a.zh = f.zh; a.is_signed = f.is_signed;
+    const size_t N = (size_t)f.B * (size_t)f.K;
+    hipLaunchKernelGGL(swd_ellip_kernel<true>, dim3((unsigned)((N + ELLIP_THREADS - 1) / ELLIP_THREADS)), dim3(ELLIP_THREADS), 0, st, a);
+}
 
 extern "C" int bh_swd_ellip(bh_engine *e, int memspace, void *stream, int B, int Lmax, const int32_t *nlay, const double *h,
                             const double *vp, const double *vs, const double *rho, ptrdiff_t sl, ptrdiff_t sb, int K,
@@ -267,7 +305,7 @@ extern "C" int bh_swd_ellip(bh_engine *e, int memspace, void *stream, int B, int
     a.err = d_err;
     BH_CHK(e, hipMemsetAsync(a.flag, 0, (size_t)B * sizeof(int32_t), st));
     const unsigned grid = (unsigned)((N + ELLIP_THREADS - 1) / ELLIP_THREADS);
-    hipLaunchKernelGGL(swd_ellip_kernel, dim3(grid), dim3(ELLIP_THREADS), 0, st, a);
+    hipLaunchKernelGGL(swd_ellip_kernel<false>, dim3(grid), dim3(ELLIP_THREADS), 0, st, a);
     BH_CHK(e, hipGetLastError());
     if (!host) return BH_OK;
     BH_CHK(e, hipMemcpyAsync(hv, a.hv, N * sizeof(double), hipMemcpyDeviceToHost, st));

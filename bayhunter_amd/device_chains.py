@@ -294,7 +294,7 @@ class DeviceChains(object):
         if self.sites is None:   # (SiteTargets refuses it itself: "a user plugin")
             from .Targets import RayleighEllipticity
             for t in (targets.targets if isinstance(targets, JointTarget) else targets):
-                if isinstance(t, RayleighEllipticity):
+                if isinstance(t, RayleighEllipticity) and not t.engine_backed():   # (fused=True: part of the fused call)
                     raise EngineError("DeviceChains does not run RayleighEllipticity: the device chains evaluate engine-backed "
                                       "targets in one fused call, and the ellipticity is not part of it yet (ChainBatch runs it)")
         # (checked before anything touches the GPU)

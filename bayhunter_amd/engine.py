@@ -26,6 +26,7 @@ VEL_PHASE, VEL_GROUP = 0, 1
 RF_P, RF_SV = 0, 1
 LAW_NOCORR, LAW_NOCORR_SCALED, LAW_EXP, LAW_GAUSS = 0, 1, 2, 3
 TARGET_SWD, TARGET_RF, TARGET_USER = 0, 1, 2
+TARGET_ELLIP = 3                    # BH_TARGET_ELLIP (include/bh_engine_ellip_target.h): a USER target given the ellipticity forward model
 SEARCH_REFERENCE, SEARCH_FAST, SEARCH_FAST_RAYLEIGH = 0, 1, 2  # bh_engine_set_swd_search
 ARITH_EXACT, ARITH_FAST = 0, 1  # bh_engine_set_swd_arith
 SCAN_STEPS, SCAN_COUNTED, SCAN_AUTO = 0, 1, 2  # bh_engine_set_swd_scan
@@ -276,6 +277,10 @@ def load_library():
                                C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
     for name in SWD_ELLIP_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_targets_set_ellip.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int]
+    L.bh_plan_ellip.argtypes = [C.c_int, vp, C.c_int, vp]
+    for name in ELLIP_TARGET_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_debug_guard_list", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_probe_swd_secular", "bh_chain_propose", "bh_chain_accept",
@@ -395,6 +400,9 @@ CHAIN_DIAG_FEATURES_SYMBOLS = ("bh_chain_diag_features",)
 # (Engine.swd_ellip; bayhunter_amd/surf96_ellip.py)
 SWD_ELLIP_SYMBOLS = ("bh_swd_ellip",)
 ELLIP_MAXSTEPS = 3                  # nsteps of bh_swd_ellip: 0..3
+# include/bh_engine_ellip_target.h: the ellipticity as a registered target with a forward model -- the fused calls and the device
+# chains run it (Engine.set_targets; Targets.RayleighEllipticity(fused=True)) -- and the pure plan of where its velocities come from
+ELLIP_TARGET_SYMBOLS = ("bh_targets_set_ellip", "bh_plan_ellip")
 
 
 def _f64(a):
@@ -827,6 +835,19 @@ class Engine(object):
         self.ntargets = len(descs)
         self.ldy = ldy
         self.nsites = 0
+        for i, d in enumerate(descs):   # (a USER descriptor with nsteps: it takes the ellipticity forward model at its x)
+            if int(d["kind"]) == TARGET_USER and "nsteps" in d:
+                self.set_target_ellip(i, d["x"], nsteps=d["nsteps"], signed=d.get("signed", False), ratio=d.get("ratio", "hv"))
+
+    TARGET_ELLIP = TARGET_ELLIP
+
+    def set_target_ellip(self, t, periods, nsteps=2, signed=False, ratio="hv"):
+        """Give registered USER target t the Rayleigh-ellipticity forward model at `periods` (bh_targets_set_ellip,
+        include/bh_engine_ellip_target.h): its kind is TARGET_ELLIP from then on, and the fused calls compute it."""
+        if ratio not in ("hv", "zh"):
+            raise ValueError("ratio must be 'hv' or 'zh', not %r" % (ratio,))
+        x = _f64(np.asarray(periods, dtype=float).reshape(-1))
+        self._check(self._L.bh_targets_set_ellip(self._h, int(t), int(x.size), _ptr(x), int(nsteps), int(bool(signed)), int(ratio == "zh")))
 
     def evaluate_batch(self, nlay, h, vp, vs, noise, rho=None, layout="layer_major", want_ymod=False):
         """Batched JointTarget.evaluate.  noise[B, 2*nt].  Returns (logL[B], misfits[B, nt+1],

@@ -25,6 +25,7 @@ from . import engine as _engine
 from .Targets import JointTarget, LAWS
 from .rfmini_modrf import RFminiModRF
 from .surf96_modsw import SurfDisp
+from .surf96_ellip import SurfEllip
 
 # the most periods a site may have with per_site_x=True (beyond them a one-site run interpolates: surf96_modsw.py)
 SITE_X_MAX_PERIODS = 60
@@ -79,6 +80,8 @@ def _bits(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64)).tobytes()
 
 
+# the parameters of an ellipticity plugin the sites of a slot must agree in (the engine registers one forward model per slot)
+SITE_ELLIP_PARAMS = ("nsteps", "signed", "ratio")
 # the receiver-function call arguments that may differ between sites with per_site_rf=True (RFminiModRF._call_args)
 SITE_RF_ARGS = ("p", "nsv")
 # ... and with per_site_rf="all": everything but the wave type
@@ -143,7 +146,12 @@ class SiteTargets(object):
     matrices are compared among the Gauss sites only, and the sites under another law are in class -1 of `gauss_class_arrays`.
     The flag SWITCHES per_site_corr ON: a Gauss-law slot with a site under another law needs the class table in any case, and
     stations that differ in their laws fix their correlations independently.  Still refused: the Gauss law on a dispersion
-    target (periods per site)."""
+    target (periods per site).
+
+    A `RayleighEllipticity(fused=True)` slot (include/bh_engine_ellip_target.h) is engine-backed and admitted: its periods x and
+    its plugin's nsteps / signed / ratio are shared by all sites, whatever per_site_x gives the DISPERSION slots beside it
+    (under a table of periods per site the ellipticity runs a phase-velocity search of its own at its shared periods).  Not
+    with missing=True (hence not with per_site_law): a site that lacks the ellipticity is not served yet."""
 
     def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False, missing=False, per_site_corr=False,
                  per_site_law=False):
@@ -270,6 +278,9 @@ class SiteTargets(object):
             have = [s for s, row in enumerate(self._slots) if row[i] is not None]
             first = self._slot_site(i)
             t0 = self._slots[first][i]
+            if isinstance(t0.moddata.plugin, SurfEllip):
+                raise ValueError("site %d (%s), slot %d (%s): missing=True does not serve a %s slot (every site has the ellipticity, "
+                                 "at shared periods)" % (first, self._names[first], i, getattr(t0, "ref", "?"), type(t0).__name__))
             for s in have:
                 t = self._slots[s][i]
                 what = "site %d (%s), slot %d (%s)" % (s, self._names[s], i, getattr(t, "ref", "?"))
@@ -305,6 +316,10 @@ class SiteTargets(object):
             a0 = (p0.wavetype, p0.veltype, p0.modelparams["mode"], p0.modelparams["flsph"])
             if a != a0:
                 raise ValueError("%s: dispersion parameters (wave, velocity, mode, flsph) %r, %s's %r" % (what, a, whose, a0))
+        elif isinstance(p, SurfEllip):
+            a, a0 = [tuple(q.modelparams[k] for k in SITE_ELLIP_PARAMS) for q in (p, p0)]
+            if a != a0:
+                raise ValueError("%s: ellipticity parameters (nsteps, signed, ratio) %r, %s's %r" % (what, a, whose, a0))
         elif isinstance(p, RFminiModRF):
             a, a0 = p._call_args(), p0._call_args()
             if self.per_site_rf:
