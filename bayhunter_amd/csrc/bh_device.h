@@ -82,7 +82,7 @@ struct SwdKernelArgs {
     int counted;      // 1: Love scans skip the steps a mode count proves empty (SearchT: the counted scan; same bits)
     int farith;       // 1: a launch of the short refinement (fundamental-mode phase velocities) computes with the fast arithmetic (swd_fa.h)
     int32_t *gcount, *glist; // short refinement: models its guard fired on are appended here (count, indices), see SearchT
-    // A group velocity's two chains of roots (SearchT: F_CHAIN_A / F_ONE).  igr = 2 (bh_engine.hip swd_target, for a job the plan
+    // A group velocity's two chains of roots (SearchT: F_CHAIN_A / F_ONE).  igr = 2 (engine_swd.hip swd_target, for a job the plan
     // marks SwdPlan::first_roots; never a caller's value): the chain of first roots, unrounded into vel,
     // the value getsol keeps from the mode's first search into first[model].  second = 1 (igr = 1): B = Bm x K searches, entry
     // v = the second root of period v / Bm of model v % Bm, which reads vel and first and writes the group velocity (err untouched).
@@ -119,7 +119,7 @@ struct SwdTarget {
                           // re-run of the models the short refinement's guard fired on: perm = that list)
     int32_t *gcount, *glist; // short refinement: models its guard fired on are appended here (count, indices), see SearchT
     int refseq;              // 1: in a launch with the short refinement this (phase-velocity) target keeps the reference's sequence
-    double *first;           // igr = 2 (the chain of a group velocity's first roots, SwdKernelArgs; bh_engine.hip swd_target): [B]
+    double *first;           // igr = 2 (the chain of a group velocity's first roots, SwdKernelArgs; engine_swd.hip swd_target): [B]
 };
 struct SwdMultiArgs {
     int B, Lmax, ntargets;
@@ -193,7 +193,7 @@ void bh_launch_swd_second_x(const SwdKernelArgs &a, int iwave, const SwdSiteXArg
 int bh_swd_pick_group(int B, int ntargets, int Lmax);
 double bh_swd_plan(int B, int Lmax, int ntargets, const int *iwave, int Gforce, int *G, int *look);
 size_t bh_swd_group_lds_bytes(int G, int J, int Lmax, int Kmax, int maxmode, bool sitex = false);
-// Work space of the SIMD-pairing order (swd_kernel.hip: pair_order_kernel; bh_engine.hip: order_models).  The
+// Work space of the SIMD-pairing order (swd_kernel.hip: pair_order_kernel; engine_swd.hip: order_models).  The
 // dispersion kernel's time is that of its slowest SIMD, a SIMD's time follows the SUM of the root-search lengths of the
 // two wavefronts it holds, and which wavefronts of a launch share a SIMD is a fixed function of their grid index; so the
 // models are dealt to the wavefronts by PREDICTED search length such that every SIMD gets a long and a short wavefront
@@ -213,7 +213,7 @@ struct PairOrderTarget {
                               // wavefronts that run on XCD x (workgroup index mod 8); the value = wavefronts of this target per workgroup (4, or 2
                               // where two targets alternate): every XCD's L2 then sees an eighth of the model arrays
 };
-// The words a dispersion call wants zero before its kernels run -- the guard's head (bh_engine.hip guard_space), the per-target
+// The words a dispersion call wants zero before its kernels run -- the guard's head (engine_swd.hip guard_space), the per-target
 // failure flags, the counters -- where the ordering launch that precedes them zeroes them (the call's prologue: no fill
 // dispatches of their own).  A count of 0: nothing to zero there.
 struct SwdFills {
@@ -482,7 +482,7 @@ void bh_launch_like_sites_l(const LikeKernelArgs &a, const LikeSiteXArgs &sites,
 
 void bh_launch_probe(int op, int n, const double *in, double *out, hipStream_t stream);
 
-// ---- the site table's part of a fused call (bh_engine.hip: SiteTable, plan_eval; DESIGN.md "The site table") ----
+// ---- the site table's part of a fused call (bh_engine_impl.h: SiteTable; engine_eval.hip: plan_eval; DESIGN.md "The site table") ----
 // How far the registered table lets the sites differ: every level admits what the one before it admits, and one thing more.
 enum SiteLevel {
     SITES_NONE,          // no table

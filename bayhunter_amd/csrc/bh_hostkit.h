@@ -2,7 +2,7 @@
 // chain_rank_kernel.hip, chain_ladder_evidence_kernel.hip; chain_ladder_sweep_kernel.hip takes fail and BH_CHK) and of the posterior
 // handle (posterior_common.h): a device buffer that goes with its frame, the refusal through the engine's last error, the check of
 // a HIP call, and the staging of what a call of memspace BH_HOST brings.  Header only; every function is host code around HIP calls.
-// (bh_engine.hip's DevBuf / ensure are another thing: workspaces the engine owns and grows.)
+// (bh_engine_impl.h's DevBuf / ensure are another thing: workspaces the engine owns and grows.)
 #ifndef BH_HOSTKIT_H
 #define BH_HOSTKIT_H
 

@@ -498,7 +498,7 @@ static int g_scan_mode = 0;
 void bho_swd_set_scan(int counted) { g_scan_mode = counted ? 1 : 0; }
 static int g_stride_first = 16, g_stride_next = 4, g_stride_back = -1, g_stride_secant = 1; /* (tuning experiments) */
 void bho_swd_set_scan_tuning(int first, int next, int back) { g_stride_first = first; g_stride_next = next % 100; g_stride_back = back; g_stride_secant = next < 100; }
-/* Group velocities of the fundamental mode as the device runs them (bh_engine.hip launch_swd_jobs): first the chain
+/* Group velocities of the fundamental mode as the device runs them (engine_swd.hip launch_swd_jobs): first the chain
  * of the roots at t/(1+h) over all periods, then -- each on its own, in any order -- the roots at t/(1-h), which start from the
  * first root of their own period (:282-287) and from nothing else.  The same calls with the same arguments as one after the
  * other: tests/test_oracle_swd.py checks the bits against the reference's order (and, in this container, the compiled reference). */

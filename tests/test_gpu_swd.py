@@ -341,7 +341,7 @@ def test_experiment_switches_are_a_table_with_an_api(engine):
 @pytest.mark.parametrize("iwave", [1, 2])
 def test_group_velocity_chains_as_two_launches_return_the_same_bits(engine, oracle, iwave):
     """Fundamental-mode group velocities run as the chain of the first roots (t/(1+h)), then one independent search per (model,
-    period) for the second roots (t/(1-h), surfdisp96.f:282-287) -- bh_engine.hip launch_swd_jobs; bh_tuning.h swd_gsplit = 0
+    period) for the second roots (t/(1-h), surfdisp96.f:282-287) -- engine_swd.hip launch_swd_jobs; bh_tuning.h swd_gsplit = 0
     keeps the single launch.  Both ways, every batch shape, flattened or not: the oracle's bits."""
     rs = np.random.RandomState(77 + iwave)
     assert engine.tuning("swd_gsplit") == 1 << 24

@@ -270,7 +270,7 @@ def group_velocity_sets():
 
 def test_group_velocity_roots_in_the_device_order_are_the_reference_bits(oracle):
     """The device runs a fundamental-mode group velocity as the chain of its first roots (t/(1+h)) and then the second roots (t/(1-h))
-    as independent searches (bh_engine.hip launch_swd_jobs): the second root of a period starts from the first root of
+    as independent searches (engine_swd.hip launch_swd_jobs): the second root of a period starts from the first root of
     the same period and from nothing else (surfdisp96.f:282-287).  The oracle in that order (last period first) against the
     reference's order: the same bits and flags -- golden models (with the models surf96 fails on), sorted velocities with a
     low-velocity zone, models drawn from a sampler's prior, flat and flattened, with and without the counted Love scan; and

@@ -1,4 +1,4 @@
-"""The site part of a fused call's plan (bh_plan_sites, csrc/bh_engine.hip), which needs no GPU, against the truth table of
+"""The site part of a fused call's plan (bh_plan_sites, csrc/engine_eval.hip), which needs no GPU, against the truth table of
 tests/golden/site_plan_golden.npz: what the commit before the site half of plan_eval became this function decided, row by row.
 
 The table was recorded once from that commit through a temporary export that was never committed.  It filled a

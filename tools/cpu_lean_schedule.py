@@ -142,7 +142,7 @@ def wave_rounds(sorted_blocks, rounds, mpw=MPW):
 
 def placement_pairs(Q, rule):
     """(Rayleigh position, Love position) of the SIMDs of one XCD; a position is the target's q-th wavefront on that XCD.
-    "same": position q of both targets.  "rotate": the dispatcher's rule of build_slot_ranks (bh_engine.hip) carried over to
+    "same": position q of both targets.  "rotate": the dispatcher's rule of build_slot_ranks (engine_swd.hip) carried over to
     workgroups of four -- workgroup i holds R 2i, L 2i, R 2i + 1, L 2i + 1, the CU's second workgroup is i + Q / 4 and sits one SIMD on."""
     if rule == "same":
         return [(q, q) for q in range(Q)]
