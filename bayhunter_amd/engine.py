@@ -560,14 +560,30 @@ class Engine(object):
         return {SEARCH_FAST: "fast", SEARCH_FAST_RAYLEIGH: "fast_rayleigh"}.get(self._L.bh_engine_get_swd_search(self._h), "reference")
 
     @contextlib.contextmanager
-    def searching(self, search):
-        """The calls inside run with this root refinement; the engine's setting is restored afterwards."""
-        prev = self.swd_search()
-        self.set_swd_search(search)
+    def settings(self, search=None, arith=None, trials=None, typical_layers=None):
+        """The calls inside run with these settings (set_swd_search / set_swd_arith / set_swd_trials / set_typical_layers); an argument
+        of None leaves the engine's own.  A value is set only where it differs from the engine's, and what was set is restored
+        afterwards, in reverse order, also when the body raises.  typical_layers cannot be read back: it is set on entry and reset
+        to 0 (unknown) on exit."""
+        undo = []
         try:
+            for value, get, put in ((search, self.swd_search, self.set_swd_search), (arith, self.swd_arith, self.set_swd_arith),
+                                    (trials, self.swd_trials, self.set_swd_trials)):
+                prev = None if value is None else get()
+                if prev != value:
+                    put(value)
+                    undo.append((put, prev))
+            if typical_layers is not None:
+                self.set_typical_layers(typical_layers)
+                undo.append((self.set_typical_layers, 0))
             yield self
         finally:
-            self.set_swd_search(prev)
+            for put, prev in reversed(undo):
+                put(prev)
+
+    def searching(self, search):
+        """The calls inside run with this root refinement; the engine's setting is restored afterwards."""
+        return self.settings(search=search)
 
     def set_swd_arith(self, arith):
         """Arithmetic of the launches in which every target takes the short refinement (include/bh_engine.h:
@@ -587,18 +603,10 @@ class Engine(object):
     def swd_trials(self):
         return int(self._L.bh_engine_get_swd_trials(self._h))
 
-    @contextlib.contextmanager
     def trying(self, trials):
         """The calls inside run the trial-per-lane kernel with this many trials per round (None: the engine's setting stays);
         the engine's setting is restored afterwards."""
-        prev = self.swd_trials()
-        if trials is not None:
-            self.set_swd_trials(trials)
-        try:
-            yield self
-        finally:
-            if trials is not None:
-                self.set_swd_trials(prev)
+        return self.settings(trials=trials)
 
     def last_swd_kernel(self):
         """Which dispersion kernel the most recent call launched: "group", "lane", "lean" (bh_engine_last_swd_kernel) or None."""
@@ -637,15 +645,9 @@ class Engine(object):
     def swd_arith(self):
         return "fast" if self._L.bh_engine_get_swd_arith(self._h) == ARITH_FAST else "exact"
 
-    @contextlib.contextmanager
     def computing(self, arith):
         """The calls inside run with this arithmetic; the engine's setting is restored afterwards."""
-        prev = self.swd_arith()
-        self.set_swd_arith(arith)
-        try:
-            yield self
-        finally:
-            self.set_swd_arith(prev)
+        return self.settings(arith=arith)
 
     def set_swd_scan(self, scan):
         """Love bracket scans: "counted" = skip the steps a mode count proves to be without a sign change (same brackets, same
