@@ -556,6 +556,13 @@ struct EllipFusedArgs {
     const double *vel; int ldvel;
     double *y; int ldy;
     int32_t *err_row;
+    // Periods per site (include/bh_engine_sites_ellip.h; site != null: the site build).  K is the CAPACITY of the target's columns and
+    // `periods` is not read: model b of site s = site[b] has the xn[s * ldn] periods xper[s * ldx ...] -- the count table's and the
+    // period table's column of the target.  A lane at or beyond its model's count (count 0: the site lacks the target) or of a site
+    // out of range writes 0.0, raises no flag and evaluates nothing.
+    const int32_t *site = nullptr; int nsites = 0;
+    const int32_t *xn = nullptr; int ldn = 0;
+    const double *xper = nullptr; int ldx = 0;
 };
 void bh_launch_ellip_fused(const EllipFusedArgs &a, hipStream_t stream);
 

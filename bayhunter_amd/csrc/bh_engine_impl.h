@@ -15,6 +15,7 @@
 #include "../../include/bh_engine_sites_rf_axis.h"
 #include "../../include/bh_engine_sites_laws.h"
 #include "../../include/bh_engine_ellip_target.h"
+#include "../../include/bh_engine_sites_ellip.h"
 #include "bh_device.h"
 #include "bh_tuning.h"
 
@@ -49,6 +50,7 @@ struct TargetHost {
     // BH_TARGET_ELLIP (bh_targets_set_ellip): the polish steps and the transform; the velocities of a search of its own
     int ell_nsteps = 0, ell_signed = 0, ell_zh = 0;
     DevBuf ell_vel;    // [B][n]
+    bool ell_sites = false; // bh_targets_set_ellip_sites: periods and counts per site, from the count table (n: the capacity)
 };
 
 inline void release(DevBuf &b)
@@ -88,6 +90,7 @@ struct SiteTable {
     std::vector<int32_t> law_host;  // ... the laws as registered (bh_sites_set_gauss checks its classes against them)
     DevBuf desc_n;                  // [nsites][nt] the descriptors' counts: the count table of a class call below SITES_X
     DevBuf class_work;              // the grouping's work space of a call (bh_gauss_class_work_words)
+    int32_t ell_source[BH_MAX_TARGETS] = {}; // level >= SITES_X_ALL: bh_plan_ellip_sites of the count table as registered (plan_eval reads it)
     SiteTarget t[BH_MAX_TARGETS];
 
     // The one invalidation rule.  `part` is being registered anew -- out of force until its entry point has succeeded -- and what
@@ -108,6 +111,7 @@ struct SiteTable {
             nsites = 0;
             xn_host.clear();
             for (SiteTarget &T : t) T.lacks = T.rf_own_counts = false;
+            for (int32_t &j : ell_source) j = -1;
             [[fallthrough]];
         case PART_RF:
             rf = false;

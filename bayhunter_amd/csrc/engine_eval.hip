@@ -94,6 +94,34 @@ extern "C" int bh_plan_ellip(int nt, const bh_ellip_plan_target *T, int x_table,
     return own;
 }
 
+// ... under a count table whose ellipticity targets may carry their own periods (include/bh_engine_sites_ellip.h): pure as well
+extern "C" int bh_plan_ellip_sites(int nt, const bh_ellip_plan_target *T, const int32_t *own, int nsites, const int32_t *n,
+                                   const double *x, int ldx, const int32_t *off, int32_t *source)
+{
+    if (nt < 0 || nt > BH_MAX_TARGETS || nsites < 1 || ldx < 0 || !T || !own || !n || !x || !off || !source) return -1;
+    int added = 0;
+    for (int t = 0; t < nt; ++t) {
+        source[t] = -2;
+        if (T[t].kind != BH_TARGET_ELLIP) continue;
+        source[t] = -1;
+        for (int j = 0; j < nt && own[t] && source[t] < 0; ++j) {
+            if (!(T[j].kind == BH_TARGET_SWD && T[j].iwave == BH_WAVE_RAYLEIGH && T[j].igr == BH_VEL_PHASE && T[j].mode <= 1 &&
+                  T[j].flsph == 0 && T[j].n <= BH_MAX_PERIODS))
+                continue;
+            bool same = true; // at every site that has t: j with the same count and the same bits
+            for (int s = 0; s < nsites && same; ++s) {
+                const int nst = n[(size_t)s * nt + t];
+                if (nst <= 0) continue;
+                same = n[(size_t)s * nt + j] == nst &&
+                       std::memcmp(x + (size_t)s * ldx + off[j], x + (size_t)s * ldx + off[t], (size_t)nst * sizeof(double)) == 0;
+            }
+            if (same) source[t] = j;
+        }
+        added += source[t] < 0;
+    }
+    return added;
+}
+
 namespace {
 
 // What a target does in a fused call: nothing (a BH_TARGET_USER target has no forward model), dispersion at its own periods,
@@ -168,6 +196,13 @@ EvalPlan plan_eval(const bh_engine *e, int B, bool sites, bool want_ymod)
             p.nswd += bh_plan_ellip(p.nt, q, p.sites.x_table, p.ell_source);
             for (int t = 0; t < p.nt; ++t)
                 if (p.ell_source[t] != -2) p.role[t] = ROLE_ELLIP;
+            // (periods per site on an ellipticity target, bh_targets_set_ellip_sites: what bh_plan_ellip_sites decided when the count
+            // table was registered)
+            for (int t = 0; t < p.nt && p.sites.x_all; ++t)
+                if (e->targets[(size_t)t].ell_sites && e->sites.ell_source[t] >= 0) {
+                    p.ell_source[t] = e->sites.ell_source[t];
+                    --p.nswd;
+                }
         }
     }
     p.fork = have_rf && p.nswd > 0 && e->overlap_rf;
@@ -428,7 +463,7 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
     }
     // (the ellipticity targets' own searches come after the dispersion targets' jobs: those keep their places in the launch and
     // in the guard's statistics.  Under a period table the job reads the table's column of its target, which holds the periods
-    // every site shares.)
+    // every site shares -- or, bh_targets_set_ellip_sites, every site's own periods and count, the job's K being the capacity.)
     for (int t = 0; t < nt; ++t) {
         if (p.role[t] != ROLE_ELLIP || p.ell_source[t] >= 0) continue;
         const TargetHost &T = e->targets[(size_t)t];
@@ -503,6 +538,11 @@ int run_forward(bh_engine *e, const EvalPlan &p, const EvalCall &c)
         a.ldvel = j >= 0 ? ldy : T.d.n;
         a.y = c.ymod + T.off; a.ldy = ldy;
         a.err_row = row;
+        if (T.ell_sites) { // (K: the capacity; a lane's period and its model's count are the table's, column t)
+            a.site = c.site; a.nsites = S.nsites;
+            a.xn = (const int32_t *)S.xn.p + t; a.ldn = nt;
+            a.xper = (const double *)S.xper.p + T.off; a.ldx = ldy;
+        }
         bh_launch_ellip_fused(a, st);
     }
     return p.fork ? wait_for(e, e->ev_join, e->aux, st) : BH_OK;
@@ -552,6 +592,9 @@ int evaluate(bh_engine *e, int memspace, void *stream, int B, int Lmax, const in
     int rc;
     const ModelBatch m{B, Lmax, nlay, h, vp, vs, rho, nullptr, nullptr, sl, sb};
     if ((rc = check_models(e, m))) return rc;
+    if (!site) // (bh_evaluate_batch reads no table: include/bh_engine_sites_ellip.h)
+        for (const TargetHost &T : e->targets)
+            if (T.ell_sites) return fail(e, BH_EINVAL, "bh_evaluate_batch: an ellipticity target with periods per site (bh_targets_set_ellip_sites) is served by bh_evaluate_sites");
     const bool host = (memspace != BH_DEVICE);
     const EvalPlan p = plan_eval(e, B, site != nullptr, ymod != nullptr);
     LikeKernelArgs la{};

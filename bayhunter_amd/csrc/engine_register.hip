@@ -131,6 +131,24 @@ int bh_targets_set_ellip(bh_engine *e, int t, int K, const double *periods, int 
     return BH_OK;
 }
 
+int bh_targets_set_ellip_sites(bh_engine *e, int t, int own)
+{
+    if (!e) return BH_EINVAL;
+    if (t < 0 || t >= e->nt) return fail(e, BH_EINVAL, "bh_targets_set_ellip_sites: no such target (bh_targets_set)");
+    if (e->targets[(size_t)t].d.kind != BH_TARGET_ELLIP) return fail(e, BH_EINVAL, "bh_targets_set_ellip_sites: the target is not a BH_TARGET_ELLIP (bh_targets_set_ellip)");
+    if (e->sites.nsites > 0) return fail(e, BH_EINVAL, "bh_targets_set_ellip_sites: a site table is in force (call it between bh_targets_set_ellip and bh_sites_set*)");
+    e->targets[(size_t)t].ell_sites = own != 0;
+    return BH_OK;
+}
+
+// the first registered ellipticity target with periods per site (bh_targets_set_ellip_sites), or -1
+static int first_ellip_sites(const bh_engine *e)
+{
+    for (int t = 0; t < e->nt; ++t)
+        if (e->targets[(size_t)t].d.kind == BH_TARGET_ELLIP && e->targets[(size_t)t].ell_sites) return t;
+    return -1;
+}
+
 // bh_sites_set (n == null: every site has the descriptors' counts) and bh_sites_set_x (n[s * nt + t] samples of site s for
 // target t: yobs, yerr and the scaled-error tables are formed over a site's own samples; the columns beyond them hold 0 / 1)
 static int sites_register(bh_engine *e, int nsites, const int32_t *n, const double *yobs, const double *yerr)
@@ -172,6 +190,8 @@ int bh_sites_set(bh_engine *e, int nsites, const double *yobs, const double *yer
     bool scaled = false;
     for (const auto &T : e->targets) scaled = scaled || T.d.law == BH_LAW_NOCORR_SCALED;
     if (scaled && !yerr) return fail(e, BH_EINVAL, "a BH_LAW_NOCORR_SCALED target needs yerr of every site");
+    if (first_ellip_sites(e) >= 0)
+        return fail(e, BH_EINVAL, "bh_sites_set: an ellipticity target with periods per site (bh_targets_set_ellip_sites) needs the table of bh_sites_set_x_all or of a later entry point");
     return sites_register(e, nsites, nullptr, yobs, yerr);
 }
 
@@ -192,6 +212,8 @@ static int sites_register_x(bh_engine *e, const char *who, SiteLevel level, int 
     const bool admits_absent = level >= SITES_MISSING;              // a count of 0 -- the site lacks the target -- but every site has a target and every target a site
     const bool admits_absent_gauss = level >= SITES_MISSING_GAUSS;  // ... on a Gauss-law target as well
     const bool admits_rf_counts = level >= SITES_AXES;              // a receiver function's count may be 0 or 1 .. its descriptor's n
+    if (!admits_any_dispersion && first_ellip_sites(e) >= 0)
+        return fail(e, BH_EINVAL, (w + ": an ellipticity target with periods per site (bh_targets_set_ellip_sites) needs the table of bh_sites_set_x_all or of a later entry point").c_str());
     if (admits_absent) {
         for (size_t s = 0; s < S; ++s) {
             bool any = false;
@@ -212,7 +234,8 @@ static int sites_register_x(bh_engine *e, const char *who, SiteLevel level, int 
     for (int t = 0; t < nt; ++t) {
         const TargetHost &T = e->targets[(size_t)t];
         const bh_target_desc &d = T.d;
-        if (d.kind != BH_TARGET_SWD) { // (a receiver function's x is its descriptor's time axis: shared, but for bh_sites_set_axes)
+        // (an ellipticity target with periods per site, bh_targets_set_ellip_sites: the rules of a dispersion curve, below)
+        if (d.kind != BH_TARGET_SWD && !(d.kind == BH_TARGET_ELLIP && T.ell_sites)) { // (a receiver function's x is its descriptor's time axis: shared, but for bh_sites_set_axes)
             for (size_t s = 0; s < S; ++s) {
                 if (admits_rf_counts && d.kind == BH_TARGET_RF && n[s * nt + t] >= 0 && n[s * nt + t] <= d.n) continue;
                 if (admits_rf_counts && d.kind == BH_TARGET_RF) return fail(e, BH_EINVAL, (w + ": a receiver function's sample count is below 0 or above its descriptor's n (the capacity)").c_str());
@@ -256,6 +279,17 @@ static int sites_register_x(bh_engine *e, const char *who, SiteLevel level, int 
     }
     tab.level = level;
     tab.xn_host.assign(n, n + S * nt);
+    if (first_ellip_sites(e) >= 0) { // where the ellipticity targets with periods per site take their velocities: decided once, here
+        bh_ellip_plan_target q[BH_MAX_TARGETS];
+        int32_t own[BH_MAX_TARGETS], off[BH_MAX_TARGETS];
+        for (int t = 0; t < nt; ++t) {
+            const TargetHost &T = e->targets[(size_t)t];
+            q[t] = bh_ellip_plan_target{T.d.kind, T.d.iwave, T.d.igr, T.d.mode, T.d.flsph, T.d.n, T.xid};
+            own[t] = T.ell_sites ? 1 : 0;
+            off[t] = T.off;
+        }
+        (void)bh_plan_ellip_sites(nt, q, own, nsites, n, xs.data(), ldy, off, tab.ell_source);
+    }
     for (int t = 0; t < nt; ++t)
         for (size_t s = 0; s < S; ++s)
             if (n[s * nt + t] == 0) tab.t[t].lacks = true;

@@ -104,6 +104,10 @@ struct EllipArgs {
     // the fused build (bh_launch_ellip_fused): vel is read with the row stride ldvel; hv is a target's columns of ymod, row stride ldy,
     // and takes y = the transform of include/bh_engine_ellip_target.h; flag is the target's row of err_t, which holds err already
     int ldvel, ldy, zh, is_signed;
+    // the site build (EllipFusedArgs::site; include/bh_engine_sites_ellip.h): K is the capacity, periods is not read
+    const int32_t *site, *xn;
+    const double *xper;
+    int nsites, ldn, ldx;
 };
 
 // what a lane's pending evaluation is for
@@ -135,9 +139,13 @@ struct EllipOut {
     }
 };
 
-template <bool FUSED>
+// SITES (a fused build): a lane reads its model's site's count and its own period from the tables; a lane at or beyond the count --
+// count 0, the site lacks the target, included -- or of a site out of range is IDLE: it writes 0.0, raises no flag, evaluates
+// nothing and is never live, so neither the wavefront's loop bound nor its ballot sees it.
+template <bool FUSED, bool SITES = false>
 __global__ __launch_bounds__(ELLIP_THREADS) void swd_ellip_kernel(EllipArgs A)
 {
+    static_assert(FUSED || !SITES, "the site build is a fused build");
     __shared__ __align__(16) unsigned char smem[ELLIP_LDS];
     const LibmTabs LT = stage_libm_tables(smem, threadIdx.x, ELLIP_THREADS);
     __syncthreads();
@@ -148,12 +156,26 @@ __global__ __launch_bounds__(ELLIP_THREADS) void swd_ellip_kernel(EllipArgs A)
     const int b = inrange ? (int)(idx / A.K) : 0;
     const int k = inrange ? (int)(idx % A.K) : 0;
     const int mmax = inrange ? A.nlay[b] : 1;
-    const double c = !inrange ? 0.0 : FUSED ? A.vel[(long long)b * A.ldvel + k] : A.vel[idx];
+    const double *periods = A.periods;
+    bool idle = false;
+    if constexpr (SITES) {
+        if (inrange) {
+            const int s = A.site[b];
+            int n = 0; // (a site out of range reads nothing of the tables)
+            if (s >= 0 && s < A.nsites) {
+                n = A.xn[(long long)s * A.ldn];
+                periods = A.xper + (long long)s * A.ldx;
+            }
+            idle = k >= n;
+            if (idle) A.hv[(long long)b * A.ldy + k] = 0.0;
+        }
+    }
+    const double c = (!inrange || idle) ? 0.0 : FUSED ? A.vel[(long long)b * A.ldvel + k] : A.vel[idx];
     bool flagged = false;
     const EllipOut<FUSED> out{A, idx, (long long)b * A.ldy + k, flagged};
     // no root: nothing is evaluated, the lane's outputs are zero
-    bool live = inrange && A.err[b] == 0 && c > 0.0 && mmax >= 1 && mmax <= A.Lmax;
-    if (inrange && !live) out.put(0.0, 0.0, 0.0);
+    bool live = inrange && !idle && A.err[b] == 0 && c > 0.0 && mmax >= 1 && mmax <= A.Lmax;
+    if (inrange && !idle && !live) out.put(0.0, 0.0, 0.0);
     ModelGlobal md;
     {
         const ptrdiff_t base = (ptrdiff_t)b * A.sb;
@@ -173,7 +195,7 @@ __global__ __launch_bounds__(ELLIP_THREADS) void swd_ellip_kernel(EllipArgs A)
 
     // as SearchT::set_period and the search's rounds form them (swd_common.h, swd_kernel.hip)
     const double twopi = 2.0 * 3.141592653589793;
-    const double omega = live ? twopi / A.periods[k] : 1.0;
+    const double omega = live ? twopi / periods[k] : 1.0;
 
     // the polish of the header as a state machine: one evaluation of the compound vector per round for every live lane
     int stage = (A.nsteps == 0) ? EL_LAST : EL_F0;
@@ -240,7 +262,13 @@ void bh_launch_ellip_fused(const EllipFusedArgs &f, hipStream_t st)
     a.hv = f.y; a.flag = f.err_row;
     a.ldvel = f.ldvel; a.ldy = f.ldy; a.zh = f.zh; a.is_signed = f.is_signed;
     const size_t N = (size_t)f.B * (size_t)f.K;
-    hipLaunchKernelGGL(swd_ellip_kernel<true>, dim3((unsigned)((N + ELLIP_THREADS - 1) / ELLIP_THREADS)), dim3(ELLIP_THREADS), 0, st, a);
+    const dim3 grid((unsigned)((N + ELLIP_THREADS - 1) / ELLIP_THREADS));
+    if (f.site != nullptr) { // periods and counts per site (include/bh_engine_sites_ellip.h)
+        a.site = f.site; a.nsites = f.nsites; a.xn = f.xn; a.ldn = f.ldn; a.xper = f.xper; a.ldx = f.ldx;
+        hipLaunchKernelGGL((swd_ellip_kernel<true, true>), grid, dim3(ELLIP_THREADS), 0, st, a);
+        return;
+    }
+    hipLaunchKernelGGL(swd_ellip_kernel<true>, grid, dim3(ELLIP_THREADS), 0, st, a);
 }
 
 extern "C" int bh_swd_ellip(bh_engine *e, int memspace, void *stream, int B, int Lmax, const int32_t *nlay, const double *h,

@@ -281,6 +281,10 @@ def load_library():
     L.bh_plan_ellip.argtypes = [C.c_int, vp, C.c_int, vp]
     for name in ELLIP_TARGET_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.bh_targets_set_ellip_sites.argtypes = [vp, C.c_int, C.c_int]
+    L.bh_plan_ellip_sites.argtypes = [C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    for name in SITE_ELLIP_SYMBOLS:
+        getattr(L, name).restype = C.c_int
     for name in ("bh_engine_create", "bh_engine_synchronize", "bh_engine_set_instrumentation", "bh_engine_set_swd_group", "bh_engine_set_swd_lookahead", "bh_engine_set_swd_search", "bh_engine_get_swd_search", "bh_engine_set_swd_arith", "bh_engine_get_swd_arith", "bh_engine_last_swd_kernel", "bh_engine_set_swd_trials", "bh_engine_get_swd_trials", "bh_engine_set_swd_scan", "bh_engine_get_swd_scan", "bh_engine_set_tuning", "bh_engine_get_tuning", "bh_engine_guard_stats", "bh_engine_set_typical_layers", "bh_engine_set_model_order",
                  "bh_timing_reset", "bh_timing_collect", "bh_timing_steps", "bh_last_neval", "bh_debug_counters", "bh_debug_trace", "bh_debug_guard_list", "bh_swd_batch", "bh_rf_batch", "bh_targets_set",
                  "bh_evaluate_batch", "bh_loglike_batch", "bh_probe_math", "bh_probe_swd_secular", "bh_chain_propose", "bh_chain_accept",
@@ -403,6 +407,9 @@ ELLIP_MAXSTEPS = 3                  # nsteps of bh_swd_ellip: 0..3
 # include/bh_engine_ellip_target.h: the ellipticity as a registered target with a forward model -- the fused calls and the device
 # chains run it (Engine.set_targets; Targets.RayleighEllipticity(fused=True)) -- and the pure plan of where its velocities come from
 ELLIP_TARGET_SYMBOLS = ("bh_targets_set_ellip", "bh_plan_ellip")
+# include/bh_engine_sites_ellip.h: an ellipticity target with its own periods at every site, or absent at a site
+# (Engine.set_target_ellip_sites; SiteTargets(per_site_ellip=True)), and the pure plan of its search under a count table
+SITE_ELLIP_SYMBOLS = ("bh_targets_set_ellip_sites", "bh_plan_ellip_sites")
 
 
 def _f64(a):
@@ -840,8 +847,17 @@ class Engine(object):
         for i, d in enumerate(descs):   # (a USER descriptor with nsteps: it takes the ellipticity forward model at its x)
             if int(d["kind"]) == TARGET_USER and "nsteps" in d:
                 self.set_target_ellip(i, d["x"], nsteps=d["nsteps"], signed=d.get("signed", False), ratio=d.get("ratio", "hv"))
+                if d.get("ellip_sites"):    # (its periods and counts are the count table's, site by site)
+                    self.set_target_ellip_sites(i, True)
 
     TARGET_ELLIP = TARGET_ELLIP
+
+    def set_target_ellip_sites(self, t, own=True):
+        """Registered ellipticity target t takes its periods and their count from the count table, site by site
+        (bh_targets_set_ellip_sites, include/bh_engine_sites_ellip.h): between set_target_ellip and any set_sites*.  Its n is then
+        the capacity of its columns and its registered periods a placeholder; set_sites_x_all or a later table serves it, with
+        set_sites_missing and beyond a site may lack it (count 0).  evaluate_batch refuses such a set; set_targets resets the flag."""
+        self._check(self._L.bh_targets_set_ellip_sites(self._h, int(t), int(bool(own))))
 
     def set_target_ellip(self, t, periods, nsteps=2, signed=False, ratio="hv"):
         """Give registered USER target t the Rayleigh-ellipticity forward model at `periods` (bh_targets_set_ellip,

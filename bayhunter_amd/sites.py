@@ -18,6 +18,8 @@ And so may a receiver function's time axis and Gauss filter (per_site_rf="all", 
 rate, sample count and filter width are then a station's own, and each model's trace is synthesised on its site's axis.
 Last, the installed noise LAW of a slot may differ between sites (per_site_law=True, include/bh_engine_sites_laws.h): the sampler
 installs a target's law from the station's own priors and data, so stations with their own priors differ in them.
+The Rayleigh ellipticity (H/V) slot follows the dispersion slots in all of this with per_site_ellip=True
+(include/bh_engine_sites_ellip.h): its periods and their number are then a station's own, and a station may lack it.
 """
 import numpy as np
 
@@ -150,11 +152,22 @@ class SiteTargets(object):
 
     A `RayleighEllipticity(fused=True)` slot (include/bh_engine_ellip_target.h) is engine-backed and admitted: its periods x and
     its plugin's nsteps / signed / ratio are shared by all sites, whatever per_site_x gives the DISPERSION slots beside it
-    (under a table of periods per site the ellipticity runs a phase-velocity search of its own at its shared periods).  Not
-    with missing=True (hence not with per_site_law): a site that lacks the ellipticity is not served yet."""
+    (under a table of periods per site the ellipticity runs a phase-velocity search of its own at its shared periods).  Without
+    per_site_ellip not with missing=True (hence not with per_site_law): every site then has the ellipticity.
+
+    per_site_ellip=True (needs per_site_x="all"; include/bh_engine_sites_ellip.h): the ellipticity slot's periods x and their number
+    (1 to 60 per site; not with the Gauss law) may differ between sites as a dispersion slot's do -- a station's H/V curve has its
+    own usable band, rarely its phase-velocity curve's; nsteps / signed / ratio stay shared.  With missing=True the slot may then be
+    None at a site, and per_site_law=True is open to it.  Each model's ellipticities are computed at its own site's periods, the
+    bits of a one-site run; in the synthetics they are followed by zeros up to the largest count of any site.  Where, at every
+    site that has the ellipticity, the site's Rayleigh phase-velocity slot has the same periods bit for bit, the ellipticity
+    reads that slot's velocities and costs no search of its own.  Without the flag every check above is what it was."""
 
     def __init__(self, jointtargets, names=None, engine=None, per_site_rf=False, per_site_x=False, missing=False, per_site_corr=False,
-                 per_site_law=False):
+                 per_site_law=False, per_site_ellip=False):
+        self.per_site_ellip = bool(per_site_ellip)
+        if self.per_site_ellip and per_site_x != "all":
+            raise ValueError("per_site_ellip=True needs per_site_x=\"all\" (the table of counts it extends)")
         self.missing = bool(missing)
         self.per_site_law = bool(per_site_law)
         if self.per_site_law and not self.missing:
@@ -278,7 +291,7 @@ class SiteTargets(object):
             have = [s for s, row in enumerate(self._slots) if row[i] is not None]
             first = self._slot_site(i)
             t0 = self._slots[first][i]
-            if isinstance(t0.moddata.plugin, SurfEllip):
+            if isinstance(t0.moddata.plugin, SurfEllip) and not self.per_site_ellip:
                 raise ValueError("site %d (%s), slot %d (%s): missing=True does not serve a %s slot (every site has the ellipticity, "
                                  "at shared periods)" % (first, self._names[first], i, getattr(t0, "ref", "?"), type(t0).__name__))
             for s in have:
@@ -299,10 +312,13 @@ class SiteTargets(object):
         site_x = self.per_site_x and isinstance(t.moddata.plugin, SurfDisp) and isinstance(t0.moddata.plugin, SurfDisp)
         site_axis = (self.per_site_rf == "all" and isinstance(t.moddata.plugin, RFminiModRF)
                      and isinstance(t0.moddata.plugin, RFminiModRF))
-        if not same_x and not site_x and not site_axis:
+        site_ellip = self.per_site_ellip and isinstance(t.moddata.plugin, SurfEllip) and isinstance(t0.moddata.plugin, SurfEllip)
+        if not same_x and not site_x and not site_axis and not site_ellip:
             raise ValueError("%s: x differs from %s's (sites share x bit for bit)" % (what, whose))
         if site_x:
             self._check_site_x(what, t, x, same_x)
+        if site_ellip:
+            self._check_site_ellip(what, t, x)
         if site_axis and t.moddata.plugin.nsamp > SITE_RF_AXIS_MAX_NSAMP:
             raise ValueError("%s: %d samples need a transform of %d points; a site has at most %d with per_site_rf=\"all\""
                              % (what, x.size, t.moddata.plugin.nsamp, SITE_RF_AXIS_MAX_NSAMP))
@@ -354,6 +370,16 @@ class SiteTargets(object):
             raise ValueError("%s: a period that is not finite and positive" % what)
         if t.law() == "gauss":
             raise ValueError("%s: Gauss law on a dispersion target with periods per site (R^-1 depends on their number)" % what)
+
+    def _check_site_ellip(self, what, t, x):
+        """what the engine refuses of an ellipticity target registered with periods per site (include/bh_engine_sites_ellip.h): the
+        rules of a dispersion target"""
+        if x.ndim != 1 or x.size < 1 or x.size > SITE_X_MAX_PERIODS:
+            raise ValueError("%s: %d periods; a site has 1 to %d with per_site_ellip" % (what, x.size, SITE_X_MAX_PERIODS))
+        if not np.all(np.isfinite(x) & (x > 0)):
+            raise ValueError("%s: a period that is not finite and positive" % what)
+        if t.law() == "gauss":
+            raise ValueError("%s: Gauss law on an ellipticity target with periods per site (R^-1 depends on their number)" % what)
 
     def site_x_arrays(self):
         """(n[S, nt] int32, x[S, ldy], yobs[S, ldy], yerr[S, ldy] or None) for Engine.set_sites_x: the samples of every (site,
@@ -419,6 +445,14 @@ class SiteTargets(object):
                 d["x"], d["yobs"] = np.ones(cap), np.zeros(cap)
                 if "yerr" in d:
                     d["yerr"] = np.ones(cap)
+            if self.per_site_ellip and d["kind"] == _engine.TARGET_USER and "nsteps" in d:
+                # (the ellipticity slot likewise; Engine.set_targets makes the key the call of bh_targets_set_ellip_sites)
+                cap = int(n[:, i].max())
+                d["n"] = cap
+                d["x"], d["yobs"] = np.ones(cap), np.zeros(cap)
+                if "yerr" in d:
+                    d["yerr"] = np.ones(cap)
+                d["ellip_sites"] = True
             descs.append(d)
         return descs
 

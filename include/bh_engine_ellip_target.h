@@ -37,6 +37,7 @@
  * SITES.  bh_targets_set_ellip belongs between bh_targets_set and any bh_sites_set*.  Every site shares the target's periods: the
  * count tables (bh_sites_set_x ... bh_sites_set_axes) take the descriptor's count for it at every site -- a count of 0, a site
  * that lacks the target, is refused with BH_EUNSUPPORTED -- and x equal to `periods` bit for bit (BH_EINVAL otherwise).
+ * (Periods per site and sites without the target: bh_targets_set_ellip_sites of include/bh_engine_sites_ellip.h, opt-in.)
  *
  * bh_loglike_batch serves a target set with such a target as it serves a BH_TARGET_USER: the caller's synthetics.
  */
