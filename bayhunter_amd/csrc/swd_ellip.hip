@@ -241,6 +241,9 @@ __global__ __launch_bounds__(ELLIP_THREADS) void swd_ellip_kernel(EllipArgs A)
                 hv = mis = __longlong_as_double(0x7ff8000000000000ll);
                 flagged = true;
             }
+            // the gate on the certificate, in every build (the fused ones write no mismatch, but fail the model by it): the two
+            // expressions of hv do not agree, so the arithmetic does not determine it; hv, mis and cpol stay as they are
+            if (!(mis <= BH_ELLIP_MISMATCH_MAX)) flagged = true;
             out.put(hv, mis, ceval);
             live = false;
         }

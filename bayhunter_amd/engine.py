@@ -404,6 +404,7 @@ CHAIN_DIAG_FEATURES_SYMBOLS = ("bh_chain_diag_features",)
 # (Engine.swd_ellip; bayhunter_amd/surf96_ellip.py)
 SWD_ELLIP_SYMBOLS = ("bh_swd_ellip",)
 ELLIP_MAXSTEPS = 3                  # nsteps of bh_swd_ellip: 0..3
+ELLIP_MISMATCH_MAX = 1.0e-2         # BH_ELLIP_MISMATCH_MAX: an entry whose mismatch is above it raises the flag
 # include/bh_engine_ellip_target.h: the ellipticity as a registered target with a forward model -- the fused calls and the device
 # chains run it (Engine.set_targets; Targets.RayleighEllipticity(fused=True)) -- and the pure plan of where its velocities come from
 ELLIP_TARGET_SYMBOLS = ("bh_targets_set_ellip", "bh_plan_ellip")
@@ -784,7 +785,7 @@ class Engine(object):
         search runs first (with the search and arithmetic it is set to).  nsteps: secant steps of the polish (0..3).
         Returns a dict: hv [B, K], mismatch [B, K] (the relative difference of the two expressions of hv: a bound of its
         error), c [B, K] (the velocity hv was evaluated at), vel [B, K], err [B], flag [B] (a step of the polish left the window of
-        1e-5 c, or a value is not a number).  A model without a root (err != 0) and an entry with vel <= 0 are zero rows."""
+        1e-5 c, a value is not a number, or a mismatch is above ELLIP_MISMATCH_MAX: the arithmetic does not determine hv).  A model without a root (err != 0) and an entry with vel <= 0 are zero rows."""
         B, Lmax, sl, sb, nlay, (h, vp, vs, rho) = self._model_args(nlay, h, vp, vs, rho, layout)
         periods = _f64(periods).reshape(-1)
         K = periods.size

@@ -53,7 +53,8 @@ class SurfEllip(object):
 
     def run_models(self, nlay, h, vp, vs, rho, layout="layer_major"):
         """Batch of models -> (x[K], y[B, K], err[B]).  A model fails in band (err != 0, its row NaN) when the dispersion search
-        found no root, when the polish or a value raised the call's flag, or when a value is not finite."""
+        found no root, when the polish, a value or the gate on the mismatch raised the call's flag (include/bh_engine_swd_ellip.h),
+        or when a value is not finite."""
         p = self.modelparams
         out = self.engine.swd_ellip(nlay, h, vp, vs, rho, self.obsx, nsteps=p["nsteps"], layout=layout)
         y = out["hv"]

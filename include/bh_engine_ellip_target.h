@@ -14,7 +14,10 @@
  * A FUSED CALL with such a target.
  *   Failure.  err_t[t][b] != 0 -- hence logL = -1e15, misfits = 1e15, err[b] = 1 -- exactly when the phase-velocity search found
  *     no root for model b (its failure flag), or one of the model's K entries raised the flag of bh_swd_ellip (a water layer, a
- *     polish step that left the window, a vanishing component), or one of its K values y is not finite (zh at hv == 0 included).
+ *     polish step that left the window, a vanishing component, a mismatch of the two expressions of hv above
+ *     BH_ELLIP_MISMATCH_MAX -- the gate: the fused build forms the mismatch without writing it), or one of its K values y is not
+ *     finite (zh at hv == 0 included).  So no synthetic that the arithmetic does not determine reaches the likelihood: about a third
+ *     of the (model, period) pairs drawn from a chain's prior fail this way (profiles/swd_ellip_accuracy.txt).
  *   Values.  A lane whose y is not finite writes 0.0; a lane without a root (the search failed, or its velocity is not positive)
  *     writes 0.0, or fails as above where the transform of 0.0 is not finite.  The other ymod columns of a FAILED model are
  *     unspecified (a lane may see its model's failure raised by a neighbour and write 0.0, or may not).

@@ -27,7 +27,18 @@
  * Both are the surface u_r / u_z of the fundamental mode AT a root of e0; POSITIVE MEANS RETROGRADE particle motion (a
  * homogeneous half-space: hv = 2 sqrt(1 - c^2/b^2) / (2 - c^2/b^2) > 0), negative prograde.  Off the root the two move in opposite
  * directions, so mismatch bounds the error of hv that a c which is not quite the root leaves (measured: error <= 0.87 x
- * mismatch); |d ln hv / d ln c| is 8 to 30, more at an H/V peak.
+ * mismatch on four well-behaved stacks).  |d ln hv / d ln c| is 8 to 30 on those stacks at 4 to 40 s, more at an H/V peak; on models
+ * of the kind a chain proposes (velocities in any order; tests/golden/ellip_exact.npz, against a 110-digit reference) it is 1.1 to
+ * 2.4e3 where two polish steps converge and 1.4e5 to 2.2e9 where they do not: a mode trapped in a low-velocity channel has
+ * almost no surface expression, e0 goes from -1 to 1 between neighbouring doubles, and a c good to the last bit leaves hv
+ * undetermined.  mismatch is O(1) there.  (The two expressions also meet where the displacement minor vanishes instead of the
+ * traction minor, so a small mismatch is a necessary sign of a root, not a proof of one.)
+ *
+ * THE GATE.  An entry whose mismatch is not <= BH_ELLIP_MISMATCH_MAX raises the flag, exactly like a polish step that leaves the
+ * window: an ellipticity that the arithmetic does not determine is not a value.  hv, mismatch and cpol are written as computed.
+ * The constant: the largest mismatch of an entry the tests take as a value -- unpolished, from a velocity within the search's 2e-6
+ * of the root -- is 2.5e-4 (profiles/swd_ellip_accuracy.txt); the smallest power of ten at least ten times that.  For an entry
+ * that passes, |atan(hv) - atan(hv at the root)| <= BH_ELLIP_MISMATCH_MAX where the root's value lies between the two expressions.
  *
  * THE POLISH, nsteps = 0..3 secant steps on e0 from the c handed in (the search's c is within ~2e-6 of the root):
  *     nsteps == 0:  E = E(c), cpol = c.
@@ -48,6 +59,7 @@
  *     evaluated, no flag.  The zero rows of a failed dispersion search stay zero rows.
  *   - (float)vs of the top layer <= 0 (a water layer; not supported), E[1] == 0, E[2] == 0, or one of hv, hv_alt, mismatch not
  *     finite: hv = mismatch = NaN, cpol as above, the flag is set.
+ *   - mismatch > BH_ELLIP_MISMATCH_MAX (the gate): the flag is set, the values stay.
  * flag[b] = 1 if any of model b's K entries set the flag, else 0.
  *
  * Errors leave their message in bh_engine_last_error.  BH_EINVAL launches nothing and writes nothing.
@@ -56,6 +68,8 @@
 #define BH_ENGINE_SWD_ELLIP_H
 
 #include "bh_engine.h"
+
+#define BH_ELLIP_MISMATCH_MAX 1.0e-2 /* the gate above */
 
 #ifdef __cplusplus
 extern "C" {

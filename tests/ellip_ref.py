@@ -31,6 +31,7 @@ def _sincos(x):
 
 TWOPI = 2.0 * 3.141592653589793
 NAN = float("nan")
+MISMATCH_MAX = 1.0e-2   # BH_ELLIP_MISMATCH_MAX: an entry whose mismatch is not at most this raises the flag
 
 
 def f32(x):
@@ -189,8 +190,9 @@ def ratios(e, k):
     return hv, hv_alt, mis, False
 
 
-def ellip(model, T, c, nsteps=2):
-    """One (model, period) of a model that has a root: (hv, mismatch, cpol, flag) -- the header's polish and results."""
+def ellip(model, T, c, nsteps=2, mismatch_max=MISMATCH_MAX):
+    """One (model, period) of a model that has a root: (hv, mismatch, cpol, flag) -- the header's polish, results and gate
+    (mismatch_max = inf: the call before it had the gate)."""
     if not (model[2][0] > 0.0):     # a water layer
         return NAN, NAN, c, 1
     flag = 0
@@ -219,7 +221,7 @@ def ellip(model, T, c, nsteps=2):
             f1 = e[0]
             cpol = c1
     hv, hv_alt, mis, bad = ratios(e, k)
-    if bad:
+    if bad or not (mis <= mismatch_max):   # the gate on the certificate: hv, mis and cpol stay as they are
         flag = 1
     return hv, mis, cpol, flag
 
